@@ -32,10 +32,17 @@ Rank 0 prints ONE JSON line (contract in the task statement).  Besides the contr
                     C-ABI with host pointers (PCIe, launches, synchronisation included), the CPU checker on the same frames beside it
   cpu_baseline      the single-threaded CPU restatement ("port") timed on a bounded sample of the same frames on this box's host
                     cores (rank 0, N=1 only); cpu_baseline_all_cores: one independent sequence per core
+The line carries the headline record in full and each side leg (latency_b1 onwards) by its headline numbers only (value, unit,
+times, parity): the full record had grown past 34 kB on one line, more than line-oriented readers of the result take in.
+`--report FILE` writes the full record, every side leg in detail, as JSON.
+`--dump-outputs DIR` writes what the timed step handed its caller in the last timed step (rank 0) as DIR/<name>.npy, float32 /
+float64, under 64 MB: every frame's pose, counts and aligner result, and the matches, fixed points and correspondences of a fixed,
+seeded sample of frames.  The inputs are seeded, so two builds run with the same arguments can be compared file by file.
 `--mode closed-loop` prints the closed-loop line alone; under torch.distributed.run it shards KITTI sequences 00-07 (BASELINE.json
 config 5) over the ranks, longest first.
 """
 import argparse
+import ctypes as C
 import json
 import os
 import sys
@@ -52,12 +59,14 @@ FP32_VECTOR_TFLOPS = 157.3  # MI355X_MICROARCH.md: peak FP32 (vector)
 FLOP_PER_CORRESPONDENCE = 250.0  # one linearised correspondence of one GN iteration
 GPU_CLOCK_HZ = 2.4e9        # MI355X_MICROARCH.md: peak engine clock (s_memtime totals of one-workgroup kernels here: ~2.3e9)
 N_CU = 256
+DUMP_BUDGET_BYTES = 64 << 20  # --dump-outputs: all files together
+DUMP_SAMPLE_SEED = 20251015   # --dump-outputs: which frames the per-point sample holds
 
 
 def parse():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=10)
+    ap.add_argument("--steps", type=int, default=10, help="timed steps (>= 1)")
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--batch", type=int, default=55296,
                     help="independent sequences (frames per step) per GPU; 55296 = 216 per CU, a multiple of the 1 / 3 / 8 workgroups per CU the "
@@ -88,10 +97,16 @@ def parse():
                     help="worker processes of the all-core CPU figure (one independent sequence per core, SURVEY 8d); "
                          "-1 = min(host cores, 256), 0 = skip")
     ap.add_argument("--cpu-worker", type=int, default=0, help=argparse.SUPPRESS)  # internal: frames to time in a CPU-only child
+    ap.add_argument("--report", metavar="FILE", default=None, help="write the full record (every side leg in detail) as JSON (rank 0)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the outputs of the last timed step as DIR/<name>.npy (rank 0; see the module docstring)")
     ap.add_argument("--dry-run", action="store_true",
                     help="control-flow check without a device (CPU tests of the N > 1 path): ranks rendezvous over gloo, a step is a fixed sleep, "
                          "the line carries value 0 and data 'dry-run'")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
+    return args
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -325,6 +340,9 @@ class FrameWorkload:
         self.pp = ops.pcf_params(cfg)
         self.ap = ops.aligner_params(cfg, stop_at_fixed_point=0 if all_iterations else 1)
         self.ops = ops
+        # the copies above run on the default stream; callers step on a torch stream of their own (non-blocking, not ordered
+        # against it), so the inputs, state0 and X0_all must be complete before the first step reads them
+        torch.cuda.synchronize(self.dev)
 
     def step(self, ev=None, fresh_finders=True):
         # the motion-model guess for every frame of the batch; fresh finder objects (heaviest case: maximum search radius)
@@ -394,6 +412,70 @@ class FrameWorkload:
             gc = snap["corr"][u]
             exact = exact and len(gc) == len(c) and bool(np.array_equal(gc["fixed_idx"], c["fixed_idx"])) and bool(np.array_equal(gc["moving_idx"], c["moving_idx"]))
         return {"pose_rel_frobenius_max": worst, "correspondences_bit_exact": exact, "frames_checked": min(len(poses), len(snap["corr"]))}
+
+    def dump_outputs(self, out_dir, budget=DUMP_BUDGET_BYTES, n_sample=256, seed=DUMP_SAMPLE_SEED):
+        """the arrays a caller of the timed step receives, as left by the last step, -> out_dir/<name>.npy (float32 / float64).
+        Per frame: pose, counts, aligner result.  Per point (matches, fixed points, correspondences): a fixed, seeded sample of
+        n_sample frames, zero past each frame's count.  Per-frame arrays of a batch too large for half the budget are sampled the
+        same way.  -> total bytes written"""
+        import torch
+        from srrg2_proslam_amd import _lib
+        torch.cuda.synchronize()
+        a, B = self.aframes, self.B
+        res = a.result.cpu().numpy()
+        f32, i32 = res.view(np.float32), res.view(np.int32)
+        per_frame = {"pose": a.X.cpu().numpy().reshape(B, 4, 4), "n_correspondences": a.n_corr.cpu().numpy().astype(np.float64),
+                     "n_fixed": a.n_fixed.cpu().numpy().astype(np.float64)}
+        for name, ctype in _lib.AlignResult._fields_:  # prs_align_result field by field (4-byte scalars and arrays)
+            elem = ctype._type_ if issubclass(ctype, C.Array) else ctype
+            off, n = getattr(_lib.AlignResult, name).offset // 4, C.sizeof(ctype) // 4
+            col = f32[:, off: off + n] if elem is C.c_float else i32[:, off: off + n].astype(np.float64)
+            per_frame["align_" + name] = np.ascontiguousarray(col if n > 1 else col[:, 0])
+        if self.stereo:
+            per_frame["n_stereo_matches"] = self.sframes.n_matches.cpu().numpy().astype(np.float64)
+            per_frame["stereo_status"] = self.sframes.status.cpu().numpy().astype(np.float64)
+        rng = np.random.default_rng(seed)
+        arrays = {}
+        if sum(v.nbytes for v in per_frame.values()) > budget // 2:
+            rows = np.sort(rng.choice(B, size=max(1, B * (budget // 2) // sum(v.nbytes for v in per_frame.values())), replace=False))
+            per_frame = {k: v[rows] for k, v in per_frame.items()}
+            arrays["per_frame_rows"] = rows.astype(np.float64)
+        arrays.update(per_frame)
+        stride = self.sframes.stride if self.stereo else a.fixed_stride
+        room = (budget - sum(v.nbytes for v in arrays.values())) // (stride * 14 * 4)  # 14 float32 columns per point at most
+        sample = np.sort(rng.choice(B, size=max(1, min(n_sample, B, room)), replace=False))
+        idx = torch.from_numpy(sample).to(self.dev)
+
+        def rows_of(t, counts, width):  # [S, width, ...] of the sampled frames, zero past each frame's count
+            v = t.index_select(0, idx)[:, :width].cpu().numpy()
+            keep = (np.arange(width)[None, :] < counts[:, None]).reshape(len(counts), width, *([1] * (v.ndim - 2)))
+            return np.where(keep, v, 0).astype(v.dtype)
+
+        def corr(t, counts, width):  # prs_corr rows (fixed_idx, moving_idx, response bits) -> float32 columns
+            raw = rows_of(t, counts, width)
+            return np.stack([raw[..., 0].astype(np.float32), raw[..., 1].astype(np.float32), raw[..., 2].view(np.float32)], axis=-1)
+
+        arrays["sample_frames"] = sample.astype(np.float64)
+        n_corr = a.n_corr.index_select(0, idx).cpu().numpy()
+        counts = [n_corr]
+        if self.stereo:
+            sf = self.sframes
+            n_match, n_fix = sf.n_matches.index_select(0, idx).cpu().numpy(), sf.n_fixed.index_select(0, idx).cpu().numpy()
+            counts += [n_match, n_fix]
+        width = int(min(max(int(max(c.max() for c in counts)), 1), stride))
+        if self.stereo:
+            arrays["sample_stereo_matches"] = corr(sf.matches, n_match, width)
+            arrays["sample_fixed_uvuv"] = rows_of(sf.fixed_uvuv, n_fix, width)
+            arrays["sample_fixed_xyz"] = rows_of(sf.fixed_xyz, n_fix, width)
+        arrays["sample_correspondences"] = corr(a.corr, n_corr, width)
+        total = sum(v.nbytes for v in arrays.values())
+        if total > budget:
+            raise SystemExit("--dump-outputs: %d bytes over the %d byte budget" % (total, budget))
+        os.makedirs(out_dir, exist_ok=True)
+        for name, v in arrays.items():
+            assert v.dtype in (np.float32, np.float64), (name, v.dtype)
+            np.save(os.path.join(out_dir, name + ".npy"), v)
+        return total
 
     def close(self):
         self.ctx.close()
@@ -1160,6 +1242,35 @@ def visible_gpu_count():
     return n
 
 
+SIDE_LEGS = ("latency_b1", "roofline_f1", "roofline_f2", "roofline_f3", "roofline_f4", "a13_alt", "tolerance_exit", "small_batch", "streamed",
+             "from_images", "other_configs", "closed_loop")
+LEG_SUMMARY_KEYS = ("value", "unit", "ms_per_step", "ms_per_launch", "ms_per_frame_median", "achieved", "frac", "error")
+
+
+def leg_summary(leg):
+    """the headline numbers of a side leg for the result line: LEG_SUMMARY_KEYS and parity records, nested records likewise"""
+    if not isinstance(leg, dict):
+        return leg
+    out = {k: v for k, v in leg.items() if k in LEG_SUMMARY_KEYS or k.startswith("parity")}
+    for k, v in leg.items():
+        if isinstance(v, dict) and not k.startswith("parity"):
+            sub = leg_summary(v)
+            if sub:
+                out[k] = sub
+    return out
+
+
+def result_line(record):
+    """the printed line: the headline record in full, every side leg by its summary (--report keeps the full record)"""
+    line = {}
+    for k, v in record.items():
+        if k not in SIDE_LEGS:
+            line[k] = v
+        elif leg_summary(v):
+            line[k] = leg_summary(v)
+    return line
+
+
 def spawn_ranks(args):
     """`python bench.py --gpus N` without a launcher: this process (which makes NO GPU call: the devices are counted from the KFD
     topology in sysfs, visible_gpu_count) starts N fresh children of itself, one per device, with the environment
@@ -1275,6 +1386,7 @@ def main():
         fps_per_rank = sharding.gather_over_ranks(B * args.steps / elapsed_local, red_dev)
         snap = w.snapshot()  # results of the timed configuration
         status_ok, it_exec = w.check(snap)
+        dumped = w.dump_outputs(args.dump_outputs) if rank == 0 and args.dump_outputs else None  # before any further step
         kt = w.kernel_times(max(args.timing_steps, 1))  # per-kernel times: a separate pass, outside the timed region
         # ---- steady state: the same frames again with the finders carried over (radius / threshold schedule adapted) ----
         steady = None
@@ -1415,6 +1527,8 @@ def main():
                         "launcher": "bench.py itself" if os.environ.get("PRS_BENCH_SPAWNED") == "1" else "external (torch.distributed.run)"}
     if steady:
         out["steady_state"] = steady
+    if dumped is not None:
+        out["dump_outputs"] = {"dir": args.dump_outputs, "bytes": dumped}
 
     if rank == 0 and world == 1 and not args.no_cpu_baseline and args.cpu_frames > 0:
         cpu_fps, cpu_s, poses = cpu_baseline(cfg, w.uniq, args.cpu_frames)
@@ -1495,7 +1609,11 @@ def main():
                                                  "finder_retries_per_frame", "track_losses_per_frame", "drift_percent_of_path", "parity_vs_oracle_chain",
                                                  "cpu_baseline") if k in cl}
     if rank == 0:
-        print(json.dumps(out))
+        if args.report:
+            with open(args.report, "w") as f:
+                json.dump(out, f, indent=1)
+                f.write("\n")
+        print(json.dumps(result_line(out)))
     sharding.shutdown()
 
 

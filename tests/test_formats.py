@@ -1,5 +1,6 @@
 """Harness formats: trajectory writers in the reference's KITTI / TUM layouts
 (apps/app_benchmark.cpp:195-262) and the `.conf` reader subset.  CPU only."""
+import json
 import os
 
 import numpy as np
@@ -7,7 +8,9 @@ import pytest
 
 from srrg2_proslam_amd import configs, formats
 
-REFERENCE_CONFS = "/root/reference/configurations"
+# the hot-path values formats.hot_path_params reads from the reference's shipped configurations/*.conf
+# (stored by tools/make_ref_fixtures.py; lists are the reader's tuples)
+CONF_HOT_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "ref_conf_hot_path.json")
 
 
 def _pose(rng):
@@ -146,11 +149,12 @@ def test_conf_reader_records_pointers_and_comments():
         formats.parse_conf('{ "no_class_name" : 1 }')
 
 
-@pytest.mark.skipif(not os.path.isdir(REFERENCE_CONFS), reason="the reference tree is only present in the build container")
 @pytest.mark.parametrize("name", ["kitti", "euroc", "icl", "tum"])
 def test_shipped_configurations_agree_with_the_carried_parameter_sets(name):
-    """`configs.py` carries the hot-path values of the shipped `.conf` files by hand; this reads the files themselves."""
-    hp = formats.hot_path_params(formats.read_conf(os.path.join(REFERENCE_CONFS, name + ".conf")))
+    """`configs.py` carries the hot-path values of the shipped `.conf` files by hand; this checks them against what the
+    `.conf` reader extracted from the files themselves (tests/golden/ref_conf_hot_path.json)."""
+    with open(CONF_HOT_PATH) as f:
+        hp = {group: {key: tuple(v) if isinstance(v, list) else v for key, v in values.items()} for group, values in json.load(f)[name].items()}
     carried = configs.get(name)
     checked = 0
     for group, values in hp.items():

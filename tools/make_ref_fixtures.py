@@ -1,10 +1,13 @@
 #!/usr/bin/env python3
 """Turns the DATA files the reference's own tests read (/root/reference/test_data, loaded by
-srrg2_proslam/tests/fixtures.hpp:555-1152) into the committed fixtures tests/golden/ref_*.npz.
+srrg2_proslam/tests/fixtures.hpp:555-1152) into the committed fixtures tests/golden/ref_*.npz, and the
+hot-path parameter values of its shipped configurations (configurations/*.conf, read with
+srrg2_proslam_amd.formats) into tests/golden/ref_conf_hot_path.json.
 
 Run in the build container only (the reference tree does not exist on the GPU box); the tests read the
 .npz files, never /root/reference.  What is stored is data: decoded pixels, depth, ground-truth poses and
-the sparse disparity ground truth -- no source text of the reference.
+the sparse disparity ground truth, and the parameter values the `.conf` reader extracts -- no source text
+of the reference.
 
     python tools/make_ref_fixtures.py [/root/reference]
 
@@ -56,6 +59,17 @@ def scene_flow_gt(path):
     return np.loadtxt(path).astype(np.float32)
 
 
+def conf_hot_path(names=("kitti", "euroc", "icl", "tum")):
+    """{config: {group: {key: value}}} as formats.hot_path_params reads it from the shipped .conf files"""
+    import json
+    sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+    from srrg2_proslam_amd import formats
+    out = {n: formats.hot_path_params(formats.read_conf(os.path.join(REF, "configurations", n + ".conf"))) for n in names}
+    with open(os.path.join(OUT, "ref_conf_hot_path.json"), "w") as f:
+        json.dump(out, f, indent=1, sort_keys=True)
+        f.write("\n")
+
+
 def main():
     k = os.path.join(DATA, "kitti")
     np.savez_compressed(
@@ -81,6 +95,7 @@ def main():
                         left=gray_u8(os.path.join(s, "image_left.png")), right=gray_u8(os.path.join(s, "image_right.png")),
                         gt_threshold_10=scene_flow_gt(os.path.join(s, "gt_stereo_matching_threshold-10.txt")),
                         gt_threshold_100=scene_flow_gt(os.path.join(s, "gt_stereo_matching_threshold-100.txt")))
+    conf_hot_path()
     for f in sorted(os.listdir(OUT)):
         if f.startswith("ref_"):
             print(f, os.path.getsize(os.path.join(OUT, f)) // 1024, "KiB")
