@@ -1831,7 +1831,7 @@ __global__ __launch_bounds__(T, SPLIT ? 6 : 1) void align_kernel(const AlignArgs
     gstate->has_converged        = sh.converged;
     gstate->config_changed       = sh.config_changed;
     gstate->num_recomputes       = sh.num_recomputes;
-    gstate->reserved             = sh.no_prune;
+    gstate->reserved             = (gstate->reserved & ~1) | sh.no_prune;  // (bit 0 only: the other bits are not the library's)
     g.b.n_corr[frame]            = sh.n_corr;
     gres->chi_inliers            = sh.chi_in;
     gres->chi_total              = sh.chi_tot;
