@@ -106,9 +106,10 @@ PRS_API int prs_version(void);
  * prs_aligner_params).  PRS_ABI_VERSION is what this header describes, prs_version() what the loaded library was built from; a
  * client checks that they agree once (prs_abi_check: also the sizes of the structs it will pass, as the client's compiler laid
  * them out) instead of finding out through a library that reads past a shorter struct (101 -> 102: step_norm_exit at the end of
- * prs_aligner_params; 102 also adds the entry points prs_abi_check and prs_context_set_bruteforce_dense_phase).  Callers memset() parameter structs before
+ * prs_aligner_params; 102 also adds the entry points prs_abi_check and prs_context_set_bruteforce_dense_phase; 103 adds the
+ * selective extractor: prs_selective_extractor_params, prs_selective_extract_batch and their two entry points, no existing struct changed).  Callers memset() parameter structs before
  * filling them, so that fields they do not know select the shipped defaults (all zero). */
-#define PRS_ABI_VERSION 102
+#define PRS_ABI_VERSION 103
 PRS_API int prs_abi_check(int32_t header_version, uint64_t sizeof_stereo_params, uint64_t sizeof_pcf_params, uint64_t sizeof_aligner_params,
                           uint64_t sizeof_align_batch);
 #define PRS_ABI_CHECK() prs_abi_check(PRS_ABI_VERSION, sizeof(prs_stereo_params), sizeof(prs_pcf_params), sizeof(prs_aligner_params), sizeof(prs_align_batch))
@@ -840,6 +841,84 @@ PRS_API int prs_extract_features(prs_context* ctx,
                                  uint8_t* descriptors,
                                  int32_t capacity,
                                  int32_t* n_features);
+
+/* ================================================================================================
+ * Selective intensity feature extraction
+ * replaces IntensityFeatureExtractorSelective_::computeKeypoints + compute (sensor_processing/feature_extractors/
+ * intensity_feature_extractor_selective.cpp:45-203, intensity_feature_extractor_base.cpp:56-85): in TRACKING mode (the image
+ * has projections) keypoints are detected only inside rectangles around the projections of tracked landmarks, and optionally
+ * seeded in the rest of the image (appended behind them); in SEEDING mode (no projections) in the whole image or inside an
+ * external mask.  Both use cv::GFTTDetector, restated from OpenCV's published algorithm (goodFeaturesToTrack, blockSize 3,
+ * 3x3 Sobel, no Harris, qualityLevel 0.01, maxCorners = target_number_of_keypoints, minDistance = target_bin_width_pixels):
+ *  - minimum eigenvalue of the 3x3 box-summed gradient covariance (reflect-101 borders, float), maximum over the detection
+ *    mask only, values not above 0.01 * maximum set to 0, candidates = non-zero 3x3 local maxima inside the mask and 1 px
+ *    inside the image, sorted by response, ties by pixel index descending (OpenCV >= 3.4's greaterThanPtr; the reference's
+ *    pinned counts do not decide ties: this is the build's choice), accepted greedily when no accepted corner lies at a
+ *    squared distance below minDistance^2, at most maxCorners;
+ *  - descriptors as prs_extract_features_batch (cv::ORB::compute, unrotated pattern, 31-px border filter, order kept).
+ *    "BRIEF-256" is cv::ORB as well in the reference's OpenCV >= 3 build without contrib (base.cpp:153-158).
+ * Projection rectangles (selective.cpp:62-150): r = detection_radius + 10, (row, col) = round half away from zero of (v, u);
+ * rows [max(row - r, 0), + min(2r, rows - that)); columns likewise, or [0, col) with enable_full_distance_to_left only,
+ * [col, cols) with _right only, all columns with both.  The seeding run after tracking uses the complement of their union,
+ * its own maximum and its own maxCorners budget.  Projections must lie inside the image (the reference asserts it):
+ * PRS_ERR_RANGE otherwise.
+ * Status per image: PRS_WARN_NO_MATCHES (no keypoints, selective.cpp:145-150,184-189), PRS_ERR_CAPACITY (more GFTT
+ * candidates of one run than max_candidates, or more features than `stride`; no features are returned).
+ * ============================================================================================== */
+enum { PRS_DETECTOR_GFTT = 0, PRS_DETECTOR_FAST = 1 /* not built: PRS_ERR_UNSUPPORTED */ };
+enum { PRS_DESCRIPTOR_ORB_256 = 0, PRS_DESCRIPTOR_BRIEF_256 = 1 };
+
+typedef struct {
+  int32_t detector_type;                 /* PRS_DETECTOR_* (intensity_feature_extractor_base.h param detector_type) */
+  int32_t descriptor_type;               /* PRS_DESCRIPTOR_* (param descriptor_type) */
+  int32_t target_number_of_keypoints;    /* GFTT maxCorners, per run; in [1, 8192] */
+  int32_t target_bin_width_pixels;       /* GFTT minDistance; 0 = no distance test */
+  int32_t enable_full_distance_to_left;  /* intensity_feature_extractor_selective.h:17-28 (default 0) */
+  int32_t enable_full_distance_to_right; /* (default 0) */
+  int32_t enable_seeding_when_tracking;  /* :29-34 (default 1) */
+  int32_t max_candidates;                /* GFTT candidates per run the selection sort holds: 0 = 8192, at most 16384 */
+} prs_selective_extractor_params;
+
+typedef struct {
+  int32_t batch;
+  int32_t rows, cols;           /* image size, each in [8, 4096] */
+  int32_t pitch;                /* bytes between image rows (>= cols) */
+  const uint8_t* images;        /* [batch][rows][pitch] 8-bit intensity */
+  int32_t projection_stride;    /* row stride of projections (0 when projections is NULL) */
+  const prs_kp2* projections;   /* [batch][projection_stride] (u, v) or NULL = every image seeds */
+  const int32_t* n_projections; /* [batch] projections of image b (0 = seeding mode), or NULL with projections */
+  const int32_t* detection_radius; /* [batch] radius of image b's projections (setProjections), or NULL = 0 */
+  const uint8_t* seeding_mask;  /* [batch][rows][pitch], non-zero = detect, used in seeding mode only (setKeypointDetectionMask);
+                                   NULL = none */
+  int32_t stride;               /* feature capacity per image = row stride of the outputs */
+  prs_kp2* keypoints;           /* out [batch][stride] (u, v) = (column, row) */
+  float* intensity;             /* out [batch][stride] or NULL */
+  uint8_t* descriptors;         /* out [batch][stride][32] */
+  int32_t* n_features;          /* out [batch] */
+  int32_t* status;              /* out [batch] */
+} prs_selective_extract_batch;
+
+/* device pointers; enqueues on the context's stream (graph-capturable, like prs_extract_features_batch) */
+PRS_API int prs_extract_features_selective_batch(prs_context* ctx, const prs_selective_extractor_params* params,
+                                                 const prs_selective_extract_batch* batch);
+
+/* host pointers, one image: uploads, runs, downloads, synchronises (like prs_extract_features).  projections [n_projections][2]
+ * (u, v) or NULL; seeding_mask rows x cols (pitch `pitch`) or NULL.  Returns the image's status; on an error nothing is returned. */
+PRS_API int prs_extract_features_selective(prs_context* ctx,
+                                           const prs_selective_extractor_params* params,
+                                           const uint8_t* image,
+                                           int32_t rows,
+                                           int32_t cols,
+                                           int32_t pitch,
+                                           const float* projections,
+                                           int32_t n_projections,
+                                           int32_t detection_radius,
+                                           const uint8_t* seeding_mask,
+                                           float* keypoints,
+                                           float* intensity,
+                                           uint8_t* descriptors,
+                                           int32_t capacity,
+                                           int32_t* n_features);
 
 #ifdef __cplusplus
 }

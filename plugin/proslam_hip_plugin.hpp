@@ -14,6 +14,8 @@
 //   SceneClipperProjective3D (mapping/scene_clipper_projective_3d.h) -> SceneClipperProjective3DHIP
 //   MultiAligner3DQR + AlignerSliceProcessorProjective*            -> AlignerProjectiveHIP
 //     (registration/aligner_slice_processor_projective.h:14-192, tests/test_aligners.cpp:1237-1253)
+//   IntensityFeatureExtractorSelective{2D,3D}                      -> IntensityFeatureExtractorSelective{2D,3D}HIP
+//     (sensor_processing/feature_extractors/intensity_feature_extractor_selective.h)
 //
 // When the srrg2 headers are available the same bodies become real plugin subclasses: see
 // INTEGRATION.md for the BOSS_REGISTER_CLASS adapters.  Points are AoS like the reference's
@@ -720,6 +722,122 @@ protected:
   ContextPtr _ctx;
   PointCloudType* _features = nullptr;
 };
+
+// IntensityFeatureExtractorSelective_ (sensor_processing/feature_extractors/intensity_feature_extractor_selective.{h,cpp}, base class
+// intensity_feature_extractor_base.h): same PARAM names and defaults, setFeatures() / setProjections(points, radius) /
+// setKeypointDetectionMask() / compute(image).  Projections are consumed by one compute() (selective.cpp:175-176), the external
+// mask by the next one that does not return early.  Only the GFTT detector is built (detector_type "FAST", the reference's default,
+// throws); target_bin_width_pixels must be a whole number of pixels.  The 3D cloud carries (u, v, 0).
+template <int Dim_>
+class IntensityFeatureExtractorSelectiveHIP_ {
+public:
+  using PointCloudType = PointIntensityDescriptorVectorCloud<Dim_>;
+  explicit IntensityFeatureExtractorSelectiveHIP_(ContextPtr ctx) : _ctx(std::move(ctx)) {}
+  Property_<std::string> param_descriptor_type{"ORB-256"};  // intensity_feature_extractor_base.h:24-28
+  Property_<std::string> param_detector_type{"FAST"};       // :30-34
+  PropertyFloat param_target_bin_width_pixels{10.f};        // :42-46
+  Property_<int> param_target_number_of_keypoints{500};     // :54-58
+  PropertyBool param_enable_full_distance_to_left{false};   // intensity_feature_extractor_selective.h:17-21
+  PropertyBool param_enable_full_distance_to_right{false};  // :23-27
+  PropertyBool param_enable_seeding_when_tracking{true};    // :29-33
+  void setFeatures(PointCloudType* features_) { _features = features_; }
+  void setProjections(const PointCloudType* projections_, const size_t& projection_detection_radius_) {
+    _projections = projections_;
+    _radius      = projection_detection_radius_;
+  }
+  // mask: rows x cols bytes (pitch `pitch`), non-zero = detect; seeding mode only.  The caller keeps it alive until compute().
+  void setKeypointDetectionMask(const uint8_t* mask, int pitch) {
+    _mask       = mask;
+    _mask_pitch = pitch;
+  }
+  void compute(const uint8_t* image, int rows, int cols, int pitch) {
+    if (!_features) {
+      std::cerr << "IntensityFeatureExtractor::compute|WARNING: target feature buffer not set, ignoring call" << std::endl;
+      return;
+    }
+    if (!image || rows <= 0 || cols <= 0) throw std::runtime_error("IntensityFeatureExtractor::compute|ERROR: image not set");
+    prs_selective_extractor_params p;
+    std::memset(&p, 0, sizeof(p));
+    const std::string& det  = param_detector_type.value();
+    const std::string& desc = param_descriptor_type.value();
+    if (det == "GFTT") {
+      p.detector_type = PRS_DETECTOR_GFTT;
+    } else {
+      throw std::runtime_error("IntensityFeatureExtractorSelectiveHIP::compute|ERROR: detector type not built: " + det);
+    }
+    if (desc == "ORB-256") {
+      p.descriptor_type = PRS_DESCRIPTOR_ORB_256;
+    } else if (desc == "BRIEF-256") {
+      p.descriptor_type = PRS_DESCRIPTOR_BRIEF_256;
+    } else {
+      throw std::runtime_error("IntensityFeatureExtractorSelectiveHIP::compute|ERROR: descriptor type not built: " + desc);
+    }
+    const float width = param_target_bin_width_pixels.value();
+    if (width < 0.f || width != std::floor(width)) {
+      throw std::runtime_error("IntensityFeatureExtractorSelectiveHIP::compute|ERROR: target_bin_width_pixels must be a whole number");
+    }
+    p.target_number_of_keypoints    = param_target_number_of_keypoints.value();
+    p.target_bin_width_pixels       = (int32_t) width;
+    p.enable_full_distance_to_left  = param_enable_full_distance_to_left.value() ? 1 : 0;
+    p.enable_full_distance_to_right = param_enable_full_distance_to_right.value() ? 1 : 0;
+    p.enable_seeding_when_tracking  = param_enable_seeding_when_tracking.value() ? 1 : 0;
+    p.max_candidates                = 16384;
+    const bool tracking = _projections && !_projections->empty();
+    std::vector<float> proj;
+    if (tracking) {
+      proj.reserve(2 * _projections->size());
+      for (const auto& q : *_projections) {
+        proj.push_back(q.coords[0]);
+        proj.push_back(q.coords[1]);
+      }
+    }
+    // the mask has the image's pitch on the device: repack it when the caller's differs
+    std::vector<uint8_t> mask;
+    const uint8_t* m = nullptr;
+    if (!tracking && _mask) {
+      mask.resize((size_t) rows * pitch);
+      for (int r = 0; r < rows; ++r) std::memcpy(&mask[(size_t) r * pitch], _mask + (size_t) r * _mask_pitch, (size_t) cols);
+      m = mask.data();
+    }
+    const int32_t capacity = 2 * 8192;
+    std::vector<float> kp(2 * (size_t) capacity), inten((size_t) capacity);
+    std::vector<uint8_t> d(PRS_DESC_BYTES * (size_t) capacity);
+    int32_t n    = 0;
+    const int rc = prs_extract_features_selective(_ctx->get(), &p, image, rows, cols, pitch, tracking ? proj.data() : nullptr,
+                                                  tracking ? (int32_t) _projections->size() : 0, (int32_t) _radius, m, kp.data(),
+                                                  inten.data(), d.data(), capacity, &n);
+    if (rc < 0) throw std::runtime_error(std::string("IntensityFeatureExtractorSelectiveHIP::compute|ERROR: ") + prs_last_error(_ctx->get()));
+    _features->clear();
+    _features->reserve((size_t) n);
+    for (int32_t i = 0; i < n; ++i) {
+      PointIntensityDescriptor_<Dim_> q;
+      std::memset(q.coords, 0, sizeof(q.coords));
+      q.coords[0]       = kp[2 * (size_t) i];
+      q.coords[1]       = kp[2 * (size_t) i + 1];
+      q.intensity_value = inten[(size_t) i];
+      std::memcpy(q.descriptor_row, &d[PRS_DESC_BYTES * (size_t) i], PRS_DESC_BYTES);
+      _features->push_back(q);
+    }
+    if (tracking) {
+      if (n == 0) std::cerr << "IntensityFeatureExtractorSelective_::computeKeypoints|WARNING: no keypoints detected for projected regions: " << _projections->size();
+      _projections = nullptr;  // selective.cpp:175-176: back to seeding for the next call
+    } else if (n == 0) {
+      std::cerr << "IntensityFeatureExtractorSelective_::computeKeypoints|WARNING: unable to seed keypoints" << std::endl;
+      return;  // (the reference returns before clearing the mask here: selective.cpp:193-199)
+    }
+    _mask = nullptr;
+  }
+
+protected:
+  ContextPtr _ctx;
+  PointCloudType* _features          = nullptr;
+  const PointCloudType* _projections = nullptr;
+  size_t _radius                     = 0;
+  const uint8_t* _mask               = nullptr;
+  int _mask_pitch                    = 0;
+};
+using IntensityFeatureExtractorSelective2DHIP = IntensityFeatureExtractorSelectiveHIP_<2>;
+using IntensityFeatureExtractorSelective3DHIP = IntensityFeatureExtractorSelectiveHIP_<3>;
 
 // MergerRigidStereoTriangulation with LandmarkEstimatorWeightedMean4D3D (mapping/mergers/merger_rigid_stereo_triangulation.h,
 // merger_projective.h, landmarks/landmark_estimator_weighted_mean.h): same setters and PARAM names; the scene is mirrored into a

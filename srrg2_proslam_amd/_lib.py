@@ -9,7 +9,7 @@ import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libproslam_hip.so")
-ABI_VERSION = 102  # PRS_ABI_VERSION of include/proslam_hip.h
+ABI_VERSION = 103  # PRS_ABI_VERSION of include/proslam_hip.h
 
 # status codes (include/proslam_hip.h)
 OK = 0
@@ -263,6 +263,22 @@ class ExtractBatch(C.Structure):
                 ("n_features", C.c_void_p), ("status", C.c_void_p)]
 
 
+class SelectiveExtractorParams(C.Structure):
+    """prs_selective_extractor_params"""
+    _fields_ = [("detector_type", C.c_int32), ("descriptor_type", C.c_int32), ("target_number_of_keypoints", C.c_int32),
+                ("target_bin_width_pixels", C.c_int32), ("enable_full_distance_to_left", C.c_int32),
+                ("enable_full_distance_to_right", C.c_int32), ("enable_seeding_when_tracking", C.c_int32),
+                ("max_candidates", C.c_int32)]
+
+
+class SelectiveExtractBatch(C.Structure):
+    """prs_selective_extract_batch (device pointers)"""
+    _fields_ = [("batch", C.c_int32), ("rows", C.c_int32), ("cols", C.c_int32), ("pitch", C.c_int32), ("images", C.c_void_p),
+                ("projection_stride", C.c_int32), ("projections", C.c_void_p), ("n_projections", C.c_void_p),
+                ("detection_radius", C.c_void_p), ("seeding_mask", C.c_void_p), ("stride", C.c_int32), ("keypoints", C.c_void_p),
+                ("intensity", C.c_void_p), ("descriptors", C.c_void_p), ("n_features", C.c_void_p), ("status", C.c_void_p)]
+
+
 MODE_ALIGN, MODE_FINDER, MODE_LINEARIZE = 0, 1, 2
 
 # every symbol include/proslam_hip.h declares: (restype, argtypes)
@@ -313,6 +329,9 @@ SYMBOLS = {
     "prs_extract_features_batch": (C.c_int, [_vp, C.POINTER(ExtractorParams), C.POINTER(ExtractBatch)]),
     "prs_selection_order": (C.c_int, [_vp, _vp, C.c_int32, _vp]),
     "prs_extract_features": (C.c_int, [_vp, C.POINTER(ExtractorParams), _vp, C.c_int32, C.c_int32, C.c_int32, _vp, _vp, _vp, C.c_int32, _i32p]),
+    "prs_extract_features_selective_batch": (C.c_int, [_vp, C.POINTER(SelectiveExtractorParams), C.POINTER(SelectiveExtractBatch)]),
+    "prs_extract_features_selective": (C.c_int, [_vp, C.POINTER(SelectiveExtractorParams), _vp, C.c_int32, C.c_int32, C.c_int32, _vp,
+                                                 C.c_int32, C.c_int32, _vp, _vp, _vp, _vp, C.c_int32, _i32p]),
     "prs_pose_compose_batch": (C.c_int, [_vp, C.c_int32, _vp, _vp, _vp]),
     "prs_motion_predict_batch": (C.c_int, [_vp, C.c_int32, _vp, _vp, _vp]),
     "prs_merge_batch_run": (C.c_int, [_vp, C.POINTER(MergerParams), C.POINTER(MergeBatch)]),

@@ -148,10 +148,69 @@ __device__ __attribute__((noinline)) void score_overflowed(const uint8_t* tile8,
   }
 }
 
+// ---- 7x7 Gaussian of one 64x64 tile on the matrix cores (round 5; rounds 2-4: packed 16-bit / v_dot vector passes through LDS, a fifth of the
+// kernel's vector instructions -- and the kernel is bound by exactly those).  Separable, fixed point, both passes as
+// v_mfma_i32_16x16x32_i8 against a banded matrix of the taps; integer products and sums: exact.  Wave w owns the tile's
+// columns 16 w .. 16 w + 15 and needs nobody else's data, so nothing goes through LDS and there is no barrier:
+//   rows:    H[80 x 16] = P[80 x 32] * Bh[32 x 16], five MFMAs; P = the tile's rows -3 .. 76 (beyond the halo: whatever
+//            the clamped row holds, those sums feed no output), columns 16 w - 4 .. 16 w + 27, as signed bytes p - 128;
+//            the accumulator starts at 128 * 257 (the taps sum to 257), so H is the true sum 0 .. 65535.  An MFMA result has
+//            its column on the lane and four consecutive rows in its registers = the A operand of a product that sums over rows;
+//   columns: out^T[16 x 16] = H^T[16 x 32] * Bv[32 x 16] per 16 output rows, H split into its two bytes (each as b - 128, two
+//            MFMAs, recombined with a shift); the K order inside the operand is the one the first result arrives in (rows
+//            4 g + r of two row blocks), Bv is built for that order.  Result: four consecutive pixels of one row per lane.
+// Lane maps checked with exact integer data: tools/probes/mfma_i8_probe.hip.
+template <bool BORDER>
+__device__ __forceinline__ void blur_tile(const FeatureArgs& a, const uint8_t* tile8, const int img, const int x0, const int y0, const int rows, const int wave,
+                                        const int lane) {
+  typedef int v4i __attribute__((ext_vector_type(4)));
+  constexpr unsigned long long kTaps = 0x0012223137312212ull;  // bytes 0 .. 6 = 18 34 49 55 49 34 18
+  auto taps_from = [](const int d) -> unsigned long long {       // byte j = tap j + d (0 outside 0 .. 6)
+    return d >= 0 ? (d < 8 ? kTaps >> (8 * d) : 0ull) : (d > -8 ? kTaps << (-8 * d) : 0ull);
+  };
+  const int li = lane & 15, g = lane >> 4;
+  // Bh[k][n]: input column k (tile byte 16 w + k) feeds output column n (tile byte 16 w + 4 + n) with tap k - n - 1
+  const long bh = (long) taps_from(8 * g - li - 1);
+  // Bv[k][q]: byte t < 4 of lane group g is H row 4 g + t of the first row block, t >= 4 row 16 + 4 g + t - 4 (second block);
+  // H row h feeds output row q with tap h - q
+  const long bv = (long) ((taps_from(4 * g - li) & 0xffffffffull) | (taps_from(16 + 4 * g - li) << 32));
+  const uint8_t* strip = tile8 + 16 * wave + 8 * min(g, 2);  // (the fourth lane group's columns carry no tap: any bytes will do)
+  uint32_t hlo[5], hhi[5];
+#pragma unroll
+  for (int b = 0; b < 5; ++b) {
+    const int ty = min(16 * b + li + 1, kTileRows - 1);
+    const uint64_t p = *reinterpret_cast<const uint64_t*>(strip + ty * kTilePitch);  // (8-byte aligned: the pitch is 72)
+    const v4i h = __builtin_amdgcn_mfma_i32_16x16x32_i8((long) (p ^ 0x8080808080808080ull), bh, v4i{32896, 32896, 32896, 32896}, 0, 0, 0);
+    const uint32_t p01 = __builtin_amdgcn_perm((uint32_t) h[1], (uint32_t) h[0], 0x05010400u);  // h0.b0 h1.b0 h0.b1 h1.b1
+    const uint32_t p23 = __builtin_amdgcn_perm((uint32_t) h[3], (uint32_t) h[2], 0x05010400u);
+    hlo[b] = __builtin_amdgcn_perm(p23, p01, 0x05040100u) ^ 0x80808080u;
+    hhi[b] = __builtin_amdgcn_perm(p23, p01, 0x07060302u) ^ 0x80808080u;
+  }
+  uint8_t* __restrict__ blur = a.blur + (size_t) img * a.blur_stride;
+#pragma unroll
+  for (int j = 0; j < kTileH / 16; ++j) {
+    const long alo = (long) (((uint64_t) hlo[j + 1] << 32) | hlo[j]), ahi = (long) (((uint64_t) hhi[j + 1] << 32) | hhi[j]);
+    // sum g H = sum g (lo - 128) + 256 sum g (hi - 128) + 257 * 128 * 257; + 2^15 for the rounding
+    const v4i slo = __builtin_amdgcn_mfma_i32_16x16x32_i8(alo, bv, v4i{65664, 65664, 65664, 65664}, 0, 0, 0);
+    const v4i shi = __builtin_amdgcn_mfma_i32_16x16x32_i8(ahi, bv, v4i{32896, 32896, 32896, 32896}, 0, 0, 0);
+    uint32_t v[4];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      v[r] = min((uint32_t) slo[r] + ((uint32_t) shi[r] << 8), 0x00ffffffu);  // (sum + 2^15) >> 16, saturated (the taps sum to 257 / 256)
+    }
+    const uint32_t out = __builtin_amdgcn_perm(v[1], v[0], 0x0c0c0602u) | (__builtin_amdgcn_perm(v[3], v[2], 0x0c0c0602u) << 16);
+    const int gy = y0 + 16 * j + li, gx = x0 + 16 * wave + 4 * g;
+    if (!BORDER || (gy < rows && gx < 16 * a.blur_ncb)) {  // (the padding columns of the last block take whatever the word holds)
+      *reinterpret_cast<uint32_t*>(blur + blur_offset(gy, gx, a.blur_ncb)) = out;
+    }
+  }
+}
+
 // image tile (+ 4-px halo) in LDS -> compass test on four pixels per lane -> survivors (dense lists, one per wave) ->
 // arc minima on dense lanes -> responses of the tile and its 1-px ring -> non-maximum suppression, four pixels per
-// lane; the separable 7x7 Gaussian of the tile on the side (packed 16-bit horizontal pass, 32-bit vertical pass).
-template <bool BORDER>
+// lane; the separable 7x7 Gaussian of the tile on the side (blur_tile).  DETECT = false: the Gaussian alone (blur_kernel: the
+// smoothed image the descriptors of keypoints from another detector sample); the response tile and the lists are not touched.
+template <bool BORDER, bool DETECT = true>
 __device__ __forceinline__ void fast_blur_tile(const FeatureArgs& a, uint32_t* tile32, uint32_t* resp32, uint16_t (*list)[kListCap],
                                               uint16_t (*second)[kSecondCap], int* list_n) {
   const int rows = a.b.rows, cols = a.b.cols, pitch = a.b.pitch;
@@ -207,12 +266,18 @@ __device__ __forceinline__ void fast_blur_tile(const FeatureArgs& a, uint32_t* t
     for (int u = 0; u < kLoads; ++u) {
       if (tid < kLoaders && ty0 + kLoadRows * u < kTileRows) {
         tile32[tid + kLoaders * u] = w[u];
-        resp32[tid + kLoaders * u] = 0;
+        if (DETECT) {
+          resp32[tid + kLoaders * u] = 0;
+        }
       }
     }
   }
   __syncthreads();
   stamp(1);
+  if (!DETECT) {
+    blur_tile<BORDER>(a, tile8, img, x0, y0, rows, wave, lane);
+    return;
+  }
   const int t       = a.p.detector_threshold;  // 1 .. 254 (checked by the host)
   const uint32_t T2 = (uint32_t) t * 0x00010001u;
   const int w1 = tid & 15, r0 = tid >> 4;
@@ -363,61 +428,7 @@ __device__ __forceinline__ void fast_blur_tile(const FeatureArgs& a, uint32_t* t
       }
     }
   }
-  // ---- 7x7 Gaussian on the matrix cores (round 5; rounds 2-4: packed 16-bit / v_dot vector passes through LDS, a fifth of the
-  // kernel's vector instructions -- and the kernel is bound by exactly those).  Separable, fixed point, both passes as
-  // v_mfma_i32_16x16x32_i8 against a banded matrix of the taps; integer products and sums: exact.  Wave w owns the tile's
-  // columns 16 w .. 16 w + 15 and needs nobody else's data, so nothing goes through LDS and there is no barrier:
-  //   rows:    H[80 x 16] = P[80 x 32] * Bh[32 x 16], five MFMAs; P = the tile's rows -3 .. 76 (beyond the halo: whatever
-  //            the clamped row holds, those sums feed no output), columns 16 w - 4 .. 16 w + 27, as signed bytes p - 128;
-  //            the accumulator starts at 128 * 257 (the taps sum to 257), so H is the true sum 0 .. 65535.  An MFMA result has
-  //            its column on the lane and four consecutive rows in its registers = the A operand of a product that sums over rows;
-  //   columns: out^T[16 x 16] = H^T[16 x 32] * Bv[32 x 16] per 16 output rows, H split into its two bytes (each as b - 128, two
-  //            MFMAs, recombined with a shift); the K order inside the operand is the one the first result arrives in (rows
-  //            4 g + r of two row blocks), Bv is built for that order.  Result: four consecutive pixels of one row per lane.
-  // Lane maps checked with exact integer data: tools/probes/mfma_i8_probe.hip.
-  {
-    typedef int v4i __attribute__((ext_vector_type(4)));
-    constexpr unsigned long long kTaps = 0x0012223137312212ull;  // bytes 0 .. 6 = 18 34 49 55 49 34 18
-    auto taps_from = [](const int d) -> unsigned long long {       // byte j = tap j + d (0 outside 0 .. 6)
-      return d >= 0 ? (d < 8 ? kTaps >> (8 * d) : 0ull) : (d > -8 ? kTaps << (-8 * d) : 0ull);
-    };
-    const int li = lane & 15, g = lane >> 4;
-    // Bh[k][n]: input column k (tile byte 16 w + k) feeds output column n (tile byte 16 w + 4 + n) with tap k - n - 1
-    const long bh = (long) taps_from(8 * g - li - 1);
-    // Bv[k][q]: byte t < 4 of lane group g is H row 4 g + t of the first row block, t >= 4 row 16 + 4 g + t - 4 (second block);
-    // H row h feeds output row q with tap h - q
-    const long bv = (long) ((taps_from(4 * g - li) & 0xffffffffull) | (taps_from(16 + 4 * g - li) << 32));
-    const uint8_t* strip = tile8 + 16 * wave + 8 * min(g, 2);  // (the fourth lane group's columns carry no tap: any bytes will do)
-    uint32_t hlo[5], hhi[5];
-#pragma unroll
-    for (int b = 0; b < 5; ++b) {
-      const int ty = min(16 * b + li + 1, kTileRows - 1);
-      const uint64_t p = *reinterpret_cast<const uint64_t*>(strip + ty * kTilePitch);  // (8-byte aligned: the pitch is 72)
-      const v4i h = __builtin_amdgcn_mfma_i32_16x16x32_i8((long) (p ^ 0x8080808080808080ull), bh, v4i{32896, 32896, 32896, 32896}, 0, 0, 0);
-      const uint32_t p01 = __builtin_amdgcn_perm((uint32_t) h[1], (uint32_t) h[0], 0x05010400u);  // h0.b0 h1.b0 h0.b1 h1.b1
-      const uint32_t p23 = __builtin_amdgcn_perm((uint32_t) h[3], (uint32_t) h[2], 0x05010400u);
-      hlo[b] = __builtin_amdgcn_perm(p23, p01, 0x05040100u) ^ 0x80808080u;
-      hhi[b] = __builtin_amdgcn_perm(p23, p01, 0x07060302u) ^ 0x80808080u;
-    }
-    uint8_t* __restrict__ blur = a.blur + (size_t) img * a.blur_stride;
-#pragma unroll
-    for (int j = 0; j < kTileH / 16; ++j) {
-      const long alo = (long) (((uint64_t) hlo[j + 1] << 32) | hlo[j]), ahi = (long) (((uint64_t) hhi[j + 1] << 32) | hhi[j]);
-      // sum g H = sum g (lo - 128) + 256 sum g (hi - 128) + 257 * 128 * 257; + 2^15 for the rounding
-      const v4i slo = __builtin_amdgcn_mfma_i32_16x16x32_i8(alo, bv, v4i{65664, 65664, 65664, 65664}, 0, 0, 0);
-      const v4i shi = __builtin_amdgcn_mfma_i32_16x16x32_i8(ahi, bv, v4i{32896, 32896, 32896, 32896}, 0, 0, 0);
-      uint32_t v[4];
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        v[r] = min((uint32_t) slo[r] + ((uint32_t) shi[r] << 8), 0x00ffffffu);  // (sum + 2^15) >> 16, saturated (the taps sum to 257 / 256)
-      }
-      const uint32_t out = __builtin_amdgcn_perm(v[1], v[0], 0x0c0c0602u) | (__builtin_amdgcn_perm(v[3], v[2], 0x0c0c0602u) << 16);
-      const int gy = y0 + 16 * j + li, gx = x0 + 16 * wave + 4 * g;
-      if (!BORDER || (gy < rows && gx < 16 * a.blur_ncb)) {  // (the padding columns of the last block take whatever the word holds)
-        *reinterpret_cast<uint32_t*>(blur + blur_offset(gy, gx, a.blur_ncb)) = out;
-      }
-    }
-  }
+  blur_tile<BORDER>(a, tile8, img, x0, y0, rows, wave, lane);
   stamp(3);
   __syncthreads();  // the lists are dead: their bytes hold the tile's words with a detection from here on
   stamp(4);
@@ -580,6 +591,18 @@ __global__ __launch_bounds__(kFastThreads, 8) void fast_blur_kernel(const Featur
     fast_blur_tile<false>(a, tile32, resp32, list, second, list_n);
   } else {
     fast_blur_tile<true>(a, tile32, resp32, list, second, list_n);
+  }
+}
+
+// the Gaussian alone, same tiles and same arithmetic as fast_blur_kernel (describe_selected_launch: keypoints from another detector)
+__global__ __launch_bounds__(kFastThreads) void blur_kernel(const FeatureArgs a) {
+  __shared__ __attribute__((aligned(16))) uint32_t tile32[kTileRows * kTileWords];
+  __shared__ int list_n[kFastThreads / 64 + 3];
+  const int x0 = blockIdx.x * kTileW, y0 = blockIdx.y * kTileH;
+  if (x0 >= 4 && x0 + kTileW + 4 <= a.b.cols && y0 >= 4 && y0 + kTileH + 4 <= a.b.rows) {
+    fast_blur_tile<false, false>(a, tile32, nullptr, nullptr, nullptr, list_n);
+  } else {
+    fast_blur_tile<true, false>(a, tile32, nullptr, nullptr, nullptr, list_n);
   }
 }
 
@@ -1509,6 +1532,32 @@ int extract_features_launch(prs_context* ctx, const prs_extractor_params* params
     if (batch->cols > 5 * kTileW && batch->rows > 2 * kTileH) {
       ctx_report_stamps(ctx, batch->batch, 6, "fast_blur_kernel, tile (5, 2): load | compass | arcs + Gaussian | barrier | suppression", false, (size_t) batch->batch);
     }
+  }
+  return PRS_OK;
+}
+
+// descriptors of keypoints selected elsewhere (selective.hip): kept [batch][stride] pixel indices, batch->n_features already
+// written on the device (0 for an image that failed).  The blur and describe kernels of the FAST extractor, unchanged.
+int describe_selected_launch(prs_context* ctx, const prs_extract_batch* batch, uint32_t* kept) {
+  FeatureArgs a{};
+  a.b           = *batch;
+  a.kept        = kept;
+  a.blur_ncb    = (batch->cols + 15) / 16;
+  a.blur_stride = (size_t) ((batch->rows + 7) / 8) * a.blur_ncb * 128;
+  a.blur        = static_cast<uint8_t*>(ctx_device_scratch_slot(ctx, 1, (size_t) batch->batch * a.blur_stride));
+  if (!a.blur) {
+    return ctx_fail(ctx, PRS_ERR_HIP, "describe_selected_launch: scratch allocation failed");
+  }
+  fill_window_offsets(kOrbPattern, &a);
+  hipStream_t stream  = ctx_stream(ctx);
+  const int per_block = (kDescThreads / 64) * kDescPerWave;
+  const int chunks    = (batch->stride + per_block - 1) / per_block;
+  const dim3 tiles((batch->cols + kTileW - 1) / kTileW, (batch->rows + kTileH - 1) / kTileH, batch->batch);
+  hipLaunchKernelGGL(blur_kernel, tiles, dim3(kFastThreads), 0, stream, a);
+  hipLaunchKernelGGL(describe_kernel, dim3((unsigned) (((batch->batch + 7) / 8) * 8 * chunks), 1, 1), dim3(kDescThreads), 0, stream, a, chunks, kDescPerWave);
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) {
+    return ctx_fail_hip(ctx, e, "describe_selected_launch");
   }
   return PRS_OK;
 }

@@ -864,6 +864,73 @@ def extract_features(ctx, params, image, capacity=4096):
     return uv[:k].copy(), inten[:k].copy(), desc[:k].copy()
 
 
+# ---- selective extraction (IntensityFeatureExtractorSelective_, GFTT corners around the projections of tracked landmarks) ----
+DETECTOR_GFTT, DETECTOR_FAST = 0, 1            # PRS_DETECTOR_* (FAST is not built: PRS_ERR_UNSUPPORTED)
+DESCRIPTOR_ORB_256, DESCRIPTOR_BRIEF_256 = 0, 1  # PRS_DESCRIPTOR_* (both cv::ORB in the reference's build)
+_DETECTORS = {"GFTT": DETECTOR_GFTT, "FAST": DETECTOR_FAST}
+_DESCRIPTORS = {"ORB-256": DESCRIPTOR_ORB_256, "BRIEF-256": DESCRIPTOR_BRIEF_256}
+
+
+def selective_extractor_params(detector_type="GFTT", descriptor_type="ORB-256", target_number_of_keypoints=1000,
+                               target_bin_width_pixels=10, enable_full_distance_to_left=False, enable_full_distance_to_right=False,
+                               enable_seeding_when_tracking=True, max_candidates=0):
+    """prs_selective_extractor_params; types by the reference's PARAM strings or the PRS_* values.  max_candidates: GFTT
+    candidates per run the selection sort holds (0 = 8192, at most 16384)"""
+    det = _DETECTORS[detector_type] if isinstance(detector_type, str) else int(detector_type)
+    desc = _DESCRIPTORS[descriptor_type] if isinstance(descriptor_type, str) else int(descriptor_type)
+    return _lib.SelectiveExtractorParams(det, desc, int(target_number_of_keypoints), int(target_bin_width_pixels),
+                                         int(bool(enable_full_distance_to_left)), int(bool(enable_full_distance_to_right)),
+                                         int(bool(enable_seeding_when_tracking)), int(max_candidates))
+
+
+def extract_features_selective(ctx, params, image, projections=None, radius=0, capacity=4096, seeding_mask=None):
+    """host arrays, one 8-bit image [rows, cols]; projections [n, 2] (u, v) = tracking mode, None / empty = seeding mode
+    (seeding_mask [rows, cols], non-zero = detect, applies there only) -> (uv [n, 2] f32, intensity [n] f32,
+    descriptors [n, 32] u8); synchronises"""
+    img = np.ascontiguousarray(image, dtype=np.uint8)
+    rows, cols = img.shape
+    proj = None if projections is None else np.ascontiguousarray(projections, dtype=np.float32).reshape(-1, 2)
+    n_proj = 0 if proj is None else len(proj)
+    mask = None if seeding_mask is None else np.ascontiguousarray(seeding_mask, dtype=np.uint8)
+    if mask is not None and mask.shape != img.shape:
+        raise ValueError("seeding_mask must have the image's shape")
+    uv = np.zeros((capacity, 2), dtype=np.float32)
+    inten = np.zeros(capacity, dtype=np.float32)
+    desc = np.zeros((capacity, 32), dtype=np.uint8)
+    n = C.c_int32(0)
+    rc = _lib.load().prs_extract_features_selective(ctx._h, C.byref(params), _p(img), rows, cols, cols, _p(proj) if n_proj else None, n_proj,
+                                                    int(radius), _p(mask) if mask is not None else None, _p(uv), _p(inten), _p(desc),
+                                                    capacity, C.byref(n))
+    _check(ctx, rc, "prs_extract_features_selective")
+    k = n.value
+    return uv[:k].copy(), inten[:k].copy(), desc[:k].copy()
+
+
+def extract_features_selective_batch(ctx, params, images, keypoints, descriptors, n_features, status, intensity=None,
+                                     projections=None, n_projections=None, radius=None, seeding_mask=None):
+    """images: uint8 device tensor [B, rows, cols(pitch)]; projections: f32 device tensor [B, P, 2] with n_projections
+    (i32 [B]; 0 = that image seeds) and radius (i32 [B] or None = 0); seeding_mask: uint8 device tensor shaped like images,
+    or None.  Outputs as extract_features_batch."""
+    d = _lib.SelectiveExtractBatch()
+    d.batch, d.rows, d.cols, d.pitch = int(images.shape[0]), int(images.shape[1]), int(images.shape[2]), int(images.stride(1))
+    d.images = images.data_ptr()
+    if projections is not None:
+        d.projection_stride = int(projections.shape[1])
+        d.projections, d.n_projections = projections.data_ptr(), n_projections.data_ptr()
+    d.detection_radius = radius.data_ptr() if radius is not None else None
+    if seeding_mask is not None:
+        if tuple(seeding_mask.shape) != tuple(images.shape) or seeding_mask.stride(1) != images.stride(1):
+            raise ValueError("seeding_mask must have the images' shape and pitch")
+        d.seeding_mask = seeding_mask.data_ptr()
+    d.stride = int(keypoints.shape[1])
+    d.keypoints, d.descriptors = keypoints.data_ptr(), descriptors.data_ptr()
+    d.intensity = intensity.data_ptr() if intensity is not None else None
+    d.n_features, d.status = n_features.data_ptr(), status.data_ptr()
+    rc = _lib.load().prs_extract_features_selective_batch(ctx._h, C.byref(params), C.byref(d))
+    _check(ctx, rc, "prs_extract_features_selective_batch")
+    return rc
+
+
 def selftest_reciprocal(ctx):
     """(operands that differ from 1.0f / x, operands that took the short form) over all 2^32 float bit patterns (prs_selftest_reciprocal)"""
     counts = np.zeros(2, dtype=np.uint64)
