@@ -121,3 +121,73 @@ def test_external_seeding_mask():
     # the external mask is a seeding-mode input only: with projections it is ignored
     proj = [(40.0, 40.0)]
     assert np.array_equal(sr.extract(img, 100, 3, projections=proj, external_mask=mask)[0], sr.extract(img, 100, 3, projections=proj)[0])
+
+
+def _reflect101_index(n, pad):
+    """indices of a row or column padded by `pad` with BORDER_REFLECT_101 (..., 2, 1 | 0, 1, ..., n-1 | n-2, ...)"""
+    i = np.arange(-pad, n + pad)
+    i = np.where(i < 0, -i, i)
+    return np.where(i > n - 1, 2 * (n - 1) - i, i)
+
+
+def _min_eigen_f64(image):
+    """cornerMinEigenVal(blockSize 3, ksize 3) in float64, written apart from sr.min_eigen: integer Sobel on the reflect-101
+    padded image, products in float64, unnormalised 3x3 box sums of the reflect-101 padded products, closed-form smaller
+    eigenvalue of [[Sxx, Sxy], [Sxy, Syy]] / 2.  -> (eig, (Sxx + Syy) / 2), both [rows, cols] float64"""
+    img = np.asarray(image, np.int64)
+    rows, cols = img.shape
+    p = img[_reflect101_index(rows, 1)][:, _reflect101_index(cols, 1)]
+    sx = np.zeros((rows, cols), np.int64)
+    sy = np.zeros((rows, cols), np.int64)
+    for k, w in ((0, 1), (1, 2), (2, 1)):
+        sx += w * (p[k:k + rows, 2:] - p[k:k + rows, :-2])
+        sy += w * (p[2:, k:k + cols] - p[:-2, k:k + cols])
+    dx, dy = sx / 3060.0, sy / 3060.0  # 4 * 3 * 255
+    ri, ci = _reflect101_index(rows, 1), _reflect101_index(cols, 1)
+    box = []
+    for q in (dx * dx, dx * dy, dy * dy):
+        qp = q[ri][:, ci]
+        box.append(sum(qp[a:a + rows, b:b + cols] for a in range(3) for b in range(3)))
+    sxx, sxy, syy = box
+    half = (sxx + syy) / 2
+    return half - np.sqrt(((sxx - syy) / 2) ** 2 + sxy ** 2), half
+
+
+# |eig32 - eig64| <= C * 2^-24 * (Sxx + Syy) / 2, with u = 2^-24 and T = (Sxx + Syy) / 2 = a + c (a = Sxx / 2, c = Syy / 2, b = Sxy):
+#   dx = fl(sx * fl(1/3060)): 2u relative (the integer Sobel converts exactly); a product dx * dy: 2u + 2u + u = 5u relative;
+#   a box sum passes every product through four additions: Sxx, Syy within 9u relative, Sxy within 9u * sum |dx dy| <= 9u * T
+#   (|dx dy| <= (dx^2 + dy^2) / 2).  So |da| + |dc| <= 9u T and |db| <= 9u T.
+#   R = sqrt((a - c)^2 + b^2) <= T (Cauchy-Schwarz: b^2 <= 4ac) is 1-Lipschitz in (a - c, b): the inputs move it by <= 18u T.
+#   The formula's own roundings: a + c (u T), a - c (u T through R), d*d + b*b and the square root (2u R <= 2u T), the final
+#   subtraction (u |eig| <= u T).  Together 9 + 18 + 1 + 1 + 2 + 1 = 32 u T to first order; C = 33 covers the second-order terms
+#   (below 1e3 u^2 T) and the float64 reference's own rounding (below 1e2 * 2^-53 T).
+# The error scales with T, not with |eig|: the cancellation in (a + c) - R loses what a and c carry of T.
+C_EIG = 33
+
+
+def _bound_images():
+    rng = np.random.default_rng(17)
+    yy, xx = np.mgrid[:96, :128]
+    blocky = np.repeat(np.repeat(rng.integers(0, 256, (16, 22)), 6, 0), 6, 1)[:96, :128]
+    return {
+        "kitti": rp.kitti_image("left", 0),
+        "icl": rp.icl_gray(0),
+        "random": rng.integers(0, 256, (120, 200)),
+        "blocky": blocky,
+        "ramp": (3 * xx + 6 * yy) % 256,
+        "ramp_x2y": (xx + 2 * yy) % 256,
+        "stripes": np.sin((xx + 2 * yy) * 0.3) * 100 + 128,
+    }
+
+
+@pytest.mark.parametrize("name", list(_bound_images()))
+def test_min_eigen_within_the_float32_bound_of_a_float64_evaluation(name):
+    img = np.asarray(_bound_images()[name]).astype(np.uint8)
+    e32 = sr.min_eigen(img).astype(np.float64)
+    e64, half = _min_eigen_f64(img)
+    assert (half >= 0).all() and (e64 >= -1e-12 * np.maximum(half, 1e-30)).all()  # positive semidefinite up to float64 rounding
+    err = np.abs(e32 - e64)
+    bound = C_EIG * 2.0 ** -24 * half
+    assert (err <= bound).all(), (name, float((err / np.maximum(bound, 1e-300)).max()))
+    # the float32 arithmetic really is what is measured: somewhere the difference is not zero
+    assert err.max() > 0
