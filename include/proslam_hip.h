@@ -107,9 +107,10 @@ PRS_API int prs_version(void);
  * client checks that they agree once (prs_abi_check: also the sizes of the structs it will pass, as the client's compiler laid
  * them out) instead of finding out through a library that reads past a shorter struct (101 -> 102: step_norm_exit at the end of
  * prs_aligner_params; 102 also adds the entry points prs_abi_check and prs_context_set_bruteforce_dense_phase; 103 adds the
- * selective extractor: prs_selective_extractor_params, prs_selective_extract_batch and their two entry points, no existing struct changed).  Callers memset() parameter structs before
+ * selective extractor: prs_selective_extractor_params, prs_selective_extract_batch and their two entry points, no existing struct changed; 104 adds
+ * the RGB-D preprocessor: prs_depth_params, prs_depth_batch and their two entry points, no existing struct changed).  Callers memset() parameter structs before
  * filling them, so that fields they do not know select the shipped defaults (all zero). */
-#define PRS_ABI_VERSION 103
+#define PRS_ABI_VERSION 104
 PRS_API int prs_abi_check(int32_t header_version, uint64_t sizeof_stereo_params, uint64_t sizeof_pcf_params, uint64_t sizeof_aligner_params,
                           uint64_t sizeof_align_batch);
 #define PRS_ABI_CHECK() prs_abi_check(PRS_ABI_VERSION, sizeof(prs_stereo_params), sizeof(prs_pcf_params), sizeof(prs_aligner_params), sizeof(prs_align_batch))
@@ -919,6 +920,64 @@ PRS_API int prs_extract_features_selective(prs_context* ctx,
                                            uint8_t* descriptors,
                                            int32_t capacity,
                                            int32_t* n_features);
+
+/* ================================================================================================
+ * RGB-D preprocessing: depth images to (u, v, d) measurements
+ * replaces RawDataPreprocessorMonocularDepth::compute + _readDepth (sensor_processing/raw_data_preprocessor_monocular_depth.cpp:
+ * 50-180) after its feature extractor has run (a separate launch behind prs_extract_features_batch or
+ * prs_extract_features_selective_batch, whose outputs it reads in place).  For every feature i of an image, in order:
+ *  - raw = depth(rint(v_i), rint(u_i)) (:165-166; rint rounds half to even, so -0.5 is row / column 0), a TYPE_16UC1 image read
+ *    as float (exact) or a TYPE_32FC1 image (:117-129);
+ *  - the feature is kept iff raw > 0 (:169: NaN, -0, 0 and negative depths are dropped, +inf is kept) with
+ *    d = depth_scaling_factor_to_meters * raw (one float multiply, :170);
+ *  - the kept features are compacted in order (:171-176): fixed[k] = (u, v, d, 0) with the feature's descriptor and intensity.
+ * The reference does not check the lookup's bounds (undefined behaviour there): a rounded keypoint outside the depth image is
+ * PRS_ERR_RANGE for that image here.
+ * Status per image: the extractor's error when extract_status[b] < 0; else PRS_ERR_CAPACITY (n_features[b] > stride),
+ * PRS_ERR_RANGE (a keypoint outside the depth image, or n_features[b] < 0); else the OR of PRS_WARN_NO_MATCHES (nothing kept:
+ * the reference's _status = Error, :131-136; also what the extractor reports for an image without keypoints) and
+ * PRS_WARN_SPARSE_DEPTH ((float) without_depth / (float) n > 0.25, :139-145).  An image with an error has n_fixed 0 and
+ * outputs that are not valid; the other images of the batch are unaffected.
+ * Call-level errors: PRS_ERR_UNSUPPORTED (unknown depth_type, or an output row pointer not 16-byte aligned), PRS_ERR_RANGE
+ * (non-finite scale, rows or cols below 1, stride below 1, pitch below cols * element size or not a multiple of it),
+ * PRS_ERR_NULL (a required pointer unset, or exactly one of intensity / fixed_intensity set).
+ * ============================================================================================== */
+enum { PRS_DEPTH_U16 = 0, PRS_DEPTH_F32 = 1 };  /* TYPE_16UC1 / TYPE_32FC1 (:117-129) */
+enum { PRS_WARN_SPARSE_DEPTH = 64 };            /* > 25 % of the features without depth (:139-145) */
+
+typedef struct {
+  int32_t depth_type;                     /* PRS_DEPTH_* (the reference takes it from the image) */
+  float depth_scaling_factor_to_meters;   /* raw_data_preprocessor_monocular_depth.h:26-30 (default 1.0) */
+} prs_depth_params;
+
+typedef struct {
+  int32_t batch, rows, cols, pitch;       /* depth image size; pitch in bytes, a multiple of the element size */
+  const void* depth;                      /* [batch][rows][pitch] */
+  int32_t stride;                         /* row stride of every per-feature array below, in and out */
+  const prs_kp2* keypoints;               /* [batch][stride] (u, v): the extractor's output */
+  const float* intensity;                 /* [batch][stride] or NULL */
+  const uint8_t* descriptors;             /* [batch][stride][32] */
+  const int32_t* n_features;              /* [batch] */
+  const int32_t* extract_status;          /* the extractor's per-image status, or NULL; may alias `status` */
+  float* fixed;                           /* out [batch][stride][4] (u, v, d, 0): the layout of prs_align_batch.fixed and
+                                             prs_merge_batch.measurement, consumed in place */
+  uint8_t* fixed_desc;                    /* out [batch][stride][32] */
+  float* fixed_intensity;                 /* out [batch][stride]; NULL iff intensity is NULL */
+  int32_t* n_fixed;                       /* out [batch] */
+  int32_t* status;                        /* out [batch] */
+} prs_depth_batch;
+
+/* device pointers; enqueues one kernel on the context's stream (graph-capturable, like prs_extract_features_batch).  Inputs and
+ * outputs must not overlap, except extract_status with status. */
+PRS_API int prs_depth_measurements_batch(prs_context* ctx, const prs_depth_params* params, const prs_depth_batch* batch);
+
+/* host pointers, one image: what an adapter's compute() binds.  depth: rows x cols elements of params->depth_type, `pitch` bytes
+ * between rows; keypoints [n][2] (u, v), intensity [n] or NULL, descriptors [n][32]; out: uvd [n][3] (u, v, d), intensity_out
+ * [n] (ignored when intensity is NULL, may be NULL), desc_out [n][32], *n_fixed.  Uploads, runs, downloads, synchronises;
+ * returns the image's status (on an error nothing is returned and *n_fixed is 0). */
+PRS_API int prs_depth_measurements(prs_context* ctx, const prs_depth_params* params, const void* depth, int32_t rows, int32_t cols,
+                                   int32_t pitch, const float* keypoints, const float* intensity, const uint8_t* descriptors,
+                                   int32_t n, float* uvd, float* intensity_out, uint8_t* desc_out, int32_t* n_fixed);
 
 #ifdef __cplusplus
 }

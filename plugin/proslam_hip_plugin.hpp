@@ -16,6 +16,8 @@
 //     (registration/aligner_slice_processor_projective.h:14-192, tests/test_aligners.cpp:1237-1253)
 //   IntensityFeatureExtractorSelective{2D,3D}                      -> IntensityFeatureExtractorSelective{2D,3D}HIP
 //     (sensor_processing/feature_extractors/intensity_feature_extractor_selective.h)
+//   RawDataPreprocessorMonocularDepth                              -> RawDataPreprocessorMonocularDepthHIP
+//     (sensor_processing/raw_data_preprocessor_monocular_depth.{h,cpp})
 //
 // When the srrg2 headers are available the same bodies become real plugin subclasses: see
 // INTEGRATION.md for the BOSS_REGISTER_CLASS adapters.  Points are AoS like the reference's
@@ -838,6 +840,77 @@ protected:
 };
 using IntensityFeatureExtractorSelective2DHIP = IntensityFeatureExtractorSelectiveHIP_<2>;
 using IntensityFeatureExtractorSelective3DHIP = IntensityFeatureExtractorSelectiveHIP_<3>;
+
+// RawDataPreprocessorMonocularDepth (sensor_processing/raw_data_preprocessor_monocular_depth.{h,cpp}): same PARAM name and
+// default, setMeas() / compute(); the intensity and depth images are plain buffers here where the reference takes ImageMessages,
+// and the depth type (PRS_DEPTH_U16 = TYPE_16UC1, PRS_DEPTH_F32 = TYPE_32FC1) comes with the depth image as it does there.
+// compute() runs the owned binned extractor, then the device depth lookup (prs_depth_measurements): features without depth are
+// dropped, the others become (u, v, d) points in order.  status() is Ready, or Error when no feature is left (:131-136); the
+// sparse-depth warning goes to std::cerr (:139-145).  An unknown depth type or a keypoint outside the depth image throws.
+class RawDataPreprocessorMonocularDepthHIP {
+public:
+  using MeasurementType = PointIntensityDescriptorVectorCloud<3>;
+  enum Status { Error = 0, Ready = 1 };
+  explicit RawDataPreprocessorMonocularDepthHIP(ContextPtr ctx) : _ctx(ctx), _extractor(new IntensityFeatureExtractorBinnedHIP(ctx)) {}
+  PropertyFloat param_depth_scaling_factor_to_meters{1.0f};  // raw_data_preprocessor_monocular_depth.h:26-30
+  IntensityFeatureExtractorBinnedHIP& featureExtractor() { return *_extractor; }  // param_feature_extractor
+  void setMeas(MeasurementType* meas_) { _meas = meas_; }
+  Status status() const { return _status; }
+  // intensity: rows x cols 8-bit (pitch bytes between rows); depth: depth_rows x depth_cols elements of depth_type
+  void compute(const uint8_t* intensity, int rows, int cols, int pitch, const void* depth, int depth_rows, int depth_cols, int depth_pitch,
+               int depth_type) {
+    _status = Error;
+    if (!intensity || !depth) throw std::runtime_error("RawDataPreprocessorMonocularDepth::compute|ERROR: measurement not set");
+    if (!_meas) throw std::runtime_error("RawDataPreprocessorMonocularDepth::compute|ERROR: destination buffer not set");
+    if (rows <= 0 || cols <= 0 || depth_rows <= 0 || depth_cols <= 0) {
+      throw std::runtime_error("RawDataPreprocessorMonocularDepth::compute|ERROR: image has zero rows or columns");
+    }
+    _meas->clear();
+    PointIntensityDescriptorVectorCloud<2> features;
+    _extractor->setFeatures(&features);
+    _extractor->compute(intensity, rows, cols, pitch);
+    if (features.empty()) std::cerr << "RawDataPreprocessorMonocularDepth::compute|WARNING: no features found" << std::endl;
+    const size_t n = features.size();
+    std::vector<float> kp(2 * n + 2), inten(n + 1), uvd(3 * n + 3), inten_out(n + 1);
+    std::vector<uint8_t> desc(PRS_DESC_BYTES * (n + 1)), desc_out(PRS_DESC_BYTES * (n + 1));
+    for (size_t i = 0; i < n; ++i) {
+      kp[2 * i]     = features[i].coords[0];
+      kp[2 * i + 1] = features[i].coords[1];
+      inten[i]      = features[i].intensity_value;
+      std::memcpy(&desc[PRS_DESC_BYTES * i], features[i].descriptor_row, PRS_DESC_BYTES);
+    }
+    prs_depth_params p;
+    p.depth_type                     = depth_type;
+    p.depth_scaling_factor_to_meters = param_depth_scaling_factor_to_meters.value();
+    int32_t k    = 0;
+    const int rc = prs_depth_measurements(_ctx->get(), &p, depth, depth_rows, depth_cols, depth_pitch, kp.data(), inten.data(), desc.data(),
+                                          (int32_t) n, uvd.data(), inten_out.data(), desc_out.data(), &k);
+    if (rc < 0) throw std::runtime_error(std::string("RawDataPreprocessorMonocularDepthHIP::compute|ERROR: ") + prs_last_error(_ctx->get()));
+    _meas->reserve((size_t) k);
+    for (int32_t i = 0; i < k; ++i) {
+      PointIntensityDescriptor3f q;
+      std::memcpy(q.coords, &uvd[3 * (size_t) i], 3 * sizeof(float));
+      q.intensity_value = inten_out[(size_t) i];
+      std::memcpy(q.descriptor_row, &desc_out[PRS_DESC_BYTES * (size_t) i], PRS_DESC_BYTES);
+      _meas->push_back(q);
+    }
+    if (rc & PRS_WARN_NO_MATCHES) {
+      std::cerr << "RawDataPreprocessorMonocularDepth::compute|WARNING: no adapted measurements generated" << std::endl;
+      return;  // _status stays Error (:131-136)
+    }
+    if (rc & PRS_WARN_SPARSE_DEPTH) {
+      std::cerr << "RawDataPreprocessorMonocularDepth::compute|WARNING: high number of points without depth: " << (n - (size_t) k) << "/" << n
+                << std::endl;
+    }
+    _status = Ready;
+  }
+
+protected:
+  ContextPtr _ctx;
+  std::unique_ptr<IntensityFeatureExtractorBinnedHIP> _extractor;
+  MeasurementType* _meas = nullptr;
+  Status _status         = Error;
+};
 
 // MergerRigidStereoTriangulation with LandmarkEstimatorWeightedMean4D3D (mapping/mergers/merger_rigid_stereo_triangulation.h,
 // merger_projective.h, landmarks/landmark_estimator_weighted_mean.h): same setters and PARAM names; the scene is mirrored into a

@@ -9,7 +9,7 @@ import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libproslam_hip.so")
-ABI_VERSION = 103  # PRS_ABI_VERSION of include/proslam_hip.h
+ABI_VERSION = 104  # PRS_ABI_VERSION of include/proslam_hip.h
 
 # status codes (include/proslam_hip.h)
 OK = 0
@@ -19,6 +19,7 @@ WARN_LOW_RATIO = 4
 WARN_RETRIED = 8
 WARN_TRACK_LOST = 16
 WARN_NO_PROJECTION = 32
+WARN_SPARSE_DEPTH = 64  # PRS_WARN_SPARSE_DEPTH (RGB-D preprocessor)
 ERR_NULL = -1
 ERR_CAPACITY = -2
 ERR_HIP = -3
@@ -279,6 +280,19 @@ class SelectiveExtractBatch(C.Structure):
                 ("intensity", C.c_void_p), ("descriptors", C.c_void_p), ("n_features", C.c_void_p), ("status", C.c_void_p)]
 
 
+class DepthParams(C.Structure):
+    """prs_depth_params"""
+    _fields_ = [("depth_type", C.c_int32), ("depth_scaling_factor_to_meters", C.c_float)]
+
+
+class DepthBatch(C.Structure):
+    """prs_depth_batch (device pointers)"""
+    _fields_ = [("batch", C.c_int32), ("rows", C.c_int32), ("cols", C.c_int32), ("pitch", C.c_int32), ("depth", C.c_void_p),
+                ("stride", C.c_int32), ("keypoints", C.c_void_p), ("intensity", C.c_void_p), ("descriptors", C.c_void_p),
+                ("n_features", C.c_void_p), ("extract_status", C.c_void_p), ("fixed", C.c_void_p), ("fixed_desc", C.c_void_p),
+                ("fixed_intensity", C.c_void_p), ("n_fixed", C.c_void_p), ("status", C.c_void_p)]
+
+
 MODE_ALIGN, MODE_FINDER, MODE_LINEARIZE = 0, 1, 2
 
 # every symbol include/proslam_hip.h declares: (restype, argtypes)
@@ -332,6 +346,9 @@ SYMBOLS = {
     "prs_extract_features_selective_batch": (C.c_int, [_vp, C.POINTER(SelectiveExtractorParams), C.POINTER(SelectiveExtractBatch)]),
     "prs_extract_features_selective": (C.c_int, [_vp, C.POINTER(SelectiveExtractorParams), _vp, C.c_int32, C.c_int32, C.c_int32, _vp,
                                                  C.c_int32, C.c_int32, _vp, _vp, _vp, _vp, C.c_int32, _i32p]),
+    "prs_depth_measurements_batch": (C.c_int, [_vp, C.POINTER(DepthParams), C.POINTER(DepthBatch)]),
+    "prs_depth_measurements": (C.c_int, [_vp, C.POINTER(DepthParams), _vp, C.c_int32, C.c_int32, C.c_int32, _vp, _vp, _vp, C.c_int32,
+                                         _vp, _vp, _vp, _i32p]),
     "prs_pose_compose_batch": (C.c_int, [_vp, C.c_int32, _vp, _vp, _vp]),
     "prs_motion_predict_batch": (C.c_int, [_vp, C.c_int32, _vp, _vp, _vp]),
     "prs_merge_batch_run": (C.c_int, [_vp, C.POINTER(MergerParams), C.POINTER(MergeBatch)]),

@@ -85,6 +85,9 @@ ICL = {
                 "min_num_inliers": 6, "min_num_correspondences": 0,  # icl.conf:584
                 "enable_inlier_only_runs": 1, "keep_only_inlier_correspondences": 1},  # icl.conf:50-53, :57-59
     "depth": {"min": 0.5, "max": 6.0},
+    # RawDataPreprocessorMonocularDepth (icl.conf:642-650) and its IntensityFeatureExtractorBinned3D (icl.conf:745-770)
+    "rgbd": {"depth_scaling_factor_to_meters": 0.001, "detector_threshold": 5, "enable_non_maximum_suppression": 1,
+             "number_of_detectors_vertical": 3, "number_of_detectors_horizontal": 3, "target_number_of_keypoints": 500},
 }
 
 TUM = {
@@ -108,6 +111,9 @@ TUM = {
                 "min_num_inliers": 6, "min_num_correspondences": 0,  # tum.conf:260
                 "enable_inlier_only_runs": 1, "keep_only_inlier_correspondences": 1},  # tum.conf:90-93, :97-99
     "depth": {"min": 0.5, "max": 6.0},
+    # RawDataPreprocessorMonocularDepth (tum.conf:633-640) and its IntensityFeatureExtractorBinned3D (tum.conf:858-883)
+    "rgbd": {"depth_scaling_factor_to_meters": 0.001, "detector_threshold": 5, "enable_non_maximum_suppression": 1,
+             "number_of_detectors_vertical": 3, "number_of_detectors_horizontal": 3, "target_number_of_keypoints": 1000},
 }
 
 CONFIGS = {"kitti": KITTI, "euroc": EUROC, "icl": ICL, "tum": TUM}

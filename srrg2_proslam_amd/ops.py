@@ -962,3 +962,125 @@ def extract_features_batch(ctx, params, images, keypoints, descriptors, n_featur
     rc = _lib.load().prs_extract_features_batch(ctx._h, C.byref(params), C.byref(d))
     _check(ctx, rc, "prs_extract_features_batch")
     return rc
+
+
+# ---- RGB-D preprocessing (RawDataPreprocessorMonocularDepth: extractor keypoints + depth image -> (u, v, d) measurements) ----
+DEPTH_U16, DEPTH_F32 = 0, 1  # PRS_DEPTH_* (TYPE_16UC1 / TYPE_32FC1)
+_DEPTH_TYPES = {"u16": DEPTH_U16, "f32": DEPTH_F32}
+_DEPTH_NP = {DEPTH_U16: np.uint16, DEPTH_F32: np.float32}
+
+
+def depth_params(depth_type="u16", scale=1.0):
+    """prs_depth_params; depth_type "u16" / "f32" or a PRS_DEPTH_* value, scale = depth_scaling_factor_to_meters
+    (raw_data_preprocessor_monocular_depth.h:26-30, default 1.0; icl.conf:646 / tum.conf:638 use 0.001)"""
+    t = _DEPTH_TYPES[depth_type] if isinstance(depth_type, str) else int(depth_type)
+    return _lib.DepthParams(t, float(scale))
+
+
+def depth_measurements(ctx, params, depth, keypoints, descriptors, intensity=None):
+    """host arrays, one image: depth [rows, cols] (uint16 or float32 as params.depth_type), keypoints [n, 2] (u, v),
+    descriptors [n, 32], intensity [n] or None -> (uvd [k, 3] f32, intensity [k] f32 or None, descriptors [k, 32] u8, status);
+    synchronises"""
+    dep = np.ascontiguousarray(depth, dtype=_DEPTH_NP.get(params.depth_type))  # an unknown type is the library's to refuse
+    rows, cols = dep.shape
+    kp = _np(keypoints, np.float32, (-1, 2))
+    n = kp.shape[0]
+    desc = _np(descriptors, np.uint8, (n, 32))
+    inten = None if intensity is None else _np(intensity, np.float32, (n,))
+    cap = max(n, 1)
+    uvd = np.zeros((cap, 3), dtype=np.float32)
+    inten_out = np.zeros(cap, dtype=np.float32)
+    desc_out = np.zeros((cap, 32), dtype=np.uint8)
+    k = C.c_int32(0)
+    rc = _lib.load().prs_depth_measurements(ctx._h, C.byref(params), _p(dep), rows, cols, dep.strides[0], _p(kp),
+                                            _p(inten) if inten is not None else None, _p(desc), n, _p(uvd), _p(inten_out), _p(desc_out),
+                                            C.byref(k))
+    _check(ctx, rc, "prs_depth_measurements")
+    m = k.value
+    return uvd[:m].copy(), (inten_out[:m].copy() if inten is not None else None), desc_out[:m].copy(), rc
+
+
+def depth_measurements_batch(ctx, params, depth, keypoints, descriptors, n_features, fixed, fixed_desc, n_fixed, status,
+                             intensity=None, fixed_intensity=None, extract_status=None):
+    """device tensors: depth [B, rows, cols(pitch)] uint16 / float32; keypoints [B, stride, 2] f32, descriptors [B, stride, 32] u8,
+    n_features [B] i32 (an extractor's outputs), intensity [B, stride] f32 or None, extract_status [B] i32 or None (may be
+    `status`); out: fixed [B, stride, 4] f32 (u, v, d, 0), fixed_desc [B, stride, 32] u8, fixed_intensity [B, stride] f32 (with
+    intensity), n_fixed [B] i32, status [B] i32.  Enqueues on the context stream (asynchronous)."""
+    d = _lib.DepthBatch()
+    d.batch, d.rows, d.cols = int(depth.shape[0]), int(depth.shape[1]), int(depth.shape[2])
+    d.pitch = int(depth.stride(1)) * depth.element_size()
+    d.depth = depth.data_ptr()
+    d.stride = int(keypoints.shape[1])
+    for t in (descriptors, fixed, fixed_desc) + ((intensity, fixed_intensity) if intensity is not None else ()):
+        if int(t.shape[1]) != d.stride:
+            raise ValueError("every per-feature tensor needs the keypoints' stride")
+    d.keypoints, d.descriptors, d.n_features = keypoints.data_ptr(), descriptors.data_ptr(), n_features.data_ptr()
+    d.intensity = intensity.data_ptr() if intensity is not None else None
+    d.extract_status = extract_status.data_ptr() if extract_status is not None else None
+    d.fixed, d.fixed_desc, d.n_fixed, d.status = fixed.data_ptr(), fixed_desc.data_ptr(), n_fixed.data_ptr(), status.data_ptr()
+    d.fixed_intensity = fixed_intensity.data_ptr() if fixed_intensity is not None else None
+    rc = _lib.load().prs_depth_measurements_batch(ctx._h, C.byref(params), C.byref(d))
+    _check(ctx, rc, "prs_depth_measurements_batch")
+    return rc
+
+
+class RGBDFrames:
+    """B RGB-D frames resident in HBM: the intensity and depth images, the extractor's outputs and the depth stage's
+    measurements.  `fixed` / `fixed_desc` / `n_fixed` have the layout of AlignFrames.fixed / fixed_desc / n_fixed and
+    MapBatch.measurement / measurement_desc / n_measured, so those can point at them (as StereoFrames.fixed_uvuv does for stereo):
+    extract -> depth -> align / merge without a host copy.  `status` holds the extractor's status after extract() and the
+    depth stage's after depth()."""
+
+    def __init__(self, device, batch, rows, cols, stride, depth_type="u16", with_intensity=True):
+        import torch
+        dev = torch.device("cuda", device)
+        self.batch, self.rows, self.cols, self.stride = int(batch), int(rows), int(cols), int(stride)
+        t = _DEPTH_TYPES[depth_type] if isinstance(depth_type, str) else int(depth_type)
+        z = lambda shape, dt: torch.zeros(shape, dtype=dt, device=dev)  # noqa: E731
+        self.images = z((batch, rows, cols), torch.uint8)
+        self.depth = z((batch, rows, cols), torch.uint16 if t == DEPTH_U16 else torch.float32)
+        self.keypoints = z((batch, stride, 2), torch.float32)
+        self.descriptors = z((batch, stride, 32), torch.uint8)
+        self.intensity = z((batch, stride), torch.float32) if with_intensity else None
+        self.n_features = z((batch,), torch.int32)
+        self.fixed = z((batch, stride, 4), torch.float32)
+        self.fixed_desc = z((batch, stride, 32), torch.uint8)
+        self.fixed_intensity = z((batch, stride), torch.float32) if with_intensity else None
+        self.n_fixed = z((batch,), torch.int32)
+        self.status = z((batch,), torch.int32)
+
+    def upload(self, b, image, depth):
+        import torch
+        self.images[b] = torch.from_numpy(np.ascontiguousarray(image, dtype=np.uint8))
+        self.depth[b] = torch.from_numpy(np.ascontiguousarray(depth, dtype=np.uint16 if self.depth.dtype == torch.uint16 else np.float32))
+
+    def extract(self, ctx, extractor_params_):
+        """the binned extractor on every image (status <- the extractor's)"""
+        return extract_features_batch(ctx, extractor_params_, self.images, self.keypoints, self.descriptors, self.n_features,
+                                      self.status, self.intensity)
+
+    def measure(self, ctx, depth_params_):
+        """the depth stage on the extractor's outputs in place (status <- the extractor's error or the stage's own)"""
+        return depth_measurements_batch(ctx, depth_params_, self.depth, self.keypoints, self.descriptors, self.n_features, self.fixed,
+                                        self.fixed_desc, self.n_fixed, self.status, self.intensity, self.fixed_intensity, self.status)
+
+    def run(self, ctx, extractor_params_, depth_params_):
+        self.extract(ctx, extractor_params_)
+        return self.measure(ctx, depth_params_)
+
+    def fixed_of(self, b):
+        """download frame b: (uvd [k, 3] f32, descriptors [k, 32] u8, intensity [k] f32 or None, status)"""
+        k = int(self.n_fixed[b].item())
+        uvd = self.fixed[b, :k, :3].cpu().numpy().copy()
+        desc = self.fixed_desc[b, :k].cpu().numpy().copy()
+        inten = self.fixed_intensity[b, :k].cpu().numpy().copy() if self.fixed_intensity is not None else None
+        return uvd, desc, inten, int(self.status[b].item())
+
+
+def rgbd_params(cfg, selection_order=SELECT_LIBSTDCXX, max_raw_detections=32768, depth_type="u16"):
+    """(prs_extractor_params, prs_depth_params) of a configs.* RGB-D dictionary's "rgbd" group (icl, tum); the extractor keeps the
+    reference's std::sort order by default"""
+    r = cfg["rgbd"]
+    ep = extractor_params(int(r["detector_threshold"]), int(r["enable_non_maximum_suppression"]), int(r["target_number_of_keypoints"]),
+                          int(r["number_of_detectors_vertical"]), int(r["number_of_detectors_horizontal"]), selection_order, max_raw_detections)
+    return ep, depth_params(depth_type, r["depth_scaling_factor_to_meters"])

@@ -228,6 +228,18 @@ def stereo_images(rng, cfg, n_rectangles=140, max_disparity=90):
     return left, right, rects
 
 
+def _layer_texture(rng, h, w, size):
+    """blocks of size x size random grey levels with 4 x 4 black / white blobs: the texture of one layer of the sequences below"""
+    b = rng.integers(20, 236, ((h + size - 1) // size, (w + size - 1) // size)).astype(np.uint8)
+    t = np.kron(b, np.ones((size, size), np.uint8))[:h, :w].copy()
+    n_blobs = max(h * w // 220, 1)
+    ys, xs = rng.integers(0, max(h - 4, 1), n_blobs), rng.integers(0, max(w - 4, 1), n_blobs)
+    gs = rng.integers(0, 2, n_blobs) * 255
+    for y, x, g in zip(ys, xs, gs):
+        t[y: y + 4, x: x + 4] = g
+    return t
+
+
 def stereo_image_sequence(rng, cfg, n_frames, n_rectangles=140, max_disparity=88):
     """rectified stereo image pairs of ONE static layered scene seen from a camera that steps sideways by a quarter of
     the baseline per frame: every disparity is a multiple of 4, so a layer moves by disparity / 4 whole pixels from
@@ -238,14 +250,7 @@ def stereo_image_sequence(rng, cfg, n_frames, n_rectangles=140, max_disparity=88
     margin = (max_disparity // 4) * n_frames + max_disparity + 8  # content that scrolls into view
 
     def blocks(h, w, size):
-        b = rng.integers(20, 236, ((h + size - 1) // size, (w + size - 1) // size)).astype(np.uint8)
-        t = np.kron(b, np.ones((size, size), np.uint8))[:h, :w].copy()
-        n_blobs = max(h * w // 220, 1)
-        ys, xs = rng.integers(0, max(h - 4, 1), n_blobs), rng.integers(0, max(w - 4, 1), n_blobs)
-        gs = rng.integers(0, 2, n_blobs) * 255
-        for y, x, g in zip(ys, xs, gs):
-            t[y: y + 4, x: x + 4] = g
-        return t
+        return _layer_texture(rng, h, w, size)
 
     wide = cols + 2 * margin
     background = blocks(rows, wide, 16)  # disparity 4: one pixel per frame
@@ -274,3 +279,50 @@ def stereo_image_sequence(rng, cfg, n_frames, n_rectangles=140, max_disparity=88
         right = render(lambda dd: k * dd // 4 + dd)
         frames.append((left, right))
     return frames, float(cam["baseline_m"]) / 4.0
+
+
+def rgbd_image_sequence(rng, cfg, n_frames, baseline_m=0.2, n_rectangles=140, max_disparity=88, holes_per_layer=3):
+    """RGB-D frames of the layered scene of `stereo_image_sequence`, seen by one camera of cfg (icl / tum) that steps sideways
+    by baseline_m / 4 per frame: a layer of "disparity" dd (a multiple of 4) lies at depth fx * baseline_m / dd and moves by
+    dd / 4 whole pixels from frame to frame.  The depth image is uint16 millimetres (depth_scaling_factor_to_meters 0.001,
+    icl.conf:646) of each layer, with a few holes of depth 0 that travel with their layer.  Returns
+    ([(gray, depth_mm)] per frame, step in metres): camera k sits at x = k * step in the frame of camera 0."""
+    cam = cfg["camera"]
+    rows, cols = int(cam["rows"]), int(cam["cols"])
+    margin = (max_disparity // 4) * n_frames + max_disparity + 8
+
+    def blocks(h, w, size):
+        return _layer_texture(rng, h, w, size)
+
+    def depth_of(h, w, dd):
+        z = np.full((h, w), int(round(1000.0 * float(cam["fx"]) * baseline_m / dd)), np.uint16)
+        for _ in range(holes_per_layer):
+            hh, ww = int(rng.integers(4, max(h // 3, 5))), int(rng.integers(4, max(w // 3, 5)))
+            y, x = int(rng.integers(0, max(h - hh, 1))), int(rng.integers(0, max(w - ww, 1)))
+            z[y: y + hh, x: x + ww] = 0
+        return z
+
+    wide = cols + 2 * margin
+    background = (blocks(rows, wide, 16), depth_of(rows, wide, 4))
+    d = np.sort(rng.integers(2, max_disparity // 4 + 1, n_rectangles)) * 4
+    rects = []
+    for k in range(n_rectangles):
+        w, h = int(rng.integers(60, 220)), int(rng.integers(40, 140))
+        x, y = int(rng.integers(0, wide - w)), int(rng.integers(0, rows - h))
+        rects.append((x, y, blocks(h, w, 8), depth_of(h, w, int(d[k])), int(d[k])))
+
+    frames = []
+    for k in range(n_frames):
+        img = np.empty((rows, cols), np.uint8)
+        dep = np.empty((rows, cols), np.uint16)
+        s0 = k  # the background (dd = 4) moves one pixel per frame
+        img[:] = background[0][:, margin + s0: margin + s0 + cols]
+        dep[:] = background[1][:, margin + s0: margin + s0 + cols]
+        for x, y, tex, z, dd in rects:  # far to near
+            xs = x - margin - k * dd // 4
+            x0, x1 = max(xs, 0), min(xs + tex.shape[1], cols)
+            if x1 > x0:
+                img[y: y + tex.shape[0], x0: x1] = tex[:, x0 - xs: x1 - xs]
+                dep[y: y + tex.shape[0], x0: x1] = z[:, x0 - xs: x1 - xs]
+        frames.append((img, dep))
+    return frames, baseline_m / 4.0
