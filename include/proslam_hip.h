@@ -108,7 +108,9 @@ PRS_API int prs_version(void);
  * them out) instead of finding out through a library that reads past a shorter struct (101 -> 102: step_norm_exit at the end of
  * prs_aligner_params; 102 also adds the entry points prs_abi_check and prs_context_set_bruteforce_dense_phase; 103 adds the
  * selective extractor: prs_selective_extractor_params, prs_selective_extract_batch and their two entry points, no existing struct changed; 104 adds
- * the RGB-D preprocessor: prs_depth_params, prs_depth_batch and their two entry points, no existing struct changed).  Callers memset() parameter structs before
+ * the RGB-D preprocessor: prs_depth_params, prs_depth_batch and their two entry points, no existing struct changed; the loop aligner's
+ * prs_point_align_params, prs_point_align_pairs, prs_point_align_result and its two entry points came later under the same version:
+ * new structs and new entry points only, nothing a 104 client passes changed).  Callers memset() parameter structs before
  * filling them, so that fields they do not know select the shipped defaults (all zero). */
 #define PRS_ABI_VERSION 104
 PRS_API int prs_abi_check(int32_t header_version, uint64_t sizeof_stereo_params, uint64_t sizeof_pcf_params, uint64_t sizeof_aligner_params,
@@ -978,6 +980,105 @@ PRS_API int prs_depth_measurements_batch(prs_context* ctx, const prs_depth_param
 PRS_API int prs_depth_measurements(prs_context* ctx, const prs_depth_params* params, const void* depth, int32_t rows, int32_t cols,
                                    int32_t pitch, const float* keypoints, const float* intensity, const uint8_t* descriptors,
                                    int32_t n, float* uvd, float* intensity_out, uint8_t* desc_out, int32_t* n_fixed);
+
+/* ================================================================================================
+ * Loop aligner: point-to-point SE(3) registration of matched 3D clouds (the consumer of the
+ * brute-force matcher's correspondences)
+ * replaces MultiAligner3DQR "loop_aligner" with one AlignerSliceProcessor3D (registration/aligner_slice_processor_3d.hpp:7-22:
+ * SE3Point2PointErrorFactor, information I3; registered at registration/instances.cpp:28,52), the aligner every shipped .conf wires
+ * in as MultiLoopDetectorHBST3D.relocalize_aligner (kitti.conf:938-978), and the accept / reject verdict of the loop detector and
+ * MultiRelocalizer3D (parameter comments kitti.conf:966-977).  HBST candidate search, pose-graph insertion and the closure merger
+ * are not served.
+ *
+ * The factor, the robustifiers, the loop and the verdict live in srrg2_solver / srrg2_slam_interfaces, not in the tree
+ * (BUILD-DEFINED, stated like rows a13 / a14 of SURVEY.md Appendix A):
+ *   factor       e = R p + t - f, X = [R | t] = movingInFixed, p a moving point, f its fixed partner; chi = e^T e (Omega = I3);
+ *                J = R [I3 | -2 [p]x], the right perturbation X <- X exp(dx) of VariableSE3QuaternionRight.
+ *   robustifier  inlier iff chi <= chi_threshold.  CLAMP: an outlier gets weight 0.  SATURATED: an outlier gets Omega / chi (the
+ *                shipped a13 reading, PRS_KERNEL_WEIGHT_INV_CHI).  Both report an outlier's chi as chi_threshold in chi_total.  A
+ *                correspondence whose chi is not finite (NaN / inf coordinates) is INVALID: no weight, neither inlier nor outlier.
+ *   step         prs_gn_step's LDL^T of (H + damping diag(H)) dx = -b, X <- X exp(dx); a non-positive pivot leaves X untouched.
+ *   loop         max_iterations x (linearise, step), no termination criterion; the result holds the LAST linearisation (H, b,
+ *                chi sums, counts), status = num_inliers >= min_num_inliers.  n_corr < min_num_correspondences, or no
+ *                correspondence at all, means status 0, no iteration and X unchanged.
+ *   verdict      accepted = status && num_inliers >= relocalize_min_inliers
+ *                && (float) num_inliers / (float) n_corr >= relocalize_min_inliers_ratio
+ *                && chi_inliers / (float) num_inliers <= relocalize_max_chi_inliers.
+ * Sums (BUILD-DEFINED, fixed shape): with y = R p (each component ((R_i0 px + R_i1 py) + R_i2 pz)), e = (y + t) - f,
+ * chi = (e0 e0 + e1 e1) + e2 e2 and w the weight, the 18 terms w, w y, w (y1 y1 + y2 y2), w (y0 y0 + y2 y2), w (y0 y0 + y1 y1),
+ * w (y0 y1), w (y0 y2), w (y1 y2), w e, w (y x e), chi (inliers) and chi or chi_threshold (all valid) of correspondence k go to
+ * lane k mod 64, each lane sums its correspondences in ascending k from +0, and the 64 lane sums are combined by the butterfly
+ * v[l] <- v[l] + v[l ^ m], m = 32, 16, 8, 4, 2, 1.  The camera-frame system [[sum w I, -2 [sum w y]x], [2 [sum w y]x,
+ * 4 sum w [y]x^T[y]x]], [sum w e; 2 sum w (y x e)] is rotated once, H = Rt^T H_c Rt, b = Rt^T b_c (Rt = blockdiag(R, R)), in the
+ * operation order of rotate_normal_equations with separate multiplies and adds (csrc/point_align.hip).  Same inputs give the same
+ * bits for every batch size, position in the batch, kernel instantiation and entry point.
+ * Checked per pair (written to result[].warnings, other pairs unaffected): a negative match_status is passed through without
+ * iterating; n_corr > corr_stride, n_fixed > fixed_stride or n_moving > moving_stride gives PRS_ERR_CAPACITY, a negative count or
+ * an index outside [0, n_fixed) / [0, n_moving) PRS_ERR_RANGE; zero correspondences PRS_WARN_NO_MATCHES.
+ * ============================================================================================== */
+/* result of one cloud pair */
+typedef struct {
+  float H[36];                 /* last linearisation, row-major */
+  float b[6];
+  float chi_inliers;
+  float chi_total;
+  int32_t num_inliers;
+  int32_t num_outliers;
+  int32_t num_invalid;
+  int32_t num_correspondences; /* n_corr */
+  int32_t status;              /* 1 Success, 0 Fail */
+  int32_t accepted;            /* the loop detector's verdict */
+  int32_t iterations;          /* linearisations run (max_iterations, 1 with linearize_only, 0 when not iterated) */
+  int32_t warnings;            /* PRS_WARN_NO_MATCHES, or a PRS_ERR_* code (a negative match_status passed through) */
+} prs_point_align_result;
+
+enum { PRS_ROBUSTIFIER_CLAMP = 0, PRS_ROBUSTIFIER_SATURATED = 1 };
+
+typedef struct {
+  int32_t robustifier;                /* PRS_ROBUSTIFIER_*: RobustifierClamp / RobustifierSaturated of the slice (kitti.conf:649-677) */
+  float chi_threshold;                /* the robustifier's chi_threshold */
+  float damping;                      /* IterationAlgorithmGN damping of the aligner's solver (0 in every shipped .conf) */
+  int32_t max_iterations;             /* MultiAligner3DQR max_iterations (one GN iteration each) */
+  int32_t min_num_inliers;            /* MultiAligner3DQR min_num_inliers: status */
+  int32_t min_num_correspondences;    /* AlignerSliceProcessor3D min_num_correspondences */
+  int32_t relocalize_min_inliers;     /* verdict thresholds of the loop detector / MultiRelocalizer3D (kitti.conf:966-977) */
+  float relocalize_min_inliers_ratio;
+  float relocalize_max_chi_inliers;
+  int32_t linearize_only;             /* 1: ONE linearisation at X and no step (factor-level use); 0: the aligner loop */
+  int32_t parked_per_lane;            /* 0 (what memset gives) = by corr_stride; 1, 4, 6 select the kernel instantiation that
+                                         keeps that many correspondences per lane in registers (tests, A-B runs: same results) */
+} prs_point_align_params;
+
+/* device-resident batch of B independent (fixed, moving) cloud pairs; rows as the triangulator and the map write them */
+typedef struct {
+  int32_t batch;
+  int32_t fixed_stride;
+  int32_t moving_stride;
+  int32_t corr_stride;           /* <= 8192 (the brute-force matcher's output stride min(fixed_stride, moving_stride) fits) */
+  const float* fixed;            /* [batch][fixed_stride][4] (x, y, z, -), 16-byte aligned */
+  const int32_t* n_fixed;        /* [batch] */
+  const float* moving;           /* [batch][moving_stride][4] (x, y, z, -), 16-byte aligned */
+  const int32_t* n_moving;       /* [batch] */
+  const prs_corr* corr;          /* [batch][corr_stride]: fixed_idx / moving_idx, as prs_bruteforce_match_batch emits them */
+  const int32_t* n_corr;         /* [batch] */
+  const int32_t* match_status;   /* optional [batch]: the matcher's status words; a negative one is passed through */
+  float* X;                      /* [batch][16] in: movingInFixed guess, out: estimate (row-major 4x4) */
+  prs_point_align_result* result; /* [batch] */
+  uint8_t* inlier_mask;          /* optional [batch][corr_stride]: 1 = inlier at the last linearisation, 0 = outlier or invalid
+                                    (0 for every correspondence of a pair that was not linearised; untouched on an error) */
+} prs_point_align_pairs;
+
+/* device pointers, asynchronous on the context's stream: one kernel launch, no allocation and no synchronisation (graph-capturable).
+ * Replaces MultiAligner3DQR::compute with AlignerSliceProcessor3D (registration/aligner_slice_processor_3d.hpp:7-22) for B pairs. */
+PRS_API int prs_point_align_batch(prs_context* ctx, const prs_point_align_params* params, const prs_point_align_pairs* batch);
+
+/* host pointers, one pair: what an adapter's compute() binds (AlignerSliceProcessor3D setFixed / setMoving / setCorrespondences,
+ * MultiAligner3DQR setMovingInFixed / compute / status / movingInFixed).  fixed_xyz [n_fixed][3], moving_xyz [n_moving][3], corr
+ * [n_corr] (n_corr <= 8192), X16 in/out, inlier_mask [n_corr] or NULL.  Uploads, runs, downloads, synchronises; returns the pair's
+ * warnings, or its PRS_ERR_* code. */
+PRS_API int prs_point_align(prs_context* ctx, const prs_point_align_params* params, const float* fixed_xyz, int32_t n_fixed,
+                            const float* moving_xyz, int32_t n_moving, const prs_corr* corr, int32_t n_corr, float* X16,
+                            prs_point_align_result* result, uint8_t* inlier_mask);
 
 #ifdef __cplusplus
 }

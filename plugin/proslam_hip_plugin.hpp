@@ -18,6 +18,8 @@
 //     (sensor_processing/feature_extractors/intensity_feature_extractor_selective.h)
 //   RawDataPreprocessorMonocularDepth                              -> RawDataPreprocessorMonocularDepthHIP
 //     (sensor_processing/raw_data_preprocessor_monocular_depth.{h,cpp})
+//   MultiAligner3DQR "loop_aligner" + AlignerSliceProcessor3D      -> AlignerSliceProcessor3DHIP
+//     (registration/aligner_slice_processor_3d.hpp:7-22, the relocalize_aligner of the loop detector)
 //
 // When the srrg2 headers are available the same bodies become real plugin subclasses: see
 // INTEGRATION.md for the BOSS_REGISTER_CLASS adapters.  Points are AoS like the reference's
@@ -1067,6 +1069,74 @@ protected:
   float _measurement_in_world[16];
   float _baseline_px = 0.f;
   size_t _n_merged = 0, _n_added = 0;
+};
+
+// ---- loop aligner -----------------------------------------------------------------------------------
+// MultiAligner3DQR "loop_aligner" with one AlignerSliceProcessor3D (registration/aligner_slice_processor_3d.hpp:7-22): point-to-point
+// SE(3) registration of two 3D clouds through given correspondences (SE3Point2PointErrorFactor, Omega = I3), plus the loop
+// detector's accept / reject verdict (kitti.conf:966-977).  Defaults: the kitti.conf loop aligner (:380-408, :938-978).
+class AlignerSliceProcessor3DHIP {
+public:
+  enum Status { Fail = 0, Success = 1 };
+  enum Robustifier { Clamp = PRS_ROBUSTIFIER_CLAMP, Saturated = PRS_ROBUSTIFIER_SATURATED };
+  using CloudType = PointIntensityDescriptorVectorCloud<3>;
+  explicit AlignerSliceProcessor3DHIP(ContextPtr ctx) : _ctx(std::move(ctx)) {}
+  PropertyInt param_robustifier{Clamp};                  // slice->param_robustifier: RobustifierClamp / RobustifierSaturated
+  PropertyFloat param_chi_threshold{3.0f};               // the robustifier's chi_threshold
+  PropertyUnsignedInt param_min_num_correspondences{30};  // AlignerSliceProcessor3D
+  PropertyUnsignedInt param_max_iterations{100};         // MultiAligner3DQR
+  PropertyUnsignedInt param_min_num_inliers{10};
+  PropertyFloat param_damping{0.0f};                     // IterationAlgorithmGN
+  PropertyUnsignedInt param_relocalize_min_inliers{25};  // MultiLoopDetectorHBST3D / MultiRelocalizer3D verdict
+  PropertyFloat param_relocalize_min_inliers_ratio{0.5f};
+  PropertyFloat param_relocalize_max_chi_inliers{2.0f};
+
+  void setFixed(const CloudType* fixed_) { _fixed = fixed_; }
+  void setMoving(const CloudType* moving_) { _moving = moving_; }
+  void setCorrespondences(const CorrespondenceVector* correspondences_) { _correspondences = correspondences_; }
+  void setMovingInFixed(const float* T16_row_major) { std::memcpy(_moving_in_fixed, T16_row_major, sizeof(_moving_in_fixed)); }
+  const float* movingInFixed() const { return _moving_in_fixed; }
+  Status status() const { return _status; }
+  bool accepted() const { return _result.accepted != 0; }
+  const prs_point_align_result& result() const { return _result; }
+  const std::vector<uint8_t>& inliers() const { return _inliers; }  // 1 = inlier at the last linearisation
+
+  void compute() {
+    if (!_fixed) throw std::runtime_error("AlignerSliceProcessor3DHIP::compute|ERROR: fixed not set");
+    if (!_moving) throw std::runtime_error("AlignerSliceProcessor3DHIP::compute|ERROR: moving not set");
+    if (!_correspondences) throw std::runtime_error("AlignerSliceProcessor3DHIP::compute|ERROR: correspondences not set");
+    prs_point_align_params p;
+    std::memset(&p, 0, sizeof(p));
+    p.robustifier                  = (int32_t) param_robustifier.value();
+    p.chi_threshold                = param_chi_threshold.value();
+    p.damping                      = param_damping.value();
+    p.max_iterations               = (int32_t) param_max_iterations.value();
+    p.min_num_inliers              = (int32_t) param_min_num_inliers.value();
+    p.min_num_correspondences      = (int32_t) param_min_num_correspondences.value();
+    p.relocalize_min_inliers       = (int32_t) param_relocalize_min_inliers.value();
+    p.relocalize_min_inliers_ratio = param_relocalize_min_inliers_ratio.value();
+    p.relocalize_max_chi_inliers   = param_relocalize_max_chi_inliers.value();
+    std::vector<float> f(_fixed->size() * 3), m(_moving->size() * 3);
+    for (size_t i = 0; i < _fixed->size(); ++i) std::memcpy(&f[3 * i], (*_fixed)[i].coordinates(), 3 * sizeof(float));
+    for (size_t i = 0; i < _moving->size(); ++i) std::memcpy(&m[3 * i], (*_moving)[i].coordinates(), 3 * sizeof(float));
+    _inliers.assign(_correspondences->size(), 0);
+    const int rc = prs_point_align(_ctx->get(), &p, f.data(), (int32_t) _fixed->size(), m.data(), (int32_t) _moving->size(),
+                                   reinterpret_cast<const prs_corr*>(_correspondences->data()), (int32_t) _correspondences->size(),
+                                   _moving_in_fixed, &_result, _inliers.data());
+    if (rc < 0) throw std::runtime_error(std::string("AlignerSliceProcessor3DHIP::compute|ERROR: ") + prs_last_error(_ctx->get()));
+    warn("AlignerSliceProcessor3DHIP::compute", rc);
+    _status = _result.status ? Success : Fail;
+  }
+
+protected:
+  ContextPtr _ctx;
+  const CloudType* _fixed                       = nullptr;
+  const CloudType* _moving                      = nullptr;
+  const CorrespondenceVector* _correspondences = nullptr;
+  float _moving_in_fixed[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
+  Status _status             = Fail;
+  prs_point_align_result _result{};
+  std::vector<uint8_t> _inliers;
 };
 
 }  // namespace proslam_hip

@@ -293,6 +293,32 @@ class DepthBatch(C.Structure):
                 ("fixed_intensity", C.c_void_p), ("n_fixed", C.c_void_p), ("status", C.c_void_p)]
 
 
+ROBUSTIFIER_CLAMP, ROBUSTIFIER_SATURATED = 0, 1  # PRS_ROBUSTIFIER_*
+
+
+class PointAlignParams(C.Structure):
+    """prs_point_align_params"""
+    _fields_ = [("robustifier", C.c_int32), ("chi_threshold", C.c_float), ("damping", C.c_float), ("max_iterations", C.c_int32),
+                ("min_num_inliers", C.c_int32), ("min_num_correspondences", C.c_int32), ("relocalize_min_inliers", C.c_int32),
+                ("relocalize_min_inliers_ratio", C.c_float), ("relocalize_max_chi_inliers", C.c_float), ("linearize_only", C.c_int32),
+                ("parked_per_lane", C.c_int32)]
+
+
+class PointAlignResult(C.Structure):
+    """prs_point_align_result"""
+    _fields_ = [("H", C.c_float * 36), ("b", C.c_float * 6), ("chi_inliers", C.c_float), ("chi_total", C.c_float),
+                ("num_inliers", C.c_int32), ("num_outliers", C.c_int32), ("num_invalid", C.c_int32), ("num_correspondences", C.c_int32),
+                ("status", C.c_int32), ("accepted", C.c_int32), ("iterations", C.c_int32), ("warnings", C.c_int32)]
+
+
+class PointAlignPairs(C.Structure):
+    """prs_point_align_pairs (device pointers)"""
+    _fields_ = [("batch", C.c_int32), ("fixed_stride", C.c_int32), ("moving_stride", C.c_int32), ("corr_stride", C.c_int32),
+                ("fixed", C.c_void_p), ("n_fixed", C.c_void_p), ("moving", C.c_void_p), ("n_moving", C.c_void_p), ("corr", C.c_void_p),
+                ("n_corr", C.c_void_p), ("match_status", C.c_void_p), ("X", C.c_void_p), ("result", C.c_void_p),
+                ("inlier_mask", C.c_void_p)]
+
+
 MODE_ALIGN, MODE_FINDER, MODE_LINEARIZE = 0, 1, 2
 
 # every symbol include/proslam_hip.h declares: (restype, argtypes)
@@ -349,6 +375,9 @@ SYMBOLS = {
     "prs_depth_measurements_batch": (C.c_int, [_vp, C.POINTER(DepthParams), C.POINTER(DepthBatch)]),
     "prs_depth_measurements": (C.c_int, [_vp, C.POINTER(DepthParams), _vp, C.c_int32, C.c_int32, C.c_int32, _vp, _vp, _vp, C.c_int32,
                                          _vp, _vp, _vp, _i32p]),
+    "prs_point_align_batch": (C.c_int, [_vp, C.POINTER(PointAlignParams), C.POINTER(PointAlignPairs)]),
+    "prs_point_align": (C.c_int, [_vp, C.POINTER(PointAlignParams), _vp, C.c_int32, _vp, C.c_int32, _vp, C.c_int32, _vp,
+                                  C.POINTER(PointAlignResult), _vp]),
     "prs_pose_compose_batch": (C.c_int, [_vp, C.c_int32, _vp, _vp, _vp]),
     "prs_motion_predict_batch": (C.c_int, [_vp, C.c_int32, _vp, _vp, _vp]),
     "prs_merge_batch_run": (C.c_int, [_vp, C.POINTER(MergerParams), C.POINTER(MergeBatch)]),

@@ -11,6 +11,20 @@ FACTOR_MONO, FACTOR_DEPTH, FACTOR_STEREO = 2, 3, 4
 
 _SQRT_FLT_MAX = 1.84467e19  # kitti.conf:40 "infinity_depth_meters"
 
+
+def _loop(robustifier, chi_threshold, max_iterations, min_num_correspondences, max_distance, detector, relocalizer):
+    """the loop aligner's group: MultiAligner3DQR min_num_inliers 10 and IterationAlgorithmGN damping 0 in every shipped file.
+    SUBSTITUTION: HBST (srrg_hbst, not in the tree) finds the correspondences in the reference; the brute-force matcher stands in
+    with the detector's maximum_descriptor_distance and the matcher's class-default Lowe ratio 0.9
+    (CF/correspondence_finder_descriptor_based_bruteforce.h:27-31)."""
+    return {"robustifier": robustifier, "chi_threshold": chi_threshold, "damping": 0.0, "max_iterations": max_iterations,
+            "min_num_inliers": 10, "min_num_correspondences": min_num_correspondences, "maximum_descriptor_distance": max_distance,
+            "maximum_distance_ratio_to_second_best": 0.9, "relocalize_min_inliers": detector[0],
+            "relocalize_min_inliers_ratio": detector[1], "relocalize_max_chi_inliers": detector[2],
+            "relocalizer": {"relocalize_min_inliers": relocalizer[0], "relocalize_min_inliers_ratio": relocalizer[1],
+                            "relocalize_max_chi_inliers": relocalizer[2]}}
+
+
 KITTI = {
     "name": "kitti",
     # tests/fixtures.hpp:810-816,1093-1094
@@ -35,6 +49,10 @@ KITTI = {
     "aligner": {"factor_type": FACTOR_STEREO, "diagonal_info": (1.0, 2.0, 1.0), "chi_threshold": 25.0,
                 "enable_inverse_depth_weighting": 1, "damping": 1.0, "max_iterations": 100,
                 "min_num_inliers": 6, "min_num_correspondences": 10},
+    # loop aligner (include/proslam_hip.h prs_point_align_*): kitti.conf:938-978 (MultiLoopDetectorHBST3D -> relocalize_aligner
+    # MultiAligner3DQR "loop_aligner"), :380-408 (AlignerSliceProcessor3D + RobustifierClamp), :877-882 (IterationAlgorithmGN),
+    # :91-110 (MultiRelocalizer3D)
+    "loop": _loop("clamp", 3.0, 100, 30, 25.0, (25, 0.5, 2.0), (25, 0.5, 5.0)),
     "depth": {"min": 4.0, "max": 80.0},
 }
 
@@ -61,6 +79,8 @@ EUROC = {
     "aligner": {"factor_type": FACTOR_STEREO, "diagonal_info": (1.0, 2.0, 1.0), "chi_threshold": 100.0,
                 "enable_inverse_depth_weighting": 1, "damping": 1.0, "max_iterations": 100,
                 "min_num_inliers": 6, "min_num_correspondences": 0},  # euroc.conf:493
+    # euroc.conf: MultiLoopDetectorHBST3D.relocalize_aligner -> AlignerSliceProcessor3D + RobustifierSaturated, MultiRelocalizer3D
+    "loop": _loop("saturated", 1.0, 100, 0, 50.0, (100, 0.9, 0.25), (100, 0.9, 100.0)),
     "depth": {"min": 1.0, "max": 15.0},
 }
 
@@ -84,6 +104,8 @@ ICL = {
                 "enable_inverse_depth_weighting": 0, "damping": 0.1, "max_iterations": 100,
                 "min_num_inliers": 6, "min_num_correspondences": 0,  # icl.conf:584
                 "enable_inlier_only_runs": 1, "keep_only_inlier_correspondences": 1},  # icl.conf:50-53, :57-59
+    # icl.conf:1-29 (loop_aligner), :600-628 (slice + RobustifierClamp), :153-158 (damping), :197-237 (detector), :687-705 (relocalizer)
+    "loop": _loop("clamp", 1.0, 10, 0, 35.0, (50, 0.5, 0.1), (100, 0.5, 1000.0)),
     "depth": {"min": 0.5, "max": 6.0},
     # RawDataPreprocessorMonocularDepth (icl.conf:642-650) and its IntensityFeatureExtractorBinned3D (icl.conf:745-770)
     "rgbd": {"depth_scaling_factor_to_meters": 0.001, "detector_threshold": 5, "enable_non_maximum_suppression": 1,
@@ -110,6 +132,8 @@ TUM = {
                 "enable_inverse_depth_weighting": 0, "damping": 0.1, "max_iterations": 100,
                 "min_num_inliers": 6, "min_num_correspondences": 0,  # tum.conf:260
                 "enable_inlier_only_runs": 1, "keep_only_inlier_correspondences": 1},  # tum.conf:90-93, :97-99
+    # tum.conf: MultiLoopDetectorHBST3D.relocalize_aligner -> AlignerSliceProcessor3D + RobustifierClamp, MultiRelocalizer3D
+    "loop": _loop("clamp", 0.25, 10, 0, 25.0, (40, 0.5, 0.05), (40, 0.5, 100.0)),
     "depth": {"min": 0.5, "max": 6.0},
     # RawDataPreprocessorMonocularDepth (tum.conf:633-640) and its IntensityFeatureExtractorBinned3D (tum.conf:858-883)
     "rgbd": {"depth_scaling_factor_to_meters": 0.001, "detector_threshold": 5, "enable_non_maximum_suppression": 1,

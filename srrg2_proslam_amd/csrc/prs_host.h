@@ -91,6 +91,7 @@ int extract_features_launch(prs_context* ctx, const prs_extractor_params* params
 int describe_selected_launch(prs_context* ctx, const prs_extract_batch* batch, uint32_t* kept);
 int selective_extract_launch(prs_context* ctx, const prs_selective_extractor_params* params, const prs_selective_extract_batch* batch);
 int depth_measurements_launch(prs_context* ctx, const prs_depth_params* params, const prs_depth_batch* batch);
+int point_align_launch(prs_context* ctx, const prs_point_align_params* params, const prs_point_align_pairs* batch);
 int pose_compose_launch(prs_context* ctx, int batch, const float* prediction, const float* X, float* pose_out);
 int motion_predict_launch(prs_context* ctx, int batch, const float* prev2, const float* prev1, float* pred);
 int merge_batch_launch(prs_context* ctx, const prs_merger_params* params, const prs_merge_batch* batch);

@@ -284,3 +284,44 @@ def hot_path_params(conf):
             break
     out["aligner"] = al
     return out
+
+
+_ROBUSTIFIERS = (("RobustifierSaturated", "saturated"), ("RobustifierClamp", "clamp"))
+_VERDICT = ("relocalize_min_inliers", "relocalize_min_inliers_ratio", "relocalize_max_chi_inliers")
+
+
+def loop_params(conf):
+    """the loop aligner's parameter group of a parsed configuration, following the file's own wiring: MultiLoopDetectorHBST3D ->
+    relocalize_aligner (a MultiAligner) -> its AlignerSliceProcessor3D -> robustifier class and chi_threshold; the aligner's solver
+    -> algorithm damping; the detector's maximum_descriptor_distance and verdict thresholds, and MultiRelocalizer3D's thresholds
+    under "relocalizer".  Only fields present in the file are returned."""
+    out = {}
+    detector = next((r for r in conf.records if r.class_name.startswith("MultiLoopDetector")), None)
+    if detector is not None:
+        out.update(_pick(detector, ("maximum_descriptor_distance",) + _VERDICT))
+        aligner = conf.follow(detector, "relocalize_aligner")
+        if aligner is not None:
+            out.update(_pick(aligner, ("max_iterations", "min_num_inliers", "enable_inlier_only_runs", "keep_only_inlier_correspondences")))
+            for ptr in aligner.get("slice_processors", []):
+                sl = conf.deref(ptr)
+                if sl is None or not sl.class_name.startswith("AlignerSliceProcessor3D"):
+                    continue
+                out.update(_pick(sl, ("min_num_correspondences",)))
+                robustifier = conf.follow(sl, "robustifier")
+                if robustifier is not None:
+                    for prefix, kind in _ROBUSTIFIERS:
+                        if robustifier.class_name.startswith(prefix):
+                            out["robustifier"] = kind
+                    if "chi_threshold" in robustifier:
+                        out["chi_threshold"] = robustifier["chi_threshold"]
+                break
+            solver = conf.follow(aligner, "solver")
+            if solver is not None and "max_iterations" in solver:
+                out["solver_iterations"] = solver["max_iterations"]
+            algorithm = conf.follow(aligner, "solver", "algorithm")
+            if algorithm is not None and "damping" in algorithm:
+                out["damping"] = algorithm["damping"]
+    relocalizer = next((r for r in conf.records if r.class_name.startswith("MultiRelocalizer")), None)
+    if relocalizer is not None:
+        out["relocalizer"] = _pick(relocalizer, _VERDICT)
+    return out

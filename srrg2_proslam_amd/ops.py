@@ -681,6 +681,140 @@ def bruteforce_match_batch(ctx, params, clouds):
     return rc
 
 
+# ---- loop aligner (MultiAligner3DQR "loop_aligner" + AlignerSliceProcessor3D, registration/aligner_slice_processor_3d.hpp:7-22) ----
+def point_align_params(loop, linearize_only=0, parked_per_lane=0, **overrides):
+    """prs_point_align_params from a configs.py `loop` group (the loop detector's verdict thresholds); overrides by field name"""
+    p = _lib.PointAlignParams()
+    p.robustifier = _lib.ROBUSTIFIER_SATURATED if loop["robustifier"] == "saturated" else _lib.ROBUSTIFIER_CLAMP
+    p.chi_threshold, p.damping = loop["chi_threshold"], loop["damping"]
+    p.max_iterations, p.min_num_inliers = loop["max_iterations"], loop["min_num_inliers"]
+    p.min_num_correspondences = loop["min_num_correspondences"]
+    p.relocalize_min_inliers = loop["relocalize_min_inliers"]
+    p.relocalize_min_inliers_ratio = loop["relocalize_min_inliers_ratio"]
+    p.relocalize_max_chi_inliers = loop["relocalize_max_chi_inliers"]
+    p.linearize_only, p.parked_per_lane = int(linearize_only), int(parked_per_lane)
+    for k, v in overrides.items():
+        setattr(p, k, v)
+    return p
+
+
+def _result_dict(r):
+    return dict(H=np.ctypeslib.as_array(r.H).reshape(6, 6).copy(), b=np.ctypeslib.as_array(r.b).copy(), chi_inliers=np.float32(r.chi_inliers),
+                chi_total=np.float32(r.chi_total), num_inliers=r.num_inliers, num_outliers=r.num_outliers, num_invalid=r.num_invalid,
+                num_correspondences=r.num_correspondences, status=r.status, accepted=r.accepted, iterations=r.iterations, warnings=r.warnings)
+
+
+def point_align(ctx, params, fixed_xyz, moving_xyz, corr, X_init, with_mask=True):
+    """host arrays, one pair -> (X [4, 4], result dict, inlier mask [n] | None, status).  corr: CORR_DTYPE or [n, 2] (fixed, moving)"""
+    f, m = _np(fixed_xyz, np.float32, (-1, 3)), _np(moving_xyz, np.float32, (-1, 3))
+    c = _corr_rows(corr)
+    X = _np(X_init, np.float32, (4, 4)).copy()
+    res = _lib.PointAlignResult()
+    mask = np.zeros(max(len(c), 1), np.uint8) if with_mask else None
+    rc = _lib.load().prs_point_align(ctx._h, C.byref(params), _p(f), f.shape[0], _p(m), m.shape[0], _p(c), len(c), _p(X), C.byref(res),
+                                     _p(mask) if with_mask else None)
+    _check(ctx, rc, "prs_point_align")
+    return X, _result_dict(res), (mask[: len(c)].copy() if with_mask else None), rc
+
+
+def _corr_rows(corr):
+    corr = np.asarray(corr)
+    out = np.zeros(len(corr), dtype=CORR_DTYPE)
+    if len(corr):
+        if corr.dtype.names:
+            out["fixed_idx"], out["moving_idx"] = corr["fixed_idx"], corr["moving_idx"]
+        else:
+            out["fixed_idx"], out["moving_idx"] = corr[:, 0], corr[:, 1]
+    return out
+
+
+class PointAlignBatch:
+    """B (fixed, moving) point-cloud pairs resident in HBM, their correspondences, estimates and results.  `corr`, `n_corr` and
+    `match_status` may be another batch's tensors (LoopClosureBatch points them at the brute-force matcher's outputs)."""
+
+    def __init__(self, device, batch, fixed_stride, moving_stride, corr_stride=None, with_mask=True, with_status=False, corr=None,
+                 n_corr=None, match_status=None):
+        import torch
+        dev = torch.device("cuda", device)
+        self.batch, self.fixed_stride, self.moving_stride = int(batch), int(fixed_stride), int(moving_stride)
+        self.corr_stride = int(corr_stride if corr_stride is not None else min(fixed_stride, moving_stride))
+        self.fixed = torch.zeros((batch, fixed_stride, 4), dtype=torch.float32, device=dev)
+        self.moving = torch.zeros((batch, moving_stride, 4), dtype=torch.float32, device=dev)
+        self.n_fixed = torch.zeros((batch,), dtype=torch.int32, device=dev)
+        self.n_moving = torch.zeros((batch,), dtype=torch.int32, device=dev)
+        self.corr = corr if corr is not None else torch.zeros((batch, self.corr_stride, 3), dtype=torch.int32, device=dev)
+        self.n_corr = n_corr if n_corr is not None else torch.zeros((batch,), dtype=torch.int32, device=dev)
+        self.match_status = match_status if match_status is not None else (
+            torch.zeros((batch,), dtype=torch.int32, device=dev) if with_status else None)
+        self.X = torch.eye(4, dtype=torch.float32, device=dev).reshape(1, 16).repeat(batch, 1).contiguous()
+        self.result = torch.zeros((batch, C.sizeof(_lib.PointAlignResult) // 4), dtype=torch.int32, device=dev)
+        self.inlier_mask = torch.zeros((batch, self.corr_stride), dtype=torch.uint8, device=dev) if with_mask else None
+
+    def upload(self, b, fixed_xyz, moving_xyz, corr=None, X_init=None):
+        import torch
+        dev = self.fixed.device
+        f, m = _np(fixed_xyz, np.float32, (-1, 3)), _np(moving_xyz, np.float32, (-1, 3))
+        if len(f):
+            self.fixed[b, : len(f), :3] = torch.from_numpy(f).to(dev)
+        if len(m):
+            self.moving[b, : len(m), :3] = torch.from_numpy(m).to(dev)
+        self.n_fixed[b], self.n_moving[b] = len(f), len(m)
+        if corr is not None:
+            c = _corr_rows(corr)
+            if len(c):
+                self.corr[b, : len(c)] = torch.from_numpy(c.view(np.int32).reshape(-1, 3).copy()).to(dev)
+            self.n_corr[b] = len(c)
+        self.X[b] = torch.from_numpy(_np(np.eye(4) if X_init is None else X_init, np.float32, (16,))).to(dev)
+
+    def descriptor(self):
+        d = _lib.PointAlignPairs()
+        d.batch, d.fixed_stride, d.moving_stride, d.corr_stride = self.batch, self.fixed_stride, self.moving_stride, self.corr_stride
+        d.fixed, d.n_fixed, d.moving, d.n_moving = self.fixed.data_ptr(), self.n_fixed.data_ptr(), self.moving.data_ptr(), self.n_moving.data_ptr()
+        d.corr, d.n_corr = self.corr.data_ptr(), self.n_corr.data_ptr()
+        d.match_status = self.match_status.data_ptr() if self.match_status is not None else None
+        d.X, d.result = self.X.data_ptr(), self.result.data_ptr()
+        d.inlier_mask = self.inlier_mask.data_ptr() if self.inlier_mask is not None else None
+        return d
+
+    def X_of(self, b):
+        return self.X[b].cpu().numpy().reshape(4, 4).copy()
+
+    def result_of(self, b):
+        raw = self.result[b].cpu().numpy().copy()
+        return _result_dict(_lib.PointAlignResult.from_buffer_copy(raw.tobytes()))
+
+    def mask_of(self, b):
+        n = int(self.n_corr[b].item())
+        return self.inlier_mask[b, : max(n, 0)].cpu().numpy().copy()
+
+
+def point_align_batch(ctx, params, pairs):
+    """enqueue the loop aligner for every pair of the batch on the context stream (asynchronous)"""
+    d = pairs.descriptor()
+    rc = _lib.load().prs_point_align_batch(ctx._h, C.byref(params), C.byref(d))
+    _check(ctx, rc, "prs_point_align_batch")
+    return rc
+
+
+class LoopClosureBatch:
+    """descriptors -> brute-force matches -> registered pose and verdict for B (query, reference) pairs, device-resident: the
+    matcher's correspondences, counts and status words feed the aligner directly (fixed = query, moving = reference), both
+    enqueued back to back on the context stream with no host round trip."""
+
+    def __init__(self, device, batch, fixed_stride, moving_stride, with_mask=True, candidate_capacity=0):
+        self.clouds = BruteforceClouds(device, batch, fixed_stride, moving_stride, candidate_capacity)
+        self.pairs = PointAlignBatch(device, batch, fixed_stride, moving_stride, corr_stride=self.clouds.out_stride, with_mask=with_mask,
+                                     corr=self.clouds.matches, n_corr=self.clouds.n_matches, match_status=self.clouds.status)
+
+    def upload(self, b, fixed_xyz, fixed_desc, moving_xyz, moving_desc, X_init=None):
+        self.clouds.upload(b, fixed_desc, moving_desc)
+        self.pairs.upload(b, fixed_xyz, moving_xyz, None, X_init)
+
+    def run(self, ctx, matcher_params, align_params):
+        bruteforce_match_batch(ctx, matcher_params, self.clouds)
+        return point_align_batch(ctx, align_params, self.pairs)
+
+
 # ---- landmark estimators + projective mergers (mapping/mergers, mapping/landmarks) ----
 EST_WEIGHTED_MEAN, EST_EKF, EST_SMOOTHER = 0, 1, 2
 MERGER_STEREO_TRIANGULATION, MERGER_STEREO_EKF, MERGER_DEPTH_EKF = 0, 1, 2
