@@ -110,7 +110,8 @@ PRS_API int prs_version(void);
  * selective extractor: prs_selective_extractor_params, prs_selective_extract_batch and their two entry points, no existing struct changed; 104 adds
  * the RGB-D preprocessor: prs_depth_params, prs_depth_batch and their two entry points, no existing struct changed; the loop aligner's
  * prs_point_align_params, prs_point_align_pairs, prs_point_align_result and its two entry points came later under the same version:
- * new structs and new entry points only, nothing a 104 client passes changed).  Callers memset() parameter structs before
+ * new structs and new entry points only, nothing a 104 client passes changed; so did the loop detector's place database:
+ * prs_place_db, prs_place_params, prs_place_queries, prs_place_pairs and the prs_place_* entry points).  Callers memset() parameter structs before
  * filling them, so that fields they do not know select the shipped defaults (all zero). */
 #define PRS_ABI_VERSION 104
 PRS_API int prs_abi_check(int32_t header_version, uint64_t sizeof_stereo_params, uint64_t sizeof_pcf_params, uint64_t sizeof_aligner_params,
@@ -987,8 +988,8 @@ PRS_API int prs_depth_measurements(prs_context* ctx, const prs_depth_params* par
  * replaces MultiAligner3DQR "loop_aligner" with one AlignerSliceProcessor3D (registration/aligner_slice_processor_3d.hpp:7-22:
  * SE3Point2PointErrorFactor, information I3; registered at registration/instances.cpp:28,52), the aligner every shipped .conf wires
  * in as MultiLoopDetectorHBST3D.relocalize_aligner (kitti.conf:938-978), and the accept / reject verdict of the loop detector and
- * MultiRelocalizer3D (parameter comments kitti.conf:966-977).  HBST candidate search, pose-graph insertion and the closure merger
- * are not served.
+ * MultiRelocalizer3D (parameter comments kitti.conf:966-977).  The candidate search in front of it is the place database below;
+ * pose-graph insertion and the closure merger are not served.
  *
  * The factor, the robustifiers, the loop and the verdict live in srrg2_solver / srrg2_slam_interfaces, not in the tree
  * (BUILD-DEFINED, stated like rows a13 / a14 of SURVEY.md Appendix A):
@@ -1079,6 +1080,100 @@ PRS_API int prs_point_align_batch(prs_context* ctx, const prs_point_align_params
 PRS_API int prs_point_align(prs_context* ctx, const prs_point_align_params* params, const float* fixed_xyz, int32_t n_fixed,
                             const float* moving_xyz, int32_t n_moving, const prs_corr* corr, int32_t n_corr, float* X16,
                             prs_point_align_result* result, uint8_t* inlier_mask);
+
+/* ================================================================================================
+ * Loop detector: place database and candidate search (the step in front of the brute-force matcher + loop aligner chain)
+ * replaces CorrespondenceFinderHBST_::compute (registration/correspondence_finders/correspondence_finder_hbst.cpp:5-91, correspondences
+ * :95-127), the finder of the MultiLoopDetectorHBST3D every shipped .conf wires in (kitti.conf:938-978), and its addPreviousQuery.
+ *
+ * SUBSTITUTION (BUILD-DEFINED): the reference searches an srrg_hbst::BinaryTree256 (leaf size, depth and partitioning parameters),
+ * an external library that is not in the tree.  This build searches the database EXHAUSTIVELY: every stored descriptor within the
+ * threshold counts, a superset of what any tree returns.  The search is O(database size) per query, where a tree is sublinear, and
+ * match counts and correspondence counts are >= (in general different from) HBST's.  maximum_leaf_size, maximum_depth and
+ * maximum_partitioning are read from the configurations but unused.  Everything around database.match is restated exactly:
+ *   Valid        only query points whose status is Valid take part (:57-62); `valid` [n] nonzero = Valid, NULL = all Valid.
+ *   index_query  the number of stored maps for a new map, the stored index when the query's graph id is in the database (:47-55).
+ *   match        a (query point, stored descriptor) pair with Hamming distance d < maximum_descriptor_distance (strict).
+ *   age          std::fabs(index_query - reference) > minimum_age_difference_to_candidates with uint64_t operands (:73-74): when a
+ *                re-queried map is older than a reference the difference wraps around and the rule passes.
+ *   inliers      number_of_matches > relocalize_min_inliers (strict, :77), the count over every matching pair of the map (a
+ *                negative relocalize_min_inliers compares as a huge unsigned value: nothing passes).
+ *   candidates   in ascending reference (map) index (HBST's MatchVectorMap order is not in the tree: BUILD-DEFINED).
+ *   correspondences of a candidate: for each stored descriptor of the map that matched, the query point with the smallest distance,
+ *                the earlier query point on a tie (strict < in query order, :101-119): (fixed_idx = query point index, moving_idx
+ *                = the reference's point index, response = distance), in ascending moving_idx.  The ambiguity filter
+ *                object_references.size() == 1 is a no-op: every shipped .conf has maximum_distance_for_merge 0, nothing is merged.
+ * Storage: a map keeps its Valid descriptors (and xyz) in point order, padded to a multiple of 16 rows.  Adding a graph id that is
+ * already stored is refused (PRS_ERR_RANGE).  Status per query (status[]): PRS_WARN_EMPTY_INPUT for n_query == 0 (the reference's
+ * "query descriptor vector is empty", :13-18: no candidates); PRS_ERR_RANGE for a negative graph id or n_query; PRS_ERR_CAPACITY
+ * for n_query > query_stride (no candidates) or for more candidates than max_candidates (the first max_candidates are written).
+ * ============================================================================================== */
+typedef struct prs_place_db prs_place_db;
+
+typedef struct {
+  float maximum_descriptor_distance;              /* match iff distance < this */
+  uint32_t minimum_age_difference_to_candidates;  /* kitti 10, icl 1, euroc 5 */
+  int32_t relocalize_min_inliers;                 /* candidate iff number of matches > this */
+  int32_t max_candidates;                         /* candidate slots per query, [1, 256] */
+} prs_place_params;
+
+/* device-resident batch of B queries and their outputs */
+typedef struct {
+  int32_t batch;
+  int32_t query_stride;        /* rows per query slot, <= 65536 */
+  const uint8_t* desc;         /* [batch][query_stride][32] */
+  const uint8_t* valid;        /* optional [batch][query_stride]: nonzero = POINT_STATUS::Valid */
+  const float* xyz;            /* [batch][query_stride][4] (x, y, z, -): read by prs_place_gather_pairs only */
+  const int32_t* n_query;      /* [batch] */
+  const int64_t* graph_id;     /* [batch] graph id of the query's local map (>= 0) */
+  int32_t count_stride;        /* >= stored maps */
+  uint32_t* match_counts;      /* out [batch][count_stride]: matches per stored map, before the age and inlier rules */
+  int32_t key_stride;          /* >= stored rows (prs_place_db_size) */
+  uint32_t* best_keys;         /* out [batch][key_stride] per stored row: distance << 23 | query point index of its best match, ~0 none */
+  int32_t corr_stride;         /* >= the largest stored map (prs_place_db_size max_map_rows) */
+  int32_t* candidates;         /* out [batch][max_candidates]: map indices, ascending, -1 past n_candidates */
+  int32_t* n_candidates;       /* out [batch] */
+  prs_corr* corr;              /* out [batch][max_candidates][corr_stride] */
+  int32_t* n_corr;             /* out [batch][max_candidates] */
+  int32_t* status;             /* out [batch] */
+  int64_t* index_query;        /* optional out [batch] */
+} prs_place_queries;
+
+/* the pair slots (query b, candidate k) -> slot b * max_candidates + k of a loop-closure batch (prs_bruteforce_batch +
+ * prs_point_align_pairs): fixed = the query's Valid points in point order, moving = the candidate map's stored points, X = identity;
+ * a slot without a candidate gets n_fixed = n_moving = 0 (a query with PRS_ERR_CAPACITY for too many candidates fills its slots) */
+typedef struct {
+  int32_t fixed_stride;        /* >= query_stride */
+  int32_t moving_stride;       /* >= the largest stored map */
+  float* fixed_xyz;            /* [slots][fixed_stride][4] */
+  uint8_t* fixed_desc;         /* [slots][fixed_stride][32] */
+  int32_t* n_fixed;            /* [slots] */
+  float* moving_xyz;           /* [slots][moving_stride][4] */
+  uint8_t* moving_desc;        /* [slots][moving_stride][32] */
+  int32_t* n_moving;           /* [slots] */
+  float* X;                    /* [slots][16] */
+} prs_place_pairs;
+
+PRS_API int prs_place_db_create(prs_context* ctx, prs_place_db** db);
+PRS_API int prs_place_db_destroy(prs_place_db* db);
+PRS_API int prs_place_db_clear(prs_place_db* db);
+/* device capacity for `maps` maps and `rows` stored rows (pads included); prs_place_db_add grows it on demand */
+PRS_API int prs_place_db_reserve(prs_place_db* db, int64_t maps, int64_t rows);
+PRS_API int prs_place_db_size(const prs_place_db* db, int32_t* maps, int32_t* rows, int32_t* max_map_rows);
+/* addPreviousQuery: stores a local map (host pointers: xyz [n][3] or NULL, desc [n][32], valid [n] or NULL) as map index = the
+ * number of maps stored before it; uploads and synchronises */
+PRS_API int prs_place_db_add(prs_place_db* db, int64_t graph_id, const float* xyz, const uint8_t* desc, const uint8_t* valid, int32_t n);
+/* device pointers, asynchronous on the context's stream: three kernel launches, no allocation and no synchronisation
+ * (graph-capturable; a captured query holds the database's buffers and size as they were at capture) */
+PRS_API int prs_place_query_batch(prs_place_db* db, const prs_place_params* params, const prs_place_queries* queries);
+/* host pointers, one query: candidates [max_candidates], corr [max_candidates][corr_stride], n_corr [max_candidates], match_counts
+ * [maps] or NULL.  Returns the query's status. */
+PRS_API int prs_place_query(prs_place_db* db, const prs_place_params* params, int64_t graph_id, const uint8_t* desc, const uint8_t* valid,
+                            int32_t n, int32_t* candidates, int32_t* n_candidates, prs_corr* corr, int32_t corr_stride, int32_t* n_corr,
+                            uint32_t* match_counts);
+/* device pointers, asynchronous: after prs_place_query_batch, fill the pair slots of a loop-closure batch (one kernel launch) */
+PRS_API int prs_place_gather_pairs(prs_place_db* db, const prs_place_params* params, const prs_place_queries* queries,
+                                   const prs_place_pairs* pairs);
 
 #ifdef __cplusplus
 }

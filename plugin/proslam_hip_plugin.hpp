@@ -20,6 +20,8 @@
 //     (sensor_processing/raw_data_preprocessor_monocular_depth.{h,cpp})
 //   MultiAligner3DQR "loop_aligner" + AlignerSliceProcessor3D      -> AlignerSliceProcessor3DHIP
 //     (registration/aligner_slice_processor_3d.hpp:7-22, the relocalize_aligner of the loop detector)
+//   CorrespondenceFinderHBST_ (the loop detector's candidate search) -> CorrespondenceFinderPlaceHIP
+//     (registration/correspondence_finders/correspondence_finder_hbst.{h,cpp}; exhaustive search in place of the HBST tree)
 //
 // When the srrg2 headers are available the same bodies become real plugin subclasses: see
 // INTEGRATION.md for the BOSS_REGISTER_CLASS adapters.  Points are AoS like the reference's
@@ -1137,6 +1139,95 @@ protected:
   Status _status             = Fail;
   prs_point_align_result _result{};
   std::vector<uint8_t> _inliers;
+};
+
+// ---- loop detector: candidate search --------------------------------------------------------------
+// CorrespondenceFinderHBST_ (correspondence_finder_hbst.cpp:5-127) over the device place database: compute() queries every earlier local
+// map, indices() lists the candidates (ascending), correspondences(i) holds candidate i's (query, reference, distance) triples, and
+// addPreviousQuery() stores the last query's local map.  SUBSTITUTION: the HBST tree is searched exhaustively (include/proslam_hip.h);
+// its leaf size, depth and partitioning parameters do not exist here.  Defaults: kitti.conf:938-978.
+template <int Dim_>
+class CorrespondenceFinderPlaceHIP {
+public:
+  using CloudType = PointIntensityDescriptorVectorCloud<Dim_>;
+  explicit CorrespondenceFinderPlaceHIP(ContextPtr ctx) : _ctx(std::move(ctx)) {
+    const int rc = prs_place_db_create(_ctx->get(), &_db);
+    if (rc != PRS_OK) throw std::runtime_error(std::string("CorrespondenceFinderPlaceHIP|ERROR: ") + prs_status_string(rc));
+  }
+  ~CorrespondenceFinderPlaceHIP() { prs_place_db_destroy(_db); }
+  CorrespondenceFinderPlaceHIP(const CorrespondenceFinderPlaceHIP&) = delete;
+  CorrespondenceFinderPlaceHIP& operator=(const CorrespondenceFinderPlaceHIP&) = delete;
+  PropertyFloat param_maximum_descriptor_distance{25.0f};
+  PropertyUnsignedInt param_minimum_age_difference_to_candidates{10};
+  PropertyInt param_relocalize_min_inliers{25};
+  PropertyInt param_max_candidates{16};  // candidate slots per query (this build: a fixed-size output)
+
+  // the local map's graph identifier and its points (status Valid = point.valid)
+  void setCurrentLocalMapAndPoints(int64_t graph_id_, const CloudType* query_local_map_points_) {
+    _graph_id = graph_id_;
+    _query    = query_local_map_points_;
+  }
+
+  void compute() {
+    _indices.clear();
+    _correspondences.clear();
+    if (!_query || _graph_id < 0) throw std::runtime_error("CorrespondenceFinderPlaceHIP::compute|ERROR: no local map set");
+    prs_place_params p;
+    std::memset(&p, 0, sizeof(p));
+    p.maximum_descriptor_distance          = param_maximum_descriptor_distance.value();
+    p.minimum_age_difference_to_candidates = param_minimum_age_difference_to_candidates.value();
+    p.relocalize_min_inliers               = param_relocalize_min_inliers.value();
+    p.max_candidates                       = param_max_candidates.value();
+    const size_t n = _query->size();
+    _desc.resize(n * PRS_DESC_BYTES);
+    _xyz.assign(n * 3, 0.0f);
+    _valid.resize(n);
+    for (size_t i = 0; i < n; ++i) {
+      std::memcpy(&_desc[i * PRS_DESC_BYTES], (*_query)[i].descriptor(), PRS_DESC_BYTES);
+      std::memcpy(&_xyz[i * 3], (*_query)[i].coordinates(), (Dim_ < 3 ? Dim_ : 3) * sizeof(float));
+      _valid[i] = (*_query)[i].valid ? 1 : 0;
+    }
+    int32_t maps = 0, rows = 0, big = 0;
+    prs_place_db_size(_db, &maps, &rows, &big);
+    const int32_t stride = big > 0 ? big : 1;
+    std::vector<int32_t> cand((size_t) p.max_candidates), ncorr((size_t) p.max_candidates);
+    std::vector<Correspondence> corr((size_t) p.max_candidates * (size_t) stride);
+    int32_t nc = 0;
+    const int rc = prs_place_query(_db, &p, _graph_id, _desc.data(), _valid.data(), (int32_t) n, cand.data(), &nc,
+                                   reinterpret_cast<prs_corr*>(corr.data()), stride, ncorr.data(), nullptr);
+    if (rc < 0) throw std::runtime_error(std::string("CorrespondenceFinderPlaceHIP::compute|ERROR: ") + prs_last_error(_ctx->get()));
+    if (rc & PRS_WARN_EMPTY_INPUT) std::cerr << "MultiLoopDetectorHBST::compute|WARNING: query descriptor vector is empty" << std::endl;
+    _query_stored = rc & PRS_WARN_EMPTY_INPUT ? false : true;
+    for (int32_t k = 0; k < nc; ++k) {
+      _indices.push_back((size_t) cand[(size_t) k]);
+      const Correspondence* first = corr.data() + (size_t) k * (size_t) stride;
+      _correspondences.emplace_back(first, first + ncorr[(size_t) k]);
+    }
+  }
+
+  // stores the last queried local map (graph id -> the next database index); a graph id already stored is left as it is
+  void addPreviousQuery() {
+    if (!_query_stored) return;
+    _query_stored = false;
+    const int rc = prs_place_db_add(_db, _graph_id, _xyz.data(), _desc.data(), _valid.data(), (int32_t) _valid.size());
+    if (rc == PRS_ERR_RANGE) return;
+    if (rc < 0) throw std::runtime_error(std::string("CorrespondenceFinderPlaceHIP::addPreviousQuery|ERROR: ") + prs_last_error(_ctx->get()));
+  }
+
+  const std::vector<size_t>& indices() const { return _indices; }
+  // candidate i of indices(): correspondences (fixed = query point, moving = reference point, response = distance)
+  CorrespondenceVector correspondences(size_t i) const { return _correspondences.at(i); }
+
+protected:
+  ContextPtr _ctx;
+  prs_place_db* _db    = nullptr;
+  int64_t _graph_id    = -1;
+  const CloudType* _query = nullptr;
+  bool _query_stored   = false;
+  std::vector<uint8_t> _desc, _valid;
+  std::vector<float> _xyz;
+  std::vector<size_t> _indices;
+  std::vector<CorrespondenceVector> _correspondences;
 };
 
 }  // namespace proslam_hip

@@ -319,6 +319,28 @@ class PointAlignPairs(C.Structure):
                 ("inlier_mask", C.c_void_p)]
 
 
+class PlaceParams(C.Structure):
+    """prs_place_params"""
+    _fields_ = [("maximum_descriptor_distance", C.c_float), ("minimum_age_difference_to_candidates", C.c_uint32),
+                ("relocalize_min_inliers", C.c_int32), ("max_candidates", C.c_int32)]
+
+
+class PlaceQueries(C.Structure):
+    """prs_place_queries (device pointers)"""
+    _fields_ = [("batch", C.c_int32), ("query_stride", C.c_int32), ("desc", C.c_void_p), ("valid", C.c_void_p), ("xyz", C.c_void_p),
+                ("n_query", C.c_void_p), ("graph_id", C.c_void_p), ("count_stride", C.c_int32), ("match_counts", C.c_void_p),
+                ("key_stride", C.c_int32), ("best_keys", C.c_void_p), ("corr_stride", C.c_int32), ("candidates", C.c_void_p),
+                ("n_candidates", C.c_void_p), ("corr", C.c_void_p), ("n_corr", C.c_void_p), ("status", C.c_void_p),
+                ("index_query", C.c_void_p)]
+
+
+class PlacePairs(C.Structure):
+    """prs_place_pairs (device pointers)"""
+    _fields_ = [("fixed_stride", C.c_int32), ("moving_stride", C.c_int32), ("fixed_xyz", C.c_void_p), ("fixed_desc", C.c_void_p),
+                ("n_fixed", C.c_void_p), ("moving_xyz", C.c_void_p), ("moving_desc", C.c_void_p), ("n_moving", C.c_void_p),
+                ("X", C.c_void_p)]
+
+
 MODE_ALIGN, MODE_FINDER, MODE_LINEARIZE = 0, 1, 2
 
 # every symbol include/proslam_hip.h declares: (restype, argtypes)
@@ -378,6 +400,15 @@ SYMBOLS = {
     "prs_point_align_batch": (C.c_int, [_vp, C.POINTER(PointAlignParams), C.POINTER(PointAlignPairs)]),
     "prs_point_align": (C.c_int, [_vp, C.POINTER(PointAlignParams), _vp, C.c_int32, _vp, C.c_int32, _vp, C.c_int32, _vp,
                                   C.POINTER(PointAlignResult), _vp]),
+    "prs_place_db_create": (C.c_int, [_vp, C.POINTER(C.c_void_p)]),
+    "prs_place_db_destroy": (C.c_int, [_vp]),
+    "prs_place_db_clear": (C.c_int, [_vp]),
+    "prs_place_db_reserve": (C.c_int, [_vp, C.c_int64, C.c_int64]),
+    "prs_place_db_size": (C.c_int, [_vp, _i32p, _i32p, _i32p]),
+    "prs_place_db_add": (C.c_int, [_vp, C.c_int64, _vp, _vp, _vp, C.c_int32]),
+    "prs_place_query_batch": (C.c_int, [_vp, C.POINTER(PlaceParams), C.POINTER(PlaceQueries)]),
+    "prs_place_query": (C.c_int, [_vp, C.POINTER(PlaceParams), C.c_int64, _vp, _vp, C.c_int32, _vp, _i32p, _vp, C.c_int32, _vp, _vp]),
+    "prs_place_gather_pairs": (C.c_int, [_vp, C.POINTER(PlaceParams), C.POINTER(PlaceQueries), C.POINTER(PlacePairs)]),
     "prs_pose_compose_batch": (C.c_int, [_vp, C.c_int32, _vp, _vp, _vp]),
     "prs_motion_predict_batch": (C.c_int, [_vp, C.c_int32, _vp, _vp, _vp]),
     "prs_merge_batch_run": (C.c_int, [_vp, C.POINTER(MergerParams), C.POINTER(MergeBatch)]),

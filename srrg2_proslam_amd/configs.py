@@ -25,6 +25,17 @@ def _loop(robustifier, chi_threshold, max_iterations, min_num_correspondences, m
                             "relocalize_max_chi_inliers": relocalizer[2]}}
 
 
+
+def _place(max_distance, minimum_age, min_inliers):
+    """the loop detector's candidate search (include/proslam_hip.h prs_place_*): MultiLoopDetectorHBST3D's
+    maximum_descriptor_distance, minimum_age_difference_to_candidates and relocalize_min_inliers.  SUBSTITUTION: the HBST tree
+    (srrg_hbst, not in the tree) is searched exhaustively; its leaf size 100, depth 16 and partitioning 0.1 (every shipped file) are
+    read but unused, and maximum_distance_for_merge is 0 everywhere (nothing merged)."""
+    return {"maximum_descriptor_distance": max_distance, "minimum_age_difference_to_candidates": minimum_age,
+            "relocalize_min_inliers": min_inliers, "maximum_leaf_size": 100, "maximum_depth": 16, "maximum_partitioning": 0.1,
+            "maximum_distance_for_merge": 0}
+
+
 KITTI = {
     "name": "kitti",
     # tests/fixtures.hpp:810-816,1093-1094
@@ -53,6 +64,7 @@ KITTI = {
     # MultiAligner3DQR "loop_aligner"), :380-408 (AlignerSliceProcessor3D + RobustifierClamp), :877-882 (IterationAlgorithmGN),
     # :91-110 (MultiRelocalizer3D)
     "loop": _loop("clamp", 3.0, 100, 30, 25.0, (25, 0.5, 2.0), (25, 0.5, 5.0)),
+    "place": _place(25.0, 10, 25),  # kitti.conf:938-978
     "depth": {"min": 4.0, "max": 80.0},
 }
 
@@ -81,6 +93,7 @@ EUROC = {
                 "min_num_inliers": 6, "min_num_correspondences": 0},  # euroc.conf:493
     # euroc.conf: MultiLoopDetectorHBST3D.relocalize_aligner -> AlignerSliceProcessor3D + RobustifierSaturated, MultiRelocalizer3D
     "loop": _loop("saturated", 1.0, 100, 0, 50.0, (100, 0.9, 0.25), (100, 0.9, 100.0)),
+    "place": _place(50.0, 5, 100),  # euroc.conf: MultiLoopDetectorHBST3D
     "depth": {"min": 1.0, "max": 15.0},
 }
 
@@ -106,6 +119,7 @@ ICL = {
                 "enable_inlier_only_runs": 1, "keep_only_inlier_correspondences": 1},  # icl.conf:50-53, :57-59
     # icl.conf:1-29 (loop_aligner), :600-628 (slice + RobustifierClamp), :153-158 (damping), :197-237 (detector), :687-705 (relocalizer)
     "loop": _loop("clamp", 1.0, 10, 0, 35.0, (50, 0.5, 0.1), (100, 0.5, 1000.0)),
+    "place": _place(35.0, 1, 50),  # icl.conf:197-240
     "depth": {"min": 0.5, "max": 6.0},
     # RawDataPreprocessorMonocularDepth (icl.conf:642-650) and its IntensityFeatureExtractorBinned3D (icl.conf:745-770)
     "rgbd": {"depth_scaling_factor_to_meters": 0.001, "detector_threshold": 5, "enable_non_maximum_suppression": 1,
@@ -134,6 +148,7 @@ TUM = {
                 "enable_inlier_only_runs": 1, "keep_only_inlier_correspondences": 1},  # tum.conf:90-93, :97-99
     # tum.conf: MultiLoopDetectorHBST3D.relocalize_aligner -> AlignerSliceProcessor3D + RobustifierClamp, MultiRelocalizer3D
     "loop": _loop("clamp", 0.25, 10, 0, 25.0, (40, 0.5, 0.05), (40, 0.5, 100.0)),
+    "place": _place(25.0, 1, 40),  # tum.conf: MultiLoopDetectorHBST3D
     "depth": {"min": 0.5, "max": 6.0},
     # RawDataPreprocessorMonocularDepth (tum.conf:633-640) and its IntensityFeatureExtractorBinned3D (tum.conf:858-883)
     "rgbd": {"depth_scaling_factor_to_meters": 0.001, "detector_threshold": 5, "enable_non_maximum_suppression": 1,

@@ -24,6 +24,7 @@
 #include <type_traits>
 
 #include "prs_device.h"
+#include "prs_hamming_tile.h"
 #include "prs_host.h"
 
 namespace prs {
@@ -529,7 +530,6 @@ __global__ __launch_bounds__(THREADS, 4) void bruteforce_kernel(const BfArgs a) 
 // Candidates go through the same global counters / bitmaps / list as the split popcount shape (MODE kBfDense);
 // bruteforce_kernel<.., kBfRegister> then registers them pair by pair.  Built for one candidate per fixed point (uniform random
 // rows): the entries it parks are re-scored from memory at a flush behind barriers, which real descriptors make the bulk of its time.
-typedef int bf_v4i __attribute__((ext_vector_type(4)));
 constexpr int kBfmThreads  = 512;                                  // 8 waves; two workgroups per CU: one scores while the other flushes / waits at its barrier
 constexpr int kBfmRowsWave = 64;                                   // fixed rows per wave (4 A tiles)
 constexpr int kBfmRowsWg   = kBfmRowsWave * (kBfmThreads / 64);    // 1024 fixed rows per workgroup
@@ -702,24 +702,12 @@ __global__ __launch_bounds__(kBfmThreads, 4) void bruteforce_dense_mfma_kernel(c
   sink.cap     = a.cap;
 
   if (tid < 16) {
-    uint32_t v01 = 0, vpm = 0;
-#pragma unroll
-    for (int b = 0; b < 4; ++b) {
-      v01 |= ((tid >> b) & 1 ? 0x01u : 0x00u) << (8 * b);
-      vpm |= ((tid >> b) & 1 ? 0xffu : 0x01u) << (8 * b);
-    }
+    uint32_t v01, vpm;
+    hamming_lut_entry(tid, v01, vpm);
     lut_a[tid] = v01;
     lut_b[tid] = vpm;
   }
   __syncthreads();
-  auto expand16 = [](const uint32_t* lut, const uint32_t bits16) -> bf_v4i {
-    bf_v4i v;
-    v.x = (int) lut[bits16 & 15u];
-    v.y = (int) lut[(bits16 >> 4) & 15u];
-    v.z = (int) lut[(bits16 >> 8) & 15u];
-    v.w = (int) lut[(bits16 >> 12) & 15u];
-    return v;
-  };
   // ---- this wave's fixed rows: A[t][kb] = bits [64 kb + 16 lg, +16) of row row0 + 16 t + li (rows past the end: zeros) ----
   // Thread-index values are RE-DERIVED where the chunk loop uses them (the lane from v_mbcnt behind a volatile asm the compiler cannot
   // hoist, the wave in a scalar register): kept live beside the 64 registers of A they were spilled, and a reload from scratch ahead of
@@ -750,7 +738,7 @@ __global__ __launch_bounds__(kBfmThreads, 4) void bruteforce_dense_mfma_kernel(c
       const bool live = row0 + 16 * t + (l & 15) < nf;
 #pragma unroll
       for (int kb = 0; kb < 4; ++kb) {
-        A[t][kb] = expand16(lut_a, live ? (w[t][kb] >> (16 * ((l >> 4) & 1))) & 0xffffu : 0u);
+        A[t][kb] = hamming_expand16(lut_a, live ? (w[t][kb] >> (16 * ((l >> 4) & 1))) & 0xffffu : 0u);
       }
     }
   };
@@ -773,8 +761,8 @@ __global__ __launch_bounds__(kBfmThreads, 4) void bruteforce_dense_mfma_kernel(c
   auto stage = [&](const int c, const int buf, const uint32_t w) {
     const int l = lane_now(), row = 8 * wave_s + (l >> 3), j = l & 7;
     unsigned char* dst = &bbuf[buf][(2 * (j & 1)) * kBfmPlane + __mul24(row, kBfmPlaneRow) + 16 * (j >> 1)];
-    *reinterpret_cast<bf_v4i*>(dst)             = expand16(lut_b, w & 0xffffu);
-    *reinterpret_cast<bf_v4i*>(dst + kBfmPlane) = expand16(lut_b, w >> 16);
+    *reinterpret_cast<bf_v4i*>(dst)             = hamming_expand16(lut_b, w & 0xffffu);
+    *reinterpret_cast<bf_v4i*>(dst + kBfmPlane) = hamming_expand16(lut_b, w >> 16);
     // pop(b) of the row: its 8 words sit on 8 neighbouring lanes
     int pop = __popc(w);
     pop += __builtin_amdgcn_update_dpp(0, pop, 0xb1, 0xf, 0xf, true);   // quad_perm [1, 0, 3, 2]
@@ -791,7 +779,6 @@ __global__ __launch_bounds__(kBfmThreads, 4) void bruteforce_dense_mfma_kernel(c
   };
   stage(0, 0, fetch(0));
   __syncthreads();
-  const bf_v4i zero = {0, 0, 0, 0};
   for (int c = 0; c < n_chunks; ++c) {
     const int buf = c & 1;
     uint32_t w_next = 0u;
@@ -814,17 +801,7 @@ __global__ __launch_bounds__(kBfmThreads, 4) void bruteforce_dense_mfma_kernel(c
           B[kb] = *reinterpret_cast<const bf_v4i*>(brow + 16 * kb);
         }
         bf_v4i acc[4];
-#pragma unroll
-        for (int t = 0; t < 4; ++t) {
-          acc[t] = __builtin_amdgcn_mfma_i32_16x16x64_i8(A[t][0], B[0], zero, 0, 0, 0);
-        }
-#pragma unroll
-        for (int kb = 1; kb < 4; ++kb) {
-#pragma unroll
-          for (int t = 0; t < 4; ++t) {
-            acc[t] = __builtin_amdgcn_mfma_i32_16x16x64_i8(A[t][kb], B[kb], acc[t], 0, 0, 0);
-          }
-        }
+        hamming_tiles(A, B, acc);
         bool any_t[4];
 #pragma unroll
         for (int t = 0; t < 4; ++t) {
@@ -929,12 +906,8 @@ __device__ __forceinline__ void bf_matrix_phase1(const BfArgs& a, unsigned char*
   const int tid    = threadIdx.x;
   const int wave_s = __builtin_amdgcn_readfirstlane(tid >> 6);
   if (tid < 16) {
-    uint32_t v01 = 0, vpm = 0;
-#pragma unroll
-    for (int b = 0; b < 4; ++b) {
-      v01 |= ((tid >> b) & 1 ? 0x01u : 0x00u) << (8 * b);
-      vpm |= ((tid >> b) & 1 ? 0xffu : 0x01u) << (8 * b);
-    }
+    uint32_t v01, vpm;
+    hamming_lut_entry(tid, v01, vpm);
     lut_a[tid] = v01;
     lut_b[tid] = vpm;
   }
@@ -942,14 +915,6 @@ __device__ __forceinline__ void bf_matrix_phase1(const BfArgs& a, unsigned char*
   if (nf == 0 || nm == 0) {
     return;  // (block-uniform)
   }
-  auto expand16 = [](const uint32_t* lut, const uint32_t bits16) -> bf_v4i {
-    bf_v4i v;
-    v.x = (int) lut[bits16 & 15u];
-    v.y = (int) lut[(bits16 >> 4) & 15u];
-    v.z = (int) lut[(bits16 >> 8) & 15u];
-    v.w = (int) lut[(bits16 >> 12) & 15u];
-    return v;
-  };
   uint4* segment    = segments + wave_s * kMxSeg;
   uint32_t my_count = 0;  // entries in this wave's segment (wave-uniform: a scalar register)
   // this wave's parked entries -> the pair's candidate list and registration state (:52-69)
@@ -1018,8 +983,8 @@ __device__ __forceinline__ void bf_matrix_phase1(const BfArgs& a, unsigned char*
   auto stage = [&](const int c, const int buf, const uint32_t w) {
     const int l = lane_now(), row = 8 * wave_s + (l >> 3), j = l & 7;
     unsigned char* dst = bbuf + buf * (4 * kPlane) + (2 * (j & 1)) * kPlane + __mul24(row, kBfmPlaneRow) + 16 * (j >> 1);
-    *reinterpret_cast<bf_v4i*>(dst)             = expand16(lut_b, w & 0xffffu);
-    *reinterpret_cast<bf_v4i*>(dst + kPlane) = expand16(lut_b, w >> 16);
+    *reinterpret_cast<bf_v4i*>(dst)             = hamming_expand16(lut_b, w & 0xffffu);
+    *reinterpret_cast<bf_v4i*>(dst + kPlane) = hamming_expand16(lut_b, w >> 16);
     int pop = __popc(w);
     pop += __builtin_amdgcn_update_dpp(0, pop, 0xb1, 0xf, 0xf, true);   // quad_perm [1, 0, 3, 2]
     pop += __builtin_amdgcn_update_dpp(0, pop, 0x4e, 0xf, 0xf, true);   // quad_perm [2, 3, 0, 1]
@@ -1029,7 +994,6 @@ __device__ __forceinline__ void bf_matrix_phase1(const BfArgs& a, unsigned char*
     }
   };
   const bool stager = wave_s < CHUNK * 8 / 64;  // (512 words per chunk)
-  const bf_v4i zero = {0, 0, 0, 0};
   for (int pass_first = 0; pass_first < nf; pass_first += THREADS) {
     const int row0       = pass_first + wave_s * kBfmRowsWave;
     const bool wave_live = row0 < nf;
@@ -1051,7 +1015,7 @@ __device__ __forceinline__ void bf_matrix_phase1(const BfArgs& a, unsigned char*
         const bool live = row0 + 16 * t + (l & 15) < nf;
 #pragma unroll
         for (int kb = 0; kb < 4; ++kb) {
-          A[t][kb] = expand16(lut_a, live ? (w[t][kb] >> (16 * ((l >> 4) & 1))) & 0xffffu : 0u);
+          A[t][kb] = hamming_expand16(lut_a, live ? (w[t][kb] >> (16 * ((l >> 4) & 1))) & 0xffffu : 0u);
         }
       }
     }
@@ -1082,17 +1046,7 @@ __device__ __forceinline__ void bf_matrix_phase1(const BfArgs& a, unsigned char*
             B[kb] = *reinterpret_cast<const bf_v4i*>(brow + 16 * kb);
           }
           bf_v4i acc[4];
-#pragma unroll
-          for (int t = 0; t < 4; ++t) {
-            acc[t] = __builtin_amdgcn_mfma_i32_16x16x64_i8(A[t][0], B[0], zero, 0, 0, 0);
-          }
-#pragma unroll
-          for (int kb = 1; kb < 4; ++kb) {
-#pragma unroll
-            for (int t = 0; t < 4; ++t) {
-              acc[t] = __builtin_amdgcn_mfma_i32_16x16x64_i8(A[t][kb], B[kb], acc[t], 0, 0, 0);
-            }
-          }
+          hamming_tiles(A, B, acc);
           bool any_t[4];
 #pragma unroll
           for (int t = 0; t < 4; ++t) {

@@ -1,0 +1,867 @@
+// place_db.hip -- the loop detector's candidate search on the device: CorrespondenceFinderHBST_::compute
+// (registration/correspondence_finders/correspondence_finder_hbst.cpp:5-91, correspondences :95-127) against a descriptor database of
+// every earlier local map (include/proslam_hip.h, prs_place_db_* / prs_place_query_batch).
+//
+// The database (BUILD-DEFINED substitution for srrg_hbst::BinaryTree256, which is not in the tree) is searched EXHAUSTIVELY: every
+// stored descriptor within the threshold counts.  Storage: the stored descriptors of the maps one after another, each map padded to a
+// multiple of 16 rows, so that a 16-row tile of the database never spans two maps (tile_map[] names its map, row_pidx[] the point index
+// of a row in its map, -1 on a pad row).
+//
+// One query batch is three launches on the context's stream:
+//   place_init_kernel    match counts [batch][maps] <- 0, best keys [batch][rows] <- ~0.
+//   place_score_kernel   grid (database slices of 1024 rows, query blocks of 256 rows, batch).  A wave owns 64 query rows (4 A tiles,
+//                        expanded once into registers as 0 / 1 bytes), the workgroup walks its database slice in chunks of 64 rows that
+//                        all four waves expand into LDS as +1 / -1 bytes; a 16 x 16 tile of distances is prs_hamming_tile.h's four
+//                        v_mfma_i32_16x16x64_i8 per A tile.  A pair (q, r) matches iff q is a Valid query point and d < lim.  Per
+//                        database row the best (distance, query index) is one packed atomicMin key (distance << 23 | q): integer, so
+//                        the result does not depend on the order the waves arrive in.  The match count of a map is summed in a scalar
+//                        register from the ballots of its tiles and added with one atomic per (wave, map run).
+//   place_select_kernel  one workgroup per query: index_query (the stored index of the query's graph id, else the number of maps), the
+//                        age and inlier rules, the candidates in ascending map index (capped at max_candidates), and per candidate the
+//                        correspondences: every row of the map with a key, in ascending row = ascending reference point index.
+// prs_place_gather_pairs adds a fourth (place_gather_kernel): the pair slots of a loop-closure batch from the candidate lists.
+#include <string.h>
+
+#include <cmath>
+#include <unordered_map>
+#include <vector>
+
+#include "prs_device.h"
+#include "prs_hamming_tile.h"
+#include "prs_host.h"
+
+struct prs_place_db {
+  prs_context* ctx = nullptr;
+  int32_t maps = 0, rows = 0, max_map_rows = 0;
+  int32_t map_cap = 0, row_cap = 0;  // device capacities (rows: a multiple of 16)
+  uint8_t* desc      = nullptr;      // [row_cap][32]
+  float* xyz         = nullptr;      // [row_cap][4]
+  int32_t* row_pidx  = nullptr;      // [row_cap]
+  int32_t* tile_map  = nullptr;      // [row_cap / 16]
+  int32_t* map_off   = nullptr;      // [map_cap] first row
+  int32_t* map_rows  = nullptr;      // [map_cap] stored descriptors (pads excluded)
+  int64_t* map_gid   = nullptr;      // [map_cap] graph id
+  std::unordered_map<int64_t, int32_t> index_of;
+};
+
+namespace prs {
+
+namespace {
+
+constexpr int kPdThreads  = 256;                      // 4 waves
+constexpr int kPdRowsWave = 64;                       // query rows per wave (4 A tiles)
+constexpr int kPdRowsWg   = kPdRowsWave * (kPdThreads / 64);
+constexpr int kPdChunk    = 64;                       // database rows per LDS chunk (4 B tiles)
+constexpr int kPdSlice    = 16 * kPdChunk;            // database rows per workgroup
+constexpr int kPdPlaneRow = 64 + 16;                  // a row of a plane: four K blocks of 16 B + 16 B pad (bruteforce.hip's bank layout)
+constexpr int kPdPlane    = kPdChunk * kPdPlaneRow;
+constexpr int kPdMaxQuery = 65536;                    // query rows per slot (the key keeps 23 bits of query index)
+constexpr int kPdMaxCorrStride = 1 << 20;
+constexpr uint32_t kNoKey = 0xffffffffu;
+
+struct PlaceArgs {
+  prs_place_queries q;
+  prs_place_params p;
+  const uint32_t* desc;  // database rows as 8 words
+  const int32_t* row_pidx;
+  const int32_t* tile_map;
+  const int32_t* map_off;
+  const int32_t* map_rows;
+  const int64_t* map_gid;
+  int32_t maps, rows;
+  int lim;               // match iff d < lim  (== (float) d < maximum_descriptor_distance)
+};
+
+__global__ __launch_bounds__(kPdThreads) void place_init_kernel(const PlaceArgs a) {
+  const size_t b  = blockIdx.y;
+  const size_t i0 = (size_t) blockIdx.x * kPdThreads + threadIdx.x;
+  const size_t step = (size_t) gridDim.x * kPdThreads;
+  for (size_t i = i0; i < (size_t) a.rows; i += step) {
+    a.q.best_keys[b * (size_t) a.q.key_stride + i] = kNoKey;
+  }
+  for (size_t i = i0; i < (size_t) a.maps; i += step) {
+    a.q.match_counts[b * (size_t) a.q.count_stride + i] = 0u;
+  }
+}
+
+__device__ __forceinline__ int clamp_n(const int n, const int stride) {
+  return n < 0 ? 0 : (n > stride ? stride : n);
+}
+
+__global__ __launch_bounds__(kPdThreads) void place_score_kernel(const PlaceArgs a) {
+  __shared__ __attribute__((aligned(256))) unsigned char bbuf[4 * kPdPlane];
+  static_assert(kPdPlane % 256 == 0, "planes must not shift the banks");
+  __shared__ int popm[kPdChunk];
+  __shared__ int tmap[kPdChunk / 16];
+  __shared__ uint32_t lut_a[16], lut_b[16];
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave_s = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const size_t b   = blockIdx.z;
+  const int nq     = clamp_n(a.q.n_query[b], a.q.query_stride);
+  const int qblock = (int) blockIdx.y * kPdRowsWg;
+  const int row_begin = (int) blockIdx.x * kPdSlice;
+  const int row_end   = row_begin + kPdSlice < a.rows ? row_begin + kPdSlice : a.rows;
+  if (qblock >= nq) {
+    return;  // (block-uniform)
+  }
+  if (tid < 16) {
+    uint32_t v01, vpm;
+    hamming_lut_entry(tid, v01, vpm);
+    lut_a[tid] = v01;
+    lut_b[tid] = vpm;
+  }
+  __syncthreads();
+  const uint32_t* __restrict__ gdq = reinterpret_cast<const uint32_t*>(a.q.desc + b * (size_t) a.q.query_stride * PRS_DESC_BYTES);
+  const uint8_t* valid = a.q.valid ? a.q.valid + b * (size_t) a.q.query_stride : nullptr;
+  // ---- this wave's query rows: A[t][kb] = bits [64 kb + 16 lg, +16) of row q0 + 16 t + li (absent or not Valid: zeros) ----
+  const int q0         = qblock + wave_s * kPdRowsWave;
+  const bool wave_live = q0 < nq;
+  bf_v4i A[4][4];
+  uint64_t rowmask[16];  // accumulator (t, r) of lane l is query row q0 + 16 t + 4 (l >> 4) + r: which lanes hold a Valid one
+  {
+    uint32_t w[4][4];
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+      const int q  = q0 + 16 * t + (lane & 15);
+      const int qr = q < nq ? q : (nq > 0 ? nq - 1 : 0);
+#pragma unroll
+      for (int kb = 0; kb < 4; ++kb) {
+        w[t][kb] = gdq[8 * (size_t) qr + 2 * kb + (lane >> 5)];
+      }
+    }
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+      const int q     = q0 + 16 * t + (lane & 15);
+      const bool live = q < nq && (!valid || valid[q] != 0);
+#pragma unroll
+      for (int kb = 0; kb < 4; ++kb) {
+        A[t][kb] = hamming_expand16(lut_a, live ? (w[t][kb] >> (16 * ((lane >> 4) & 1))) & 0xffffu : 0u);
+      }
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int qr = q0 + 16 * t + 4 * (lane >> 4) + r;
+        rowmask[4 * t + r] = __ballot(qr < nq && (!valid || valid[qr] != 0));
+      }
+    }
+  }
+  uint32_t* keys   = a.q.best_keys + b * (size_t) a.q.key_stride;
+  uint32_t* counts = a.q.match_counts + b * (size_t) a.q.count_stride;
+  int run_map      = -1;  // the map of the tiles counted in run_count (wave-uniform)
+  uint32_t run_count = 0;
+  for (int c = row_begin; c < row_end; c += kPdChunk) {
+    // ---- stage 64 database rows: two words per thread (row = idx >> 3, word j = idx & 7), pop(row) over its 8 lanes ----
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+      const int idx = tid + kPdThreads * h, row = idx >> 3, j = idx & 7;
+      const int grow   = c + row;
+      const uint32_t w = grow < row_end ? a.desc[8 * (size_t) grow + j] : 0u;
+      unsigned char* dst = &bbuf[(2 * (j & 1)) * kPdPlane + row * kPdPlaneRow + 16 * (j >> 1)];
+      *reinterpret_cast<bf_v4i*>(dst)            = hamming_expand16(lut_b, w & 0xffffu);
+      *reinterpret_cast<bf_v4i*>(dst + kPdPlane) = hamming_expand16(lut_b, w >> 16);
+      int pop = __popc(w);
+      pop += __shfl_xor(pop, 1, 64);
+      pop += __shfl_xor(pop, 2, 64);
+      pop += __shfl_xor(pop, 4, 64);
+      if (j == 0) {
+        popm[row] = grow < row_end && a.row_pidx[grow] >= 0 ? pop : (1 << 20);  // a pad row never meets the threshold
+      }
+    }
+    if (tid < kPdChunk / 16) {
+      tmap[tid] = c + 16 * tid < row_end ? a.tile_map[(c >> 4) + tid] : -1;
+    }
+    __syncthreads();
+    if (wave_live) {
+      const int li = lane & 15, lg = lane >> 4;
+#pragma unroll 1
+      for (int bt = 0; bt < kPdChunk / 16; ++bt) {
+        if (c + 16 * bt >= row_end) {
+          break;  // (uniform)
+        }
+        const int m = __builtin_amdgcn_readfirstlane(tmap[bt]);
+        if (m != run_map) {
+          if (run_count != 0u && lane == 0) {
+            atomicAdd(&counts[run_map], run_count);
+          }
+          run_map   = m;
+          run_count = 0u;
+        }
+        const unsigned char* brow = &bbuf[lg * kPdPlane + (16 * bt + li) * kPdPlaneRow];
+        const int pop_b = popm[16 * bt + li];
+        const int thr   = a.lim - pop_b;  // match  <=>  acc < thr
+        bf_v4i B[4];
+#pragma unroll
+        for (int kb = 0; kb < 4; ++kb) {
+          B[kb] = *reinterpret_cast<const bf_v4i*>(brow + 16 * kb);
+        }
+        bf_v4i acc[4];
+        hamming_tiles(A, B, acc);
+        const int grow = c + 16 * bt + li;
+#pragma unroll
+        for (int t = 0; t < 4; ++t) {
+          const int v[4] = {acc[t].x, acc[t].y, acc[t].z, acc[t].w};
+#pragma unroll
+          for (int r = 0; r < 4; ++r) {
+            const uint64_t hit = __ballot(v[r] < thr) & rowmask[4 * t + r];
+            if (hit != 0ull) {  // (uniform)
+              run_count += (uint32_t) __popcll(hit);
+              if ((hit >> lane) & 1ull) {
+                const uint32_t q = (uint32_t) (q0 + 16 * t + 4 * lg + r);
+                atomicMin(&keys[grow], ((uint32_t) (v[r] + pop_b) << 23) | q);
+              }
+            }
+          }
+        }
+      }
+    }
+    __syncthreads();  // (the chunk is consumed before the next one is staged over it)
+  }
+  if (run_count != 0u && lane == 0) {
+    atomicAdd(&counts[run_map], run_count);
+  }
+}
+
+// the query's status word: 0, PRS_WARN_EMPTY_INPUT (the reference's "query descriptor vector is empty", :13-18), or a PRS_ERR_* code
+__device__ __forceinline__ int query_status(const PlaceArgs& a, const size_t b) {
+  const int n = a.q.n_query[b];
+  if (a.q.graph_id[b] < 0 || n < 0) {
+    return PRS_ERR_RANGE;
+  }
+  if (n > a.q.query_stride) {
+    return PRS_ERR_CAPACITY;
+  }
+  return n == 0 ? PRS_WARN_EMPTY_INPUT : 0;
+}
+
+__global__ __launch_bounds__(kPdThreads) void place_select_kernel(const PlaceArgs a) {
+  __shared__ int s_index;
+  __shared__ int s_ncand;
+  __shared__ int s_cand[256];  // candidates of the query (max_candidates <= 256)
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const size_t b   = blockIdx.x;
+  const int maxc   = a.p.max_candidates;
+  int status       = query_status(a, b);
+  // index_query (:47-55): the stored index of the query's graph id, else the number of maps
+  if (tid == 0) {
+    s_index = a.maps;
+  }
+  __syncthreads();
+  const int64_t gid = a.q.graph_id[b];
+  for (int m = tid; m < a.maps; m += kPdThreads) {
+    if (a.map_gid[m] == gid) {
+      atomicMin(&s_index, m);
+    }
+  }
+  __syncthreads();
+  const uint64_t index_query = (uint64_t) s_index;
+  // the candidates in ascending map index (:70-90), by one wave
+  if (wave == 0) {
+    const uint32_t* counts = a.q.match_counts + b * (size_t) a.q.count_stride;
+    int total = 0;
+    if (status >= 0 && status != PRS_WARN_EMPTY_INPUT) {
+      for (int base = 0; base < a.maps; base += 64) {
+        const int m = base + lane;
+        bool pass   = false;
+        if (m < a.maps) {
+          const uint64_t ref  = (uint64_t) m;
+          const uint64_t diff = index_query - ref;  // uint64_t: wraps when the query is older than the reference
+          pass = (double) diff > (double) a.p.minimum_age_difference_to_candidates && a.p.relocalize_min_inliers >= 0 &&
+                 counts[m] > (uint32_t) a.p.relocalize_min_inliers;
+        }
+        const uint64_t mk = __ballot(pass);
+        const int pos = total + (int) __builtin_amdgcn_mbcnt_hi((uint32_t) (mk >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t) mk, 0u));
+        if (pass && pos < maxc) {
+          s_cand[pos] = m;
+        }
+        total += __popcll(mk);
+      }
+    }
+    if (lane == 0) {
+      s_ncand = total < maxc ? total : maxc;
+      if (total > maxc) {
+        status = PRS_ERR_CAPACITY;
+      }
+      a.q.n_candidates[b] = total < maxc ? total : maxc;
+      a.q.status[b]       = status;
+      if (a.q.index_query) {
+        a.q.index_query[b] = (int64_t) index_query;
+      }
+    }
+  }
+  __syncthreads();
+  const int ncand = s_ncand;
+  if (tid < maxc) {
+    a.q.candidates[b * (size_t) maxc + tid] = tid < ncand ? s_cand[tid] : -1;
+  }
+  // per candidate, its correspondences (:95-127): every row with a key, (fixed = query index, moving = point index, distance)
+  const uint32_t* keys = a.q.best_keys + b * (size_t) a.q.key_stride;
+  for (int k = wave; k < maxc; k += kPdThreads / 64) {
+    int n = 0;
+    if (k < ncand) {
+      const int m = s_cand[k], off = a.map_off[m], nr = a.map_rows[m];
+      prs_corr* out = a.q.corr + (b * (size_t) maxc + (size_t) k) * (size_t) a.q.corr_stride;
+      int row = off;  // stored rows of the map: [off, off + nr) (pads follow)
+      for (int base = 0; base < nr; base += 64) {
+        const int r       = row + base + lane;
+        const uint32_t ky = base + lane < nr ? keys[r] : kNoKey;
+        const bool hit    = ky != kNoKey;
+        const uint64_t mk = __ballot(hit);
+        const int pos     = n + (int) __builtin_amdgcn_mbcnt_hi((uint32_t) (mk >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t) mk, 0u));
+        if (hit) {
+          prs_corr cr;
+          cr.fixed_idx  = (int32_t) (ky & 0x7fffffu);
+          cr.moving_idx = a.row_pidx[r];
+          cr.response   = (float) (ky >> 23);
+          out[pos]      = cr;
+        }
+        n += __popcll(mk);
+      }
+    }
+    if (lane == 0) {
+      a.q.n_corr[b * (size_t) maxc + (size_t) k] = n;
+    }
+  }
+}
+
+struct GatherArgs {
+  prs_place_queries q;
+  prs_place_pairs o;
+  const uint8_t* desc;
+  const float* xyz;
+  const int32_t* map_off;
+  const int32_t* map_rows;
+  int maxc;
+};
+
+// one wave per pair slot (query b, candidate k): fixed = the query's Valid points in index order, moving = the candidate map's stored
+// points, X = identity; a slot without a candidate gets n = 0 on both sides
+__global__ __launch_bounds__(kPdThreads) void place_gather_kernel(const GatherArgs g) {
+  const int lane = threadIdx.x & 63;
+  const size_t slot = (size_t) blockIdx.x * (kPdThreads / 64) + (threadIdx.x >> 6);
+  if (slot >= (size_t) g.q.batch * (size_t) g.maxc) {
+    return;
+  }
+  const size_t b = slot / (size_t) g.maxc;
+  const int k    = (int) (slot % (size_t) g.maxc);
+  const bool use = k < g.q.n_candidates[b];  // (a query over max_candidates still fills its slots; other errors have none)
+  int nf = 0, nm = 0;
+  if (use) {
+    const int nq = clamp_n(g.q.n_query[b], g.q.query_stride);
+    const uint8_t* valid = g.q.valid ? g.q.valid + b * (size_t) g.q.query_stride : nullptr;
+    const uint4* qd = reinterpret_cast<const uint4*>(g.q.desc + b * (size_t) g.q.query_stride * PRS_DESC_BYTES);
+    const float4* qx = reinterpret_cast<const float4*>(g.q.xyz + b * (size_t) g.q.query_stride * 4);
+    uint4* fd  = reinterpret_cast<uint4*>(g.o.fixed_desc + slot * (size_t) g.o.fixed_stride * PRS_DESC_BYTES);
+    float4* fx = reinterpret_cast<float4*>(g.o.fixed_xyz + slot * (size_t) g.o.fixed_stride * 4);
+    for (int base = 0; base < nq; base += 64) {
+      const int i    = base + lane;
+      const bool in  = i < nq && (!valid || valid[i] != 0);
+      const uint64_t mk = __ballot(in);
+      const int pos  = nf + (int) __builtin_amdgcn_mbcnt_hi((uint32_t) (mk >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t) mk, 0u));
+      if (in) {
+        fd[2 * (size_t) pos]     = qd[2 * (size_t) i];
+        fd[2 * (size_t) pos + 1] = qd[2 * (size_t) i + 1];
+        fx[pos]                  = qx[i];
+      }
+      nf += __popcll(mk);
+    }
+    const int m = g.q.candidates[b * (size_t) g.maxc + (size_t) k];
+    const int off = g.map_off[m];
+    nm = g.map_rows[m];
+    const uint4* dd  = reinterpret_cast<const uint4*>(g.desc) + 2 * (size_t) off;
+    const float4* dx = reinterpret_cast<const float4*>(g.xyz) + (size_t) off;
+    uint4* md  = reinterpret_cast<uint4*>(g.o.moving_desc + slot * (size_t) g.o.moving_stride * PRS_DESC_BYTES);
+    float4* mx = reinterpret_cast<float4*>(g.o.moving_xyz + slot * (size_t) g.o.moving_stride * 4);
+    for (int i = lane; i < nm; i += 64) {
+      md[2 * (size_t) i]     = dd[2 * (size_t) i];
+      md[2 * (size_t) i + 1] = dd[2 * (size_t) i + 1];
+      mx[i]                  = dx[i];
+    }
+  }
+  if (lane < 16) {
+    g.o.X[16 * slot + lane] = (lane % 5 == 0) ? 1.0f : 0.0f;
+  }
+  if (lane == 0) {
+    g.o.n_fixed[slot]  = nf;
+    g.o.n_moving[slot] = nm;
+  }
+}
+
+bool aligned(const void* ptr, size_t a) {
+  return (reinterpret_cast<uintptr_t>(ptr) & (a - 1)) == 0;
+}
+
+int lim_of(const float thr) {
+  // (float) d < maximum_descriptor_distance for integer d  <=>  d < lim  (lim 257: every distance of 256 bits)
+  int lim = 0;
+  while (lim <= 256 && (float) lim < thr) {
+    ++lim;
+  }
+  return lim;
+}
+
+int check_params(prs_context* ctx, const prs_place_params* p, const char* what) {
+  if (!p) {
+    return ctx_fail(ctx, PRS_ERR_NULL, what);
+  }
+  if (std::isnan(p->maximum_descriptor_distance)) {
+    return ctx_fail(ctx, PRS_ERR_RANGE, "prs_place_query: maximum_descriptor_distance is NaN");
+  }
+  if (p->max_candidates < 1 || p->max_candidates > 256) {
+    return ctx_fail(ctx, PRS_ERR_RANGE, "prs_place_query: max_candidates must be in [1, 256]");
+  }
+  return PRS_OK;
+}
+
+PlaceArgs make_args(const prs_place_db* db, const prs_place_params* p, const prs_place_queries* q) {
+  PlaceArgs a;
+  memset(&a, 0, sizeof(a));
+  a.q        = *q;
+  a.p        = *p;
+  a.desc     = reinterpret_cast<const uint32_t*>(db->desc);
+  a.row_pidx = db->row_pidx;
+  a.tile_map = db->tile_map;
+  a.map_off  = db->map_off;
+  a.map_rows = db->map_rows;
+  a.map_gid  = db->map_gid;
+  a.maps     = db->maps;
+  a.rows     = db->rows;
+  a.lim      = lim_of(p->maximum_descriptor_distance);
+  return a;
+}
+
+int place_query_launch(prs_place_db* db, const prs_place_params* p, const prs_place_queries* q) {
+  prs_context* ctx = db->ctx;
+  int rc = check_params(ctx, p, "prs_place_query_batch: parameters not set");
+  if (rc != PRS_OK) {
+    return rc;
+  }
+  if (!q) {
+    return ctx_fail(ctx, PRS_ERR_NULL, "prs_place_query_batch: queries not set");
+  }
+  if (q->batch <= 0) {
+    return PRS_OK;
+  }
+  if (!q->desc || !q->n_query || !q->graph_id || !q->match_counts || !q->best_keys || !q->candidates || !q->n_candidates || !q->corr ||
+      !q->n_corr || !q->status) {
+    return ctx_fail(ctx, PRS_ERR_NULL, "prs_place_query_batch: input or output buffer not set");
+  }
+  if (q->batch > 65535) {
+    return ctx_fail(ctx, PRS_ERR_UNSUPPORTED, "prs_place_query_batch: more than 65535 queries");
+  }
+  if (q->query_stride < 1 || q->query_stride > kPdMaxQuery) {
+    return ctx_fail(ctx, PRS_ERR_UNSUPPORTED, "prs_place_query_batch: query_stride must be in [1, 65536]");
+  }
+  if (q->count_stride < db->maps || q->key_stride < db->rows || q->corr_stride < db->max_map_rows || q->corr_stride > kPdMaxCorrStride) {
+    return ctx_fail(ctx, PRS_ERR_CAPACITY, "prs_place_query_batch: count_stride, key_stride or corr_stride below the database's size");
+  }
+  if (!aligned(q->desc, 4)) {
+    return ctx_fail(ctx, PRS_ERR_UNSUPPORTED, "prs_place_query_batch: descriptor rows must be 4-byte aligned");
+  }
+  const PlaceArgs a = make_args(db, p, q);
+  hipStream_t s     = ctx_stream(ctx);
+  if (db->rows > 0 || db->maps > 0) {
+    const int big = db->rows > db->maps ? db->rows : db->maps;
+    const unsigned gx = (unsigned) ((big + kPdThreads - 1) / kPdThreads < 1024 ? (big + kPdThreads - 1) / kPdThreads : 1024);
+    hipLaunchKernelGGL(place_init_kernel, dim3(gx, (unsigned) q->batch), dim3(kPdThreads), 0, s, a);
+  }
+  if (db->rows > 0) {
+    const dim3 grid((unsigned) ((db->rows + kPdSlice - 1) / kPdSlice), (unsigned) ((q->query_stride + kPdRowsWg - 1) / kPdRowsWg),
+                    (unsigned) q->batch);
+    hipLaunchKernelGGL(place_score_kernel, grid, dim3(kPdThreads), 0, s, a);
+  }
+  hipLaunchKernelGGL(place_select_kernel, dim3((unsigned) q->batch), dim3(kPdThreads), 0, s, a);
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) {
+    return ctx_fail_hip(ctx, e, "prs_place_query_batch launch");
+  }
+  return PRS_OK;
+}
+
+template <typename T>
+int grow(prs_context* ctx, T*& ptr, const size_t old_n, const size_t new_n) {
+  T* p = nullptr;
+  if (hipMalloc(&p, new_n * sizeof(T) > 0 ? new_n * sizeof(T) : sizeof(T)) != hipSuccess) {
+    return ctx_fail(ctx, PRS_ERR_HIP, "prs_place_db: device allocation failed");
+  }
+  hipError_t e = hipMemsetAsync(p, 0, new_n * sizeof(T), ctx->stream);
+  if (e == hipSuccess && ptr && old_n > 0) {
+    e = hipMemcpyAsync(p, ptr, old_n * sizeof(T), hipMemcpyDeviceToDevice, ctx->stream);
+  }
+  if (e == hipSuccess) {
+    e = hipStreamSynchronize(ctx->stream);
+  }
+  if (e != hipSuccess) {
+    (void) hipFree(p);
+    return ctx_fail_hip(ctx, e, "prs_place_db: growth copy");
+  }
+  if (ptr) {
+    (void) hipFree(ptr);
+  }
+  ptr = p;
+  return PRS_OK;
+}
+
+int db_reserve(prs_place_db* db, int64_t maps, int64_t rows) {
+  prs_context* ctx = db->ctx;
+  rows = (rows + 15) / 16 * 16;
+  if (maps > INT32_MAX || rows > INT32_MAX - 16) {
+    return ctx_fail(ctx, PRS_ERR_UNSUPPORTED, "prs_place_db_reserve: above 2^31 maps or rows");
+  }
+  (void) hipSetDevice(ctx->device);
+  if (maps > db->map_cap) {
+    const size_t o = (size_t) db->maps, n = (size_t) maps;
+    int rc = grow(ctx, db->map_off, o, n);
+    rc     = rc == PRS_OK ? grow(ctx, db->map_rows, o, n) : rc;
+    rc     = rc == PRS_OK ? grow(ctx, db->map_gid, o, n) : rc;
+    if (rc != PRS_OK) {
+      return rc;
+    }
+    db->map_cap = (int32_t) maps;
+  }
+  if (rows > db->row_cap) {
+    const size_t o = (size_t) db->rows, n = (size_t) rows;
+    int rc = grow(ctx, db->desc, o * PRS_DESC_BYTES, n * PRS_DESC_BYTES);
+    rc     = rc == PRS_OK ? grow(ctx, db->xyz, o * 4, n * 4) : rc;
+    rc     = rc == PRS_OK ? grow(ctx, db->row_pidx, o, n) : rc;
+    rc     = rc == PRS_OK ? grow(ctx, db->tile_map, o / 16, n / 16) : rc;
+    if (rc != PRS_OK) {
+      return rc;
+    }
+    db->row_cap = (int32_t) rows;
+  }
+  return PRS_OK;
+}
+
+}  // namespace
+
+}  // namespace prs
+
+using namespace prs;
+
+extern "C" {
+
+int prs_place_db_create(prs_context* ctx, prs_place_db** db) {
+  if (!ctx || !db) {
+    return PRS_ERR_NULL;
+  }
+  *db = new prs_place_db();
+  (*db)->ctx = ctx;
+  return PRS_OK;
+}
+
+int prs_place_db_destroy(prs_place_db* db) {
+  if (!db) {
+    return PRS_OK;
+  }
+  (void) hipSetDevice(db->ctx->device);
+  (void) hipStreamSynchronize(db->ctx->stream);
+  void* ptrs[] = {db->desc, db->xyz, db->row_pidx, db->tile_map, db->map_off, db->map_rows, db->map_gid};
+  for (void* p : ptrs) {
+    if (p) {
+      (void) hipFree(p);
+    }
+  }
+  delete db;
+  return PRS_OK;
+}
+
+int prs_place_db_clear(prs_place_db* db) {
+  if (!db) {
+    return PRS_ERR_NULL;
+  }
+  db->maps = db->rows = db->max_map_rows = 0;
+  db->index_of.clear();
+  return PRS_OK;
+}
+
+int prs_place_db_reserve(prs_place_db* db, int64_t maps, int64_t rows) {
+  if (!db) {
+    return PRS_ERR_NULL;
+  }
+  if (maps < 0 || rows < 0) {
+    return ctx_fail(db->ctx, PRS_ERR_RANGE, "prs_place_db_reserve: negative size");
+  }
+  return db_reserve(db, maps, rows);
+}
+
+int prs_place_db_size(const prs_place_db* db, int32_t* maps, int32_t* rows, int32_t* max_map_rows) {
+  if (!db) {
+    return PRS_ERR_NULL;
+  }
+  if (maps) {
+    *maps = db->maps;
+  }
+  if (rows) {
+    *rows = db->rows;
+  }
+  if (max_map_rows) {
+    *max_map_rows = db->max_map_rows;
+  }
+  return PRS_OK;
+}
+
+int prs_place_db_add(prs_place_db* db, int64_t graph_id, const float* xyz, const uint8_t* desc, const uint8_t* valid, int32_t n) {
+  if (!db) {
+    return PRS_ERR_NULL;
+  }
+  prs_context* ctx = db->ctx;
+  if (n < 0 || graph_id < 0) {
+    return ctx_fail(ctx, PRS_ERR_RANGE, "prs_place_db_add: negative size or graph id");
+  }
+  if (n > 0 && !desc) {
+    return ctx_fail(ctx, PRS_ERR_NULL, "prs_place_db_add: descriptors not set");
+  }
+  if (db->index_of.count(graph_id)) {
+    return ctx_fail(ctx, PRS_ERR_RANGE, "prs_place_db_add: graph id already stored");
+  }
+  std::vector<int32_t> keep;
+  keep.reserve((size_t) n);
+  for (int32_t i = 0; i < n; ++i) {
+    if (!valid || valid[i] != 0) {
+      keep.push_back(i);
+    }
+  }
+  const int32_t nk = (int32_t) keep.size(), padded = (nk + 15) / 16 * 16;
+  if ((int64_t) db->rows + padded > INT32_MAX - 16) {
+    return ctx_fail(ctx, PRS_ERR_UNSUPPORTED, "prs_place_db_add: above 2^31 rows");
+  }
+  if (db->maps + 1 > db->map_cap || db->rows + padded > db->row_cap) {
+    const int64_t want_maps = db->maps + 1 > db->map_cap ? 2 * (int64_t) db->map_cap + 16 : db->map_cap;
+    const int64_t want_rows = db->rows + padded > db->row_cap ? 2 * (int64_t) db->row_cap + padded + 1024 : db->row_cap;
+    const int rc = db_reserve(db, want_maps, want_rows > INT32_MAX - 16 ? (int64_t) db->rows + padded : want_rows);
+    if (rc != PRS_OK) {
+      return rc;
+    }
+  }
+  (void) hipSetDevice(ctx->device);
+  const size_t tiles = (size_t) padded / 16;
+  const size_t o_xyz = (size_t) padded * PRS_DESC_BYTES, o_pidx = o_xyz + (size_t) padded * 16, o_tile = o_pidx + (size_t) padded * 4;
+  const size_t o_map = o_tile + tiles * 4, total = o_map + 16;
+  unsigned char* h = static_cast<unsigned char*>(ctx_pinned_scratch(ctx, total));
+  if (!h) {
+    return ctx_fail(ctx, PRS_ERR_HIP, "prs_place_db_add: staging allocation failed");
+  }
+  memset(h, 0, total);
+  float* hx    = reinterpret_cast<float*>(h + o_xyz);
+  int32_t* hp  = reinterpret_cast<int32_t*>(h + o_pidx);
+  int32_t* ht  = reinterpret_cast<int32_t*>(h + o_tile);
+  for (int32_t r = 0; r < padded; ++r) {
+    hp[r] = -1;
+  }
+  for (int32_t r = 0; r < nk; ++r) {
+    const int32_t i = keep[(size_t) r];
+    memcpy(h + (size_t) r * PRS_DESC_BYTES, desc + (size_t) i * PRS_DESC_BYTES, PRS_DESC_BYTES);
+    if (xyz) {
+      hx[4 * (size_t) r]     = xyz[3 * (size_t) i];
+      hx[4 * (size_t) r + 1] = xyz[3 * (size_t) i + 1];
+      hx[4 * (size_t) r + 2] = xyz[3 * (size_t) i + 2];
+    }
+    hp[r] = i;
+  }
+  const int32_t m = db->maps;
+  for (size_t t = 0; t < tiles; ++t) {
+    ht[t] = m;
+  }
+  int32_t* hm = reinterpret_cast<int32_t*>(h + o_map);
+  hm[0] = db->rows;
+  hm[1] = nk;
+  memcpy(h + o_map + 8, &graph_id, 8);
+  hipStream_t s = ctx->stream;
+  const size_t r0 = (size_t) db->rows;
+  hipError_t e = hipSuccess;
+  if (padded > 0) {
+    e = hipMemcpyAsync(db->desc + r0 * PRS_DESC_BYTES, h, (size_t) padded * PRS_DESC_BYTES, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) {
+      e = hipMemcpyAsync(db->xyz + r0 * 4, hx, (size_t) padded * 16, hipMemcpyHostToDevice, s);
+    }
+    if (e == hipSuccess) {
+      e = hipMemcpyAsync(db->row_pidx + r0, hp, (size_t) padded * 4, hipMemcpyHostToDevice, s);
+    }
+    if (e == hipSuccess) {
+      e = hipMemcpyAsync(db->tile_map + r0 / 16, ht, tiles * 4, hipMemcpyHostToDevice, s);
+    }
+  }
+  if (e == hipSuccess) {
+    e = hipMemcpyAsync(db->map_off + m, hm, 4, hipMemcpyHostToDevice, s);
+  }
+  if (e == hipSuccess) {
+    e = hipMemcpyAsync(db->map_rows + m, hm + 1, 4, hipMemcpyHostToDevice, s);
+  }
+  if (e == hipSuccess) {
+    e = hipMemcpyAsync(db->map_gid + m, h + o_map + 8, 8, hipMemcpyHostToDevice, s);
+  }
+  if (e == hipSuccess) {
+    e = hipStreamSynchronize(s);  // (the pinned staging is reused by the next call)
+  }
+  if (e != hipSuccess) {
+    return ctx_fail_hip(ctx, e, "prs_place_db_add upload");
+  }
+  db->index_of[graph_id] = m;
+  db->maps += 1;
+  db->rows += padded;
+  db->max_map_rows = nk > db->max_map_rows ? nk : db->max_map_rows;
+  return PRS_OK;
+}
+
+int prs_place_query_batch(prs_place_db* db, const prs_place_params* params, const prs_place_queries* queries) {
+  if (!db) {
+    return PRS_ERR_NULL;
+  }
+  (void) hipSetDevice(db->ctx->device);
+  return place_query_launch(db, params, queries);
+}
+
+int prs_place_query(prs_place_db* db, const prs_place_params* params, int64_t graph_id, const uint8_t* desc, const uint8_t* valid,
+                    int32_t n, int32_t* candidates, int32_t* n_candidates, prs_corr* corr, int32_t corr_stride, int32_t* n_corr,
+                    uint32_t* match_counts) {
+  if (!db) {
+    return PRS_ERR_NULL;
+  }
+  prs_context* ctx = db->ctx;
+  int rc = check_params(ctx, params, "prs_place_query: parameters not set");
+  if (rc != PRS_OK) {
+    return rc;
+  }
+  if (!candidates || !n_candidates || !corr || !n_corr || (n > 0 && !desc)) {
+    return ctx_fail(ctx, PRS_ERR_NULL, "prs_place_query: input or output buffer not set");
+  }
+  if (n > kPdMaxQuery) {
+    return ctx_fail(ctx, PRS_ERR_UNSUPPORTED, "prs_place_query: more than 65536 query points");
+  }
+  if (corr_stride < db->max_map_rows || corr_stride < 1) {
+    return ctx_fail(ctx, PRS_ERR_CAPACITY, "prs_place_query: corr_stride below the largest stored map");
+  }
+  (void) hipSetDevice(ctx->device);
+  auto align256 = [](size_t x) { return (x + 255) & ~(size_t) 255; };
+  const int maxc  = params->max_candidates;
+  const size_t nq = (size_t) (n > 0 ? n : 1), maps = (size_t) (db->maps > 0 ? db->maps : 1), rows = (size_t) (db->rows > 0 ? db->rows : 1);
+  // staging (same on both sides): descriptors | valid | n, graph id (uploaded) | status, counts | candidates | n_corr | corr (downloaded) | keys
+  const size_t o_valid = align256(nq * PRS_DESC_BYTES), o_small = o_valid + align256(nq), o_status = o_small + 256;
+  const size_t o_counts = o_status + 256, o_cand = o_counts + align256(maps * 4), o_ncorr = o_cand + align256((size_t) maxc * 4);
+  const size_t o_corr = o_ncorr + align256((size_t) maxc * 4), o_keys = o_corr + align256((size_t) maxc * (size_t) corr_stride * sizeof(prs_corr));
+  const size_t total = o_keys + align256(rows * 4);
+  unsigned char* d = static_cast<unsigned char*>(ctx_device_scratch(ctx, total));
+  unsigned char* h = static_cast<unsigned char*>(ctx_pinned_scratch(ctx, o_keys));
+  if (!d || !h) {
+    return ctx_fail(ctx, PRS_ERR_HIP, "prs_place_query: scratch allocation failed");
+  }
+  if (n > 0) {
+    memcpy(h, desc, (size_t) n * PRS_DESC_BYTES);
+    if (valid) {
+      memcpy(h + o_valid, valid, (size_t) n);
+    }
+  }
+  int32_t* hs = reinterpret_cast<int32_t*>(h + o_small);
+  hs[0]       = n;
+  memcpy(h + o_small + 8, &graph_id, 8);
+  hipStream_t s = ctx->stream;
+  hipError_t e  = hipMemcpyAsync(d, h, o_status, hipMemcpyHostToDevice, s);
+  if (e != hipSuccess) {
+    return ctx_fail_hip(ctx, e, "prs_place_query upload");
+  }
+  prs_place_queries q;
+  memset(&q, 0, sizeof(q));
+  q.batch        = 1;
+  q.query_stride = (int32_t) nq;
+  q.desc         = d;
+  q.valid        = valid ? d + o_valid : nullptr;
+  q.n_query      = reinterpret_cast<const int32_t*>(d + o_small);
+  q.graph_id     = reinterpret_cast<const int64_t*>(d + o_small + 8);
+  q.count_stride = (int32_t) maps;
+  q.match_counts = reinterpret_cast<uint32_t*>(d + o_counts);
+  q.key_stride   = (int32_t) rows;
+  q.best_keys    = reinterpret_cast<uint32_t*>(d + o_keys);
+  q.corr_stride  = corr_stride;
+  q.candidates   = reinterpret_cast<int32_t*>(d + o_cand);
+  q.n_candidates = reinterpret_cast<int32_t*>(d + o_status + 4);
+  q.corr         = reinterpret_cast<prs_corr*>(d + o_corr);
+  q.n_corr       = reinterpret_cast<int32_t*>(d + o_ncorr);
+  q.status       = reinterpret_cast<int32_t*>(d + o_status);
+  rc = place_query_launch(db, params, &q);
+  if (rc != PRS_OK) {
+    return rc;
+  }
+  e = hipMemcpyAsync(h + o_status, d + o_status, o_corr - o_status, hipMemcpyDeviceToHost, s);
+  if (e == hipSuccess) {
+    e = hipStreamSynchronize(s);
+  }
+  if (e != hipSuccess) {
+    return ctx_fail_hip(ctx, e, "prs_place_query download");
+  }
+  const int32_t* hst = reinterpret_cast<const int32_t*>(h + o_status);
+  const int32_t nc   = hst[1];
+  const int32_t* hn  = reinterpret_cast<const int32_t*>(h + o_ncorr);
+  memcpy(candidates, h + o_cand, (size_t) maxc * 4);
+  memcpy(n_corr, hn, (size_t) maxc * 4);
+  *n_candidates = nc;
+  // the correspondences of the candidates only (candidate k's rows start at k * corr_stride)
+  for (int32_t k = 0; k < nc; ++k) {
+    if (hn[k] > 0) {
+      e = hipMemcpyAsync(corr + (size_t) k * (size_t) corr_stride, d + o_corr + (size_t) k * (size_t) corr_stride * sizeof(prs_corr),
+                         (size_t) hn[k] * sizeof(prs_corr), hipMemcpyDeviceToHost, s);
+      if (e != hipSuccess) {
+        break;
+      }
+    }
+  }
+  if (e == hipSuccess && match_counts && db->maps > 0) {
+    e = hipMemcpyAsync(match_counts, d + o_counts, (size_t) db->maps * 4, hipMemcpyDeviceToHost, s);
+  }
+  if (e == hipSuccess) {
+    e = hipStreamSynchronize(s);
+  }
+  if (e != hipSuccess) {
+    return ctx_fail_hip(ctx, e, "prs_place_query download");
+  }
+  if (hst[0] < 0) {
+    return ctx_fail(ctx, hst[0], "prs_place_query: query rejected (graph id, size or candidate capacity)");
+  }
+  return hst[0];
+}
+
+int prs_place_gather_pairs(prs_place_db* db, const prs_place_params* params, const prs_place_queries* queries, const prs_place_pairs* pairs) {
+  if (!db) {
+    return PRS_ERR_NULL;
+  }
+  prs_context* ctx = db->ctx;
+  int rc = check_params(ctx, params, "prs_place_gather_pairs: parameters not set");
+  if (rc != PRS_OK) {
+    return rc;
+  }
+  if (!queries || !pairs) {
+    return ctx_fail(ctx, PRS_ERR_NULL, "prs_place_gather_pairs: queries or pairs not set");
+  }
+  if (queries->batch <= 0) {
+    return PRS_OK;
+  }
+  if (!queries->desc || !queries->xyz || !queries->n_query || !queries->candidates || !queries->n_candidates || !queries->status ||
+      !pairs->fixed_xyz || !pairs->fixed_desc || !pairs->n_fixed || !pairs->moving_xyz || !pairs->moving_desc || !pairs->n_moving ||
+      !pairs->X) {
+    return ctx_fail(ctx, PRS_ERR_NULL, "prs_place_gather_pairs: input or output buffer not set");
+  }
+  if (pairs->fixed_stride < queries->query_stride || pairs->moving_stride < db->max_map_rows) {
+    return ctx_fail(ctx, PRS_ERR_CAPACITY, "prs_place_gather_pairs: a pair slot is smaller than the query or the largest stored map");
+  }
+  if (!aligned(queries->desc, 16) || !aligned(queries->xyz, 16) || !aligned(pairs->fixed_xyz, 16) || !aligned(pairs->fixed_desc, 16) ||
+      !aligned(pairs->moving_xyz, 16) || !aligned(pairs->moving_desc, 16)) {
+    return ctx_fail(ctx, PRS_ERR_UNSUPPORTED, "prs_place_gather_pairs: rows must be 16-byte aligned");
+  }
+  (void) hipSetDevice(ctx->device);
+  GatherArgs g;
+  memset(&g, 0, sizeof(g));
+  g.q        = *queries;
+  g.o        = *pairs;
+  g.desc     = db->desc;
+  g.xyz      = db->xyz;
+  g.map_off  = db->map_off;
+  g.map_rows = db->map_rows;
+  g.maxc     = params->max_candidates;
+  const size_t slots = (size_t) queries->batch * (size_t) params->max_candidates;
+  hipLaunchKernelGGL(place_gather_kernel, dim3((unsigned) ((slots + 3) / 4)), dim3(kPdThreads), 0, ctx_stream(ctx), g);
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) {
+    return ctx_fail_hip(ctx, e, "prs_place_gather_pairs launch");
+  }
+  return PRS_OK;
+}
+
+}  // extern "C"

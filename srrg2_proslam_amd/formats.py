@@ -325,3 +325,15 @@ def loop_params(conf):
     if relocalizer is not None:
         out["relocalizer"] = _pick(relocalizer, _VERDICT)
     return out
+
+
+_PLACE = ("maximum_descriptor_distance", "minimum_age_difference_to_candidates", "relocalize_min_inliers", "maximum_leaf_size",
+          "maximum_depth", "maximum_partitioning", "maximum_distance_for_merge")
+
+
+def place_params(conf):
+    """the loop detector's candidate-search group of a parsed configuration (MultiLoopDetectorHBST*: correspondence_finder_hbst.h).
+    maximum_leaf_size, maximum_depth and maximum_partitioning shape the HBST tree, which this build replaces by an exhaustive search:
+    read, unused.  Only fields present in the file are returned."""
+    detector = next((r for r in conf.records if r.class_name.startswith("MultiLoopDetector")), None)
+    return _pick(detector, _PLACE) if detector is not None else {}

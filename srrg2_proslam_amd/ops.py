@@ -815,6 +815,201 @@ class LoopClosureBatch:
         return point_align_batch(ctx, align_params, self.pairs)
 
 
+# ---- loop detector: place database + candidate search (CorrespondenceFinderHBST_, correspondence_finder_hbst.cpp:5-127) ----
+def place_params(place, max_candidates=8, **overrides):
+    """prs_place_params from a configs.py `place` group; overrides by field name"""
+    p = _lib.PlaceParams()
+    p.maximum_descriptor_distance = place["maximum_descriptor_distance"]
+    p.minimum_age_difference_to_candidates = place["minimum_age_difference_to_candidates"]
+    p.relocalize_min_inliers = place["relocalize_min_inliers"]
+    p.max_candidates = int(max_candidates)
+    for k, v in overrides.items():
+        setattr(p, k, v)
+    return p
+
+
+class PlaceDatabase:
+    """prs_place_db: the descriptors (and points) of every earlier local map, resident in HBM"""
+
+    def __init__(self, ctx):
+        self._ctx = ctx
+        h = C.c_void_p()
+        _check(ctx, _lib.load().prs_place_db_create(ctx._h, C.byref(h)), "prs_place_db_create")
+        self._h = h
+        ctx._children.add(self)
+
+    def close(self):
+        if getattr(self, "_h", None):
+            _lib.load().prs_place_db_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def add(self, graph_id, desc, xyz=None, valid=None):
+        """addPreviousQuery: store a local map (its Valid descriptors and points) as the next map index"""
+        d = _np(desc, np.uint8, (-1, 32))
+        x = _np(xyz, np.float32, (-1, 3)) if xyz is not None else None
+        v = _np(valid, np.uint8, (-1,)) if valid is not None else None
+        rc = _lib.load().prs_place_db_add(self._h, int(graph_id), _p(x) if x is not None else None, _p(d), _p(v) if v is not None else None,
+                                          d.shape[0])
+        return _check(self._ctx, rc, "prs_place_db_add")
+
+    def clear(self):
+        _check(self._ctx, _lib.load().prs_place_db_clear(self._h), "prs_place_db_clear")
+
+    def reserve(self, maps, rows):
+        _check(self._ctx, _lib.load().prs_place_db_reserve(self._h, int(maps), int(rows)), "prs_place_db_reserve")
+
+    def size(self):
+        """(maps, rows with pads, largest map)"""
+        m, r, x = C.c_int32(0), C.c_int32(0), C.c_int32(0)
+        _check(self._ctx, _lib.load().prs_place_db_size(self._h, C.byref(m), C.byref(r), C.byref(x)), "prs_place_db_size")
+        return m.value, r.value, x.value
+
+    def query(self, params, graph_id, desc, valid=None, corr_stride=None):
+        """host arrays, one query -> dict(status, candidates, corr [list of CORR_DTYPE], counts [maps])"""
+        maps, _, big = self.size()
+        d = _np(desc, np.uint8, (-1, 32))
+        v = _np(valid, np.uint8, (-1,)) if valid is not None else None
+        k = params.max_candidates
+        stride = max(int(corr_stride if corr_stride is not None else big), 1)
+        cand = np.zeros(max(k, 1), np.int32)
+        ncorr = np.zeros(max(k, 1), np.int32)
+        corr = np.zeros(max(k, 1) * stride, CORR_DTYPE)
+        counts = np.zeros(max(maps, 1), np.uint32)
+        nc = C.c_int32(0)
+        rc = _lib.load().prs_place_query(self._h, C.byref(params), int(graph_id), _p(d), _p(v) if v is not None else None, d.shape[0],
+                                         _p(cand), C.byref(nc), _p(corr), stride, _p(ncorr), _p(counts))
+        _check(self._ctx, rc, "prs_place_query")
+        n = nc.value
+        return dict(status=rc, candidates=cand[:n].tolist(), counts=counts[:maps].astype(np.int64),
+                    corr=[corr[i * stride: i * stride + ncorr[i]].copy() for i in range(n)])
+
+
+class PlaceQueries:
+    """B queries resident in HBM and the candidate search's outputs, sized for `db` as it stands (count / key / corr strides)"""
+
+    def __init__(self, device, batch, query_stride, max_candidates, db=None, count_stride=None, key_stride=None, corr_stride=None,
+                 with_valid=False):
+        import torch
+        dev = torch.device("cuda", device)
+        maps, rows, big = db.size() if db is not None else (0, 0, 0)
+        self.batch, self.query_stride, self.max_candidates = int(batch), int(query_stride), int(max_candidates)
+        self.count_stride = max(int(count_stride if count_stride is not None else maps), 1)
+        self.key_stride = max(int(key_stride if key_stride is not None else rows), 1)
+        self.corr_stride = max(int(corr_stride if corr_stride is not None else big), 1)
+        self.desc = torch.zeros((batch, query_stride, 32), dtype=torch.uint8, device=dev)
+        self.valid = torch.ones((batch, query_stride), dtype=torch.uint8, device=dev) if with_valid else None
+        self.xyz = torch.zeros((batch, query_stride, 4), dtype=torch.float32, device=dev)
+        self.n_query = torch.zeros((batch,), dtype=torch.int32, device=dev)
+        self.graph_id = torch.zeros((batch,), dtype=torch.int64, device=dev)
+        self.match_counts = torch.zeros((batch, self.count_stride), dtype=torch.int32, device=dev)
+        self.best_keys = torch.zeros((batch, self.key_stride), dtype=torch.int32, device=dev)
+        self.candidates = torch.zeros((batch, max_candidates), dtype=torch.int32, device=dev)
+        self.n_candidates = torch.zeros((batch,), dtype=torch.int32, device=dev)
+        self.corr = torch.zeros((batch, max_candidates, self.corr_stride, 3), dtype=torch.int32, device=dev)
+        self.n_corr = torch.zeros((batch, max_candidates), dtype=torch.int32, device=dev)
+        self.status = torch.zeros((batch,), dtype=torch.int32, device=dev)
+        self.index_query = torch.zeros((batch,), dtype=torch.int64, device=dev)
+
+    def upload(self, b, graph_id, desc, xyz=None, valid=None):
+        import torch
+        dev = self.desc.device
+        d = _np(desc, np.uint8, (-1, 32))
+        n = d.shape[0]
+        if n:
+            self.desc[b, :n] = torch.from_numpy(d).to(dev)
+            if xyz is not None:
+                self.xyz[b, :n, :3] = torch.from_numpy(_np(xyz, np.float32, (-1, 3))).to(dev)
+        if valid is not None:
+            self.valid[b, :n] = torch.from_numpy(_np(valid, np.uint8, (-1,))).to(dev)
+        self.n_query[b], self.graph_id[b] = n, int(graph_id)
+
+    def descriptor(self):
+        d = _lib.PlaceQueries()
+        d.batch, d.query_stride = self.batch, self.query_stride
+        d.desc, d.xyz, d.n_query, d.graph_id = self.desc.data_ptr(), self.xyz.data_ptr(), self.n_query.data_ptr(), self.graph_id.data_ptr()
+        d.valid = self.valid.data_ptr() if self.valid is not None else None
+        d.count_stride, d.match_counts = self.count_stride, self.match_counts.data_ptr()
+        d.key_stride, d.best_keys = self.key_stride, self.best_keys.data_ptr()
+        d.corr_stride, d.candidates, d.n_candidates = self.corr_stride, self.candidates.data_ptr(), self.n_candidates.data_ptr()
+        d.corr, d.n_corr, d.status, d.index_query = self.corr.data_ptr(), self.n_corr.data_ptr(), self.status.data_ptr(), self.index_query.data_ptr()
+        return d
+
+    def result_of(self, b, maps=None):
+        """dict(status, index_query, candidates, corr [list of CORR_DTYPE], counts [maps])"""
+        n = int(self.n_candidates[b].item())
+        corr = []
+        for k in range(n):
+            m = int(self.n_corr[b, k].item())
+            raw = self.corr[b, k, :m].cpu().numpy()
+            c = np.zeros(m, CORR_DTYPE)
+            c["fixed_idx"], c["moving_idx"], c["response"] = raw[:, 0], raw[:, 1], raw[:, 2].view(np.float32)
+            corr.append(c)
+        counts = self.match_counts[b].cpu().numpy().view(np.uint32).astype(np.int64)
+        return dict(status=int(self.status[b].item()), index_query=int(self.index_query[b].item()),
+                    candidates=self.candidates[b, :n].cpu().numpy().tolist(), corr=corr,
+                    counts=counts[: maps] if maps is not None else counts)
+
+
+def place_query_batch(ctx, db, params, queries):
+    """enqueue the candidate search for every query of the batch on the context stream (asynchronous)"""
+    d = queries.descriptor()
+    rc = _lib.load().prs_place_query_batch(db._h, C.byref(params), C.byref(d))
+    _check(ctx, rc, "prs_place_query_batch")
+    return rc
+
+
+class LoopDetectorBatch:
+    """B query local maps -> candidate search -> one loop-closure pair slot per (query, candidate) -> brute-force matcher -> loop
+    aligner and verdict, all enqueued on the context stream with no host round trip.  Slot b * max_candidates + k holds query b
+    against its k-th candidate; slots without a candidate carry n = 0 and are never accepted."""
+
+    def __init__(self, device, db, batch, query_stride, max_candidates, moving_stride=None, with_valid=False, candidate_capacity=None):
+        _, _, big = db.size()
+        self.db, self.batch, self.max_candidates = db, int(batch), int(max_candidates)
+        self.queries = PlaceQueries(device, batch, query_stride, max_candidates, db, with_valid=with_valid)
+        ms = max(int(moving_stride if moving_stride is not None else big), 1)
+        slots = self.batch * self.max_candidates
+        # the matcher's candidate list per slot: by default room for every pair (0 = the matcher's own default, 16 x the larger cloud)
+        cap = query_stride * ms if candidate_capacity is None else int(candidate_capacity)
+        self.closures = LoopClosureBatch(device, slots, query_stride, ms, with_mask=False, candidate_capacity=cap)
+        # one set of point counts per slot: the gather writes the matcher's, the aligner reads the same tensors
+        self.closures.pairs.n_fixed, self.closures.pairs.n_moving = self.closures.clouds.n_fixed, self.closures.clouds.n_moving
+
+    def upload(self, b, graph_id, desc, xyz, valid=None):
+        self.queries.upload(b, graph_id, desc, xyz, valid)
+
+    def pairs_descriptor(self):
+        lc = self.closures
+        d = _lib.PlacePairs()
+        d.fixed_stride, d.moving_stride = lc.pairs.fixed_stride, lc.pairs.moving_stride
+        d.fixed_xyz, d.fixed_desc, d.n_fixed = lc.pairs.fixed.data_ptr(), lc.clouds.fixed_desc.data_ptr(), lc.clouds.n_fixed.data_ptr()
+        d.moving_xyz, d.moving_desc, d.n_moving = lc.pairs.moving.data_ptr(), lc.clouds.moving_desc.data_ptr(), lc.clouds.n_moving.data_ptr()
+        d.X = lc.pairs.X.data_ptr()
+        return d
+
+    def run(self, ctx, place_params_, matcher_params, align_params):
+        place_query_batch(ctx, self.db, place_params_, self.queries)
+        q, pairs = self.queries.descriptor(), self.pairs_descriptor()
+        _check(ctx, _lib.load().prs_place_gather_pairs(self.db._h, C.byref(place_params_), C.byref(q), C.byref(pairs)), "prs_place_gather_pairs")
+        lc = self.closures
+        # the aligner's point counts are the matcher's (one cloud pair per slot)
+        bruteforce_match_batch(ctx, matcher_params, lc.clouds)
+        return point_align_batch(ctx, align_params, lc.pairs)
+
+    def result_of(self, b):
+        """dict(candidates, poses [4, 4] per candidate, accepted per candidate, search result)"""
+        r = self.queries.result_of(b, self.db.size()[0])
+        slots = [b * self.max_candidates + k for k in range(len(r["candidates"]))]
+        return dict(candidates=r["candidates"], poses=[self.closures.pairs.X_of(s) for s in slots],
+                    accepted=[self.closures.pairs.result_of(s)["accepted"] for s in slots], search=r)
+
+
 # ---- landmark estimators + projective mergers (mapping/mergers, mapping/landmarks) ----
 EST_WEIGHTED_MEAN, EST_EKF, EST_SMOOTHER = 0, 1, 2
 MERGER_STEREO_TRIANGULATION, MERGER_STEREO_EKF, MERGER_DEPTH_EKF = 0, 1, 2

@@ -81,6 +81,17 @@ def conf_loop(names=("kitti", "euroc", "icl", "tum", "malaga")):
         f.write("\n")
 
 
+def conf_place(names=("kitti", "euroc", "icl", "tum", "malaga")):
+    """{config: place group} as formats.place_params reads it from the shipped .conf files (the loop detector's candidate search)"""
+    import json
+    sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+    from srrg2_proslam_amd import formats
+    out = {n: formats.place_params(formats.read_conf(os.path.join(REF, "configurations", n + ".conf"))) for n in names}
+    with open(os.path.join(OUT, "ref_conf_place.json"), "w") as f:
+        json.dump(out, f, indent=1, sort_keys=True)
+        f.write("\n")
+
+
 def main():
     k = os.path.join(DATA, "kitti")
     np.savez_compressed(
@@ -108,6 +119,7 @@ def main():
                         gt_threshold_100=scene_flow_gt(os.path.join(s, "gt_stereo_matching_threshold-100.txt")))
     conf_hot_path()
     conf_loop()
+    conf_place()
     for f in sorted(os.listdir(OUT)):
         if f.startswith("ref_"):
             print(f, os.path.getsize(os.path.join(OUT, f)) // 1024, "KiB")
