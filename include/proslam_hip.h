@@ -695,6 +695,30 @@ typedef struct {
                                  prs_align_batch.corr (fixed_idx -> measurement, moving_idx -> clipped scene) */
 } prs_merge_batch;
 
+/* Merges one frame into every map of the batch (asynchronous, on the context's stream).
+ * Status per map (result[b].status), every map on its own: a map with an error leaves the other maps of the launch unaffected.
+ *   PRS_ERR_RANGE      frame[b] outside [0, max_frames), n_points[b] outside [0, capacity], n_measured[b] < 0 or n_corr[b] < 0;
+ *                      or the correspondence vector names a landmark outside [0, n_points[b]) (after scene_index_map, where one is
+ *                      given) or a measurement outside [0, n_measured[b]), or a measurement that passes the appearance gate lies
+ *                      outside the bin grid of the canvas.
+ *   PRS_ERR_CAPACITY   n_measured[b] > measurement_stride or n_corr[b] > corr_stride (what prs_map_merge refuses on the host).
+ *   PRS_ERR_DUPLICATE  a landmark appears in two correspondences.
+ *     For these three the map's arrays, its pose table and n_points[b] are left exactly as they were and n_merged = n_added = 0.
+ *     Counts are tested first; of several faults of one correspondence vector the FIRST in vector order is reported, as a
+ *     sequential walk over the vector meets it (a duplicate counts at its second appearance).  A faulty vector is refused
+ *     before any landmark is updated, so it also goes before the two codes below.
+ *   PRS_ERR_HISTORY    (pose-based smoother) a landmark to update already holds max_measurements measurements.  The other
+ *                      landmarks of the frame have been updated; nothing is added; n_merged counts the updates made.
+ *   PRS_ERR_SCENE_FULL n_points[b] + the landmarks to add exceed capacity.  The frame's updates have been made, rows from
+ *                      n_points[b] on may be overwritten, n_points[b] itself is unchanged and n_added = 0.
+ *     After these two the map should be discarded or rebuilt: a sequential merger stops at the fault, this one does not.  The
+ *     same holds for a measurement outside the bin grid that only the addition step meets (no correspondence names it):
+ *     PRS_ERR_RANGE after the frame's updates.
+ *   >= 0               PRS_WARN_NO_MATCHES / PRS_WARN_LOW_RATIO bits; n_points[b] has grown by n_added.
+ * 2-D (mono) measurements carry no depth: that form only updates landmarks, also for a frame without correspondences.
+ * Call-level errors (return value, nothing launched, every map untouched): PRS_ERR_NULL (a required pointer unset),
+ * PRS_ERR_UNSUPPORTED (unknown merger / estimator or a combination no merger of the reference has, a bin narrower than one
+ * pixel, or a bin table + scene bitmap + pose cache beyond the 160 KiB of LDS), PRS_ERR_HIP. */
 PRS_API int prs_merge_batch_run(prs_context* ctx, const prs_merger_params* params, const prs_merge_batch* batch);
 
 /* ---- host, one local map: stateful handle mirroring the reference's merger object ---------------------------------

@@ -123,8 +123,28 @@ def _lib():
         L.orc_merge.restype = C.c_int
         L.orc_merge.argtypes = [C.POINTER(MergerParams), vp, vp, vp, C.c_int32, C.POINTER(MapStruct), vp, vp, C.c_int32, vp, C.c_int32, vp,
                                 C.POINTER(MergeResult)]
+        L.orc_smoother_trace.restype = None
+        L.orc_smoother_trace.argtypes = [vp, vp, C.c_int32]
         _bound = True
     return L
+
+
+class smoother_trace:
+    """test-only: `with smoother_trace(capacity) as t:` records, for every landmark the pose-based smoother optimises
+    inside the block, t.iterations[index] (iterations its loop ran, 0 = not optimised) and t.first_repeat[index] (iterations
+    after which its state first repeated an earlier one bit for bit, -1 = never)"""
+
+    def __init__(self, capacity):
+        self.iterations = np.zeros(capacity, np.uint32)
+        self.first_repeat = np.full(capacity, -1, np.int32)
+
+    def __enter__(self):
+        _lib().orc_smoother_trace(self.iterations.ctypes.data, self.first_repeat.ctypes.data, len(self.iterations))
+        return self
+
+    def __exit__(self, *exc):
+        _lib().orc_smoother_trace(None, None, 0)
+        return False
 
 
 def set_pose(poses, frame, sensor_in_world):

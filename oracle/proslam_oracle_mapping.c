@@ -342,6 +342,19 @@ static void solve3_full_pivot(const float* A_in, const float* rhs, float* x) {
   }
 }
 
+/* test-only trace of the optimisation loop (orc_smoother_trace): per landmark the iterations it ran and the first
+ * iteration count at which its state repeated an earlier one bit for bit (-1: never) */
+static uint32_t* trace_iterations  = NULL;
+static int32_t* trace_first_repeat = NULL;
+static int32_t trace_capacity      = 0;
+enum { TRACE_STATES = 256 };
+
+void orc_smoother_trace(uint32_t* iterations, int32_t* first_repeat, int32_t capacity) {
+  trace_iterations   = iterations;
+  trace_first_repeat = first_repeat;
+  trace_capacity     = (iterations && first_repeat) ? capacity : 0;
+}
+
 static int estimate_smoother(const orc_estimator_params* P, const estimator_transforms* t, const orc_frame_pose* poses, int32_t frame,
                              orc_map* map, int idx, const float* measurement, const float* landmark_in_sensor) {
   map->inlier[idx] = 0; /* :13 */
@@ -375,7 +388,20 @@ static int estimate_smoother(const orc_estimator_params* P, const estimator_tran
   const float max_kernel   = P->maximum_reprojection_error_pixels_squared;
   float total_previous     = 0.0f; /* :46 */
   uint32_t number_of_inliers = 0;
+  const int traced = idx < trace_capacity;
+  float visited[TRACE_STATES][3];
+  uint32_t iterations_run = 0;
+  int32_t first_repeat    = -1;
   for (uint32_t it = 0; it < P->maximum_number_of_iterations; ++it) {
+    if (traced && it < TRACE_STATES) {
+      memcpy(visited[it], world, sizeof(float) * 3); /* the state iteration `it` starts from */
+      for (uint32_t j = 0; j < it && first_repeat < 0; ++j) {
+        if (memcmp(visited[j], world, sizeof(float) * 3) == 0) {
+          first_repeat = (int32_t) it;
+        }
+      }
+    }
+    iterations_run = it + 1;
     float H[9], b[3];
     memset(H, 0, sizeof(H));
     memset(b, 0, sizeof(b));
@@ -439,6 +465,10 @@ static int estimate_smoother(const orc_estimator_params* P, const estimator_tran
       break;
     }
     total_previous = total_error_squared;
+  }
+  if (traced) {
+    trace_iterations[idx]   = iterations_run;
+    trace_first_repeat[idx] = first_repeat;
   }
   if (number_of_inliers > map->n_opt[idx]) { /* :122-127 */
     add_optimization_result(map, idx, world, NULL);
@@ -616,7 +646,8 @@ int orc_merge(const orc_merger_params* P,
   }
   /* _addPoints (:56-57, :154-161, :210-305) */
   const int initial = map->n_points;
-  if (rc == 0 && (n_corr == 0 || ((uint32_t) n_merged < P->target_number_of_merges && n_merged < n_measured))) {
+  /* (mono measurements (u, v) carry no depth: that form only updates, whatever the correspondences) */
+  if (rc == 0 && dim > 2 && (n_corr == 0 || ((uint32_t) n_merged < P->target_number_of_merges && n_merged < n_measured))) {
     int32_t* slot_of_bin = (int32_t*) malloc(sizeof(int32_t) * (size_t) nbr * nbc);
     int32_t* cand        = (int32_t*) malloc(sizeof(int32_t) * (size_t) (n_measured > 0 ? n_measured : 1));
     int n_cand           = 0;

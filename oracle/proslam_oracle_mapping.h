@@ -112,6 +112,12 @@ typedef struct {
   int32_t flags; /* ORC_WARN_* bits: NO_MATCHES = all merge attempts failed, LOW_RATIO = low merge ratio */
 } orc_merge_result;
 
+/* Test-only: while set, every pose-based smoother optimisation of a landmark with index < capacity records the iterations
+ * its loop ran (iterations[index]) and the number of iterations after which its state first repeated an earlier state of
+ * the same loop bit for bit (first_repeat[index], -1: never).  Landmarks that are averaged (too few measurements) are not
+ * written.  NULL switches the trace off.  Not thread-safe. */
+void orc_smoother_trace(uint32_t* iterations, int32_t* first_repeat, int32_t capacity);
+
 /* MergerProjective_::compute (merger_projective_impl.cpp:8-190) for one frame.
  * measurement: [n_meas][measurement_dim] image-space points + descriptors; correspondences index
  * (fixed_idx -> scene, moving_idx -> measurement); scene_index_map optional (clipped -> full scene index).

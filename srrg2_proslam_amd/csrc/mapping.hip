@@ -853,8 +853,12 @@ __global__ __launch_bounds__(kMergeThreads) void merge_kernel(const MergeArgs a)
   const prs_merger_params& P = a.p;
   const int nbins   = a.nbr * a.nbc;
   int n_points      = B.n_points[map];
-  const int n_meas  = B.n_measured[map] < 0 ? 0 : (B.n_measured[map] > B.measurement_stride ? B.measurement_stride : B.n_measured[map]);
-  const int n_corr  = B.n_corr ? (B.n_corr[map] < 0 ? 0 : (B.n_corr[map] > B.corr_stride ? B.corr_stride : B.n_corr[map])) : 0;
+  // counts as the caller gave them: a negative one is PRS_ERR_RANGE, one beyond its stride PRS_ERR_CAPACITY (below);
+  // the clamped values only keep the loops of a refused frame inside the rows
+  const int n_meas_in = B.n_measured[map];
+  const int n_corr_in = B.n_corr ? B.n_corr[map] : 0;
+  const int n_meas  = n_meas_in < 0 ? 0 : (n_meas_in > B.measurement_stride ? B.measurement_stride : n_meas_in);
+  const int n_corr  = n_corr_in < 0 ? 0 : (n_corr_in > B.corr_stride ? B.corr_stride : n_corr_in);
   const int frame   = B.frame[map];
   const float4* __restrict__ zs = reinterpret_cast<const float4*>(B.measurement) + (size_t) map * B.measurement_stride;
   const uint8_t* __restrict__ zdesc = B.measurement_desc + (size_t) map * B.measurement_stride * 32;
@@ -885,7 +889,10 @@ __global__ __launch_bounds__(kMergeThreads) void merge_kernel(const MergeArgs a)
       sh.world_in_local_map[i]   = Wl[i];
       sh.measurement_in_scene[i] = Ts[i];
     }
-    sh.error    = (frame < 0 || frame >= B.max_frames || n_points < 0 || n_points > B.capacity) ? PRS_ERR_RANGE : 0;
+    sh.error    = (frame < 0 || frame >= B.max_frames || n_points < 0 || n_points > B.capacity || n_meas_in < 0 || n_corr_in < 0) ? PRS_ERR_RANGE : 0;
+    if (!sh.error && (n_meas_in > B.measurement_stride || n_corr_in > B.corr_stride)) {
+      sh.error = PRS_ERR_CAPACITY;  // (the host handle refuses the same condition, map_api.hip: prs_map_merge)
+    }
     sh.n_merged = 0;
     sh.base     = 0;
     sh.n_work   = 0;
@@ -952,6 +959,8 @@ __global__ __launch_bounds__(kMergeThreads) void merge_kernel(const MergeArgs a)
       s = imap[s];
     }
     const int m = B.corr_from_aligner ? cr.fixed_idx : cr.moving_idx;
+    // Any fault of the vector only raises a flag here (which lane's store lands last is arbitrary, and which of two
+    // entries naming one landmark meets the other's bit is too); the code reported is settled below, in vector order.
     if (s < 0 || s >= n_points || m < 0 || m >= n_meas) {
       sh.error = PRS_ERR_RANGE;
       continue;
@@ -959,9 +968,6 @@ __global__ __launch_bounds__(kMergeThreads) void merge_kernel(const MergeArgs a)
     if (atomicOr(&seen[s >> 5], 1u << (s & 31)) & (1u << (s & 31))) {
       sh.error = PRS_ERR_DUPLICATE;
       continue;
-    }
-    if (kFront) {
-      B.inlier[(size_t) map * B.capacity + s] = 0;  // :64
     }
     if (cr.response > P.maximum_distance_appearance) {  // :70-73
       continue;
@@ -977,6 +983,41 @@ __global__ __launch_bounds__(kMergeThreads) void merge_kernel(const MergeArgs a)
     }
   }
   __syncthreads();
+  if (sh.error && kFront) {
+    // A faulty vector (rare, and the frame is refused whole): the FIRST fault in vector order is the one reported, as
+    // a sequential walk over the vector would meet it (:59-122).  One lane repeats the walk on a cleared bitmap.
+    for (int i = tid; i < (B.capacity + 31) / 32; i += kMergeThreads) {
+      seen[i] = 0u;
+    }
+    __syncthreads();
+    if (tid == 0) {
+      int code = 0;
+      for (int c = 0; c < n_corr && !code; ++c) {
+        const prs_corr cr = corr[c];
+        int s             = B.corr_from_aligner ? cr.moving_idx : cr.fixed_idx;
+        if (s >= 0 && s < B.capacity && imap) {
+          s = imap[s];
+        }
+        const int m = B.corr_from_aligner ? cr.fixed_idx : cr.moving_idx;
+        if (s < 0 || s >= n_points || m < 0 || m >= n_meas) {
+          code = PRS_ERR_RANGE;
+        } else if (seen[s >> 5] & (1u << (s & 31))) {
+          code = PRS_ERR_DUPLICATE;
+        } else {
+          seen[s >> 5] |= 1u << (s & 31);
+          if (!(cr.response > P.maximum_distance_appearance) && P.enable_binning) {
+            const float4 z    = zs[m];
+            const uint32_t br = bin_of(z.y, a.row_w), bc = bin_of(z.x, a.col_w);
+            if (br >= (uint32_t) a.nbr || bc >= (uint32_t) a.nbc) {
+              code = PRS_ERR_RANGE;
+            }
+          }
+        }
+      }
+      sh.error = code ? code : sh.error;
+    }
+    __syncthreads();
+  }
   if (sh.error) {
     if (tid == 0 && kFront) {
       B.result[map].n_merged = 0;
@@ -993,12 +1034,13 @@ __global__ __launch_bounds__(kMergeThreads) void merge_kernel(const MergeArgs a)
   // ---- _updatePoint for every correspondence that owns its bin (:124-128, :192-208) -----------------------
   for (int c = tid; kFront && c < n_corr; c += kMergeThreads) {
     const prs_corr cr = corr[c];
-    if (cr.response > P.maximum_distance_appearance) {
-      continue;
-    }
     const int sc   = B.corr_from_aligner ? cr.moving_idx : cr.fixed_idx;
     const int s    = imap ? imap[sc] : sc;
     const int m    = B.corr_from_aligner ? cr.fixed_idx : cr.moving_idx;
+    B.inlier[(size_t) map * B.capacity + s] = 0;  // :64 (here, not in the loop above: a refused vector leaves the map untouched)
+    if (cr.response > P.maximum_distance_appearance) {
+      continue;
+    }
     const float4 z = zs[m];
     if (P.enable_binning) {
       const uint32_t br = bin_of(z.y, a.row_w), bc = bin_of(z.x, a.col_w);
@@ -1100,7 +1142,9 @@ __global__ __launch_bounds__(kMergeThreads) void merge_kernel(const MergeArgs a)
 
   // ---- _addPoints (:55-57, :154-161, :210-305) -------------------------------------------------------------
   int n_added = 0;
-  if (!sh.error && (n_corr == 0 || ((uint32_t) n_merged < P.target_number_of_merges && n_merged < n_meas))) {
+  // (DIM 2: mono measurements (u, v) carry no depth, the third column of their rows is not defined: that form only
+  // updates, also for a frame without correspondences)
+  if (!sh.error && DIM > 2 && (n_corr == 0 || ((uint32_t) n_merged < P.target_number_of_merges && n_merged < n_meas))) {
     if (P.enable_binning) {
       // per free bin: the first measurement (it fixes the bin's place in the output) and the best one
       for (int i = tid; i < n_meas; i += kMergeThreads) {
@@ -1483,6 +1527,18 @@ int merge_batch_launch(prs_context* ctx, const prs_merger_params* params, const 
   } else if (e.type == PRS_EST_SMOOTHER && (ctx->merge_fused || a.stamps)) {
     launch(merge_kernel<PRS_EST_SMOOTHER, 4, 0>);
   } else if (e.type == PRS_EST_SMOOTHER) {
+    // smoother_kernel's own request (pose cache + ring): settled before anything is launched, so that a refusal leaves the maps untouched
+    const size_t lds_s = ((sizeof(MergeShared) + 15) & ~(size_t) 15) + (((size_t) b.max_frames * 21 + 3) & ~(size_t) 3) * sizeof(float) +
+                         (size_t) kSmootherRing * 5 * 64 * sizeof(float);
+    if (lds_s > 160u * 1024u) {
+      return ctx_fail(ctx, PRS_ERR_UNSUPPORTED, "prs_merge_batch_run: pose table does not fit the 160 KiB LDS");
+    }
+    if (lds_s > 64u * 1024u) {  // (the pose cache of a long local map)
+      e2 = hipFuncSetAttribute(reinterpret_cast<const void*>(smoother_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds_s);
+      if (e2 != hipSuccess) {
+        return ctx_fail_hip(ctx, e2, "prs_merge_batch_run: smoother kernel LDS request");
+      }
+    }
     a.carry = static_cast<MergeCarry*>(ctx_device_scratch_slot(ctx, 1, (size_t) b.batch * sizeof(MergeCarry)));
     if (!a.carry) {
       return ctx_fail(ctx, PRS_ERR_HIP, "prs_merge_batch_run: carry allocation failed");
@@ -1498,8 +1554,6 @@ int merge_batch_launch(prs_context* ctx, const prs_merger_params* params, const 
     (void) hipMemsetAsync(a.tail_count, 0, sizeof(int), ctx_stream(ctx));
     launch(merge_kernel<PRS_EST_SMOOTHER, 4, 1>);
     if (e2 == hipSuccess) {
-      const size_t lds_s = ((sizeof(MergeShared) + 15) & ~(size_t) 15) + (((size_t) b.max_frames * 21 + 3) & ~(size_t) 3) * sizeof(float) +
-                           (size_t) kSmootherRing * 5 * 64 * sizeof(float);
       hipLaunchKernelGGL(smoother_kernel, dim3(b.batch), dim3(kSmootherThreads), lds_s, ctx_stream(ctx), a);
       const int tail_waves = b.batch < 2048 ? b.batch : 2048;  // grid-stride over however many stragglers there are
       hipLaunchKernelGGL(smoother_tail_kernel, dim3(tail_waves), dim3(kSmootherThreads), 0, ctx_stream(ctx), a);

@@ -105,3 +105,25 @@ def test_merger_cases_through_the_host_handle(B, hip_ctx, oracle):
         h.merge(_gpu_params(case["params"]), rm.I4, rm.I4, case["fixed"], case["desc"], case["corr"][:4])
     assert ei.value.status == ops._lib.ERR_CAPACITY
     h.close()
+    # two DIFFERENT transforms (setMeasurementInWorld / setMeasurementInScene of a local map whose origin is not the world's):
+    # three frames of tests/merge_cases.py through the handle, every readable array against the checker
+    from tests import merge_cases as mc
+    for kind in ("weighted_mean", "smoother", "stereo_ekf", "depth_ekf"):
+        seq = mc.Sequence(kind, 2100, 200, 3, response_max=50)
+        P = mc.merger_params(kind, 1)
+        m, poses = seq.new_map(1024), om.pose_table(3)
+        h = ops.MapHandle(hip_ctx, 1024, seq.max_meas, max_frames=3, max_measured=1024)
+        for k in range(3):
+            Tw, Ts, z, desc, corr = seq.inputs(k, m)
+            assert np.abs(Tw - Ts).max() > 10.0
+            rc, res = om.merge(P, Tw, Ts, poses, k, m, z, desc, corr)
+            assert rc == 0
+            got = h.merge(_gpu_params(P), Tw, Ts, z, desc, corr)
+            assert got == (res.n_merged, res.n_added, res.flags), (kind, k, got)
+            sc = h.scene()
+            n = m.n_points
+            assert h.size() == (n, k + 1)
+            assert np.array_equal(bits(sc["coords"]), bits(m.coords[:n, :3])) and np.array_equal(bits(sc["state"]), bits(m.state[:n, :3])), (kind, k)
+            assert np.array_equal(sc["desc"], m.desc[:n]) and np.array_equal(sc["n_opt"], m.n_opt[:n]) and np.array_equal(sc["inlier"], m.inlier[:n]), (kind, k)
+        assert m.n_opt[: m.n_points].max() >= 2 and np.abs(m.coords[: m.n_points, :3] - m.state[: m.n_points, :3]).max() > 10.0
+        h.close()
