@@ -23,23 +23,77 @@ int ctx_fail_hip(prs_context* ctx, hipError_t e, const char* what) {
   return PRS_ERR_HIP;
 }
 
-void* ctx_device_scratch(prs_context* ctx, size_t bytes) {
-  if (bytes <= ctx->d_scratch_size) {
-    return ctx->d_scratch;
+void* ctx_arena(prs_context* ctx, Arena arena, size_t bytes) {
+  auto& a = ctx->arena[arena];
+  if (bytes <= a.size) {
+    return a.p;
   }
-  if (ctx->d_scratch) {
-    (void) hipStreamSynchronize(ctx->stream);
-    (void) hipFree(ctx->d_scratch);
-    ctx->d_scratch      = nullptr;
-    ctx->d_scratch_size = 0;
+  const bool pinned = arena == ARENA_PINNED;
+  if (a.p) {
+    (void) hipStreamSynchronize(ctx->stream);  // whatever was enqueued on the old block finishes before it goes
+    (void) (pinned ? hipHostFree(a.p) : hipFree(a.p));
+    a.p    = nullptr;
+    a.size = 0;
   }
-  size_t want = bytes + bytes / 2 + 4096;
-  if (hipMalloc(&ctx->d_scratch, want) != hipSuccess) {
-    ctx->d_scratch = nullptr;
+  // slack: the default staging pair grows by half, the work arenas and the two small staging arenas by a quarter
+  const size_t want = bytes + bytes / (arena == ARENA_STAGE || pinned ? 2 : 4) + 4096;
+  void* p           = nullptr;
+  if ((pinned ? hipHostMalloc(&p, want, hipHostMallocDefault) : hipMalloc(&p, want)) != hipSuccess) {
     return nullptr;
   }
-  ctx->d_scratch_size = want;
-  return ctx->d_scratch;
+  a.p    = p;
+  a.size = want;
+  return p;
+}
+
+int Staging::commit() {
+  if (n_ > kMaxSections) {
+    return ctx_fail(ctx_, PRS_ERR_UNSUPPORTED, (std::string(entry_) + ": too many staging sections").c_str());
+  }
+  size_t mirrored = 0;
+  for (int i = 0; i < n_; ++i) {
+    for (int k = 0; k < 2; ++k) {
+      if (rec_[i].flags & (k == 0 ? kUp : kDown)) {
+        first_[k] = first_[k] < 0 ? i : first_[k];
+        last_[k]  = i;
+      }
+    }
+    if (rec_[i].flags) {
+      mirrored = rec_[i].off + align256(rec_[i].bytes);
+    }
+  }
+  for (int k = 0; k < 2; ++k) {
+    for (int i = first_[k]; i < last_[k]; ++i) {
+      if (rec_[i].bytes > 0 && !(rec_[i].flags & (k == 0 ? kUp : kDown))) {
+        return ctx_fail(ctx_, PRS_ERR_UNSUPPORTED, (std::string(entry_) + ": a staging section lies inside a copy it is not part of").c_str());
+      }
+    }
+  }
+  d_ = static_cast<unsigned char*>(ctx_arena(ctx_, arena_, end_));
+  h_ = static_cast<unsigned char*>(ctx_arena(ctx_, ARENA_PINNED, mirrored));
+  if (!d_ || !h_) {
+    return ctx_fail(ctx_, PRS_ERR_HIP, (std::string(entry_) + ": scratch allocation failed").c_str());
+  }
+  return PRS_OK;
+}
+
+int Staging::copy(size_t off, size_t bytes, bool to_device) {
+  hipError_t e = to_device ? hipMemcpyAsync(d_ + off, h_ + off, bytes, hipMemcpyHostToDevice, ctx_->stream)
+                           : hipMemcpyAsync(h_ + off, d_ + off, bytes, hipMemcpyDeviceToHost, ctx_->stream);
+  if (e == hipSuccess && !to_device) {
+    e = hipStreamSynchronize(ctx_->stream);
+  }
+  return e == hipSuccess ? PRS_OK : ctx_fail_hip(ctx_, e, (std::string(entry_) + (to_device ? " upload" : " download")).c_str());
+}
+
+int Staging::upload(size_t last_bytes) {
+  const Rec &a = rec_[first_[0]], &b = rec_[last_[0]];
+  return copy(a.off, b.off + (last_bytes == kAll ? b.bytes : last_bytes) - a.off, true);
+}
+
+int Staging::download() {
+  const Rec &a = rec_[first_[1]], &b = rec_[last_[1]];
+  return copy(a.off, b.off + b.bytes - a.off, false);
 }
 
 const float* ctx_info_scale_table(prs_context* ctx) {
@@ -62,44 +116,6 @@ const float* ctx_info_scale_table(prs_context* ctx) {
     ctx->d_info_lut = d;
   }
   return ctx->d_info_lut;
-}
-
-void* ctx_device_scratch_slot(prs_context* ctx, int slot, size_t bytes) {
-  if (bytes <= ctx->d_slot_size[slot]) {
-    return ctx->d_slot[slot];
-  }
-  if (ctx->d_slot[slot]) {
-    (void) hipStreamSynchronize(ctx->stream);
-    (void) hipFree(ctx->d_slot[slot]);
-    ctx->d_slot[slot]      = nullptr;
-    ctx->d_slot_size[slot] = 0;
-  }
-  size_t want = bytes + bytes / 4 + 4096;
-  if (hipMalloc(&ctx->d_slot[slot], want) != hipSuccess) {
-    ctx->d_slot[slot] = nullptr;
-    return nullptr;
-  }
-  ctx->d_slot_size[slot] = want;
-  return ctx->d_slot[slot];
-}
-
-void* ctx_pinned_scratch(prs_context* ctx, size_t bytes) {
-  if (bytes <= ctx->h_pinned_size) {
-    return ctx->h_pinned;
-  }
-  if (ctx->h_pinned) {
-    (void) hipStreamSynchronize(ctx->stream);
-    (void) hipHostFree(ctx->h_pinned);
-    ctx->h_pinned      = nullptr;
-    ctx->h_pinned_size = 0;
-  }
-  size_t want = bytes + bytes / 2 + 4096;
-  if (hipHostMalloc(&ctx->h_pinned, want, hipHostMallocDefault) != hipSuccess) {
-    ctx->h_pinned = nullptr;
-    return nullptr;
-  }
-  ctx->h_pinned_size = want;
-  return ctx->h_pinned;
 }
 
 unsigned long long* ctx_stamps(prs_context* ctx, size_t bytes) {
@@ -135,10 +151,6 @@ void ctx_report_stamps(prs_context* ctx, int blocks, int n_stamps, const char* l
     total += acc / blocks;
   }
   fprintf(stderr, " | total %.0f\n", total);
-}
-
-static inline size_t align256(size_t v) {
-  return (v + 255) / 256 * 256;
 }
 
 } // namespace prs
@@ -232,21 +244,15 @@ int prs_context_destroy(prs_context* ctx) {
   if (ctx->align_job && ctx->align_job_free) {
     ctx->align_job_free(ctx->align_job);
   }
-  if (ctx->d_scratch) {
-    (void) hipFree(ctx->d_scratch);
-  }
-  if (ctx->h_pinned) {
-    (void) hipHostFree(ctx->h_pinned);
-  }
   if (ctx->d_stamps) {
     (void) hipFree(ctx->d_stamps);
   }
   if (ctx->d_info_lut) {
     (void) hipFree(ctx->d_info_lut);
   }
-  for (int i = 0; i < 4; ++i) {
-    if (ctx->d_slot[i]) {
-      (void) hipFree(ctx->d_slot[i]);
+  for (int i = 0; i < ARENA_COUNT; ++i) {
+    if (ctx->arena[i].p) {
+      (void) (i == ARENA_PINNED ? hipHostFree(ctx->arena[i].p) : hipFree(ctx->arena[i].p));
     }
   }
   if (ctx->own) {
@@ -371,71 +377,55 @@ int prs_stereo_match(prs_context* ctx,
     return ctx_fail(ctx, PRS_ERR_CAPACITY, "prs_stereo_match: capacity < n_left");
   }
   (void) hipSetDevice(ctx->device);
-  *n_out           = 0;
-  const int stride = n_left > n_right ? (n_left > 0 ? n_left : 1) : (n_right > 0 ? n_right : 1);
-  // one block on the device and a pinned mirror with the same layout: [ matches | meta | left kp | right kp | left rows | right rows ];
-  // ONE upload of [meta .. right rows] from pinned memory, the launch, ONE download of [matches | meta]
-  const size_t sz_kp   = align256(sizeof(prs_kp2) * (size_t) stride);
-  const size_t sz_desc = align256((size_t) PRS_DESC_BYTES * (size_t) stride);
-  const size_t sz_corr = align256(sizeof(prs_corr) * (size_t) stride);
-  const size_t off_meta = sz_corr, off_kpl = off_meta + 256, off_kpr = off_kpl + sz_kp, off_dl = off_kpr + sz_kp, off_dr = off_dl + sz_desc;
-  const size_t total    = off_dr + sz_desc;
-  unsigned char* d      = static_cast<unsigned char*>(ctx_device_scratch(ctx, total));
-  unsigned char* h      = static_cast<unsigned char*>(ctx_pinned_scratch(ctx, total));
-  if (!d || !h) {
-    return ctx_fail(ctx, PRS_ERR_HIP, "prs_stereo_match: scratch allocation failed");
-  }
-  int32_t* d_meta = reinterpret_cast<int32_t*>(d + off_meta);  // n_left, n_right, n_matches, status
-  int32_t* h_meta = reinterpret_cast<int32_t*>(h + off_meta);
-  hipStream_t s   = ctx->stream;
-  hipError_t e    = hipSuccess;
-  h_meta[0] = n_left, h_meta[1] = n_right, h_meta[2] = 0, h_meta[3] = 0;
+  *n_out              = 0;
+  const size_t stride = (size_t) (n_left > n_right ? (n_left > 0 ? n_left : 1) : (n_right > 0 ? n_right : 1));
+  struct Meta {
+    int32_t n_left, n_right, n_matches, status;
+  };
+  // [ matches | meta | left kp | right kp | left rows | right rows ]: ONE upload of [meta .. the last right row], the launch,
+  // ONE download of [matches | meta]
+  Staging st(ctx, "prs_stereo_match");
+  auto matches = st.down<prs_corr>(stride);
+  auto meta    = st.both<Meta>(1);
+  auto kp_l    = st.up<prs_kp2>(stride);
+  auto kp_r    = st.up<prs_kp2>(stride);
+  auto desc_l  = st.up<uint8_t>(PRS_DESC_BYTES * stride);
+  auto desc_r  = st.up<uint8_t>(PRS_DESC_BYTES * stride);
+  PRS_TRY(st.commit());
+  *meta.h() = {n_left, n_right, 0, 0};
   if (n_left > 0) {
-    memcpy(h + off_kpl, left, sizeof(prs_kp2) * (size_t) n_left);
-    memcpy(h + off_dl, desc_left, (size_t) PRS_DESC_BYTES * (size_t) n_left);
+    memcpy(kp_l.h(), left, sizeof(prs_kp2) * (size_t) n_left);
+    memcpy(desc_l.h(), desc_left, (size_t) PRS_DESC_BYTES * (size_t) n_left);
   }
   if (n_right > 0) {
-    memcpy(h + off_kpr, right, sizeof(prs_kp2) * (size_t) n_right);
-    memcpy(h + off_dr, desc_right, (size_t) PRS_DESC_BYTES * (size_t) n_right);
+    memcpy(kp_r.h(), right, sizeof(prs_kp2) * (size_t) n_right);
+    memcpy(desc_r.h(), desc_right, (size_t) PRS_DESC_BYTES * (size_t) n_right);
   }
-#define PRS_TRY(x)                                  \
-  do {                                              \
-    e = (x);                                        \
-    if (e != hipSuccess) {                          \
-      return ctx_fail_hip(ctx, e, "prs_stereo_match"); \
-    }                                               \
-  } while (0)
-  PRS_TRY(hipMemcpyAsync(d + off_meta, h + off_meta, off_dr + (size_t) PRS_DESC_BYTES * (size_t) (n_right > 0 ? n_right : 0) - off_meta, hipMemcpyHostToDevice, s));
+  PRS_TRY(st.upload((size_t) PRS_DESC_BYTES * (size_t) n_right));
   prs_stereo_batch b;
   memset(&b, 0, sizeof(b));
   b.batch      = 1;
-  b.stride     = stride;
-  b.left_kp    = reinterpret_cast<prs_kp2*>(d + off_kpl);
-  b.left_desc  = d + off_dl;
-  b.n_left     = d_meta + 0;
-  b.right_kp   = reinterpret_cast<prs_kp2*>(d + off_kpr);
-  b.right_desc = d + off_dr;
-  b.n_right    = d_meta + 1;
-  b.matches    = reinterpret_cast<prs_corr*>(d);
-  b.n_matches  = d_meta + 2;
-  b.status     = d_meta + 3;
-  const int rc = stereo_match_batch_launch(ctx, params, &b);
-  if (rc != PRS_OK) {
-    return rc;
+  b.stride     = (int32_t) stride;
+  b.left_kp    = kp_l.d();
+  b.left_desc  = desc_l.d();
+  b.n_left     = &meta.d()->n_left;
+  b.right_kp   = kp_r.d();
+  b.right_desc = desc_r.d();
+  b.n_right    = &meta.d()->n_right;
+  b.matches    = matches.d();
+  b.n_matches  = &meta.d()->n_matches;
+  b.status     = &meta.d()->status;
+  PRS_TRY(stereo_match_batch_launch(ctx, params, &b));
+  PRS_TRY(st.download());
+  const Meta& m = *meta.h();
+  if (m.status < 0) {
+    return ctx_fail(ctx, m.status, "prs_stereo_match: keypoint outside the supported domain (0<=u<32768, 0<=v<image_rows)");
   }
-  // (a frame has at most n_left matches: the copy covers them and the meta words behind the match array)
-  const size_t lo = 0;
-  PRS_TRY(hipMemcpyAsync(h + lo, d + lo, off_meta + 16 - lo, hipMemcpyDeviceToHost, s));
-  PRS_TRY(hipStreamSynchronize(s));
-#undef PRS_TRY
-  if (h_meta[3] < 0) {
-    return ctx_fail(ctx, h_meta[3], "prs_stereo_match: keypoint outside the supported domain (0<=u<32768, 0<=v<image_rows)");
+  if (m.n_matches > 0) {
+    memcpy(out, matches.h(), sizeof(prs_corr) * (size_t) m.n_matches);
   }
-  if (h_meta[2] > 0) {
-    memcpy(out, h, sizeof(prs_corr) * (size_t) h_meta[2]);
-  }
-  *n_out = h_meta[2];
-  return h_meta[3];
+  *n_out = m.n_matches;
+  return m.status;
 }
 
 int prs_align_batch_run(prs_context* ctx, const prs_pcf_params* finder, const prs_aligner_params* aligner, const prs_align_batch* batch, int32_t mode) {
@@ -506,32 +496,15 @@ int prs_triangulate(prs_context* ctx, const prs_triangulator_params* params, con
     return PRS_WARN_EMPTY_INPUT;
   }
   (void) hipSetDevice(ctx->device);
-  const size_t bytes = sizeof(float) * 4 * (size_t) n;
-  unsigned char* d   = static_cast<unsigned char*>(ctx_device_scratch(ctx, 2 * align256(bytes)));
-  float* h_in        = static_cast<float*>(ctx_pinned_scratch(ctx, 2 * align256(bytes)));  // [measurements | points]: pinned both ways
-  if (!d || !h_in) {
-    return ctx_fail(ctx, PRS_ERR_HIP, "prs_triangulate: scratch allocation failed");
-  }
-  float* h      = reinterpret_cast<float*>(reinterpret_cast<unsigned char*>(h_in) + align256(bytes));
-  float* d_in   = reinterpret_cast<float*>(d);
-  float* d_out  = reinterpret_cast<float*>(d + align256(bytes));
-  hipStream_t s = ctx->stream;
-  memcpy(h_in, uvuv, bytes);
-  hipError_t e  = hipMemcpyAsync(d_in, h_in, bytes, hipMemcpyHostToDevice, s);
-  if (e != hipSuccess) {
-    return ctx_fail_hip(ctx, e, "prs_triangulate upload");
-  }
-  const int rc = triangulate_launch(ctx, params, d_in, n, d_out);
-  if (rc != PRS_OK) {
-    return rc;
-  }
-  e = hipMemcpyAsync(h, d_out, bytes, hipMemcpyDeviceToHost, s);
-  if (e == hipSuccess) {
-    e = hipStreamSynchronize(s);
-  }
-  if (e != hipSuccess) {
-    return ctx_fail_hip(ctx, e, "prs_triangulate download");
-  }
+  Staging st(ctx, "prs_triangulate");  // [measurements | points]: pinned both ways
+  auto in  = st.up<float>(4 * (size_t) n);
+  auto pts = st.down<float>(4 * (size_t) n);
+  PRS_TRY(st.commit());
+  memcpy(in.h(), uvuv, sizeof(float) * 4 * (size_t) n);
+  PRS_TRY(st.upload());
+  PRS_TRY(triangulate_launch(ctx, params, in.d(), n, pts.d()));
+  PRS_TRY(st.download());
+  const float* h = pts.h();
   for (int32_t i = 0; i < n; ++i) {
     xyz[3 * i + 0] = h[4 * i + 0];
     xyz[3 * i + 1] = h[4 * i + 1];
@@ -584,66 +557,51 @@ int prs_scene_clip(prs_context* ctx,
     return ctx_fail(ctx, PRS_ERR_CAPACITY, "prs_scene_clip: output capacity below the scene size");
   }
   (void) hipSetDevice(ctx->device);
-  const size_t nn      = (size_t) n;
-  const size_t b_xyzw  = align256(nn * 16);
-  const size_t b_desc  = scene_desc ? align256(nn * PRS_DESC_BYTES) : 0;
-  const size_t b_idx   = align256(nn * 4);
-  const size_t b_small = 256;  // n_scene, pose, n_clipped, status
-  const size_t total   = 2 * b_xyzw + 2 * b_desc + b_idx + b_small;
-  unsigned char* d     = static_cast<unsigned char*>(ctx_device_scratch(ctx, total));
-  unsigned char* h     = static_cast<unsigned char*>(ctx_pinned_scratch(ctx, total));
-  if (!d || !h) {
-    return ctx_fail(ctx, PRS_ERR_HIP, "prs_scene_clip: scratch allocation failed");
-  }
-  // staging layout (same on both sides): [inputs: xyzw | desc | small] [outputs: xyzw | desc | idx]
-  const size_t o_in_xyzw = 0, o_in_desc = b_xyzw, o_small = b_xyzw + b_desc;
-  const size_t o_out_xyzw = o_small + b_small, o_out_desc = o_out_xyzw + b_xyzw, o_out_idx = o_out_desc + b_desc;
-  memcpy(h + o_in_xyzw, scene_xyzw, nn * 16);
+  const size_t nn = (size_t) n;
+  struct Meta {
+    int32_t n_scene, n_clipped, status, pad;
+    float robot_in_local_map[16];
+  };
+  // [inputs: xyzw | desc | meta] [outputs: xyzw | desc | idx]
+  Staging st(ctx, "prs_scene_clip");
+  auto in_xyzw  = st.up<float>(nn * 4);
+  auto in_desc  = st.up<uint8_t>(scene_desc ? nn * PRS_DESC_BYTES : 0);
+  auto meta     = st.both<Meta>(1);
+  auto out_xyzw = st.down<float>(nn * 4);
+  auto out_desc = st.down<uint8_t>(scene_desc ? nn * PRS_DESC_BYTES : 0);
+  auto out_idx  = st.down<int32_t>(nn);
+  PRS_TRY(st.commit());
+  memcpy(in_xyzw.h(), scene_xyzw, nn * 16);
   if (scene_desc) {
-    memcpy(h + o_in_desc, scene_desc, nn * PRS_DESC_BYTES);
+    memcpy(in_desc.h(), scene_desc, nn * PRS_DESC_BYTES);
   }
-  int32_t* hs = reinterpret_cast<int32_t*>(h + o_small);
-  hs[0]       = n;   // n_scene
-  hs[1]       = 0;   // n_clipped
-  hs[2]       = 0;   // status
-  memcpy(hs + 4, robot_in_local_map16, 64);
-  hipStream_t s = ctx->stream;
-  hipError_t e  = hipMemcpyAsync(d, h, o_out_xyzw, hipMemcpyHostToDevice, s);
-  if (e != hipSuccess) {
-    return ctx_fail_hip(ctx, e, "prs_scene_clip upload");
-  }
+  Meta& m = *meta.h();
+  m.n_scene = n, m.n_clipped = 0, m.status = 0, m.pad = 0;
+  memcpy(m.robot_in_local_map, robot_in_local_map16, 64);
+  PRS_TRY(st.upload());
   prs_clip_batch b;
   b.batch              = 1;
   b.stride             = n;
-  b.scene_xyzw         = reinterpret_cast<const float*>(d + o_in_xyzw);
-  b.scene_desc         = scene_desc ? d + o_in_desc : nullptr;
-  b.n_scene            = reinterpret_cast<const int32_t*>(d + o_small);
-  b.robot_in_local_map = reinterpret_cast<const float*>(d + o_small + 16);
-  b.clipped_xyzw       = reinterpret_cast<float*>(d + o_out_xyzw);
-  b.clipped_desc       = scene_desc ? d + o_out_desc : nullptr;
-  b.global_indices     = reinterpret_cast<int32_t*>(d + o_out_idx);
-  b.n_clipped          = reinterpret_cast<int32_t*>(d + o_small + 4);
-  b.status             = reinterpret_cast<int32_t*>(d + o_small + 8);
+  b.scene_xyzw         = in_xyzw.d();
+  b.scene_desc         = scene_desc ? in_desc.d() : nullptr;
+  b.n_scene            = &meta.d()->n_scene;
+  b.robot_in_local_map = meta.d()->robot_in_local_map;
+  b.clipped_xyzw       = out_xyzw.d();
+  b.clipped_desc       = scene_desc ? out_desc.d() : nullptr;
+  b.global_indices     = out_idx.d();
+  b.n_clipped          = &meta.d()->n_clipped;
+  b.status             = &meta.d()->status;
   b.scene_n_opt        = nullptr;
-  const int rc = scene_clip_launch(ctx, projector, sensor_in_robot16, &b);
-  if (rc != PRS_OK) {
-    return rc;
-  }
-  e = hipMemcpyAsync(h + o_small, d + o_small, total - o_small, hipMemcpyDeviceToHost, s);
-  if (e == hipSuccess) {
-    e = hipStreamSynchronize(s);
-  }
-  if (e != hipSuccess) {
-    return ctx_fail_hip(ctx, e, "prs_scene_clip download");
-  }
-  const int32_t m = hs[1];
-  memcpy(clipped_xyzw, h + o_out_xyzw, (size_t) m * 16);
+  PRS_TRY(scene_clip_launch(ctx, projector, sensor_in_robot16, &b));
+  PRS_TRY(st.download());
+  const size_t k = (size_t) m.n_clipped;
+  memcpy(clipped_xyzw, out_xyzw.h(), k * 16);
   if (clipped_desc) {
-    memcpy(clipped_desc, h + o_out_desc, (size_t) m * PRS_DESC_BYTES);
+    memcpy(clipped_desc, out_desc.h(), k * PRS_DESC_BYTES);
   }
-  memcpy(global_indices, h + o_out_idx, (size_t) m * 4);
-  *n_clipped = m;
-  return hs[2];
+  memcpy(global_indices, out_idx.h(), k * 4);
+  *n_clipped = m.n_clipped;
+  return m.status;
 }
 
 int prs_bruteforce_match_batch(prs_context* ctx, const prs_bruteforce_params* params, const prs_bruteforce_batch* batch) {
@@ -685,40 +643,32 @@ int prs_bruteforce_match(prs_context* ctx,
     return ctx_fail(ctx, PRS_ERR_CAPACITY, "prs_bruteforce_match: output capacity below min(n_fixed, n_moving)");
   }
   (void) hipSetDevice(ctx->device);
-  const size_t b_f   = align256((size_t) n_fixed * PRS_DESC_BYTES);
-  const size_t b_m   = align256((size_t) n_moving * PRS_DESC_BYTES);
-  const size_t b_s   = 256;  // n_fixed, n_moving, n_matches, status
-  const size_t b_out = align256((size_t) n_min * sizeof(prs_corr));
-  const size_t total = b_f + b_m + b_s + b_out;
-  // slot 3: the launch itself uses slots 0..2
-  unsigned char* d   = static_cast<unsigned char*>(ctx_device_scratch_slot(ctx, 3, total));
-  unsigned char* h   = static_cast<unsigned char*>(ctx_pinned_scratch(ctx, total));
-  if (!d || !h) {
-    return ctx_fail(ctx, PRS_ERR_HIP, "prs_bruteforce_match: scratch allocation failed");
-  }
-  memcpy(h, fixed_desc, (size_t) n_fixed * PRS_DESC_BYTES);
-  memcpy(h + b_f, moving_desc, (size_t) n_moving * PRS_DESC_BYTES);
-  int32_t* hs = reinterpret_cast<int32_t*>(h + b_f + b_m);
-  hs[0] = n_fixed;
-  hs[1] = n_moving;
-  hs[2] = 0;
-  hs[3] = 0;
-  hipStream_t s = ctx->stream;
-  hipError_t e  = hipMemcpyAsync(d, h, b_f + b_m + b_s, hipMemcpyHostToDevice, s);
-  if (e != hipSuccess) {
-    return ctx_fail_hip(ctx, e, "prs_bruteforce_match upload");
-  }
+  struct Meta {
+    int32_t n_fixed, n_moving, n_matches, status;
+  };
+  // (an arena of its own: the block stays live while the launch is repeated below)
+  Staging st(ctx, "prs_bruteforce_match", ARENA_STAGE_BRUTEFORCE);
+  auto fixed   = st.up<uint8_t>((size_t) n_fixed * PRS_DESC_BYTES);
+  auto moving  = st.up<uint8_t>((size_t) n_moving * PRS_DESC_BYTES);
+  auto meta    = st.both<Meta>(1);
+  auto matches = st.down<prs_corr>((size_t) n_min);
+  PRS_TRY(st.commit());
+  memcpy(fixed.h(), fixed_desc, (size_t) n_fixed * PRS_DESC_BYTES);
+  memcpy(moving.h(), moving_desc, (size_t) n_moving * PRS_DESC_BYTES);
+  Meta& m = *meta.h();
+  m       = {n_fixed, n_moving, 0, 0};
+  PRS_TRY(st.upload());
   prs_bruteforce_batch b;
-  b.batch              = 1;
-  b.fixed_stride       = n_fixed;
-  b.moving_stride      = n_moving;
-  b.fixed_desc         = d;
-  b.n_fixed            = reinterpret_cast<const int32_t*>(d + b_f + b_m);
-  b.moving_desc        = d + b_f;
-  b.n_moving           = reinterpret_cast<const int32_t*>(d + b_f + b_m + 4);
-  b.matches            = reinterpret_cast<prs_corr*>(d + b_f + b_m + b_s);
-  b.n_matches          = reinterpret_cast<int32_t*>(d + b_f + b_m + 8);
-  b.status             = reinterpret_cast<int32_t*>(d + b_f + b_m + 12);
+  b.batch         = 1;
+  b.fixed_stride  = n_fixed;
+  b.moving_stride = n_moving;
+  b.fixed_desc    = fixed.d();
+  b.n_fixed       = &meta.d()->n_fixed;
+  b.moving_desc   = moving.d();
+  b.n_moving      = &meta.d()->n_moving;
+  b.matches       = matches.d();
+  b.n_matches     = &meta.d()->n_matches;
+  b.status        = &meta.d()->status;
   // the candidate list defaults to 16 entries per descriptor; a loose threshold on correlated descriptors can need more
   // (at most every pair): grow and repeat, like the reference's std::vector would
   const long long all_pairs = (long long) n_fixed * (long long) n_moving;
@@ -728,34 +678,22 @@ int prs_bruteforce_match(prs_context* ctx,
       cand_cap = all_pairs;
     }
     b.candidate_capacity = (int32_t) (cand_cap > 0x7fffffffll ? 0x7fffffffll : cand_cap);
-    const int rc         = bruteforce_batch_launch(ctx, params, &b);
-    if (rc != PRS_OK) {
-      return rc;
-    }
-    e = hipMemcpyAsync(h + b_f + b_m, d + b_f + b_m, b_s + b_out, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) {
-      e = hipStreamSynchronize(s);
-    }
-    if (e != hipSuccess) {
-      return ctx_fail_hip(ctx, e, "prs_bruteforce_match download");
-    }
-    if (hs[3] != PRS_ERR_CAPACITY || cand_cap >= all_pairs) {
+    PRS_TRY(bruteforce_batch_launch(ctx, params, &b));
+    PRS_TRY(st.download());
+    if (m.status != PRS_ERR_CAPACITY || cand_cap >= all_pairs) {
       break;
     }
     cand_cap *= 8;
-    hs[2] = 0;
-    hs[3] = 0;
-    e     = hipMemcpyAsync(d + b_f + b_m, h + b_f + b_m, b_s, hipMemcpyHostToDevice, s);
-    if (e != hipSuccess) {
-      return ctx_fail_hip(ctx, e, "prs_bruteforce_match upload");
-    }
+    m.n_matches = 0;
+    m.status    = 0;
+    PRS_TRY(st.upload(meta));  // the meta words only
   }
-  if (hs[3] < 0) {
-    return ctx_fail(ctx, hs[3], "prs_bruteforce_match: more candidates below the threshold than the kernel's candidate capacity");
+  if (m.status < 0) {
+    return ctx_fail(ctx, m.status, "prs_bruteforce_match: more candidates below the threshold than the kernel's candidate capacity");
   }
-  memcpy(correspondences, h + b_f + b_m + b_s, (size_t) hs[2] * sizeof(prs_corr));
-  *n_correspondences = hs[2];
-  return hs[3];
+  memcpy(correspondences, matches.h(), (size_t) m.n_matches * sizeof(prs_corr));
+  *n_correspondences = m.n_matches;
+  return m.status;
 }
 
 int prs_merge_batch_run(prs_context* ctx, const prs_merger_params* params, const prs_merge_batch* batch) {
@@ -809,35 +747,19 @@ int prs_selection_order(prs_context* ctx, const uint8_t* response, int32_t n, in
     }
   }
   (void) hipSetDevice(ctx->device);
-  const size_t b_resp = align256((size_t) n), b_order = align256((size_t) n * 4);
-  const size_t total  = b_resp + b_order + 256;
-  unsigned char* d    = static_cast<unsigned char*>(ctx_device_scratch(ctx, total));
-  unsigned char* h    = static_cast<unsigned char*>(ctx_pinned_scratch(ctx, total));
-  if (!d || !h) {
-    return ctx_fail(ctx, PRS_ERR_HIP, "prs_selection_order: scratch allocation failed");
+  Staging st(ctx, "prs_selection_order");
+  auto resp     = st.up<uint8_t>((size_t) n);
+  auto order_st = st.down<int32_t>((size_t) n);
+  auto status   = st.down<int32_t>(1);
+  PRS_TRY(st.commit());
+  memcpy(resp.h(), response, (size_t) n);
+  PRS_TRY(st.upload());
+  PRS_TRY(selection_order_launch(ctx, resp.d(), n, order_st.d(), status.d()));
+  PRS_TRY(st.download());
+  if (*status.h() != PRS_OK) {
+    return ctx_fail(ctx, *status.h(), "prs_selection_order: the sort did not finish");
   }
-  memcpy(h, response, (size_t) n);
-  hipStream_t s = ctx->stream;
-  hipError_t e  = hipMemcpyAsync(d, h, (size_t) n, hipMemcpyHostToDevice, s);
-  if (e != hipSuccess) {
-    return ctx_fail_hip(ctx, e, "prs_selection_order upload");
-  }
-  const int rc = selection_order_launch(ctx, d, n, reinterpret_cast<int32_t*>(d + b_resp), reinterpret_cast<int32_t*>(d + b_resp + b_order));
-  if (rc != PRS_OK) {
-    return rc;
-  }
-  e = hipMemcpyAsync(h + b_resp, d + b_resp, b_order + 4, hipMemcpyDeviceToHost, s);
-  if (e == hipSuccess) {
-    e = hipStreamSynchronize(s);
-  }
-  if (e != hipSuccess) {
-    return ctx_fail_hip(ctx, e, "prs_selection_order download");
-  }
-  const int32_t status = *reinterpret_cast<const int32_t*>(h + b_resp + b_order);
-  if (status != PRS_OK) {
-    return ctx_fail(ctx, status, "prs_selection_order: the sort did not finish");
-  }
-  memcpy(order, h + b_resp, (size_t) n * 4);
+  memcpy(order, order_st.h(), (size_t) n * 4);
   return PRS_OK;
 }
 
@@ -865,62 +787,46 @@ int prs_extract_features(prs_context* ctx,
     return ctx_fail(ctx, PRS_ERR_UNSUPPORTED, "prs_extract_features: invalid image size, pitch or capacity");
   }
   (void) hipSetDevice(ctx->device);
-  const size_t cap    = (size_t) capacity;
-  const size_t b_img  = align256((size_t) rows * (size_t) pitch);
-  const size_t b_kp   = align256(cap * sizeof(prs_kp2));
-  const size_t b_int  = align256(cap * sizeof(float));
-  const size_t b_desc = align256(cap * PRS_DESC_BYTES);
-  const size_t b_small = 256;
-  const size_t total   = b_img + b_small + b_kp + b_int + b_desc;
-  unsigned char* d     = static_cast<unsigned char*>(ctx_device_scratch(ctx, total));
-  unsigned char* h     = static_cast<unsigned char*>(ctx_pinned_scratch(ctx, total));
-  if (!d || !h) {
-    return ctx_fail(ctx, PRS_ERR_HIP, "prs_extract_features: scratch allocation failed");
-  }
-  // staging layout (same on both sides): image | n_features, status | keypoints | intensity | descriptors
-  const size_t o_small = b_img, o_kp = o_small + b_small, o_int = o_kp + b_kp, o_desc = o_int + b_int;
+  const size_t cap = (size_t) capacity;
+  struct Meta {
+    int32_t n_features, status;
+  };
+  // image | n_features, status | keypoints | intensity | descriptors
+  Staging st(ctx, "prs_extract_features");
+  auto img   = st.up<uint8_t>((size_t) rows * (size_t) pitch);
+  auto meta  = st.down<Meta>(1);
+  auto kp    = st.down<prs_kp2>(cap);
+  auto inten = st.down<float>(cap);
+  auto desc  = st.down<uint8_t>(cap * PRS_DESC_BYTES);
+  PRS_TRY(st.commit());
   // (the last row of a pitched view, e.g. a cv::Mat ROI, owns only `cols` bytes)
   const size_t image_bytes = (size_t) (rows - 1) * (size_t) pitch + (size_t) cols;
-  memcpy(h, image, image_bytes);
-  hipStream_t s = ctx->stream;
-  hipError_t e  = hipMemcpyAsync(d, h, image_bytes, hipMemcpyHostToDevice, s);
-  if (e != hipSuccess) {
-    return ctx_fail_hip(ctx, e, "prs_extract_features upload");
-  }
+  memcpy(img.h(), image, image_bytes);
+  PRS_TRY(st.upload(image_bytes));
   prs_extract_batch b;
   b.batch       = 1;
   b.rows        = rows;
   b.cols        = cols;
   b.pitch       = pitch;
-  b.images      = d;
+  b.images      = img.d();
   b.stride      = capacity;
-  b.keypoints   = reinterpret_cast<prs_kp2*>(d + o_kp);
-  b.intensity   = reinterpret_cast<float*>(d + o_int);
-  b.descriptors = d + o_desc;
-  b.n_features  = reinterpret_cast<int32_t*>(d + o_small);
-  b.status      = reinterpret_cast<int32_t*>(d + o_small + 4);
-  const int rc  = extract_features_launch(ctx, params, &b);
-  if (rc != PRS_OK) {
-    return rc;
-  }
-  e = hipMemcpyAsync(h + o_small, d + o_small, total - o_small, hipMemcpyDeviceToHost, s);
-  if (e == hipSuccess) {
-    e = hipStreamSynchronize(s);
-  }
-  if (e != hipSuccess) {
-    return ctx_fail_hip(ctx, e, "prs_extract_features download");
-  }
-  const int32_t* hs = reinterpret_cast<const int32_t*>(h + o_small);
-  const int32_t n = hs[0], status = hs[1];
+  b.keypoints   = kp.d();
+  b.intensity   = inten.d();
+  b.descriptors = desc.d();
+  b.n_features  = &meta.d()->n_features;
+  b.status      = &meta.d()->status;
+  PRS_TRY(extract_features_launch(ctx, params, &b));
+  PRS_TRY(st.download());
+  const int32_t n = meta.h()->n_features, status = meta.h()->status;
   if (status < 0) {
     *n_features = 0;
     return ctx_fail(ctx, status, "prs_extract_features: more raw detections or features than the buffers hold");
   }
-  memcpy(keypoints, h + o_kp, (size_t) n * sizeof(prs_kp2));
+  memcpy(keypoints, kp.h(), (size_t) n * sizeof(prs_kp2));
   if (intensity) {
-    memcpy(intensity, h + o_int, (size_t) n * sizeof(float));
+    memcpy(intensity, inten.h(), (size_t) n * sizeof(float));
   }
-  memcpy(descriptors, h + o_desc, (size_t) n * PRS_DESC_BYTES);
+  memcpy(descriptors, desc.h(), (size_t) n * PRS_DESC_BYTES);
   *n_features = n;
   return status;
 }
@@ -962,79 +868,61 @@ int prs_extract_features_selective(prs_context* ctx,
     return ctx_fail(ctx, PRS_ERR_UNSUPPORTED, "prs_extract_features_selective: invalid image size, pitch, capacity or projection count");
   }
   (void) hipSetDevice(ctx->device);
-  const size_t cap      = (size_t) capacity;
-  const size_t n_proj   = (size_t) (n_projections > 0 ? n_projections : 1);
+  const size_t cap         = (size_t) capacity;
+  const size_t n_proj      = (size_t) (n_projections > 0 ? n_projections : 1);
   const size_t image_bytes = (size_t) (rows - 1) * (size_t) pitch + (size_t) cols;
-  const size_t b_img    = align256((size_t) rows * (size_t) pitch);
-  const size_t b_mask   = seeding_mask ? b_img : 0;
-  const size_t b_proj   = align256(n_proj * sizeof(prs_kp2));
-  const size_t b_small  = 256;
-  const size_t b_kp     = align256(cap * sizeof(prs_kp2));
-  const size_t b_int    = align256(cap * sizeof(float));
-  const size_t b_desc   = align256(cap * PRS_DESC_BYTES);
-  const size_t total    = b_img + b_mask + b_proj + b_small + b_kp + b_int + b_desc;
-  unsigned char* d      = static_cast<unsigned char*>(ctx_device_scratch(ctx, total));
-  unsigned char* h      = static_cast<unsigned char*>(ctx_pinned_scratch(ctx, total));
-  if (!d || !h) {
-    return ctx_fail(ctx, PRS_ERR_HIP, "prs_extract_features_selective: scratch allocation failed");
-  }
-  // staging layout (same on both sides): image | seeding mask | projections, then n_features, status, n_projections, radius |
-  // keypoints | intensity | descriptors
-  const size_t o_mask = b_img, o_proj = o_mask + b_mask, o_small = o_proj + b_proj, o_kp = o_small + b_small, o_int = o_kp + b_kp, o_desc = o_int + b_int;
-  memcpy(h, image, image_bytes);
+  struct Meta {
+    int32_t n_features, status, n_projections, detection_radius;
+  };
+  // image | seeding mask | projections | meta | keypoints | intensity | descriptors
+  Staging st(ctx, "prs_extract_features_selective");
+  auto img   = st.up<uint8_t>((size_t) rows * (size_t) pitch);
+  auto mask  = st.up<uint8_t>(seeding_mask ? (size_t) rows * (size_t) pitch : 0);
+  auto proj  = st.up<prs_kp2>(n_proj);
+  auto meta  = st.both<Meta>(1);
+  auto kp    = st.down<prs_kp2>(cap);
+  auto inten = st.down<float>(cap);
+  auto desc  = st.down<uint8_t>(cap * PRS_DESC_BYTES);
+  PRS_TRY(st.commit());
+  memcpy(img.h(), image, image_bytes);
   if (seeding_mask) {
-    memcpy(h + o_mask, seeding_mask, image_bytes);
+    memcpy(mask.h(), seeding_mask, image_bytes);
   }
   if (n_projections > 0) {
-    memcpy(h + o_proj, projections, (size_t) n_projections * sizeof(prs_kp2));
+    memcpy(proj.h(), projections, (size_t) n_projections * sizeof(prs_kp2));
   }
-  int32_t* hs = reinterpret_cast<int32_t*>(h + o_small);
-  hs[2] = n_projections;
-  hs[3] = detection_radius;
-  hipStream_t s = ctx->stream;
-  hipError_t e  = hipMemcpyAsync(d, h, o_small + 16, hipMemcpyHostToDevice, s);
-  if (e != hipSuccess) {
-    return ctx_fail_hip(ctx, e, "prs_extract_features_selective upload");
-  }
+  *meta.h() = {0, 0, n_projections, detection_radius};
+  PRS_TRY(st.upload());
   prs_selective_extract_batch b;
   memset(&b, 0, sizeof(b));
   b.batch             = 1;
   b.rows              = rows;
   b.cols              = cols;
   b.pitch             = pitch;
-  b.images            = d;
+  b.images            = img.d();
   b.projection_stride = (int32_t) n_proj;
-  b.projections       = reinterpret_cast<const prs_kp2*>(d + o_proj);
-  b.n_projections     = reinterpret_cast<const int32_t*>(d + o_small + 8);
-  b.detection_radius  = reinterpret_cast<const int32_t*>(d + o_small + 12);
-  b.seeding_mask      = seeding_mask ? d + o_mask : nullptr;
+  b.projections       = proj.d();
+  b.n_projections     = &meta.d()->n_projections;
+  b.detection_radius  = &meta.d()->detection_radius;
+  b.seeding_mask      = seeding_mask ? mask.d() : nullptr;
   b.stride            = capacity;
-  b.keypoints         = reinterpret_cast<prs_kp2*>(d + o_kp);
-  b.intensity         = reinterpret_cast<float*>(d + o_int);
-  b.descriptors       = d + o_desc;
-  b.n_features        = reinterpret_cast<int32_t*>(d + o_small);
-  b.status            = reinterpret_cast<int32_t*>(d + o_small + 4);
-  const int rc        = selective_extract_launch(ctx, params, &b);
-  if (rc != PRS_OK) {
-    return rc;
-  }
-  e = hipMemcpyAsync(h + o_small, d + o_small, total - o_small, hipMemcpyDeviceToHost, s);
-  if (e == hipSuccess) {
-    e = hipStreamSynchronize(s);
-  }
-  if (e != hipSuccess) {
-    return ctx_fail_hip(ctx, e, "prs_extract_features_selective download");
-  }
-  const int32_t n = hs[0], status = hs[1];
+  b.keypoints         = kp.d();
+  b.intensity         = inten.d();
+  b.descriptors       = desc.d();
+  b.n_features        = &meta.d()->n_features;
+  b.status            = &meta.d()->status;
+  PRS_TRY(selective_extract_launch(ctx, params, &b));
+  PRS_TRY(st.download());
+  const int32_t n = meta.h()->n_features, status = meta.h()->status;
   if (status < 0) {
     *n_features = 0;
     return ctx_fail(ctx, status, "prs_extract_features_selective: projection outside the image, or more candidates or features than the buffers hold");
   }
-  memcpy(keypoints, h + o_kp, (size_t) n * sizeof(prs_kp2));
+  memcpy(keypoints, kp.h(), (size_t) n * sizeof(prs_kp2));
   if (intensity) {
-    memcpy(intensity, h + o_int, (size_t) n * sizeof(float));
+    memcpy(intensity, inten.h(), (size_t) n * sizeof(float));
   }
-  memcpy(descriptors, h + o_desc, (size_t) n * PRS_DESC_BYTES);
+  memcpy(descriptors, desc.h(), (size_t) n * PRS_DESC_BYTES);
   *n_features = n;
   return status;
 }

@@ -1177,9 +1177,9 @@ int bruteforce_batch_launch(prs_context* ctx, const prs_bruteforce_params* param
   const size_t b_cand = (size_t) grid * a.cap * sizeof(uint2);
   const size_t b_bm   = (size_t) grid * (size_t) (batch->fixed_stride + batch->moving_stride) * a.nw * sizeof(uint32_t);
   const size_t b_acc  = a.chunks > 1 ? (size_t) batch->batch * (size_t) (batch->fixed_stride + batch->moving_stride + kBfLevels + 8) * sizeof(uint32_t) : 0;
-  a.cand     = static_cast<uint2*>(ctx_device_scratch_slot(ctx, 0, b_cand));
-  a.by_level = static_cast<uint2*>(ctx_device_scratch_slot(ctx, 1, b_cand));
-  a.bitmaps  = static_cast<uint32_t*>(ctx_device_scratch_slot(ctx, 2, b_bm + b_acc));
+  a.cand     = static_cast<uint2*>(ctx_arena(ctx, ARENA_WORK_0, b_cand));
+  a.by_level = static_cast<uint2*>(ctx_arena(ctx, ARENA_WORK_1, b_cand));
+  a.bitmaps  = static_cast<uint32_t*>(ctx_arena(ctx, ARENA_WORK_2, b_bm + b_acc));
   a.g_acc    = a.bitmaps ? a.bitmaps + b_bm / sizeof(uint32_t) : nullptr;
   if (!a.cand || !a.by_level || !a.bitmaps) {
     return ctx_fail(ctx, PRS_ERR_HIP, "prs_bruteforce_match: scratch allocation failed");

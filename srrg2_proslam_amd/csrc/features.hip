@@ -1481,11 +1481,11 @@ int extract_features_launch(prs_context* ctx, const prs_extractor_params* params
   a.p = *params;
   a.b = *batch;
   const size_t npix = (size_t) batch->rows * batch->cols;
-  a.kept  = static_cast<uint32_t*>(ctx_device_scratch_slot(ctx, 0, (size_t) batch->batch * (size_t) batch->stride * sizeof(uint32_t)));
+  a.kept  = static_cast<uint32_t*>(ctx_arena(ctx, ARENA_WORK_0, (size_t) batch->batch * (size_t) batch->stride * sizeof(uint32_t)));
   a.blur_ncb    = (batch->cols + 15) / 16;
   a.blur_stride = (size_t) ((batch->rows + 7) / 8) * a.blur_ncb * 128;
-  a.blur        = static_cast<uint8_t*>(ctx_device_scratch_slot(ctx, 1, (size_t) batch->batch * a.blur_stride));
-  uint32_t* rawbuf = static_cast<uint32_t*>(ctx_device_scratch_slot(ctx, 2, (size_t) batch->batch * ((size_t) max_raw + 1) * 4));
+  a.blur        = static_cast<uint8_t*>(ctx_arena(ctx, ARENA_WORK_1, (size_t) batch->batch * a.blur_stride));
+  uint32_t* rawbuf = static_cast<uint32_t*>(ctx_arena(ctx, ARENA_WORK_2, (size_t) batch->batch * ((size_t) max_raw + 1) * 4));
   if (!a.kept || !a.blur || !rawbuf) {
     return ctx_fail(ctx, PRS_ERR_HIP, "prs_extract_features_batch: scratch allocation failed");
   }
@@ -1544,7 +1544,7 @@ int describe_selected_launch(prs_context* ctx, const prs_extract_batch* batch, u
   a.kept        = kept;
   a.blur_ncb    = (batch->cols + 15) / 16;
   a.blur_stride = (size_t) ((batch->rows + 7) / 8) * a.blur_ncb * 128;
-  a.blur        = static_cast<uint8_t*>(ctx_device_scratch_slot(ctx, 1, (size_t) batch->batch * a.blur_stride));
+  a.blur        = static_cast<uint8_t*>(ctx_arena(ctx, ARENA_WORK_1, (size_t) batch->batch * a.blur_stride));
   if (!a.blur) {
     return ctx_fail(ctx, PRS_ERR_HIP, "describe_selected_launch: scratch allocation failed");
   }

@@ -1500,9 +1500,9 @@ int merge_batch_launch(prs_context* ctx, const prs_merger_params* params, const 
   if (e.type == PRS_EST_SMOOTHER) {
     if (!b.corr || b.corr_stride <= 0) {
       // no correspondences at all: nothing to iterate, but the pointer must be valid
-      a.work = ctx_device_scratch_slot(ctx, 0, 64);
+      a.work = ctx_arena(ctx, ARENA_WORK_0, 64);
     } else {
-      a.work = ctx_device_scratch_slot(ctx, 0, (size_t) b.batch * 2 * (size_t) b.corr_stride * sizeof(SmootherItem));
+      a.work = ctx_arena(ctx, ARENA_WORK_0, (size_t) b.batch * 2 * (size_t) b.corr_stride * sizeof(SmootherItem));
     }
     if (!a.work) {
       return ctx_fail(ctx, PRS_ERR_HIP, "prs_merge_batch_run: smoother work list allocation failed");
@@ -1539,13 +1539,13 @@ int merge_batch_launch(prs_context* ctx, const prs_merger_params* params, const 
         return ctx_fail_hip(ctx, e2, "prs_merge_batch_run: smoother kernel LDS request");
       }
     }
-    a.carry = static_cast<MergeCarry*>(ctx_device_scratch_slot(ctx, 1, (size_t) b.batch * sizeof(MergeCarry)));
+    a.carry = static_cast<MergeCarry*>(ctx_arena(ctx, ARENA_WORK_1, (size_t) b.batch * sizeof(MergeCarry)));
     if (!a.carry) {
       return ctx_fail(ctx, PRS_ERR_HIP, "prs_merge_batch_run: carry allocation failed");
     }
     // tail list: [batch * kTailPerFrame] items + the counter in front of them
     a.tail_capacity    = b.batch * kTailPerFrame;
-    unsigned char* tmem = static_cast<unsigned char*>(ctx_device_scratch_slot(ctx, 2, 256 + (size_t) a.tail_capacity * sizeof(TailItem)));
+    unsigned char* tmem = static_cast<unsigned char*>(ctx_arena(ctx, ARENA_WORK_2, 256 + (size_t) a.tail_capacity * sizeof(TailItem)));
     if (!tmem) {
       return ctx_fail(ctx, PRS_ERR_HIP, "prs_merge_batch_run: tail list allocation failed");
     }

@@ -38,10 +38,7 @@ namespace {
 constexpr size_t kSmState = 0, kSmX = 192, kSmNcorr = 256, kSmResult = 320, kSmallBytes = 640;
 constexpr size_t kHdNfixed = 0, kHdNmoving = 4, kHdChanged = 8, kHdPrior = 64, kHdPriorMean = 256, kHeadBytes = 384;
 static_assert(sizeof(prs_pcf_state) <= kSmX - kSmState && sizeof(prs_align_result) <= kSmallBytes - kSmResult, "small block layout");
-
-size_t align256(size_t v) {
-  return (v + 255) / 256 * 256;
-}
+using prs::align256;
 
 int fail(prs_pcf* h, int status, const char* what) {
   return prs::ctx_fail(h ? h->ctx : nullptr, status, what);
@@ -422,29 +419,17 @@ int prs_selftest_reciprocal(prs_context* ctx, uint64_t counts[2]) {
     return PRS_ERR_NULL;
   }
   (void) hipSetDevice(ctx->device);
-  unsigned long long* d = static_cast<unsigned long long*>(prs::ctx_device_scratch_slot(ctx, 2, 512));
-  if (!d) {
-    return prs::ctx_fail(ctx, PRS_ERR_HIP, "prs_selftest_reciprocal: scratch allocation failed");
-  }
-  hipStream_t s = ctx->stream;
-  hipError_t e  = hipMemsetAsync(d, 0, 2 * sizeof(unsigned long long), s);
+  prs::Staging st(ctx, "prs_selftest_reciprocal", prs::ARENA_STAGE_SOLVER);
+  auto sums = st.down<unsigned long long>(2);
+  PRS_TRY(st.commit());
+  const hipError_t e = hipMemsetAsync(sums.d(), 0, 2 * sizeof(unsigned long long), ctx->stream);
   if (e != hipSuccess) {
     return prs::ctx_fail_hip(ctx, e, "prs_selftest_reciprocal");
   }
-  const int rc = prs::recip_selftest_launch(ctx, d);
-  if (rc != PRS_OK) {
-    return rc;
-  }
-  unsigned long long h[2] = {0, 0};
-  e = hipMemcpyAsync(h, d, sizeof h, hipMemcpyDeviceToHost, s);
-  if (e == hipSuccess) {
-    e = hipStreamSynchronize(s);
-  }
-  if (e != hipSuccess) {
-    return prs::ctx_fail_hip(ctx, e, "prs_selftest_reciprocal download");
-  }
-  counts[0] = h[0];
-  counts[1] = h[1];
+  PRS_TRY(prs::recip_selftest_launch(ctx, sums.d()));
+  PRS_TRY(st.download());
+  counts[0] = sums.h()[0];
+  counts[1] = sums.h()[1];
   return PRS_OK;
 }
 
@@ -456,37 +441,24 @@ int prs_gn_step_ex(prs_context* ctx, const float* H36, const float* b6, float da
     return prs::ctx_fail(ctx, PRS_ERR_UNSUPPORTED, "prs_gn_step_ex: unknown damping form");
   }
   (void) hipSetDevice(ctx->device);
-  float* d = static_cast<float*>(prs::ctx_device_scratch_slot(ctx, 2, 512));
-  if (!d) {
-    return prs::ctx_fail(ctx, PRS_ERR_HIP, "prs_gn_step: scratch allocation failed");
-  }
-  hipStream_t s = ctx->stream;
-  hipError_t e  = hipMemcpyAsync(d, H36, sizeof(float) * 36, hipMemcpyHostToDevice, s);
-  if (e == hipSuccess) {
-    e = hipMemcpyAsync(d + 36, b6, sizeof(float) * 6, hipMemcpyHostToDevice, s);
-  }
-  if (e == hipSuccess) {
-    e = hipMemcpyAsync(d + 48, X16, sizeof(float) * 16, hipMemcpyHostToDevice, s);
-  }
-  if (e != hipSuccess) {
-    return prs::ctx_fail_hip(ctx, e, "prs_gn_step upload");
-  }
-  const int rc = prs::gn_step_launch(ctx, d, d + 36, damping, damping_form, d + 48, reinterpret_cast<int*>(d + 64));
-  if (rc != PRS_OK) {
-    return rc;
-  }
-  int ok = 0;
-  e      = hipMemcpyAsync(X16, d + 48, sizeof(float) * 16, hipMemcpyDeviceToHost, s);
-  if (e == hipSuccess) {
-    e = hipMemcpyAsync(&ok, d + 64, sizeof(int), hipMemcpyDeviceToHost, s);
-  }
-  if (e == hipSuccess) {
-    e = hipStreamSynchronize(s);
-  }
-  if (e != hipSuccess) {
-    return prs::ctx_fail_hip(ctx, e, "prs_gn_step download");
-  }
-  return ok ? PRS_OK : 1;  // 1: system not positive definite, X unchanged
+  struct System {
+    float H[36], b[6], pad[6], X[16];
+    int32_t ok;
+  };
+  prs::Staging st(ctx, "prs_gn_step", prs::ARENA_STAGE_SOLVER);
+  auto sys = st.both<System>(1);
+  PRS_TRY(st.commit());
+  System& h = *sys.h();
+  memcpy(h.H, H36, sizeof(h.H));
+  memcpy(h.b, b6, sizeof(h.b));
+  memcpy(h.X, X16, sizeof(h.X));
+  h.ok = 0;
+  PRS_TRY(st.upload());
+  System* d = sys.d();
+  PRS_TRY(prs::gn_step_launch(ctx, d->H, d->b, damping, damping_form, d->X, &d->ok));
+  PRS_TRY(st.download());
+  memcpy(X16, h.X, sizeof(h.X));
+  return h.ok ? PRS_OK : 1;  // 1: system not positive definite, X unchanged
 }
 
 void prs_info_scale_from_nopt(const uint32_t* n_opt, int32_t n, float* scale) {

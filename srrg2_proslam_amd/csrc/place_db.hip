@@ -636,7 +636,7 @@ int prs_place_db_add(prs_place_db* db, int64_t graph_id, const float* xyz, const
   const size_t tiles = (size_t) padded / 16;
   const size_t o_xyz = (size_t) padded * PRS_DESC_BYTES, o_pidx = o_xyz + (size_t) padded * 16, o_tile = o_pidx + (size_t) padded * 4;
   const size_t o_map = o_tile + tiles * 4, total = o_map + 16;
-  unsigned char* h = static_cast<unsigned char*>(ctx_pinned_scratch(ctx, total));
+  unsigned char* h = static_cast<unsigned char*>(ctx_arena(ctx, ARENA_PINNED, total));
   if (!h) {
     return ctx_fail(ctx, PRS_ERR_HIP, "prs_place_db_add: staging allocation failed");
   }
@@ -717,10 +717,7 @@ int prs_place_query(prs_place_db* db, const prs_place_params* params, int64_t gr
     return PRS_ERR_NULL;
   }
   prs_context* ctx = db->ctx;
-  int rc = check_params(ctx, params, "prs_place_query: parameters not set");
-  if (rc != PRS_OK) {
-    return rc;
-  }
+  PRS_TRY(check_params(ctx, params, "prs_place_query: parameters not set"));
   if (!candidates || !n_candidates || !corr || !n_corr || (n > 0 && !desc)) {
     return ctx_fail(ctx, PRS_ERR_NULL, "prs_place_query: input or output buffer not set");
   }
@@ -731,72 +728,68 @@ int prs_place_query(prs_place_db* db, const prs_place_params* params, int64_t gr
     return ctx_fail(ctx, PRS_ERR_CAPACITY, "prs_place_query: corr_stride below the largest stored map");
   }
   (void) hipSetDevice(ctx->device);
-  auto align256 = [](size_t x) { return (x + 255) & ~(size_t) 255; };
-  const int maxc  = params->max_candidates;
+  const size_t maxc = (size_t) params->max_candidates;
   const size_t nq = (size_t) (n > 0 ? n : 1), maps = (size_t) (db->maps > 0 ? db->maps : 1), rows = (size_t) (db->rows > 0 ? db->rows : 1);
-  // staging (same on both sides): descriptors | valid | n, graph id (uploaded) | status, counts | candidates | n_corr | corr (downloaded) | keys
-  const size_t o_valid = align256(nq * PRS_DESC_BYTES), o_small = o_valid + align256(nq), o_status = o_small + 256;
-  const size_t o_counts = o_status + 256, o_cand = o_counts + align256(maps * 4), o_ncorr = o_cand + align256((size_t) maxc * 4);
-  const size_t o_corr = o_ncorr + align256((size_t) maxc * 4), o_keys = o_corr + align256((size_t) maxc * (size_t) corr_stride * sizeof(prs_corr));
-  const size_t total = o_keys + align256(rows * 4);
-  unsigned char* d = static_cast<unsigned char*>(ctx_device_scratch(ctx, total));
-  unsigned char* h = static_cast<unsigned char*>(ctx_pinned_scratch(ctx, o_keys));
-  if (!d || !h) {
-    return ctx_fail(ctx, PRS_ERR_HIP, "prs_place_query: scratch allocation failed");
-  }
+  struct In {
+    int32_t n_query;
+    int64_t graph_id;
+  };
+  struct Out {
+    int32_t status, n_candidates;
+  };
+  // descriptors | valid | n, graph id (uploaded) | status | counts | candidates | n_corr (downloaded) | corr | keys (device only:
+  // the rows of the candidates go straight into the caller's buffer below)
+  Staging st(ctx, "prs_place_query");
+  auto qdesc  = st.up<uint8_t>(nq * PRS_DESC_BYTES);
+  auto qvalid = st.up<uint8_t>(nq);
+  auto in     = st.up<In>(1);
+  auto out    = st.down<Out>(1);
+  auto counts = st.down<uint32_t>(maps);
+  auto cand   = st.down<int32_t>(maxc);
+  auto ncorr  = st.down<int32_t>(maxc);
+  auto dcorr  = st.device<prs_corr>(maxc * (size_t) corr_stride);
+  auto keys   = st.device<uint32_t>(rows);
+  PRS_TRY(st.commit());
   if (n > 0) {
-    memcpy(h, desc, (size_t) n * PRS_DESC_BYTES);
+    memcpy(qdesc.h(), desc, (size_t) n * PRS_DESC_BYTES);
     if (valid) {
-      memcpy(h + o_valid, valid, (size_t) n);
+      memcpy(qvalid.h(), valid, (size_t) n);
     }
   }
-  int32_t* hs = reinterpret_cast<int32_t*>(h + o_small);
-  hs[0]       = n;
-  memcpy(h + o_small + 8, &graph_id, 8);
-  hipStream_t s = ctx->stream;
-  hipError_t e  = hipMemcpyAsync(d, h, o_status, hipMemcpyHostToDevice, s);
-  if (e != hipSuccess) {
-    return ctx_fail_hip(ctx, e, "prs_place_query upload");
-  }
+  in.h()->n_query  = n;
+  in.h()->graph_id = graph_id;
+  PRS_TRY(st.upload());
   prs_place_queries q;
   memset(&q, 0, sizeof(q));
   q.batch        = 1;
   q.query_stride = (int32_t) nq;
-  q.desc         = d;
-  q.valid        = valid ? d + o_valid : nullptr;
-  q.n_query      = reinterpret_cast<const int32_t*>(d + o_small);
-  q.graph_id     = reinterpret_cast<const int64_t*>(d + o_small + 8);
+  q.desc         = qdesc.d();
+  q.valid        = valid ? qvalid.d() : nullptr;
+  q.n_query      = &in.d()->n_query;
+  q.graph_id     = &in.d()->graph_id;
   q.count_stride = (int32_t) maps;
-  q.match_counts = reinterpret_cast<uint32_t*>(d + o_counts);
+  q.match_counts = counts.d();
   q.key_stride   = (int32_t) rows;
-  q.best_keys    = reinterpret_cast<uint32_t*>(d + o_keys);
+  q.best_keys    = keys.d();
   q.corr_stride  = corr_stride;
-  q.candidates   = reinterpret_cast<int32_t*>(d + o_cand);
-  q.n_candidates = reinterpret_cast<int32_t*>(d + o_status + 4);
-  q.corr         = reinterpret_cast<prs_corr*>(d + o_corr);
-  q.n_corr       = reinterpret_cast<int32_t*>(d + o_ncorr);
-  q.status       = reinterpret_cast<int32_t*>(d + o_status);
-  rc = place_query_launch(db, params, &q);
-  if (rc != PRS_OK) {
-    return rc;
-  }
-  e = hipMemcpyAsync(h + o_status, d + o_status, o_corr - o_status, hipMemcpyDeviceToHost, s);
-  if (e == hipSuccess) {
-    e = hipStreamSynchronize(s);
-  }
-  if (e != hipSuccess) {
-    return ctx_fail_hip(ctx, e, "prs_place_query download");
-  }
-  const int32_t* hst = reinterpret_cast<const int32_t*>(h + o_status);
-  const int32_t nc   = hst[1];
-  const int32_t* hn  = reinterpret_cast<const int32_t*>(h + o_ncorr);
-  memcpy(candidates, h + o_cand, (size_t) maxc * 4);
-  memcpy(n_corr, hn, (size_t) maxc * 4);
+  q.candidates   = cand.d();
+  q.n_candidates = &out.d()->n_candidates;
+  q.corr         = dcorr.d();
+  q.n_corr       = ncorr.d();
+  q.status       = &out.d()->status;
+  PRS_TRY(place_query_launch(db, params, &q));
+  PRS_TRY(st.download());
+  const int32_t nc  = out.h()->n_candidates;
+  const int32_t* hn = ncorr.h();
+  memcpy(candidates, cand.h(), maxc * 4);
+  memcpy(n_corr, hn, maxc * 4);
   *n_candidates = nc;
   // the correspondences of the candidates only (candidate k's rows start at k * corr_stride)
+  hipStream_t s = ctx->stream;
+  hipError_t e  = hipSuccess;
   for (int32_t k = 0; k < nc; ++k) {
     if (hn[k] > 0) {
-      e = hipMemcpyAsync(corr + (size_t) k * (size_t) corr_stride, d + o_corr + (size_t) k * (size_t) corr_stride * sizeof(prs_corr),
+      e = hipMemcpyAsync(corr + (size_t) k * (size_t) corr_stride, dcorr.d() + (size_t) k * (size_t) corr_stride,
                          (size_t) hn[k] * sizeof(prs_corr), hipMemcpyDeviceToHost, s);
       if (e != hipSuccess) {
         break;
@@ -804,7 +797,7 @@ int prs_place_query(prs_place_db* db, const prs_place_params* params, int64_t gr
     }
   }
   if (e == hipSuccess && match_counts && db->maps > 0) {
-    e = hipMemcpyAsync(match_counts, d + o_counts, (size_t) db->maps * 4, hipMemcpyDeviceToHost, s);
+    e = hipMemcpyAsync(match_counts, counts.d(), (size_t) db->maps * 4, hipMemcpyDeviceToHost, s);
   }
   if (e == hipSuccess) {
     e = hipStreamSynchronize(s);
@@ -812,10 +805,10 @@ int prs_place_query(prs_place_db* db, const prs_place_params* params, int64_t gr
   if (e != hipSuccess) {
     return ctx_fail_hip(ctx, e, "prs_place_query download");
   }
-  if (hst[0] < 0) {
-    return ctx_fail(ctx, hst[0], "prs_place_query: query rejected (graph id, size or candidate capacity)");
+  if (out.h()->status < 0) {
+    return ctx_fail(ctx, out.h()->status, "prs_place_query: query rejected (graph id, size or candidate capacity)");
   }
-  return hst[0];
+  return out.h()->status;
 }
 
 int prs_place_gather_pairs(prs_place_db* db, const prs_place_params* params, const prs_place_queries* queries, const prs_place_pairs* pairs) {

@@ -416,19 +416,23 @@ int prs_point_align(prs_context* ctx, const prs_point_align_params* params, cons
     return ctx_fail(ctx, PRS_ERR_UNSUPPORTED, "prs_point_align: more than 8192 correspondences");
   }
   (void) hipSetDevice(ctx->device);
-  auto align256 = [](size_t x) { return (x + 255) & ~(size_t) 255; };
   const size_t nf = (size_t) (n_fixed > 0 ? n_fixed : 1), nm = (size_t) (n_moving > 0 ? n_moving : 1);
   const size_t nc = (size_t) (n_corr > 0 ? n_corr : 1);
-  // staging layout (same on both sides): fixed rows | moving rows | correspondences | sizes, X (uploaded) | result | mask (downloaded)
-  const size_t o_mov = align256(nf * 16), o_corr = o_mov + align256(nm * 16), o_small = o_corr + align256(nc * sizeof(prs_corr));
-  const size_t o_res = o_small + 256, o_mask = o_res + align256(sizeof(prs_point_align_result)), total = o_mask + align256(nc);
-  unsigned char* d = static_cast<unsigned char*>(ctx_device_scratch(ctx, total));
-  unsigned char* h = static_cast<unsigned char*>(ctx_pinned_scratch(ctx, total));
-  if (!d || !h) {
-    return ctx_fail(ctx, PRS_ERR_HIP, "prs_point_align: scratch allocation failed");
-  }
-  float* hf = reinterpret_cast<float*>(h);
-  float* hm = reinterpret_cast<float*>(h + o_mov);
+  struct Meta {
+    int32_t n_fixed, n_moving, n_corr, pad;
+    float X[16];
+  };
+  // fixed rows | moving rows | correspondences | sizes, X (uploaded) | result | mask (downloaded)
+  Staging st(ctx, "prs_point_align");
+  auto fixed  = st.up<float>(nf * 4);
+  auto moving = st.up<float>(nm * 4);
+  auto pairs  = st.up<prs_corr>(nc);
+  auto meta   = st.both<Meta>(1);
+  auto res    = st.down<prs_point_align_result>(1);
+  auto mask   = st.down<uint8_t>(nc);
+  PRS_TRY(st.commit());
+  float* hf = fixed.h();
+  float* hm = moving.h();
   for (int32_t i = 0; i < n_fixed; ++i) {
     hf[4 * (size_t) i]     = fixed_xyz[3 * (size_t) i];
     hf[4 * (size_t) i + 1] = fixed_xyz[3 * (size_t) i + 1];
@@ -442,48 +446,33 @@ int prs_point_align(prs_context* ctx, const prs_point_align_params* params, cons
     hm[4 * (size_t) i + 3] = 0.0f;
   }
   if (n_corr > 0) {
-    memcpy(h + o_corr, corr, (size_t) n_corr * sizeof(prs_corr));
+    memcpy(pairs.h(), corr, (size_t) n_corr * sizeof(prs_corr));
   }
-  int32_t* hs = reinterpret_cast<int32_t*>(h + o_small);
-  hs[0]       = n_fixed;
-  hs[1]       = n_moving;
-  hs[2]       = n_corr;
-  memcpy(h + o_small + 16, X16, 16 * sizeof(float));
-  hipStream_t s = ctx->stream;
-  hipError_t e  = hipMemcpyAsync(d, h, o_res, hipMemcpyHostToDevice, s);
-  if (e != hipSuccess) {
-    return ctx_fail_hip(ctx, e, "prs_point_align upload");
-  }
+  Meta& m = *meta.h();
+  m.n_fixed = n_fixed, m.n_moving = n_moving, m.n_corr = n_corr, m.pad = 0;
+  memcpy(m.X, X16, sizeof(m.X));
+  PRS_TRY(st.upload());
   prs_point_align_pairs b;
   memset(&b, 0, sizeof(b));
   b.batch         = 1;
   b.fixed_stride  = (int32_t) nf;
   b.moving_stride = (int32_t) nm;
   b.corr_stride   = (int32_t) nc;
-  b.fixed         = reinterpret_cast<const float*>(d);
-  b.moving        = reinterpret_cast<const float*>(d + o_mov);
-  b.corr          = reinterpret_cast<const prs_corr*>(d + o_corr);
-  b.n_fixed       = reinterpret_cast<const int32_t*>(d + o_small);
-  b.n_moving      = reinterpret_cast<const int32_t*>(d + o_small + 4);
-  b.n_corr        = reinterpret_cast<const int32_t*>(d + o_small + 8);
-  b.X             = reinterpret_cast<float*>(d + o_small + 16);
-  b.result        = reinterpret_cast<prs_point_align_result*>(d + o_res);
-  b.inlier_mask   = inlier_mask ? d + o_mask : nullptr;
-  const int rc = point_align_launch(ctx, params, &b);
-  if (rc != PRS_OK) {
-    return rc;
-  }
-  e = hipMemcpyAsync(h + o_small, d + o_small, total - o_small, hipMemcpyDeviceToHost, s);
-  if (e == hipSuccess) {
-    e = hipStreamSynchronize(s);
-  }
-  if (e != hipSuccess) {
-    return ctx_fail_hip(ctx, e, "prs_point_align download");
-  }
-  memcpy(result, h + o_res, sizeof(prs_point_align_result));
-  memcpy(X16, h + o_small + 16, 16 * sizeof(float));
+  b.fixed         = fixed.d();
+  b.moving        = moving.d();
+  b.corr          = pairs.d();
+  b.n_fixed       = &meta.d()->n_fixed;
+  b.n_moving      = &meta.d()->n_moving;
+  b.n_corr        = &meta.d()->n_corr;
+  b.X             = meta.d()->X;
+  b.result        = res.d();
+  b.inlier_mask   = inlier_mask ? mask.d() : nullptr;
+  PRS_TRY(point_align_launch(ctx, params, &b));
+  PRS_TRY(st.download());
+  memcpy(result, res.h(), sizeof(prs_point_align_result));
+  memcpy(X16, m.X, sizeof(m.X));
   if (inlier_mask && n_corr > 0) {
-    memcpy(inlier_mask, h + o_mask, (size_t) n_corr);
+    memcpy(inlier_mask, mask.h(), (size_t) n_corr);
   }
   if (result->warnings < 0) {
     return ctx_fail(ctx, result->warnings, "prs_point_align: a correspondence index lies outside its cloud");

@@ -8,6 +8,25 @@
 
 #include "../../include/proslam_hip.h"
 
+namespace prs {
+
+// The context's grow-only scratch blocks.  The rule that keeps two users of one block apart: a launch function (*_launch)
+// takes work arenas only, and what it puts there is dead when its kernels have run; a host-pointer entry point stages its
+// arguments and results only in a staging arena (through prs::Staging below), never in a work arena.
+enum Arena {
+  ARENA_WORK_0,            // launches: candidates (brute force), kept features (extractor), smoother items (merger)
+  ARENA_WORK_1,            // launches: candidates by level (brute force), blurred images (extractors), carry (merger)
+  ARENA_WORK_2,            // launches: bitmaps (brute force), raw detections (extractor), tail items (merger)
+  ARENA_WORK_3,            // launches: tile counts (scene clipper), work block (selective extractor)
+  ARENA_STAGE,             // device side of the host-pointer entry points' staging block
+  ARENA_STAGE_BRUTEFORCE,  // the same for prs_bruteforce_match, whose block stays live across its relaunches
+  ARENA_STAGE_SOLVER,      // the same for prs_gn_step_ex and prs_selftest_reciprocal
+  ARENA_PINNED,            // host side (pinned) of all of them: an entry point synchronises before it returns
+  ARENA_COUNT
+};
+
+}  // namespace prs
+
 struct prs_context {
   int device            = 0;
   hipStream_t stream    = nullptr;  // stream work is enqueued on
@@ -22,14 +41,11 @@ struct prs_context {
   int bf_mfma           = 1;        // PRS_BF_DENSE_*: the brute-force matcher's dense phase (prs_context_set_bruteforce_dense_phase; PRS_BF_MFMA=0 / auto / 1)
   bool no_lone_gn       = false;    // PRS_NO_LONE_GN=1: small batches use the throughput instantiation of the Gauss-Newton kernel too (diagnostic)
   bool stamps_split     = false;    // PRS_STAMPS_SPLIT=1 (with PRS_STAMPS=1): phase stamps of the split search kernel
-  // reusable device scratch for the host-pointer entry points
-  void* d_scratch       = nullptr;
-  size_t d_scratch_size = 0;
-  void* d_slot[4]       = {nullptr, nullptr, nullptr, nullptr};  // kernel-owned scratch (candidates, ...)
-  size_t d_slot_size[4] = {0, 0, 0, 0};
+  struct {
+    void* p     = nullptr;
+    size_t size = 0;
+  } arena[prs::ARENA_COUNT];        // reusable scratch (prs::ctx_arena)
   float* d_info_lut     = nullptr;  // information scale by landmark age, 4096 entries (scene clipper)
-  void* h_pinned        = nullptr;
-  size_t h_pinned_size  = 0;
   // per-kernel HIP-event timing of the split aligner pipeline (prs_context_enable_timing; measurement only)
   bool timing           = false;
   double t_search_ms = 0.0, t_gn_ms = 0.0;
@@ -62,10 +78,94 @@ inline bool ctx_matcher_v3(const prs_context* ctx) {
 inline bool ctx_force_unstaged(const prs_context* ctx) {
   return ctx->force_unstaged;
 }
-// grows (never shrinks) the context's device scratch; returns nullptr on failure
-void* ctx_device_scratch(prs_context* ctx, size_t bytes);
-void* ctx_pinned_scratch(prs_context* ctx, size_t bytes);
-void* ctx_device_scratch_slot(prs_context* ctx, int slot, size_t bytes);
+// a step that returns a PRS status: anything but PRS_OK leaves the enclosing function with it (the step has set the message)
+#define PRS_TRY(step)         \
+  do {                        \
+    const int rc_ = (step);   \
+    if (rc_ != PRS_OK) {      \
+      return rc_;             \
+    }                         \
+  } while (0)
+
+inline size_t align256(size_t v) {
+  return (v + 255) / 256 * 256;
+}
+// grows (never shrinks) one of the context's arenas to at least `bytes`, after the stream has drained if a block has to be
+// freed; returns nullptr on failure
+void* ctx_arena(prs_context* ctx, Arena arena, size_t bytes);
+
+// The staging block of a host-pointer entry point: sections in declaration order, each starting on a 256-byte boundary, with
+// the same layout in a device arena and in the pinned arena.  Declare the sections, commit(), fill the .h() side, upload()
+// (ONE copy over the span of the up / both sections), point the batch descriptor at the .d() side and launch, download()
+// (ONE copy over the span of the both / down sections, then a stream synchronise), read the .h() side.  Every error it
+// returns has set the context's message, prefixed with the entry point's name.
+class Staging {
+ public:
+  template <class T>
+  struct Section {
+    const Staging* st;
+    int index;
+    T* h() const {  // pinned side (not for device-only sections)
+      return reinterpret_cast<T*>(st->h_ + st->rec_[index].off);
+    }
+    T* d() const {
+      return reinterpret_cast<T*>(st->d_ + st->rec_[index].off);
+    }
+  };
+  static constexpr size_t kAll = ~(size_t) 0;
+
+  Staging(prs_context* ctx, const char* entry, Arena arena = ARENA_STAGE) : ctx_(ctx), entry_(entry), arena_(arena) {}
+  template <class T>
+  Section<T> up(size_t n) {  // uploaded
+    return {this, add(kUp, n * sizeof(T))};
+  }
+  template <class T>
+  Section<T> down(size_t n) {  // downloaded
+    return {this, add(kDown, n * sizeof(T))};
+  }
+  template <class T>
+  Section<T> both(size_t n) {  // uploaded and downloaded
+    return {this, add(kUp | kDown, n * sizeof(T))};
+  }
+  template <class T>
+  Section<T> device(size_t n) {  // on the device only: no pinned mirror, so these come after every mirrored section
+    return {this, add(0, n * sizeof(T))};
+  }
+  // sizes both arenas and resolves the sections.  Refuses a layout in which a copy would overwrite live bytes with stale
+  // ones: a section that lies inside the upload (download) span has to be an uploaded (downloaded) one itself
+  int commit();
+  // last_bytes: how much of the last uploaded section has been filled (the copy ends there)
+  int upload(size_t last_bytes = kAll);
+  template <class T>
+  int upload(const Section<T>& s) {  // that section alone, again
+    return copy(rec_[s.index].off, rec_[s.index].bytes, true);
+  }
+  int download();
+
+ private:
+  enum { kUp = 1, kDown = 2, kMaxSections = 10 };
+  struct Rec {
+    size_t off, bytes;
+    int flags;
+  };
+  int add(int flags, size_t bytes) {
+    if (n_ < kMaxSections) {
+      rec_[n_] = {end_, bytes, flags};
+      end_ += align256(bytes);
+    }
+    return n_++;
+  }
+  int copy(size_t off, size_t bytes, bool to_device);
+  prs_context* ctx_;
+  const char* entry_;
+  Arena arena_;
+  Rec rec_[kMaxSections];
+  int n_                = 0;
+  size_t end_           = 0;
+  int first_[2]         = {-1, -1}, last_[2] = {-1, -1};  // the up [0] and down [1] spans, by section
+  unsigned char *h_ = nullptr, *d_ = nullptr;
+};
+
 // device table scale[n] = n > 2 ? 1 + log(n) : 1 for n < 4096 (built once per context)
 const float* ctx_info_scale_table(prs_context* ctx);
 // diagnostic: device buffer for phase stamps when PRS_STAMPS=1, else nullptr

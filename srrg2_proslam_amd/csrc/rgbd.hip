@@ -117,10 +117,6 @@ __global__ __launch_bounds__(kThreads) void depth_kernel(const DepthArgs a) {
   }
 }
 
-inline size_t align256(size_t b) {
-  return (b + 255) & ~(size_t) 255;
-}
-
 bool aligned(const void* p, size_t bytes) {
   return (reinterpret_cast<uintptr_t>(p) & (bytes - 1)) == 0;
 }
@@ -203,10 +199,7 @@ int prs_depth_measurements(prs_context* ctx, const prs_depth_params* params, con
     return ctx_fail(ctx, PRS_ERR_NULL, "prs_depth_measurements: input or output buffer not set");
   }
   *n_fixed = 0;
-  int rc = check_params(ctx, params, rows, cols, pitch, "prs_depth_measurements: unknown depth_type, non-finite scale, or invalid size or pitch");
-  if (rc != PRS_OK) {
-    return rc;
-  }
+  PRS_TRY(check_params(ctx, params, rows, cols, pitch, "prs_depth_measurements: unknown depth_type, non-finite scale, or invalid size or pitch"));
   if (n < 0) {
     return ctx_fail(ctx, PRS_ERR_RANGE, "prs_depth_measurements: negative feature count");
   }
@@ -215,74 +208,63 @@ int prs_depth_measurements(prs_context* ctx, const prs_depth_params* params, con
   const size_t cap         = (size_t) (n > 0 ? n : 1);
   const size_t elem        = params->depth_type == PRS_DEPTH_U16 ? 2 : 4;
   const size_t depth_bytes = (size_t) (rows - 1) * (size_t) pitch + (size_t) cols * elem;
-  const size_t b_depth = align256((size_t) rows * (size_t) pitch), b_small = 256, b_kp = align256(cap * sizeof(prs_kp2));
-  const size_t b_int = align256(cap * sizeof(float)), b_desc = align256(cap * PRS_DESC_BYTES), b_fixed = align256(cap * 16);
-  // staging layout (same on both sides): depth | keypoints | intensity | descriptors (uploaded) | n_features, status, n_fixed |
-  // fixed | fixed intensity | fixed descriptors (downloaded)
-  const size_t o_kp = b_depth, o_int = o_kp + b_kp, o_desc = o_int + b_int, o_small = o_desc + b_desc, o_fixed = o_small + b_small;
-  const size_t o_fint = o_fixed + b_fixed, o_fdesc = o_fint + b_int, total = o_fdesc + b_desc;
-  unsigned char* d = static_cast<unsigned char*>(ctx_device_scratch(ctx, total));
-  unsigned char* h = static_cast<unsigned char*>(ctx_pinned_scratch(ctx, total));
-  if (!d || !h) {
-    return ctx_fail(ctx, PRS_ERR_HIP, "prs_depth_measurements: scratch allocation failed");
-  }
-  memcpy(h, depth, depth_bytes);
+  struct Meta {
+    int32_t n_features, status, n_fixed;
+  };
+  // depth | keypoints | intensity | descriptors (uploaded) | meta | fixed | fixed intensity | fixed descriptors (downloaded)
+  Staging st(ctx, "prs_depth_measurements");
+  auto dimg  = st.up<uint8_t>((size_t) rows * (size_t) pitch);
+  auto kp    = st.up<prs_kp2>(cap);
+  auto inten = st.up<float>(cap);
+  auto desc  = st.up<uint8_t>(cap * PRS_DESC_BYTES);
+  auto meta  = st.both<Meta>(1);
+  auto fixed = st.down<float>(cap * 4);
+  auto fint  = st.down<float>(cap);
+  auto fdesc = st.down<uint8_t>(cap * PRS_DESC_BYTES);
+  PRS_TRY(st.commit());
+  memcpy(dimg.h(), depth, depth_bytes);
   if (n > 0) {
-    memcpy(h + o_kp, keypoints, (size_t) n * sizeof(prs_kp2));
-    memcpy(h + o_desc, descriptors, (size_t) n * PRS_DESC_BYTES);
+    memcpy(kp.h(), keypoints, (size_t) n * sizeof(prs_kp2));
+    memcpy(desc.h(), descriptors, (size_t) n * PRS_DESC_BYTES);
     if (with_int) {
-      memcpy(h + o_int, intensity, (size_t) n * sizeof(float));
+      memcpy(inten.h(), intensity, (size_t) n * sizeof(float));
     }
   }
-  int32_t* hs = reinterpret_cast<int32_t*>(h + o_small);
-  hs[0]       = n;
-  hipStream_t s = ctx->stream;
-  hipError_t e  = hipMemcpyAsync(d, h, o_small + 4, hipMemcpyHostToDevice, s);
-  if (e != hipSuccess) {
-    return ctx_fail_hip(ctx, e, "prs_depth_measurements upload");
-  }
+  *meta.h() = {n, 0, 0};
+  PRS_TRY(st.upload());
   prs_depth_batch b;
   memset(&b, 0, sizeof(b));
   b.batch           = 1;
   b.rows            = rows;
   b.cols            = cols;
   b.pitch           = pitch;
-  b.depth           = d;
+  b.depth           = dimg.d();
   b.stride          = (int32_t) cap;
-  b.keypoints       = reinterpret_cast<const prs_kp2*>(d + o_kp);
-  b.intensity       = with_int ? reinterpret_cast<const float*>(d + o_int) : nullptr;
-  b.descriptors     = d + o_desc;
-  b.n_features      = reinterpret_cast<const int32_t*>(d + o_small);
-  b.fixed           = reinterpret_cast<float*>(d + o_fixed);
-  b.fixed_desc      = d + o_fdesc;
-  b.fixed_intensity = with_int ? reinterpret_cast<float*>(d + o_fint) : nullptr;
-  b.n_fixed         = reinterpret_cast<int32_t*>(d + o_small + 8);
-  b.status          = reinterpret_cast<int32_t*>(d + o_small + 4);
-  rc = depth_measurements_launch(ctx, params, &b);
-  if (rc != PRS_OK) {
-    return rc;
-  }
-  e = hipMemcpyAsync(h + o_small, d + o_small, total - o_small, hipMemcpyDeviceToHost, s);
-  if (e == hipSuccess) {
-    e = hipStreamSynchronize(s);
-  }
-  if (e != hipSuccess) {
-    return ctx_fail_hip(ctx, e, "prs_depth_measurements download");
-  }
-  const int32_t status = hs[1], k = hs[2];
+  b.keypoints       = kp.d();
+  b.intensity       = with_int ? inten.d() : nullptr;
+  b.descriptors     = desc.d();
+  b.n_features      = &meta.d()->n_features;
+  b.fixed           = fixed.d();
+  b.fixed_desc      = fdesc.d();
+  b.fixed_intensity = with_int ? fint.d() : nullptr;
+  b.n_fixed         = &meta.d()->n_fixed;
+  b.status          = &meta.d()->status;
+  PRS_TRY(depth_measurements_launch(ctx, params, &b));
+  PRS_TRY(st.download());
+  const int32_t status = meta.h()->status, k = meta.h()->n_fixed;
   if (status < 0) {
     return ctx_fail(ctx, status, "prs_depth_measurements: a keypoint lies outside the depth image");
   }
-  const float* fx = reinterpret_cast<const float*>(h + o_fixed);
+  const float* fx = fixed.h();
   for (int32_t i = 0; i < k; ++i) {
     uvd[3 * (size_t) i]     = fx[4 * (size_t) i];
     uvd[3 * (size_t) i + 1] = fx[4 * (size_t) i + 1];
     uvd[3 * (size_t) i + 2] = fx[4 * (size_t) i + 2];
   }
   if (with_int) {
-    memcpy(intensity_out, h + o_fint, (size_t) k * sizeof(float));
+    memcpy(intensity_out, fint.h(), (size_t) k * sizeof(float));
   }
-  memcpy(desc_out, h + o_fdesc, (size_t) k * PRS_DESC_BYTES);
+  memcpy(desc_out, fdesc.h(), (size_t) k * PRS_DESC_BYTES);
   *n_fixed = k;
   return status;
 }

@@ -274,7 +274,7 @@ int scene_clip_launch(prs_context* ctx, const prs_projector* projector, const fl
   if (walk) {
     hipLaunchKernelGGL(scene_clip_kernel<kClipWalk>, dim3(batch->batch), dim3(kClipThreads), 0, stream, a);
   } else {
-    a.counts = static_cast<int*>(ctx_device_scratch_slot(ctx, 3, (size_t) batch->batch * a.tiles * sizeof(int)));
+    a.counts = static_cast<int*>(ctx_arena(ctx, ARENA_WORK_3, (size_t) batch->batch * a.tiles * sizeof(int)));
     if (!a.counts) {
       return ctx_fail(ctx, PRS_ERR_HIP, "prs_scene_clip: scratch allocation failed");
     }

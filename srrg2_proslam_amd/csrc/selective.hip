@@ -464,10 +464,6 @@ __global__ __launch_bounds__(256) void finalize_kernel(const SelArgs a) {
   }
 }
 
-inline size_t align256(size_t b) {
-  return (b + 255) & ~(size_t) 255;
-}
-
 }  // namespace
 
 int selective_extract_launch(prs_context* ctx, const prs_selective_extractor_params* params, const prs_selective_extract_batch* batch) {
@@ -524,7 +520,7 @@ int selective_extract_launch(prs_context* ctx, const prs_selective_extractor_par
   a.wpr = (batch->cols + 31) / 32;
   const size_t b_mask = align256(B * batch->rows * a.wpr * 4), b_small = align256(B * 5 * 4), b_cand = align256(B * 2 * cap * 8);
   const size_t b_sel = align256(B * 2 * a.maxc * 4), b_nsel = align256(B * 2 * 4), b_kept = align256(B * batch->stride * 4);
-  unsigned char* d = static_cast<unsigned char*>(ctx_device_scratch_slot(ctx, 3, b_mask + b_small + b_cand + b_sel + b_nsel + b_kept));
+  unsigned char* d = static_cast<unsigned char*>(ctx_arena(ctx, ARENA_WORK_3, b_mask + b_small + b_cand + b_sel + b_nsel + b_kept));
   if (!d) {
     return ctx_fail(ctx, PRS_ERR_HIP, "prs_extract_features_selective_batch: scratch allocation failed");
   }
