@@ -532,7 +532,7 @@ __global__ __launch_bounds__(THREADS, 4) void bruteforce_kernel(const BfArgs a) 
 // rows): the entries it parks are re-scored from memory at a flush behind barriers, which real descriptors make the bulk of its time.
 constexpr int kBfmThreads  = 512;                                  // 8 waves; two workgroups per CU: one scores while the other flushes / waits at its barrier
 constexpr int kBfmRowsWave = 64;                                   // fixed rows per wave (4 A tiles)
-constexpr int kBfmRowsWg   = kBfmRowsWave * (kBfmThreads / 64);    // 1024 fixed rows per workgroup
+constexpr int kBfmRowsWg   = kBfmRowsWave * (kBfmThreads / 64);    // 512 fixed rows per workgroup
 constexpr int kBfmChunk    = 64;                                   // moving rows per LDS chunk (4 B tiles; 128 rows per chunk: two more registers, spills, slower)
 // LDS image of a chunk: four planes (one per 16-bit slice g of a 64-bit K block), a row of a plane = its four K blocks (64 B) + 16 B of
 // pad.  A ds_read_b128 is served in groups of 16 lanes that mix two values of g ({0-3, 12-15, 20-27}, ...): with the planes a multiple

@@ -3,6 +3,8 @@ correspondence vectors identical to the oracle INCLUDING order ((response, fixed
 import numpy as np
 import pytest
 
+import bruteforce_cases as bc
+import bruteforce_ref as br
 from srrg2_proslam_amd import ops
 from tests import helpers as hp
 
@@ -31,6 +33,12 @@ def _tie_heavy(rng, n_base, n, flips):
             b = int(rng.integers(0, 256))
             out[i, b >> 3] ^= np.uint8(1 << (b & 7))
     return out
+
+
+def _holds_content(df, dm, max_dist, ref):
+    """the pair is worth comparing: candidates below the threshold, and matches among them (two clouds drawn from DIFFERENT
+    prototype arrays are ~128 bits apart everywhere: no candidate, and every kernel agrees with the oracle on nothing)"""
+    return len(br.candidates(df, dm, max_dist)[0]) > 0 and len(ref) > 0
 
 
 @pytest.mark.parametrize("max_dist,ratio", [(50.0, 0.9), (25.0, 0.8), (75.0, 0.5), (33.5, 0.95), (256.0, 1.5)])
@@ -65,10 +73,10 @@ def test_cloud_versus_itself(oracle, hip_ctx):
 def test_pools_with_ties_and_conflicts(oracle, hip_ctx, seed):
     rng = np.random.default_rng(100 + seed)
     nf, nm = int(rng.integers(50, 1500)), int(rng.integers(50, 1500))
-    df = _tie_heavy(rng, 40, nf, 6)
-    dm = _tie_heavy(np.random.default_rng(100 + seed), 40, nm, 6)  # same prototypes
+    df, dm = bc.shared_prototypes(rng, 40, nf, nm, 6)  # both clouds from ONE prototype array
     for max_dist, ratio in ((20.0, 0.9), (12.0, 0.7), (30.0, 1.0)):
         ref, rflags = oracle.bruteforce_match(df, dm, max_dist, ratio)
+        assert _holds_content(df, dm, max_dist, ref), (seed, max_dist, ratio)
         clouds = ops.BruteforceClouds(0, 1, nf, nm, candidate_capacity=nf * nm)
         clouds.upload(0, df, dm)
         ops.bruteforce_match_batch(hip_ctx, ops.bruteforce_params(max_dist, ratio), clouds)
@@ -188,8 +196,7 @@ def test_full_batch_with_dense_candidates_and_two_row_passes(oracle, hip_ctx):
     for b in range(B):
         nf = int(rng.integers(900, fs + 1)) if b % 3 else int(rng.integers(1, 200))
         nm = int(rng.integers(700, ms + 1)) if b % 5 else int(rng.integers(1, 100))
-        df = _tie_heavy(rng, 60, nf, 40)
-        dm = _tie_heavy(np.random.default_rng(23), 60, nm, 40)  # (the same prototypes)
+        df, dm = bc.shared_prototypes(rng, 60, nf, nm, 40)  # (both clouds from one prototype array)
         inputs.append((df, dm))
         clouds.upload(b, df, dm)
     for max_dist, ratio in ((50.0, 0.9), (31.0, 0.8)):
@@ -197,6 +204,7 @@ def test_full_batch_with_dense_candidates_and_two_row_passes(oracle, hip_ctx):
         hip_ctx.synchronize()
         for b in list(range(0, B, 13)) + [B - 1]:
             ref, rflags = oracle.bruteforce_match(inputs[b][0], inputs[b][1], max_dist, ratio)
+            assert _holds_content(inputs[b][0], inputs[b][1], max_dist, ref), (b, max_dist)
             assert hp.corr_equal(ref, clouds.matches_of(b)), (b, max_dist)
             assert int(clouds.status[b].item()) == rflags, (b, max_dist)
 
@@ -283,12 +291,16 @@ def test_forty_cloud_pairs(oracle, hip_ctx, monkeypatch, two_workgroups):
     inputs = []
     for b in range(B):
         nf, nm = int(rng.integers(1, fs + 1)), int(rng.integers(1, ms + 1))
-        df = _tie_heavy(rng, 30, nf, 30) if b % 2 else rng.integers(0, 256, (nf, 32), dtype=np.uint8)
-        dm = _tie_heavy(np.random.default_rng(41), 30, nm, 30) if b % 2 else df[rng.integers(0, nf, nm)].copy()
+        if b % 2:
+            df, dm = bc.shared_prototypes(rng, 30, nf, nm, 30)  # (tie-heavy, both clouds from one prototype array)
+        else:
+            df = rng.integers(0, 256, (nf, 32), dtype=np.uint8)
+            dm = df[rng.integers(0, nf, nm)].copy()
         inputs.append((df, dm))
         clouds.upload(b, df, dm)
     ops.bruteforce_match_batch(hip_ctx, ops.bruteforce_params(45.0, 0.85), clouds)
     hip_ctx.synchronize()
     for b in range(0, B, 3):
         ref, rflags = oracle.bruteforce_match(inputs[b][0], inputs[b][1], 45.0, 0.85)
+        assert _holds_content(inputs[b][0], inputs[b][1], 45.0, ref), b
         assert hp.corr_equal(ref, clouds.matches_of(b)) and int(clouds.status[b].item()) == rflags, b

@@ -46,19 +46,36 @@ def fuzz_clip(cases, rng, ctx, oracle):
     return bad, kept
 
 
+def _any_candidate(df, dm, max_dist):
+    """does any pair of rows lie below the threshold ((float) d < max_dist, bruteforce_impl.cpp:53)?"""
+    bits_m = np.unpackbits(dm, axis=1).astype(np.float32)
+    for f0 in range(0, len(df), 512):
+        bits_f = np.unpackbits(df[f0:f0 + 512], axis=1).astype(np.float32)
+        # hamming = pop(a) + pop(b) - 2 a.b, exact in float32 (integers up to 256)
+        d = bits_f.sum(axis=1)[:, None] + bits_m.sum(axis=1)[None, :] - 2.0 * (bits_f @ bits_m.T)
+        if (d < np.float32(max_dist)).any():
+            return True
+    return False
+
+
 def fuzz_bruteforce(cases, rng, ctx, oracle):
     from srrg2_proslam_amd import ops
     from tests import helpers as hp
     from tests.test_bruteforce_gpu import _tie_heavy
-    bad = total = 0
+    bad = total = empty = 0
     for c in range(cases):
-        nf, nm = int(rng.choice([1, 2, 65, 300, 1000, 2100])), int(rng.choice([1, 3, 64, 500, 1500]))
+        # (fixed clouds above 4096 rows: the popcount kernels' eight rows per thread)
+        nf, nm = int(rng.choice([1, 2, 65, 300, 1000, 2100, 4100, 8192])), int(rng.choice([1, 3, 64, 500, 1500]))
         protos = int(rng.choice([3, 40, 5000]))
+        if nf > 4096:
+            protos = 5000  # (few prototypes x thousands of rows: millions of candidates in one pool, quadratic in the oracle)
         seed = int(rng.integers(1 << 30))
         df = _tie_heavy(np.random.default_rng(seed), protos, nf, int(rng.integers(0, 12)))
         dm = _tie_heavy(np.random.default_rng(seed), protos, nm, int(rng.integers(0, 12)))
-        max_dist, ratio = float(rng.choice([5.0, 20.0, 33.5, 50.0, 120.0])), float(rng.choice([0.5, 0.8, 0.95, 1.0, 1.5]))
+        # (32 / 33 / 64: the thresholds at which the distance bitmaps grow by a word)
+        max_dist, ratio = float(rng.choice([5.0, 20.0, 32.0, 33.0, 33.5, 50.0, 64.0, 120.0])), float(rng.choice([0.5, 0.8, 0.95, 1.0, 1.5]))
         ref, rflags = oracle.bruteforce_match(df, dm, max_dist, ratio)
+        empty += not _any_candidate(df, dm, max_dist)
         clouds = ops.BruteforceClouds(0, 1, nf, nm, candidate_capacity=nf * nm)
         clouds.upload(0, df, dm)
         ctx.set_bruteforce_dense_phase((ops.BF_DENSE_MATRIX_WHEN_FULL, ops.BF_DENSE_POPCOUNT, ops.BF_DENSE_MATRIX)[c % 3])  # every kernel family
@@ -93,6 +110,7 @@ def fuzz_bruteforce(cases, rng, ctx, oracle):
                 bad += 1
                 print("BRUTEFORCE BATCH MISMATCH batch %d pair %d fs %d ms %d dist %g ratio %g: %d vs %d (flags %d %d)" % (
                     c, b, fs, ms, max_dist, ratio, len(ref), len(got), rflags, gflags))
+    fuzz_bruteforce.empty_cases = (empty, cases)  # single-pair cases that held no candidate at all (they compare empty with empty)
     return bad, total
 
 
@@ -164,6 +182,7 @@ def run(cases, seed, ctx=None, oracle=None, verbose=True):
     if verbose:
         for k, (bad, total) in out.items():
             print("%s: %d mismatches, %d items compared" % (k, bad, total))
+        print("bruteforce: %d of %d single-pair cases held no candidate" % fuzz_bruteforce.empty_cases)
     return out
 
 
