@@ -83,7 +83,7 @@ struct FrameCtl {
   int executed;
   int flags;        // OR of finder warnings over the frame loop
   int n_inl, n_out, n_inv;
-  int db_ready;     // the lattice of this frame's fixed cloud is in AlignArgs::dbcache (built by an earlier search launch)
+  int db_ready;     // the lattice of this frame's fixed cloud is in AlignArgs::dbcache, its descriptor rows in AlignArgs::rowcache (left by an earlier search launch)
 };
 constexpr int kModeSplitSearch = 100;  // internal: align_kernel<512> performing ONE finder.compute() for frames that wait for it
 constexpr int kSearchThreads   = 512;
@@ -105,6 +105,8 @@ struct AlignArgs {
   int* pending;    // split pipeline: number of frames the last GN launch left unfinished
   unsigned char* dbcache;  // split pipeline: [batch][db_blob] image of the LDS lattice (db | inv | cellstart)
   uint32_t db_blob;        // bytes of that image (multiple of 16)
+  au32x4* rowcache;        // split pipeline, lattice patterns: [batch][2][max_fixed] fixed descriptor half rows in lattice order, as the scan
+                           // reads them from LDS (first halves of all rows, then second halves); written beside the image (NULL = KD-tree finder)
   unsigned long long* stamps;  // diagnostic: [batch][16] accumulated shader clocks per phase (NULL = off)
   int max_fixed;   // LDS capacity in fixed points (frames with more are rejected loudly)
   uint32_t off_db, off_inv, off_cellstart, off_cfix, off_cmov, off_cls, off_sh;  // persistent for the whole frame loop
@@ -147,6 +149,43 @@ __device__ __forceinline__ int hamming_regs(const au32x4& a0, const au32x4& a1, 
 __device__ __forceinline__ int cold_copy(int v) {
   asm volatile("" : "+v"(v));
   return v;
+}
+
+// inclusive prefix sum over the 64 lanes of a wave on the DPP network (the matcher's, stereo_match_v5.hip: Hillis-Steele inside every row
+// of 16 lanes, then lane 15 of rows 0 / 2 onto rows 1 / 3 and lane 31 onto the upper half)
+__device__ __forceinline__ uint32_t wave_inclusive_scan_dpp(uint32_t v) {
+  v += (uint32_t) __builtin_amdgcn_update_dpp(0, (int) v, 0x111, 0xf, 0xf, true);   // row_shr:1
+  v += (uint32_t) __builtin_amdgcn_update_dpp(0, (int) v, 0x112, 0xf, 0xf, true);   // row_shr:2
+  v += (uint32_t) __builtin_amdgcn_update_dpp(0, (int) v, 0x114, 0xf, 0xf, true);   // row_shr:4
+  v += (uint32_t) __builtin_amdgcn_update_dpp(0, (int) v, 0x118, 0xf, 0xf, true);   // row_shr:8
+  v += (uint32_t) __builtin_amdgcn_update_dpp(0, (int) v, 0x142, 0xa, 0xf, false);  // row_bcast:15 -> rows 1, 3
+  v += (uint32_t) __builtin_amdgcn_update_dpp(0, (int) v, 0x143, 0xc, 0xf, false);  // row_bcast:31 -> rows 2, 3
+  return v;
+}
+
+// ONE lane: the sequential float sum of col[0 .. n) in index order (bindFixed's disparity sum, aligner_slice_processor_projective.cpp:80-88:
+// its order is the reference's).  The column is read 16 floats ahead: up to 32 floats past n must be readable (their values are not used).
+__device__ __forceinline__ float serial_float_sum(const float* col, const int n) {
+  float acc = 0.0f;
+  int i     = 0;
+  const float4* t4 = reinterpret_cast<const float4*>(col);
+  float4 n0 = t4[0], n1 = t4[1], n2 = t4[2], n3 = t4[3];
+  for (; i + 16 <= n; i += 16) {
+    const float4 q0 = n0, q1 = n1, q2 = n2, q3 = n3;
+    const int k = (i >> 2) + 4;
+    n0 = t4[k];
+    n1 = t4[k + 1];
+    n2 = t4[k + 2];
+    n3 = t4[k + 3];
+    acc += q0.x; acc += q0.y; acc += q0.z; acc += q0.w;
+    acc += q1.x; acc += q1.y; acc += q1.z; acc += q1.w;
+    acc += q2.x; acc += q2.y; acc += q2.z; acc += q2.w;
+    acc += q3.x; acc += q3.y; acc += q3.z; acc += q3.w;
+  }
+  for (; i < n; ++i) {
+    acc += col[i];
+  }
+  return acc;
 }
 
 __device__ __forceinline__ int hamming_half(const au32x4& a0, const au32x4& b0) {
@@ -638,13 +677,42 @@ __global__ __launch_bounds__(T, SPLIT ? 6 : 1) void align_kernel(const AlignArgs
   if (tid < 6) {
     sh.b[tid] = 0.0f;
   }
+  // Later searches of a frame loop (split pipeline, lattice patterns): the first search left an image of the lattice and the fixed
+  // descriptor rows in lattice order in global memory.  Both stream back here, next to the state loads and ahead of the same
+  // barrier: coalesced, independent of each other and of `inv` (the gather through the lattice is the first search's alone).
+  // Nothing of an earlier batch can be read: split_init_kernel clears db_ready in every enqueue, a replayed graph included.
+  bool db_built = false;
+  if (split_search && lattice && g.rowcache && ctl->db_ready && ctl->it_align != 0 && nF <= g.max_fixed) {
+    const uint4* __restrict__ img   = reinterpret_cast<const uint4*>(g.dbcache + (size_t) frame * g.db_blob);
+    const au32x4* __restrict__ rows = g.rowcache + (size_t) frame * 2 * (size_t) g.max_fixed;
+    uint4* dst      = reinterpret_cast<uint4*>(smem + g.off_db);
+    const int n_img = (int) (g.db_blob >> 4);
+    for (int i = tid; i < (n_img > nF ? n_img : nF); i += T) {
+      uint4 a   = make_uint4(0u, 0u, 0u, 0u);
+      au32x4 lo = {0u, 0u, 0u, 0u}, hi = {0u, 0u, 0u, 0u};
+      if (i < n_img) {
+        a = img[i];
+      }
+      if (i < nF) {
+        lo = rows[i];
+        hi = rows[g.max_fixed + i];
+      }
+      if (i < n_img) {
+        dst[i] = a;
+      }
+      if (i < nF) {
+        fdesc[i]    = lo;
+        fdesc_hi[i] = hi;
+      }
+    }
+    db_built = true;
+  }
   __syncthreads();
 
   bool inputs_changed = g.b.inputs_changed ? (g.b.inputs_changed[frame] != 0) : true;
   if (split_search && ctl->it_align != 0) {
     inputs_changed = false;  // later searches of the same frame loop
   }
-  bool db_built       = false;
   if (inputs_changed && g.mode != PRS_MODE_LINEARIZE) {
     // a new fixed/moving cloud invalidates the previous frame's correspondence vector
     if (tid == 0) {
@@ -654,37 +722,26 @@ __global__ __launch_bounds__(T, SPLIT ? 6 : 1) void align_kernel(const AlignArgs
   }
 
   // ---- bindFixed: mean disparity over ALL fixed points, sequential float sum -------------------
-  // (aligner_slice_processor_projective.cpp:80-88)
-  if (g.mode != PRS_MODE_FINDER && (!split_search || ctl->it_align == 0) && g.a.factor_type == PRS_FACTOR_STEREO &&
-      g.a.enable_inverse_depth_weighting && g.a.mean_disparity < 0.0f && !sh.error) {
+  // (aligner_slice_processor_projective.cpp:80-88)  The search half with a lattice pattern takes the disparity column in the pass
+  // that builds the lattice and sums it there (below); a first launch that builds none (a finder with nothing new to do) sums on its
+  // way out.
+  const auto binds_disparity = [&]() {
+    return g.mode != PRS_MODE_FINDER && (!split_search || ctl->it_align == 0) && g.a.factor_type == PRS_FACTOR_STEREO && g.a.enable_inverse_depth_weighting &&
+           g.a.mean_disparity < 0.0f;
+  };
+  const auto bind_disparity = [&]() {  // (the whole workgroup; `terms` is free)
     for (int i = tid; i < nF; i += T) {
       const float4 c = gfix[i];
       terms[i]       = c.x - c.z;
     }
     __syncthreads();
     if (tid == 0) {
-      float acc = 0.0f;
-      int i     = 0;
-      const float4* t4 = reinterpret_cast<const float4*>(terms);
-      float4 n0 = t4[0], n1 = t4[1], n2 = t4[2], n3 = t4[3];  // the column is padded with zeros up to a multiple of 16
-      for (; i + 16 <= nF; i += 16) {
-        const float4 q0 = n0, q1 = n1, q2 = n2, q3 = n3;
-        const int k = (i >> 2) + 4;
-        n0 = t4[k];
-        n1 = t4[k + 1];
-        n2 = t4[k + 2];
-        n3 = t4[k + 3];
-        acc += q0.x; acc += q0.y; acc += q0.z; acc += q0.w;
-        acc += q1.x; acc += q1.y; acc += q1.z; acc += q1.w;
-        acc += q2.x; acc += q2.y; acc += q2.z; acc += q2.w;
-        acc += q3.x; acc += q3.y; acc += q3.z; acc += q3.w;
-      }
-      for (; i < nF; ++i) {
-        acc += terms[i];
-      }
-      sh.mean_disp = nF > 0 ? acc / (float) (size_t) nF : 0.0f;
+      sh.mean_disp = nF > 0 ? serial_float_sum(terms, nF) / (float) (size_t) nF : 0.0f;
     }
     __syncthreads();
+  };
+  if (!(split_search && lattice) && binds_disparity() && !sh.error) {
+    bind_disparity();
   }
 
   // the caller-owned correspondence vector persists across calls: "nothing new" finder calls keep
@@ -768,6 +825,9 @@ __global__ __launch_bounds__(T, SPLIT ? 6 : 1) void align_kernel(const AlignArgs
 
         // -- converged: correspondences are not touched (:138-142)
         if (tid == 0) {
+          if (nF == 0 || nM == 0) {
+            sh.flags |= PRS_WARN_EMPTY_INPUT;  // _preCompute (bruteforce_impl.cpp:217-226)
+          }
           sh.decision = kDecisionCommit;
           if (sh.converged) {
             sh.decision = kDecisionReturn;
@@ -807,6 +867,9 @@ __global__ __launch_bounds__(T, SPLIT ? 6 : 1) void align_kernel(const AlignArgs
 
         SUB_MARK();
         // -- the lattice lives in LDS: (re)build it on the first search of a launch and after every reset
+        // (search half: the descriptor rows in lattice order stay in LDS as long as the lattice does -- nothing else uses their
+        // region -- so they are gathered when it is built and not again by a repeated search of this launch)
+        const bool stage_rows = !split_search || !db_built;
         if (!db_built && split_search && g.dbcache && ctl->db_ready) {
           // the lattice only depends on the fixed cloud: the first search launch of a frame built it and left
           // an image of the three LDS arrays in global memory; later launches copy it back (11 kB, coalesced)
@@ -1042,23 +1105,72 @@ __global__ __launch_bounds__(T, SPLIT ? 6 : 1) void align_kernel(const AlignArgs
           // CANONICAL position (stable row sort, ascending index inside a row) and the lattice itself
           // is bucketed into a 2-D cell grid: a query visits the cells under its search region
           // instead of every entry of ~2r+1 rows.
-          const int histcap  = (R > g.ncells ? R : g.ncells) + 2;
-          uint32_t* hist     = reinterpret_cast<uint32_t*>(terms);
-          uint16_t* slot     = reinterpret_cast<uint16_t*>(hist + histcap);
-          uint16_t* bucket   = slot + g.max_fixed + 2;
-          uint16_t* canon    = bucket + g.max_fixed + 2;
-          uint16_t* rowfirst = canon + g.max_fixed + 2;
+          // ONE pass over the fixed cloud in global memory: it takes both histograms (rows: the canonical order, cells: the lattice),
+          // leaves row | column of every point in LDS for the passes behind it and -- search half, first search of a frame loop --
+          // the disparity column of bindFixed's mean.  That sum is a chain of nF dependent float additions in the reference's order;
+          // where every disparity is a multiple of 1/16 px and their magnitudes add up to less than 2^24 sixteenths (corners on
+          // pixel or 1/16-pixel positions: what corner detectors deliver), every partial sum of the chain is an integer number of
+          // sixteenths below 2^24, a float holds it exactly, no addition rounds and the chain's result IS the integer sum: all
+          // threads add integers.  Anything else (sub-pixel refinement, NaN, huge values) takes the chain, on one lane.  Both prefix
+          // scans run on all waves at once (a thread sums its slice, the wave scans on the DPP network, the wave totals cross one
+          // barrier).  A point's canonical position stays in its thread's register from the rank to the scatter.
+          constexpr int kWaves = T / 64;
+          static_assert(2 * kWaves <= 16, "AlignShared::wave_tot holds the wave totals of both scans");
+          float* disp         = terms;                                                 // [max_fixed + 40] (serial_float_sum reads ahead)
+          uint32_t* hist_row  = reinterpret_cast<uint32_t*>(disp + g.max_fixed + 40);  // [R + 2]
+          uint32_t* hist_cell = hist_row + R + 2;                                      // [ncells + 2]
+          uint32_t* rowcol    = hist_cell + g.ncells + 2;                              // [max_fixed] row | column << 16
+          int* dsum           = reinterpret_cast<int*>(rowcol + g.max_fixed);          // [4] the disparities in 1/16 px summed as integers, their magnitudes, "one is off that grid"
+          uint16_t* slot      = reinterpret_cast<uint16_t*>(dsum + 4);                 // a point's slot inside its row ...
+          uint16_t* cslot     = slot + g.max_fixed + 2;                                // ... and inside its cell
+          uint16_t* bucket    = cslot + g.max_fixed + 2;
+          uint16_t* rowfirst  = bucket + g.max_fixed + 2;
+          const bool bind     = split_search && binds_disparity();
           for (int i = tid; i <= R; i += T) {
-            hist[i] = 0;
+            hist_row[i] = 0;
+          }
+          for (int i = tid; i <= g.ncells; i += T) {
+            hist_cell[i] = 0;
+          }
+          if (tid == 0) {
+            dsum[0] = dsum[1] = dsum[2] = 0;
           }
           __syncthreads();
+          int msum = 0, mabs = 0;
+          bool inexact = false;
           for (int i = tid; i < nF; i += T) {
             const float4 c = gfix[i];
+            if (bind) {
+              const float d = c.x - c.z;
+              const float q = d * 16.0f;                                                // (a power of two: exact)
+              const bool ok = __builtin_fabsf(q) < 1048576.0f && q == __builtin_rintf(q);  // a whole number of sixteenths below 2^20 (2047 of them stay below 2^31)
+              const int m   = ok ? (int) q : 0;
+              disp[i]       = d;
+              msum += m;
+              mabs += m < 0 ? -m : m;
+              inexact = inexact || !ok;
+            }
             if (c.x >= 0.0f && c.x < 32767.0f && c.y >= 0.0f && c.y < (float) R) {
               const int row = (int) (int16_t) c.y;  // Element(coordinates(1), coordinates(0), i)
-              slot[i]       = (uint16_t) atomicAdd(&hist[row], 1u);
+              const int col = (int) (int16_t) c.x;
+              int cxi       = col >> g.cell_sx;
+              cxi           = cxi < g.cell_ncx ? cxi : g.cell_ncx - 1;
+              rowcol[i]     = ((uint32_t) row & 0xffffu) | ((uint32_t) col << 16);
+              slot[i]       = (uint16_t) atomicAdd(&hist_row[row], 1u);
+              cslot[i]      = (uint16_t) atomicAdd(&hist_cell[(row >> g.cell_sy) * g.cell_ncx + cxi], 1u);
             } else {
               sh.error = PRS_ERR_RANGE;
+            }
+          }
+          if (bind) {
+            const uint32_t wsum = wave_inclusive_scan_dpp((uint32_t) msum), wabs = wave_inclusive_scan_dpp((uint32_t) mabs);
+            const bool winexact = __ballot(inexact) != 0ull;
+            if (lane == 63) {
+              atomicAdd(&dsum[0], (int) wsum);
+              atomicAdd(&dsum[1], (int) wabs);
+              if (winexact) {
+                dsum[2] = 1;
+              }
             }
           }
           __syncthreads();
@@ -1066,96 +1178,68 @@ __global__ __launch_bounds__(T, SPLIT ? 6 : 1) void align_kernel(const AlignArgs
             break;
           }
           {
-            if (wave == 0) {
-              const int n     = R + 1;
-              const int chunk = (n + 63) >> 6;
-              uint32_t sum    = 0;
-              for (int j = 0; j < chunk; ++j) {
-                const int r = lane * chunk + j;
-                sum += r < n ? hist[r] : 0u;
-              }
-              uint32_t incl = sum;
-#pragma unroll
-              for (int d = 1; d < 64; d <<= 1) {
-                const uint32_t o = __shfl_up(incl, d, 64);
-                if (lane >= d) {
-                  incl += o;
-                }
-              }
-              uint32_t run = incl - sum;
-              for (int j = 0; j < chunk; ++j) {
-                const int r = lane * chunk + j;
-                if (r < n) {
-                  rowfirst[r] = (uint16_t) run;
-                  run += hist[r];
-                }
-              }
+            const int chunk_r = (R + T) / T, chunk_c = (g.ncells + T) / T;  // entries 0 .. R and 0 .. ncells, T slices each
+            uint32_t sum_r = 0, sum_c = 0;
+            for (int j = 0; j < chunk_r; ++j) {
+              const int r = tid * chunk_r + j;
+              sum_r += r <= R ? hist_row[r] : 0u;
+            }
+            for (int j = 0; j < chunk_c; ++j) {
+              const int r = tid * chunk_c + j;
+              sum_c += r <= g.ncells ? hist_cell[r] : 0u;
+            }
+            const uint32_t incl_r = wave_inclusive_scan_dpp(sum_r), incl_c = wave_inclusive_scan_dpp(sum_c);
+            if (lane == 63) {
+              sh.wave_tot[wave]          = (int) incl_r;
+              sh.wave_tot[kWaves + wave] = (int) incl_c;
+            }
+            if (bind && tid == T - 64) {
+              const bool exact = !dsum[2] && dsum[1] < (1 << 24);
+              const float acc  = exact ? (float) dsum[0] * 0.0625f : serial_float_sum(disp, nF);
+              sh.mean_disp     = nF > 0 ? acc / (float) (size_t) nF : 0.0f;
             }
             __syncthreads();
-            for (int i = tid; i < nF; i += T) {
-              const int row = (int) (int16_t) gfix[i].y;
-              bucket[rowfirst[row] + slot[i]] = (uint16_t) i;
-            }
-            __syncthreads();
-            for (int i = tid; i < nF; i += T) {
-              const int row = (int) (int16_t) gfix[i].y;
-              const int s = rowfirst[row], e = rowfirst[row + 1];
-              int rank = 0;
-              for (int j = s; j < e; ++j) {
-                rank += bucket[j] < (uint16_t) i ? 1 : 0;
-              }
-              canon[i] = (uint16_t) (s + rank);
-            }
-          }
-          __syncthreads();
-          // bucket by cell (order inside a cell is irrelevant: ties are resolved on the canonical position)
-          for (int i = tid; i <= g.ncells; i += T) {
-            hist[i] = 0;
-          }
-          __syncthreads();
-          for (int i = tid; i < nF; i += T) {
-            const float4 c = gfix[i];
-            const int row  = (int) (int16_t) c.y;
-            int cxi        = ((int) (int16_t) c.x) >> g.cell_sx;
-            cxi            = cxi < g.cell_ncx ? cxi : g.cell_ncx - 1;
-            slot[i]        = (uint16_t) atomicAdd(&hist[(row >> g.cell_sy) * g.cell_ncx + cxi], 1u);
-          }
-          __syncthreads();
-          if (wave == 0) {
-            const int n     = g.ncells + 1;
-            const int chunk = (n + 63) >> 6;
-            uint32_t sum    = 0;
-            for (int j = 0; j < chunk; ++j) {
-              const int r = lane * chunk + j;
-              sum += r < n ? hist[r] : 0u;
-            }
-            uint32_t incl = sum;
+            uint32_t run_r = incl_r - sum_r, run_c = incl_c - sum_c;
 #pragma unroll
-            for (int d = 1; d < 64; d <<= 1) {
-              const uint32_t o = __shfl_up(incl, d, 64);
-              if (lane >= d) {
-                incl += o;
+            for (int w = 0; w < kWaves; ++w) {
+              run_r += w < wave ? (uint32_t) sh.wave_tot[w] : 0u;
+              run_c += w < wave ? (uint32_t) sh.wave_tot[kWaves + w] : 0u;
+            }
+            for (int j = 0; j < chunk_r; ++j) {
+              const int r = tid * chunk_r + j;
+              if (r <= R) {
+                rowfirst[r] = (uint16_t) run_r;
+                run_r += hist_row[r];
               }
             }
-            uint32_t run = incl - sum;
-            for (int j = 0; j < chunk; ++j) {
-              const int r = lane * chunk + j;
-              if (r < n) {
-                cellstart[r] = (uint16_t) run;
-                run += hist[r];
+            for (int j = 0; j < chunk_c; ++j) {
+              const int r = tid * chunk_c + j;
+              if (r <= g.ncells) {
+                cellstart[r] = (uint16_t) run_c;
+                run_c += hist_cell[r];
               }
             }
           }
           __syncthreads();
           for (int i = tid; i < nF; i += T) {
-            const float4 c = gfix[i];
-            const int row  = (int) (int16_t) c.y;
-            const int col  = (int) (int16_t) c.x;
-            int cxi        = col >> g.cell_sx;
-            cxi            = cxi < g.cell_ncx ? cxi : g.cell_ncx - 1;
-            db[cellstart[(row >> g.cell_sy) * g.cell_ncx + cxi] + slot[i]] =
-              make_uint2(((uint32_t) row & 0xffffu) | ((uint32_t) col << 16), (uint32_t) i | ((uint32_t) canon[i] << 16));
-            inv[canon[i]] = (uint16_t) i;
+            bucket[rowfirst[rowcol[i] & 0xffffu] + slot[i]] = (uint16_t) i;
+          }
+          __syncthreads();
+          // rank inside the row = canonical position; bucket by cell (order inside a cell is irrelevant: ties are resolved on the
+          // canonical position)
+          for (int i = tid; i < nF; i += T) {
+            const uint32_t rc = rowcol[i];
+            const int row = (int) (rc & 0xffffu), col = (int) (rc >> 16);
+            const int s = rowfirst[row], e = rowfirst[row + 1];
+            int rank = 0;
+            for (int j = s; j < e; ++j) {
+              rank += bucket[j] < (uint16_t) i ? 1 : 0;
+            }
+            const int canon = s + rank;
+            int cxi         = col >> g.cell_sx;
+            cxi             = cxi < g.cell_ncx ? cxi : g.cell_ncx - 1;
+            db[cellstart[(row >> g.cell_sy) * g.cell_ncx + cxi] + cslot[i]] = make_uint2(rc, (uint32_t) i | ((uint32_t) canon << 16));
+            inv[canon]                                                      = (uint16_t) i;
           }
           if (tid == 0) {
             db[nF] = make_uint2(0x7fff7fffu, 0xffffffffu);  // sentinel behind the last entry: row / column no search pattern accepts
@@ -1186,10 +1270,20 @@ __global__ __launch_bounds__(T, SPLIT ? 6 : 1) void align_kernel(const AlignArgs
           if (lattice) {
             // rows in lattice order (the entry at db[pos] owns fdesc[pos] / fdesc_hi[pos]); the fixed cloud of the stereo adaptor is
             // row-sorted like the cells, so neighbouring positions read neighbouring rows
-            for (int pos = tid; pos < nF; pos += T) {
-              const int fi  = (int) (db[pos].y & 0xffffu);
-              fdesc[pos]    = gfd[2 * fi];
-              fdesc_hi[pos] = gfd[2 * fi + 1];
+            if (stage_rows) {
+              // (search half: the gathered rows also go to the per-frame cache beside the lattice image; the later searches of this
+              // frame loop stream them back at the top of the kernel)
+              au32x4* rows = split_search && g.rowcache ? g.rowcache + (size_t) frame * 2 * (size_t) g.max_fixed : nullptr;
+              for (int pos = tid; pos < nF; pos += T) {
+                const int fi    = (int) (db[pos].y & 0xffffu);
+                const au32x4 lo = gfd[2 * fi], hi = gfd[2 * fi + 1];
+                fdesc[pos]      = lo;
+                fdesc_hi[pos]   = hi;
+                if (rows) {
+                  rows[pos]               = lo;
+                  rows[g.max_fixed + pos] = hi;
+                }
+              }
             }
           } else {
             for (int i = tid; i < 2 * nF; i += T) {
@@ -1496,42 +1590,64 @@ __global__ __launch_bounds__(T, SPLIT ? 6 : 1) void align_kernel(const AlignArgs
           const float ratio = g.f.maximum_distance_ratio_to_second_best;
           const float dd    = sh.dd;
           int base          = 0;
-          for (int f0 = 0; f0 < nF; f0 += T) {
-            const int f = f0 + tid;
-            bool acc    = false;
-            if (f < nF) {
-              const uint32_t bk = bestkey[f];
-              if (bk != kNoneU32) {
-                const float resp = (float) (bk >> 17);
-                const uint32_t s = second[f];
-                const float fs   = s == kNoneU32 ? kFltMax : (float) s;
-                // bijection (:82-99): the winner must be the moving point's own best emission
-                acc = resp < dd && resp / fs < ratio && (bk & 1u) == 0u;
+          // two chunks of T fixed points per pass, their wave totals side by side in wave_tot: one barrier per pass (the headline's
+          // ~700 fixed points: one pass, one barrier)
+          constexpr int kWaves = T / 64;
+          static_assert(2 * kWaves <= 16, "AlignShared::wave_tot holds the wave totals of two chunks");
+          for (int f0 = 0; f0 < nF; f0 += 2 * T) {
+            if (f0 != 0) {
+              __syncthreads();  // every wave has read the totals of the previous pass
+            }
+            bool acc[2];
+            int pre[2];
+#pragma unroll
+            for (int k = 0; k < 2; ++k) {
+              const int f = f0 + k * T + tid;
+              acc[k]      = false;
+              if (f < nF) {
+                const uint32_t bk = bestkey[f];
+                if (bk != kNoneU32) {
+                  const float resp = (float) (bk >> 17);
+                  const uint32_t s = second[f];
+                  const float fs   = s == kNoneU32 ? kFltMax : (float) s;
+                  // bijection (:82-99): the winner must be the moving point's own best emission
+                  acc[k] = resp < dd && resp / fs < ratio && (bk & 1u) == 0u;
+                }
+              }
+              const unsigned long long bal = __ballot(acc[k]);
+              pre[k]                       = __popcll(bal & ((1ull << lane) - 1ull));
+              if (lane == 0) {
+                sh.wave_tot[k * kWaves + wave] = __popcll(bal);
               }
             }
-            const unsigned long long bal = __ballot(acc);
-            const int pre                = __popcll(bal & ((1ull << lane) - 1ull));
-            if (lane == 0) {
-              sh.wave_tot[wave] = __popcll(bal);
-            }
             __syncthreads();
-            int wbase = base;
-            for (int w = 0; w < wave; ++w) {
-              wbase += sh.wave_tot[w];
+            int wbase[2] = {0, 0};
+            int run      = base;
+#pragma unroll
+            for (int j = 0; j < 2 * kWaves; ++j) {
+              if (j == wave) {
+                wbase[0] = run;
+              }
+              if (j == kWaves + wave) {
+                wbase[1] = run;
+              }
+              run += sh.wave_tot[j];
             }
-            if (f < nF) {
-              second[f] = acc ? (uint32_t) (wbase + pre) : kNoneU32;
+            base = run;
+#pragma unroll
+            for (int k = 0; k < 2; ++k) {
+              const int f = f0 + k * T + tid;
+              if (f < nF) {
+                second[f] = acc[k] ? (uint32_t) (wbase[k] + pre[k]) : kNoneU32;
+              }
             }
-            for (int w = 0; w < T / 64; ++w) {
-              base += sh.wave_tot[w];
-            }
-            __syncthreads();
           }
           if (tid == 0) {
             sh.n_filtered = base;
           }
         }
-        __syncthreads();
+        // (no barrier: the section below is thread 0's, which holds the count itself; the slots in second[] are read behind the
+        // barrier that follows it)
         // -- matching ratio, reset + internal repeat, convergence latch (:215-291)
         if (tid == 0) {
           if (sh.n_projected == 0) {
@@ -1598,7 +1714,12 @@ __global__ __launch_bounds__(T, SPLIT ? 6 : 1) void align_kernel(const AlignArgs
             // round 5 wrote them here, 32 B per correspondence and search, behind two gathers that missed the L2)
           }
         }
-        __syncthreads();
+        // (search half: nothing in LDS is written after this point and the state written back below is thread 0's own or older
+        // than the barrier behind the decision, so neither this barrier nor the ones up to the write-back order anything there;
+        // with phase stamps on it stays, so that the commit stamp is the workgroup's and not thread 0's)
+        if (!split_search || g.stamps) {
+          __syncthreads();
+        }
         SUB_ACC(acc_commit);
         break;
       }  // finder compute()
@@ -1609,7 +1730,9 @@ __global__ __launch_bounds__(T, SPLIT ? 6 : 1) void align_kernel(const AlignArgs
       if (tid == 0 && sh.n_corr == 0) {
         sh.flags |= PRS_WARN_NO_MATCHES;
       }
-      __syncthreads();
+      if (!split_search) {
+        __syncthreads();
+      }
     }
     ALIGN_ACC(acc_finder);
     if (g.mode == PRS_MODE_FINDER || split_search) {
@@ -1776,7 +1899,9 @@ __global__ __launch_bounds__(T, SPLIT ? 6 : 1) void align_kernel(const AlignArgs
   }
 
   // ---- keep_only_inlier_correspondences: the returned vector keeps the inliers of the last linearisation, in order ----
-  __syncthreads();
+  if (!split_search) {
+    __syncthreads();
+  }
   if (g.mode == PRS_MODE_ALIGN && !split_search && g.a.keep_only_inlier_correspondences && sh.have_cls && !sh.error) {
     const int nc = sh.n_corr;
     int base     = 0;
@@ -1808,8 +1933,14 @@ __global__ __launch_bounds__(T, SPLIT ? 6 : 1) void align_kernel(const AlignArgs
     __syncthreads();
   }
 
+  if (split_search && lattice && !db_built && binds_disparity() && sh.error != PRS_ERR_CAPACITY) {
+    bind_disparity();  // a first launch that built no lattice
+  }
+
   // ---- write back --------------------------------------------------------------------------------
-  __syncthreads();
+  if (!split_search) {
+    __syncthreads();
+  }
   if (tid < 16) {
     if (!split_search) {
       g.b.X[(size_t) frame * 16 + tid] = sh.X[tid];
@@ -2459,10 +2590,10 @@ static inline uint32_t align_up16(uint32_t v) {
 struct SplitJob {
   bool active = false;
   // The job OWNS the buffers its launches read and write between enqueue and finish (frame control + pending counter, operand
-  // rows, lattice images): the context's shared scratch slots belong to whatever call runs next (scene clipper, extractor,
+  // rows, lattice images, descriptor rows in lattice order): the context's shared scratch slots belong to whatever call runs next (scene clipper, extractor,
   // brute-force matcher, merger), and a caller may run any of them between the two halves.  Grow-only; freed with the context.
-  void* own[3]        = {nullptr, nullptr, nullptr};
-  size_t own_bytes[3] = {0, 0, 0};
+  void* own[4]        = {nullptr, nullptr, nullptr, nullptr};
+  size_t own_bytes[4] = {0, 0, 0, 0};
   hipStream_t stream  = nullptr;  // the stream the rounds run on: where they were enqueued, or where the captured graph was last replayed (finish synchronises this one)
   hipStream_t capture_stream = nullptr;  // the stream align_batch_launch enqueued / captured on (what a rearm without a stream goes back to)
   ~SplitJob() {
@@ -2597,16 +2728,13 @@ int align_batch_launch(prs_context* ctx, const prs_pcf_params* finder, const prs
     g.off_second = u; u = align_up16(u + nf * 4);
     g.off_lut    = u; u = align_up16(u + lut_cap * 2);
     g.off_surv   = u; u = align_up16(u + (uint32_t) (with_operands ? kAlignThreads : kSearchThreads) * (uint32_t) g.surv_slots * 2);  // slots x u16 per thread
-    // GN-phase terms; the region also serves the database build (hist + slot + bucket) and the disparity column
+    // GN-phase terms; the region also serves the database build and the disparity column
     g.off_terms = off;
     uint32_t terms_bytes       = kTerms * kAlignThreads * 4;
-    const uint32_t histcap     = (R > (uint32_t) g.ncells ? R : (uint32_t) g.ncells) + 2;
-    const uint32_t build_bytes = histcap * 4 + (nf + 2) * 2 * 3 + (R + 2) * 2 + 16;
+    // lattice build: disparity column (read ahead), row + cell histograms, row | column, the integer disparity sums, slot + cslot + bucket, rowfirst
+    const uint32_t build_bytes = (nf + 40) * 4 + (R + 2 + (uint32_t) g.ncells + 2) * 4 + nf * 4 + 16 + (nf + 2) * 2 * 3 + (R + 2) * 2 + 16;
     if (build_bytes > terms_bytes) {
       terms_bytes = build_bytes;
-    }
-    if (nf * 4 + 160 > terms_bytes) {
-      terms_bytes = nf * 4 + 160;
     }
     const uint32_t kd_bytes = (uint32_t) kd_open_capacity((int) nf) * (40 + 7 * 4) + (nf + 2) * 2 * 3 + 64;  // KD-tree build scratch
     if (kdtree && kd_bytes > terms_bytes) {
@@ -2626,6 +2754,7 @@ int align_batch_launch(prs_context* ctx, const prs_pcf_params* finder, const prs
   g.pending = nullptr;
   g.dbcache = nullptr;
   g.db_blob = 0;
+  g.rowcache = nullptr;
   hipStream_t stream = ctx_stream(ctx);
   hipError_t e;
   // diagnostic: PRS_STAMPS=1 times the phases of the fused kernel; with PRS_STAMPS_SPLIT=1 the split pipeline
@@ -2690,6 +2819,14 @@ int align_batch_launch(prs_context* ctx, const prs_pcf_params* finder, const prs
   gs.dbcache = static_cast<unsigned char*>(job->buffer(stream, 2, (size_t) batch->batch * gs.db_blob));
   if (!gs.dbcache) {
     return ctx_fail(ctx, PRS_ERR_HIP, "prs_align_batch_run: lattice cache allocation failed");
+  }
+  // ... and, for the lattice patterns, the fixed descriptor rows in lattice order (two half-row arrays of max_fixed entries per frame)
+  gs.rowcache = nullptr;
+  if (!kdtree) {
+    gs.rowcache = static_cast<au32x4*>(job->buffer(stream, 3, (size_t) batch->batch * (size_t) max_fixed * 2 * sizeof(au32x4)));
+    if (!gs.rowcache) {
+      return ctx_fail(ctx, PRS_ERR_HIP, "prs_align_batch_run: descriptor row cache allocation failed");
+    }
   }
   const bool wide_slots = gs.surv_slots == 8;
   auto skernel = finder->search_type == PRS_SEARCH_CIRCLE
