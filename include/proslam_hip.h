@@ -111,7 +111,9 @@ PRS_API int prs_version(void);
  * the RGB-D preprocessor: prs_depth_params, prs_depth_batch and their two entry points, no existing struct changed; the loop aligner's
  * prs_point_align_params, prs_point_align_pairs, prs_point_align_result and its two entry points came later under the same version:
  * new structs and new entry points only, nothing a 104 client passes changed; so did the loop detector's place database:
- * prs_place_db, prs_place_params, prs_place_queries, prs_place_pairs and the prs_place_* entry points).  Callers memset() parameter structs before
+ * prs_place_db, prs_place_params, prs_place_queries, prs_place_pairs and the prs_place_* entry points; and the pose-graph optimiser:
+ * prs_pose_graph_params, prs_pose_graph_result, prs_pose_graphs, prs_pose_graph_closures, the prs_pose_graph_* entry points and the
+ * status PRS_ERR_NOT_POSITIVE_DEFINITE).  Callers memset() parameter structs before
  * filling them, so that fields they do not know select the shipped defaults (all zero). */
 #define PRS_ABI_VERSION 104
 PRS_API int prs_abi_check(int32_t header_version, uint64_t sizeof_stereo_params, uint64_t sizeof_pcf_params, uint64_t sizeof_aligner_params,
@@ -1012,8 +1014,8 @@ PRS_API int prs_depth_measurements(prs_context* ctx, const prs_depth_params* par
  * replaces MultiAligner3DQR "loop_aligner" with one AlignerSliceProcessor3D (registration/aligner_slice_processor_3d.hpp:7-22:
  * SE3Point2PointErrorFactor, information I3; registered at registration/instances.cpp:28,52), the aligner every shipped .conf wires
  * in as MultiLoopDetectorHBST3D.relocalize_aligner (kitti.conf:938-978), and the accept / reject verdict of the loop detector and
- * MultiRelocalizer3D (parameter comments kitti.conf:966-977).  The candidate search in front of it is the place database below;
- * pose-graph insertion and the closure merger are not served.
+ * MultiRelocalizer3D (parameter comments kitti.conf:966-977).  The candidate search in front of it is the place database below, the
+ * consumer of an accepted closure the pose-graph optimiser at the end of this header; the closure merger is not served.
  *
  * The factor, the robustifiers, the loop and the verdict live in srrg2_solver / srrg2_slam_interfaces, not in the tree
  * (BUILD-DEFINED, stated like rows a13 / a14 of SURVEY.md Appendix A):
@@ -1198,6 +1200,131 @@ PRS_API int prs_place_query(prs_place_db* db, const prs_place_params* params, in
 /* device pointers, asynchronous: after prs_place_query_batch, fill the pair slots of a loop-closure batch (one kernel launch) */
 PRS_API int prs_place_gather_pairs(prs_place_db* db, const prs_place_params* params, const prs_place_queries* queries,
                                    const prs_place_pairs* pairs);
+
+/* ================================================================================================
+ * Pose-graph optimiser: SE(3) graphs with loop closures (the consumer of the loop detector's accepted closures)
+ * replaces the `global_solver` every shipped .conf wires into MultiGraphSLAM3D (kitti.conf:895-936 -> Solver :420-444 with
+ * max_iterations 10, IterationAlgorithmGN :826-832 with damping 1e-06, SimpleTerminationCriteria :884-889 with epsilon 0.001,
+ * SparseBlockLinearSolverCholeskyCholmod; closure_validator is null in every file) and the insertion of a closure
+ * (query map, candidate map, X) as an edge of the graph.  The closure MERGER (landmarks of the two maps) is still not served.
+ *
+ * The factor, the algorithm, the criterion and the linear solver live in srrg2_solver, not in the tree (BUILD-DEFINED, stated like
+ * rows a13 / a14 of SURVEY.md Appendix A and the loop aligner above).  Everything is float64 except the measurements:
+ *   factor       stands in for SE3PosePoseGeodesicErrorFactor.  Edge (from, to, Z, Omega): E = Z^-1 X_from^-1 X_to (isometry
+ *                inverses [R^T | -R^T t] and products in the expression order of csrc/prs_se3.h, in double), e = t2tnq(E): the
+ *                translation and the imaginary part of the unit quaternion (w, v) with w >= 0; chi = e^T Omega e.  Z is float32
+ *                [16] (it comes from prs_point_align_pairs.X or the tracker), Omega float32 [36] row-major, both widened exactly.
+ *   perturbation X <- X tnq2t(dx) (VariableSE3QuaternionRight).  Rotations are NOT re-orthonormalised: X in must be isometries.
+ *   Jacobians    with E = [R_E | t_E], A = X_from^-1 X_to = [R_A | t_A], Z = [R_Z | t_Z]:
+ *                J_to = [[R_E, 0], [0, w I + [v]x]],  J_from = [[-R_Z^T, 2 R_Z^T [t_A]x], [0, -(w I - [v]x) R_Z^T]]
+ *                (tests/test_pose_graph_ref.py checks both against central differences).
+ *   sums         edges are taken in ascending index.  Per edge: Omega e, Omega J_from, Omega J_to (each entry a chain over the
+ *                inner index, ascending, starting with its first product), then J_from^T (Omega J_from), J_to^T (Omega J_to),
+ *                J_to^T (Omega J_from) -- the block (to, from); for from > to its transpose goes to block (from, to) of the lower
+ *                triangle -- and J^T (Omega e), the same chains over the row index.  A diagonal block, an off-diagonal block, a
+ *                segment of b and chi each add their edges' terms in ascending edge index from +0.  Separate multiplies and adds.
+ *   fixed nodes  fixed[i] != 0: the node's edges add nothing to its blocks and its segment of b; its diagonal block is the
+ *                identity (not damped), so dx = 0 and the pose is not touched.
+ *   damping      prs_gn_step's: PRS_DAMPING_DIAG h_rr <- h_rr + damping * h_rr (shipped), PRS_DAMPING_IDENTITY h_rr + damping.
+ *   solve        scalar LDL^T on the row envelope in the natural node order, no reordering: first(j) = the smallest node joined
+ *                to j by an edge, or j; the six scalar rows of node j start at column 6 first(j) and envelope_blocks = sum over j of
+ *                (j - first(j) + 1).  u_rc = h_rc - sum_m l_rm u_cm, l_rc = u_rc * (1 / d_c), d_r = h_rr - sum_m l_rm u_rm, every sum
+ *                one chain in ascending m over the columns both rows hold; one IEEE reciprocal per pivot.  y_r = -b_r - sum_m l_rm
+ *                y_m (ascending m); z = y * (1 / d); for r descending dx_r = z_r, then z_m -= l_rm dx_r for every m of row r.
+ *                A pivot that is <= 0 or not finite ends the graph with PRS_ERR_NOT_POSITIVE_DEFINITE: its poses stay as they
+ *                were before that iteration.  (A free node without an edge, damping 0, is such a case.  A free COMPONENT with
+ *                edges but without a fixed node is singular only up to rounding: it may pass with a meaningless step; fix a node
+ *                per component or damp.)
+ *   loop         iteration it = 0 .. max_iterations - 1: linearise (chi[it]), test, solve, update every free node.  The test is the
+ *                BUILD-DEFINED reading of SimpleTerminationCriteria's "ratio of decay of chi2 between iteration": epsilon > 0,
+ *                it > 0 and chi[it-1] - chi[it] < epsilon * chi[it-1] stops before solving; epsilon <= 0 disables it.  After the
+ *                last update one error-only pass writes chi_final.  max_iterations <= PRS_POSE_GRAPH_MAX_ITERATIONS.
+ * Same inputs give the same bits for every batch size, position in the batch and entry point: no floating-point atomics.
+ * Checked per graph (result[].status, other graphs unaffected), in this order: a negative count PRS_ERR_RANGE; n_nodes >
+ * node_stride or n_edges > edge_stride PRS_ERR_CAPACITY; n_nodes == 0 PRS_WARN_EMPTY_INPUT; an endpoint outside [0, n_nodes) or
+ * from == to PRS_ERR_RANGE; an envelope larger than the graph's share of the workspace PRS_ERR_CAPACITY.  No edges, or no free
+ * node: success with 0 iterations.  Multiple edges between the same pair are allowed.
+ * Limits: node_stride <= 1024 (PRS_ERR_CAPACITY at the call).  One wave works on a graph; it keeps 1 / d and the right-hand side
+ * (6 doubles per node each), first() and the row offsets (one int per node each) in LDS, 104 bytes per node, and the block row it
+ * is factorising in what is left of the 160 KiB (54 KiB, 194 blocks wide, at node_stride 1024; wider rows are factorised in place
+ * in the workspace, same bits).  The envelope itself lives in the caller's workspace: 288 bytes per block.
+ * ============================================================================================== */
+#define PRS_POSE_GRAPH_MAX_ITERATIONS 32
+enum { PRS_ERR_NOT_POSITIVE_DEFINITE = -10 }; /* a pivot of the pose graph's normal matrix is <= 0 or not finite */
+
+typedef struct {
+  float damping;             /* IterationAlgorithmGN damping (1e-06 in every shipped .conf) */
+  int32_t damping_form;      /* PRS_DAMPING_DIAG (0, shipped) or PRS_DAMPING_IDENTITY */
+  int32_t max_iterations;    /* Solver max_iterations (10), <= PRS_POSE_GRAPH_MAX_ITERATIONS */
+  float epsilon;             /* SimpleTerminationCriteria epsilon (0.001); <= 0: no criterion */
+  float closure_information; /* prs_pose_graph_append_closures: Omega = closure_information * I6 */
+} prs_pose_graph_params;
+
+typedef struct {
+  double chi[PRS_POSE_GRAPH_MAX_ITERATIONS]; /* chi[it] of every linearisation, 0 past `linearizations` */
+  double chi_final;                          /* after the last update */
+  int32_t linearizations;                    /* entries of chi[] */
+  int32_t iterations;                        /* updates applied (a run the criterion stops has linearizations = iterations + 1) */
+  int32_t envelope_blocks;
+  int32_t status;                            /* PRS_OK, PRS_WARN_EMPTY_INPUT or a PRS_ERR_* code */
+} prs_pose_graph_result;
+
+/* device-resident batch of B independent graphs */
+typedef struct {
+  int32_t batch;
+  int32_t node_stride;       /* <= 1024 */
+  int32_t edge_stride;
+  int32_t reserved;
+  double* X;                 /* [batch][node_stride][16] in: guess, out: estimate (row-major 4x4 isometries), 8-byte aligned */
+  const uint8_t* fixed;      /* [batch][node_stride] */
+  const int32_t* n_nodes;    /* [batch] */
+  int32_t* from;             /* [batch][edge_stride] (written by prs_pose_graph_append_closures only) */
+  int32_t* to;               /* [batch][edge_stride] */
+  float* Z;                  /* [batch][edge_stride][16] measurement: X_from^-1 X_to */
+  float* omega;              /* [batch][edge_stride][36] row-major, or NULL: identity for every edge */
+  int32_t* n_edges;          /* [batch] in; in/out for prs_pose_graph_append_closures */
+  void* workspace;           /* the envelopes: workspace_bytes / batch per graph (prs_pose_graph_workspace_bytes) */
+  uint64_t workspace_bytes;
+  prs_pose_graph_result* result; /* [batch] */
+} prs_pose_graphs;
+
+/* the loop detector's outputs for B queries of max_candidates slots each (ops.LoopDetectorBatch: prs_place_queries.candidates,
+ * prs_point_align_pairs.result and .X) and where they go.  DIRECTION: prs_place_gather_pairs makes the query the fixed cloud and the
+ * candidate map the moving one, and the aligner's X is movingInFixed (e = R p + t - f, p a moving point): X = X_query^-1 X_candidate.
+ * The appended edge is therefore from = the query's node, to = the candidate map's node, Z = X. */
+typedef struct {
+  int32_t n_queries;
+  int32_t max_candidates;
+  int32_t n_maps;                       /* entries of node_of_map */
+  int32_t reserved;
+  const int32_t* candidates;            /* [n_queries][max_candidates] map indices, -1 = none */
+  const prs_point_align_result* result; /* [n_queries * max_candidates]: accepted != 0 selects the slot */
+  const float* X;                       /* [n_queries * max_candidates][16] */
+  const int32_t* graph_of_query;        /* [n_queries] target graph; outside [0, batch): the query is skipped */
+  const int32_t* node_of_query;         /* [n_queries] node of the query's local map; < 0: skipped */
+  const int32_t* node_of_map;           /* [n_maps] node of every stored map; < 0: slots of that map are skipped */
+  int32_t* status;                      /* out [batch]: PRS_OK, PRS_ERR_CAPACITY (nothing appended to that graph), PRS_ERR_RANGE */
+  int32_t* n_appended;                  /* optional out [batch] */
+} prs_pose_graph_closures;
+
+/* bytes of workspace for `batch` graphs whose envelopes hold up to envelope_blocks_per_graph 6 x 6 blocks each (288 bytes a block;
+ * a chain of n nodes has 2 n - 1, a closure (i, j) adds |j - i| - 1 unless a longer one already ends at the same node) */
+PRS_API uint64_t prs_pose_graph_workspace_bytes(int32_t batch, int32_t node_stride, int64_t envelope_blocks_per_graph);
+/* sizeof prs_pose_graph_params, _result, prs_pose_graphs, prs_pose_graph_closures as the library was compiled (bindings check) */
+PRS_API void prs_pose_graph_struct_sizes(uint64_t* sizes4);
+/* device pointers, asynchronous on the context's stream: one kernel launch, no allocation and no synchronisation (graph-capturable) */
+PRS_API int prs_pose_graph_optimize_batch(prs_context* ctx, const prs_pose_graph_params* params, const prs_pose_graphs* graphs);
+/* device pointers, asynchronous, one kernel launch: appends the accepted closures to the graphs' edge lists, per graph in ascending
+ * slot order (a prefix count, not arrival order).  A graph whose edge_stride would overflow gets PRS_ERR_CAPACITY and nothing.
+ * graphs->omega == NULL requires closure_information == 1 (PRS_ERR_UNSUPPORTED otherwise). */
+PRS_API int prs_pose_graph_append_closures(prs_context* ctx, const prs_pose_graph_params* params, const prs_pose_graphs* graphs,
+                                           const prs_pose_graph_closures* closures);
+/* host pointers, one graph of up to 1024 nodes: what an adapter's compute() binds.  X16 [n_nodes][16] double in/out, fixed [n_nodes],
+ * from / to [n_edges], Z16 [n_edges][16] float, omega36 [n_edges][36] float or NULL.  Sizes the envelope, uploads, runs, downloads,
+ * synchronises; returns the graph's status. */
+PRS_API int prs_pose_graph_optimize(prs_context* ctx, const prs_pose_graph_params* params, int32_t n_nodes, double* X16,
+                                    const uint8_t* fixed, int32_t n_edges, const int32_t* from, const int32_t* to, const float* Z16,
+                                    const float* omega36, prs_pose_graph_result* result);
 
 #ifdef __cplusplus
 }

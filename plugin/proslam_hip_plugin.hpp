@@ -1230,4 +1230,80 @@ protected:
   std::vector<CorrespondenceVector> _correspondences;
 };
 
+
+// ------------------------------------------------------------------------------------------------
+// The global solver of the pose graph: Solver + IterationAlgorithmGN + SimpleTerminationCriteria as MultiGraphSLAM3D's
+// `global_solver` uses them (kitti.conf:895-936), over prs_pose_graph_optimize.  A graph is handed over as plain arrays: variable i is
+// the i-th pose (VariableSE3QuaternionRight, estimate as a row-major 4x4 double), a factor is (from, to, measurement, information)
+// (SE3PosePoseGeodesicErrorFactor).  setGraph() copies, compute() optimises, poses() / pose(i) give the estimates back.
+class SolverPoseGraphHIP {
+public:
+  PropertyInt param_max_iterations{10};  // Solver max_iterations
+  PropertyFloat param_damping{1e-6f};    // IterationAlgorithmGN damping
+  PropertyFloat param_epsilon{1e-3f};    // SimpleTerminationCriteria epsilon
+  PropertyInt param_damping_form{PRS_DAMPING_DIAG};
+
+  explicit SolverPoseGraphHIP(ContextPtr ctx) : _ctx(std::move(ctx)) {}
+
+  // poses16 [n][16] double, fixed [n] (nonzero = the variable is fixed), from / to [m], measurements16 [m][16] float,
+  // information36 [m][36] float or nullptr (identity)
+  void setGraph(size_t n, const double* poses16, const uint8_t* fixed, size_t m, const int32_t* from, const int32_t* to,
+                const float* measurements16, const float* information36 = nullptr) {
+    _poses.assign(poses16, poses16 + 16 * n);
+    _fixed.assign(fixed, fixed + n);
+    _from.assign(from, from + m);
+    _to.assign(to, to + m);
+    _z.assign(measurements16, measurements16 + 16 * m);
+    _omega.clear();
+    if (information36) _omega.assign(information36, information36 + 36 * m);
+    _set = true;
+  }
+
+  // one closure (or odometry) edge more, e.g. an accepted verdict of the loop detector: measurement = X_from^-1 X_to
+  void addFactor(int32_t from, int32_t to, const float* measurement16, const float* information36 = nullptr) {
+    if (!_omega.empty() || information36) {
+      static const float eye[36] = {1, 0, 0, 0, 0, 0, 0, 1, 0, 0, 0, 0, 0, 0, 1, 0, 0, 0, 0, 0, 0, 1, 0, 0, 0, 0, 0, 0, 1, 0, 0, 0, 0, 0, 0, 1};
+      if (_omega.empty()) {
+        for (size_t k = 0; k < _from.size(); ++k) _omega.insert(_omega.end(), eye, eye + 36);
+      }
+      const float* o = information36 ? information36 : eye;
+      _omega.insert(_omega.end(), o, o + 36);
+    }
+    _from.push_back(from);
+    _to.push_back(to);
+    _z.insert(_z.end(), measurement16, measurement16 + 16);
+  }
+
+  void compute() {
+    if (!_set) throw std::runtime_error("SolverPoseGraphHIP::compute|ERROR: graph not set");
+    prs_pose_graph_params p;
+    std::memset(&p, 0, sizeof(p));
+    p.damping             = param_damping.value();
+    p.damping_form        = param_damping_form.value();
+    p.max_iterations      = param_max_iterations.value();
+    p.epsilon             = param_epsilon.value();
+    p.closure_information = 1.0f;
+    const int rc = prs_pose_graph_optimize(_ctx->get(), &p, (int32_t) _fixed.size(), _poses.data(), _fixed.data(), (int32_t) _from.size(),
+                                           _from.data(), _to.data(), _z.data(), _omega.empty() ? nullptr : _omega.data(), &_result);
+    if (rc < 0) throw std::runtime_error(std::string("SolverPoseGraphHIP::compute|ERROR: ") + prs_last_error(_ctx->get()));
+    warn("SolverPoseGraphHIP::compute", rc);
+  }
+
+  size_t size() const { return _fixed.size(); }
+  const std::vector<double>& poses() const { return _poses; }
+  const double* pose(size_t i) const { return _poses.data() + 16 * i; }
+  int iterations() const { return _result.iterations; }
+  double chi2() const { return _result.chi_final; }
+  const prs_pose_graph_result& result() const { return _result; }
+
+protected:
+  ContextPtr _ctx;
+  bool _set = false;
+  std::vector<double> _poses;
+  std::vector<uint8_t> _fixed;
+  std::vector<int32_t> _from, _to;
+  std::vector<float> _z, _omega;
+  prs_pose_graph_result _result = {};
+};
+
 }  // namespace proslam_hip

@@ -26,6 +26,7 @@ ERR_HIP = -3
 ERR_RANGE = -4
 ERR_UNSUPPORTED = -5
 ERR_NO_DEVICE = -6
+ERR_NOT_POSITIVE_DEFINITE = -10  # PRS_ERR_NOT_POSITIVE_DEFINITE (pose-graph optimiser)
 
 
 class StereoParams(C.Structure):
@@ -341,6 +342,37 @@ class PlacePairs(C.Structure):
                 ("X", C.c_void_p)]
 
 
+DAMPING_DIAG, DAMPING_IDENTITY = 0, 1  # PRS_DAMPING_*
+POSE_GRAPH_MAX_ITERATIONS = 32         # PRS_POSE_GRAPH_MAX_ITERATIONS
+
+
+class PoseGraphParams(C.Structure):
+    """prs_pose_graph_params"""
+    _fields_ = [("damping", C.c_float), ("damping_form", C.c_int32), ("max_iterations", C.c_int32), ("epsilon", C.c_float),
+                ("closure_information", C.c_float)]
+
+
+class PoseGraphResult(C.Structure):
+    """prs_pose_graph_result"""
+    _fields_ = [("chi", C.c_double * POSE_GRAPH_MAX_ITERATIONS), ("chi_final", C.c_double), ("linearizations", C.c_int32),
+                ("iterations", C.c_int32), ("envelope_blocks", C.c_int32), ("status", C.c_int32)]
+
+
+class PoseGraphs(C.Structure):
+    """prs_pose_graphs (device pointers)"""
+    _fields_ = [("batch", C.c_int32), ("node_stride", C.c_int32), ("edge_stride", C.c_int32), ("reserved", C.c_int32),
+                ("X", C.c_void_p), ("fixed", C.c_void_p), ("n_nodes", C.c_void_p), ("from_", C.c_void_p), ("to", C.c_void_p),
+                ("Z", C.c_void_p), ("omega", C.c_void_p), ("n_edges", C.c_void_p), ("workspace", C.c_void_p),
+                ("workspace_bytes", C.c_uint64), ("result", C.c_void_p)]
+
+
+class PoseGraphClosures(C.Structure):
+    """prs_pose_graph_closures (device pointers)"""
+    _fields_ = [("n_queries", C.c_int32), ("max_candidates", C.c_int32), ("n_maps", C.c_int32), ("reserved", C.c_int32),
+                ("candidates", C.c_void_p), ("result", C.c_void_p), ("X", C.c_void_p), ("graph_of_query", C.c_void_p),
+                ("node_of_query", C.c_void_p), ("node_of_map", C.c_void_p), ("status", C.c_void_p), ("n_appended", C.c_void_p)]
+
+
 MODE_ALIGN, MODE_FINDER, MODE_LINEARIZE = 0, 1, 2
 
 # every symbol include/proslam_hip.h declares: (restype, argtypes)
@@ -409,6 +441,12 @@ SYMBOLS = {
     "prs_place_query_batch": (C.c_int, [_vp, C.POINTER(PlaceParams), C.POINTER(PlaceQueries)]),
     "prs_place_query": (C.c_int, [_vp, C.POINTER(PlaceParams), C.c_int64, _vp, _vp, C.c_int32, _vp, _i32p, _vp, C.c_int32, _vp, _vp]),
     "prs_place_gather_pairs": (C.c_int, [_vp, C.POINTER(PlaceParams), C.POINTER(PlaceQueries), C.POINTER(PlacePairs)]),
+    "prs_pose_graph_workspace_bytes": (C.c_uint64, [C.c_int32, C.c_int32, C.c_int64]),
+    "prs_pose_graph_struct_sizes": (None, [C.POINTER(C.c_uint64)]),
+    "prs_pose_graph_optimize_batch": (C.c_int, [_vp, C.POINTER(PoseGraphParams), C.POINTER(PoseGraphs)]),
+    "prs_pose_graph_append_closures": (C.c_int, [_vp, C.POINTER(PoseGraphParams), C.POINTER(PoseGraphs), C.POINTER(PoseGraphClosures)]),
+    "prs_pose_graph_optimize": (C.c_int, [_vp, C.POINTER(PoseGraphParams), C.c_int32, _vp, _vp, C.c_int32, _vp, _vp, _vp, _vp,
+                                          C.POINTER(PoseGraphResult)]),
     "prs_pose_compose_batch": (C.c_int, [_vp, C.c_int32, _vp, _vp, _vp]),
     "prs_motion_predict_batch": (C.c_int, [_vp, C.c_int32, _vp, _vp, _vp]),
     "prs_merge_batch_run": (C.c_int, [_vp, C.POINTER(MergerParams), C.POINTER(MergeBatch)]),

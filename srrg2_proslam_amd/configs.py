@@ -36,6 +36,16 @@ def _place(max_distance, minimum_age, min_inliers):
             "maximum_distance_for_merge": 0}
 
 
+def _graph(algorithm, damping):
+    """the global solver of the pose graph (include/proslam_hip.h prs_pose_graph_*): MultiGraphSLAM3D.global_solver, a Solver with
+    max_iterations [10] and SimpleTerminationCriteria epsilon 0.001 in every shipped file; closure_validator is null in all of them.
+    kitti, euroc and malaga wire IterationAlgorithmGN with damping 1e-06 and SparseBlockLinearSolverCholeskyCholmod; icl and tum wire
+    IterationAlgorithmLM (user_lambda_init 0: its own lambda schedule) and SparseBlockLinearSolverCholeskyCSparse.  SUBSTITUTION:
+    this build has the damped Gauss-Newton only (a direct float64 LDL^T on the row envelope stands in for both linear solvers); for
+    the LM files `damping` is the Gauss-Newton files' 1e-06, not a value of theirs."""
+    return {"algorithm": algorithm, "damping": damping, "max_iterations": 10, "epsilon": 0.001}
+
+
 KITTI = {
     "name": "kitti",
     # tests/fixtures.hpp:810-816,1093-1094
@@ -65,6 +75,8 @@ KITTI = {
     # :91-110 (MultiRelocalizer3D)
     "loop": _loop("clamp", 3.0, 100, 30, 25.0, (25, 0.5, 2.0), (25, 0.5, 5.0)),
     "place": _place(25.0, 10, 25),  # kitti.conf:938-978
+    # kitti.conf:895-936 (global_solver) -> Solver :420-444, IterationAlgorithmGN :826-832, SimpleTerminationCriteria :884-889
+    "graph": _graph("IterationAlgorithmGN", 1e-06),
     "depth": {"min": 4.0, "max": 80.0},
 }
 
@@ -94,6 +106,7 @@ EUROC = {
     # euroc.conf: MultiLoopDetectorHBST3D.relocalize_aligner -> AlignerSliceProcessor3D + RobustifierSaturated, MultiRelocalizer3D
     "loop": _loop("saturated", 1.0, 100, 0, 50.0, (100, 0.9, 0.25), (100, 0.9, 100.0)),
     "place": _place(50.0, 5, 100),  # euroc.conf: MultiLoopDetectorHBST3D
+    "graph": _graph("IterationAlgorithmGN", 1e-06),  # euroc.conf:641-651 (MultiGraphSLAM3D -> global_solver)
     "depth": {"min": 1.0, "max": 15.0},
 }
 
@@ -120,6 +133,7 @@ ICL = {
     # icl.conf:1-29 (loop_aligner), :600-628 (slice + RobustifierClamp), :153-158 (damping), :197-237 (detector), :687-705 (relocalizer)
     "loop": _loop("clamp", 1.0, 10, 0, 35.0, (50, 0.5, 0.1), (100, 0.5, 1000.0)),
     "place": _place(35.0, 1, 50),  # icl.conf:197-240
+    "graph": _graph("IterationAlgorithmLM", 1e-06),  # icl.conf:797-807 (MultiGraphSLAM3D -> global_solver), LM :665-681
     "depth": {"min": 0.5, "max": 6.0},
     # RawDataPreprocessorMonocularDepth (icl.conf:642-650) and its IntensityFeatureExtractorBinned3D (icl.conf:745-770)
     "rgbd": {"depth_scaling_factor_to_meters": 0.001, "detector_threshold": 5, "enable_non_maximum_suppression": 1,
@@ -149,6 +163,7 @@ TUM = {
     # tum.conf: MultiLoopDetectorHBST3D.relocalize_aligner -> AlignerSliceProcessor3D + RobustifierClamp, MultiRelocalizer3D
     "loop": _loop("clamp", 0.25, 10, 0, 25.0, (40, 0.5, 0.05), (40, 0.5, 100.0)),
     "place": _place(25.0, 1, 40),  # tum.conf: MultiLoopDetectorHBST3D
+    "graph": _graph("IterationAlgorithmLM", 1e-06),  # tum.conf:453-463 (MultiGraphSLAM3D -> global_solver), LM :174-190
     "depth": {"min": 0.5, "max": 6.0},
     # RawDataPreprocessorMonocularDepth (tum.conf:633-640) and its IntensityFeatureExtractorBinned3D (tum.conf:858-883)
     "rgbd": {"depth_scaling_factor_to_meters": 0.001, "detector_threshold": 5, "enable_non_maximum_suppression": 1,

@@ -185,6 +185,7 @@ const char* prs_status_string(int status) {
     case PRS_ERR_HISTORY: return "measurement history of a landmark is full";
     case PRS_ERR_SCENE_FULL: return "map capacity exhausted";
     case PRS_ERR_DUPLICATE: return "scene index referenced by two correspondences";
+    case PRS_ERR_NOT_POSITIVE_DEFINITE: return "normal matrix of the pose graph is not positive definite";
     default: return status > 0 ? "warning bits set" : "unknown error";
   }
 }

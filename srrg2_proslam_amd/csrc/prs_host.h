@@ -21,6 +21,7 @@ enum Arena {
   ARENA_STAGE,             // device side of the host-pointer entry points' staging block
   ARENA_STAGE_BRUTEFORCE,  // the same for prs_bruteforce_match, whose block stays live across its relaunches
   ARENA_STAGE_SOLVER,      // the same for prs_gn_step_ex and prs_selftest_reciprocal
+  ARENA_STAGE_POSE_GRAPH,  // the same for prs_pose_graph_optimize, whose block also holds the graph's envelope
   ARENA_PINNED,            // host side (pinned) of all of them: an entry point synchronises before it returns
   ARENA_COUNT
 };
@@ -192,6 +193,9 @@ int describe_selected_launch(prs_context* ctx, const prs_extract_batch* batch, u
 int selective_extract_launch(prs_context* ctx, const prs_selective_extractor_params* params, const prs_selective_extract_batch* batch);
 int depth_measurements_launch(prs_context* ctx, const prs_depth_params* params, const prs_depth_batch* batch);
 int point_align_launch(prs_context* ctx, const prs_point_align_params* params, const prs_point_align_pairs* batch);
+int pose_graph_launch(prs_context* ctx, const prs_pose_graph_params* params, const prs_pose_graphs* graphs);
+int pose_graph_append_launch(prs_context* ctx, const prs_pose_graph_params* params, const prs_pose_graphs* graphs,
+                             const prs_pose_graph_closures* closures);
 int pose_compose_launch(prs_context* ctx, int batch, const float* prediction, const float* X, float* pose_out);
 int motion_predict_launch(prs_context* ctx, int batch, const float* prev2, const float* prev1, float* pred);
 int merge_batch_launch(prs_context* ctx, const prs_merger_params* params, const prs_merge_batch* batch);

@@ -337,3 +337,27 @@ def place_params(conf):
     read, unused.  Only fields present in the file are returned."""
     detector = next((r for r in conf.records if r.class_name.startswith("MultiLoopDetector")), None)
     return _pick(detector, _PLACE) if detector is not None else {}
+
+
+def graph_params(conf):
+    """the global solver's parameter group of a parsed configuration (the pose-graph optimiser, include/proslam_hip.h
+    prs_pose_graph_*), following the file's own wiring: MultiGraphSLAM* -> global_solver (a Solver: max_iterations) -> algorithm
+    (IterationAlgorithmGN: damping), termination_criteria (SimpleTerminationCriteria: epsilon) and linear_solver (its class name);
+    closure_validator as the file has it (0 = none).  Only fields present in the file are returned."""
+    slam = next((r for r in conf.records if r.class_name.startswith("MultiGraphSLAM")), None)
+    solver = conf.follow(slam, "global_solver") if slam is not None else None
+    if solver is None:
+        return {}
+    out = _pick(solver, ("max_iterations",))
+    algorithm = conf.follow(solver, "algorithm")
+    if algorithm is not None:
+        out["algorithm"] = algorithm.class_name
+        out.update(_pick(algorithm, ("damping",)))
+    criteria = conf.follow(solver, "termination_criteria")
+    if criteria is not None:
+        out.update(_pick(criteria, ("epsilon",)))
+    linear = conf.follow(solver, "linear_solver")
+    if linear is not None:
+        out["linear_solver"] = linear.class_name
+    out["closure_validator"] = 0 if conf.follow(slam, "closure_validator") is None else 1
+    return out

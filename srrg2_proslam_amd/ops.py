@@ -1010,6 +1010,147 @@ class LoopDetectorBatch:
                     accepted=[self.closures.pairs.result_of(s)["accepted"] for s in slots], search=r)
 
 
+# ---- pose-graph optimiser: the global solver over SE(3) graphs with loop closures (include/proslam_hip.h) ----
+def pose_graph_params(cfg_graph, closure_information=1.0, **overrides):
+    """prs_pose_graph_params from a configs.py `graph` group; overrides by field name"""
+    p = _lib.PoseGraphParams()
+    p.damping, p.damping_form = cfg_graph["damping"], _lib.DAMPING_DIAG
+    p.max_iterations, p.epsilon = cfg_graph["max_iterations"], cfg_graph["epsilon"]
+    p.closure_information = closure_information
+    for k, v in overrides.items():
+        setattr(p, k, v)
+    return p
+
+
+def _graph_result_dict(r):
+    n = r.linearizations
+    return dict(chi=np.ctypeslib.as_array(r.chi)[:n].copy(), chi_final=np.float64(r.chi_final), linearizations=n, iterations=r.iterations,
+                envelope_blocks=r.envelope_blocks, status=r.status)
+
+
+def pose_graph_optimize(ctx, params, poses, fixed, src, dst, Z, omega=None):
+    """host arrays, one graph -> (X [n, 4, 4] float64, result dict, status).  poses [n, 4, 4] float64, fixed [n], src / dst [E], Z
+    [E, 4, 4] float32, omega [E, 6, 6] float32 or None (identity).  A refused or numerically failed graph raises ProslamHipError."""
+    X = _np(poses, np.float64, (-1, 16)).copy()
+    fx = _np(fixed, np.uint8, (-1,))
+    f, t = _np(src, np.int32, (-1,)), _np(dst, np.int32, (-1,))
+    z = _np(Z, np.float32, (-1, 16))
+    om = _np(omega, np.float32, (-1, 36)) if omega is not None else None
+    res = _lib.PoseGraphResult()
+    rc = _lib.load().prs_pose_graph_optimize(ctx._h, C.byref(params), X.shape[0], _p(X), _p(fx), len(f), _p(f), _p(t), _p(z),
+                                             _p(om) if om is not None else None, C.byref(res))
+    _check(ctx, rc, "prs_pose_graph_optimize")
+    return X.reshape(-1, 4, 4), _graph_result_dict(res), rc
+
+
+def pose_graph_envelope_blocks(n_nodes, src, dst):
+    """6 x 6 blocks of the row envelope of a graph: the sum over nodes j of j - first(j) + 1 (first = smallest neighbour, or j)"""
+    first = np.arange(int(n_nodes))
+    for a, b in zip(np.asarray(src).reshape(-1), np.asarray(dst).reshape(-1)):
+        lo, hi = (a, b) if a < b else (b, a)
+        if 0 <= lo and hi < n_nodes and lo != hi:
+            first[hi] = min(first[hi], lo)
+    return int(np.sum(np.arange(int(n_nodes)) - first + 1))
+
+
+class PoseGraphBatch:
+    """B pose graphs resident in HBM (torch tensors own the memory): poses (float64), fixed flags, edge lists with float32
+    measurements and information matrices, the envelope workspace and the results.  envelope_blocks: room per graph (default: the
+    full lower triangle of node_stride nodes when that is small, else 64 blocks per node)."""
+
+    def __init__(self, device, batch, node_stride, edge_stride, envelope_blocks=None, with_omega=True):
+        import torch
+        dev = torch.device("cuda", device)
+        self.batch, self.node_stride, self.edge_stride = int(batch), int(node_stride), int(edge_stride)
+        full = self.node_stride * (self.node_stride + 1) // 2
+        self.envelope_blocks = int(envelope_blocks if envelope_blocks is not None else min(full, 64 * self.node_stride))
+        self.X = torch.eye(4, dtype=torch.float64, device=dev).reshape(1, 1, 16).repeat(batch, node_stride, 1).contiguous()
+        self.fixed = torch.zeros((batch, node_stride), dtype=torch.uint8, device=dev)
+        self.n_nodes = torch.zeros((batch,), dtype=torch.int32, device=dev)
+        self.src = torch.zeros((batch, edge_stride), dtype=torch.int32, device=dev)
+        self.dst = torch.zeros((batch, edge_stride), dtype=torch.int32, device=dev)
+        self.Z = torch.zeros((batch, edge_stride, 16), dtype=torch.float32, device=dev)
+        self.omega = torch.zeros((batch, edge_stride, 36), dtype=torch.float32, device=dev) if with_omega else None
+        self.n_edges = torch.zeros((batch,), dtype=torch.int32, device=dev)
+        self.workspace_bytes = int(_lib.load().prs_pose_graph_workspace_bytes(self.batch, self.node_stride, self.envelope_blocks))
+        self.workspace = torch.zeros((max(self.workspace_bytes // 8, 1),), dtype=torch.float64, device=dev)
+        self.result = torch.zeros((batch, C.sizeof(_lib.PoseGraphResult) // 8), dtype=torch.float64, device=dev)
+        self.append_status = torch.zeros((batch,), dtype=torch.int32, device=dev)
+        self.n_appended = torch.zeros((batch,), dtype=torch.int32, device=dev)
+
+    def upload(self, b, poses, fixed, edges):
+        """edges: (src [E], dst [E], Z [E, 4, 4], omega [E, 6, 6] or None = identity)"""
+        import torch
+        dev = self.X.device
+        X = _np(poses, np.float64, (-1, 16))
+        src, dst, Z = _np(edges[0], np.int32, (-1,)), _np(edges[1], np.int32, (-1,)), _np(edges[2], np.float32, (-1, 16))
+        omega = edges[3] if len(edges) > 3 else None
+        n, e = len(X), len(src)
+        if n:
+            self.X[b, :n] = torch.from_numpy(X).to(dev)
+            self.fixed[b, :n] = torch.from_numpy(_np(fixed, np.uint8, (-1,))).to(dev)
+        if e:
+            self.src[b, :e], self.dst[b, :e] = torch.from_numpy(src).to(dev), torch.from_numpy(dst).to(dev)
+            self.Z[b, :e] = torch.from_numpy(Z).to(dev)
+            if self.omega is not None:
+                om = np.tile(np.eye(6, dtype=np.float32).reshape(1, 36), (e, 1)) if omega is None else _np(omega, np.float32, (-1, 36))
+                self.omega[b, :e] = torch.from_numpy(om).to(dev)
+            elif omega is not None:
+                raise ValueError("this batch was built without omega (identity information only)")
+        self.n_nodes[b], self.n_edges[b] = n, e
+
+    def descriptor(self):
+        d = _lib.PoseGraphs()
+        d.batch, d.node_stride, d.edge_stride = self.batch, self.node_stride, self.edge_stride
+        d.X, d.fixed, d.n_nodes = self.X.data_ptr(), self.fixed.data_ptr(), self.n_nodes.data_ptr()
+        d.from_, d.to, d.Z, d.n_edges = self.src.data_ptr(), self.dst.data_ptr(), self.Z.data_ptr(), self.n_edges.data_ptr()
+        d.omega = self.omega.data_ptr() if self.omega is not None else None
+        d.workspace, d.workspace_bytes, d.result = self.workspace.data_ptr(), self.workspace_bytes, self.result.data_ptr()
+        return d
+
+    def result_of(self, b):
+        raw = self.result[b].cpu().numpy().copy()
+        return _graph_result_dict(_lib.PoseGraphResult.from_buffer_copy(raw.tobytes()))
+
+    def poses_of(self, b):
+        n = max(int(self.n_nodes[b].item()), 0)
+        return self.X[b, : min(n, self.node_stride)].cpu().numpy().reshape(-1, 4, 4).copy()
+
+    def edges_of(self, b):
+        """(src, dst, Z [E, 4, 4], omega [E, 6, 6] | None) as they stand on the device"""
+        e = int(self.n_edges[b].item())
+        om = self.omega[b, :e].cpu().numpy().reshape(-1, 6, 6).copy() if self.omega is not None else None
+        return self.src[b, :e].cpu().numpy().copy(), self.dst[b, :e].cpu().numpy().copy(), self.Z[b, :e].cpu().numpy().reshape(-1, 4, 4).copy(), om
+
+    def append_closures(self, ctx, detector, graph_of_query, node_of_query, node_of_map, params=None):
+        """enqueue the append of `detector`'s (a LoopDetectorBatch, after run()) accepted closures: query b goes to graph
+        graph_of_query[b] as an edge from node_of_query[b] to node_of_map[candidate], Z = the aligner's X.  The three maps are int32
+        device tensors (or arrays, uploaded here).  Per-graph status lands in self.append_status (asynchronous)."""
+        import torch
+        dev = self.X.device
+        as_dev = lambda a: a.to(dev, torch.int32).contiguous() if isinstance(a, torch.Tensor) else torch.from_numpy(_np(a, np.int32, (-1,))).to(dev)
+        self._closure_maps = (as_dev(graph_of_query), as_dev(node_of_query), as_dev(node_of_map))  # kept alive until the kernel has run
+        pairs = detector.closures.pairs
+        c = _lib.PoseGraphClosures()
+        c.n_queries, c.max_candidates, c.n_maps = detector.batch, detector.max_candidates, int(self._closure_maps[2].numel())
+        c.candidates, c.result, c.X = detector.queries.candidates.data_ptr(), pairs.result.data_ptr(), pairs.X.data_ptr()
+        c.graph_of_query, c.node_of_query, c.node_of_map = (t.data_ptr() for t in self._closure_maps)
+        c.status, c.n_appended = self.append_status.data_ptr(), self.n_appended.data_ptr()
+        p = params if params is not None else pose_graph_params(dict(damping=0.0, max_iterations=0, epsilon=0.0))
+        d = self.descriptor()
+        rc = _lib.load().prs_pose_graph_append_closures(ctx._h, C.byref(p), C.byref(d), C.byref(c))
+        _check(ctx, rc, "prs_pose_graph_append_closures")
+        return rc
+
+
+def pose_graph_optimize_batch(ctx, params, graphs):
+    """enqueue the optimiser for every graph of the batch on the context stream (asynchronous, one launch)"""
+    d = graphs.descriptor()
+    rc = _lib.load().prs_pose_graph_optimize_batch(ctx._h, C.byref(params), C.byref(d))
+    _check(ctx, rc, "prs_pose_graph_optimize_batch")
+    return rc
+
+
 # ---- landmark estimators + projective mergers (mapping/mergers, mapping/landmarks) ----
 EST_WEIGHTED_MEAN, EST_EKF, EST_SMOOTHER = 0, 1, 2
 MERGER_STEREO_TRIANGULATION, MERGER_STEREO_EKF, MERGER_DEPTH_EKF = 0, 1, 2

@@ -92,6 +92,17 @@ def conf_place(names=("kitti", "euroc", "icl", "tum", "malaga")):
         f.write("\n")
 
 
+def conf_graph(names=("kitti", "euroc", "icl", "tum", "malaga")):
+    """{config: graph group} as formats.graph_params reads it from the shipped .conf files (the global solver of the pose graph)"""
+    import json
+    sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+    from srrg2_proslam_amd import formats
+    out = {n: formats.graph_params(formats.read_conf(os.path.join(REF, "configurations", n + ".conf"))) for n in names}
+    with open(os.path.join(OUT, "ref_conf_graph.json"), "w") as f:
+        json.dump(out, f, indent=1, sort_keys=True)
+        f.write("\n")
+
+
 def main():
     k = os.path.join(DATA, "kitti")
     np.savez_compressed(
@@ -120,6 +131,7 @@ def main():
     conf_hot_path()
     conf_loop()
     conf_place()
+    conf_graph()
     for f in sorted(os.listdir(OUT)):
         if f.startswith("ref_"):
             print(f, os.path.getsize(os.path.join(OUT, f)) // 1024, "KiB")
