@@ -113,7 +113,8 @@ PRS_API int prs_version(void);
  * new structs and new entry points only, nothing a 104 client passes changed; so did the loop detector's place database:
  * prs_place_db, prs_place_params, prs_place_queries, prs_place_pairs and the prs_place_* entry points; and the pose-graph optimiser:
  * prs_pose_graph_params, prs_pose_graph_result, prs_pose_graphs, prs_pose_graph_closures, the prs_pose_graph_* entry points and the
- * status PRS_ERR_NOT_POSITIVE_DEFINITE).  Callers memset() parameter structs before
+ * status PRS_ERR_NOT_POSITIVE_DEFINITE; and its Levenberg-Marquardt form: prs_pose_graph_lm_params, prs_pose_graph_lm_result and the
+ * prs_pose_graph_lm_* / prs_pose_graph_optimize_lm* entry points).  Callers memset() parameter structs before
  * filling them, so that fields they do not know select the shipped defaults (all zero). */
 #define PRS_ABI_VERSION 104
 PRS_API int prs_abi_check(int32_t header_version, uint64_t sizeof_stereo_params, uint64_t sizeof_pcf_params, uint64_t sizeof_aligner_params,
@@ -1325,6 +1326,88 @@ PRS_API int prs_pose_graph_append_closures(prs_context* ctx, const prs_pose_grap
 PRS_API int prs_pose_graph_optimize(prs_context* ctx, const prs_pose_graph_params* params, int32_t n_nodes, double* X16,
                                     const uint8_t* fixed, int32_t n_edges, const int32_t* from, const int32_t* to, const float* Z16,
                                     const float* omega36, prs_pose_graph_result* result);
+
+/* ------------------------------------------------------------------------------------------------
+ * Levenberg-Marquardt form of the optimiser above: what icl.conf:665-685 and tum.conf:174-194 wire into their global_solver
+ * (IterationAlgorithmLM: lm_iterations_max 100, step_high 0.666667, step_low 0.333333, tau 1e-05, user_lambda_init 0,
+ * variable_damping 1).  IterationAlgorithmLM lives in srrg2_solver, not in the tree: BUILD-DEFINED like the rest of this section.
+ * The reading is Nielsen's gain-ratio schedule as g2o implements it, which is what the .conf comments describe ("upper / lower
+ * clamp for lambda if things go well", "tau: scale factor for the lambda computed by the system", "variable_damping: lambda *
+ * diag(H), otherwise lambda * I").  Factor, Jacobians, sums, fixed nodes, solve, pose update and the per-graph checks are those of
+ * prs_pose_graph_optimize_batch (the same device functions); the Gauss-Newton entry points are not touched by any of this.
+ *   state        lambda and nu, double, per graph.  The float parameters are widened once.
+ *   round        it = 0 .. max_iterations - 1:
+ *                1 linearise at X: chi[it], H, b.
+ *                2 the stop test of the Gauss-Newton loop, unchanged (chi[] holds accepted states only).
+ *                3 it == 0: nu = 2; lambda = user_lambda_init if that is > 0, else tau * max h_rr over the scalar rows of free
+ *                  nodes (a maximum has no order).  In the second case a maximum that is not > 0, or a h_rr of a free node that is
+ *                  not finite, ends the graph with PRS_ERR_NOT_POSITIVE_DEFINITE, poses untouched, no trial.
+ *                4 keep d_r = h_rr (undamped), g_r = -b_r and X0 = X (workspace, 28 doubles per node behind the envelope).
+ *                5 trials t = 1 .. lm_iterations_max:
+ *                  a damp: h_rr + lambda * h_rr (variable_damping != 0) or h_rr + lambda: the two damping forms above with lambda
+ *                    for `damping`; fixed nodes the identity; right-hand side -b.  For t > 1 the undamped system is linearised
+ *                    again at X0 (the same bits; no second envelope is kept).
+ *                  b solve as above.  A pivot <= 0 or not finite: the trial is rejected (e), X is untouched.
+ *                  c X <- X0 tnq2t(dx) for free nodes; chi_t by the error-only pass.
+ *                  d scale = (sum over the scalar rows r of free nodes of dx_r * ((lambda * D_r) * dx_r + g_r)) + 1e-3, D_r = d_r
+ *                    (variable_damping != 0) or 1: separate multiplies and adds, ONE chain over r ascending from +0, the 1e-3 added
+ *                    last.  rho = (chi[it] - chi_t) / scale, one IEEE division.  (The sum is the decrease of the linearised chi,
+ *                    without a factor 1/2; the 1e-3 is g2o's guard against 0 / 0.)
+ *                  e accept iff rho > 0 and chi_t is finite: u = 2 * rho - 1, alpha = 1 - (u * u) * u, lambda <- lambda *
+ *                    max(step_low, min(alpha, step_high)), nu <- 2, the round ends.  Otherwise X <- X0, lambda <- lambda * nu,
+ *                    nu <- 2 * nu, and a lambda that is no longer finite ends the trials.
+ *                6 a round with an accepted trial is an iteration.  A round without one ends the run with the poses X0:
+ *                  PRS_ERR_NOT_POSITIVE_DEFINITE if its last trial failed on a pivot, else PRS_OK with stalled = 1.
+ *                After the last round one error-only pass writes chi_final.
+ *   consequences a graph whose optimum has zero residual (a tree) reaches chi = 0, which the stop test does not catch
+ *                (0 - 0 < epsilon * 0 is false); every later trial is rejected (rho = 0) until lambda overflows after about 45
+ *                trials: stalled = 1, PRS_OK, poses restored -- harmless.  A free node that no edge reaches has h_rr = 0: with
+ *                variable_damping != 0 every trial fails on its pivot (PRS_ERR_NOT_POSITIVE_DEFINITE after lm_iterations_max
+ *                trials or when lambda overflows); with variable_damping == 0 the graph solves.
+ * Same inputs give the same bits for every batch size, position in the batch and entry point.  Per-graph checks and limits as
+ * above, with the envelope's room = the graph's share of the workspace less 28 doubles per node of node_stride (a workspace sized
+ * by prs_pose_graph_workspace_bytes is too small: PRS_ERR_CAPACITY).  At the call: lm_iterations_max < 1 or step_low > step_high,
+ * a parameter that is not finite, tau < 0 or max_iterations outside [0, 32] PRS_ERR_RANGE.
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct {
+  float user_lambda_init;    /* > 0: the first lambda; otherwise tau * max h_rr (0 shipped) */
+  float tau;                 /* 1e-05 */
+  float step_high;           /* 0.666667 */
+  float step_low;            /* 0.333333 */
+  int32_t lm_iterations_max; /* trials per round (100), >= 1 */
+  int32_t variable_damping;  /* != 0: lambda * diag(H) (shipped), 0: lambda * I */
+  int32_t max_iterations;    /* Solver max_iterations (10): rounds, <= PRS_POSE_GRAPH_MAX_ITERATIONS */
+  float epsilon;             /* SimpleTerminationCriteria epsilon (0.001); <= 0: no criterion */
+} prs_pose_graph_lm_params;
+
+typedef struct {
+  double chi[PRS_POSE_GRAPH_MAX_ITERATIONS];     /* chi[it] of every round's linearisation, 0 past `linearizations` */
+  double chi_final;                              /* at the poses returned */
+  double lambda[PRS_POSE_GRAPH_MAX_ITERATIONS];  /* the lambda the round's last trial solved with; 0 for rounds without a trial */
+  int32_t trials[PRS_POSE_GRAPH_MAX_ITERATIONS]; /* trials of every round */
+  int32_t linearizations;                        /* entries of chi[] (linearisations repeated for t > 1 are not counted) */
+  int32_t iterations;                            /* rounds with an accepted trial */
+  int32_t envelope_blocks;
+  int32_t status;                                /* PRS_OK, PRS_WARN_EMPTY_INPUT or a PRS_ERR_* code */
+  int32_t trials_total;
+  int32_t rejected_not_positive_definite;        /* trials rejected at a pivot */
+  int32_t stalled;                               /* 1: the last round accepted no trial and did not fail on a pivot */
+  int32_t reserved;
+} prs_pose_graph_lm_result;
+
+/* bytes of workspace for the LM entry: the envelopes as above and 28 doubles per node of node_stride per graph */
+PRS_API uint64_t prs_pose_graph_lm_workspace_bytes(int32_t batch, int32_t node_stride, int64_t envelope_blocks_per_graph);
+/* sizeof prs_pose_graph_lm_params, prs_pose_graph_lm_result as the library was compiled (bindings check) */
+PRS_API void prs_pose_graph_lm_struct_sizes(uint64_t* sizes2);
+/* device pointers, asynchronous on the context's stream: one kernel launch, no allocation and no synchronisation (graph-capturable).
+ * `graphs` as for prs_pose_graph_optimize_batch with a workspace of prs_pose_graph_lm_workspace_bytes; graphs->result is ignored and
+ * may be NULL: results go to result [batch] (device, 8-byte aligned). */
+PRS_API int prs_pose_graph_optimize_lm_batch(prs_context* ctx, const prs_pose_graph_lm_params* params, const prs_pose_graphs* graphs,
+                                             prs_pose_graph_lm_result* result);
+/* host pointers, one graph: prs_pose_graph_optimize with the LM loop */
+PRS_API int prs_pose_graph_optimize_lm(prs_context* ctx, const prs_pose_graph_lm_params* params, int32_t n_nodes, double* X16,
+                                       const uint8_t* fixed, int32_t n_edges, const int32_t* from, const int32_t* to, const float* Z16,
+                                       const float* omega36, prs_pose_graph_lm_result* result);
 
 #ifdef __cplusplus
 }

@@ -1233,7 +1233,8 @@ protected:
 
 // ------------------------------------------------------------------------------------------------
 // The global solver of the pose graph: Solver + IterationAlgorithmGN + SimpleTerminationCriteria as MultiGraphSLAM3D's
-// `global_solver` uses them (kitti.conf:895-936), over prs_pose_graph_optimize.  A graph is handed over as plain arrays: variable i is
+// `global_solver` uses them (kitti.conf:895-936), over prs_pose_graph_optimize; with param_algorithm = LevenbergMarquardt the
+// IterationAlgorithmLM of icl.conf:665-685 / tum.conf:174-194, over prs_pose_graph_optimize_lm.  A graph is handed over as plain arrays: variable i is
 // the i-th pose (VariableSE3QuaternionRight, estimate as a row-major 4x4 double), a factor is (from, to, measurement, information)
 // (SE3PosePoseGeodesicErrorFactor).  setGraph() copies, compute() optimises, poses() / pose(i) give the estimates back.
 class SolverPoseGraphHIP {
@@ -1242,6 +1243,14 @@ public:
   PropertyFloat param_damping{1e-6f};    // IterationAlgorithmGN damping
   PropertyFloat param_epsilon{1e-3f};    // SimpleTerminationCriteria epsilon
   PropertyInt param_damping_form{PRS_DAMPING_DIAG};
+  enum Algorithm { GaussNewton = 0, LevenbergMarquardt = 1 };
+  PropertyInt param_algorithm{GaussNewton};      // the class of the Solver's `algorithm`: IterationAlgorithmGN / IterationAlgorithmLM
+  PropertyInt param_lm_iterations_max{100};      // IterationAlgorithmLM, used by LevenbergMarquardt only
+  PropertyFloat param_step_high{0.666667f};
+  PropertyFloat param_step_low{0.333333f};
+  PropertyFloat param_tau{1e-5f};
+  PropertyFloat param_user_lambda_init{0.f};
+  PropertyInt param_variable_damping{1};
 
   explicit SolverPoseGraphHIP(ContextPtr ctx) : _ctx(std::move(ctx)) {}
 
@@ -1276,6 +1285,11 @@ public:
 
   void compute() {
     if (!_set) throw std::runtime_error("SolverPoseGraphHIP::compute|ERROR: graph not set");
+    if (param_algorithm.value() == LevenbergMarquardt) {
+      computeLM();
+      return;
+    }
+    if (param_algorithm.value() != GaussNewton) throw std::runtime_error("SolverPoseGraphHIP::compute|ERROR: unknown algorithm");
     prs_pose_graph_params p;
     std::memset(&p, 0, sizeof(p));
     p.damping             = param_damping.value();
@@ -1283,6 +1297,7 @@ public:
     p.max_iterations      = param_max_iterations.value();
     p.epsilon             = param_epsilon.value();
     p.closure_information = 1.0f;
+    _ran_lm               = false;
     const int rc = prs_pose_graph_optimize(_ctx->get(), &p, (int32_t) _fixed.size(), _poses.data(), _fixed.data(), (int32_t) _from.size(),
                                            _from.data(), _to.data(), _z.data(), _omega.empty() ? nullptr : _omega.data(), &_result);
     if (rc < 0) throw std::runtime_error(std::string("SolverPoseGraphHIP::compute|ERROR: ") + prs_last_error(_ctx->get()));
@@ -1292,11 +1307,31 @@ public:
   size_t size() const { return _fixed.size(); }
   const std::vector<double>& poses() const { return _poses; }
   const double* pose(size_t i) const { return _poses.data() + 16 * i; }
-  int iterations() const { return _result.iterations; }
-  double chi2() const { return _result.chi_final; }
-  const prs_pose_graph_result& result() const { return _result; }
+  // of the last compute(), whichever algorithm it ran
+  int iterations() const { return _ran_lm ? _lm_result.iterations : _result.iterations; }
+  double chi2() const { return _ran_lm ? _lm_result.chi_final : _result.chi_final; }
+  const prs_pose_graph_result& result() const { return _result; }         // GaussNewton runs
+  const prs_pose_graph_lm_result& resultLM() const { return _lm_result; }  // LevenbergMarquardt runs
 
 protected:
+  void computeLM() {
+    prs_pose_graph_lm_params p;
+    std::memset(&p, 0, sizeof(p));
+    p.user_lambda_init  = param_user_lambda_init.value();
+    p.tau               = param_tau.value();
+    p.step_high         = param_step_high.value();
+    p.step_low          = param_step_low.value();
+    p.lm_iterations_max = param_lm_iterations_max.value();
+    p.variable_damping  = param_variable_damping.value();
+    p.max_iterations    = param_max_iterations.value();
+    p.epsilon           = param_epsilon.value();
+    _ran_lm             = true;
+    const int rc = prs_pose_graph_optimize_lm(_ctx->get(), &p, (int32_t) _fixed.size(), _poses.data(), _fixed.data(), (int32_t) _from.size(),
+                                              _from.data(), _to.data(), _z.data(), _omega.empty() ? nullptr : _omega.data(), &_lm_result);
+    if (rc < 0) throw std::runtime_error(std::string("SolverPoseGraphHIP::compute|ERROR: ") + prs_last_error(_ctx->get()));
+    warn("SolverPoseGraphHIP::compute", rc);
+  }
+
   ContextPtr _ctx;
   bool _set = false;
   std::vector<double> _poses;
@@ -1304,6 +1339,8 @@ protected:
   std::vector<int32_t> _from, _to;
   std::vector<float> _z, _omega;
   prs_pose_graph_result _result = {};
+  prs_pose_graph_lm_result _lm_result = {};
+  bool _ran_lm = false;
 };
 
 }  // namespace proslam_hip

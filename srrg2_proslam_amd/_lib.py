@@ -358,6 +358,20 @@ class PoseGraphResult(C.Structure):
                 ("iterations", C.c_int32), ("envelope_blocks", C.c_int32), ("status", C.c_int32)]
 
 
+class PoseGraphLmParams(C.Structure):
+    """prs_pose_graph_lm_params"""
+    _fields_ = [("user_lambda_init", C.c_float), ("tau", C.c_float), ("step_high", C.c_float), ("step_low", C.c_float),
+                ("lm_iterations_max", C.c_int32), ("variable_damping", C.c_int32), ("max_iterations", C.c_int32), ("epsilon", C.c_float)]
+
+
+class PoseGraphLmResult(C.Structure):
+    """prs_pose_graph_lm_result"""
+    _fields_ = [("chi", C.c_double * POSE_GRAPH_MAX_ITERATIONS), ("chi_final", C.c_double), ("lambda_", C.c_double * POSE_GRAPH_MAX_ITERATIONS),
+                ("trials", C.c_int32 * POSE_GRAPH_MAX_ITERATIONS), ("linearizations", C.c_int32), ("iterations", C.c_int32),
+                ("envelope_blocks", C.c_int32), ("status", C.c_int32), ("trials_total", C.c_int32),
+                ("rejected_not_positive_definite", C.c_int32), ("stalled", C.c_int32), ("reserved", C.c_int32)]
+
+
 class PoseGraphs(C.Structure):
     """prs_pose_graphs (device pointers)"""
     _fields_ = [("batch", C.c_int32), ("node_stride", C.c_int32), ("edge_stride", C.c_int32), ("reserved", C.c_int32),
@@ -447,6 +461,11 @@ SYMBOLS = {
     "prs_pose_graph_append_closures": (C.c_int, [_vp, C.POINTER(PoseGraphParams), C.POINTER(PoseGraphs), C.POINTER(PoseGraphClosures)]),
     "prs_pose_graph_optimize": (C.c_int, [_vp, C.POINTER(PoseGraphParams), C.c_int32, _vp, _vp, C.c_int32, _vp, _vp, _vp, _vp,
                                           C.POINTER(PoseGraphResult)]),
+    "prs_pose_graph_lm_workspace_bytes": (C.c_uint64, [C.c_int32, C.c_int32, C.c_int64]),
+    "prs_pose_graph_lm_struct_sizes": (None, [C.POINTER(C.c_uint64)]),
+    "prs_pose_graph_optimize_lm_batch": (C.c_int, [_vp, C.POINTER(PoseGraphLmParams), C.POINTER(PoseGraphs), _vp]),
+    "prs_pose_graph_optimize_lm": (C.c_int, [_vp, C.POINTER(PoseGraphLmParams), C.c_int32, _vp, _vp, C.c_int32, _vp, _vp, _vp, _vp,
+                                             C.POINTER(PoseGraphLmResult)]),
     "prs_pose_compose_batch": (C.c_int, [_vp, C.c_int32, _vp, _vp, _vp]),
     "prs_motion_predict_batch": (C.c_int, [_vp, C.c_int32, _vp, _vp, _vp]),
     "prs_merge_batch_run": (C.c_int, [_vp, C.POINTER(MergerParams), C.POINTER(MergeBatch)]),

@@ -36,14 +36,25 @@ def _place(max_distance, minimum_age, min_inliers):
             "maximum_distance_for_merge": 0}
 
 
-def _graph(algorithm, damping):
+def _graph(algorithm, damping, lm=None):
     """the global solver of the pose graph (include/proslam_hip.h prs_pose_graph_*): MultiGraphSLAM3D.global_solver, a Solver with
     max_iterations [10] and SimpleTerminationCriteria epsilon 0.001 in every shipped file; closure_validator is null in all of them.
     kitti, euroc and malaga wire IterationAlgorithmGN with damping 1e-06 and SparseBlockLinearSolverCholeskyCholmod; icl and tum wire
-    IterationAlgorithmLM (user_lambda_init 0: its own lambda schedule) and SparseBlockLinearSolverCholeskyCSparse.  SUBSTITUTION:
-    this build has the damped Gauss-Newton only (a direct float64 LDL^T on the row envelope stands in for both linear solvers); for
-    the LM files `damping` is the Gauss-Newton files' 1e-06, not a value of theirs."""
-    return {"algorithm": algorithm, "damping": damping, "max_iterations": 10, "epsilon": 0.001}
+    IterationAlgorithmLM, whose six values are the `lm` sub-dict (prs_pose_graph_lm_params; ops.pose_graph_algorithm picks the entry
+    from `algorithm`), and SparseBlockLinearSolverCholeskyCSparse.  `damping` of the LM files is the Gauss-Newton files' 1e-06, not
+    a value of theirs: it serves a caller who runs the Gauss-Newton entry on them anyway.  SUBSTITUTION: a direct float64 LDL^T on
+    the row envelope stands in for both sparse linear solvers."""
+    out = {"algorithm": algorithm, "damping": damping, "max_iterations": 10, "epsilon": 0.001}
+    if lm is not None:
+        out["lm"] = lm
+    return out
+
+
+# icl.conf:665-685 and tum.conf:174-194 (IterationAlgorithmLM), the same values: lm_iterations_max :669 / :178, step_high :672 / :181,
+# step_low :675 / :184, tau :678 / :187, user_lambda_init :681 / :190, variable_damping :684 / :193
+def _lm():
+    return {"lm_iterations_max": 100, "step_high": 0.666667, "step_low": 0.333333, "tau": 1e-05, "user_lambda_init": 0,
+            "variable_damping": 1}
 
 
 KITTI = {
@@ -133,7 +144,7 @@ ICL = {
     # icl.conf:1-29 (loop_aligner), :600-628 (slice + RobustifierClamp), :153-158 (damping), :197-237 (detector), :687-705 (relocalizer)
     "loop": _loop("clamp", 1.0, 10, 0, 35.0, (50, 0.5, 0.1), (100, 0.5, 1000.0)),
     "place": _place(35.0, 1, 50),  # icl.conf:197-240
-    "graph": _graph("IterationAlgorithmLM", 1e-06),  # icl.conf:797-807 (MultiGraphSLAM3D -> global_solver), LM :665-681
+    "graph": _graph("IterationAlgorithmLM", 1e-06, _lm()),  # icl.conf:797-807 (MultiGraphSLAM3D -> global_solver), LM :665-685
     "depth": {"min": 0.5, "max": 6.0},
     # RawDataPreprocessorMonocularDepth (icl.conf:642-650) and its IntensityFeatureExtractorBinned3D (icl.conf:745-770)
     "rgbd": {"depth_scaling_factor_to_meters": 0.001, "detector_threshold": 5, "enable_non_maximum_suppression": 1,
@@ -163,7 +174,7 @@ TUM = {
     # tum.conf: MultiLoopDetectorHBST3D.relocalize_aligner -> AlignerSliceProcessor3D + RobustifierClamp, MultiRelocalizer3D
     "loop": _loop("clamp", 0.25, 10, 0, 25.0, (40, 0.5, 0.05), (40, 0.5, 100.0)),
     "place": _place(25.0, 1, 40),  # tum.conf: MultiLoopDetectorHBST3D
-    "graph": _graph("IterationAlgorithmLM", 1e-06),  # tum.conf:453-463 (MultiGraphSLAM3D -> global_solver), LM :174-190
+    "graph": _graph("IterationAlgorithmLM", 1e-06, _lm()),  # tum.conf:453-463 (MultiGraphSLAM3D -> global_solver), LM :174-194
     "depth": {"min": 0.5, "max": 6.0},
     # RawDataPreprocessorMonocularDepth (tum.conf:633-640) and its IntensityFeatureExtractorBinned3D (tum.conf:858-883)
     "rgbd": {"depth_scaling_factor_to_meters": 0.001, "detector_threshold": 5, "enable_non_maximum_suppression": 1,

@@ -21,11 +21,18 @@
 //                       + 6 + 6 sums of an edge spread over the lanes; every element of the factor is one chain in ascending column
 //                       (right-looking inside the block row: step m applies subtraction m to every element of the six rows that
 //                       has one, which is the order of the left-looking definition).
+//   pose_graph_lm_kernel  the Levenberg-Marquardt form (prs_pose_graph_optimize_lm_batch; IterationAlgorithmLM of icl.conf:665-685 and
+//                       tum.conf:174-194, BUILD-DEFINED like the rest: Nielsen's gain-ratio schedule, stated in the header).  The same
+//                       mapping and the same device functions: a round is a Gauss-Newton iteration inside a loop of trials that
+//                       damp with lambda, solve, try the step from X0 and accept or reject it by the gain ratio.  d = diag(H), g = -b
+//                       and X0 of the round (28 doubles per node) live in the workspace behind the envelope -- LDS is full at
+//                       node_stride 1024 -- and a trial after a rejection linearises again at X0 instead of keeping a second envelope.
 //   append_closures_kernel  one wave per graph scans the detector's slots in ascending order and appends the accepted ones by a
 //                       prefix count (ballot + popcount): the order is the slot order, whatever the hardware does.
 #include <string.h>
 
 #include <cmath>
+#include <string>
 #include <vector>
 
 #include "prs_device.h"
@@ -417,21 +424,18 @@ __device__ __forceinline__ bool factor_block_row(const Graph& G, const Lds& s, d
   return true;
 }
 
-__global__ __launch_bounds__(kThreads) void pose_graph_kernel(const PoseGraphArgs args) {
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  const prs_pose_graphs& B      = args.g;
-  const prs_pose_graph_params& P = args.p;
-  const int lane = threadIdx.x, g = blockIdx.x;
-  const int N = B.node_stride;
-  Lds s;
+__device__ __forceinline__ void carve_lds(Lds& s, unsigned char* smem, const int N, const int rb_cols) {
   s.invd  = reinterpret_cast<double*>(smem);
   s.y     = s.invd + 6 * (size_t) N;
   s.row   = s.y + 6 * (size_t) N;
-  s.edge  = s.row + 6 * (size_t) args.rb_cols;
+  s.edge  = s.row + 6 * (size_t) rb_cols;
   s.first = reinterpret_cast<int*>(s.edge + kEdgeScratch);
   s.off   = s.first + N;
+}
 
-  Graph G;
+// graph g of the batch; its envelope starts at `env`
+__device__ __forceinline__ void graph_of(Graph& G, const prs_pose_graphs& B, const int g, double* env) {
+  const int N = B.node_stride;
   G.n       = B.n_nodes[g];
   G.n_edges = B.n_edges[g];
   G.X       = B.X + (size_t) g * N * 16;
@@ -440,13 +444,17 @@ __global__ __launch_bounds__(kThreads) void pose_graph_kernel(const PoseGraphArg
   G.to      = B.to + (size_t) g * B.edge_stride;
   G.Z       = B.Z + (size_t) g * B.edge_stride * 16;
   G.omega   = B.omega ? B.omega + (size_t) g * B.edge_stride * 36 : nullptr;
-  G.env     = reinterpret_cast<double*>(B.workspace) + (size_t) g * (size_t) args.capacity_blocks * 36;
-  const int n = G.n, E = G.n_edges;
-  prs_pose_graph_result* res = B.result + g;
+  G.env     = env;
+}
 
-  // ---- the checks of the header's table, then first() and the envelope ----
-  int status = PRS_OK, blocks = 0;
-  bool any_free = false;
+// The checks of the header's table, then first() and the envelope's offsets -> the graph's status; `blocks` and `any_free` are set
+// where the status is PRS_OK (blocks also where the envelope does not fit).
+__device__ __forceinline__ int check_graph(const Graph& G, const Lds& s, const prs_pose_graphs& B, const long long capacity_blocks,
+                                           const int lane, int& blocks, bool& any_free) {
+  const int n = G.n, E = G.n_edges, N = B.node_stride;
+  int status = PRS_OK;
+  blocks   = 0;
+  any_free = false;
   if (n < 0 || E < 0) {
     status = PRS_ERR_RANGE;
   } else if (n > N || E > B.edge_stride) {
@@ -498,25 +506,129 @@ __global__ __launch_bounds__(kThreads) void pose_graph_kernel(const PoseGraphArg
       }
       blocks = base;
       __syncthreads();
-      if ((long long) blocks > args.capacity_blocks) {
+      if ((long long) blocks > capacity_blocks) {
         status = PRS_ERR_CAPACITY;
       }
     }
   }
+  return status;
+}
+
+// H <- 0, b <- 0
+__device__ __forceinline__ void clear_system(const Graph& G, const Lds& s, const int blocks, const int lane) {
+  for (size_t i = lane; i < (size_t) blocks * 36; i += kThreads) {
+    G.env[i] = 0.0;
+  }
+  for (int i = lane; i < 6 * G.n; i += kThreads) {
+    s.y[i] = 0.0;
+  }
+  __syncthreads();
+}
+
+// fixed nodes, damping, right-hand side -b
+__device__ __forceinline__ void damp_system(const Graph& G, const Lds& s, const double lambda, const int damping_form, const int lane) {
+  for (int r = lane; r < 6 * G.n; r += kThreads) {
+    const int j = r / 6, a = r - 6 * j;
+    double* d = G.env + row_base(s, j) + (size_t) a * row_width(s, j) + 6 * (j - s.first[j]) + a;
+    if (G.fixed[j]) {
+      *d = 1.0;
+    } else if (damping_form == PRS_DAMPING_IDENTITY) {
+      *d = *d + lambda;
+    } else {
+      *d = *d + lambda * *d;
+    }
+    s.y[r] = -s.y[r];
+  }
+  __syncthreads();
+}
+
+// Factorisation and both substitutions: dx is left in s.y.  Returns false at a pivot that is not positive and finite.
+__device__ __forceinline__ bool solve_system(const Graph& G, const Lds& s, const int rb_cols, const int lane) {
+  const int n = G.n;
+  bool ok = true;
+  for (int j = 0; j < n && ok; ++j) {
+    const int W    = row_width(s, j);
+    double* in_env = G.env + row_base(s, j);
+    if (W <= rb_cols) {
+      for (int i = lane; i < 6 * W; i += kThreads) {
+        s.row[i] = in_env[i];
+      }
+      __syncthreads();
+      ok = factor_block_row(G, s, s.row, j, lane);
+      for (int i = lane; i < 6 * W; i += kThreads) {
+        in_env[i] = s.row[i];
+      }
+      __syncthreads();
+    } else {
+      ok = factor_block_row(G, s, in_env, j, lane);
+    }
+  }
+  if (!ok) {
+    return false;
+  }
+  // z = y / d, then column-oriented back substitution: dx_r = z_r is final, z_m -= l_rm dx_r for every m of row r
+  for (int r = lane; r < 6 * n; r += kThreads) {
+    s.y[r] = s.y[r] * s.invd[r];
+  }
+  __syncthreads();
+  for (int r = 6 * n - 1; r > 0; --r) {
+    const int j = r / 6, a = r - 6 * j, c0 = 6 * s.first[j];
+    const double dxr  = s.y[r];
+    const double* urow = G.env + row_base(s, j) + (size_t) a * row_width(s, j);
+    for (int m = c0 + lane; m < r; m += kThreads) {
+      s.y[m] = s.y[m] - (urow[m - c0] * s.invd[m]) * dxr;
+    }
+    __syncthreads();
+  }
+  return true;
+}
+
+// X <- X0 tnq2t(dx) for every free node (X0 [n][16]; Gauss-Newton passes the poses themselves)
+__device__ __forceinline__ void update_poses(const Graph& G, const Lds& s, const double* X0, const int lane) {
+  for (int i = lane; i < G.n; i += kThreads) {
+    if (G.fixed[i] == 0) {
+      double dx[6], D[12], X[12], Xn[12];
+#pragma unroll
+      for (int q = 0; q < 6; ++q) {
+        dx[q] = s.y[6 * i + q];
+      }
+#pragma unroll
+      for (int q = 0; q < 12; ++q) {
+        X[q] = X0[16 * (size_t) i + q];
+      }
+      tnq2t_d(dx, D);
+      mul_d(X, D, Xn);
+#pragma unroll
+      for (int q = 0; q < 12; ++q) {
+        G.X[16 * (size_t) i + q] = Xn[q];
+      }
+    }
+  }
+  __syncthreads();
+}
+
+__global__ __launch_bounds__(kThreads) void pose_graph_kernel(const PoseGraphArgs args) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  const prs_pose_graphs& B      = args.g;
+  const prs_pose_graph_params& P = args.p;
+  const int lane = threadIdx.x, g = blockIdx.x;
+  Lds s;
+  carve_lds(s, smem, B.node_stride, args.rb_cols);
+  Graph G;
+  graph_of(G, B, g, reinterpret_cast<double*>(B.workspace) + (size_t) g * (size_t) args.capacity_blocks * 36);
+  const int E = G.n_edges;
+  prs_pose_graph_result* res = B.result + g;
+
+  int blocks = 0;
+  bool any_free = false;
+  int status = check_graph(G, s, B, args.capacity_blocks, lane, blocks, any_free);
 
   int iterations = 0, n_chi = 0;
   double chi_prev = 0.0, chi_final = 0.0;
   if (status == PRS_OK && E > 0 && any_free) {
     const double lambda = (double) P.damping, eps = (double) P.epsilon;
     for (int it = 0; it < P.max_iterations; ++it) {
-      // H <- 0, b <- 0
-      for (size_t i = lane; i < (size_t) blocks * 36; i += kThreads) {
-        G.env[i] = 0.0;
-      }
-      for (int i = lane; i < 6 * n; i += kThreads) {
-        s.y[i] = 0.0;
-      }
-      __syncthreads();
+      clear_system(G, s, blocks, lane);
       const double chi = linearize<true>(G, s, lane);
       if (lane == 0) {
         res->chi[it] = chi;
@@ -526,77 +638,12 @@ __global__ __launch_bounds__(kThreads) void pose_graph_kernel(const PoseGraphArg
         break;
       }
       chi_prev = chi;
-      // fixed nodes, damping, right-hand side -b
-      for (int r = lane; r < 6 * n; r += kThreads) {
-        const int j = r / 6, a = r - 6 * j;
-        double* d = G.env + row_base(s, j) + (size_t) a * row_width(s, j) + 6 * (j - s.first[j]) + a;
-        if (G.fixed[j]) {
-          *d = 1.0;
-        } else if (P.damping_form == PRS_DAMPING_IDENTITY) {
-          *d = *d + lambda;
-        } else {
-          *d = *d + lambda * *d;
-        }
-        s.y[r] = -s.y[r];
-      }
-      __syncthreads();
-      bool ok = true;
-      for (int j = 0; j < n && ok; ++j) {
-        const int W    = row_width(s, j);
-        double* in_env = G.env + row_base(s, j);
-        if (W <= args.rb_cols) {
-          for (int i = lane; i < 6 * W; i += kThreads) {
-            s.row[i] = in_env[i];
-          }
-          __syncthreads();
-          ok = factor_block_row(G, s, s.row, j, lane);
-          for (int i = lane; i < 6 * W; i += kThreads) {
-            in_env[i] = s.row[i];
-          }
-          __syncthreads();
-        } else {
-          ok = factor_block_row(G, s, in_env, j, lane);
-        }
-      }
-      if (!ok) {
+      damp_system(G, s, lambda, P.damping_form, lane);
+      if (!solve_system(G, s, args.rb_cols, lane)) {
         status = PRS_ERR_NOT_POSITIVE_DEFINITE;
         break;
       }
-      // z = y / d, then column-oriented back substitution: dx_r = z_r is final, z_m -= l_rm dx_r for every m of row r
-      for (int r = lane; r < 6 * n; r += kThreads) {
-        s.y[r] = s.y[r] * s.invd[r];
-      }
-      __syncthreads();
-      for (int r = 6 * n - 1; r > 0; --r) {
-        const int j = r / 6, a = r - 6 * j, c0 = 6 * s.first[j];
-        const double dxr  = s.y[r];
-        const double* urow = G.env + row_base(s, j) + (size_t) a * row_width(s, j);
-        for (int m = c0 + lane; m < r; m += kThreads) {
-          s.y[m] = s.y[m] - (urow[m - c0] * s.invd[m]) * dxr;
-        }
-        __syncthreads();
-      }
-      // X <- X tnq2t(dx) for every free node
-      for (int i = lane; i < n; i += kThreads) {
-        if (G.fixed[i] == 0) {
-          double dx[6], D[12], X[12], Xn[12];
-#pragma unroll
-          for (int q = 0; q < 6; ++q) {
-            dx[q] = s.y[6 * i + q];
-          }
-#pragma unroll
-          for (int q = 0; q < 12; ++q) {
-            X[q] = G.X[16 * (size_t) i + q];
-          }
-          tnq2t_d(dx, D);
-          mul_d(X, D, Xn);
-#pragma unroll
-          for (int q = 0; q < 12; ++q) {
-            G.X[16 * (size_t) i + q] = Xn[q];
-          }
-        }
-      }
-      __syncthreads();
+      update_poses(G, s, G.X, lane);
       iterations = it + 1;
     }
   }
@@ -612,6 +659,184 @@ __global__ __launch_bounds__(kThreads) void pose_graph_kernel(const PoseGraphArg
     res->iterations      = iterations;
     res->envelope_blocks = blocks;
     res->status          = status;
+  }
+}
+
+// ---- Levenberg-Marquardt: the same linearisation, solve and update inside Nielsen's gain-ratio schedule (the header states it) ----
+struct PoseGraphLmArgs {
+  prs_pose_graphs g;
+  prs_pose_graph_lm_params p;
+  prs_pose_graph_lm_result* result;
+  long long graph_doubles;    // doubles of workspace per graph: the envelope, then d, g (6 per node each) and X0 (16 per node)
+  long long capacity_blocks;  // envelope blocks of workspace per graph
+  int rb_cols;
+};
+
+constexpr int kLmNodeDoubles = 28;
+
+__global__ __launch_bounds__(kThreads) void pose_graph_lm_kernel(const PoseGraphLmArgs args) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  const prs_pose_graphs& B          = args.g;
+  const prs_pose_graph_lm_params& P = args.p;
+  const int lane = threadIdx.x, g = blockIdx.x;
+  const int N = B.node_stride;
+  Lds s;
+  carve_lds(s, smem, N, args.rb_cols);
+  Graph G;
+  double* ws = reinterpret_cast<double*>(B.workspace) + (size_t) g * (size_t) args.graph_doubles;
+  graph_of(G, B, g, ws);
+  double* sd  = ws + (size_t) args.capacity_blocks * 36;  // d_r = h_rr, undamped
+  double* sg  = sd + 6 * (size_t) N;                       // g_r = -b_r
+  double* sX0 = sg + 6 * (size_t) N;                       // the poses the round started from
+  const int n = G.n, E = G.n_edges;
+  prs_pose_graph_lm_result* res = args.result + g;
+
+  int blocks = 0;
+  bool any_free = false;
+  int status = check_graph(G, s, B, args.capacity_blocks, lane, blocks, any_free);
+
+  int iterations = 0, n_chi = 0, rounds = 0, trials_total = 0, rejected_npd = 0, stalled = 0;
+  double chi_final = 0.0;
+  if (status == PRS_OK && E > 0 && any_free) {
+    const double eps = (double) P.epsilon, user = (double) P.user_lambda_init, tau = (double) P.tau;
+    const double step_high = (double) P.step_high, step_low = (double) P.step_low;
+    const bool variable = P.variable_damping != 0;
+    const int form      = variable ? PRS_DAMPING_DIAG : PRS_DAMPING_IDENTITY;
+    double lambda = 0.0, nu = 2.0, chi_prev = 0.0;
+    for (int it = 0; it < P.max_iterations; ++it) {
+      clear_system(G, s, blocks, lane);
+      const double chi = linearize<true>(G, s, lane);
+      if (lane == 0) {
+        res->chi[it] = chi;
+      }
+      n_chi = it + 1;
+      if (eps > 0.0 && it > 0 && chi_prev - chi < eps * chi_prev) {
+        break;
+      }
+      chi_prev = chi;
+      // d, g and X0 of this round; the largest h_rr of a free node (a maximum has no order)
+      double hmax = 0.0;
+      bool odd = false;  // a diagonal entry that is not finite
+      for (int r = lane; r < 6 * n; r += kThreads) {
+        const int j = r / 6, a = r - 6 * j;
+        const double h = G.env[row_base(s, j) + (size_t) a * row_width(s, j) + 6 * (j - s.first[j]) + a];
+        sd[r] = h;
+        sg[r] = -s.y[r];
+        if (G.fixed[j] == 0) {
+          odd  = odd || !__builtin_isfinite(h);
+          hmax = h > hmax ? h : hmax;
+        }
+      }
+      for (int i = lane; i < 16 * n; i += kThreads) {
+        sX0[i] = G.X[i];
+      }
+      if (it == 0) {
+        nu = 2.0;
+        if (user > 0.0) {
+          lambda = user;
+        } else {
+#pragma unroll
+          for (int d = kThreads / 2; d > 0; d >>= 1) {
+            const double o = __shfl_xor(hmax, d, kThreads);
+            hmax = o > hmax ? o : hmax;
+          }
+          if (__ballot(odd) != 0ull || !(hmax > 0.0)) {
+            status = PRS_ERR_NOT_POSITIVE_DEFINITE;
+            break;
+          }
+          lambda = tau * hmax;
+        }
+      }
+      __syncthreads();
+      bool accepted = false, pivot_failed = false;
+      double lambda_used = lambda;
+      int t = 0;
+      for (t = 1; t <= P.lm_iterations_max; ++t) {
+        if (t > 1) {
+          // the undamped system again: X is X0, so these are the bits of the round's linearisation
+          clear_system(G, s, blocks, lane);
+          (void) linearize<true>(G, s, lane);
+        }
+        lambda_used = lambda;
+        damp_system(G, s, lambda, form, lane);
+        pivot_failed = !solve_system(G, s, args.rb_cols, lane);
+        accepted     = false;
+        if (pivot_failed) {
+          ++rejected_npd;
+        } else {
+          update_poses(G, s, sX0, lane);
+          const double chi_t = linearize<false>(G, s, lane);
+          // scale: the terms dx_r ((lambda D_r) dx_r + g_r) side by side (1 / d is no longer needed: they go where it was), then
+          // one chain over the rows in ascending order from +0, which every lane runs (uniform)
+          for (int r = lane; r < 6 * n; r += kThreads) {
+            const double dx = s.y[r], D = variable ? sd[r] : 1.0;
+            s.invd[r] = G.fixed[r / 6] ? 0.0 : dx * ((lambda * D) * dx + sg[r]);
+          }
+          __syncthreads();
+          double scale = 0.0;
+          for (int r = 0; r < 6 * n; ++r) {
+            scale = scale + s.invd[r];
+          }
+          scale = scale + 1e-3;
+          __syncthreads();
+          const double rho = (chi - chi_t) / scale;
+          accepted         = rho > 0.0 && __builtin_isfinite(chi_t);
+          if (accepted) {
+            const double u = 2.0 * rho - 1.0;
+            const double alpha = 1.0 - (u * u) * u;
+            const double m = alpha < step_high ? alpha : step_high;
+            lambda = lambda * (m > step_low ? m : step_low);
+            nu     = 2.0;
+            break;
+          }
+          for (int i = lane; i < 16 * n; i += kThreads) {
+            G.X[i] = sX0[i];
+          }
+          __syncthreads();
+        }
+        lambda = lambda * nu;
+        nu     = 2.0 * nu;
+        if (!__builtin_isfinite(lambda)) {
+          break;
+        }
+      }
+      t = t > P.lm_iterations_max ? P.lm_iterations_max : t;
+      if (lane == 0) {
+        res->lambda[it] = lambda_used;
+        res->trials[it] = t;
+      }
+      trials_total += t;
+      rounds = it + 1;
+      if (!accepted) {
+        if (pivot_failed) {
+          status = PRS_ERR_NOT_POSITIVE_DEFINITE;
+        } else {
+          stalled = 1;
+        }
+        break;
+      }
+      iterations = it + 1;
+    }
+  }
+  if ((status == PRS_OK || status == PRS_ERR_NOT_POSITIVE_DEFINITE) && E > 0) {
+    chi_final = linearize<false>(G, s, lane);
+  }
+  if (lane == 0) {
+    for (int i = n_chi; i < kMaxIterations; ++i) {
+      res->chi[i] = 0.0;
+    }
+    for (int i = rounds; i < kMaxIterations; ++i) {  // rounds that ran no trial: lambda 0, 0 trials
+      res->lambda[i] = 0.0;
+      res->trials[i] = 0;
+    }
+    res->chi_final                      = chi_final;
+    res->linearizations                 = n_chi;
+    res->iterations                     = iterations;
+    res->envelope_blocks                = blocks;
+    res->status                         = status;
+    res->trials_total                   = trials_total;
+    res->rejected_not_positive_definite = rejected_npd;
+    res->stalled                        = stalled;
   }
 }
 
@@ -695,6 +920,45 @@ int pose_graph_rb_cols(const int node_stride) {
 
 }  // namespace
 
+namespace {
+
+// the call-level checks both algorithms share (`who`: the entry point, for the message)
+int check_batch(prs_context* ctx, const std::string& who, const prs_pose_graphs* graphs, const void* result) {
+  if (!graphs->X || !graphs->fixed || !graphs->n_nodes || !graphs->from || !graphs->to || !graphs->Z || !graphs->n_edges ||
+      !graphs->workspace || !result) {
+    return ctx_fail(ctx, PRS_ERR_NULL, (who + ": input or output buffer not set").c_str());
+  }
+  if (graphs->node_stride < 1 || graphs->edge_stride < 1) {
+    return ctx_fail(ctx, PRS_ERR_RANGE, (who + ": stride below 1").c_str());
+  }
+  if (graphs->node_stride > kMaxNodeStride) {
+    return ctx_fail(ctx, PRS_ERR_CAPACITY, (who + ": node_stride above 1024 (LDS holds 104 bytes per node)").c_str());
+  }
+  if ((reinterpret_cast<uintptr_t>(graphs->X) | reinterpret_cast<uintptr_t>(graphs->workspace) | reinterpret_cast<uintptr_t>(result)) & 7) {
+    return ctx_fail(ctx, PRS_ERR_UNSUPPORTED, (who + ": X, workspace and result must be 8-byte aligned").c_str());
+  }
+  return PRS_OK;
+}
+
+template <class Kernel, class Args>
+int launch_one_wave_per_graph(prs_context* ctx, const std::string& who, Kernel kernel, const Args& a, const int batch, const int node_stride) {
+  const size_t lds = lds_fixed_bytes(node_stride) + (size_t) a.rb_cols * 6 * sizeof(double);
+  hipError_t e     = hipSuccess;
+  if (lds > 64u * 1024u) {
+    e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds);
+  }
+  if (e == hipSuccess) {
+    hipLaunchKernelGGL(kernel, dim3((unsigned) batch), dim3(kThreads), lds, ctx_stream(ctx), a);
+    e = hipGetLastError();
+  }
+  if (e != hipSuccess) {
+    return ctx_fail_hip(ctx, e, (who + " launch").c_str());
+  }
+  return PRS_OK;
+}
+
+}  // namespace
+
 int pose_graph_launch(prs_context* ctx, const prs_pose_graph_params* params, const prs_pose_graphs* graphs) {
   if (!params || !graphs) {
     return ctx_fail(ctx, PRS_ERR_NULL, "prs_pose_graph_optimize_batch: parameters not set");
@@ -709,38 +973,44 @@ int pose_graph_launch(prs_context* ctx, const prs_pose_graph_params* params, con
   if (graphs->batch <= 0) {
     return PRS_OK;
   }
-  if (!graphs->X || !graphs->fixed || !graphs->n_nodes || !graphs->from || !graphs->to || !graphs->Z || !graphs->n_edges ||
-      !graphs->workspace || !graphs->result) {
-    return ctx_fail(ctx, PRS_ERR_NULL, "prs_pose_graph_optimize_batch: input or output buffer not set");
-  }
-  if (graphs->node_stride < 1 || graphs->edge_stride < 1) {
-    return ctx_fail(ctx, PRS_ERR_RANGE, "prs_pose_graph_optimize_batch: stride below 1");
-  }
-  if (graphs->node_stride > kMaxNodeStride) {
-    return ctx_fail(ctx, PRS_ERR_CAPACITY, "prs_pose_graph_optimize_batch: node_stride above 1024 (LDS holds 104 bytes per node)");
-  }
-  if ((reinterpret_cast<uintptr_t>(graphs->X) | reinterpret_cast<uintptr_t>(graphs->workspace) | reinterpret_cast<uintptr_t>(graphs->result)) & 7) {
-    return ctx_fail(ctx, PRS_ERR_UNSUPPORTED, "prs_pose_graph_optimize_batch: X, workspace and result must be 8-byte aligned");
-  }
+  PRS_TRY(check_batch(ctx, "prs_pose_graph_optimize_batch", graphs, graphs->result));
   PoseGraphArgs a;
   memset(&a, 0, sizeof(a));
   a.g               = *graphs;
   a.p               = *params;
   a.capacity_blocks = (long long) (graphs->workspace_bytes / (uint64_t) graphs->batch / (36 * sizeof(double)));
   a.rb_cols         = pose_graph_rb_cols(graphs->node_stride);
-  const size_t lds  = lds_fixed_bytes(graphs->node_stride) + (size_t) a.rb_cols * 6 * sizeof(double);
-  hipError_t e      = hipSuccess;
-  if (lds > 64u * 1024u) {
-    e = hipFuncSetAttribute(reinterpret_cast<const void*>(pose_graph_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds);
+  return launch_one_wave_per_graph(ctx, "prs_pose_graph_optimize_batch", pose_graph_kernel, a, graphs->batch, graphs->node_stride);
+}
+
+int pose_graph_lm_launch(prs_context* ctx, const prs_pose_graph_lm_params* params, const prs_pose_graphs* graphs,
+                         prs_pose_graph_lm_result* result) {
+  if (!params || !graphs) {
+    return ctx_fail(ctx, PRS_ERR_NULL, "prs_pose_graph_optimize_lm_batch: parameters not set");
   }
-  if (e == hipSuccess) {
-    hipLaunchKernelGGL(pose_graph_kernel, dim3((unsigned) graphs->batch), dim3(kThreads), lds, ctx_stream(ctx), a);
-    e = hipGetLastError();
+  if (!std::isfinite(params->user_lambda_init) || !std::isfinite(params->tau) || params->tau < 0.0f || !std::isfinite(params->step_high) ||
+      !std::isfinite(params->step_low) || !std::isfinite(params->epsilon) || params->max_iterations < 0 ||
+      params->max_iterations > kMaxIterations) {
+    return ctx_fail(ctx, PRS_ERR_RANGE, "prs_pose_graph_optimize_lm_batch: a parameter is not finite, tau is negative, or max_iterations outside [0, 32]");
   }
-  if (e != hipSuccess) {
-    return ctx_fail_hip(ctx, e, "prs_pose_graph_optimize_batch launch");
+  if (params->lm_iterations_max < 1 || params->step_low > params->step_high) {
+    return ctx_fail(ctx, PRS_ERR_RANGE, "prs_pose_graph_optimize_lm_batch: lm_iterations_max below 1 or step_low above step_high");
   }
-  return PRS_OK;
+  if (graphs->batch <= 0) {
+    return PRS_OK;
+  }
+  PRS_TRY(check_batch(ctx, "prs_pose_graph_optimize_lm_batch", graphs, result));
+  PoseGraphLmArgs a;
+  memset(&a, 0, sizeof(a));
+  a.g             = *graphs;
+  a.p             = *params;
+  a.result        = result;
+  a.graph_doubles = (long long) (graphs->workspace_bytes / (uint64_t) graphs->batch / sizeof(double));
+  // what d, g and X0 leave of a graph's share is its envelope (a share below them: no room for any graph, PRS_ERR_CAPACITY each)
+  const long long left = a.graph_doubles - (long long) kLmNodeDoubles * graphs->node_stride;
+  a.capacity_blocks    = left > 0 ? left / 36 : 0;
+  a.rb_cols            = pose_graph_rb_cols(graphs->node_stride);
+  return launch_one_wave_per_graph(ctx, "prs_pose_graph_optimize_lm_batch", pose_graph_lm_kernel, a, graphs->batch, graphs->node_stride);
 }
 
 int pose_graph_append_launch(prs_context* ctx, const prs_pose_graph_params* params, const prs_pose_graphs* graphs,
@@ -774,6 +1044,104 @@ int pose_graph_append_launch(prs_context* ctx, const prs_pose_graph_params* para
     return ctx_fail_hip(ctx, e, "prs_pose_graph_append_closures launch");
   }
   return PRS_OK;
+}
+
+// The host-pointer entry of either algorithm: sizes the envelope, stages, runs `launch(descriptor, device result)`, downloads.
+// node_doubles: doubles of workspace per node behind the envelope.
+template <class Params, class Result, class Launch>
+int optimize_on_host(prs_context* ctx, const char* entry, const Params* params, int32_t n_nodes, double* X16, const uint8_t* fixed,
+                     int32_t n_edges, const int32_t* from, const int32_t* to, const float* Z16, const float* omega36, Result* result,
+                     const int node_doubles, Launch launch) {
+  const std::string who(entry);
+  if (!ctx) {
+    return PRS_ERR_NULL;
+  }
+  if (!params || !result || (n_nodes > 0 && (!X16 || !fixed)) || (n_edges > 0 && (!from || !to || !Z16))) {
+    return ctx_fail(ctx, PRS_ERR_NULL, (who + ": input or output buffer not set").c_str());
+  }
+  if (n_nodes < 0 || n_edges < 0) {
+    return ctx_fail(ctx, PRS_ERR_RANGE, (who + ": negative size").c_str());
+  }
+  if (n_nodes > kMaxNodeStride) {
+    return ctx_fail(ctx, PRS_ERR_CAPACITY, (who + ": more than 1024 nodes").c_str());
+  }
+  (void) hipSetDevice(ctx->device);
+  const size_t nn = (size_t) (n_nodes > 0 ? n_nodes : 1), ne = (size_t) (n_edges > 0 ? n_edges : 1);
+  // the envelope of this graph (an endpoint out of range is the kernel's to report: it takes no part here)
+  size_t blocks = 0;
+  {
+    std::vector<int32_t> first(nn);
+    for (int32_t i = 0; i < n_nodes; ++i) {
+      first[i] = i;
+    }
+    for (int32_t k = 0; k < n_edges; ++k) {
+      const int32_t f = from[k], t = to[k];
+      if (f >= 0 && f < n_nodes && t >= 0 && t < n_nodes && f != t) {
+        const int32_t hi = f > t ? f : t, lo = f > t ? t : f;
+        first[hi] = lo < first[hi] ? lo : first[hi];
+      }
+    }
+    for (int32_t i = 0; i < n_nodes; ++i) {
+      blocks += (size_t) (i - first[i] + 1);
+    }
+  }
+  blocks = blocks > 0 ? blocks : 1;
+  struct Meta {
+    int32_t n_nodes, n_edges;
+  };
+  // fixed | sizes | from | to | Z | omega (uploaded) | X (both) | result (downloaded) | envelope (device only)
+  Staging st(ctx, entry, ARENA_STAGE_POSE_GRAPH);
+  auto s_fixed = st.up<uint8_t>(nn);
+  auto s_meta  = st.up<Meta>(1);
+  auto s_from  = st.up<int32_t>(ne);
+  auto s_to    = st.up<int32_t>(ne);
+  auto s_Z     = st.up<float>(ne * 16);
+  auto s_omega = st.up<float>(omega36 ? ne * 36 : 0);
+  auto s_X     = st.both<double>(nn * 16);
+  auto s_res   = st.down<Result>(1);
+  const size_t ws_doubles = blocks * 36 + (size_t) node_doubles * nn;
+  auto s_env   = st.device<double>(ws_doubles);
+  PRS_TRY(st.commit());
+  if (n_nodes > 0) {
+    memcpy(s_fixed.h(), fixed, (size_t) n_nodes);
+    memcpy(s_X.h(), X16, (size_t) n_nodes * 16 * sizeof(double));
+  }
+  s_meta.h()->n_nodes = n_nodes;
+  s_meta.h()->n_edges = n_edges;
+  if (n_edges > 0) {
+    memcpy(s_from.h(), from, (size_t) n_edges * sizeof(int32_t));
+    memcpy(s_to.h(), to, (size_t) n_edges * sizeof(int32_t));
+    memcpy(s_Z.h(), Z16, (size_t) n_edges * 16 * sizeof(float));
+    if (omega36) {
+      memcpy(s_omega.h(), omega36, (size_t) n_edges * 36 * sizeof(float));
+    }
+  }
+  PRS_TRY(st.upload());
+  prs_pose_graphs b;
+  memset(&b, 0, sizeof(b));
+  b.batch           = 1;
+  b.node_stride     = (int32_t) nn;
+  b.edge_stride     = (int32_t) ne;
+  b.X               = s_X.d();
+  b.fixed           = s_fixed.d();
+  b.n_nodes         = &s_meta.d()->n_nodes;
+  b.from            = s_from.d();
+  b.to              = s_to.d();
+  b.Z               = s_Z.d();
+  b.omega           = omega36 ? s_omega.d() : nullptr;
+  b.n_edges         = &s_meta.d()->n_edges;
+  b.workspace       = s_env.d();
+  b.workspace_bytes = ws_doubles * sizeof(double);
+  PRS_TRY(launch(&b, s_res.d()));
+  PRS_TRY(st.download());
+  memcpy(result, s_res.h(), sizeof(Result));
+  if (n_nodes > 0) {
+    memcpy(X16, s_X.h(), (size_t) n_nodes * 16 * sizeof(double));
+  }
+  if (result->status < 0) {
+    return ctx_fail(ctx, result->status, (who + ": the graph was refused or its system is not positive definite").c_str());
+  }
+  return result->status;
 }
 
 }  // namespace prs
@@ -817,95 +1185,41 @@ int prs_pose_graph_append_closures(prs_context* ctx, const prs_pose_graph_params
 int prs_pose_graph_optimize(prs_context* ctx, const prs_pose_graph_params* params, int32_t n_nodes, double* X16, const uint8_t* fixed,
                             int32_t n_edges, const int32_t* from, const int32_t* to, const float* Z16, const float* omega36,
                             prs_pose_graph_result* result) {
+  return optimize_on_host(ctx, "prs_pose_graph_optimize", params, n_nodes, X16, fixed, n_edges, from, to, Z16, omega36, result, 0,
+                          [&](prs_pose_graphs* b, prs_pose_graph_result* d_result) {
+                            b->result = d_result;
+                            return pose_graph_launch(ctx, params, b);
+                          });
+}
+
+uint64_t prs_pose_graph_lm_workspace_bytes(int32_t batch, int32_t node_stride, int64_t envelope_blocks_per_graph) {
+  if (batch <= 0 || node_stride <= 0 || envelope_blocks_per_graph <= 0) {
+    return 0;
+  }
+  return (uint64_t) batch * ((uint64_t) envelope_blocks_per_graph * 36u + (uint64_t) kLmNodeDoubles * (uint64_t) node_stride) * sizeof(double);
+}
+
+void prs_pose_graph_lm_struct_sizes(uint64_t* sizes2) {
+  sizes2[0] = sizeof(prs_pose_graph_lm_params);
+  sizes2[1] = sizeof(prs_pose_graph_lm_result);
+}
+
+int prs_pose_graph_optimize_lm_batch(prs_context* ctx, const prs_pose_graph_lm_params* params, const prs_pose_graphs* graphs,
+                                     prs_pose_graph_lm_result* result) {
   if (!ctx) {
     return PRS_ERR_NULL;
   }
-  if (!params || !result || (n_nodes > 0 && (!X16 || !fixed)) || (n_edges > 0 && (!from || !to || !Z16))) {
-    return ctx_fail(ctx, PRS_ERR_NULL, "prs_pose_graph_optimize: input or output buffer not set");
-  }
-  if (n_nodes < 0 || n_edges < 0) {
-    return ctx_fail(ctx, PRS_ERR_RANGE, "prs_pose_graph_optimize: negative size");
-  }
-  if (n_nodes > kMaxNodeStride) {
-    return ctx_fail(ctx, PRS_ERR_CAPACITY, "prs_pose_graph_optimize: more than 1024 nodes");
-  }
   (void) hipSetDevice(ctx->device);
-  const size_t nn = (size_t) (n_nodes > 0 ? n_nodes : 1), ne = (size_t) (n_edges > 0 ? n_edges : 1);
-  // the envelope of this graph (an endpoint out of range is the kernel's to report: it takes no part here)
-  size_t blocks = 0;
-  {
-    std::vector<int32_t> first(nn);
-    for (int32_t i = 0; i < n_nodes; ++i) {
-      first[i] = i;
-    }
-    for (int32_t k = 0; k < n_edges; ++k) {
-      const int32_t f = from[k], t = to[k];
-      if (f >= 0 && f < n_nodes && t >= 0 && t < n_nodes && f != t) {
-        const int32_t hi = f > t ? f : t, lo = f > t ? t : f;
-        first[hi] = lo < first[hi] ? lo : first[hi];
-      }
-    }
-    for (int32_t i = 0; i < n_nodes; ++i) {
-      blocks += (size_t) (i - first[i] + 1);
-    }
-  }
-  blocks = blocks > 0 ? blocks : 1;
-  struct Meta {
-    int32_t n_nodes, n_edges;
-  };
-  // fixed | sizes | from | to | Z | omega (uploaded) | X (both) | result (downloaded) | envelope (device only)
-  Staging st(ctx, "prs_pose_graph_optimize", ARENA_STAGE_POSE_GRAPH);
-  auto s_fixed = st.up<uint8_t>(nn);
-  auto s_meta  = st.up<Meta>(1);
-  auto s_from  = st.up<int32_t>(ne);
-  auto s_to    = st.up<int32_t>(ne);
-  auto s_Z     = st.up<float>(ne * 16);
-  auto s_omega = st.up<float>(omega36 ? ne * 36 : 0);
-  auto s_X     = st.both<double>(nn * 16);
-  auto s_res   = st.down<prs_pose_graph_result>(1);
-  auto s_env   = st.device<double>(blocks * 36);
-  PRS_TRY(st.commit());
-  if (n_nodes > 0) {
-    memcpy(s_fixed.h(), fixed, (size_t) n_nodes);
-    memcpy(s_X.h(), X16, (size_t) n_nodes * 16 * sizeof(double));
-  }
-  s_meta.h()->n_nodes = n_nodes;
-  s_meta.h()->n_edges = n_edges;
-  if (n_edges > 0) {
-    memcpy(s_from.h(), from, (size_t) n_edges * sizeof(int32_t));
-    memcpy(s_to.h(), to, (size_t) n_edges * sizeof(int32_t));
-    memcpy(s_Z.h(), Z16, (size_t) n_edges * 16 * sizeof(float));
-    if (omega36) {
-      memcpy(s_omega.h(), omega36, (size_t) n_edges * 36 * sizeof(float));
-    }
-  }
-  PRS_TRY(st.upload());
-  prs_pose_graphs b;
-  memset(&b, 0, sizeof(b));
-  b.batch           = 1;
-  b.node_stride     = (int32_t) nn;
-  b.edge_stride     = (int32_t) ne;
-  b.X               = s_X.d();
-  b.fixed           = s_fixed.d();
-  b.n_nodes         = &s_meta.d()->n_nodes;
-  b.from            = s_from.d();
-  b.to              = s_to.d();
-  b.Z               = s_Z.d();
-  b.omega           = omega36 ? s_omega.d() : nullptr;
-  b.n_edges         = &s_meta.d()->n_edges;
-  b.workspace       = s_env.d();
-  b.workspace_bytes = blocks * 36 * sizeof(double);
-  b.result          = s_res.d();
-  PRS_TRY(pose_graph_launch(ctx, params, &b));
-  PRS_TRY(st.download());
-  memcpy(result, s_res.h(), sizeof(prs_pose_graph_result));
-  if (n_nodes > 0) {
-    memcpy(X16, s_X.h(), (size_t) n_nodes * 16 * sizeof(double));
-  }
-  if (result->status < 0) {
-    return ctx_fail(ctx, result->status, "prs_pose_graph_optimize: the graph was refused or its system is not positive definite");
-  }
-  return result->status;
+  return pose_graph_lm_launch(ctx, params, graphs, result);
+}
+
+int prs_pose_graph_optimize_lm(prs_context* ctx, const prs_pose_graph_lm_params* params, int32_t n_nodes, double* X16,
+                               const uint8_t* fixed, int32_t n_edges, const int32_t* from, const int32_t* to, const float* Z16,
+                               const float* omega36, prs_pose_graph_lm_result* result) {
+  return optimize_on_host(ctx, "prs_pose_graph_optimize_lm", params, n_nodes, X16, fixed, n_edges, from, to, Z16, omega36, result,
+                          kLmNodeDoubles, [&](prs_pose_graphs* b, prs_pose_graph_lm_result* d_result) {
+                            return pose_graph_lm_launch(ctx, params, b, d_result);
+                          });
 }
 
 }  // extern "C"

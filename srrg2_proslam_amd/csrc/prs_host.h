@@ -194,6 +194,8 @@ int selective_extract_launch(prs_context* ctx, const prs_selective_extractor_par
 int depth_measurements_launch(prs_context* ctx, const prs_depth_params* params, const prs_depth_batch* batch);
 int point_align_launch(prs_context* ctx, const prs_point_align_params* params, const prs_point_align_pairs* batch);
 int pose_graph_launch(prs_context* ctx, const prs_pose_graph_params* params, const prs_pose_graphs* graphs);
+int pose_graph_lm_launch(prs_context* ctx, const prs_pose_graph_lm_params* params, const prs_pose_graphs* graphs,
+                         prs_pose_graph_lm_result* result);
 int pose_graph_append_launch(prs_context* ctx, const prs_pose_graph_params* params, const prs_pose_graphs* graphs,
                              const prs_pose_graph_closures* closures);
 int pose_compose_launch(prs_context* ctx, int batch, const float* prediction, const float* X, float* pose_out);

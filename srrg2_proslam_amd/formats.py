@@ -361,3 +361,17 @@ def graph_params(conf):
         out["linear_solver"] = linear.class_name
     out["closure_validator"] = 0 if conf.follow(slam, "closure_validator") is None else 1
     return out
+
+
+_GRAPH_LM = ("lm_iterations_max", "step_high", "step_low", "tau", "user_lambda_init", "variable_damping")
+
+
+def graph_lm_params(conf):
+    """the Levenberg-Marquardt block of the global solver (prs_pose_graph_lm_params), by the same wiring as graph_params:
+    MultiGraphSLAM* -> global_solver -> algorithm, when that is an IterationAlgorithmLM; {} for a file that wires another algorithm.
+    Only fields present in the file are returned."""
+    slam = next((r for r in conf.records if r.class_name.startswith("MultiGraphSLAM")), None)
+    algorithm = conf.follow(slam, "global_solver", "algorithm") if slam is not None else None
+    if algorithm is None or not algorithm.class_name.startswith("IterationAlgorithmLM"):
+        return {}
+    return _pick(algorithm, _GRAPH_LM)

@@ -1028,19 +1028,65 @@ def _graph_result_dict(r):
                 envelope_blocks=r.envelope_blocks, status=r.status)
 
 
-def pose_graph_optimize(ctx, params, poses, fixed, src, dst, Z, omega=None):
-    """host arrays, one graph -> (X [n, 4, 4] float64, result dict, status).  poses [n, 4, 4] float64, fixed [n], src / dst [E], Z
-    [E, 4, 4] float32, omega [E, 6, 6] float32 or None (identity).  A refused or numerically failed graph raises ProslamHipError."""
+def pose_graph_lm_params(cfg_graph, **overrides):
+    """prs_pose_graph_lm_params from a configs.py `graph` group that has an `lm` sub-dict (icl, tum); overrides by field name"""
+    lm = cfg_graph["lm"]
+    p = _lib.PoseGraphLmParams()
+    p.user_lambda_init, p.tau, p.step_high, p.step_low = lm["user_lambda_init"], lm["tau"], lm["step_high"], lm["step_low"]
+    p.lm_iterations_max, p.variable_damping = lm["lm_iterations_max"], lm["variable_damping"]
+    p.max_iterations, p.epsilon = cfg_graph["max_iterations"], cfg_graph["epsilon"]
+    for k, v in overrides.items():
+        setattr(p, k, v)
+    return p
+
+
+def _graph_lm_result_dict(r):
+    n = r.linearizations
+    rounds = sum(1 for t in r.trials if t > 0)
+    return dict(chi=np.ctypeslib.as_array(r.chi)[:n].copy(), chi_final=np.float64(r.chi_final),
+                lam=np.ctypeslib.as_array(r.lambda_)[:rounds].copy(), trials=[int(t) for t in r.trials[:rounds]], linearizations=n,
+                iterations=r.iterations, envelope_blocks=r.envelope_blocks, status=r.status, trials_total=r.trials_total,
+                rejected_not_positive_definite=r.rejected_not_positive_definite, stalled=r.stalled)
+
+
+def _host_graph(poses, fixed, src, dst, Z, omega):
     X = _np(poses, np.float64, (-1, 16)).copy()
     fx = _np(fixed, np.uint8, (-1,))
     f, t = _np(src, np.int32, (-1,)), _np(dst, np.int32, (-1,))
     z = _np(Z, np.float32, (-1, 16))
     om = _np(omega, np.float32, (-1, 36)) if omega is not None else None
+    return X, (X.shape[0], _p(X), _p(fx), len(f), _p(f), _p(t), _p(z), _p(om) if om is not None else None), (fx, f, t, z, om)
+
+
+def pose_graph_optimize(ctx, params, poses, fixed, src, dst, Z, omega=None):
+    """host arrays, one graph -> (X [n, 4, 4] float64, result dict, status).  poses [n, 4, 4] float64, fixed [n], src / dst [E], Z
+    [E, 4, 4] float32, omega [E, 6, 6] float32 or None (identity).  A refused or numerically failed graph raises ProslamHipError."""
+    X, args, _keep = _host_graph(poses, fixed, src, dst, Z, omega)
     res = _lib.PoseGraphResult()
-    rc = _lib.load().prs_pose_graph_optimize(ctx._h, C.byref(params), X.shape[0], _p(X), _p(fx), len(f), _p(f), _p(t), _p(z),
-                                             _p(om) if om is not None else None, C.byref(res))
+    rc = _lib.load().prs_pose_graph_optimize(ctx._h, C.byref(params), *args, C.byref(res))
     _check(ctx, rc, "prs_pose_graph_optimize")
     return X.reshape(-1, 4, 4), _graph_result_dict(res), rc
+
+
+def pose_graph_optimize_lm(ctx, params, poses, fixed, src, dst, Z, omega=None):
+    """pose_graph_optimize with the Levenberg-Marquardt loop (params: pose_graph_lm_params); the result dict adds lam and trials
+    per round, trials_total, rejected_not_positive_definite and stalled"""
+    X, args, _keep = _host_graph(poses, fixed, src, dst, Z, omega)
+    res = _lib.PoseGraphLmResult()
+    rc = _lib.load().prs_pose_graph_optimize_lm(ctx._h, C.byref(params), *args, C.byref(res))
+    _check(ctx, rc, "prs_pose_graph_optimize_lm")
+    return X.reshape(-1, 4, 4), _graph_lm_result_dict(res), rc
+
+
+def pose_graph_algorithm(cfg_graph, **overrides):
+    """(params, batch entry, host entry) for a configs.py `graph` group by its `algorithm`: IterationAlgorithmLM (icl, tum) gets the
+    LM entries, IterationAlgorithmGN the Gauss-Newton ones; any other name is an error"""
+    name = cfg_graph["algorithm"]
+    if name == "IterationAlgorithmLM":
+        return pose_graph_lm_params(cfg_graph, **overrides), pose_graph_optimize_lm_batch, pose_graph_optimize_lm
+    if name == "IterationAlgorithmGN":
+        return pose_graph_params(cfg_graph, **overrides), pose_graph_optimize_batch, pose_graph_optimize
+    raise ValueError("no pose-graph entry for algorithm %r" % (name,))
 
 
 def pose_graph_envelope_blocks(n_nodes, src, dst):
@@ -1056,9 +1102,10 @@ def pose_graph_envelope_blocks(n_nodes, src, dst):
 class PoseGraphBatch:
     """B pose graphs resident in HBM (torch tensors own the memory): poses (float64), fixed flags, edge lists with float32
     measurements and information matrices, the envelope workspace and the results.  envelope_blocks: room per graph (default: the
-    full lower triangle of node_stride nodes when that is small, else 64 blocks per node)."""
+    full lower triangle of node_stride nodes when that is small, else 64 blocks per node).  lm=True: the workspace also holds the
+    28 doubles per node of the Levenberg-Marquardt entry (pose_graph_optimize_lm_batch), whose results land in lm_result."""
 
-    def __init__(self, device, batch, node_stride, edge_stride, envelope_blocks=None, with_omega=True):
+    def __init__(self, device, batch, node_stride, edge_stride, envelope_blocks=None, with_omega=True, lm=False):
         import torch
         dev = torch.device("cuda", device)
         self.batch, self.node_stride, self.edge_stride = int(batch), int(node_stride), int(edge_stride)
@@ -1072,9 +1119,12 @@ class PoseGraphBatch:
         self.Z = torch.zeros((batch, edge_stride, 16), dtype=torch.float32, device=dev)
         self.omega = torch.zeros((batch, edge_stride, 36), dtype=torch.float32, device=dev) if with_omega else None
         self.n_edges = torch.zeros((batch,), dtype=torch.int32, device=dev)
-        self.workspace_bytes = int(_lib.load().prs_pose_graph_workspace_bytes(self.batch, self.node_stride, self.envelope_blocks))
+        self.lm = bool(lm)
+        size = _lib.load().prs_pose_graph_lm_workspace_bytes if self.lm else _lib.load().prs_pose_graph_workspace_bytes
+        self.workspace_bytes = int(size(self.batch, self.node_stride, self.envelope_blocks))
         self.workspace = torch.zeros((max(self.workspace_bytes // 8, 1),), dtype=torch.float64, device=dev)
         self.result = torch.zeros((batch, C.sizeof(_lib.PoseGraphResult) // 8), dtype=torch.float64, device=dev)
+        self.lm_result = torch.zeros((batch, C.sizeof(_lib.PoseGraphLmResult) // 8), dtype=torch.float64, device=dev)
         self.append_status = torch.zeros((batch,), dtype=torch.int32, device=dev)
         self.n_appended = torch.zeros((batch,), dtype=torch.int32, device=dev)
 
@@ -1112,6 +1162,10 @@ class PoseGraphBatch:
         raw = self.result[b].cpu().numpy().copy()
         return _graph_result_dict(_lib.PoseGraphResult.from_buffer_copy(raw.tobytes()))
 
+    def lm_result_of(self, b):
+        raw = self.lm_result[b].cpu().numpy().copy()
+        return _graph_lm_result_dict(_lib.PoseGraphLmResult.from_buffer_copy(raw.tobytes()))
+
     def poses_of(self, b):
         n = max(int(self.n_nodes[b].item()), 0)
         return self.X[b, : min(n, self.node_stride)].cpu().numpy().reshape(-1, 4, 4).copy()
@@ -1148,6 +1202,16 @@ def pose_graph_optimize_batch(ctx, params, graphs):
     d = graphs.descriptor()
     rc = _lib.load().prs_pose_graph_optimize_batch(ctx._h, C.byref(params), C.byref(d))
     _check(ctx, rc, "prs_pose_graph_optimize_batch")
+    return rc
+
+
+def pose_graph_optimize_lm_batch(ctx, params, graphs):
+    """enqueue the Levenberg-Marquardt optimiser for every graph of the batch (asynchronous, one launch); results in
+    graphs.lm_result.  A batch built without lm=True has a workspace without the 28 doubles per node: its graphs whose envelope
+    no longer fits report PRS_ERR_CAPACITY."""
+    d = graphs.descriptor()
+    rc = _lib.load().prs_pose_graph_optimize_lm_batch(ctx._h, C.byref(params), C.byref(d), graphs.lm_result.data_ptr())
+    _check(ctx, rc, "prs_pose_graph_optimize_lm_batch")
     return rc
 
 

@@ -1,0 +1,326 @@
+"""The Levenberg-Marquardt pose-graph optimiser on the device (prs_pose_graph_optimize_lm_batch / prs_pose_graph_optimize_lm / the C++
+adapter) equals its float64 restatement (tests/pose_graph_lm_ref.py optimize_lm) bit for bit -- poses, chi history, chi_final, the
+lambda and the trial count of every round, the counters, status -- for every case of tests/pose_graph_cases.py from its own guess,
+the rejecting guesses of tests/pose_graph_lm_cases.py, any position of a batch and either entry point; the status rules of the
+header; a closure appended from a real detector run; and the Gauss-Newton entry is what it was, before and after an LM launch."""
+import os
+import subprocess
+import tempfile
+
+import numpy as np
+import pytest
+
+import point_align_ref as par
+import pose_graph_cases as pc
+import pose_graph_lm_cases as lc
+import pose_graph_lm_ref as lm
+import pose_graph_ref as ref
+from srrg2_proslam_amd import _lib, configs
+
+pytestmark = pytest.mark.gpu
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+ROUNDS, EPS = 10, 1e-3
+
+
+@pytest.fixture(scope="module")
+def env():
+    import torch
+    import __graft_entry__ as g
+    g.build()
+    from srrg2_proslam_amd import ops
+    assert torch.cuda.is_available()
+    ctx = ops.Context(0)
+    yield ctx, ops
+    ctx.close()
+
+
+def params(ops, rounds=ROUNDS, eps=EPS, **over):
+    """shipped icl / tum parameters, overrides by field name"""
+    fields = dict(max_iterations=rounds, epsilon=eps)
+    fields.update(over)
+    return ops.pose_graph_lm_params(configs.get("icl")["graph"], **fields)
+
+
+_wanted = {}
+
+
+def want(c, rounds=ROUNDS, eps=EPS, caps=None, **over):
+    key = (c["name"], rounds, eps, tuple(sorted((caps or {}).items())), tuple(sorted(over.items())))
+    if key not in _wanted:
+        _wanted[key] = lm.optimize_lm(c["poses"], c["fixed"], c["src"], c["dst"], c["Z"], c["omega"], over, rounds, eps, **(caps or {}))
+    return _wanted[key]
+
+
+def rejecting(i):
+    name, sigmas, _ = lc.REJECTING[i]
+    return lc.perturbed(name, *sigmas)
+
+
+def bits(a):
+    return np.ascontiguousarray(a, np.float64).reshape(-1).view(np.uint64)
+
+
+def assert_same(got_X, got, w, what):
+    assert got["status"] == w["status"], (what, got["status"], w["status"])
+    assert got["envelope_blocks"] == w["envelope_blocks"] and got["iterations"] == w["iterations"], (what, got, w["iterations"])
+    assert got["linearizations"] == len(w["chi"]), what
+    assert got["trials"] == w["trials"], (what, got["trials"], w["trials"])
+    assert (got["trials_total"], got["rejected_not_positive_definite"], got["stalled"]) == \
+        (w["trials_total"], w["rejected_not_positive_definite"], w["stalled"]), (what, got)
+    assert np.array_equal(bits(got["lam"]), bits(w["lam"])), (what, got["lam"], w["lam"])
+    assert np.array_equal(bits(got["chi"]), bits(w["chi"])), (what, got["chi"], w["chi"])
+    assert np.array_equal(bits(got["chi_final"]), bits(w["chi_final"])), (what, got["chi_final"], w["chi_final"])
+    assert np.array_equal(bits(got_X), bits(w["X"])), (what, np.abs(np.asarray(got_X).reshape(-1, 16) - w["X"]).max())
+
+
+def upload(graphs, b, c):
+    graphs.upload(b, c["poses"], c["fixed"], (c["src"], c["dst"], c["Z"], c["omega"]))
+
+
+def run_batch(ctx, ops, cs, P, node_stride=None, edge_stride=None, envelope_blocks=None, lm_workspace=True):
+    ns = node_stride or max(max(len(c["poses"]) for c in cs), 1)
+    es = edge_stride or max(max(len(c["src"]) for c in cs), 1)
+    graphs = ops.PoseGraphBatch(0, len(cs), ns, es, envelope_blocks, lm=lm_workspace)
+    for b, c in enumerate(cs):
+        upload(graphs, b, c)
+    ops.pose_graph_optimize_lm_batch(ctx, P, graphs)
+    ctx.synchronize()
+    return graphs
+
+
+def test_every_case_from_its_own_guess(env):
+    """includes the two stalls by lambda overflow (n2_one_edge, chain3) and, once, the KITTI graph with the shipped icl parameters"""
+    ctx, ops = env
+    cs = list(pc.cases()) + [pc.kitti_case()]
+    graphs = run_batch(ctx, ops, cs, params(ops))
+    for b, c in enumerate(cs):
+        assert_same(graphs.poses_of(b), graphs.lm_result_of(b), want(c), c["name"])
+    for name in lc.OVERFLOW_STALLS:
+        r = graphs.lm_result_of([c["name"] for c in cs].index(name))
+        assert r["stalled"] == 1 and r["status"] == 0 and r["trials"][-1] >= 40
+    k = graphs.lm_result_of(len(cs) - 1)
+    assert k["iterations"] > 0 and k["chi_final"] < k["chi"][0]
+
+
+def test_rejecting_guesses(env):
+    """the perturbed guesses, each with both variable_damping values, and one run from user_lambda_init > 0"""
+    ctx, ops = env
+    seen = set()
+    for name, sig, _ in lc.REJECTING + (lc.ALL_ACCEPTED,):
+        c = lc.perturbed(name, *sig)
+        for vd in (1, 0):
+            graphs = run_batch(ctx, ops, [c], params(ops, variable_damping=vd))
+            w = want(c, variable_damping=vd)
+            assert_same(graphs.poses_of(0), graphs.lm_result_of(0), w, "%s variable_damping %d" % (c["name"], vd))
+            seen.update(w["trials"])
+    assert {1, 2}.issubset(seen) and max(seen) >= 3  # accepted at once, one rejection, consecutive rejections
+    c = rejecting(0)
+    graphs = run_batch(ctx, ops, [c], params(ops, user_lambda_init=0.25))
+    w = want(c, user_lambda_init=0.25)
+    assert w["lam"][0] == 0.25
+    assert_same(graphs.poses_of(0), graphs.lm_result_of(0), w, "user_lambda_init")
+
+
+def test_trial_cap_stalls_and_restores(env):
+    ctx, ops = env
+    name, sig, vd = lc.REJECTING[1]  # a round of five trials
+    c = lc.perturbed(name, *sig)
+    for cap in (1, 3):
+        graphs = run_batch(ctx, ops, [c], params(ops, variable_damping=vd, lm_iterations_max=cap))
+        w = want(c, variable_damping=vd, lm_iterations_max=cap)
+        got = graphs.lm_result_of(0)
+        assert_same(graphs.poses_of(0), got, w, "cap %d" % cap)
+        assert got["stalled"] == 1 and got["status"] == 0 and got["trials"][-1] == cap
+        # X0 of the stalled round: the poses of the run that stops one round earlier
+        earlier = want(c, rounds=got["iterations"], variable_damping=vd, lm_iterations_max=cap)
+        assert earlier["stalled"] == 0 and np.array_equal(bits(graphs.poses_of(0)), bits(earlier["X"]))
+
+
+def test_position_in_the_batch_and_entry_point(env):
+    ctx, ops = env
+    P = params(ops)
+    cs = [pc.case(n) for n in pc.MIXED_BATCH]
+    graphs = run_batch(ctx, ops, cs, P)
+    for b, c in enumerate(cs):
+        assert_same(graphs.poses_of(b), graphs.lm_result_of(b), want(c), "mixed %d %s" % (b, c["name"]))
+        single = run_batch(ctx, ops, [c], P)
+        assert np.array_equal(bits(single.poses_of(0)), bits(graphs.poses_of(b)))
+        assert np.array_equal(single.lm_result[0].cpu().numpy().view(np.uint64), graphs.lm_result[b].cpu().numpy().view(np.uint64))
+    assert np.array_equal(bits(graphs.poses_of(0)), bits(graphs.poses_of(4)))
+    assert np.array_equal(graphs.lm_result[0].cpu().numpy().view(np.uint64), graphs.lm_result[4].cpu().numpy().view(np.uint64))
+    for c in (pc.case("ring8"), pc.case("omega"), pc.case("n65"), pc.case("n1"), rejecting(0)):
+        X, res, rc = ops.pose_graph_optimize_lm(ctx, P, c["poses"], c["fixed"], c["src"], c["dst"], c["Z"], c["omega"])
+        assert rc == 0
+        assert_same(X, res, want(c), "host entry " + c["name"])
+    # the entry chosen from the configuration's algorithm
+    p, batch_entry, host_entry = ops.pose_graph_algorithm(configs.get("tum")["graph"])
+    assert batch_entry is ops.pose_graph_optimize_lm_batch and host_entry is ops.pose_graph_optimize_lm
+    c = pc.case("ring8")
+    X, res, rc = host_entry(ctx, p, c["poses"], c["fixed"], c["src"], c["dst"], c["Z"], c["omega"])
+    assert_same(X, res, want(c), "tum through pose_graph_algorithm")
+    assert ops.pose_graph_algorithm(configs.get("kitti")["graph"])[1] is ops.pose_graph_optimize_batch
+
+
+def test_gauss_newton_diverges_where_lm_converges(env):
+    ctx, ops = env
+    c = lc.perturbed("n65", 5.0, 0.55)
+    Pg = ops.pose_graph_params(dict(damping=1e-6, max_iterations=ROUNDS, epsilon=EPS))
+    _, g, _ = ops.pose_graph_optimize(ctx, Pg, c["poses"], c["fixed"], c["src"], c["dst"], c["Z"], c["omega"])
+    X, r, _ = ops.pose_graph_optimize_lm(ctx, params(ops), c["poses"], c["fixed"], c["src"], c["dst"], c["Z"], c["omega"])
+    print("chi[0] %.6g  Gauss-Newton chi_final %.6g  LM chi_final %.6g" % (g["chi"][0], g["chi_final"], r["chi_final"]))
+    assert g["chi_final"] > g["chi"][0]
+    assert r["chi"][0] == g["chi"][0] and r["chi_final"] < 1e-3 * r["chi"][0]
+    assert_same(X, r, want(c), "perturbed n65")
+
+
+def _status_case(base, **kw):
+    c = dict(pc.case(base))
+    c.update(kw)
+    return c
+
+
+def test_status_rules(env):
+    ctx, ops = env
+    import torch
+    P = params(ops, rounds=3, eps=0.0)
+    ring, chain = pc.case("ring8"), pc.case("chain3")
+    bad_end = _status_case("chain3", name="bad_endpoint", dst=np.array([1, 3], np.int32))
+    no_free = _status_case("chain3", name="no_free", fixed=np.ones(3, np.uint8))
+    no_edges = _status_case("chain3", name="no_edges", src=np.zeros(0, np.int32), dst=np.zeros(0, np.int32), Z=np.zeros((0, 16), np.float32))
+    lonely = _status_case("chain3", name="free_node_without_edge", src=np.array([0], np.int32), dst=np.array([1], np.int32),
+                          Z=pc.case("chain3")["Z"][:1])
+    cs = [ring, bad_end, no_free, ring, no_edges, lonely, chain]
+    graphs = ops.PoseGraphBatch(0, len(cs) + 5, 8, 8, 21, lm=True)  # room for ring8 exactly: 21 blocks
+    for b, c in enumerate(cs):
+        upload(graphs, b, c)
+    n = len(cs)
+    for b in range(n, n + 4):
+        upload(graphs, b, chain)
+    # n_nodes > node_stride, n_edges > edge_stride, negative node count, negative edge count; n + 4 stays empty
+    graphs.n_nodes[n], graphs.n_edges[n + 1], graphs.n_nodes[n + 2], graphs.n_edges[n + 3] = 9, 9, -1, -1
+    before = graphs.X.clone()
+    ops.pose_graph_optimize_lm_batch(ctx, P, graphs)
+    ctx.synchronize()
+    got = [graphs.lm_result_of(b) for b in range(n + 5)]
+    assert [g["status"] for g in got] == [0, ref.ERR_RANGE, 0, 0, 0, ref.ERR_NOT_POSITIVE, 0, ref.ERR_CAPACITY, ref.ERR_CAPACITY,
+                                          ref.ERR_RANGE, ref.ERR_RANGE, ref.WARN_EMPTY_INPUT]
+    caps = dict(node_stride=8, edge_stride=8, capacity_blocks=21)
+    for b in (0, 3, 6):
+        assert_same(graphs.poses_of(b), got[b], want(cs[b], rounds=3, eps=0.0, caps=caps), "neighbour %d" % b)
+    # refused and failed graphs keep their poses; no edges / no free node: success, 0 rounds
+    for b in (1, 2, 4, 5, n, n + 1, n + 2, n + 3, n + 4):
+        assert torch.equal(graphs.X[b], before[b]), b
+        assert got[b]["iterations"] == 0
+    for b in (2, 4):
+        assert got[b]["linearizations"] == 0 and got[b]["trials"] == [] and got[b]["trials_total"] == 0
+    assert np.array_equal(bits(got[2]["chi_final"]), bits(want(no_free, rounds=3, eps=0.0)["chi_final"]))
+    assert got[4]["chi_final"] == 0.0 and got[4]["envelope_blocks"] == 3
+    # the isolated free node: lambda * diag(H) leaves its pivot 0 in every trial, lambda * I lifts it
+    w = want(lonely, rounds=3, eps=0.0, caps=caps)
+    assert_same(graphs.poses_of(5), got[5], w, "lonely, variable damping")
+    assert got[5]["rejected_not_positive_definite"] == got[5]["trials_total"] > 1 and got[5]["stalled"] == 0
+    g0 = run_batch(ctx, ops, [lonely], params(ops, rounds=3, eps=0.0, variable_damping=0))
+    assert_same(g0.poses_of(0), g0.lm_result_of(0), want(lonely, rounds=3, eps=0.0, variable_damping=0), "lonely, identity damping")
+    assert g0.lm_result_of(0)["status"] == 0 and g0.lm_result_of(0)["iterations"] > 0
+    # a workspace of exactly the needed size, one block short, and one sized for Gauss-Newton (too small by 28 doubles per node)
+    for blocks, lm_ws, status in ((21, True, 0), (20, True, ref.ERR_CAPACITY), (21, False, ref.ERR_CAPACITY)):
+        g1 = run_batch(ctx, ops, [ring, chain], P, envelope_blocks=blocks, lm_workspace=lm_ws)
+        assert g1.lm_result_of(0)["status"] == status, (blocks, lm_ws)
+        if lm_ws:
+            assert g1.lm_result_of(1)["status"] == 0
+            w = want(ring, rounds=3, eps=0.0, caps=dict(capacity_blocks=blocks))
+            assert_same(g1.poses_of(0), g1.lm_result_of(0), w, "workspace of %d blocks" % blocks)
+        else:
+            assert torch.equal(g1.X[0], torch.from_numpy(ring["poses"]).to(g1.X.device))
+    # call-level refusals
+    for bad in (dict(lm_iterations_max=0), dict(step_low=0.7, step_high=0.6), dict(max_iterations=33)):
+        with pytest.raises(_lib.ProslamHipError) as e:
+            ops.pose_graph_optimize_lm_batch(ctx, params(ops, **bad), graphs)
+        assert e.value.status == _lib.ERR_RANGE, bad
+    with pytest.raises(_lib.ProslamHipError) as e:
+        ops.pose_graph_optimize_lm_batch(ctx, P, ops.PoseGraphBatch(0, 1, 1025, 4, 8, lm=True))
+    assert e.value.status == _lib.ERR_CAPACITY
+
+
+def test_gauss_newton_before_and_after(env):
+    ctx, ops = env
+    c = pc.case("two_closures_one_row")
+    Pg = ops.pose_graph_params(dict(damping=1e-6, max_iterations=6, epsilon=1e-3))
+    w = ref.optimize(c["poses"], c["fixed"], c["src"], c["dst"], c["Z"], c["omega"], 1e-6, ref.DAMPING_DIAG, 6, 1e-3)
+    graphs = ops.PoseGraphBatch(0, 1, len(c["poses"]), len(c["src"]), lm=True)
+    for when in ("before", "after"):
+        upload(graphs, 0, c)
+        ops.pose_graph_optimize_batch(ctx, Pg, graphs)
+        ctx.synchronize()
+        got = graphs.result_of(0)
+        assert got["status"] == w["status"] and got["iterations"] == w["iterations"] and got["linearizations"] == len(w["chi"]), when
+        assert np.array_equal(bits(got["chi"]), bits(w["chi"])) and np.array_equal(bits(got["chi_final"]), bits(w["chi_final"])), when
+        assert np.array_equal(bits(graphs.poses_of(0)), bits(w["X"])), when
+        if when == "before":
+            upload(graphs, 0, c)
+            ops.pose_graph_optimize_lm_batch(ctx, params(ops), graphs)
+            ctx.synchronize()
+            assert_same(graphs.poses_of(0), graphs.lm_result_of(0), want(c), "LM in between")
+
+
+def test_closure_from_the_detector(env):
+    """the fixture of tests/test_pose_graph_gpu.py::test_closures_from_the_detector: the detector's accepted slots become the edges
+    1 -> 0 and 2 -> 0 behind three odometry edges, then the LM entry runs on the same stream with no host round trip"""
+    import torch
+    from test_ref_pins import OracleBackend
+    ctx, ops = env
+    B = OracleBackend()
+    sc = {s["name"]: s for s in par.scenarios(B)}
+    k = configs.get("kitti")
+    db = ops.PlaceDatabase(ctx)
+    s0 = sc["kitti_00_00"]
+    db.add(0, s0["moving_desc"], s0["moving"])
+    Pp = ops.place_params(k["place"], max_candidates=2, minimum_age_difference_to_candidates=0)
+    unrelated = [u for u in par.unrelated(B) if u["config"] == "kitti"]
+    qs = [sc["kitti_00_00"], sc["kitti_00_01"]]
+    det = ops.LoopDetectorBatch(0, db, 3, max(len(q["fixed"]) for q in qs + unrelated[:1]), 2)
+    for b, q in enumerate(qs):
+        det.upload(b, 1 + b, q["fixed_desc"], q["fixed"])
+    det.upload(2, 9, unrelated[0]["fixed_desc"], unrelated[0]["fixed"])
+    step = np.eye(4)
+    step[2, 3] = 0.8
+    poses = np.stack([np.linalg.matrix_power(step, i) for i in range(4)])
+    odo = (np.array([0, 1, 2], np.int32), np.array([1, 2, 3], np.int32), np.stack([step] * 3).astype(np.float32), None)
+    fixed = np.array([1, 0, 0, 0], np.uint8)
+    graphs = ops.PoseGraphBatch(0, 1, 4, 5, lm=True)
+    graphs.upload(0, poses, fixed, odo)
+    dev = graphs.X.device
+    to_dev = lambda a: torch.tensor(a, dtype=torch.int32, device=dev)
+    Pa = ops.pose_graph_params(dict(damping=0.0, max_iterations=0, epsilon=0.0), closure_information=4.0)
+    torch.cuda.synchronize()
+    det.run(ctx, Pp, ops.bruteforce_params(k["loop"]["maximum_descriptor_distance"], 0.9), ops.point_align_params(k["loop"]))
+    graphs.append_closures(ctx, det, to_dev([0, 0, 0]), to_dev([1, 2, 3]), to_dev([0]), Pa)
+    ops.pose_graph_optimize_lm_batch(ctx, params(ops), graphs)
+    ctx.synchronize()
+    assert graphs.append_status.tolist() == [0] and graphs.n_appended.tolist() == [2] and graphs.n_edges.tolist() == [5]
+    src, dst, Z, om = graphs.edges_of(0)
+    assert src.tolist() == [0, 1, 2, 1, 2] and dst.tolist() == [1, 2, 3, 0, 0]
+    w = lm.optimize_lm(poses.reshape(-1, 16), fixed, src, dst, Z.reshape(-1, 16), om.reshape(-1, 36), {}, ROUNDS, EPS)
+    assert_same(graphs.poses_of(0), graphs.lm_result_of(0), w, "graph with closures")
+    assert w["iterations"] > 0 and w["chi_final"] < w["chi"][0]
+
+
+def test_plugin_adapter(env):
+    exe = os.path.join(ROOT, "tests", "cpp", "test_pose_graph_lm_plugin")
+    assert os.path.exists(exe), "build() did not produce the adapter test program"
+    c = rejecting(0)
+    assert c["omega"] is None
+    tmp = tempfile.mkdtemp()
+    names = {n: os.path.join(tmp, "pose_graph_lm_plugin_%s.bin" % n) for n in ("poses", "fixed", "src", "dst", "Z", "out")}
+    c["poses"].astype(np.float64).tofile(names["poses"])
+    c["fixed"].astype(np.uint8).tofile(names["fixed"])
+    c["src"].astype(np.int32).tofile(names["src"])
+    c["dst"].astype(np.int32).tofile(names["dst"])
+    c["Z"].astype(np.float32).tofile(names["Z"])
+    out = subprocess.run([exe, str(len(c["poses"])), str(len(c["src"])), names["poses"], names["fixed"], names["src"], names["dst"], names["Z"],
+                          names["out"]], capture_output=True, text=True, timeout=120)
+    assert out.returncode == 0, out.stdout + out.stderr
+    w = want(c)
+    assert "iterations %d trials %s " % (w["iterations"], ",".join(str(t) for t in w["trials"])) in out.stdout, out.stdout
+    assert 2 in w["trials"]
+    assert np.array_equal(bits(np.fromfile(names["out"], np.float64)), bits(w["X"]))
