@@ -114,7 +114,8 @@ PRS_API int prs_version(void);
  * prs_place_db, prs_place_params, prs_place_queries, prs_place_pairs and the prs_place_* entry points; and the pose-graph optimiser:
  * prs_pose_graph_params, prs_pose_graph_result, prs_pose_graphs, prs_pose_graph_closures, the prs_pose_graph_* entry points and the
  * status PRS_ERR_NOT_POSITIVE_DEFINITE; and its Levenberg-Marquardt form: prs_pose_graph_lm_params, prs_pose_graph_lm_result and the
- * prs_pose_graph_lm_* / prs_pose_graph_optimize_lm* entry points).  Callers memset() parameter structs before
+ * prs_pose_graph_lm_* / prs_pose_graph_optimize_lm* entry points; and the closure merger: prs_closure_merger_params,
+ * prs_closure_merge_batch, the prs_closure_merge* entry points and prs_map_merge_closure).  Callers memset() parameter structs before
  * filling them, so that fields they do not know select the shipped defaults (all zero). */
 #define PRS_ABI_VERSION 104
 PRS_API int prs_abi_check(int32_t header_version, uint64_t sizeof_stereo_params, uint64_t sizeof_pcf_params, uint64_t sizeof_aligner_params,
@@ -1016,7 +1017,7 @@ PRS_API int prs_depth_measurements(prs_context* ctx, const prs_depth_params* par
  * SE3Point2PointErrorFactor, information I3; registered at registration/instances.cpp:28,52), the aligner every shipped .conf wires
  * in as MultiLoopDetectorHBST3D.relocalize_aligner (kitti.conf:938-978), and the accept / reject verdict of the loop detector and
  * MultiRelocalizer3D (parameter comments kitti.conf:966-977).  The candidate search in front of it is the place database below, the
- * consumer of an accepted closure the pose-graph optimiser at the end of this header; the closure merger is not served.
+ * consumer of an accepted closure the pose-graph optimiser and the closure merger at the end of this header.
  *
  * The factor, the robustifiers, the loop and the verdict live in srrg2_solver / srrg2_slam_interfaces, not in the tree
  * (BUILD-DEFINED, stated like rows a13 / a14 of SURVEY.md Appendix A):
@@ -1408,6 +1409,122 @@ PRS_API int prs_pose_graph_optimize_lm_batch(prs_context* ctx, const prs_pose_gr
 PRS_API int prs_pose_graph_optimize_lm(prs_context* ctx, const prs_pose_graph_lm_params* params, int32_t n_nodes, double* X16,
                                        const uint8_t* fixed, int32_t n_edges, const int32_t* from, const int32_t* to, const float* Z16,
                                        const float* omega36, prs_pose_graph_lm_result* result);
+
+/* ================================================================================================
+ * Closure merger: folds the landmarks of the local map being left into the one a relocalisation re-enters
+ * replaces MergerCorrespondencePointIntensityDescriptor3f, the `closure_merger` of every shipped tracker slice (kitti.conf:446-460,
+ * euroc.conf:519, icl.conf:773, tum.conf:437, malaga.conf:536; apps/app_benchmark.cpp:140-160 setClosure, :183 merge), and
+ * MergerCorrespondenceProjectiveDepth3D, the same merger behind an unprojection
+ * (mapping/mergers/merger_correspondence_projective_depth_3d.cpp:7-33; tests/test_mergers.cpp:174-246).
+ *
+ * BUILD-DEFINED: MergerCorrespondence_::compute lives in srrg2_slam_interfaces, which is not in the tree.  The rule below is this
+ * build's, fitted to the two results the reference pins for the base merge on its ICL frames (321 points stay 321 and nothing moves;
+ * 321 become 431 with 338 measurements, every old point within 0.25 per coordinate); tests/closure_merge_ref.py restates it in
+ * numpy float32 and the kernel equals that bit for bit.  Float expressions are evaluated term by term, left to right.
+ *   1 points      an XYZ measurement (x, y, z, -) is used as is; a (u, v, d, -) measurement is unprojected, p = ((u - cx) / fx * d,
+ *                 (v - cy) / fy * d, d), the expression of PRS_MERGER_DEPTH_EKF.  A measurement with a component of p that is not
+ *                 finite, or (u, v, d) with d <= 0, is invalid: never merged, never added.
+ *   2 merge       per correspondence, in any order (the result does not depend on it): skipped if response >= maximum_response or the
+ *                 measurement is invalid; q = measurement_in_scene * p; d2 = (dx dx + dy dy) + dz dz against the landmark; skipped
+ *                 unless d2 < maximum_distance_geometry_squared; else coords = 0.5f * (coords + q) (the row's fourth float is kept),
+ *                 the landmark takes the measurement's descriptor (merger_projective_impl.cpp:186) and the measurement is marked
+ *                 merged.  Every landmark a correspondence names gets inlier = merged ? 1 : 0 (:66), a merged one n_opt += 1 and,
+ *                 where the map keeps it, state = (scene_in_world * coords, 0).  n_merged counts merged correspondences.
+ *   3 how many    n_to_add = max(0, min(target_number_of_merges - n_merged, n_measured - n_merged)) if n_merged <
+ *                 target_number_of_merges, else 0 (:158-163).
+ *   4 candidates  the valid measurements that were not merged.  At most n_to_add of them: all are added.  Otherwise, without binning,
+ *                 the first n_to_add in measurement order.
+ *   5 binning     decides only WHICH candidates are taken when there are more than n_to_add.  Image position: (u, v) of a (u, v, d)
+ *                 measurement; u = fx * x / z + cx, v = fy * y / z + cy of an XYZ measurement with z > 0.  A point whose position is
+ *                 not inside [0, canvas_cols) x [0, canvas_rows) is unbinned.  bin_row = round(v / (canvas_rows / number_of_row_bins)),
+ *                 the column likewise (:32-35, :84-85, std::round).  Bins that hold a merged measurement are blocked.  Pass 1 takes,
+ *                 per unblocked bin, the candidate with the smallest depth (p.z), the lowest index on ties; of more than n_to_add
+ *                 winners the lowest measurement indices are kept.  Pass 2 fills what is left from the remaining candidates, unbinned
+ *                 ones included, in measurement order.
+ *   6 append      the chosen measurements in ascending measurement index from row n_points: coords = (q, 0), the descriptor copied;
+ *                 where the map keeps them state = (scene_in_world * q, 0), covariance identity, n_opt = 0, inlier = 1, n_meas = 0
+ *                 (:317-320).  n_points grows by n_added.
+ * Status per pair (result[b].status), every pair on its own:
+ *   PRS_ERR_RANGE      n_points[b] outside [0, capacity], n_measured[b] < 0 or n_corr[b] < 0; or a correspondence names a landmark
+ *                      outside [0, n_points[b]) or a measurement outside [0, n_measured[b]).
+ *   PRS_ERR_CAPACITY   n_measured[b] > measurement_stride or n_corr[b] > corr_stride.
+ *   PRS_ERR_DUPLICATE  a landmark appears in two correspondences.
+ *     For these three the pair is left exactly as it was and n_merged = n_added = 0.  Counts are tested first; of several faults of
+ *     one vector the FIRST in vector order is reported (a duplicate counts at its second appearance).
+ *   PRS_ERR_SCENE_FULL n_points[b] + n_added > capacity (n_points[b] + n_added == capacity fits).  Decided before anything is
+ *                      appended: the merges of step 2 have been made, no row from n_points[b] on is written, n_points[b] is unchanged,
+ *                      n_merged is reported and n_added = 0.
+ *   PRS_OK             otherwise; also for a pair whose gate says "not accepted", which is left exactly as it was (0 merged, 0 added).
+ * Limits (PRS_ERR_UNSUPPORTED at the call, nothing launched): measurement_stride <= 16384; the scene bitmap (capacity / 8 bytes), the
+ * measurement bitmaps (4.5 bytes per 8 measurements of measurement_stride) and the bin table (8 bytes per bin of (rows + 2) x
+ * (cols + 2)) share 64 KiB of LDS; with binning 1 .. 4096 bins a side and a canvas; coords, desc, state, measurement and
+ * measurement_desc 16-byte aligned.  PRS_ERR_NULL: a required pointer unset, or state without scene_in_world.
+ * ============================================================================================== */
+enum { PRS_CLOSURE_XYZ = 0, PRS_CLOSURE_UVD = 1 };
+
+typedef struct {
+  int32_t measurement_kind;  /* PRS_CLOSURE_XYZ: MergerCorrespondencePointIntensityDescriptor3f; _UVD: ..ProjectiveDepth3D */
+  int32_t enable_binning;    /* MergerCorrespondence_::param_enable_binning (1 in every shipped .conf) */
+  uint32_t number_of_row_bins, number_of_col_bins; /* 10, 30 (merger_projective.h:47-56) */
+  int32_t canvas_rows, canvas_cols;
+  float fx, fy, cx, cy;      /* the unprojector's (UVD) / the binning projection's (XYZ) camera matrix */
+  float maximum_distance_geometry_squared; /* 0.25 */
+  float maximum_response;                  /* 50 */
+  uint32_t target_number_of_merges;        /* 200 */
+} prs_closure_merger_params;
+
+/* B (scene, measurement) pairs; device pointers */
+typedef struct {
+  int32_t batch;
+  int32_t capacity;            /* landmarks per scene (row stride of the per-landmark arrays) */
+  /* the scene: required */
+  float* coords;               /* [batch][capacity][4] xyz in the scene frame */
+  uint8_t* desc;               /* [batch][capacity][32] */
+  int32_t* n_points;           /* [batch] in/out */
+  /* its statistics: each optional, NULL if not kept */
+  float* state;                /* [batch][capacity][4] world frame; needs scene_in_world */
+  float* covariance;           /* [batch][capacity][9] */
+  uint32_t* n_opt;             /* [batch][capacity] */
+  uint8_t* inlier;             /* [batch][capacity] */
+  uint32_t* n_meas;            /* [batch][capacity] */
+  const float* scene_in_world; /* [batch][16] */
+  /* the measurement cloud */
+  int32_t measurement_stride;
+  int32_t corr_stride;
+  const float* measurement;    /* [batch][measurement_stride][4]: (x, y, z, -) or (u, v, d, -) */
+  const uint8_t* measurement_desc; /* [batch][measurement_stride][32] */
+  const int32_t* n_measured;   /* [batch] */
+  const prs_corr* corr;        /* [batch][corr_stride] */
+  const int32_t* n_corr;       /* [batch] */
+  const float* transform;      /* [batch][16] */
+  const prs_point_align_result* gate; /* optional [batch]: a pair whose `accepted` is 0 is left untouched */
+  prs_merge_result* result;    /* [batch] */
+  int32_t corr_from_aligner;   /* 0: fixed_idx -> scene, moving_idx -> measurement; 1: the aligner's / matcher's vector
+                                  (fixed_idx -> measurement, moving_idx -> scene), as in prs_merge_batch */
+  int32_t transform_is_scene_in_measurement; /* 0: transform is measurement_in_scene; 1: its rigid inverse is taken.  The loop
+                                  aligner's X is movingInFixed with the query fixed: with the candidate map as the scene and the
+                                  query as the measurement, X is scene-in-measurement */
+} prs_closure_merge_batch;
+
+/* device pointers, asynchronous on the context's stream: one kernel launch, no allocation and no synchronisation (graph-capturable) */
+PRS_API int prs_closure_merge_batch_run(prs_context* ctx, const prs_closure_merger_params* params, const prs_closure_merge_batch* batch);
+/* sizeof prs_closure_merger_params, prs_closure_merge_batch as the library was compiled (bindings check) */
+PRS_API void prs_closure_merge_struct_sizes(uint64_t* sizes2);
+/* host pointers, one pair, arrays of `capacity` rows in the layout above (coords4 / state4 [capacity][4]; any of state4 ..
+ * n_meas may be NULL; measurement4 [n_measured][4]).  Uploads, runs, downloads, synchronises; returns result->status. */
+PRS_API int prs_closure_merge(prs_context* ctx, const prs_closure_merger_params* params, int32_t capacity, int32_t* n_points,
+                              float* coords4, uint8_t* desc, float* state4, float* covariance9, uint32_t* n_opt, uint8_t* inlier,
+                              uint32_t* n_meas, const float* scene_in_world16, const float* measurement4,
+                              const uint8_t* measurement_desc, int32_t n_measured, const prs_corr* corr, int32_t n_corr,
+                              int32_t corr_from_aligner, const float* transform16, int32_t transform_is_scene_in_measurement,
+                              prs_merge_result* result);
+/* merges a measurement cloud into a device-resident map handle (prs_map_create), whose statistics arrays are kept up;
+ * measurement4 [n_measured][4]; scene_in_world16 NULL = identity.  No frame is counted and the pose table is not touched.
+ * Returns result->status. */
+PRS_API int prs_map_merge_closure(prs_map* h, const prs_closure_merger_params* params, const float* transform16,
+                                  int32_t transform_is_scene_in_measurement, const float* scene_in_world16, const float* measurement4,
+                                  const uint8_t* measurement_desc, int32_t n_measured, const prs_corr* corr, int32_t n_corr,
+                                  int32_t corr_from_aligner, prs_merge_result* result);
 
 #ifdef __cplusplus
 }

@@ -1073,6 +1073,107 @@ protected:
   size_t _n_merged = 0, _n_added = 0;
 };
 
+// ---- closure merger ---------------------------------------------------------------------------------------------------
+// MergerCorrespondence_ (srrg2_slam_interfaces, not in the tree: BUILD-DEFINED rule, include/proslam_hip.h "Closure merger"): folds a
+// measurement cloud into a scene through given correspondences, in place like the reference object.  PARAM names are the
+// reference's; the base class's own defaults are not in the tree, so the values every shipped .conf sets stand in (kitti.conf:446-460),
+// the bin counts are merger_projective.h:47-56.  KIND_ selects the measurement: 3D points (the tracker slice's closure_merger) or
+// (u, v, d) behind the unprojector (mapping/mergers/merger_correspondence_projective_depth_3d.cpp:7-33).
+struct UnprojectorPinholeHIP {
+  PropertyUnsignedInt param_canvas_rows{0};
+  PropertyUnsignedInt param_canvas_cols{0};
+  float camera_matrix[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
+  void setCameraMatrix(const float* K9) { std::memcpy(camera_matrix, K9, sizeof(camera_matrix)); }
+};
+using UnprojectorPinholeHIPPtr = std::shared_ptr<UnprojectorPinholeHIP>;
+
+template <int KIND_>
+class MergerCorrespondenceHIP_ {
+public:
+  using SceneType       = PointIntensityDescriptorVectorCloud<3>;
+  using MeasurementType = PointIntensityDescriptorVectorCloud<3>;
+  explicit MergerCorrespondenceHIP_(ContextPtr ctx) : param_unprojector(new UnprojectorPinholeHIP()), _ctx(std::move(ctx)) {
+    const float I[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
+    std::memcpy(_measurement_in_scene, I, sizeof(I));
+  }
+  PropertyBool param_enable_binning{true};
+  PropertyFloat param_maximum_distance_geometry_squared{0.25f};
+  PropertyFloat param_maximum_response{50.f};
+  PropertyUnsignedInt param_target_number_of_merges{200};
+  PropertyUnsignedInt param_number_of_row_bins{10};
+  PropertyUnsignedInt param_number_of_col_bins{30};
+  // camera matrix and canvas: the unprojector of the (u, v, d) form; for 3D measurements only the binning projects with them
+  UnprojectorPinholeHIPPtr param_unprojector;
+  void setScene(SceneType* scene_) { _scene = scene_; }
+  void setMeasurement(const MeasurementType* measurement_) { _measurement = measurement_; }
+  void setCorrespondences(const CorrespondenceVector* correspondences_) { _correspondences = correspondences_; }
+  void setMeasurementInScene(const float* T16) { std::memcpy(_measurement_in_scene, T16, sizeof(_measurement_in_scene)); }
+  size_t numberOfMergedPoints() const { return _n_merged; }
+  size_t numberOfAddedPoints() const { return _n_added; }
+  void compute() {
+    if (!_scene) throw std::runtime_error("MergerCorrespondence::compute|ERROR: scene not set");
+    if (!_measurement) throw std::runtime_error("MergerCorrespondence::compute|ERROR: measurement not set");
+    if (!_correspondences) throw std::runtime_error("MergerCorrespondence::compute|ERROR: correspondences not set");
+    if (!param_unprojector) throw std::runtime_error("MergerCorrespondence::compute|ERROR: unprojector not set");
+    prs_closure_merger_params p;
+    std::memset(&p, 0, sizeof(p));
+    const float* K = param_unprojector->camera_matrix;
+    p.measurement_kind   = KIND_;
+    p.number_of_row_bins = (uint32_t) param_number_of_row_bins.value();
+    p.number_of_col_bins = (uint32_t) param_number_of_col_bins.value();
+    p.canvas_rows        = (int32_t) param_unprojector->param_canvas_rows.value();
+    p.canvas_cols        = (int32_t) param_unprojector->param_canvas_cols.value();
+    // (a merger whose canvas was never set cannot bin: the first gtest of the reference leaves it unset, tests/test_mergers.cpp:174-181)
+    p.enable_binning = param_enable_binning.value() && p.canvas_rows > 0 && p.canvas_cols > 0 ? 1 : 0;
+    p.fx = K[0];
+    p.fy = K[4];
+    p.cx = K[2];
+    p.cy = K[5];
+    p.maximum_distance_geometry_squared = param_maximum_distance_geometry_squared.value();
+    p.maximum_response                  = param_maximum_response.value();
+    p.target_number_of_merges           = (uint32_t) param_target_number_of_merges.value();
+    const size_t n = _scene->size(), nm = _measurement->size(), cap = n + nm + 1;
+    std::vector<float> xyz(4 * cap, 0.f), z(4 * (nm + 1), 0.f);
+    std::vector<uint8_t> desc(PRS_DESC_BYTES * cap, 0), zd(PRS_DESC_BYTES * (nm + 1), 0);
+    std::vector<uint32_t> nopt(cap, 0u);
+    for (size_t i = 0; i < n; ++i) {
+      std::memcpy(&xyz[4 * i], (*_scene)[i].coords, sizeof(float) * 3);
+      std::memcpy(&desc[PRS_DESC_BYTES * i], (*_scene)[i].descriptor_row, PRS_DESC_BYTES);
+      nopt[i] = (*_scene)[i].number_of_optimizations;
+    }
+    for (size_t i = 0; i < nm; ++i) {
+      std::memcpy(&z[4 * i], (*_measurement)[i].coords, sizeof(float) * 3);
+      std::memcpy(&zd[PRS_DESC_BYTES * i], (*_measurement)[i].descriptor_row, PRS_DESC_BYTES);
+    }
+    int32_t n_points = (int32_t) n;
+    prs_merge_result res;
+    const int rc = prs_closure_merge(_ctx->get(), &p, (int32_t) cap, &n_points, xyz.data(), desc.data(), nullptr, nullptr, nopt.data(), nullptr,
+                                     nullptr, nullptr, z.data(), zd.data(), (int32_t) nm,
+                                     reinterpret_cast<const prs_corr*>(_correspondences->data()), (int32_t) _correspondences->size(), 0,
+                                     _measurement_in_scene, 0, &res);
+    if (rc < 0) throw std::runtime_error(std::string("MergerCorrespondence::compute|ERROR: ") + prs_status_string(rc) + " " + prs_last_error(_ctx->get()));
+    _n_merged = (size_t) res.n_merged;
+    _n_added  = (size_t) res.n_added;
+    // the scene in place: element order intact, new points appended
+    _scene->resize((size_t) n_points);
+    for (int32_t i = 0; i < n_points; ++i) {
+      std::memcpy((*_scene)[(size_t) i].coords, &xyz[4 * (size_t) i], sizeof(float) * 3);
+      std::memcpy((*_scene)[(size_t) i].descriptor_row, &desc[PRS_DESC_BYTES * (size_t) i], PRS_DESC_BYTES);
+      (*_scene)[(size_t) i].number_of_optimizations = nopt[(size_t) i];
+    }
+  }
+
+protected:
+  ContextPtr _ctx;
+  SceneType* _scene                            = nullptr;
+  const MeasurementType* _measurement          = nullptr;
+  const CorrespondenceVector* _correspondences = nullptr;
+  float _measurement_in_scene[16];
+  size_t _n_merged = 0, _n_added = 0;
+};
+using MergerCorrespondencePointIntensityDescriptor3fHIP = MergerCorrespondenceHIP_<PRS_CLOSURE_XYZ>;
+using MergerCorrespondenceProjectiveDepth3DHIP          = MergerCorrespondenceHIP_<PRS_CLOSURE_UVD>;
+
 // ---- loop aligner -----------------------------------------------------------------------------------
 // MultiAligner3DQR "loop_aligner" with one AlignerSliceProcessor3D (registration/aligner_slice_processor_3d.hpp:7-22): point-to-point
 // SE(3) registration of two 3D clouds through given correspondences (SE3Point2PointErrorFactor, Omega = I3), plus the loop

@@ -387,6 +387,27 @@ class PoseGraphClosures(C.Structure):
                 ("node_of_query", C.c_void_p), ("node_of_map", C.c_void_p), ("status", C.c_void_p), ("n_appended", C.c_void_p)]
 
 
+CLOSURE_XYZ, CLOSURE_UVD = 0, 1  # PRS_CLOSURE_*
+
+
+class ClosureMergerParams(C.Structure):
+    """prs_closure_merger_params"""
+    _fields_ = [("measurement_kind", C.c_int32), ("enable_binning", C.c_int32), ("number_of_row_bins", C.c_uint32),
+                ("number_of_col_bins", C.c_uint32), ("canvas_rows", C.c_int32), ("canvas_cols", C.c_int32), ("fx", C.c_float),
+                ("fy", C.c_float), ("cx", C.c_float), ("cy", C.c_float), ("maximum_distance_geometry_squared", C.c_float),
+                ("maximum_response", C.c_float), ("target_number_of_merges", C.c_uint32)]
+
+
+class ClosureMergeBatch(C.Structure):
+    """prs_closure_merge_batch (device pointers)"""
+    _fields_ = [("batch", C.c_int32), ("capacity", C.c_int32), ("coords", C.c_void_p), ("desc", C.c_void_p), ("n_points", C.c_void_p),
+                ("state", C.c_void_p), ("covariance", C.c_void_p), ("n_opt", C.c_void_p), ("inlier", C.c_void_p), ("n_meas", C.c_void_p),
+                ("scene_in_world", C.c_void_p), ("measurement_stride", C.c_int32), ("corr_stride", C.c_int32),
+                ("measurement", C.c_void_p), ("measurement_desc", C.c_void_p), ("n_measured", C.c_void_p), ("corr", C.c_void_p),
+                ("n_corr", C.c_void_p), ("transform", C.c_void_p), ("gate", C.c_void_p), ("result", C.c_void_p),
+                ("corr_from_aligner", C.c_int32), ("transform_is_scene_in_measurement", C.c_int32)]
+
+
 MODE_ALIGN, MODE_FINDER, MODE_LINEARIZE = 0, 1, 2
 
 # every symbol include/proslam_hip.h declares: (restype, argtypes)
@@ -478,6 +499,12 @@ SYMBOLS = {
     "prs_map_set_frame_pose": (C.c_int, [_vp, C.c_int32, _vp]),
     "prs_map_merge": (C.c_int, [_vp, C.POINTER(MergerParams), _vp, _vp, _vp, _vp, C.c_int32, _vp, C.c_int32, _vp, C.c_int32, _vp]),
     "prs_map_get_scene": (C.c_int, [_vp, C.c_int32, _vp, _vp, _vp, _vp, _vp, _i32p]),
+    "prs_closure_merge_batch_run": (C.c_int, [_vp, C.POINTER(ClosureMergerParams), C.POINTER(ClosureMergeBatch)]),
+    "prs_closure_merge_struct_sizes": (None, [C.POINTER(C.c_uint64)]),
+    "prs_closure_merge": (C.c_int, [_vp, C.POINTER(ClosureMergerParams), C.c_int32, _i32p, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                    C.c_int32, _vp, C.c_int32, C.c_int32, _vp, C.c_int32, _vp]),
+    "prs_map_merge_closure": (C.c_int, [_vp, C.POINTER(ClosureMergerParams), _vp, C.c_int32, _vp, _vp, _vp, C.c_int32, _vp, C.c_int32,
+                                        C.c_int32, _vp]),
     "prs_scene_clip_batch": (C.c_int, [_vp, C.POINTER(Projector), _vp, C.POINTER(ClipBatch)]),
     "prs_scene_clip": (C.c_int, [_vp, C.POINTER(Projector), _vp, _vp, _vp, _vp, C.c_int32, _vp, _vp, _vp, C.c_int32, _i32p]),
 }

@@ -50,6 +50,14 @@ def _graph(algorithm, damping, lm=None):
     return out
 
 
+def _closure_merger():
+    """the tracker slice's closure_merger (include/proslam_hip.h prs_closure_*): a MergerCorrespondencePointIntensityDescriptor3f
+    with the same four values in every shipped file; the bin counts are the class defaults of merger_projective.h:47-56 (the
+    merger's own defaults live in srrg2_slam_interfaces, not in the tree), the canvas and camera matrix come from "camera"."""
+    return {"enable_binning": 1, "maximum_distance_geometry_squared": 0.25, "maximum_response": 50, "target_number_of_merges": 200,
+            "number_of_row_bins": 10, "number_of_col_bins": 30}
+
+
 # icl.conf:665-685 and tum.conf:174-194 (IterationAlgorithmLM), the same values: lm_iterations_max :669 / :178, step_high :672 / :181,
 # step_low :675 / :184, tau :678 / :187, user_lambda_init :681 / :190, variable_damping :684 / :193
 def _lm():
@@ -88,6 +96,7 @@ KITTI = {
     "place": _place(25.0, 10, 25),  # kitti.conf:938-978
     # kitti.conf:895-936 (global_solver) -> Solver :420-444, IterationAlgorithmGN :826-832, SimpleTerminationCriteria :884-889
     "graph": _graph("IterationAlgorithmGN", 1e-06),
+    "closure_merger": _closure_merger(),  # kitti.conf:335-337 (slice) -> :446-460
     "depth": {"min": 4.0, "max": 80.0},
 }
 
@@ -118,6 +127,7 @@ EUROC = {
     "loop": _loop("saturated", 1.0, 100, 0, 50.0, (100, 0.9, 0.25), (100, 0.9, 100.0)),
     "place": _place(50.0, 5, 100),  # euroc.conf: MultiLoopDetectorHBST3D
     "graph": _graph("IterationAlgorithmGN", 1e-06),  # euroc.conf:641-651 (MultiGraphSLAM3D -> global_solver)
+    "closure_merger": _closure_merger(),  # euroc.conf:898-900 (slice) -> :519
     "depth": {"min": 1.0, "max": 15.0},
 }
 
@@ -145,6 +155,7 @@ ICL = {
     "loop": _loop("clamp", 1.0, 10, 0, 35.0, (50, 0.5, 0.1), (100, 0.5, 1000.0)),
     "place": _place(35.0, 1, 50),  # icl.conf:197-240
     "graph": _graph("IterationAlgorithmLM", 1e-06, _lm()),  # icl.conf:797-807 (MultiGraphSLAM3D -> global_solver), LM :665-685
+    "closure_merger": _closure_merger(),  # icl.conf:178-180 (slice) -> :773
     "depth": {"min": 0.5, "max": 6.0},
     # RawDataPreprocessorMonocularDepth (icl.conf:642-650) and its IntensityFeatureExtractorBinned3D (icl.conf:745-770)
     "rgbd": {"depth_scaling_factor_to_meters": 0.001, "detector_threshold": 5, "enable_non_maximum_suppression": 1,
@@ -175,6 +186,7 @@ TUM = {
     "loop": _loop("clamp", 0.25, 10, 0, 25.0, (40, 0.5, 0.05), (40, 0.5, 100.0)),
     "place": _place(25.0, 1, 40),  # tum.conf: MultiLoopDetectorHBST3D
     "graph": _graph("IterationAlgorithmLM", 1e-06, _lm()),  # tum.conf:453-463 (MultiGraphSLAM3D -> global_solver), LM :174-194
+    "closure_merger": _closure_merger(),  # tum.conf:221-223 (slice) -> :437
     "depth": {"min": 0.5, "max": 6.0},
     # RawDataPreprocessorMonocularDepth (tum.conf:633-640) and its IntensityFeatureExtractorBinned3D (tum.conf:858-883)
     "rgbd": {"depth_scaling_factor_to_meters": 0.001, "detector_threshold": 5, "enable_non_maximum_suppression": 1,

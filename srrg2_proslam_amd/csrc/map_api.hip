@@ -451,6 +451,85 @@ int prs_map_merge(prs_map* h,
   return back.res.status;
 }
 
+int prs_map_merge_closure(prs_map* h, const prs_closure_merger_params* params, const float* transform16, int32_t transform_is_scene_in_measurement,
+                          const float* scene_in_world16, const float* measurement4, const uint8_t* measurement_desc, int32_t n_measured,
+                          const prs_corr* corr, int32_t n_corr, int32_t corr_from_aligner, prs_merge_result* result) {
+  if (!h) {
+    return PRS_ERR_NULL;
+  }
+  if (!params || !transform16) {
+    return fail(h, PRS_ERR_NULL, "prs_map_merge_closure: parameters / transform not set");
+  }
+  if (n_measured < 0 || (n_measured > 0 && (!measurement4 || !measurement_desc))) {
+    return fail(h, PRS_ERR_NULL, "prs_map_merge_closure: measurement not set");
+  }
+  if (n_corr < 0 || (n_corr > 0 && !corr)) {
+    return fail(h, PRS_ERR_NULL, "prs_map_merge_closure: correspondences not set");
+  }
+  if (n_measured > h->max_measured || n_corr > h->max_measured) {
+    return fail(h, PRS_ERR_CAPACITY, "prs_map_merge_closure: more measurements / correspondences than the handle was created for");
+  }
+  (void) hipSetDevice(h->ctx->device);
+  hipStream_t s = h->ctx->stream;
+  Small sm      = small_of(h->d_small);
+  if (n_measured > 0) {
+    MAP_TRY(hipMemcpyAsync(h->d_measurement, measurement4, (size_t) n_measured * 16, hipMemcpyHostToDevice, s));
+    MAP_TRY(hipMemcpyAsync(h->d_mdesc, measurement_desc, (size_t) n_measured * PRS_DESC_BYTES, hipMemcpyHostToDevice, s));
+  }
+  if (n_corr > 0) {
+    MAP_TRY(hipMemcpyAsync(h->d_corr, corr, (size_t) n_corr * sizeof(prs_corr), hipMemcpyHostToDevice, s));
+  }
+  static const float kIdentity[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
+  int32_t head[4] = {h->n_points, n_measured, n_corr, 0};
+  MAP_TRY(hipMemcpyAsync(h->d_small, head, sizeof(head), hipMemcpyHostToDevice, s));
+  MAP_TRY(hipMemcpyAsync(sm.in_world, scene_in_world16 ? scene_in_world16 : kIdentity, 64, hipMemcpyHostToDevice, s));
+  MAP_TRY(hipMemcpyAsync(sm.in_scene, transform16, 64, hipMemcpyHostToDevice, s));
+  prs_closure_merge_batch b;
+  memset(&b, 0, sizeof(b));
+  b.batch = 1;
+  b.capacity = h->capacity;
+  b.coords = h->d_coords;
+  b.desc = h->d_desc;
+  b.n_points = sm.n_points;
+  b.state = h->d_state;
+  b.covariance = h->d_cov;
+  b.n_opt = h->d_n_opt;
+  b.inlier = h->d_inlier;
+  b.n_meas = h->d_n_meas;
+  b.scene_in_world = sm.in_world;
+  b.measurement_stride = h->max_measured;
+  b.corr_stride = h->max_measured;
+  b.measurement = h->d_measurement;
+  b.measurement_desc = h->d_mdesc;
+  b.n_measured = sm.n_measured;
+  b.corr = h->d_corr;
+  b.n_corr = sm.n_corr;
+  b.transform = sm.in_scene;
+  b.result = sm.result;
+  b.corr_from_aligner = corr_from_aligner ? 1 : 0;
+  b.transform_is_scene_in_measurement = transform_is_scene_in_measurement ? 1 : 0;
+  const int rc = prs::closure_merge_launch(h->ctx, params, &b);
+  if (rc != PRS_OK) {
+    (void) hipStreamSynchronize(s);  // (copies from the caller's buffers may be in flight)
+    return rc;
+  }
+  struct {
+    int32_t n_points;
+    int32_t pad[3];
+    prs_merge_result res;
+  } back;
+  MAP_TRY(hipMemcpyAsync(&back, h->d_small, sizeof(back), hipMemcpyDeviceToHost, s));
+  MAP_TRY(hipStreamSynchronize(s));
+  if (result) {
+    *result = back.res;
+  }
+  if (back.res.status < 0) {
+    return fail(h, back.res.status, "prs_map_merge_closure: the merge kernel refused the pair (range, duplicate scene index or scene full)");
+  }
+  h->n_points = back.n_points;
+  return back.res.status;
+}
+
 int prs_map_get_scene(prs_map* h, int32_t capacity, float* coords_in_scene, float* state_in_world, uint8_t* desc, uint32_t* n_opt,
                       uint8_t* inlier, int32_t* n_points) {
   if (!h || !n_points) {

@@ -375,3 +375,20 @@ def graph_lm_params(conf):
     if algorithm is None or not algorithm.class_name.startswith("IterationAlgorithmLM"):
         return {}
     return _pick(algorithm, _GRAPH_LM)
+
+
+_CLOSURE_MERGER = ("enable_binning", "maximum_distance_geometry_squared", "maximum_response", "target_number_of_merges")
+
+
+def closure_merger_params(conf):
+    """the closure merger's parameter group of a parsed configuration (include/proslam_hip.h prs_closure_*), following the file's
+    own wiring: the tracker slice (the first record that holds a `closure_merger` pointer) -> that merger, a
+    MergerCorrespondencePointIntensityDescriptor3f in every shipped file; its class name under "class".  Only fields present in
+    the file are returned."""
+    for r in conf.records:
+        merger = conf.follow(r, "closure_merger")
+        if isinstance(merger, ConfRecord):
+            out = _pick(merger, _CLOSURE_MERGER)
+            out["class"] = merger.class_name
+            return out
+    return {}

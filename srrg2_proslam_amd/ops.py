@@ -1344,6 +1344,23 @@ class MapHandle:
         _check(self._ctx, rc, "prs_map_merge")
         return int(res[0]), int(res[1]), int(res[2])
 
+    def merge_closure(self, params, transform, measurement, measurement_desc, corr, scene_in_world=None, transform_is_scene_in_measurement=0,
+                      corr_from_aligner=0, check=True):
+        """the closure merger (closure_merger_params) on this map: measurement [n, 4] rows -> (n_merged, n_added, status).  The map's
+        statistics arrays are kept up; no frame is counted.  check=False returns a pair's error code instead of raising"""
+        z = _np(measurement, np.float32, (-1, 4))
+        d = _np(measurement_desc, np.uint8, (-1, 32))
+        c = np.ascontiguousarray(corr, dtype=CORR_DTYPE)
+        T = _np(transform, np.float32, (16,))
+        W = None if scene_in_world is None else _np(scene_in_world, np.float32, (16,))
+        res = (C.c_int32 * 3)()
+        rc = _lib.load().prs_map_merge_closure(self._h, C.byref(params), _p(T), int(transform_is_scene_in_measurement),
+                                               None if W is None else _p(W), _p(z) if len(z) else None, _p(d) if len(z) else None,
+                                               z.shape[0], _p(c) if len(c) else None, len(c), int(corr_from_aligner), res)
+        if check or rc != int(res[2]):
+            _check(self._ctx, rc, "prs_map_merge_closure")
+        return int(res[0]), int(res[1]), int(res[2])
+
     def scene(self):
         """-> dict(coords [n,3], state [n,3], desc [n,32], n_opt [n], inlier [n])"""
         cap = self.capacity
@@ -1354,6 +1371,165 @@ class MapHandle:
         _check(self._ctx, rc, "prs_map_get_scene")
         k = n.value
         return dict(coords=coords[:k].copy(), state=state[:k].copy(), desc=desc[:k].copy(), n_opt=n_opt[:k].copy(), inlier=inl[:k].copy())
+
+
+# ---- closure merger (the tracker slice's closure_merger: MergerCorrespondencePointIntensityDescriptor3f / ..ProjectiveDepth3D) ----
+CLOSURE_XYZ, CLOSURE_UVD = _lib.CLOSURE_XYZ, _lib.CLOSURE_UVD
+_CLOSURE_STATS = (("state", np.float32, 4), ("covariance", np.float32, 9), ("n_opt", np.uint32, 0), ("inlier", np.uint8, 0),
+                  ("n_meas", np.uint32, 0))
+
+
+def closure_merger_params(group, camera, measurement_kind="xyz", **overrides):
+    """prs_closure_merger_params from a configs.py `closure_merger` group and `camera` (canvas + camera matrix); measurement_kind
+    "xyz" (MergerCorrespondencePointIntensityDescriptor3f) or "uvd" (MergerCorrespondenceProjectiveDepth3D); overrides by field name"""
+    p = _lib.ClosureMergerParams()
+    p.measurement_kind = {"xyz": CLOSURE_XYZ, "uvd": CLOSURE_UVD}[measurement_kind]
+    p.enable_binning = int(group["enable_binning"])
+    p.number_of_row_bins, p.number_of_col_bins = int(group.get("number_of_row_bins", 10)), int(group.get("number_of_col_bins", 30))
+    p.canvas_rows, p.canvas_cols = int(camera["rows"]), int(camera["cols"])
+    p.fx, p.fy, p.cx, p.cy = camera["fx"], camera["fy"], camera["cx"], camera["cy"]
+    p.maximum_distance_geometry_squared = group["maximum_distance_geometry_squared"]
+    p.maximum_response = group["maximum_response"]
+    p.target_number_of_merges = int(group["target_number_of_merges"])
+    for k, v in overrides.items():
+        setattr(p, k, v)
+    return p
+
+
+def closure_merge(ctx, params, scene, measurement, measurement_desc, corr, transform, scene_in_world=None,
+                  transform_is_scene_in_measurement=0, corr_from_aligner=0, check=True):
+    """host arrays, one pair.  scene: dict(coords [capacity, 4], desc [capacity, 32], n_points, and any of state [capacity, 4],
+    covariance [capacity, 9], n_opt, inlier, n_meas [capacity]); measurement [n, 4] rows ((x, y, z, -) or (u, v, d, -)).
+    -> (scene after: a new dict, (n_merged, n_added, status)).  check=False returns a pair's error code instead of raising"""
+    out = dict(coords=_np(scene["coords"], np.float32, (-1, 4)).copy(), desc=_np(scene["desc"], np.uint8, (-1, 32)).copy())
+    cap = out["coords"].shape[0]
+    for name, dt, width in _CLOSURE_STATS:
+        if scene.get(name) is not None:
+            out[name] = _np(scene[name], dt, (cap, width) if width else (cap,)).copy()
+    z = _np(measurement, np.float32, (-1, 4))
+    d = _np(measurement_desc, np.uint8, (-1, 32))
+    c = np.ascontiguousarray(corr, dtype=CORR_DTYPE)
+    T = _np(transform, np.float32, (16,))
+    W = None if scene_in_world is None else _np(scene_in_world, np.float32, (16,))
+    n = C.c_int32(int(scene["n_points"]))
+    res = (C.c_int32 * 3)()
+    opt = lambda name: _p(out[name]) if name in out else None  # noqa: E731
+    rc = _lib.load().prs_closure_merge(ctx._h, C.byref(params), cap, C.byref(n), _p(out["coords"]), _p(out["desc"]), opt("state"),
+                                       opt("covariance"), opt("n_opt"), opt("inlier"), opt("n_meas"), None if W is None else _p(W),
+                                       _p(z) if len(z) else None, _p(d) if len(z) else None, z.shape[0], _p(c) if len(c) else None, len(c),
+                                       int(corr_from_aligner), _p(T), int(transform_is_scene_in_measurement), res)
+    if check or rc != int(res[2]):
+        _check(ctx, rc, "prs_closure_merge")
+    out["n_points"] = n.value
+    return out, (int(res[0]), int(res[1]), int(res[2]))
+
+
+class ClosureMergeBatch:
+    """B (scene, measurement cloud) pairs resident in HBM in the layout of prs_closure_merge_batch.  The tensors may be another
+    batch's: from_closures points them at a LoopClosureBatch so that the merger follows the matcher and the aligner on one stream."""
+
+    def __init__(self, device, batch, capacity, measurement_stride, corr_stride, with_stats=True, with_gate=False):
+        import torch
+        dev = torch.device("cuda", device)
+        z = lambda shape, dt: torch.zeros(shape, dtype=dt, device=dev)  # noqa: E731
+        self.batch, self.capacity = int(batch), int(capacity)
+        self.measurement_stride, self.corr_stride = int(measurement_stride), int(corr_stride)
+        self.coords, self.desc, self.n_points = z((batch, capacity, 4), torch.float32), z((batch, capacity, 32), torch.uint8), z((batch,), torch.int32)
+        self.state = z((batch, capacity, 4), torch.float32) if with_stats else None
+        self.covariance = z((batch, capacity, 9), torch.float32) if with_stats else None
+        self.n_opt = z((batch, capacity), torch.int32) if with_stats else None
+        self.inlier = z((batch, capacity), torch.uint8) if with_stats else None
+        self.n_meas = z((batch, capacity), torch.int32) if with_stats else None
+        self.scene_in_world = torch.eye(4, dtype=torch.float32, device=dev).reshape(1, 16).repeat(batch, 1).contiguous() if with_stats else None
+        self.measurement = z((batch, measurement_stride, 4), torch.float32)
+        self.measurement_desc = z((batch, measurement_stride, 32), torch.uint8)
+        self.n_measured = z((batch,), torch.int32)
+        self.corr, self.n_corr = z((batch, max(corr_stride, 1), 3), torch.int32), z((batch,), torch.int32)
+        self.transform = torch.eye(4, dtype=torch.float32, device=dev).reshape(1, 16).repeat(batch, 1).contiguous()
+        self.gate = z((batch, C.sizeof(_lib.PointAlignResult) // 4), torch.int32) if with_gate else None
+        self.result = z((batch, 3), torch.int32)
+        self.corr_from_aligner, self.transform_is_scene_in_measurement = 0, 0
+
+    @classmethod
+    def from_closures(cls, closures):
+        """the merger's batch over the tensors of a LoopClosureBatch that has run (or is enqueued): nothing is copied.  The scene is
+        the candidate map (the aligner's MOVING cloud and descriptors, capacity = moving_stride, count = pairs.n_moving, which
+        grows), the measurement the query (its FIXED cloud); corr / n_corr are the matcher's (corr_from_aligner = 1); transform is
+        the aligner's X, movingInFixed = scene-in-measurement, so the inverse flag is set; the gate is the aligner's verdict."""
+        import torch
+        self = cls.__new__(cls)
+        pairs, clouds = closures.pairs, closures.clouds
+        self.batch, self.capacity = pairs.batch, pairs.moving_stride
+        self.measurement_stride, self.corr_stride = pairs.fixed_stride, pairs.corr_stride
+        self.coords, self.desc, self.n_points = pairs.moving, clouds.moving_desc, pairs.n_moving
+        self.state = self.covariance = self.n_opt = self.inlier = self.n_meas = self.scene_in_world = None
+        self.measurement, self.measurement_desc, self.n_measured = pairs.fixed, clouds.fixed_desc, pairs.n_fixed
+        self.corr, self.n_corr = pairs.corr, pairs.n_corr
+        self.transform, self.gate = pairs.X, pairs.result
+        self.result = torch.zeros((pairs.batch, 3), dtype=torch.int32, device=pairs.moving.device)
+        self.corr_from_aligner, self.transform_is_scene_in_measurement = 1, 1
+        return self
+
+    def upload(self, b, scene, measurement, measurement_desc, corr, transform, scene_in_world=None, accepted=None, n_measured=None,
+               n_corr=None):
+        """scene: the dict closure_merge takes (arrays of `capacity` rows).  n_measured / n_corr override the counts (tests of the
+        count checks); accepted sets the gate's verdict for the pair"""
+        import torch
+        dev = self.coords.device
+        put = lambda t, a: t.__setitem__(b, torch.from_numpy(np.ascontiguousarray(a)).to(dev))  # noqa: E731
+        put(self.coords, _np(scene["coords"], np.float32, (self.capacity, 4)))
+        put(self.desc, _np(scene["desc"], np.uint8, (self.capacity, 32)))
+        self.n_points[b] = int(scene["n_points"])
+        for name, dt, width in _CLOSURE_STATS:
+            t = getattr(self, name)
+            if t is not None and scene.get(name) is not None:
+                a = _np(scene[name], dt, (self.capacity, width) if width else (self.capacity,))
+                put(t, a.view(np.int32) if dt == np.uint32 else a)
+        z, d = _np(measurement, np.float32, (-1, 4)), _np(measurement_desc, np.uint8, (-1, 32))
+        if len(z):
+            self.measurement[b, : len(z)] = torch.from_numpy(z).to(dev)
+            self.measurement_desc[b, : len(z)] = torch.from_numpy(d).to(dev)
+        self.n_measured[b] = len(z) if n_measured is None else int(n_measured)
+        c = np.ascontiguousarray(corr, dtype=CORR_DTYPE)
+        if len(c):
+            self.corr[b, : len(c)] = torch.from_numpy(c.view(np.int32).reshape(-1, 3).copy()).to(dev)
+        self.n_corr[b] = len(c) if n_corr is None else int(n_corr)
+        put(self.transform, _np(transform, np.float32, (16,)))
+        if self.scene_in_world is not None:
+            put(self.scene_in_world, _np(np.eye(4) if scene_in_world is None else scene_in_world, np.float32, (16,)))
+        if self.gate is not None:
+            self.gate[b, _lib.PointAlignResult.accepted.offset // 4] = 1 if accepted is None else int(accepted)
+
+    def descriptor(self):
+        d = _lib.ClosureMergeBatch()
+        d.batch, d.capacity, d.measurement_stride, d.corr_stride = self.batch, self.capacity, self.measurement_stride, self.corr_stride
+        for name in ("coords", "desc", "n_points", "state", "covariance", "n_opt", "inlier", "n_meas", "scene_in_world", "measurement",
+                     "measurement_desc", "n_measured", "corr", "n_corr", "transform", "gate", "result"):
+            t = getattr(self, name)
+            setattr(d, name, t.data_ptr() if t is not None else None)
+        d.corr_from_aligner, d.transform_is_scene_in_measurement = int(self.corr_from_aligner), int(self.transform_is_scene_in_measurement)
+        return d
+
+    def result_of(self, b):
+        """-> (n_merged, n_added, status)"""
+        return tuple(int(v) for v in self.result[b].cpu().numpy())
+
+    def scene_of(self, b):
+        """the scene of pair b in the dict layout of closure_merge (whole capacity)"""
+        out = dict(coords=self.coords[b].cpu().numpy().copy(), desc=self.desc[b].cpu().numpy().copy(), n_points=int(self.n_points[b].item()))
+        for name, dt, _ in _CLOSURE_STATS:
+            t = getattr(self, name)
+            if t is not None:
+                out[name] = t[b].cpu().numpy().view(dt).copy()
+        return out
+
+
+def closure_merge_batch(ctx, params, pairs):
+    """enqueue the closure merger for every pair of the batch on the context stream (asynchronous, one launch)"""
+    d = pairs.descriptor()
+    rc = _lib.load().prs_closure_merge_batch_run(ctx._h, C.byref(params), C.byref(d))
+    _check(ctx, rc, "prs_closure_merge_batch_run")
+    return rc
 
 
 def pose_compose_batch(ctx, prediction, X, pose_out):
