@@ -132,6 +132,26 @@ def query_loop(db, P, graph_id, desc, valid=None):
     return cands[: P["max_candidates"]], corr[: P["max_candidates"]], counts
 
 
+def gather_pairs(db, result, desc, xyz, valid, max_candidates):
+    """what prs_place_gather_pairs promises for one query: `max_candidates` slots of dict(fixed_desc, fixed_xyz, n_fixed, moving_desc,
+    moving_xyz, n_moving, X).  Slot k < len(result["candidates"]) holds the query's Valid descriptors and points in index order
+    (fixed) and the stored rows of candidate k (moving); every other slot has both counts 0.  X is the identity in every slot."""
+    desc = np.ascontiguousarray(desc, np.uint8).reshape(-1, 32)
+    xyz = np.zeros((len(desc), 3), np.float32) if xyz is None else np.asarray(xyz, np.float32).reshape(-1, 3)
+    qv = np.arange(len(desc)) if valid is None else np.flatnonzero(np.asarray(valid)[: len(desc)] != 0)
+    empty = dict(fixed_desc=desc[:0], fixed_xyz=xyz[:0], n_fixed=0, moving_desc=desc[:0], moving_xyz=xyz[:0], n_moving=0)
+    slots = []
+    for k in range(max_candidates):
+        slot = dict(empty)
+        if k < len(result["candidates"]):
+            m = db.maps[result["candidates"][k]]
+            slot.update(fixed_desc=desc[qv], fixed_xyz=xyz[qv], n_fixed=len(qv), moving_desc=m["desc"], moving_xyz=m["xyz"],
+                        n_moving=len(m["desc"]))
+        slot["X"] = np.eye(4, dtype=np.float32)
+        slots.append(slot)
+    return slots
+
+
 # ------------------------------------------------------------------------------------------------------------ scenarios
 def recognition_3d(B):
     """test_place_recognition.cpp 3D cases: (name, map 0 desc, query desc, thr, min_inliers, pinned correspondence count | None)"""

@@ -10,6 +10,7 @@ import pytest
 
 import place_ref as pr
 import point_align_ref as par
+from place_cases import Pair, assert_same, batch_query, both_entries, cparams
 from srrg2_proslam_amd import _lib, configs
 
 pytestmark = pytest.mark.gpu
@@ -27,54 +28,6 @@ def env():
     ctx = ops.Context(0)
     yield ctx, ops, OracleBackend()
     ctx.close()
-
-
-class Pair:
-    """the device database and the checker's, kept in step"""
-
-    def __init__(self, ctx, ops):
-        self.dev, self.ref = ops.PlaceDatabase(ctx), pr.Database()
-
-    def add(self, gid, desc, xyz=None, valid=None):
-        self.dev.add(gid, desc, xyz, valid)
-        self.ref.add(gid, desc, valid, xyz)
-
-
-def cparams(p):
-    return pr.params(p.maximum_descriptor_distance, p.minimum_age_difference_to_candidates, p.relocalize_min_inliers, p.max_candidates)
-
-
-def assert_same(got, want, what=""):
-    assert got["status"] == want["status"], (what, got["status"], want["status"])
-    assert got["candidates"] == want["candidates"], (what, got["candidates"], want["candidates"])
-    if want["status"] >= 0 and want["status"] != pr.WARN_EMPTY_INPUT:
-        assert np.array_equal(np.asarray(got["counts"], np.int64), want["counts"]), what
-    assert len(got["corr"]) == len(want["corr"]), what
-    for a, b in zip(got["corr"], want["corr"]):
-        assert len(a) == len(b), (what, len(a), len(b))
-        for k in ("fixed_idx", "moving_idx"):
-            assert np.array_equal(a[k], b[k]), (what, k)
-        assert np.array_equal(a["response"].astype(np.float32).view(np.uint32), b["response"].astype(np.float32).view(np.uint32)), what
-
-
-def batch_query(ctx, ops, pair, P, items, query_stride=None, with_valid=False, corr_stride=None):
-    """items: (graph_id, desc[, valid]) -> per-query result dicts of the batch entry"""
-    qs = query_stride or max(max(len(i[1]) for i in items), 1)
-    q = ops.PlaceQueries(0, len(items), qs, P.max_candidates, pair.dev, with_valid=with_valid, corr_stride=corr_stride)
-    for b, it in enumerate(items):
-        q.upload(b, it[0], it[1], None, it[2] if len(it) > 2 else None)
-    ops.place_query_batch(ctx, pair.dev, P, q)
-    ctx.synchronize()
-    return [q.result_of(b, pair.dev.size()[0]) for b in range(len(items))]
-
-
-def both_entries(ctx, ops, pair, P, gid, desc, valid=None, what=""):
-    want = pair.ref.query(cparams(P), gid, desc, valid)
-    got_b = batch_query(ctx, ops, pair, P, [(gid, desc, valid)], with_valid=valid is not None)[0]
-    assert_same(got_b, want, what + " batch")
-    if want["status"] >= 0:
-        assert_same(pair.dev.query(P, gid, desc, valid), want, what + " host")
-    return want
 
 
 def near(rng, base, n, flips):
