@@ -505,6 +505,9 @@ PRS_API void prs_info_scale_from_nopt(const uint32_t* n_opt, int32_t n, float* s
  * aligner's `moving` arrays, so it can be consumed in place.
  * Status per scene: PRS_WARN_EMPTY_INPUT for an empty full scene (outputs AND n_clipped left
  * untouched, like the reference :21-28), PRS_WARN_NO_PROJECTION when nothing survives (:55-58).
+ * n_scene[b] above `stride` is read as `stride` (a scene owns `stride` rows of every array and no
+ * row beyond them is read or written); n_scene[b] below zero is read as zero, an empty scene.
+ * Rows at and past n_clipped[b] of the three output arrays are not written.
  * ============================================================================================== */
 typedef struct {
   int32_t batch;                   /* independent scenes (one per sequence) */

@@ -63,7 +63,9 @@ def test_sparse_with_descriptors_and_sensor_offset(oracle, hip_ctx):
             assert ref[3] == got[3]
 
 
-def test_batched_walk_ragged_empty_and_blind_scenes(oracle, hip_ctx):
+def test_batched_ragged_empty_and_blind_scenes_count_and_scatter(oracle, hip_ctx):
+    # 9 scenes at stride 3000 are three tiles in a batch below 128: the launcher takes count + scatter, not the walk
+    # (the walk with more than two tiles is tested in tests/test_scene_clip_edges_gpu.py)
     rng = np.random.default_rng(3)
     full = hp.icl_dense_scene(4)
     sizes = [0, 1, 700, 2000, 2600, 3000, 1024, 0, 2048]
