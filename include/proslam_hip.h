@@ -115,7 +115,8 @@ PRS_API int prs_version(void);
  * prs_pose_graph_params, prs_pose_graph_result, prs_pose_graphs, prs_pose_graph_closures, the prs_pose_graph_* entry points and the
  * status PRS_ERR_NOT_POSITIVE_DEFINITE; and its Levenberg-Marquardt form: prs_pose_graph_lm_params, prs_pose_graph_lm_result and the
  * prs_pose_graph_lm_* / prs_pose_graph_optimize_lm* entry points; and the closure merger: prs_closure_merger_params,
- * prs_closure_merge_batch, the prs_closure_merge* entry points and prs_map_merge_closure).  Callers memset() parameter structs before
+ * prs_closure_merge_batch, the prs_closure_merge* entry points and prs_map_merge_closure; and the local-map manager:
+ * prs_session_params, prs_session_batch and the prs_session_* entry points).  Callers memset() parameter structs before
  * filling them, so that fields they do not know select the shipped defaults (all zero). */
 #define PRS_ABI_VERSION 104
 PRS_API int prs_abi_check(int32_t header_version, uint64_t sizeof_stereo_params, uint64_t sizeof_pcf_params, uint64_t sizeof_aligner_params,
@@ -1528,6 +1529,125 @@ PRS_API int prs_map_merge_closure(prs_map* h, const prs_closure_merger_params* p
                                   int32_t transform_is_scene_in_measurement, const float* scene_in_world16, const float* measurement4,
                                   const uint8_t* measurement_desc, int32_t n_measured, const prs_corr* corr, int32_t n_corr,
                                   int32_t corr_from_aligner, prs_merge_result* result);
+
+/* ================================================================================================
+ * Local-map manager: per-sequence splits, pose-graph growth and trajectories (the loop around the tracker)
+ * replaces the bookkeeping of SLAMBenchmark::benchmarkCompute between tracker->align() and tracker->merge()
+ * (apps/app_benchmark.cpp:100-183): the trajectory log (:107-121), the switch on the tracker's status (:123-178) with
+ * LocalMapSplittingCriterionViewpoint3D (kitti.conf:542-550) and makeNewMap(1) / makeNewMap(0.1), and unrollFullTrajectory
+ * (:195-203).  One launch per frame between prs_align_batch_run and prs_merge_batch_run; it stands where prs_pose_compose_batch,
+ * the copy of the previous pose, prs_motion_predict_batch and the copies into the merger's two pose arrays stood.
+ *
+ * BUILD-DEFINED: makeNewMap, the MultiTracker status and the criterion class live in srrg2_slam_interfaces, which is not in the
+ * tree.  The rule below is this build's; tests/session_ref.py restates it in numpy and the kernels equal that bit for bit.  Float32
+ * expressions are explicit two-operand operations in the order written (csrc/prs_se3.h: se3_inverse, se3_mul, motion_predict).
+ * Per sequence b, with k = n_frames[b]:
+ *   frame 0      k == 0: pose = prev = I, no criterion, frame[b] = 0, n_corr_merge[b] = 0, the log gets (cur_node[b], I).  Graph b is
+ *                expected to hold node 0 with X = I, fixed = 1, n_nodes = 1, n_edges = 0 and cur_node[b] = 0.
+ *   pose         lost = result[b].status != 1 or result[b].warnings < 0.  Not lost: pose_new = prediction * X^-1 (the expressions of
+ *                prs_pose_compose_batch).  Lost: pose_new = prediction -- a failed alignment never enters the pose (the reference's
+ *                finder resets its estimate to identity on total loss).  prev_new = pose (the old one).
+ *   log          before the switch, as :107-121: frame_node[b][k] = cur_node[b], frame_pose[b][k] = pose_new.  On a split frame the
+ *                logged pose is relative to the OLD map.
+ *   criterion    t2 = (tx tx + ty ty) + tz tz and c = (((r00 + r11) + r22) - 1) * 0.5f of pose_new.  Viewpoint split iff t2 > d2 or
+ *                c < cos_a, both strict; the launcher forms d2 = local_map_distance * local_map_distance in float and cos_a =
+ *                (float) cos((double) local_map_angle_distance_radians), and an angle >= pi never splits by rotation (cos_a = -inf).
+ *                No acos on the device: a restatement decides the same bits.
+ *   split        reason 2 (lost, information = lost_information, makeNewMap(0.1)) goes before reason 1 (viewpoint, information =
+ *                split_information, makeNewMap(1)).  New node m = n_nodes[b]: X[m] = X[cur_node] * (double) pose_new (float64, the
+ *                expressions of se3_mul), fixed[m] = 0; new edge n_edges[b]: from = cur_node, to = m, Z = pose_new, omega =
+ *                information * I6; n_nodes++, n_edges++, cur_node = m.  Rebase: prev = pose_new^-1 * prev_new, pose = I.  The
+ *                finished map is handed over (below), then reset: n_points[b] = 0, n_meas[b][0 .. capacity) = 0.  frame[b] = 0 and
+ *                n_corr_merge[b] = 0: the frame's measurements seed the new map in the one merge that follows.
+ *   no split     frame[b] = slot[b], n_corr_merge[b] = n_corr[b], pose = pose_new, prev = prev_new.
+ *   after either slot[b] = frame[b] + 1, n_frames[b]++, prediction = the constant-velocity prediction of (prev, pose) (the function of
+ *                prs_motion_predict_batch), measurement_in_world[b] = measurement_in_scene[b] = pose.
+ *   hand-over    optional (handover_desc != NULL), prs_place_queries-shaped: on a split rows [0, n_points) of coords and desc are
+ *                copied to handover_xyz[b] / handover_desc[b], handover_n_query[b] = n_points, handover_graph_id[b] =
+ *                graph_id_base[b] (0 without the array) + the old node; with no split (or an error) handover_n_query[b] = 0, which
+ *                prs_place_query_batch answers with PRS_WARN_EMPTY_INPUT and no candidates.
+ * status[b] and reason[b] (PRS_SESSION_*: the split performed):
+ *   PRS_ERR_RANGE     a negative n_frames, slot, cur_node, n_nodes, n_edges or n_points, cur_node >= n_nodes, n_nodes > node_stride,
+ *                     n_edges > edge_stride or n_points > capacity: nothing but status, reason and handover_n_query is written.
+ *   PRS_ERR_CAPACITY  a split needs a node beyond node_stride or an edge beyond edge_stride: the split is not performed (reason 0)
+ *                     and the sequence goes on in its map (the no-split branch, with pose_new as computed).  Also n_frames[b] >=
+ *                     frame_stride: the step runs and only the log row is skipped.
+ *   PRS_OK            otherwise.  A sequence never writes outside its rows, whatever its status.
+ * Call-level (return value, nothing launched): PRS_ERR_NULL (a mandatory pointer unset; handover_xyz / _n_query / _graph_id are
+ * mandatory once handover_desc is set), PRS_ERR_CAPACITY (handover_stride < capacity), PRS_ERR_RANGE (a stride or capacity below 1, a
+ * parameter that is not finite or a negative distance), PRS_ERR_UNSUPPORTED (coords, desc, handover_xyz or handover_desc not 16-byte
+ * aligned, graph_X not 8-byte aligned, or graphs without omega and an information other than 1).
+ * One 256-thread workgroup per sequence, no allocation, no synchronisation, no host read: graph-capturable.
+ *
+ * prs_session_unroll_batch: out[b][k] = (float) X[b][frame_node[b][k]] * frame_pose[b][k] for k < min(n_frames[b], frame_stride), float32
+ * se3_mul as unrollFullTrajectory composes Isometry3f; rows from n_frames[b] on, and rows whose node is outside [0, node_stride), are
+ * left untouched.  Before or after prs_pose_graph_optimize*_batch it gives the open-loop or the optimised trajectory.
+ * ============================================================================================== */
+enum { PRS_SESSION_NO_SPLIT = 0, PRS_SESSION_SPLIT_VIEWPOINT = 1, PRS_SESSION_SPLIT_LOST = 2 };
+
+typedef struct {
+  float local_map_distance;               /* kitti.conf:549 (10), euroc.conf:638 (1), icl.conf:553 (5), tum.conf:546 (1) */
+  float local_map_angle_distance_radians; /* kitti.conf:546 (0.25), euroc.conf:635 (0.5), icl.conf:550 (3), tum.conf:543 (0.25) */
+  float split_information;                /* makeNewMap(1), apps/app_benchmark.cpp:143 */
+  float lost_information;                 /* makeNewMap(0.1), :167 */
+} prs_session_params;
+
+/* B sequences; device pointers.  The arrays of the aligner (prs_align_batch), the merger (prs_merge_batch) and the pose graphs
+ * (prs_pose_graphs) are those structs' own arrays. */
+typedef struct {
+  int32_t batch;
+  int32_t frame_stride;        /* log rows per sequence */
+  int32_t capacity;            /* landmarks per map (prs_merge_batch.capacity) */
+  int32_t node_stride;         /* prs_pose_graphs.node_stride */
+  int32_t edge_stride;         /* prs_pose_graphs.edge_stride */
+  int32_t handover_stride;     /* rows per hand-over slot, >= capacity */
+  /* the session's own state */
+  float* pose;                 /* [batch][16] sensor in the current local map */
+  float* prev;                 /* [batch][16] the pose one frame earlier, in the same map */
+  float* prediction;           /* [batch][16] in: the prediction the frame was aligned at; out: the next frame's */
+  int32_t* slot;               /* [batch] pose-table slot the next frame of the map takes */
+  int32_t* cur_node;           /* [batch] node of the current local map */
+  int32_t* n_frames;           /* [batch] frames stepped */
+  int32_t* frame_node;         /* [batch][frame_stride] */
+  float* frame_pose;           /* [batch][frame_stride][16] */
+  int32_t* status;             /* out [batch] */
+  int32_t* reason;             /* out [batch] PRS_SESSION_* */
+  /* the aligner's outputs */
+  const float* X;              /* [batch][16] */
+  const prs_align_result* result; /* [batch] */
+  const int32_t* n_corr;       /* [batch] */
+  /* the map and the merger's per-frame inputs */
+  const float* coords;         /* [batch][capacity][4] */
+  const uint8_t* desc;         /* [batch][capacity][32] */
+  int32_t* n_points;           /* [batch] */
+  uint32_t* n_meas;            /* [batch][capacity] */
+  int32_t* frame;              /* out [batch] prs_merge_batch.frame */
+  int32_t* n_corr_merge;       /* out [batch] prs_merge_batch.n_corr */
+  float* measurement_in_world; /* out [batch][16] */
+  float* measurement_in_scene; /* out [batch][16] */
+  /* the pose graphs */
+  double* graph_X;             /* [batch][node_stride][16] */
+  uint8_t* fixed;              /* [batch][node_stride] */
+  int32_t* n_nodes;            /* [batch] */
+  int32_t* from;               /* [batch][edge_stride] */
+  int32_t* to;                 /* [batch][edge_stride] */
+  float* Z;                    /* [batch][edge_stride][16] */
+  float* omega;                /* [batch][edge_stride][36], or NULL (both informations must be 1) */
+  int32_t* n_edges;            /* [batch] */
+  /* optional hand-over of a finished map to the loop detector (prs_place_queries.desc / xyz / n_query / graph_id) */
+  uint8_t* handover_desc;      /* [batch][handover_stride][32] */
+  float* handover_xyz;         /* [batch][handover_stride][4] */
+  int32_t* handover_n_query;   /* [batch] */
+  int64_t* handover_graph_id;  /* [batch] */
+  const int64_t* graph_id_base; /* optional [batch] */
+} prs_session_batch;
+
+/* device pointers, asynchronous on the context's stream: one kernel launch each */
+PRS_API int prs_session_step_batch(prs_context* ctx, const prs_session_params* params, const prs_session_batch* batch);
+/* out [batch][frame_stride][16] */
+PRS_API int prs_session_unroll_batch(prs_context* ctx, const prs_session_batch* batch, float* out);
+/* sizeof prs_session_params, prs_session_batch as the library was compiled (bindings check) */
+PRS_API void prs_session_struct_sizes(uint64_t* sizes2);
 
 #ifdef __cplusplus
 }

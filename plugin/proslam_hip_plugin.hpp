@@ -22,6 +22,8 @@
 //     (registration/aligner_slice_processor_3d.hpp:7-22, the relocalize_aligner of the loop detector)
 //   CorrespondenceFinderHBST_ (the loop detector's candidate search) -> CorrespondenceFinderPlaceHIP
 //     (registration/correspondence_finders/correspondence_finder_hbst.{h,cpp}; exhaustive search in place of the HBST tree)
+//   SLAMBenchmark::benchmarkCompute's status switch + LocalMapSplittingCriterionViewpoint3D -> LocalMapManagerHIP
+//     (apps/app_benchmark.cpp:100-183; only with PROSLAM_HIP_WITH_HIP_RUNTIME: it owns device arrays, so it needs the HIP runtime)
 //
 // When the srrg2 headers are available the same bodies become real plugin subclasses: see
 // INTEGRATION.md for the BOSS_REGISTER_CLASS adapters.  Points are AoS like the reference's
@@ -39,6 +41,9 @@
 #include <vector>
 
 #include "proslam_hip.h"
+#ifdef PROSLAM_HIP_WITH_HIP_RUNTIME
+#include <hip/hip_runtime_api.h>
+#endif
 
 namespace proslam_hip {
 
@@ -1443,5 +1448,155 @@ protected:
   prs_pose_graph_lm_result _lm_result = {};
   bool _ran_lm = false;
 };
+
+#ifdef PROSLAM_HIP_WITH_HIP_RUNTIME
+// ------------------------------------------------------------------------------------------------
+// The local-map manager at B = 1: the block of SLAMBenchmark::benchmarkCompute between tracker->align() and tracker->merge()
+// (apps/app_benchmark.cpp:100-183) over prs_session_step_batch.  The trajectory log (:107-121), the switch on the tracker's status
+// (:123-178), LocalMapSplittingCriterionViewpoint3D's compute() / hasToSplit() and makeNewMap(1) / makeNewMap(0.1) are one call,
+// step(); unrollFullTrajectory() (:195-203) is the other.  The session entries take device arrays only, so this adapter owns them
+// (one allocation): the session's state, the aligner's three outputs, a local map's coords / desc / counters of `capacity` rows, the
+// merger's per-frame inputs and one pose graph.  A caller whose merger runs on the device points it at batch()'s map arrays.
+class LocalMapManagerHIP {
+public:
+  PropertyFloat param_local_map_distance{10.f};                // LocalMapSplittingCriterionViewpoint3D (kitti.conf:549)
+  PropertyFloat param_local_map_angle_distance_radians{0.25f}; // (kitti.conf:546)
+  PropertyFloat param_split_information{1.f};                  // makeNewMap(1)
+  PropertyFloat param_lost_information{0.1f};                  // makeNewMap(0.1)
+
+  LocalMapManagerHIP(ContextPtr ctx, int capacity, int node_stride, int edge_stride, int frame_stride) : _ctx(std::move(ctx)) {
+    if (capacity < 1 || node_stride < 1 || edge_stride < 1 || frame_stride < 1) {
+      throw std::runtime_error("LocalMapManagerHIP|ERROR: a size below 1");
+    }
+    std::memset(&_b, 0, sizeof(_b));
+    _b.batch = 1, _b.frame_stride = frame_stride, _b.capacity = capacity, _b.node_stride = node_stride, _b.edge_stride = edge_stride;
+    size_t end = 0;
+    auto take = [&end](size_t bytes) {
+      const size_t at = end;
+      end += (bytes + 255) / 256 * 256;
+      return at;
+    };
+    const size_t o_pose = take(64), o_prev = take(64), o_pred = take(64), o_slot = take(4), o_cur = take(4), o_nf = take(4),
+                 o_fnode = take(4 * (size_t) frame_stride), o_fpose = take(64 * (size_t) frame_stride), o_status = take(4), o_reason = take(4),
+                 o_X = take(64), o_res = take(sizeof(prs_align_result)), o_ncorr = take(4), o_coords = take(16 * (size_t) capacity),
+                 o_desc = take(32 * (size_t) capacity), o_np = take(4), o_nm = take(4 * (size_t) capacity), o_frame = take(4),
+                 o_ncm = take(4), o_miw = take(64), o_mis = take(64), o_gx = take(128 * (size_t) node_stride), o_fixed = take(node_stride),
+                 o_nn = take(4), o_from = take(4 * (size_t) edge_stride), o_to = take(4 * (size_t) edge_stride),
+                 o_Z = take(64 * (size_t) edge_stride), o_om = take(144 * (size_t) edge_stride), o_ne = take(4),
+                 o_traj = take(64 * (size_t) frame_stride);
+    _bytes = end;
+    if (hipMalloc(&_block, _bytes) != hipSuccess) throw std::runtime_error("LocalMapManagerHIP|ERROR: device allocation failed");
+    char* d = static_cast<char*>(_block);
+    _b.pose = (float*) (d + o_pose), _b.prev = (float*) (d + o_prev), _b.prediction = (float*) (d + o_pred);
+    _b.slot = (int32_t*) (d + o_slot), _b.cur_node = (int32_t*) (d + o_cur), _b.n_frames = (int32_t*) (d + o_nf);
+    _b.frame_node = (int32_t*) (d + o_fnode), _b.frame_pose = (float*) (d + o_fpose);
+    _b.status = (int32_t*) (d + o_status), _b.reason = (int32_t*) (d + o_reason);
+    _b.X = (const float*) (d + o_X), _b.result = (const prs_align_result*) (d + o_res), _b.n_corr = (const int32_t*) (d + o_ncorr);
+    _b.coords = (const float*) (d + o_coords), _b.desc = (const uint8_t*) (d + o_desc), _b.n_points = (int32_t*) (d + o_np);
+    _b.n_meas = (uint32_t*) (d + o_nm), _b.frame = (int32_t*) (d + o_frame), _b.n_corr_merge = (int32_t*) (d + o_ncm);
+    _b.measurement_in_world = (float*) (d + o_miw), _b.measurement_in_scene = (float*) (d + o_mis);
+    _b.graph_X = (double*) (d + o_gx), _b.fixed = (uint8_t*) (d + o_fixed), _b.n_nodes = (int32_t*) (d + o_nn);
+    _b.from = (int32_t*) (d + o_from), _b.to = (int32_t*) (d + o_to), _b.Z = (float*) (d + o_Z), _b.omega = (float*) (d + o_om);
+    _b.n_edges = (int32_t*) (d + o_ne);
+    _trajectory = (float*) (d + o_traj);
+    reset();
+  }
+  ~LocalMapManagerHIP() {
+    if (_block) (void) hipFree(_block);
+  }
+  LocalMapManagerHIP(const LocalMapManagerHIP&) = delete;
+  LocalMapManagerHIP& operator=(const LocalMapManagerHIP&) = delete;
+
+  // the first local map: the graph holds node 0 alone (identity, fixed); the next step() is frame 0
+  void reset() {
+    prs_context_synchronize(_ctx->get());
+    check(hipMemset(_block, 0, _bytes), "reset");
+    static const float eye[16]   = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
+    static const double eye_d[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
+    up(_b.pose, eye, 64), up(_b.prev, eye, 64), up(_b.prediction, eye, 64);
+    up(_b.graph_X, eye_d, 128);
+    const uint8_t one_u8 = 1;
+    const int32_t one    = 1;
+    up(_b.fixed, &one_u8, 1), up(_b.n_nodes, &one, 4);
+  }
+
+  // one frame: `X16` is the aligner's estimate (moving in fixed, relative to the prediction the local map was clipped at),
+  // `status` TrackerBase-like (1 = the alignment succeeded), `warnings` the aligner's word (negative = error).  Logs the pose,
+  // evaluates the criterion, makes the new map on a split or a loss.  Synchronises; returns the split made (PRS_SESSION_*).
+  int step(const float* X16, int status, int warnings, int n_corr = 0) {
+    prs_align_result r;
+    std::memset(&r, 0, sizeof(r));
+    r.status = status, r.warnings = warnings;
+    const int32_t nc = n_corr;
+    up(const_cast<float*>(_b.X), X16, 64), up(const_cast<prs_align_result*>(_b.result), &r, sizeof(r)), up(const_cast<int32_t*>(_b.n_corr), &nc, 4);
+    prs_session_params p;
+    std::memset(&p, 0, sizeof(p));
+    p.local_map_distance               = param_local_map_distance.value();
+    p.local_map_angle_distance_radians = param_local_map_angle_distance_radians.value();
+    p.split_information                = param_split_information.value();
+    p.lost_information                 = param_lost_information.value();
+    const int rc = prs_session_step_batch(_ctx->get(), &p, &_b);
+    if (rc < 0) throw std::runtime_error(std::string("LocalMapManagerHIP::step|ERROR: ") + prs_last_error(_ctx->get()));
+    prs_context_synchronize(_ctx->get());
+    _status = word(_b.status);
+    _reason = word(_b.reason);
+    if (_status == PRS_ERR_RANGE) throw std::runtime_error("LocalMapManagerHIP::step|ERROR: a counter is out of range");
+    if (_status == PRS_ERR_CAPACITY) std::cerr << "LocalMapManagerHIP::step|WARNING: graph or log full, staying in the local map" << std::endl;
+    return _reason;
+  }
+
+  bool hasToSplit() const { return _reason != PRS_SESSION_NO_SPLIT; }  // of the last step()
+  int status() const { return _status; }
+  int currentLocalMap() const { return word(_b.cur_node); }            // graph id of the current local map (node index)
+  int numLocalMaps() const { return word(_b.n_nodes); }
+  int numFrames() const { return word(_b.n_frames); }
+  std::vector<float> robotInLocalMap() const { return down<float>(_b.pose, 16); }
+  std::vector<float> prediction() const { return down<float>(_b.prediction, 16); }  // where the next frame's clip goes
+  // the graph as it stands: estimates double [n][16], factors (from, to, measurement float [m][16], information float [m][36])
+  std::vector<double> estimates() const { return down<double>(_b.graph_X, 16 * (size_t) numLocalMaps()); }
+  void factors(std::vector<int32_t>& from, std::vector<int32_t>& to, std::vector<float>& measurements16, std::vector<float>& information36) const {
+    const size_t m = (size_t) word(_b.n_edges);
+    from = down<int32_t>(_b.from, m), to = down<int32_t>(_b.to, m);
+    measurements16 = down<float>(_b.Z, 16 * m), information36 = down<float>(_b.omega, 36 * m);
+  }
+  // (local map of every frame, pose in it) as logged, float [n][16]
+  void fullTrajectory(std::vector<int32_t>& local_map, std::vector<float>& poses16) const {
+    const size_t n = (size_t) std::min(numFrames(), _b.frame_stride);
+    local_map = down<int32_t>(_b.frame_node, n), poses16 = down<float>(_b.frame_pose, 16 * n);
+  }
+  // global poses float [n][16]: estimate of the frame's local map * the pose in it (unrollFullTrajectory)
+  std::vector<float> unrollFullTrajectory() {
+    const int rc = prs_session_unroll_batch(_ctx->get(), &_b, _trajectory);
+    if (rc < 0) throw std::runtime_error(std::string("LocalMapManagerHIP::unrollFullTrajectory|ERROR: ") + prs_last_error(_ctx->get()));
+    prs_context_synchronize(_ctx->get());
+    return down<float>(_trajectory, 16 * (size_t) std::min(numFrames(), _b.frame_stride));
+  }
+  // the device arrays (a device-resident merger reads frame, n_corr_merge and the two poses, and owns coords .. n_meas)
+  const prs_session_batch& batch() const { return _b; }
+
+protected:
+  static void check(hipError_t e, const char* what) {
+    if (e != hipSuccess) throw std::runtime_error(std::string("LocalMapManagerHIP::") + what + "|ERROR: " + hipGetErrorString(e));
+  }
+  template <class T>
+  static void up(T* dst, const void* src, size_t bytes) {
+    check(hipMemcpy(dst, src, bytes, hipMemcpyHostToDevice), "upload");
+  }
+  template <class T>
+  static std::vector<T> down(const T* src, size_t count) {
+    std::vector<T> out(count);
+    if (count) check(hipMemcpy(out.data(), src, count * sizeof(T), hipMemcpyDeviceToHost), "download");
+    return out;
+  }
+  static int word(const int32_t* src) { return down<int32_t>(src, 1)[0]; }
+
+  ContextPtr _ctx;
+  prs_session_batch _b;
+  void* _block      = nullptr;
+  size_t _bytes     = 0;
+  float* _trajectory = nullptr;
+  int _status = 0, _reason = 0;
+};
+#endif  // PROSLAM_HIP_WITH_HIP_RUNTIME
 
 }  // namespace proslam_hip

@@ -408,6 +408,30 @@ class ClosureMergeBatch(C.Structure):
                 ("corr_from_aligner", C.c_int32), ("transform_is_scene_in_measurement", C.c_int32)]
 
 
+SESSION_NO_SPLIT, SESSION_SPLIT_VIEWPOINT, SESSION_SPLIT_LOST = 0, 1, 2  # PRS_SESSION_*
+
+
+class SessionParams(C.Structure):
+    """prs_session_params"""
+    _fields_ = [("local_map_distance", C.c_float), ("local_map_angle_distance_radians", C.c_float), ("split_information", C.c_float),
+                ("lost_information", C.c_float)]
+
+
+class SessionBatch(C.Structure):
+    """prs_session_batch (device pointers)"""
+    _fields_ = [("batch", C.c_int32), ("frame_stride", C.c_int32), ("capacity", C.c_int32), ("node_stride", C.c_int32),
+                ("edge_stride", C.c_int32), ("handover_stride", C.c_int32),
+                ("pose", C.c_void_p), ("prev", C.c_void_p), ("prediction", C.c_void_p), ("slot", C.c_void_p), ("cur_node", C.c_void_p),
+                ("n_frames", C.c_void_p), ("frame_node", C.c_void_p), ("frame_pose", C.c_void_p), ("status", C.c_void_p),
+                ("reason", C.c_void_p), ("X", C.c_void_p), ("result", C.c_void_p), ("n_corr", C.c_void_p), ("coords", C.c_void_p),
+                ("desc", C.c_void_p), ("n_points", C.c_void_p), ("n_meas", C.c_void_p), ("frame", C.c_void_p),
+                ("n_corr_merge", C.c_void_p), ("measurement_in_world", C.c_void_p), ("measurement_in_scene", C.c_void_p),
+                ("graph_X", C.c_void_p), ("fixed", C.c_void_p), ("n_nodes", C.c_void_p), ("from_", C.c_void_p), ("to", C.c_void_p),
+                ("Z", C.c_void_p), ("omega", C.c_void_p), ("n_edges", C.c_void_p), ("handover_desc", C.c_void_p),
+                ("handover_xyz", C.c_void_p), ("handover_n_query", C.c_void_p), ("handover_graph_id", C.c_void_p),
+                ("graph_id_base", C.c_void_p)]
+
+
 MODE_ALIGN, MODE_FINDER, MODE_LINEARIZE = 0, 1, 2
 
 # every symbol include/proslam_hip.h declares: (restype, argtypes)
@@ -505,6 +529,9 @@ SYMBOLS = {
                                     C.c_int32, _vp, C.c_int32, C.c_int32, _vp, C.c_int32, _vp]),
     "prs_map_merge_closure": (C.c_int, [_vp, C.POINTER(ClosureMergerParams), _vp, C.c_int32, _vp, _vp, _vp, C.c_int32, _vp, C.c_int32,
                                         C.c_int32, _vp]),
+    "prs_session_step_batch": (C.c_int, [_vp, C.POINTER(SessionParams), C.POINTER(SessionBatch)]),
+    "prs_session_unroll_batch": (C.c_int, [_vp, C.POINTER(SessionBatch), _vp]),
+    "prs_session_struct_sizes": (None, [C.POINTER(C.c_uint64)]),
     "prs_scene_clip_batch": (C.c_int, [_vp, C.POINTER(Projector), _vp, C.POINTER(ClipBatch)]),
     "prs_scene_clip": (C.c_int, [_vp, C.POINTER(Projector), _vp, _vp, _vp, _vp, C.c_int32, _vp, _vp, _vp, C.c_int32, _i32p]),
 }

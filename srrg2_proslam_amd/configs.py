@@ -65,6 +65,13 @@ def _lm():
             "variable_damping": 1}
 
 
+# LocalMapSplittingCriterionViewpoint3D, the `splitting_criterion` of MultiGraphSLAM3D (the local-map manager, include/proslam_hip.h
+# prs_session_params): a new local map once the sensor is further than the distance, or turned by more than the angle, from the
+# map's origin
+def _split(distance, angle):
+    return {"local_map_distance": distance, "local_map_angle_distance_radians": angle}
+
+
 KITTI = {
     "name": "kitti",
     # tests/fixtures.hpp:810-816,1093-1094
@@ -97,6 +104,7 @@ KITTI = {
     # kitti.conf:895-936 (global_solver) -> Solver :420-444, IterationAlgorithmGN :826-832, SimpleTerminationCriteria :884-889
     "graph": _graph("IterationAlgorithmGN", 1e-06),
     "closure_merger": _closure_merger(),  # kitti.conf:335-337 (slice) -> :446-460
+    "split": _split(10, 0.25),  # kitti.conf:925 (splitting_criterion) -> :542-550: distance :549, angle :546
     "depth": {"min": 4.0, "max": 80.0},
 }
 
@@ -128,6 +136,7 @@ EUROC = {
     "place": _place(50.0, 5, 100),  # euroc.conf: MultiLoopDetectorHBST3D
     "graph": _graph("IterationAlgorithmGN", 1e-06),  # euroc.conf:641-651 (MultiGraphSLAM3D -> global_solver)
     "closure_merger": _closure_merger(),  # euroc.conf:898-900 (slice) -> :519
+    "split": _split(1, 0.5),  # euroc.conf:631-639: distance :638, angle :635
     "depth": {"min": 1.0, "max": 15.0},
 }
 
@@ -156,6 +165,7 @@ ICL = {
     "place": _place(35.0, 1, 50),  # icl.conf:197-240
     "graph": _graph("IterationAlgorithmLM", 1e-06, _lm()),  # icl.conf:797-807 (MultiGraphSLAM3D -> global_solver), LM :665-685
     "closure_merger": _closure_merger(),  # icl.conf:178-180 (slice) -> :773
+    "split": _split(5, 3),  # icl.conf:546-554: distance :553, angle :550
     "depth": {"min": 0.5, "max": 6.0},
     # RawDataPreprocessorMonocularDepth (icl.conf:642-650) and its IntensityFeatureExtractorBinned3D (icl.conf:745-770)
     "rgbd": {"depth_scaling_factor_to_meters": 0.001, "detector_threshold": 5, "enable_non_maximum_suppression": 1,
@@ -187,6 +197,7 @@ TUM = {
     "place": _place(25.0, 1, 40),  # tum.conf: MultiLoopDetectorHBST3D
     "graph": _graph("IterationAlgorithmLM", 1e-06, _lm()),  # tum.conf:453-463 (MultiGraphSLAM3D -> global_solver), LM :174-194
     "closure_merger": _closure_merger(),  # tum.conf:221-223 (slice) -> :437
+    "split": _split(1, 0.25),  # tum.conf:539-547: distance :546, angle :543
     "depth": {"min": 0.5, "max": 6.0},
     # RawDataPreprocessorMonocularDepth (tum.conf:633-640) and its IntensityFeatureExtractorBinned3D (tum.conf:858-883)
     "rgbd": {"depth_scaling_factor_to_meters": 0.001, "detector_threshold": 5, "enable_non_maximum_suppression": 1,

@@ -1604,19 +1604,13 @@ __global__ __launch_bounds__(256) void motion_predict_kernel(int batch, const fl
   if (b >= batch) {
     return;
   }
-  float P2[16], P1[16], I2[16], M[16], raw[16], R[16], v[6];
+  float P2[16], P1[16], R[16];
 #pragma unroll
   for (int i = 0; i < 16; ++i) {
     P2[i] = prev2[(size_t) b * 16 + i];
     P1[i] = prev1[(size_t) b * 16 + i];
   }
-  se3_inverse(P2, I2);
-  se3_mul(I2, P1, M);
-  se3_mul(P1, M, raw);
-  // through the unit quaternion: the recursion would otherwise amplify the rotation block's drift from orthonormality
-  // by ~2.4x per frame (se3_inverse transposes)
-  t2tnq(raw, v);
-  tnq2t(v, R);
+  motion_predict(P2, P1, R);  // (prs_se3.h: through the unit quaternion)
 #pragma unroll
   for (int i = 0; i < 16; ++i) {
     pred[(size_t) b * 16 + i] = R[i];

@@ -198,6 +198,8 @@ int pose_graph_lm_launch(prs_context* ctx, const prs_pose_graph_lm_params* param
                          prs_pose_graph_lm_result* result);
 int pose_graph_append_launch(prs_context* ctx, const prs_pose_graph_params* params, const prs_pose_graphs* graphs,
                              const prs_pose_graph_closures* closures);
+int session_step_launch(prs_context* ctx, const prs_session_params* params, const prs_session_batch* batch);
+int session_unroll_launch(prs_context* ctx, const prs_session_batch* batch, float* out);
 int pose_compose_launch(prs_context* ctx, int batch, const float* prediction, const float* X, float* pose_out);
 int motion_predict_launch(prs_context* ctx, int batch, const float* prev2, const float* prev1, float* pred);
 int merge_batch_launch(prs_context* ctx, const prs_merger_params* params, const prs_merge_batch* batch);

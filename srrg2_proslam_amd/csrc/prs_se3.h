@@ -143,6 +143,18 @@ __device__ __forceinline__ void tnq2t(const float* v6, float* T) {
   T[15] = 1.0f;
 }
 
+// MotionModelConstantVelocity3D: R = P1 * (P2^-1 * P1), the rotation block renormalised through its unit quaternion (the recursion
+// would otherwise amplify the block's drift from orthonormality by ~2.4x per frame: se3_inverse transposes).  R must not alias P2 / P1.
+// (motion_predict_kernel in mapping.hip and the session step in session.hip evaluate this one function.)
+__device__ __forceinline__ void motion_predict(const float* P2, const float* P1, float* R) {
+  float I2[16], M[16], raw[16], v[6];
+  se3_inverse(P2, I2);
+  se3_mul(I2, P1, M);
+  se3_mul(P1, M, raw);
+  t2tnq(raw, v);
+  tnq2t(v, R);
+}
+
 // The aligner sums its normal equations in the CAMERA frame (align.hip, factor_accumulate): with A = [R | t] the transform points
 // go through, J = D G_c Rt, G_c = [ wt I | -[y]x ], y = 2 R p, Rt = blockdiag(R, R), so J^T Omega J = Rt^T (G_c^T D^T Omega D G_c) Rt
 // and the rotation is the same for every correspondence: it is applied once, here, to the summed system.  Row r of the result

@@ -392,3 +392,20 @@ def closure_merger_params(conf):
             out["class"] = merger.class_name
             return out
     return {}
+
+
+_SPLIT = ("local_map_distance", "local_map_angle_distance_radians")
+
+
+def split_params(conf):
+    """the local-map splitting criterion's group of a parsed configuration (include/proslam_hip.h prs_session_params), following the
+    file's own wiring: the record that holds a `splitting_criterion` pointer (MultiGraphSLAM3D) -> that criterion, a
+    LocalMapSplittingCriterionViewpoint3D in every shipped file; its class name under "class".  Only fields present in the file
+    are returned."""
+    for r in conf.records:
+        criterion = conf.follow(r, "splitting_criterion")
+        if isinstance(criterion, ConfRecord):
+            out = _pick(criterion, _SPLIT)
+            out["class"] = criterion.class_name
+            return out
+    return {}

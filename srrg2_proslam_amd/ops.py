@@ -1548,6 +1548,111 @@ def motion_predict_batch(ctx, pose_prev2, pose_prev1, pose_pred):
     return rc
 
 
+# ---- local-map manager: per-sequence splits, graph growth, trajectories (include/proslam_hip.h prs_session_*) ----
+SESSION_NO_SPLIT, SESSION_SPLIT_VIEWPOINT, SESSION_SPLIT_LOST = _lib.SESSION_NO_SPLIT, _lib.SESSION_SPLIT_VIEWPOINT, _lib.SESSION_SPLIT_LOST
+
+
+def session_params(cfg_split, split_information=1.0, lost_information=0.1, **overrides):
+    """prs_session_params from a configs.py `split` group; the two informations are the arguments of the reference's makeNewMap
+    calls (apps/app_benchmark.cpp:143, :167); overrides by field name"""
+    p = _lib.SessionParams()
+    p.local_map_distance = cfg_split["local_map_distance"]
+    p.local_map_angle_distance_radians = cfg_split["local_map_angle_distance_radians"]
+    p.split_information, p.lost_information = split_information, lost_information
+    for k, v in overrides.items():
+        setattr(p, k, v)
+    return p
+
+
+class SessionBatch:
+    """B tracking sessions resident in HBM: pose, previous pose and prediction in the current local map, the pose-table slot, the
+    current node, the trajectory log and the per-frame status / reason.  step() is the one launch between align_batch and
+    merge_batch: it reads `frames` (an AlignFrames: X, result, n_corr), writes the merger's per-frame inputs of `maps` (a MapBatch:
+    frame, measurement_in_world, measurement_in_scene and maps.n_corr, which is pointed at this object's n_corr_merge), resets a
+    finished map and grows `graphs` (a PoseGraphBatch with omega).  handover: a PlaceQueries (a LoopDetectorBatch's .queries) that
+    receives every finished map as a query, or None; graph_id_base: optional int64 [B] device tensor added to the node index."""
+
+    def __init__(self, device, maps, frames, graphs, frame_stride, handover=None, graph_id_base=None):
+        import torch
+        dev = torch.device("cuda", device)
+        B = int(maps.batch)
+        if int(frames.batch) != B or int(graphs.batch) != B or (handover is not None and int(handover.batch) != B):
+            raise ValueError("maps, frames, graphs and the hand-over must hold the same number of sequences")
+        self.batch, self.frame_stride = B, int(frame_stride)
+        self.maps, self.frames, self.graphs, self.handover, self.graph_id_base = maps, frames, graphs, handover, graph_id_base
+        eye = torch.eye(4, dtype=torch.float32, device=dev).reshape(1, 16).repeat(B, 1).contiguous()
+        self.pose, self.prev, self.prediction = eye.clone(), eye.clone(), eye.clone()
+        z = lambda shape, dt: torch.zeros(shape, dtype=dt, device=dev)  # noqa: E731
+        self.slot, self.cur_node, self.n_frames = z((B,), torch.int32), z((B,), torch.int32), z((B,), torch.int32)
+        self.frame_node = z((B, self.frame_stride), torch.int32)
+        self.frame_pose = z((B, self.frame_stride, 16), torch.float32)
+        self.status, self.reason = z((B,), torch.int32), z((B,), torch.int32)
+        self.n_corr_merge = z((B,), torch.int32)
+        self.trajectory = z((B, self.frame_stride, 16), torch.float32)
+        maps.n_corr = self.n_corr_merge
+        self.reset()
+
+    def reset(self):
+        """frame 0 comes next: identity poses, empty log, and every graph holds node 0 alone (X = I, fixed)"""
+        import torch
+        g = self.graphs
+        eye = torch.eye(4, dtype=torch.float32, device=self.pose.device).reshape(1, 16)
+        for t in (self.pose, self.prev, self.prediction):
+            t.copy_(eye.expand(self.batch, 16))
+        for t in (self.slot, self.cur_node, self.n_frames, self.status, self.reason, self.n_corr_merge):
+            t.zero_()
+        g.X[:, 0] = torch.eye(4, dtype=torch.float64, device=g.X.device).reshape(16)
+        g.fixed[:, 0] = 1
+        g.n_nodes.fill_(1)
+        g.n_edges.zero_()
+
+    def descriptor(self):
+        m, f, g, h = self.maps, self.frames, self.graphs, self.handover
+        d = _lib.SessionBatch()
+        d.batch, d.frame_stride, d.capacity = self.batch, self.frame_stride, m.capacity
+        d.node_stride, d.edge_stride = g.node_stride, g.edge_stride
+        for name in ("pose", "prev", "prediction", "slot", "cur_node", "n_frames", "frame_node", "frame_pose", "status", "reason",
+                     "n_corr_merge"):
+            setattr(d, name, getattr(self, name).data_ptr())
+        d.X, d.result, d.n_corr = f.X.data_ptr(), f.result.data_ptr(), f.n_corr.data_ptr()
+        d.coords, d.desc, d.n_points, d.n_meas = m.coords.data_ptr(), m.desc.data_ptr(), m.n_points.data_ptr(), m.n_meas.data_ptr()
+        d.frame = m.frame.data_ptr()
+        d.measurement_in_world, d.measurement_in_scene = m.measurement_in_world.data_ptr(), m.measurement_in_scene.data_ptr()
+        d.graph_X, d.fixed, d.n_nodes = g.X.data_ptr(), g.fixed.data_ptr(), g.n_nodes.data_ptr()
+        d.from_, d.to, d.Z, d.n_edges = g.src.data_ptr(), g.dst.data_ptr(), g.Z.data_ptr(), g.n_edges.data_ptr()
+        d.omega = g.omega.data_ptr() if g.omega is not None else None
+        if h is not None:
+            d.handover_stride = h.query_stride
+            d.handover_desc, d.handover_xyz = h.desc.data_ptr(), h.xyz.data_ptr()
+            d.handover_n_query, d.handover_graph_id = h.n_query.data_ptr(), h.graph_id.data_ptr()
+        d.graph_id_base = self.graph_id_base.data_ptr() if self.graph_id_base is not None else None
+        return d
+
+    def step(self, ctx, params):
+        """enqueue the per-frame step of every sequence (asynchronous, one launch); per-sequence status lands in self.status"""
+        d = self.descriptor()
+        rc = _lib.load().prs_session_step_batch(ctx._h, C.byref(params), C.byref(d))
+        _check(ctx, rc, "prs_session_step_batch")
+        return rc
+
+    def unroll(self, ctx):
+        """enqueue the unrolling of the logged trajectories through the graphs as they stand -> self.trajectory [B, frame_stride, 16]
+        (rows from n_frames[b] on are left as they were)"""
+        d = self.descriptor()
+        rc = _lib.load().prs_session_unroll_batch(ctx._h, C.byref(d), self.trajectory.data_ptr())
+        _check(ctx, rc, "prs_session_unroll_batch")
+        return self.trajectory
+
+    def result_of(self, b):
+        """dict(status, reason, n_frames, slot, cur_node, pose, prev, prediction [4, 4], frame_node [n], frame_pose [n, 4, 4])"""
+        n = min(max(int(self.n_frames[b].item()), 0), self.frame_stride)
+        m44 = lambda t: t[b].cpu().numpy().reshape(4, 4).copy()  # noqa: E731
+        return dict(status=int(self.status[b].item()), reason=int(self.reason[b].item()), n_frames=int(self.n_frames[b].item()),
+                    slot=int(self.slot[b].item()), cur_node=int(self.cur_node[b].item()), pose=m44(self.pose), prev=m44(self.prev),
+                    prediction=m44(self.prediction), frame_node=self.frame_node[b, :n].cpu().numpy().copy(),
+                    frame_pose=self.frame_pose[b, :n].cpu().numpy().reshape(-1, 4, 4).copy())
+
+
 # ---- intensity feature extraction (sensor_processing/feature_extractors) ----
 SELECT_CANONICAL, SELECT_LIBSTDCXX = 0, 1
 BF_DENSE_POPCOUNT, BF_DENSE_MATRIX_WHEN_FULL, BF_DENSE_MATRIX = 0, 1, 2  # include/proslam_hip.h PRS_BF_DENSE_*

@@ -125,6 +125,17 @@ def conf_closure(names=("kitti", "euroc", "icl", "tum", "malaga")):
         f.write("\n")
 
 
+def conf_split(names=("kitti", "kitti_in_baselink", "euroc", "icl", "tum", "malaga")):
+    """{config: splitting-criterion group} as formats.split_params reads it through MultiGraphSLAM3D's pointer: settings only"""
+    import json
+    sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+    from srrg2_proslam_amd import formats
+    out = {n: formats.split_params(formats.read_conf(os.path.join(REF, "configurations", n + ".conf"))) for n in names}
+    with open(os.path.join(OUT, "ref_conf_split.json"), "w") as f:
+        json.dump(out, f, indent=1, sort_keys=True)
+        f.write("\n")
+
+
 def main():
     k = os.path.join(DATA, "kitti")
     np.savez_compressed(
@@ -156,6 +167,7 @@ def main():
     conf_graph()
     conf_graph_lm()
     conf_closure()
+    conf_split()
     for f in sorted(os.listdir(OUT)):
         if f.startswith("ref_"):
             print(f, os.path.getsize(os.path.join(OUT, f)) // 1024, "KiB")
