@@ -151,18 +151,6 @@ __device__ __forceinline__ int cold_copy(int v) {
   return v;
 }
 
-// inclusive prefix sum over the 64 lanes of a wave on the DPP network (the matcher's, stereo_match_v5.hip: Hillis-Steele inside every row
-// of 16 lanes, then lane 15 of rows 0 / 2 onto rows 1 / 3 and lane 31 onto the upper half)
-__device__ __forceinline__ uint32_t wave_inclusive_scan_dpp(uint32_t v) {
-  v += (uint32_t) __builtin_amdgcn_update_dpp(0, (int) v, 0x111, 0xf, 0xf, true);   // row_shr:1
-  v += (uint32_t) __builtin_amdgcn_update_dpp(0, (int) v, 0x112, 0xf, 0xf, true);   // row_shr:2
-  v += (uint32_t) __builtin_amdgcn_update_dpp(0, (int) v, 0x114, 0xf, 0xf, true);   // row_shr:4
-  v += (uint32_t) __builtin_amdgcn_update_dpp(0, (int) v, 0x118, 0xf, 0xf, true);   // row_shr:8
-  v += (uint32_t) __builtin_amdgcn_update_dpp(0, (int) v, 0x142, 0xa, 0xf, false);  // row_bcast:15 -> rows 1, 3
-  v += (uint32_t) __builtin_amdgcn_update_dpp(0, (int) v, 0x143, 0xc, 0xf, false);  // row_bcast:31 -> rows 2, 3
-  return v;
-}
-
 // ONE lane: the sequential float sum of col[0 .. n) in index order (bindFixed's disparity sum, aligner_slice_processor_projective.cpp:80-88:
 // its order is the reference's).  The column is read 16 floats ahead: up to 32 floats past n must be readable (their values are not used).
 __device__ __forceinline__ float serial_float_sum(const float* col, const int n) {

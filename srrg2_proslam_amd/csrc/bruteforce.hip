@@ -633,14 +633,7 @@ __device__ __attribute__((noinline)) void bf_flush(const BfSink sink, const uint
         }
       }
       const uint32_t mine = (d[0] < lim ? 1u : 0u) + (d[1] < lim ? 1u : 0u) + (d[2] < lim ? 1u : 0u) + (d[3] < lim ? 1u : 0u);
-      uint32_t incl       = mine;
-#pragma unroll
-      for (int o = 1; o < 64; o <<= 1) {
-        const uint32_t up = __shfl_up(incl, o, 64);
-        if (lane >= o) {
-          incl += up;
-        }
-      }
+      const uint32_t incl = wave_inclusive_scan_shfl(mine, lane);
       const uint32_t total = __shfl(incl, 63, 64);
       if (total != 0u) {  // (wave-uniform)
         uint32_t base = 0;

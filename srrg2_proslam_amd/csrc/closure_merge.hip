@@ -51,7 +51,7 @@ struct ClosureShared {
 __device__ __forceinline__ bool closure_point(const prs_closure_merger_params& P, const float4 z, float* p) {
   if (P.measurement_kind == PRS_CLOSURE_UVD) {
     const float d = z.z;
-    p[0]          = (z.x - P.cx) / P.fx * d;  // the expression of PRS_MERGER_DEPTH_EKF (mapping.hip)
+    p[0]          = (z.x - P.cx) / P.fx * d;  // the expression of PRS_MERGER_DEPTH_EKF (mapping.hip; one function for both changes that kernel's code)
     p[1]          = (z.y - P.cy) / P.fy * d;
     p[2]          = d;
     return __builtin_isfinite(p[0]) && __builtin_isfinite(p[1]) && __builtin_isfinite(p[2]) && d > 0.0f;
@@ -60,13 +60,6 @@ __device__ __forceinline__ bool closure_point(const prs_closure_merger_params& P
   p[1] = z.y;
   p[2] = z.z;
   return __builtin_isfinite(p[0]) && __builtin_isfinite(p[1]) && __builtin_isfinite(p[2]);
-}
-
-__device__ __forceinline__ void closure_apply(const float* T, const float* p, float* out) {
-#pragma unroll
-  for (int i = 0; i < 3; ++i) {
-    out[i] = ((T[4 * i + 0] * p[0] + T[4 * i + 1] * p[1]) + T[4 * i + 2] * p[2]) + T[4 * i + 3];
-  }
 }
 
 // bin of a measurement, -1: unbinned (behind the camera or off the canvas)
@@ -242,7 +235,7 @@ __global__ __launch_bounds__(kClosureThreads) void closure_merge_kernel(const Cl
       const bool valid = closure_point(P, zs[m], p);
       float4 l         = coords[s];
       if (valid && !(cr.response >= P.maximum_response)) {
-        closure_apply(sh.measurement_in_scene, p, q);
+        se3_apply(sh.measurement_in_scene, p, q);
         const float dx = l.x - q[0], dy = l.y - q[1], dz = l.z - q[2];
         const float d2 = (dx * dx + dy * dy) + dz * dz;
         ok             = d2 < P.maximum_distance_geometry_squared;
@@ -263,7 +256,7 @@ __global__ __launch_bounds__(kClosureThreads) void closure_merge_kernel(const Cl
         if (state) {
           const float lp[3] = {l.x, l.y, l.z};
           float w[3];
-          closure_apply(sh.scene_in_world, lp, w);
+          se3_apply(sh.scene_in_world, lp, w);
           state[s] = make_float4(w[0], w[1], w[2], 0.0f);
         }
       }
@@ -377,7 +370,7 @@ __global__ __launch_bounds__(kClosureThreads) void closure_merge_kernel(const Cl
     const int r = n_points + prefix[i >> 6] + __popcll(word & ((1ull << (i & 63)) - 1ull));
     float p[3], q[3];
     (void) closure_point(P, zs[i], p);
-    closure_apply(sh.measurement_in_scene, p, q);
+    se3_apply(sh.measurement_in_scene, p, q);
     coords[r]        = make_float4(q[0], q[1], q[2], 0.0f);
     const uint4* src = reinterpret_cast<const uint4*>(zdesc + 32 * (size_t) i);
     uint4* dst       = reinterpret_cast<uint4*>(B.desc + 32 * (row0 + (size_t) r));
@@ -385,7 +378,7 @@ __global__ __launch_bounds__(kClosureThreads) void closure_merge_kernel(const Cl
     dst[1]           = src[1];
     if (state) {  // merger_projective_impl.cpp:317-320
       float w[3];
-      closure_apply(sh.scene_in_world, q, w);
+      se3_apply(sh.scene_in_world, q, w);
       state[r] = make_float4(w[0], w[1], w[2], 0.0f);
     }
     if (B.covariance) {

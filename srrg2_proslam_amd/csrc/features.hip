@@ -88,9 +88,6 @@ __device__ __forceinline__ void wave_sync_lds() {
   __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");  // LDS written by one lane is read by other lanes of the wave
   __builtin_amdgcn_wave_barrier();
 }
-__device__ __forceinline__ int lanes_below(uint64_t m, int base) {  // base + number of set bits of m below this lane
-  return (int) __builtin_amdgcn_mbcnt_hi((uint32_t) (m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t) m, (uint32_t) base));
-}
 
 constexpr int kTileWords  = kTilePitch / 4;   // 18 words per tile row
 constexpr int kTileRows   = kTileH + 8;       // 4-px halo above and below
@@ -637,14 +634,7 @@ __global__ __launch_bounds__(kNmsThreads) void raster_order_kernel(const Feature
   __syncthreads();
   {  // exclusive scan of the bucket sizes, one bucket per thread
     const uint32_t c = count[tid];
-    uint32_t incl    = c;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-      const uint32_t v = (uint32_t) __shfl_up((int) incl, o, 64);
-      if (lane >= o) {
-        incl += v;
-      }
-    }
+    const uint32_t incl = wave_inclusive_scan_shfl(c, lane);
     if (lane == 63) {
       wave_tot[wave] = incl;
     }

@@ -68,12 +68,6 @@ struct MergeShared {
   int n_work, n_next;  // smoother work items of this / the next round
 };
 
-__device__ __forceinline__ void apply_rows(const float* T, const float* p, float* out) {
-#pragma unroll
-  for (int i = 0; i < 3; ++i) {
-    out[i] = ((T[4 * i + 0] * p[0] + T[4 * i + 1] * p[1]) + T[4 * i + 2] * p[2]) + T[4 * i + 3];
-  }
-}
 __device__ __forceinline__ float sqnorm3(const float* a, const float* b) {
   const float d0 = a[0] - b[0], d1 = a[1] - b[1], d2 = a[2] - b[2];
   return (d0 * d0 + d1 * d1) + d2 * d2;
@@ -124,7 +118,7 @@ __device__ int estimate_weighted_mean(const prs_estimator_params& P, const Merge
   *l.inlier           = 0;  // :13
   const float init[3] = {l.state[0], l.state[1], l.state[2]};
   float upd[3];
-  apply_rows(sh.sensor_in_world, landmark_in_sensor, upd);  // :20-21
+  se3_apply(sh.sensor_in_world, landmark_in_sensor, upd);  // :20-21
   const float npo = (float) (*l.n_opt + 1u);                // :23
   float cw[3];
 #pragma unroll
@@ -137,7 +131,7 @@ __device__ int estimate_weighted_mean(const prs_estimator_params& P, const Merge
   add_optimization_result(l, cw, nullptr);  // :37
   *l.inlier = 1;
   float loc[3];
-  apply_rows(sh.world_in_local_map, cw, loc);  // :41
+  se3_apply(sh.world_in_local_map, cw, loc);  // :41
   l.coords[0] = loc[0];
   l.coords[1] = loc[1];
   l.coords[2] = loc[2];
@@ -374,7 +368,7 @@ __device__ int estimate_ekf(const prs_estimator_params& P, const MergeShared& sh
   }
   const float sf[3] = {(float) sp[0], (float) sp[1], (float) sp[2]};
   float cw[3];
-  apply_rows(sh.sensor_in_world, sf, cw);  // :68-69
+  se3_apply(sh.sensor_in_world, sf, cw);  // :68-69
   if (sqnorm3(cw, init) > P.maximum_distance_geometry_meters_squared) {  // :70-74
     return 0;
   }
@@ -386,7 +380,7 @@ __device__ int estimate_ekf(const prs_estimator_params& P, const MergeShared& sh
   add_optimization_result(l, cw, covf);  // :77-78
   *l.inlier = 1;
   float loc[3];
-  apply_rows(sh.world_in_local_map, cw, loc);  // :82-83
+  se3_apply(sh.world_in_local_map, cw, loc);  // :82-83
   l.coords[0] = loc[0];
   l.coords[1] = loc[1];
   l.coords[2] = loc[2];
@@ -394,16 +388,12 @@ __device__ int estimate_ekf(const prs_estimator_params& P, const MergeShared& sh
 }
 
 // ---- LandmarkEstimatorPoseBasedSmoother_ -------------------------------------------------------------
-__device__ void apply_pose(const float* T12, const float* p, float* out) {
-  apply_rows(T12, p, out);
-}
-
 // _setMeanCoordinatesInWorld (:138-147)
 __device__ void mean_in_world(const prs_camera_measurement* m, uint32_t n, const prs_frame_pose* poses, float* out) {
   float acc0 = 0.0f, acc1 = 0.0f, acc2 = 0.0f;
   for (uint32_t k = 0; k < n; ++k) {
     float w[3];
-    apply_pose(poses[m[k].frame].sensor_in_world, m[k].point_in_camera, w);
+    se3_apply(poses[m[k].frame].sensor_in_world, m[k].point_in_camera, w);
     acc0 += w[0];
     acc1 += w[1];
     acc2 += w[2];
@@ -564,7 +554,7 @@ __device__ int smoother_begin(const prs_estimator_params& P, const MergeShared& 
     mean_in_world(M, n, poses, world);
     if (sqnorm3(world, init) < P.maximum_distance_geometry_meters_squared) {
       float loc[3];
-      apply_rows(sh.world_in_local_map, world, loc);
+      se3_apply(sh.world_in_local_map, world, loc);
       l.coords[0] = loc[0];
       l.coords[1] = loc[1];
       l.coords[2] = loc[2];
@@ -660,7 +650,7 @@ __device__ bool smoother_iterate(const prs_estimator_params& P, const float* pos
         Jl = Jg;
       }
       float pc[3];
-      apply_pose(W, world, pc);  // :63
+      se3_apply(W, world, pc);  // :63
       if (pc[2] <= 0.0f) {
         ++number_of_outliers;
         return;
@@ -794,38 +784,29 @@ __device__ int smoother_finish(const float* world_in_local_map, const prs_frame_
     l.state[2] = world[2];
   }
   float loc[3];
-  apply_rows(world_in_local_map, world, loc);  // :138
+  se3_apply(world_in_local_map, world, loc);  // :138
   l.coords[0] = loc[0];
   l.coords[1] = loc[1];
   l.coords[2] = loc[2];
   return *l.inlier;
 }
 
-// triangulateRectifiedMidpoint (mapping/triangulator_rigid_stereo.cpp:60-85)
+// triangulate_rectified into p[3]; false (p zero): disparity below the minimum.  The test is the helper's own, stated first so that
+// the refused measurement leaves before the arithmetic, as it always did here (a NaN disparity passes both).
 __device__ __forceinline__ bool triangulate_one(const prs_triangulator_params& tp, const float4 z, float* p) {
-  const float x_L = z.x, y_L = z.y, x_R = z.z, y_R = z.w;
   p[0] = p[1] = p[2] = 0.0f;
-  if (x_L - x_R < tp.minimum_disparity_pixels) {
+  if (z.x - z.z < tp.minimum_disparity_pixels) {
     return false;
   }
-  float depth_meters = tp.infinity_depth_meters;
-  if (x_L > x_R) {
-    depth_meters = tp.b_x / (x_L - x_R);
-  }
-  p[2] = depth_meters;
-  p[0] = 1 / tp.fx * (x_L - tp.cx) * depth_meters;
-  p[1] = 1 / tp.fy * ((y_L + y_R) / 2 - tp.cy) * depth_meters;
+  const float4 pt = triangulate_rectified(tp, z.x, z.y, z.z, z.w);
+  p[2] = pt.z;
+  p[0] = pt.x;
+  p[1] = pt.y;
   return true;
 }
 
 __device__ __forceinline__ uint32_t bin_of(float coordinate, float width) {
   return (uint32_t) roundf(coordinate / width);  // merger_projective_impl.cpp:84-85
-}
-
-// order-preserving map of a float onto unsigned integers
-__device__ __forceinline__ uint32_t float_key(float v) {
-  const uint32_t u = __float_as_uint(v);
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
 }
 
 // EST / DIM are compile-time so that an instantiation only carries the registers of its own estimator
@@ -1163,7 +1144,7 @@ __global__ __launch_bounds__(kMergeThreads) void merge_kernel(const MergeArgs a)
         // strictly smaller depth (merger_projective_depth_ekf_impl.cpp:50-57) replaces the occupant, so the
         // bin ends with the earliest measurement among the best
         const float q = P.variant == PRS_MERGER_DEPTH_EKF ? -z.z : z.x - z.z;
-        const unsigned long long key = ((unsigned long long) float_key(q) << 32) | (unsigned long long) (0xffffffffu - (uint32_t) i);
+        const unsigned long long key = ((unsigned long long) ordered(q) << 32) | (unsigned long long) (0xffffffffu - (uint32_t) i);
         atomicMax(&best[bin], key);
       }
       __syncthreads();
@@ -1218,7 +1199,7 @@ __global__ __launch_bounds__(kMergeThreads) void merge_kernel(const MergeArgs a)
           // _initializeLandmark (:308-326) + move into the scene frame (:282-286)
           const Landmark l = landmark_at(B, map, idx);
           float w3[3], loc[3];
-          apply_rows(sh.sensor_in_world, p, w3);
+          se3_apply(sh.sensor_in_world, p, w3);
           l.state[0] = w3[0];
           l.state[1] = w3[1];
           l.state[2] = w3[2];
@@ -1243,7 +1224,7 @@ __global__ __launch_bounds__(kMergeThreads) void merge_kernel(const MergeArgs a)
             l.meas[0]             = nm;
             *l.n_meas             = 1;
           }
-          apply_rows(sh.measurement_in_scene, p, loc);
+          se3_apply(sh.measurement_in_scene, p, loc);
           l.coords[0] = loc[0];
           l.coords[1] = loc[1];
           l.coords[2] = loc[2];
@@ -1379,10 +1360,7 @@ __global__ __launch_bounds__(kSmootherThreads) void smoother_kernel(const MergeA
     nxt             = t;
     __syncthreads();
   }
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) {
-    merged += __shfl_xor(merged, d, 64);
-  }
+  merged = wave_sum(merged);
   if (lane == 0) {
     carry->n_merged += merged;
   }

@@ -40,14 +40,6 @@ struct PointAlignArgs {
   prs_point_align_params p;
 };
 
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) {
-    v = v + __shfl_xor(v, m, 64);
-  }
-  return v;
-}
-
 // terms of one correspondence, added to the lane's running sums; returns 1 inlier, 0 outlier, -1 invalid
 __device__ __forceinline__ int accumulate(const float* X, const float tau, const bool saturated, const float px, const float py,
                                           const float pz, const float fx, const float fy, const float fz, float* s) {

@@ -37,6 +37,7 @@
 
 #include "prs_device.h"
 #include "prs_host.h"
+#include "prs_se3.h"
 
 namespace prs {
 
@@ -53,121 +54,6 @@ struct PoseGraphArgs {
   long long capacity_blocks;  // envelope blocks of workspace per graph
   int rb_cols;                // scalar columns of the LDS block-row buffer
 };
-
-// ---- prs_se3.h in double, the same expression order ----
-__device__ __forceinline__ void inverse_d(const double* T, double* Ti) {
-  const double tx = T[3], ty = T[7], tz = T[11];
-#pragma unroll
-  for (int i = 0; i < 3; ++i) {
-    const double r0 = T[0 + i], r1 = T[4 + i], r2 = T[8 + i];
-    Ti[4 * i + 0] = r0;
-    Ti[4 * i + 1] = r1;
-    Ti[4 * i + 2] = r2;
-    Ti[4 * i + 3] = -((r0 * tx + r1 * ty) + r2 * tz);
-  }
-}
-
-// rows 0-2 only (12 entries used, row-major with stride 4)
-__device__ __forceinline__ void mul_d(const double* A, const double* B, double* C) {
-#pragma unroll
-  for (int i = 0; i < 3; ++i) {
-#pragma unroll
-    for (int j = 0; j < 3; ++j) {
-      C[4 * i + j] = (A[4 * i + 0] * B[0 + j] + A[4 * i + 1] * B[4 + j]) + A[4 * i + 2] * B[8 + j];
-    }
-    C[4 * i + 3] = ((A[4 * i + 0] * B[3] + A[4 * i + 1] * B[7]) + A[4 * i + 2] * B[11]) + A[4 * i + 3];
-  }
-}
-
-// translation, imaginary part and (returned) real part of the unit quaternion with w >= 0
-__device__ __forceinline__ double t2tnq_d(const double* T, double* v6) {
-  const double m00 = T[0], m01 = T[1], m02 = T[2];
-  const double m10 = T[4], m11 = T[5], m12 = T[6];
-  const double m20 = T[8], m21 = T[9], m22 = T[10];
-  double q0, q1, q2, q3;
-  double t = (m00 + m11) + m22;
-  if (t > 0.0) {
-    t  = sqrt(t + 1.0);
-    q0 = 0.5 * t;
-    t  = 0.5 / t;
-    q1 = (m21 - m12) * t;
-    q2 = (m02 - m20) * t;
-    q3 = (m10 - m01) * t;
-  } else {
-    int i = 0;
-    if (m11 > m00) {
-      i = 1;
-    }
-    if (m22 > (i == 0 ? m00 : m11)) {
-      i = 2;
-    }
-    if (i == 0) {
-      t  = sqrt(((m00 - m11) - m22) + 1.0);
-      q1 = 0.5 * t;
-      t  = 0.5 / t;
-      q0 = (m21 - m12) * t;
-      q2 = (m10 + m01) * t;
-      q3 = (m20 + m02) * t;
-    } else if (i == 1) {
-      t  = sqrt(((m11 - m22) - m00) + 1.0);
-      q2 = 0.5 * t;
-      t  = 0.5 / t;
-      q0 = (m02 - m20) * t;
-      q3 = (m21 + m12) * t;
-      q1 = (m01 + m10) * t;
-    } else {
-      t  = sqrt(((m22 - m00) - m11) + 1.0);
-      q3 = 0.5 * t;
-      t  = 0.5 / t;
-      q0 = (m10 - m01) * t;
-      q1 = (m02 + m20) * t;
-      q2 = (m12 + m21) * t;
-    }
-  }
-  const double n = sqrt(((q0 * q0 + q1 * q1) + q2 * q2) + q3 * q3);
-  double s       = 1.0 / n;
-  if (q0 < 0.0) {
-    s = -s;
-  }
-  v6[0] = T[3];
-  v6[1] = T[7];
-  v6[2] = T[11];
-  v6[3] = q1 * s;
-  v6[4] = q2 * s;
-  v6[5] = q3 * s;
-  return q0 * s;
-}
-
-__device__ __forceinline__ void tnq2t_d(const double* v6, double* T) {
-  double x = v6[3], y = v6[4], z = v6[5];
-  const double n2 = (x * x + y * y) + z * z;
-  double w;
-  if (n2 < 1.0) {
-    w = sqrt(1.0 - n2);
-  } else {
-    const double s = 1.0 / sqrt(n2);
-    x = x * s;
-    y = y * s;
-    z = z * s;
-    w = 0.0;
-  }
-  const double tx = 2.0 * x, ty = 2.0 * y, tz = 2.0 * z;
-  const double twx = tx * w, twy = ty * w, twz = tz * w;
-  const double txx = tx * x, txy = ty * x, txz = tz * x;
-  const double tyy = ty * y, tyz = tz * y, tzz = tz * z;
-  T[0]  = 1.0 - (tyy + tzz);
-  T[1]  = txy - twz;
-  T[2]  = txz + twy;
-  T[3]  = v6[0];
-  T[4]  = txy + twz;
-  T[5]  = 1.0 - (txx + tzz);
-  T[6]  = tyz - twx;
-  T[7]  = v6[1];
-  T[8]  = txz - twy;
-  T[9]  = tyz + twx;
-  T[10] = 1.0 - (txx + tyy);
-  T[11] = v6[2];
-}
 
 // what one graph's workgroup keeps in LDS
 struct Lds {
@@ -216,11 +102,11 @@ __device__ __forceinline__ double linearize_edge(const Graph& G, const Lds& s, c
     Xt[i] = G.X[16 * (size_t) t + i];
   }
   double Zi[12], Xfi[12], A[12], E[12], e[6];
-  inverse_d(Z, Zi);
-  inverse_d(Xf, Xfi);
-  mul_d(Xfi, Xt, A);
-  mul_d(Zi, A, E);
-  const double w = t2tnq_d(E, e);
+  se3_inverse<false>(Z, Zi);
+  se3_inverse<false>(Xf, Xfi);
+  se3_mul<false>(Xfi, Xt, A);
+  se3_mul<false>(Zi, A, E);
+  const double w = t2tnq(E, e);
   double* sJf  = s.edge;
   double* sJt  = s.edge + 36;
   double* sOJf = s.edge + 72;
@@ -596,8 +482,8 @@ __device__ __forceinline__ void update_poses(const Graph& G, const Lds& s, const
       for (int q = 0; q < 12; ++q) {
         X[q] = X0[16 * (size_t) i + q];
       }
-      tnq2t_d(dx, D);
-      mul_d(X, D, Xn);
+      tnq2t<false>(dx, D);
+      se3_mul<false>(X, D, Xn);
 #pragma unroll
       for (int q = 0; q < 12; ++q) {
         G.X[16 * (size_t) i + q] = Xn[q];

@@ -11,8 +11,6 @@
 
 namespace prs {
 
-// 256-bit Hamming distance of two 32-byte rows held as 2 x uint4 each
-// (replaces srrg2_core PointDescriptorField::distance; call site CF/..epipolar_impl.cpp:157)
 // 1.0f / x, correctly rounded (the value the IEEE division of the CPU side produces), in 3 + 2 instructions instead of the twelve of
 // the compiler's expansion (v_div_scale x 2, v_rcp, 4 x v_fma, v_div_fmas, v_div_fixup).  tools/probes/rcp_exact_probe.hip runs ALL 2^32
 // bit patterns on gfx950: v_rcp_f32 followed by ONE Newton step in fused multiply-adds equals the IEEE quotient for every x whose biased
@@ -31,7 +29,10 @@ __device__ __forceinline__ float recip_exact(const float x) {
   return __builtin_fmaf(__builtin_fmaf(-x, y, 1.0f), y, y);
 }
 
-__device__ __forceinline__ int hamming256(const uint4& a0, const uint4& a1, const uint4& b0, const uint4& b1) {
+// 256-bit Hamming distance of two 32-byte rows held as 2 x V each, V any vector of four 32-bit words (.x .y .z .w)
+// (replaces srrg2_core PointDescriptorField::distance; call site CF/..epipolar_impl.cpp:157)
+template <typename V>
+__device__ __forceinline__ int hamming256(const V& a0, const V& a1, const V& b0, const V& b1) {
   int d = __popc(a0.x ^ b0.x);
   d += __popc(a0.y ^ b0.y);
   d += __popc(a0.z ^ b0.z);
@@ -63,6 +64,76 @@ __device__ __forceinline__ uint64_t wave_inclusive_scan_u64(uint64_t v) {
     }
   }
   return v;
+}
+
+// inclusive prefix sum of a 32-bit count over the 64 lanes of a wave by shuffles; `lane` is the caller's lane index (a thread index
+// below 64 will do).  The scans inside loops that also broadcast the total (bruteforce.hip, pose_graph.hip) and those of align.hip and
+// the first-generation matcher's epilogue spell the same loop out: through this function their kernels compile to other code.
+template <typename T>
+__device__ __forceinline__ T wave_inclusive_scan_shfl(T v, const int lane) {
+#pragma unroll
+  for (int d = 1; d < PRS_WAVE; d <<= 1) {
+    const T o = __shfl_up(v, d, PRS_WAVE);
+    if (lane >= d) {
+      v += o;
+    }
+  }
+  return v;
+}
+
+// the same sum on the DPP network (was six ds_bpermute round trips): Hillis-Steele inside every row of 16 lanes (row_shr 1, 2, 4, 8,
+// lanes shifted in from outside a row read 0), then lane 15 of rows 0 / 2 onto rows 1 / 3 (row_bcast:15) and lane 31 onto the upper
+// half (row_bcast:31)
+__device__ __forceinline__ uint32_t wave_inclusive_scan_dpp(uint32_t v) {
+  v += (uint32_t) __builtin_amdgcn_update_dpp(0, (int) v, 0x111, 0xf, 0xf, true);   // row_shr:1
+  v += (uint32_t) __builtin_amdgcn_update_dpp(0, (int) v, 0x112, 0xf, 0xf, true);   // row_shr:2
+  v += (uint32_t) __builtin_amdgcn_update_dpp(0, (int) v, 0x114, 0xf, 0xf, true);   // row_shr:4
+  v += (uint32_t) __builtin_amdgcn_update_dpp(0, (int) v, 0x118, 0xf, 0xf, true);   // row_shr:8
+  v += (uint32_t) __builtin_amdgcn_update_dpp(0, (int) v, 0x142, 0xa, 0xf, false);  // row_bcast:15 -> rows 1, 3
+  v += (uint32_t) __builtin_amdgcn_update_dpp(0, (int) v, 0x143, 0xc, 0xf, false);  // row_bcast:31 -> rows 2, 3
+  return v;
+}
+
+// butterfly sum over the 64 lanes of a wave: every lane ends with the total (for floats: in this fixed order)
+template <typename T>
+__device__ __forceinline__ T wave_sum(T v) {
+#pragma unroll
+  for (int m = 32; m >= 1; m >>= 1) {
+    v += __shfl_xor(v, m, PRS_WAVE);
+  }
+  return v;
+}
+
+// base + number of set bits of m below this lane
+__device__ __forceinline__ int lanes_below(uint64_t m, int base) {
+  return (int) __builtin_amdgcn_mbcnt_hi((uint32_t) (m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t) m, (uint32_t) base));
+}
+
+// order-preserving map of a float onto unsigned integers (no NaN), and back
+__device__ __forceinline__ uint32_t ordered(const float f) {
+  const uint32_t u = __float_as_uint(f);
+  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+__device__ __forceinline__ float from_ordered(const uint32_t o) {
+  return __uint_as_float((o & 0x80000000u) ? (o & 0x7fffffffu) : ~o);
+}
+
+// triangulateRectifiedMidpoint (mapping/triangulator_rigid_stereo.cpp:39-45,60-85, operation order kept): the point of a rectified
+// stereo pair in the left camera, w = 1; all zero when the disparity is below the minimum (a NaN disparity is not)
+__device__ __forceinline__ float4 triangulate_rectified(const prs_triangulator_params& t, const float x_L, const float y_L, const float x_R,
+                                                        const float y_R) {
+  float4 pt = make_float4(0.f, 0.f, 0.f, 0.f);
+  if (!(x_L - x_R < t.minimum_disparity_pixels)) {
+    float depth = t.infinity_depth_meters;
+    if (x_L > x_R) {
+      depth = t.b_x / (x_L - x_R);
+    }
+    pt.z = depth;
+    pt.x = 1 / t.fx * (x_L - t.cx) * depth;
+    pt.y = 1 / t.fy * ((y_L + y_R) / 2 - t.cy) * depth;
+    pt.w = 1.0f;
+  }
+  return pt;
 }
 
 // exclusive prefix over all threads of the block (blockDim.x multiple of 64, <= 1024).

@@ -1,10 +1,12 @@
-// prs_se3.h -- exact float SE(3) / 6x6 solver helpers for the aligner kernels.
+// prs_se3.h -- exact SE(3) / 6x6 solver helpers for the aligner kernels.
 // Every expression is written as explicit two-operand operations in a fixed order and the library
 // is compiled with -ffp-contract=off; division and sqrt are IEEE correctly rounded (hipcc default),
 // so results are reproducible bit-for-bit against a plain sequential float evaluation.
-// 4x4 transforms are row-major float[16].
+// 4x4 transforms are row-major S[16].
 #pragma once
 #include <hip/hip_runtime.h>
+
+#include "prs_device.h"
 
 namespace prs {
 
@@ -15,25 +17,34 @@ __device__ __forceinline__ void se3_identity(float* T) {
   }
 }
 
+// The SE(3) helpers are templates over the scalar S (float for the aligner and the mapper, double for the pose graph): one written
+// expression order for both.  BOTTOM = false leaves entries 12..15 alone, for callers that hold only the top three rows (S[12]).
+__device__ __forceinline__ float sqrt_s(const float x) { return sqrtf(x); }
+__device__ __forceinline__ double sqrt_s(const double x) { return sqrt(x); }
+
 // Isometry inverse [R^T | -R^T t]
-__device__ __forceinline__ void se3_inverse(const float* T, float* Ti) {
-  const float tx = T[3], ty = T[7], tz = T[11];
+template <bool BOTTOM = true, typename S>
+__device__ __forceinline__ void se3_inverse(const S* T, S* Ti) {
+  const S tx = T[3], ty = T[7], tz = T[11];
 #pragma unroll
   for (int i = 0; i < 3; ++i) {
-    const float r0 = T[0 + i], r1 = T[4 + i], r2 = T[8 + i];  // row i of R^T
+    const S r0 = T[0 + i], r1 = T[4 + i], r2 = T[8 + i];  // row i of R^T
     Ti[4 * i + 0]  = r0;
     Ti[4 * i + 1]  = r1;
     Ti[4 * i + 2]  = r2;
     Ti[4 * i + 3]  = -((r0 * tx + r1 * ty) + r2 * tz);
   }
-  Ti[12] = 0.0f;
-  Ti[13] = 0.0f;
-  Ti[14] = 0.0f;
-  Ti[15] = 1.0f;
+  if (BOTTOM) {
+    Ti[12] = S(0.0);
+    Ti[13] = S(0.0);
+    Ti[14] = S(0.0);
+    Ti[15] = S(1.0);
+  }
 }
 
 // C = A * B (C must not alias A or B)
-__device__ __forceinline__ void se3_mul(const float* A, const float* B, float* C) {
+template <bool BOTTOM = true, typename S>
+__device__ __forceinline__ void se3_mul(const S* A, const S* B, S* C) {
 #pragma unroll
   for (int i = 0; i < 3; ++i) {
 #pragma unroll
@@ -42,24 +53,35 @@ __device__ __forceinline__ void se3_mul(const float* A, const float* B, float* C
     }
     C[4 * i + 3] = ((A[4 * i + 0] * B[3] + A[4 * i + 1] * B[7]) + A[4 * i + 2] * B[11]) + A[4 * i + 3];
   }
-  C[12] = 0.0f;
-  C[13] = 0.0f;
-  C[14] = 0.0f;
-  C[15] = 1.0f;
+  if (BOTTOM) {
+    C[12] = S(0.0);
+    C[13] = S(0.0);
+    C[14] = S(0.0);
+    C[15] = S(1.0);
+  }
 }
 
-// geometry3d::t2tnq (srrg2_core): translation + imaginary part of the normalised quaternion, w >= 0
+// out = T p (the rotation rows and the translation; float only: every caller holds points in float)
+__device__ __forceinline__ void se3_apply(const float* T, const float* p, float* out) {
+#pragma unroll
+  for (int i = 0; i < 3; ++i) {
+    out[i] = ((T[4 * i + 0] * p[0] + T[4 * i + 1] * p[1]) + T[4 * i + 2] * p[2]) + T[4 * i + 3];
+  }
+}
+
+// geometry3d::t2tnq (srrg2_core): translation + imaginary part of the normalised quaternion, w >= 0; returns the real part w
 // (used at CF/correspondence_finder_projective_base_impl.cpp:182)
-__device__ __forceinline__ void t2tnq(const float* T, float* v6) {
-  const float m00 = T[0], m01 = T[1], m02 = T[2];
-  const float m10 = T[4], m11 = T[5], m12 = T[6];
-  const float m20 = T[8], m21 = T[9], m22 = T[10];
-  float q0, q1, q2, q3;  // w x y z
-  float t = (m00 + m11) + m22;
-  if (t > 0.0f) {
-    t  = sqrtf(t + 1.0f);
-    q0 = 0.5f * t;
-    t  = 0.5f / t;
+template <typename S>
+__device__ __forceinline__ S t2tnq(const S* T, S* v6) {
+  const S m00 = T[0], m01 = T[1], m02 = T[2];
+  const S m10 = T[4], m11 = T[5], m12 = T[6];
+  const S m20 = T[8], m21 = T[9], m22 = T[10];
+  S q0, q1, q2, q3;  // w x y z
+  S t = (m00 + m11) + m22;
+  if (t > S(0.0)) {
+    t  = sqrt_s(t + S(1.0));
+    q0 = S(0.5) * t;
+    t  = S(0.5) / t;
     q1 = (m21 - m12) * t;
     q2 = (m02 - m20) * t;
     q3 = (m10 - m01) * t;
@@ -72,31 +94,31 @@ __device__ __forceinline__ void t2tnq(const float* T, float* v6) {
       i = 2;
     }
     if (i == 0) {  // j = 1, k = 2
-      t  = sqrtf(((m00 - m11) - m22) + 1.0f);
-      q1 = 0.5f * t;
-      t  = 0.5f / t;
+      t  = sqrt_s(((m00 - m11) - m22) + S(1.0));
+      q1 = S(0.5) * t;
+      t  = S(0.5) / t;
       q0 = (m21 - m12) * t;
       q2 = (m10 + m01) * t;
       q3 = (m20 + m02) * t;
     } else if (i == 1) {  // j = 2, k = 0
-      t  = sqrtf(((m11 - m22) - m00) + 1.0f);
-      q2 = 0.5f * t;
-      t  = 0.5f / t;
+      t  = sqrt_s(((m11 - m22) - m00) + S(1.0));
+      q2 = S(0.5) * t;
+      t  = S(0.5) / t;
       q0 = (m02 - m20) * t;
       q3 = (m21 + m12) * t;
       q1 = (m01 + m10) * t;
     } else {  // j = 0, k = 1
-      t  = sqrtf(((m22 - m00) - m11) + 1.0f);
-      q3 = 0.5f * t;
-      t  = 0.5f / t;
+      t  = sqrt_s(((m22 - m00) - m11) + S(1.0));
+      q3 = S(0.5) * t;
+      t  = S(0.5) / t;
       q0 = (m10 - m01) * t;
       q1 = (m02 + m20) * t;
       q2 = (m12 + m21) * t;
     }
   }
-  const float n = sqrtf(((q0 * q0 + q1 * q1) + q2 * q2) + q3 * q3);
-  float s       = 1.0f / n;
-  if (q0 < 0.0f) {
+  const S n = sqrt_s(((q0 * q0 + q1 * q1) + q2 * q2) + q3 * q3);
+  S s       = S(1.0) / n;
+  if (q0 < S(0.0)) {
     s = -s;
   }
   v6[0] = T[3];
@@ -105,42 +127,46 @@ __device__ __forceinline__ void t2tnq(const float* T, float* v6) {
   v6[3] = q1 * s;
   v6[4] = q2 * s;
   v6[5] = q3 * s;
+  return q0 * s;
 }
 
 // perturbation [dt; dq] -> isometry, q = (sqrt(1 - |dq|^2), dq) (VariableSE3QuaternionRight)
-__device__ __forceinline__ void tnq2t(const float* v6, float* T) {
-  float x = v6[3], y = v6[4], z = v6[5];
-  const float n2 = (x * x + y * y) + z * z;
-  float w;
-  if (n2 < 1.0f) {
-    w = sqrtf(1.0f - n2);
+template <bool BOTTOM = true, typename S>
+__device__ __forceinline__ void tnq2t(const S* v6, S* T) {
+  S x = v6[3], y = v6[4], z = v6[5];
+  const S n2 = (x * x + y * y) + z * z;
+  S w;
+  if (n2 < S(1.0)) {
+    w = sqrt_s(S(1.0) - n2);
   } else {
-    const float s = 1.0f / sqrtf(n2);
+    const S s = S(1.0) / sqrt_s(n2);
     x *= s;
     y *= s;
     z *= s;
-    w = 0.0f;
+    w = S(0.0);
   }
-  const float tx = 2.0f * x, ty = 2.0f * y, tz = 2.0f * z;
-  const float twx = tx * w, twy = ty * w, twz = tz * w;
-  const float txx = tx * x, txy = ty * x, txz = tz * x;
-  const float tyy = ty * y, tyz = tz * y, tzz = tz * z;
-  T[0]  = 1.0f - (tyy + tzz);
+  const S tx = S(2.0) * x, ty = S(2.0) * y, tz = S(2.0) * z;
+  const S twx = tx * w, twy = ty * w, twz = tz * w;
+  const S txx = tx * x, txy = ty * x, txz = tz * x;
+  const S tyy = ty * y, tyz = tz * y, tzz = tz * z;
+  T[0]  = S(1.0) - (tyy + tzz);
   T[1]  = txy - twz;
   T[2]  = txz + twy;
   T[3]  = v6[0];
   T[4]  = txy + twz;
-  T[5]  = 1.0f - (txx + tzz);
+  T[5]  = S(1.0) - (txx + tzz);
   T[6]  = tyz - twx;
   T[7]  = v6[1];
   T[8]  = txz - twy;
   T[9]  = tyz + twx;
-  T[10] = 1.0f - (txx + tyy);
+  T[10] = S(1.0) - (txx + tyy);
   T[11] = v6[2];
-  T[12] = 0.0f;
-  T[13] = 0.0f;
-  T[14] = 0.0f;
-  T[15] = 1.0f;
+  if (BOTTOM) {
+    T[12] = S(0.0);
+    T[13] = S(0.0);
+    T[14] = S(0.0);
+    T[15] = S(1.0);
+  }
 }
 
 // MotionModelConstantVelocity3D: R = P1 * (P2^-1 * P1), the rotation block renormalised through its unit quaternion (the recursion

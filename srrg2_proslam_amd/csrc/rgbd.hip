@@ -28,10 +28,6 @@ struct DepthArgs {
   float scale;
 };
 
-__device__ __forceinline__ int rank_in_wave(const uint64_t mask) {
-  return (int) __builtin_amdgcn_mbcnt_hi((uint32_t) (mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t) mask, 0u));
-}
-
 __global__ __launch_bounds__(kThreads) void depth_kernel(const DepthArgs a) {
   __shared__ int wave_kept[2][kWaves];
   __shared__ int wave_bad[2][kWaves];
@@ -90,7 +86,7 @@ __global__ __launch_bounds__(kThreads) void depth_kernel(const DepthArgs a) {
         break;
       }
       if (keep) {
-        const size_t o = row0 + (size_t) (kept + before + rank_in_wave(keep_mask));
+        const size_t o = row0 + (size_t) (kept + before + lanes_below(keep_mask, 0));
         reinterpret_cast<float4*>(B.fixed)[o] = make_float4(u, v, a.scale * raw, 0.f);
         const uint4* src = reinterpret_cast<const uint4*>(B.descriptors + (row0 + i) * PRS_DESC_BYTES);
         uint4* dst       = reinterpret_cast<uint4*>(B.fixed_desc + o * PRS_DESC_BYTES);

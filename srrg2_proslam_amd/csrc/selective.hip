@@ -58,13 +58,6 @@ struct SelArgs {
   int maxc, md, cell, gw, gh;
 };
 
-__device__ __forceinline__ uint32_t ordered(const float f) {  // monotone float -> uint (no NaN here)
-  const uint32_t u = __float_as_uint(f);
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ float from_ordered(const uint32_t o) {
-  return __uint_as_float((o & 0x80000000u) ? (o & 0x7fffffffu) : ~o);
-}
 __device__ __forceinline__ int reflect_clamp(int v, const int n) {  // BORDER_REFLECT_101 for the 3 px around the image
   v = v < 0 ? -v : (v >= n ? 2 * n - 2 - v : v);
   return v < 0 ? 0 : (v >= n ? n - 1 : v);

@@ -38,22 +38,6 @@ struct StepShared {
   int edge;       // the new edge (split)
 };
 
-// C = A * B in double, the expressions of se3_mul
-__device__ __forceinline__ void se3_mul_f64(const double* A, const double* B, double* C) {
-#pragma unroll
-  for (int i = 0; i < 3; ++i) {
-#pragma unroll
-    for (int j = 0; j < 3; ++j) {
-      C[4 * i + j] = (A[4 * i + 0] * B[0 + j] + A[4 * i + 1] * B[4 + j]) + A[4 * i + 2] * B[8 + j];
-    }
-    C[4 * i + 3] = ((A[4 * i + 0] * B[3] + A[4 * i + 1] * B[7]) + A[4 * i + 2] * B[11]) + A[4 * i + 3];
-  }
-  C[12] = 0.0;
-  C[13] = 0.0;
-  C[14] = 0.0;
-  C[15] = 1.0;
-}
-
 // one workgroup per sequence: the first wave loads, thread 0 does the pose arithmetic and publishes the decision through LDS, the
 // workgroup stores the matrices and, on a split (block-uniform), copies the finished map out and clears its measurement counts
 __global__ __launch_bounds__(kThreads) void session_step_kernel(const StepArgs a) {
@@ -144,7 +128,7 @@ __global__ __launch_bounds__(kThreads) void session_step_kernel(const StepArgs a
           Xc[i] = gx[i];
           Pd[i] = (double) pose_new[i];
         }
-        se3_mul_f64(Xc, Pd, Xn);
+        se3_mul(Xc, Pd, Xn);
 #pragma unroll
         for (int i = 0; i < 16; ++i) {
           sh.node_X[i] = Xn[i];

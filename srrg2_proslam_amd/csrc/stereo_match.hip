@@ -57,18 +57,6 @@ constexpr uint32_t kNone16   = 0xffffu;
     }                                                                       \
   } while (0)
 
-__device__ __forceinline__ int hamming_u32x4(const u32x4& a0, const u32x4& a1, const u32x4& b0, const u32x4& b1) {
-  int d = __popc(a0.x ^ b0.x);
-  d += __popc(a0.y ^ b0.y);
-  d += __popc(a0.z ^ b0.z);
-  d += __popc(a0.w ^ b0.w);
-  d += __popc(a1.x ^ b1.x);
-  d += __popc(a1.y ^ b1.y);
-  d += __popc(a1.z ^ b1.z);
-  d += __popc(a1.w ^ b1.w);
-  return d;
-}
-
 // exclusive scan of n counters by ONE wave (all 64 lanes of the calling wave take part).
 // in[] holds counts, out[] receives the exclusive prefix (out may alias in).
 // returns the total in every lane.  Up to 8 counters per lane are read with independent loads.
@@ -95,14 +83,7 @@ __device__ __forceinline__ uint32_t wave_exclusive_scan(const TIn* in, TOut* out
       sum += r < n ? (uint32_t) in[r] : 0u;
     }
   }
-  uint32_t incl = sum;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const uint32_t o = __shfl_up(incl, d, 64);
-    if (lane >= d) {
-      incl += o;
-    }
-  }
+  const uint32_t incl = wave_inclusive_scan_shfl(sum, lane);
   uint32_t run = incl - sum;
   if (chunk <= 8) {
 #pragma unroll
@@ -461,7 +442,7 @@ __global__ __launch_bounds__(kStereoThreads) void stereo_match_kernel(const Ster
                   e0 = gdR[2 * idx_r];
                   e1 = gdR[2 * idx_r + 1];
                 }
-                dist[j] = (uint32_t) hamming_u32x4(d0, d1, e0, e1);
+                dist[j] = (uint32_t) hamming256(d0, d1, e0, e1);
               }
             }
           }
@@ -516,7 +497,7 @@ __global__ __launch_bounds__(kStereoThreads) void stereo_match_kernel(const Ster
                   e0 = gdR[2 * idx_r];
                   e1 = gdR[2 * idx_r + 1];
                 }
-                const uint32_t d = (uint32_t) hamming_u32x4(d0, d1, e0, e1);
+                const uint32_t d = (uint32_t) hamming256(d0, d1, e0, e1);
                 if (d < best) {  // epipolar_impl.cpp:158-164
                   second = best;
                   best   = d;
@@ -655,19 +636,7 @@ __global__ __launch_bounds__(kStereoThreads) void stereo_match_kernel(const Ster
             fd[0]       = gdL[2 * i];
             fd[1]       = gdL[2 * i + 1];
           }
-          // triangulator_rigid_stereo.cpp:39-45,60-85 (operation order kept)
-          float4 pt = make_float4(0.f, 0.f, 0.f, 0.f);
-          if (!(x_L - x_R < a.tri.minimum_disparity_pixels)) {
-            float depth = a.tri.infinity_depth_meters;
-            if (x_L > x_R) {
-              depth = a.tri.b_x / (x_L - x_R);
-            }
-            pt.z = depth;
-            pt.x = 1 / a.tri.fx * (x_L - a.tri.cx) * depth;
-            pt.y = 1 / a.tri.fy * ((y_L + y_R) / 2 - a.tri.cy) * depth;
-            pt.w = 1.0f;
-          }
-          reinterpret_cast<float4*>(a.b.fixed_xyz)[g] = pt;
+          reinterpret_cast<float4*>(a.b.fixed_xyz)[g] = triangulate_rectified(a.tri, x_L, y_L, x_R, y_R);
         }
       }
       fixed_base += misc[2];
@@ -709,20 +678,8 @@ __global__ __launch_bounds__(256) void triangulate_kernel(const prs_triangulator
                                                           int64_t n,
                                                           float4* __restrict__ xyz4) {
   for (int64_t i = (int64_t) blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t) gridDim.x * blockDim.x) {
-    const float4 m  = uvuv[i];
-    const float x_L = m.x, y_L = m.y, x_R = m.z, y_R = m.w;
-    float4 pt       = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (!(x_L - x_R < t.minimum_disparity_pixels)) {
-      float depth = t.infinity_depth_meters;
-      if (x_L > x_R) {
-        depth = t.b_x / (x_L - x_R);
-      }
-      pt.z = depth;
-      pt.x = 1 / t.fx * (x_L - t.cx) * depth;
-      pt.y = 1 / t.fy * ((y_L + y_R) / 2 - t.cy) * depth;
-      pt.w = 1.0f;
-    }
-    xyz4[i] = pt;
+    const float4 m = uvuv[i];
+    xyz4[i]        = triangulate_rectified(t, m.x, m.y, m.z, m.w);
   }
 }
 

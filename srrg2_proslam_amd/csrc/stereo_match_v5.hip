@@ -66,18 +66,6 @@ constexpr uint32_t kOutRescored = 1u << 27;
     }                                                                       \
   } while (0)
 
-__device__ __forceinline__ uint32_t hamming5(const q32& a0, const q32& a1, const q32& b0, const q32& b1) {
-  uint32_t d = __popc(a0.x ^ b0.x);
-  d += __popc(a0.y ^ b0.y);
-  d += __popc(a0.z ^ b0.z);
-  d += __popc(a0.w ^ b0.w);
-  d += __popc(a1.x ^ b1.x);
-  d += __popc(a1.y ^ b1.y);
-  d += __popc(a1.z ^ b1.z);
-  d += __popc(a1.w ^ b1.w);
-  return d;
-}
-
 // Keys are (col << 16 | index) with col < 32768: 31-bit values, and so are the compare bounds.  For such
 // a, b the top bit of a - b says a < b, which needs no compare-to-VCC round trip (every VALU write of
 // VCC costs wait states before the next VALU read of it on gfx950): below_bits shifts the four sign bits
@@ -116,19 +104,6 @@ __device__ __attribute__((noinline)) void sweep_pooled_window(uint32_t* w, const
   }
 }
 
-// inclusive prefix sum over the 64 lanes of a wave on the DPP network (round 4; was six ds_bpermute round trips): Hillis-Steele inside
-// every row of 16 lanes (row_shr 1, 2, 4, 8, lanes shifted in from outside a row read 0), then lane 15 of rows 0 / 2 onto rows 1 / 3
-// (row_bcast:15) and lane 31 onto the upper half (row_bcast:31)
-__device__ __forceinline__ uint32_t wave_inclusive_scan(uint32_t v) {
-  v += (uint32_t) __builtin_amdgcn_update_dpp(0, (int) v, 0x111, 0xf, 0xf, true);  // row_shr:1
-  v += (uint32_t) __builtin_amdgcn_update_dpp(0, (int) v, 0x112, 0xf, 0xf, true);  // row_shr:2
-  v += (uint32_t) __builtin_amdgcn_update_dpp(0, (int) v, 0x114, 0xf, 0xf, true);  // row_shr:4
-  v += (uint32_t) __builtin_amdgcn_update_dpp(0, (int) v, 0x118, 0xf, 0xf, true);  // row_shr:8
-  v += (uint32_t) __builtin_amdgcn_update_dpp(0, (int) v, 0x142, 0xa, 0xf, false); // row_bcast:15 -> rows 1, 3
-  v += (uint32_t) __builtin_amdgcn_update_dpp(0, (int) v, 0x143, 0xc, 0xf, false); // row_bcast:31 -> rows 2, 3
-  return v;
-}
-
 // ONE wave: start[r] = sum over r' < r of the count rounded up to a multiple of four, len[r] = count
 __device__ __forceinline__ void wave_padded_scan(const uint32_t* hist, uint16_t* start, uint16_t* len, int n) {
   const int lane  = threadIdx.x & 63;
@@ -149,7 +124,7 @@ __device__ __forceinline__ void wave_padded_scan(const uint32_t* hist, uint16_t*
       sum += r < n ? ((hist[r] + 3u) & ~3u) : 0u;
     }
   }
-  const uint32_t incl = wave_inclusive_scan(sum);
+  const uint32_t incl = wave_inclusive_scan_dpp(sum);
   uint32_t run        = incl - sum;
   if (chunk <= 8) {
 #pragma unroll
@@ -194,7 +169,7 @@ __device__ __forceinline__ uint32_t wave_scan_u32(uint32_t* cnt, int n) {
       sum += r < n ? cnt[r] : 0u;
     }
   }
-  const uint32_t incl = wave_inclusive_scan(sum);
+  const uint32_t incl = wave_inclusive_scan_dpp(sum);
   uint32_t run        = incl - sum;
   if (chunk <= 8) {
 #pragma unroll
@@ -526,7 +501,7 @@ __global__ __launch_bounds__(kT) void stereo_match5_kernel(const Args5 a) {
                 uint32_t entry = kPoolPruned;
                 if (!(multipass && ((bitsR[q >> 5] >> (q & 31)) & 1u))) {
                   const int idx_r = (int) (sortedR[q] & 0xffffu);
-                  entry           = hamming5(d0, d1, ldR[2 * idx_r], ldR[2 * idx_r + 1]);
+                  entry           = (uint32_t) hamming256(d0, d1, ldR[2 * idx_r], ldR[2 * idx_r + 1]);
                   if (EPI) {
                     const prs_kp2 kr = ldKR[idx_r];
                     const float hd = cL[k].u - kr.u, vd = cL[k].v - kr.v;
@@ -550,7 +525,7 @@ __global__ __launch_bounds__(kT) void stereo_match5_kernel(const Args5 a) {
                 const int q = lo + j;
                 if (!(multipass && ((bitsR[q >> 5] >> (q & 31)) & 1u))) {
                   const int idx_r = (int) (sortedR[q] & 0xffffu);
-                  dist[j]         = hamming5(d0, d1, ldR[2 * idx_r], ldR[2 * idx_r + 1]);
+                  dist[j]         = (uint32_t) hamming256(d0, d1, ldR[2 * idx_r], ldR[2 * idx_r + 1]);
                   if (EPI) {
                     // raw_data_preprocessor_stereo_projective.cpp:117-125
                     const prs_kp2 kr = ldKR[idx_r];
@@ -650,7 +625,7 @@ __global__ __launch_bounds__(kT) void stereo_match5_kernel(const Args5 a) {
                 continue;
               }
               const int idx_r  = (int) (kr & 0xffffu);
-              const uint32_t d = hamming5(d0, d1, ldR[2 * idx_r], ldR[2 * idx_r + 1]);
+              const uint32_t d = (uint32_t) hamming256(d0, d1, ldR[2 * idx_r], ldR[2 * idx_r + 1]);
               if (d < best) {  // epipolar_impl.cpp:158-164
                 second = best;
                 best   = d;
@@ -771,19 +746,7 @@ __global__ __launch_bounds__(kT) void stereo_match5_kernel(const Args5 a) {
             q32* fd = reinterpret_cast<q32*>(a.b.fixed_desc) + 2 * g;
             fd[0]   = dL[2 * k];
             fd[1]   = dL[2 * k + 1];
-            // triangulator_rigid_stereo.cpp:39-45,60-85 (operation order kept)
-            float4 pt = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (!(x_L - x_R < a.tri.minimum_disparity_pixels)) {
-              float depth = a.tri.infinity_depth_meters;
-              if (x_L > x_R) {
-                depth = a.tri.b_x / (x_L - x_R);
-              }
-              pt.z = depth;
-              pt.x = 1 / a.tri.fx * (x_L - a.tri.cx) * depth;
-              pt.y = 1 / a.tri.fy * ((y_L + y_R) / 2 - a.tri.cy) * depth;
-              pt.w = 1.0f;
-            }
-            reinterpret_cast<float4*>(a.b.fixed_xyz)[g] = pt;
+            reinterpret_cast<float4*>(a.b.fixed_xyz)[g] = triangulate_rectified(a.tri, x_L, y_L, x_R, y_R);
           }
         }
       }
