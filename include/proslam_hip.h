@@ -795,7 +795,10 @@ PRS_API int prs_pose_compose_batch(prs_context* ctx, int32_t batch, const float*
 
 /* MotionModelConstantVelocity3D (external; configurations/kitti.conf:257-260): the tracker's guess for the next pose
  * repeats the last inter-frame motion, pose_pred[b] = pose_prev1[b] * (pose_prev2[b]^-1 * pose_prev1[b]), with the
- * rotation block renormalised through its unit quaternion (the recursion amplifies rounding otherwise).
+ * rotation block renormalised through its unit quaternion (the recursion amplifies rounding otherwise).  Up to 120 degrees
+ * of rotation (real part w >= 0.5) the block is rebuilt from the imaginary part, w = sqrt(1 - |q|^2); beyond, that recovery
+ * loses eps / (2 w) -- a milliradian a milliradian away from a half turn -- so the w of the extraction is carried instead: the
+ * round trip costs a few 1e-7 rad at every angle (tests/test_pose_algebra_ref.py, profiles/pose_algebra/README.md).
  * Device arrays of [batch][16] row-major float; pose_pred may alias pose_prev2. */
 PRS_API int prs_motion_predict_batch(prs_context* ctx, int32_t batch, const float* pose_prev2, const float* pose_prev1, float* pose_pred);
 

@@ -462,6 +462,15 @@ def motion_predict(pose_prev2, pose_prev1):
     return out
 
 
+def linear_system(H, b):
+    """a LinearSystem from plain H [36] and b [6] (the statistics stay zero): what gn_step reads"""
+    H, b = _f32(H, (36,)), _f32(b, (6,))
+    sys = LinearSystem()
+    C.memmove(sys.H, _ptr(H), 36 * 4)
+    C.memmove(sys.b, _ptr(b), 6 * 4)
+    return sys
+
+
 def gn_step(sys, damping, X):
     X = _f32(X, (4, 4)).copy()
     rc = lib().orc_gn_step(C.byref(sys), float(damping), _ptr(X))

@@ -383,7 +383,7 @@ static void r2q(const float* T, float* q /* w x y z */) {
 
 /* geometry3d::t2tnq: translation + imaginary part of the normalised quaternion (w >= 0);
  * used at CF/correspondence_finder_projective_base_impl.cpp:182, tests/test_aligners.cpp:630 */
-void orc_t2tnq(const float* T, float* v6) {
+static float t2tnq_w(const float* T, float* v6) {
   float q[4];
   r2q(T, q);
   const float n = sqrtf(((q[0] * q[0] + q[1] * q[1]) + q[2] * q[2]) + q[3] * q[3]);
@@ -397,6 +397,11 @@ void orc_t2tnq(const float* T, float* v6) {
   v6[3] = q[1] * s;
   v6[4] = q[2] * s;
   v6[5] = q[3] * s;
+  return q[0] * s; /* the real part, >= 0 */
+}
+
+void orc_t2tnq(const float* T, float* v6) {
+  (void) t2tnq_w(T, v6);
 }
 
 /* unit quaternion (w, x, y, z) -> rotation matrix, Eigen's toRotationMatrix operation order */
@@ -1649,8 +1654,25 @@ void orc_motion_predict(const float* pose_prev2, const float* pose_prev1, float*
   /* the rotation goes through its unit quaternion: se3_inverse transposes, so a rotation block that has drifted from
    * orthonormality by d comes back as 2 d + d' from this recursion (growth ~2.4x per frame: 1e-7 of float rounding is
    * centimetres of pose error after a dozen frames); the round trip keeps the prediction a rigid transform */
-  orc_t2tnq(raw, v);
-  orc_tnq2t(v, pose_pred);
+  /* up to 120 degrees (w >= 0.5) tnq2t recovers the real part from the imaginary one, good to an ulp; beyond, that recovery loses
+   * eps / (2 w) (a milliradian a milliradian from a half turn), so the w of t2tnq is carried (csrc/prs_se3.h motion_predict) */
+  const float w = t2tnq_w(raw, v);
+  if (w < 0.5f) {
+    float R[9];
+    q2r(w, v[3], v[4], v[5], R);
+    for (int i = 0; i < 3; ++i) {
+      pose_pred[4 * i + 0] = R[3 * i + 0];
+      pose_pred[4 * i + 1] = R[3 * i + 1];
+      pose_pred[4 * i + 2] = R[3 * i + 2];
+      pose_pred[4 * i + 3] = v[i];
+    }
+    pose_pred[12] = 0;
+    pose_pred[13] = 0;
+    pose_pred[14] = 0;
+    pose_pred[15] = 1;
+  } else {
+    orc_tnq2t(v, pose_pred);
+  }
 }
 
 /* MultiAligner3DQR::compute (srrg2_slam_interfaces, external) restated minimally per SURVEY.md

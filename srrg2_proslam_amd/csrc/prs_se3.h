@@ -130,21 +130,9 @@ __device__ __forceinline__ S t2tnq(const S* T, S* v6) {
   return q0 * s;
 }
 
-// perturbation [dt; dq] -> isometry, q = (sqrt(1 - |dq|^2), dq) (VariableSE3QuaternionRight)
+// unit quaternion (w, x, y, z) + translation v6[0..2] -> isometry (Eigen's toRotationMatrix operation order)
 template <bool BOTTOM = true, typename S>
-__device__ __forceinline__ void tnq2t(const S* v6, S* T) {
-  S x = v6[3], y = v6[4], z = v6[5];
-  const S n2 = (x * x + y * y) + z * z;
-  S w;
-  if (n2 < S(1.0)) {
-    w = sqrt_s(S(1.0) - n2);
-  } else {
-    const S s = S(1.0) / sqrt_s(n2);
-    x *= s;
-    y *= s;
-    z *= s;
-    w = S(0.0);
-  }
+__device__ __forceinline__ void tq2t(const S* v6, const S w, const S x, const S y, const S z, S* T) {
   const S tx = S(2.0) * x, ty = S(2.0) * y, tz = S(2.0) * z;
   const S twx = tx * w, twy = ty * w, twz = tz * w;
   const S txx = tx * x, txy = ty * x, txz = tz * x;
@@ -169,16 +157,44 @@ __device__ __forceinline__ void tnq2t(const S* v6, S* T) {
   }
 }
 
+// perturbation [dt; dq] -> isometry, q = (sqrt(1 - |dq|^2), dq) (VariableSE3QuaternionRight).  The real part is RECOVERED from the
+// imaginary one: its error is about eps / (2 w), which is nothing for a perturbation (w near 1) and grows without bound towards a
+// half turn (w near 0): whoever holds the real part of a large rotation passes it to tq2t instead (motion_predict).
+template <bool BOTTOM = true, typename S>
+__device__ __forceinline__ void tnq2t(const S* v6, S* T) {
+  S x = v6[3], y = v6[4], z = v6[5];
+  const S n2 = (x * x + y * y) + z * z;
+  S w;
+  if (n2 < S(1.0)) {
+    w = sqrt_s(S(1.0) - n2);
+  } else {
+    const S s = S(1.0) / sqrt_s(n2);
+    x *= s;
+    y *= s;
+    z *= s;
+    w = S(0.0);
+  }
+  tq2t<BOTTOM>(v6, w, x, y, z, T);
+}
+
 // MotionModelConstantVelocity3D: R = P1 * (P2^-1 * P1), the rotation block renormalised through its unit quaternion (the recursion
 // would otherwise amplify the block's drift from orthonormality by ~2.4x per frame: se3_inverse transposes).  R must not alias P2 / P1.
+// Here the quaternion is a whole pose, not a perturbation.  Up to 120 degrees (t2tnq's positive-trace branch, w >= 0.5) the rotation
+// is rebuilt by tnq2t, which recovers w from the imaginary part: good to an ulp there.  Beyond (w < 0.5: one of the three
+// largest-diagonal branches) the recovered w would be off by eps / (2 w) -- a milliradian a milliradian away from a half turn -- so
+// the w that t2tnq computed is carried into tq2t: the round trip then costs a few 1e-7 rad at every angle.
 // (motion_predict_kernel in mapping.hip and the session step in session.hip evaluate this one function.)
 __device__ __forceinline__ void motion_predict(const float* P2, const float* P1, float* R) {
   float I2[16], M[16], raw[16], v[6];
   se3_inverse(P2, I2);
   se3_mul(I2, P1, M);
   se3_mul(P1, M, raw);
-  t2tnq(raw, v);
-  tnq2t(v, R);
+  const float w = t2tnq(raw, v);
+  if (w < 0.5f) {
+    tq2t(v, w, v[3], v[4], v[5], R);
+  } else {
+    tnq2t(v, R);
+  }
 }
 
 // The aligner sums its normal equations in the CAMERA frame (align.hip, factor_accumulate): with A = [R | t] the transform points

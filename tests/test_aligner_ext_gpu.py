@@ -89,21 +89,34 @@ def test_inlier_flags_and_prior_parity_batched(oracle, cfg_name, fused):
                            env=env, capture_output=True, text=True, cwd=os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
         assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-2000:]
         return
-    B = 12
+    _prior_parity_batched(oracle, cfg_name, 12, 300, PRIOR_INFO)
+
+
+PRIOR_INFO = (3.0, 3.0, 3.0, 50.0, 50.0, 50.0)
+FAR_PRIOR_INFO = (0.3, 0.3, 0.3, 5.0, 5.0, 5.0)  # a tenth of PRIOR_INFO: the checker's run stays finite with the mean 2.5 rad away
+
+
+def _prior_parity_batched(oracle, cfg_name, B, seed0, info, prior_mean_of=None):
+    """B frames through prs_align_batch_run with the motion prior on, against the checker; prior_mean_of(b, X0) -> the prior mean
+    of frame b (default: the initial guess).  -> the checker's poses"""
     kw = dict(enable_inlier_only_runs=1, keep_only_inlier_correspondences=1, inlier_only_iterations=9)
-    cfg, cases = _batched_case(oracle, cfg_name, B, 300)
+    cfg, cases = _batched_case(oracle, cfg_name, B, seed0)
     ctx = ops.Context(0)
     ctx.use_torch_stream()
+    poses = []
     try:
         fs = max(len(c[0]) for c in cases) + 5
         ms = max(len(c[2]["xyz"]) for c in cases) + 3
         frames = ops.AlignFrames(0, B, fs, ms)
         rng = np.random.default_rng(17)
-        Z = np.stack([np.asarray(c[4], np.float32) for c in cases])  # prior mean = the initial guess
+        if prior_mean_of is None:
+            Z = np.stack([np.asarray(c[4], np.float32) for c in cases])  # prior mean = the initial guess
+        else:
+            Z = np.stack([np.asarray(prior_mean_of(b, c[4]), np.float32) for b, c in enumerate(cases)])
         frames.prior_mean = torch.from_numpy(Z.reshape(B, 16).copy()).cuda()
         for b, (fixed, dfix, mp, scale, X0) in enumerate(cases):
             frames.upload(b, fixed, dfix, mp["xyz"], scale, mp["desc"], X0)
-        gap = ops.set_motion_prior(ops.aligner_params(cfg, stop_at_fixed_point=0, **kw), (3.0, 3.0, 3.0, 50.0, 50.0, 50.0))
+        gap = ops.set_motion_prior(ops.aligner_params(cfg, stop_at_fixed_point=0, **kw), info)
         ops.align_batch(ctx, ops.pcf_params(cfg), gap, frames)
         ctx.synchronize()
         for b, (fixed, dfix, mp, scale, X0) in enumerate(cases):
@@ -113,15 +126,37 @@ def test_inlier_flags_and_prior_parity_batched(oracle, cfg_name, fused):
             md = oracle.mean_disparity(fixed) if fixed.shape[1] == 4 else 0.0
             oap = oracle_aligner_params(oracle, cfg, mean_disparity=md, **kw)
             oap.enable_motion_prior = 1
-            for i, v in enumerate((3.0, 3.0, 3.0, 50.0, 50.0, 50.0)):
+            for i, v in enumerate(info):
                 oap.motion_prior_info[i] = v
             res, rcorr = oracle.align_frame(of, oap, fixed, mp["xyz"], scale, X0, prior_mean=Z[b])
             X, gres = frames.X[b].cpu().numpy().reshape(4, 4), frames.result_of(b)
             assert corr_equal(rcorr, frames.corr_of(b)), b
             assert np.array_equal(_bits(np.array(res.X).reshape(4, 4)), _bits(X)), b
             assert (res.status, res.num_inliers, res.num_correspondences, res.iterations) == (gres.status, gres.num_inliers, gres.num_correspondences, gres.iterations), b
+            poses.append((np.array(res.X, np.float32).reshape(4, 4), len(rcorr)))
     finally:
         ctx.close()
+    return poses
+
+
+@pytest.mark.parametrize("axis", [0, 1, 2])
+def test_prior_mean_a_large_rotation_off_the_guess_batched(oracle, axis):
+    """the prior error t2tnq(Z^-1 X) (align.hip add_motion_prior) with Z 2.5 rad about x / y / z off the guess: its rotation is beyond
+    120 degrees, so t2tnq takes the largest-diagonal branch of that axis at every iteration (the other prior tests stay in the
+    positive-trace branch).  One 300-point frame per axis"""
+    import pose_algebra_cases as pa
+    off = pa.pose(pa.rotation(np.eye(3)[axis], -2.5), (0.0, 0.0, 0.0))
+    guesses = []
+
+    def mean(b, X0):
+        guesses.append(np.asarray(X0, np.float32).reshape(4, 4))
+        return (guesses[-1].astype(np.float64) @ off).astype(np.float32)
+
+    (X, n_corr), = _prior_parity_batched(oracle, "kitti", 1, 310 + axis, FAR_PRIOR_INFO, mean)
+    assert np.isfinite(X).all() and n_corr > 40
+    Z = mean(0, guesses[0])
+    for pose in (guesses[0], X):  # the branch at the guess and at the result
+        assert pa.branch_f32(oracle.se3_mul(oracle.se3_inverse(Z), pose)) == (1 + axis, False)
 
 
 def test_motion_predict_batch(oracle, hip_ctx):
