@@ -116,7 +116,8 @@ PRS_API int prs_version(void);
  * status PRS_ERR_NOT_POSITIVE_DEFINITE; and its Levenberg-Marquardt form: prs_pose_graph_lm_params, prs_pose_graph_lm_result and the
  * prs_pose_graph_lm_* / prs_pose_graph_optimize_lm* entry points; and the closure merger: prs_closure_merger_params,
  * prs_closure_merge_batch, the prs_closure_merge* entry points and prs_map_merge_closure; and the local-map manager:
- * prs_session_params, prs_session_batch and the prs_session_* entry points).  Callers memset() parameter structs before
+ * prs_session_params, prs_session_batch and the prs_session_* entry points; and the place bank: prs_place_bank,
+ * prs_place_bank_append, prs_place_bank_links and the prs_place_bank_* entry points).  Callers memset() parameter structs before
  * filling them, so that fields they do not know select the shipped defaults (all zero). */
 #define PRS_ABI_VERSION 104
 PRS_API int prs_abi_check(int32_t header_version, uint64_t sizeof_stereo_params, uint64_t sizeof_pcf_params, uint64_t sizeof_aligner_params,
@@ -1199,7 +1200,8 @@ PRS_API int prs_place_db_size(const prs_place_db* db, int32_t* maps, int32_t* ro
  * number of maps stored before it; uploads and synchronises */
 PRS_API int prs_place_db_add(prs_place_db* db, int64_t graph_id, const float* xyz, const uint8_t* desc, const uint8_t* valid, int32_t n);
 /* device pointers, asynchronous on the context's stream: three kernel launches, no allocation and no synchronisation
- * (graph-capturable; a captured query holds the database's buffers and size as they were at capture) */
+ * (graph-capturable; a captured query holds the database's buffers and size as they were at capture -- prs_place_bank below keeps
+ * its sizes on the device) */
 PRS_API int prs_place_query_batch(prs_place_db* db, const prs_place_params* params, const prs_place_queries* queries);
 /* host pointers, one query: candidates [max_candidates], corr [max_candidates][corr_stride], n_corr [max_candidates], match_counts
  * [maps] or NULL.  Returns the query's status. */
@@ -1209,6 +1211,82 @@ PRS_API int prs_place_query(prs_place_db* db, const prs_place_params* params, in
 /* device pointers, asynchronous: after prs_place_query_batch, fill the pair slots of a loop-closure batch (one kernel launch) */
 PRS_API int prs_place_gather_pairs(prs_place_db* db, const prs_place_params* params, const prs_place_queries* queries,
                                    const prs_place_pairs* pairs);
+
+/* ------------------------------------------------------------------------------------------------
+ * Place bank: B independent place databases, one per sequence, whose contents AND sizes live on the device.  The reference keeps one
+ * tree per SLAM instance (MultiLoopDetectorHBST3D, correspondence_finder_hbst.cpp:47-74); a prs_place_db shared by a batch would let
+ * sequence 3 find sequence 5's maps and compare positions in an interleaved list.  Query b searches database b only, a finished map
+ * is stored by a kernel from the session's hand-over slots (prs_session_batch.handover_*), and nothing is sized on the host after
+ * creation: a captured step sees the maps stored by earlier replays.  prs_place_db_* is unchanged and keeps serving the one-sequence
+ * adapters and the plugin.
+ *   arenas       fixed at creation, per sequence the arrays of a prs_place_db: desc [row_stride][32], xyz [row_stride][4], row_pidx
+ *                [row_stride], tile_map [row_stride / 16], map_off / map_rows / map_gid [map_stride]; counters n_maps, n_rows,
+ *                max_map_rows [batch]; node_of_map [batch][map_stride] int32, -1 where nothing is stored.  row_stride is rounded up
+ *                to a multiple of 16 (a 16-row tile never spans two maps).
+ *   append       prs_place_db_add on the device (addPreviousQuery), one workgroup per sequence: the Valid rows in point order on the
+ *                arena's tail, padded with zero rows (row_pidx -1) to a multiple of 16; xyz is stored as (x, y, z, 0), zeros
+ *                without xyz.  After an append the arena holds what prs_place_db_add builds from the same rows, so queries are
+ *                bit-equal.  node_of_map = (int32) (graph_id - graph_id_base[b]) (base 0 without the array).  Per sequence
+ *                (status[]), nothing written and the counters unchanged in every case, tested in this order: n_query == 0
+ *                PRS_WARN_EMPTY_INPUT (the session's "no split this frame"); a negative n_query or graph id PRS_ERR_RANGE; n_query >
+ *                query_stride PRS_ERR_CAPACITY; a graph id already stored IN THIS SEQUENCE PRS_ERR_RANGE; n_maps == map_stride or
+ *                n_rows + padded rows > row_stride PRS_ERR_CAPACITY.  n_query > 0 without a Valid row stores a map of 0 rows.
+ *   query        every rule of the block comment above with the sequence's own indices; sizes are read from the counters.  The
+ *                grids are sized by capacity, workgroups past the live sizes return at once.  match_counts [0, n_maps[b]) and
+ *                best_keys [0, n_rows[b]) of query b are written, the rest is untouched.  A candidate map larger than
+ *                corr_stride (a slot larger than moving_stride in the gather) is refused on the device: n_corr 0 and
+ *                PRS_ERR_CAPACITY for the query (n_fixed = n_moving = 0 for the slot).
+ *   links        optional outputs that let prs_pose_graph_append_closures consume the result as it stands: candidates_flat =
+ *                b * map_stride + map index (-1 none), query_node = (int32) (graph_id[b] - graph_id_base[b]), -1 for a query
+ *                without candidates or with an error.  The closures struct is then candidates = candidates_flat, n_maps = batch *
+ *                map_stride, node_of_map = the bank's array, node_of_query = query_node, graph_of_query = 0 .. B - 1.
+ * Order within a step is the reference's: query, gather, append -- a map never matches itself because it is not stored yet.  All
+ * three are plain launches on the context's stream: no allocation, no synchronisation, no host read (graph-capturable).
+ * Call-level (return value, nothing launched): PRS_ERR_NULL (a struct or mandatory pointer unset); PRS_ERR_RANGE (batch differs from
+ * the bank's); PRS_ERR_UNSUPPORTED (query_stride outside [1, 65536]; rows not aligned: 4 bytes for the query's descriptors, 16 for
+ * append and gather); PRS_ERR_CAPACITY
+ * (count_stride < map_stride, key_stride < row_stride, corr_stride or moving_stride < min(row_stride, the largest query_stride
+ * prs_place_bank_append_batch has accepted so far): the live sizes are not known on the host, so the capacities decide).
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct prs_place_bank prs_place_bank;
+
+/* the maps to store, shaped like the session's hand-over slots and the first fields of prs_place_queries (device pointers) */
+typedef struct {
+  int32_t batch;                 /* == the bank's */
+  int32_t query_stride;          /* rows per slot, <= 65536 */
+  const uint8_t* desc;           /* [batch][query_stride][32], 16-byte aligned */
+  const uint8_t* valid;          /* optional [batch][query_stride]: nonzero = Valid; NULL: all Valid */
+  const float* xyz;              /* optional [batch][query_stride][4] (x, y, z, -), 16-byte aligned; NULL: zeros are stored */
+  const int32_t* n_query;        /* [batch]; 0: nothing to store */
+  const int64_t* graph_id;       /* [batch] */
+  const int64_t* graph_id_base;  /* optional [batch]: node_of_map = graph_id - base */
+  int32_t* status;               /* out [batch] */
+} prs_place_bank_append;
+
+typedef struct {
+  int32_t* candidates_flat;      /* out [batch][max_candidates]: b * map_stride + map index, -1 = none */
+  int32_t* query_node;           /* out [batch] */
+  const int64_t* graph_id_base;  /* optional [batch] */
+} prs_place_bank_links;
+
+/* row_stride is rounded up to a multiple of 16; batch in [1, 65535], map_stride >= 1, row_stride in [1, 2^20] (PRS_ERR_RANGE) */
+PRS_API int prs_place_bank_create(prs_context* ctx, int32_t batch, int32_t map_stride, int32_t row_stride, prs_place_bank** bank);
+PRS_API int prs_place_bank_destroy(prs_place_bank* bank);
+/* asynchronous, one launch (graph-capturable): every sequence empty, node_of_map -1 */
+PRS_API int prs_place_bank_clear(prs_place_bank* bank);
+/* host arrays [batch] (each may be NULL); copies the counters back and synchronises: tests and tools only */
+PRS_API int prs_place_bank_sizes(prs_place_bank* bank, int32_t* maps, int32_t* rows, int32_t* max_map_rows);
+/* sizeof prs_place_bank_append, prs_place_bank_links as the library was compiled (bindings check) */
+PRS_API void prs_place_bank_struct_sizes(uint64_t* sizes2);
+/* node_of_map lives in the caller's device array [batch][map_stride] from now on (what prs_pose_graph_closures.node_of_map reads);
+ * the current contents are copied over (asynchronous).  NULL: back to the bank's own array.  The array must outlive the bank's use. */
+PRS_API int prs_place_bank_bind_node_of_map(prs_place_bank* bank, int32_t* node_of_map);
+/* device pointers, asynchronous on the context's stream, one launch each (prs_place_bank_query_batch: three) */
+PRS_API int prs_place_bank_append_batch(prs_place_bank* bank, const prs_place_bank_append* in);
+PRS_API int prs_place_bank_query_batch(prs_place_bank* bank, const prs_place_params* params, const prs_place_queries* queries,
+                                       const prs_place_bank_links* links /* may be NULL */);
+PRS_API int prs_place_bank_gather_pairs(prs_place_bank* bank, const prs_place_params* params, const prs_place_queries* queries,
+                                        const prs_place_pairs* pairs);
 
 /* ================================================================================================
  * Pose-graph optimiser: SE(3) graphs with loop closures (the consumer of the loop detector's accepted closures)

@@ -342,6 +342,17 @@ class PlacePairs(C.Structure):
                 ("X", C.c_void_p)]
 
 
+class PlaceBankAppend(C.Structure):
+    """prs_place_bank_append (device pointers)"""
+    _fields_ = [("batch", C.c_int32), ("query_stride", C.c_int32), ("desc", C.c_void_p), ("valid", C.c_void_p), ("xyz", C.c_void_p),
+                ("n_query", C.c_void_p), ("graph_id", C.c_void_p), ("graph_id_base", C.c_void_p), ("status", C.c_void_p)]
+
+
+class PlaceBankLinks(C.Structure):
+    """prs_place_bank_links (device pointers)"""
+    _fields_ = [("candidates_flat", C.c_void_p), ("query_node", C.c_void_p), ("graph_id_base", C.c_void_p)]
+
+
 DAMPING_DIAG, DAMPING_IDENTITY = 0, 1  # PRS_DAMPING_*
 POSE_GRAPH_MAX_ITERATIONS = 32         # PRS_POSE_GRAPH_MAX_ITERATIONS
 
@@ -500,6 +511,15 @@ SYMBOLS = {
     "prs_place_query_batch": (C.c_int, [_vp, C.POINTER(PlaceParams), C.POINTER(PlaceQueries)]),
     "prs_place_query": (C.c_int, [_vp, C.POINTER(PlaceParams), C.c_int64, _vp, _vp, C.c_int32, _vp, _i32p, _vp, C.c_int32, _vp, _vp]),
     "prs_place_gather_pairs": (C.c_int, [_vp, C.POINTER(PlaceParams), C.POINTER(PlaceQueries), C.POINTER(PlacePairs)]),
+    "prs_place_bank_create": (C.c_int, [_vp, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_void_p)]),
+    "prs_place_bank_destroy": (C.c_int, [_vp]),
+    "prs_place_bank_clear": (C.c_int, [_vp]),
+    "prs_place_bank_sizes": (C.c_int, [_vp, _vp, _vp, _vp]),
+    "prs_place_bank_struct_sizes": (None, [C.POINTER(C.c_uint64)]),
+    "prs_place_bank_bind_node_of_map": (C.c_int, [_vp, _vp]),
+    "prs_place_bank_append_batch": (C.c_int, [_vp, C.POINTER(PlaceBankAppend)]),
+    "prs_place_bank_query_batch": (C.c_int, [_vp, C.POINTER(PlaceParams), C.POINTER(PlaceQueries), C.POINTER(PlaceBankLinks)]),
+    "prs_place_bank_gather_pairs": (C.c_int, [_vp, C.POINTER(PlaceParams), C.POINTER(PlaceQueries), C.POINTER(PlacePairs)]),
     "prs_pose_graph_workspace_bytes": (C.c_uint64, [C.c_int32, C.c_int32, C.c_int64]),
     "prs_pose_graph_struct_sizes": (None, [C.POINTER(C.c_uint64)]),
     "prs_pose_graph_optimize_batch": (C.c_int, [_vp, C.POINTER(PoseGraphParams), C.POINTER(PoseGraphs)]),

@@ -20,6 +20,11 @@
 //                        age and inlier rules, the candidates in ascending map index (capped at max_candidates), and per candidate the
 //                        correspondences: every row of the map with a key, in ascending row = ascending reference point index.
 // prs_place_gather_pairs adds a fourth (place_gather_kernel): the pair slots of a loop-closure batch from the candidate lists.
+//
+// The place bank (prs_place_bank_*) is B such databases in fixed device arenas, one per sequence, whose sizes are device counters.
+// Its query is the same three launches (place_bank_init / _score / _select_kernel) over grids sized by capacity; the bodies of the
+// score, select and gather kernels are device functions over a per-sequence view, shared by both forms.  place_bank_append_kernel
+// stores a finished map from the session's hand-over slot as prs_place_db_add would, one workgroup per sequence.
 #include <string.h>
 
 #include <cmath>
@@ -42,6 +47,23 @@ struct prs_place_db {
   int32_t* map_rows  = nullptr;      // [map_cap] stored descriptors (pads excluded)
   int64_t* map_gid   = nullptr;      // [map_cap] graph id
   std::unordered_map<int64_t, int32_t> index_of;
+};
+
+// B databases in fixed arenas; the sizes live in `counters` on the device (the host knows capacities only)
+struct prs_place_bank {
+  prs_context* ctx = nullptr;
+  int32_t batch = 0, map_stride = 0, row_stride = 0;  // row_stride: a multiple of 16
+  int32_t max_query_stride = 0;   // the largest slot an append has been called with: no stored map is larger
+  uint8_t* desc      = nullptr;   // [batch][row_stride][32]
+  float* xyz         = nullptr;   // [batch][row_stride][4]
+  int32_t* row_pidx  = nullptr;   // [batch][row_stride]
+  int32_t* tile_map  = nullptr;   // [batch][row_stride / 16]
+  int32_t* map_off   = nullptr;   // [batch][map_stride]
+  int32_t* map_rows  = nullptr;   // [batch][map_stride]
+  int64_t* map_gid   = nullptr;   // [batch][map_stride]
+  int32_t* own_nodes = nullptr;   // [batch][map_stride] the bank's node_of_map
+  int32_t* node_of_map = nullptr; // own_nodes, or the array prs_place_bank_bind_node_of_map named
+  int32_t* counters  = nullptr;   // n_maps [batch] | n_rows [batch] | max_map_rows [batch]
 };
 
 namespace prs {
@@ -88,7 +110,23 @@ __device__ __forceinline__ int clamp_n(const int n, const int stride) {
   return n < 0 ? 0 : (n > stride ? stride : n);
 }
 
-__global__ __launch_bounds__(kPdThreads) void place_score_kernel(const PlaceArgs a) {
+// one sequence's database and query as the scoring loop sees them: place_score_kernel fills it from the handle's arrays and host
+// sizes, place_bank_score_kernel from arena b and its device counters
+struct ScoreView {
+  const uint32_t* desc;  // database rows as 8 words
+  const int32_t* row_pidx;
+  const int32_t* tile_map;
+  int rows;
+  const uint32_t* qdesc;  // the query's rows as 8 words
+  const uint8_t* valid;   // or nullptr
+  int nq;                 // clamped to the slot
+  uint32_t* keys;
+  uint32_t* counts;
+  int lim;                // match iff d < lim
+};
+
+// the workgroup (blockIdx.x: database slice, blockIdx.y: query block) of one sequence
+__device__ __forceinline__ void place_score_body(const ScoreView& a) {
   __shared__ __attribute__((aligned(256))) unsigned char bbuf[4 * kPdPlane];
   static_assert(kPdPlane % 256 == 0, "planes must not shift the banks");
   __shared__ int popm[kPdChunk];
@@ -96,13 +134,12 @@ __global__ __launch_bounds__(kPdThreads) void place_score_kernel(const PlaceArgs
   __shared__ uint32_t lut_a[16], lut_b[16];
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave_s = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const size_t b   = blockIdx.z;
-  const int nq     = clamp_n(a.q.n_query[b], a.q.query_stride);
+  const int nq     = a.nq;
   const int qblock = (int) blockIdx.y * kPdRowsWg;
   const int row_begin = (int) blockIdx.x * kPdSlice;
   const int row_end   = row_begin + kPdSlice < a.rows ? row_begin + kPdSlice : a.rows;
-  if (qblock >= nq) {
-    return;  // (block-uniform)
+  if (qblock >= nq || row_begin >= a.rows) {
+    return;  // (block-uniform, before any barrier: a grid sized by capacity ends here past the live sizes)
   }
   if (tid < 16) {
     uint32_t v01, vpm;
@@ -111,8 +148,8 @@ __global__ __launch_bounds__(kPdThreads) void place_score_kernel(const PlaceArgs
     lut_b[tid] = vpm;
   }
   __syncthreads();
-  const uint32_t* __restrict__ gdq = reinterpret_cast<const uint32_t*>(a.q.desc + b * (size_t) a.q.query_stride * PRS_DESC_BYTES);
-  const uint8_t* valid = a.q.valid ? a.q.valid + b * (size_t) a.q.query_stride : nullptr;
+  const uint32_t* __restrict__ gdq = a.qdesc;
+  const uint8_t* valid = a.valid;
   // ---- this wave's query rows: A[t][kb] = bits [64 kb + 16 lg, +16) of row q0 + 16 t + li (absent or not Valid: zeros) ----
   const int q0         = qblock + wave_s * kPdRowsWave;
   const bool wave_live = q0 < nq;
@@ -144,8 +181,8 @@ __global__ __launch_bounds__(kPdThreads) void place_score_kernel(const PlaceArgs
       }
     }
   }
-  uint32_t* keys   = a.q.best_keys + b * (size_t) a.q.key_stride;
-  uint32_t* counts = a.q.match_counts + b * (size_t) a.q.count_stride;
+  uint32_t* keys   = a.keys;
+  uint32_t* counts = a.counts;
   int run_map      = -1;  // the map of the tiles counted in run_count (wave-uniform)
   uint32_t run_count = 0;
   for (int c = row_begin; c < row_end; c += kPdChunk) {
@@ -220,32 +257,66 @@ __global__ __launch_bounds__(kPdThreads) void place_score_kernel(const PlaceArgs
   }
 }
 
+__device__ __forceinline__ ScoreView score_view_of_query(const prs_place_queries& q, const size_t b, const int lim) {
+  ScoreView v;
+  v.qdesc  = reinterpret_cast<const uint32_t*>(q.desc + b * (size_t) q.query_stride * PRS_DESC_BYTES);
+  v.valid  = q.valid ? q.valid + b * (size_t) q.query_stride : nullptr;
+  v.nq     = clamp_n(q.n_query[b], q.query_stride);
+  v.keys   = q.best_keys + b * (size_t) q.key_stride;
+  v.counts = q.match_counts + b * (size_t) q.count_stride;
+  v.lim    = lim;
+  return v;
+}
+
+__global__ __launch_bounds__(kPdThreads) void place_score_kernel(const PlaceArgs a) {
+  ScoreView v  = score_view_of_query(a.q, blockIdx.z, a.lim);
+  v.desc       = a.desc;
+  v.row_pidx   = a.row_pidx;
+  v.tile_map   = a.tile_map;
+  v.rows       = a.rows;
+  place_score_body(v);
+}
+
 // the query's status word: 0, PRS_WARN_EMPTY_INPUT (the reference's "query descriptor vector is empty", :13-18), or a PRS_ERR_* code
-__device__ __forceinline__ int query_status(const PlaceArgs& a, const size_t b) {
-  const int n = a.q.n_query[b];
-  if (a.q.graph_id[b] < 0 || n < 0) {
+__device__ __forceinline__ int query_status(const prs_place_queries& q, const size_t b) {
+  const int n = q.n_query[b];
+  if (q.graph_id[b] < 0 || n < 0) {
     return PRS_ERR_RANGE;
   }
-  if (n > a.q.query_stride) {
+  if (n > q.query_stride) {
     return PRS_ERR_CAPACITY;
   }
   return n == 0 ? PRS_WARN_EMPTY_INPUT : 0;
 }
 
-__global__ __launch_bounds__(kPdThreads) void place_select_kernel(const PlaceArgs a) {
+// one sequence's maps as the selection sees them, and the bank's optional link outputs (all nullptr for a prs_place_db)
+struct SelectView {
+  int maps;
+  const int64_t* map_gid;
+  const int32_t* map_off;
+  const int32_t* map_rows;
+  const int32_t* row_pidx;
+  int32_t* cand_flat;    // [max_candidates] of this query, or nullptr
+  int32_t flat_base;     // b * map_stride
+  int32_t* query_node;   // this query's word, or nullptr
+  int64_t graph_id_base;
+};
+
+// kBank: the live sizes are not known at the call, so a candidate map larger than corr_stride is refused here
+template <bool kBank>
+__device__ __forceinline__ void place_select_body(const prs_place_queries& q, const prs_place_params& p, const SelectView& a, const size_t b) {
   __shared__ int s_index;
   __shared__ int s_ncand;
   __shared__ int s_cand[256];  // candidates of the query (max_candidates <= 256)
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const size_t b   = blockIdx.x;
-  const int maxc   = a.p.max_candidates;
-  int status       = query_status(a, b);
+  const int maxc   = p.max_candidates;
+  int status       = query_status(q, b);
   // index_query (:47-55): the stored index of the query's graph id, else the number of maps
   if (tid == 0) {
     s_index = a.maps;
   }
   __syncthreads();
-  const int64_t gid = a.q.graph_id[b];
+  const int64_t gid = q.graph_id[b];
   for (int m = tid; m < a.maps; m += kPdThreads) {
     if (a.map_gid[m] == gid) {
       atomicMin(&s_index, m);
@@ -255,7 +326,7 @@ __global__ __launch_bounds__(kPdThreads) void place_select_kernel(const PlaceArg
   const uint64_t index_query = (uint64_t) s_index;
   // the candidates in ascending map index (:70-90), by one wave
   if (wave == 0) {
-    const uint32_t* counts = a.q.match_counts + b * (size_t) a.q.count_stride;
+    const uint32_t* counts = q.match_counts + b * (size_t) q.count_stride;
     int total = 0;
     if (status >= 0 && status != PRS_WARN_EMPTY_INPUT) {
       for (int base = 0; base < a.maps; base += 64) {
@@ -264,8 +335,8 @@ __global__ __launch_bounds__(kPdThreads) void place_select_kernel(const PlaceArg
         if (m < a.maps) {
           const uint64_t ref  = (uint64_t) m;
           const uint64_t diff = index_query - ref;  // uint64_t: wraps when the query is older than the reference
-          pass = (double) diff > (double) a.p.minimum_age_difference_to_candidates && a.p.relocalize_min_inliers >= 0 &&
-                 counts[m] > (uint32_t) a.p.relocalize_min_inliers;
+          pass = (double) diff > (double) p.minimum_age_difference_to_candidates && p.relocalize_min_inliers >= 0 &&
+                 counts[m] > (uint32_t) p.relocalize_min_inliers;
         }
         const uint64_t mk = __ballot(pass);
         const int pos = total + (int) __builtin_amdgcn_mbcnt_hi((uint32_t) (mk >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t) mk, 0u));
@@ -280,25 +351,41 @@ __global__ __launch_bounds__(kPdThreads) void place_select_kernel(const PlaceArg
       if (total > maxc) {
         status = PRS_ERR_CAPACITY;
       }
-      a.q.n_candidates[b] = total < maxc ? total : maxc;
-      a.q.status[b]       = status;
-      if (a.q.index_query) {
-        a.q.index_query[b] = (int64_t) index_query;
+      q.n_candidates[b] = total < maxc ? total : maxc;
+      q.status[b]       = status;
+      if (q.index_query) {
+        q.index_query[b] = (int64_t) index_query;
+      }
+      if (a.query_node) {
+        *a.query_node = status >= 0 && total > 0 ? (int32_t) (gid - a.graph_id_base) : -1;
       }
     }
   }
   __syncthreads();
   const int ncand = s_ncand;
   if (tid < maxc) {
-    a.q.candidates[b * (size_t) maxc + tid] = tid < ncand ? s_cand[tid] : -1;
+    q.candidates[b * (size_t) maxc + tid] = tid < ncand ? s_cand[tid] : -1;
+    if (a.cand_flat) {
+      a.cand_flat[tid] = tid < ncand ? a.flat_base + s_cand[tid] : -1;
+    }
   }
   // per candidate, its correspondences (:95-127): every row with a key, (fixed = query index, moving = point index, distance)
-  const uint32_t* keys = a.q.best_keys + b * (size_t) a.q.key_stride;
+  const uint32_t* keys = q.best_keys + b * (size_t) q.key_stride;
   for (int k = wave; k < maxc; k += kPdThreads / 64) {
     int n = 0;
     if (k < ncand) {
-      const int m = s_cand[k], off = a.map_off[m], nr = a.map_rows[m];
-      prs_corr* out = a.q.corr + (b * (size_t) maxc + (size_t) k) * (size_t) a.q.corr_stride;
+      const int m = s_cand[k], off = a.map_off[m];
+      int nr      = a.map_rows[m];
+      if (kBank && nr > q.corr_stride) {  // (uniform; written after the barrier that follows the status word above)
+        nr = 0;
+        if (lane == 0) {
+          q.status[b] = PRS_ERR_CAPACITY;
+          if (a.query_node) {
+            *a.query_node = -1;
+          }
+        }
+      }
+      prs_corr* out = q.corr + (b * (size_t) maxc + (size_t) k) * (size_t) q.corr_stride;
       int row = off;  // stored rows of the map: [off, off + nr) (pads follow)
       for (int base = 0; base < nr; base += 64) {
         const int r       = row + base + lane;
@@ -317,9 +404,23 @@ __global__ __launch_bounds__(kPdThreads) void place_select_kernel(const PlaceArg
       }
     }
     if (lane == 0) {
-      a.q.n_corr[b * (size_t) maxc + (size_t) k] = n;
+      q.n_corr[b * (size_t) maxc + (size_t) k] = n;
     }
   }
+}
+
+__global__ __launch_bounds__(kPdThreads) void place_select_kernel(const PlaceArgs a) {
+  SelectView v;
+  v.maps          = a.maps;
+  v.map_gid       = a.map_gid;
+  v.map_off       = a.map_off;
+  v.map_rows      = a.map_rows;
+  v.row_pidx      = a.row_pidx;
+  v.cand_flat     = nullptr;
+  v.flat_base     = 0;
+  v.query_node    = nullptr;
+  v.graph_id_base = 0;
+  place_select_body<false>(a.q, a.p, v, blockIdx.x);
 }
 
 struct GatherArgs {
@@ -333,24 +434,29 @@ struct GatherArgs {
 };
 
 // one wave per pair slot (query b, candidate k): fixed = the query's Valid points in index order, moving = the candidate map's stored
-// points, X = identity; a slot without a candidate gets n = 0 on both sides
-__global__ __launch_bounds__(kPdThreads) void place_gather_kernel(const GatherArgs g) {
+// points, X = identity; a slot without a candidate gets n = 0 on both sides.  desc / xyz / map_off / map_rows: the database of query b;
+// kBank: a map larger than the slot is refused here (n = 0 on both sides), the live sizes are not known at the call
+template <bool kBank>
+__device__ __forceinline__ void place_gather_slot(const prs_place_queries& q, const prs_place_pairs& o, const int maxc, const size_t slot,
+                                                  const size_t b, const int k, const uint8_t* desc, const float* xyz,
+                                                  const int32_t* map_off, const int32_t* map_rows) {
   const int lane = threadIdx.x & 63;
-  const size_t slot = (size_t) blockIdx.x * (kPdThreads / 64) + (threadIdx.x >> 6);
-  if (slot >= (size_t) g.q.batch * (size_t) g.maxc) {
-    return;
+  bool use = k < q.n_candidates[b];  // (a query over max_candidates still fills its slots; other errors have none)
+  int m = 0;
+  if (use) {
+    m = q.candidates[b * (size_t) maxc + (size_t) k];
+    if (kBank && map_rows[m] > o.moving_stride) {
+      use = false;
+    }
   }
-  const size_t b = slot / (size_t) g.maxc;
-  const int k    = (int) (slot % (size_t) g.maxc);
-  const bool use = k < g.q.n_candidates[b];  // (a query over max_candidates still fills its slots; other errors have none)
   int nf = 0, nm = 0;
   if (use) {
-    const int nq = clamp_n(g.q.n_query[b], g.q.query_stride);
-    const uint8_t* valid = g.q.valid ? g.q.valid + b * (size_t) g.q.query_stride : nullptr;
-    const uint4* qd = reinterpret_cast<const uint4*>(g.q.desc + b * (size_t) g.q.query_stride * PRS_DESC_BYTES);
-    const float4* qx = reinterpret_cast<const float4*>(g.q.xyz + b * (size_t) g.q.query_stride * 4);
-    uint4* fd  = reinterpret_cast<uint4*>(g.o.fixed_desc + slot * (size_t) g.o.fixed_stride * PRS_DESC_BYTES);
-    float4* fx = reinterpret_cast<float4*>(g.o.fixed_xyz + slot * (size_t) g.o.fixed_stride * 4);
+    const int nq = clamp_n(q.n_query[b], q.query_stride);
+    const uint8_t* valid = q.valid ? q.valid + b * (size_t) q.query_stride : nullptr;
+    const uint4* qd = reinterpret_cast<const uint4*>(q.desc + b * (size_t) q.query_stride * PRS_DESC_BYTES);
+    const float4* qx = reinterpret_cast<const float4*>(q.xyz + b * (size_t) q.query_stride * 4);
+    uint4* fd  = reinterpret_cast<uint4*>(o.fixed_desc + slot * (size_t) o.fixed_stride * PRS_DESC_BYTES);
+    float4* fx = reinterpret_cast<float4*>(o.fixed_xyz + slot * (size_t) o.fixed_stride * 4);
     for (int base = 0; base < nq; base += 64) {
       const int i    = base + lane;
       const bool in  = i < nq && (!valid || valid[i] != 0);
@@ -363,13 +469,12 @@ __global__ __launch_bounds__(kPdThreads) void place_gather_kernel(const GatherAr
       }
       nf += __popcll(mk);
     }
-    const int m = g.q.candidates[b * (size_t) g.maxc + (size_t) k];
-    const int off = g.map_off[m];
-    nm = g.map_rows[m];
-    const uint4* dd  = reinterpret_cast<const uint4*>(g.desc) + 2 * (size_t) off;
-    const float4* dx = reinterpret_cast<const float4*>(g.xyz) + (size_t) off;
-    uint4* md  = reinterpret_cast<uint4*>(g.o.moving_desc + slot * (size_t) g.o.moving_stride * PRS_DESC_BYTES);
-    float4* mx = reinterpret_cast<float4*>(g.o.moving_xyz + slot * (size_t) g.o.moving_stride * 4);
+    const int off = map_off[m];
+    nm = map_rows[m];
+    const uint4* dd  = reinterpret_cast<const uint4*>(desc) + 2 * (size_t) off;
+    const float4* dx = reinterpret_cast<const float4*>(xyz) + (size_t) off;
+    uint4* md  = reinterpret_cast<uint4*>(o.moving_desc + slot * (size_t) o.moving_stride * PRS_DESC_BYTES);
+    float4* mx = reinterpret_cast<float4*>(o.moving_xyz + slot * (size_t) o.moving_stride * 4);
     for (int i = lane; i < nm; i += 64) {
       md[2 * (size_t) i]     = dd[2 * (size_t) i];
       md[2 * (size_t) i + 1] = dd[2 * (size_t) i + 1];
@@ -377,12 +482,21 @@ __global__ __launch_bounds__(kPdThreads) void place_gather_kernel(const GatherAr
     }
   }
   if (lane < 16) {
-    g.o.X[16 * slot + lane] = (lane % 5 == 0) ? 1.0f : 0.0f;
+    o.X[16 * slot + lane] = (lane % 5 == 0) ? 1.0f : 0.0f;
   }
   if (lane == 0) {
-    g.o.n_fixed[slot]  = nf;
-    g.o.n_moving[slot] = nm;
+    o.n_fixed[slot]  = nf;
+    o.n_moving[slot] = nm;
   }
+}
+
+__global__ __launch_bounds__(kPdThreads) void place_gather_kernel(const GatherArgs g) {
+  const size_t slot = (size_t) blockIdx.x * (kPdThreads / 64) + (threadIdx.x >> 6);
+  if (slot >= (size_t) g.q.batch * (size_t) g.maxc) {
+    return;
+  }
+  place_gather_slot<false>(g.q, g.o, g.maxc, slot, slot / (size_t) g.maxc, (int) (slot % (size_t) g.maxc), g.desc, g.xyz, g.map_off,
+                           g.map_rows);
 }
 
 bool aligned(const void* ptr, size_t a) {
@@ -529,6 +643,263 @@ int db_reserve(prs_place_db* db, int64_t maps, int64_t rows) {
     db->row_cap = (int32_t) rows;
   }
   return PRS_OK;
+}
+
+// ---- place bank: the same three launches over per-sequence arenas whose sizes are device counters, and the append kernel ----
+struct BankDev {
+  uint8_t* desc;
+  float* xyz;
+  int32_t* row_pidx;
+  int32_t* tile_map;
+  int32_t* map_off;
+  int32_t* map_rows;
+  int64_t* map_gid;
+  int32_t* node_of_map;
+  int32_t* n_maps;
+  int32_t* n_rows;
+  int32_t* max_map_rows;
+  int32_t batch, map_stride, row_stride;
+};
+
+struct BankArgs {
+  prs_place_queries q;
+  prs_place_params p;
+  BankDev d;
+  prs_place_bank_links links;  // all nullptr without links
+  int lim;
+};
+
+// live sizes of arena b, clamped to the capacities (the counters have one writer, the append kernel, which keeps them inside)
+__device__ __forceinline__ int bank_rows(const BankDev& d, const size_t b) {
+  return clamp_n(d.n_rows[b], d.row_stride);
+}
+__device__ __forceinline__ int bank_maps(const BankDev& d, const size_t b) {
+  return clamp_n(d.n_maps[b], d.map_stride);
+}
+
+__global__ __launch_bounds__(kPdThreads) void place_bank_init_kernel(const BankArgs a) {
+  const size_t b  = blockIdx.y;
+  const size_t i0 = (size_t) blockIdx.x * kPdThreads + threadIdx.x;
+  const size_t step = (size_t) gridDim.x * kPdThreads;
+  const size_t rows = (size_t) bank_rows(a.d, b), maps = (size_t) bank_maps(a.d, b);
+  for (size_t i = i0; i < rows; i += step) {
+    a.q.best_keys[b * (size_t) a.q.key_stride + i] = kNoKey;
+  }
+  for (size_t i = i0; i < maps; i += step) {
+    a.q.match_counts[b * (size_t) a.q.count_stride + i] = 0u;
+  }
+}
+
+__global__ __launch_bounds__(kPdThreads) void place_bank_score_kernel(const BankArgs a) {
+  const size_t b = blockIdx.z;
+  ScoreView v    = score_view_of_query(a.q, b, a.lim);
+  v.desc         = reinterpret_cast<const uint32_t*>(a.d.desc) + b * (size_t) a.d.row_stride * 8;
+  v.row_pidx     = a.d.row_pidx + b * (size_t) a.d.row_stride;
+  v.tile_map     = a.d.tile_map + b * (size_t) (a.d.row_stride / 16);
+  v.rows         = bank_rows(a.d, b);
+  place_score_body(v);
+}
+
+__global__ __launch_bounds__(kPdThreads) void place_bank_select_kernel(const BankArgs a) {
+  const size_t b = blockIdx.x;
+  SelectView v;
+  v.maps          = bank_maps(a.d, b);
+  v.map_gid       = a.d.map_gid + b * (size_t) a.d.map_stride;
+  v.map_off       = a.d.map_off + b * (size_t) a.d.map_stride;
+  v.map_rows      = a.d.map_rows + b * (size_t) a.d.map_stride;
+  v.row_pidx      = a.d.row_pidx + b * (size_t) a.d.row_stride;
+  v.cand_flat     = a.links.candidates_flat ? a.links.candidates_flat + b * (size_t) a.p.max_candidates : nullptr;
+  v.flat_base     = (int32_t) b * a.d.map_stride;
+  v.query_node    = a.links.query_node ? a.links.query_node + b : nullptr;
+  v.graph_id_base = a.links.graph_id_base ? a.links.graph_id_base[b] : 0;
+  place_select_body<true>(a.q, a.p, v, b);
+}
+
+struct BankGatherArgs {
+  prs_place_queries q;
+  prs_place_pairs o;
+  BankDev d;
+  int maxc;
+};
+
+__global__ __launch_bounds__(kPdThreads) void place_bank_gather_kernel(const BankGatherArgs g) {
+  const size_t slot = (size_t) blockIdx.x * (kPdThreads / 64) + (threadIdx.x >> 6);
+  if (slot >= (size_t) g.q.batch * (size_t) g.maxc) {
+    return;
+  }
+  const size_t b = slot / (size_t) g.maxc;
+  place_gather_slot<true>(g.q, g.o, g.maxc, slot, b, (int) (slot % (size_t) g.maxc), g.d.desc + b * (size_t) g.d.row_stride * PRS_DESC_BYTES,
+                          g.d.xyz + b * (size_t) g.d.row_stride * 4, g.d.map_off + b * (size_t) g.d.map_stride,
+                          g.d.map_rows + b * (size_t) g.d.map_stride);
+}
+
+__global__ __launch_bounds__(kPdThreads) void place_bank_clear_kernel(const BankDev d) {
+  const size_t i = (size_t) blockIdx.x * kPdThreads + threadIdx.x;
+  if (i < (size_t) d.batch * (size_t) d.map_stride) {
+    d.node_of_map[i] = -1;
+  }
+  if (i < (size_t) d.batch) {
+    d.n_maps[i]       = 0;
+    d.n_rows[i]       = 0;
+    d.max_map_rows[i] = 0;
+  }
+}
+
+struct AppendArgs {
+  prs_place_bank_append in;
+  BankDev d;
+};
+
+// prs_place_db_add on the device, one workgroup per sequence: checks, count of the Valid rows, compaction in point order onto the
+// arena's tail (ballot + mbcnt prefix per wave, the waves' counts through LDS, a running offset across chunks of 256 rows), pad rows,
+// tile and map entries, and last of all the counters, by one thread.  Every early return is block-uniform.
+__global__ __launch_bounds__(kPdThreads) void place_bank_append_kernel(const AppendArgs a) {
+  __shared__ int s_wave[kPdThreads / 64];
+  __shared__ int s_dup;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const size_t b    = blockIdx.x;
+  const int n       = a.in.n_query[b];
+  const int64_t gid = a.in.graph_id[b];
+  const int maps    = bank_maps(a.d, b), rows = bank_rows(a.d, b);
+  int status        = PRS_OK;
+  if (n == 0) {
+    status = PRS_WARN_EMPTY_INPUT;
+  } else if (n < 0 || gid < 0) {
+    status = PRS_ERR_RANGE;
+  } else if (n > a.in.query_stride) {
+    status = PRS_ERR_CAPACITY;
+  }
+  if (status != PRS_OK) {
+    if (tid == 0) {
+      a.in.status[b] = status;
+    }
+    return;
+  }
+  if (tid == 0) {
+    s_dup = 0;
+  }
+  __syncthreads();
+  const int64_t* map_gid = a.d.map_gid + b * (size_t) a.d.map_stride;
+  for (int m = tid; m < maps; m += kPdThreads) {
+    if (map_gid[m] == gid) {
+      s_dup = 1;
+    }
+  }
+  // the Valid rows of the slot
+  const uint8_t* valid = a.in.valid ? a.in.valid + b * (size_t) a.in.query_stride : nullptr;
+  int mine = 0;
+  for (int base = 0; base < n; base += kPdThreads) {
+    const int i = base + tid;
+    mine += (int) __popcll(__ballot(i < n && (!valid || valid[i] != 0)));  // (per wave: every lane holds its wave's count)
+  }
+  if (lane == 0) {
+    s_wave[wave] = mine;
+  }
+  __syncthreads();
+  int nk = 0;
+#pragma unroll
+  for (int w = 0; w < kPdThreads / 64; ++w) {
+    nk += s_wave[w];
+  }
+  const int padded = (nk + 15) / 16 * 16;
+  if (s_dup != 0) {
+    status = PRS_ERR_RANGE;
+  } else if (maps >= a.d.map_stride || padded > a.d.row_stride - rows) {
+    status = PRS_ERR_CAPACITY;
+  }
+  if (status != PRS_OK) {
+    if (tid == 0) {
+      a.in.status[b] = status;
+    }
+    return;
+  }
+  const uint4* src_d  = reinterpret_cast<const uint4*>(a.in.desc + b * (size_t) a.in.query_stride * PRS_DESC_BYTES);
+  const float4* src_x = a.in.xyz ? reinterpret_cast<const float4*>(a.in.xyz + b * (size_t) a.in.query_stride * 4) : nullptr;
+  const size_t r0     = b * (size_t) a.d.row_stride + (size_t) rows;  // the first new row, counted over the whole bank
+  uint4* dst_d        = reinterpret_cast<uint4*>(a.d.desc) + 2 * r0;
+  float4* dst_x       = reinterpret_cast<float4*>(a.d.xyz) + r0;
+  int32_t* dst_p      = a.d.row_pidx + r0;
+  int done = 0;  // rows stored by the chunks before this one
+  for (int base = 0; base < n; base += kPdThreads) {
+    __syncthreads();  // (s_wave of the chunk before, or of the count, has been read)
+    const int i       = base + tid;
+    const bool in     = i < n && (!valid || valid[i] != 0);
+    const uint64_t mk = __ballot(in);
+    if (lane == 0) {
+      s_wave[wave] = (int) __popcll(mk);
+    }
+    __syncthreads();
+    int before = 0, chunk = 0;
+#pragma unroll
+    for (int w = 0; w < kPdThreads / 64; ++w) {
+      before += w < wave ? s_wave[w] : 0;
+      chunk += s_wave[w];
+    }
+    if (in) {
+      const int pos = done + before + (int) __builtin_amdgcn_mbcnt_hi((uint32_t) (mk >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t) mk, 0u));
+      if (pos < padded) {  // (always: pos < nk; keeps a sequence inside its arena whatever the inputs do between the two passes)
+        dst_d[2 * (size_t) pos]     = src_d[2 * (size_t) i];
+        dst_d[2 * (size_t) pos + 1] = src_d[2 * (size_t) i + 1];
+        float4 x = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        if (src_x) {
+          x   = src_x[i];
+          x.w = 0.0f;
+        }
+        dst_x[pos] = x;
+        dst_p[pos] = i;
+      }
+    }
+    done += chunk;
+  }
+  // pad rows, the tiles of the map, the map's entry
+  for (int r = (done < nk ? done : nk) + tid; r < padded; r += kPdThreads) {
+    dst_d[2 * (size_t) r]     = make_uint4(0u, 0u, 0u, 0u);
+    dst_d[2 * (size_t) r + 1] = make_uint4(0u, 0u, 0u, 0u);
+    dst_x[r]                  = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    dst_p[r]                  = -1;
+  }
+  int32_t* tiles = a.d.tile_map + b * (size_t) (a.d.row_stride / 16) + (size_t) (rows / 16);
+  for (int t = tid; t < padded / 16; t += kPdThreads) {
+    tiles[t] = maps;
+  }
+  __syncthreads();
+  if (tid == 0) {
+    const size_t m = b * (size_t) a.d.map_stride + (size_t) maps;
+    a.d.map_off[m]     = rows;
+    a.d.map_rows[m]    = nk;
+    a.d.map_gid[m]     = gid;
+    a.d.node_of_map[m] = (int32_t) (gid - (a.in.graph_id_base ? a.in.graph_id_base[b] : 0));
+    a.d.n_maps[b]      = maps + 1;
+    a.d.n_rows[b]      = rows + padded;
+    if (nk > a.d.max_map_rows[b]) {
+      a.d.max_map_rows[b] = nk;
+    }
+    a.in.status[b] = PRS_OK;
+  }
+}
+
+BankDev bank_dev(const prs_place_bank* k) {
+  BankDev d;
+  d.desc         = k->desc;
+  d.xyz          = k->xyz;
+  d.row_pidx     = k->row_pidx;
+  d.tile_map     = k->tile_map;
+  d.map_off      = k->map_off;
+  d.map_rows     = k->map_rows;
+  d.map_gid      = k->map_gid;
+  d.node_of_map  = k->node_of_map;
+  d.n_maps       = k->counters;
+  d.n_rows       = k->counters + k->batch;
+  d.max_map_rows = k->counters + 2 * (size_t) k->batch;
+  d.batch        = k->batch;
+  d.map_stride   = k->map_stride;
+  d.row_stride   = k->row_stride;
+  return d;
+}
+
+// the smallest slot that holds every map the bank can hold
+int32_t bank_largest_map(const prs_place_bank* k) {
+  return k->row_stride < k->max_query_stride ? k->row_stride : k->max_query_stride;
 }
 
 }  // namespace
@@ -853,6 +1224,255 @@ int prs_place_gather_pairs(prs_place_db* db, const prs_place_params* params, con
   const hipError_t e = hipGetLastError();
   if (e != hipSuccess) {
     return ctx_fail_hip(ctx, e, "prs_place_gather_pairs launch");
+  }
+  return PRS_OK;
+}
+
+int prs_place_bank_create(prs_context* ctx, int32_t batch, int32_t map_stride, int32_t row_stride, prs_place_bank** bank) {
+  if (!ctx || !bank) {
+    return PRS_ERR_NULL;
+  }
+  *bank = nullptr;
+  if (batch < 1 || batch > 65535 || map_stride < 1 || row_stride < 1 || row_stride > (1 << 20)) {
+    return ctx_fail(ctx, PRS_ERR_RANGE, "prs_place_bank_create: batch in [1, 65535], map_stride >= 1, row_stride in [1, 2^20]");
+  }
+  if ((int64_t) batch * map_stride > INT32_MAX) {
+    return ctx_fail(ctx, PRS_ERR_RANGE, "prs_place_bank_create: batch * map_stride above 2^31 (the flat candidate index is int32)");
+  }
+  (void) hipSetDevice(ctx->device);
+  prs_place_bank* k = new prs_place_bank();
+  k->ctx        = ctx;
+  k->batch      = batch;
+  k->map_stride = map_stride;
+  k->row_stride = (row_stride + 15) / 16 * 16;
+  const size_t rows = (size_t) batch * (size_t) k->row_stride, maps = (size_t) batch * (size_t) map_stride;
+  bool ok = hipMalloc(&k->desc, rows * PRS_DESC_BYTES) == hipSuccess;
+  ok      = ok && hipMalloc(&k->xyz, rows * 16) == hipSuccess;
+  ok      = ok && hipMalloc(&k->row_pidx, rows * 4) == hipSuccess;
+  ok      = ok && hipMalloc(&k->tile_map, rows / 16 * 4) == hipSuccess;
+  ok      = ok && hipMalloc(&k->map_off, maps * 4) == hipSuccess;
+  ok      = ok && hipMalloc(&k->map_rows, maps * 4) == hipSuccess;
+  ok      = ok && hipMalloc(&k->map_gid, maps * 8) == hipSuccess;
+  ok      = ok && hipMalloc(&k->own_nodes, maps * 4) == hipSuccess;
+  ok      = ok && hipMalloc(&k->counters, (size_t) batch * 3 * 4) == hipSuccess;
+  k->node_of_map = k->own_nodes;
+  if (!ok || prs_place_bank_clear(k) != PRS_OK) {
+    (void) hipGetLastError();
+    (void) prs_place_bank_destroy(k);
+    return ctx_fail(ctx, PRS_ERR_HIP, "prs_place_bank_create: device allocation failed");
+  }
+  *bank = k;
+  return PRS_OK;
+}
+
+int prs_place_bank_destroy(prs_place_bank* bank) {
+  if (!bank) {
+    return PRS_OK;
+  }
+  (void) hipSetDevice(bank->ctx->device);
+  (void) hipStreamSynchronize(bank->ctx->stream);
+  void* ptrs[] = {bank->desc, bank->xyz, bank->row_pidx, bank->tile_map, bank->map_off, bank->map_rows, bank->map_gid, bank->own_nodes,
+                  bank->counters};
+  for (void* p : ptrs) {
+    if (p) {
+      (void) hipFree(p);
+    }
+  }
+  delete bank;
+  return PRS_OK;
+}
+
+int prs_place_bank_clear(prs_place_bank* bank) {
+  if (!bank) {
+    return PRS_ERR_NULL;
+  }
+  prs_context* ctx = bank->ctx;
+  (void) hipSetDevice(ctx->device);
+  const size_t n = (size_t) bank->batch * (size_t) bank->map_stride;  // >= batch
+  hipLaunchKernelGGL(place_bank_clear_kernel, dim3((unsigned) ((n + kPdThreads - 1) / kPdThreads)), dim3(kPdThreads), 0, ctx_stream(ctx),
+                     bank_dev(bank));
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) {
+    return ctx_fail_hip(ctx, e, "prs_place_bank_clear launch");
+  }
+  return PRS_OK;
+}
+
+int prs_place_bank_sizes(prs_place_bank* bank, int32_t* maps, int32_t* rows, int32_t* max_map_rows) {
+  if (!bank) {
+    return PRS_ERR_NULL;
+  }
+  prs_context* ctx = bank->ctx;
+  (void) hipSetDevice(ctx->device);
+  const size_t B = (size_t) bank->batch;
+  std::vector<int32_t> h(3 * B);
+  hipError_t e = hipMemcpyAsync(h.data(), bank->counters, 3 * B * 4, hipMemcpyDeviceToHost, ctx->stream);
+  if (e == hipSuccess) {
+    e = hipStreamSynchronize(ctx->stream);
+  }
+  if (e != hipSuccess) {
+    return ctx_fail_hip(ctx, e, "prs_place_bank_sizes download");
+  }
+  int32_t* out[3] = {maps, rows, max_map_rows};
+  for (int i = 0; i < 3; ++i) {
+    if (out[i]) {
+      memcpy(out[i], h.data() + (size_t) i * B, B * 4);
+    }
+  }
+  return PRS_OK;
+}
+
+void prs_place_bank_struct_sizes(uint64_t* sizes2) {
+  if (sizes2) {
+    sizes2[0] = sizeof(prs_place_bank_append);
+    sizes2[1] = sizeof(prs_place_bank_links);
+  }
+}
+
+int prs_place_bank_bind_node_of_map(prs_place_bank* bank, int32_t* node_of_map) {
+  if (!bank) {
+    return PRS_ERR_NULL;
+  }
+  prs_context* ctx = bank->ctx;
+  int32_t* to      = node_of_map ? node_of_map : bank->own_nodes;
+  if (to != bank->node_of_map) {
+    (void) hipSetDevice(ctx->device);
+    const hipError_t e = hipMemcpyAsync(to, bank->node_of_map, (size_t) bank->batch * (size_t) bank->map_stride * 4, hipMemcpyDeviceToDevice,
+                                        ctx->stream);
+    if (e != hipSuccess) {
+      return ctx_fail_hip(ctx, e, "prs_place_bank_bind_node_of_map copy");
+    }
+    bank->node_of_map = to;
+  }
+  return PRS_OK;
+}
+
+int prs_place_bank_append_batch(prs_place_bank* bank, const prs_place_bank_append* in) {
+  if (!bank) {
+    return PRS_ERR_NULL;
+  }
+  prs_context* ctx = bank->ctx;
+  if (!in) {
+    return ctx_fail(ctx, PRS_ERR_NULL, "prs_place_bank_append_batch: input not set");
+  }
+  if (!in->desc || !in->n_query || !in->graph_id || !in->status) {
+    return ctx_fail(ctx, PRS_ERR_NULL, "prs_place_bank_append_batch: input or output buffer not set");
+  }
+  if (in->batch != bank->batch) {
+    return ctx_fail(ctx, PRS_ERR_RANGE, "prs_place_bank_append_batch: batch differs from the bank's");
+  }
+  if (in->query_stride < 1 || in->query_stride > kPdMaxQuery) {
+    return ctx_fail(ctx, PRS_ERR_UNSUPPORTED, "prs_place_bank_append_batch: query_stride must be in [1, 65536]");
+  }
+  if (!aligned(in->desc, 16) || !aligned(in->xyz, 16)) {
+    return ctx_fail(ctx, PRS_ERR_UNSUPPORTED, "prs_place_bank_append_batch: rows must be 16-byte aligned");
+  }
+  (void) hipSetDevice(ctx->device);
+  AppendArgs a;
+  memset(&a, 0, sizeof(a));
+  a.in = *in;
+  a.d  = bank_dev(bank);
+  hipLaunchKernelGGL(place_bank_append_kernel, dim3((unsigned) bank->batch), dim3(kPdThreads), 0, ctx_stream(ctx), a);
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) {
+    return ctx_fail_hip(ctx, e, "prs_place_bank_append_batch launch");
+  }
+  bank->max_query_stride = in->query_stride > bank->max_query_stride ? in->query_stride : bank->max_query_stride;
+  return PRS_OK;
+}
+
+int prs_place_bank_query_batch(prs_place_bank* bank, const prs_place_params* params, const prs_place_queries* q,
+                               const prs_place_bank_links* links) {
+  if (!bank) {
+    return PRS_ERR_NULL;
+  }
+  prs_context* ctx = bank->ctx;
+  PRS_TRY(check_params(ctx, params, "prs_place_bank_query_batch: parameters not set"));
+  if (!q) {
+    return ctx_fail(ctx, PRS_ERR_NULL, "prs_place_bank_query_batch: queries not set");
+  }
+  if (!q->desc || !q->n_query || !q->graph_id || !q->match_counts || !q->best_keys || !q->candidates || !q->n_candidates || !q->corr ||
+      !q->n_corr || !q->status || (links && (!links->candidates_flat || !links->query_node))) {
+    return ctx_fail(ctx, PRS_ERR_NULL, "prs_place_bank_query_batch: input or output buffer not set");
+  }
+  if (q->batch != bank->batch) {
+    return ctx_fail(ctx, PRS_ERR_RANGE, "prs_place_bank_query_batch: batch differs from the bank's");
+  }
+  if (q->query_stride < 1 || q->query_stride > kPdMaxQuery) {
+    return ctx_fail(ctx, PRS_ERR_UNSUPPORTED, "prs_place_bank_query_batch: query_stride must be in [1, 65536]");
+  }
+  if (q->count_stride < bank->map_stride || q->key_stride < bank->row_stride || q->corr_stride < bank_largest_map(bank) ||
+      q->corr_stride < 1 || q->corr_stride > kPdMaxCorrStride) {
+    return ctx_fail(ctx, PRS_ERR_CAPACITY, "prs_place_bank_query_batch: count_stride, key_stride or corr_stride below the bank's capacity");
+  }
+  if (!aligned(q->desc, 4)) {
+    return ctx_fail(ctx, PRS_ERR_UNSUPPORTED, "prs_place_bank_query_batch: descriptor rows must be 4-byte aligned");
+  }
+  (void) hipSetDevice(ctx->device);
+  BankArgs a;
+  memset(&a, 0, sizeof(a));
+  a.q   = *q;
+  a.p   = *params;
+  a.d   = bank_dev(bank);
+  a.lim = lim_of(params->maximum_descriptor_distance);
+  if (links) {
+    a.links = *links;
+  }
+  hipStream_t s = ctx_stream(ctx);
+  const int big = bank->row_stride > bank->map_stride ? bank->row_stride : bank->map_stride;
+  const unsigned gx = (unsigned) ((big + kPdThreads - 1) / kPdThreads < 1024 ? (big + kPdThreads - 1) / kPdThreads : 1024);
+  hipLaunchKernelGGL(place_bank_init_kernel, dim3(gx, (unsigned) q->batch), dim3(kPdThreads), 0, s, a);
+  const dim3 grid((unsigned) ((bank->row_stride + kPdSlice - 1) / kPdSlice), (unsigned) ((q->query_stride + kPdRowsWg - 1) / kPdRowsWg),
+                  (unsigned) q->batch);
+  hipLaunchKernelGGL(place_bank_score_kernel, grid, dim3(kPdThreads), 0, s, a);
+  hipLaunchKernelGGL(place_bank_select_kernel, dim3((unsigned) q->batch), dim3(kPdThreads), 0, s, a);
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) {
+    return ctx_fail_hip(ctx, e, "prs_place_bank_query_batch launch");
+  }
+  return PRS_OK;
+}
+
+int prs_place_bank_gather_pairs(prs_place_bank* bank, const prs_place_params* params, const prs_place_queries* queries,
+                                const prs_place_pairs* pairs) {
+  if (!bank) {
+    return PRS_ERR_NULL;
+  }
+  prs_context* ctx = bank->ctx;
+  PRS_TRY(check_params(ctx, params, "prs_place_bank_gather_pairs: parameters not set"));
+  if (!queries || !pairs) {
+    return ctx_fail(ctx, PRS_ERR_NULL, "prs_place_bank_gather_pairs: queries or pairs not set");
+  }
+  if (!queries->desc || !queries->xyz || !queries->n_query || !queries->candidates || !queries->n_candidates || !queries->status ||
+      !pairs->fixed_xyz || !pairs->fixed_desc || !pairs->n_fixed || !pairs->moving_xyz || !pairs->moving_desc || !pairs->n_moving ||
+      !pairs->X) {
+    return ctx_fail(ctx, PRS_ERR_NULL, "prs_place_bank_gather_pairs: input or output buffer not set");
+  }
+  if (queries->batch != bank->batch) {
+    return ctx_fail(ctx, PRS_ERR_RANGE, "prs_place_bank_gather_pairs: batch differs from the bank's");
+  }
+  if (queries->query_stride < 1 || queries->query_stride > kPdMaxQuery) {
+    return ctx_fail(ctx, PRS_ERR_UNSUPPORTED, "prs_place_bank_gather_pairs: query_stride must be in [1, 65536]");
+  }
+  if (pairs->fixed_stride < queries->query_stride || pairs->moving_stride < bank_largest_map(bank) || pairs->moving_stride < 1) {
+    return ctx_fail(ctx, PRS_ERR_CAPACITY, "prs_place_bank_gather_pairs: a pair slot is smaller than the query or the largest map the bank holds");
+  }
+  if (!aligned(queries->desc, 16) || !aligned(queries->xyz, 16) || !aligned(pairs->fixed_xyz, 16) || !aligned(pairs->fixed_desc, 16) ||
+      !aligned(pairs->moving_xyz, 16) || !aligned(pairs->moving_desc, 16)) {
+    return ctx_fail(ctx, PRS_ERR_UNSUPPORTED, "prs_place_bank_gather_pairs: rows must be 16-byte aligned");
+  }
+  (void) hipSetDevice(ctx->device);
+  BankGatherArgs g;
+  memset(&g, 0, sizeof(g));
+  g.q    = *queries;
+  g.o    = *pairs;
+  g.d    = bank_dev(bank);
+  g.maxc = params->max_candidates;
+  const size_t slots = (size_t) queries->batch * (size_t) params->max_candidates;
+  hipLaunchKernelGGL(place_bank_gather_kernel, dim3((unsigned) ((slots + 3) / 4)), dim3(kPdThreads), 0, ctx_stream(ctx), g);
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) {
+    return ctx_fail_hip(ctx, e, "prs_place_bank_gather_pairs launch");
   }
   return PRS_OK;
 }

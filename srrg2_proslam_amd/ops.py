@@ -1010,6 +1010,155 @@ class LoopDetectorBatch:
                     accepted=[self.closures.pairs.result_of(s)["accepted"] for s in slots], search=r)
 
 
+# ---- place bank: one place database per sequence, contents and sizes on the device (include/proslam_hip.h prs_place_bank_*) ----
+class PlaceBank:
+    """prs_place_bank: `batch` independent place databases in fixed device arenas (map_stride maps, row_stride rows each).  Maps are
+    stored by a kernel (append) and the sizes are device counters, so a captured step sees what earlier replays stored."""
+
+    def __init__(self, ctx, batch, map_stride, row_stride):
+        import torch
+        self._ctx = ctx
+        h = C.c_void_p()
+        _check(ctx, _lib.load().prs_place_bank_create(ctx._h, int(batch), int(map_stride), int(row_stride), C.byref(h)), "prs_place_bank_create")
+        self._h = h
+        ctx._children.add(self)
+        self.batch, self.map_stride, self.row_stride = int(batch), int(map_stride), (int(row_stride) + 15) // 16 * 16
+        dev = torch.device("cuda", ctx.device)
+        # node_of_map lives in a tensor, so that PoseGraphBatch.append_closures reads it in place
+        self.node_of_map = torch.full((self.batch, self.map_stride), -1, dtype=torch.int32, device=dev)
+        _check(ctx, _lib.load().prs_place_bank_bind_node_of_map(self._h, self.node_of_map.data_ptr()), "prs_place_bank_bind_node_of_map")
+        self.append_status = torch.zeros((self.batch,), dtype=torch.int32, device=dev)
+
+    def close(self):
+        if getattr(self, "_h", None):
+            _lib.load().prs_place_bank_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def append(self, queries, graph_id_base=None):
+        """enqueue addPreviousQuery for every sequence: slot b of `queries` (a PlaceQueries, or anything with its batch,
+        query_stride, desc, xyz, valid, n_query and graph_id) becomes the next map of database b; n_query == 0 stores nothing.
+        graph_id_base: int64 device tensor [batch] or None.  Per-sequence status lands in self.append_status (asynchronous)."""
+        a = _lib.PlaceBankAppend()
+        a.batch, a.query_stride = int(queries.batch), int(queries.query_stride)
+        a.desc, a.n_query, a.graph_id = queries.desc.data_ptr(), queries.n_query.data_ptr(), queries.graph_id.data_ptr()
+        xyz, valid = getattr(queries, "xyz", None), getattr(queries, "valid", None)
+        a.xyz = xyz.data_ptr() if xyz is not None else None
+        a.valid = valid.data_ptr() if valid is not None else None
+        a.graph_id_base = graph_id_base.data_ptr() if graph_id_base is not None else None
+        a.status = self.append_status.data_ptr()
+        self._append_keep = (queries, graph_id_base)  # alive until the kernel has run
+        return _check(self._ctx, _lib.load().prs_place_bank_append_batch(self._h, C.byref(a)), "prs_place_bank_append_batch")
+
+    def clear(self):
+        _check(self._ctx, _lib.load().prs_place_bank_clear(self._h), "prs_place_bank_clear")
+
+    def sizes(self):
+        """(maps [batch], rows with pads [batch], largest map [batch]) as int32 arrays; synchronises: tests and tools only"""
+        out = [np.zeros(self.batch, np.int32) for _ in range(3)]
+        _check(self._ctx, _lib.load().prs_place_bank_sizes(self._h, *(_p(o) for o in out)), "prs_place_bank_sizes")
+        return tuple(out)
+
+
+class PlaceBankLinks:
+    """the optional outputs of place_bank_query_batch that prs_pose_graph_append_closures reads: the flat candidate list, the
+    queries' nodes and (constant) the graph of every query"""
+
+    def __init__(self, device, batch, max_candidates, graph_id_base=None):
+        import torch
+        dev = torch.device("cuda", device)
+        self.candidates_flat = torch.full((batch, max_candidates), -1, dtype=torch.int32, device=dev)
+        self.query_node = torch.full((batch,), -1, dtype=torch.int32, device=dev)
+        self.graph_of_query = torch.arange(batch, dtype=torch.int32, device=dev)
+        self.graph_id_base = graph_id_base
+
+    def descriptor(self):
+        d = _lib.PlaceBankLinks()
+        d.candidates_flat, d.query_node = self.candidates_flat.data_ptr(), self.query_node.data_ptr()
+        d.graph_id_base = self.graph_id_base.data_ptr() if self.graph_id_base is not None else None
+        return d
+
+
+def place_bank_query_batch(ctx, bank, params, queries, links=None):
+    """enqueue the candidate search of query b in database b for every sequence (asynchronous, no host read)"""
+    d = queries.descriptor()
+    ld = links.descriptor() if links is not None else None
+    rc = _lib.load().prs_place_bank_query_batch(bank._h, C.byref(params), C.byref(d), C.byref(ld) if ld is not None else None)
+    _check(ctx, rc, "prs_place_bank_query_batch")
+    return rc
+
+
+class _ClosureView:
+    """what PoseGraphBatch.append_closures reads of a detector, with the bank's flat candidate list as .queries.candidates"""
+
+    class _Q:
+        def __init__(self, candidates):
+            self.candidates = candidates
+
+    def __init__(self, det):
+        self.batch, self.max_candidates, self.closures = det.batch, det.max_candidates, det.closures
+        self.queries = self._Q(det.links.candidates_flat)
+        self._det = det
+
+    def node_maps(self):
+        """(graph_of_query, node_of_query, node_of_map): int32 device tensors"""
+        return self._det.links.graph_of_query, self._det.links.query_node, self._det.bank.node_of_map.view(-1)
+
+
+class BankDetectorBatch:
+    """LoopDetectorBatch over a PlaceBank: query b searches database b, the pair slots are gathered, matched and aligned, and (append)
+    the query itself is stored as the next map of its sequence -- query, gather, append as the reference does, all enqueued on the
+    context stream with no host round trip.  moving_stride defaults to query_stride: a stored map never exceeds the slot it came
+    from.  graph_id_base: int64 device tensor [batch] (the session's) or None; node = graph id - base."""
+
+    def __init__(self, device, bank, batch, query_stride, max_candidates, moving_stride=None, with_valid=False, candidate_capacity=None,
+                 graph_id_base=None):
+        self.bank, self.batch, self.max_candidates = bank, int(batch), int(max_candidates)
+        self.graph_id_base = graph_id_base
+        self.queries = PlaceQueries(device, batch, query_stride, max_candidates, None, count_stride=bank.map_stride,
+                                    key_stride=bank.row_stride, corr_stride=min(int(query_stride), bank.row_stride), with_valid=with_valid)
+        self.links = PlaceBankLinks(device, self.batch, self.max_candidates, graph_id_base)
+        ms = max(int(moving_stride if moving_stride is not None else query_stride), 1)
+        slots = self.batch * self.max_candidates
+        cap = query_stride * ms if candidate_capacity is None else int(candidate_capacity)
+        self.closures = LoopClosureBatch(device, slots, query_stride, ms, with_mask=False, candidate_capacity=cap)
+        self.closures.pairs.n_fixed, self.closures.pairs.n_moving = self.closures.clouds.n_fixed, self.closures.clouds.n_moving
+        self.view = _ClosureView(self)
+
+    def upload(self, b, graph_id, desc, xyz, valid=None):
+        self.queries.upload(b, graph_id, desc, xyz, valid)
+
+    pairs_descriptor = LoopDetectorBatch.pairs_descriptor
+
+    def run(self, ctx, place_params_, matcher_params, align_params, append=True):
+        place_bank_query_batch(ctx, self.bank, place_params_, self.queries, self.links)
+        q, pairs = self.queries.descriptor(), self.pairs_descriptor()
+        _check(ctx, _lib.load().prs_place_bank_gather_pairs(self.bank._h, C.byref(place_params_), C.byref(q), C.byref(pairs)),
+               "prs_place_bank_gather_pairs")
+        lc = self.closures
+        bruteforce_match_batch(ctx, matcher_params, lc.clouds)
+        rc = point_align_batch(ctx, align_params, lc.pairs)
+        if append:
+            self.bank.append(self.queries, self.graph_id_base)
+        return rc
+
+    def node_maps(self):
+        return self.view.node_maps()
+
+    def result_of(self, b, maps=None):
+        """dict(candidates [map indices of sequence b], poses, accepted, search result); maps: the number of match counts to keep"""
+        r = self.queries.result_of(b, maps)
+        slots = [b * self.max_candidates + k for k in range(len(r["candidates"]))]
+        return dict(candidates=r["candidates"], poses=[self.closures.pairs.X_of(s) for s in slots],
+                    accepted=[self.closures.pairs.result_of(s)["accepted"] for s in slots], search=r,
+                    query_node=int(self.links.query_node[b].item()))
+
+
 # ---- pose-graph optimiser: the global solver over SE(3) graphs with loop closures (include/proslam_hip.h) ----
 def pose_graph_params(cfg_graph, closure_information=1.0, **overrides):
     """prs_pose_graph_params from a configs.py `graph` group; overrides by field name"""
