@@ -117,7 +117,9 @@ PRS_API int prs_version(void);
  * prs_pose_graph_lm_* / prs_pose_graph_optimize_lm* entry points; and the closure merger: prs_closure_merger_params,
  * prs_closure_merge_batch, the prs_closure_merge* entry points and prs_map_merge_closure; and the local-map manager:
  * prs_session_params, prs_session_batch and the prs_session_* entry points; and the place bank: prs_place_bank,
- * prs_place_bank_append, prs_place_bank_links and the prs_place_bank_* entry points).  Callers memset() parameter structs before
+ * prs_place_bank_append, prs_place_bank_links and the prs_place_bank_* entry points; and map re-entry: prs_map_archive,
+ * prs_reentry_params, prs_reentry_batch, prs_session_step_archive_batch, prs_session_reenter_batch and
+ * prs_map_archive_struct_sizes).  Callers memset() parameter structs before
  * filling them, so that fields they do not know select the shipped defaults (all zero). */
 #define PRS_ABI_VERSION 104
 PRS_API int prs_abi_check(int32_t header_version, uint64_t sizeof_stereo_params, uint64_t sizeof_pcf_params, uint64_t sizeof_aligner_params,
@@ -1729,6 +1731,145 @@ PRS_API int prs_session_step_batch(prs_context* ctx, const prs_session_params* p
 PRS_API int prs_session_unroll_batch(prs_context* ctx, const prs_session_batch* batch, float* out);
 /* sizeof prs_session_params, prs_session_batch as the library was compiled (bindings check) */
 PRS_API void prs_session_struct_sizes(uint64_t* sizes2);
+
+/* ================================================================================================
+ * Map re-entry: finished local maps are archived on the device and reloaded when a closure leads back into one
+ * replaces what SLAMBenchmark::benchmarkCompute does with an accepted closure at a split (apps/app_benchmark.cpp:136-160): it does
+ * not open a new local map, it re-enters the old one and calls tracker->setClosure(...) ("reloading old local map"), so that the
+ * closure merger (:183) folds the map being left into the one re-entered.  Two launches around the loop detector:
+ *   prs_session_step_archive_batch   in the place of prs_session_step_batch: the same step, and a finished map's whole state is kept
+ *   prs_session_reenter_batch        after prs_place_bank_* / prs_point_align_batch, prs_pose_graph_append_closures and the
+ *                                    optimiser (the reference's order: detect, validate, optimise, relocalize), before
+ *                                    prs_closure_merge_batch_run and prs_merge_batch_run
+ *
+ * BUILD-DEFINED: relocalize(), MultiRelocalizer3D and setClosure live in srrg2_slam_interfaces, which is not in the tree.  The rule
+ * below is this build's; tests/reentry_ref.py restates it in numpy and the kernels equal that bit for bit.  Float32 expressions are
+ * explicit two-operand operations in the order written (csrc/prs_se3.h: se3_inverse, se3_mul, motion_predict).
+ *
+ * Archive (prs_map_archive, caller-owned device arrays): per sequence slot_stride fixed slots of `capacity` rows, each the
+ * per-landmark arrays of prs_merge_batch (coords [4], desc [32], state [4], covariance [9], n_opt, inlier, n_meas: 109 bytes a
+ * landmark), n_points and next_frame per slot and, both or neither, the measurement history meas [capacity][max_measurements] and
+ * the pose table poses [max_frames].  Per sequence slot_of_node [node_stride] (-1 = the node's map is not archived; the caller fills
+ * it with -1 before the first frame), n_slots and status.
+ *
+ * prs_session_step_archive_batch: every output of prs_session_step_batch, bit for bit (the same kernel body behind a block-uniform
+ * flag), and per sequence b:
+ *   no split     (or a session status PRS_ERR_RANGE): archive.status[b] = PRS_OK, nothing else of the archive is written.
+ *   split        (lost or viewpoint) before the map is reset: the slot is slot_of_node[b][old node] if that is >= 0 -- a re-entered
+ *                map that is finished again overwrites its own slot -- else slot n_slots[b], with n_slots[b]++ and slot_of_node set.
+ *                Rows [0, n_points) of every per-landmark array (n_meas before it is zeroed), n_points, next_frame = slot[b] as the
+ *                frame found it and, where kept, rows [0, n_points) of the history and the whole pose table are copied.
+ *                archive.status[b] = PRS_OK.
+ *   full         n_slots[b] == slot_stride (or outside [0, slot_stride]) and the node has no slot: archive.status[b] =
+ *                PRS_ERR_CAPACITY, nothing is stored, the split proceeds as without an archive.  A slot_of_node entry >= slot_stride:
+ *                PRS_ERR_RANGE, nothing stored.
+ * Call-level, besides prs_session_step_batch's: PRS_ERR_NULL (maps, archive or one of their arrays unset; meas without poses or the
+ * reverse, in the archive or, once the archive keeps them, in maps), PRS_ERR_RANGE (batch, capacity or node_stride differ between
+ * the structs, slot_stride < 1, or the archive keeps the history and max_measurements / max_frames differ from maps' or are < 1),
+ * PRS_ERR_UNSUPPORTED (the archive's coords, desc or state, or maps' state, not 16-byte aligned; other arrays not 4-byte aligned).
+ *
+ * prs_session_reenter_batch, per sequence b, one workgroup:
+ *   eligible     reason[b] == PRS_SESSION_SPLIT_VIEWPOINT (the reference never relocalises on Lost) and the session's status[b] ==
+ *                PRS_OK.  Otherwise the sequence is treated as "no slot qualifies".
+ *   the split    m = n_nodes[b] - 1 must be cur_node[b] and exactly one edge e of [0, n_edges[b]) must have to == m; f = from[e] is
+ *                the finished map's node, Z_e the sensor pose in f.
+ *   qualifies    candidate slot k of [0, max_candidates), s = b * max_candidates + k: c = candidates_flat[s] >= 0 with c - b *
+ *                map_stride in [0, map_stride), result[s].accepted != 0, o = node_of_map[c] with 0 <= o < n_nodes[b], o != f, o != m
+ *                and slot_of_node[b][o] >= 0; num_inliers >= relocalize_min_inliers; (float) num_inliers / (float)
+ *                num_correspondences >= relocalize_min_inliers_ratio; chi_inliers / (float) num_inliers <=
+ *                relocalize_max_chi_inliers; and, with P = X_s^-1 * Z_e (se3_inverse, se3_mul) and t2 = (tx tx + ty ty) + tz tz of
+ *                P, t2 <= max_translation * max_translation (the product formed in float by the launcher).  Every comparison is
+ *                non-strict: equality passes.  These are MultiRelocalizer3D's values (kitti.conf:100-109), not the detector's.
+ *   winner       the largest num_inliers, the lowest k on a tie.  No slot qualifies: reentered[b] = 0, gate[b].accepted = 0,
+ *                merge_n_corr[b] = 0, status[b] = PRS_OK and nothing of the session, the map or the graph is written.
+ *   graph        edge e is removed: the edges behind it (the closures prs_pose_graph_append_closures appended this frame) move
+ *                down by one in their order -- from, to, Z and, where kept, omega; n_edges--, n_nodes--, cur_node = o.  The frame
+ *                log is not touched: the split frame stays logged against f.
+ *   session      pose = P, prev = P * prev, prediction = motion_predict(prev, pose), measurement_in_world = measurement_in_scene =
+ *                pose.
+ *   map          the archive slot of o goes back into the live arrays: rows [0, n_points) of every per-landmark array, n_points,
+ *                n_meas[n_points .. capacity) = 0.  With the history kept: its rows [0, n_points), the pose table, frame[b] =
+ *                next_frame.  Without: n_meas = 0 everywhere and frame[b] = 0.  slot[b] = frame[b] + 1.
+ *   regular merge   n_corr_merge[b] = 0 and n_measured[b] = 0: the reference runs the closure merger IN PLACE of the regular merger
+ *                on this frame, so the prs_merge_batch_run that follows adds nothing to the re-entered map.
+ *   closure merge   the outputs form a prs_closure_merge_batch of batch B over the live map: corr = merge_corr, n_corr =
+ *                merge_n_corr (the winner's matcher vector, corr_from_aligner = 1), transform = merge_transform = X_s
+ *                (transform_is_scene_in_measurement = 1), scene_in_world[b] = (float) graph_X[b][o], gate[b] = result[s] with
+ *                accepted = 1; the measurement cloud is the session's hand-over slot (the finished map, PRS_CLOSURE_XYZ).
+ *                INVARIANT: the vector's moving indices are rows of the map as the bank stored it, used here as rows of the map as
+ *                the archive holds it.  A map's rows are only ever appended to (merger and closure merger), so the bank's
+ *                first-stored version is a prefix of every later archived one and the indices name the same landmarks.
+ *   status[b]    PRS_ERR_RANGE, with nothing but status[b] and reentered[b] = 0 written (gate[b] keeps what an earlier frame left:
+ *                stop the sequence): an eligible sequence with n_nodes outside [1, node_stride], n_edges outside [0, edge_stride],
+ *                cur_node != n_nodes - 1, not exactly one edge into m or its from outside [0, m); the winner's archive slot >=
+ *                slot_stride, its n_points outside [0, capacity] or its n_corr outside [0, corr_stride].  PRS_OK otherwise.  A
+ *                sequence never writes outside its rows.
+ * Call-level (return value, nothing launched): PRS_ERR_NULL, PRS_ERR_RANGE (strides or the capacity differ or are < 1,
+ * max_candidates < 1, a parameter not finite or negative), PRS_ERR_UNSUPPORTED (alignment, as above), as the session block's.
+ * One 256-thread workgroup per sequence for both launches: a re-entry moves one map (0.4 MB at 4096 landmarks) on a frame that
+ * splits, and a grid of row chunks would have to agree on the winner first (profiles/reentry/README.md).  No allocation, no
+ * synchronisation, no host read: graph-capturable.
+ * ============================================================================================== */
+typedef struct {
+  int32_t batch;
+  int32_t capacity;            /* rows per slot == prs_session_batch.capacity */
+  int32_t slot_stride;         /* slots per sequence */
+  int32_t node_stride;         /* == prs_session_batch.node_stride */
+  int32_t max_measurements;    /* with the history: == prs_merge_batch.max_measurements */
+  int32_t max_frames;          /* with the history: == prs_merge_batch.max_frames */
+  float* coords;               /* [batch][slot_stride][capacity][4], 16-byte aligned */
+  uint8_t* desc;               /* [batch][slot_stride][capacity][32], 16-byte aligned */
+  float* state;                /* [batch][slot_stride][capacity][4], 16-byte aligned */
+  float* covariance;           /* [batch][slot_stride][capacity][9] */
+  uint32_t* n_opt;             /* [batch][slot_stride][capacity] */
+  uint8_t* inlier;             /* [batch][slot_stride][capacity] */
+  uint32_t* n_meas;            /* [batch][slot_stride][capacity] */
+  int32_t* n_points;           /* [batch][slot_stride] */
+  int32_t* next_frame;         /* [batch][slot_stride] pose-table slot the map's next frame takes */
+  prs_camera_measurement* meas; /* optional [batch][slot_stride][capacity][max_measurements] */
+  prs_frame_pose* poses;       /* optional (with meas) [batch][slot_stride][max_frames] */
+  int32_t* slot_of_node;       /* [batch][node_stride], -1 = none */
+  int32_t* n_slots;            /* [batch] */
+  int32_t* status;             /* out [batch], written by prs_session_step_archive_batch */
+} prs_map_archive;
+
+typedef struct {
+  float max_translation;              /* MultiRelocalizer3D max_translation: kitti.conf:100 (10), euroc.conf:143 (2.5), icl.conf:696 (3), tum.conf:59 (1) */
+  int32_t relocalize_min_inliers;     /* kitti.conf:106 (25) */
+  float relocalize_min_inliers_ratio; /* kitti.conf:109 (0.5) */
+  float relocalize_max_chi_inliers;   /* kitti.conf:103 (5) */
+} prs_reentry_params;
+
+/* the loop detector's outputs for B sequences of max_candidates slots each, and the kernel's own outputs; device pointers */
+typedef struct {
+  int32_t max_candidates;
+  int32_t map_stride;                    /* the place bank's */
+  int32_t corr_stride;                   /* entries per slot of corr, and per sequence of merge_corr */
+  int32_t reserved;
+  const int32_t* candidates_flat;        /* [batch][max_candidates] prs_place_bank_links.candidates_flat */
+  const prs_point_align_result* result;  /* [batch * max_candidates] prs_point_align_pairs.result */
+  const float* X;                        /* [batch * max_candidates][16] prs_point_align_pairs.X */
+  const prs_corr* corr;                  /* [batch * max_candidates][corr_stride] the matcher's vectors */
+  const int32_t* n_corr;                 /* [batch * max_candidates] */
+  const int32_t* node_of_map;            /* [batch][map_stride] the bank's */
+  int32_t* n_measured;                   /* [batch] prs_merge_batch.n_measured: zeroed on a re-entry */
+  int32_t* reentered;                    /* out [batch] 1: the sequence re-entered an archived map */
+  int32_t* status;                       /* out [batch] */
+  prs_corr* merge_corr;                  /* out [batch][corr_stride] prs_closure_merge_batch.corr */
+  int32_t* merge_n_corr;                 /* out [batch] .n_corr */
+  float* merge_transform;                /* out [batch][16] .transform */
+  float* scene_in_world;                 /* out [batch][16] .scene_in_world */
+  prs_point_align_result* gate;          /* out [batch] .gate */
+} prs_reentry_batch;
+
+/* device pointers, asynchronous on the context's stream: one kernel launch each.  maps supplies the live map's statistics arrays
+ * (state, covariance, n_opt, inlier and, with the history, meas and poses); its coords, desc, n_meas and n_points are the session's */
+PRS_API int prs_session_step_archive_batch(prs_context* ctx, const prs_session_params* params, const prs_session_batch* batch,
+                                           const prs_merge_batch* maps, const prs_map_archive* archive);
+PRS_API int prs_session_reenter_batch(prs_context* ctx, const prs_reentry_params* params, const prs_session_batch* batch,
+                                      const prs_merge_batch* maps, const prs_map_archive* archive, const prs_reentry_batch* reentry);
+/* sizeof prs_map_archive, prs_reentry_params, prs_reentry_batch as the library was compiled (bindings check) */
+PRS_API void prs_map_archive_struct_sizes(uint64_t* sizes3);
 
 #ifdef __cplusplus
 }

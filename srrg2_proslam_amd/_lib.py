@@ -443,6 +443,30 @@ class SessionBatch(C.Structure):
                 ("graph_id_base", C.c_void_p)]
 
 
+class MapArchive(C.Structure):
+    """prs_map_archive (device pointers)"""
+    _fields_ = [("batch", C.c_int32), ("capacity", C.c_int32), ("slot_stride", C.c_int32), ("node_stride", C.c_int32),
+                ("max_measurements", C.c_int32), ("max_frames", C.c_int32),
+                ("coords", C.c_void_p), ("desc", C.c_void_p), ("state", C.c_void_p), ("covariance", C.c_void_p), ("n_opt", C.c_void_p),
+                ("inlier", C.c_void_p), ("n_meas", C.c_void_p), ("n_points", C.c_void_p), ("next_frame", C.c_void_p),
+                ("meas", C.c_void_p), ("poses", C.c_void_p), ("slot_of_node", C.c_void_p), ("n_slots", C.c_void_p), ("status", C.c_void_p)]
+
+
+class ReentryParams(C.Structure):
+    """prs_reentry_params"""
+    _fields_ = [("max_translation", C.c_float), ("relocalize_min_inliers", C.c_int32), ("relocalize_min_inliers_ratio", C.c_float),
+                ("relocalize_max_chi_inliers", C.c_float)]
+
+
+class ReentryBatch(C.Structure):
+    """prs_reentry_batch (device pointers)"""
+    _fields_ = [("max_candidates", C.c_int32), ("map_stride", C.c_int32), ("corr_stride", C.c_int32), ("reserved", C.c_int32),
+                ("candidates_flat", C.c_void_p), ("result", C.c_void_p), ("X", C.c_void_p), ("corr", C.c_void_p), ("n_corr", C.c_void_p),
+                ("node_of_map", C.c_void_p), ("n_measured", C.c_void_p), ("reentered", C.c_void_p), ("status", C.c_void_p),
+                ("merge_corr", C.c_void_p), ("merge_n_corr", C.c_void_p), ("merge_transform", C.c_void_p),
+                ("scene_in_world", C.c_void_p), ("gate", C.c_void_p)]
+
+
 MODE_ALIGN, MODE_FINDER, MODE_LINEARIZE = 0, 1, 2
 
 # every symbol include/proslam_hip.h declares: (restype, argtypes)
@@ -552,6 +576,11 @@ SYMBOLS = {
     "prs_session_step_batch": (C.c_int, [_vp, C.POINTER(SessionParams), C.POINTER(SessionBatch)]),
     "prs_session_unroll_batch": (C.c_int, [_vp, C.POINTER(SessionBatch), _vp]),
     "prs_session_struct_sizes": (None, [C.POINTER(C.c_uint64)]),
+    "prs_session_step_archive_batch": (C.c_int, [_vp, C.POINTER(SessionParams), C.POINTER(SessionBatch), C.POINTER(MergeBatch),
+                                                 C.POINTER(MapArchive)]),
+    "prs_session_reenter_batch": (C.c_int, [_vp, C.POINTER(ReentryParams), C.POINTER(SessionBatch), C.POINTER(MergeBatch),
+                                            C.POINTER(MapArchive), C.POINTER(ReentryBatch)]),
+    "prs_map_archive_struct_sizes": (None, [C.POINTER(C.c_uint64)]),
     "prs_scene_clip_batch": (C.c_int, [_vp, C.POINTER(Projector), _vp, C.POINTER(ClipBatch)]),
     "prs_scene_clip": (C.c_int, [_vp, C.POINTER(Projector), _vp, _vp, _vp, _vp, C.c_int32, _vp, _vp, _vp, C.c_int32, _i32p]),
 }
@@ -595,5 +624,12 @@ def load():
         raise ImportError("libproslam_hip.so (version %d) does not match the Python binding (version %d, struct sizes %d/%d/%d/%d): "
                           "rebuild with `python -c 'import __graft_entry__ as g; g.build()'`"
                           % (lib.prs_version(), ABI_VERSION, C.sizeof(StereoParams), C.sizeof(PcfParams), C.sizeof(AlignerParams), C.sizeof(AlignBatch)))
+    # the structs of the later sections have their own size queries
+    sizes = (C.c_uint64 * 3)()
+    lib.prs_map_archive_struct_sizes(sizes)
+    if list(sizes) != [C.sizeof(MapArchive), C.sizeof(ReentryParams), C.sizeof(ReentryBatch)]:
+        raise ImportError("libproslam_hip.so lays out prs_map_archive / prs_reentry_params / prs_reentry_batch as %s bytes, the Python "
+                          "binding as %s: rebuild with `python -c 'import __graft_entry__ as g; g.build()'`"
+                          % (list(sizes), [C.sizeof(MapArchive), C.sizeof(ReentryParams), C.sizeof(ReentryBatch)]))
     _lib = lib
     return lib

@@ -207,6 +207,21 @@ TUM = {
 CONFIGS = {"kitti": KITTI, "euroc": EUROC, "icl": ICL, "tum": TUM}
 
 
+def _reentry(max_translation, min_inliers, min_inliers_ratio, max_chi_inliers):
+    """MultiRelocalizer3D's own gates for re-entering an old local map (include/proslam_hip.h prs_reentry_params): the largest jump
+    it attempts and its verdict thresholds -- not the loop detector's, which gate the closure itself (the "loop" groups above)"""
+    return {"max_translation": max_translation, "relocalize_min_inliers": min_inliers, "relocalize_min_inliers_ratio": min_inliers_ratio,
+            "relocalize_max_chi_inliers": max_chi_inliers}
+
+
+REENTRY = {
+    "kitti": _reentry(10, 25, 0.5, 5),       # kitti.conf:91-110: max_translation :100, chi :103, inliers :106, ratio :109
+    "euroc": _reentry(2.5, 100, 0.9, 100),   # euroc.conf:134-153: :143, :146, :149, :152
+    "icl": _reentry(3, 100, 0.5, 1000),      # icl.conf:687-706: :696, :699, :702, :705
+    "tum": _reentry(1, 40, 0.5, 100),        # tum.conf:50-69: :59, :62, :65, :68
+}
+
+
 def get(name):
     return copy.deepcopy(CONFIGS[name])
 

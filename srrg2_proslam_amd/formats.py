@@ -409,3 +409,13 @@ def split_params(conf):
             out["class"] = criterion.class_name
             return out
     return {}
+
+
+_RELOCALIZER = ("max_translation",) + _VERDICT
+
+
+def relocalizer_params(conf):
+    """the re-entry gates of a parsed configuration (include/proslam_hip.h prs_reentry_params): the MultiRelocalizer* record's
+    max_translation and its three verdict thresholds.  Only fields present in the file are returned."""
+    relocalizer = next((r for r in conf.records if r.class_name.startswith("MultiRelocalizer")), None)
+    return _pick(relocalizer, _RELOCALIZER) if relocalizer is not None else {}

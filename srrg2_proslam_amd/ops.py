@@ -1802,6 +1802,143 @@ class SessionBatch:
                     frame_pose=self.frame_pose[b, :n].cpu().numpy().reshape(-1, 4, 4).copy())
 
 
+# ---- map re-entry: archive finished maps, reload one on a closure (include/proslam_hip.h prs_map_archive, prs_session_reenter_batch) ----
+def reentry_params(group, **overrides):
+    """prs_reentry_params from a configs.REENTRY group (MultiRelocalizer3D's own values); overrides by field name"""
+    p = _lib.ReentryParams()
+    p.max_translation = group["max_translation"]
+    p.relocalize_min_inliers = group["relocalize_min_inliers"]
+    p.relocalize_min_inliers_ratio = group["relocalize_min_inliers_ratio"]
+    p.relocalize_max_chi_inliers = group["relocalize_max_chi_inliers"]
+    for k, v in overrides.items():
+        setattr(p, k, v)
+    return p
+
+
+class MapArchive:
+    """prs_map_archive: slot_stride slots per sequence, each the per-landmark arrays of a MapBatch (and, with_history, its measurement
+    history and pose table), plus slot_of_node [B, node_stride] (-1 = none), n_slots and status.  The tensors own the memory."""
+
+    ROW_ARRAYS = ("coords", "desc", "state", "covariance", "n_opt", "inlier", "n_meas")
+
+    def __init__(self, device, maps, node_stride, slot_stride, with_history=False):
+        import torch
+        dev = torch.device("cuda", device)
+        z = lambda shape, dt: torch.zeros(shape, dtype=dt, device=dev)  # noqa: E731
+        B, S, cap = int(maps.batch), int(slot_stride), int(maps.capacity)
+        self.batch, self.capacity, self.slot_stride, self.node_stride = B, cap, S, int(node_stride)
+        self.with_history = bool(with_history)
+        if self.with_history and maps.max_measurements < 1:
+            raise ValueError("the maps keep no measurement history to archive")
+        self.max_measurements, self.max_frames = (maps.max_measurements, maps.max_frames) if self.with_history else (0, 0)
+        self.coords, self.desc = z((B, S, cap, 4), torch.float32), z((B, S, cap, 32), torch.uint8)
+        self.state, self.covariance = z((B, S, cap, 4), torch.float32), z((B, S, cap, 9), torch.float32)
+        self.n_opt, self.inlier, self.n_meas = z((B, S, cap), torch.int32), z((B, S, cap), torch.uint8), z((B, S, cap), torch.int32)
+        self.n_points, self.next_frame = z((B, S), torch.int32), z((B, S), torch.int32)
+        self.meas = z((B, S, cap, self.max_measurements, MapBatch.MEAS_WORDS), torch.int32) if self.with_history else None
+        self.poses = z((B, S, self.max_frames, MapBatch.POSE_WORDS), torch.float32) if self.with_history else None
+        self.slot_of_node = torch.full((B, self.node_stride), -1, dtype=torch.int32, device=dev)
+        self.n_slots, self.status = z((B,), torch.int32), z((B,), torch.int32)
+
+    def clear(self):
+        self.slot_of_node.fill_(-1)
+        self.n_slots.zero_()
+        self.status.zero_()
+
+    def descriptor(self):
+        d = _lib.MapArchive()
+        d.batch, d.capacity, d.slot_stride, d.node_stride = self.batch, self.capacity, self.slot_stride, self.node_stride
+        d.max_measurements, d.max_frames = self.max_measurements, self.max_frames
+        for name in self.ROW_ARRAYS + ("n_points", "next_frame", "slot_of_node", "n_slots", "status"):
+            setattr(d, name, getattr(self, name).data_ptr())
+        d.meas = self.meas.data_ptr() if self.meas is not None else None
+        d.poses = self.poses.data_ptr() if self.poses is not None else None
+        return d
+
+    def slot_of(self, b, node):
+        """the archived map of `node` in the layout of ClosureMergeBatch.scene_of (whole capacity) + next_frame, or None"""
+        s = int(self.slot_of_node[b, node].item())
+        if s < 0:
+            return None
+        out = dict(slot=s, n_points=int(self.n_points[b, s].item()), next_frame=int(self.next_frame[b, s].item()))
+        for name in self.ROW_ARRAYS:
+            out[name] = getattr(self, name)[b, s].cpu().numpy().copy()
+        return out
+
+
+class ReentryBatch:
+    """map re-entry for the B sequences of a SessionBatch: step() is the session step that also archives a finished map
+    (prs_session_step_archive_batch, in the place of session.step()), reenter() the launch that follows the detector, append_closures
+    and the optimiser (prs_session_reenter_batch), merge_view a ClosureMergeBatch over the live MapBatch and reenter()'s outputs --
+    nothing copied -- for closure_merge_batch; merge_batch(maps) runs last.  bank_detector: a BankDetectorBatch whose .queries is the
+    session's hand-over."""
+
+    def __init__(self, session, maps, bank_detector, archive):
+        import torch
+        det = bank_detector
+        if session.handover is not det.queries:
+            raise ValueError("the session must hand its finished maps over to the detector's queries")
+        if int(archive.batch) != session.batch or int(det.batch) != session.batch or maps is not session.maps:
+            raise ValueError("session, maps, detector and archive must hold the same sequences")
+        self.session, self.maps, self.detector, self.archive = session, maps, det, archive
+        dev = session.pose.device
+        B, pairs = session.batch, det.closures.pairs
+        z = lambda shape, dt: torch.zeros(shape, dtype=dt, device=dev)  # noqa: E731
+        self.batch, self.corr_stride = B, int(pairs.corr_stride)
+        self.reentered, self.status = z((B,), torch.int32), z((B,), torch.int32)
+        self.merge_corr, self.merge_n_corr = z((B, self.corr_stride, 3), torch.int32), z((B,), torch.int32)
+        self.merge_transform = torch.eye(4, dtype=torch.float32, device=dev).reshape(1, 16).repeat(B, 1).contiguous()
+        self.scene_in_world = self.merge_transform.clone()
+        self.gate = z((B, C.sizeof(_lib.PointAlignResult) // 4), torch.int32)
+        # the closure merger's batch: the live map as the scene, the hand-over slot (the finished map) as the XYZ measurement cloud
+        v = ClosureMergeBatch.__new__(ClosureMergeBatch)
+        q = det.queries
+        v.batch, v.capacity, v.measurement_stride, v.corr_stride = B, maps.capacity, int(q.query_stride), self.corr_stride
+        v.coords, v.desc, v.n_points = maps.coords, maps.desc, maps.n_points
+        v.state, v.covariance, v.n_opt, v.inlier, v.n_meas = maps.state, maps.covariance, maps.n_opt, maps.inlier, maps.n_meas
+        v.scene_in_world = self.scene_in_world
+        v.measurement, v.measurement_desc, v.n_measured = q.xyz, q.desc, q.n_query
+        v.corr, v.n_corr, v.transform, v.gate = self.merge_corr, self.merge_n_corr, self.merge_transform, self.gate
+        v.result = z((B, 3), torch.int32)
+        v.corr_from_aligner, v.transform_is_scene_in_measurement = 1, 1
+        self.merge_view = v
+
+    def descriptor(self):
+        det, pairs = self.detector, self.detector.closures.pairs
+        d = _lib.ReentryBatch()
+        d.max_candidates, d.map_stride, d.corr_stride = det.max_candidates, det.bank.map_stride, self.corr_stride
+        d.candidates_flat, d.node_of_map = det.links.candidates_flat.data_ptr(), det.bank.node_of_map.data_ptr()
+        d.result, d.X, d.corr, d.n_corr = pairs.result.data_ptr(), pairs.X.data_ptr(), pairs.corr.data_ptr(), pairs.n_corr.data_ptr()
+        d.n_measured = self.maps.n_measured.data_ptr()
+        for name in ("reentered", "status", "merge_corr", "merge_n_corr", "merge_transform", "scene_in_world", "gate"):
+            setattr(d, name, getattr(self, name).data_ptr())
+        return d
+
+    def step(self, ctx, params):
+        """enqueue the per-frame step of every sequence with the archive behind it (asynchronous, one launch); the session's status
+        lands in session.status, the archive's in archive.status"""
+        s, m, a = self.session.descriptor(), self.maps.descriptor(), self.archive.descriptor()
+        rc = _lib.load().prs_session_step_archive_batch(ctx._h, C.byref(params), C.byref(s), C.byref(m), C.byref(a))
+        _check(ctx, rc, "prs_session_step_archive_batch")
+        return rc
+
+    def reenter(self, ctx, params):
+        """enqueue the re-entry of every sequence whose split found an accepted closure into an archived map (asynchronous, one
+        launch); per-sequence status lands in self.status, the decision in self.reentered"""
+        s, m, a, r = self.session.descriptor(), self.maps.descriptor(), self.archive.descriptor(), self.descriptor()
+        rc = _lib.load().prs_session_reenter_batch(ctx._h, C.byref(params), C.byref(s), C.byref(m), C.byref(a), C.byref(r))
+        _check(ctx, rc, "prs_session_reenter_batch")
+        return rc
+
+    def result_of(self, b):
+        """dict(status, reentered, cur_node, n_corr, transform [4, 4], scene_in_world [4, 4], gate (the winner's aligner result))"""
+        m44 = lambda t: t[b].cpu().numpy().reshape(4, 4).copy()  # noqa: E731
+        gate = _result_dict(_lib.PointAlignResult.from_buffer_copy(self.gate[b].cpu().numpy().tobytes()))
+        return dict(status=int(self.status[b].item()), reentered=int(self.reentered[b].item()),
+                    cur_node=int(self.session.cur_node[b].item()), n_corr=int(self.merge_n_corr[b].item()),
+                    transform=m44(self.merge_transform), scene_in_world=m44(self.scene_in_world), gate=gate)
+
+
 # ---- intensity feature extraction (sensor_processing/feature_extractors) ----
 SELECT_CANONICAL, SELECT_LIBSTDCXX = 0, 1
 BF_DENSE_POPCOUNT, BF_DENSE_MATRIX_WHEN_FULL, BF_DENSE_MATRIX = 0, 1, 2  # include/proslam_hip.h PRS_BF_DENSE_*

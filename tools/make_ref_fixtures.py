@@ -136,6 +136,17 @@ def conf_split(names=("kitti", "kitti_in_baselink", "euroc", "icl", "tum", "mala
         f.write("\n")
 
 
+def conf_relocalizer(names=("kitti", "kitti_in_baselink", "euroc", "icl", "tum", "malaga")):
+    """{config: MultiRelocalizer3D's max_translation and verdict thresholds} as formats.relocalizer_params reads them: settings only"""
+    import json
+    sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+    from srrg2_proslam_amd import formats
+    out = {n: formats.relocalizer_params(formats.read_conf(os.path.join(REF, "configurations", n + ".conf"))) for n in names}
+    with open(os.path.join(OUT, "ref_conf_relocalizer.json"), "w") as f:
+        json.dump(out, f, indent=1, sort_keys=True)
+        f.write("\n")
+
+
 def main():
     k = os.path.join(DATA, "kitti")
     np.savez_compressed(
@@ -168,6 +179,7 @@ def main():
     conf_graph_lm()
     conf_closure()
     conf_split()
+    conf_relocalizer()
     for f in sorted(os.listdir(OUT)):
         if f.startswith("ref_"):
             print(f, os.path.getsize(os.path.join(OUT, f)) // 1024, "KiB")
