@@ -119,7 +119,9 @@ PRS_API int prs_version(void);
  * prs_session_params, prs_session_batch and the prs_session_* entry points; and the place bank: prs_place_bank,
  * prs_place_bank_append, prs_place_bank_links and the prs_place_bank_* entry points; and map re-entry: prs_map_archive,
  * prs_reentry_params, prs_reentry_batch, prs_session_step_archive_batch, prs_session_reenter_batch and
- * prs_map_archive_struct_sizes).  Callers memset() parameter structs before
+ * prs_map_archive_struct_sizes; and the dispatch plans for tests and tools: prs_dispatch_env,
+ * prs_dispatch_plan, prs_context_get_dispatch_env, the prs_*_plan entry points, prs_dispatch_kernel_name and
+ * prs_dispatch_struct_sizes).  Callers memset() parameter structs before
  * filling them, so that fields they do not know select the shipped defaults (all zero). */
 #define PRS_ABI_VERSION 104
 PRS_API int prs_abi_check(int32_t header_version, uint64_t sizeof_stereo_params, uint64_t sizeof_pcf_params, uint64_t sizeof_aligner_params,
@@ -1870,6 +1872,71 @@ PRS_API int prs_session_reenter_batch(prs_context* ctx, const prs_reentry_params
                                       const prs_merge_batch* maps, const prs_map_archive* archive, const prs_reentry_batch* reentry);
 /* sizeof prs_map_archive, prs_reentry_params, prs_reentry_batch as the library was compiled (bindings check) */
 PRS_API void prs_map_archive_struct_sizes(uint64_t* sizes3);
+
+/* ================================================================================================
+ * Dispatch plans -- tests and tools only.  What a launch of the stereo matcher, the aligner, the brute-force matcher or the merger
+ * WOULD run for a shape: the kernels by the names a kernel trace prints, grid, block, dynamic LDS bytes, the refusal if there is
+ * one, and the layout facts the kernels' data-dependent paths hang on.  The library's launch functions consume the same plans.
+ * Nothing here touches a device: the batch descriptors' pointers are only tested for being set, never followed, and a
+ * prs_dispatch_env can be written by hand (a CU count, the knobs) or read from a live context.
+ * ================================================================================================ */
+typedef struct {
+  int32_t cus;               /* compute units of the context's device (256 when the query failed) */
+  int32_t fused_align;       /* PRS_FUSED_ALIGN */
+  int32_t matcher_v3;        /* PRS_MATCHER_V3 */
+  int32_t force_unstaged;    /* PRS_FORCE_UNSTAGED */
+  int32_t no_lone_gn;        /* PRS_NO_LONE_GN */
+  int32_t merge_fused;       /* PRS_MERGE_FUSED */
+  int32_t bf_mfma;           /* PRS_BF_DENSE_* (prs_context_set_bruteforce_dense_phase) */
+  int32_t stamps;            /* PRS_STAMPS */
+  int32_t stamps_split;      /* PRS_STAMPS_SPLIT */
+  int32_t bf_global_state;   /* PRS_BF_GLOBAL_STATE is set (read from the environment per launch) */
+  int32_t bf_two_workgroups; /* PRS_BF_TWO_WORKGROUPS: -1 unset, 0, 1 (read from the environment per launch) */
+} prs_dispatch_env;
+PRS_API int prs_context_get_dispatch_env(const prs_context* ctx, prs_dispatch_env* env);
+
+#define PRS_PLAN_MAX_LAUNCHES 4
+#define PRS_PLAN_MAX_FACTS 48
+typedef struct {
+  const char* kernel; /* as a kernel trace prints it (static storage) */
+  int32_t grid_x, grid_y, block;
+  uint32_t lds_bytes; /* dynamic LDS */
+} prs_plan_launch;
+typedef struct {
+  int32_t status;      /* PRS_OK or the refusal's status */
+  const char* message; /* the refusal's message (static storage), NULL when there is none */
+  int32_t n_launches;  /* 0: refused, or an empty batch */
+  prs_plan_launch launch[PRS_PLAN_MAX_LAUNCHES];
+  int32_t fact[PRS_PLAN_MAX_FACTS]; /* indexed by the family's PRS_PLAN_* enumerators; the rest is 0 */
+} prs_dispatch_plan;
+
+enum { PRS_DISPATCH_STEREO = 0, PRS_DISPATCH_ALIGN = 1, PRS_DISPATCH_BRUTEFORCE = 2, PRS_DISPATCH_MERGE = 3 };
+/* stereo: V5 = 1 the second-generation kernel runs; V5_WHY = why it does not (0 it does, 1 stride, 2 knob, 3 cap, 4 lds, 5 best_lim);
+ * CAP .. POOL_CAP: the v5 layout (set when v5 got that far); the first generation's staged / unstaged carve */
+enum { PRS_PLAN_STEREO_V5, PRS_PLAN_STEREO_V5_WHY, PRS_PLAN_STEREO_CAP, PRS_PLAN_STEREO_OFF_POOL, PRS_PLAN_STEREO_POOL_CAP,
+       PRS_PLAN_STEREO_V5_LDS, PRS_PLAN_STEREO_KPT, PRS_PLAN_STEREO_EPI, PRS_PLAN_STEREO_STAGE,
+       PRS_PLAN_STEREO_STAGED_LDS, PRS_PLAN_STEREO_UNSTAGED_LDS, PRS_PLAN_STEREO_SORT_CAP, PRS_PLAN_STEREO_BEST_LIM };
+enum { PRS_PLAN_ALIGN_MAX_FIXED, PRS_PLAN_ALIGN_CELL_SY, PRS_PLAN_ALIGN_CELL_SX, PRS_PLAN_ALIGN_CELL_NCY, PRS_PLAN_ALIGN_CELL_NCX,
+       PRS_PLAN_ALIGN_LUT_CAP, PRS_PLAN_ALIGN_SPLIT, PRS_PLAN_ALIGN_SURV_SLOTS, PRS_PLAN_ALIGN_DB_BLOB, PRS_PLAN_ALIGN_LONE,
+       PRS_PLAN_ALIGN_FIVE, PRS_PLAN_ALIGN_FAST, PRS_PLAN_ALIGN_PLAIN, PRS_PLAN_ALIGN_MPRIOR, PRS_PLAN_ALIGN_DEPTH,
+       PRS_PLAN_ALIGN_OFF_U, PRS_PLAN_ALIGN_SEARCH_OFF_U };
+enum { PRS_PLAN_BF_LIM, PRS_PLAN_BF_NW, PRS_PLAN_BF_CAP, PRS_PLAN_BF_GRID, PRS_PLAN_BF_CHUNKS, PRS_PLAN_BF_BM_FITS, PRS_PLAN_BF_LVL_CAP,
+       PRS_PLAN_BF_FUSED_MATRIX, PRS_PLAN_BF_DUAL, PRS_PLAN_BF_MFMA, PRS_PLAN_BF_LDS, PRS_PLAN_BF_OFF_CNT_F, PRS_PLAN_BF_OFF_CNT_M,
+       PRS_PLAN_BF_OFF_REG_F, PRS_PLAN_BF_OFF_REG_M, PRS_PLAN_BF_OFF_ACC, PRS_PLAN_BF_OFF_HIST, PRS_PLAN_BF_OFF_BM, PRS_PLAN_BF_OFF_LVL,
+       PRS_PLAN_BF_OFF_MX };
+enum { PRS_PLAN_MERGE_NBR, PRS_PLAN_MERGE_NBC, PRS_PLAN_MERGE_SPLIT, PRS_PLAN_MERGE_OFF_OWNER,
+       PRS_PLAN_MERGE_OFF_FIRST, PRS_PLAN_MERGE_OFF_BEST, PRS_PLAN_MERGE_OFF_SEEN, PRS_PLAN_MERGE_OFF_SH, PRS_PLAN_MERGE_OFF_WAVE,
+       PRS_PLAN_MERGE_OFF_POSE_CACHE, PRS_PLAN_MERGE_TAIL_CAPACITY };
+PRS_API int prs_stereo_plan(const prs_stereo_params* params, const prs_stereo_batch* batch, const prs_dispatch_env* env, prs_dispatch_plan* plan);
+PRS_API int prs_align_plan(const prs_pcf_params* finder, const prs_aligner_params* aligner, const prs_align_batch* batch, int32_t mode,
+                           const prs_dispatch_env* env, prs_dispatch_plan* plan);
+PRS_API int prs_bruteforce_plan(const prs_bruteforce_params* params, const prs_bruteforce_batch* batch, const prs_dispatch_env* env,
+                                prs_dispatch_plan* plan);
+PRS_API int prs_merge_plan(const prs_merger_params* params, const prs_merge_batch* batch, const prs_dispatch_env* env, prs_dispatch_plan* plan);
+/* the index-th kernel of a family's variant tables (every kernel a plan of that family can name); NULL past the end */
+PRS_API const char* prs_dispatch_kernel_name(int32_t family, int32_t index);
+/* sizeof prs_dispatch_env, prs_dispatch_plan as the library was compiled (bindings check) */
+PRS_API void prs_dispatch_struct_sizes(uint64_t* sizes2);
 
 #ifdef __cplusplus
 }

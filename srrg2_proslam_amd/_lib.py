@@ -467,6 +467,35 @@ class ReentryBatch(C.Structure):
                 ("scene_in_world", C.c_void_p), ("gate", C.c_void_p)]
 
 
+class DispatchEnv(C.Structure):
+    """prs_dispatch_env: what a dispatch depends on outside its arguments (tests and tools)"""
+    _fields_ = [(n, C.c_int32) for n in ("cus", "fused_align", "matcher_v3", "force_unstaged", "no_lone_gn", "merge_fused", "bf_mfma", "stamps",
+                                         "stamps_split", "bf_global_state", "bf_two_workgroups")]
+
+
+class PlanLaunch(C.Structure):
+    """prs_plan_launch"""
+    _fields_ = [("kernel", C.c_char_p), ("grid_x", C.c_int32), ("grid_y", C.c_int32), ("block", C.c_int32), ("lds_bytes", C.c_uint32)]
+
+
+class DispatchPlan(C.Structure):
+    """prs_dispatch_plan"""
+    _fields_ = [("status", C.c_int32), ("message", C.c_char_p), ("n_launches", C.c_int32), ("launch", PlanLaunch * 4), ("fact", C.c_int32 * 48)]
+
+
+DISPATCH_STEREO, DISPATCH_ALIGN, DISPATCH_BRUTEFORCE, DISPATCH_MERGE = 0, 1, 2, 3
+# the PRS_PLAN_<FAMILY>_* enumerators in order, lower case
+PLAN_FACTS = {
+    DISPATCH_STEREO: ("v5", "v5_why", "cap", "off_pool", "pool_cap", "v5_lds", "kpt", "epi", "stage", "staged_lds", "unstaged_lds", "sort_cap",
+                      "best_lim"),
+    DISPATCH_ALIGN: ("max_fixed", "cell_sy", "cell_sx", "cell_ncy", "cell_ncx", "lut_cap", "split", "surv_slots", "db_blob", "lone", "five",
+                     "fast", "plain", "mprior", "depth", "off_u", "search_off_u"),
+    DISPATCH_BRUTEFORCE: ("lim", "nw", "cap", "grid", "chunks", "bm_fits", "lvl_cap", "fused_matrix", "dual", "mfma", "lds", "off_cnt_f",
+                          "off_cnt_m", "off_reg_f", "off_reg_m", "off_acc", "off_hist", "off_bm", "off_lvl", "off_mx"),
+    DISPATCH_MERGE: ("nbr", "nbc", "split", "off_owner", "off_first", "off_best", "off_seen", "off_sh", "off_wave", "off_pose_cache",
+                     "tail_capacity"),
+}
+
 MODE_ALIGN, MODE_FINDER, MODE_LINEARIZE = 0, 1, 2
 
 # every symbol include/proslam_hip.h declares: (restype, argtypes)
@@ -581,6 +610,14 @@ SYMBOLS = {
     "prs_session_reenter_batch": (C.c_int, [_vp, C.POINTER(ReentryParams), C.POINTER(SessionBatch), C.POINTER(MergeBatch),
                                             C.POINTER(MapArchive), C.POINTER(ReentryBatch)]),
     "prs_map_archive_struct_sizes": (None, [C.POINTER(C.c_uint64)]),
+    "prs_context_get_dispatch_env": (C.c_int, [_vp, C.POINTER(DispatchEnv)]),
+    "prs_stereo_plan": (C.c_int, [C.POINTER(StereoParams), C.POINTER(StereoBatch), C.POINTER(DispatchEnv), C.POINTER(DispatchPlan)]),
+    "prs_align_plan": (C.c_int, [C.POINTER(PcfParams), C.POINTER(AlignerParams), C.POINTER(AlignBatch), C.c_int32, C.POINTER(DispatchEnv),
+                                 C.POINTER(DispatchPlan)]),
+    "prs_bruteforce_plan": (C.c_int, [C.POINTER(BruteforceParams), C.POINTER(BruteforceBatch), C.POINTER(DispatchEnv), C.POINTER(DispatchPlan)]),
+    "prs_merge_plan": (C.c_int, [C.POINTER(MergerParams), C.POINTER(MergeBatch), C.POINTER(DispatchEnv), C.POINTER(DispatchPlan)]),
+    "prs_dispatch_kernel_name": (C.c_char_p, [C.c_int32, C.c_int32]),
+    "prs_dispatch_struct_sizes": (None, [C.POINTER(C.c_uint64)]),
     "prs_scene_clip_batch": (C.c_int, [_vp, C.POINTER(Projector), _vp, C.POINTER(ClipBatch)]),
     "prs_scene_clip": (C.c_int, [_vp, C.POINTER(Projector), _vp, _vp, _vp, _vp, C.c_int32, _vp, _vp, _vp, C.c_int32, _i32p]),
 }
@@ -631,5 +668,11 @@ def load():
         raise ImportError("libproslam_hip.so lays out prs_map_archive / prs_reentry_params / prs_reentry_batch as %s bytes, the Python "
                           "binding as %s: rebuild with `python -c 'import __graft_entry__ as g; g.build()'`"
                           % (list(sizes), [C.sizeof(MapArchive), C.sizeof(ReentryParams), C.sizeof(ReentryBatch)]))
+    sizes = (C.c_uint64 * 2)()
+    lib.prs_dispatch_struct_sizes(sizes)
+    if list(sizes) != [C.sizeof(DispatchEnv), C.sizeof(DispatchPlan)]:
+        raise ImportError("libproslam_hip.so lays out prs_dispatch_env / prs_dispatch_plan as %s bytes, the Python binding as %s: rebuild "
+                          "with `python -c 'import __graft_entry__ as g; g.build()'`"
+                          % (list(sizes), [C.sizeof(DispatchEnv), C.sizeof(DispatchPlan)]))
     _lib = lib
     return lib

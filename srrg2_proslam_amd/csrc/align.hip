@@ -2621,53 +2621,73 @@ struct SplitJob {
 };
 static int split_rounds(prs_context* ctx, SplitJob* job, int rounds);
 
-// mode PRS_MODE_ALIGN with the split pipeline only ENQUEUES `rounds` rounds (0 = the nominal five); align_batch_finish completes it
-int align_batch_launch(prs_context* ctx, const prs_pcf_params* finder, const prs_aligner_params* aligner, const prs_align_batch* batch, int mode, int rounds) {
-  if (ctx->align_job && static_cast<SplitJob*>(ctx->align_job)->active) {
-    return ctx_fail(ctx, PRS_ERR_UNSUPPORTED, "prs_align_batch_*: the previous batch of this context has not been finished (prs_align_batch_finish)");
-  }
-  if (!finder || !aligner || !batch || !batch->fixed || !batch->fixed_desc || !batch->n_fixed || !batch->moving ||
-      !batch->moving_desc || !batch->n_moving || !batch->state || !batch->X || !batch->corr || !batch->n_corr || !batch->result) {
-    return ctx_fail(ctx, PRS_ERR_NULL, "prs_align_batch_run: fixed, moving, correspondences, state or result not set");
-  }
+// align_kernel<THREADS, SPLIT, pattern, survivor slots> (the fused kernel, then the search kernels of the split pipeline) and
+// gn_kernel<SLOTS, DIM, KEEP_CLS, LDS_SLOTS, WAVES, PLAIN>
+#define AK(...) PRS_VARIANT("prs::", align_kernel, AlignArgs, __VA_ARGS__)
+#define GN(...) PRS_VARIANT("prs::", gn_kernel, AlignArgs, __VA_ARGS__)
+static const Variant<AlignArgs> kAlignVariants[] = {
+    AK(256, false, -1, 4),
+    AK(512, true, 2, 8), AK(512, true, 2, 4), AK(512, true, 1, 8), AK(512, true, 1, 4), AK(512, true, 3, 8), AK(512, true, 3, 4), AK(512, true, 0, 4),
+    GN(4, 4, false, 4, 1, 1), GN(4, 4, false, 4, 1, 0), GN(8, 4, false, 4, 1, 1), GN(8, 4, false, 4, 1, 0),  // lone: WAVES = 1
+    GN(4, 4, false, 4, 4, 2), GN(4, 4, false, 4, 4, 0), GN(4, 4, false, 4, 4, 1), GN(4, 3, true, 4, 4, 0), GN(4, 0, true, 4, 4, 0),
+    GN(8, 4, false, 3, 5, 2), GN(8, 4, false, 3, 5, 0), GN(8, 4, false, 3, 5, 1), GN(8, 3, true, 4, 4, 0), GN(8, 0, true, 4, 4, 0),
+};
+#undef AK
+#undef GN
+static_assert(kAlignThreads == 256 && kSearchThreads == 512 && kGnLdsSlots == 4 && PRS_SEARCH_KDTREE == 0 && PRS_SEARCH_SQUARE == 1 && PRS_SEARCH_CIRCLE == 2 &&
+                PRS_SEARCH_RHOMBUS == 3 && PRS_FACTOR_DEPTH == 3 && PRS_FACTOR_STEREO == 4,
+              "kAlignVariants spells these as literals");
+
+const char* align_kernel_name(int index) {
+  return index >= 0 && index < (int) (sizeof(kAlignVariants) / sizeof(kAlignVariants[0])) ? kAlignVariants[index].name : nullptr;
+}
+
+struct AlignPlan : Plan {  // launches: the fused kernel alone, or the search kernel and the Gauss-Newton kernel of one round
+  AlignArgs g = {}, gs = {};  // fused / Gauss-Newton side and search side: mode, max_fixed, the cell grid, lut_cap, surv_slots, the LDS carve, db_blob
+  bool split = false, stamps_split = false;
+  bool lone = false, five = false, fast = false, plain = false, mprior = false, depth = false;  // what picks the Gauss-Newton instantiation
+};
+
+static AlignPlan align_plan(const prs_pcf_params& finder, const prs_aligner_params& aligner, const prs_align_batch& batch, int mode, const DispatchEnv& env) {
+  AlignPlan p;
   if (mode < PRS_MODE_ALIGN || mode > PRS_MODE_LINEARIZE) {
-    return ctx_fail(ctx, PRS_ERR_UNSUPPORTED, "prs_align_batch_run: unknown mode");
+    p.refuse(PRS_ERR_UNSUPPORTED, "prs_align_batch_run: unknown mode");
+    return p;
   }
-  if (batch->batch <= 0) {
-    return PRS_OK;
+  if (batch.batch <= 0) {
+    return p;
   }
-  if (batch->fixed_stride <= 0 || batch->fixed_stride > 32767 || batch->moving_stride <= 0 || batch->moving_stride > 65535) {
-    return ctx_fail(ctx, PRS_ERR_UNSUPPORTED, "prs_align_batch_run: fixed_stride must be in [1,32767], moving_stride in [1,65535]");
+  if (batch.fixed_stride <= 0 || batch.fixed_stride > 32767 || batch.moving_stride <= 0 || batch.moving_stride > 65535) {
+    p.refuse(PRS_ERR_UNSUPPORTED, "prs_align_batch_run: fixed_stride must be in [1,32767], moving_stride in [1,65535]");
+    return p;
   }
-  if (finder->projector.canvas_rows <= 0 || finder->projector.canvas_rows > 8192 || finder->projector.canvas_cols <= 0 ||
-      finder->projector.canvas_cols > 32767) {
-    return ctx_fail(ctx, PRS_ERR_UNSUPPORTED, "prs_align_batch_run: projector canvas must be within 32767 x 8192");
+  if (finder.projector.canvas_rows <= 0 || finder.projector.canvas_rows > 8192 || finder.projector.canvas_cols <= 0 ||
+      finder.projector.canvas_cols > 32767) {
+    p.refuse(PRS_ERR_UNSUPPORTED, "prs_align_batch_run: projector canvas must be within 32767 x 8192");
+    return p;
   }
-  if (finder->maximum_search_radius_pixels > 16383 || finder->search_type < PRS_SEARCH_KDTREE || finder->search_type > PRS_SEARCH_RHOMBUS) {
-    return ctx_fail(ctx, PRS_ERR_UNSUPPORTED, "prs_align_batch_run: search radius > 16383 px or unknown search type");
+  if (finder.maximum_search_radius_pixels > 16383 || finder.search_type < PRS_SEARCH_KDTREE || finder.search_type > PRS_SEARCH_RHOMBUS) {
+    p.refuse(PRS_ERR_UNSUPPORTED, "prs_align_batch_run: search radius > 16383 px or unknown search type");
+    return p;
   }
-  if (aligner->factor_type != PRS_FACTOR_MONO && aligner->factor_type != PRS_FACTOR_DEPTH && aligner->factor_type != PRS_FACTOR_STEREO) {
-    return ctx_fail(ctx, PRS_ERR_UNSUPPORTED, "prs_align_batch_run: factor_type must be 2, 3 or 4");
+  if (aligner.factor_type != PRS_FACTOR_MONO && aligner.factor_type != PRS_FACTOR_DEPTH && aligner.factor_type != PRS_FACTOR_STEREO) {
+    p.refuse(PRS_ERR_UNSUPPORTED, "prs_align_batch_run: factor_type must be 2, 3 or 4");
+    return p;
   }
-  if ((aligner->kernel_weight_form != PRS_KERNEL_WEIGHT_INV_CHI && aligner->kernel_weight_form != PRS_KERNEL_WEIGHT_TAU_OVER_CHI) ||
-      (aligner->damping_form != PRS_DAMPING_DIAG && aligner->damping_form != PRS_DAMPING_IDENTITY) ||
-      (aligner->translation_weight_form != PRS_TRANSLATION_WEIGHT_OFFSET && aligner->translation_weight_form != PRS_TRANSLATION_WEIGHT_CLAMP)) {
-    return ctx_fail(ctx, PRS_ERR_UNSUPPORTED, "prs_align_batch_run: unknown kernel_weight_form / damping_form / translation_weight_form");
+  if ((aligner.kernel_weight_form != PRS_KERNEL_WEIGHT_INV_CHI && aligner.kernel_weight_form != PRS_KERNEL_WEIGHT_TAU_OVER_CHI) ||
+      (aligner.damping_form != PRS_DAMPING_DIAG && aligner.damping_form != PRS_DAMPING_IDENTITY) ||
+      (aligner.translation_weight_form != PRS_TRANSLATION_WEIGHT_OFFSET && aligner.translation_weight_form != PRS_TRANSLATION_WEIGHT_CLAMP)) {
+    p.refuse(PRS_ERR_UNSUPPORTED, "prs_align_batch_run: unknown kernel_weight_form / damping_form / translation_weight_form");
+    return p;
   }
-  AlignArgs g;
-  g.f          = *finder;
-  g.a          = *aligner;
-  g.b          = *batch;
+  AlignArgs& g = p.g;
   g.mode       = mode;
-  g.no_prefilter = ctx->no_prefilter ? 1 : 0;
-  g.narrow_prefilter_limit = ctx->prefilter_96_limit;
-  g.prior_mean = batch->prior_mean;
-  g.rows_table = finder->projector.canvas_rows;
-  const int max_fixed = batch->max_fixed > 0 && batch->max_fixed < batch->fixed_stride ? batch->max_fixed : batch->fixed_stride;
+  g.rows_table = finder.projector.canvas_rows;
+  const int max_fixed = batch.max_fixed > 0 && batch.max_fixed < batch.fixed_stride ? batch.max_fixed : batch.fixed_stride;
   g.max_fixed       = max_fixed;
   const uint32_t nf = (uint32_t) max_fixed;
   const uint32_t R  = (uint32_t) g.rows_table;
-  uint32_t lut_cap  = 2u * (uint32_t) finder->maximum_search_radius_pixels + 1u;
+  uint32_t lut_cap  = 2u * (uint32_t) finder.maximum_search_radius_pixels + 1u;
   if (lut_cap > 2048u) {
     lut_cap = 2048u;
   }
@@ -2676,7 +2696,7 @@ int align_batch_launch(prs_context* ctx, const prs_pcf_params* finder, const prs
   int sy = 4, sx = 4;
   auto cells_of = [&](int shift_y, int shift_x, int& ncy, int& ncx) {
     ncy = ((int) R + (1 << shift_y) - 1) >> shift_y;
-    ncx = (finder->projector.canvas_cols + (1 << shift_x) - 1) >> shift_x;
+    ncx = (finder.projector.canvas_cols + (1 << shift_x) - 1) >> shift_x;
     return ncy * ncx;
   };
   int ncy = 0, ncx = 0;
@@ -2696,7 +2716,7 @@ int align_batch_launch(prs_context* ctx, const prs_pcf_params* finder, const prs
   // them through the committed correspondence vector)
   // the KD-tree finder keeps its tree where the lattice finders keep theirs: nodes in `db`, leaf members in `inv`, root + leaf
   // offsets in `cellstart` (2 + n_leaves + 1 <= max_fixed + 3 entries)
-  const bool kdtree         = finder->search_type == PRS_SEARCH_KDTREE;
+  const bool kdtree         = finder.search_type == PRS_SEARCH_KDTREE;
   const uint32_t cs_entries = kdtree && nf + 4u > (uint32_t) g.ncells + 2u ? nf + 4u : (uint32_t) g.ncells + 2u;
   auto carve = [&](AlignArgs& g, bool with_operands) -> size_t {
     uint32_t off = 0;
@@ -2711,7 +2731,7 @@ int align_batch_launch(prs_context* ctx, const prs_pcf_params* finder, const prs
     // search-phase arrays
     uint32_t u = off;
     g.off_fdesc  = u; u = align_up16(u + nf * 32);
-    g.off_fuv    = u; u = align_up16(u + (finder->search_type == PRS_SEARCH_KDTREE ? nf * 8 : 0));
+    g.off_fuv    = u; u = align_up16(u + (kdtree ? nf * 8 : 0));
     g.off_best   = u; u = align_up16(u + nf * 4);
     g.off_second = u; u = align_up16(u + nf * 4);
     g.off_lut    = u; u = align_up16(u + lut_cap * 2);
@@ -2734,32 +2754,105 @@ int align_batch_launch(prs_context* ctx, const prs_pcf_params* finder, const prs
   g.surv_slots     = 4;
   const size_t lds = carve(g, true);
   if (lds > 160 * 1024) {
-    return ctx_fail(ctx, PRS_ERR_UNSUPPORTED, "prs_align_batch_run: fixed cloud does not fit the 160 KiB LDS (lower max_fixed)");
+    p.refuse(PRS_ERR_UNSUPPORTED, "prs_align_batch_run: fixed cloud does not fit the 160 KiB LDS (lower max_fixed)");
+    return p;
   }
-  g.stamps = ctx_stamps(ctx, (size_t) batch->batch * 16 * sizeof(unsigned long long));
-  g.ops     = nullptr;
-  g.ctl     = nullptr;
-  g.pending = nullptr;
-  g.dbcache = nullptr;
-  g.db_blob = 0;
-  g.rowcache = nullptr;
-  hipStream_t stream = ctx_stream(ctx);
-  hipError_t e;
-  // diagnostic: PRS_STAMPS=1 times the phases of the fused kernel; with PRS_STAMPS_SPLIT=1 the split pipeline
-  // runs instead and the finder phases of every search launch are reported
   if (max_fixed >= (int) kClsOutUnit) {
     // the class counts of a linearisation travel as ONE exact float code (#inliers + kClsOutUnit * #kernelised)
-    return ctx_fail(ctx, PRS_ERR_UNSUPPORTED, "prs_align_batch_run: max_fixed must be below 2048");
+    p.refuse(PRS_ERR_UNSUPPORTED, "prs_align_batch_run: max_fixed must be below 2048");
+    return p;
   }
-  const bool stamps_split = g.stamps && ctx->stamps_split;
-  const bool split = mode == PRS_MODE_ALIGN && !ctx_fused_align(ctx) && max_fixed <= kGnThreads * kGnSlots && (!g.stamps || stamps_split);
-  if (!split) {
-    auto kernel = align_kernel<kAlignThreads, false, -1>;
-    e           = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds);
+  // diagnostic: PRS_STAMPS=1 times the phases of the fused kernel; with PRS_STAMPS_SPLIT=1 the split pipeline
+  // runs instead and the finder phases of every search launch are reported
+  p.stamps_split = env.stamps && env.stamps_split;
+  p.split        = mode == PRS_MODE_ALIGN && !env.fused_align && max_fixed <= kGnThreads * kGnSlots && (!env.stamps || p.stamps_split);
+  if (!p.split) {
+    p.add(find_variant(kAlignVariants, {kAlignThreads, 0, -1, 4}), batch.batch, 1, kAlignThreads, lds);
+    return p;
+  }
+  // ---- split pipeline: search kernel (512 threads/frame) and GN kernel (operands in registers,
+  //      ~30 KB LDS, many frames per CU) alternate; every launch skips frames that do not wait for it.
+  AlignArgs& gs = p.gs;
+  gs            = g;
+  gs.mode       = kModeSplitSearch;
+  // eight survivor slots per thread where they cost no resident workgroup (a wide search radius or correlated rows overflow four:
+  // tum.conf's shape 1.02 -> 0.93 ms per 6144 frames), four otherwise (the headline's 49.6 + 4 KB keep three workgroups per CU)
+  gs.surv_slots = 8;  // (the KD-tree finder parks nothing)
+  size_t lds_search = carve(gs, false);
+  gs.surv_slots     = 4;
+  {
+    const size_t lds4 = carve(gs, false);
+    if ((160u * 1024u) / lds_search == (160u * 1024u) / lds4 && !kdtree) {
+      gs.surv_slots = 8;
+      lds_search    = carve(gs, false);
+    } else {
+      lds_search = lds4;
+    }
+  }
+  // image of the lattice arrays (contiguous in LDS: db | inv | cellstart), kept per frame between search launches
+  gs.db_blob = align_up16(gs.off_cellstart + cs_entries * 2) - gs.off_db;
+  // two waves per frame (eight frames resident per CU: the kernel is bound by its single-wave phases and by
+  // instruction issue, more independent frames fill the idle slots)
+  p.add(find_variant(kAlignVariants, {kSearchThreads, 1, finder.search_type, gs.surv_slots}), batch.batch, 1, kSearchThreads, lds_search);
+  // (the rectified-stereo factor, the one kitti.conf / euroc.conf use, has its own instantiation: the factor type as a
+  // compile-time constant removes ~10 selects per linearised correspondence; so does not remembering the factor classes)
+  p.fast = aligner.factor_type == PRS_FACTOR_STEREO && !aligner.keep_only_inlier_correspondences && aligner.kernel_weight_form == PRS_KERNEL_WEIGHT_INV_CHI &&
+           aligner.damping_form == PRS_DAMPING_DIAG && aligner.translation_weight_form == PRS_TRANSLATION_WEIGHT_OFFSET;
+  // a batch that cannot fill the chip (fewer frames than two per CU) is bound by the serial chain of each frame, not by occupancy:
+  // its instantiation may use the whole register file (WAVES = 1: no spills in the solve, the compiler schedules for latency)
+  p.lone = p.fast && batch.batch <= 2 * env.cus && !env.no_lone_gn;
+  p.five = p.fast && !p.lone && max_fixed > 4 * 128;  // (gn_kernel: LDS_SLOTS / WAVES)
+  const bool lean = !batch.prior && !aligner.with_sensor && !aligner.enable_inlier_only_runs;
+  p.plain  = lean && !aligner.enable_motion_prior;  // (gn_kernel / gn_solve_wave: PLAIN = 1)
+  p.mprior = lean && aligner.enable_motion_prior;   // (PLAIN = 2; the lone instantiations have no form of their own for it)
+  // (the depth factor of the RGB-D configurations -- tum.conf / icl.conf: kept classes, inlier-only runs -- as a compile-time constant too)
+  p.depth = aligner.factor_type == PRS_FACTOR_DEPTH && aligner.kernel_weight_form == PRS_KERNEL_WEIGHT_INV_CHI && aligner.damping_form == PRS_DAMPING_DIAG;
+  const int slots = max_fixed <= 4 * 128 ? 4 : 8, lds_slots = p.five ? 3 : kGnLdsSlots;
+  const int gn    = p.fast ? find_variant(kAlignVariants, {slots, PRS_FACTOR_STEREO, 0, lds_slots, p.lone ? 1 : (p.five ? 5 : 4),
+                                                           p.plain ? 1 : (p.mprior && !p.lone ? 2 : 0)})
+                           : find_variant(kAlignVariants, {slots, p.depth ? PRS_FACTOR_DEPTH : 0, 1, kGnLdsSlots, 4, 0});
+  p.add(gn, batch.batch, 1, kGnThreads, gn_lds_bytes(lds_slots));
+  return p;
+}
+
+// mode PRS_MODE_ALIGN with the split pipeline only ENQUEUES `rounds` rounds (0 = the nominal five); align_batch_finish completes it
+int align_batch_launch(prs_context* ctx, const prs_pcf_params* finder, const prs_aligner_params* aligner, const prs_align_batch* batch, int mode, int rounds) {
+  if (ctx->align_job && static_cast<SplitJob*>(ctx->align_job)->active) {
+    return ctx_fail(ctx, PRS_ERR_UNSUPPORTED, "prs_align_batch_*: the previous batch of this context has not been finished (prs_align_batch_finish)");
+  }
+  if (!finder || !aligner || !batch || !batch->fixed || !batch->fixed_desc || !batch->n_fixed || !batch->moving ||
+      !batch->moving_desc || !batch->n_moving || !batch->state || !batch->X || !batch->corr || !batch->n_corr || !batch->result) {
+    return ctx_fail(ctx, PRS_ERR_NULL, "prs_align_batch_run: fixed, moving, correspondences, state or result not set");
+  }
+  const AlignPlan plan = align_plan(*finder, *aligner, *batch, mode, dispatch_env(ctx));
+  if (plan.status != PRS_OK) {
+    return ctx_fail(ctx, plan.status, plan.message);
+  }
+  if (plan.n_launches == 0) {
+    return PRS_OK;
+  }
+  unsigned long long* stamps = ctx_stamps(ctx, (size_t) batch->batch * 16 * sizeof(unsigned long long));
+  auto with_inputs = [&](AlignArgs a) {  // a side's layout from the plan + what the caller and the context supply
+    a.f          = *finder;
+    a.a          = *aligner;
+    a.b          = *batch;
+    a.no_prefilter = ctx->no_prefilter ? 1 : 0;
+    a.narrow_prefilter_limit = ctx->prefilter_96_limit;
+    a.prior_mean = batch->prior_mean;
+    a.stamps     = stamps;
+    return a;
+  };
+  AlignArgs g        = with_inputs(plan.g);
+  hipStream_t stream = ctx_stream(ctx);
+  hipError_t e;
+  if (!plan.split) {
+    const Plan::Launch& l = plan.launch[0];
+    auto kernel = kAlignVariants[l.kernel].fn;
+    e           = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int) l.lds);
     if (e != hipSuccess) {
       return ctx_fail_hip(ctx, e, "prs_align_batch_run attribute");
     }
-    hipLaunchKernelGGL(kernel, dim3(batch->batch), dim3(kAlignThreads), lds, stream, g);
+    hipLaunchKernelGGL(kernel, dim3(l.grid_x), dim3(l.block), l.lds, stream, g);
     e = hipGetLastError();
     if (e != hipSuccess) {
       return ctx_fail_hip(ctx, e, "prs_align_batch_run launch");
@@ -2769,14 +2862,14 @@ int align_batch_launch(prs_context* ctx, const prs_pcf_params* finder, const prs
     }
     return PRS_OK;
   }
-  // ---- split pipeline: search kernel (512 threads/frame) and GN kernel (operands in registers,
-  //      ~30 KB LDS, many frames per CU) alternate; every launch skips frames that do not wait for it.
+  const Plan::Launch &ls = plan.launch[0], &lg = plan.launch[1];  // search, Gauss-Newton
   SplitJob* job = static_cast<SplitJob*>(ctx->align_job);
   if (!job) {
     job                 = new SplitJob();
     ctx->align_job      = job;
     ctx->align_job_free = [](void* p) { delete static_cast<SplitJob*>(p); };
   }
+  const int max_fixed    = g.max_fixed;
   const size_t ops_bytes = (size_t) batch->batch * (size_t) max_fixed * 2 * sizeof(float4);
   const size_t ctl_bytes = (size_t) batch->batch * sizeof(FrameCtl) + 256;
   unsigned char* small   = static_cast<unsigned char*>(job->buffer(stream, 0, ctl_bytes));
@@ -2786,73 +2879,26 @@ int align_batch_launch(prs_context* ctx, const prs_pcf_params* finder, const prs
   }
   g.pending = reinterpret_cast<int*>(small);
   g.ctl     = reinterpret_cast<FrameCtl*>(small + 256);
-  AlignArgs gs = g;
-  gs.mode      = kModeSplitSearch;
-  // eight survivor slots per thread where they cost no resident workgroup (a wide search radius or correlated rows overflow four:
-  // tum.conf's shape 1.02 -> 0.93 ms per 6144 frames), four otherwise (the headline's 49.6 + 4 KB keep three workgroups per CU)
-  gs.surv_slots = 8;  // (the KD-tree finder parks nothing)
-  size_t lds_search = carve(gs, false);
-  gs.surv_slots     = 4;
-  {
-    const size_t lds4 = carve(gs, false);
-    if ((160u * 1024u) / lds_search == (160u * 1024u) / lds4 && finder->search_type != PRS_SEARCH_KDTREE) {
-      gs.surv_slots = 8;
-      lds_search    = carve(gs, false);
-    } else {
-      lds_search = lds4;
-    }
-  }
-  // image of the lattice arrays (contiguous in LDS: db | inv | cellstart), kept per frame between search launches
-  gs.db_blob = align_up16(gs.off_cellstart + cs_entries * 2) - gs.off_db;
-  gs.dbcache = static_cast<unsigned char*>(job->buffer(stream, 2, (size_t) batch->batch * gs.db_blob));
+  AlignArgs gs = with_inputs(plan.gs);
+  gs.ops       = g.ops;
+  gs.pending   = g.pending;
+  gs.ctl       = g.ctl;
+  gs.dbcache   = static_cast<unsigned char*>(job->buffer(stream, 2, (size_t) batch->batch * gs.db_blob));
   if (!gs.dbcache) {
     return ctx_fail(ctx, PRS_ERR_HIP, "prs_align_batch_run: lattice cache allocation failed");
   }
   // ... and, for the lattice patterns, the fixed descriptor rows in lattice order (two half-row arrays of max_fixed entries per frame)
-  gs.rowcache = nullptr;
-  if (!kdtree) {
+  if (finder->search_type != PRS_SEARCH_KDTREE) {
     gs.rowcache = static_cast<au32x4*>(job->buffer(stream, 3, (size_t) batch->batch * (size_t) max_fixed * 2 * sizeof(au32x4)));
     if (!gs.rowcache) {
       return ctx_fail(ctx, PRS_ERR_HIP, "prs_align_batch_run: descriptor row cache allocation failed");
     }
   }
-  const bool wide_slots = gs.surv_slots == 8;
-  auto skernel = finder->search_type == PRS_SEARCH_CIRCLE
-                   ? (wide_slots ? align_kernel<kSearchThreads, true, PRS_SEARCH_CIRCLE, 8> : align_kernel<kSearchThreads, true, PRS_SEARCH_CIRCLE, 4>)
-                   : (finder->search_type == PRS_SEARCH_SQUARE
-                        ? (wide_slots ? align_kernel<kSearchThreads, true, PRS_SEARCH_SQUARE, 8> : align_kernel<kSearchThreads, true, PRS_SEARCH_SQUARE, 4>)
-                        : (finder->search_type == PRS_SEARCH_RHOMBUS
-                             ? (wide_slots ? align_kernel<kSearchThreads, true, PRS_SEARCH_RHOMBUS, 8> : align_kernel<kSearchThreads, true, PRS_SEARCH_RHOMBUS, 4>)
-                             : align_kernel<kSearchThreads, true, PRS_SEARCH_KDTREE, 4>));
-  // two waves per frame (eight frames resident per CU: the kernel is bound by its single-wave phases and by
-  // instruction issue, more independent frames fill the idle slots)
-  e = hipFuncSetAttribute(reinterpret_cast<const void*>(skernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds_search);
+  e = hipFuncSetAttribute(reinterpret_cast<const void*>(kAlignVariants[ls.kernel].fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int) ls.lds);
   if (e != hipSuccess) {
     return ctx_fail_hip(ctx, e, "prs_align_batch_run attribute");
   }
   hipLaunchKernelGGL(split_init_kernel, dim3((batch->batch + 255) / 256), dim3(256), 0, stream, g.ctl, batch->result, g.pending, batch->batch);
-  // (the rectified-stereo factor, the one kitti.conf / euroc.conf use, has its own instantiation: the factor type as a
-  // compile-time constant removes ~10 selects per linearised correspondence; so does not remembering the factor classes)
-  const bool fast = aligner->factor_type == PRS_FACTOR_STEREO && !aligner->keep_only_inlier_correspondences && aligner->kernel_weight_form == PRS_KERNEL_WEIGHT_INV_CHI &&
-                    aligner->damping_form == PRS_DAMPING_DIAG && aligner->translation_weight_form == PRS_TRANSLATION_WEIGHT_OFFSET;
-  // a batch that cannot fill the chip (fewer frames than two per CU) is bound by the serial chain of each frame, not by occupancy:
-  // its instantiation may use the whole register file (WAVES = 1: no spills in the solve, the compiler schedules for latency)
-  int n_cu = 0;
-  (void) hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, ctx->device);
-  const bool lone = fast && batch->batch <= 2 * (n_cu > 0 ? n_cu : 256) && !ctx->no_lone_gn;
-  const bool five = fast && !lone && max_fixed > 4 * 128;  // (gn_kernel: LDS_SLOTS / WAVES)
-  const bool lean  = !batch->prior && !aligner->with_sensor && !aligner->enable_inlier_only_runs;
-  const bool plain = lean && !aligner->enable_motion_prior;   // (gn_kernel / gn_solve_wave: PLAIN = 1)
-  const bool mprior = lean && aligner->enable_motion_prior;   // (PLAIN = 2)
-  // (the depth factor of the RGB-D configurations -- tum.conf / icl.conf: kept classes, inlier-only runs -- as a compile-time constant too)
-  const bool depth = aligner->factor_type == PRS_FACTOR_DEPTH && aligner->kernel_weight_form == PRS_KERNEL_WEIGHT_INV_CHI && aligner->damping_form == PRS_DAMPING_DIAG;
-  auto gnk        = lone ? (max_fixed <= 4 * 128 ? (plain ? gn_kernel<4, PRS_FACTOR_STEREO, false, kGnLdsSlots, 1, 1> : gn_kernel<4, PRS_FACTOR_STEREO, false, kGnLdsSlots, 1>)
-                                                 : (plain ? gn_kernel<8, PRS_FACTOR_STEREO, false, kGnLdsSlots, 1, 1> : gn_kernel<8, PRS_FACTOR_STEREO, false, kGnLdsSlots, 1>))
-                         : (max_fixed <= 4 * 128 ? (fast ? (plain ? gn_kernel<4, PRS_FACTOR_STEREO, false, kGnLdsSlots, 4, 1> : (mprior ? gn_kernel<4, PRS_FACTOR_STEREO, false, kGnLdsSlots, 4, 2> : gn_kernel<4, PRS_FACTOR_STEREO, false>))
-                                                         : (depth ? gn_kernel<4, PRS_FACTOR_DEPTH, true> : gn_kernel<4, 0, true>))
-                                                 : (fast ? (plain ? gn_kernel<8, PRS_FACTOR_STEREO, false, 3, 5, 1> : (mprior ? gn_kernel<8, PRS_FACTOR_STEREO, false, 3, 5, 2> : gn_kernel<8, PRS_FACTOR_STEREO, false, 3, 5>))
-                                                         : (depth ? gn_kernel<8, PRS_FACTOR_DEPTH, true> : gn_kernel<8, 0, true>)));
-  const size_t lds_gn = gn_lds_bytes(five ? 3 : kGnLdsSlots);
   // The job lives in the context until align_batch_finish: the rounds are plain launches on the context's stream (no host
   // synchronisation here, the sequence can be captured in a HIP graph once the scratch buffers exist).
   job->active      = true;
@@ -2860,15 +2906,15 @@ int align_batch_launch(prs_context* ctx, const prs_pcf_params* finder, const prs
   job->capture_stream = stream;
   job->g           = g;
   job->gs          = gs;
-  job->search      = reinterpret_cast<void (*)(AlignArgs)>(skernel);
-  job->gn          = reinterpret_cast<void (*)(AlignArgs)>(gnk);
-  job->lds_search  = lds_search;
-  job->lds_gn      = lds_gn;
+  job->search      = kAlignVariants[ls.kernel].fn;
+  job->gn          = kAlignVariants[lg.kernel].fn;
+  job->lds_search  = ls.lds;
+  job->lds_gn      = lg.lds;
   job->total       = 0;
   job->limit       = 2 * (aligner->max_iterations + inlier_run_length(*aligner)) + 8;
   job->ev_used     = 0;
   job->rounds_timed = 0;
-  job->stamps      = stamps_split;
+  job->stamps      = plan.stamps_split && stamps;
   job->enqueued    = rounds > 0 ? rounds : 5;
   return split_rounds(ctx, job, job->enqueued);
 }
@@ -3023,3 +3069,20 @@ int gn_step_launch(prs_context* ctx, const float* dH, const float* db, float dam
 }
 
 }  // namespace prs
+
+extern "C" int prs_align_plan(const prs_pcf_params* finder, const prs_aligner_params* aligner, const prs_align_batch* batch, int32_t mode,
+                              const prs_dispatch_env* env, prs_dispatch_plan* out) {
+  if (!finder || !aligner || !batch || !env || !out) {
+    return PRS_ERR_NULL;
+  }
+  const prs::AlignPlan p = prs::align_plan(*finder, *aligner, *batch, mode, *env);
+  prs::export_plan(p, prs::kAlignVariants, out);
+  const prs::AlignArgs& g = p.g;
+  int32_t* f = out->fact;
+  f[PRS_PLAN_ALIGN_MAX_FIXED] = g.max_fixed, f[PRS_PLAN_ALIGN_CELL_SY] = g.cell_sy, f[PRS_PLAN_ALIGN_CELL_SX] = g.cell_sx, f[PRS_PLAN_ALIGN_CELL_NCY] = g.cell_ncy;
+  f[PRS_PLAN_ALIGN_CELL_NCX] = g.cell_ncx, f[PRS_PLAN_ALIGN_LUT_CAP] = g.lut_cap, f[PRS_PLAN_ALIGN_SPLIT] = p.split;
+  f[PRS_PLAN_ALIGN_SURV_SLOTS] = p.split ? p.gs.surv_slots : g.surv_slots, f[PRS_PLAN_ALIGN_DB_BLOB] = (int32_t) p.gs.db_blob, f[PRS_PLAN_ALIGN_LONE] = p.lone;
+  f[PRS_PLAN_ALIGN_FIVE] = p.five, f[PRS_PLAN_ALIGN_FAST] = p.fast, f[PRS_PLAN_ALIGN_PLAIN] = p.plain, f[PRS_PLAN_ALIGN_MPRIOR] = p.mprior;
+  f[PRS_PLAN_ALIGN_DEPTH] = p.depth, f[PRS_PLAN_ALIGN_OFF_U] = (int32_t) g.off_u, f[PRS_PLAN_ALIGN_SEARCH_OFF_U] = (int32_t) p.gs.off_u;
+  return PRS_OK;
+}

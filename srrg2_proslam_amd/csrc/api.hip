@@ -153,6 +153,24 @@ void ctx_report_stamps(prs_context* ctx, int blocks, int n_stamps, const char* l
   fprintf(stderr, " | total %.0f\n", total);
 }
 
+DispatchEnv dispatch_env(const prs_context* ctx) {
+  DispatchEnv env;
+  env.cus            = ctx->cus;
+  env.fused_align    = ctx->fused_align;
+  env.matcher_v3     = ctx->matcher_v3;
+  env.force_unstaged = ctx->force_unstaged;
+  env.no_lone_gn     = ctx->no_lone_gn;
+  env.merge_fused    = ctx->merge_fused;
+  env.bf_mfma        = ctx->bf_mfma;
+  env.stamps         = ctx->stamps_enabled;
+  env.stamps_split   = ctx->stamps_split;
+  // (tests and A-B runs set these two after the library is loaded: read per launch)
+  env.bf_global_state   = getenv("PRS_BF_GLOBAL_STATE") != nullptr;
+  const char* two_wg    = getenv("PRS_BF_TWO_WORKGROUPS");
+  env.bf_two_workgroups = two_wg ? (two_wg[0] == '1' ? 1 : 0) : -1;
+  return env;
+}
+
 } // namespace prs
 
 using namespace prs;
@@ -212,6 +230,10 @@ int prs_context_create(int device_id, prs_context** out) {
     return PRS_ERR_HIP;
   }
   ctx->stream          = ctx->own;
+  int cus              = 0;
+  if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device_id) == hipSuccess && cus > 0) {
+    ctx->cus = cus;
+  }
   const char* unstaged = getenv("PRS_FORCE_UNSTAGED");
   ctx->force_unstaged  = unstaged && unstaged[0] == '1';
   const char* v3       = getenv("PRS_MATCHER_V3");
@@ -234,6 +256,29 @@ int prs_context_create(int device_id, prs_context** out) {
   ctx->merge_fused     = mfused && mfused[0] == '1';
   *out                 = ctx;
   return PRS_OK;
+}
+
+int prs_context_get_dispatch_env(const prs_context* ctx, prs_dispatch_env* env) {
+  if (!ctx || !env) {
+    return PRS_ERR_NULL;
+  }
+  *env = dispatch_env(ctx);
+  return PRS_OK;
+}
+
+const char* prs_dispatch_kernel_name(int32_t family, int32_t index) {
+  switch (family) {
+    case PRS_DISPATCH_STEREO: return stereo_kernel_name(index);
+    case PRS_DISPATCH_ALIGN: return align_kernel_name(index);
+    case PRS_DISPATCH_BRUTEFORCE: return bruteforce_kernel_name(index);
+    case PRS_DISPATCH_MERGE: return merge_kernel_name(index);
+    default: return nullptr;
+  }
+}
+
+void prs_dispatch_struct_sizes(uint64_t* sizes2) {
+  sizes2[0] = sizeof(prs_dispatch_env);
+  sizes2[1] = sizeof(prs_dispatch_plan);
 }
 
 int prs_context_destroy(prs_context* ctx) {

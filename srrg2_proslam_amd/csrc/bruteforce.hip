@@ -1080,44 +1080,50 @@ static inline uint32_t bf_align16(uint32_t v) {
   return (v + 15u) & ~15u;
 }
 
-int bruteforce_batch_launch(prs_context* ctx, const prs_bruteforce_params* params, const prs_bruteforce_batch* batch) {
-  if (!params || !batch || !batch->fixed_desc || !batch->n_fixed) {
-    return ctx_fail(ctx, PRS_ERR_NULL, "prs_bruteforce_match: fixed not set");  // bruteforce_impl.cpp:204-206
+// every kernel of the matcher, in the order the plan's comments below name them
+#define BF(...) PRS_VARIANT("prs::", bruteforce_kernel, BfArgs, __VA_ARGS__)
+static const Variant<BfArgs> kBfVariants[] = {
+    PRS_VARIANT_PLAIN("prs::", bruteforce_dense_mfma_kernel, BfArgs, -1),
+    BF(1, 1, false, 1024), BF(2, 1, false, 1024), BF(4, 1, false, 1024), BF(8, 1, false, 1024),  // kBfDense
+    BF(1, 2, false, 1024), BF(2, 2, false, 1024), BF(4, 2, false, 1024), BF(8, 2, false, 1024),  // kBfRegister
+    BF(1, 0, true, 512),   BF(1, 0, true, 1024),                                                 // kBfFused on the matrix cores
+    BF(1, 0, false, 1024), BF(2, 0, false, 1024), BF(4, 0, false, 1024), BF(8, 0, false, 1024),  // kBfFused
+};
+#undef BF
+static_assert(kBfFused == 0 && kBfDense == 1 && kBfRegister == 2 && kBfThreads == 1024 && kBfmThreads == 512, "kBfVariants spells these as literals");
+
+struct BfPlan : Plan {
+  BfArgs a = {};  // lim, nw, cap, chunks, the LDS carve, lvl_cap (the batch descriptor and the pointers are the launch's)
+  bool bm_fits = false, fused_matrix = false, dual = false, mfma = false;
+  int grid     = 0;     // workgroups of the fused shape = rows of the scratch arrays
+  uint32_t lds = 0;     // dynamic LDS of the bruteforce_kernel launches
+  size_t b_cand = 0, b_bm = 0, b_acc = 0;  // scratch: candidates (twice), bitmaps, accumulators of the split shape
+};
+
+static BfPlan bruteforce_plan(const prs_bruteforce_params& params, const prs_bruteforce_batch& batch, const DispatchEnv& env) {
+  BfPlan p;
+  BfArgs& a = p.a;
+  if (batch.batch <= 0) {
+    return p;
   }
-  if (!batch->moving_desc || !batch->n_moving) {
-    return ctx_fail(ctx, PRS_ERR_NULL, "prs_bruteforce_match: moving not set");  // :207-210
+  if (batch.fixed_stride <= 0 || batch.moving_stride <= 0 || batch.fixed_stride > 8192 || batch.moving_stride > 65535) {
+    p.refuse(PRS_ERR_UNSUPPORTED, "prs_bruteforce_match: fixed_stride must be in [1,8192], moving_stride in [1,65535]");
+    return p;
   }
-  if (!batch->matches || !batch->n_matches || !batch->status) {
-    return ctx_fail(ctx, PRS_ERR_NULL, "prs_bruteforce_match: correspondences not set");  // :211-214
-  }
-  if (batch->batch <= 0) {
-    return PRS_OK;
-  }
-  if (batch->fixed_stride <= 0 || batch->moving_stride <= 0 || batch->fixed_stride > 8192 || batch->moving_stride > 65535) {
-    return ctx_fail(ctx, PRS_ERR_UNSUPPORTED, "prs_bruteforce_match: fixed_stride must be in [1,8192], moving_stride in [1,65535]");
-  }
-  BfArgs a;
-  a.b         = *batch;
-  a.max_ratio = params->maximum_distance_ratio_to_second_best;
   // (float) d < maximum_descriptor_distance for integer d  <=>  d < lim
   int lim = 0;
-  while (lim <= 257 && (float) lim < params->maximum_descriptor_distance) {
+  while (lim <= 257 && (float) lim < params.maximum_descriptor_distance) {
     ++lim;
   }
   if (lim > kBfLevels) {
-    return ctx_fail(ctx, PRS_ERR_UNSUPPORTED, "prs_bruteforce_match: maximum_descriptor_distance above 256 bits");
+    p.refuse(PRS_ERR_UNSUPPORTED, "prs_bruteforce_match: maximum_descriptor_distance above 256 bits");
+    return p;
   }
   a.lim = lim;
   a.nw  = lim > 0 ? (lim + 31) / 32 : 1;
-  const int big = batch->fixed_stride > batch->moving_stride ? batch->fixed_stride : batch->moving_stride;
-  a.cap = batch->candidate_capacity > 0 ? batch->candidate_capacity : 16 * big;
-  int cus = 256;
-  {
-    hipDeviceProp_t prop;
-    if (hipGetDeviceProperties(&prop, ctx->device) == hipSuccess && prop.multiProcessorCount > 0) {
-      cus = prop.multiProcessorCount;
-    }
-  }
+  const int big = batch.fixed_stride > batch.moving_stride ? batch.fixed_stride : batch.moving_stride;
+  a.cap = batch.candidate_capacity > 0 ? batch.candidate_capacity : 16 * big;
+  const int cus = env.cus;
   // Which kernels score the pairs (prs_context_set_bruteforce_dense_phase).  PRS_BF_DENSE_MATRIX_WHEN_FULL, the default: a batch of
   // 32 or more cloud pairs takes the fused shape with its dense phase on the matrix cores
   // (bruteforce_kernel<1, kBfFused, true>: 1024 real cloud pairs 0.99 -> 0.62 ms, 1024 pairs of 2000 uniform random rows 2.75 -> 1.23 ms);
@@ -1125,25 +1131,26 @@ int bruteforce_batch_launch(prs_context* ctx, const prs_bruteforce_params* param
   // 0.11 ms against 0.23 ms).
   // LDS of the fused / registration workgroups: the registration state first
   uint32_t off = 0;
-  a.off_cnt_f = off; off = bf_align16(off + (uint32_t) batch->fixed_stride * 4);
-  a.off_cnt_m = off; off = bf_align16(off + (uint32_t) batch->moving_stride * 4);
-  a.off_reg_f = off; off = bf_align16(off + (uint32_t) batch->fixed_stride);
-  a.off_reg_m = off; off = bf_align16(off + (uint32_t) batch->moving_stride);
-  a.off_acc   = off; off = bf_align16(off + (uint32_t) batch->fixed_stride * 4);
+  a.off_cnt_f = off; off = bf_align16(off + (uint32_t) batch.fixed_stride * 4);
+  a.off_cnt_m = off; off = bf_align16(off + (uint32_t) batch.moving_stride * 4);
+  a.off_reg_f = off; off = bf_align16(off + (uint32_t) batch.fixed_stride);
+  a.off_reg_m = off; off = bf_align16(off + (uint32_t) batch.moving_stride);
+  a.off_acc   = off; off = bf_align16(off + (uint32_t) batch.fixed_stride * 4);
   a.off_hist  = off; off = bf_align16(off + (4 * kBfLevels + 8) * 4);
   if (off > 160u * 1024u) {
-    return ctx_fail(ctx, PRS_ERR_UNSUPPORTED, "prs_bruteforce_match: clouds do not fit the 160 KiB LDS");
+    p.refuse(PRS_ERR_UNSUPPORTED, "prs_bruteforce_match: clouds do not fit the 160 KiB LDS");
+    return p;
   }
-  const uint64_t bm_bytes  = (uint64_t) (batch->fixed_stride + batch->moving_stride) * (uint64_t) a.nw * 4u;
-  const bool bm_fits       = !getenv("PRS_BF_GLOBAL_STATE") && off + bm_bytes + 4096u <= 160u * 1024u;
-  const bool fused_regime  = !(batch->batch * 2 <= cus && batch->moving_stride >= 256);  // (else: few pairs, each spread over several workgroups)
-  const bool matrix_forced = ctx->bf_mfma == PRS_BF_DENSE_MATRIX, matrix_when_full = ctx->bf_mfma == PRS_BF_DENSE_MATRIX_WHEN_FULL;
+  const uint64_t bm_bytes  = (uint64_t) (batch.fixed_stride + batch.moving_stride) * (uint64_t) a.nw * 4u;
+  const bool bm_fits       = !env.bf_global_state && off + bm_bytes + 4096u <= 160u * 1024u;
+  const bool fused_regime  = !(batch.batch * 2 <= cus && batch.moving_stride >= 256);  // (else: few pairs, each spread over several workgroups)
+  const bool matrix_forced = env.bf_mfma == PRS_BF_DENSE_MATRIX, matrix_when_full = env.bf_mfma == PRS_BF_DENSE_MATRIX_WHEN_FULL;
   // the fused shape with its dense phase on the matrix cores (bruteforce_kernel<1, kBfFused, true>): the registration state AND the
   // phase's scratch must fit the LDS
   // (by default from 32 cloud pairs on: one round of fused workgroups -- 0.14 ms for <= 256 real pairs of ~750 points -- beats the
   //  popcount kernels' split shape from ~27 pairs of that size on, earlier for larger clouds: 128 pairs 0.27 ms, 136 pairs 0.14 ms
   //  when the switch sat at half the CUs)
-  const bool fused_matrix = ((matrix_forced && fused_regime) || (matrix_when_full && batch->batch >= 32 && batch->fixed_stride >= 256 && batch->moving_stride >= 64)) &&
+  const bool fused_matrix = ((matrix_forced && fused_regime) || (matrix_when_full && batch.batch >= 32 && batch.fixed_stride >= 256 && batch.moving_stride >= 64)) &&
                             bm_fits && ((off + bm_bytes + 255u) & ~(uint64_t) 255u) + kMxBytes <= 160u * 1024u;
   // (the split matrix-core kernel, bruteforce_dense_mfma_kernel + the registration launch: only when forced and the fused shape is
   //  not taken -- it is the fastest on uniform random rows and the slowest on real ones, see the header)
@@ -1154,29 +1161,21 @@ int bruteforce_batch_launch(prs_context* ctx, const prs_bruteforce_params* param
   const uint32_t lds_limit_dual = 80u * 1024u - 512u;
   // (for more cloud pairs than CUs: 1024 real pairs 0.54 -> 0.47 ms, 384 pairs 0.27 -> 0.24; with one pair per CU the half-sized
   //  workgroup only takes longer, 128 real pairs 0.14 -> 0.20 ms.  PRS_BF_TWO_WORKGROUPS=1 / 0 forces it where it fits / never: tests, A-B)
-  const char* two_wg = getenv("PRS_BF_TWO_WORKGROUPS");
-  const bool dual = fused_matrix && (two_wg ? two_wg[0] == '1' : batch->batch > cus) &&
+  const bool dual = fused_matrix && (env.bf_two_workgroups >= 0 ? env.bf_two_workgroups == 1 : batch.batch > cus) &&
                     ((off + bm_bytes + 255u) & ~(uint64_t) 255u) + kMxBytesDual <= lds_limit_dual;
-  const int grid = mfma ? batch->batch : (dual ? (batch->batch < 2 * cus ? batch->batch : 2 * cus) : (batch->batch < cus ? batch->batch : cus));
+  const int grid = mfma ? batch.batch : (dual ? (batch.batch < 2 * cus ? batch.batch : 2 * cus) : (batch.batch < cus ? batch.batch : cus));
   // few pairs: spread the dense phase of each pair over several workgroups (slices of >= 32 moving rows: one drain block)
   a.chunks = 1;
   if (mfma) {
     a.chunks = 2;  // (any value > 1: per-pair scratch rows + global accumulators, as in the split popcount shape)
-  } else if (!fused_matrix && batch->batch * 2 <= cus && batch->moving_stride >= 256) {
-    int c = cus / batch->batch;
-    const int most = batch->moving_stride / 32;
+  } else if (!fused_matrix && batch.batch * 2 <= cus && batch.moving_stride >= 256) {
+    int c = cus / batch.batch;
+    const int most = batch.moving_stride / 32;
     a.chunks = c < most ? c : most;
   }
-  const size_t b_cand = (size_t) grid * a.cap * sizeof(uint2);
-  const size_t b_bm   = (size_t) grid * (size_t) (batch->fixed_stride + batch->moving_stride) * a.nw * sizeof(uint32_t);
-  const size_t b_acc  = a.chunks > 1 ? (size_t) batch->batch * (size_t) (batch->fixed_stride + batch->moving_stride + kBfLevels + 8) * sizeof(uint32_t) : 0;
-  a.cand     = static_cast<uint2*>(ctx_arena(ctx, ARENA_WORK_0, b_cand));
-  a.by_level = static_cast<uint2*>(ctx_arena(ctx, ARENA_WORK_1, b_cand));
-  a.bitmaps  = static_cast<uint32_t*>(ctx_arena(ctx, ARENA_WORK_2, b_bm + b_acc));
-  a.g_acc    = a.bitmaps ? a.bitmaps + b_bm / sizeof(uint32_t) : nullptr;
-  if (!a.cand || !a.by_level || !a.bitmaps) {
-    return ctx_fail(ctx, PRS_ERR_HIP, "prs_bruteforce_match: scratch allocation failed");
-  }
+  p.b_cand = (size_t) grid * a.cap * sizeof(uint2);
+  p.b_bm   = (size_t) grid * (size_t) (batch.fixed_stride + batch.moving_stride) * a.nw * sizeof(uint32_t);
+  p.b_acc  = a.chunks > 1 ? (size_t) batch.batch * (size_t) (batch.fixed_stride + batch.moving_stride + kBfLevels + 8) * sizeof(uint32_t) : 0;
   // one workgroup per CU (the grid never exceeds the CUs): what the arrays above leave of the 160 KiB holds the distance bitmaps, then
   // the level lists of as many candidates as fit (pairs with more keep the 8-byte lists in global memory); the scratch of the
   // matrix-core dense phase is dead when the lists are written and lies under them
@@ -1195,49 +1194,65 @@ int bruteforce_batch_launch(prs_context* ctx, const prs_bruteforce_params* param
     const uint32_t lists = 4u * (uint32_t) a.lvl_cap, mx = dual ? kMxBytesDual : kMxBytes;
     off += fused_matrix && mx > lists ? mx : lists;
   }
-  const int kpt = (batch->fixed_stride + kBfThreads - 1) / kBfThreads;
+  p.bm_fits = bm_fits, p.fused_matrix = fused_matrix, p.dual = dual, p.mfma = mfma, p.grid = grid, p.lds = off;
+  const int kpt    = (batch.fixed_stride + kBfThreads - 1) / kBfThreads;
+  const int kpt_of = kpt <= 1 ? 1 : (kpt <= 2 ? 2 : (kpt <= 4 ? 4 : 8));
+  auto popcount = [&](int mode) { return find_variant(kBfVariants, {kpt_of, mode, 0, kBfThreads}); };
+  if (a.chunks > 1) {  // split shape: the dense phase of every slice, then one registration workgroup per pair
+    if (mfma) {
+      p.add(find_variant(kBfVariants, {-1, 0, 0, 0, 0, 0}), (batch.fixed_stride + kBfmRowsWg - 1) / kBfmRowsWg, batch.batch, kBfmThreads, 0);
+    } else {
+      p.add(popcount(kBfDense), a.chunks, batch.batch, kBfThreads, off);
+    }
+    p.add(popcount(kBfRegister), batch.batch, 1, kBfThreads, off);
+  } else if (dual) {
+    p.add(find_variant(kBfVariants, {1, kBfFused, 1, 512}), grid, 1, 512, off);
+  } else if (fused_matrix) {
+    p.add(find_variant(kBfVariants, {1, kBfFused, 1, kBfThreads}), grid, 1, kBfThreads, off);
+  } else {
+    p.add(popcount(kBfFused), grid, 1, kBfThreads, off);
+  }
+  return p;
+}
+
+int bruteforce_batch_launch(prs_context* ctx, const prs_bruteforce_params* params, const prs_bruteforce_batch* batch) {
+  if (!params || !batch || !batch->fixed_desc || !batch->n_fixed) {
+    return ctx_fail(ctx, PRS_ERR_NULL, "prs_bruteforce_match: fixed not set");  // bruteforce_impl.cpp:204-206
+  }
+  if (!batch->moving_desc || !batch->n_moving) {
+    return ctx_fail(ctx, PRS_ERR_NULL, "prs_bruteforce_match: moving not set");  // :207-210
+  }
+  if (!batch->matches || !batch->n_matches || !batch->status) {
+    return ctx_fail(ctx, PRS_ERR_NULL, "prs_bruteforce_match: correspondences not set");  // :211-214
+  }
+  const BfPlan plan = bruteforce_plan(*params, *batch, dispatch_env(ctx));
+  if (plan.status != PRS_OK) {
+    return ctx_fail(ctx, plan.status, plan.message);
+  }
+  if (plan.n_launches == 0) {
+    return PRS_OK;
+  }
+  BfArgs a    = plan.a;
+  a.b         = *batch;
+  a.max_ratio = params->maximum_distance_ratio_to_second_best;
+  a.cand      = static_cast<uint2*>(ctx_arena(ctx, ARENA_WORK_0, plan.b_cand));
+  a.by_level  = static_cast<uint2*>(ctx_arena(ctx, ARENA_WORK_1, plan.b_cand));
+  a.bitmaps   = static_cast<uint32_t*>(ctx_arena(ctx, ARENA_WORK_2, plan.b_bm + plan.b_acc));
+  a.g_acc     = a.bitmaps ? a.bitmaps + plan.b_bm / sizeof(uint32_t) : nullptr;
+  if (!a.cand || !a.by_level || !a.bitmaps) {
+    return ctx_fail(ctx, PRS_ERR_HIP, "prs_bruteforce_match: scratch allocation failed");
+  }
   hipStream_t stream = ctx_stream(ctx);
   hipError_t e       = hipSuccess;
-  auto launch = [&](auto kernel, dim3 g, const int threads = kBfThreads) {
-    if (off > 64u * 1024u) {
-      e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int) off);
-    }
-    if (e == hipSuccess) {
-      hipLaunchKernelGGL(kernel, g, dim3(threads), off, stream, a);
-      e = hipGetLastError();
-    }
-  };
-  auto launch_mode = [&](auto mode, dim3 g) {
-    constexpr int M = decltype(mode)::value;
-    if (kpt <= 1) {
-      launch(bruteforce_kernel<1, M>, g);
-    } else if (kpt <= 2) {
-      launch(bruteforce_kernel<2, M>, g);
-    } else if (kpt <= 4) {
-      launch(bruteforce_kernel<4, M>, g);
-    } else {
-      launch(bruteforce_kernel<8, M>, g);
-    }
-  };
   if (a.chunks > 1) {
-    const size_t acc_bytes = (size_t) batch->batch * (size_t) (batch->fixed_stride + batch->moving_stride + kBfLevels + 8) * sizeof(uint32_t);
-    e = hipMemsetAsync(a.bitmaps, 0, b_bm + acc_bytes, stream);  // (the bitmaps and the accumulators behind them: one launch)
-    if (e == hipSuccess && mfma) {
-      hipLaunchKernelGGL(bruteforce_dense_mfma_kernel, dim3((batch->fixed_stride + kBfmRowsWg - 1) / kBfmRowsWg, batch->batch), dim3(kBfmThreads), 0, stream, a);
-      e = hipGetLastError();
-    } else if (e == hipSuccess) {
-      launch_mode(std::integral_constant<int, kBfDense>{}, dim3(a.chunks, batch->batch));
-    }
+    e = hipMemsetAsync(a.bitmaps, 0, plan.b_bm + plan.b_acc, stream);  // (the bitmaps and the accumulators behind them: one launch)
+  }
+  for (int i = 0; i < plan.n_launches && e == hipSuccess; ++i) {
+    const Plan::Launch& l = plan.launch[i];
+    e = allow_lds(kBfVariants[l.kernel].fn, l.lds);
     if (e == hipSuccess) {
-      launch_mode(std::integral_constant<int, kBfRegister>{}, dim3(batch->batch));
-    }
-  } else {
-    if (dual) {
-      launch(bruteforce_kernel<1, kBfFused, true, 512>, dim3(grid), 512);
-    } else if (fused_matrix) {
-      launch(bruteforce_kernel<1, kBfFused, true>, dim3(grid));
-    } else {
-      launch_mode(std::integral_constant<int, kBfFused>{}, dim3(grid));
+      hipLaunchKernelGGL(kBfVariants[l.kernel].fn, dim3(l.grid_x, l.grid_y), dim3(l.block), l.lds, stream, a);
+      e = hipGetLastError();
     }
   }
   if (e != hipSuccess) {
@@ -1246,4 +1261,26 @@ int bruteforce_batch_launch(prs_context* ctx, const prs_bruteforce_params* param
   return PRS_OK;
 }
 
+const char* bruteforce_kernel_name(int index) {
+  return index >= 0 && index < (int) (sizeof(kBfVariants) / sizeof(kBfVariants[0])) ? kBfVariants[index].name : nullptr;
+}
+
 }  // namespace prs
+
+extern "C" int prs_bruteforce_plan(const prs_bruteforce_params* params, const prs_bruteforce_batch* batch, const prs_dispatch_env* env,
+                                   prs_dispatch_plan* out) {
+  if (!params || !batch || !env || !out) {
+    return PRS_ERR_NULL;
+  }
+  const prs::BfPlan p = prs::bruteforce_plan(*params, *batch, *env);
+  prs::export_plan(p, prs::kBfVariants, out);
+  const prs::BfArgs& a = p.a;
+  int32_t* f = out->fact;
+  f[PRS_PLAN_BF_LIM] = a.lim, f[PRS_PLAN_BF_NW] = a.nw, f[PRS_PLAN_BF_CAP] = a.cap, f[PRS_PLAN_BF_GRID] = p.grid, f[PRS_PLAN_BF_CHUNKS] = a.chunks;
+  f[PRS_PLAN_BF_BM_FITS] = p.bm_fits, f[PRS_PLAN_BF_LVL_CAP] = a.lvl_cap, f[PRS_PLAN_BF_FUSED_MATRIX] = p.fused_matrix, f[PRS_PLAN_BF_DUAL] = p.dual;
+  f[PRS_PLAN_BF_MFMA] = p.mfma, f[PRS_PLAN_BF_LDS] = (int32_t) p.lds, f[PRS_PLAN_BF_OFF_CNT_F] = (int32_t) a.off_cnt_f;
+  f[PRS_PLAN_BF_OFF_CNT_M] = (int32_t) a.off_cnt_m, f[PRS_PLAN_BF_OFF_REG_F] = (int32_t) a.off_reg_f, f[PRS_PLAN_BF_OFF_REG_M] = (int32_t) a.off_reg_m;
+  f[PRS_PLAN_BF_OFF_ACC] = (int32_t) a.off_acc, f[PRS_PLAN_BF_OFF_HIST] = (int32_t) a.off_hist, f[PRS_PLAN_BF_OFF_BM] = (int32_t) a.off_bm;
+  f[PRS_PLAN_BF_OFF_LVL] = (int32_t) a.off_lvl, f[PRS_PLAN_BF_OFF_MX] = (int32_t) a.off_mx;
+  return PRS_OK;
+}

@@ -1407,6 +1407,115 @@ static inline uint32_t mg_align16(uint32_t v) {
   return (v + 15u) & ~15u;
 }
 
+// merge_kernel<EST, DIM, PHASE> and the two smoother kernels
+#define MG(...) PRS_VARIANT("prs::", merge_kernel, MergeArgs, __VA_ARGS__)
+static const Variant<MergeArgs> kMergeVariants[] = {
+    PRS_VARIANT_PLAIN("prs::", smoother_kernel, MergeArgs, -1), PRS_VARIANT_PLAIN("prs::", smoother_tail_kernel, MergeArgs, -2),
+    MG(0, 4, 0), MG(2, 4, 0), MG(2, 4, 1), MG(2, 4, 2), MG(1, 4, 0), MG(1, 3, 0), MG(1, 2, 0),
+};
+#undef MG
+static_assert(PRS_EST_WEIGHTED_MEAN == 0 && PRS_EST_EKF == 1 && PRS_EST_SMOOTHER == 2, "kMergeVariants spells these as literals");
+
+const char* merge_kernel_name(int index) {
+  return index >= 0 && index < (int) (sizeof(kMergeVariants) / sizeof(kMergeVariants[0])) ? kMergeVariants[index].name : nullptr;
+}
+
+struct MergePlan : Plan {
+  MergeArgs a = {};   // bin widths, bin table, LDS carve, tail_capacity
+  bool split = false;  // the pose-based smoother as front | smoother_kernel | smoother_tail_kernel | back
+  size_t work_bytes = 0;  // smoother work list (0: not a smoother)
+};
+
+static MergePlan merge_plan(const prs_merger_params& params, const prs_merge_batch& b, const DispatchEnv& env) {
+  MergePlan p;
+  if (b.batch <= 0) {
+    return p;
+  }
+  const prs_estimator_params& e = params.estimator;
+  if (params.variant < PRS_MERGER_STEREO_TRIANGULATION || params.variant > PRS_MERGER_DEPTH_EKF || e.type < PRS_EST_WEIGHTED_MEAN ||
+      e.type > PRS_EST_SMOOTHER || e.measurement_dim < 2 || e.measurement_dim > 4 || b.capacity <= 0 || b.max_frames <= 0 || b.measurement_stride <= 0) {
+    p.refuse(PRS_ERR_UNSUPPORTED, "prs_merge_batch_run: unknown merger / estimator or empty strides");
+    return p;
+  }
+  // Which estimator a merger may own (mapping/instances.cpp:29-40 registers more types than any merger of mapping/mergers drives):
+  //   weighted mean / pose-based smoother: the landmark's position in the sensor comes from the MERGER, and only
+  //     MergerRigidStereoTriangulation computes one (merger_projective_rigid_stereo_triangulation_impl.cpp:15-35): the 4D3D forms.
+  //     The 2D3D / 3D3D forms have no caller in the reference that sets it: refused, not guessed;
+  //   stereo / depth filter: measurement layout and merger must agree;
+  //   mono filter (ProjectivePointEKF3D, 2-D measurements): no merger of the reference adds points from (u, v) alone: updates only.
+  if ((e.type == PRS_EST_WEIGHTED_MEAN || e.type == PRS_EST_SMOOTHER) && (params.variant != PRS_MERGER_STEREO_TRIANGULATION || e.measurement_dim != 4)) {
+    p.refuse(PRS_ERR_UNSUPPORTED,
+             "prs_merge_batch_run: the weighted-mean / smoother estimators are served in their 4D3D form under PRS_MERGER_STEREO_TRIANGULATION only "
+             "(no merger of the reference provides landmark_in_sensor for 2-D / 3-D measurements)");
+    return p;
+  }
+  if (e.type == PRS_EST_EKF && ((e.measurement_dim == 4 && params.variant == PRS_MERGER_DEPTH_EKF) ||
+                                (e.measurement_dim == 3 && params.variant != PRS_MERGER_DEPTH_EKF))) {
+    p.refuse(PRS_ERR_UNSUPPORTED, "prs_merge_batch_run: 4-D measurements need a stereo merger, 3-D measurements PRS_MERGER_DEPTH_EKF");
+    return p;
+  }
+  if (e.type == PRS_EST_EKF && e.measurement_dim == 2 && params.target_number_of_merges != 0) {
+    p.refuse(PRS_ERR_UNSUPPORTED,
+             "prs_merge_batch_run: the mono filter updates landmarks only (target_number_of_merges must be 0: a point cannot be added from (u, v))");
+    return p;
+  }
+  if (e.type == PRS_EST_SMOOTHER && (!b.meas || b.max_measurements <= 0 || e.measurement_dim < 3)) {
+    p.refuse(PRS_ERR_NULL, "prs_merge_batch_run: the pose-based smoother needs the measurement history");
+    return p;
+  }
+  if (params.number_of_row_bins == 0 || params.number_of_col_bins == 0) {
+    p.refuse(PRS_ERR_UNSUPPORTED, "prs_merge_batch_run: bin counts must be positive");
+    return p;
+  }
+  MergeArgs& a = p.a;
+  a.row_w = (float) params.canvas_rows / (float) params.number_of_row_bins;  // merger_projective_impl.cpp:30-33
+  a.col_w = (float) params.canvas_cols / (float) params.number_of_col_bins;
+  if (a.row_w < 1.0f || a.col_w < 1.0f) {  // :35-47 throws
+    p.refuse(PRS_ERR_UNSUPPORTED, "prs_merge_batch_run: bin width must be at least 1 pixel");
+    return p;
+  }
+  a.nbr = (int) params.number_of_row_bins + 2;
+  a.nbc = (int) params.number_of_col_bins + 2;
+  const uint32_t nbins = (uint32_t) a.nbr * (uint32_t) a.nbc;
+  uint32_t off = 0;
+  a.off_owner = off; off = mg_align16(off + nbins * 4);
+  a.off_first = off; off = mg_align16(off + nbins * 4);
+  a.off_best  = off; off = mg_align16(off + nbins * 8);
+  a.off_seen  = off; off = mg_align16(off + ((uint32_t) b.capacity + 31) / 32 * 4);
+  a.off_sh    = off; off = mg_align16(off + (uint32_t) sizeof(MergeShared));
+  a.off_wave  = off; off = mg_align16(off + kMergeWaves * 4);
+  a.off_pose_cache = off; off = mg_align16(off + (e.type == PRS_EST_SMOOTHER ? (uint32_t) b.max_frames * 21 * 4 : 0));
+  if (off > 160u * 1024u) {
+    p.refuse(PRS_ERR_UNSUPPORTED, "prs_merge_batch_run: bin table / scene do not fit the 160 KiB LDS");
+    return p;
+  }
+  auto merge = [&](int est, int dim, int phase) { p.add(find_variant(kMergeVariants, {est, dim, phase}), b.batch, 1, kMergeThreads, off); };
+  if (e.type == PRS_EST_SMOOTHER) {
+    // (no correspondences at all: nothing to iterate, but the pointer must be valid)
+    p.work_bytes = !b.corr || b.corr_stride <= 0 ? 64 : (size_t) b.batch * 2 * (size_t) b.corr_stride * sizeof(SmootherItem);
+  }
+  if (e.type != PRS_EST_SMOOTHER) {
+    merge(e.type, e.type == PRS_EST_WEIGHTED_MEAN ? 4 : e.measurement_dim, 0);
+  } else if (env.merge_fused || env.stamps) {
+    merge(PRS_EST_SMOOTHER, 4, 0);
+  } else {
+    // smoother_kernel's own request (pose cache + ring): settled before anything is launched, so that a refusal leaves the maps untouched
+    const size_t lds_s = ((sizeof(MergeShared) + 15) & ~(size_t) 15) + (((size_t) b.max_frames * 21 + 3) & ~(size_t) 3) * sizeof(float) +
+                         (size_t) kSmootherRing * 5 * 64 * sizeof(float);
+    if (lds_s > 160u * 1024u) {
+      p.refuse(PRS_ERR_UNSUPPORTED, "prs_merge_batch_run: pose table does not fit the 160 KiB LDS");
+      return p;
+    }
+    p.split         = true;
+    a.tail_capacity = b.batch * kTailPerFrame;  // tail list: [batch * kTailPerFrame] items + the counter in front of them
+    merge(PRS_EST_SMOOTHER, 4, 1);
+    p.add(find_variant(kMergeVariants, {-1, 0, 0, 0, 0, 0}), b.batch, 1, kSmootherThreads, lds_s);
+    p.add(find_variant(kMergeVariants, {-2, 0, 0, 0, 0, 0}), b.batch < 2048 ? b.batch : 2048, 1, kSmootherThreads, 0);  // grid-stride over however many stragglers there are
+    merge(PRS_EST_SMOOTHER, 4, 2);
+  }
+  return p;
+}
+
 int merge_batch_launch(prs_context* ctx, const prs_merger_params* params, const prs_merge_batch* batch) {
   if (!params || !batch) {
     return ctx_fail(ctx, PRS_ERR_NULL, "prs_merge_batch_run: parameters not set");
@@ -1418,111 +1527,33 @@ int merge_batch_launch(prs_context* ctx, const prs_merger_params* params, const 
   if (!b.measurement || !b.measurement_desc || !b.n_measured || !b.measurement_in_world || !b.measurement_in_scene || !b.frame || !b.result) {
     return ctx_fail(ctx, PRS_ERR_NULL, "prs_merge_batch_run: measurement not set");
   }
-  if (b.batch <= 0) {
+  const MergePlan plan = merge_plan(*params, b, dispatch_env(ctx));
+  if (plan.status != PRS_OK) {
+    return ctx_fail(ctx, plan.status, plan.message);
+  }
+  if (plan.n_launches == 0) {
     return PRS_OK;
   }
-  const prs_estimator_params& e = params->estimator;
-  if (params->variant < PRS_MERGER_STEREO_TRIANGULATION || params->variant > PRS_MERGER_DEPTH_EKF || e.type < PRS_EST_WEIGHTED_MEAN ||
-      e.type > PRS_EST_SMOOTHER || e.measurement_dim < 2 || e.measurement_dim > 4 || b.capacity <= 0 || b.max_frames <= 0 || b.measurement_stride <= 0) {
-    return ctx_fail(ctx, PRS_ERR_UNSUPPORTED, "prs_merge_batch_run: unknown merger / estimator or empty strides");
-  }
-  // Which estimator a merger may own (mapping/instances.cpp:29-40 registers more types than any merger of mapping/mergers drives):
-  //   weighted mean / pose-based smoother: the landmark's position in the sensor comes from the MERGER, and only
-  //     MergerRigidStereoTriangulation computes one (merger_projective_rigid_stereo_triangulation_impl.cpp:15-35): the 4D3D forms.
-  //     The 2D3D / 3D3D forms have no caller in the reference that sets it: refused, not guessed;
-  //   stereo / depth filter: measurement layout and merger must agree;
-  //   mono filter (ProjectivePointEKF3D, 2-D measurements): no merger of the reference adds points from (u, v) alone: updates only.
-  if ((e.type == PRS_EST_WEIGHTED_MEAN || e.type == PRS_EST_SMOOTHER) && (params->variant != PRS_MERGER_STEREO_TRIANGULATION || e.measurement_dim != 4)) {
-    return ctx_fail(ctx, PRS_ERR_UNSUPPORTED,
-                    "prs_merge_batch_run: the weighted-mean / smoother estimators are served in their 4D3D form under PRS_MERGER_STEREO_TRIANGULATION only "
-                    "(no merger of the reference provides landmark_in_sensor for 2-D / 3-D measurements)");
-  }
-  if (e.type == PRS_EST_EKF && ((e.measurement_dim == 4 && params->variant == PRS_MERGER_DEPTH_EKF) ||
-                                (e.measurement_dim == 3 && params->variant != PRS_MERGER_DEPTH_EKF))) {
-    return ctx_fail(ctx, PRS_ERR_UNSUPPORTED, "prs_merge_batch_run: 4-D measurements need a stereo merger, 3-D measurements PRS_MERGER_DEPTH_EKF");
-  }
-  if (e.type == PRS_EST_EKF && e.measurement_dim == 2 && params->target_number_of_merges != 0) {
-    return ctx_fail(ctx, PRS_ERR_UNSUPPORTED,
-                    "prs_merge_batch_run: the mono filter updates landmarks only (target_number_of_merges must be 0: a point cannot be added from (u, v))");
-  }
-  if (e.type == PRS_EST_SMOOTHER && (!b.meas || b.max_measurements <= 0 || e.measurement_dim < 3)) {
-    return ctx_fail(ctx, PRS_ERR_NULL, "prs_merge_batch_run: the pose-based smoother needs the measurement history");
-  }
-  if (params->number_of_row_bins == 0 || params->number_of_col_bins == 0) {
-    return ctx_fail(ctx, PRS_ERR_UNSUPPORTED, "prs_merge_batch_run: bin counts must be positive");
-  }
-  MergeArgs a;
-  a.p     = *params;
-  a.b     = b;
-  a.row_w = (float) params->canvas_rows / (float) params->number_of_row_bins;  // merger_projective_impl.cpp:30-33
-  a.col_w = (float) params->canvas_cols / (float) params->number_of_col_bins;
-  if (a.row_w < 1.0f || a.col_w < 1.0f) {  // :35-47 throws
-    return ctx_fail(ctx, PRS_ERR_UNSUPPORTED, "prs_merge_batch_run: bin width must be at least 1 pixel");
-  }
-  a.nbr = (int) params->number_of_row_bins + 2;
-  a.nbc = (int) params->number_of_col_bins + 2;
-  const uint32_t nbins = (uint32_t) a.nbr * (uint32_t) a.nbc;
-  uint32_t off = 0;
-  a.off_owner = off; off = mg_align16(off + nbins * 4);
-  a.off_first = off; off = mg_align16(off + nbins * 4);
-  a.off_best  = off; off = mg_align16(off + nbins * 8);
-  a.off_seen  = off; off = mg_align16(off + ((uint32_t) b.capacity + 31) / 32 * 4);
-  a.off_sh    = off; off = mg_align16(off + (uint32_t) sizeof(MergeShared));
-  a.off_wave  = off; off = mg_align16(off + kMergeWaves * 4);
-  a.off_pose_cache = off; off = mg_align16(off + (e.type == PRS_EST_SMOOTHER ? (uint32_t) b.max_frames * 21 * 4 : 0));
-  if (off > 160u * 1024u) {
-    return ctx_fail(ctx, PRS_ERR_UNSUPPORTED, "prs_merge_batch_run: bin table / scene do not fit the 160 KiB LDS");
-  }
-  a.stamps = ctx_stamps(ctx, (size_t) b.batch * 16 * sizeof(unsigned long long));
-  a.work   = nullptr;
-  if (e.type == PRS_EST_SMOOTHER) {
-    if (!b.corr || b.corr_stride <= 0) {
-      // no correspondences at all: nothing to iterate, but the pointer must be valid
-      a.work = ctx_arena(ctx, ARENA_WORK_0, 64);
-    } else {
-      a.work = ctx_arena(ctx, ARENA_WORK_0, (size_t) b.batch * 2 * (size_t) b.corr_stride * sizeof(SmootherItem));
-    }
+  MergeArgs a = plan.a;
+  a.p         = *params;
+  a.b         = b;
+  a.stamps    = ctx_stamps(ctx, (size_t) b.batch * 16 * sizeof(unsigned long long));
+  if (plan.work_bytes) {
+    a.work = ctx_arena(ctx, ARENA_WORK_0, plan.work_bytes);
     if (!a.work) {
       return ctx_fail(ctx, PRS_ERR_HIP, "prs_merge_batch_run: smoother work list allocation failed");
     }
   }
-  hipError_t e2 = hipSuccess;
-  auto launch = [&](auto kernel) {
-    if (off > 64u * 1024u) {
-      e2 = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int) off);
-    }
-    if (e2 == hipSuccess) {
-      hipLaunchKernelGGL(kernel, dim3(b.batch), dim3(kMergeThreads), off, ctx_stream(ctx), a);
-      e2 = hipGetLastError();
-    }
-  };
-  a.carry         = nullptr;
-  a.tail          = nullptr;
-  a.tail_count    = nullptr;
-  a.tail_capacity = 0;
-  if (e.type == PRS_EST_WEIGHTED_MEAN) {
-    launch(merge_kernel<PRS_EST_WEIGHTED_MEAN, 4, 0>);
-  } else if (e.type == PRS_EST_SMOOTHER && (ctx->merge_fused || a.stamps)) {
-    launch(merge_kernel<PRS_EST_SMOOTHER, 4, 0>);
-  } else if (e.type == PRS_EST_SMOOTHER) {
-    // smoother_kernel's own request (pose cache + ring): settled before anything is launched, so that a refusal leaves the maps untouched
-    const size_t lds_s = ((sizeof(MergeShared) + 15) & ~(size_t) 15) + (((size_t) b.max_frames * 21 + 3) & ~(size_t) 3) * sizeof(float) +
-                         (size_t) kSmootherRing * 5 * 64 * sizeof(float);
-    if (lds_s > 160u * 1024u) {
-      return ctx_fail(ctx, PRS_ERR_UNSUPPORTED, "prs_merge_batch_run: pose table does not fit the 160 KiB LDS");
-    }
-    if (lds_s > 64u * 1024u) {  // (the pose cache of a long local map)
-      e2 = hipFuncSetAttribute(reinterpret_cast<const void*>(smoother_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds_s);
-      if (e2 != hipSuccess) {
-        return ctx_fail_hip(ctx, e2, "prs_merge_batch_run: smoother kernel LDS request");
-      }
+  hipError_t e = hipSuccess;
+  if (plan.split) {
+    e = allow_lds(kMergeVariants[plan.launch[1].kernel].fn, plan.launch[1].lds);  // (the pose cache of a long local map)
+    if (e != hipSuccess) {
+      return ctx_fail_hip(ctx, e, "prs_merge_batch_run: smoother kernel LDS request");
     }
     a.carry = static_cast<MergeCarry*>(ctx_arena(ctx, ARENA_WORK_1, (size_t) b.batch * sizeof(MergeCarry)));
     if (!a.carry) {
       return ctx_fail(ctx, PRS_ERR_HIP, "prs_merge_batch_run: carry allocation failed");
     }
-    // tail list: [batch * kTailPerFrame] items + the counter in front of them
-    a.tail_capacity    = b.batch * kTailPerFrame;
     unsigned char* tmem = static_cast<unsigned char*>(ctx_arena(ctx, ARENA_WORK_2, 256 + (size_t) a.tail_capacity * sizeof(TailItem)));
     if (!tmem) {
       return ctx_fail(ctx, PRS_ERR_HIP, "prs_merge_batch_run: tail list allocation failed");
@@ -1530,23 +1561,17 @@ int merge_batch_launch(prs_context* ctx, const prs_merger_params* params, const 
     a.tail_count = reinterpret_cast<int*>(tmem);
     a.tail       = reinterpret_cast<TailItem*>(tmem + 256);
     (void) hipMemsetAsync(a.tail_count, 0, sizeof(int), ctx_stream(ctx));
-    launch(merge_kernel<PRS_EST_SMOOTHER, 4, 1>);
-    if (e2 == hipSuccess) {
-      hipLaunchKernelGGL(smoother_kernel, dim3(b.batch), dim3(kSmootherThreads), lds_s, ctx_stream(ctx), a);
-      const int tail_waves = b.batch < 2048 ? b.batch : 2048;  // grid-stride over however many stragglers there are
-      hipLaunchKernelGGL(smoother_tail_kernel, dim3(tail_waves), dim3(kSmootherThreads), 0, ctx_stream(ctx), a);
-      e2 = hipGetLastError();
-    }
-    launch(merge_kernel<PRS_EST_SMOOTHER, 4, 2>);
-  } else if (e.measurement_dim == 4) {
-    launch(merge_kernel<PRS_EST_EKF, 4, 0>);
-  } else if (e.measurement_dim == 3) {
-    launch(merge_kernel<PRS_EST_EKF, 3, 0>);
-  } else {
-    launch(merge_kernel<PRS_EST_EKF, 2, 0>);
   }
-  if (e2 != hipSuccess) {
-    return ctx_fail_hip(ctx, e2, "prs_merge_batch_run launch");
+  for (int i = 0; i < plan.n_launches && e == hipSuccess; ++i) {
+    const Plan::Launch& l = plan.launch[i];
+    e = allow_lds(kMergeVariants[l.kernel].fn, l.lds);
+    if (e == hipSuccess) {
+      hipLaunchKernelGGL(kMergeVariants[l.kernel].fn, dim3(l.grid_x), dim3(l.block), l.lds, ctx_stream(ctx), a);
+      e = hipGetLastError();
+    }
+  }
+  if (e != hipSuccess) {
+    return ctx_fail_hip(ctx, e, "prs_merge_batch_run launch");
   }
   if (a.stamps) {
     ctx_report_stamps(ctx, b.batch, 7, "merge: setup + pose cache | correspondences (gate, bins) | update / smoother start | smoother rounds | addition bins | additions");
@@ -1626,3 +1651,18 @@ int pose_compose_launch(prs_context* ctx, int batch, const float* prediction, co
 }
 
 }  // namespace prs
+
+extern "C" int prs_merge_plan(const prs_merger_params* params, const prs_merge_batch* batch, const prs_dispatch_env* env, prs_dispatch_plan* out) {
+  if (!params || !batch || !env || !out) {
+    return PRS_ERR_NULL;
+  }
+  const prs::MergePlan p = prs::merge_plan(*params, *batch, *env);
+  prs::export_plan(p, prs::kMergeVariants, out);
+  const prs::MergeArgs& a = p.a;
+  int32_t* f = out->fact;
+  f[PRS_PLAN_MERGE_NBR] = a.nbr, f[PRS_PLAN_MERGE_NBC] = a.nbc, f[PRS_PLAN_MERGE_SPLIT] = p.split, f[PRS_PLAN_MERGE_OFF_OWNER] = (int32_t) a.off_owner;
+  f[PRS_PLAN_MERGE_OFF_FIRST] = (int32_t) a.off_first, f[PRS_PLAN_MERGE_OFF_BEST] = (int32_t) a.off_best, f[PRS_PLAN_MERGE_OFF_SEEN] = (int32_t) a.off_seen;
+  f[PRS_PLAN_MERGE_OFF_SH] = (int32_t) a.off_sh, f[PRS_PLAN_MERGE_OFF_WAVE] = (int32_t) a.off_wave, f[PRS_PLAN_MERGE_OFF_POSE_CACHE] = (int32_t) a.off_pose_cache;
+  f[PRS_PLAN_MERGE_TAIL_CAPACITY] = a.tail_capacity;
+  return PRS_OK;
+}

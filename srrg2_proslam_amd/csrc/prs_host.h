@@ -30,6 +30,7 @@ enum Arena {
 
 struct prs_context {
   int device            = 0;
+  int cus               = 256;      // compute units of `device`, read once at prs_context_create (256 when the query fails)
   hipStream_t stream    = nullptr;  // stream work is enqueued on
   hipStream_t own       = nullptr;  // stream created (and destroyed) by the context
   std::string last_error;
@@ -69,15 +70,6 @@ int ctx_fail(prs_context* ctx, int status, const char* what);
 int ctx_fail_hip(prs_context* ctx, hipError_t e, const char* what);
 inline hipStream_t ctx_stream(prs_context* ctx) {
   return ctx->stream;
-}
-inline bool ctx_fused_align(const prs_context* ctx) {
-  return ctx->fused_align;
-}
-inline bool ctx_matcher_v3(const prs_context* ctx) {
-  return ctx->matcher_v3;
-}
-inline bool ctx_force_unstaged(const prs_context* ctx) {
-  return ctx->force_unstaged;
 }
 // a step that returns a PRS status: anything but PRS_OK leaves the enclosing function with it (the step has set the message)
 #define PRS_TRY(step)         \
@@ -174,11 +166,108 @@ unsigned long long* ctx_stamps(prs_context* ctx, size_t bytes);
 // synchronises and prints mean per-phase cycle counts (n_stamps consecutive stamps per block)
 void ctx_report_stamps(prs_context* ctx, int blocks, int n_stamps, const char* legend, bool raw = false, size_t first_block = 0);  // raw: the words are per-phase totals, not cumulative stamps
 
+// ---- dispatch: plan, then launch.  The five launchers that choose among kernel instantiations (stereo matcher, v5 matcher, aligner,
+// brute-force matcher, merger) each have a *_plan function next to them: pure host code (no HIP call, no getenv, no context, no
+// batch pointer followed) from the parameter structs, the batch descriptor's strides / counts / which optional pointers are set
+// and a DispatchEnv to a plan -- a refusal, or the launches (kernel = index into the family's variant table, grid, block, dynamic
+// LDS bytes) plus the kernel argument struct with every layout field set.  The launcher validates pointers, takes the plan,
+// allocates what the plan sizes, adds the pointers and launches.  The prs_*_plan entry points show the same plans to tests.
+using DispatchEnv = prs_dispatch_env;  // everything outside the arguments a dispatch depends on
+// the context's knobs and CU count, and the two brute-force switches from the environment as it is now
+DispatchEnv dispatch_env(const prs_context* ctx);
+
+// one kernel instantiation: the function and its name as a kernel trace prints it, both from ONE template-argument list; key = that
+// list as integers, which is how a plan finds the entry (find_variant) once it has worked out the arguments it wants
+template <class Args>
+struct Variant {
+  void (*fn)(Args);
+  const char* name;
+  int key[6];
+};
+#define PRS_VARIANT(scope, kernel, args, ...) \
+  { kernel<__VA_ARGS__>, "void " scope #kernel "<" #__VA_ARGS__ ">(" scope #args ")", { __VA_ARGS__ } }
+#define PRS_VARIANT_PLAIN(scope, kernel, args, id) \
+  { kernel, scope #kernel "(" scope #args ")", { id } }
+template <class Args, size_t N>
+inline int find_variant(const Variant<Args> (&table)[N], const int (&key)[6]) {
+  for (size_t i = 0; i < N; ++i) {
+    bool same = true;
+    for (int k = 0; k < 6; ++k) {
+      same = same && table[i].key[k] == key[k];
+    }
+    if (same) {
+      return (int) i;
+    }
+  }
+  return -1;  // (a plan turns this into a refusal: a missing instantiation is an error, never another kernel)
+}
+
+struct Plan {
+  int status          = PRS_OK;
+  const char* message = nullptr;
+  int n_launches      = 0;  // 0 with PRS_OK: an empty batch
+  struct Launch {
+    int kernel;  // index into the family's variant table
+    unsigned grid_x, grid_y, block;
+    size_t lds;
+  } launch[PRS_PLAN_MAX_LAUNCHES];
+  void refuse(int code, const char* what) {
+    status     = code;
+    message    = what;
+    n_launches = 0;
+  }
+  void add(int kernel, unsigned grid_x, unsigned grid_y, unsigned block, size_t lds) {
+    if (kernel < 0) {
+      refuse(PRS_ERR_UNSUPPORTED, "dispatch: no kernel instantiation for this shape");
+    } else if (status == PRS_OK) {
+      launch[n_launches++] = {kernel, grid_x, grid_y, block, lds};
+    }
+  }
+};
+// status, message and launches of a plan in the ABI's form (facts zeroed: the family's entry point fills them)
+template <class Args, size_t N>
+inline void export_plan(const Plan& p, const Variant<Args> (&table)[N], prs_dispatch_plan* out) {
+  *out            = prs_dispatch_plan{};
+  out->status     = p.status;
+  out->message    = p.message;
+  out->n_launches = p.n_launches;
+  for (int i = 0; i < p.n_launches; ++i) {
+    const Plan::Launch& l = p.launch[i];
+    out->launch[i]        = {table[l.kernel].name, (int32_t) l.grid_x, (int32_t) l.grid_y, (int32_t) l.block, (uint32_t) l.lds};
+  }
+}
+// the index-th name of each family's variant tables, nullptr past the end (prs_dispatch_kernel_name)
+const char* stereo_kernel_name(int index);
+const char* align_kernel_name(int index);
+const char* bruteforce_kernel_name(int index);
+const char* merge_kernel_name(int index);
+// the request a kernel needs before it may be launched with more than 64 KiB of dynamic LDS
+template <class Args>
+inline hipError_t allow_lds(void (*kernel)(Args), size_t lds) {
+  return lds > 64u * 1024u ? hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds)
+                           : hipSuccess;
+}
+
 // exact integer form of `best < max_distance && best / second < max_ratio` (epipolar_impl.cpp:171-173),
 // evaluated on the host with the same IEEE float operations the reference performs:
 // accept iff best < *best_lim && best <= bmax[second] (index 257 = no second candidate)
 void fill_accept_table(const prs_stereo_params* params, int* best_lim, int16_t* bmax258);
-int stereo_match_v5_launch(prs_context* ctx, const prs_stereo_params* params, const prs_stereo_batch* batch);
+// The stereo matcher's two generations live in two translation units; stereo_plan (stereo_match.hip) decides between them in one
+// place and asks the v5 unit for its kernel's layout: `why` says whether the shape is v5's (kV5Taken) or what keeps it out
+enum { kV5Taken = 0, kV5Stride, kV5Knob, kV5Cap, kV5Lds, kV5BestLim };
+constexpr int kStereoV5Variants = 8;
+struct StereoV5Layout {
+  int why    = kV5Taken;
+  int kernel = -1;  // index into the v5 variant table
+  int cap = 0, nwords = 0, pool_cap = 0;
+  uint32_t off_desc_r = 0, off_kp_r = 0, off_sorted_l = 0, off_sorted_r = 0, off_bucket = 0, off_hist = 0, off_rs = 0, off_len = 0, off_rowcnt = 0,
+           off_out = 0, off_bits = 0, off_misc = 0, off_tab = 0, off_pool = 0;
+  uint32_t lds = 0;  // dynamic LDS bytes (the arrays alone when they do not fit)
+};
+StereoV5Layout stereo_v5_layout(const prs_stereo_params& params, int stride, bool epilogue, int best_lim, const DispatchEnv& env);
+const char* stereo_v5_kernel_name(int index);
+int stereo_match_v5_launch(prs_context* ctx, const prs_stereo_params* params, const prs_stereo_batch* batch, const StereoV5Layout& layout,
+                           const Plan::Launch& launch);
 int stereo_match_batch_launch(prs_context* ctx, const prs_stereo_params* params, const prs_stereo_batch* batch);
 int align_batch_launch(prs_context* ctx, const prs_pcf_params* finder, const prs_aligner_params* aligner, const prs_align_batch* batch, int mode, int rounds);
 int align_batch_finish(prs_context* ctx);

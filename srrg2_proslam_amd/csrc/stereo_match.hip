@@ -687,33 +687,18 @@ static inline uint32_t align_up(uint32_t v, uint32_t a) {
   return (v + a - 1) / a * a;
 }
 
-template <int KPT, bool STAGE>
-static hipError_t launch_variant(const StereoArgs& a, size_t lds, hipStream_t stream) {
-  auto kernel = stereo_match_kernel<KPT, STAGE>;
-  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds);
-  if (e != hipSuccess) {
-    return e;
+// (float) d < maximum_descriptor_distance for integer d  <=>  d < the limit
+static int accept_limit(const prs_stereo_params& params) {
+  int lim = 0;
+  while (lim <= 256 && (float) lim < params.maximum_descriptor_distance) {
+    ++lim;
   }
-  int grid = a.b.batch;
-  if (STAGE) {
-    // persistent: one workgroup per CU (the LDS footprint allows no more), frames strided over them
-    int dev = 0, cus = 0;
-    if (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && cus > 0 &&
-        cus < grid) {
-      grid = cus;
-    }
-  }
-  hipLaunchKernelGGL(kernel, dim3(grid), dim3(kStereoThreads), lds, stream, a);
-  return hipGetLastError();
+  return lim;
 }
 
 void fill_accept_table(const prs_stereo_params* params, int* best_lim, int16_t* bmax) {
-  const float max_dist = params->maximum_descriptor_distance, ratio = params->maximum_distance_ratio_to_second_best;
-  int lim = 0;
-  while (lim <= 256 && (float) lim < max_dist) {
-    ++lim;
-  }
-  *best_lim = lim;
+  const float ratio = params->maximum_distance_ratio_to_second_best;
+  *best_lim         = accept_limit(*params);
   for (int s = 0; s <= 257; ++s) {
     const float fs = s == 257 ? 3.402823466e+38f : (float) s;
     int bm         = -1;
@@ -728,45 +713,64 @@ void fill_accept_table(const prs_stereo_params* params, int* best_lim, int16_t* 
   }
 }
 
-int stereo_match_batch_launch(prs_context* ctx, const prs_stereo_params* params, const prs_stereo_batch* batch) {
-  if (!params || !batch || !batch->left_kp || !batch->left_desc || !batch->n_left || !batch->right_kp ||
-      !batch->right_desc || !batch->n_right || !batch->matches || !batch->n_matches || !batch->status) {
-    return ctx_fail(ctx, PRS_ERR_NULL, "prs_stereo_match_batch: fixed, moving or correspondences not set");
+// the first generation's instantiations <KPT, STAGE>; in the family's numbering they follow the v5 unit's (stereo_kernel_name)
+#define SM(...) PRS_VARIANT("prs::", stereo_match_kernel, StereoArgs, __VA_ARGS__)
+static const Variant<StereoArgs> kStereoVariants[] = {
+    SM(1, true), SM(2, true),  // descriptor staging only exists for frames that fit the LDS (stride <= 2048)
+    SM(1, false), SM(2, false), SM(4, false), SM(8, false),
+};
+#undef SM
+constexpr int kStereoFirstGen = sizeof(kStereoVariants) / sizeof(kStereoVariants[0]);
+static const char* const kTriangulateName =
+  "prs::triangulate_kernel(prs_triangulator_params, HIP_vector_type<float, 4u> const*, long, HIP_vector_type<float, 4u>*)";
+
+const char* stereo_kernel_name(int index) {
+  if (index < kStereoV5Variants) {
+    return stereo_v5_kernel_name(index);
   }
-  if (batch->batch <= 0) {
-    return PRS_OK;
+  index -= kStereoV5Variants;
+  return index < kStereoFirstGen ? kStereoVariants[index].name : (index == kStereoFirstGen ? kTriangulateName : nullptr);
+}
+
+struct StereoPlan : Plan {  // launch[0].kernel: an index into the v5 table when v5.why == kV5Taken, else into kStereoVariants
+  StereoV5Layout v5;
+  StereoArgs a = {};  // the first generation's sort_cap and LDS carve
+  int best_lim = 0, kpt = 0;
+  bool epilogue = false, stage = false;
+  uint32_t staged_lds = 0, unstaged_lds = 0;
+};
+
+static StereoPlan stereo_plan(const prs_stereo_params& params, const prs_stereo_batch& batch, const DispatchEnv& env) {
+  StereoPlan p;
+  if (batch.batch <= 0) {
+    return p;
   }
-  const int stride = batch->stride;
-  if (stride <= 0 || stride > 8192 || params->image_rows <= 0 || params->image_rows > 4096) {
-    return ctx_fail(ctx, PRS_ERR_UNSUPPORTED, "prs_stereo_match_batch: stride must be in [1,8192], image_rows in [1,4096]");
+  const int stride = batch.stride;
+  if (stride <= 0 || stride > 8192 || params.image_rows <= 0 || params.image_rows > 4096) {
+    p.refuse(PRS_ERR_UNSUPPORTED, "prs_stereo_match_batch: stride must be in [1,8192], image_rows in [1,4096]");
+    return p;
   }
-  if (params->epipolar_line_thickness_pixels > 120) {
-    return ctx_fail(ctx, PRS_ERR_UNSUPPORTED, "prs_stereo_match_batch: epipolar_line_thickness_pixels > 120");
+  if (params.epipolar_line_thickness_pixels > 120) {
+    p.refuse(PRS_ERR_UNSUPPORTED, "prs_stereo_match_batch: epipolar_line_thickness_pixels > 120");
+    return p;
   }
-  {
-    // instruction-lean staged kernel for frames of <= 2048 keypoints (stereo_match_v5.hip)
-    const int rc5 = stereo_match_v5_launch(ctx, params, batch);
-    if (rc5 != 1) {
-      return rc5;
-    }
+  p.epilogue = batch.fixed_uvuv && batch.fixed_desc && batch.n_fixed && batch.fixed_xyz && batch.triangulator;
+  p.best_lim = accept_limit(params);
+  // both generations are persistent where they stage: one workgroup per CU (the LDS footprint allows no more), frames strided over them
+  const unsigned persistent = batch.batch < env.cus ? batch.batch : env.cus;
+  // instruction-lean staged kernel for frames of <= 2048 keypoints (stereo_match_v5.hip)
+  p.v5 = stereo_v5_layout(params, stride, p.epilogue, p.best_lim, env);
+  if (p.v5.why == kV5Taken) {
+    p.add(p.v5.kernel, persistent, 1, kStereoThreads, p.v5.lds);
+    return p;
   }
-  StereoArgs a;
-  a.p        = *params;
-  a.b        = *batch;
-  a.epilogue = (batch->fixed_uvuv && batch->fixed_desc && batch->n_fixed && batch->fixed_xyz && batch->triangulator) ? 1 : 0;
-  if (a.epilogue) {
-    a.tri = *batch->triangulator;
-  } else {
-    a.tri = prs_triangulator_params{1.f, 1.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-  }
-  fill_accept_table(params, &a.best_lim, a.bmax);
-  a.stamps              = ctx_stamps(ctx, (size_t) batch->batch * 16 * sizeof(unsigned long long));
+  StereoArgs& a         = p.a;
   const int kpt         = stride <= 1024 ? 1 : (stride <= 2048 ? 2 : (stride <= 4096 ? 4 : 8));
-  const uint32_t rows1  = (uint32_t) params->image_rows + 1;
+  const uint32_t rows1  = (uint32_t) params.image_rows + 1;
   a.sort_cap            = (int) (((uint32_t) stride > rows1 ? (uint32_t) stride : rows1));
   const uint32_t nwords = ((uint32_t) stride + 31) / 32;
   // LDS carve; every offset is a multiple of 16 (cdna_hip_programming.md Guideline 17)
-  auto carve = [&](bool stage, StereoArgs& s) -> size_t {
+  auto carve = [&](bool stage, StereoArgs& s) -> uint32_t {
     uint32_t off          = 0;
     const uint32_t dbytes = stage ? (uint32_t) stride * PRS_DESC_BYTES : 0;
     s.off_desc_l     = off;  // left rows are not staged
@@ -783,31 +787,56 @@ int stereo_match_batch_launch(prs_context* ctx, const prs_stereo_params* params,
     s.off_kp_r       = off; off = align_up(off + (stage ? (uint32_t) stride * 8 : 0), 16);
     return off;
   };
-  const size_t lds_limit = 160 * 1024;
-  bool stage             = true;
-  size_t lds             = carve(true, a);
-  if (lds > lds_limit || kpt > 2 || ctx_force_unstaged(ctx)) {
-    stage = false;
-    lds   = carve(false, a);
+  const uint32_t lds_limit = 160 * 1024;
+  p.kpt               = kpt;
+  StereoArgs unstaged = a;
+  p.staged_lds        = carve(true, a);
+  p.unstaged_lds      = carve(false, unstaged);
+  p.stage             = !(p.staged_lds > lds_limit || kpt > 2 || env.force_unstaged);
+  if (!p.stage) {
+    a = unstaged;
   }
+  const uint32_t lds = p.stage ? p.staged_lds : p.unstaged_lds;
   if (lds > lds_limit) {
-    return ctx_fail(ctx, PRS_ERR_UNSUPPORTED, "prs_stereo_match_batch: frame does not fit the 160 KiB LDS");
+    p.refuse(PRS_ERR_UNSUPPORTED, "prs_stereo_match_batch: frame does not fit the 160 KiB LDS");
+    return p;
   }
-  hipStream_t stream = ctx_stream(ctx);
-  hipError_t e       = hipSuccess;
-  // descriptor staging only exists for frames that fit the LDS (stride <= 2048)
-  if (stage && kpt == 1) {
-    e = launch_variant<1, true>(a, lds, stream);
-  } else if (stage && kpt == 2) {
-    e = launch_variant<2, true>(a, lds, stream);
-  } else if (kpt == 1) {
-    e = launch_variant<1, false>(a, lds, stream);
-  } else if (kpt == 2) {
-    e = launch_variant<2, false>(a, lds, stream);
-  } else if (kpt == 4) {
-    e = launch_variant<4, false>(a, lds, stream);
+  p.add(find_variant(kStereoVariants, {kpt, p.stage}), p.stage ? persistent : batch.batch, 1, kStereoThreads, lds);
+  return p;
+}
+
+int stereo_match_batch_launch(prs_context* ctx, const prs_stereo_params* params, const prs_stereo_batch* batch) {
+  if (!params || !batch || !batch->left_kp || !batch->left_desc || !batch->n_left || !batch->right_kp ||
+      !batch->right_desc || !batch->n_right || !batch->matches || !batch->n_matches || !batch->status) {
+    return ctx_fail(ctx, PRS_ERR_NULL, "prs_stereo_match_batch: fixed, moving or correspondences not set");
+  }
+  const StereoPlan plan = stereo_plan(*params, *batch, dispatch_env(ctx));
+  if (plan.status != PRS_OK) {
+    return ctx_fail(ctx, plan.status, plan.message);
+  }
+  if (plan.n_launches == 0) {
+    return PRS_OK;
+  }
+  const Plan::Launch& l = plan.launch[0];
+  if (plan.v5.why == kV5Taken) {
+    return stereo_match_v5_launch(ctx, params, batch, plan.v5, l);
+  }
+  StereoArgs a = plan.a;
+  a.p          = *params;
+  a.b          = *batch;
+  a.epilogue   = plan.epilogue ? 1 : 0;
+  if (a.epilogue) {
+    a.tri = *batch->triangulator;
   } else {
-    e = launch_variant<8, false>(a, lds, stream);
+    a.tri = prs_triangulator_params{1.f, 1.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+  }
+  fill_accept_table(params, &a.best_lim, a.bmax);
+  a.stamps     = ctx_stamps(ctx, (size_t) batch->batch * 16 * sizeof(unsigned long long));
+  auto kernel  = kStereoVariants[l.kernel].fn;
+  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int) l.lds);
+  if (e == hipSuccess) {
+    hipLaunchKernelGGL(kernel, dim3(l.grid_x), dim3(l.block), l.lds, ctx_stream(ctx), a);
+    e = hipGetLastError();
   }
   if (e != hipSuccess) {
     return ctx_fail_hip(ctx, e, "prs_stereo_match_batch launch");
@@ -840,3 +869,27 @@ int triangulate_launch(prs_context* ctx, const prs_triangulator_params* params, 
 }
 
 } // namespace prs
+
+extern "C" int prs_stereo_plan(const prs_stereo_params* params, const prs_stereo_batch* batch, const prs_dispatch_env* env, prs_dispatch_plan* out) {
+  if (!params || !batch || !env || !out) {
+    return PRS_ERR_NULL;
+  }
+  const prs::StereoPlan p = prs::stereo_plan(*params, *batch, *env);
+  const bool v5 = p.v5.why == prs::kV5Taken;
+  *out            = prs_dispatch_plan{};
+  out->status     = p.status;
+  out->message    = p.message;
+  out->n_launches = p.n_launches;
+  if (p.n_launches) {
+    const prs::Plan::Launch& l = p.launch[0];
+    out->launch[0] = {prs::stereo_kernel_name(v5 ? l.kernel : prs::kStereoV5Variants + l.kernel), (int32_t) l.grid_x, (int32_t) l.grid_y, (int32_t) l.block,
+                      (uint32_t) l.lds};
+  }
+  int32_t* f = out->fact;
+  f[PRS_PLAN_STEREO_V5] = p.n_launches && v5, f[PRS_PLAN_STEREO_V5_WHY] = p.v5.why, f[PRS_PLAN_STEREO_CAP] = p.v5.cap;
+  f[PRS_PLAN_STEREO_OFF_POOL] = (int32_t) p.v5.off_pool, f[PRS_PLAN_STEREO_POOL_CAP] = p.v5.pool_cap, f[PRS_PLAN_STEREO_V5_LDS] = (int32_t) p.v5.lds;
+  f[PRS_PLAN_STEREO_KPT] = p.kpt, f[PRS_PLAN_STEREO_EPI] = p.epilogue, f[PRS_PLAN_STEREO_STAGE] = p.stage;
+  f[PRS_PLAN_STEREO_STAGED_LDS] = (int32_t) p.staged_lds, f[PRS_PLAN_STEREO_UNSTAGED_LDS] = (int32_t) p.unstaged_lds;
+  f[PRS_PLAN_STEREO_SORT_CAP] = p.a.sort_cap, f[PRS_PLAN_STEREO_BEST_LIM] = p.best_lim;
+  return PRS_OK;
+}

@@ -784,42 +784,35 @@ inline uint32_t up16(uint32_t v) {
   return (v + 15u) & ~15u;
 }
 
-template <int KPT>
-hipError_t launch5(const Args5& a, size_t lds, hipStream_t stream) {
-  const bool multi = a.p.epipolar_line_thickness_pixels > 0;
-  auto kernel      = a.epilogue ? (multi ? stereo_match5_kernel<KPT, true, true> : stereo_match5_kernel<KPT, false, true>)
-                                : (multi ? stereo_match5_kernel<KPT, true, false> : stereo_match5_kernel<KPT, false, false>);
-  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds);
-  if (e != hipSuccess) {
-    return e;
-  }
-  // persistent: one workgroup per CU (the LDS footprint allows no more), frames strided over them
-  int grid = a.b.batch, dev = 0, cus = 0;
-  if (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && cus > 0 &&
-      cus < grid) {
-    grid = cus;
-  }
-  hipLaunchKernelGGL(kernel, dim3(grid), dim3(kT), lds, stream, a);
-  return hipGetLastError();
-}
-
 }  // namespace v5
 using namespace v5;
 
-// returns 1 when the frame shape is outside this kernel's domain (the caller falls back to stereo_match_kernel)
-int stereo_match_v5_launch(prs_context* ctx, const prs_stereo_params* params, const prs_stereo_batch* batch) {
-  const int stride = batch->stride;
-  const int rows   = params->image_rows;
-  if (stride > 2 * kT || ctx_force_unstaged(ctx) || ctx_matcher_v3(ctx)) {
-    return 1;
+#define V5(...) PRS_VARIANT("prs::v5::", stereo_match5_kernel, Args5, __VA_ARGS__)
+static const Variant<Args5> kV5Variants[kStereoV5Variants] = {  // <KPT, MULTI, EPI>
+    V5(1, true, true), V5(1, false, true), V5(1, true, false), V5(1, false, false),
+    V5(2, true, true), V5(2, false, true), V5(2, true, false), V5(2, false, false),
+};
+#undef V5
+
+const char* stereo_v5_kernel_name(int index) {
+  return index >= 0 && index < kStereoV5Variants ? kV5Variants[index].name : nullptr;
+}
+
+// the v5 kernel's variant and LDS layout for a frame shape, or why the shape is outside its domain (the first generation takes it)
+StereoV5Layout stereo_v5_layout(const prs_stereo_params& params, int stride, bool epilogue, int best_lim, const DispatchEnv& env) {
+  StereoV5Layout a;
+  const int rows = params.image_rows;
+  if (stride > 2 * kT || env.force_unstaged || env.matcher_v3) {
+    a.why = stride > 2 * kT ? kV5Stride : kV5Knob;
+    return a;
   }
-  Args5 a;
   // every non-empty row is padded by at most three entries
   const uint32_t cap = ((uint32_t) stride + 3u * (uint32_t) (rows < stride ? rows : stride) + 3u) & ~3u;
+  a.cap = (int) cap;
   if (cap > 8188u) {
-    return 1;  // sorted positions are stored in 13 bits
+    a.why = kV5Cap;  // sorted positions are stored in 13 bits
+    return a;
   }
-  a.cap    = (int) cap;
   a.nwords = (int) ((cap + 31u) / 32u);
   uint32_t off = 0;
   const uint32_t rows2 = (uint32_t) rows + 2u;
@@ -836,15 +829,31 @@ int stereo_match_v5_launch(prs_context* ctx, const prs_stereo_params* params, co
   a.off_bits     = off; off = up16(off + (uint32_t) a.nwords * 2u * 4u);
   a.off_misc     = off; off = up16(off + 32u);
   a.off_tab      = off; off = up16(off + 258u * 2u);
+  a.lds          = off;
   if (off > 160u * 1024u) {
-    return 1;
+    a.why = kV5Lds;
+    return a;
   }
   // what is left of the 160 KB holds the scored candidates of crowded windows (four bytes each, at most 4096)
   a.off_pool = off;
   a.pool_cap = (int) (((160u * 1024u - off) / 4u) & ~3u);
   a.pool_cap = a.pool_cap > 4096 ? 4096 : (a.pool_cap < 64 ? 0 : a.pool_cap);
-  off        = up16(off + (uint32_t) a.pool_cap * 4u);
-  const size_t lds = off;
+  a.lds      = up16(off + (uint32_t) a.pool_cap * 4u);
+  if (best_lim > 255) {
+    a.why = kV5BestLim;  // the candidate records keep 8 bits per distance
+    return a;
+  }
+  a.kernel = find_variant(kV5Variants, {stride <= kT ? 1 : 2, params.epipolar_line_thickness_pixels > 0, epilogue});
+  return a;
+}
+
+int stereo_match_v5_launch(prs_context* ctx, const prs_stereo_params* params, const prs_stereo_batch* batch, const StereoV5Layout& l,
+                           const Plan::Launch& launch) {
+  Args5 a;
+  a.cap = l.cap, a.nwords = l.nwords, a.pool_cap = l.pool_cap;
+  a.off_desc_r = l.off_desc_r, a.off_kp_r = l.off_kp_r, a.off_sorted_l = l.off_sorted_l, a.off_sorted_r = l.off_sorted_r;
+  a.off_bucket = l.off_bucket, a.off_hist = l.off_hist, a.off_rs = l.off_rs, a.off_len = l.off_len, a.off_rowcnt = l.off_rowcnt;
+  a.off_out = l.off_out, a.off_bits = l.off_bits, a.off_misc = l.off_misc, a.off_tab = l.off_tab, a.off_pool = l.off_pool;
   a.p        = *params;
   a.b        = *batch;
   a.epilogue = (batch->fixed_uvuv && batch->fixed_desc && batch->n_fixed && batch->fixed_xyz && batch->triangulator) ? 1 : 0;
@@ -854,12 +863,14 @@ int stereo_match_v5_launch(prs_context* ctx, const prs_stereo_params* params, co
     a.tri = prs_triangulator_params{1.f, 1.f, 0.f, 0.f, 0.f, 0.f, 0.f};
   }
   fill_accept_table(params, &a.best_lim, a.bmax);
-  if (a.best_lim > 255) {
-    return 1;  // the candidate records keep 8 bits per distance
-  }
   a.stamps           = ctx_stamps(ctx, (size_t) batch->batch * 16 * sizeof(unsigned long long));
-  hipStream_t stream = ctx_stream(ctx);
-  const hipError_t e = stride <= kT ? launch5<1>(a, lds, stream) : launch5<2>(a, lds, stream);
+  auto kernel        = kV5Variants[launch.kernel].fn;
+  hipError_t e       = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int) launch.lds);
+  if (e == hipSuccess) {
+    // persistent: one workgroup per CU (the LDS footprint allows no more), frames strided over them
+    hipLaunchKernelGGL(kernel, dim3(launch.grid_x), dim3(launch.block), launch.lds, ctx_stream(ctx), a);
+    e = hipGetLastError();
+  }
   if (e != hipSuccess) {
     return ctx_fail_hip(ctx, e, "prs_stereo_match_batch launch");
   }

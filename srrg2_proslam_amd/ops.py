@@ -90,6 +90,58 @@ class Context:
         return list(a), list(b), n.value
 
 
+# =================================================================================================
+# dispatch plans (tests and tools): which kernels a launch would run, without a device
+# =================================================================================================
+def dispatch_env(ctx=None, **fields):
+    """prs_dispatch_env: a live context's (its real CU count and knobs, the brute-force switches from the environment as it is now),
+    or 256 CUs with every knob at its default; fields override either"""
+    env = _lib.DispatchEnv(cus=256, bf_mfma=1, bf_two_workgroups=-1)  # (PRS_BF_DENSE_MATRIX_WHEN_FULL)
+    if ctx is not None:
+        _check(ctx, _lib.load().prs_context_get_dispatch_env(ctx._h, C.byref(env)), "prs_context_get_dispatch_env")
+    for k, v in fields.items():
+        setattr(env, k, int(v))
+    return env
+
+
+def dispatch_kernel_names(family):
+    """every kernel a plan of the family (_lib.DISPATCH_*) can name, as a kernel trace prints them"""
+    lib, names = _lib.load(), []
+    while lib.prs_dispatch_kernel_name(family, len(names)) is not None:
+        names.append(lib.prs_dispatch_kernel_name(family, len(names)).decode())
+    return names
+
+
+def _plan(family, entry, *args):
+    """-> dict(status, message, kernels, launches=[dict(kernel, grid_x, grid_y, block, lds)], + the family's facts by name)"""
+    plan = _lib.DispatchPlan()
+    rc = getattr(_lib.load(), entry)(*[a if isinstance(a, int) else C.byref(a) for a in args], C.byref(plan))
+    if rc != 0:
+        raise ProslamHipError(rc, entry)
+    launches = [dict(kernel=l.kernel.decode(), grid_x=l.grid_x, grid_y=l.grid_y, block=l.block, lds=l.lds_bytes) for l in plan.launch[:plan.n_launches]]
+    out = dict(status=plan.status, message=plan.message.decode() if plan.message else None, launches=launches,
+               kernels=[l["kernel"] for l in launches])
+    out.update(zip(_lib.PLAN_FACTS[family], plan.fact))
+    return out
+
+
+def stereo_plan(params, batch, env):
+    """prs_stereo_plan(prs_stereo_params, prs_stereo_batch descriptor, prs_dispatch_env)"""
+    return _plan(_lib.DISPATCH_STEREO, "prs_stereo_plan", params, batch, env)
+
+
+def align_plan(finder_params, aligner_params_, batch, env, mode=_lib.MODE_ALIGN):
+    return _plan(_lib.DISPATCH_ALIGN, "prs_align_plan", finder_params, aligner_params_, batch, int(mode), env)
+
+
+def bruteforce_plan(params, batch, env):
+    return _plan(_lib.DISPATCH_BRUTEFORCE, "prs_bruteforce_plan", params, batch, env)
+
+
+def merge_plan(params, batch, env):
+    return _plan(_lib.DISPATCH_MERGE, "prs_merge_plan", params, batch, env)
+
+
 def stereo_params(cfg_matcher, image_rows, image_cols=0):
     """image_cols is reserved (ignored)"""
     return StereoParams(

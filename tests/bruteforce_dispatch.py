@@ -1,10 +1,12 @@
-"""Plain-Python restatement of the brute-force matcher's host dispatch, bruteforce_batch_launch (csrc/bruteforce.hip); no GPU needed.
+"""Plain-Python restatement of the brute-force matcher's host dispatch, bruteforce_plan (csrc/bruteforce.hip); no GPU needed.
 
 dispatch() says which of the 15 kernels a launch reaches (or why it is refused), by the names a kernel trace prints, together with
 the facts the data-dependent forks of the kernels hang on: the candidate limit `lim`, the bitmap words `nw`, the candidate capacity
 `cap`, the grid, the slices of the split shape (`chunks`), whether the distance bitmaps live in LDS (`bm_fits`), how many candidates
-of a pair keep their level lists in LDS (`lvl_cap`), and the dynamic LDS bytes.  tests/test_bruteforce_dispatch_table.py checks the
-constants below against the source."""
+of a pair keep their level lists in LDS (`lvl_cap`), and the dynamic LDS bytes.  tests/test_bruteforce_dispatch_table.py checks
+dispatch() against the library's own plan (prs_bruteforce_plan), field by field over a sweep of shapes, modes and switches."""
+import functools
+
 import numpy as np
 
 POPCOUNT, MATRIX_WHEN_FULL, MATRIX = 0, 1, 2  # PRS_BF_DENSE_*
@@ -44,6 +46,7 @@ def mx_bytes(threads, chunk):
 MX_BYTES, MX_BYTES_DUAL = mx_bytes(THREADS, 64), mx_bytes(512, 32)
 
 
+@functools.lru_cache(maxsize=None)
 def limit_of(max_dist):
     """candidate iff d < lim  <=>  (float) d < maximum_descriptor_distance; above LEVELS: refused"""
     max_dist = np.float32(max_dist)

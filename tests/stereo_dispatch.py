@@ -1,12 +1,15 @@
 """Plain-Python restatement of the stereo matcher's host dispatch (no GPU needed).
 
-stereo_match_batch_launch (csrc/stereo_match.hip) refuses a frame shape, hands it to stereo_match_v5_launch
-(csrc/stereo_match_v5.hip) or carves the LDS of the first-generation kernel; v5 refuses shapes whose padded sorted positions
-or LDS layout do not fit, and distance thresholds above its 8-bit records.  dispatch() says which of the 15 instantiations a
+stereo_plan (csrc/stereo_match.hip) refuses a frame shape, takes the layout stereo_v5_layout (csrc/stereo_match_v5.hip) gives it
+or carves the LDS of the first-generation kernel; v5 is not taken for shapes whose padded sorted positions or LDS layout do not
+fit, nor for distance thresholds above its 8-bit records.  dispatch() says which of the 15 instantiations a
 launch reaches (or why it is refused) together with the layout facts the data-dependent paths hang on: v5's `cap`, the pool
-offset and `pool_cap`, the first generation's staged / unstaged carve.  window_demand() counts, per pass of a frame, the
+offset and `pool_cap`, the first generation's staged / unstaged carve, the grid.  window_demand() counts, per pass of a frame, the
 in-window candidates of crowded windows (more than four), which go to the LDS pool until it is full and to the chain's replay
-sweep after that.  tests/test_stereo_dispatch_table.py checks the constants below against the source."""
+sweep after that.  tests/test_stereo_dispatch_table.py checks dispatch() against the library's own plan (prs_stereo_plan), field
+by field over a sweep of shapes and knobs."""
+import functools
+
 import numpy as np
 
 KT = 1024               # threads of both matcher kernels (kT, kStereoThreads)
@@ -24,12 +27,28 @@ def _up16(v):
     return (v + 15) & ~15
 
 
-def fill_accept_table(max_dist, ratio):
-    """fill_accept_table: best_lim and bmax[258] from the reference's float operations (epipolar_impl.cpp:171-173)"""
-    max_dist, ratio = np.float32(max_dist), np.float32(ratio)
+@functools.lru_cache(maxsize=None)
+def accept_limit(max_dist):
+    """accept iff best < this: (float) d < maximum_descriptor_distance for integer d"""
+    max_dist = np.float32(max_dist)
     lim = 0
     while lim <= 256 and np.float32(lim) < max_dist:
         lim += 1
+    return lim
+
+
+def trace_name(kernel, args):
+    """an instantiation (kernel, "KPT,MULTI,EPI" or "KPT,STAGE") as a kernel trace prints it"""
+    scope, arg_type = ("prs::v5::", "Args5") if kernel == "stereo_match5_kernel" else ("prs::", "StereoArgs")
+    return "void %s%s<%s>(%s%s)" % (scope, kernel, args.replace(",", ", "), scope, arg_type)
+
+
+TRIANGULATE_KERNEL = "prs::triangulate_kernel(prs_triangulator_params, HIP_vector_type<float, 4u> const*, long, HIP_vector_type<float, 4u>*)"
+
+
+def fill_accept_table(max_dist, ratio):
+    """fill_accept_table: best_lim and bmax[258] from the reference's float operations (epipolar_impl.cpp:171-173)"""
+    lim, ratio = accept_limit(max_dist), np.float32(ratio)
     bmax = []
     with np.errstate(divide="ignore", invalid="ignore"):
         for s in range(258):
@@ -79,13 +98,13 @@ def first_gen_carve(stride, rows, stage):
     return off
 
 
-def dispatch(stride, rows, thickness, max_dist, epilogue, matcher_v3=False, force_unstaged=False):
-    """-> dict(kernel, args, refused, v5, staged_lds, unstaged_lds): the instantiation one launch runs.
+def dispatch(stride, rows, thickness, max_dist, epilogue, matcher_v3=False, force_unstaged=False, batch=1, cus=256):
+    """-> dict(kernel, args, refused, v5, staged_lds, unstaged_lds, grid): the instantiation one launch runs.
 
     kernel / args spell the template as the dispatch does (stereo_match5_kernel "KPT,MULTI,EPI" or stereo_match_kernel
     "KPT,STAGE"); refused is None or the host's reason ("shape", "thickness", "lds"); v5 is v5_layout() when v5 was consulted
     and got as far as its layout."""
-    res = dict(kernel=None, args=None, refused=None, v5=None, v5_why=None, staged_lds=None, unstaged_lds=None)
+    res = dict(kernel=None, args=None, refused=None, v5=None, v5_why=None, staged_lds=None, unstaged_lds=None, grid=0)
     if stride <= 0 or stride > MAX_STRIDE or rows <= 0 or rows > MAX_ROWS:
         res["refused"] = "shape"
         return res
@@ -93,7 +112,8 @@ def dispatch(stride, rows, thickness, max_dist, epilogue, matcher_v3=False, forc
         res["refused"] = "thickness"
         return res
     multi = thickness > 0
-    best_lim, _ = fill_accept_table(max_dist, 0.5)
+    best_lim = accept_limit(max_dist)
+    persistent = min(batch, cus)  # one workgroup per CU, frames strided over them
     if stride > V5_MAX_STRIDE or force_unstaged or matcher_v3:
         res["v5_why"] = "knob" if stride <= V5_MAX_STRIDE else "stride"
     else:
@@ -107,6 +127,7 @@ def dispatch(stride, rows, thickness, max_dist, epilogue, matcher_v3=False, forc
             kpt = 1 if stride <= KT else 2
             res["kernel"] = "stereo_match5_kernel"
             res["args"] = "%d,%s,%s" % (kpt, "true" if multi else "false", "true" if epilogue else "false")
+            res["grid"] = persistent
             return res
     kpt = 1 if stride <= 1024 else (2 if stride <= 2048 else (4 if stride <= 4096 else 8))
     res["staged_lds"] = first_gen_carve(stride, rows, True)
@@ -117,6 +138,7 @@ def dispatch(stride, rows, thickness, max_dist, epilogue, matcher_v3=False, forc
         return res
     res["kernel"] = "stereo_match_kernel"
     res["args"] = "%d,%s" % (kpt, "true" if stage else "false")
+    res["grid"] = persistent if stage else batch
     return res
 
 

@@ -5,7 +5,8 @@ The dispatch picks a Gauss-Newton kernel (gn_kernel<SLOTS, DIM, KEEP_CLS, LDS_SL
 (the "lone" variants), max_fixed against 512 (SLOTS) and 1024 (split vs fused), the stereo factor and shipped forms ("fast"),
 prior / with_sensor / inlier-only runs ("plain", motion-prior-only), the depth factor, and an LDS occupancy comparison (the survivor
 slot width).  DISPATCH below names one row per instantiation with the knobs that select it; tests/test_align_dispatch_table.py
-checks (without a GPU) that every instantiation in the dispatch block has a row.  Each row runs a batch of distinct frames and is
+checks (without a GPU) that every instantiation in the library's variant table has a row and that the library's plan
+(prs_align_plan) picks each row's kernels from the row's knobs.  Each row runs a batch of distinct frames and is
 compared with the per-frame oracle bit for bit (correspondences incl. response bits, pose bits, status / warnings, finder state),
 and every converged frame's final pose is checked to be a fixed point of a float64 Gauss-Newton step on its own correspondences.
 Then the capacity edges (LDS-parked operand rows, max_fixed 512/513, 1024/1025, 2047/2048, a frame over its max_fixed), the pruned
@@ -26,29 +27,44 @@ SENSOR = syn.make_transform([0.12, -0.05, 0.3], [0.01, -0.02, 0.015]).astype(np.
 # quaternion imaginary part) below this: the CPU oracle's own results for these rows reach 4.3e-5 (inlier-only runs), <= 1e-6 otherwise
 F64_STEP_TOL = 2e-4
 
-# One row per instantiation of the dispatch.  gn / search: the template argument lists as the dispatch spells them (whitespace
-# removed; the search kernel's last argument is the survivor slot width the LDS comparison gives at this max_fixed: 4 at 600 / 896,
-# 8 at 384 / 512 / 700 / 1000 / 1024 for these canvases and radii, 4 for the KD-tree); no_lone: PRS_NO_LONE_GN=1; fused: PRS_FUSED_ALIGN=1.  mprior = motion prior (prior mean = the
-# initial guess), sensor = with_sensor, akw / fkw = aligner / finder overrides (inlier-only runs, kept inlier classes, radius).
+# One row per instantiation of the dispatch.  gn / search: the kernels as a kernel trace prints them (the search kernel's last
+# argument is the survivor slot width the LDS comparison gives at this max_fixed, SLOT_WIDTHS below; 4 for the KD-tree);
+# no_lone: PRS_NO_LONE_GN=1; fused: PRS_FUSED_ALIGN=1.  mprior = motion prior (prior mean = the initial guess), sensor = with_sensor,
+# akw / fkw = aligner / finder overrides (inlier-only runs, kept inlier classes, radius).
+def GN(args):
+    return "void prs::gn_kernel<%s>(prs::AlignArgs)" % args
+
+
+def AK(args):
+    return "void prs::align_kernel<%s>(prs::AlignArgs)" % args
+
+
+# the survivor slot width of the lattice finders by max_fixed, for the rows' canvases and radii
+SLOT_WIDTHS = {600: 4, 896: 4, 384: 8, 512: 8, 700: 8, 1000: 8, 1024: 8}
 DISPATCH = [
-    dict(id="lone4_plain", cfg="kitti", max_fixed=512, no_lone=0, gn="4,PRS_FACTOR_STEREO,false,kGnLdsSlots,1,1", search="kSearchThreads,true,PRS_SEARCH_CIRCLE,8", fkw=dict(search_type=2)),
-    dict(id="lone4_mprior", cfg="kitti", max_fixed=512, no_lone=0, mprior=1, gn="4,PRS_FACTOR_STEREO,false,kGnLdsSlots,1", search="kSearchThreads,true,PRS_SEARCH_SQUARE,8", fkw=dict(search_type=1)),
-    dict(id="lone8_plain", cfg="kitti", max_fixed=600, no_lone=0, gn="8,PRS_FACTOR_STEREO,false,kGnLdsSlots,1,1", search="kSearchThreads,true,PRS_SEARCH_CIRCLE,4", fkw=dict(search_type=2, maximum_search_radius_pixels=100)),
-    dict(id="lone8_sensor", cfg="kitti", max_fixed=896, no_lone=0, sensor=1, gn="8,PRS_FACTOR_STEREO,false,kGnLdsSlots,1", search="kSearchThreads,true,PRS_SEARCH_SQUARE,4", fkw=dict(search_type=1, maximum_search_radius_pixels=100)),
-    dict(id="tp4_plain", cfg="kitti", max_fixed=512, no_lone=1, gn="4,PRS_FACTOR_STEREO,false,kGnLdsSlots,4,1", search="kSearchThreads,true,PRS_SEARCH_RHOMBUS,8", fkw=dict(search_type=3)),
-    dict(id="tp4_mprior", cfg="kitti", max_fixed=448, no_lone=1, mprior=1, gn="4,PRS_FACTOR_STEREO,false,kGnLdsSlots,4,2", search="kSearchThreads,true,PRS_SEARCH_KDTREE,4", fkw=dict(search_type=0)),
-    dict(id="tp4_sensor", cfg="kitti", max_fixed=384, no_lone=1, sensor=1, gn="4,PRS_FACTOR_STEREO,false", search="kSearchThreads,true,PRS_SEARCH_CIRCLE,8", fkw=dict(search_type=2)),
-    dict(id="depth4", cfg="tum", max_fixed=512, no_lone=0, gn="4,PRS_FACTOR_DEPTH,true", search="kSearchThreads,true,PRS_SEARCH_SQUARE,8", fkw=dict(search_type=1)),
-    dict(id="generic4", cfg="euroc", max_fixed=512, no_lone=0, akw=dict(keep_only_inlier_correspondences=1), gn="4,0,true", search="kSearchThreads,true,PRS_SEARCH_RHOMBUS,8", fkw=dict(search_type=3)),
-    dict(id="five_plain", cfg="kitti", max_fixed=896, no_lone=1, gn="8,PRS_FACTOR_STEREO,false,3,5,1", search="kSearchThreads,true,PRS_SEARCH_RHOMBUS,4", fkw=dict(search_type=3, maximum_search_radius_pixels=100)),
-    dict(id="five_mprior", cfg="kitti", max_fixed=1000, no_lone=1, mprior=1, gn="8,PRS_FACTOR_STEREO,false,3,5,2", search="kSearchThreads,true,PRS_SEARCH_SQUARE,8", fkw=dict(search_type=1)),
-    dict(id="five_inlier_runs", cfg="kitti", max_fixed=700, no_lone=1, akw=dict(enable_inlier_only_runs=1, inlier_only_iterations=5), gn="8,PRS_FACTOR_STEREO,false,3,5", search="kSearchThreads,true,PRS_SEARCH_CIRCLE,8", fkw=dict(search_type=2)),
-    dict(id="depth8", cfg="tum", max_fixed=600, no_lone=0, gn="8,PRS_FACTOR_DEPTH,true", search="kSearchThreads,true,PRS_SEARCH_KDTREE,4", fkw=dict(search_type=0)),
-    dict(id="generic8", cfg="euroc", max_fixed=1024, no_lone=0, akw=dict(keep_only_inlier_correspondences=1), gn="8,0,true", search="kSearchThreads,true,PRS_SEARCH_CIRCLE,8", fkw=dict(search_type=2)),
-    dict(id="fused_forced", cfg="kitti", max_fixed=800, no_lone=0, fused=1, gn=None, search="kAlignThreads,false,-1", fkw=dict(search_type=2)),
-    dict(id="fused_by_size", cfg="euroc", max_fixed=1100, no_lone=0, gn=None, search="kAlignThreads,false,-1", fkw=dict(search_type=1)),
+    dict(id="lone4_plain", cfg="kitti", max_fixed=512, no_lone=0, gn=GN("4, 4, false, 4, 1, 1"), search=AK("512, true, 2, 8"), fkw=dict(search_type=2)),
+    dict(id="lone4_mprior", cfg="kitti", max_fixed=512, no_lone=0, mprior=1, gn=GN("4, 4, false, 4, 1, 0"), search=AK("512, true, 1, 8"), fkw=dict(search_type=1)),
+    dict(id="lone8_plain", cfg="kitti", max_fixed=600, no_lone=0, gn=GN("8, 4, false, 4, 1, 1"), search=AK("512, true, 2, 4"), fkw=dict(search_type=2, maximum_search_radius_pixels=100)),
+    dict(id="lone8_sensor", cfg="kitti", max_fixed=896, no_lone=0, sensor=1, gn=GN("8, 4, false, 4, 1, 0"), search=AK("512, true, 1, 4"), fkw=dict(search_type=1, maximum_search_radius_pixels=100)),
+    dict(id="tp4_plain", cfg="kitti", max_fixed=512, no_lone=1, gn=GN("4, 4, false, 4, 4, 1"), search=AK("512, true, 3, 8"), fkw=dict(search_type=3)),
+    dict(id="tp4_mprior", cfg="kitti", max_fixed=448, no_lone=1, mprior=1, gn=GN("4, 4, false, 4, 4, 2"), search=AK("512, true, 0, 4"), fkw=dict(search_type=0)),
+    dict(id="tp4_sensor", cfg="kitti", max_fixed=384, no_lone=1, sensor=1, gn=GN("4, 4, false, 4, 4, 0"), search=AK("512, true, 2, 8"), fkw=dict(search_type=2)),
+    dict(id="depth4", cfg="tum", max_fixed=512, no_lone=0, gn=GN("4, 3, true, 4, 4, 0"), search=AK("512, true, 1, 8"), fkw=dict(search_type=1)),
+    dict(id="generic4", cfg="euroc", max_fixed=512, no_lone=0, akw=dict(keep_only_inlier_correspondences=1), gn=GN("4, 0, true, 4, 4, 0"), search=AK("512, true, 3, 8"), fkw=dict(search_type=3)),
+    dict(id="five_plain", cfg="kitti", max_fixed=896, no_lone=1, gn=GN("8, 4, false, 3, 5, 1"), search=AK("512, true, 3, 4"), fkw=dict(search_type=3, maximum_search_radius_pixels=100)),
+    dict(id="five_mprior", cfg="kitti", max_fixed=1000, no_lone=1, mprior=1, gn=GN("8, 4, false, 3, 5, 2"), search=AK("512, true, 1, 8"), fkw=dict(search_type=1)),
+    dict(id="five_inlier_runs", cfg="kitti", max_fixed=700, no_lone=1, akw=dict(enable_inlier_only_runs=1, inlier_only_iterations=5), gn=GN("8, 4, false, 3, 5, 0"), search=AK("512, true, 2, 8"), fkw=dict(search_type=2)),
+    dict(id="depth8", cfg="tum", max_fixed=600, no_lone=0, gn=GN("8, 3, true, 4, 4, 0"), search=AK("512, true, 0, 4"), fkw=dict(search_type=0)),
+    dict(id="generic8", cfg="euroc", max_fixed=1024, no_lone=0, akw=dict(keep_only_inlier_correspondences=1), gn=GN("8, 0, true, 4, 4, 0"), search=AK("512, true, 2, 8"), fkw=dict(search_type=2)),
+    dict(id="fused_forced", cfg="kitti", max_fixed=800, no_lone=0, fused=1, gn=None, search=AK("256, false, -1, 4"), fkw=dict(search_type=2)),
+    dict(id="fused_by_size", cfg="euroc", max_fixed=1100, no_lone=0, gn=None, search=AK("256, false, -1, 4"), fkw=dict(search_type=1)),
 ]
 FRAMES_PER_ROW = 6
+
+
+def row_kernels(row):
+    """the kernels of a round as a plan lists them (search, Gauss-Newton); None for the ad-hoc rows of the edge tests"""
+    return ([row["search"]] + ([row["gn"]] if row["gn"] else [])) if "search" in row else None
 
 
 def _bits(a):
@@ -107,7 +123,7 @@ def _device_params(cfg, fkw, akw, sensor=False, mprior=False):
     return ops.pcf_params(cfg, **fkw), ap
 
 
-def _run_batch(ctx, cfg, cases, max_fixed, fkw, akw, sensor=False, mprior=False, stride=None, frames=None):
+def _run_batch(ctx, cfg, cases, max_fixed, fkw, akw, sensor=False, mprior=False, stride=None, frames=None, expect=None):
     import torch
     B = len(cases)
     if frames is None:
@@ -118,6 +134,8 @@ def _run_batch(ctx, cfg, cases, max_fixed, fkw, akw, sensor=False, mprior=False,
         if mprior:
             frames.prior_mean = torch.from_numpy(np.stack([c["X0"].reshape(16) for c in cases]).astype(np.float32)).cuda()
     fp, ap = _device_params(cfg, fkw, akw, sensor, mprior)
+    if expect is not None:  # what the library plans for these inputs on this device (host only)
+        assert ops.align_plan(fp, ap, frames.descriptor(), ops.dispatch_env(ctx))["kernels"] == expect
     ops.align_batch(ctx, fp, ap, frames)
     torch.cuda.synchronize()
     return frames
@@ -155,7 +173,7 @@ def _check_frame(frames, b, of, res, rcorr, what):
 def _row_parity(oracle, ctx, row, cases, cfg, stride=None):
     """the row's batch against the per-frame oracle + the float64 fixed-point check; returns (n_corr list, converged frames)"""
     fkw, akw, sensor, mprior = row.get("fkw", {}), row.get("akw", {}), bool(row.get("sensor")), bool(row.get("mprior"))
-    frames = _run_batch(ctx, cfg, cases, row["max_fixed"], fkw, akw, sensor, mprior, stride=stride)
+    frames = _run_batch(ctx, cfg, cases, row["max_fixed"], fkw, akw, sensor, mprior, stride=stride, expect=row_kernels(row))
     n_corr, converged = [], 0
     for b, c in enumerate(cases):
         of, res, rcorr = _oracle_frame(oracle, cfg, c, fkw, akw, sensor, mprior)
@@ -194,9 +212,10 @@ def test_lone_threshold_both_sides(oracle, monkeypatch):
         c["scale"] = oracle.info_scale_from_nopt(c["n_opt"])
     ctx = _context(monkeypatch)
     try:
-        for B in (2 * n_cu, 2 * n_cu + 1):
+        assert ops.dispatch_env(ctx).cus == n_cu
+        for B, gn in ((2 * n_cu, GN("4, 4, false, 4, 1, 1")), (2 * n_cu + 1, GN("4, 4, false, 4, 4, 1"))):  # the plan flips
             cases = [uniq[b % len(uniq)] for b in range(B)]
-            frames = _run_batch(ctx, cfg, cases, 256, {}, {})
+            frames = _run_batch(ctx, cfg, cases, 256, {}, {}, expect=[AK("512, true, 2, 8"), gn])
             for u, c in enumerate(uniq):
                 of, res, rcorr = _oracle_frame(oracle, cfg, c, {}, {})
                 _check_frame(frames, u, of, res, rcorr, "batch %d frame %d" % (B, u))

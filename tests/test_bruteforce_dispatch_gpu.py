@@ -1,14 +1,14 @@
 """Every kernel the brute-force matcher's dispatch can launch, on inputs that hold candidates, against the C oracle AND the plain-Python
 reference (tests/bruteforce_ref.py), through the device-resident batch entry of the C-ABI.
 
-bruteforce_batch_launch (csrc/bruteforce.hip) chooses among 15 kernels: bruteforce_kernel<KPT, MODE> for KPT 1 / 2 / 4 / 8 x
+bruteforce_plan (csrc/bruteforce.hip) chooses among 15 kernels: bruteforce_kernel<KPT, MODE> for KPT 1 / 2 / 4 / 8 x
 {fused, dense, register}, the two matrix-core fused shapes (1024 and 512 threads) and bruteforce_dense_mfma_kernel.  DISPATCH holds
 one row per path: the kernels it was written for (as a kernel trace prints them), a builder of its cloud pairs -- a row may size its
 batch by the device's CU count -- and what it claims to exercise.  Every row first asserts that tests/bruteforce_dispatch.py, the
-restatement of the host's choice, names the row's kernels for this device, then compares matches, their order, n_matches and status
+restatement of the host's choice, and the library's own plan name the row's kernels for this device, then compares matches, their order, n_matches and status
 of every pair bit for bit with the oracle, and of every pair (batches up to 16 pairs) or of the edge pairs and one pair in eight (larger
-batches) with the Python reference.  tests/test_bruteforce_dispatch_table.py checks without a GPU that the launch block names no
-kernel without a row and that every row holds the content it claims: candidates, pool conflicts, Lowe rejections, at least three
+batches) with the Python reference.  tests/test_bruteforce_dispatch_table.py checks without a GPU that the variant table names no
+kernel without a row, that the restatement equals the library's plan and that every row holds the content it claims: candidates, pool conflicts, Lowe rejections, at least three
 distance levels, candidate counts on the stated side of `cap` / `lvl_cap`, second row passes, segment drains and flushes."""
 import zlib
 
@@ -528,6 +528,8 @@ def test_dispatch_row(oracle, monkeypatch, r):
         for max_dist, ratio in case.launches:
             d = case.dispatch(cus, max_dist)
             assert d["refused"] is None and d["kernels"] == r["kernels"], (max_dist, d)
+            # ... and so does the library's own plan for these inputs on this context (host only)
+            assert ops.bruteforce_plan(ops.bruteforce_params(max_dist, ratio), clouds.descriptor(), ops.dispatch_env(ctx))["kernels"] == r["kernels"]
             clouds.n_matches.fill_(-7)
             clouds.status.fill_(-7)
             ops.bruteforce_match_batch(ctx, ops.bruteforce_params(max_dist, ratio), clouds)

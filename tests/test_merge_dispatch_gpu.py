@@ -4,7 +4,7 @@ inside a batch.  Each launch merges one frame into B DIFFERENT maps (tests/merge
 origins differ, measurement_in_scene != measurement_in_world) and every map is compared with the per-map CPU checker bit for bit
 (all map arrays, the pose table, the result triple); the rows of DISPATCH are also compared with the float64 restatement of
 tests/mapping_ref.py, with the constants of tests/test_mapping_ref.py.  tests/test_merge_dispatch_table.py keeps DISPATCH and the
-dispatch block of mapping.hip in step.
+library's variant table and plan (prs_merge_plan) in step.
 
 The tail kernel: the checker's test-only trace (oracle.binding_mapping.smoother_trace) tells which landmarks are still iterating,
 without a repeated state, after kTailRounds * 8 = 24 iterations; those are certain to be handed to smoother_tail_kernel.  With the
@@ -27,18 +27,29 @@ from tests.test_mapping_ref import assert_within
 
 pytestmark = pytest.mark.gpu
 
-# one row per instantiation merge_batch_launch can launch, with the knobs that select it.  index_map: the row's launches go
-# through scene_index_map and corr_from_aligner = 1 (one row per estimator; the depth form has tests/test_mapping_gpu.py)
+def MG(args):
+    """merge_kernel<EST, DIM, PHASE> as a kernel trace prints it (EST 0 = weighted mean, 1 = EKF, 2 = pose-based smoother)"""
+    return "void prs::merge_kernel<%s>(prs::MergeArgs)" % args
+
+
+# one row per instantiation merge_batch_launch can launch, with the knobs that select it (merge / smoother: the kernels by the
+# names a kernel trace prints).  index_map: the row's launches go through scene_index_map and corr_from_aligner = 1 (one row
+# per estimator; the depth form has tests/test_mapping_gpu.py)
 DISPATCH = [
-    {"id": "weighted_mean", "kind": "weighted_mean", "fused": False, "index_map": True, "merge": ["PRS_EST_WEIGHTED_MEAN,4,0"], "smoother": []},
-    {"id": "smoother_fused", "kind": "smoother", "fused": True, "index_map": False, "merge": ["PRS_EST_SMOOTHER,4,0"], "smoother": []},
-    {"id": "smoother_split", "kind": "smoother", "fused": False, "index_map": True, "merge": ["PRS_EST_SMOOTHER,4,1", "PRS_EST_SMOOTHER,4,2"],
-     "smoother": ["smoother_kernel", "smoother_tail_kernel"]},
-    {"id": "stereo_ekf", "kind": "stereo_ekf", "fused": False, "index_map": True, "merge": ["PRS_EST_EKF,4,0"], "smoother": []},
-    {"id": "depth_ekf", "kind": "depth_ekf", "fused": False, "index_map": False, "merge": ["PRS_EST_EKF,3,0"], "smoother": []},
-    {"id": "mono_ekf", "kind": "mono_ekf", "fused": False, "index_map": False, "merge": ["PRS_EST_EKF,2,0"], "smoother": []},
+    {"id": "weighted_mean", "kind": "weighted_mean", "fused": False, "index_map": True, "merge": [MG("0, 4, 0")], "smoother": []},
+    {"id": "smoother_fused", "kind": "smoother", "fused": True, "index_map": False, "merge": [MG("2, 4, 0")], "smoother": []},
+    {"id": "smoother_split", "kind": "smoother", "fused": False, "index_map": True, "merge": [MG("2, 4, 1"), MG("2, 4, 2")],
+     "smoother": ["prs::smoother_kernel(prs::MergeArgs)", "prs::smoother_tail_kernel(prs::MergeArgs)"]},
+    {"id": "stereo_ekf", "kind": "stereo_ekf", "fused": False, "index_map": True, "merge": [MG("1, 4, 0")], "smoother": []},
+    {"id": "depth_ekf", "kind": "depth_ekf", "fused": False, "index_map": False, "merge": [MG("1, 3, 0")], "smoother": []},
+    {"id": "mono_ekf", "kind": "mono_ekf", "fused": False, "index_map": False, "merge": [MG("1, 2, 0")], "smoother": []},
 ]
 ROW = {r["id"]: r for r in DISPATCH}
+
+
+def row_kernels(row):
+    """the row's launches in order: one merge_kernel, or front | smoother_kernel | smoother_tail_kernel | back"""
+    return row["merge"][:1] + row["smoother"] + row["merge"][1:]
 ROW_IDS = [r["id"] for r in DISPATCH]
 SMOOTHER_ROWS = ["smoother_fused", "smoother_split"]
 
@@ -272,6 +283,8 @@ def small_batch(kind, n_maps, n_frames=4, seed=500, n_world=(24, 56), **kw):
 def test_row_merges_distinct_maps_off_the_world_frame(oracle, row_ctx, row_id, binning):
     row = ROW[row_id]
     run = BatchRun(row_ctx(row), mc.merger_params(row["kind"], binning), mc.distinct_batch(row["kind"]), capacity=1600, index_map=row["index_map"])
+    # what the library plans for these inputs on this context (host only)
+    assert ops.merge_plan(run.pg, run.maps.descriptor(), ops.dispatch_env(run.ctx))["kernels"] == row_kernels(row)
     rcs = run.run(5, f64=True, what=row_id)
     assert all(rc == 0 for step in rcs for rc in step)
     assert_within(run.dev, "%s binning %d" % (row_id, binning))

@@ -1,10 +1,10 @@
 """Every instantiation the stereo matcher's dispatch can reach, against the C oracle, and the kernels' capacity and data-path edges.
 
-stereo_match_batch_launch (csrc/stereo_match.hip) and stereo_match_v5_launch (csrc/stereo_match_v5.hip) choose among
+stereo_plan (csrc/stereo_match.hip, with the v5 layout of csrc/stereo_match_v5.hip) chooses among
 stereo_match5_kernel<KPT, MULTI, EPI> (8), stereo_match_kernel<KPT, STAGE> (6) and, for prs_triangulate, triangulate_kernel.
 DISPATCH names one row per instantiation with the knobs that select it; tests/stereo_dispatch.py restates the host's choice and
-every row asserts that its knobs pick its variant; tests/test_stereo_dispatch_table.py checks (without a GPU) that the dispatch
-blocks name no instantiation without a row.  Every frame of every batch is compared with the oracle: correspondences including
+every row asserts that its knobs pick its variant; tests/test_stereo_dispatch_table.py checks (without a GPU) that the library's
+variant tables name no instantiation without a row and that the restatement equals the library's plan.  Every frame of every batch is compared with the oracle: correspondences including
 their order and response bits, status / warning bits and, with the fused epilogue, n_fixed and the bits of fixed_uvuv, fixed_desc
 and fixed_xyz (validity included).  The edge rows then pin the shape limits, the layout fallbacks, the acceptance table's
 extremes, the candidate pool (windows of four / five, pool partly used, pool exhausted and the replay sweep, pool_cap 64 / 0), the
@@ -88,12 +88,16 @@ def _assert_variant(d, kernel, args):
     assert d["refused"] is None and (d["kernel"], d["args"]) == (kernel, args), d
 
 
-def run_batch(ctx, m, rows, data, stride, epi, tp=None):
+def run_batch(ctx, m, rows, data, stride, epi, tp=None, expect=None):
+    """expect: (kernel, args) the library's plan for these inputs on this context must name (host only), before anything runs"""
     import torch
     frames = ops.StereoFrames(0, len(data), stride, epilogue=bool(epi))
     for b, fr in enumerate(data):
         frames.upload(b, fr["uv_left"], fr["desc_left"], fr["uv_right"], fr["desc_right"])
-    ops.stereo_match_batch(ctx, ops.stereo_params(m, rows), frames, (tp or _tri()) if epi else None)
+    params, tri = ops.stereo_params(m, rows), (tp or _tri()) if epi else None
+    if expect is not None:
+        assert ops.stereo_plan(params, frames.descriptor(tri), ops.dispatch_env(ctx))["kernels"] == [sd.trace_name(*expect)]
+    ops.stereo_match_batch(ctx, params, frames, tri)
     torch.cuda.synchronize()
     return frames
 
@@ -162,7 +166,7 @@ def test_dispatch_row_matches_oracle(oracle, make_ctx, row):
     _assert_variant(_expect(row["stride"], 376, m, row["epi"], row.get("v3", 0), row.get("unstaged", 0)), row["kernel"], row["args"])
     ctx = make_ctx(row.get("v3", 0), row.get("unstaged", 0))
     data = [kitti_like(1000 * len(row["id"]) + 17 * b + row["stride"], n, jitter=0.2 if row["thickness"] else 0.0) for b, n in enumerate(row["n"])]
-    frames = run_batch(ctx, m, 376, data, row["stride"], row["epi"])
+    frames = run_batch(ctx, m, 376, data, row["stride"], row["epi"], expect=(row["kernel"], row["args"]))
     assert check_batch(oracle, frames, data, m, row["epi"]) > 300
 
 
@@ -200,7 +204,7 @@ def test_shape_edges(oracle, make_ctx, stride, rows, thickness, kernel, args):
     ctx = make_ctx()
     ns = [stride, max(1, stride // 2 + 1), min(stride, 37)]
     data = [kitti_like(stride + rows + b, n, rows, jitter=0.2 if thickness else 0.0) for b, n in enumerate(ns)]
-    frames = run_batch(ctx, m, rows, data, stride, 1)
+    frames = run_batch(ctx, m, rows, data, stride, 1, expect=(kernel, args))
     assert check_batch(oracle, frames, data, m, 1) > min(stride, 300) // 3
 
 
