@@ -121,7 +121,8 @@ PRS_API int prs_version(void);
  * prs_reentry_params, prs_reentry_batch, prs_session_step_archive_batch, prs_session_reenter_batch and
  * prs_map_archive_struct_sizes; and the dispatch plans for tests and tools: prs_dispatch_env,
  * prs_dispatch_plan, prs_context_get_dispatch_env, the prs_*_plan entry points, prs_dispatch_kernel_name and
- * prs_dispatch_struct_sizes).  Callers memset() parameter structs before
+ * prs_dispatch_struct_sizes; and the trajectory evaluator: prs_trajectory_params, prs_trajectory_result, prs_trajectory_batch,
+ * prs_trajectory_eval_batch and prs_trajectory_struct_sizes).  Callers memset() parameter structs before
  * filling them, so that fields they do not know select the shipped defaults (all zero). */
 #define PRS_ABI_VERSION 104
 PRS_API int prs_abi_check(int32_t header_version, uint64_t sizeof_stereo_params, uint64_t sizeof_pcf_params, uint64_t sizeof_aligner_params,
@@ -1937,6 +1938,102 @@ PRS_API int prs_merge_plan(const prs_merger_params* params, const prs_merge_batc
 PRS_API const char* prs_dispatch_kernel_name(int32_t family, int32_t index);
 /* sizeof prs_dispatch_env, prs_dispatch_plan as the library was compiled (bindings check) */
 PRS_API void prs_dispatch_struct_sizes(uint64_t* sizes2);
+
+/* ================================================================================================
+ * Trajectory evaluator: ATE, RPE and the KITTI metric of B trajectories against ground truth, on the device
+ * stands where the reference's five benchmarks/benchmark_*.cpp feed every pose to a benchmark suite and fail on
+ * isRegression(mean / std translation, mean / std rotation) (benchmark_kitti.cpp:17-20 and its four siblings).  It reads the layout
+ * prs_session_unroll_batch writes, in place: one launch after the unroll gives one figure of merit per sequence without a host read.
+ *
+ * BUILD-DEFINED: the suite (srrg_benchmark) is not in the tree, so nothing below is the reference's own definition.  The metrics are
+ * the published ones: the absolute trajectory error after a closed-form rigid alignment (Horn 1987 / Umeyama 1991 without scale) and
+ * the fixed-delta relative pose error as TUM's evaluate_ate.py / evaluate_rpe.py state them (Sturm et al., IROS 2012), and the KITTI
+ * odometry devkit's subsequence errors (evaluate_odometry.cpp: trajectoryDistances, lastFrameFromSegmentLength, calcSequenceErrors).
+ * Ours, not theirs: the rotation angle by atan2 where both use acos; the rigid inverse [R^T | -R^T t] for every inverse; path_length
+ * and the per-axis block, which exists so that the four Vector3f thresholds of the reference's benchmarks have a counterpart;
+ * population standard deviations; the treatment of invalid rows.  tests/trajectory_ref.py restates all of it in numpy.
+ *
+ * All arithmetic is float64 on the float32 inputs.  P_k is the estimate's row k, G_k the ground truth's, n = min(n_frames[b],
+ * frame_stride); a row counts when k < n and valid[b][k] != 0 (no valid array: every row).  t(X) is the translation, R(X) the rotation.
+ *   alignment   NONE: S = I.  FIRST: S = G_f P_f^-1 at the first valid row f.  RIGID: S = [R | c_G - R c_P] with c_P, c_G the
+ *               centroids of the valid rows' translations and R the proper rotation (det = +1) that minimises sum |t(G_k) - S t(P_k)|^2:
+ *               both clouds are centred in float64, M = sum (t(P_k) - c_P)(t(G_k) - c_G)^T, and R is the rotation of the unit
+ *               quaternion that is the eigenvector of the largest eigenvalue of Horn's symmetric 4x4 N(M) (cyclic Jacobi, 12 sweeps).
+ *               A quaternion gives a proper rotation also where the unconstrained optimum is a reflection.  Collinear (or coincident)
+ *               clouds are NOT detected: the largest eigenvalue is then repeated and R is one of the minimisers, whichever the
+ *               iteration lands on.  Fewer than 3 valid rows under RIGID, or none under FIRST: result[b].status = PRS_ERR_RANGE,
+ *               n_valid is written, n_rpe = n_kitti = 0, every metric is 0, S = I and frame_error[b][..] = -1.
+ *   ATE         e_k = |t(G_k) - S t(P_k)| over the valid rows: rmse, mean, max.  frame_error[b][k] = (float) e_k, -1 for every other
+ *               row k < frame_stride.
+ *   path_length sum of |t(G_k) - t(G_k-1)| over the k for which rows k and k - 1 are both valid.
+ *   RPE         for every k with k + rpe_delta < n and both rows valid (n_rpe of them): dG = G_k^-1 G_k+d, dP = P_k^-1 P_k+d,
+ *               E = dG^-1 dP, with X^-1 Y = [Rx^T Ry | Rx^T (ty - tx)].  Translation error |t(E)|; rotation error theta =
+ *               atan2(|v| / 2, (tr R(E) - 1) / 2) with v = (R21 - R12, R02 - R20, R10 - R01) (|v| = 2 sin theta; no acos, which
+ *               loses half the digits at small angles): rmse, mean, max of each.
+ *   axis block  over the same pairs, mean and population standard deviation of |t(E)_i| (metres) and of |theta v_i / |v|| in degrees
+ *               (0 when |v| = 0), i = x, y, z: accumulated as running means and squared deviations (Welford) and merged pairwise
+ *               (Chan), so that a deviation far below the mean keeps its digits.  Within about 1e-6 rad of a half turn v is the
+ *               difference of nearly equal numbers and vanishes at the half turn itself: theta stays accurate there, the DIRECTION
+ *               does not, and the rotation components of the axis block are then meaningless (0 at |v| = 0).
+ *   KITTI       only when kitti_step > 0, n > 0 and every row k < n is valid; n_kitti = 0 and zeros otherwise.  dist[k] = sum of
+ *               |t(G_j) - t(G_j-1)| for 0 < j <= k, kept in workspace[b] (a block prefix sum in a fixed order).  For first = 0,
+ *               kitti_step, 2 kitti_step, ... < n and each length L: last = the first index i with dist[i] > dist[first] + L (the
+ *               devkit's linear scan; found by bisection, the same index on a non-decreasing array); no such index: the pair is
+ *               skipped.  E as in RPE between rows first and last, t_err = |t(E)| / L, r_err = theta / L.  kitti_t / kitti_r are the
+ *               means over all subsequences (a ratio; rad / m), kitti_*_len[i] the same per length, kitti_n_len[i] their number.
+ * status per sequence: PRS_ERR_RANGE for n_frames[b] < 0 (treated as the alignment failure above, n_valid = 0) and for the alignment
+ * failures; PRS_OK otherwise.  A sequence never writes outside its rows of result, frame_error and workspace.
+ * Call-level (return value, nothing launched, outputs untouched): PRS_ERR_NULL (params, batch, estimate, ground_truth, n_frames or
+ * result unset, or workspace unset with kitti_step > 0); PRS_ERR_RANGE (batch or frame_stride < 1, rpe_delta < 1, kitti_step < 0,
+ * n_lengths outside 0..8, a length that is not finite, not positive or not above the one before it, an unknown align);
+ * PRS_ERR_UNSUPPORTED (estimate or ground_truth not 16-byte aligned, result or workspace not 8-byte aligned).
+ * One launch, one 512-thread workgroup per sequence, no allocation, no synchronisation, no host read: graph-capturable.  Every sum is
+ * a fixed-order reduction (per-thread strided partials, wave shuffles, a tree over the waves in LDS) and there are no floating-point
+ * atomics: a sequence's result bytes depend neither on the batch around it nor on the run.  The translations of both clouds (24
+ * bytes a row) are staged in LDS once for the centroid, covariance, residual and distance passes while frame_stride <= 6400, and a
+ * copy of dist beside them for the subsequence search while frame_stride <= 4800; beyond, the passes read global memory (same
+ * arithmetic, same bytes).
+ * ============================================================================================== */
+enum { PRS_TRAJ_ALIGN_NONE = 0, PRS_TRAJ_ALIGN_FIRST = 1, PRS_TRAJ_ALIGN_RIGID = 2 };
+
+typedef struct {
+  int32_t align;        /* PRS_TRAJ_ALIGN_*: how the estimate is brought into the ground truth's frame before ATE */
+  int32_t rpe_delta;    /* frames between the two ends of a relative pose, >= 1 */
+  int32_t kitti_step;   /* a subsequence starts every kitti_step rows (devkit: 10); 0 skips the KITTI block */
+  int32_t n_lengths;    /* 0 .. 8 */
+  float   lengths[8];   /* metres, ascending (devkit: 100 .. 800) */
+} prs_trajectory_params;
+
+typedef struct {
+  int32_t status, n_valid, n_rpe, n_kitti;
+  double  S[16];                                   /* estimate -> ground-truth frame, as applied (row-major 4x4) */
+  double  path_length;                             /* of the ground truth, metres */
+  double  ate_rmse, ate_mean, ate_max;             /* metres */
+  double  rpe_t_rmse, rpe_t_mean, rpe_t_max;       /* metres */
+  double  rpe_r_rmse, rpe_r_mean, rpe_r_max;       /* radians */
+  double  axis_t_mean[3], axis_t_std[3];           /* metres; |component| of the relative translation error */
+  double  axis_r_mean[3], axis_r_std[3];           /* degrees; |component| of the relative rotation error's rotation vector */
+  double  kitti_t, kitti_r;                        /* mean of t_err / len (ratio) and r_err / len (rad / m) over all subsequences */
+  double  kitti_t_len[8], kitti_r_len[8];          /* the same means per length */
+  int32_t kitti_n_len[8];
+} prs_trajectory_result;
+
+/* device pointers */
+typedef struct {
+  int32_t batch, frame_stride;
+  const float*   estimate;      /* [batch][frame_stride][16], the layout prs_session_unroll_batch writes */
+  const float*   ground_truth;  /* same layout, row k belongs to estimate row k */
+  const int32_t* n_frames;      /* [batch]; clamped to frame_stride as the unroll clamps it */
+  const uint8_t* valid;         /* optional [batch][frame_stride]; 0 = row has no ground truth or no estimate */
+  prs_trajectory_result* result;/* out [batch], 8-byte aligned */
+  float*  frame_error;          /* optional out [batch][frame_stride]: ATE residual per row, -1 where not valid */
+  double* workspace;            /* [batch][frame_stride], needed when kitti_step > 0 */
+} prs_trajectory_batch;
+
+/* asynchronous on the context's stream: one kernel launch */
+PRS_API int prs_trajectory_eval_batch(prs_context* ctx, const prs_trajectory_params* params, const prs_trajectory_batch* batch);
+/* sizeof prs_trajectory_params, prs_trajectory_result, prs_trajectory_batch as the library was compiled (bindings check) */
+PRS_API void prs_trajectory_struct_sizes(uint64_t* sizes3);
 
 #ifdef __cplusplus
 }

@@ -467,6 +467,33 @@ class ReentryBatch(C.Structure):
                 ("scene_in_world", C.c_void_p), ("gate", C.c_void_p)]
 
 
+TRAJ_ALIGN_NONE, TRAJ_ALIGN_FIRST, TRAJ_ALIGN_RIGID = 0, 1, 2  # PRS_TRAJ_ALIGN_*
+
+
+class TrajectoryParams(C.Structure):
+    """prs_trajectory_params"""
+    _fields_ = [("align", C.c_int32), ("rpe_delta", C.c_int32), ("kitti_step", C.c_int32), ("n_lengths", C.c_int32),
+                ("lengths", C.c_float * 8)]
+
+
+class TrajectoryResult(C.Structure):
+    """prs_trajectory_result"""
+    _fields_ = [("status", C.c_int32), ("n_valid", C.c_int32), ("n_rpe", C.c_int32), ("n_kitti", C.c_int32), ("S", C.c_double * 16),
+                ("path_length", C.c_double), ("ate_rmse", C.c_double), ("ate_mean", C.c_double), ("ate_max", C.c_double),
+                ("rpe_t_rmse", C.c_double), ("rpe_t_mean", C.c_double), ("rpe_t_max", C.c_double),
+                ("rpe_r_rmse", C.c_double), ("rpe_r_mean", C.c_double), ("rpe_r_max", C.c_double),
+                ("axis_t_mean", C.c_double * 3), ("axis_t_std", C.c_double * 3), ("axis_r_mean", C.c_double * 3),
+                ("axis_r_std", C.c_double * 3), ("kitti_t", C.c_double), ("kitti_r", C.c_double), ("kitti_t_len", C.c_double * 8),
+                ("kitti_r_len", C.c_double * 8), ("kitti_n_len", C.c_int32 * 8)]
+
+
+class TrajectoryBatch(C.Structure):
+    """prs_trajectory_batch (device pointers)"""
+    _fields_ = [("batch", C.c_int32), ("frame_stride", C.c_int32), ("estimate", C.c_void_p), ("ground_truth", C.c_void_p),
+                ("n_frames", C.c_void_p), ("valid", C.c_void_p), ("result", C.c_void_p), ("frame_error", C.c_void_p),
+                ("workspace", C.c_void_p)]
+
+
 class DispatchEnv(C.Structure):
     """prs_dispatch_env: what a dispatch depends on outside its arguments (tests and tools)"""
     _fields_ = [(n, C.c_int32) for n in ("cus", "fused_align", "matcher_v3", "force_unstaged", "no_lone_gn", "merge_fused", "bf_mfma", "stamps",
@@ -618,6 +645,8 @@ SYMBOLS = {
     "prs_merge_plan": (C.c_int, [C.POINTER(MergerParams), C.POINTER(MergeBatch), C.POINTER(DispatchEnv), C.POINTER(DispatchPlan)]),
     "prs_dispatch_kernel_name": (C.c_char_p, [C.c_int32, C.c_int32]),
     "prs_dispatch_struct_sizes": (None, [C.POINTER(C.c_uint64)]),
+    "prs_trajectory_eval_batch": (C.c_int, [_vp, C.POINTER(TrajectoryParams), C.POINTER(TrajectoryBatch)]),
+    "prs_trajectory_struct_sizes": (None, [C.POINTER(C.c_uint64)]),
     "prs_scene_clip_batch": (C.c_int, [_vp, C.POINTER(Projector), _vp, C.POINTER(ClipBatch)]),
     "prs_scene_clip": (C.c_int, [_vp, C.POINTER(Projector), _vp, _vp, _vp, _vp, C.c_int32, _vp, _vp, _vp, C.c_int32, _i32p]),
 }
@@ -674,5 +703,11 @@ def load():
         raise ImportError("libproslam_hip.so lays out prs_dispatch_env / prs_dispatch_plan as %s bytes, the Python binding as %s: rebuild "
                           "with `python -c 'import __graft_entry__ as g; g.build()'`"
                           % (list(sizes), [C.sizeof(DispatchEnv), C.sizeof(DispatchPlan)]))
+    sizes = (C.c_uint64 * 3)()
+    lib.prs_trajectory_struct_sizes(sizes)
+    if list(sizes) != [C.sizeof(TrajectoryParams), C.sizeof(TrajectoryResult), C.sizeof(TrajectoryBatch)]:
+        raise ImportError("libproslam_hip.so lays out prs_trajectory_params / prs_trajectory_result / prs_trajectory_batch as %s bytes, "
+                          "the Python binding as %s: rebuild with `python -c 'import __graft_entry__ as g; g.build()'`"
+                          % (list(sizes), [C.sizeof(TrajectoryParams), C.sizeof(TrajectoryResult), C.sizeof(TrajectoryBatch)]))
     _lib = lib
     return lib

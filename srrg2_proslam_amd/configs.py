@@ -222,6 +222,38 @@ REENTRY = {
 }
 
 
+def _gate(mean_t, std_t, mean_r, std_r, where):
+    return {"mean_translation": (mean_t,) * 3, "std_translation": (std_t,) * 3, "mean_rotation": (mean_r,) * 3,
+            "std_rotation": (std_r,) * 3, "source": where}
+
+
+# maximum_mean_translation_rmse, maximum_standard_deviation_translation_rmse (metres), maximum_mean_rotation_rmse,
+# maximum_standard_deviation_rotation_rmse (degrees): the four Vector3f each benchmark program hands to isRegression
+BENCHMARK_GATES = {
+    "kitti": _gate(0.3, 1.0, 3, 3, "benchmarks/benchmark_kitti.cpp:17-20"),
+    "icl": _gate(0.02, 0.1, 3, 3, "benchmarks/benchmark_icl.cpp:17-20"),
+    "tum": _gate(0.05, 0.25, 3, 3, "benchmarks/benchmark_tum.cpp:17-20"),
+    "euroc": _gate(0.5, 0.5, 3, 3, "benchmarks/benchmark_euroc.cpp:17-20"),
+    "malaga": _gate(25, 10, 3, 3, "benchmarks/benchmark_malaga.cpp:17-20"),
+}
+
+
+def is_regression(result, gate):
+    """True when a trajectory evaluator result (ops.TrajectoryEvalBatch.results) exceeds one of a benchmark's thresholds in any axis:
+    axis_t_mean against mean_translation, axis_t_std against std_translation, axis_r_mean against mean_rotation, axis_r_std against
+    std_rotation; also True for a result without relative poses or with an error status (nothing was measured).
+    BUILD-DEFINED: the benchmark suite that owns isRegression and the statistics it compares is not in the reference tree.  The
+    thresholds are the reference's; what they are compared with -- mean and population standard deviation of the absolute components
+    of the relative pose error, metres and degrees -- is this build's reading of their names."""
+    if isinstance(gate, str):
+        gate = BENCHMARK_GATES[gate]
+    if result["status"] < 0 or result["n_rpe"] < 1:
+        return True
+    pairs = (("axis_t_mean", "mean_translation"), ("axis_t_std", "std_translation"), ("axis_r_mean", "mean_rotation"),
+             ("axis_r_std", "std_rotation"))
+    return any(not (float(result[field][i]) <= gate[limit][i]) for field, limit in pairs for i in range(3))
+
+
 def get(name):
     return copy.deepcopy(CONFIGS[name])
 

@@ -134,6 +134,29 @@ def read_trajectory_tum(path):
     return np.array(stamps), np.array(poses).reshape(-1, 4, 4)
 
 
+def associate(stamps_est, stamps_gt, max_difference=0.02):
+    """TUM's association (associate.py) of an estimate's time stamps with a ground truth's: every pair closer than max_difference is a
+    candidate, candidates are taken nearest first, and a stamp of either side is used once.  -> (gt_row int64 [n_est], the ground
+    truth's row for each row of the estimate or -1, valid uint8 [n_est]).  gt[gt_row] with the mask is what the trajectory
+    evaluator takes (ops.TrajectoryEvalBatch.set_ground_truth): the ICL / TUM / EuRoC route, whose ground truth has its own clock."""
+    est = np.asarray(stamps_est, np.float64).reshape(-1)
+    gt = np.asarray(stamps_gt, np.float64).reshape(-1)
+    order = np.argsort(gt, kind="stable")
+    sgt = gt[order]
+    lo = np.searchsorted(sgt, est - max_difference, side="left")
+    hi = np.searchsorted(sgt, est + max_difference, side="right")
+    cand = [(abs(est[i] - sgt[j]), i, int(order[j])) for i in range(est.size) for j in range(lo[i], hi[i])
+            if abs(est[i] - sgt[j]) < max_difference]
+    cand.sort()
+    gt_row = np.full(est.size, -1, np.int64)
+    used = np.zeros(gt.size, bool)
+    for _, i, j in cand:
+        if gt_row[i] < 0 and not used[j]:
+            gt_row[i] = j
+            used[j] = True
+    return gt_row, (gt_row >= 0).astype(np.uint8)
+
+
 # ---------------------------------------------------------------- .conf reader (subset)
 def _strip_line_comments(text):
     out, in_string, i = [], False, 0

@@ -1854,6 +1854,134 @@ class SessionBatch:
                     frame_pose=self.frame_pose[b, :n].cpu().numpy().reshape(-1, 4, 4).copy())
 
 
+# ---- trajectory evaluator: ATE, RPE and the KITTI metric on the device (include/proslam_hip.h prs_trajectory_*) ----
+TRAJ_ALIGN = {"none": _lib.TRAJ_ALIGN_NONE, "first": _lib.TRAJ_ALIGN_FIRST, "rigid": _lib.TRAJ_ALIGN_RIGID}
+KITTI_LENGTHS = (100, 200, 300, 400, 500, 600, 700, 800)  # the devkit's
+_TRAJ_NP = {C.c_int32: np.int32, C.c_double: np.float64}
+_TRAJ_RESULT_DTYPE = np.dtype([(name, _TRAJ_NP[ct._type_], (ct._length_,)) if hasattr(ct, "_length_") else (name, _TRAJ_NP[ct])
+                               for name, ct in _lib.TrajectoryResult._fields_])
+assert _TRAJ_RESULT_DTYPE.itemsize == C.sizeof(_lib.TrajectoryResult)
+
+
+def trajectory_params(align="rigid", rpe_delta=1, kitti_step=10, lengths=KITTI_LENGTHS):
+    """prs_trajectory_params: align "none" / "first" / "rigid" (or a PRS_TRAJ_ALIGN_* value), the frames between the two ends of a
+    relative pose, and the KITTI block's start step (0 skips it) and lengths in metres (the defaults are the devkit's)"""
+    p = _lib.TrajectoryParams()
+    p.align = TRAJ_ALIGN[align] if isinstance(align, str) else int(align)
+    p.rpe_delta, p.kitti_step = int(rpe_delta), int(kitti_step)
+    if len(lengths) > 8:
+        raise ValueError("at most 8 lengths")
+    p.n_lengths = len(lengths)
+    for i, v in enumerate(lengths):
+        p.lengths[i] = v
+    return p
+
+
+def _rows16(poses):
+    """[n, 4, 4], [n, 16] or [n, 12] (KITTI rows) -> float32 [n, 16]"""
+    a = np.asarray(poses, np.float32)
+    a = a.reshape(a.shape[0], -1) if a.ndim == 3 else a
+    if a.shape[1] == 12:
+        a = np.concatenate([a, np.tile(np.array([[0, 0, 0, 1]], np.float32), (a.shape[0], 1))], axis=1)
+    if a.ndim != 2 or a.shape[1] != 16:
+        raise ValueError("poses must be [n, 4, 4], [n, 16] or [n, 12]")
+    return np.ascontiguousarray(a)
+
+
+def _traj_result_dict(rec):
+    d = {name: (rec[name].copy() if rec[name].ndim else rec[name].item()) for name in _TRAJ_RESULT_DTYPE.names}
+    d["S"] = d["S"].reshape(4, 4)
+    return d
+
+
+class TrajectoryEvalBatch:
+    """B trajectories and their ground truth resident in HBM, in the layout prs_session_unroll_batch writes ([B, frame_stride, 16]).
+    Owns ground_truth, valid, result, frame_error and workspace; estimate and n_frames are its own too unless from_session() bound
+    a SessionBatch's trajectory and n_frames in place.  with_valid=False passes no valid array: every row k < n_frames[b] counts."""
+
+    def __init__(self, device, batch, frame_stride, with_valid=True, estimate=None, n_frames=None):
+        import torch
+        dev = torch.device("cuda", device)
+        self.batch, self.frame_stride = int(batch), int(frame_stride)
+        B, F = self.batch, self.frame_stride
+        z = lambda shape, dt: torch.zeros(shape, dtype=dt, device=dev)  # noqa: E731
+        self.estimate = estimate if estimate is not None else z((B, F, 16), torch.float32)
+        self.n_frames = n_frames if n_frames is not None else z((B,), torch.int32)
+        self.ground_truth = z((B, F, 16), torch.float32)
+        self.valid = torch.ones((B, F), dtype=torch.uint8, device=dev) if with_valid else None
+        self.result = z((B, C.sizeof(_lib.TrajectoryResult)), torch.uint8)
+        self.frame_error = z((B, F), torch.float32)
+        self.workspace = z((B, F), torch.float64)
+
+    @classmethod
+    def from_session(cls, sess, with_valid=True):
+        """evaluates sess.trajectory (what SessionBatch.unroll writes) over sess.n_frames rows, in place: no copy"""
+        return cls(sess.trajectory.device.index, sess.batch, sess.frame_stride, with_valid=with_valid, estimate=sess.trajectory,
+                   n_frames=sess.n_frames)
+
+    def set_ground_truth(self, b, poses, valid=None):
+        """uploads sequence b's ground truth, row k for estimate row k; rows from len(poses) on count as having none.  valid: optional
+        [len(poses)] mask, e.g. formats.associate's"""
+        import torch
+        rows = _rows16(poses)
+        n = rows.shape[0]
+        if n > self.frame_stride:
+            raise ValueError("more ground-truth rows than frame_stride")
+        self.ground_truth[b, :n] = torch.from_numpy(rows).to(self.ground_truth.device)
+        if self.valid is not None:
+            self.valid[b] = 0
+            v = np.ones(n, np.uint8) if valid is None else (np.asarray(valid).reshape(n) != 0).astype(np.uint8)
+            self.valid[b, :n] = torch.from_numpy(v).to(self.valid.device)
+        elif valid is not None:
+            raise ValueError("this batch was made with_valid=False")
+
+    def set_estimate(self, b, poses):
+        """uploads sequence b's estimate and sets n_frames[b] (for trajectories that do not come from a session)"""
+        import torch
+        rows = _rows16(poses)
+        n = rows.shape[0]
+        if n > self.frame_stride:
+            raise ValueError("more rows than frame_stride")
+        self.estimate[b, :n] = torch.from_numpy(rows).to(self.estimate.device)
+        self.n_frames[b] = n
+
+    def descriptor(self):
+        d = _lib.TrajectoryBatch()
+        d.batch, d.frame_stride = self.batch, self.frame_stride
+        d.estimate, d.ground_truth, d.n_frames = self.estimate.data_ptr(), self.ground_truth.data_ptr(), self.n_frames.data_ptr()
+        d.valid = self.valid.data_ptr() if self.valid is not None else None
+        d.result, d.frame_error, d.workspace = self.result.data_ptr(), self.frame_error.data_ptr(), self.workspace.data_ptr()
+        return d
+
+    def evaluate(self, ctx, params):
+        """enqueue the evaluation of every sequence (asynchronous, one launch); per-sequence status lands in the results"""
+        d = self.descriptor()
+        rc = _lib.load().prs_trajectory_eval_batch(ctx._h, C.byref(params), C.byref(d))
+        _check(ctx, rc, "prs_trajectory_eval_batch")
+        return rc
+
+    def results(self):
+        """the B results as dicts (field names of prs_trajectory_result, S as [4, 4]); copies `result` to the host when called"""
+        rec = np.frombuffer(self.result.cpu().numpy().tobytes(), dtype=_TRAJ_RESULT_DTYPE)
+        return [_traj_result_dict(rec[b]) for b in range(self.batch)]
+
+
+def trajectory_eval(ctx, params, estimate, ground_truth, valid=None):
+    """one sequence from host arrays ([n, 4, 4], [n, 16] or [n, 12] each, row k of one for row k of the other) -> the result dict plus
+    "frame_error" (float32 [n], -1 where the row is not valid)"""
+    est, gt = _rows16(estimate), _rows16(ground_truth)
+    if est.shape != gt.shape:
+        raise ValueError("estimate and ground truth must have the same number of rows")
+    n = est.shape[0]
+    ev = TrajectoryEvalBatch(ctx.device, 1, max(n, 1), with_valid=valid is not None)
+    ev.set_estimate(0, est)
+    ev.set_ground_truth(0, gt, valid)
+    ev.evaluate(ctx, params)
+    out = ev.results()[0]
+    out["frame_error"] = ev.frame_error[0, :n].cpu().numpy().copy()
+    return out
+
+
 # ---- map re-entry: archive finished maps, reload one on a closure (include/proslam_hip.h prs_map_archive, prs_session_reenter_batch) ----
 def reentry_params(group, **overrides):
     """prs_reentry_params from a configs.REENTRY group (MultiRelocalizer3D's own values); overrides by field name"""
