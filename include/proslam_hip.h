@@ -84,6 +84,13 @@ PRS_API int prs_context_get_align_timing(prs_context* ctx, double* search_ms, do
 /* the same sums by round of the batch: search_ms16[r] / gn_ms16[r] = total time of the r-th search / Gauss-Newton launch over
  * `batches` timed batches (round 15 collects every later round) */
 PRS_API int prs_context_get_align_round_timing(prs_context* ctx, double* search_ms16, double* gn_ms16, int64_t* batches);
+/* diagnostic, for tests and profiles: which path the later projective searches of the context's LAST FINISHED aligner batch
+ * took (a batch that ran the fused kernel reports 0 / 0, whatever a split batch before it counted). A later search of a frame loop settles a query from the frame's query cache (a hit: its cell rectangle lies inside the
+ * one its last pruned scan covered) or scans it again (a miss); both are summed over the batch's frames and later searches.  0 / 0
+ * when no search read the cache: PRS_NO_SEARCH_REUSE=1, the KD-tree finder, eight survivor slots, unpruned searches, the fused
+ * kernel.  One device-to-host copy of the frame control words and a stream synchronise; PRS_ERR_UNSUPPORTED while a batch is
+ * enqueued and not finished.  Results never depend on the path. */
+PRS_API int prs_context_get_search_reuse(prs_context* ctx, int64_t* hits, int64_t* misses);
 /* Dense phase of the brute-force matcher (prs_bruteforce_match_batch): which kernels score the N_f x N_m pairs.  Results are
  * identical; only the cost differs.
  *   PRS_BF_DENSE_MATRIX_WHEN_FULL (the default): a batch of 32 or more cloud pairs (of at least 256 x 64 points) runs one workgroup
@@ -122,7 +129,8 @@ PRS_API int prs_version(void);
  * prs_map_archive_struct_sizes; and the dispatch plans for tests and tools: prs_dispatch_env,
  * prs_dispatch_plan, prs_context_get_dispatch_env, the prs_*_plan entry points, prs_dispatch_kernel_name and
  * prs_dispatch_struct_sizes; and the trajectory evaluator: prs_trajectory_params, prs_trajectory_result, prs_trajectory_batch,
- * prs_trajectory_eval_batch and prs_trajectory_struct_sizes).  Callers memset() parameter structs before
+ * prs_trajectory_eval_batch and prs_trajectory_struct_sizes; and the search's query-cache read-out prs_context_get_search_reuse
+ * with prs_dispatch_env::no_search_reuse at the end of that tests-and-tools struct).  Callers memset() parameter structs before
  * filling them, so that fields they do not know select the shipped defaults (all zero). */
 #define PRS_ABI_VERSION 104
 PRS_API int prs_abi_check(int32_t header_version, uint64_t sizeof_stereo_params, uint64_t sizeof_pcf_params, uint64_t sizeof_aligner_params,
@@ -1893,6 +1901,7 @@ typedef struct {
   int32_t stamps_split;      /* PRS_STAMPS_SPLIT */
   int32_t bf_global_state;   /* PRS_BF_GLOBAL_STATE is set (read from the environment per launch) */
   int32_t bf_two_workgroups; /* PRS_BF_TWO_WORKGROUPS: -1 unset, 0, 1 (read from the environment per launch) */
+  int32_t no_search_reuse;   /* PRS_NO_SEARCH_REUSE (appended with prs_context_get_search_reuse) */
 } prs_dispatch_env;
 PRS_API int prs_context_get_dispatch_env(const prs_context* ctx, prs_dispatch_env* env);
 

@@ -497,7 +497,7 @@ class TrajectoryBatch(C.Structure):
 class DispatchEnv(C.Structure):
     """prs_dispatch_env: what a dispatch depends on outside its arguments (tests and tools)"""
     _fields_ = [(n, C.c_int32) for n in ("cus", "fused_align", "matcher_v3", "force_unstaged", "no_lone_gn", "merge_fused", "bf_mfma", "stamps",
-                                         "stamps_split", "bf_global_state", "bf_two_workgroups")]
+                                         "stamps_split", "bf_global_state", "bf_two_workgroups", "no_search_reuse")]
 
 
 class PlanLaunch(C.Structure):
@@ -541,6 +541,7 @@ SYMBOLS = {
     "prs_context_set_bruteforce_dense_phase": (C.c_int, [_vp, C.c_int32]),
     "prs_context_get_align_timing": (C.c_int, [_vp, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "prs_context_get_align_round_timing": (C.c_int, [_vp, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int64)]),
+    "prs_context_get_search_reuse": (C.c_int, [_vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "prs_last_error": (C.c_char_p, [_vp]),
     "prs_stereo_match": (C.c_int, [_vp, C.POINTER(StereoParams), _vp, _vp, C.c_int32, _vp, _vp, C.c_int32, _vp, C.c_int32, _i32p]),
     "prs_stereo_match_batch": (C.c_int, [_vp, C.POINTER(StereoParams), C.POINTER(StereoBatch)]),

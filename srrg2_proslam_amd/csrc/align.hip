@@ -59,6 +59,8 @@ struct AlignShared {
   float chi_in, chi_tot, mean_disp, change_norm, dd;
   float kd_range;   // KD-tree finder: the search radius _initializeDatabase last ran with (leaf range of the tree)
   int kd_nodes, kd_leaves, kd_open_next;  // KD-tree build counters
+  int q_tag;        // query cache of the split search: low half = the tag the frame's entries were written with (FrameCtl::q_tag as the search
+                    // now running met it), high half = the tag that search writes (thread 0's, moved down behind the search)
   unsigned long long radius, it;
   unsigned long long stamp_acc[9], stamp_mark, stamp_sub;  // PRS_STAMPS phase timers of thread 0 (in LDS: no registers when they are off)
   int converged, config_changed, num_recomputes;
@@ -69,8 +71,10 @@ struct AlignShared {
   int no_prune;     // the finder's hint (prs_pcf_state.reserved bit 0): this sequence's descriptor rows are correlated, do not prune
   int have_cls;     // the last executed iteration linearised (cls[] holds its factor classes)
   int wave_tot[16];
+  int q_miss;       // query cache of the split search (AlignArgs::qcache): length of this search's miss queue
 };
 
+static_assert(sizeof(AlignShared) == 832, "the largest max_fixed of the fused kernel fills the 160 KiB of LDS to the byte: new fields go where padding was (q_tag, q_miss), so that no other field moves");
 static_assert(offsetof(AlignShared, b) == offsetof(AlignShared, H) + 36 * sizeof(float) && offsetof(AlignShared, chi_in) == offsetof(AlignShared, b) + 6 * sizeof(float) &&
                 offsetof(AlignShared, chi_tot) == offsetof(AlignShared, chi_in) + sizeof(float),
               "the summed slots are written through AlignShared::H");
@@ -84,6 +88,8 @@ struct FrameCtl {
   int flags;        // OR of finder warnings over the frame loop
   int n_inl, n_out, n_inv;
   int db_ready;     // the lattice of this frame's fixed cloud is in AlignArgs::dbcache, its descriptor rows in AlignArgs::rowcache (left by an earlier search launch)
+  int q_tag;        // AlignArgs::qcache holds this frame's entries, written with this bound (prune_at | compared words << 8); 0 = none.  Ends with db_ready
+  int q_hits, q_misses;  // diagnostic: queries the later searches of this frame loop settled from the cache / scanned
 };
 constexpr int kModeSplitSearch = 100;  // internal: align_kernel<512> performing ONE finder.compute() for frames that wait for it
 constexpr int kSearchThreads   = 512;
@@ -114,6 +120,11 @@ struct AlignArgs {
   uint32_t off_u;                                              // phase-exclusive union region:
   uint32_t off_fdesc, off_fuv, off_best, off_second, off_lut, off_surv;  //   search phase (relative to the LDS base)
   uint32_t off_terms;                                          //   GN phase / database build / disparity column
+  // (the query cache's two pointers stand behind everything else: the kernels that do not read them load their arguments as before)
+  au32x4* qcache;          // split pipeline, lattice patterns with four survivor slots: [batch][moving_stride] what each query's last pruned scan
+                           // covered and kept (x: cell rectangle cx0 | cx1 << 8 | cy0 << 16 | cy1 << 24, y: survivors + 1 or 0 = invalid,
+                           // z, w: four lattice positions); NULL = every search scans (PRS_NO_SEARCH_REUSE=1, other finders, no memory)
+  uint16_t* missq;         // [batch][moving_stride] the queries a later search has to scan (filled and drained inside one launch)
 };
 
 enum { kDecisionCommit = 0, kDecisionRetry = 1, kDecisionReturn = 2 };
@@ -568,6 +579,9 @@ __global__ __launch_bounds__(T, SPLIT ? 6 : 1) void align_kernel(const AlignArgs
   const int lane  = tid & 63;
   const int wave  = tid >> 6;
   const int tid_hot = tid;  // (cold blocks shadow tid / lane / wave with cold_copy(tid_hot))
+  // the instantiations that can keep a query cache (AlignArgs::qcache).  Everything the cache adds to this kernel stands behind this
+  // constant: every other instantiation compiles to the code it had without it
+  constexpr bool kReuse = SPLIT && SLOTS == 4;
   const int frame = blockIdx.x;
 
   int nF = g.b.n_fixed[frame];
@@ -628,6 +642,10 @@ __global__ __launch_bounds__(T, SPLIT ? 6 : 1) void align_kernel(const AlignArgs
     sh.num_recomputes = gstate->num_recomputes;
     sh.no_prune       = gstate->reserved & 1;
     sh.n_overflow     = 0;
+    if constexpr (kReuse) {
+      sh.q_tag  = (split_search && ctl->it_align != 0 && ctl->db_ready) ? ctl->q_tag : 0;
+      sh.q_miss = 0;
+    }
     sh.n_corr         = g.b.n_corr[frame];
     sh.flags          = 0;
     sh.error          = 0;
@@ -802,6 +820,9 @@ __global__ __launch_bounds__(T, SPLIT ? 6 : 1) void align_kernel(const AlignArgs
             se3_identity(sh.Tprev);
             sh.config_changed = 0;
             sh.kd_range       = (float) sh.radius;  // _initializeDatabase(): KDTree(fixed, _search_radius_pixels, ..) (kdtree_impl.cpp:21-24)
+            if constexpr (kReuse) {
+              sh.q_tag = 0;  // a new database: nothing cached about it
+            }
           }
           inputs_changed = false;
           db_built       = false;  // _initializeDatabase() is part of the reset (:131)
@@ -837,6 +858,9 @@ __global__ __launch_bounds__(T, SPLIT ? 6 : 1) void align_kernel(const AlignArgs
               }
               sh.n_projected = 0;
               sh.n_overflow  = 0;
+              if constexpr (kReuse) {
+                sh.q_miss = 0;
+              }
               ++sh.num_recomputes;
             } else {
 #pragma unroll
@@ -1311,26 +1335,41 @@ __global__ __launch_bounds__(T, SPLIT ? 6 : 1) void align_kernel(const AlignArgs
           // the int16 row / column arithmetic of the reference cannot wrap on this canvas
           const bool circle_exact = rad < 8192 && R + rad < 32000 && (g.cell_ncx << g.cell_sx) + rad < 32000;
           int projected      = 0;
-          // four queries per thread are fetched together (point + 256-bit row: 48 B each) so the
-          // global-memory latency is paid once per block of queries, not once per query
-          constexpr int kPre = SPLIT ? 1 : 4;  // queries fetched together
-          for (int m0 = tid; m0 < nM; m0 += kPre * T) {
-           float4 pre_p[kPre];
-           au32x4 pre_q0[kPre], pre_q1[kPre];
-#pragma unroll
-           for (int qi = 0; qi < kPre; ++qi) {
-             const int mm = m0 + qi * T < nM ? m0 + qi * T : m0;
-             pre_p[qi]     = gmov[mm];
-             pre_q0[qi]    = gmd[2 * mm];
-             pre_q1[qi]    = gmd[2 * mm + 1];
-           }
-#pragma unroll
-           for (int qi = 0; qi < kPre; ++qi) {
-            const int m = m0 + qi * T;
-            if (m >= nM) {
-              continue;
+          // ---- the query cache (search half, lattice patterns, four survivor slots, pruning on) ----
+          // Within a frame loop the lattice and both descriptor sets are constant, and the bound test of the pruned scan compares row
+          // bits with prune_at only: the survivors of the bound inside a set of cells are a per-query constant of the loop.  A query's
+          // pruned scan that kept all its survivors leaves the cell rectangle it covered and the survivors' lattice positions in the
+          // frame's entries; a later search whose rectangle for that query lies INSIDE the cached one (the pose moved by a pixel or
+          // two) settles the query from the entry and scans nothing.  Why the result is the same:
+          //   * every entry the pattern accepts lies in a cell of the new rectangle, which lies inside the cached one;
+          //   * the cached scan tested every entry of its cells against the same bound (the frame's tag: prune_at and the compared
+          //     words) with the same row data, so the cached survivors are a superset of a fresh scan's -- which is itself only a
+          //     superset of the pattern, because of the "one past the segment" slots;
+          //   * the pattern test and the full score behind it are the same code (settle), and the emission is order-independent;
+          //   * no result depends on whether a query overflowed its slots, only the prune hint does.  (That hint is not strictly the same
+          //     on both paths: a fresh scan of a smaller rectangle can read a "one past the segment" entry the cached scan did not -- the
+          //     segment's length has the other parity -- and count five survivors where the entry holds four.  A hit does not count
+          //     as overflowed, so n_overflow, and with it the moment a finder stops pruning, may differ between a run with and one
+          //     without the cache; the searches' results do not.)
+          // A search that reads the cache runs two passes: every query is projected and either settled from its entry or queued
+          // (16-bit indices, one LDS counter); behind one barrier the queue is scanned with dense waves by today's body, which
+          // refreshes the entries.  Entries are invalid for queries that were not visible, overflowed or could not be scanned; a
+          // search that runs unpruned drops the frame's tag instead.  split_init_kernel clears the tag with db_ready in every
+          // enqueue, a replayed graph included: nothing of an earlier batch is read.
+          const bool q_on   = kReuse && split_search && g.qcache != nullptr && prune_at > 0;
+          const int q_tag   = q_on ? (prune_at | ((prune_at <= g.narrow_prefilter_limit ? 3 : 4) << 8)) : 0;
+          const bool q_read = q_on && (sh.q_tag & 0xffff) == q_tag;  // (block-uniform: the low half changes behind the barrier that follows the search)
+          au32x4* const qc  = q_on ? g.qcache + mbase : nullptr;
+          if (kReuse && split_search && tid == 0) {
+            sh.q_tag = (sh.q_tag & 0xffff) | (q_tag << 16);  // what the entries hold behind this search (0: it runs unpruned and writes none)
+          }
+          // first_pass_tag: true = the first pass of a search that reads the cache (q0 / q1 are loaded here, for an entry that holds a survivor)
+          auto query = [&](const int m, const float4 p, au32x4 q0, au32x4 q1, auto first_pass_tag) {
+            constexpr bool FIRST_PASS = decltype(first_pass_tag)::value;
+            au32x4 ent = {0u, 0u, 0u, 0u};
+            if (FIRST_PASS) {
+              ent = qc[m];
             }
-            const float4 p = pre_p[qi];
             // PointProjectorPinhole_::compute (external)
             const float x = ((W0 * p.x + W1 * p.y) + W2 * p.z) + W3;
             const float y = ((W4 * p.x + W5 * p.y) + W6 * p.z) + W7;
@@ -1345,9 +1384,18 @@ __global__ __launch_bounds__(T, SPLIT ? 6 : 1) void align_kernel(const AlignArgs
               v              = hy / z;
               visible        = !(u < 0.0f || u >= cols || v < 0.0f || v >= rows);
             }
+            if (!FIRST_PASS && SPLIT && SLOTS == 4) {
+              // (a use of the row on this side of the visibility test: the row is waited for here and not inside the scan.  With it
+              // the pruned scan loops of the query-cache instantiations are the 61 / 65 instructions per trip pair (96 / 128 bits) they
+              // are without the cache; without it the allocator parks three scalars in a vector register and reads them back in every
+              // trip, 65 / 69.  Counted in the assembly of this build (`make asm`); profiles/search_reuse/README.md has the timings)
+              asm volatile("" : "+v"(q0), "+v"(q1));
+            }
             if (visible) {
-              ++projected;
-              const au32x4 q0 = pre_q0[qi], q1 = pre_q1[qi];
+              if (!FIRST_PASS) {
+                ++projected;
+              }
+              bool hit = false, cached = false;  // settled from the entry / left a valid entry
               // top-2 on (distance, canonical lattice position) keys: identical to the reference's
               // sequential "strictly smaller wins" scan, but independent of the visiting order
               uint32_t bestk = kNoneU32, seck = kNoneU32;
@@ -1518,26 +1566,57 @@ __global__ __launch_bounds__(T, SPLIT ? 6 : 1) void align_kernel(const AlignArgs
                 auto scan_pattern = [&](auto pruned_tag) {
                   return lean_circle ? scan(accepts_circle, pruned_tag) : scan(accepts_any, pruned_tag);
                 };
-                if (prune_at > 0) {
+                auto settle = [&](const int n_surv) {  // pattern test + full score of the survivors parked in this thread's slots
+                  for (int i = 0; i < n_surv; ++i) {
+                    const int p = (int) surv[i];
+                    bool seen   = false;  // (an entry read as "one past a segment" and again in its own)
+                    for (int j = 0; j < i; ++j) {
+                      seen = seen | ((int) surv[j] == p);
+                    }
+                    if (!seen && (lean_circle ? accepts_circle(db[p]) : accepts_any(db[p]))) {
+                      score_at(p);
+                    }
+                  }
+                };
+                if (FIRST_PASS) {
+                  // the cells this query would scan now, inside the ones its entry covers?
+                  const int cy0 = r0 >> g.cell_sy, cy1 = r1 >> g.cell_sy;
+                  hit = ent.y != 0u && ent.y <= (uint32_t) kSurvivors + 1u && cx0 >= (int) (ent.x & 0xffu) && cx1 <= (int) ((ent.x >> 8) & 0xffu) && cy0 >= (int) ((ent.x >> 16) & 0xffu) &&
+                        cy1 <= (int) (ent.x >> 24);
+                  if (hit && ent.y > 1u) {
+                    q0 = gmd[2 * m];
+                    q1 = gmd[2 * m + 1];
+                    *reinterpret_cast<uint2*>(surv) = make_uint2(ent.z, ent.w);
+                    settle((int) ent.y - 1);
+                  }
+                } else if (prune_at > 0) {
                   const int n_surv = (prune_at <= g.narrow_prefilter_limit) ? scan_pattern(std::integral_constant<int, 3>{}) : scan_pattern(std::integral_constant<int, 4>{});
                   if (n_surv > kSurvivors) {
                     atomicAdd(&sh.n_overflow, 1);
                     scan_pattern(std::integral_constant<int, 0>{});  // (nothing has been scored yet)
                   } else {
-                    for (int i = 0; i < n_surv; ++i) {
-                      const int p = (int) surv[i];
-                      bool seen   = false;  // (an entry read as "one past a segment" and again in its own)
-                      for (int j = 0; j < i; ++j) {
-                        seen = seen | ((int) surv[j] == p);
-                      }
-                      if (!seen && (lean_circle ? accepts_circle(db[p]) : accepts_any(db[p]))) {
-                        score_at(p);
-                      }
+                    settle(n_surv);
+                    if (q_on) {
+                      const uint2 kept = *reinterpret_cast<const uint2*>(surv);
+                      qc[m]  = au32x4{(uint32_t) cx0 | ((uint32_t) cx1 << 8) | ((uint32_t) (r0 >> g.cell_sy) << 16) | ((uint32_t) (r1 >> g.cell_sy) << 24),
+                                      (uint32_t) n_surv + 1u, kept.x, kept.y};
+                      cached = true;
                     }
                   }
                 } else {
                   scan_pattern(std::integral_constant<int, 0>{});
                 }
+              }
+              if (FIRST_PASS) {
+                if (!hit) {
+                  g.missq[mbase + (size_t) atomicAdd(&sh.q_miss, 1)] = (uint16_t) m;  // scanned behind the barrier
+                  bestk = kNoneU32;  // (a miss has scored nothing: nothing is emitted below)
+                } else {
+                  ++projected;
+                }
+              } else if (q_on && !cached) {  // overflowed, or nothing to scan
+                const uint32_t none = (uint32_t) cold_copy(0);
+                qc[m]               = au32x4{none, none, none, none};
               }
               if (bestk != kNoneU32) {  // circle_impl.cpp:78-92 / kdtree_impl.cpp:72-78 (best only)
                 cd.x = (lattice ? (uint32_t) inv[bestk & 0xffffu] : (bestk & 0xffffu)) | ((bestk >> 16) << 16);
@@ -1563,8 +1642,49 @@ __global__ __launch_bounds__(T, SPLIT ? 6 : 1) void align_kernel(const AlignArgs
               if (cd.y != kNoneU32) {
                 emit(cd.y, 1u);
               }
+            } else if (FIRST_PASS ? ent.y != 0u : q_on) {
+              const uint32_t none = (uint32_t) cold_copy(0);  // (made here: a zero vector kept from the top of the kernel is a spilled one)
+              qc[m]               = au32x4{none, none, none, none};
             }
-           }
+          };
+          // four queries per thread are fetched together (point + 256-bit row: 48 B each) so the
+          // global-memory latency is paid once per block of queries, not once per query
+          constexpr int kPre = SPLIT ? 1 : 4;  // queries fetched together
+          if constexpr (!kReuse) {
+            for (int m0 = tid; m0 < nM; m0 += kPre * T) {
+              float4 pre_p[kPre];
+              au32x4 pre_q0[kPre], pre_q1[kPre];
+#pragma unroll
+              for (int qi = 0; qi < kPre; ++qi) {
+                const int mm = m0 + qi * T < nM ? m0 + qi * T : m0;
+                pre_p[qi]    = gmov[mm];
+                pre_q0[qi]   = gmd[2 * mm];
+                pre_q1[qi]   = gmd[2 * mm + 1];
+              }
+#pragma unroll
+              for (int qi = 0; qi < kPre; ++qi) {
+                const int m = m0 + qi * T;
+                if (m >= nM) {
+                  continue;
+                }
+                query(m, pre_p[qi], pre_q0[qi], pre_q1[qi], std::false_type{});
+              }
+            }
+          } else {
+            static_assert(kPre == 1, "the search half fetches one query at a time");
+            int n_query = nM;
+            if (q_read) {
+              for (int m = tid; m < nM; m += T) {
+                query(m, gmov[m], au32x4{0u, 0u, 0u, 0u}, au32x4{0u, 0u, 0u, 0u}, std::true_type{});
+              }
+              __syncthreads();
+              SUB_ACC(acc_lin);     // (the search half linearises nothing: its slot times the cache pass)
+              n_query = sh.q_miss;  // the second pass: today's body over the queue
+            }
+            for (int i = tid; i < n_query; i += T) {
+              const int m = q_read ? (int) g.missq[mbase + (size_t) i] : i;
+              query(m, gmov[m], gmd[2 * m], gmd[2 * m + 1], std::false_type{});
+            }
           }
           if (projected) {
             atomicAdd(&sh.n_projected, projected);
@@ -1574,7 +1694,11 @@ __global__ __launch_bounds__(T, SPLIT ? 6 : 1) void align_kernel(const AlignArgs
         SUB_ACC(acc_search);
         // -- _filterCorrespondences (:41-102) in ascending fixed index; second[] is recycled to hold
         //    the output slot of accepted entries
+        // (query-cache instantiations: thread index, lane and wave made here.  Kept from the top of the kernel, the lane mask below is
+        // there a spilled value that every use reloads from scratch memory, one memory latency each in a phase that is a chain of barriers)
+        const int f_tid = kReuse ? cold_copy(tid_hot) : tid, f_lane = kReuse ? (f_tid & 63) : lane, f_wave = kReuse ? (f_tid >> 6) : wave;
         {
+          const int tid = f_tid, lane = f_lane, wave = f_wave;
           const float ratio = g.f.maximum_distance_ratio_to_second_best;
           const float dd    = sh.dd;
           int base          = 0;
@@ -1643,6 +1767,15 @@ __global__ __launch_bounds__(T, SPLIT ? 6 : 1) void align_kernel(const AlignArgs
           }
           if (8 * sh.n_overflow > sh.n_projected) {
             sh.no_prune = 1;  // more than an eighth of the queries were scanned twice: this finder stops pruning (until its configuration changes)
+          }
+          if (kReuse && split_search) {
+            // (nothing here waits for global memory: the workgroup stands at the next barrier meanwhile)
+            const int tag_now = sh.q_tag >> 16;
+            if (tag_now != 0 && (sh.q_tag & 0xffff) == tag_now) {  // the search read the query cache: every projected query was a hit or went through the queue
+              atomicAdd(&ctl->q_hits, sh.n_projected - sh.q_miss);
+              atomicAdd(&ctl->q_misses, sh.q_miss);
+            }
+            sh.q_tag = tag_now;
           }
           const float matching_ratio = (float) sh.n_filtered / (float) (size_t) nF;
           sh.decision                = kDecisionCommit;
@@ -1967,6 +2100,9 @@ __global__ __launch_bounds__(T, SPLIT ? 6 : 1) void align_kernel(const AlignArgs
       ctl->flags |= sh.flags;
       ctl->need_search = 0;
       gres->warnings   = sh.error ? sh.error : ctl->flags;
+      if constexpr (kReuse) {
+        ctl->q_tag = sh.q_tag & 0xffff;
+      }
     }
     if (g.stamps) {
       unsigned long long* st = g.stamps + (size_t) frame * 16;
@@ -2534,6 +2670,7 @@ __global__ void split_init_kernel(FrameCtl* ctl, prs_align_result* res, int* pen
     c.flags       = 0;
     c.n_inl = c.n_out = c.n_inv = 0;
     c.db_ready                  = 0;
+    c.q_tag = c.q_hits = c.q_misses = 0;
     ctl[i]                      = c;
     prs_align_result r;
     for (int k = 0; k < 36; ++k) {
@@ -2577,11 +2714,12 @@ static inline uint32_t align_up16(uint32_t v) {
 // an enqueued batch of the split pipeline (kept in the context between align_batch_launch and align_batch_finish)
 struct SplitJob {
   bool active = false;
+  bool last   = false;  // the context's last aligner batch went through this job (a fused batch since: the query-cache read-out has nothing to report)
   // The job OWNS the buffers its launches read and write between enqueue and finish (frame control + pending counter, operand
-  // rows, lattice images, descriptor rows in lattice order): the context's shared scratch slots belong to whatever call runs next (scene clipper, extractor,
+  // rows, lattice images, descriptor rows in lattice order, query cache, miss queues): the context's shared scratch slots belong to whatever call runs next (scene clipper, extractor,
   // brute-force matcher, merger), and a caller may run any of them between the two halves.  Grow-only; freed with the context.
-  void* own[4]        = {nullptr, nullptr, nullptr, nullptr};
-  size_t own_bytes[4] = {0, 0, 0, 0};
+  void* own[6]        = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+  size_t own_bytes[6] = {0, 0, 0, 0, 0, 0};
   hipStream_t stream  = nullptr;  // the stream the rounds run on: where they were enqueued, or where the captured graph was last replayed (finish synchronises this one)
   hipStream_t capture_stream = nullptr;  // the stream align_batch_launch enqueued / captured on (what a rearm without a stream goes back to)
   ~SplitJob() {
@@ -2645,6 +2783,7 @@ const char* align_kernel_name(int index) {
 struct AlignPlan : Plan {  // launches: the fused kernel alone, or the search kernel and the Gauss-Newton kernel of one round
   AlignArgs g = {}, gs = {};  // fused / Gauss-Newton side and search side: mode, max_fixed, the cell grid, lut_cap, surv_slots, the LDS carve, db_blob
   bool split = false, stamps_split = false;
+  bool reuse = false;  // the search launches keep a query cache (AlignArgs::qcache)
   bool lone = false, five = false, fast = false, plain = false, mprior = false, depth = false;  // what picks the Gauss-Newton instantiation
 };
 
@@ -2794,6 +2933,8 @@ static AlignPlan align_plan(const prs_pcf_params& finder, const prs_aligner_para
   // two waves per frame (eight frames resident per CU: the kernel is bound by its single-wave phases and by
   // instruction issue, more independent frames fill the idle slots)
   p.add(find_variant(kAlignVariants, {kSearchThreads, 1, finder.search_type, gs.surv_slots}), batch.batch, 1, kSearchThreads, lds_search);
+  // the query cache of the later searches: lattice patterns with four survivor slots, cell coordinates that fit a byte each
+  p.reuse = !env.no_search_reuse && !kdtree && gs.surv_slots == 4 && ncx <= 256 && ncy <= 256;
   // (the rectified-stereo factor, the one kitti.conf / euroc.conf use, has its own instantiation: the factor type as a
   // compile-time constant removes ~10 selects per linearised correspondence; so does not remembering the factor classes)
   p.fast = aligner.factor_type == PRS_FACTOR_STEREO && !aligner.keep_only_inlier_correspondences && aligner.kernel_weight_form == PRS_KERNEL_WEIGHT_INV_CHI &&
@@ -2853,6 +2994,9 @@ int align_batch_launch(prs_context* ctx, const prs_pcf_params* finder, const prs
       return ctx_fail_hip(ctx, e, "prs_align_batch_run attribute");
     }
     hipLaunchKernelGGL(kernel, dim3(l.grid_x), dim3(l.block), l.lds, stream, g);
+    if (ctx->align_job) {
+      static_cast<SplitJob*>(ctx->align_job)->last = false;
+    }
     e = hipGetLastError();
     if (e != hipSuccess) {
       return ctx_fail_hip(ctx, e, "prs_align_batch_run launch");
@@ -2894,6 +3038,17 @@ int align_batch_launch(prs_context* ctx, const prs_pcf_params* finder, const prs
       return ctx_fail(ctx, PRS_ERR_HIP, "prs_align_batch_run: descriptor row cache allocation failed");
     }
   }
+  // ... and the query cache with its miss queues (16 + 2 bytes per moving point).  Without the memory every search scans, as it
+  // does without the switch
+  if (plan.reuse) {
+    const size_t queries = (size_t) batch->batch * (size_t) batch->moving_stride;
+    gs.qcache            = static_cast<au32x4*>(job->buffer(stream, 4, queries * sizeof(au32x4)));
+    gs.missq             = gs.qcache ? static_cast<uint16_t*>(job->buffer(stream, 5, queries * sizeof(uint16_t))) : nullptr;
+    if (!gs.missq) {
+      (void) hipGetLastError();
+      gs.qcache = nullptr;
+    }
+  }
   e = hipFuncSetAttribute(reinterpret_cast<const void*>(kAlignVariants[ls.kernel].fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int) ls.lds);
   if (e != hipSuccess) {
     return ctx_fail_hip(ctx, e, "prs_align_batch_run attribute");
@@ -2908,6 +3063,7 @@ int align_batch_launch(prs_context* ctx, const prs_pcf_params* finder, const prs
   job->gs          = gs;
   job->search      = kAlignVariants[ls.kernel].fn;
   job->gn          = kAlignVariants[lg.kernel].fn;
+  job->last        = true;
   job->lds_search  = ls.lds;
   job->lds_gn      = lg.lds;
   job->total       = 0;
@@ -2938,7 +3094,7 @@ static int split_rounds(prs_context* ctx, SplitJob* job, int rounds) {
     hipLaunchKernelGGL(job->search, dim3(batch), dim3(kSearchThreads), job->lds_search, stream, job->gs);
     tick();
     if (job->stamps) {
-      ctx_report_stamps(ctx, batch, 10, "search launch (split): - | - | - | - || lattice build | projection+search | staging (keys, fixed rows -> LDS) | filter | commit");
+      ctx_report_stamps(ctx, batch, 10, "search launch (split): - | query-cache pass | - | - || lattice build | projection+search (behind a cache pass: the scan of its queue) | staging (keys, fixed rows -> LDS) | filter | commit");
     }
     hipLaunchKernelGGL(job->gn, dim3(batch), dim3(kGnThreads), job->lds_gn, stream, job->g);
     tick();
@@ -3023,6 +3179,31 @@ int align_batch_rearm(prs_context* ctx, hipStream_t replay_stream) {
   job->total        = job->enqueued;  // the rounds the captured enqueue holds
   job->ev_used      = 0;
   job->rounds_timed = 0;
+  return PRS_OK;
+}
+
+// diagnostic: queries the later searches of the last finished batch settled from the query cache / scanned, summed over its frames
+int align_reuse_counts(prs_context* ctx, long long* hits, long long* misses) {
+  *hits = *misses = 0;
+  SplitJob* job = static_cast<SplitJob*>(ctx->align_job);
+  if (!job || !job->gn || !job->last) {
+    return PRS_OK;  // the last batch did not go through the split pipeline: no search read a cache
+  }
+  if (job->active) {
+    return ctx_fail(ctx, PRS_ERR_UNSUPPORTED, "prs_context_get_search_reuse: the batch has not been finished (prs_align_batch_finish)");
+  }
+  std::vector<FrameCtl> ctl((size_t) job->g.b.batch);
+  hipError_t e = hipMemcpyAsync(ctl.data(), job->g.ctl, ctl.size() * sizeof(FrameCtl), hipMemcpyDeviceToHost, job->stream);
+  if (e == hipSuccess) {
+    e = hipStreamSynchronize(job->stream);
+  }
+  if (e != hipSuccess) {
+    return ctx_fail_hip(ctx, e, "prs_context_get_search_reuse");
+  }
+  for (const FrameCtl& c : ctl) {
+    *hits += c.q_hits;
+    *misses += c.q_misses;
+  }
   return PRS_OK;
 }
 

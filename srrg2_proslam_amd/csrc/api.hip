@@ -164,6 +164,7 @@ DispatchEnv dispatch_env(const prs_context* ctx) {
   env.bf_mfma        = ctx->bf_mfma;
   env.stamps         = ctx->stamps_enabled;
   env.stamps_split   = ctx->stamps_split;
+  env.no_search_reuse = ctx->no_search_reuse;
   // (tests and A-B runs set these two after the library is loaded: read per launch)
   env.bf_global_state   = getenv("PRS_BF_GLOBAL_STATE") != nullptr;
   const char* two_wg    = getenv("PRS_BF_TWO_WORKGROUPS");
@@ -246,6 +247,8 @@ int prs_context_create(int device_id, prs_context** out) {
   ctx->stamps_split    = ssplit && ssplit[0] == '1';
   const char* nopre    = getenv("PRS_NO_PREFILTER");
   ctx->no_prefilter    = nopre && nopre[0] == '1';
+  const char* noreuse  = getenv("PRS_NO_SEARCH_REUSE");
+  ctx->no_search_reuse = noreuse && noreuse[0] == '1';
   const char* nolone   = getenv("PRS_NO_LONE_GN");
   ctx->no_lone_gn      = nolone && nolone[0] == '1';
   const char* p96      = getenv("PRS_PREFILTER_96_LIMIT");
@@ -359,6 +362,17 @@ int prs_context_get_align_timing(prs_context* ctx, double* search_ms, double* gn
   *search_launches = ctx->n_search;
   *gn_launches     = ctx->n_gn;
   return PRS_OK;
+}
+
+int prs_context_get_search_reuse(prs_context* ctx, int64_t* hits, int64_t* misses) {
+  if (!ctx || !hits || !misses) {
+    return PRS_ERR_NULL;
+  }
+  long long h = 0, m = 0;
+  const int rc = align_reuse_counts(ctx, &h, &m);
+  *hits        = h;
+  *misses      = m;
+  return rc;
 }
 
 int prs_context_set_stream(prs_context* ctx, void* hip_stream) {

@@ -41,6 +41,7 @@ struct prs_context {
   bool no_prefilter     = false;    // PRS_NO_PREFILTER=1: the search scan scores every candidate in full (diagnostic: what the irrelevance bound buys)
   int prefilter_96_limit = 32;      // PRS_PREFILTER_96_LIMIT: largest irrelevance bound the search scan tests on 96 instead of 128 bits (diagnostic / A-B)
   int bf_mfma           = 1;        // PRS_BF_DENSE_*: the brute-force matcher's dense phase (prs_context_set_bruteforce_dense_phase; PRS_BF_MFMA=0 / auto / 1)
+  bool no_search_reuse  = false;    // PRS_NO_SEARCH_REUSE=1: every projective search of the split pipeline scans (no query cache; diagnostic / A-B)
   bool no_lone_gn       = false;    // PRS_NO_LONE_GN=1: small batches use the throughput instantiation of the Gauss-Newton kernel too (diagnostic)
   bool stamps_split     = false;    // PRS_STAMPS_SPLIT=1 (with PRS_STAMPS=1): phase stamps of the split search kernel
   struct {
@@ -273,6 +274,7 @@ int align_batch_launch(prs_context* ctx, const prs_pcf_params* finder, const prs
 int align_batch_finish(prs_context* ctx);
 int align_batch_rearm(prs_context* ctx, hipStream_t replay_stream);
 bool align_job_active(const prs_context* ctx);
+int align_reuse_counts(prs_context* ctx, long long* hits, long long* misses);
 int gn_step_launch(prs_context* ctx, const float* dH, const float* db, float damping, int damping_form, float* dX, int* dok);
 int recip_selftest_launch(prs_context* ctx, unsigned long long* d_counts);
 int bruteforce_batch_launch(prs_context* ctx, const prs_bruteforce_params* params, const prs_bruteforce_batch* batch);

@@ -83,6 +83,12 @@ class Context:
         _check(self, _lib.load().prs_context_get_align_timing(self._h, C.byref(a), C.byref(b), C.byref(c), C.byref(d)), "prs_context_get_align_timing")
         return {"search_ms": a.value, "gn_ms": b.value, "search_launches": c.value, "gn_launches": d.value}
 
+    def search_reuse(self):
+        """-> (hits, misses): queries the later searches of the last finished batch settled from the query cache / scanned again"""
+        h, m = C.c_int64(0), C.c_int64(0)
+        _check(self, _lib.load().prs_context_get_search_reuse(self._h, C.byref(h), C.byref(m)), "prs_context_get_search_reuse")
+        return h.value, m.value
+
     def align_round_timing(self):
         """-> (search_ms[16], gn_ms[16], batches): the timed launches by round of the batch (mean per batch = value / batches)"""
         a, b, n = (C.c_double * 16)(), (C.c_double * 16)(), C.c_int64(0)
