@@ -130,7 +130,8 @@ PRS_API int prs_version(void);
  * prs_dispatch_plan, prs_context_get_dispatch_env, the prs_*_plan entry points, prs_dispatch_kernel_name and
  * prs_dispatch_struct_sizes; and the trajectory evaluator: prs_trajectory_params, prs_trajectory_result, prs_trajectory_batch,
  * prs_trajectory_eval_batch and prs_trajectory_struct_sizes; and the search's query-cache read-out prs_context_get_search_reuse
- * with prs_dispatch_env::no_search_reuse at the end of that tests-and-tools struct).  Callers memset() parameter structs before
+ * with prs_dispatch_env::no_search_reuse at the end of that tests-and-tools struct; and the world map: prs_world_map_params,
+ * prs_world_map_batch, prs_world_map_workspace_bytes, prs_world_map_batch_run and prs_world_map_struct_sizes).  Callers memset() parameter structs before
  * filling them, so that fields they do not know select the shipped defaults (all zero). */
 #define PRS_ABI_VERSION 104
 PRS_API int prs_abi_check(int32_t header_version, uint64_t sizeof_stereo_params, uint64_t sizeof_pcf_params, uint64_t sizeof_aligner_params,
@@ -1881,6 +1882,91 @@ PRS_API int prs_session_reenter_batch(prs_context* ctx, const prs_reentry_params
                                       const prs_merge_batch* maps, const prs_map_archive* archive, const prs_reentry_batch* reentry);
 /* sizeof prs_map_archive, prs_reentry_params, prs_reentry_batch as the library was compiled (bindings check) */
 PRS_API void prs_map_archive_struct_sizes(uint64_t* sizes3);
+
+/* ================================================================================================
+ * World map: one landmark cloud per sequence, in the world frame of the pose graph as it stands, from the archive and the live map
+ * stands where SLAMBenchmark::benchmarkCompute speaks of "global landmark updates" (apps/app_benchmark.cpp:180-182), which the
+ * reference performs only for the map being tracked.  Landmarks live in their local map's frame (coords); the one world-frame copy
+ * is `state`, written by the merger with the scene_in_world of the merge frame, and stale as soon as prs_pose_graph_optimize*_batch
+ * moves the nodes.  This call puts archive, live map and graph together on the device: it runs after the optimiser, at any frame or
+ * at the end, and changes nothing it reads unless refresh_state asks for it.
+ *
+ * BUILD-DEFINED: the reference writes no map file, so the rule below is this build's.  tests/world_map_ref.py restates it in numpy
+ * and the kernels equal that byte for byte (explicit two-operand float64 operations in the order written, -ffp-contract=off).
+ *
+ *   maps         per sequence b the nodes n = 0 .. n_nodes[b] - 1 in ascending order, each with at most one map.  include_live and
+ *                n == cur_node[b]: the live map -- coords, desc and n_points[b] of the session, n_opt, inlier and state of `maps` --
+ *                also when the node has an archive slot (a re-entered map's live copy is the newer one).  Otherwise s =
+ *                slot_of_node[b][n] >= 0: archive slot s with its own n_points.  Otherwise the node contributes nothing.
+ *   rows         row r of a chosen map is kept when r < n_points, n_opt[r] >= min_n_opt, (!require_inlier or inlier[r] != 0) and
+ *                its three world coordinates are finite.  A row that fails the last test alone counts in n_nonfinite[b].
+ *   world        with X = graph_X[b][n] (float64, row-major 4x4) and (x, y, z) = coords[r]:
+ *                w_i = (float) (((X[4i+0] * (double) x + X[4i+1] * (double) y) + X[4i+2] * (double) z) + X[4i+3]), i = 0, 1, 2: one
+ *                rounding to float, never through (float) X, which at kilometre translations loses the millimetres the optimiser
+ *                recovered.  "Finite" is tested on the rounded floats.  The output row is (w_0, w_1, w_2, coords[r][3]), the last
+ *                one copied bit for bit.
+ *   order        kept rows by node ascending, then by row ascending.  Row i < out_stride of that order is written to xyz[b][i],
+ *                desc[b][i], node[b][i] (n), row[b][i] (r), n_opt[b][i]; rows from n_out[b] on are left untouched.  n_total[b]
+ *                counts every kept row; n_total[b] > out_stride: status[b] = PRS_ERR_CAPACITY, n_out[b] = out_stride and those rows
+ *                are valid.
+ *   count only   xyz == NULL: n_total, n_nonfinite and status are written, n_out[b] = 0, no other output is touched and the status
+ *                is never PRS_ERR_CAPACITY.  Callers size the output with it.
+ *   bounds       bounds[b] = min over the rows written of (w_0 + 0.0f, w_1 + 0.0f, w_2 + 0.0f), then the max of the same: the sum
+ *                turns -0 into +0, so the result does not depend on the order of the reduction.  Nothing written: +inf x 3, -inf x 3.
+ *   refresh_state   non-zero: every chosen map also gets state[r] = (w_0, w_1, w_2, state[r][3] as it was) for every r < n_points
+ *                whose world coordinates are finite, whatever the filter and out_stride say, in the archive slot or in maps.state
+ *                for the live map; legal in a count-only call.  This is the global landmark update.  Zero: no input is written.
+ * status[b]: PRS_ERR_RANGE, with n_out[b] = n_total[b] = n_nonfinite[b] = 0 and nothing else of the sequence written (no row, no
+ * bounds, no state): n_nodes[b] outside [1, node_stride]; cur_node[b] outside [0, n_nodes[b]); with include_live, the live n_points[b]
+ * outside [0, capacity]; a used slot_of_node entry >= slot_stride; a used slot's n_points outside [0, capacity]; two used nodes that
+ * name the same slot (its state rows would be refreshed twice).  "Used": of a node below n_nodes[b] that the live map does not
+ * replace.  Otherwise PRS_ERR_CAPACITY as above, or PRS_OK.  A sequence never writes outside its rows.
+ * Call-level (return value, nothing launched, outputs untouched): PRS_ERR_NULL (a struct, coords, desc, n_points, graph_X, n_nodes or
+ * cur_node of the session, n_opt or inlier of maps, coords, desc, n_opt, inlier, n_points or slot_of_node of the archive, n_out,
+ * n_total, n_nonfinite, status or the workspace unset; with refresh_state also state of maps and of the archive; desc, node, row,
+ * n_opt and bounds of the output are optional); PRS_ERR_RANGE (batch, capacity or node_stride differ between the three structs or
+ * are < 1, slot_stride < 1, out_stride < 0, or out_stride < 1 with xyz set); PRS_ERR_UNSUPPORTED (xyz, desc, coords, a state that is
+ * written or the workspace not 16-byte aligned, graph_X not 8-byte aligned, another array not 4-byte aligned; batch * (slot_stride +
+ * 1) * ceil(capacity / 256) beyond 2^31 - 1 workgroups or (slot_stride + 1) * capacity beyond 2^31 - 1 rows).
+ * A stable stream compaction spread over (sequence, map, chunk of 256 rows), so that one sequence of hundreds of maps fills the
+ * device: count (a workgroup per chunk), scan (a workgroup per sequence: validation, node order, chunk bases), scatter (a workgroup
+ * per chunk: ballots, wave totals in LDS, the scanned base) and, with bounds, a reduction per sequence.  Up to four plain launches
+ * on the context's stream; no allocation, no synchronisation, no host read: graph-capturable.  No atomic decides a position or a
+ * value: the output bytes depend neither on the batch around a sequence nor on the run.  Everything transient lives in the
+ * caller's workspace, which two calls in flight must not share.
+ * ============================================================================================== */
+typedef struct {
+  uint32_t min_n_opt;     /* keep landmarks optimised at least this often (0: all) */
+  int32_t require_inlier; /* non-zero: keep only landmarks whose inlier flag is set */
+  int32_t include_live;   /* non-zero: the current node's map is the live one */
+  int32_t refresh_state;  /* non-zero: rewrite `state` of every chosen map from the graph */
+} prs_world_map_params;
+
+/* device pointers */
+typedef struct {
+  int32_t out_stride;     /* rows per sequence of the output arrays */
+  int32_t reserved;
+  float* xyz;             /* out [batch][out_stride][4], 16-byte aligned, or NULL = count only */
+  uint8_t* desc;          /* out [batch][out_stride][32], 16-byte aligned (NULL allowed: not written) */
+  int32_t* node;          /* out [batch][out_stride] graph node of the landmark's map (NULL allowed) */
+  int32_t* row;           /* out [batch][out_stride] its row in that map (NULL allowed) */
+  uint32_t* n_opt;        /* out [batch][out_stride] (NULL allowed) */
+  int32_t* n_out;         /* out [batch] rows written */
+  int32_t* n_total;       /* out [batch] rows that pass the filter, whatever out_stride is */
+  int32_t* n_nonfinite;   /* out [batch] rows dropped because a world coordinate is not finite */
+  float* bounds;          /* out [batch][6] min xyz, max xyz over the rows written (NULL allowed) */
+  int32_t* status;        /* out [batch] */
+  void* workspace;        /* prs_world_map_workspace_bytes(batch, slot_stride, capacity) bytes, 16-byte aligned */
+} prs_world_map_batch;
+
+/* bytes of workspace a call over `batch` sequences of an archive of slot_stride slots of `capacity` rows needs (0: a size below 1) */
+PRS_API uint64_t prs_world_map_workspace_bytes(int32_t batch, int32_t slot_stride, int32_t capacity);
+/* device pointers, asynchronous on the context's stream.  maps supplies the live map's n_opt, inlier and state; its coords, desc
+ * and n_points are the session's */
+PRS_API int prs_world_map_batch_run(prs_context* ctx, const prs_world_map_params* params, const prs_session_batch* session,
+                                    const prs_merge_batch* maps, const prs_map_archive* archive, const prs_world_map_batch* out);
+/* sizeof prs_world_map_params, prs_world_map_batch as the library was compiled (bindings check) */
+PRS_API void prs_world_map_struct_sizes(uint64_t* sizes2);
 
 /* ================================================================================================
  * Dispatch plans -- tests and tools only.  What a launch of the stereo matcher, the aligner, the brute-force matcher or the merger

@@ -494,6 +494,18 @@ class TrajectoryBatch(C.Structure):
                 ("workspace", C.c_void_p)]
 
 
+class WorldMapParams(C.Structure):
+    """prs_world_map_params"""
+    _fields_ = [("min_n_opt", C.c_uint32), ("require_inlier", C.c_int32), ("include_live", C.c_int32), ("refresh_state", C.c_int32)]
+
+
+class WorldMapBatch(C.Structure):
+    """prs_world_map_batch (device pointers)"""
+    _fields_ = [("out_stride", C.c_int32), ("reserved", C.c_int32), ("xyz", C.c_void_p), ("desc", C.c_void_p), ("node", C.c_void_p),
+                ("row", C.c_void_p), ("n_opt", C.c_void_p), ("n_out", C.c_void_p), ("n_total", C.c_void_p), ("n_nonfinite", C.c_void_p),
+                ("bounds", C.c_void_p), ("status", C.c_void_p), ("workspace", C.c_void_p)]
+
+
 class DispatchEnv(C.Structure):
     """prs_dispatch_env: what a dispatch depends on outside its arguments (tests and tools)"""
     _fields_ = [(n, C.c_int32) for n in ("cus", "fused_align", "matcher_v3", "force_unstaged", "no_lone_gn", "merge_fused", "bf_mfma", "stamps",
@@ -648,6 +660,10 @@ SYMBOLS = {
     "prs_dispatch_struct_sizes": (None, [C.POINTER(C.c_uint64)]),
     "prs_trajectory_eval_batch": (C.c_int, [_vp, C.POINTER(TrajectoryParams), C.POINTER(TrajectoryBatch)]),
     "prs_trajectory_struct_sizes": (None, [C.POINTER(C.c_uint64)]),
+    "prs_world_map_workspace_bytes": (C.c_uint64, [C.c_int32, C.c_int32, C.c_int32]),
+    "prs_world_map_batch_run": (C.c_int, [_vp, C.POINTER(WorldMapParams), C.POINTER(SessionBatch), C.POINTER(MergeBatch),
+                                          C.POINTER(MapArchive), C.POINTER(WorldMapBatch)]),
+    "prs_world_map_struct_sizes": (None, [C.POINTER(C.c_uint64)]),
     "prs_scene_clip_batch": (C.c_int, [_vp, C.POINTER(Projector), _vp, C.POINTER(ClipBatch)]),
     "prs_scene_clip": (C.c_int, [_vp, C.POINTER(Projector), _vp, _vp, _vp, _vp, C.c_int32, _vp, _vp, _vp, C.c_int32, _i32p]),
 }
@@ -710,5 +726,11 @@ def load():
         raise ImportError("libproslam_hip.so lays out prs_trajectory_params / prs_trajectory_result / prs_trajectory_batch as %s bytes, "
                           "the Python binding as %s: rebuild with `python -c 'import __graft_entry__ as g; g.build()'`"
                           % (list(sizes), [C.sizeof(TrajectoryParams), C.sizeof(TrajectoryResult), C.sizeof(TrajectoryBatch)]))
+    sizes = (C.c_uint64 * 2)()
+    lib.prs_world_map_struct_sizes(sizes)
+    if list(sizes) != [C.sizeof(WorldMapParams), C.sizeof(WorldMapBatch)]:
+        raise ImportError("libproslam_hip.so lays out prs_world_map_params / prs_world_map_batch as %s bytes, the Python binding as %s: "
+                          "rebuild with `python -c 'import __graft_entry__ as g; g.build()'`"
+                          % (list(sizes), [C.sizeof(WorldMapParams), C.sizeof(WorldMapBatch)]))
     _lib = lib
     return lib

@@ -157,6 +157,29 @@ def associate(stamps_est, stamps_gt, max_difference=0.02):
     return gt_row, (gt_row >= 0).astype(np.uint8)
 
 
+def write_ply(path, xyz, desc=None):
+    """a minimal binary-little-endian PLY of a landmark cloud (ops.WorldMapBatch.cloud_of: xyz [n, 3] or [n, 4], the first three
+    columns are written; desc: optional uint8 [n, 32], written as 32 uchar properties d0 .. d31 of every vertex)"""
+    xyz = np.asarray(xyz, np.float32)
+    if xyz.ndim != 2 or xyz.shape[1] not in (3, 4):
+        raise ValueError("xyz must be [n, 3] or [n, 4]")
+    n = xyz.shape[0]
+    fields = [("x", "<f4"), ("y", "<f4"), ("z", "<f4")] + ([("d%d" % i, "u1") for i in range(32)] if desc is not None else [])
+    rec = np.zeros(n, np.dtype(fields))
+    rec["x"], rec["y"], rec["z"] = xyz[:, 0], xyz[:, 1], xyz[:, 2]
+    if desc is not None:
+        desc = np.asarray(desc, np.uint8)
+        if desc.shape != (n, 32):
+            raise ValueError("desc must be [n, 32]")
+        for i in range(32):
+            rec["d%d" % i] = desc[:, i]
+    header = ["ply", "format binary_little_endian 1.0", "element vertex %d" % n]
+    header += ["property %s %s" % ("float" if rec.dtype[name].kind == "f" else "uchar", name) for name in rec.dtype.names]
+    with open(path, "wb") as f:
+        f.write(("\n".join(header + ["end_header"]) + "\n").encode("ascii"))
+        f.write(rec.tobytes())
+
+
 # ---------------------------------------------------------------- .conf reader (subset)
 def _strip_line_comments(text):
     out, in_string, i = [], False, 0

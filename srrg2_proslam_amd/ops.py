@@ -2125,6 +2125,90 @@ class ReentryBatch:
                     transform=m44(self.merge_transform), scene_in_world=m44(self.scene_in_world), gate=gate)
 
 
+# ---- world map: one landmark cloud per sequence from archive, live map and graph (include/proslam_hip.h prs_world_map_*) ----
+def world_map_params(min_n_opt=0, require_inlier=False, include_live=True, refresh_state=False):
+    """prs_world_map_params: keep landmarks optimised at least min_n_opt times (and, require_inlier, flagged inliers); include_live
+    takes the current node's map from the live arrays; refresh_state rewrites `state` of every chosen map from the graph"""
+    p = _lib.WorldMapParams()
+    if int(min_n_opt) < 0:
+        raise ValueError("min_n_opt must not be negative")
+    p.min_n_opt = int(min_n_opt)
+    p.require_inlier, p.include_live, p.refresh_state = int(bool(require_inlier)), int(bool(include_live)), int(bool(refresh_state))
+    return p
+
+
+class WorldMapBatch:
+    """the world cloud of the B sequences of a SessionBatch: the maps of `archive` (a MapArchive) and the live `maps` (the session's
+    MapBatch) carried into the world frame by the session's graphs as they stand.  Owns the output tensors (out_stride rows per
+    sequence) and the workspace.  outputs: which of the optional arrays ("desc", "node", "row", "n_opt", "bounds") are kept."""
+
+    OPTIONAL = ("desc", "node", "row", "n_opt", "bounds")
+
+    def __init__(self, session, maps, archive, out_stride, outputs=OPTIONAL):
+        import torch
+        if maps is not session.maps or int(archive.batch) != session.batch:
+            raise ValueError("session, maps and archive must hold the same sequences")
+        if set(outputs) - set(self.OPTIONAL):
+            raise ValueError("outputs: a subset of %s" % (self.OPTIONAL,))
+        self.session, self.maps, self.archive = session, maps, archive
+        dev = session.pose.device
+        B, n = session.batch, int(out_stride)
+        if n < 1:
+            raise ValueError("out_stride must be at least 1")
+        self.batch, self.out_stride = B, n
+        z = lambda shape, dt: torch.zeros(shape, dtype=dt, device=dev)  # noqa: E731
+        self.xyz = z((B, n, 4), torch.float32)
+        self.desc = z((B, n, 32), torch.uint8) if "desc" in outputs else None
+        self.node = z((B, n), torch.int32) if "node" in outputs else None
+        self.row = z((B, n), torch.int32) if "row" in outputs else None
+        self.n_opt = z((B, n), torch.int32) if "n_opt" in outputs else None
+        self.bounds = z((B, 6), torch.float32) if "bounds" in outputs else None
+        self.n_out, self.n_total, self.n_nonfinite = z((B,), torch.int32), z((B,), torch.int32), z((B,), torch.int32)
+        self.status = z((B,), torch.int32)
+        nbytes = int(_lib.load().prs_world_map_workspace_bytes(B, archive.slot_stride, maps.capacity))
+        if nbytes < 1:
+            raise ValueError("batch, slot_stride and capacity must be at least 1")
+        self.workspace = z((nbytes,), torch.uint8)
+
+    def descriptor(self, count_only=False):
+        d = _lib.WorldMapBatch()
+        d.out_stride = self.out_stride
+        for name in ("n_out", "n_total", "n_nonfinite", "status", "workspace"):
+            setattr(d, name, getattr(self, name).data_ptr())
+        if not count_only:
+            for name in ("xyz",) + self.OPTIONAL:
+                t = getattr(self, name)
+                setattr(d, name, t.data_ptr() if t is not None else None)
+        return d
+
+    def _launch(self, ctx, params, count_only):
+        s, m, a, d = self.session.descriptor(), self.maps.descriptor(), self.archive.descriptor(), self.descriptor(count_only)
+        rc = _lib.load().prs_world_map_batch_run(ctx._h, C.byref(params), C.byref(s), C.byref(m), C.byref(a), C.byref(d))
+        _check(ctx, rc, "prs_world_map_batch_run")
+        return rc
+
+    def run(self, ctx, params):
+        """enqueue the export of every sequence's cloud (asynchronous); per-sequence status lands in self.status"""
+        return self._launch(ctx, params, False)
+
+    def count(self, ctx, params):
+        """enqueue the count-only call (asynchronous): n_total, n_nonfinite and status, n_out = 0; sizes an output"""
+        return self._launch(ctx, params, True)
+
+    def cloud_of(self, b):
+        """dict of numpy arrays trimmed to n_out rows (xyz [n, 4] and the optional arrays that are kept) plus n_out, n_total,
+        n_nonfinite, bounds [6] and status; copies to the host when called"""
+        n = min(max(int(self.n_out[b].item()), 0), self.out_stride)
+        out = dict(n_out=n, n_total=int(self.n_total[b].item()), n_nonfinite=int(self.n_nonfinite[b].item()),
+                   status=int(self.status[b].item()), xyz=self.xyz[b, :n].cpu().numpy().copy())
+        for name in ("desc", "node", "row", "n_opt"):
+            t = getattr(self, name)
+            if t is not None:
+                out[name] = t[b, :n].cpu().numpy().copy()
+        out["bounds"] = self.bounds[b].cpu().numpy().copy() if self.bounds is not None else None
+        return out
+
+
 # ---- intensity feature extraction (sensor_processing/feature_extractors) ----
 SELECT_CANONICAL, SELECT_LIBSTDCXX = 0, 1
 BF_DENSE_POPCOUNT, BF_DENSE_MATRIX_WHEN_FULL, BF_DENSE_MATRIX = 0, 1, 2  # include/proslam_hip.h PRS_BF_DENSE_*
