@@ -131,7 +131,9 @@ PRS_API int prs_version(void);
  * prs_dispatch_struct_sizes; and the trajectory evaluator: prs_trajectory_params, prs_trajectory_result, prs_trajectory_batch,
  * prs_trajectory_eval_batch and prs_trajectory_struct_sizes; and the search's query-cache read-out prs_context_get_search_reuse
  * with prs_dispatch_env::no_search_reuse at the end of that tests-and-tools struct; and the world map: prs_world_map_params,
- * prs_world_map_batch, prs_world_map_workspace_bytes, prs_world_map_batch_run and prs_world_map_struct_sizes).  Callers memset() parameter structs before
+ * prs_world_map_batch, prs_world_map_workspace_bytes, prs_world_map_batch_run and prs_world_map_struct_sizes; and the world voxel filter:
+ * prs_world_voxel_params, prs_world_voxel_batch, prs_world_voxel_workspace_bytes, prs_world_voxel_batch_run and
+ * prs_world_voxel_struct_sizes).  Callers memset() parameter structs before
  * filling them, so that fields they do not know select the shipped defaults (all zero). */
 #define PRS_ABI_VERSION 104
 PRS_API int prs_abi_check(int32_t header_version, uint64_t sizeof_stereo_params, uint64_t sizeof_pcf_params, uint64_t sizeof_aligner_params,
@@ -1967,6 +1969,100 @@ PRS_API int prs_world_map_batch_run(prs_context* ctx, const prs_world_map_params
                                     const prs_merge_batch* maps, const prs_map_archive* archive, const prs_world_map_batch* out);
 /* sizeof prs_world_map_params, prs_world_map_batch as the library was compiled (bindings check) */
 PRS_API void prs_world_map_struct_sizes(uint64_t* sizes2);
+
+/* ================================================================================================
+ * World voxel filter: the rows of a world-frame landmark cloud that lie in one cubic voxel are fused into one row.  A split resets
+ * the live map, so the next local map triangulates again what the previous one held, and every revisit adds another copy: the
+ * world map's cloud holds one physical corner many times over.  This stage consumes the world map's output arrays in place (or any
+ * cloud of the same layout) and hands out one row per voxel; the maps themselves and the archive keep their duplicates.
+ *
+ * BUILD-DEFINED: the reference writes no map, so the rule below is this build's.  tests/world_voxel_ref.py restates it in numpy and
+ * the kernels equal that byte for byte.  All arithmetic is explicit two-operand float64 in the order written, -ffp-contract=off.
+ * With s = (double) voxel_size, per sequence b:
+ *
+ *   rows         n = in_n[b]; the rows are i = 0 .. n - 1 and (x_0, x_1, x_2) = in_xyz[b][i][0..2].  A row with a coordinate that
+ *                is not finite is dropped and counted in n_nonfinite[b].
+ *   voxel        k_a = floor((double) x_a / s).  A row with some k_a outside [-2^20, 2^20) is dropped and counted in
+ *                n_outside[b].  The voxel key is ((k_0 + 2^20) << 42) | ((k_1 + 2^20) << 21) | (k_2 + 2^20): below 2^63, so an
+ *                all-ones word can mark an empty slot.  floor, not truncation: -1e-30 lies in voxel -1, and -0.0 in voxel 0.
+ *   representative   of the rows of one voxel the one with the greatest n_opt, among equals the smallest i: as a packed key the
+ *                minimum of ((uint64) ~n_opt << 32) | i, which does not depend on the order of evaluation.  in_n_opt == NULL: every
+ *                row has n_opt 0.  count is the number of rows of the voxel.
+ *   position     PRS_VOXEL_REPRESENTATIVE: the representative's four input floats, bit for bit.
+ *                PRS_VOXEL_MEAN: per axis f_a = (double) x_a - k_a * s, q_a = (int64) rint((f_a / s) * 1073741824.0), S_a = the
+ *                integer sum of q_a over the voxel's rows (exact, free of order, |S_a| < 2^62 for any in_stride),
+ *                m_a = (float) ((k_a + ((double) S_a / (double) count) / 1073741824.0) * s); the output row is
+ *                (m_0, m_1, m_2, w of the representative).
+ *                Descriptors are never averaged: desc, node, row and n_opt always come from the representative, which is why one
+ *                is chosen and not only a centroid computed.  Each of the four is written only when both its input and its output
+ *                are set.
+ *   order        voxels by their representative's i, ascending: the output is a subsequence of the input cloud and keeps its
+ *                node-then-row order.  Voxel j < out_stride is written to xyz[b][j], index[b][j] (the representative's i),
+ *                count[b][j] and the gathered arrays; rows from n_out[b] on are left untouched.  n_voxels[b] is the true number of
+ *                voxels; n_voxels[b] > out_stride: status[b] = PRS_ERR_CAPACITY, n_out[b] = out_stride and those rows are valid.
+ *   count only   xyz == NULL: n_voxels, n_nonfinite, n_outside and status are written, n_out[b] = 0, nothing else is touched.
+ *   table        table_stride, a power of two >= 1, gives the slots of a sequence's hash table.  A sequence with more voxels than
+ *                slots: status[b] = PRS_ERR_CAPACITY, n_out[b] = 0, n_voxels[b] = -1 (which tells it from truncation) and no row
+ *                written; n_nonfinite and n_outside are still written.  The probing visits every slot, so an insertion fails only
+ *                when the table is full of other keys, which happens exactly when the sequence has more voxels than slots: the
+ *                outcome does not depend on the run.
+ * status[b]: PRS_ERR_RANGE, with n_out[b] = n_voxels[b] = n_nonfinite[b] = n_outside[b] = 0 and nothing else of the sequence
+ * written: in_n[b] outside [0, in_stride].  Otherwise PRS_ERR_CAPACITY as above, or PRS_OK.
+ * Call-level (return value, nothing launched, outputs untouched): PRS_ERR_NULL (a struct, in_xyz, in_n, n_out, n_voxels,
+ * n_nonfinite, n_outside, status or the workspace unset); PRS_ERR_RANGE (batch or in_stride < 1, table_stride not a power of two
+ * >= 1, voxel_size not finite or <= 0, an unknown position, out_stride < 1 with xyz set); PRS_ERR_UNSUPPORTED (in_xyz, in_desc, xyz,
+ * desc or the workspace not 16-byte aligned, another array not 4-byte aligned; batch * ceil(in_stride / 256) or batch *
+ * ceil(table_stride / 256) beyond 2^31 - 1 workgroups).
+ * Five plain launches on the context's stream (four in a count-only call): clear the tables, insert (one thread per row: the key,
+ * linear probing by 64-bit compare-and-swap, then an integer min on the rank, an add on the count and, MEAN only, on the three
+ * sums), flag the representatives and count them per chunk of 256 rows, scan (a workgroup per sequence: validation, table overflow,
+ * chunk bases) and scatter (ballots plus the scanned base).  No allocation, no synchronisation, no host read: graph-capturable.
+ * Every atomic is an integer min, add or compare-and-swap whose result is free of order; none decides a position or an output
+ * value.  WHICH slot a voxel lands in may differ from run to run, no output byte does.  Everything transient lives in the caller's
+ * workspace, which two calls in flight must not share.
+ * ============================================================================================== */
+#define PRS_VOXEL_REPRESENTATIVE 0
+#define PRS_VOXEL_MEAN 1
+typedef struct {
+  float voxel_size;     /* edge of a voxel in metres, finite and > 0 */
+  int32_t position;     /* PRS_VOXEL_REPRESENTATIVE or PRS_VOXEL_MEAN */
+  int32_t reserved[2];
+} prs_world_voxel_params;
+
+/* device pointers */
+typedef struct {
+  int32_t batch;
+  int32_t in_stride;         /* rows per sequence of the input arrays */
+  const float* in_xyz;       /* in [batch][in_stride][4], 16-byte aligned (the world map's xyz) */
+  const int32_t* in_n;       /* in [batch] rows of the sequence (the world map's n_out) */
+  const uint32_t* in_n_opt;  /* in [batch][in_stride] (NULL allowed: every row has n_opt 0) */
+  const uint8_t* in_desc;    /* in [batch][in_stride][32], 16-byte aligned (NULL allowed) */
+  const int32_t* in_node;    /* in [batch][in_stride] (NULL allowed) */
+  const int32_t* in_row;     /* in [batch][in_stride] (NULL allowed) */
+  int32_t out_stride;        /* rows per sequence of the output arrays */
+  int32_t table_stride;      /* slots per sequence of the hash table, a power of two */
+  float* xyz;                /* out [batch][out_stride][4], 16-byte aligned, or NULL = count only */
+  int32_t* index;            /* out [batch][out_stride] input row of the voxel's representative (NULL allowed) */
+  int32_t* count;            /* out [batch][out_stride] rows fused into the voxel (NULL allowed) */
+  uint8_t* desc;             /* out [batch][out_stride][32], 16-byte aligned (NULL allowed) */
+  int32_t* node;             /* out [batch][out_stride] (NULL allowed) */
+  int32_t* row;              /* out [batch][out_stride] (NULL allowed) */
+  uint32_t* n_opt;           /* out [batch][out_stride] (NULL allowed) */
+  int32_t* n_out;            /* out [batch] rows written */
+  int32_t* n_voxels;         /* out [batch] voxels, whatever out_stride is; -1: more voxels than table_stride */
+  int32_t* n_nonfinite;      /* out [batch] rows dropped because a coordinate is not finite */
+  int32_t* n_outside;        /* out [batch] rows dropped because they lie outside the grid of 2^21 voxels per axis */
+  int32_t* status;           /* out [batch] */
+  void* workspace;           /* prs_world_voxel_workspace_bytes(batch, in_stride, table_stride) bytes, 16-byte aligned */
+} prs_world_voxel_batch;
+
+/* bytes of workspace a call needs: batch * (48 * table_stride + 16 + 4 * in_stride + 4 * ceil(in_stride / 256)), rounded up to 16
+ * (0: a size below 1) */
+PRS_API uint64_t prs_world_voxel_workspace_bytes(int32_t batch, int32_t in_stride, int32_t table_stride);
+/* device pointers, asynchronous on the context's stream */
+PRS_API int prs_world_voxel_batch_run(prs_context* ctx, const prs_world_voxel_params* params, const prs_world_voxel_batch* batch);
+/* sizeof prs_world_voxel_params, prs_world_voxel_batch as the library was compiled (bindings check) */
+PRS_API void prs_world_voxel_struct_sizes(uint64_t* sizes2);
 
 /* ================================================================================================
  * Dispatch plans -- tests and tools only.  What a launch of the stereo matcher, the aligner, the brute-force matcher or the merger

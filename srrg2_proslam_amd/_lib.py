@@ -506,6 +506,20 @@ class WorldMapBatch(C.Structure):
                 ("bounds", C.c_void_p), ("status", C.c_void_p), ("workspace", C.c_void_p)]
 
 
+class WorldVoxelParams(C.Structure):
+    """prs_world_voxel_params"""
+    _fields_ = [("voxel_size", C.c_float), ("position", C.c_int32), ("reserved", C.c_int32 * 2)]
+
+
+class WorldVoxelBatch(C.Structure):
+    """prs_world_voxel_batch (device pointers)"""
+    _fields_ = [("batch", C.c_int32), ("in_stride", C.c_int32), ("in_xyz", C.c_void_p), ("in_n", C.c_void_p), ("in_n_opt", C.c_void_p),
+                ("in_desc", C.c_void_p), ("in_node", C.c_void_p), ("in_row", C.c_void_p), ("out_stride", C.c_int32),
+                ("table_stride", C.c_int32), ("xyz", C.c_void_p), ("index", C.c_void_p), ("count", C.c_void_p), ("desc", C.c_void_p),
+                ("node", C.c_void_p), ("row", C.c_void_p), ("n_opt", C.c_void_p), ("n_out", C.c_void_p), ("n_voxels", C.c_void_p),
+                ("n_nonfinite", C.c_void_p), ("n_outside", C.c_void_p), ("status", C.c_void_p), ("workspace", C.c_void_p)]
+
+
 class DispatchEnv(C.Structure):
     """prs_dispatch_env: what a dispatch depends on outside its arguments (tests and tools)"""
     _fields_ = [(n, C.c_int32) for n in ("cus", "fused_align", "matcher_v3", "force_unstaged", "no_lone_gn", "merge_fused", "bf_mfma", "stamps",
@@ -664,6 +678,9 @@ SYMBOLS = {
     "prs_world_map_batch_run": (C.c_int, [_vp, C.POINTER(WorldMapParams), C.POINTER(SessionBatch), C.POINTER(MergeBatch),
                                           C.POINTER(MapArchive), C.POINTER(WorldMapBatch)]),
     "prs_world_map_struct_sizes": (None, [C.POINTER(C.c_uint64)]),
+    "prs_world_voxel_workspace_bytes": (C.c_uint64, [C.c_int32, C.c_int32, C.c_int32]),
+    "prs_world_voxel_batch_run": (C.c_int, [_vp, C.POINTER(WorldVoxelParams), C.POINTER(WorldVoxelBatch)]),
+    "prs_world_voxel_struct_sizes": (None, [C.POINTER(C.c_uint64)]),
     "prs_scene_clip_batch": (C.c_int, [_vp, C.POINTER(Projector), _vp, C.POINTER(ClipBatch)]),
     "prs_scene_clip": (C.c_int, [_vp, C.POINTER(Projector), _vp, _vp, _vp, _vp, C.c_int32, _vp, _vp, _vp, C.c_int32, _i32p]),
 }
@@ -732,5 +749,10 @@ def load():
         raise ImportError("libproslam_hip.so lays out prs_world_map_params / prs_world_map_batch as %s bytes, the Python binding as %s: "
                           "rebuild with `python -c 'import __graft_entry__ as g; g.build()'`"
                           % (list(sizes), [C.sizeof(WorldMapParams), C.sizeof(WorldMapBatch)]))
+    lib.prs_world_voxel_struct_sizes(sizes)
+    if list(sizes) != [C.sizeof(WorldVoxelParams), C.sizeof(WorldVoxelBatch)]:
+        raise ImportError("libproslam_hip.so lays out prs_world_voxel_params / prs_world_voxel_batch as %s bytes, the Python binding as %s: "
+                          "rebuild with `python -c 'import __graft_entry__ as g; g.build()'`"
+                          % (list(sizes), [C.sizeof(WorldVoxelParams), C.sizeof(WorldVoxelBatch)]))
     _lib = lib
     return lib

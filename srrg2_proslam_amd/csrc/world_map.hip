@@ -16,6 +16,7 @@
 #include <algorithm>
 #include <string>
 
+#include "prs_compact.h"
 #include "prs_device.h"
 #include "prs_host.h"
 
@@ -27,7 +28,7 @@ constexpr int kThreads = 256;
 constexpr int kChunk   = kThreads;  // rows per workgroup: one row per thread, a wave's rows are 64 consecutive ones
 constexpr int kWaves   = kThreads / PRS_WAVE;
 constexpr int kWideThreads = 1024;  // the per-sequence kernels at one long sequence: as many threads as it has nodes, or chunks
-constexpr int kBatch   = 8;         // chunk counts a thread of the scan loads before it looks at one
+constexpr int kBatch   = kCompactBatch;
 
 struct WorldMapArgs {
   prs_world_map_params p;
@@ -89,10 +90,6 @@ __device__ __forceinline__ MapRows map_rows(const WorldMapArgs& a, const int b, 
     r.state  = reinterpret_cast<float4*>(a.ar_state) + at;
   }
   return r;
-}
-
-__device__ __forceinline__ bool finite_bits(const float f) {
-  return (__float_as_uint(f) & 0x7f800000u) != 0x7f800000u;
 }
 
 // one landmark in the world: float64 products and sums in the order the header writes them, one rounding to float each
@@ -216,19 +213,6 @@ __global__ __launch_bounds__(kThreads) void world_map_count_kernel(const WorldMa
 }
 
 // ---- scan: one workgroup per sequence, of 64 .. kWideThreads threads as node_stride asks ------------------------------------------
-// n <= C counts at p from chunk c0 on, into v[kBatch] (0 behind the row's end).  The loads are unconditional at a clamped index, so the
-// compiler issues them back to back and waits once: a loop of one load per iteration pays one memory latency per chunk
-__device__ __forceinline__ void load_counts(const int32_t* p, const int c0, const int C, int32_t (&v)[kBatch]) {
-#pragma unroll
-  for (int j = 0; j < kBatch; ++j) {
-    v[j] = p[c0 + j < C ? c0 + j : C - 1];
-  }
-#pragma unroll
-  for (int j = 0; j < kBatch; ++j) {
-    v[j] = c0 + j < C ? v[j] : 0;
-  }
-}
-
 __global__ __launch_bounds__(kWideThreads) void world_map_scan_kernel(const WorldMapArgs a) {
   __shared__ uint64_t s_scan[17];
   const int tid = threadIdx.x, threads = blockDim.x, b = blockIdx.x;
@@ -375,16 +359,7 @@ __global__ __launch_bounds__(kThreads) void world_map_scatter_kernel(const World
   if (!a.write_out) {
     return;
   }
-  const uint64_t mask = __ballot(keep);
-  if (lane == 0) {
-    s_kept[wave] = __popcll(mask);
-  }
-  __syncthreads();
-  int pos = a.ws_count[id];
-  for (int v = 0; v < wave; ++v) {
-    pos += s_kept[v];
-  }
-  pos                = lanes_below(mask, pos);
+  const int pos      = chunk_position(__ballot(keep), s_kept, a.ws_count + id);
   const bool written = keep && pos < a.o.out_stride;
   if (written) {
     const size_t at                                = (size_t) b * a.o.out_stride + pos;
@@ -479,10 +454,6 @@ __global__ __launch_bounds__(kWideThreads) void world_map_bounds_kernel(const Wo
     }
     a.o.bounds[(size_t) b * 6 + tid] = r6;
   }
-}
-
-bool aligned_to(const void* p, uintptr_t to) {
-  return (reinterpret_cast<uintptr_t>(p) & (to - 1)) == 0;
 }
 
 // entries of 4 bytes in the workspace, 0 when the shape is not one the launcher takes

@@ -2209,6 +2209,109 @@ class WorldMapBatch:
         return out
 
 
+# ---- world voxel filter: one row per voxel of a world cloud (include/proslam_hip.h prs_world_voxel_*) ----
+VOXEL_REPRESENTATIVE, VOXEL_MEAN = 0, 1
+_VOXEL_POSITIONS = {"representative": VOXEL_REPRESENTATIVE, "mean": VOXEL_MEAN}
+
+
+def world_voxel_params(voxel_size, position="representative"):
+    """prs_world_voxel_params: the voxel's edge in metres (finite, > 0, also as a float32) and where the fused row lies:
+    "representative" (the best-optimised row's own coordinates) or "mean" (the voxel's rows averaged)"""
+    p = _lib.WorldVoxelParams()
+    p.voxel_size = float(voxel_size)
+    if not (np.isfinite(p.voxel_size) and p.voxel_size > 0.0):
+        raise ValueError("voxel_size must be finite and positive as a float32")
+    if position not in _VOXEL_POSITIONS:
+        raise ValueError("position: one of %s" % (sorted(_VOXEL_POSITIONS),))
+    p.position = _VOXEL_POSITIONS[position]
+    return p
+
+
+class WorldVoxelBatch:
+    """the voxel-grid filter of B clouds of in_stride rows: owns the output tensors (out_stride rows per sequence), the hash tables
+    (table_stride slots per sequence, a power of two; default: the next one >= 2 * in_stride) and the workspace.  outputs: which of the
+    optional arrays ("index", "count", "desc", "node", "row", "n_opt") are kept.  A cloud is an ops.WorldMapBatch, whose tensors are
+    read in place, or a dict of device tensors: xyz [B, in_stride, 4] float32 and n_out [B] int32, optionally n_opt, desc, node, row."""
+
+    OPTIONAL = ("index", "count", "desc", "node", "row", "n_opt")
+    INPUTS = ("n_opt", "desc", "node", "row")
+
+    def __init__(self, batch, in_stride, out_stride, table_stride=None, outputs=OPTIONAL, device=0):
+        import torch
+        if set(outputs) - set(self.OPTIONAL):
+            raise ValueError("outputs: a subset of %s" % (self.OPTIONAL,))
+        B, N, n = int(batch), int(in_stride), int(out_stride)
+        if B < 1 or N < 1 or n < 1:
+            raise ValueError("batch, in_stride and out_stride must be at least 1")
+        T = 1 << (2 * N - 1).bit_length() if table_stride is None else int(table_stride)
+        if T < 1 or T & (T - 1):
+            raise ValueError("table_stride must be a power of two")
+        self.batch, self.in_stride, self.out_stride, self.table_stride = B, N, n, T
+        dev = torch.device("cuda", device) if isinstance(device, int) else device
+        z = lambda shape, dt: torch.zeros(shape, dtype=dt, device=dev)  # noqa: E731
+        self.xyz = z((B, n, 4), torch.float32)
+        self.index = z((B, n), torch.int32) if "index" in outputs else None
+        self.voxel_count = z((B, n), torch.int32) if "count" in outputs else None  # "count": count() is the count-only call
+        self.desc = z((B, n, 32), torch.uint8) if "desc" in outputs else None
+        self.node = z((B, n), torch.int32) if "node" in outputs else None
+        self.row = z((B, n), torch.int32) if "row" in outputs else None
+        self.n_opt = z((B, n), torch.int32) if "n_opt" in outputs else None
+        self.n_out, self.n_voxels, self.status = z((B,), torch.int32), z((B,), torch.int32), z((B,), torch.int32)
+        self.n_nonfinite, self.n_outside = z((B,), torch.int32), z((B,), torch.int32)
+        self.workspace = z((int(_lib.load().prs_world_voxel_workspace_bytes(B, N, T)),), torch.uint8)
+
+    def descriptor(self, cloud, count_only=False):
+        get = (lambda k: cloud.get(k)) if isinstance(cloud, dict) else (lambda k: getattr(cloud, k))  # noqa: E731
+        xyz, n = get("xyz"), get("n_out")
+        if tuple(xyz.shape) != (self.batch, self.in_stride, 4) or tuple(n.shape) != (self.batch,):
+            raise ValueError("the cloud holds xyz %s and n_out %s, this filter was sized for [%d, %d, 4] and [%d]"
+                             % (tuple(xyz.shape), tuple(n.shape), self.batch, self.in_stride, self.batch))
+        d = _lib.WorldVoxelBatch()
+        d.batch, d.in_stride, d.out_stride, d.table_stride = self.batch, self.in_stride, self.out_stride, self.table_stride
+        d.in_xyz, d.in_n = xyz.data_ptr(), n.data_ptr()
+        for name in self.INPUTS:
+            t = get(name)
+            setattr(d, "in_" + name, t.data_ptr() if t is not None else None)
+        for name in ("n_out", "n_voxels", "n_nonfinite", "n_outside", "status", "workspace"):
+            setattr(d, name, getattr(self, name).data_ptr())
+        if not count_only:
+            for name in ("xyz",) + self.OPTIONAL:
+                t = self.tensor(name)
+                setattr(d, name, t.data_ptr() if t is not None else None)
+        return d
+
+    def tensor(self, name):
+        """the output tensor of that name ("xyz", one of OPTIONAL or a per-sequence count), None when it is not kept"""
+        return getattr(self, "voxel_count" if name == "count" else name)
+
+    def _launch(self, ctx, params, cloud, count_only):
+        d = self.descriptor(cloud, count_only)
+        rc = _lib.load().prs_world_voxel_batch_run(ctx._h, C.byref(params), C.byref(d))
+        _check(ctx, rc, "prs_world_voxel_batch_run")
+        return rc
+
+    def run(self, ctx, params, cloud):
+        """enqueue the filter of every sequence's cloud (asynchronous); per-sequence status lands in self.status"""
+        return self._launch(ctx, params, cloud, False)
+
+    def count(self, ctx, params, cloud):
+        """enqueue the count-only call (asynchronous): n_voxels, n_nonfinite, n_outside and status, n_out = 0; sizes an output"""
+        return self._launch(ctx, params, cloud, True)
+
+    def cloud_of(self, b):
+        """dict of numpy arrays trimmed to n_out rows, in the shape of WorldMapBatch.cloud_of (n_total is the number of voxels, bounds
+        None) plus index, count, n_voxels and n_outside; copies to the host when called"""
+        n = min(max(int(self.n_out[b].item()), 0), self.out_stride)
+        nv = int(self.n_voxels[b].item())
+        out = dict(n_out=n, n_total=nv, n_voxels=nv, n_nonfinite=int(self.n_nonfinite[b].item()), n_outside=int(self.n_outside[b].item()),
+                   status=int(self.status[b].item()), xyz=self.xyz[b, :n].cpu().numpy().copy(), bounds=None)
+        for name in self.OPTIONAL:
+            t = self.tensor(name)
+            if t is not None:
+                out[name] = t[b, :n].cpu().numpy().copy()
+        return out
+
+
 # ---- intensity feature extraction (sensor_processing/feature_extractors) ----
 SELECT_CANONICAL, SELECT_LIBSTDCXX = 0, 1
 BF_DENSE_POPCOUNT, BF_DENSE_MATRIX_WHEN_FULL, BF_DENSE_MATRIX = 0, 1, 2  # include/proslam_hip.h PRS_BF_DENSE_*
