@@ -122,8 +122,12 @@ struct AlignArgs {
   uint32_t off_terms;                                          //   GN phase / database build / disparity column
   // (the query cache's two pointers stand behind everything else: the kernels that do not read them load their arguments as before)
   au32x4* qcache;          // split pipeline, lattice patterns with four survivor slots: [batch][moving_stride] what each query's last pruned scan
-                           // covered and kept (x: cell rectangle cx0 | cx1 << 8 | cy0 << 16 | cy1 << 24, y: survivors + 1 or 0 = invalid,
-                           // z, w: four lattice positions); NULL = every search scans (PRS_NO_SEARCH_REUSE=1, other finders, no memory)
+                           // covered and kept.  x: cell rectangle cx0 | cx1 << 8 | cy0 << 16 | cy1 << 24.  y, z, w: up to four distinct survivors
+                           // s_i = lattice position (11 bits) | full 256-bit distance to this query << 11 (9 bits: 0 .. 256), and their number:
+                           //   y = s_0 | (survivors + 1) << 20 (three bits; 0 = invalid: an invalid entry is all zero)
+                           //   z = s_1 | position of s_3 << 20
+                           //   w = s_2 | distance of s_3 << 20
+                           // NULL = every search scans (PRS_NO_SEARCH_REUSE=1, other finders, no memory, max_fixed beyond the position field)
   uint16_t* missq;         // [batch][moving_stride] the queries a later search has to scan (filled and drained inside one launch)
 };
 
@@ -1345,7 +1349,11 @@ __global__ __launch_bounds__(T, SPLIT ? 6 : 1) void align_kernel(const AlignArgs
           //   * the cached scan tested every entry of its cells against the same bound (the frame's tag: prune_at and the compared
           //     words) with the same row data, so the cached survivors are a superset of a fresh scan's -- which is itself only a
           //     superset of the pattern, because of the "one past the segment" slots;
-          //   * the pattern test and the full score behind it are the same code (settle), and the emission is order-independent;
+          //   * the pattern test is the same code on the same lattice entry, and the full distance is a constant of the loop as well:
+          //     same fixed rows, same query row, hence the same distance -- the scan that writes the entry takes it for every distinct
+          //     survivor it keeps (one the pattern rejects now may be inside a later search's), a hit reads it from the entry and loads
+          //     neither row; best / second best are the same min / second-min of (distance, canonical position) keys, and the
+          //     emission is order-independent;
           //   * no result depends on whether a query overflowed its slots, only the prune hint does.  (That hint is not strictly the same
           //     on both paths: a fresh scan of a smaller rectangle can read a "one past the segment" entry the cached scan did not -- the
           //     segment's length has the other parity -- and count five survivors where the entry holds four.  A hit does not count
@@ -1363,13 +1371,9 @@ __global__ __launch_bounds__(T, SPLIT ? 6 : 1) void align_kernel(const AlignArgs
           if (kReuse && split_search && tid == 0) {
             sh.q_tag = (sh.q_tag & 0xffff) | (q_tag << 16);  // what the entries hold behind this search (0: it runs unpruned and writes none)
           }
-          // first_pass_tag: true = the first pass of a search that reads the cache (q0 / q1 are loaded here, for an entry that holds a survivor)
-          auto query = [&](const int m, const float4 p, au32x4 q0, au32x4 q1, auto first_pass_tag) {
+          // first_pass_tag: true = the first pass of a search that reads the cache (ent: the query's entry; no descriptor row is needed)
+          auto query = [&](const int m, const float4 p, au32x4 q0, au32x4 q1, const au32x4 ent, auto first_pass_tag) {
             constexpr bool FIRST_PASS = decltype(first_pass_tag)::value;
-            au32x4 ent = {0u, 0u, 0u, 0u};
-            if (FIRST_PASS) {
-              ent = qc[m];
-            }
             // PointProjectorPinhole_::compute (external)
             const float x = ((W0 * p.x + W1 * p.y) + W2 * p.z) + W3;
             const float y = ((W4 * p.x + W5 * p.y) + W6 * p.z) + W7;
@@ -1484,14 +1488,17 @@ __global__ __launch_bounds__(T, SPLIT ? 6 : 1) void align_kernel(const AlignArgs
                 // are looked at for the survivors only (a true match and next to nothing else: 1.4 % of the scanned entries).  The
                 // set of candidates that reach the full score is the same as with the pattern test first: both tests are conjuncts.
                 const bool lean_circle = stype == PRS_SEARCH_CIRCLE && circle_exact;
-                auto score_at = [&](const int p) {  // full distance of the entry at lattice position p
-                  const uint32_t ey = db[p].y;       // fixed index | canonical lattice position << 16
-                  const uint32_t d  = (uint32_t) hamming_regs(fdesc[p], fdesc_hi[p], q0, q1);
+                auto take = [&](const uint32_t d, const uint32_t ey) {  // a candidate: full distance, fixed index | canonical lattice position << 16
                   // best / second best (circle_impl.cpp:64-72) as min / second-min of unique keys
                   const uint32_t key = (d << 16) | (ey >> 16);
                   const uint32_t hi  = key > bestk ? key : bestk;
                   seck               = hi < seck ? hi : seck;
                   bestk              = key < bestk ? key : bestk;
+                };
+                auto score_at = [&](const int p) {  // full distance of the entry at lattice position p
+                  const uint32_t ey = db[p].y;
+                  const uint32_t d  = (uint32_t) hamming_regs(fdesc[p], fdesc_hi[p], q0, q1);
+                  take(d, ey);
                 };
                 typedef __attribute__((address_space(3))) unsigned char lds_byte;
                 const uint32_t fd_lds = (uint32_t) (uintptr_t) (lds_byte*) fdesc;  // LDS byte offset of the half rows
@@ -1512,6 +1519,14 @@ __global__ __launch_bounds__(T, SPLIT ? 6 : 1) void align_kernel(const AlignArgs
                   const uint16_t* cs = cellstart + (r0 >> g.cell_sy) * g.cell_ncx + cx0;  // bounds of the next cell row's segment
                   const int width    = cx1 + 1 - cx0;
                   int rows_left      = (r1 >> g.cell_sy) - (r0 >> g.cell_sy) + 1;
+                  int ncx            = g.cell_ncx;
+                  uint32_t fd        = fd_lds;
+                  if constexpr (kReuse) {
+                    // (the row stride and the half rows' offset made in scalar registers in front of the loop: kept from further up, the
+                    // allocator parks one of them in a vector register's lane in the query-cache instantiations and reads it back inside
+                    // the loop, 63 / 67)
+                    asm volatile("" : "+s"(ncx), "+s"(fd));
+                  }
                   int pos = 0, seg1 = 0;
                   int n_surv = 0;
                   for (;;) {
@@ -1521,7 +1536,7 @@ __global__ __launch_bounds__(T, SPLIT ? 6 : 1) void align_kernel(const AlignArgs
                       }
                       pos  = cs[0];
                       seg1 = cs[width];
-                      cs += g.cell_ncx;
+                      cs += ncx;
                       --rows_left;
                     }
                     if (pos < seg1) {
@@ -1530,7 +1545,7 @@ __global__ __launch_bounds__(T, SPLIT ? 6 : 1) void align_kernel(const AlignArgs
                         au32x4 la, lb;
                         asm volatile("ds_read_b128 %0, %2\n\tds_read_b128 %1, %2 offset:16\n\ts_waitcnt lgkmcnt(0)"
                                      : "=&v"(la), "=&v"(lb)
-                                     : "v"(fd_lds + 16u * (uint32_t) pos));
+                                     : "v"(fd + 16u * (uint32_t) pos));
                         // (no "pos + 1 < seg1" test on the second slot: the entry behind a segment is another cell's.  If it survives the
                         // bound and lies in the pattern it is in a scanned cell too -- the cells cover the pattern's bounding box -- and is
                         // met again there: survivors are de-duplicated before they are scored.  Behind the last entry sits a sentinel no
@@ -1566,28 +1581,59 @@ __global__ __launch_bounds__(T, SPLIT ? 6 : 1) void align_kernel(const AlignArgs
                 auto scan_pattern = [&](auto pruned_tag) {
                   return lean_circle ? scan(accepts_circle, pruned_tag) : scan(accepts_any, pruned_tag);
                 };
-                auto settle = [&](const int n_surv) {  // pattern test + full score of the survivors parked in this thread's slots
+                // pattern test + full score of the survivors parked in this thread's slots.  The query-cache instantiations take the full
+                // distance of EVERY distinct survivor, accepted or not, and return the entry's words y, z, w (AlignArgs::qcache): a
+                // duplicate is dropped from the entry, so a hit scores each position once without looking for one
+                auto settle = [&](const int n_surv) {
+                  unsigned long long packed = 0ull;  // s_0 | s_1 << 20 | s_2 << 40 (s_3, shifted by 60, leaves four bits nobody reads)
+                  uint32_t last = 0u, n = 0u;        // the survivor packed last: s_3 where there are four
                   for (int i = 0; i < n_surv; ++i) {
                     const int p = (int) surv[i];
                     bool seen   = false;  // (an entry read as "one past a segment" and again in its own)
                     for (int j = 0; j < i; ++j) {
                       seen = seen | ((int) surv[j] == p);
                     }
-                    if (!seen && (lean_circle ? accepts_circle(db[p]) : accepts_any(db[p]))) {
-                      score_at(p);
+                    if constexpr (kReuse) {
+                      if (!seen) {
+                        const uint2 e    = db[p];
+                        const uint32_t d = (uint32_t) hamming_regs(fdesc[p], fdesc_hi[p], q0, q1);
+                        last = (uint32_t) p | (d << 11);
+                        packed |= (unsigned long long) last << (20u * n);
+                        ++n;
+                        if (lean_circle ? accepts_circle(e) : accepts_any(e)) {
+                          take(d, e.y);
+                        }
+                      }
+                    } else {
+                      if (!seen && (lean_circle ? accepts_circle(db[p]) : accepts_any(db[p]))) {
+                        score_at(p);
+                      }
                     }
                   }
+                  const uint32_t fourth = n == 4u ? last : 0u;
+                  return make_uint3(((uint32_t) packed & 0xfffffu) | ((n + 1u) << 20), ((uint32_t) (packed >> 20) & 0xfffffu) | ((fourth & 0x7ffu) << 20),
+                                    ((uint32_t) (packed >> 40) & 0xfffffu) | ((fourth >> 11) << 20));
                 };
                 if (FIRST_PASS) {
                   // the cells this query would scan now, inside the ones its entry covers?
                   const int cy0 = r0 >> g.cell_sy, cy1 = r1 >> g.cell_sy;
-                  hit = ent.y != 0u && ent.y <= (uint32_t) kSurvivors + 1u && cx0 >= (int) (ent.x & 0xffu) && cx1 <= (int) ((ent.x >> 8) & 0xffu) && cy0 >= (int) ((ent.x >> 16) & 0xffu) &&
+                  const uint32_t code = ent.y >> 20;  // survivors + 1
+                  hit = code != 0u && code <= (uint32_t) kSurvivors + 1u && cx0 >= (int) (ent.x & 0xffu) && cx1 <= (int) ((ent.x >> 8) & 0xffu) && cy0 >= (int) ((ent.x >> 16) & 0xffu) &&
                         cy1 <= (int) (ent.x >> 24);
-                  if (hit && ent.y > 1u) {
-                    q0 = gmd[2 * m];
-                    q1 = gmd[2 * m + 1];
-                    *reinterpret_cast<uint2*>(surv) = make_uint2(ent.z, ent.w);
-                    settle((int) ent.y - 1);
+                  if (hit && code > 1u) {
+                    // the entry's survivors are distinct and carry their distance: pattern test on the lattice entry, no row is read
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) {
+                      if ((uint32_t) i + 1u < code) {
+                        const uint32_t w  = i == 0 ? ent.y : (i == 1 ? ent.z : ent.w);
+                        const uint32_t sp = i < 3 ? (w & 0x7ffu) : ((ent.z >> 20) & 0x7ffu);
+                        const uint32_t sd = i < 3 ? ((w >> 11) & 0x1ffu) : (ent.w >> 20);
+                        const uint2 e     = db[sp];
+                        if (lean_circle ? accepts_circle(e) : accepts_any(e)) {
+                          take(sd, e.y);
+                        }
+                      }
+                    }
                   }
                 } else if (prune_at > 0) {
                   const int n_surv = (prune_at <= g.narrow_prefilter_limit) ? scan_pattern(std::integral_constant<int, 3>{}) : scan_pattern(std::integral_constant<int, 4>{});
@@ -1595,11 +1641,10 @@ __global__ __launch_bounds__(T, SPLIT ? 6 : 1) void align_kernel(const AlignArgs
                     atomicAdd(&sh.n_overflow, 1);
                     scan_pattern(std::integral_constant<int, 0>{});  // (nothing has been scored yet)
                   } else {
-                    settle(n_surv);
+                    const uint3 kept = settle(n_surv);
                     if (q_on) {
-                      const uint2 kept = *reinterpret_cast<const uint2*>(surv);
                       qc[m]  = au32x4{(uint32_t) cx0 | ((uint32_t) cx1 << 8) | ((uint32_t) (r0 >> g.cell_sy) << 16) | ((uint32_t) (r1 >> g.cell_sy) << 24),
-                                      (uint32_t) n_surv + 1u, kept.x, kept.y};
+                                      kept.x, kept.y, kept.z};
                       cached = true;
                     }
                   }
@@ -1667,15 +1712,33 @@ __global__ __launch_bounds__(T, SPLIT ? 6 : 1) void align_kernel(const AlignArgs
                 if (m >= nM) {
                   continue;
                 }
-                query(m, pre_p[qi], pre_q0[qi], pre_q1[qi], std::false_type{});
+                query(m, pre_p[qi], pre_q0[qi], pre_q1[qi], au32x4{0u, 0u, 0u, 0u}, std::false_type{});
               }
             }
           } else {
             static_assert(kPre == 1, "the search half fetches one query at a time");
             int n_query = nM;
             if (q_read) {
-              for (int m = tid; m < nM; m += T) {
-                query(m, gmov[m], au32x4{0u, 0u, 0u, 0u}, au32x4{0u, 0u, 0u, 0u}, std::true_type{});
+              // the cache pass reads a point and an entry per query (32 B) and no row: a thread's queries are fetched two at a time, one
+              // memory latency per pair instead of one per query.  (Four at a time -- all of a thread's queries at the headline -- is
+              // not faster and spills three more registers; profiles/search_cache_dist/README.md)
+              constexpr int kQPre = 2;
+              for (int m0 = tid; m0 < nM; m0 += kQPre * T) {
+                float4 pre_p[kQPre];
+                au32x4 pre_e[kQPre];
+#pragma unroll
+                for (int qi = 0; qi < kQPre; ++qi) {
+                  const int mm = m0 + qi * T < nM ? m0 + qi * T : m0;
+                  pre_p[qi]    = gmov[mm];
+                  pre_e[qi]    = qc[mm];
+                }
+#pragma unroll
+                for (int qi = 0; qi < kQPre; ++qi) {
+                  const int m = m0 + qi * T;
+                  if (m < nM) {
+                    query(m, pre_p[qi], au32x4{0u, 0u, 0u, 0u}, au32x4{0u, 0u, 0u, 0u}, pre_e[qi], std::true_type{});
+                  }
+                }
               }
               __syncthreads();
               SUB_ACC(acc_lin);     // (the search half linearises nothing: its slot times the cache pass)
@@ -1683,7 +1746,7 @@ __global__ __launch_bounds__(T, SPLIT ? 6 : 1) void align_kernel(const AlignArgs
             }
             for (int i = tid; i < n_query; i += T) {
               const int m = q_read ? (int) g.missq[mbase + (size_t) i] : i;
-              query(m, gmov[m], gmd[2 * m], gmd[2 * m + 1], std::false_type{});
+              query(m, gmov[m], gmd[2 * m], gmd[2 * m + 1], au32x4{0u, 0u, 0u, 0u}, std::false_type{});
             }
           }
           if (projected) {
@@ -2934,7 +2997,8 @@ static AlignPlan align_plan(const prs_pcf_params& finder, const prs_aligner_para
   // instruction issue, more independent frames fill the idle slots)
   p.add(find_variant(kAlignVariants, {kSearchThreads, 1, finder.search_type, gs.surv_slots}), batch.batch, 1, kSearchThreads, lds_search);
   // the query cache of the later searches: lattice patterns with four survivor slots, cell coordinates that fit a byte each
-  p.reuse = !env.no_search_reuse && !kdtree && gs.surv_slots == 4 && ncx <= 256 && ncy <= 256;
+  // and lattice positions (0 .. max_fixed: the sentinel behind the last entry included) that fit the entry's 11-bit field
+  p.reuse = !env.no_search_reuse && !kdtree && gs.surv_slots == 4 && ncx <= 256 && ncy <= 256 && max_fixed < 2048;
   // (the rectified-stereo factor, the one kitti.conf / euroc.conf use, has its own instantiation: the factor type as a
   // compile-time constant removes ~10 selects per linearised correspondence; so does not remembering the factor classes)
   p.fast = aligner.factor_type == PRS_FACTOR_STEREO && !aligner.keep_only_inlier_correspondences && aligner.kernel_weight_form == PRS_KERNEL_WEIGHT_INV_CHI &&
