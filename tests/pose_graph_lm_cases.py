@@ -26,16 +26,37 @@ MEASURED_MAX_DT = 3.5e-6   # metres (fixed_not_first perturbed by (8, 0.6): 3.40
 MEASURED_MAX_DQ = 5.6e-7   # quaternion units (the same case: 5.55e-7)
 
 
-@functools.lru_cache(maxsize=None)
-def perturbed(name, t_sigma, q_sigma, seed=SEED):
-    """the case `name` with every free node's guess, in ascending index, right-multiplied by _rand_pose(rng, t_sigma, q_sigma); one
-    default_rng(seed) serves the whole graph"""
-    c = dict(pc.case(name))
+def perturb(case, t_sigma, q_sigma, seed=SEED):
+    """a copy of the case with every free node's guess, in ascending index, right-multiplied by _rand_pose(rng, t_sigma, q_sigma);
+    one default_rng(seed) serves the whole graph"""
+    c = dict(case)
     rng = np.random.default_rng(seed)
     poses = c["poses"].copy()
     for i in range(len(poses)):
         if not c["fixed"][i]:
             poses[i] = ref.se3_mul(poses[i], pc._rand_pose(rng, t_sigma, q_sigma))
     c["poses"] = poses
-    c["name"] = "%s_p%g_%g_s%d" % (name, t_sigma, q_sigma, seed)
+    c["name"] = "%s_p%g_%g_s%d" % (case["name"], t_sigma, q_sigma, seed)
     return c
+
+
+@functools.lru_cache(maxsize=None)
+def perturbed(name, t_sigma, q_sigma, seed=SEED):
+    """perturb() of the case `name` of tests/pose_graph_cases.py"""
+    return perturb(pc.case(name), t_sigma, q_sigma, seed)
+
+
+# the Gauss-Newton suite's graph whose block row is wider than the 194-block LDS buffer left at node_stride 1024: 200 nodes, closure
+# (0, 199).  From (sigmas, seed) below the restatement rejects steps in two rounds of four: trials [1, 3, 3, 1]
+WIDE_ROW_REJECTING = ((0.3, 0.25), SEED, 4)
+
+
+@functools.lru_cache(maxsize=None)
+def wide_row():
+    return pc._graph("n200", np.random.default_rng(5), 200, closures=[(0, 199)], noise=(0.02, 0.004))
+
+
+@functools.lru_cache(maxsize=None)
+def wide_row_rejecting():
+    sigmas, seed, _ = WIDE_ROW_REJECTING
+    return perturb(wide_row(), *sigmas, seed)

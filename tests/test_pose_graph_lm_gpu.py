@@ -161,6 +161,52 @@ def test_position_in_the_batch_and_entry_point(env):
     assert ops.pose_graph_algorithm(configs.get("kitti")["graph"])[1] is ops.pose_graph_optimize_batch
 
 
+def test_wide_rows_in_global_memory(env):
+    """node_stride 1024 leaves the LDS row buffer 194 blocks, the closure (0, 199) of 200 nodes makes a row of 200: the row is
+    factorised in place in the workspace, where d, g and X0 stand behind capacity_blocks * 36 doubles.  The same bits with the row in
+    LDS, with a workspace of exactly the envelope, with one 37 blocks larger (d, g and X0 start elsewhere) and in the middle of a batch"""
+    ctx, ops = env
+    c, ring = lc.wide_row(), pc.case("ring8")
+    P = params(ops, rounds=2)
+    w = want(c, rounds=2)
+    blocks = w["envelope_blocks"]
+    widest = int((np.arange(200) - ref.first_of(200, c["src"], c["dst"]) + 1).max())
+    assert w["status"] == 0 and w["iterations"] == 2 and widest == 200 > 194
+    small = run_batch(ctx, ops, [c], P)
+    assert small.node_stride == 200
+    assert_same(small.poses_of(0), small.lm_result_of(0), w, "n200 row in LDS")
+    for extra in (0, 37):
+        big = run_batch(ctx, ops, [c], P, node_stride=1024, envelope_blocks=blocks + extra)
+        assert big.workspace_bytes == 8 * (36 * (blocks + extra) + 28 * 1024)
+        assert_same(big.poses_of(0), big.lm_result_of(0), w, "n200 row in place, %d blocks to spare" % extra)
+    three = run_batch(ctx, ops, [ring, c, ring], P, node_stride=1024, envelope_blocks=blocks)
+    assert_same(three.poses_of(1), three.lm_result_of(1), w, "n200 between two ring8")
+    alone = run_batch(ctx, ops, [ring], P)
+    for b in (0, 2):
+        assert_same(three.poses_of(b), three.lm_result_of(b), want(ring, rounds=2), "ring8 at %d beside n200" % b)
+        assert np.array_equal(bits(three.poses_of(b)), bits(alone.poses_of(0)))
+        assert np.array_equal(three.lm_result[b].cpu().numpy().view(np.uint64), alone.lm_result[0].cpu().numpy().view(np.uint64))
+
+
+def test_wide_rows_after_rejected_trials(env):
+    """a rejected trial linearises and factorises again, in place, on the envelope the trial before it overwrote: with the row in
+    global memory, and one block short of it"""
+    import torch
+    ctx, ops = env
+    c = lc.wide_row_rejecting()
+    rounds = lc.WIDE_ROW_REJECTING[2]
+    P = params(ops, rounds=rounds)
+    w = want(c, rounds=rounds)
+    assert w["status"] == 0 and max(w["trials"]) >= 2 and w["trials"][-1] == 1  # a rejection, and an accepted round behind it
+    blocks = w["envelope_blocks"]
+    big = run_batch(ctx, ops, [c], P, node_stride=1024, envelope_blocks=blocks)
+    assert_same(big.poses_of(0), big.lm_result_of(0), w, "rejecting n200 row in place")
+    short = run_batch(ctx, ops, [c], P, node_stride=1024, envelope_blocks=blocks - 1)
+    got = short.lm_result_of(0)
+    assert got["status"] == ref.ERR_CAPACITY and got["iterations"] == 0
+    assert torch.equal(short.X[0, :200], torch.from_numpy(c["poses"]).to(short.X.device))
+
+
 def test_gauss_newton_diverges_where_lm_converges(env):
     ctx, ops = env
     c = lc.perturbed("n65", 5.0, 0.55)

@@ -161,6 +161,94 @@ def test_planted_motions(hip_ctx):
     assert got.tobytes() == want.tobytes()
 
 
+UNROLL_NODES = 5
+# (B, frame_stride) and the n_frames of the runs: the unroll takes one thread per (sequence, frame) of a flat index over workgroups
+# of 256 threads.  (1, 257): the second workgroup, of one row.  (3, 300): workgroups that hold the end of one sequence and the start
+# of the next.  (2, 4541): the real length.  n_frames cover 0, 1, 256, 257 and frame_stride
+UNROLL_SHAPES = [
+    (1, 257, [(257,), (257,), (257,), (256,), (1,), (0,)]),
+    (3, 300, [(300, 256, 257), (257, 300, 1), (0, 1, 300)]),
+    (2, 4541, [(4541, 257), (256, 4541)]),
+]
+
+
+def _fill_log(rig, rng, run):
+    """a hand-filled log on both sides: rigid logged poses, nodes 0 .. UNROLL_NODES - 1 with distinct node poses far from the
+    identity and, in every workgroup of the unroll, a row whose node is -1 and a row whose node is node_stride.  A workgroup of a
+    single row takes turns with `run`: a good node, -1, node_stride.  -> the flat rows with a node out of range"""
+    import torch
+    w = rig.w
+    B, fs, ns = w.batch, w.frame_stride, w.node_stride
+    for b in range(B):
+        for n in range(ns):
+            T = sc.rotation(rng.normal(size=3), rng.uniform(0.5, 3.0)) @ sc.rotation(rng.normal(size=3), rng.uniform(0.5, 3.0))
+            T[:3, 3] = rng.normal(size=3) * 50.0
+            w.X[b, n] = T
+    pose = np.tile(np.eye(4, dtype=F), (B * fs, 1, 1))
+    for i in range(B * fs):
+        T = sc.rotation(rng.normal(size=3), rng.uniform(-3.0, 3.0))
+        T[:3, 3] = rng.normal(size=3) * 5.0
+        pose[i] = T.astype(F)
+    w.frame_pose[...] = pose.reshape(B, fs, 4, 4)
+    node = rng.integers(0, ns, B * fs).astype(np.int32)
+    bad = []
+    for lo in range(0, B * fs, 256):
+        rows = min(256, B * fs - lo)
+        if rows == 1:
+            node[lo] = (ns - 1, -1, ns)[run % 3]  # the good node is not node 0, whose pose a wrong index would find
+            if run % 3:
+                bad.append(lo)
+        else:
+            at = rng.choice(rows, 2, replace=False) + lo
+            node[at[0]], node[at[1]] = -1, ns
+            bad += [int(at[0]), int(at[1])]
+    w.frame_node[...] = node.reshape(B, fs)
+    dev = rig.sess.frame_pose.device
+    rig.sess.frame_pose.copy_(torch.from_numpy(w.frame_pose.reshape(B, fs, 16)).to(dev))
+    rig.sess.frame_node.copy_(torch.from_numpy(w.frame_node).to(dev))
+    rig.graphs.X.copy_(torch.from_numpy(w.X.reshape(B, ns, 16)).to(dev))
+    return bad
+
+
+@pytest.mark.parametrize("B,frame_stride,runs", UNROLL_SHAPES, ids=["1x257", "3x300", "2x4541"])
+def test_unroll_over_more_than_one_workgroup(hip_ctx, B, frame_stride, runs):
+    """bytes against the restatement; the sentinel wherever the rule writes nothing; and, independently of the restatement, every
+    written entry within 8 * 2^-24 * sum |terms| of the float64 product of the node pose and the logged pose.  The terms of entry
+    (i, k) are G_ij * P_jk over j < 3 and, in the translation column, G_i3: the kernel rounds G to float32 once, every product
+    once and adds three times, five roundings a term, and 8 leaves room for their compounding"""
+    import torch
+    rig = Rig(B, frame_stride, 4, UNROLL_NODES, 2)
+    rng = np.random.default_rng([B, frame_stride])
+    sentinel = np.full((B, frame_stride, 4, 4), 0xA5A5A5A5, np.uint32)
+    seen_workgroups = set()
+    for run, n_frames in enumerate(runs):
+        bad = _fill_log(rig, rng, run)
+        assert len(set(rig.w.frame_node.reshape(-1).tolist()) & set(range(UNROLL_NODES))) == UNROLL_NODES
+        rig.w.n_frames[...] = n_frames
+        rig.sess.n_frames.copy_(torch.tensor(n_frames, dtype=torch.int32))
+        rig.sess.trajectory.view(torch.uint8).fill_(0xA5)
+        want = ref.unroll(rig.w, sentinel.view(F).copy())
+        got = rig.sess.unroll(hip_ctx).cpu().numpy().reshape(B, frame_stride, 4, 4)
+        assert got.tobytes() == want.tobytes(), (run, n_frames)
+        # which rows are written, from the rule alone
+        written = np.arange(frame_stride)[None, :] < np.asarray(n_frames)[:, None]
+        written.reshape(-1)[bad] = False
+        untouched = (got.view(np.uint32) == 0xA5A5A5A5).all(axis=(2, 3))
+        assert np.array_equal(untouched, ~written), (run, n_frames)
+        seen_workgroups.update((np.nonzero(written.reshape(-1))[0] // 256).tolist())
+        # the float64 product
+        G = rig.w.X[np.arange(B)[:, None], np.clip(rig.w.frame_node, 0, UNROLL_NODES - 1)]  # [B, fs, 4, 4] float64
+        P = rig.w.frame_pose.astype(np.float64)
+        product = G @ P
+        terms = np.abs(G[..., :3, :3]) @ np.abs(P[..., :3, :])
+        terms[..., 3] += np.abs(G[..., :3, 3])
+        error = np.abs(got[..., :3, :].astype(np.float64) - product[..., :3, :])[written]
+        bound = (8.0 * 2.0 ** -24) * terms[written]
+        assert error.shape[0] == written.sum() and (error <= bound).all(), (run, n_frames, float((error / bound).max()))
+        assert (got[written][:, 3] == np.array([0, 0, 0, 1], F)).all()
+    assert seen_workgroups == set(range(-(-B * frame_stride // 256)))  # every workgroup of the launch has written rows
+
+
 def test_batch_invariance(hip_ctx):
     """one sequence alone and the same sequence at slot 3 of B = 5 give the same bits"""
     frames = planted_inputs()

@@ -150,6 +150,43 @@ def test_more_nodes_than_a_workgroup_has_threads(hip_ctx):
     assert all(w["status"] == ref.PRS_ERR_CAPACITY for w in rig.check(ops.world_map_params(include_live=False)))
 
 
+def _scattered_slots(rng, B, capacity, slot_stride, node_stride):
+    """B sequences whose slot_stride slots are named by as many nodes picked from all node_stride, in a permuted order; the other
+    nodes have no slot.  Point counts 0 .. capacity with both ends planted; the current node has a slot in sequence 0 and none in 1.
+    The last node holds a map with rows: it is the one node whose base takes the totals of every wave of the scan before its own"""
+    seqs = []
+    for b in range(B):
+        nn = node_stride - b
+        holders = rng.choice(nn - 1, slot_stride, replace=False)
+        holders[3] = nn - 1
+        son = np.full(nn, -1, np.int32)
+        son[holders] = rng.permutation(slot_stride)
+        n_points = rng.integers(0, capacity + 1, slot_stride)
+        n_points[son[holders[0]]], n_points[son[holders[1]]], n_points[son[holders[3]]] = 0, capacity, capacity // 2 + 1
+        cur = int(holders[2]) if b == 0 else int(np.nonzero(son < 0)[0][nn // 3])
+        seqs.append(wc.make_sequence(rng, capacity, slot_stride, node_stride, nn, cur, son, n_points, capacity - 7 * b))
+    return seqs
+
+
+@pytest.mark.parametrize("node_stride,capacity,scan_threads,bounds_threads", [(130, 515, 192, 128), (700, 65, 704, 64)])
+def test_scans_between_one_wave_and_sixteen(hip_ctx, node_stride, capacity, scan_threads, bounds_threads):
+    """the scan runs roundup64(node_stride) threads and the bounds kernel roundup64(maps * chunks): 130 nodes give 3 waves over one
+    tile and 41 maps of 3 chunks give 2 waves; 700 nodes give 11 waves over one partial tile.  The other tests run both at 1 or 16"""
+    S = 40
+    chunks = -(-capacity // 256)
+    assert -(-node_stride // 64) * 64 == scan_threads and -(-(S + 1) * chunks // 64) * 64 == bounds_threads
+    seqs = _scattered_slots(np.random.default_rng(node_stride), 2, capacity, S, node_stride)
+    rig = Rig(hip_ctx, seqs, (S + 1) * capacity + 3)
+    for refresh in (True, False):
+        want = rig.check(ops.world_map_params(min_n_opt=1, refresh_state=refresh), what="refresh %d" % refresh)
+        for w, s in zip(want, seqs):
+            assert w["status"] == ref.PRS_OK and w["bounds"] is not None and w["n_total"] > 4 * capacity
+            assert len(set(w["node"].tolist())) >= S - 2 and (np.diff(w["node"]) >= 0).all()  # node order, not slot order
+            # rows of the last node, so of the last wave, behind rows of at least two waves before it
+            assert w["node"][-1] == s["n_nodes"] - 1 and len(set((w["node"] // 64).tolist())) >= 3
+    rig.check(ops.world_map_params(require_inlier=True), count_only=True, what="count only")
+
+
 def test_more_chunks_than_the_scan_loads_at_once(hip_ctx):
     """capacity 2305: ten chunks of 256 rows a map, the scan takes them eight at a time"""
     seqs = _batch(2305, 1, 2)

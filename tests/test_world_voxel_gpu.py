@@ -21,23 +21,33 @@ POSITIONS = ("representative", "mean")
 SIZE = 0.3
 
 
+def expected_of(clouds, inputs, p, out_stride, table_stride):
+    """the restatement's result for every cloud of a list, given the optional input arrays `inputs`.  out_stride None: the
+    count-only call.  Runs on the host alone"""
+    rp = ref.params(p.voxel_size, p.position)
+    clouds = [dict(c, **{k: None for k in INPUTS if k not in inputs}) for c in clouds]
+    return [ref.world_voxel(c, rp, out_stride, table_stride) for c in clouds]
+
+
 class Rig:
     """a WorldVoxelBatch over device copies of a list of clouds in the restatement's layout.  inputs: which of the optional input
-    arrays the call is given"""
+    arrays the call is given (the others are not uploaded).  known: results of expected_of for these clouds, out_stride and
+    table_stride that a test formed before it built the rig, {(position, count_only): results}; they are not computed again"""
 
-    def __init__(self, ctx, clouds, out_stride, table_stride=None, outputs=ops.WorldVoxelBatch.OPTIONAL, inputs=INPUTS):
+    def __init__(self, ctx, clouds, out_stride, table_stride=None, outputs=ops.WorldVoxelBatch.OPTIONAL, inputs=INPUTS, known=None):
         import torch
-        self.ctx, self.clouds, self.B, self.inputs = ctx, clouds, len(clouds), tuple(inputs)
+        self.ctx, self.clouds, self.B, self.inputs, self.known = ctx, clouds, len(clouds), tuple(inputs), dict(known or {})
         N = clouds[0]["in_stride"]
         dev = torch.device("cuda", 0)
         z = lambda shape, dt: torch.zeros(shape, dtype=dt, device=dev)  # noqa: E731
-        self.dev = dict(xyz=z((self.B, N, 4), torch.float32), n_out=z((self.B,), torch.int32), n_opt=z((self.B, N), torch.int32),
-                        desc=z((self.B, N, 32), torch.uint8), node=z((self.B, N), torch.int32), row=z((self.B, N), torch.int32))
+        self.dev = dict(xyz=z((self.B, N, 4), torch.float32), n_out=z((self.B,), torch.int32))
+        for k in self.inputs:
+            self.dev[k] = z((self.B, N, 32), torch.uint8) if k == "desc" else z((self.B, N), torch.int32)
         self.vx = ops.WorldVoxelBatch(self.B, N, out_stride, table_stride, outputs)
         self.upload()
 
     def cloud(self):
-        return {k: v for k, v in self.dev.items() if k in ("xyz", "n_out") + self.inputs}
+        return dict(self.dev)
 
     def upload(self):
         import torch
@@ -57,9 +67,9 @@ class Rig:
         return {k: self.vx.tensor(k).cpu().numpy() for k in ROW_OUTPUTS + COUNTS if self.vx.tensor(k) is not None}
 
     def expected(self, p, count_only=False):
-        rp = ref.params(p.voxel_size, p.position)
-        clouds = [dict(c, **{k: None for k in INPUTS if k not in self.inputs}) for c in self.clouds]
-        return [ref.world_voxel(c, rp, None if count_only else self.vx.out_stride, self.vx.table_stride) for c in clouds]
+        if (p.position, count_only) in self.known:
+            return self.known[p.position, count_only]
+        return expected_of(self.clouds, self.inputs, p, None if count_only else self.vx.out_stride, self.vx.table_stride)
 
     def compare(self, got, want, what=""):
         for b, w in enumerate(want):
@@ -238,6 +248,134 @@ def test_a_sequence_does_not_depend_on_its_batch_or_on_the_run(hip_ctx, position
     rig1 = Rig(hip_ctx, [clouds[2]], 400)
     rig1.check(p)
     assert _snapshot(rig1, 0) == first  # position 0 of B = 1 against position 2 of B = 3
+
+
+# ---- beyond one wave and one tile of the scan.  The scan kernel runs roundup64(ceil(chunks / 8)) threads, at most 1024, over tiles of
+# 8 * threads chunks: 512 chunks are the last single wave, 513 take two; 8192 chunks are one tile of 1024 threads, 8193 start a second
+# one, whose bases stand on the carry.  voxels: more than 2^16 and 2^20, so that chunk bases pass both
+BIG_VOXELS = {131072: 80000, 131073: 80000, 2097152: 1200000, 2097153: 1200000}
+BIG_SIDE = 200  # 8e6 cells: room for 1.2 million voxels
+
+
+def _big_cloud(rows):
+    """in_n = in_stride = rows over BIG_VOXELS[rows] voxels, with two chunks of 256 representatives in the first and the last of the
+    rows that take one voxel each, a chunk of none in the middle of the rows behind them, and, where the last chunk holds one row,
+    that row a representative.  -> (cloud, voxels, the empty chunk)"""
+    voxels, chunks = BIG_VOXELS[rows], -(-rows // 256)
+    c = vc.make_cloud(_rng(13, rows), rows, rows, SIZE, voxels, side=BIG_SIDE)
+    lead = voxels // 256  # chunks whose rows take one voxel each
+    empty = (lead + 1 + chunks) // 2
+    vc.plant_chunk_counts(c, voxels, (1, lead - 1), (empty,))
+    if rows % 256 == 1:
+        c["n_opt"][rows - 1] = vc.HIGHEST_N_OPT
+    return c, voxels, empty
+
+
+_shared = {}
+
+
+def _cloud_131073():
+    """the two-wave cloud, shared by the tests that read it (none of them writes to it)"""
+    if "c" not in _shared:
+        _shared["c"] = _big_cloud(131073)
+    return _shared["c"]
+
+
+@pytest.mark.parametrize("rows", sorted(BIG_VOXELS))
+def test_scan_beyond_one_wave_and_one_tile(hip_ctx, rows):
+    """every output byte, both positions, run and count-only, at the four sizes either side of the scan's two switches.  What each
+    case is there for is asserted on the restatement's result before anything is launched.  At the two sizes above 2 million rows
+    the time goes to the host: about 1 s to seed the cloud and 1 to 1.6 s for each of the restatement's four results"""
+    c, voxels, empty = _big_cloud(rows) if rows != 131073 else _cloud_131073()
+    chunks, large = -(-rows // 256), rows > 1 << 20
+    assert chunks == {131072: 512, 131073: 513, 2097152: 8192, 2097153: 8193}[rows]
+    keep = (lambda names: tuple(k for k in names if k != "desc")) if large else tuple
+    inputs, outputs = keep(INPUTS), keep(ops.WorldVoxelBatch.OPTIONAL)
+    table_stride = 1 << voxels.bit_length()  # the next power of two above the voxel count: 2^17 and 2^21 slots
+    out_stride = voxels + 3
+    known = {}
+    for position in POSITIONS:
+        p = ops.world_voxel_params(SIZE, position)
+        known[p.position, False] = expected_of([c], inputs, p, out_stride, table_stride)
+        w = known[p.position, False][0]
+        assert w["status"] == ref.PRS_OK and w["n_out"] == w["n_voxels"] == voxels and w["count"].sum() == rows
+        counts, bases = vc.chunk_counts(w["index"], chunks)
+        assert counts.min() == 0 and counts.max() == 256 and ((counts > 0) & (counts < 256)).any()
+        assert 0 < empty < chunks - 1 and counts[empty] == 0 and counts[:empty].all() and counts[empty + 1:].all()
+        assert bases[-1] > (1 << 20 if large else 1 << 16)
+        if rows % 256 == 1:  # the last chunk holds one row and it represents its voxel
+            assert counts[-1] == 1 and bases[-1] == voxels - 1 and w["index"][bases[-1]] == rows - 1
+        if rows == 2097153:  # chunk 8192 is the first of the second tile: its base is the carry alone
+            assert chunks - 1 == 8192 and w["index"][bases[8192]] >= 2097152
+    rig = Rig(hip_ctx, [c], out_stride, table_stride, outputs, inputs, known)
+    rig.check_both(SIZE, "rows %d" % rows)
+    rig.check_both(SIZE, "rows %d, count only" % rows, count_only=True)
+
+
+def test_truncation_at_a_large_base(hip_ctx):
+    """out_stride one below the voxel count, with the cut in a chunk whose base is above 2^16"""
+    c, voxels, _ = _cloud_131073()
+    table_stride, inputs = 1 << voxels.bit_length(), INPUTS
+    known = {}
+    for position in POSITIONS:
+        p = ops.world_voxel_params(SIZE, position)
+        full = expected_of([c], inputs, p, voxels, table_stride)[0]
+        known[p.position, False] = expected_of([c], inputs, p, voxels - 1, table_stride)
+        w = known[p.position, False][0]
+        assert (w["status"], w["n_out"], w["n_voxels"]) == (ref.PRS_ERR_CAPACITY, voxels - 1, voxels)
+        assert w["index"].tolist() == full["index"][:-1].tolist() and w["index"][-1] > 1 << 16
+        assert full["index"][-1] == 131072  # the row that is cut off: the one row of the last chunk
+    rig = Rig(hip_ctx, [c], voxels - 1, table_stride, known=known)
+    rig.check_both(SIZE)
+
+
+def test_all_rows_of_two_waves_of_chunks_in_one_voxel(hip_ctx):
+    """131073 rows on one slot: the rank's row index passes 2^16 and the MEAN divides sums of 131073 terms of up to 2^30"""
+    c = vc.one_voxel_cloud(_rng(14), 131073, 131073, SIZE)
+    c["n_opt"][70000], c["n_opt"][100000] = 9, 9  # the tie goes to the lower row
+    known = {}
+    for position in POSITIONS:
+        p = ops.world_voxel_params(SIZE, position)
+        known[p.position, False] = expected_of([c], INPUTS, p, 5, 1 << 18)
+        w = known[p.position, False][0]
+        assert w["n_voxels"] == 1 and w["index"].tolist() == [70000] and w["count"].tolist() == [131073]
+    rig = Rig(hip_ctx, [c], 5, 1 << 18, known=known)
+    rig.check_both(SIZE)
+
+
+@pytest.mark.parametrize("position", POSITIONS)
+def test_a_short_sequence_beside_a_long_one(hip_ctx, position):
+    """B = 2 with 131073 and 2305 rows in one in_stride: the scan's workgroup is sized by the stride, the short sequence's result is
+    what it is alone"""
+    long_, voxels, _ = _cloud_131073()
+    short = vc.make_cloud(_rng(15), 131073, 2305, SIZE, 500)
+    p = ops.world_voxel_params(SIZE, position)
+    rig2 = Rig(hip_ctx, [long_, short], voxels + 3, 1 << 18)
+    want = rig2.check(p)
+    assert [w["n_voxels"] for w in want] == [voxels, 500]
+    both = _snapshot(rig2, 1)
+    rig1 = Rig(hip_ctx, [short], voxels + 3, 1 << 18)
+    rig1.check(p)
+    assert _snapshot(rig1, 0) == both
+
+
+def test_rank_key_at_the_extremes_of_n_opt(hip_ctx):
+    """n_opt 0, 1, 2^31 - 1, 2^31 and 2^32 - 1 inside the same voxels: the complement and the shift that pack the rank"""
+    values = [0, 1, (1 << 31) - 1, 1 << 31, (1 << 32) - 1]
+    c = vc.make_cloud(_rng(16), 2305, 2305, SIZE, 300)
+    vc.spread_n_opt(_rng(16, 1), c, SIZE, values)
+    assert c["n_opt"].dtype == np.uint32 and sorted(set(c["n_opt"].tolist())) == values
+    known = {}
+    for position in POSITIONS:
+        p = ops.world_voxel_params(SIZE, position)
+        known[p.position, False] = expected_of([c], INPUTS, p, 2305, 8192)
+        w = known[p.position, False][0]
+        assert w["n_voxels"] == 300 and sorted(set(w["n_opt"].tolist())) == values  # every value wins somewhere
+        # and loses somewhere: voxels whose best row is not their first hold every value but the lowest
+        later = w["index"] >= 300
+        assert sorted(set(w["n_opt"][later].tolist())) == values[1:]
+    rig = Rig(hip_ctx, [c], 2305, 8192, known=known)
+    rig.check_both(SIZE)
 
 
 def test_call_level_refusals_write_nothing(hip_ctx):
