@@ -133,7 +133,8 @@ PRS_API int prs_version(void);
  * with prs_dispatch_env::no_search_reuse at the end of that tests-and-tools struct; and the world map: prs_world_map_params,
  * prs_world_map_batch, prs_world_map_workspace_bytes, prs_world_map_batch_run and prs_world_map_struct_sizes; and the world voxel filter:
  * prs_world_voxel_params, prs_world_voxel_batch, prs_world_voxel_workspace_bytes, prs_world_voxel_batch_run and
- * prs_world_voxel_struct_sizes).  Callers memset() parameter structs before
+ * prs_world_voxel_struct_sizes; and the image rectifier: prs_rectify_map, prs_rectify_params, prs_rectify_batch, prs_rectify_batch_run
+ * and prs_rectify_struct_sizes).  Callers memset() parameter structs before
  * filling them, so that fields they do not know select the shipped defaults (all zero). */
 #define PRS_ABI_VERSION 104
 PRS_API int prs_abi_check(int32_t header_version, uint64_t sizeof_stereo_params, uint64_t sizeof_pcf_params, uint64_t sizeof_aligner_params,
@@ -2225,6 +2226,98 @@ typedef struct {
 PRS_API int prs_trajectory_eval_batch(prs_context* ctx, const prs_trajectory_params* params, const prs_trajectory_batch* batch);
 /* sizeof prs_trajectory_params, prs_trajectory_result, prs_trajectory_batch as the library was compiled (bindings check) */
 PRS_API void prs_trajectory_struct_sizes(uint64_t* sizes3);
+
+/* ================================================================================================
+ * Image rectifier: raw frames are undistorted and stereo-rectified on the device, in front of the feature extractors and the RGB-D
+ * preprocessor, whose image arrays it writes in place (dst has the layout of prs_extract_batch.images and prs_depth_batch.depth).
+ *
+ * BUILD-DEFINED: the reference has no such stage.  Both of its converters stamp distortion_model = "undistorted" on whatever they
+ * are given (apps/convert_stereo_to_srrg2.cpp:145, apps/convert_rgbd_to_srrg2.cpp:147) and its epipolar matcher runs with
+ * epipolar_line_thickness_pixels 0 (euroc.conf:535-551), so it needs images that are row-aligned to the pixel; EuRoC and TUM frames
+ * are not recorded that way.  The rule below is this build's; tests/rectify_ref.py restates it in numpy and the kernel equals the
+ * float32 restatement byte for byte.  Every operation is a two-operand float32 operation in the order written (-ffp-contract=off,
+ * correctly rounded division).  For the destination pixel (u, v) of image b with m = maps[map_of[b]] (map_of == NULL: maps[0]):
+ *
+ *   ray       x = (u - dst_cx) / dst_fx, y = (v - dst_cy) / dst_fy; with R row-major, taking source-camera coordinates to
+ *             rectified-camera coordinates (OpenCV's R1 / R2), the ray in the source camera is R^T (x, y, 1):
+ *             rx = (R[0] x + R[3] y) + R[6], ry = (R[1] x + R[4] y) + R[7], rz = (R[2] x + R[5] y) + R[8].
+ *   distort   xn = rx / rz, yn = ry / rz, xx = xn xn, yy = yn yn, xy = xn yn, r2 = xx + yy,
+ *             rad = 1 + r2 (k1 + r2 (k2 + r2 k3)),
+ *             xd = (xn rad + (2 p1) xy) + p2 (r2 + 2 xx), yd = (yn rad + p1 (r2 + 2 yy)) + (2 p2) xy
+ *             (PRS_DISTORTION_RADTAN, the radial-tangential model of OpenCV; all five coefficients 0: a pinhole).
+ *   project   us = src_fx xd + src_cx, vs = src_fy yd + src_cy.
+ *   border    the pixel is `border` unless rz > 0, us > -1, us < src_cols, vs > -1 and vs < src_rows all hold.  NaN fails every
+ *             comparison, and no float outside that range is ever converted to an integer.
+ *   bilinear  (PRS_PIXEL_U8 only) x0 = floor(us), y0 = floor(vs), ax = us - x0, ay = vs - y0; taps a = (y0, x0), b = (y0, x0 + 1),
+ *             c = (y0 + 1, x0), d = (y0 + 1, x0 + 1) as floats, a tap outside the source reads `border`;
+ *             top = a + ax (b - a), bot = c + ax (d - c), val = top + ay (bot - top); the output is
+ *             (uint8) min(max(floor(val + 0.5f), 0), 255).
+ *   nearest   xi = floor(us + 0.5f), yi = floor(vs + 0.5f): the source element's bits unchanged, `border` when (yi, xi) lies
+ *             outside.  The depth image's mode: interpolating depth across an edge invents surfaces.
+ *   border value   params->border converted once on the host: U8 / U16 (uint) min(max(floor(border + 0.5f), 0), 255 / 65535), NaN
+ *             gives 0; F32 keeps its bits.
+ * n_border[b] (optional) is the number of destination pixels of image b that are `border` by the border rule (not those with only
+ * some taps outside); the entry clears it on the stream and each workgroup adds its tile's count with one integer atomic.
+ * status[b]: PRS_ERR_RANGE when map_of[b] lies outside [0, n_maps) or the map has a field that is not finite, a focal length
+ * (src_fx, src_fy, dst_fx, dst_fy) that is 0 or an unknown model: every pixel of the image is then `border` and n_border[b] =
+ * dst_rows * dst_cols; the other images are unaffected.  PRS_OK otherwise.  Bytes of dst between dst_cols elements and dst_pitch are
+ * never written.
+ * Call-level (return value, nothing enqueued, outputs untouched): PRS_ERR_NULL (params, batch, src, dst, maps or status unset);
+ * PRS_ERR_UNSUPPORTED (an unknown pixel_type or interpolation, bilinear for other than PRS_PIXEL_U8, dst not 4-byte aligned, src not
+ * aligned to its element, src and dst overlapping, more than 2^31 - 1 workgroups); PRS_ERR_RANGE (batch, n_maps or a size below 1,
+ * a pitch below cols * element size or not a multiple of the element size, an image of 2^31 bytes or more).
+ * One kernel launch behind one clear of n_border on the context's stream: no allocation, no synchronisation, no host read,
+ * graph-capturable like prs_extract_features_batch.  The map costs about a hundred vector instructions and two divisions a pixel,
+ * the pixels far less, so a workgroup owns one destination tile (16 rows of 64 pixels: four adjacent pixels per lane, one 4-byte
+ * store per lane for 8-bit pixels) and a chunk of up to 16 consecutive images; it holds (source offset, ax, ay, tap validity) in
+ * registers and recomputes them only when map_of[b] differs from the map it holds, so callers that keep one camera's images
+ * together (ops.RectifyBatch: left block, right block) pay for the map once per chunk.  Any order is correct.  The chunk shrinks
+ * while the grid would not fill the chip (PRS_RECTIFY_CHUNK = 1 .. 64 in the environment, read per launch, fixes it: tests and
+ * tools).  For 8-bit bilinear the workgroup stages the tile's source footprint -- the box around the taps it holds, in whole
+ * 16-byte pieces of the source rows -- in LDS per image and reads the taps from there, when src and src_pitch are multiples of 16
+ * bytes and the box fits 8 KB; otherwise, and for nearest, the lanes fetch their taps from global memory (PRS_RECTIFY_VARIANT = 0
+ * forces that: tools).  Staging reads a source row up to the next multiple of 16 bytes, which lies inside src_pitch.  There is no
+ * host-pointer variant and no C++ adapter in plugin/: the reference has no class to mirror.
+ * ============================================================================================== */
+enum { PRS_DISTORTION_RADTAN = 0 };
+enum { PRS_PIXEL_U8 = 0, PRS_PIXEL_U16 = 1, PRS_PIXEL_F32 = 2 };
+enum { PRS_RECTIFY_BILINEAR = 0, PRS_RECTIFY_NEAREST = 1 };
+
+/* one camera's map, an element of a device array; 96 bytes */
+typedef struct {
+  int32_t model;                           /* PRS_DISTORTION_RADTAN; the field is there for fisheye and rational models */
+  int32_t reserved;
+  float src_fx, src_fy, src_cx, src_cy;    /* the raw camera's matrix */
+  float k1, k2, p1, p2, k3;                /* its distortion, in OpenCV's order */
+  float R[9];                              /* row-major, source camera -> rectified camera (the identity: undistortion only) */
+  float dst_fx, dst_fy, dst_cx, dst_cy;    /* the rectified camera's matrix */
+} prs_rectify_map;
+
+typedef struct {
+  int32_t pixel_type;      /* PRS_PIXEL_* */
+  int32_t interpolation;   /* PRS_RECTIFY_*; bilinear needs PRS_PIXEL_U8 */
+  float border;            /* value of a pixel that has no source */
+  int32_t reserved;
+} prs_rectify_params;
+
+/* device pointers */
+typedef struct {
+  int32_t batch;
+  int32_t src_rows, src_cols, src_pitch;   /* pitches in bytes, multiples of the element size */
+  const void* src;                         /* [batch][src_rows][src_pitch] */
+  int32_t dst_rows, dst_cols, dst_pitch;   /* the destination's size may differ from the source's */
+  void* dst;                               /* out [batch][dst_rows][dst_pitch], 4-byte aligned; must not overlap src */
+  int32_t n_maps;
+  const prs_rectify_map* maps;             /* [n_maps] */
+  const int32_t* map_of;                   /* [batch], or NULL: every image uses maps[0] */
+  int32_t* n_border;                       /* out [batch] border pixels of the image, or NULL */
+  int32_t* status;                         /* out [batch] */
+} prs_rectify_batch;
+
+/* device pointers, asynchronous on the context's stream */
+PRS_API int prs_rectify_batch_run(prs_context* ctx, const prs_rectify_params* params, const prs_rectify_batch* batch);
+/* sizeof prs_rectify_map, prs_rectify_params, prs_rectify_batch as the library was compiled (bindings check) */
+PRS_API void prs_rectify_struct_sizes(uint64_t* sizes3);
 
 #ifdef __cplusplus
 }

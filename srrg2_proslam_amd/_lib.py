@@ -520,6 +520,25 @@ class WorldVoxelBatch(C.Structure):
                 ("n_nonfinite", C.c_void_p), ("n_outside", C.c_void_p), ("status", C.c_void_p), ("workspace", C.c_void_p)]
 
 
+class RectifyMap(C.Structure):
+    """prs_rectify_map: one camera's map, an element of a device array (96 bytes)"""
+    _fields_ = [("model", C.c_int32), ("reserved", C.c_int32), ("src_fx", C.c_float), ("src_fy", C.c_float), ("src_cx", C.c_float),
+                ("src_cy", C.c_float), ("k1", C.c_float), ("k2", C.c_float), ("p1", C.c_float), ("p2", C.c_float), ("k3", C.c_float),
+                ("R", C.c_float * 9), ("dst_fx", C.c_float), ("dst_fy", C.c_float), ("dst_cx", C.c_float), ("dst_cy", C.c_float)]
+
+
+class RectifyParams(C.Structure):
+    """prs_rectify_params"""
+    _fields_ = [("pixel_type", C.c_int32), ("interpolation", C.c_int32), ("border", C.c_float), ("reserved", C.c_int32)]
+
+
+class RectifyBatch(C.Structure):
+    """prs_rectify_batch (device pointers)"""
+    _fields_ = [("batch", C.c_int32), ("src_rows", C.c_int32), ("src_cols", C.c_int32), ("src_pitch", C.c_int32), ("src", C.c_void_p),
+                ("dst_rows", C.c_int32), ("dst_cols", C.c_int32), ("dst_pitch", C.c_int32), ("dst", C.c_void_p), ("n_maps", C.c_int32),
+                ("maps", C.c_void_p), ("map_of", C.c_void_p), ("n_border", C.c_void_p), ("status", C.c_void_p)]
+
+
 class DispatchEnv(C.Structure):
     """prs_dispatch_env: what a dispatch depends on outside its arguments (tests and tools)"""
     _fields_ = [(n, C.c_int32) for n in ("cus", "fused_align", "matcher_v3", "force_unstaged", "no_lone_gn", "merge_fused", "bf_mfma", "stamps",
@@ -681,6 +700,8 @@ SYMBOLS = {
     "prs_world_voxel_workspace_bytes": (C.c_uint64, [C.c_int32, C.c_int32, C.c_int32]),
     "prs_world_voxel_batch_run": (C.c_int, [_vp, C.POINTER(WorldVoxelParams), C.POINTER(WorldVoxelBatch)]),
     "prs_world_voxel_struct_sizes": (None, [C.POINTER(C.c_uint64)]),
+    "prs_rectify_batch_run": (C.c_int, [_vp, C.POINTER(RectifyParams), C.POINTER(RectifyBatch)]),
+    "prs_rectify_struct_sizes": (None, [C.POINTER(C.c_uint64)]),
     "prs_scene_clip_batch": (C.c_int, [_vp, C.POINTER(Projector), _vp, C.POINTER(ClipBatch)]),
     "prs_scene_clip": (C.c_int, [_vp, C.POINTER(Projector), _vp, _vp, _vp, _vp, C.c_int32, _vp, _vp, _vp, C.c_int32, _i32p]),
 }
@@ -754,5 +775,11 @@ def load():
         raise ImportError("libproslam_hip.so lays out prs_world_voxel_params / prs_world_voxel_batch as %s bytes, the Python binding as %s: "
                           "rebuild with `python -c 'import __graft_entry__ as g; g.build()'`"
                           % (list(sizes), [C.sizeof(WorldVoxelParams), C.sizeof(WorldVoxelBatch)]))
+    sizes = (C.c_uint64 * 3)()
+    lib.prs_rectify_struct_sizes(sizes)
+    if list(sizes) != [C.sizeof(RectifyMap), C.sizeof(RectifyParams), C.sizeof(RectifyBatch)]:
+        raise ImportError("libproslam_hip.so lays out prs_rectify_map / prs_rectify_params / prs_rectify_batch as %s bytes, the Python "
+                          "binding as %s: rebuild with `python -c 'import __graft_entry__ as g; g.build()'`"
+                          % (list(sizes), [C.sizeof(RectifyMap), C.sizeof(RectifyParams), C.sizeof(RectifyBatch)]))
     _lib = lib
     return lib

@@ -2558,3 +2558,179 @@ def rgbd_params(cfg, selection_order=SELECT_LIBSTDCXX, max_raw_detections=32768,
     ep = extractor_params(int(r["detector_threshold"]), int(r["enable_non_maximum_suppression"]), int(r["target_number_of_keypoints"]),
                           int(r["number_of_detectors_vertical"]), int(r["number_of_detectors_horizontal"]), selection_order, max_raw_detections)
     return ep, depth_params(depth_type, r["depth_scaling_factor_to_meters"])
+
+
+# ---- image rectifier: undistort and stereo-rectify raw frames in front of the extractors (include/proslam_hip.h prs_rectify_*) ----
+DISTORTION_RADTAN = 0                                # PRS_DISTORTION_*
+PIXEL_U8, PIXEL_U16, PIXEL_F32 = 0, 1, 2             # PRS_PIXEL_*
+RECTIFY_BILINEAR, RECTIFY_NEAREST = 0, 1             # PRS_RECTIFY_*
+_PIXEL_TYPES = {"u8": PIXEL_U8, "u16": PIXEL_U16, "f32": PIXEL_F32}
+_PIXEL_NP = {PIXEL_U8: np.uint8, PIXEL_U16: np.uint16, PIXEL_F32: np.float32}
+_INTERPOLATIONS = {"bilinear": RECTIFY_BILINEAR, "nearest": RECTIFY_NEAREST}
+
+
+def rectify_params(pixel_type="u8", interpolation=None, border=0):
+    """prs_rectify_params.  pixel_type "u8" / "u16" / "f32", interpolation "bilinear" / "nearest" (None: bilinear for u8, nearest
+    otherwise: depth is never interpolated), border = the value of a pixel without a source (an integer type's must lie in its range)"""
+    if pixel_type not in _PIXEL_TYPES:
+        raise ValueError("pixel_type: one of %s" % (sorted(_PIXEL_TYPES),))
+    t = _PIXEL_TYPES[pixel_type]
+    if interpolation is None:
+        interpolation = "bilinear" if t == PIXEL_U8 else "nearest"
+    if interpolation not in _INTERPOLATIONS:
+        raise ValueError("interpolation: one of %s" % (sorted(_INTERPOLATIONS),))
+    i = _INTERPOLATIONS[interpolation]
+    if i == RECTIFY_BILINEAR and t != PIXEL_U8:
+        raise ValueError("bilinear interpolation is for u8 pixels only")
+    if t != PIXEL_F32 and not (np.isfinite(border) and 0 <= border <= (255 if t == PIXEL_U8 else 65535)):
+        raise ValueError("border must lie in the range of the pixel type")
+    return _lib.RectifyParams(t, i, float(border), 0)
+
+
+class RectifyMap:
+    """one camera's rectification map, held in float64: K_src [3, 3] and dist (k1, k2, p1, p2, k3) of the raw camera, R [3, 3] taking
+    its coordinates to the rectified camera's, K_dst [3, 3] of the rectified camera.  struct() is the prs_rectify_map (float32)."""
+
+    def __init__(self, K_src, dist, R, K_dst):
+        self.K_src, self.dist, self.R, self.K_dst = K_src, dist, R, K_dst
+
+    def struct(self):
+        m = _lib.RectifyMap()
+        m.model = DISTORTION_RADTAN
+        m.src_fx, m.src_fy, m.src_cx, m.src_cy = self.K_src[0, 0], self.K_src[1, 1], self.K_src[0, 2], self.K_src[1, 2]
+        m.k1, m.k2, m.p1, m.p2, m.k3 = self.dist
+        m.R[:] = [float(x) for x in self.R.reshape(9)]
+        m.dst_fx, m.dst_fy, m.dst_cx, m.dst_cy = self.K_dst[0, 0], self.K_dst[1, 1], self.K_dst[0, 2], self.K_dst[1, 2]
+        return m
+
+
+def _finite32(a):
+    """finite, also as the float32 the kernel is handed"""
+    with np.errstate(over="ignore"):
+        return bool(np.all(np.isfinite(a)) and np.all(np.isfinite(a.astype(np.float32))))
+
+
+def _camera_matrix(K, what):
+    K = np.asarray(K, dtype=np.float64)
+    if K.shape != (3, 3):
+        raise ValueError("%s must be a 3 x 3 camera matrix" % what)
+    if not _finite32(K):
+        raise ValueError("%s is not finite" % what)
+    if np.float32(K[0, 0]) == 0 or np.float32(K[1, 1]) == 0:
+        raise ValueError("%s is singular: a focal length is 0" % what)
+    return K.copy()
+
+
+def rectify_map(K_src, dist, R=None, K_dst=None):
+    """one RectifyMap from the raw camera's matrix K_src [3, 3] and distortion (k1, k2, p1, p2[, k3]), the rotation R [3, 3] from its
+    coordinates to the rectified camera's (None: the identity, undistortion only) and the rectified camera's matrix K_dst (None:
+    K_src).  ValueError for a wrong shape, a value that is not finite (also as a float32), a zero focal length or a singular R."""
+    Ks = _camera_matrix(K_src, "K_src")
+    Kd = Ks.copy() if K_dst is None else _camera_matrix(K_dst, "K_dst")
+    d = np.asarray(dist, dtype=np.float64).reshape(-1)
+    if d.size not in (4, 5):
+        raise ValueError("dist holds (k1, k2, p1, p2) or (k1, k2, p1, p2, k3)")
+    d = np.concatenate([d, np.zeros(5 - d.size)])
+    Rm = np.eye(3) if R is None else np.asarray(R, dtype=np.float64)
+    if Rm.shape != (3, 3):
+        raise ValueError("R must be 3 x 3")
+    if not (_finite32(d) and _finite32(Rm)):
+        raise ValueError("dist or R is not finite")
+    if abs(np.linalg.det(Rm)) < 1e-12:
+        raise ValueError("R is singular")
+    return RectifyMap(Ks, d, Rm.copy(), Kd)
+
+
+def stereo_rectification(K_l, D_l, K_r, D_r, R_rl, t_rl, image_size=None):
+    """(map_left, map_right, camera) of a calibrated stereo pair, on the host in float64.  BUILD-DEFINED (the reference is handed
+    rectified images).  R_rl [3, 3], t_rl [3]: the pose of the right camera in the left camera's frame (X_l = R_rl X_r + t_rl).
+    The rectified x axis runs along the baseline, e1 = t / |t|; e2 = (0, 0, 1) x e1 normalised keeps the left camera's viewing
+    direction as far as that allows; e3 = e1 x e2.  R_l has the rows e1, e2, e3 and R_r = R_l R_rl: both rectified cameras look
+    along e3 and the right one stands at (|t|, 0, 0), so rows agree and u_l - u_r = fx |t| / z.  Both get the same matrix: fx = fy =
+    the mean of the four focal lengths, the principal point the mean of the two.  camera has the keys of configs.*["camera"]
+    (cols, rows from image_size = (cols, rows), None when it is not given; baseline_m = |t|)."""
+    ml, mr = rectify_map(K_l, D_l), rectify_map(K_r, D_r)
+    R_rl = np.asarray(R_rl, dtype=np.float64)
+    t = np.asarray(t_rl, dtype=np.float64).reshape(-1)
+    if R_rl.shape != (3, 3) or t.shape != (3,) or not (np.all(np.isfinite(R_rl)) and np.all(np.isfinite(t))):
+        raise ValueError("R_rl must be a finite 3 x 3 rotation and t_rl a finite 3-vector")
+    b = float(np.linalg.norm(t))
+    if not b > 0.0:
+        raise ValueError("t_rl is zero: the cameras have no baseline")
+    e1 = t / b
+    e2 = np.cross([0.0, 0.0, 1.0], e1)
+    n2 = float(np.linalg.norm(e2))
+    if not n2 > 1e-9:
+        raise ValueError("the baseline runs along the optical axis")
+    e2 = e2 / n2
+    e3 = np.cross(e1, e2)
+    R_l = np.stack([e1, e2, e3])
+    R_r = R_l @ R_rl
+    f = (ml.K_src[0, 0] + ml.K_src[1, 1] + mr.K_src[0, 0] + mr.K_src[1, 1]) / 4.0
+    cx, cy = (ml.K_src[0, 2] + mr.K_src[0, 2]) / 2.0, (ml.K_src[1, 2] + mr.K_src[1, 2]) / 2.0
+    K = np.array([[f, 0.0, cx], [0.0, f, cy], [0.0, 0.0, 1.0]])
+    cols, rows = (None, None) if image_size is None else (int(image_size[0]), int(image_size[1]))
+    camera = {"fx": float(f), "fy": float(f), "cx": float(cx), "cy": float(cy), "cols": cols, "rows": rows, "baseline_m": b}
+    return rectify_map(ml.K_src, ml.dist, R_l, K), rectify_map(mr.K_src, mr.dist, R_r, K), camera
+
+
+class RectifyBatch:
+    """the rectifier of `batch` images of src_shape = (rows, cols) into dst_shape (None: the same): owns the device array of maps,
+    dst, n_border and status.  run(src) enqueues on the context's stream and returns dst, a [batch, rows, cols] view whose rows are
+    padded to a multiple of four elements (one store per lane); the extractors and the depth stage take it in place with its pitch.
+    stereo=True: two maps (left, right) and an even batch laid out as the left block [0 : batch / 2] then the right block, so a
+    workgroup's run of images shares one map; left / right are the two halves of dst."""
+
+    def __init__(self, ctx, params, maps, batch, src_shape, dst_shape=None, stereo=False):
+        import torch
+        maps = [maps] if isinstance(maps, RectifyMap) else list(maps)
+        B = int(batch)
+        if B < 1 or not maps:
+            raise ValueError("batch and the number of maps must be at least 1")
+        if stereo and (len(maps) != 2 or B % 2):
+            raise ValueError("a stereo batch has two maps and an even number of images")
+        self.ctx, self.params, self.batch, self.n_maps = ctx, params, B, len(maps)
+        self.src_shape = (int(src_shape[0]), int(src_shape[1]))
+        self.dst_shape = self.src_shape if dst_shape is None else (int(dst_shape[0]), int(dst_shape[1]))
+        if min(self.src_shape + self.dst_shape) < 1:
+            raise ValueError("image sizes must be at least 1")
+        self.np_dtype = _PIXEL_NP.get(params.pixel_type, np.uint8)  # an unknown type is the library's to refuse
+        self.dtype = {np.uint8: torch.uint8, np.uint16: torch.uint16, np.float32: torch.float32}[self.np_dtype]
+        dev = torch.device("cuda", ctx.device)
+        arr = (_lib.RectifyMap * len(maps))(*[m.struct() for m in maps])
+        host = np.frombuffer(arr, dtype=np.uint8).copy()
+        self.maps = torch.from_numpy(host).to(dev)
+        rows, cols = self.dst_shape
+        self._dst = torch.zeros((B, rows, (cols + 3) // 4 * 4), dtype=self.dtype, device=dev)
+        self.dst = self._dst[:, :, :cols]
+        self.n_border = torch.zeros((B,), dtype=torch.int32, device=dev)
+        self.status = torch.zeros((B,), dtype=torch.int32, device=dev)
+        self.map_of = None
+        if stereo:
+            self.map_of = torch.cat([torch.zeros(B // 2, dtype=torch.int32), torch.ones(B // 2, dtype=torch.int32)]).to(dev)
+        self.left, self.right = (self.dst[: B // 2], self.dst[B // 2:]) if stereo else (None, None)
+
+    def descriptor(self, src, map_of=None):
+        rows, cols = self.src_shape
+        if src.dtype != self.dtype or tuple(src.shape) != (self.batch, rows, cols) or src.stride(2) != 1 or \
+                (self.batch > 1 and src.stride(0) != rows * src.stride(1)):
+            raise ValueError("src must be a %s tensor [%d, %d, %d] with dense images (stride(0) = rows * pitch)" % (self.dtype, self.batch, rows, cols))
+        map_of = self.map_of if map_of is None else map_of
+        if map_of is not None and (map_of.dtype != self.n_border.dtype or tuple(map_of.shape) != (self.batch,) or not map_of.is_contiguous()):
+            raise ValueError("map_of must be a contiguous int32 tensor [%d]" % self.batch)
+        d = _lib.RectifyBatch()
+        es = src.element_size()
+        d.batch, d.src_rows, d.src_cols, d.src_pitch, d.src = self.batch, rows, cols, int(src.stride(1)) * es, src.data_ptr()
+        d.dst_rows, d.dst_cols, d.dst_pitch, d.dst = self.dst_shape[0], self.dst_shape[1], int(self._dst.stride(1)) * es, self._dst.data_ptr()
+        d.n_maps, d.maps = self.n_maps, self.maps.data_ptr()
+        d.map_of = map_of.data_ptr() if map_of is not None else None
+        d.n_border, d.status = self.n_border.data_ptr(), self.status.data_ptr()
+        return d
+
+    def run(self, src, map_of=None):
+        """enqueue the rectification of src [batch, rows, cols] (asynchronous; map_of: int32 [batch] or None = the stereo layout's,
+        else map 0 for every image); returns dst.  Per-image status and border counts land in self.status and self.n_border."""
+        d = self.descriptor(src, map_of)
+        rc = _lib.load().prs_rectify_batch_run(self.ctx._h, C.byref(self.params), C.byref(d))
+        _check(self.ctx, rc, "prs_rectify_batch_run")
+        return self.dst
