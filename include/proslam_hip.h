@@ -134,7 +134,8 @@ PRS_API int prs_version(void);
  * prs_world_map_batch, prs_world_map_workspace_bytes, prs_world_map_batch_run and prs_world_map_struct_sizes; and the world voxel filter:
  * prs_world_voxel_params, prs_world_voxel_batch, prs_world_voxel_workspace_bytes, prs_world_voxel_batch_run and
  * prs_world_voxel_struct_sizes; and the image rectifier: prs_rectify_map, prs_rectify_params, prs_rectify_batch, prs_rectify_batch_run
- * and prs_rectify_struct_sizes).  Callers memset() parameter structs before
+ * and prs_rectify_struct_sizes; and the dense RGB-D cloud: prs_depth_cloud_params, prs_depth_cloud_batch,
+ * prs_depth_cloud_workspace_bytes, prs_depth_cloud_batch_run and prs_depth_cloud_struct_sizes).  Callers memset() parameter structs before
  * filling them, so that fields they do not know select the shipped defaults (all zero). */
 #define PRS_ABI_VERSION 104
 PRS_API int prs_abi_check(int32_t header_version, uint64_t sizeof_stereo_params, uint64_t sizeof_pcf_params, uint64_t sizeof_aligner_params,
@@ -2318,6 +2319,100 @@ typedef struct {
 PRS_API int prs_rectify_batch_run(prs_context* ctx, const prs_rectify_params* params, const prs_rectify_batch* batch);
 /* sizeof prs_rectify_map, prs_rectify_params, prs_rectify_batch as the library was compiled (bindings check) */
 PRS_API void prs_rectify_struct_sizes(uint64_t* sizes3);
+
+/* ================================================================================================
+ * Dense RGB-D cloud: every sampled depth pixel of a sequence's chosen frames, placed in the world by the trajectory.  The depth
+ * images are those of prs_depth_batch.depth or the rectifier's dst, the poses the array prs_session_unroll_batch writes, and the
+ * output has the world map's layout, so prs_world_voxel_batch_run reads it in place (frame and pixel in the places of in_node and
+ * in_row).
+ *
+ * BUILD-DEFINED: the unprojector of apps/example_unproject_rgbd.cpp lives in srrg2_core, outside the reference tree, so the rule
+ * below is this build's, put together from the depth test and scaling of RawDataPreprocessorMonocularDepth::_readDepth
+ * (raw_data_preprocessor_monocular_depth.cpp:156-180), the unprojection of the depth merger and the float32 se3_mul / se3_apply of
+ * the other stages; the app's range_min 0.1, range_max 10 and its depth scale 1e-3 are the defaults of the Python layer.
+ * tests/depth_cloud_ref.py restates it in numpy and the kernels equal that byte for byte.  All arithmetic is explicit two-operand
+ * float32 in the order written, -ffp-contract=off, division correctly rounded.  Per sequence b:
+ *
+ *   frames       f = 0 .. n_images[b] - 1 in order.  k = frame_index[b][f], or f when frame_index is NULL.  A frame whose k lies
+ *                outside [0, pose_stride), or whose pose[b][k] has an entry that is not finite among the twelve of its top three
+ *                rows, gives no row and is counted in n_skipped[b].  Otherwise T = se3_mul(pose[b][k], sensor_in_robot):
+ *                T[i][j] = (A[i][0] * B[0][j] + A[i][1] * B[1][j]) + A[i][2] * B[2][j] for j < 3 and
+ *                T[i][3] = ((A[i][0] * B[0][3] + A[i][1] * B[1][3]) + A[i][2] * B[2][3]) + A[i][3].
+ *   pixels       v = 0, step, 2 step, .. < rows and inside a row u = 0, step, .. < cols, in raster order.  raw is the depth element
+ *                as a float (a 16-bit value converts exactly).  The pixel is kept iff raw > 0 (which drops NaN, -0, 0 and negative
+ *                values) and, with d = depth_scaling_factor_to_meters * raw, d >= range_min && d <= range_max (which drops +inf).
+ *   point        p = (((float) u - cx) / fx * d, ((float) v - cy) / fy * d, d);
+ *                w_i = ((T[i][0] * p_0 + T[i][1] * p_1) + T[i][2] * p_2) + T[i][3].  The row is (w_0, w_1, w_2, i) with i = 0.0f
+ *                when gray is NULL and (float) gray(v, u) * (1.0f / 255.0f) otherwise.
+ *   order        image, then raster, behind the first n_base[b] rows of the output (0 when n_base is NULL), which are not touched:
+ *                the world map's node-then-row order.  frame[b][j] = f and pixel[b][j] = v * cols + u of row j.
+ *   counts       n_total[b] = n_base[b] + the kept pixels, whatever out_stride is (saturating at 2^31 - 1);
+ *                n_out[b] = min(n_total[b], out_stride); n_total[b] > out_stride: status[b] = PRS_ERR_CAPACITY, the rows below
+ *                out_stride are valid.  Rows from n_out[b] on are left untouched.  n_base may be the pointer n_out: a long
+ *                sequence is fed in several calls, each appending behind the last.
+ *   count only   xyz == NULL: n_total, n_skipped and status (never PRS_ERR_CAPACITY) are written, n_out[b] = n_base[b], nothing
+ *                else is touched.
+ * status[b]: PRS_ERR_RANGE when n_images[b] lies outside [0, frames] or n_base[b] outside [0, out_stride], with
+ * n_total[b] = n_skipped[b] = 0, n_out[b] = n_base[b] clamped into [0, out_stride] and no row written.  Otherwise PRS_ERR_CAPACITY
+ * as above, or PRS_OK.
+ * Call-level (return value, nothing launched, outputs untouched): PRS_ERR_NULL (a struct, depth, n_images, pose, n_out, n_total,
+ * n_skipped, status or the workspace unset); PRS_ERR_RANGE (batch, frames, rows, cols, pose_stride or step < 1; pitch below
+ * cols elements or not a multiple of the element size, gray_pitch below cols with gray set; a parameter that is not finite --
+ * sensor_in_robot included --, a scale <= 0, range_min < 0 or range_min > range_max; out_stride < 1 with xyz set);
+ * PRS_ERR_UNSUPPORTED (an unknown depth_type; xyz or the workspace not 16-byte aligned, depth not aligned to its element, another
+ * array but gray not 4-byte aligned; rows * cols or frames * ceil(rows / step) * ceil(cols / step) beyond 2^31 - 1; a grid beyond
+ * 2^31 - 1 workgroups).
+ * Three plain launches on the context's stream (two in a count-only call): count (a workgroup per chunk of 1024 sampled pixels of
+ * one image, four consecutive samples a lane, wave ballots), scan (a workgroup per sequence: validation, the skipped frames,
+ * n_base, truncation, the chunk bases) and scatter (the same ballots order the chunk's rows in LDS, from where they go out behind
+ * the scanned base, one 16-byte store a row and 4 KB in one piece a store instruction of the workgroup; T once per workgroup
+ * through LDS; chunks that keep nothing, lie behind out_stride or belong to a refused sequence return before they read a pixel).  With step 1, cols a multiple of 4 and rows 8-byte (16-bit) or 16-byte (float) aligned a lane reads its four
+ * depths in one load.  No atomic at all; no allocation, no synchronisation, no host read: graph-capturable.  Everything transient
+ * lives in the caller's workspace, which two calls in flight must not share.  There is no host-pointer variant, no colour output
+ * and no C++ adapter in plugin/.
+ * ============================================================================================== */
+typedef struct {
+  int32_t depth_type;                    /* PRS_DEPTH_U16 or PRS_DEPTH_F32 */
+  float depth_scaling_factor_to_meters;  /* finite and > 0 */
+  float fx, fy, cx, cy;                  /* the depth camera's matrix */
+  float range_min, range_max;            /* metres, finite, 0 <= range_min <= range_max */
+  int32_t step;                          /* pixel stride in both directions, >= 1 */
+  float sensor_in_robot[16];             /* row-major; the identity when the poses are the camera's */
+  int32_t reserved[3];
+} prs_depth_cloud_params;
+
+/* device pointers */
+typedef struct {
+  int32_t batch;
+  int32_t frames;              /* images per sequence */
+  int32_t rows, cols;
+  int32_t pitch;               /* bytes, a multiple of the depth element's size */
+  int32_t gray_pitch;          /* bytes */
+  int32_t pose_stride;         /* poses per sequence */
+  int32_t out_stride;          /* rows per sequence of the output arrays */
+  const void* depth;           /* in [batch][frames][rows][pitch] */
+  const uint8_t* gray;         /* in [batch][frames][rows][gray_pitch] (NULL allowed: intensity 0) */
+  const int32_t* n_images;     /* in [batch] */
+  const float* pose;           /* in [batch][pose_stride][16], what prs_session_unroll_batch writes */
+  const int32_t* frame_index;  /* in [batch][frames] the pose of image f (NULL allowed: f) */
+  const int32_t* n_base;       /* in [batch] rows already in the output (NULL allowed: 0; may be n_out) */
+  float* xyz;                  /* out [batch][out_stride][4], 16-byte aligned, or NULL = count only */
+  int32_t* frame;              /* out [batch][out_stride] the image of the row (NULL allowed) */
+  int32_t* pixel;              /* out [batch][out_stride] v * cols + u of the row (NULL allowed) */
+  int32_t* n_out;              /* out [batch] rows of the output, the first n_base[b] included */
+  int32_t* n_total;            /* out [batch] n_base[b] + kept pixels, whatever out_stride is */
+  int32_t* n_skipped;          /* out [batch] frames without a usable pose */
+  int32_t* status;             /* out [batch] */
+  void* workspace;             /* prs_depth_cloud_workspace_bytes(...) bytes, 16-byte aligned */
+} prs_depth_cloud_batch;
+
+/* bytes of workspace a call needs: 4 * batch * frames * ceil(ceil(rows / step) * ceil(cols / step) / 1024), rounded up to 16
+ * (0: a size below 1, or sampled pixels beyond 2^31 - 1) */
+PRS_API uint64_t prs_depth_cloud_workspace_bytes(int32_t batch, int32_t frames, int32_t rows, int32_t cols, int32_t step);
+/* device pointers, asynchronous on the context's stream */
+PRS_API int prs_depth_cloud_batch_run(prs_context* ctx, const prs_depth_cloud_params* params, const prs_depth_cloud_batch* batch);
+/* sizeof prs_depth_cloud_params, prs_depth_cloud_batch as the library was compiled (bindings check) */
+PRS_API void prs_depth_cloud_struct_sizes(uint64_t* sizes2);
 
 #ifdef __cplusplus
 }

@@ -539,6 +539,22 @@ class RectifyBatch(C.Structure):
                 ("maps", C.c_void_p), ("map_of", C.c_void_p), ("n_border", C.c_void_p), ("status", C.c_void_p)]
 
 
+class DepthCloudParams(C.Structure):
+    """prs_depth_cloud_params"""
+    _fields_ = [("depth_type", C.c_int32), ("depth_scaling_factor_to_meters", C.c_float), ("fx", C.c_float), ("fy", C.c_float),
+                ("cx", C.c_float), ("cy", C.c_float), ("range_min", C.c_float), ("range_max", C.c_float), ("step", C.c_int32),
+                ("sensor_in_robot", C.c_float * 16), ("reserved", C.c_int32 * 3)]
+
+
+class DepthCloudBatch(C.Structure):
+    """prs_depth_cloud_batch (device pointers)"""
+    _fields_ = [("batch", C.c_int32), ("frames", C.c_int32), ("rows", C.c_int32), ("cols", C.c_int32), ("pitch", C.c_int32),
+                ("gray_pitch", C.c_int32), ("pose_stride", C.c_int32), ("out_stride", C.c_int32), ("depth", C.c_void_p), ("gray", C.c_void_p),
+                ("n_images", C.c_void_p), ("pose", C.c_void_p), ("frame_index", C.c_void_p), ("n_base", C.c_void_p), ("xyz", C.c_void_p),
+                ("frame", C.c_void_p), ("pixel", C.c_void_p), ("n_out", C.c_void_p), ("n_total", C.c_void_p), ("n_skipped", C.c_void_p),
+                ("status", C.c_void_p), ("workspace", C.c_void_p)]
+
+
 class DispatchEnv(C.Structure):
     """prs_dispatch_env: what a dispatch depends on outside its arguments (tests and tools)"""
     _fields_ = [(n, C.c_int32) for n in ("cus", "fused_align", "matcher_v3", "force_unstaged", "no_lone_gn", "merge_fused", "bf_mfma", "stamps",
@@ -702,6 +718,9 @@ SYMBOLS = {
     "prs_world_voxel_struct_sizes": (None, [C.POINTER(C.c_uint64)]),
     "prs_rectify_batch_run": (C.c_int, [_vp, C.POINTER(RectifyParams), C.POINTER(RectifyBatch)]),
     "prs_rectify_struct_sizes": (None, [C.POINTER(C.c_uint64)]),
+    "prs_depth_cloud_workspace_bytes": (C.c_uint64, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
+    "prs_depth_cloud_batch_run": (C.c_int, [_vp, C.POINTER(DepthCloudParams), C.POINTER(DepthCloudBatch)]),
+    "prs_depth_cloud_struct_sizes": (None, [C.POINTER(C.c_uint64)]),
     "prs_scene_clip_batch": (C.c_int, [_vp, C.POINTER(Projector), _vp, C.POINTER(ClipBatch)]),
     "prs_scene_clip": (C.c_int, [_vp, C.POINTER(Projector), _vp, _vp, _vp, _vp, C.c_int32, _vp, _vp, _vp, C.c_int32, _i32p]),
 }
@@ -781,5 +800,11 @@ def load():
         raise ImportError("libproslam_hip.so lays out prs_rectify_map / prs_rectify_params / prs_rectify_batch as %s bytes, the Python "
                           "binding as %s: rebuild with `python -c 'import __graft_entry__ as g; g.build()'`"
                           % (list(sizes), [C.sizeof(RectifyMap), C.sizeof(RectifyParams), C.sizeof(RectifyBatch)]))
+    sizes = (C.c_uint64 * 2)()
+    lib.prs_depth_cloud_struct_sizes(sizes)
+    if list(sizes) != [C.sizeof(DepthCloudParams), C.sizeof(DepthCloudBatch)]:
+        raise ImportError("libproslam_hip.so lays out prs_depth_cloud_params / prs_depth_cloud_batch as %s bytes, the Python binding as %s: "
+                          "rebuild with `python -c 'import __graft_entry__ as g; g.build()'`"
+                          % (list(sizes), [C.sizeof(DepthCloudParams), C.sizeof(DepthCloudBatch)]))
     _lib = lib
     return lib

@@ -2560,6 +2560,121 @@ def rgbd_params(cfg, selection_order=SELECT_LIBSTDCXX, max_raw_detections=32768,
     return ep, depth_params(depth_type, r["depth_scaling_factor_to_meters"])
 
 
+# ---- dense RGB-D cloud: the depth pixels of a sequence's frames in the world frame (include/proslam_hip.h prs_depth_cloud_*) ----
+def depth_cloud_params(camera, range_min=0.1, range_max=10.0, step=1, depth_type="u16", scale=1.0, sensor_in_robot=None):
+    """prs_depth_cloud_params.  camera: a dictionary with fx, fy, cx, cy (configs.*["camera"]); range_min / range_max in metres
+    (the defaults of the reference's unprojection app); step: the pixel stride in both directions; depth_type "u16" / "f32" or a
+    PRS_DEPTH_* value; scale = depth_scaling_factor_to_meters (1e-3 for the 16-bit millimetre images of icl and tum);
+    sensor_in_robot [4, 4] or 16 values, row-major (None: the identity, the poses are the camera's)"""
+    p = _lib.DepthCloudParams()
+    if isinstance(depth_type, str) and depth_type not in _DEPTH_TYPES:
+        raise ValueError("depth_type: one of %s" % (sorted(_DEPTH_TYPES),))
+    p.depth_type = _DEPTH_TYPES[depth_type] if isinstance(depth_type, str) else int(depth_type)
+    p.depth_scaling_factor_to_meters = float(scale)
+    p.fx, p.fy, p.cx, p.cy = (float(camera[k]) for k in ("fx", "fy", "cx", "cy"))
+    p.range_min, p.range_max, p.step = float(range_min), float(range_max), int(step)
+    S = np.eye(4, dtype=np.float32) if sensor_in_robot is None else np.asarray(sensor_in_robot, np.float32).reshape(4, 4)
+    p.sensor_in_robot[:] = [float(x) for x in S.reshape(16)]
+    values = [p.depth_scaling_factor_to_meters, p.fx, p.fy, p.cx, p.cy, p.range_min, p.range_max] + list(p.sensor_in_robot)
+    if not np.isfinite(values).all():
+        raise ValueError("every parameter must be finite as a float32")
+    if not p.depth_scaling_factor_to_meters > 0.0:
+        raise ValueError("scale must be positive as a float32")
+    if not 0.0 <= p.range_min <= p.range_max:
+        raise ValueError("0 <= range_min <= range_max must hold")
+    if p.step < 1:
+        raise ValueError("step must be at least 1")
+    return p
+
+
+class DepthCloudBatch:
+    """the dense clouds of B sequences of up to `frames` depth images of rows x cols pixels: owns xyz (out_stride rows per
+    sequence), the per-sequence counts and the workspace.  outputs: which of the optional arrays ("frame", "pixel") are kept; they
+    are exposed as `node` and `row`, with n_opt = desc = None, so that WorldVoxelBatch.run(ctx, p, this) reads the cloud in place.
+    The workspace is sized for step 1, which fits every step."""
+
+    OPTIONAL = ("frame", "pixel")
+
+    def __init__(self, batch, frames, rows, cols, out_stride, outputs=OPTIONAL, device=0):
+        import torch
+        if set(outputs) - set(self.OPTIONAL):
+            raise ValueError("outputs: a subset of %s" % (self.OPTIONAL,))
+        B, F, n = int(batch), int(frames), int(out_stride)
+        if B < 1 or F < 1 or int(rows) < 1 or int(cols) < 1 or n < 1:
+            raise ValueError("batch, frames, rows, cols and out_stride must be at least 1")
+        self.batch, self.frames, self.rows, self.cols, self.out_stride = B, F, int(rows), int(cols), n
+        dev = torch.device("cuda", device) if isinstance(device, int) else device
+        z = lambda shape, dt: torch.zeros(shape, dtype=dt, device=dev)  # noqa: E731
+        self.xyz = z((B, n, 4), torch.float32)
+        self.node = z((B, n), torch.int32) if "frame" in outputs else None  # the image of a row, where a world map has the node
+        self.row = z((B, n), torch.int32) if "pixel" in outputs else None   # v * cols + u, where a world map has the landmark's row
+        self.n_opt, self.desc = None, None
+        self.n_out, self.n_total, self.n_skipped = z((B,), torch.int32), z((B,), torch.int32), z((B,), torch.int32)
+        self.status = z((B,), torch.int32)
+        nbytes = int(_lib.load().prs_depth_cloud_workspace_bytes(B, F, self.rows, self.cols, 1))
+        if nbytes < 1:
+            raise ValueError("frames * rows * cols must stay below 2^31")
+        self.workspace = z((nbytes,), torch.uint8)
+
+    def descriptor(self, depth, pose, n_images, frame_index=None, gray=None, append=False, count_only=False):
+        """the prs_depth_cloud_batch of device tensors: depth [B, frames, rows, cols (or more: the pitch)] uint16 / float32, pose
+        [B, pose_stride, 16] float32, n_images [B] int32, frame_index [B, frames] int32 or None, gray like depth, uint8, or None"""
+        B, F = self.batch, self.frames
+        if depth.dim() != 4 or tuple(depth.shape[:3]) != (B, F, self.rows) or int(depth.shape[3]) < self.cols or depth.stride(3) != 1:
+            raise ValueError("depth must be [%d, %d, %d, >= %d] with contiguous rows" % (B, F, self.rows, self.cols))
+        if int(depth.stride(1)) != self.rows * int(depth.stride(2)) or int(depth.stride(0)) != F * int(depth.stride(1)):
+            raise ValueError("the images of depth must follow one another at rows * pitch")
+        if pose.dim() != 3 or int(pose.shape[0]) != B or int(pose.shape[2]) != 16 or not pose.is_contiguous():
+            raise ValueError("pose must be a contiguous [%d, pose_stride, 16]" % B)
+        d = _lib.DepthCloudBatch()
+        d.batch, d.frames, d.rows, d.cols, d.out_stride = B, F, self.rows, self.cols, self.out_stride
+        d.pitch, d.pose_stride = int(depth.stride(2)) * depth.element_size(), int(pose.shape[1])
+        d.depth, d.pose, d.n_images = depth.data_ptr(), pose.data_ptr(), n_images.data_ptr()
+        if gray is not None:
+            if tuple(gray.shape[:3]) != (B, F, self.rows) or int(gray.shape[3]) < self.cols or gray.stride(3) != 1 or \
+                    int(gray.stride(1)) != self.rows * int(gray.stride(2)) or int(gray.stride(0)) != F * int(gray.stride(1)):
+                raise ValueError("gray must be laid out like depth")
+            d.gray, d.gray_pitch = gray.data_ptr(), int(gray.stride(2))
+        if frame_index is not None:
+            if tuple(frame_index.shape) != (B, F) or not frame_index.is_contiguous():
+                raise ValueError("frame_index must be a contiguous [%d, %d]" % (B, F))
+            d.frame_index = frame_index.data_ptr()
+        d.n_base = self.n_out.data_ptr() if append else None
+        for name in ("n_out", "n_total", "n_skipped", "status", "workspace"):
+            setattr(d, name, getattr(self, name).data_ptr())
+        if not count_only:
+            d.xyz = self.xyz.data_ptr()
+            d.frame = self.node.data_ptr() if self.node is not None else None
+            d.pixel = self.row.data_ptr() if self.row is not None else None
+        return d
+
+    def _launch(self, ctx, params, d):
+        rc = _lib.load().prs_depth_cloud_batch_run(ctx._h, C.byref(params), C.byref(d))
+        _check(ctx, rc, "prs_depth_cloud_batch_run")
+        return rc
+
+    def run(self, ctx, params, depth, pose, n_images, frame_index=None, gray=None, append=False):
+        """enqueue the clouds of every sequence (asynchronous); per-sequence status lands in self.status.  append: the rows go behind
+        the n_out rows an earlier call left, so a long sequence is fed chunk by chunk"""
+        return self._launch(ctx, params, self.descriptor(depth, pose, n_images, frame_index, gray, append))
+
+    def count(self, ctx, params, depth, pose, n_images, frame_index=None, gray=None, append=False):
+        """enqueue the count-only call (asynchronous): n_total, n_skipped and status; n_out stays (append) or becomes 0"""
+        return self._launch(ctx, params, self.descriptor(depth, pose, n_images, frame_index, gray, append, count_only=True))
+
+    def cloud_of(self, b):
+        """dict of numpy arrays trimmed to n_out rows, in the shape of WorldMapBatch.cloud_of (node is the image, row the pixel, bounds
+        None) plus n_skipped; copies to the host when called"""
+        n = min(max(int(self.n_out[b].item()), 0), self.out_stride)
+        out = dict(n_out=n, n_total=int(self.n_total[b].item()), n_skipped=int(self.n_skipped[b].item()), n_nonfinite=0,
+                   status=int(self.status[b].item()), xyz=self.xyz[b, :n].cpu().numpy().copy(), bounds=None)
+        for name in ("node", "row"):
+            t = getattr(self, name)
+            if t is not None:
+                out[name] = t[b, :n].cpu().numpy().copy()
+        return out
+
+
 # ---- image rectifier: undistort and stereo-rectify raw frames in front of the extractors (include/proslam_hip.h prs_rectify_*) ----
 DISTORTION_RADTAN = 0                                # PRS_DISTORTION_*
 PIXEL_U8, PIXEL_U16, PIXEL_F32 = 0, 1, 2             # PRS_PIXEL_*
