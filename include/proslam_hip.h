@@ -135,7 +135,9 @@ PRS_API int prs_version(void);
  * prs_world_voxel_params, prs_world_voxel_batch, prs_world_voxel_workspace_bytes, prs_world_voxel_batch_run and
  * prs_world_voxel_struct_sizes; and the image rectifier: prs_rectify_map, prs_rectify_params, prs_rectify_batch, prs_rectify_batch_run
  * and prs_rectify_struct_sizes; and the dense RGB-D cloud: prs_depth_cloud_params, prs_depth_cloud_batch,
- * prs_depth_cloud_workspace_bytes, prs_depth_cloud_batch_run and prs_depth_cloud_struct_sizes).  Callers memset() parameter structs before
+ * prs_depth_cloud_workspace_bytes, prs_depth_cloud_batch_run and prs_depth_cloud_struct_sizes; and dense stereo:
+ * prs_dense_stereo_params, prs_dense_stereo_batch, prs_dense_stereo_workspace_bytes, prs_dense_stereo_batch_run and
+ * prs_dense_stereo_struct_sizes).  Callers memset() parameter structs before
  * filling them, so that fields they do not know select the shipped defaults (all zero). */
 #define PRS_ABI_VERSION 104
 PRS_API int prs_abi_check(int32_t header_version, uint64_t sizeof_stereo_params, uint64_t sizeof_pcf_params, uint64_t sizeof_aligner_params,
@@ -2413,6 +2415,93 @@ PRS_API uint64_t prs_depth_cloud_workspace_bytes(int32_t batch, int32_t frames, 
 PRS_API int prs_depth_cloud_batch_run(prs_context* ctx, const prs_depth_cloud_params* params, const prs_depth_cloud_batch* batch);
 /* sizeof prs_depth_cloud_params, prs_depth_cloud_batch as the library was compiled (bindings check) */
 PRS_API void prs_depth_cloud_struct_sizes(uint64_t* sizes2);
+
+/* ================================================================================================
+ * Dense stereo: a rectified pair to a dense disparity and depth image, between the rectifier's dst (left block, then right block:
+ * the two pointers are separate, so it is read in place) and prs_depth_cloud_batch.depth (PRS_DEPTH_F32, scale 1: a depth of 0 is
+ * what that stage drops).
+ *
+ * BUILD-DEFINED: the reference has no dense matcher, so the rule below is this build's.  Every decision is integer arithmetic; the
+ * only rounded operations are one float32 division and one addition a pixel (sub-pixel) and one division (depth), correctly rounded,
+ * -ffp-contract=off.  tests/dense_stereo_ref.py restates it in numpy and the kernels equal that byte for byte.  I(y, x) is the
+ * pixel at clamped coordinates, y into [0, rows - 1], x into [0, cols - 1]; so are all coordinates below.
+ *
+ *   census       c(y, x): a 62-bit word, one bit per offset dy = -3 .. 3, dx = -4 .. 4 but the centre, I(y + dy, x + dx) < I(y, x).
+ *                Only Hamming distances of the words are used.  cL of the left image, cR of the right.
+ *   raw cost     d = min_disparity + i, i = 0 .. n_disparities - 1.  C_L(y, x, d) = popcount(cL(y, x) ^ cR(y, max(x - d, 0))),
+ *                C_R(y, x, d) = popcount(cR(y, x) ^ cL(y, min(x + d, cols - 1))).
+ *   aggregation  A_L(v, u, d) = the sum over dy, dx in [-r, r] of C_L(clamp(v + dy), clamp(u + dx), d), r = aggregation_radius;
+ *                A_R the same over C_R.  At most 62 * 15 * 15 = 13950.
+ *   admissible   d for a left pixel u iff u - d >= 0, for a right pixel x iff x + d <= cols - 1.  Every minimum runs over
+ *                admissible d only; a pixel without one is invalid.
+ *   winner       d* = the admissible d of least A, the lowest on a tie; A0 its cost.  A2 = the least A over admissible d with
+ *                |d - d*| >= 2, or none.
+ *   uniqueness   left only, uniqueness_percent = q > 0: kept iff A2 is none or 100 * A0 < (100 - q) * A2 in integers (strict: a
+ *                flat region is rejected).  q = 0 keeps everything.
+ *   left-right   lr_max_diff >= 0 (-1 turns the right pass off): with xr = u - d* and dR(v, xr) the winner of A_R at the right
+ *                pixel (no uniqueness test), kept iff the right pixel has a winner and |dR - d*| <= lr_max_diff.
+ *   sub-pixel    when d* - 1 and d* + 1 are both in the disparity range and admissible and
+ *                den = (A(d* - 1) + A(d* + 1)) - 2 * A0 > 0: delta = (float) (A(d* - 1) - A(d* + 1)) / (float) (2 * den);
+ *                otherwise delta = 0.  s = (float) d* + delta.
+ *   output       valid iff kept and s > 0.  disparity(v, u) = s and depth(v, u) = bf / s when valid, else 0.0f both; bf = focal
+ *                length * baseline in pixel * metres.  n_valid[b][f] = the valid pixels of the image.  Pad columns are not touched.
+ *   sequences    images f >= n_images[b] are not touched (n_images NULL: frames).  status[b] = PRS_ERR_RANGE when n_images[b]
+ *                lies outside [0, frames], and nothing of that sequence is written; otherwise PRS_OK.
+ * Call-level (return value, nothing launched, outputs untouched): PRS_ERR_NULL (a struct, left, right, status or the workspace
+ * unset, or disparity and depth both unset); PRS_ERR_RANGE (n_disparities outside 1 .. 256, min_disparity < 0 or
+ * min_disparity + n_disparities > 4096, aggregation_radius outside 0 .. 7, uniqueness_percent outside 0 .. 99, lr_max_diff outside
+ * -1 .. 255, bf not finite or <= 0; batch, frames, rows or cols < 1, left_pitch or right_pitch < cols, out_pitch < 4 * cols or not a
+ * multiple of 4); PRS_ERR_UNSUPPORTED (disparity, depth, n_images, n_valid or status not 4-byte aligned, the workspace not 16-byte;
+ * batch * frames * rows * cols beyond 2^31 - 1; a grid beyond 2^31 - 1 workgroups).
+ * Four plain launches on the context's stream (three with lr_max_diff = -1): census (a workgroup per 64 x 16 tile of an image, the
+ * tile and its halo in LDS once), match for the left and for the right reference and each radius (a workgroup owns 64 - 2 r columns of a band of 32
+ * rows and walks down it: lane x of each of its four waves is column x of the tile with its halo, a wave takes every fourth pair
+ * of disparities, two 16-bit sums to a word; the vertical sums live in LDS and get the entering row's costs added and the leaving
+ * row's subtracted, both recomputed by 64-bit popcounts from two staged census rows; 2 r + 1 LDS reads give the box sum, a packed
+ * (cost, i) minimum the winner; the cost volume is never stored) and finish (a workgroup 8 rows of an image: left-right check,
+ * outputs, n_valid by wave ballots and one integer atomic add a workgroup).  No persistent workgroup and no spinning; no allocation, no synchronisation, no host read: graph-capturable.
+ * Everything transient lives in the caller's workspace, which two calls in flight must not share.  Left out, with reserved words
+ * in the parameters for them: semi-global path aggregation, a speckle filter, a median or hole filling, other census windows,
+ * 16-bit images.  There is no host-pointer variant and no C++ adapter in plugin/.
+ * ============================================================================================== */
+typedef struct {
+  int32_t n_disparities;       /* 1 .. 256 */
+  int32_t min_disparity;       /* >= 0, min_disparity + n_disparities <= 4096 */
+  int32_t aggregation_radius;  /* r, 0 .. 7: a (2 r + 1)^2 box */
+  int32_t uniqueness_percent;  /* q, 0 .. 99; 0 = no test */
+  int32_t lr_max_diff;         /* -1 .. 255; -1 = no right pass */
+  float bf;                    /* focal length * baseline, pixel * metres, finite and > 0 */
+  int32_t reserved[6];
+} prs_dense_stereo_params;
+
+/* device pointers */
+typedef struct {
+  int32_t batch;
+  int32_t frames;              /* pairs per sequence */
+  int32_t rows, cols;
+  int32_t left_pitch;          /* bytes */
+  int32_t right_pitch;         /* bytes */
+  int32_t out_pitch;           /* bytes of a row of disparity and of depth, a multiple of 4 */
+  int32_t reserved0;
+  const uint8_t* left;         /* in [batch][frames][rows][left_pitch] */
+  const uint8_t* right;        /* in [batch][frames][rows][right_pitch] */
+  const int32_t* n_images;     /* in [batch] (NULL allowed: frames) */
+  float* disparity;            /* out [batch][frames][rows][out_pitch / 4] (NULL allowed when depth is set) */
+  float* depth;                /* out [batch][frames][rows][out_pitch / 4] (NULL allowed when disparity is set) */
+  int32_t* n_valid;            /* out [batch][frames] (NULL allowed) */
+  int32_t* status;             /* out [batch] */
+  void* workspace;             /* prs_dense_stereo_workspace_bytes(...) bytes, 16-byte aligned */
+} prs_dense_stereo_batch;
+
+/* bytes of workspace a call needs.  With P = batch * frames * rows * cols and up16(x) = x rounded up to a multiple of 16:
+ * 3 * up16(8 P) (the two census images and the left pass's records) + up16(2 P) when lr_check != 0 (the right pass's winners).
+ * n_disparities does not enter but through its range.  0: a size below 1, n_disparities outside 1 .. 256, or P beyond 2^31 - 1 */
+PRS_API uint64_t prs_dense_stereo_workspace_bytes(int32_t batch, int32_t frames, int32_t rows, int32_t cols, int32_t n_disparities,
+                                                  int32_t lr_check);
+/* device pointers, asynchronous on the context's stream */
+PRS_API int prs_dense_stereo_batch_run(prs_context* ctx, const prs_dense_stereo_params* params, const prs_dense_stereo_batch* batch);
+/* sizeof prs_dense_stereo_params, prs_dense_stereo_batch as the library was compiled (bindings check) */
+PRS_API void prs_dense_stereo_struct_sizes(uint64_t* sizes2);
 
 #ifdef __cplusplus
 }

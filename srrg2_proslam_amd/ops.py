@@ -2675,6 +2675,107 @@ class DepthCloudBatch:
         return out
 
 
+# ---- dense stereo: rectified pairs to disparity and depth images (include/proslam_hip.h prs_dense_stereo_*) ----
+def dense_stereo_params(camera, n_disparities=128, min_disparity=0, aggregation_radius=3, uniqueness_percent=10, lr_max_diff=1):
+    """prs_dense_stereo_params.  camera: a dictionary with fx and baseline_m (configs.*["camera"], or the one ops.stereo_rectification
+    returns); bf = float32(float64(fx) * float64(baseline_m)).  Disparities min_disparity .. min_disparity + n_disparities - 1, a box of
+    (2 * aggregation_radius + 1)^2 census costs, uniqueness_percent 0 = no test, lr_max_diff -1 = no left-right check.  Raises
+    ValueError on every value the library refuses"""
+    p = _lib.DenseStereoParams()
+    p.n_disparities, p.min_disparity, p.aggregation_radius = int(n_disparities), int(min_disparity), int(aggregation_radius)
+    p.uniqueness_percent, p.lr_max_diff = int(uniqueness_percent), int(lr_max_diff)
+    with np.errstate(over="ignore"):  # a product beyond float32 becomes inf and is refused below
+        p.bf = float(np.float32(np.float64(camera["fx"]) * np.float64(camera["baseline_m"])))
+    if not 1 <= p.n_disparities <= 256:
+        raise ValueError("n_disparities must lie in 1 .. 256")
+    if p.min_disparity < 0 or p.min_disparity + p.n_disparities > 4096:
+        raise ValueError("min_disparity must be at least 0 and min_disparity + n_disparities at most 4096")
+    if not 0 <= p.aggregation_radius <= 7:
+        raise ValueError("aggregation_radius must lie in 0 .. 7")
+    if not 0 <= p.uniqueness_percent <= 99:
+        raise ValueError("uniqueness_percent must lie in 0 .. 99")
+    if not -1 <= p.lr_max_diff <= 255:
+        raise ValueError("lr_max_diff must lie in -1 .. 255")
+    if not (np.isfinite(p.bf) and p.bf > 0.0):
+        raise ValueError("fx * baseline_m must be finite and positive as a float32")
+    return p
+
+
+class DenseStereoBatch:
+    """dense stereo of B sequences of up to `frames` rectified pairs of rows x cols pixels: owns the outputs named in `outputs`
+    (disparity and depth [B, frames, rows, cols] float32 views of rows padded to a multiple of four floats, n_valid [B, frames]),
+    status and the workspace, which is sized for the left-right check.  depth is what DepthCloudBatch.run takes with
+    depth_type="f32" and scale 1."""
+
+    OUTPUTS = ("disparity", "depth", "n_valid")
+
+    def __init__(self, batch, frames, rows, cols, outputs=OUTPUTS, device=0):
+        import torch
+        if set(outputs) - set(self.OUTPUTS):
+            raise ValueError("outputs: a subset of %s" % (self.OUTPUTS,))
+        if "disparity" not in outputs and "depth" not in outputs:
+            raise ValueError("outputs: disparity, depth or both")
+        B, F = int(batch), int(frames)
+        if B < 1 or F < 1 or int(rows) < 1 or int(cols) < 1:
+            raise ValueError("batch, frames, rows and cols must be at least 1")
+        self.batch, self.frames, self.rows, self.cols = B, F, int(rows), int(cols)
+        dev = torch.device("cuda", device) if isinstance(device, int) else device
+        z = lambda shape, dt: torch.zeros(shape, dtype=dt, device=dev)  # noqa: E731
+        padded = (self.cols + 3) // 4 * 4
+        self._disparity = z((B, F, self.rows, padded), torch.float32) if "disparity" in outputs else None
+        self._depth = z((B, F, self.rows, padded), torch.float32) if "depth" in outputs else None
+        self.disparity = self._disparity[..., :self.cols] if self._disparity is not None else None
+        self.depth = self._depth[..., :self.cols] if self._depth is not None else None
+        self.out_pitch = padded * 4
+        self.n_valid = z((B, F), torch.int32) if "n_valid" in outputs else None
+        self.status = z((B,), torch.int32)
+        nbytes = int(_lib.load().prs_dense_stereo_workspace_bytes(B, F, self.rows, self.cols, 1, 1))
+        if nbytes < 1:
+            raise ValueError("batch * frames * rows * cols must stay below 2^31")
+        self.workspace = z((nbytes,), torch.uint8)
+
+    def _images(self, t, name):
+        """(pointer, pitch in bytes) of a uint8 tensor [B, frames, rows, cols] or [B * frames, rows, cols] whose images follow one
+        another at rows * pitch (a pitch above cols is allowed)"""
+        import torch
+        B, F, rows, cols = self.batch, self.frames, self.rows, self.cols
+        if t.dtype != torch.uint8 or t.stride(-1) != 1 or tuple(t.shape) not in ((B, F, rows, cols), (B * F, rows, cols)):
+            raise ValueError("%s must be a uint8 tensor [%d, %d, %d, %d] or [%d, %d, %d] with contiguous rows" % (name, B, F, rows, cols, B * F, rows, cols))
+        pitch = int(t.stride(-2))
+        image = rows * pitch
+        if t.dim() == 4:
+            dense = (F == 1 or int(t.stride(1)) == image) and (B == 1 or int(t.stride(0)) == F * image)
+        else:
+            dense = B * F == 1 or int(t.stride(0)) == image
+        if pitch < cols or not dense:
+            raise ValueError("the images of %s must follow one another at rows * pitch" % name)
+        return t.data_ptr(), pitch
+
+    def descriptor(self, left, right, n_images=None):
+        """the prs_dense_stereo_batch of device tensors: left, right uint8 [B, frames, rows, cols] or [B * frames, rows, cols] (the two
+        halves of a RectifyBatch's dst, with their pitch), n_images [B] int32 or None = frames"""
+        d = _lib.DenseStereoBatch()
+        d.batch, d.frames, d.rows, d.cols, d.out_pitch = self.batch, self.frames, self.rows, self.cols, self.out_pitch
+        d.left, d.left_pitch = self._images(left, "left")
+        d.right, d.right_pitch = self._images(right, "right")
+        if n_images is not None:
+            if tuple(n_images.shape) != (self.batch,) or n_images.dtype != self.status.dtype or not n_images.is_contiguous():
+                raise ValueError("n_images must be a contiguous int32 tensor [%d]" % self.batch)
+            d.n_images = n_images.data_ptr()
+        d.disparity = self._disparity.data_ptr() if self._disparity is not None else None
+        d.depth = self._depth.data_ptr() if self._depth is not None else None
+        d.n_valid = self.n_valid.data_ptr() if self.n_valid is not None else None
+        d.status, d.workspace = self.status.data_ptr(), self.workspace.data_ptr()
+        return d
+
+    def run(self, ctx, params, left, right, n_images=None):
+        """enqueue the disparity and depth images of every pair (asynchronous); per-sequence status lands in self.status"""
+        d = self.descriptor(left, right, n_images)
+        rc = _lib.load().prs_dense_stereo_batch_run(ctx._h, C.byref(params), C.byref(d))
+        _check(ctx, rc, "prs_dense_stereo_batch_run")
+        return rc
+
+
 # ---- image rectifier: undistort and stereo-rectify raw frames in front of the extractors (include/proslam_hip.h prs_rectify_*) ----
 DISTORTION_RADTAN = 0                                # PRS_DISTORTION_*
 PIXEL_U8, PIXEL_U16, PIXEL_F32 = 0, 1, 2             # PRS_PIXEL_*
