@@ -137,7 +137,8 @@ PRS_API int prs_version(void);
  * and prs_rectify_struct_sizes; and the dense RGB-D cloud: prs_depth_cloud_params, prs_depth_cloud_batch,
  * prs_depth_cloud_workspace_bytes, prs_depth_cloud_batch_run and prs_depth_cloud_struct_sizes; and dense stereo:
  * prs_dense_stereo_params, prs_dense_stereo_batch, prs_dense_stereo_workspace_bytes, prs_dense_stereo_batch_run and
- * prs_dense_stereo_struct_sizes).  Callers memset() parameter structs before
+ * prs_dense_stereo_struct_sizes; and the speckle filter: prs_speckle_params, prs_speckle_batch, prs_speckle_workspace_bytes,
+ * prs_speckle_batch_run and prs_speckle_struct_sizes).  Callers memset() parameter structs before
  * filling them, so that fields they do not know select the shipped defaults (all zero). */
 #define PRS_ABI_VERSION 104
 PRS_API int prs_abi_check(int32_t header_version, uint64_t sizeof_stereo_params, uint64_t sizeof_pcf_params, uint64_t sizeof_aligner_params,
@@ -2461,8 +2462,9 @@ PRS_API void prs_depth_cloud_struct_sizes(uint64_t* sizes2);
  * (cost, i) minimum the winner; the cost volume is never stored) and finish (a workgroup 8 rows of an image: left-right check,
  * outputs, n_valid by wave ballots and one integer atomic add a workgroup).  No persistent workgroup and no spinning; no allocation, no synchronisation, no host read: graph-capturable.
  * Everything transient lives in the caller's workspace, which two calls in flight must not share.  Left out, with reserved words
- * in the parameters for them: semi-global path aggregation, a speckle filter, a median or hole filling, other census windows,
- * 16-bit images.  There is no host-pointer variant and no C++ adapter in plugin/.
+ * in the parameters for them: semi-global path aggregation, a median or hole filling, other census windows, 16-bit images; the
+ * speckle filter is a stage of its own behind this one (prs_speckle_batch_run, below).  There is no host-pointer variant and no
+ * C++ adapter in plugin/.
  * ============================================================================================== */
 typedef struct {
   int32_t n_disparities;       /* 1 .. 256 */
@@ -2502,6 +2504,81 @@ PRS_API uint64_t prs_dense_stereo_workspace_bytes(int32_t batch, int32_t frames,
 PRS_API int prs_dense_stereo_batch_run(prs_context* ctx, const prs_dense_stereo_params* params, const prs_dense_stereo_batch* batch);
 /* sizeof prs_dense_stereo_params, prs_dense_stereo_batch as the library was compiled (bindings check) */
 PRS_API void prs_dense_stereo_struct_sizes(uint64_t* sizes2);
+
+/* ================================================================================================
+ * Speckle filter: the small connected segments of a disparity or depth image are set to 0, in place, between
+ * prs_dense_stereo_batch.disparity (with depth as the companion) or a 16-bit depth image (prs_depth_batch.depth, the rectifier's
+ * dst) and prs_depth_cloud_batch.depth, which drops a depth of 0.
+ *
+ * BUILD-DEFINED: the reference has no dense images, so the rule below is this build's; it follows OpenCV's filterSpeckles (the
+ * speckleWindowSize and speckleRange of StereoBM / StereoSGBM).  Every decision is exact: one float32 subtraction and comparison a
+ * pair of neighbours, integers otherwise.  tests/speckle_ref.py restates it in numpy and the kernels equal that byte for byte.
+ * Per image f < n_images[b] of sequence b, independently; x(v, u) is the element of PRS_PIXEL_F32 or PRS_PIXEL_U16 (the
+ * rectifier's constants) at row v, column u < cols:
+ *
+ *   valid        x(v, u) > 0.  For a float that drops NaN, +0, -0 and negative values; +inf is valid.
+ *   connected    two 4-neighbours (left / right, up / down) iff both are valid and fabsf((float) a - (float) b) <= max_diff: one
+ *                float32 subtraction, exact for 16-bit values.  inf - inf is NaN, so two +inf neighbours are not connected.
+ *                Components are the transitive closure: a ramp of steps of max_diff is one component whatever its ends differ
+ *                by.  Pad elements behind cols and the neighbouring images are never neighbours.
+ *   label        label(v, u) = the least raster index v * cols + u over the pixel's component; -1 for an invalid pixel.
+ *   removal      a component of at most max_size pixels is removed: each of its pixels becomes 0 in image, and so does the
+ *                element at the same (v, u) of companion when one is given (its own pixel type and pitch; whatever it held).
+ *                No other element of either array is written, pad columns included.  max_size = 0 removes nothing.
+ *   counts       n_kept[b][f] = the valid pixels left, n_removed[b][f] = the valid pixels set to 0.
+ *   label output the labels as they stood before the removal, with their own pitch; pad columns are not written.
+ *   sequences    images f >= n_images[b] are not touched (n_images NULL: frames).  status[b] = PRS_ERR_RANGE when n_images[b]
+ *                lies outside [0, frames], and nothing of that sequence is written; otherwise PRS_OK.
+ * Call-level (return value, nothing launched, outputs untouched): PRS_ERR_NULL (a struct, image, status or the workspace unset);
+ * PRS_ERR_RANGE (batch, frames, rows or cols < 1; pitch -- or, with the array set, companion_pitch or label_pitch -- below cols
+ * elements or not a multiple of the element size; max_diff not finite or < 0; max_size < 0); PRS_ERR_UNSUPPORTED (a pixel_type
+ * -- or, with a companion, a companion_type -- that is unknown or PRS_PIXEL_U8; image or companion not aligned to its element,
+ * n_images, label, n_kept, n_removed or status not 4-byte aligned, the workspace not 16-byte; companion or label overlapping
+ * image; rows * cols or batch * frames * rows * cols beyond 2^31 - 1; a grid beyond 2^31 - 1 workgroups).
+ * Four plain launches on the context's stream (three for an image of one tile): tile (a workgroup per 64 x 16 tile of an image:
+ * the values in LDS, the runs of each row from one wave ballot, vertical unions in LDS, flattened, out goes the raster index of
+ * the tile's root), seam (a thread per pixel pair across a tile border: the same union in global memory), flatten (a workgroup
+ * 2048 pixels: each pixel's root, and the runs of equal roots in a wave add their lengths to the root's size until that is seen
+ * above max_size) and apply (a workgroup 2048 pixels: the zeroes, label, and the counts by wave ballots and one integer atomic add
+ * a workgroup and counter).  The atomics are integer min and add, so no output byte depends on the order they arrive in; every
+ * loop strictly lowers an index or leaves; no workgroup waits for another.  No allocation, no synchronisation, no host read: graph-capturable.  Everything transient lives in
+ * the caller's workspace, which two calls in flight must not share.  Left out: 8-connectivity, a median or hole filling, an
+ * out-of-place destination (the caller clones what it wants to keep), a host-pointer variant and a C++ adapter in plugin/.
+ * ============================================================================================== */
+typedef struct {
+  int32_t pixel_type;      /* of image: PRS_PIXEL_U16 or PRS_PIXEL_F32 */
+  int32_t companion_type;  /* of companion, read when one is given: PRS_PIXEL_U16 or PRS_PIXEL_F32 */
+  float max_diff;          /* finite and >= 0: neighbours this close are connected */
+  int32_t max_size;        /* >= 0: components of at most this many pixels are removed; 0 removes nothing */
+  int32_t reserved[4];
+} prs_speckle_params;
+
+/* device pointers */
+typedef struct {
+  int32_t batch;
+  int32_t frames;              /* images per sequence */
+  int32_t rows, cols;
+  int32_t pitch;               /* bytes of a row of image, a multiple of its element's size */
+  int32_t companion_pitch;     /* bytes of a row of companion, a multiple of its element's size */
+  int32_t label_pitch;         /* bytes of a row of label, a multiple of 4 */
+  int32_t reserved0;
+  void* image;                 /* in, out [batch][frames][rows][pitch] */
+  void* companion;             /* in, out [batch][frames][rows][companion_pitch] (NULL allowed); must not overlap image */
+  const int32_t* n_images;     /* in [batch] (NULL allowed: frames) */
+  int32_t* label;              /* out [batch][frames][rows][label_pitch / 4] (NULL allowed); must not overlap image */
+  int32_t* n_kept;             /* out [batch][frames] (NULL allowed) */
+  int32_t* n_removed;          /* out [batch][frames] (NULL allowed) */
+  int32_t* status;             /* out [batch] */
+  void* workspace;             /* prs_speckle_workspace_bytes(...) bytes, 16-byte aligned */
+} prs_speckle_batch;
+
+/* bytes of workspace a call needs.  With P = batch * frames * rows * cols and up16(x) = x rounded up to a multiple of 16:
+ * 2 * up16(4 P) (a parent and a size, int32, per pixel).  0: a size below 1, or rows * cols or P beyond 2^31 - 1 */
+PRS_API uint64_t prs_speckle_workspace_bytes(int32_t batch, int32_t frames, int32_t rows, int32_t cols);
+/* device pointers, asynchronous on the context's stream */
+PRS_API int prs_speckle_batch_run(prs_context* ctx, const prs_speckle_params* params, const prs_speckle_batch* batch);
+/* sizeof prs_speckle_params, prs_speckle_batch as the library was compiled (bindings check) */
+PRS_API void prs_speckle_struct_sizes(uint64_t* sizes2);
 
 #ifdef __cplusplus
 }

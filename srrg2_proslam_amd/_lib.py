@@ -569,6 +569,20 @@ class DenseStereoBatch(C.Structure):
                 ("workspace", C.c_void_p)]
 
 
+class SpeckleParams(C.Structure):
+    """prs_speckle_params"""
+    _fields_ = [("pixel_type", C.c_int32), ("companion_type", C.c_int32), ("max_diff", C.c_float), ("max_size", C.c_int32),
+                ("reserved", C.c_int32 * 4)]
+
+
+class SpeckleBatch(C.Structure):
+    """prs_speckle_batch (device pointers)"""
+    _fields_ = [("batch", C.c_int32), ("frames", C.c_int32), ("rows", C.c_int32), ("cols", C.c_int32), ("pitch", C.c_int32),
+                ("companion_pitch", C.c_int32), ("label_pitch", C.c_int32), ("reserved0", C.c_int32), ("image", C.c_void_p),
+                ("companion", C.c_void_p), ("n_images", C.c_void_p), ("label", C.c_void_p), ("n_kept", C.c_void_p), ("n_removed", C.c_void_p),
+                ("status", C.c_void_p), ("workspace", C.c_void_p)]
+
+
 class DispatchEnv(C.Structure):
     """prs_dispatch_env: what a dispatch depends on outside its arguments (tests and tools)"""
     _fields_ = [(n, C.c_int32) for n in ("cus", "fused_align", "matcher_v3", "force_unstaged", "no_lone_gn", "merge_fused", "bf_mfma", "stamps",
@@ -738,6 +752,9 @@ SYMBOLS = {
     "prs_dense_stereo_workspace_bytes": (C.c_uint64, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
     "prs_dense_stereo_batch_run": (C.c_int, [_vp, C.POINTER(DenseStereoParams), C.POINTER(DenseStereoBatch)]),
     "prs_dense_stereo_struct_sizes": (None, [C.POINTER(C.c_uint64)]),
+    "prs_speckle_workspace_bytes": (C.c_uint64, [C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
+    "prs_speckle_batch_run": (C.c_int, [_vp, C.POINTER(SpeckleParams), C.POINTER(SpeckleBatch)]),
+    "prs_speckle_struct_sizes": (None, [C.POINTER(C.c_uint64)]),
     "prs_scene_clip_batch": (C.c_int, [_vp, C.POINTER(Projector), _vp, C.POINTER(ClipBatch)]),
     "prs_scene_clip": (C.c_int, [_vp, C.POINTER(Projector), _vp, _vp, _vp, _vp, C.c_int32, _vp, _vp, _vp, C.c_int32, _i32p]),
 }
@@ -829,5 +846,10 @@ def load():
         raise ImportError("libproslam_hip.so lays out prs_dense_stereo_params / prs_dense_stereo_batch as %s bytes, the Python binding as "
                           "%s: rebuild with `python -c 'import __graft_entry__ as g; g.build()'`"
                           % (list(sizes), [C.sizeof(DenseStereoParams), C.sizeof(DenseStereoBatch)]))
+    lib.prs_speckle_struct_sizes(sizes)
+    if list(sizes) != [C.sizeof(SpeckleParams), C.sizeof(SpeckleBatch)]:
+        raise ImportError("libproslam_hip.so lays out prs_speckle_params / prs_speckle_batch as %s bytes, the Python binding as %s: "
+                          "rebuild with `python -c 'import __graft_entry__ as g; g.build()'`"
+                          % (list(sizes), [C.sizeof(SpeckleParams), C.sizeof(SpeckleBatch)]))
     _lib = lib
     return lib

@@ -222,6 +222,12 @@ REENTRY = {
 }
 
 
+# the speckle filter behind dense stereo or in front of the dense cloud (include/proslam_hip.h prs_speckle_params; ops.speckle_params).
+# BUILD-DEFINED: the reference has no dense images.  The values are the customary ones of OpenCV's StereoBM / StereoSGBM, a
+# speckleWindowSize of 100 - 200 pixels and a speckleRange of 1 - 2 disparities: the larger window, the tighter range
+SPECKLE = {"max_size": 200, "max_diff": 1.0}
+
+
 def _gate(mean_t, std_t, mean_r, std_r, where):
     return {"mean_translation": (mean_t,) * 3, "std_translation": (std_t,) * 3, "mean_rotation": (mean_r,) * 3,
             "std_rotation": (std_r,) * 3, "source": where}

@@ -301,6 +301,7 @@ int world_map_launch(prs_context* ctx, const prs_world_map_params* params, const
 int world_voxel_launch(prs_context* ctx, const prs_world_voxel_params* params, const prs_world_voxel_batch* batch);
 int depth_cloud_launch(prs_context* ctx, const prs_depth_cloud_params* params, const prs_depth_cloud_batch* batch);
 int dense_stereo_launch(prs_context* ctx, const prs_dense_stereo_params* params, const prs_dense_stereo_batch* batch);
+int speckle_launch(prs_context* ctx, const prs_speckle_params* params, const prs_speckle_batch* batch);
 int pose_compose_launch(prs_context* ctx, int batch, const float* prediction, const float* X, float* pose_out);
 int motion_predict_launch(prs_context* ctx, int batch, const float* prev2, const float* prev1, float* pred);
 int merge_batch_launch(prs_context* ctx, const prs_merger_params* params, const prs_merge_batch* batch);

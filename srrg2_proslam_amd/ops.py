@@ -2776,6 +2776,102 @@ class DenseStereoBatch:
         return rc
 
 
+# ---- speckle filter: the small segments of a disparity or depth image set to 0 in place (include/proslam_hip.h prs_speckle_*) ----
+def speckle_params(max_size=200, max_diff=1.0, pixel_type="f32", companion_type=None):
+    """prs_speckle_params.  Components of at most max_size pixels are removed (0: none); 4-neighbours are connected when both are
+    > 0 and differ by at most max_diff as float32 (the defaults are configs.SPECKLE); pixel_type "f32" / "u16" of the image,
+    companion_type of the companion image (None: pixel_type; read only when SpeckleFilterBatch.run is given a companion).  Raises
+    ValueError on every value the library refuses"""
+    types = {"u16": PIXEL_U16, "f32": PIXEL_F32}
+    if pixel_type not in types or (companion_type is not None and companion_type not in types):
+        raise ValueError("pixel_type and companion_type: one of %s" % (sorted(types),))
+    p = _lib.SpeckleParams()
+    p.pixel_type = types[pixel_type]
+    p.companion_type = p.pixel_type if companion_type is None else types[companion_type]
+    if int(max_size) != max_size or not 0 <= int(max_size) <= 0x7fffffff:
+        raise ValueError("max_size must be an integer in 0 .. 2^31 - 1")
+    p.max_size = int(max_size)
+    with np.errstate(over="ignore"):  # a value beyond float32 becomes inf and is refused below
+        p.max_diff = float(np.float32(max_diff))
+    if not (np.isfinite(p.max_diff) and p.max_diff >= 0.0):
+        raise ValueError("max_diff must be finite as a float32 and at least 0")
+    return p
+
+
+class SpeckleFilterBatch:
+    """the speckle filter of B sequences of up to `frames` images of rows x cols pixels, in place: owns the outputs named in `outputs`
+    (n_kept and n_removed [B, frames]; label [B, frames, rows, cols] int32, a view of rows padded to a multiple of four), status and
+    the workspace.  A DenseStereoBatch's disparity with its depth as the companion, or a RectifyBatch's 16-bit depth, go in as they
+    are; what comes out is what DepthCloudBatch.run takes."""
+
+    OUTPUTS = ("label", "n_kept", "n_removed")
+
+    def __init__(self, batch, frames, rows, cols, outputs=("n_kept", "n_removed"), device=0):
+        import torch
+        if set(outputs) - set(self.OUTPUTS):
+            raise ValueError("outputs: a subset of %s" % (self.OUTPUTS,))
+        B, F = int(batch), int(frames)
+        if B < 1 or F < 1 or int(rows) < 1 or int(cols) < 1:
+            raise ValueError("batch, frames, rows and cols must be at least 1")
+        self.batch, self.frames, self.rows, self.cols = B, F, int(rows), int(cols)
+        dev = torch.device("cuda", device) if isinstance(device, int) else device
+        z = lambda shape, dt: torch.zeros(shape, dtype=dt, device=dev)  # noqa: E731
+        padded = (self.cols + 3) // 4 * 4
+        self._label = z((B, F, self.rows, padded), torch.int32) if "label" in outputs else None
+        self.label = self._label[..., :self.cols] if self._label is not None else None
+        self.label_pitch = padded * 4
+        self.n_kept = z((B, F), torch.int32) if "n_kept" in outputs else None
+        self.n_removed = z((B, F), torch.int32) if "n_removed" in outputs else None
+        self.status = z((B,), torch.int32)
+        nbytes = int(_lib.load().prs_speckle_workspace_bytes(B, F, self.rows, self.cols))
+        if nbytes < 1:
+            raise ValueError("rows * cols and batch * frames * rows * cols must stay below 2^31")
+        self.workspace = z((nbytes,), torch.uint8)
+
+    def _images(self, t, name, pixel_type):
+        """(pointer, pitch in bytes) of a tensor of the pixel type, [B, frames, rows, cols] or [B * frames, rows, cols], whose images
+        follow one another at rows * pitch (a pitch above cols is allowed)"""
+        import torch
+        B, F, rows, cols = self.batch, self.frames, self.rows, self.cols
+        dtype = {PIXEL_U16: torch.uint16, PIXEL_F32: torch.float32}[pixel_type]
+        if t.dtype != dtype or t.stride(-1) != 1 or tuple(t.shape) not in ((B, F, rows, cols), (B * F, rows, cols)):
+            raise ValueError("%s must be a %s tensor [%d, %d, %d, %d] or [%d, %d, %d] with contiguous rows" % (name, dtype, B, F, rows, cols, B * F, rows, cols))
+        pitch = int(t.stride(-2))
+        image = rows * pitch
+        if t.dim() == 4:
+            dense = (F == 1 or int(t.stride(1)) == image) and (B == 1 or int(t.stride(0)) == F * image)
+        else:
+            dense = B * F == 1 or int(t.stride(0)) == image
+        if pitch < cols or not dense:
+            raise ValueError("the images of %s must follow one another at rows * pitch" % name)
+        return t.data_ptr(), pitch * t.element_size()
+
+    def descriptor(self, params, image, companion=None, n_images=None):
+        """the prs_speckle_batch of device tensors: image (and companion) of params' pixel types, n_images [B] int32 or None = frames"""
+        d = _lib.SpeckleBatch()
+        d.batch, d.frames, d.rows, d.cols = self.batch, self.frames, self.rows, self.cols
+        d.image, d.pitch = self._images(image, "image", params.pixel_type)
+        if companion is not None:
+            d.companion, d.companion_pitch = self._images(companion, "companion", params.companion_type)
+        if n_images is not None:
+            if tuple(n_images.shape) != (self.batch,) or n_images.dtype != self.status.dtype or not n_images.is_contiguous():
+                raise ValueError("n_images must be a contiguous int32 tensor [%d]" % self.batch)
+            d.n_images = n_images.data_ptr()
+        if self._label is not None:
+            d.label, d.label_pitch = self._label.data_ptr(), self.label_pitch
+        d.n_kept = self.n_kept.data_ptr() if self.n_kept is not None else None
+        d.n_removed = self.n_removed.data_ptr() if self.n_removed is not None else None
+        d.status, d.workspace = self.status.data_ptr(), self.workspace.data_ptr()
+        return d
+
+    def run(self, ctx, params, image, companion=None, n_images=None):
+        """enqueue the filter of every image, in place (asynchronous); per-sequence status lands in self.status"""
+        d = self.descriptor(params, image, companion, n_images)
+        rc = _lib.load().prs_speckle_batch_run(ctx._h, C.byref(params), C.byref(d))
+        _check(ctx, rc, "prs_speckle_batch_run")
+        return rc
+
+
 # ---- image rectifier: undistort and stereo-rectify raw frames in front of the extractors (include/proslam_hip.h prs_rectify_*) ----
 DISTORTION_RADTAN = 0                                # PRS_DISTORTION_*
 PIXEL_U8, PIXEL_U16, PIXEL_F32 = 0, 1, 2             # PRS_PIXEL_*
