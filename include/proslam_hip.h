@@ -1617,7 +1617,8 @@ PRS_API int prs_closure_merge_batch_run(prs_context* ctx, const prs_closure_merg
 /* sizeof prs_closure_merger_params, prs_closure_merge_batch as the library was compiled (bindings check) */
 PRS_API void prs_closure_merge_struct_sizes(uint64_t* sizes2);
 /* host pointers, one pair, arrays of `capacity` rows in the layout above (coords4 / state4 [capacity][4]; any of state4 ..
- * n_meas may be NULL; measurement4 [n_measured][4]).  Uploads, runs, downloads, synchronises; returns result->status. */
+ * n_meas may be NULL; measurement4 [n_measured][4]).  Uploads, runs, downloads, synchronises; returns result->status.  n_measured
+ * is the measurement_stride of the limits above: beyond them PRS_ERR_UNSUPPORTED, with result and every array as the caller left them. */
 PRS_API int prs_closure_merge(prs_context* ctx, const prs_closure_merger_params* params, int32_t capacity, int32_t* n_points,
                               float* coords4, uint8_t* desc, float* state4, float* covariance9, uint32_t* n_opt, uint8_t* inlier,
                               uint32_t* n_meas, const float* scene_in_world16, const float* measurement4,
@@ -1626,7 +1627,9 @@ PRS_API int prs_closure_merge(prs_context* ctx, const prs_closure_merger_params*
                               prs_merge_result* result);
 /* merges a measurement cloud into a device-resident map handle (prs_map_create), whose statistics arrays are kept up;
  * measurement4 [n_measured][4]; scene_in_world16 NULL = identity.  No frame is counted and the pose table is not touched.
- * Returns result->status. */
+ * Returns result->status.  The handle's max_measured is the call's measurement_stride and corr_stride: more measurements or
+ * correspondences than that is PRS_ERR_CAPACITY, and a handle created with max_measured > 16384 (or a capacity whose bitmap does
+ * not fit) gets PRS_ERR_UNSUPPORTED from every call, whatever n_measured; in both cases the map is left as it was. */
 PRS_API int prs_map_merge_closure(prs_map* h, const prs_closure_merger_params* params, const float* transform16,
                                   int32_t transform_is_scene_in_measurement, const float* scene_in_world16, const float* measurement4,
                                   const uint8_t* measurement_desc, int32_t n_measured, const prs_corr* corr, int32_t n_corr,

@@ -1,6 +1,7 @@
 """Inputs of the closure-merger tests, shared by the CPU suite (which checks that every case exercises what its name says, on the
 numpy rule) and the GPU suite (which compares the kernel with that rule byte for byte): the reference's ICL frames behind its two
-gtests (tests/test_mergers.cpp:174-246) and small synthetic pairs at the edges of the kernel's paths."""
+gtests (tests/test_mergers.cpp:174-246), small synthetic pairs at the edges of the kernel's paths (EDGES) and pairs of up to 16384
+measurements, a bitmap word for every thread of the kernel's workgroup (SIZES)."""
 import numpy as np
 
 import closure_merge_ref as cr
@@ -58,16 +59,21 @@ def rigid(seed, angle, shift):
 
 def synthetic(seed, n_scene, n_meas, n_corr, kind=cr.UVD, capacity=None, transform=None, inverse=0, from_aligner=0, with_stats=True,
               target=200, binning=1, row_bins=10, col_bins=30, n_invalid=0, n_behind=0, n_off_canvas=0, depth_ties=False,
-              corner=None, **kw):
+              corner=None, half_bins=False, landmarks_from=None, alias=0, **kw):
     """one pair.  The first n_corr measurements (shuffled) are matched to distinct landmarks: most lie within the merge distance
     of their landmark, a fifth further away, a tenth carry a response >= 50 (some exactly 50).  corner = (u0, v0, u1, v1) confines
-    the image positions to that box (so that few bins are hit)."""
+    the image positions to that box (so that few bins are hit).  half_bins snaps the positions to the middle of every 8 x 8 px cell
+    (8 k + 4): with bins of that width v / row_w and u / col_w are exact halves, where std::round and round-half-even part.
+    landmarks_from = r draws the matched landmarks from rows r .. n_scene - 1 only; with alias = a a quarter of them are named
+    again a rows further up (distinct landmarks whose indices agree in their low bits)."""
     rng = np.random.default_rng(seed)
     assert n_corr <= min(n_scene, n_meas)
     T = np.eye(4, dtype=f32) if transform is None else np.asarray(transform, f32)
     box = (0.0, 0.0, COLS - 1e-3, ROWS - 1e-3) if corner is None else corner
     u = rng.uniform(box[0], box[2], n_meas).astype(f32)
     v = rng.uniform(box[1], box[3], n_meas).astype(f32)
+    if half_bins:
+        u, v = np.floor(u / f32(8)) * f32(8) + f32(4), np.floor(v / f32(8)) * f32(8) + f32(4)
     d = rng.uniform(0.5, 6.0, n_meas).astype(f32)
     if depth_ties:
         d = np.round(d).astype(f32) + f32(1)  # few distinct depths: ties inside a bin go to the lowest index
@@ -91,7 +97,16 @@ def synthetic(seed, n_scene, n_meas, n_corr, kind=cr.UVD, capacity=None, transfo
     p, _ = cr.measurement_points(P, z)
     q = cr.apply_rows(cr.se3_inverse(T) if inverse else T, np.nan_to_num(p, nan=1.0, posinf=1.0, neginf=1.0))
     xyz = rng.uniform(-4, 4, (n_scene, 3)).astype(f32)
-    mi, si = rng.permutation(n_meas)[:n_corr], rng.permutation(n_scene)[:n_corr]
+    mi = rng.permutation(n_meas)[:n_corr]
+    if landmarks_from is None:
+        si = rng.permutation(n_scene)[:n_corr]
+    elif not alias:
+        si = landmarks_from + rng.permutation(n_scene - landmarks_from)[:n_corr]
+    else:
+        k = n_corr // 4
+        low = landmarks_from + rng.permutation(n_scene - alias - landmarks_from)[:k]
+        rest = np.setdiff1d(np.arange(landmarks_from, n_scene), np.concatenate([low, low + alias]))
+        si = rng.permutation(np.concatenate([low, low + alias, rng.permutation(rest)[:n_corr - 2 * k]]))
     noise = rng.normal(0, 0.05, (n_corr, 3))
     noise[rng.random(n_corr) < 0.2] += 2.0
     xyz[si] = (q[mi] + noise).astype(f32)
@@ -198,3 +213,142 @@ def error_batch():
         out.append((synthetic(seed=54, **base), {}, cr.OK))
         _cache["errors"] = out
     return _cache["errors"]
+
+
+# ---- the sizes of a real map: a bitmap word for every thread of the workgroup ----------------------------------------------------
+# A measurement bitmap of 16384 bits is 256 words, one per thread; wave w of the workgroup owns the words of measurements
+# 4096 w .. 4096 w + 4095.  The cases below put non-zero words, caps and winners into every wave.
+WAVE = 4096
+
+
+def per_wave(idx):
+    """how many of the measurement indices fall to each of the four waves"""
+    return np.bincount(np.asarray(idx, np.int64) // WAVE, minlength=4)[:4]
+
+
+def n_candidates(info, case):
+    """the valid measurements that were not merged"""
+    valid = cr.measurement_points(case["P"], case["measurement"])[1]
+    return int(valid.sum()) - int(valid[info["merged"]].sum())
+
+
+def merged_landmarks(info, case):
+    """the landmarks of the correspondences whose measurement was merged (exact where no two correspondences share a measurement)"""
+    a = case.get("corr_from_aligner", 0)
+    m, s = case["corr"]["fixed_idx" if a else "moving_idx"], case["corr"]["moving_idx" if a else "fixed_idx"]
+    return s[np.isin(m, info["merged"])]
+
+
+def rint_bins_differ(info, case):
+    """binned measurements whose bin would be another under round-half-even"""
+    P, z = case["P"], case["measurement"]
+    row_w, col_w = f32(P["canvas_rows"]) / f32(P["number_of_row_bins"]), f32(P["canvas_cols"]) / f32(P["number_of_col_bins"])
+    other = np.rint(z[:, 1] / row_w).astype(np.int64) * (P["number_of_col_bins"] + 2) + np.rint(z[:, 0] / col_w).astype(np.int64)
+    return int(((info["bins"] >= 0) & (info["bins"] != other)).sum())
+
+
+def share_measurement(c, k0, others):
+    """correspondences `others` are renamed to correspondence k0's measurement and their landmarks moved onto k0's landmark: several
+    landmarks merge with ONE measurement (only landmarks must be distinct), so n_measured - n_merged undercounts the candidates"""
+    a = c.get("corr_from_aligner", 0)
+    m, s = c["corr"]["fixed_idx" if a else "moving_idx"], c["corr"]["moving_idx" if a else "fixed_idx"]
+    m[others] = m[k0]
+    for name in ("coords", "state"):
+        if name in c["scene"]:
+            c["scene"][name][s[others], :3] = c["scene"][name][s[k0], :3]
+    return c
+
+
+_BINS = dict(row_bins=60, col_bins=80)
+_BIG = dict(n_scene=400, n_meas=16384)
+_all_added = lambda r, i, c: (r[2] == 0 and r[1] == n_candidates(i, c) and (per_wave(i["added"]) > 0).all() and r[0] > 256 * 5)  # noqa: E731
+_shared = lambda r, i, c: (r[2] == 0 and r[1] == i["n_to_add"] < n_candidates(i, c)  # noqa: E731
+                           and r[0] + n_candidates(i, c) < c["P"]["target_number_of_merges"] and len(i["merged"]) < r[0])
+
+# name -> (arguments of synthetic, predicate on (result, info, case)); "share" in the arguments is taken out by size()
+SIZES = {
+    "cap_in_wave_2": (dict(seed=61, **_BIG, n_corr=300, target=9000, binning=0),
+                      lambda r, i, c: r[2] == 0 and i["added"][-1] // WAVE == 2 and (i["added"][-1] + 1) % 64 != 0
+                      and (per_wave(i["added"])[:3] > 0).all() and per_wave(i["added"])[3] == 0),
+    "winners_in_all_waves": (dict(seed=62, **_BIG, n_corr=50, target=9000, **_BINS),
+                             lambda r, i, c: r[2] == 0 and (per_wave(i["pass1"]) > 0).all() and 0 < len(i["pass1"]) < r[1]
+                             and (per_wave(np.setdiff1d(i["added"], i["pass1"]))[:2] > 0).all()),
+    "pass1_cut_in_wave_1": (dict(seed=63, **_BIG, n_corr=50, target=1500, **_BINS),
+                            lambda r, i, c: r[2] == 0 and i["n_winners"] > len(i["pass1"]) == i["n_to_add"] == r[1] and i["pass1"][-1] // WAVE == 1),
+    **{"n_measured_%d" % n: (dict(seed=s, n_scene=400, n_meas=n, n_corr=50, target=4000, **_BINS),
+                             lambda r, i, c, n=n: r[2] == 0 and r[1] > 0 and (n != 4097 or 4096 in i["added"]))
+       for s, n in ((64, 4095), (65, 4096), (85, 4097))},  # (seed 85: measurement 4096 wins its bin, so pass 1 adds it)
+    **{"n_measured_%d" % n: (dict(seed=s, n_scene=5000, n_meas=n, n_corr=5000, target=100000), _all_added) for s, n in ((67, 16383), (68, 16384))},
+    # (target 12000, not 9000: pass 2 takes candidates in measurement order and has to get past wave 1)
+    "xyz_16384": (dict(seed=62, **_BIG, n_corr=50, target=12000, **_BINS, kind=cr.XYZ, n_behind=2000, n_off_canvas=2000, n_invalid=64),
+                  lambda r, i, c: r[2] == 0 and len(i["pass1"]) > 0
+                  and (per_wave(np.setdiff1d(i["added"], i["pass1"])[i["bins"][np.setdiff1d(i["added"], i["pass1"])] < 0]) > 0).sum() >= 3),
+    "from_aligner_inverse_16384": (dict(seed=61, **_BIG, n_corr=300, target=9000, binning=0, transform=_X, inverse=1, from_aligner=1),
+                                   lambda r, i, c: r[2] == 0 and r[0] > 100 and r[1] > 0),
+    "shared_measurement": (dict(seed=69, n_scene=300, n_meas=200, n_corr=100, target=1000, share=0), _shared),
+    "shared_measurement_16384": (dict(seed=70, **_BIG, n_corr=300, target=100000, **_BINS, share=3 * WAVE),
+                                 lambda r, i, c: _shared(r, i, c) and c["shared"] >= 3 * WAVE and c["shared"] in i["merged"]),
+    # (bins of 8 x 8 px: 62 x 82 of them fit the kernel's 64 KiB of LDS, the 122 x 82 of 4 px rows would be refused at the call)
+    "half_bins": (dict(seed=71, n_scene=100, n_meas=400, n_corr=10, target=150, row_bins=ROWS // 8, col_bins=COLS // 8, half_bins=True),
+                  lambda r, i, c: r[2] == 0 and rint_bins_differ(i, c) > 100 and 0 < len(i["pass1"]) and n_candidates(i, c) > i["n_to_add"]),
+    "high_landmarks": (dict(seed=72, n_scene=200000, n_meas=300, n_corr=257, target=1000, capacity=200320, landmarks_from=131072, alias=65536),
+                       lambda r, i, c: r[2] == 0 and r[0] > 50 and (c["corr"]["fixed_idx"] >= 131072).sum() >= 100
+                       and merged_landmarks(i, c).max() >= 131072 + 65536
+                       and np.isin(merged_landmarks(i, c) + 65536, merged_landmarks(i, c)).sum() >= 20),  # both of a pair 2^16 apart
+}
+
+
+def size(name):
+    """a case of SIZES, with the numpy rule's answer beside it (computed once: c["want"] = (scene after, result, info))"""
+    key = "size_" + name
+    if key not in _cache:
+        args, check = SIZES[name]
+        args = dict(args)
+        share = args.pop("share", None)
+        c = synthetic(**args)
+        if share is not None:  # the first correspondence whose measurement index is >= share takes nine others' landmarks
+            k0 = int(np.nonzero(c["corr"]["moving_idx"] >= share)[0][0])
+            share_measurement(c, k0, [k for k in range(k0 + 1, k0 + 10)])
+            c["shared"] = int(c["corr"]["moving_idx"][k0])
+        c["name"], c["check"] = name, check
+        c["want"] = want(c)
+        _cache[key] = c
+    return _cache[key]
+
+
+def error_batch_sizes():
+    """three pairs of one launch at full size: the first fault in vector order is a duplicate landmark (entry 16000) with a
+    measurement index out of range behind it (entry 16200); the same two swapped; a good pair.  -> [(case, code)]"""
+    if "errors_sizes" not in _cache:
+        base = dict(n_scene=20000, n_meas=16384, n_corr=16384, target=100000)
+        out = []
+        c = synthetic(seed=80, **base)
+        c["corr"]["fixed_idx"][16000] = c["corr"]["fixed_idx"][5]
+        c["corr"]["moving_idx"][16200] = 16384
+        out.append((c, cr.ERR_DUPLICATE))
+        c = synthetic(seed=81, **base)
+        c["corr"]["moving_idx"][16000] = 16384
+        c["corr"]["fixed_idx"][16200] = c["corr"]["fixed_idx"][5]
+        out.append((c, cr.ERR_RANGE))
+        out.append((synthetic(seed=82, **base), cr.OK))
+        for c, _ in out:
+            c["want"] = want(c)
+        _cache["errors_sizes"] = out
+    return _cache["errors_sizes"]
+
+
+def mixed_group():
+    """pairs of 16384, 4097, 1 and 0 measured and cap_in_wave_2 for ONE launch: a launch has one capacity and one set of parameters,
+    so all five take the group's largest capacity and the binning and target of winners_in_all_waves"""
+    if "mixed" not in _cache:
+        common = dict(target=9000, binning=1, **_BINS, capacity=5000 + 16384)
+        out = []
+        for name, args in (("n_measured_16384", SIZES["n_measured_16384"][0]), ("n_measured_4097", SIZES["n_measured_4097"][0]),
+                           ("n_measured_1", dict(seed=90, n_scene=400, n_meas=1, n_corr=1)),
+                           ("n_measured_0", dict(seed=91, n_scene=400, n_meas=0, n_corr=0)), ("cap_in_wave_2", SIZES["cap_in_wave_2"][0])):
+            c = synthetic(**dict(args, **common))
+            c["name"], c["want"] = "mixed " + name, None
+            c["want"] = want(c)
+            out.append(c)
+        _cache["mixed"] = out
+    return _cache["mixed"]

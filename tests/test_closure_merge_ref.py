@@ -113,6 +113,62 @@ def test_synthetic_case_is_what_its_name_says(name):
             assert S[k][n1:].tobytes() == c["scene"][k][n1:].tobytes(), k
 
 
+@pytest.mark.parametrize("name", sorted(cc.SIZES))
+def test_size_case_is_what_its_name_says(name):
+    """the cases of a bitmap word per thread (tests/test_closure_merge_sizes_gpu.py replays them on the device)"""
+    c = cc.size(name)
+    S, r, info = c["want"]
+    assert c["check"](r, info, c), (name, r, len(info["pass1"]), info["n_winners"], info["n_to_add"], cc.n_candidates(info, c),
+                                    list(cc.per_wave(info["added"])), list(cc.per_wave(info["pass1"])))
+    n0, n1 = c["scene"]["n_points"], S["n_points"]
+    assert n1 == n0 + r[1] <= c["scene"]["coords"].shape[0]
+    assert np.array_equal(S["coords"][:n0, 3], c["scene"]["coords"][:n0, 3])
+    for k in S:
+        if k != "n_points":
+            assert S[k][n1:].tobytes() == c["scene"][k][n1:].tobytes(), k
+
+
+def test_shared_measurement_undercounts_the_candidates():
+    """ten landmarks merge with one measurement: n_measured - n_merged caps the additions below the number of candidates although the
+    target is far away (here 133 candidates for at most 125 places)"""
+    c = cc.size("shared_measurement")
+    _, r, info = c["want"]
+    n_cand = cc.n_candidates(info, c)
+    assert r[1] == info["n_to_add"] == 200 - r[0] < n_cand and r[0] + n_cand < 1000
+    assert r[0] - len(info["merged"]) >= 5  # most of the ten share the measurement (a response >= 50 keeps one out)
+
+
+def test_half_bins_sit_where_the_two_roundings_part():
+    c = cc.size("half_bins")
+    z = c["measurement"]
+    assert np.array_equal(z[:, 0] % 8, np.full(400, 4, np.float32)) and np.array_equal(z[:, 1] % 8, np.full(400, 4, np.float32))
+    assert cc.rint_bins_differ(c["want"][2], c) > 200
+
+
+def test_mixed_group_shares_what_a_launch_shares():
+    cases = cc.mixed_group()
+    assert [len(c["measurement"]) for c in cases] == [16384, 4097, 1, 0, 16384]
+    assert all(c["P"] == cases[0]["P"] and len(c["scene"]["coords"]) == 5000 + 16384 for c in cases)
+    results = [c["want"][1] for c in cases]
+    assert all(r[2] == cr.OK for r in results) and results[3] == (0, 0, cr.OK) and results[2][0] + results[2][1] == 1
+    # with the group's parameters the two full pairs still use every wave, and pass 1 as well as pass 2
+    for c in (cases[0], cases[4]):
+        info = c["want"][2]
+        assert (cc.per_wave(info["added"]) > 0).all() and 0 < len(info["pass1"]) < len(info["added"])
+
+
+def test_size_error_cases_report_the_first_fault():
+    items = cc.error_batch_sizes()
+    assert [code for _, code in items] == [cr.ERR_DUPLICATE, cr.ERR_RANGE, cr.OK]
+    for c, code in items:
+        S, r, _ = c["want"]
+        assert r[2] == code and len(c["corr"]) == len(c["measurement"]) == 16384
+        if code != cr.OK:
+            assert r[:2] == (0, 0) and cr.scenes_equal(S, c["scene"])
+        else:
+            assert r[0] > 256 * 5 and r[1] > 0
+
+
 def test_error_cases_report_the_first_fault():
     for c, kw, code in cc.error_batch():
         S, r, _ = cc.want(c, **kw)
