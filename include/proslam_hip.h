@@ -138,7 +138,8 @@ PRS_API int prs_version(void);
  * prs_depth_cloud_workspace_bytes, prs_depth_cloud_batch_run and prs_depth_cloud_struct_sizes; and dense stereo:
  * prs_dense_stereo_params, prs_dense_stereo_batch, prs_dense_stereo_workspace_bytes, prs_dense_stereo_batch_run and
  * prs_dense_stereo_struct_sizes; and the speckle filter: prs_speckle_params, prs_speckle_batch, prs_speckle_workspace_bytes,
- * prs_speckle_batch_run and prs_speckle_struct_sizes).  Callers memset() parameter structs before
+ * prs_speckle_batch_run and prs_speckle_struct_sizes; and semi-global dense stereo: prs_sgm_stereo_params, prs_sgm_stereo_batch,
+ * prs_sgm_stereo_workspace_bytes, prs_sgm_stereo_batch_run and prs_sgm_stereo_struct_sizes).  Callers memset() parameter structs before
  * filling them, so that fields they do not know select the shipped defaults (all zero). */
 #define PRS_ABI_VERSION 104
 PRS_API int prs_abi_check(int32_t header_version, uint64_t sizeof_stereo_params, uint64_t sizeof_pcf_params, uint64_t sizeof_aligner_params,
@@ -2465,8 +2466,9 @@ PRS_API void prs_depth_cloud_struct_sizes(uint64_t* sizes2);
  * (cost, i) minimum the winner; the cost volume is never stored) and finish (a workgroup 8 rows of an image: left-right check,
  * outputs, n_valid by wave ballots and one integer atomic add a workgroup).  No persistent workgroup and no spinning; no allocation, no synchronisation, no host read: graph-capturable.
  * Everything transient lives in the caller's workspace, which two calls in flight must not share.  Left out, with reserved words
- * in the parameters for them: semi-global path aggregation, a median or hole filling, other census windows, 16-bit images; the
- * speckle filter is a stage of its own behind this one (prs_speckle_batch_run, below).  There is no host-pointer variant and no
+ * in the parameters for them: a median or hole filling, other census windows, 16-bit images; semi-global path aggregation is a
+ * stage of its own beside this one (prs_sgm_stereo_batch_run, below) and the speckle filter one behind it
+ * (prs_speckle_batch_run, below).  There is no host-pointer variant and no
  * C++ adapter in plugin/.
  * ============================================================================================== */
 typedef struct {
@@ -2582,6 +2584,113 @@ PRS_API uint64_t prs_speckle_workspace_bytes(int32_t batch, int32_t frames, int3
 PRS_API int prs_speckle_batch_run(prs_context* ctx, const prs_speckle_params* params, const prs_speckle_batch* batch);
 /* sizeof prs_speckle_params, prs_speckle_batch as the library was compiled (bindings check) */
 PRS_API void prs_speckle_struct_sizes(uint64_t* sizes2);
+
+/* ================================================================================================
+ * Semi-global dense stereo: a rectified pair to a dense disparity and depth image by path-aggregated census costs (Hirschmueller's
+ * SGM), a stage of its own beside prs_dense_stereo_batch_run with the same inputs, outputs and output layout, so the speckle
+ * filter and the dense cloud read its images in place.  Where the box matcher rejects every pixel of an untextured surface (its
+ * uniqueness test is strict on flat costs), the paths carry the disparity of the textured surroundings across it.
+ *
+ * BUILD-DEFINED: the reference has no dense matcher, so the rule below is this build's.  Every decision is integer arithmetic; the
+ * only rounded operations are one float32 division and one addition a pixel (sub-pixel) and one division (depth), correctly rounded,
+ * -ffp-contract=off.  tests/sgm_stereo_ref.py restates it in numpy and the kernels equal that byte for byte.  I(y, x) is the
+ * pixel at clamped coordinates, y into [0, rows - 1], x into [0, cols - 1]; so are all coordinates of census and raw cost.
+ *
+ *   census       c(y, x): a 62-bit word, one bit per offset dy = -3 .. 3, dx = -4 .. 4 but the centre, I(y + dy, x + dx) < I(y, x).
+ *                Only Hamming distances of the words are used.  cL of the left image, cR of the right.
+ *   raw cost     d_i = min_disparity + i, i = 0 .. n_disparities - 1.  C(y, x, i) = popcount(cL(y, x) ^ cR(y, max(x - d_i, 0))),
+ *                0 .. 62, defined for every i, admissible or not: admissibility enters only at the winner.
+ *   paths        n_paths = 4: the directions of travel (dy, dx) = (0, +1) (0, -1) (+1, 0) (-1, 0); n_paths = 8 adds (+1, +1)
+ *                (+1, -1) (-1, +1) (-1, -1).
+ *   path cost    for a pixel p and its predecessor q = p - (dy, dx): L_r(p, i) = C(p, i) when q lies outside the image; otherwise,
+ *                with m = min over k of L_r(q, k),
+ *                L_r(p, i) = C(p, i) + min(L_r(q, i), L_r(q, i - 1) + P1, L_r(q, i + 1) + P1, m + P2) - m,
+ *                terms with i - 1 or i + 1 outside 0 .. n_disparities - 1 left out.  P1 = p1 and P2 = p2 are constants (no
+ *                intensity-adaptive P2), 0 <= P1 <= P2 <= 4095, so L_r <= 62 + P2 <= 4157: a path cost does not fit a byte.
+ *   aggregate    S(p, i) = the sum of L_r(p, i) over the paths, at most 8 * 4157 = 33256: a uint16, below the "no cost" 0xffff.
+ *   admissible   i for a left pixel u iff u - d_i >= 0.  Every minimum of the winner runs over admissible i only; a pixel without
+ *                one is invalid.
+ *   winner       i* = the admissible i of least S, the lowest on a tie; A0 its cost, d* = d_i*.  A2 = the least S over admissible i
+ *                with |i - i*| >= 2, or none.
+ *   uniqueness   uniqueness_percent = q > 0: kept iff A2 is none or 100 * A0 < (100 - q) * A2 in integers (strict: flat costs are
+ *                rejected).  q = 0 keeps everything.
+ *   left-right   lr_max_diff >= 0 (-1 turns the check off).  The right image's costs are read from the left volume, there is no
+ *                second aggregation: S_R(y, x, i) = S(y, x + d_i, i), admissible iff x + d_i <= cols - 1; dR(y, x) = the admissible
+ *                i of least S_R, the lowest on a tie (no uniqueness test).  With xr = u - d*: kept iff the right pixel xr has a
+ *                winner and |dR(v, xr) - i*| <= lr_max_diff.
+ *   sub-pixel    when i* - 1 and i* + 1 are both in the disparity range and admissible and
+ *                den = (S(i* - 1) + S(i* + 1)) - 2 * A0 > 0: delta = (float) (S(i* - 1) - S(i* + 1)) / (float) (2 * den);
+ *                otherwise delta = 0.  s = (float) d* + delta.
+ *   output       valid iff kept and s > 0.  disparity(v, u) = s and depth(v, u) = bf / s when valid, else 0.0f both; bf = focal
+ *                length * baseline in pixel * metres.  n_valid[b][f] = the valid pixels of the image.  Pad columns are not touched.
+ *   sequences    images f >= n_images[b] are not touched (n_images NULL: frames).  status[b] = PRS_ERR_RANGE when n_images[b]
+ *                lies outside [0, frames], and nothing of that sequence is written; otherwise PRS_OK.
+ * Call-level (return value, nothing launched, outputs untouched): PRS_ERR_NULL (a struct, left, right, status or the workspace
+ * unset, or disparity and depth both unset); PRS_ERR_RANGE (n_disparities outside 1 .. 256, min_disparity < 0 or
+ * min_disparity + n_disparities > 4096, n_paths not 4 or 8, p1 < 0, p2 < p1 or p2 > 4095, uniqueness_percent outside 0 .. 99,
+ * lr_max_diff outside -1 .. 255, bf not finite or <= 0; batch, frames, rows, cols or images_in_flight < 1, left_pitch or
+ * right_pitch < cols, out_pitch < 4 * cols or not a multiple of 4); PRS_ERR_UNSUPPORTED (disparity, depth, n_images, n_valid or
+ * status not 4-byte aligned, the workspace not 16-byte; batch * frames * rows * cols beyond 2^31 - 1; a grid beyond 2^31 - 1
+ * workgroups).
+ * The S volume of one image is rows * cols * n_disparities uint16 (119 MB for a KITTI image at 128 disparities), so the call
+ * works through the images b * frames + f in chunks of images_in_flight (a value above batch * frames counts as batch * frames)
+ * and reuses one set of volumes for every chunk.  Plain launches on the context's stream, 2 + chunks * (n_paths + 2) of them
+ * (n_paths + 1 with lr_max_diff = -1), a number the host knows: n_images is read on the device and the waves of skipped images leave at once.  census (dense stereo's
+ * kernel, once for all images); per chunk one path launch a direction (a wave owns a line and walks it, its lanes hold the
+ * disparities, up to four neighbouring ones a lane: a row for dy = 0; otherwise the line that starts at column x0 of the first row
+ * and visits (y, (x0 + y * dx) mod cols), restarting with L = C where it wraps, which is the border rule above, so no wave needs
+ * another wave's state; C is recomputed from the census words by 64-bit popcounts and never stored; m by a wave reduction, i - 1 and
+ * i + 1 from the neighbouring register or lane; the first direction stores S, the later ones read, add and store: launches on one
+ * stream are ordered, so there are no atomics), one winner launch (a wave a pixel at a time: the left winner with A2, uniqueness
+ * and sub-pixel into dense stereo's records) and, with the left-right check, one right-winner launch (a workgroup 128 right pixels
+ * of a row: the diagonals S(y, x + d_i, i) from the row's slice of the volume, staged in LDS 64 disparities at a time); finish
+ * (dense stereo's kernel, once: left-right check, outputs, n_valid).  The volume is indexed with 64-bit offsets.  No persistent workgroup
+ * and no spinning, no workgroup waits for another; no allocation, no synchronisation, no host read: graph-capturable.  Everything
+ * transient lives in the caller's workspace, which two calls in flight must not share.  Left out: an intensity-adaptive P2, 16
+ * paths, a median or hole filling, a host-pointer variant and a C++ adapter in plugin/.
+ * ============================================================================================== */
+typedef struct {
+  int32_t n_disparities;       /* 1 .. 256 */
+  int32_t min_disparity;       /* >= 0, min_disparity + n_disparities <= 4096 */
+  int32_t p1;                  /* P1, the penalty of a step of one disparity along a path: 0 .. p2 */
+  int32_t p2;                  /* P2, the penalty of any larger step: p1 .. 4095 */
+  int32_t n_paths;             /* 4 or 8 */
+  int32_t uniqueness_percent;  /* q, 0 .. 99; 0 = no test */
+  int32_t lr_max_diff;         /* -1 .. 255; -1 = no left-right check */
+  float bf;                    /* focal length * baseline, pixel * metres, finite and > 0 */
+  int32_t reserved[4];
+} prs_sgm_stereo_params;
+
+/* device pointers: prs_dense_stereo_batch with images_in_flight in the place of reserved0 */
+typedef struct {
+  int32_t batch;
+  int32_t frames;              /* pairs per sequence */
+  int32_t rows, cols;
+  int32_t left_pitch;          /* bytes */
+  int32_t right_pitch;         /* bytes */
+  int32_t out_pitch;           /* bytes of a row of disparity and of depth, a multiple of 4 */
+  int32_t images_in_flight;    /* >= 1: the images whose S volumes the workspace holds at a time; the one the workspace was sized for */
+  const uint8_t* left;         /* in [batch][frames][rows][left_pitch] */
+  const uint8_t* right;        /* in [batch][frames][rows][right_pitch] */
+  const int32_t* n_images;     /* in [batch] (NULL allowed: frames) */
+  float* disparity;            /* out [batch][frames][rows][out_pitch / 4] (NULL allowed when depth is set) */
+  float* depth;                /* out [batch][frames][rows][out_pitch / 4] (NULL allowed when disparity is set) */
+  int32_t* n_valid;            /* out [batch][frames] (NULL allowed) */
+  int32_t* status;             /* out [batch] */
+  void* workspace;             /* prs_sgm_stereo_workspace_bytes(...) bytes, 16-byte aligned */
+} prs_sgm_stereo_batch;
+
+/* bytes of workspace a call needs.  With P = batch * frames * rows * cols, Q = min(images_in_flight, batch * frames) * rows * cols *
+ * n_disparities and up16(x) = x rounded up to a multiple of 16: 3 * up16(8 P) (the two census images and the left winners' records)
+ * + up16(2 P) when lr_check != 0 (the right winners) + up16(2 Q) (one uint16 volume S).  A call whose params have fewer disparities
+ * than the workspace was sized for fits it.  0: a size or images_in_flight below 1, n_disparities outside 1 .. 256, or P beyond
+ * 2^31 - 1 */
+PRS_API uint64_t prs_sgm_stereo_workspace_bytes(int32_t batch, int32_t frames, int32_t rows, int32_t cols, int32_t n_disparities,
+                                                int32_t lr_check, int32_t images_in_flight);
+/* device pointers, asynchronous on the context's stream */
+PRS_API int prs_sgm_stereo_batch_run(prs_context* ctx, const prs_sgm_stereo_params* params, const prs_sgm_stereo_batch* batch);
+/* sizeof prs_sgm_stereo_params, prs_sgm_stereo_batch as the library was compiled (bindings check) */
+PRS_API void prs_sgm_stereo_struct_sizes(uint64_t* sizes2);
 
 #ifdef __cplusplus
 }

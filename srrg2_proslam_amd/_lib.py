@@ -583,6 +583,20 @@ class SpeckleBatch(C.Structure):
                 ("status", C.c_void_p), ("workspace", C.c_void_p)]
 
 
+class SgmStereoParams(C.Structure):
+    """prs_sgm_stereo_params"""
+    _fields_ = [("n_disparities", C.c_int32), ("min_disparity", C.c_int32), ("p1", C.c_int32), ("p2", C.c_int32), ("n_paths", C.c_int32),
+                ("uniqueness_percent", C.c_int32), ("lr_max_diff", C.c_int32), ("bf", C.c_float), ("reserved", C.c_int32 * 4)]
+
+
+class SgmStereoBatch(C.Structure):
+    """prs_sgm_stereo_batch (device pointers)"""
+    _fields_ = [("batch", C.c_int32), ("frames", C.c_int32), ("rows", C.c_int32), ("cols", C.c_int32), ("left_pitch", C.c_int32),
+                ("right_pitch", C.c_int32), ("out_pitch", C.c_int32), ("images_in_flight", C.c_int32), ("left", C.c_void_p),
+                ("right", C.c_void_p), ("n_images", C.c_void_p), ("disparity", C.c_void_p), ("depth", C.c_void_p), ("n_valid", C.c_void_p),
+                ("status", C.c_void_p), ("workspace", C.c_void_p)]
+
+
 class DispatchEnv(C.Structure):
     """prs_dispatch_env: what a dispatch depends on outside its arguments (tests and tools)"""
     _fields_ = [(n, C.c_int32) for n in ("cus", "fused_align", "matcher_v3", "force_unstaged", "no_lone_gn", "merge_fused", "bf_mfma", "stamps",
@@ -755,6 +769,9 @@ SYMBOLS = {
     "prs_speckle_workspace_bytes": (C.c_uint64, [C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
     "prs_speckle_batch_run": (C.c_int, [_vp, C.POINTER(SpeckleParams), C.POINTER(SpeckleBatch)]),
     "prs_speckle_struct_sizes": (None, [C.POINTER(C.c_uint64)]),
+    "prs_sgm_stereo_workspace_bytes": (C.c_uint64, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
+    "prs_sgm_stereo_batch_run": (C.c_int, [_vp, C.POINTER(SgmStereoParams), C.POINTER(SgmStereoBatch)]),
+    "prs_sgm_stereo_struct_sizes": (None, [C.POINTER(C.c_uint64)]),
     "prs_scene_clip_batch": (C.c_int, [_vp, C.POINTER(Projector), _vp, C.POINTER(ClipBatch)]),
     "prs_scene_clip": (C.c_int, [_vp, C.POINTER(Projector), _vp, _vp, _vp, _vp, C.c_int32, _vp, _vp, _vp, C.c_int32, _i32p]),
 }
@@ -851,5 +868,10 @@ def load():
         raise ImportError("libproslam_hip.so lays out prs_speckle_params / prs_speckle_batch as %s bytes, the Python binding as %s: "
                           "rebuild with `python -c 'import __graft_entry__ as g; g.build()'`"
                           % (list(sizes), [C.sizeof(SpeckleParams), C.sizeof(SpeckleBatch)]))
+    lib.prs_sgm_stereo_struct_sizes(sizes)
+    if list(sizes) != [C.sizeof(SgmStereoParams), C.sizeof(SgmStereoBatch)]:
+        raise ImportError("libproslam_hip.so lays out prs_sgm_stereo_params / prs_sgm_stereo_batch as %s bytes, the Python binding as %s: "
+                          "rebuild with `python -c 'import __graft_entry__ as g; g.build()'`"
+                          % (list(sizes), [C.sizeof(SgmStereoParams), C.sizeof(SgmStereoBatch)]))
     _lib = lib
     return lib

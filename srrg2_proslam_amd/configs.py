@@ -228,6 +228,17 @@ REENTRY = {
 SPECKLE = {"max_size": 200, "max_diff": 1.0}
 
 
+# semi-global dense stereo (include/proslam_hip.h prs_sgm_stereo_params; ops.sgm_stereo_params).  BUILD-DEFINED: the reference has
+# no dense matcher.  The penalties are on the scale of a 62-bit census cost: libSGM's defaults for its census costs, 10 and 120;
+# eight paths, the uniqueness margin and the left-right tolerance of dense stereo
+SGM_STEREO = {"n_disparities": 128, "min_disparity": 0, "p1": 10, "p2": 120, "n_paths": 8, "uniqueness_percent": 10, "lr_max_diff": 1}
+# the bytes ops.SgmStereoBatch lets the S volumes of its workspace take when images_in_flight is left to it (the 26 bytes a pixel
+# beside them grow with the batch whatever that count is).  2 GiB holds 17 KITTI-shaped images at 128 disparities (119 MB each): a
+# path kernel's wave owns a line, and 17 x 376 rows are six waves for each of the 1024 SIMDs of an MI355X.  A constant, not a
+# measurement
+SGM_STEREO_VOLUME_BUDGET = 2 << 30
+
+
 def _gate(mean_t, std_t, mean_r, std_r, where):
     return {"mean_translation": (mean_t,) * 3, "std_translation": (std_t,) * 3, "mean_rotation": (mean_r,) * 3,
             "std_rotation": (std_r,) * 3, "source": where}

@@ -388,6 +388,38 @@ Layout layout_of(const int64_t batch, const int64_t frames, const int64_t rows, 
 
 }  // namespace
 
+// the census and the finish launch for the stages that share them (sgm_stereo.hip): the caller has checked the batch; false when a
+// grid would pass 2^31 - 1 workgroups, and then nothing is launched
+bool dense_census_enqueue(hipStream_t st, const prs_dense_stereo_batch& o, uint64_t* census_l, uint64_t* census_r) {
+  DenseStereoArgs a = {};
+  a.o        = o;
+  a.ctiles_x = (o.cols + PRS_WAVE - 1) / PRS_WAVE;
+  a.ctiles_y = (o.rows + kCensusRows - 1) / kCensusRows;
+  a.census_l = census_l;
+  a.census_r = census_r;
+  const int64_t blocks = (int64_t) o.batch * o.frames * 2 * a.ctiles_x * a.ctiles_y;
+  if (blocks > 0x7fffffffll) {
+    return false;
+  }
+  hipLaunchKernelGGL(dense_census_kernel, dim3((unsigned) blocks), dim3(kThreads), 0, st, a);
+  return true;
+}
+
+bool dense_finish_enqueue(hipStream_t st, const prs_dense_stereo_params& p, const prs_dense_stereo_batch& o, uint2* rec_l, int16_t* win_r) {
+  DenseStereoArgs a = {};
+  a.p       = p;
+  a.o       = o;
+  a.fblocks = (o.rows + kFinishRows - 1) / kFinishRows;
+  a.rec_l   = rec_l;
+  a.win_r   = win_r;
+  const int64_t blocks = (int64_t) o.batch * o.frames * a.fblocks;
+  if (blocks > 0x7fffffffll) {
+    return false;
+  }
+  hipLaunchKernelGGL(dense_finish_kernel, dim3((unsigned) blocks), dim3(kThreads), 0, st, a);
+  return true;
+}
+
 int dense_stereo_launch(prs_context* ctx, const prs_dense_stereo_params* params, const prs_dense_stereo_batch* batch) {
   const std::string who = "prs_dense_stereo_batch_run";
   if (!params || !batch) {

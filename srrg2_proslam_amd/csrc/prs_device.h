@@ -104,6 +104,19 @@ __device__ __forceinline__ T wave_sum(T v) {
   return v;
 }
 
+// the least value over the 64 lanes of a wave, in every lane, on the DPP network: rotations inside every row of 16 lanes (row_ror 1, 2,
+// 4, 8: every lane of a row holds the row's minimum), lane 15 of rows 0 / 2 onto rows 1 / 3 (row_bcast:15), lane 31 onto the upper half
+// (row_bcast:31), and lane 63, which has seen all four rows, read back as a scalar.  Lanes a step does not write keep their own value
+__device__ __forceinline__ uint32_t wave_min_u32(uint32_t v) {
+  v = min(v, (uint32_t) __builtin_amdgcn_update_dpp((int) v, (int) v, 0x121, 0xf, 0xf, false));  // row_ror:1
+  v = min(v, (uint32_t) __builtin_amdgcn_update_dpp((int) v, (int) v, 0x122, 0xf, 0xf, false));  // row_ror:2
+  v = min(v, (uint32_t) __builtin_amdgcn_update_dpp((int) v, (int) v, 0x124, 0xf, 0xf, false));  // row_ror:4
+  v = min(v, (uint32_t) __builtin_amdgcn_update_dpp((int) v, (int) v, 0x128, 0xf, 0xf, false));  // row_ror:8
+  v = min(v, (uint32_t) __builtin_amdgcn_update_dpp((int) v, (int) v, 0x142, 0xa, 0xf, false));  // row_bcast:15 -> rows 1, 3
+  v = min(v, (uint32_t) __builtin_amdgcn_update_dpp((int) v, (int) v, 0x143, 0xc, 0xf, false));  // row_bcast:31 -> rows 2, 3
+  return (uint32_t) __builtin_amdgcn_readlane((int) v, 63);
+}
+
 // base + number of set bits of m below this lane
 __device__ __forceinline__ int lanes_below(uint64_t m, int base) {
   return (int) __builtin_amdgcn_mbcnt_hi((uint32_t) (m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t) m, (uint32_t) base));

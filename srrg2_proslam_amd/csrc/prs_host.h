@@ -301,6 +301,10 @@ int world_map_launch(prs_context* ctx, const prs_world_map_params* params, const
 int world_voxel_launch(prs_context* ctx, const prs_world_voxel_params* params, const prs_world_voxel_batch* batch);
 int depth_cloud_launch(prs_context* ctx, const prs_depth_cloud_params* params, const prs_depth_cloud_batch* batch);
 int dense_stereo_launch(prs_context* ctx, const prs_dense_stereo_params* params, const prs_dense_stereo_batch* batch);
+// dense stereo's census and finish launches, shared with the semi-global stage (checked batches only; false: a grid too large)
+bool dense_census_enqueue(hipStream_t st, const prs_dense_stereo_batch& o, uint64_t* census_l, uint64_t* census_r);
+bool dense_finish_enqueue(hipStream_t st, const prs_dense_stereo_params& p, const prs_dense_stereo_batch& o, uint2* rec_l, int16_t* win_r);
+int sgm_stereo_launch(prs_context* ctx, const prs_sgm_stereo_params* params, const prs_sgm_stereo_batch* batch);
 int speckle_launch(prs_context* ctx, const prs_speckle_params* params, const prs_speckle_batch* batch);
 int pose_compose_launch(prs_context* ctx, int batch, const float* prediction, const float* X, float* pose_out);
 int motion_predict_launch(prs_context* ctx, int batch, const float* prev2, const float* prev1, float* pred);

@@ -9,7 +9,7 @@ import weakref
 
 import numpy as np
 
-from . import _lib
+from . import _lib, configs
 from ._lib import ProslamHipError, StereoBatch, StereoParams, TriangulatorParams
 
 CORR_DTYPE = np.dtype([("fixed_idx", np.int32), ("moving_idx", np.int32), ("response", np.float32)])
@@ -2729,10 +2729,13 @@ class DenseStereoBatch:
         self.out_pitch = padded * 4
         self.n_valid = z((B, F), torch.int32) if "n_valid" in outputs else None
         self.status = z((B,), torch.int32)
-        nbytes = int(_lib.load().prs_dense_stereo_workspace_bytes(B, F, self.rows, self.cols, 1, 1))
+        nbytes = self._workspace_bytes()
         if nbytes < 1:
             raise ValueError("batch * frames * rows * cols must stay below 2^31")
         self.workspace = z((nbytes,), torch.uint8)
+
+    def _workspace_bytes(self):
+        return int(_lib.load().prs_dense_stereo_workspace_bytes(self.batch, self.frames, self.rows, self.cols, 1, 1))
 
     def _images(self, t, name):
         """(pointer, pitch in bytes) of a uint8 tensor [B, frames, rows, cols] or [B * frames, rows, cols] whose images follow one
@@ -2755,6 +2758,10 @@ class DenseStereoBatch:
         """the prs_dense_stereo_batch of device tensors: left, right uint8 [B, frames, rows, cols] or [B * frames, rows, cols] (the two
         halves of a RectifyBatch's dst, with their pitch), n_images [B] int32 or None = frames"""
         d = _lib.DenseStereoBatch()
+        self._fill(d, left, right, n_images)
+        return d
+
+    def _fill(self, d, left, right, n_images):
         d.batch, d.frames, d.rows, d.cols, d.out_pitch = self.batch, self.frames, self.rows, self.cols, self.out_pitch
         d.left, d.left_pitch = self._images(left, "left")
         d.right, d.right_pitch = self._images(right, "right")
@@ -2766,13 +2773,88 @@ class DenseStereoBatch:
         d.depth = self._depth.data_ptr() if self._depth is not None else None
         d.n_valid = self.n_valid.data_ptr() if self.n_valid is not None else None
         d.status, d.workspace = self.status.data_ptr(), self.workspace.data_ptr()
-        return d
 
     def run(self, ctx, params, left, right, n_images=None):
         """enqueue the disparity and depth images of every pair (asynchronous); per-sequence status lands in self.status"""
         d = self.descriptor(left, right, n_images)
         rc = _lib.load().prs_dense_stereo_batch_run(ctx._h, C.byref(params), C.byref(d))
         _check(ctx, rc, "prs_dense_stereo_batch_run")
+        return rc
+
+
+# ---- semi-global dense stereo: rectified pairs to disparity and depth images by path aggregation (include/proslam_hip.h prs_sgm_stereo_*) ----
+def sgm_stereo_params(camera, n_disparities=configs.SGM_STEREO["n_disparities"], min_disparity=configs.SGM_STEREO["min_disparity"],
+                      p1=configs.SGM_STEREO["p1"], p2=configs.SGM_STEREO["p2"], n_paths=configs.SGM_STEREO["n_paths"],
+                      uniqueness_percent=configs.SGM_STEREO["uniqueness_percent"], lr_max_diff=configs.SGM_STEREO["lr_max_diff"]):
+    """prs_sgm_stereo_params.  camera: a dictionary with fx and baseline_m, as ops.dense_stereo_params takes it.  Disparities
+    min_disparity .. min_disparity + n_disparities - 1, the penalties 0 <= p1 <= p2 <= 4095 of a path's step of one disparity and of a
+    larger one, n_paths 4 or 8, uniqueness_percent 0 = no test, lr_max_diff -1 = no left-right check.  The defaults are
+    configs.SGM_STEREO (128, 0, 10, 120, 8, 10, 1).  Raises ValueError on every value the library refuses"""
+    p = _lib.SgmStereoParams()
+    p.n_disparities, p.min_disparity, p.p1, p.p2, p.n_paths = int(n_disparities), int(min_disparity), int(p1), int(p2), int(n_paths)
+    p.uniqueness_percent, p.lr_max_diff = int(uniqueness_percent), int(lr_max_diff)
+    with np.errstate(over="ignore"):  # a product beyond float32 becomes inf and is refused below
+        p.bf = float(np.float32(np.float64(camera["fx"]) * np.float64(camera["baseline_m"])))
+    if not 1 <= p.n_disparities <= 256:
+        raise ValueError("n_disparities must lie in 1 .. 256")
+    if p.min_disparity < 0 or p.min_disparity + p.n_disparities > 4096:
+        raise ValueError("min_disparity must be at least 0 and min_disparity + n_disparities at most 4096")
+    if not 0 <= p.p1 <= p.p2 <= 4095:
+        raise ValueError("the penalties must satisfy 0 <= p1 <= p2 <= 4095")
+    if p.n_paths not in (4, 8):
+        raise ValueError("n_paths must be 4 or 8")
+    if not 0 <= p.uniqueness_percent <= 99:
+        raise ValueError("uniqueness_percent must lie in 0 .. 99")
+    if not -1 <= p.lr_max_diff <= 255:
+        raise ValueError("lr_max_diff must lie in -1 .. 255")
+    if not (np.isfinite(p.bf) and p.bf > 0.0):
+        raise ValueError("fx * baseline_m must be finite and positive as a float32")
+    return p
+
+
+def sgm_stereo_images_in_flight(batch, frames, rows, cols, n_disparities=256):
+    """the images_in_flight SgmStereoBatch picks when it is left to it: the largest count whose S volumes (2 * rows * cols *
+    n_disparities bytes an image) stay within configs.SGM_STEREO_VOLUME_BUDGET, at least 1 and at most batch * frames"""
+    volume = 2 * int(rows) * int(cols) * int(n_disparities)
+    return max(1, min(int(batch) * int(frames), configs.SGM_STEREO_VOLUME_BUDGET // volume))
+
+
+class SgmStereoBatch(DenseStereoBatch):
+    """semi-global dense stereo of B sequences of up to `frames` rectified pairs of rows x cols pixels: the outputs, padding,
+    out_pitch and run signature of DenseStereoBatch, so SpeckleFilterBatch and DepthCloudBatch read disparity and depth in place.
+    The workspace is sized for the left-right check, for params of up to `n_disparities` disparities and for the S volumes of
+    `images_in_flight` images at a time; None picks ops.sgm_stereo_images_in_flight(...)."""
+
+    def __init__(self, batch, frames, rows, cols, outputs=DenseStereoBatch.OUTPUTS, images_in_flight=None, n_disparities=256, device=0):
+        self.n_disparities = int(n_disparities)
+        if not 1 <= self.n_disparities <= 256:
+            raise ValueError("n_disparities must lie in 1 .. 256")
+        if images_in_flight is not None and int(images_in_flight) < 1:
+            raise ValueError("images_in_flight must be at least 1")
+        self._in_flight = None if images_in_flight is None else int(images_in_flight)
+        super().__init__(batch, frames, rows, cols, outputs, device)
+
+    def _workspace_bytes(self):
+        if self._in_flight is None:
+            self._in_flight = sgm_stereo_images_in_flight(self.batch, self.frames, self.rows, self.cols, self.n_disparities)
+        self.images_in_flight = min(self._in_flight, self.batch * self.frames)
+        return int(_lib.load().prs_sgm_stereo_workspace_bytes(self.batch, self.frames, self.rows, self.cols, self.n_disparities, 1,
+                                                              self.images_in_flight))
+
+    def descriptor(self, left, right, n_images=None):
+        """the prs_sgm_stereo_batch of device tensors, as DenseStereoBatch.descriptor takes them"""
+        d = _lib.SgmStereoBatch()
+        self._fill(d, left, right, n_images)
+        d.images_in_flight = self.images_in_flight
+        return d
+
+    def run(self, ctx, params, left, right, n_images=None):
+        """enqueue the disparity and depth images of every pair (asynchronous); per-sequence status lands in self.status"""
+        if params.n_disparities > self.n_disparities:
+            raise ValueError("the workspace was sized for %d disparities, the params have %d" % (self.n_disparities, params.n_disparities))
+        d = self.descriptor(left, right, n_images)
+        rc = _lib.load().prs_sgm_stereo_batch_run(ctx._h, C.byref(params), C.byref(d))
+        _check(ctx, rc, "prs_sgm_stereo_batch_run")
         return rc
 
 
