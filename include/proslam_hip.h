@@ -139,7 +139,9 @@ PRS_API int prs_version(void);
  * prs_dense_stereo_params, prs_dense_stereo_batch, prs_dense_stereo_workspace_bytes, prs_dense_stereo_batch_run and
  * prs_dense_stereo_struct_sizes; and the speckle filter: prs_speckle_params, prs_speckle_batch, prs_speckle_workspace_bytes,
  * prs_speckle_batch_run and prs_speckle_struct_sizes; and semi-global dense stereo: prs_sgm_stereo_params, prs_sgm_stereo_batch,
- * prs_sgm_stereo_workspace_bytes, prs_sgm_stereo_batch_run and prs_sgm_stereo_struct_sizes).  Callers memset() parameter structs before
+ * prs_sgm_stereo_workspace_bytes, prs_sgm_stereo_batch_run and prs_sgm_stereo_struct_sizes; and the depth consistency filter:
+ * prs_depth_consistency_params, prs_depth_consistency_batch, prs_depth_consistency_workspace_bytes, prs_depth_consistency_batch_run
+ * and prs_depth_consistency_struct_sizes).  Callers memset() parameter structs before
  * filling them, so that fields they do not know select the shipped defaults (all zero). */
 #define PRS_ABI_VERSION 104
 PRS_API int prs_abi_check(int32_t header_version, uint64_t sizeof_stereo_params, uint64_t sizeof_pcf_params, uint64_t sizeof_aligner_params,
@@ -2691,6 +2693,111 @@ PRS_API uint64_t prs_sgm_stereo_workspace_bytes(int32_t batch, int32_t frames, i
 PRS_API int prs_sgm_stereo_batch_run(prs_context* ctx, const prs_sgm_stereo_params* params, const prs_sgm_stereo_batch* batch);
 /* sizeof prs_sgm_stereo_params, prs_sgm_stereo_batch as the library was compiled (bindings check) */
 PRS_API void prs_sgm_stereo_struct_sizes(uint64_t* sizes2);
+
+/* ================================================================================================
+ * Depth consistency filter: every depth pixel of a sequence's frames is cross-checked against the neighbouring frames through the
+ * trajectory, between the speckle filter (or a depth sensor's images) and prs_depth_cloud_batch.depth, which reads out in place
+ * and drops a depth of 0.  A pixel that too few neighbours see at the same place, or whose point lies in the free space too many
+ * neighbours observed, is set to 0 (Merrell et al. 2007; the geometric consistency of multi-view stereo pipelines).
+ *
+ * BUILD-DEFINED: the reference has no dense images, so the rule below is this build's.  tests/depth_consistency_ref.py restates it
+ * in numpy and the kernels equal that byte for byte.  All float32 arithmetic is explicit two-operand arithmetic in the order
+ * written, -ffp-contract=off, division correctly rounded; the float64 part follows the same rules.  Per sequence b and image
+ * f < n_images[b] (n_images NULL: frames):
+ *
+ *   pose         k = frame_index[b][f], or f when frame_index is NULL.  The frame is usable iff k lies in [0, pose_stride) and the
+ *                twelve entries of the top three rows of pose[b][k] are finite: the dense cloud's test.  C_f = se3_mul(pose[b][k],
+ *                sensor_in_robot) in float32 with the dense cloud's operation order; R_f its rotation, t_f its translation.
+ *                An unusable frame gets an all-zero out image and zero support / violation, is counted in n_skipped[b], and its
+ *                depth elements that pass the validity test are counted in n_removed[b][f] (n_kept[b][f] = 0).
+ *   neighbours   the slots g = f - j * stride and g = f + j * stride, j = 1 .. window.  A slot exists iff 0 <= g < n_images[b] and
+ *                frame g is usable.  Only counts are formed, so the order of the slots affects no output byte.
+ *   relative     M = C_g^-1 C_f in float64 from the float32 C_f, C_g, then rounded to float32: dt = t_f - t_g per component;
+ *                M[i][j] = (Rg[0][i] * Rf[0][j] + Rg[1][i] * Rf[1][j]) + Rg[2][i] * Rf[2][j];
+ *                M[i][3] = (Rg[0][i] * dt[0] + Rg[1][i] * dt[1]) + Rg[2][i] * dt[2].  World poses reach kilometres (KITTI): the
+ *                translations are subtracted first, in float64, so the baseline is exact to far below a millimetre.
+ *   validity     of a depth element of any frame: raw is the element as a float; valid iff raw > 0 and, with
+ *                d = depth_scaling_factor_to_meters * raw, d >= range_min && d <= range_max: the dense cloud's test.  An invalid own
+ *                pixel gets out = 0, support = violation = 0 and is counted nowhere.
+ *   vote         of slot g for the valid pixel (v, u) of f: p = (((float) u - cx) / fx * d, ((float) v - cy) / fy * d, d), the
+ *                dense cloud's point; q_i = ((M[i][0] * p_0 + M[i][1] * p_1) + M[i][2] * p_2) + M[i][3].  No vote unless q_2 > 0.
+ *                x = floorf((q_0 / q_2 * fx + cx) + 0.5f), y = floorf((q_1 / q_2 * fy + cy) + 0.5f).  No vote unless
+ *                x >= 0 && x < (float) cols && y >= 0 && y < (float) rows, compared as floats before any conversion (NaN: no
+ *                vote).  raw_g = the element of frame g at ((int) y, (int) x); no vote unless it is valid; d_g its scaled value.
+ *                e = d_g - q_2, tol = max_rel_diff * q_2.  Support iff e >= -tol && e <= tol.  Violation iff e > tol: the neighbour
+ *                sees past the point, which therefore lies in its free space.  e < -tol: occluded, no vote.
+ *   decision     support(v, u) and violation(v, u) are the counts over the slots (uint8, at most 16).  The pixel is kept iff
+ *                support >= min_support && violation <= max_violation.  out(v, u) = the input element, bit for bit and in the
+ *                input's element type, when kept; 0 otherwise.  n_kept[b][f] / n_removed[b][f] = the valid pixels kept / zeroed.
+ *   untouched    pad columns of out, support and violation; everything of the images f >= n_images[b].
+ * status[b]: PRS_ERR_RANGE when n_images[b] lies outside [0, frames]: nothing of that sequence is written but status[b] and
+ * n_skipped[b] = 0.  Otherwise PRS_OK.
+ * Call-level (return value, nothing launched, outputs untouched): PRS_ERR_NULL (a struct, depth, pose, out, status or the
+ * workspace unset); PRS_ERR_RANGE (batch, frames, rows, cols or pose_stride < 1; window outside 1 .. 8, stride < 1, min_support or
+ * max_violation outside 0 .. 16, max_rel_diff not finite or < 0; a parameter that is not finite -- sensor_in_robot included --, a
+ * scale <= 0, range_min < 0 or range_min > range_max; pitch or out_pitch below cols elements or not a multiple of the element
+ * size, count_pitch below cols with support or violation set); PRS_ERR_UNSUPPORTED (an unknown depth_type; depth or out not
+ * aligned to the element, the workspace not 16-byte, another array but support and violation not 4-byte; out, support or violation
+ * overlapping depth -- neighbours are read while out is written --; rows or cols above 2^24; batch * frames * rows * cols or a
+ * grid beyond 2^31 - 1).
+ * Two plain launches on the context's stream.  prepare (a workgroup per sequence): validation, the usable flags, n_skipped, status,
+ * zeroes in n_kept / n_removed, and one 64-byte record per image and slot in the workspace -- M, the exists flag and, in slot 0,
+ * the state of the image -- so the float64 work is done once per slot, never per pixel.  filter (a workgroup per 64 x 32 pixels of
+ * one image, in eight steps of 64 x 4, a lane per pixel a step): the image's records through LDS, the slots in a uniform loop with
+ * one gather each -- a step maps to a compact patch of the neighbour --, the counts by wave ballots and one integer atomic add a
+ * workgroup and counter, so no byte depends on the order they arrive in.  The workgroups of an unusable frame write zeroes and read its depth only to count
+ * n_removed; those of an image behind n_images or of a refused sequence return before they read a depth.  No allocation, no
+ * synchronisation, no host read: graph-capturable.  Everything transient lives in the caller's workspace, which two calls in
+ * flight must not share.  Left out: a fused (averaged) depth, a back-projection pixel-error test, per-frame intrinsics, bilinear
+ * sampling of the neighbour, a companion image, any choice of key frames beyond window / stride / frame_index, a host-pointer
+ * variant and a C++ adapter in plugin/.
+ * ============================================================================================== */
+typedef struct {
+  int32_t depth_type;                    /* PRS_DEPTH_U16 or PRS_DEPTH_F32 */
+  float depth_scaling_factor_to_meters;  /* finite and > 0 */
+  float fx, fy, cx, cy;                  /* the depth camera's matrix, the same for every frame */
+  float range_min, range_max;            /* metres, finite, 0 <= range_min <= range_max */
+  int32_t window;                        /* neighbours on each side, 1 .. 8 */
+  int32_t stride;                        /* frames between two neighbours, >= 1 */
+  float max_rel_diff;                    /* finite and >= 0: |d_g - q_2| <= max_rel_diff * q_2 is support */
+  int32_t min_support;                   /* 0 .. 16 */
+  int32_t max_violation;                 /* 0 .. 16 */
+  float sensor_in_robot[16];             /* row-major; the identity when the poses are the camera's */
+  int32_t reserved[3];
+} prs_depth_consistency_params;
+
+/* device pointers */
+typedef struct {
+  int32_t batch;
+  int32_t frames;              /* images per sequence */
+  int32_t rows, cols;
+  int32_t pitch;               /* bytes of a row of depth, a multiple of the element's size */
+  int32_t out_pitch;           /* bytes of a row of out, a multiple of the element's size */
+  int32_t count_pitch;         /* bytes of a row of support and of violation */
+  int32_t pose_stride;         /* poses per sequence */
+  const void* depth;           /* in [batch][frames][rows][pitch] */
+  const int32_t* n_images;     /* in [batch] (NULL allowed: frames) */
+  const float* pose;           /* in [batch][pose_stride][16], what prs_session_unroll_batch writes */
+  const int32_t* frame_index;  /* in [batch][frames] the pose of image f (NULL allowed: f) */
+  void* out;                   /* out [batch][frames][rows][out_pitch], the element type of depth; must not overlap depth */
+  uint8_t* support;            /* out [batch][frames][rows][count_pitch] (NULL allowed); must not overlap depth */
+  uint8_t* violation;          /* out [batch][frames][rows][count_pitch] (NULL allowed); must not overlap depth */
+  int32_t* n_kept;             /* out [batch][frames] (NULL allowed) */
+  int32_t* n_removed;          /* out [batch][frames] (NULL allowed) */
+  int32_t* n_skipped;          /* out [batch] frames without a usable pose (NULL allowed) */
+  int32_t* status;             /* out [batch] */
+  void* workspace;             /* prs_depth_consistency_workspace_bytes(...) bytes, 16-byte aligned */
+} prs_depth_consistency_batch;
+
+/* bytes of workspace a call needs: 64 * batch * frames * 2 * window (one record per image and slot: the twelve floats of M, the
+ * exists flag, the image's state, two unused words), a multiple of 16.  0: a size below 1, window outside 1 .. 8, or
+ * batch * frames beyond 2^31 - 1 */
+PRS_API uint64_t prs_depth_consistency_workspace_bytes(int32_t batch, int32_t frames, int32_t window);
+/* device pointers, asynchronous on the context's stream */
+PRS_API int prs_depth_consistency_batch_run(prs_context* ctx, const prs_depth_consistency_params* params,
+                                            const prs_depth_consistency_batch* batch);
+/* sizeof prs_depth_consistency_params, prs_depth_consistency_batch as the library was compiled (bindings check) */
+PRS_API void prs_depth_consistency_struct_sizes(uint64_t* sizes2);
 
 #ifdef __cplusplus
 }

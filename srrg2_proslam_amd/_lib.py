@@ -597,6 +597,23 @@ class SgmStereoBatch(C.Structure):
                 ("status", C.c_void_p), ("workspace", C.c_void_p)]
 
 
+class DepthConsistencyParams(C.Structure):
+    """prs_depth_consistency_params"""
+    _fields_ = [("depth_type", C.c_int32), ("depth_scaling_factor_to_meters", C.c_float), ("fx", C.c_float), ("fy", C.c_float),
+                ("cx", C.c_float), ("cy", C.c_float), ("range_min", C.c_float), ("range_max", C.c_float), ("window", C.c_int32),
+                ("stride", C.c_int32), ("max_rel_diff", C.c_float), ("min_support", C.c_int32), ("max_violation", C.c_int32),
+                ("sensor_in_robot", C.c_float * 16), ("reserved", C.c_int32 * 3)]
+
+
+class DepthConsistencyBatch(C.Structure):
+    """prs_depth_consistency_batch (device pointers)"""
+    _fields_ = [("batch", C.c_int32), ("frames", C.c_int32), ("rows", C.c_int32), ("cols", C.c_int32), ("pitch", C.c_int32),
+                ("out_pitch", C.c_int32), ("count_pitch", C.c_int32), ("pose_stride", C.c_int32), ("depth", C.c_void_p),
+                ("n_images", C.c_void_p), ("pose", C.c_void_p), ("frame_index", C.c_void_p), ("out", C.c_void_p), ("support", C.c_void_p),
+                ("violation", C.c_void_p), ("n_kept", C.c_void_p), ("n_removed", C.c_void_p), ("n_skipped", C.c_void_p),
+                ("status", C.c_void_p), ("workspace", C.c_void_p)]
+
+
 class DispatchEnv(C.Structure):
     """prs_dispatch_env: what a dispatch depends on outside its arguments (tests and tools)"""
     _fields_ = [(n, C.c_int32) for n in ("cus", "fused_align", "matcher_v3", "force_unstaged", "no_lone_gn", "merge_fused", "bf_mfma", "stamps",
@@ -772,6 +789,9 @@ SYMBOLS = {
     "prs_sgm_stereo_workspace_bytes": (C.c_uint64, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
     "prs_sgm_stereo_batch_run": (C.c_int, [_vp, C.POINTER(SgmStereoParams), C.POINTER(SgmStereoBatch)]),
     "prs_sgm_stereo_struct_sizes": (None, [C.POINTER(C.c_uint64)]),
+    "prs_depth_consistency_workspace_bytes": (C.c_uint64, [C.c_int32, C.c_int32, C.c_int32]),
+    "prs_depth_consistency_batch_run": (C.c_int, [_vp, C.POINTER(DepthConsistencyParams), C.POINTER(DepthConsistencyBatch)]),
+    "prs_depth_consistency_struct_sizes": (None, [C.POINTER(C.c_uint64)]),
     "prs_scene_clip_batch": (C.c_int, [_vp, C.POINTER(Projector), _vp, C.POINTER(ClipBatch)]),
     "prs_scene_clip": (C.c_int, [_vp, C.POINTER(Projector), _vp, _vp, _vp, _vp, C.c_int32, _vp, _vp, _vp, C.c_int32, _i32p]),
 }
@@ -873,5 +893,10 @@ def load():
         raise ImportError("libproslam_hip.so lays out prs_sgm_stereo_params / prs_sgm_stereo_batch as %s bytes, the Python binding as %s: "
                           "rebuild with `python -c 'import __graft_entry__ as g; g.build()'`"
                           % (list(sizes), [C.sizeof(SgmStereoParams), C.sizeof(SgmStereoBatch)]))
+    lib.prs_depth_consistency_struct_sizes(sizes)
+    if list(sizes) != [C.sizeof(DepthConsistencyParams), C.sizeof(DepthConsistencyBatch)]:
+        raise ImportError("libproslam_hip.so lays out prs_depth_consistency_params / prs_depth_consistency_batch as %s bytes, the Python "
+                          "binding as %s: rebuild with `python -c 'import __graft_entry__ as g; g.build()'`"
+                          % (list(sizes), [C.sizeof(DepthConsistencyParams), C.sizeof(DepthConsistencyBatch)]))
     _lib = lib
     return lib

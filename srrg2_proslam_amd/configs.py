@@ -239,6 +239,14 @@ SGM_STEREO = {"n_disparities": 128, "min_disparity": 0, "p1": 10, "p2": 120, "n_
 SGM_STEREO_VOLUME_BUDGET = 2 << 30
 
 
+# the depth consistency filter between the speckle filter and the dense cloud (include/proslam_hip.h prs_depth_consistency_params;
+# ops.depth_consistency_params).  BUILD-DEFINED: the reference has no dense images.  Two neighbours on each side, a depth agreeing
+# within 2 % (COLMAP's geometric filter uses 1 %, on depths it has optimised jointly; a stereo depth is coarser), at least two
+# neighbours in support and at most one that sees past the point; the ranges are the dense cloud's
+DEPTH_CONSISTENCY = {"window": 2, "stride": 1, "max_rel_diff": 0.02, "min_support": 2, "max_violation": 1, "range_min": 0.1,
+                     "range_max": 10.0}
+
+
 def _gate(mean_t, std_t, mean_r, std_r, where):
     return {"mean_translation": (mean_t,) * 3, "std_translation": (std_t,) * 3, "mean_rotation": (mean_r,) * 3,
             "std_rotation": (std_r,) * 3, "source": where}

@@ -17,6 +17,7 @@
 #include <string>
 
 #include "prs_compact.h"
+#include "prs_depth.h"
 #include "prs_device.h"
 #include "prs_host.h"
 #include "prs_se3.h"
@@ -44,17 +45,7 @@ struct DepthCloudArgs {
 
 // the pose row of image f of sequence b when the frame gives rows, -1 when it is skipped.  Uniform over the workgroup
 __device__ __forceinline__ int pose_row_of(const DepthCloudArgs& a, const int b, const int f) {
-  const int k = a.o.frame_index ? a.o.frame_index[(size_t) b * a.o.frames + f] : f;
-  if (k < 0 || k >= a.o.pose_stride) {
-    return -1;
-  }
-  const float* P = a.o.pose + ((size_t) b * a.o.pose_stride + k) * 16;
-  bool finite    = true;
-#pragma unroll
-  for (int i = 0; i < 12; ++i) {
-    finite = finite && finite_bits(P[i]);
-  }
-  return finite ? k : -1;
+  return depth_pose_row(a.o.frame_index, a.o.pose, a.o.frames, a.o.pose_stride, b, f);
 }
 
 // blockIdx.x = (b * frames + f) * chunks_per_frame + c.  E: the depth element; VEC: a lane's four samples are one aligned load (step 1,
@@ -135,8 +126,7 @@ __global__ __launch_bounds__(kThreads) void depth_cloud_kernel(const DepthCloudA
   int kept = 0, below = 0;
 #pragma unroll
   for (int j = 0; j < kPerLane; ++j) {
-    d[j]    = a.p.depth_scaling_factor_to_meters * raw[j];
-    keep[j] = raw[j] > 0.0f && d[j] >= a.p.range_min && d[j] <= a.p.range_max;  // a sample behind the image has raw 0
+    keep[j] = depth_valid(raw[j], a.p.depth_scaling_factor_to_meters, a.p.range_min, a.p.range_max, d[j]);  // a sample behind the image has raw 0
     mask[j] = __ballot(keep[j]);
     kept += __popcll(mask[j]);
     below = lanes_below(mask[j], below);
@@ -174,9 +164,7 @@ __global__ __launch_bounds__(kThreads) void depth_cloud_kernel(const DepthCloudA
   for (int j = 0; j < kPerLane; ++j) {
     if (keep[j]) {
       float p[3], w[3];
-      p[0] = ((float) u[j] - a.p.cx) / a.p.fx * d[j];
-      p[1] = ((float) v[j] - a.p.cy) / a.p.fy * d[j];
-      p[2] = d[j];
+      depth_point(u[j], v[j], d[j], a.p.fx, a.p.fy, a.p.cx, a.p.cy, p);
       se3_apply(T, p, w);
       float intensity = 0.0f;
       if (gray) {

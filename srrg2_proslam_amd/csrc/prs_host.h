@@ -306,6 +306,7 @@ bool dense_census_enqueue(hipStream_t st, const prs_dense_stereo_batch& o, uint6
 bool dense_finish_enqueue(hipStream_t st, const prs_dense_stereo_params& p, const prs_dense_stereo_batch& o, uint2* rec_l, int16_t* win_r);
 int sgm_stereo_launch(prs_context* ctx, const prs_sgm_stereo_params* params, const prs_sgm_stereo_batch* batch);
 int speckle_launch(prs_context* ctx, const prs_speckle_params* params, const prs_speckle_batch* batch);
+int depth_consistency_launch(prs_context* ctx, const prs_depth_consistency_params* params, const prs_depth_consistency_batch* batch);
 int pose_compose_launch(prs_context* ctx, int batch, const float* prediction, const float* X, float* pose_out);
 int motion_predict_launch(prs_context* ctx, int batch, const float* prev2, const float* prev1, float* pred);
 int merge_batch_launch(prs_context* ctx, const prs_merger_params* params, const prs_merge_batch* batch);

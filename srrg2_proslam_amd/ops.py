@@ -2954,6 +2954,129 @@ class SpeckleFilterBatch:
         return rc
 
 
+# ---- depth consistency filter: depth pixels cross-checked against the neighbouring frames (include/proslam_hip.h prs_depth_consistency_*) ----
+def depth_consistency_params(camera, window=2, stride=1, max_rel_diff=0.02, min_support=2, max_violation=1, range_min=0.1, range_max=10.0,
+                             depth_type="u16", scale=1.0, sensor_in_robot=None):
+    """prs_depth_consistency_params.  camera: a dictionary with fx, fy, cx, cy (configs.*["camera"]); window neighbours on each side,
+    `stride` frames apart; a neighbour supports a pixel whose depth it sees within max_rel_diff (relative), and violates one it sees
+    past; kept with at least min_support supports and at most max_violation violations (the defaults are
+    configs.DEPTH_CONSISTENCY); range_min / range_max, depth_type, scale and sensor_in_robot as in depth_cloud_params.  Raises
+    ValueError on every value the library refuses"""
+    p = _lib.DepthConsistencyParams()
+    if isinstance(depth_type, str) and depth_type not in _DEPTH_TYPES:
+        raise ValueError("depth_type: one of %s" % (sorted(_DEPTH_TYPES),))
+    p.depth_type = _DEPTH_TYPES[depth_type] if isinstance(depth_type, str) else int(depth_type)
+    if p.depth_type not in _DEPTH_TYPES.values():
+        raise ValueError("depth_type: one of %s" % (sorted(_DEPTH_TYPES),))
+    for name, value, lo, hi in (("window", window, 1, 8), ("stride", stride, 1, 0x7fffffff), ("min_support", min_support, 0, 16),
+                                ("max_violation", max_violation, 0, 16)):
+        if int(value) != value or not lo <= int(value) <= hi:
+            raise ValueError("%s must be an integer in %d .. %d" % (name, lo, hi))
+    p.window, p.stride, p.min_support, p.max_violation = int(window), int(stride), int(min_support), int(max_violation)
+    with np.errstate(over="ignore"):  # a value beyond float32 becomes inf and is refused below
+        p.max_rel_diff = float(np.float32(max_rel_diff))
+    if not (np.isfinite(p.max_rel_diff) and p.max_rel_diff >= 0.0):
+        raise ValueError("max_rel_diff must be finite as a float32 and at least 0")
+    p.depth_scaling_factor_to_meters = float(scale)
+    p.fx, p.fy, p.cx, p.cy = (float(camera[k]) for k in ("fx", "fy", "cx", "cy"))
+    p.range_min, p.range_max = float(range_min), float(range_max)
+    S = np.eye(4, dtype=np.float32) if sensor_in_robot is None else np.asarray(sensor_in_robot, np.float32).reshape(4, 4)
+    p.sensor_in_robot[:] = [float(x) for x in S.reshape(16)]
+    values = [p.depth_scaling_factor_to_meters, p.fx, p.fy, p.cx, p.cy, p.range_min, p.range_max] + list(p.sensor_in_robot)
+    if not np.isfinite(values).all():
+        raise ValueError("every parameter must be finite as a float32")
+    if not p.depth_scaling_factor_to_meters > 0.0:
+        raise ValueError("scale must be positive as a float32")
+    if not 0.0 <= p.range_min <= p.range_max:
+        raise ValueError("0 <= range_min <= range_max must hold")
+    return p
+
+
+class DepthConsistencyBatch:
+    """the depth consistency filter of B sequences of up to `frames` depth images of rows x cols pixels with up to `window`
+    neighbours on each side: owns out, the outputs named in `outputs` (support and violation [B, frames, rows, cols] uint8, n_kept
+    and n_removed [B, frames], n_skipped [B]), status and the workspace.  out, support and violation are views of rows padded to a
+    multiple of four elements; out is what DepthCloudBatch.run takes in place of the depth it was filtered from."""
+
+    OUTPUTS = ("support", "violation", "n_kept", "n_removed", "n_skipped")
+
+    def __init__(self, batch, frames, rows, cols, window, depth_type="u16", outputs=("n_kept", "n_removed"), device=0):
+        import torch
+        if set(outputs) - set(self.OUTPUTS):
+            raise ValueError("outputs: a subset of %s" % (self.OUTPUTS,))
+        if isinstance(depth_type, str) and depth_type not in _DEPTH_TYPES:
+            raise ValueError("depth_type: one of %s" % (sorted(_DEPTH_TYPES),))
+        self.depth_type = _DEPTH_TYPES[depth_type] if isinstance(depth_type, str) else int(depth_type)
+        if self.depth_type not in _DEPTH_TYPES.values():
+            raise ValueError("depth_type: one of %s" % (sorted(_DEPTH_TYPES),))
+        B, F = int(batch), int(frames)
+        if B < 1 or F < 1 or int(rows) < 1 or int(cols) < 1:
+            raise ValueError("batch, frames, rows and cols must be at least 1")
+        if not 1 <= int(window) <= 8:
+            raise ValueError("window must lie in 1 .. 8")
+        self.batch, self.frames, self.rows, self.cols, self.window = B, F, int(rows), int(cols), int(window)
+        self.dtype = torch.uint16 if self.depth_type == DEPTH_U16 else torch.float32
+        dev = torch.device("cuda", device) if isinstance(device, int) else device
+        z = lambda shape, dt: torch.zeros(shape, dtype=dt, device=dev)  # noqa: E731
+        padded = (self.cols + 3) // 4 * 4
+        self._out = z((B, F, self.rows, padded), self.dtype)
+        self.out = self._out[..., :self.cols]
+        self._support = z((B, F, self.rows, padded), torch.uint8) if "support" in outputs else None
+        self._violation = z((B, F, self.rows, padded), torch.uint8) if "violation" in outputs else None
+        self.support = self._support[..., :self.cols] if self._support is not None else None
+        self.violation = self._violation[..., :self.cols] if self._violation is not None else None
+        self.n_kept = z((B, F), torch.int32) if "n_kept" in outputs else None
+        self.n_removed = z((B, F), torch.int32) if "n_removed" in outputs else None
+        self.n_skipped = z((B,), torch.int32) if "n_skipped" in outputs else None
+        self.status = z((B,), torch.int32)
+        nbytes = int(_lib.load().prs_depth_consistency_workspace_bytes(B, F, self.window))
+        if nbytes < 1:
+            raise ValueError("no workspace for these sizes")
+        self.workspace = z((nbytes,), torch.uint8)
+
+    def descriptor(self, depth, pose, n_images=None, frame_index=None):
+        """the prs_depth_consistency_batch of device tensors: depth [B, frames, rows, cols (a view of longer rows is allowed: the
+        pitch)] of the depth type, pose [B, pose_stride, 16] float32, n_images [B] int32 or None = frames, frame_index [B, frames]
+        int32 or None"""
+        B, F = self.batch, self.frames
+        if depth.dtype != self.dtype or depth.dim() != 4 or tuple(depth.shape[:3]) != (B, F, self.rows) or int(depth.shape[3]) < self.cols or \
+                depth.stride(3) != 1:
+            raise ValueError("depth must be a %s tensor [%d, %d, %d, >= %d] with contiguous rows" % (self.dtype, B, F, self.rows, self.cols))
+        if int(depth.stride(1)) != self.rows * int(depth.stride(2)) or int(depth.stride(0)) != F * int(depth.stride(1)):
+            raise ValueError("the images of depth must follow one another at rows * pitch")
+        if pose.dim() != 3 or int(pose.shape[0]) != B or int(pose.shape[2]) != 16 or not pose.is_contiguous():
+            raise ValueError("pose must be a contiguous [%d, pose_stride, 16]" % B)
+        d = _lib.DepthConsistencyBatch()
+        d.batch, d.frames, d.rows, d.cols = B, F, self.rows, self.cols
+        es = depth.element_size()
+        d.pitch, d.out_pitch, d.count_pitch = int(depth.stride(2)) * es, int(self._out.stride(2)) * es, int(self._out.stride(2))
+        d.pose_stride = int(pose.shape[1])
+        d.depth, d.pose, d.out = depth.data_ptr(), pose.data_ptr(), self._out.data_ptr()
+        if n_images is not None:
+            if tuple(n_images.shape) != (B,) or n_images.dtype != self.status.dtype or not n_images.is_contiguous():
+                raise ValueError("n_images must be a contiguous int32 tensor [%d]" % B)
+            d.n_images = n_images.data_ptr()
+        if frame_index is not None:
+            if tuple(frame_index.shape) != (B, F) or frame_index.dtype != self.status.dtype or not frame_index.is_contiguous():
+                raise ValueError("frame_index must be a contiguous int32 tensor [%d, %d]" % (B, F))
+            d.frame_index = frame_index.data_ptr()
+        for name, t in (("support", self._support), ("violation", self._violation), ("n_kept", self.n_kept), ("n_removed", self.n_removed),
+                        ("n_skipped", self.n_skipped)):
+            setattr(d, name, t.data_ptr() if t is not None else None)
+        d.status, d.workspace = self.status.data_ptr(), self.workspace.data_ptr()
+        return d
+
+    def run(self, ctx, params, depth, pose, n_images=None, frame_index=None):
+        """enqueue the filter of every image (asynchronous) and return out; per-sequence status lands in self.status.  params.window
+        must not exceed the window the workspace was sized for"""
+        if params.window > self.window:
+            raise ValueError("params.window %d exceeds the window %d this batch was sized for" % (params.window, self.window))
+        d = self.descriptor(depth, pose, n_images, frame_index)
+        rc = _lib.load().prs_depth_consistency_batch_run(ctx._h, C.byref(params), C.byref(d))
+        _check(ctx, rc, "prs_depth_consistency_batch_run")
+        return self.out
+
+
 # ---- image rectifier: undistort and stereo-rectify raw frames in front of the extractors (include/proslam_hip.h prs_rectify_*) ----
 DISTORTION_RADTAN = 0                                # PRS_DISTORTION_*
 PIXEL_U8, PIXEL_U16, PIXEL_F32 = 0, 1, 2             # PRS_PIXEL_*
