@@ -109,6 +109,10 @@ PRS_API int prs_context_set_bruteforce_dense_phase(prs_context* ctx, int32_t mod
 PRS_API const char* prs_last_error(const prs_context* ctx);
 PRS_API const char* prs_status_string(int status);
 PRS_API int prs_version(void);
+/* The launch-size rule every launcher applies before its first launch: HIP takes no launch of 2^32 or more work-items in a grid
+ * dimension, so a launch of `workgroups` workgroups of `threads` threads fits iff workgroups >= 1, 1 <= threads <= 1024 and
+ * workgroups * threads <= 2^32 - 1 -- 2^24 - 1 workgroups of 256 threads.  1 when it fits, else 0 (pure: no context, no device). */
+PRS_API int prs_launch_fits(int64_t workgroups, int32_t threads);
 /* The parameter structs below carry no size field and grow at their END between versions (round 5 added three int32 fields to
  * prs_aligner_params).  PRS_ABI_VERSION is what this header describes, prs_version() what the loaded library was built from; a
  * client checks that they agree once (prs_abi_check: also the sizes of the structs it will pass, as the client's compiler laid
@@ -1031,7 +1035,8 @@ typedef struct {
 } prs_depth_batch;
 
 /* device pointers; enqueues one kernel on the context's stream (graph-capturable, like prs_extract_features_batch).  Inputs and
- * outputs must not overlap, except extract_status with status. */
+ * outputs must not overlap, except extract_status with status.  A workgroup of 256 threads an image: a batch beyond 2^24 - 1 is
+ * PRS_ERR_UNSUPPORTED (prs_launch_fits). */
 PRS_API int prs_depth_measurements_batch(prs_context* ctx, const prs_depth_params* params, const prs_depth_batch* batch);
 
 /* host pointers, one image: what an adapter's compute() binds.  depth: rows x cols elements of params->depth_type, `pitch` bytes
@@ -1940,7 +1945,7 @@ PRS_API void prs_map_archive_struct_sizes(uint64_t* sizes3);
  * n_opt and bounds of the output are optional); PRS_ERR_RANGE (batch, capacity or node_stride differ between the three structs or
  * are < 1, slot_stride < 1, out_stride < 0, or out_stride < 1 with xyz set); PRS_ERR_UNSUPPORTED (xyz, desc, coords, a state that is
  * written or the workspace not 16-byte aligned, graph_X not 8-byte aligned, another array not 4-byte aligned; batch * (slot_stride +
- * 1) * ceil(capacity / 256) beyond 2^31 - 1 workgroups or (slot_stride + 1) * capacity beyond 2^31 - 1 rows).
+ * 1) * ceil(capacity / 256) beyond 2^24 - 1 workgroups (the 2^32 - 1 work-items of one launch: prs_launch_fits) or (slot_stride + 1) * capacity beyond 2^31 - 1 rows).
  * A stable stream compaction spread over (sequence, map, chunk of 256 rows), so that one sequence of hundreds of maps fills the
  * device: count (a workgroup per chunk), scan (a workgroup per sequence: validation, node order, chunk bases), scatter (a workgroup
  * per chunk: ballots, wave totals in LDS, the scanned base) and, with bounds, a reduction per sequence.  Up to four plain launches
@@ -2023,7 +2028,7 @@ PRS_API void prs_world_map_struct_sizes(uint64_t* sizes2);
  * n_nonfinite, n_outside, status or the workspace unset); PRS_ERR_RANGE (batch or in_stride < 1, table_stride not a power of two
  * >= 1, voxel_size not finite or <= 0, an unknown position, out_stride < 1 with xyz set); PRS_ERR_UNSUPPORTED (in_xyz, in_desc, xyz,
  * desc or the workspace not 16-byte aligned, another array not 4-byte aligned; batch * ceil(in_stride / 256) or batch *
- * ceil(table_stride / 256) beyond 2^31 - 1 workgroups).
+ * ceil(table_stride / 256) beyond 2^24 - 1 workgroups, the 2^32 - 1 work-items of one launch: prs_launch_fits).
  * Five plain launches on the context's stream (four in a count-only call): clear the tables, insert (one thread per row: the key,
  * linear probing by 64-bit compare-and-swap, then an integer min on the rank, an add on the count and, MEAN only, on the three
  * sums), flag the representatives and count them per chunk of 256 rows, scan (a workgroup per sequence: validation, table overflow,
@@ -2274,7 +2279,7 @@ PRS_API void prs_trajectory_struct_sizes(uint64_t* sizes3);
  * never written.
  * Call-level (return value, nothing enqueued, outputs untouched): PRS_ERR_NULL (params, batch, src, dst, maps or status unset);
  * PRS_ERR_UNSUPPORTED (an unknown pixel_type or interpolation, bilinear for other than PRS_PIXEL_U8, dst not 4-byte aligned, src not
- * aligned to its element, src and dst overlapping, more than 2^31 - 1 workgroups); PRS_ERR_RANGE (batch, n_maps or a size below 1,
+ * aligned to its element, src and dst overlapping, a launch beyond 2^32 - 1 work-items, which is 2^24 - 1 workgroups of 256 threads: prs_launch_fits); PRS_ERR_RANGE (batch, n_maps or a size below 1,
  * a pitch below cols * element size or not a multiple of the element size, an image of 2^31 bytes or more).
  * One kernel launch behind one clear of n_border on the context's stream: no allocation, no synchronisation, no host read,
  * graph-capturable like prs_extract_features_batch.  The map costs about a hundred vector instructions and two divisions a pixel,
@@ -2369,8 +2374,8 @@ PRS_API void prs_rectify_struct_sizes(uint64_t* sizes3);
  * cols elements or not a multiple of the element size, gray_pitch below cols with gray set; a parameter that is not finite --
  * sensor_in_robot included --, a scale <= 0, range_min < 0 or range_min > range_max; out_stride < 1 with xyz set);
  * PRS_ERR_UNSUPPORTED (an unknown depth_type; xyz or the workspace not 16-byte aligned, depth not aligned to its element, another
- * array but gray not 4-byte aligned; rows * cols or frames * ceil(rows / step) * ceil(cols / step) beyond 2^31 - 1; a grid beyond
- * 2^31 - 1 workgroups).
+ * array but gray not 4-byte aligned; rows * cols or frames * ceil(rows / step) * ceil(cols / step) beyond 2^31 - 1; a launch, the scan's
+ * included, beyond 2^32 - 1 work-items, which is 2^24 - 1 workgroups of 256 threads: prs_launch_fits).
  * Three plain launches on the context's stream (two in a count-only call): count (a workgroup per chunk of 1024 sampled pixels of
  * one image, four consecutive samples a lane, wave ballots), scan (a workgroup per sequence: validation, the skipped frames,
  * n_base, truncation, the chunk bases) and scatter (the same ballots order the chunk's rows in LDS, from where they go out behind
@@ -2459,7 +2464,8 @@ PRS_API void prs_depth_cloud_struct_sizes(uint64_t* sizes2);
  * min_disparity + n_disparities > 4096, aggregation_radius outside 0 .. 7, uniqueness_percent outside 0 .. 99, lr_max_diff outside
  * -1 .. 255, bf not finite or <= 0; batch, frames, rows or cols < 1, left_pitch or right_pitch < cols, out_pitch < 4 * cols or not a
  * multiple of 4); PRS_ERR_UNSUPPORTED (disparity, depth, n_images, n_valid or status not 4-byte aligned, the workspace not 16-byte;
- * batch * frames * rows * cols beyond 2^31 - 1; a grid beyond 2^31 - 1 workgroups).
+ * batch * frames * rows * cols beyond 2^31 - 1; a launch beyond 2^32 - 1 work-items, which is 2^24 - 1 workgroups of 256 threads:
+ * prs_launch_fits).
  * Four plain launches on the context's stream (three with lr_max_diff = -1): census (a workgroup per 64 x 16 tile of an image, the
  * tile and its halo in LDS once), match for the left and for the right reference and each radius (a workgroup owns 64 - 2 r columns of a band of 32
  * rows and walks down it: lane x of each of its four waves is column x of the tile with its halo, a wave takes every fourth pair
@@ -2541,7 +2547,8 @@ PRS_API void prs_dense_stereo_struct_sizes(uint64_t* sizes2);
  * elements or not a multiple of the element size; max_diff not finite or < 0; max_size < 0); PRS_ERR_UNSUPPORTED (a pixel_type
  * -- or, with a companion, a companion_type -- that is unknown or PRS_PIXEL_U8; image or companion not aligned to its element,
  * n_images, label, n_kept, n_removed or status not 4-byte aligned, the workspace not 16-byte; companion or label overlapping
- * image; rows * cols or batch * frames * rows * cols beyond 2^31 - 1; a grid beyond 2^31 - 1 workgroups).
+ * image; rows * cols or batch * frames * rows * cols beyond 2^31 - 1; a launch beyond 2^32 - 1 work-items, which is 2^24 - 1
+ * workgroups of 256 threads: prs_launch_fits).
  * Four plain launches on the context's stream (three for an image of one tile): tile (a workgroup per 64 x 16 tile of an image:
  * the values in LDS, the runs of each row from one wave ballot, vertical unions in LDS, flattened, out goes the raster index of
  * the tile's root), seam (a thread per pixel pair across a tile border: the same union in global memory), flatten (a workgroup
@@ -2632,8 +2639,8 @@ PRS_API void prs_speckle_struct_sizes(uint64_t* sizes2);
  * min_disparity + n_disparities > 4096, n_paths not 4 or 8, p1 < 0, p2 < p1 or p2 > 4095, uniqueness_percent outside 0 .. 99,
  * lr_max_diff outside -1 .. 255, bf not finite or <= 0; batch, frames, rows, cols or images_in_flight < 1, left_pitch or
  * right_pitch < cols, out_pitch < 4 * cols or not a multiple of 4); PRS_ERR_UNSUPPORTED (disparity, depth, n_images, n_valid or
- * status not 4-byte aligned, the workspace not 16-byte; batch * frames * rows * cols beyond 2^31 - 1; a grid beyond 2^31 - 1
- * workgroups).
+ * status not 4-byte aligned, the workspace not 16-byte; batch * frames * rows * cols beyond 2^31 - 1; a launch of a chunk, of the
+ * census or of the finish beyond 2^32 - 1 work-items, which is 2^24 - 1 workgroups of 256 threads: prs_launch_fits).
  * The S volume of one image is rows * cols * n_disparities uint16 (119 MB for a KITTI image at 128 disparities), so the call
  * works through the images b * frames + f in chunks of images_in_flight (a value above batch * frames counts as batch * frames)
  * and reuses one set of volumes for every chunk.  Plain launches on the context's stream, 2 + chunks * (n_paths + 2) of them
@@ -2738,8 +2745,8 @@ PRS_API void prs_sgm_stereo_struct_sizes(uint64_t* sizes2);
  * scale <= 0, range_min < 0 or range_min > range_max; pitch or out_pitch below cols elements or not a multiple of the element
  * size, count_pitch below cols with support or violation set); PRS_ERR_UNSUPPORTED (an unknown depth_type; depth or out not
  * aligned to the element, the workspace not 16-byte, another array but support and violation not 4-byte; out, support or violation
- * overlapping depth -- neighbours are read while out is written --; rows or cols above 2^24; batch * frames * rows * cols or a
- * grid beyond 2^31 - 1).
+ * overlapping depth -- neighbours are read while out is written --; rows or cols above 2^24; batch * frames * rows * cols beyond
+ * 2^31 - 1; a launch, prepare's included, beyond 2^32 - 1 work-items, which is 2^24 - 1 workgroups of 256 threads: prs_launch_fits).
  * Two plain launches on the context's stream.  prepare (a workgroup per sequence): validation, the usable flags, n_skipped, status,
  * zeroes in n_kept / n_removed, and one 64-byte record per image and slot in the workspace -- M, the exists flag and, in slot 0,
  * the state of the image -- so the float64 work is done once per slot, never per pixel.  filter (a workgroup per 64 x 32 pixels of

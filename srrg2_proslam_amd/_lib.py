@@ -650,6 +650,7 @@ _vp = C.c_void_p
 _i32p = C.POINTER(C.c_int32)
 SYMBOLS = {
     "prs_version": (C.c_int, []),
+    "prs_launch_fits": (C.c_int, [C.c_int64, C.c_int32]),
     "prs_abi_check": (C.c_int, [C.c_int32, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64]),
     "prs_status_string": (C.c_char_p, [C.c_int]),
     "prs_context_create": (C.c_int, [C.c_int, C.POINTER(_vp)]),

@@ -182,6 +182,10 @@ int prs_version(void) {
   return PRS_ABI_VERSION;  // prs_aligner_params grew at its end: round 5 kernel_weight_form, damping_form, translation_weight_form; round 6 step_norm_exit
 }
 
+int prs_launch_fits(int64_t workgroups, int32_t threads) {
+  return grid_fits(workgroups, threads) ? 1 : 0;
+}
+
 int prs_abi_check(int32_t header_version, uint64_t sizeof_stereo_params, uint64_t sizeof_pcf_params, uint64_t sizeof_aligner_params,
                   uint64_t sizeof_align_batch) {
   // (no context: the answer is the status alone)

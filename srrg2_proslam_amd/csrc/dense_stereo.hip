@@ -388,8 +388,8 @@ Layout layout_of(const int64_t batch, const int64_t frames, const int64_t rows, 
 
 }  // namespace
 
-// the census and the finish launch for the stages that share them (sgm_stereo.hip): the caller has checked the batch; false when a
-// grid would pass 2^31 - 1 workgroups, and then nothing is launched
+// the census and the finish launch for the stages that share them (sgm_stereo.hip): the caller has checked the batch; false when the
+// launch would pass 2^32 - 1 work-items (grid_fits), and then nothing is launched
 bool dense_census_enqueue(hipStream_t st, const prs_dense_stereo_batch& o, uint64_t* census_l, uint64_t* census_r) {
   DenseStereoArgs a = {};
   a.o        = o;
@@ -398,7 +398,7 @@ bool dense_census_enqueue(hipStream_t st, const prs_dense_stereo_batch& o, uint6
   a.census_l = census_l;
   a.census_r = census_r;
   const int64_t blocks = (int64_t) o.batch * o.frames * 2 * a.ctiles_x * a.ctiles_y;
-  if (blocks > 0x7fffffffll) {
+  if (!grid_fits(blocks, kThreads)) {
     return false;
   }
   hipLaunchKernelGGL(dense_census_kernel, dim3((unsigned) blocks), dim3(kThreads), 0, st, a);
@@ -413,7 +413,7 @@ bool dense_finish_enqueue(hipStream_t st, const prs_dense_stereo_params& p, cons
   a.rec_l   = rec_l;
   a.win_r   = win_r;
   const int64_t blocks = (int64_t) o.batch * o.frames * a.fblocks;
-  if (blocks > 0x7fffffffll) {
+  if (!grid_fits(blocks, kThreads)) {
     return false;
   }
   hipLaunchKernelGGL(dense_finish_kernel, dim3((unsigned) blocks), dim3(kThreads), 0, st, a);
@@ -461,8 +461,8 @@ int dense_stereo_launch(prs_context* ctx, const prs_dense_stereo_params* params,
   const int64_t images = (int64_t) o.batch * o.frames;
   const int64_t census_blocks = images * 2 * a.ctiles_x * a.ctiles_y, match_blocks = images * a.bands * a.tiles,
                 finish_blocks = images * a.fblocks;  // each factor is below 2^31 and images * rows * cols is
-  if (census_blocks > 0x7fffffffll || match_blocks > 0x7fffffffll || finish_blocks > 0x7fffffffll) {
-    return ctx_fail(ctx, PRS_ERR_UNSUPPORTED, (who + ": more workgroups than one grid holds").c_str());
+  if (!grid_fits(census_blocks, kThreads) || !grid_fits(match_blocks, kThreads) || !grid_fits(finish_blocks, kThreads)) {
+    return ctx_fail(ctx, PRS_ERR_UNSUPPORTED, (who + ": more work-items than one launch holds").c_str());
   }
   uint8_t* ws = static_cast<uint8_t*>(o.workspace);
   a.census_l  = reinterpret_cast<uint64_t*>(ws);

@@ -324,8 +324,9 @@ int depth_cloud_launch(prs_context* ctx, const prs_depth_cloud_params* params, c
     return ctx_fail(ctx, PRS_ERR_UNSUPPORTED, (who + ": rows * cols or frames * sampled pixels beyond 2^31 - 1").c_str());
   }
   const int64_t C = (int64_t) o.frames * l.chunks_per_frame, blocks = (int64_t) o.batch * C;  // C <= frames * samples < 2^31
-  if (blocks > 0x7fffffffll) {
-    return ctx_fail(ctx, PRS_ERR_UNSUPPORTED, (who + ": batch * frames * chunks of 1024 sampled pixels beyond one grid").c_str());
+  const unsigned wide = (unsigned) std::min<long long>(kWideThreads, ((C + kCompactBatch - 1) / kCompactBatch + PRS_WAVE - 1) / PRS_WAVE * PRS_WAVE);
+  if (!grid_fits(blocks, kThreads) || !grid_fits(o.batch, (int) wide)) {  // the two passes and the scan
+    return ctx_fail(ctx, PRS_ERR_UNSUPPORTED, (who + ": batch * frames * chunks of 1024 sampled pixels beyond the work-items of one launch").c_str());
   }
   DepthCloudArgs a = {};
   a.p = p;
@@ -344,7 +345,6 @@ int depth_cloud_launch(prs_context* ctx, const prs_depth_cloud_params* params, c
   } else {
     launch_pass<float>(a, vec, false, (unsigned) blocks, st);
   }
-  const unsigned wide = (unsigned) std::min<long long>(kWideThreads, ((C + kCompactBatch - 1) / kCompactBatch + PRS_WAVE - 1) / PRS_WAVE * PRS_WAVE);
   hipLaunchKernelGGL(depth_cloud_scan_kernel, dim3((unsigned) o.batch), dim3(wide), 0, st, a);
   if (a.write_out) {
     if (u16) {

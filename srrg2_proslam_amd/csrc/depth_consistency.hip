@@ -322,8 +322,8 @@ int depth_consistency_launch(prs_context* ctx, const prs_depth_consistency_param
   a.tiles_y = (o.rows + kTileH * kGroups - 1) / (kTileH * kGroups);
   a.rec     = static_cast<SlotRecord*>(o.workspace);
   const int64_t blocks = images * a.tiles_x * a.tiles_y;  // images * tiles_y <= images * rows < 2^31, tiles_x < 2^19
-  if (blocks > 0x7fffffffll) {
-    return ctx_fail(ctx, PRS_ERR_UNSUPPORTED, (who + ": more workgroups than one grid holds").c_str());
+  if (!grid_fits(o.batch, kThreads) || !grid_fits(blocks, kThreads)) {  // prepare and filter
+    return ctx_fail(ctx, PRS_ERR_UNSUPPORTED, (who + ": more work-items than one launch holds").c_str());
   }
   hipStream_t st = ctx_stream(ctx);
   hipLaunchKernelGGL(depth_consistency_prepare_kernel, dim3((unsigned) o.batch), dim3(kThreads), 0, st, a);

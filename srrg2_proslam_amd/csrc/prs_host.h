@@ -81,6 +81,12 @@ inline hipStream_t ctx_stream(prs_context* ctx) {
     }                         \
   } while (0)
 
+// whether one launch may have this grid: HIP takes no launch of 2^32 or more work-items in a dimension (hip_runtime_api.h, the note
+// on hipModuleLaunchKernel), which for 256 threads is 2^24 - 1 workgroups.  No product here overflows for any int64 count
+inline bool grid_fits(const int64_t workgroups, const int threads) {
+  return workgroups >= 1 && threads >= 1 && threads <= 1024 && workgroups <= 0xffffffffll / threads;
+}
+
 inline size_t align256(size_t v) {
   return (v + 255) / 256 * 256;
 }

@@ -402,8 +402,8 @@ int rectify_launch(prs_context* ctx, const prs_rectify_params* params, const prs
   }
   a.chunk = (int) chunk;
   const int64_t grid = tiles * ((batch->batch + chunk - 1) / chunk);
-  if (grid > INT32_MAX) {
-    return ctx_fail(ctx, PRS_ERR_UNSUPPORTED, "prs_rectify_batch_run: more than 2^31 - 1 workgroups");
+  if (!grid_fits(grid, kThreads)) {
+    return ctx_fail(ctx, PRS_ERR_UNSUPPORTED, "prs_rectify_batch_run: more than 2^32 - 1 work-items in one launch");
   }
   a.stage_ok     = (s0 % 16 == 0 && batch->src_pitch % 16 == 0) ? 1 : 0;
   a.vector_store = (d0 % (uintptr_t) (4 * elem) == 0 && batch->dst_pitch % (4 * elem) == 0) ? 1 : 0;

@@ -158,6 +158,9 @@ int depth_measurements_launch(prs_context* ctx, const prs_depth_params* params, 
       !aligned(batch->depth, (size_t) elem)) {
     return ctx_fail(ctx, PRS_ERR_UNSUPPORTED, "prs_depth_measurements_batch: fixed / descriptor rows must be 16-byte aligned");
   }
+  if (!grid_fits(batch->batch, kThreads)) {
+    return ctx_fail(ctx, PRS_ERR_UNSUPPORTED, "prs_depth_measurements_batch: more work-items than one launch holds");
+  }
   DepthArgs a;
   memset(&a, 0, sizeof(a));
   a.b          = *batch;

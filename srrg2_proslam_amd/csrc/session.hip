@@ -878,8 +878,8 @@ int session_unroll_launch(prs_context* ctx, const prs_session_batch* batch, floa
   }
   const long long total  = (long long) batch->batch * batch->frame_stride;
   const long long blocks = (total + kThreads - 1) / kThreads;
-  if (blocks > 0x7fffffffll) {
-    return ctx_fail(ctx, PRS_ERR_UNSUPPORTED, "prs_session_unroll_batch: batch * frame_stride beyond one grid");
+  if (!grid_fits(blocks, kThreads)) {
+    return ctx_fail(ctx, PRS_ERR_UNSUPPORTED, "prs_session_unroll_batch: batch * frame_stride beyond the work-items of one launch");
   }
   hipLaunchKernelGGL(session_unroll_kernel, dim3((unsigned) blocks), dim3(kThreads), 0, ctx_stream(ctx), *batch, out);
   const hipError_t e = hipGetLastError();

@@ -457,8 +457,9 @@ int sgm_stereo_launch(prs_context* ctx, const prs_sgm_stereo_params* params, con
   const int64_t winner_blocks_max = (in_flight * a.runs + kWaves - 1) / kWaves;
   const int64_t census_blocks = images * 2 * ((o.cols + 63) / 64) * ((o.rows + 15) / 16), finish_blocks = images * ((o.rows + 7) / 8);
   const int64_t right_blocks_max = in_flight * o.rows * a.rtiles;
-  if (right_blocks_max > 0x7fffffffll || path_blocks_max > 0x7fffffffll || winner_blocks_max > 0x7fffffffll || census_blocks > 0x7fffffffll || finish_blocks > 0x7fffffffll) {
-    return ctx_fail(ctx, PRS_ERR_UNSUPPORTED, (who + ": more workgroups than one grid holds").c_str());
+  if ((lr && !grid_fits(right_blocks_max, kThreads)) || !grid_fits(path_blocks_max, kThreads) || !grid_fits(winner_blocks_max, kThreads) ||
+      !grid_fits(census_blocks, kThreads) || !grid_fits(finish_blocks, kThreads)) {
+    return ctx_fail(ctx, PRS_ERR_UNSUPPORTED, (who + ": more work-items than one launch holds").c_str());
   }
   const int n = p.n_disparities;
   const PathKernel path = n <= 64    ? sgm_path_kernel<1, true>
@@ -470,7 +471,7 @@ int sgm_stereo_launch(prs_context* ctx, const prs_sgm_stereo_params* params, con
 
   hipStream_t st = ctx_stream(ctx);
   if (!dense_census_enqueue(st, db, const_cast<uint64_t*>(a.census_l), const_cast<uint64_t*>(a.census_r))) {
-    return ctx_fail(ctx, PRS_ERR_UNSUPPORTED, (who + ": more workgroups than one grid holds").c_str());
+    return ctx_fail(ctx, PRS_ERR_UNSUPPORTED, (who + ": more work-items than one launch holds").c_str());
   }
   for (int64_t image0 = 0; image0 < images; image0 += in_flight) {
     a.image0  = (int32_t) image0;

@@ -444,8 +444,8 @@ int speckle_launch(prs_context* ctx, const prs_speckle_params* params, const prs
   a.pblocks = (int32_t) (((int64_t) o.rows * o.cols + kChunk - 1) / kChunk);
   const int64_t images = (int64_t) o.batch * o.frames;
   const int64_t tile_blocks = images * a.tiles_x * a.tiles_y, seam_blocks = images * a.sblocks, pixel_blocks = images * a.pblocks;
-  if (tile_blocks > 0x7fffffffll || seam_blocks > 0x7fffffffll || pixel_blocks > 0x7fffffffll) {
-    return ctx_fail(ctx, PRS_ERR_UNSUPPORTED, (who + ": more workgroups than one grid holds").c_str());
+  if (!grid_fits(tile_blocks, kThreads) || (seam_blocks > 0 && !grid_fits(seam_blocks, kThreads)) || !grid_fits(pixel_blocks, kThreads)) {
+    return ctx_fail(ctx, PRS_ERR_UNSUPPORTED, (who + ": more work-items than one launch holds").c_str());
   }
   uint8_t* ws = static_cast<uint8_t*>(o.workspace);
   a.parent    = reinterpret_cast<int32_t*>(ws);

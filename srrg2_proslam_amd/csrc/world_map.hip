@@ -497,8 +497,8 @@ int world_map_launch(prs_context* ctx, const prs_world_map_params* params, const
   }
   const long long M = (long long) ar.slot_stride + 1, C = ((long long) s.capacity + kChunk - 1) / kChunk;
   const long long blocks = (long long) s.batch * M * C;
-  if (blocks > 0x7fffffffll || M * (long long) s.capacity > 0x7fffffffll) {
-    return ctx_fail(ctx, PRS_ERR_UNSUPPORTED, (who + ": batch * (slot_stride + 1) * chunks beyond one grid, or a sequence's rows beyond 2^31").c_str());
+  if (!grid_fits(blocks, kThreads) || M * (long long) s.capacity > 0x7fffffffll) {
+    return ctx_fail(ctx, PRS_ERR_UNSUPPORTED, (who + ": batch * (slot_stride + 1) * chunks beyond the work-items of one launch, or a sequence's rows beyond 2^31").c_str());
   }
   WorldMapArgs a = {};
   a.p = *params;

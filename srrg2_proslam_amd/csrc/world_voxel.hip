@@ -385,8 +385,8 @@ int world_voxel_launch(prs_context* ctx, const prs_world_voxel_params* params, c
   }
   const long long C = chunks_of(o.in_stride), TC = chunks_of(o.table_stride);
   const long long blocks = (long long) o.batch * C, clear_blocks = (long long) o.batch * TC;
-  if (blocks > 0x7fffffffll || clear_blocks > 0x7fffffffll) {
-    return ctx_fail(ctx, PRS_ERR_UNSUPPORTED, (who + ": batch * ceil(in_stride / 256) or batch * ceil(table_stride / 256) beyond one grid").c_str());
+  if (!grid_fits(blocks, kThreads) || !grid_fits(clear_blocks, kThreads)) {  // (the scan has at most 64 * C threads a sequence)
+    return ctx_fail(ctx, PRS_ERR_UNSUPPORTED, (who + ": batch * ceil(in_stride / 256) or batch * ceil(table_stride / 256) beyond the work-items of one launch").c_str());
   }
   WorldVoxelArgs a = {};
   a.p = *params;

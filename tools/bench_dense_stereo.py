@@ -3,7 +3,7 @@ usage: python tools/bench_dense_stereo.py [kitti|euroc ...] [--batch N ...] [--d
                                           [--no-breakdown] [--no-check] [--once]
   Shapes: kitti 376 x 1241, euroc 480 x 752; batches default to 1 64 1024 (a batch that does not fit the free memory is skipped).
   The pairs are seeded: four distinct right images of random bytes, the left ones shifted by a disparity that changes from band to
-  band of rows, replicated over the batch.  The first pair is compared with the restatement (tests/dense_stereo_ref.py) byte for byte.
+  band of rows, replicated over the batch.  The first and the last pair are compared with the restatement (tests/dense_stereo_ref.py) byte for byte.
   Per shape and batch, timed with events on the stream in interleaved rounds (median and minimum over the rounds):
     call       ms per call (census, left match, right match, finish) and us per pair
     no lr      the call with lr_max_diff = -1: without the right match and its winners
@@ -112,8 +112,9 @@ def bench(ctx, name, B, args):
            "valid_share": float(ds.n_valid.sum().item()) / pixels, "workspace_bytes": int(ds.workspace.numel()),
            "hbm_bytes": pixels * HBM_BYTES_PER_PIXEL}
     if not args.no_check:
-        want = ref.dense_stereo_image(left_np[0], right_np[0], ref.params(p.bf, args.disparities, 0, args.radius, 10, 1))
-        for b in sorted({0, B - 1} if (B - 1) % left_np.shape[0] == 0 else {0}):
+        for b in sorted({0, B - 1}):  # the first pair, and the last one: the one at the highest address
+            i = b % left_np.shape[0]
+            want = ref.dense_stereo_image(left_np[i], right_np[i], ref.params(p.bf, args.disparities, 0, args.radius, 10, 1))
             assert ds.disparity[b, 0].cpu().numpy().tobytes() == want["disparity"].tobytes(), "the kernels and the restatement disagree"
             assert ds.depth[b, 0].cpu().numpy().tobytes() == want["depth"].tobytes() and int(ds.n_valid[b, 0].item()) == want["n_valid"]
         out["checked"] = True

@@ -5,7 +5,7 @@ usage: python tools/bench_depth_consistency.py [vga|kitti ...] [--layout BxF ...
   (sequences x frames; one that does not fit the free memory is skipped), windows to 1 2 4.  Input: the scene of
   tests/depth_consistency_ref.py -- a wall 5 m away with a rectangle 3 m away in front of it -- seen from `frames` cameras 3 cm and 4
   mrad apart, 5 % of the pixels' depths off by a factor; every sequence of the batch holds a copy of its own.  Where the whole
-  restatement is affordable (frames * 2 * window <= 32) sequence 0 is compared with it byte for byte before anything is timed.
+  restatement is affordable (frames * 2 * window <= 32) the first and the last sequence are compared with it byte for byte before anything is timed.
   Each call has its own pair of events on the stream; the calls take turns round by round (median and minimum over the rounds):
     call         ms per call (prepare, filter) and us per image
     copy         a device-to-device copy of the floor's bytes

@@ -3,7 +3,7 @@ usage: python tools/bench_sgm_stereo.py [kitti|euroc ...] [--batch N ...] [--pat
                                         [--json FILE] [--no-breakdown] [--no-check] [--once]
   Shapes: kitti 376 x 1241, euroc 480 x 752; batches default to 1 64 1024 (a batch that does not fit the free memory is skipped),
   paths to 4 and 8.  The pairs are those of tools/bench_dense_stereo.py: four distinct right images of random bytes, the left ones
-  shifted by a disparity that changes from band to band of rows, replicated over the batch.  The first pair is compared with the
+  shifted by a disparity that changes from band to band of rows, replicated over the batch.  The first and the last pair are compared with the
   restatement (tests/sgm_stereo_ref.py) byte for byte before anything is timed.
   Per shape, batch and path count, timed with events on the stream in interleaved rounds (median and minimum over the rounds):
     call       ms per call (census, per chunk of images_in_flight images a path launch a direction, a winner and a right-winner
@@ -71,9 +71,9 @@ def interleaved(fns, rounds):
     return {k: (float(np.median(v)), float(np.min(v))) for k, v in times.items()}
 
 
-def reference(name, n_paths, left, right, bf, n_disparities):
+def reference(name, n_paths, index, left, right, bf, n_disparities):
     import sgm_stereo_ref as ref
-    key = (name, n_paths, n_disparities)
+    key = (name, n_paths, n_disparities, index)
     if key not in _reference:
         _reference[key] = ref.sgm_stereo_image(left, right, ref.params(bf, n_disparities, 0, 10, 120, n_paths, 10, 1))
     return _reference[key]
@@ -104,8 +104,9 @@ def bench(ctx, name, B, n_paths, args):
            "valid_share": float(sg.n_valid.sum().item()) / pixels, "workspace_bytes": int(sg.workspace.numel()),
            "hbm_bytes": pixels * args.disparities * (2 * 2 * n_paths - 2)}
     if not args.no_check:
-        want = reference(name, n_paths, left_np[0], right_np[0], p.bf, args.disparities)
-        for b in sorted({0, B - 1} if (B - 1) % left_np.shape[0] == 0 else {0}):
+        for b in sorted({0, B - 1}):  # the first pair, and the last one: the one at the highest address
+            i = b % left_np.shape[0]
+            want = reference(name, n_paths, i, left_np[i], right_np[i], p.bf, args.disparities)
             assert sg.disparity[b, 0].cpu().numpy().tobytes() == want["disparity"].tobytes(), "the kernels and the restatement disagree"
             assert sg.depth[b, 0].cpu().numpy().tobytes() == want["depth"].tobytes() and int(sg.n_valid[b, 0].item()) == want["n_valid"]
         out["checked"] = True

@@ -8,7 +8,7 @@ usage: python tools/bench_speckle.py [kitti|euroc|vga ...] [--batch N ...] [--in
                 matcher leaves islands (vga: its depth, in millimetres): the typical case
     one         a constant image: one component, every add of a size to one word
     serpentine  every other row whole, joined at alternating ends: one path through every tile and across every seam, the longest walks
-  The first image of every configuration is compared with the restatement (tests/speckle_ref.py) byte for byte before anything is
+  The first and the last image of every configuration are compared with the restatement (tests/speckle_ref.py) byte for byte before anything is
   timed.  The call works in place, so every timed call is preceded by an untimed copy that restores the image; each call has its own
   pair of events on the stream; the inputs take turns round by round (median and minimum over the rounds):
     call          ms per call (tile, seam, flatten, apply) and us per image
@@ -135,8 +135,8 @@ def bench(ctx, name, B, args):
         kept, removed = int(sf.n_kept.sum().item()), int(sf.n_removed.sum().item())
         out["inputs"][k] = {"valid_share": (kept + removed) / pixels, "removed_share_of_valid": removed / max(kept + removed, 1)}
         if not args.no_check:
-            want = ref.speckle_image(src[0, 0].cpu().numpy(), None, ref.params(args.max_size, args.max_diff))
-            for b in sorted({0, B - 1} if (B - 1) % N_DISTINCT == 0 or k != "stereo" else {0}):
+            for b in sorted({0, B - 1}):  # the first image, and the last one: the one at the highest address
+                want = ref.speckle_image(src[b, 0].cpu().numpy(), None, ref.params(args.max_size, args.max_diff))
                 assert image[b, 0].cpu().numpy().tobytes() == want["image"].tobytes(), "the kernels and the restatement disagree"
                 assert (int(sf.n_kept[b, 0].item()), int(sf.n_removed[b, 0].item())) == (want["n_kept"], want["n_removed"])
             out["inputs"][k]["checked"] = True
