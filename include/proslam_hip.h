@@ -109,7 +109,7 @@ PRS_API int prs_context_set_bruteforce_dense_phase(prs_context* ctx, int32_t mod
 PRS_API const char* prs_last_error(const prs_context* ctx);
 PRS_API const char* prs_status_string(int status);
 PRS_API int prs_version(void);
-/* The launch-size rule every launcher applies before its first launch: HIP takes no launch of 2^32 or more work-items in a grid
+/* The launch-size rule every entry point applies to every launch of a call before the first one: HIP takes no launch of 2^32 or more work-items in a grid
  * dimension, so a launch of `workgroups` workgroups of `threads` threads fits iff workgroups >= 1, 1 <= threads <= 1024 and
  * workgroups * threads <= 2^32 - 1 -- 2^24 - 1 workgroups of 256 threads.  1 when it fits, else 0 (pure: no context, no device). */
 PRS_API int prs_launch_fits(int64_t workgroups, int32_t threads);
@@ -217,6 +217,8 @@ typedef struct {
   const prs_triangulator_params* triangulator; /* HOST pointer, read at enqueue */
 } prs_stereo_batch;
 
+/* Launch size: a launch beyond 2^32 - 1 work-items is PRS_ERR_UNSUPPORTED with nothing enqueued or written (prs_launch_fits): the unstaged kernel of frames beyond 2048 keypoints has a workgroup of 1024 threads a frame, batch <= 2^22 - 1;
+ * the staged kernels launch no more workgroups than the device has compute units. */
 PRS_API int prs_stereo_match_batch(prs_context* ctx,
                                    const prs_stereo_params* params,
                                    const prs_stereo_batch* batch);
@@ -234,7 +236,7 @@ PRS_API int prs_triangulate(prs_context* ctx,
                             float* xyz,        /* host [n][3] */
                             uint8_t* valid);   /* host [n] */
 
-/* device: uvuv [n][4] -> xyz4 [n][4] = (x, y, z, valid) */
+/* device: uvuv [n][4] -> xyz4 [n][4] = (x, y, z, valid).  At most 2048 workgroups stride over the points: any n fits one launch */
 PRS_API int prs_triangulate_dev(prs_context* ctx,
                                 const prs_triangulator_params* params,
                                 const float* d_uvuv,
@@ -438,6 +440,8 @@ typedef struct {
 /* mode PRS_MODE_FINDER and PRS_MODE_LINEARIZE only enqueue.  mode PRS_MODE_ALIGN alternates a search launch and a Gauss-Newton
  * launch over the frames that are still pending (4-5 rounds at kitti.conf settings) and BLOCKS until the batch is done
  * (= prs_align_batch_enqueue + prs_align_batch_finish); results are complete in device memory when it returns. */
+/* Launch size: a launch beyond 2^32 - 1 work-items is PRS_ERR_UNSUPPORTED with nothing enqueued or written (prs_launch_fits): the search launch has a workgroup of 512 threads a frame, batch <= 2^23 - 1 (the fused kernel: 256 threads,
+ * 2^24 - 1).  prs_align_batch_enqueue alike. */
 PRS_API int prs_align_batch_run(prs_context* ctx,
                                 const prs_pcf_params* finder,
                                 const prs_aligner_params* aligner,
@@ -558,6 +562,8 @@ typedef struct {
 } prs_clip_batch;
 
 /* device pointers, asynchronous on the context's stream */
+/* Launch size: a launch beyond 2^32 - 1 work-items is PRS_ERR_UNSUPPORTED with nothing enqueued or written (prs_launch_fits): a workgroup of 256 threads a scene (128 scenes or more, or scenes of up to two tiles), batch <= 2^24 - 1;
+ * fewer and longer scenes: tiles x batch workgroups, each dimension on its own. */
 PRS_API int prs_scene_clip_batch(prs_context* ctx,
                                  const prs_projector* projector,
                                  const float* sensor_in_robot16, /* host */
@@ -609,6 +615,8 @@ typedef struct {
 } prs_bruteforce_batch;
 
 /* device pointers, asynchronous on the context's stream */
+/* Launch size: a launch beyond 2^32 - 1 work-items is PRS_ERR_UNSUPPORTED with nothing enqueued or written (prs_launch_fits): the registration launch of the split shape has a workgroup of 1024 threads a cloud pair, batch <= 2^22 - 1;
+ * the fused shapes launch no more workgroups than twice the compute units. */
 PRS_API int prs_bruteforce_match_batch(prs_context* ctx,
                                        const prs_bruteforce_params* params,
                                        const prs_bruteforce_batch* batch);
@@ -756,6 +764,7 @@ typedef struct {
  * Call-level errors (return value, nothing launched, every map untouched): PRS_ERR_NULL (a required pointer unset),
  * PRS_ERR_UNSUPPORTED (unknown merger / estimator or a combination no merger of the reference has, a bin narrower than one
  * pixel, or a bin table + scene bitmap + pose cache beyond the 160 KiB of LDS), PRS_ERR_HIP. */
+/* Launch size: a launch beyond 2^32 - 1 work-items is PRS_ERR_UNSUPPORTED with nothing enqueued or written (prs_launch_fits): a workgroup of 256 threads a map, batch <= 2^24 - 1. */
 PRS_API int prs_merge_batch_run(prs_context* ctx, const prs_merger_params* params, const prs_merge_batch* batch);
 
 /* ---- host, one local map: stateful handle mirroring the reference's merger object ---------------------------------
@@ -883,6 +892,8 @@ typedef struct {
   int32_t* status;        /* out [batch] */
 } prs_extract_batch;
 
+/* Launch size: a launch beyond 2^32 - 1 work-items is PRS_ERR_UNSUPPORTED with nothing enqueued or written (prs_launch_fits): the ordering launch has a workgroup of 1024 threads an image, batch <= 2^22 - 1, and the descriptor launch
+ * batch (rounded up to 8) * ceil(stride / 96) workgroups of 256. */
 PRS_API int prs_extract_features_batch(prs_context* ctx, const prs_extractor_params* params, const prs_extract_batch* batch);
 
 /* The order in which the reference's selection leaves ONE region's keypoints (PRS_SELECT_LIBSTDCXX): the permutation GNU
@@ -967,6 +978,8 @@ typedef struct {
 } prs_selective_extract_batch;
 
 /* device pointers; enqueues on the context's stream (graph-capturable, like prs_extract_features_batch) */
+/* Launch size: a launch beyond 2^32 - 1 work-items is PRS_ERR_UNSUPPORTED with nothing enqueued or written (prs_launch_fits): the selection launch has a workgroup of 512 threads an image and side, batch <= 2^23 - 1, and the descriptor
+ * launch batch (rounded up to 8) * ceil(stride / 96) workgroups of 256. */
 PRS_API int prs_extract_features_selective_batch(prs_context* ctx, const prs_selective_extractor_params* params,
                                                  const prs_selective_extract_batch* batch);
 
@@ -1136,6 +1149,7 @@ typedef struct {
 
 /* device pointers, asynchronous on the context's stream: one kernel launch, no allocation and no synchronisation (graph-capturable).
  * Replaces MultiAligner3DQR::compute with AlignerSliceProcessor3D (registration/aligner_slice_processor_3d.hpp:7-22) for B pairs. */
+/* Launch size: a launch beyond 2^32 - 1 work-items is PRS_ERR_UNSUPPORTED with nothing enqueued or written (prs_launch_fits): a wave a pair, four pairs a workgroup of 256 threads: ceil(batch / 4) <= 2^24 - 1. */
 PRS_API int prs_point_align_batch(prs_context* ctx, const prs_point_align_params* params, const prs_point_align_pairs* batch);
 
 /* host pointers, one pair: what an adapter's compute() binds (AlignerSliceProcessor3D setFixed / setMoving / setCorrespondences,
@@ -1238,6 +1252,8 @@ PRS_API int prs_place_query(prs_place_db* db, const prs_place_params* params, in
                             int32_t n, int32_t* candidates, int32_t* n_candidates, prs_corr* corr, int32_t corr_stride, int32_t* n_corr,
                             uint32_t* match_counts);
 /* device pointers, asynchronous: after prs_place_query_batch, fill the pair slots of a loop-closure batch (one kernel launch) */
+/* Launch size: a launch beyond 2^32 - 1 work-items is PRS_ERR_UNSUPPORTED with nothing enqueued or written (prs_launch_fits): a wave a (query, candidate) slot, four slots a workgroup of 256 threads: ceil(batch * max_candidates / 4)
+ * <= 2^24 - 1.  prs_place_query_batch keeps its stricter 65535 queries. */
 PRS_API int prs_place_gather_pairs(prs_place_db* db, const prs_place_params* params, const prs_place_queries* queries,
                                    const prs_place_pairs* pairs);
 
@@ -1429,6 +1445,7 @@ PRS_API uint64_t prs_pose_graph_workspace_bytes(int32_t batch, int32_t node_stri
 /* sizeof prs_pose_graph_params, _result, prs_pose_graphs, prs_pose_graph_closures as the library was compiled (bindings check) */
 PRS_API void prs_pose_graph_struct_sizes(uint64_t* sizes4);
 /* device pointers, asynchronous on the context's stream: one kernel launch, no allocation and no synchronisation (graph-capturable) */
+/* Launch size: a launch beyond 2^32 - 1 work-items is PRS_ERR_UNSUPPORTED with nothing enqueued or written (prs_launch_fits): a wave a graph, batch <= 2^26 - 1; prs_pose_graph_append_closures and prs_pose_graph_optimize_lm_batch alike. */
 PRS_API int prs_pose_graph_optimize_batch(prs_context* ctx, const prs_pose_graph_params* params, const prs_pose_graphs* graphs);
 /* device pointers, asynchronous, one kernel launch: appends the accepted closures to the graphs' edge lists, per graph in ascending
  * slot order (a prefix count, not arrival order).  A graph whose edge_stride would overflow gets PRS_ERR_CAPACITY and nothing.
@@ -1621,6 +1638,7 @@ typedef struct {
 } prs_closure_merge_batch;
 
 /* device pointers, asynchronous on the context's stream: one kernel launch, no allocation and no synchronisation (graph-capturable) */
+/* Launch size: a launch beyond 2^32 - 1 work-items is PRS_ERR_UNSUPPORTED with nothing enqueued or written (prs_launch_fits): a workgroup of 256 threads a map, batch <= 2^24 - 1. */
 PRS_API int prs_closure_merge_batch_run(prs_context* ctx, const prs_closure_merger_params* params, const prs_closure_merge_batch* batch);
 /* sizeof prs_closure_merger_params, prs_closure_merge_batch as the library was compiled (bindings check) */
 PRS_API void prs_closure_merge_struct_sizes(uint64_t* sizes2);
@@ -1756,6 +1774,8 @@ typedef struct {
 } prs_session_batch;
 
 /* device pointers, asynchronous on the context's stream: one kernel launch each */
+/* Launch size: a launch beyond 2^32 - 1 work-items is PRS_ERR_UNSUPPORTED with nothing enqueued or written (prs_launch_fits): a workgroup of 256 threads a sequence, batch <= 2^24 - 1; prs_session_step_archive_batch and
+ * prs_session_reenter_batch alike. */
 PRS_API int prs_session_step_batch(prs_context* ctx, const prs_session_params* params, const prs_session_batch* batch);
 /* out [batch][frame_stride][16] */
 PRS_API int prs_session_unroll_batch(prs_context* ctx, const prs_session_batch* batch, float* out);
@@ -1945,7 +1965,10 @@ PRS_API void prs_map_archive_struct_sizes(uint64_t* sizes3);
  * n_opt and bounds of the output are optional); PRS_ERR_RANGE (batch, capacity or node_stride differ between the three structs or
  * are < 1, slot_stride < 1, out_stride < 0, or out_stride < 1 with xyz set); PRS_ERR_UNSUPPORTED (xyz, desc, coords, a state that is
  * written or the workspace not 16-byte aligned, graph_X not 8-byte aligned, another array not 4-byte aligned; batch * (slot_stride +
- * 1) * ceil(capacity / 256) beyond 2^24 - 1 workgroups (the 2^32 - 1 work-items of one launch: prs_launch_fits) or (slot_stride + 1) * capacity beyond 2^31 - 1 rows).
+ * 1) * ceil(capacity / 256) beyond 2^24 - 1 workgroups, or batch workgroups of the scan's min(1024, node_stride rounded up to 64)
+ * threads or of the bounds launch's min(1024, (slot_stride + 1) * ceil(capacity / 256) rounded up to 64) beyond the 2^32 - 1
+ * work-items of one launch -- batch <= 2^22 - 1 where either has 1024 threads: prs_launch_fits --, or (slot_stride + 1) * capacity
+ * beyond 2^31 - 1 rows).
  * A stable stream compaction spread over (sequence, map, chunk of 256 rows), so that one sequence of hundreds of maps fills the
  * device: count (a workgroup per chunk), scan (a workgroup per sequence: validation, node order, chunk bases), scatter (a workgroup
  * per chunk: ballots, wave totals in LDS, the scanned base) and, with bounds, a reduction per sequence.  Up to four plain launches
@@ -2238,6 +2261,7 @@ typedef struct {
 } prs_trajectory_batch;
 
 /* asynchronous on the context's stream: one kernel launch */
+/* Launch size: a launch beyond 2^32 - 1 work-items is PRS_ERR_UNSUPPORTED with nothing enqueued or written (prs_launch_fits): a workgroup of 512 threads a sequence, batch <= 2^23 - 1. */
 PRS_API int prs_trajectory_eval_batch(prs_context* ctx, const prs_trajectory_params* params, const prs_trajectory_batch* batch);
 /* sizeof prs_trajectory_params, prs_trajectory_result, prs_trajectory_batch as the library was compiled (bindings check) */
 PRS_API void prs_trajectory_struct_sizes(uint64_t* sizes3);

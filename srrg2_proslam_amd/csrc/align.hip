@@ -2813,6 +2813,7 @@ struct SplitJob {
   AlignArgs g, gs;                      // Gauss-Newton / search kernel arguments
   void (*search)(AlignArgs) = nullptr;  // kernel instantiations of this batch
   void (*gn)(AlignArgs)     = nullptr;
+  Grid grid_search, grid_gn;  // the plan's
   size_t lds_search = 0, lds_gn = 0;
   int total = 0, limit = 0;  // rounds launched so far / upper bound
   int enqueued = 0;          // rounds align_batch_launch enqueued (what a captured graph replays)
@@ -2852,6 +2853,7 @@ struct AlignPlan : Plan {  // launches: the fused kernel alone, or the search ke
 
 static AlignPlan align_plan(const prs_pcf_params& finder, const prs_aligner_params& aligner, const prs_align_batch& batch, int mode, const DispatchEnv& env) {
   AlignPlan p;
+  p.too_large = "prs_align_batch_run: more work-items than one launch holds";
   if (mode < PRS_MODE_ALIGN || mode > PRS_MODE_LINEARIZE) {
     p.refuse(PRS_ERR_UNSUPPORTED, "prs_align_batch_run: unknown mode");
     return p;
@@ -3052,16 +3054,10 @@ int align_batch_launch(prs_context* ctx, const prs_pcf_params* finder, const prs
   hipError_t e;
   if (!plan.split) {
     const Plan::Launch& l = plan.launch[0];
-    auto kernel = kAlignVariants[l.kernel].fn;
-    e           = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int) l.lds);
-    if (e != hipSuccess) {
-      return ctx_fail_hip(ctx, e, "prs_align_batch_run attribute");
-    }
-    hipLaunchKernelGGL(kernel, dim3(l.grid_x), dim3(l.block), l.lds, stream, g);
+    e = launch_planned(kAlignVariants[l.kernel].fn, l.grid, l.lds, stream, g, true);
     if (ctx->align_job) {
       static_cast<SplitJob*>(ctx->align_job)->last = false;
     }
-    e = hipGetLastError();
     if (e != hipSuccess) {
       return ctx_fail_hip(ctx, e, "prs_align_batch_run launch");
     }
@@ -3071,6 +3067,10 @@ int align_batch_launch(prs_context* ctx, const prs_pcf_params* finder, const prs
     return PRS_OK;
   }
   const Plan::Launch &ls = plan.launch[0], &lg = plan.launch[1];  // search, Gauss-Newton
+  const Grid init_grid = Grid::checked(((int64_t) batch->batch + 255) / 256, 1, 1, 256);  // (fits whenever the plan's two do)
+  if (!init_grid) {
+    return ctx_fail(ctx, PRS_ERR_UNSUPPORTED, plan.too_large);
+  }
   SplitJob* job = static_cast<SplitJob*>(ctx->align_job);
   if (!job) {
     job                 = new SplitJob();
@@ -3113,11 +3113,11 @@ int align_batch_launch(prs_context* ctx, const prs_pcf_params* finder, const prs
       gs.qcache = nullptr;
     }
   }
-  e = hipFuncSetAttribute(reinterpret_cast<const void*>(kAlignVariants[ls.kernel].fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int) ls.lds);
+  e = allow_lds(kAlignVariants[ls.kernel].fn, ls.lds, true);
   if (e != hipSuccess) {
     return ctx_fail_hip(ctx, e, "prs_align_batch_run attribute");
   }
-  hipLaunchKernelGGL(split_init_kernel, dim3((batch->batch + 255) / 256), dim3(256), 0, stream, g.ctl, batch->result, g.pending, batch->batch);
+  launch(split_init_kernel, init_grid, 0, stream, g.ctl, batch->result, g.pending, batch->batch);
   // The job lives in the context until align_batch_finish: the rounds are plain launches on the context's stream (no host
   // synchronisation here, the sequence can be captured in a HIP graph once the scratch buffers exist).
   job->active      = true;
@@ -3128,6 +3128,8 @@ int align_batch_launch(prs_context* ctx, const prs_pcf_params* finder, const prs
   job->search      = kAlignVariants[ls.kernel].fn;
   job->gn          = kAlignVariants[lg.kernel].fn;
   job->last        = true;
+  job->grid_search = ls.grid;
+  job->grid_gn     = lg.grid;
   job->lds_search  = ls.lds;
   job->lds_gn      = lg.lds;
   job->total       = 0;
@@ -3155,21 +3157,20 @@ static int split_rounds(prs_context* ctx, SplitJob* job, int rounds) {
   for (int r = 0; r < rounds; ++r) {
     (void) hipMemsetAsync(job->g.pending, 0, sizeof(int), stream);
     tick();
-    hipLaunchKernelGGL(job->search, dim3(batch), dim3(kSearchThreads), job->lds_search, stream, job->gs);
+    launch(job->search, job->grid_search, job->lds_search, stream, job->gs);
     tick();
     if (job->stamps) {
       ctx_report_stamps(ctx, batch, 10, "search launch (split): - | query-cache pass | - | - || lattice build | projection+search (behind a cache pass: the scan of its queue) | staging (keys, fixed rows -> LDS) | filter | commit");
     }
-    hipLaunchKernelGGL(job->gn, dim3(batch), dim3(kGnThreads), job->lds_gn, stream, job->g);
+    launch(job->gn, job->grid_gn, job->lds_gn, stream, job->g);
     tick();
     ++job->total;
   }
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
+  const int rc = Launches(ctx, "prs_align_batch_run split", stream).finish();
+  if (rc != PRS_OK) {
     job->active = false;
-    return ctx_fail_hip(ctx, e, "prs_align_batch_run split launch");
   }
-  return PRS_OK;
+  return rc;
 }
 
 // blocks until the enqueued batch is complete: one 4-byte readback per group of rounds; more rounds while frames are pending
@@ -3296,21 +3297,12 @@ __global__ __launch_bounds__(256) void recip_selftest_kernel(unsigned long long*
 }
 
 int recip_selftest_launch(prs_context* ctx, unsigned long long* d_counts) {
-  hipLaunchKernelGGL(recip_selftest_kernel, dim3(256 * 32), dim3(256), 0, ctx_stream(ctx), d_counts);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    return ctx_fail_hip(ctx, e, "prs_selftest_reciprocal launch");
-  }
-  return PRS_OK;
+  return Launches(ctx, "prs_selftest_reciprocal", ctx_stream(ctx)).one(256 * 32, 256, recip_selftest_kernel, 0, d_counts);
 }
 
 int gn_step_launch(prs_context* ctx, const float* dH, const float* db, float damping, int damping_form, float* dX, int* dok) {
-  hipLaunchKernelGGL(gn_step_kernel, dim3(1), dim3(1), 0, ctx_stream(ctx), dH, db, damping, damping_form == PRS_DAMPING_IDENTITY ? 1 : 0, dX, dok);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    return ctx_fail_hip(ctx, e, "prs_gn_step launch");
-  }
-  return PRS_OK;
+  return Launches(ctx, "prs_gn_step", ctx_stream(ctx)).one(1, 1, gn_step_kernel,
+                                                           0, dH, db, damping, damping_form == PRS_DAMPING_IDENTITY ? 1 : 0, dX, dok);
 }
 
 }  // namespace prs

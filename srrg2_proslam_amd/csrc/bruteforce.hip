@@ -1102,6 +1102,7 @@ struct BfPlan : Plan {
 
 static BfPlan bruteforce_plan(const prs_bruteforce_params& params, const prs_bruteforce_batch& batch, const DispatchEnv& env) {
   BfPlan p;
+  p.too_large = "prs_bruteforce_match: more work-items than one launch holds";
   BfArgs& a = p.a;
   if (batch.batch <= 0) {
     return p;
@@ -1249,11 +1250,7 @@ int bruteforce_batch_launch(prs_context* ctx, const prs_bruteforce_params* param
   }
   for (int i = 0; i < plan.n_launches && e == hipSuccess; ++i) {
     const Plan::Launch& l = plan.launch[i];
-    e = allow_lds(kBfVariants[l.kernel].fn, l.lds);
-    if (e == hipSuccess) {
-      hipLaunchKernelGGL(kBfVariants[l.kernel].fn, dim3(l.grid_x, l.grid_y), dim3(l.block), l.lds, stream, a);
-      e = hipGetLastError();
-    }
+    e = launch_planned(kBfVariants[l.kernel].fn, l.grid, l.lds, stream, a);
   }
   if (e != hipSuccess) {
     return ctx_fail_hip(ctx, e, "prs_bruteforce_match launch");

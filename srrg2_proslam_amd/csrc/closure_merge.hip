@@ -475,12 +475,7 @@ int closure_merge_launch(prs_context* ctx, const prs_closure_merger_params* para
   a.off_prefix = off; off = cm_align16(off + (uint32_t) a.n_words * 4);
   a.off_seen   = off; off = cm_align16(off + ((uint32_t) b.capacity + 31) / 32 * 4);
   a.off_sh     = off; off = cm_align16(off + (uint32_t) sizeof(ClosureShared));
-  hipLaunchKernelGGL(closure_merge_kernel, dim3(b.batch), dim3(kClosureThreads), off, ctx_stream(ctx), a);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    return ctx_fail_hip(ctx, e, "prs_closure_merge_batch_run launch");
-  }
-  return PRS_OK;
+  return Launches(ctx, "prs_closure_merge_batch_run", ctx_stream(ctx)).one(b.batch, kClosureThreads, closure_merge_kernel, off, a);
 }
 
 }  // namespace prs

@@ -25,7 +25,6 @@
 
 #include <string>
 
-#include "prs_compact.h"
 #include "prs_device.h"
 #include "prs_host.h"
 
@@ -388,36 +387,44 @@ Layout layout_of(const int64_t batch, const int64_t frames, const int64_t rows, 
 
 }  // namespace
 
-// the census and the finish launch for the stages that share them (sgm_stereo.hip): the caller has checked the batch; false when the
-// launch would pass 2^32 - 1 work-items (grid_fits), and then nothing is launched
-bool dense_census_enqueue(hipStream_t st, const prs_dense_stereo_batch& o, uint64_t* census_l, uint64_t* census_r) {
-  DenseStereoArgs a = {};
-  a.o        = o;
-  a.ctiles_x = (o.cols + PRS_WAVE - 1) / PRS_WAVE;
-  a.ctiles_y = (o.rows + kCensusRows - 1) / kCensusRows;
-  a.census_l = census_l;
-  a.census_r = census_r;
-  const int64_t blocks = (int64_t) o.batch * o.frames * 2 * a.ctiles_x * a.ctiles_y;
-  if (!grid_fits(blocks, kThreads)) {
-    return false;
-  }
-  hipLaunchKernelGGL(dense_census_kernel, dim3((unsigned) blocks), dim3(kThreads), 0, st, a);
-  return true;
+// the census and the finish launch for the stages that share them (sgm_stereo.hip): the caller has checked the batch, declared
+// *_blocks workgroups of kDenseThreads among its launches and checked those
+static_assert(kThreads == kDenseThreads, "the shared launches' workgroup");
+static int census_tiles_x(const prs_dense_stereo_batch& o) {
+  return (o.cols + PRS_WAVE - 1) / PRS_WAVE;
+}
+static int census_tiles_y(const prs_dense_stereo_batch& o) {
+  return (o.rows + kCensusRows - 1) / kCensusRows;
+}
+static int finish_blocks_per_image(const prs_dense_stereo_batch& o) {
+  return (o.rows + kFinishRows - 1) / kFinishRows;
+}
+int64_t dense_census_blocks(const prs_dense_stereo_batch& o) {  // (each factor is below 2^31 and batch * frames * rows * cols is)
+  return (int64_t) o.batch * o.frames * 2 * census_tiles_x(o) * census_tiles_y(o);
+}
+int64_t dense_finish_blocks(const prs_dense_stereo_batch& o) {
+  return (int64_t) o.batch * o.frames * finish_blocks_per_image(o);
 }
 
-bool dense_finish_enqueue(hipStream_t st, const prs_dense_stereo_params& p, const prs_dense_stereo_batch& o, uint2* rec_l, int16_t* win_r) {
+void dense_census_enqueue(const Launches& on, const Grid& grid, const prs_dense_stereo_batch& o, uint64_t* census_l, uint64_t* census_r) {
+  DenseStereoArgs a = {};
+  a.o        = o;
+  a.ctiles_x = census_tiles_x(o);
+  a.ctiles_y = census_tiles_y(o);
+  a.census_l = census_l;
+  a.census_r = census_r;
+  on.launch(dense_census_kernel, grid, 0, a);
+}
+
+void dense_finish_enqueue(const Launches& on, const Grid& grid, const prs_dense_stereo_params& p, const prs_dense_stereo_batch& o, uint2* rec_l,
+                          int16_t* win_r) {
   DenseStereoArgs a = {};
   a.p       = p;
   a.o       = o;
-  a.fblocks = (o.rows + kFinishRows - 1) / kFinishRows;
+  a.fblocks = finish_blocks_per_image(o);
   a.rec_l   = rec_l;
   a.win_r   = win_r;
-  const int64_t blocks = (int64_t) o.batch * o.frames * a.fblocks;
-  if (!grid_fits(blocks, kThreads)) {
-    return false;
-  }
-  hipLaunchKernelGGL(dense_finish_kernel, dim3((unsigned) blocks), dim3(kThreads), 0, st, a);
-  return true;
+  on.launch(dense_finish_kernel, grid, 0, a);
 }
 
 int dense_stereo_launch(prs_context* ctx, const prs_dense_stereo_params* params, const prs_dense_stereo_batch* batch) {
@@ -455,15 +462,13 @@ int dense_stereo_launch(prs_context* ctx, const prs_dense_stereo_params* params,
   a.tile     = PRS_WAVE - 2 * p.aggregation_radius;
   a.tiles    = (o.cols + a.tile - 1) / a.tile;
   a.bands    = (o.rows + kBandRows - 1) / kBandRows;
-  a.ctiles_x = (o.cols + PRS_WAVE - 1) / PRS_WAVE;
-  a.ctiles_y = (o.rows + kCensusRows - 1) / kCensusRows;
-  a.fblocks  = (o.rows + kFinishRows - 1) / kFinishRows;
-  const int64_t images = (int64_t) o.batch * o.frames;
-  const int64_t census_blocks = images * 2 * a.ctiles_x * a.ctiles_y, match_blocks = images * a.bands * a.tiles,
-                finish_blocks = images * a.fblocks;  // each factor is below 2^31 and images * rows * cols is
-  if (!grid_fits(census_blocks, kThreads) || !grid_fits(match_blocks, kThreads) || !grid_fits(finish_blocks, kThreads)) {
-    return ctx_fail(ctx, PRS_ERR_UNSUPPORTED, (who + ": more work-items than one launch holds").c_str());
-  }
+  a.ctiles_x = census_tiles_x(o);
+  a.ctiles_y = census_tiles_y(o);
+  a.fblocks  = finish_blocks_per_image(o);
+  Launches on(ctx, who.c_str(), ctx_stream(ctx));
+  const Grid census = on.grid(dense_census_blocks(o), kThreads), match = on.grid((int64_t) o.batch * o.frames * a.bands * a.tiles, kThreads),
+             finish = on.grid(dense_finish_blocks(o), kThreads);
+  PRS_TRY(on.check());
   uint8_t* ws = static_cast<uint8_t*>(o.workspace);
   a.census_l  = reinterpret_cast<uint64_t*>(ws);
   a.census_r  = reinterpret_cast<uint64_t*>(ws + l.census);
@@ -478,18 +483,13 @@ int dense_stereo_launch(prs_context* ctx, const prs_dense_stereo_params* params,
   if (e != hipSuccess) {
     return ctx_fail_hip(ctx, e, "prs_dense_stereo_batch_run LDS request");
   }
-  hipStream_t st = ctx_stream(ctx);
-  hipLaunchKernelGGL(dense_census_kernel, dim3((unsigned) census_blocks), dim3(kThreads), 0, st, a);
-  hipLaunchKernelGGL(match_l, dim3((unsigned) match_blocks), dim3(kThreads), lds_l, st, a);
+  on.launch(dense_census_kernel, census, 0, a);
+  on.launch(match_l, match, lds_l, a);
   if (lr) {
-    hipLaunchKernelGGL(match_r, dim3((unsigned) match_blocks), dim3(kThreads), lds_r, st, a);
+    on.launch(match_r, match, lds_r, a);
   }
-  hipLaunchKernelGGL(dense_finish_kernel, dim3((unsigned) finish_blocks), dim3(kThreads), 0, st, a);
-  e = hipGetLastError();
-  if (e != hipSuccess) {
-    return ctx_fail_hip(ctx, e, "prs_dense_stereo_batch_run launch");
-  }
-  return PRS_OK;
+  on.launch(dense_finish_kernel, finish, 0, a);
+  return on.finish();
 }
 
 }  // namespace prs

@@ -272,18 +272,18 @@ Layout layout_of(const int64_t batch, const int64_t frames, const int64_t rows, 
 }
 
 template <typename E>
-void launch_pass(const DepthCloudArgs& a, const bool vec, const bool scatter, const unsigned blocks, hipStream_t st) {
+void launch_pass(const Launches& on, const Grid& grid, const DepthCloudArgs& a, const bool vec, const bool scatter) {
   if (vec) {
     if (scatter) {
-      hipLaunchKernelGGL((depth_cloud_kernel<E, true, true>), dim3(blocks), dim3(kThreads), 0, st, a);
+      on.launch(depth_cloud_kernel<E, true, true>, grid, 0, a);
     } else {
-      hipLaunchKernelGGL((depth_cloud_kernel<E, true, false>), dim3(blocks), dim3(kThreads), 0, st, a);
+      on.launch(depth_cloud_kernel<E, true, false>, grid, 0, a);
     }
   } else {
     if (scatter) {
-      hipLaunchKernelGGL((depth_cloud_kernel<E, false, true>), dim3(blocks), dim3(kThreads), 0, st, a);
+      on.launch(depth_cloud_kernel<E, false, true>, grid, 0, a);
     } else {
-      hipLaunchKernelGGL((depth_cloud_kernel<E, false, false>), dim3(blocks), dim3(kThreads), 0, st, a);
+      on.launch(depth_cloud_kernel<E, false, false>, grid, 0, a);
     }
   }
 }
@@ -324,10 +324,10 @@ int depth_cloud_launch(prs_context* ctx, const prs_depth_cloud_params* params, c
     return ctx_fail(ctx, PRS_ERR_UNSUPPORTED, (who + ": rows * cols or frames * sampled pixels beyond 2^31 - 1").c_str());
   }
   const int64_t C = (int64_t) o.frames * l.chunks_per_frame, blocks = (int64_t) o.batch * C;  // C <= frames * samples < 2^31
-  const unsigned wide = (unsigned) std::min<long long>(kWideThreads, ((C + kCompactBatch - 1) / kCompactBatch + PRS_WAVE - 1) / PRS_WAVE * PRS_WAVE);
-  if (!grid_fits(blocks, kThreads) || !grid_fits(o.batch, (int) wide)) {  // the two passes and the scan
-    return ctx_fail(ctx, PRS_ERR_UNSUPPORTED, (who + ": batch * frames * chunks of 1024 sampled pixels beyond the work-items of one launch").c_str());
-  }
+  const int wide = (int) std::min<long long>(kWideThreads, ((C + kCompactBatch - 1) / kCompactBatch + PRS_WAVE - 1) / PRS_WAVE * PRS_WAVE);
+  Launches on(ctx, who.c_str(), ctx_stream(ctx));
+  const Grid pass = on.grid(blocks, kThreads), scan = on.grid(o.batch, wide);  // the two passes: batch * frames * chunks of 1024 sampled pixels
+  PRS_TRY(on.check());
   DepthCloudArgs a = {};
   a.p = p;
   a.o = o;
@@ -338,26 +338,21 @@ int depth_cloud_launch(prs_context* ctx, const prs_depth_cloud_params* params, c
   // a lane's four samples in one load: they lie in one row (cols a multiple of 4) at an address that is a multiple of the load
   const uintptr_t load = (uintptr_t) elem * kPerLane;
   const bool vec       = p.step == 1 && o.cols % kPerLane == 0 && (uintptr_t) o.pitch % load == 0 && aligned_to(o.depth, load);
-  hipStream_t st       = ctx_stream(ctx);
   const bool u16       = p.depth_type == PRS_DEPTH_U16;
   if (u16) {
-    launch_pass<uint16_t>(a, vec, false, (unsigned) blocks, st);
+    launch_pass<uint16_t>(on, pass, a, vec, false);
   } else {
-    launch_pass<float>(a, vec, false, (unsigned) blocks, st);
+    launch_pass<float>(on, pass, a, vec, false);
   }
-  hipLaunchKernelGGL(depth_cloud_scan_kernel, dim3((unsigned) o.batch), dim3(wide), 0, st, a);
+  on.launch(depth_cloud_scan_kernel, scan, 0, a);
   if (a.write_out) {
     if (u16) {
-      launch_pass<uint16_t>(a, vec, true, (unsigned) blocks, st);
+      launch_pass<uint16_t>(on, pass, a, vec, true);
     } else {
-      launch_pass<float>(a, vec, true, (unsigned) blocks, st);
+      launch_pass<float>(on, pass, a, vec, true);
     }
   }
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    return ctx_fail_hip(ctx, e, "prs_depth_cloud_batch_run launch");
-  }
-  return PRS_OK;
+  return on.finish();
 }
 
 }  // namespace prs

@@ -15,7 +15,6 @@
 
 #include <string>
 
-#include "prs_compact.h"
 #include "prs_depth.h"
 #include "prs_device.h"
 #include "prs_host.h"
@@ -265,11 +264,6 @@ uint64_t records_of(const int64_t batch, const int64_t frames, const int64_t win
   return (uint64_t) (batch * frames * (2 * window));
 }
 
-inline bool overlap(const void* p, const uint64_t p_bytes, const void* q, const uint64_t q_bytes) {
-  const uintptr_t p0 = reinterpret_cast<uintptr_t>(p), q0 = reinterpret_cast<uintptr_t>(q);
-  return p0 < q0 + q_bytes && q0 < p0 + p_bytes;
-}
-
 }  // namespace
 
 int depth_consistency_launch(prs_context* ctx, const prs_depth_consistency_params* params, const prs_depth_consistency_batch* batch) {
@@ -321,22 +315,13 @@ int depth_consistency_launch(prs_context* ctx, const prs_depth_consistency_param
   a.tiles_x = (o.cols + kTileW - 1) / kTileW;
   a.tiles_y = (o.rows + kTileH * kGroups - 1) / (kTileH * kGroups);
   a.rec     = static_cast<SlotRecord*>(o.workspace);
-  const int64_t blocks = images * a.tiles_x * a.tiles_y;  // images * tiles_y <= images * rows < 2^31, tiles_x < 2^19
-  if (!grid_fits(o.batch, kThreads) || !grid_fits(blocks, kThreads)) {  // prepare and filter
-    return ctx_fail(ctx, PRS_ERR_UNSUPPORTED, (who + ": more work-items than one launch holds").c_str());
-  }
-  hipStream_t st = ctx_stream(ctx);
-  hipLaunchKernelGGL(depth_consistency_prepare_kernel, dim3((unsigned) o.batch), dim3(kThreads), 0, st, a);
-  if (p.depth_type == PRS_DEPTH_U16) {
-    hipLaunchKernelGGL(depth_consistency_filter_kernel<uint16_t>, dim3((unsigned) blocks), dim3(kThreads), 0, st, a);
-  } else {
-    hipLaunchKernelGGL(depth_consistency_filter_kernel<float>, dim3((unsigned) blocks), dim3(kThreads), 0, st, a);
-  }
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    return ctx_fail_hip(ctx, e, "prs_depth_consistency_batch_run launch");
-  }
-  return PRS_OK;
+  Launches on(ctx, who.c_str(), ctx_stream(ctx));
+  const Grid prepare = on.grid(o.batch, kThreads);
+  const Grid filter  = on.grid(images * a.tiles_x * a.tiles_y, kThreads);  // images * tiles_y <= images * rows < 2^31, tiles_x < 2^19
+  PRS_TRY(on.check());
+  on.launch(depth_consistency_prepare_kernel, prepare, 0, a);
+  on.launch(p.depth_type == PRS_DEPTH_U16 ? depth_consistency_filter_kernel<uint16_t> : depth_consistency_filter_kernel<float>, filter, 0, a);
+  return on.finish();
 }
 
 }  // namespace prs

@@ -1422,18 +1422,27 @@ __global__ __launch_bounds__(kSelThreads) void selection_order_kernel(const uint
   }
 }
 
+// the grids both extractors share: blur tiles of kFastThreads, describe chunks of kDescThreads (eight images' chunks at a time)
+DescribeGrids describe_selected_grids(Launches& on, const prs_extract_batch& batch) {
+  DescribeGrids g;
+  const int per_block = (kDescThreads / 64) * kDescPerWave;
+  g.chunks   = (int) (((int64_t) batch.stride + per_block - 1) / per_block);
+  g.tiles    = on.grid(((int64_t) batch.cols + kTileW - 1) / kTileW, ((int64_t) batch.rows + kTileH - 1) / kTileH, batch.batch, kFastThreads);
+  g.describe = on.grid(((int64_t) batch.batch + 7) / 8 * 8 * g.chunks, kDescThreads);
+  return g;
+}
+
 int selection_order_launch(prs_context* ctx, const uint8_t* response_dev, int n, int32_t* order_dev, int32_t* status_dev) {
   const size_t lds = (size_t) (n > 0 ? n : 1) * sizeof(uint32_t);
-  hipError_t e     = hipFuncSetAttribute(reinterpret_cast<const void*>(selection_order_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds);
+  Launches on(ctx, "prs_selection_order", ctx->stream);
+  const Grid grid = on.grid(1, kSelThreads);
+  PRS_TRY(on.check());
+  const hipError_t e = allow_lds(selection_order_kernel, lds, true);
   if (e != hipSuccess) {
     return ctx_fail_hip(ctx, e, "prs_selection_order: LDS for the keys");
   }
-  hipLaunchKernelGGL(selection_order_kernel, dim3(1), dim3(kSelThreads), lds, ctx->stream, response_dev, n, order_dev, status_dev);
-  e = hipGetLastError();
-  if (e != hipSuccess) {
-    return ctx_fail_hip(ctx, e, "prs_selection_order launch");
-  }
-  return PRS_OK;
+  on.launch(selection_order_kernel, grid, lds, response_dev, n, order_dev, status_dev);
+  return on.finish();
 }
 
 int extract_features_launch(prs_context* ctx, const prs_extractor_params* params, const prs_extract_batch* batch) {
@@ -1467,6 +1476,11 @@ int extract_features_launch(prs_context* ctx, const prs_extractor_params* params
     }
     max_raw = pow2;
   }
+  hipStream_t stream = ctx_stream(ctx);
+  Launches on(ctx, "prs_extract_features_batch", stream);
+  const DescribeGrids dg = describe_selected_grids(on, *batch);
+  const Grid per_image_nms = on.grid(batch->batch, kNmsThreads), per_image_sel = on.grid(batch->batch, kSelThreads);
+  PRS_TRY(on.check());
   FeatureArgs a;
   a.p = *params;
   a.b = *batch;
@@ -1488,15 +1502,14 @@ int extract_features_launch(prs_context* ctx, const prs_extractor_params* params
   a.cols_per   = (float) batch->cols / (float) params->number_of_detectors_horizontal;
   a.regions    = regions;
   a.target_per = (int) ((float) params->target_number_of_keypoints / (float) regions);  // :72-76
-  hipStream_t stream = ctx_stream(ctx);
   const size_t lds_keys = (size_t) max_raw * sizeof(uint32_t);
   hipError_t e = hipMemsetAsync(a.n_raw, 0, (size_t) batch->batch * sizeof(int32_t), stream);
   if (e != hipSuccess) {
     return ctx_fail_hip(ctx, e, "prs_extract_features_batch: detection counters");
   }
-  e = hipFuncSetAttribute(reinterpret_cast<const void*>(raster_order_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds_keys);
+  e = allow_lds(raster_order_kernel, lds_keys, true);
   if (e == hipSuccess) {
-    e = hipFuncSetAttribute(reinterpret_cast<const void*>(select_describe_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds_keys);
+    e = allow_lds(select_describe_kernel, lds_keys, true);
   }
   if (e != hipSuccess) {
     return ctx_fail_hip(ctx, e, "prs_extract_features_batch: LDS for the selection sort");
@@ -1505,18 +1518,11 @@ int extract_features_launch(prs_context* ctx, const prs_extractor_params* params
   while (((npix - 1) >> bucket_shift) >= (size_t) kRasterBuckets) {
     ++bucket_shift;
   }
-  const int per_wave  = kDescPerWave;
-  const int per_block = (kDescThreads / 64) * per_wave;
-  const int chunks    = (batch->stride + per_block - 1) / per_block;
-  const dim3 tiles((batch->cols + kTileW - 1) / kTileW, (batch->rows + kTileH - 1) / kTileH, batch->batch);
-  hipLaunchKernelGGL(fast_blur_kernel, tiles, dim3(kFastThreads), 0, stream, a);
-  hipLaunchKernelGGL(raster_order_kernel, dim3(batch->batch), dim3(kNmsThreads), lds_keys, stream, a, bucket_shift);
-  hipLaunchKernelGGL(select_describe_kernel, dim3(batch->batch), dim3(kSelThreads), lds_keys, stream, a);
-  hipLaunchKernelGGL(describe_kernel, dim3((unsigned) (((batch->batch + 7) / 8) * 8 * chunks), 1, 1), dim3(kDescThreads), 0, stream, a, chunks, per_wave);
-  e = hipGetLastError();
-  if (e != hipSuccess) {
-    return ctx_fail_hip(ctx, e, "prs_extract_features_batch launch");
-  }
+  on.launch(fast_blur_kernel, dg.tiles, 0, a);
+  on.launch(raster_order_kernel, per_image_nms, lds_keys, a, bucket_shift);
+  on.launch(select_describe_kernel, per_image_sel, lds_keys, a);
+  on.launch(describe_kernel, dg.describe, 0, a, dg.chunks, kDescPerWave);
+  PRS_TRY(on.finish());
   if (a.stamps) {
     ctx_report_stamps(ctx, batch->batch, 5, "select_describe_kernel: keys | sort | selection | tail");
     if (batch->cols > 5 * kTileW && batch->rows > 2 * kTileH) {
@@ -1528,7 +1534,7 @@ int extract_features_launch(prs_context* ctx, const prs_extractor_params* params
 
 // descriptors of keypoints selected elsewhere (selective.hip): kept [batch][stride] pixel indices, batch->n_features already
 // written on the device (0 for an image that failed).  The blur and describe kernels of the FAST extractor, unchanged.
-int describe_selected_launch(prs_context* ctx, const prs_extract_batch* batch, uint32_t* kept) {
+int describe_selected_launch(prs_context* ctx, const Launches& on, const DescribeGrids& dg, const prs_extract_batch* batch, uint32_t* kept) {
   FeatureArgs a{};
   a.b           = *batch;
   a.kept        = kept;
@@ -1539,17 +1545,9 @@ int describe_selected_launch(prs_context* ctx, const prs_extract_batch* batch, u
     return ctx_fail(ctx, PRS_ERR_HIP, "describe_selected_launch: scratch allocation failed");
   }
   fill_window_offsets(kOrbPattern, &a);
-  hipStream_t stream  = ctx_stream(ctx);
-  const int per_block = (kDescThreads / 64) * kDescPerWave;
-  const int chunks    = (batch->stride + per_block - 1) / per_block;
-  const dim3 tiles((batch->cols + kTileW - 1) / kTileW, (batch->rows + kTileH - 1) / kTileH, batch->batch);
-  hipLaunchKernelGGL(blur_kernel, tiles, dim3(kFastThreads), 0, stream, a);
-  hipLaunchKernelGGL(describe_kernel, dim3((unsigned) (((batch->batch + 7) / 8) * 8 * chunks), 1, 1), dim3(kDescThreads), 0, stream, a, chunks, kDescPerWave);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    return ctx_fail_hip(ctx, e, "describe_selected_launch");
-  }
-  return PRS_OK;
+  on.launch(blur_kernel, dg.tiles, 0, a);
+  on.launch(describe_kernel, dg.describe, 0, a, dg.chunks, kDescPerWave);
+  return on.finish();
 }
 
 }  // namespace prs

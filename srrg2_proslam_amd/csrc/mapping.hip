@@ -1428,6 +1428,7 @@ struct MergePlan : Plan {
 
 static MergePlan merge_plan(const prs_merger_params& params, const prs_merge_batch& b, const DispatchEnv& env) {
   MergePlan p;
+  p.too_large = "prs_merge_batch_run: more work-items than one launch holds";
   if (b.batch <= 0) {
     return p;
   }
@@ -1564,11 +1565,7 @@ int merge_batch_launch(prs_context* ctx, const prs_merger_params* params, const 
   }
   for (int i = 0; i < plan.n_launches && e == hipSuccess; ++i) {
     const Plan::Launch& l = plan.launch[i];
-    e = allow_lds(kMergeVariants[l.kernel].fn, l.lds);
-    if (e == hipSuccess) {
-      hipLaunchKernelGGL(kMergeVariants[l.kernel].fn, dim3(l.grid_x), dim3(l.block), l.lds, ctx_stream(ctx), a);
-      e = hipGetLastError();
-    }
+    e = launch_planned(kMergeVariants[l.kernel].fn, l.grid, l.lds, ctx_stream(ctx), a);
   }
   if (e != hipSuccess) {
     return ctx_fail_hip(ctx, e, "prs_merge_batch_run launch");
@@ -1627,12 +1624,8 @@ int motion_predict_launch(prs_context* ctx, int batch, const float* prev2, const
   if (batch <= 0) {
     return PRS_OK;
   }
-  hipLaunchKernelGGL(motion_predict_kernel, dim3((batch + 255) / 256), dim3(256), 0, ctx_stream(ctx), batch, prev2, prev1, pred);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    return ctx_fail_hip(ctx, e, "prs_motion_predict_batch launch");
-  }
-  return PRS_OK;
+  return Launches(ctx, "prs_motion_predict_batch", ctx_stream(ctx)).one(((int64_t) batch + 255) / 256, 256, motion_predict_kernel,
+                                                                        0, batch, prev2, prev1, pred);
 }
 
 int pose_compose_launch(prs_context* ctx, int batch, const float* prediction, const float* X, float* pose_out) {
@@ -1642,12 +1635,8 @@ int pose_compose_launch(prs_context* ctx, int batch, const float* prediction, co
   if (batch <= 0) {
     return PRS_OK;
   }
-  hipLaunchKernelGGL(pose_compose_kernel, dim3((batch + 255) / 256), dim3(256), 0, ctx_stream(ctx), batch, prediction, X, pose_out);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    return ctx_fail_hip(ctx, e, "prs_pose_compose_batch launch");
-  }
-  return PRS_OK;
+  return Launches(ctx, "prs_pose_compose_batch", ctx_stream(ctx)).one(((int64_t) batch + 255) / 256, 256, pose_compose_kernel,
+                                                                      0, batch, prediction, X, pose_out);
 }
 
 }  // namespace prs

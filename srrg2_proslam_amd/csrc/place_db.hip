@@ -499,10 +499,6 @@ __global__ __launch_bounds__(kPdThreads) void place_gather_kernel(const GatherAr
                            g.map_rows);
 }
 
-bool aligned(const void* ptr, size_t a) {
-  return (reinterpret_cast<uintptr_t>(ptr) & (a - 1)) == 0;
-}
-
 int lim_of(const float thr) {
   // (float) d < maximum_descriptor_distance for integer d  <=>  d < lim  (lim 257: every distance of 256 bits)
   int lim = 0;
@@ -567,27 +563,26 @@ int place_query_launch(prs_place_db* db, const prs_place_params* p, const prs_pl
   if (q->count_stride < db->maps || q->key_stride < db->rows || q->corr_stride < db->max_map_rows || q->corr_stride > kPdMaxCorrStride) {
     return ctx_fail(ctx, PRS_ERR_CAPACITY, "prs_place_query_batch: count_stride, key_stride or corr_stride below the database's size");
   }
-  if (!aligned(q->desc, 4)) {
+  if (!aligned_to(q->desc, 4)) {
     return ctx_fail(ctx, PRS_ERR_UNSUPPORTED, "prs_place_query_batch: descriptor rows must be 4-byte aligned");
   }
   const PlaceArgs a = make_args(db, p, q);
-  hipStream_t s     = ctx_stream(ctx);
-  if (db->rows > 0 || db->maps > 0) {
-    const int big = db->rows > db->maps ? db->rows : db->maps;
-    const unsigned gx = (unsigned) ((big + kPdThreads - 1) / kPdThreads < 1024 ? (big + kPdThreads - 1) / kPdThreads : 1024);
-    hipLaunchKernelGGL(place_init_kernel, dim3(gx, (unsigned) q->batch), dim3(kPdThreads), 0, s, a);
+  Launches on(ctx, "prs_place_query_batch", ctx_stream(ctx));
+  const int64_t big = db->rows > db->maps ? db->rows : db->maps, init_x = (big + kPdThreads - 1) / kPdThreads;
+  const Grid init   = big > 0 ? on.grid(init_x < 1024 ? init_x : 1024, q->batch, kPdThreads) : Grid();
+  const Grid score  = db->rows > 0 ? on.grid(((int64_t) db->rows + kPdSlice - 1) / kPdSlice,
+                                             ((int64_t) q->query_stride + kPdRowsWg - 1) / kPdRowsWg, q->batch, kPdThreads)
+                                   : Grid();
+  const Grid select = on.grid(q->batch, kPdThreads);
+  PRS_TRY(on.check());
+  if (init) {
+    on.launch(place_init_kernel, init, 0, a);
   }
-  if (db->rows > 0) {
-    const dim3 grid((unsigned) ((db->rows + kPdSlice - 1) / kPdSlice), (unsigned) ((q->query_stride + kPdRowsWg - 1) / kPdRowsWg),
-                    (unsigned) q->batch);
-    hipLaunchKernelGGL(place_score_kernel, grid, dim3(kPdThreads), 0, s, a);
+  if (score) {
+    on.launch(place_score_kernel, score, 0, a);
   }
-  hipLaunchKernelGGL(place_select_kernel, dim3((unsigned) q->batch), dim3(kPdThreads), 0, s, a);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    return ctx_fail_hip(ctx, e, "prs_place_query_batch launch");
-  }
-  return PRS_OK;
+  on.launch(place_select_kernel, select, 0, a);
+  return on.finish();
 }
 
 template <typename T>
@@ -1205,8 +1200,8 @@ int prs_place_gather_pairs(prs_place_db* db, const prs_place_params* params, con
   if (pairs->fixed_stride < queries->query_stride || pairs->moving_stride < db->max_map_rows) {
     return ctx_fail(ctx, PRS_ERR_CAPACITY, "prs_place_gather_pairs: a pair slot is smaller than the query or the largest stored map");
   }
-  if (!aligned(queries->desc, 16) || !aligned(queries->xyz, 16) || !aligned(pairs->fixed_xyz, 16) || !aligned(pairs->fixed_desc, 16) ||
-      !aligned(pairs->moving_xyz, 16) || !aligned(pairs->moving_desc, 16)) {
+  if (!aligned_to(queries->desc, 16) || !aligned_to(queries->xyz, 16) || !aligned_to(pairs->fixed_xyz, 16) || !aligned_to(pairs->fixed_desc, 16) ||
+      !aligned_to(pairs->moving_xyz, 16) || !aligned_to(pairs->moving_desc, 16)) {
     return ctx_fail(ctx, PRS_ERR_UNSUPPORTED, "prs_place_gather_pairs: rows must be 16-byte aligned");
   }
   (void) hipSetDevice(ctx->device);
@@ -1219,13 +1214,8 @@ int prs_place_gather_pairs(prs_place_db* db, const prs_place_params* params, con
   g.map_off  = db->map_off;
   g.map_rows = db->map_rows;
   g.maxc     = params->max_candidates;
-  const size_t slots = (size_t) queries->batch * (size_t) params->max_candidates;
-  hipLaunchKernelGGL(place_gather_kernel, dim3((unsigned) ((slots + 3) / 4)), dim3(kPdThreads), 0, ctx_stream(ctx), g);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    return ctx_fail_hip(ctx, e, "prs_place_gather_pairs launch");
-  }
-  return PRS_OK;
+  const int64_t slots = (int64_t) queries->batch * params->max_candidates;
+  return Launches(ctx, "prs_place_gather_pairs", ctx_stream(ctx)).one((slots + 3) / 4, kPdThreads, place_gather_kernel, 0, g);
 }
 
 int prs_place_bank_create(prs_context* ctx, int32_t batch, int32_t map_stride, int32_t row_stride, prs_place_bank** bank) {
@@ -1288,14 +1278,9 @@ int prs_place_bank_clear(prs_place_bank* bank) {
   }
   prs_context* ctx = bank->ctx;
   (void) hipSetDevice(ctx->device);
-  const size_t n = (size_t) bank->batch * (size_t) bank->map_stride;  // >= batch
-  hipLaunchKernelGGL(place_bank_clear_kernel, dim3((unsigned) ((n + kPdThreads - 1) / kPdThreads)), dim3(kPdThreads), 0, ctx_stream(ctx),
-                     bank_dev(bank));
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    return ctx_fail_hip(ctx, e, "prs_place_bank_clear launch");
-  }
-  return PRS_OK;
+  const int64_t n = (int64_t) bank->batch * bank->map_stride;  // >= batch
+  return Launches(ctx, "prs_place_bank_clear", ctx_stream(ctx)).one((n + kPdThreads - 1) / kPdThreads, kPdThreads, place_bank_clear_kernel,
+                                                                    0, bank_dev(bank));
 }
 
 int prs_place_bank_sizes(prs_place_bank* bank, int32_t* maps, int32_t* rows, int32_t* max_map_rows) {
@@ -1364,7 +1349,7 @@ int prs_place_bank_append_batch(prs_place_bank* bank, const prs_place_bank_appen
   if (in->query_stride < 1 || in->query_stride > kPdMaxQuery) {
     return ctx_fail(ctx, PRS_ERR_UNSUPPORTED, "prs_place_bank_append_batch: query_stride must be in [1, 65536]");
   }
-  if (!aligned(in->desc, 16) || !aligned(in->xyz, 16)) {
+  if (!aligned_to(in->desc, 16) || !aligned_to(in->xyz, 16)) {
     return ctx_fail(ctx, PRS_ERR_UNSUPPORTED, "prs_place_bank_append_batch: rows must be 16-byte aligned");
   }
   (void) hipSetDevice(ctx->device);
@@ -1372,11 +1357,11 @@ int prs_place_bank_append_batch(prs_place_bank* bank, const prs_place_bank_appen
   memset(&a, 0, sizeof(a));
   a.in = *in;
   a.d  = bank_dev(bank);
-  hipLaunchKernelGGL(place_bank_append_kernel, dim3((unsigned) bank->batch), dim3(kPdThreads), 0, ctx_stream(ctx), a);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    return ctx_fail_hip(ctx, e, "prs_place_bank_append_batch launch");
-  }
+  Launches on(ctx, "prs_place_bank_append_batch", ctx_stream(ctx));
+  const Grid grid = on.grid(bank->batch, kPdThreads);
+  PRS_TRY(on.check());
+  on.launch(place_bank_append_kernel, grid, 0, a);
+  PRS_TRY(on.finish());
   bank->max_query_stride = in->query_stride > bank->max_query_stride ? in->query_stride : bank->max_query_stride;
   return PRS_OK;
 }
@@ -1405,7 +1390,7 @@ int prs_place_bank_query_batch(prs_place_bank* bank, const prs_place_params* par
       q->corr_stride < 1 || q->corr_stride > kPdMaxCorrStride) {
     return ctx_fail(ctx, PRS_ERR_CAPACITY, "prs_place_bank_query_batch: count_stride, key_stride or corr_stride below the bank's capacity");
   }
-  if (!aligned(q->desc, 4)) {
+  if (!aligned_to(q->desc, 4)) {
     return ctx_fail(ctx, PRS_ERR_UNSUPPORTED, "prs_place_bank_query_batch: descriptor rows must be 4-byte aligned");
   }
   (void) hipSetDevice(ctx->device);
@@ -1418,19 +1403,17 @@ int prs_place_bank_query_batch(prs_place_bank* bank, const prs_place_params* par
   if (links) {
     a.links = *links;
   }
-  hipStream_t s = ctx_stream(ctx);
-  const int big = bank->row_stride > bank->map_stride ? bank->row_stride : bank->map_stride;
-  const unsigned gx = (unsigned) ((big + kPdThreads - 1) / kPdThreads < 1024 ? (big + kPdThreads - 1) / kPdThreads : 1024);
-  hipLaunchKernelGGL(place_bank_init_kernel, dim3(gx, (unsigned) q->batch), dim3(kPdThreads), 0, s, a);
-  const dim3 grid((unsigned) ((bank->row_stride + kPdSlice - 1) / kPdSlice), (unsigned) ((q->query_stride + kPdRowsWg - 1) / kPdRowsWg),
-                  (unsigned) q->batch);
-  hipLaunchKernelGGL(place_bank_score_kernel, grid, dim3(kPdThreads), 0, s, a);
-  hipLaunchKernelGGL(place_bank_select_kernel, dim3((unsigned) q->batch), dim3(kPdThreads), 0, s, a);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    return ctx_fail_hip(ctx, e, "prs_place_bank_query_batch launch");
-  }
-  return PRS_OK;
+  Launches on(ctx, "prs_place_bank_query_batch", ctx_stream(ctx));
+  const int64_t big = bank->row_stride > bank->map_stride ? bank->row_stride : bank->map_stride, init_x = (big + kPdThreads - 1) / kPdThreads;
+  const Grid init   = on.grid(init_x < 1024 ? init_x : 1024, q->batch, kPdThreads);
+  const Grid score  = on.grid(((int64_t) bank->row_stride + kPdSlice - 1) / kPdSlice, ((int64_t) q->query_stride + kPdRowsWg - 1) / kPdRowsWg,
+                              q->batch, kPdThreads);
+  const Grid select = on.grid(q->batch, kPdThreads);
+  PRS_TRY(on.check());
+  on.launch(place_bank_init_kernel, init, 0, a);
+  on.launch(place_bank_score_kernel, score, 0, a);
+  on.launch(place_bank_select_kernel, select, 0, a);
+  return on.finish();
 }
 
 int prs_place_bank_gather_pairs(prs_place_bank* bank, const prs_place_params* params, const prs_place_queries* queries,
@@ -1457,8 +1440,8 @@ int prs_place_bank_gather_pairs(prs_place_bank* bank, const prs_place_params* pa
   if (pairs->fixed_stride < queries->query_stride || pairs->moving_stride < bank_largest_map(bank) || pairs->moving_stride < 1) {
     return ctx_fail(ctx, PRS_ERR_CAPACITY, "prs_place_bank_gather_pairs: a pair slot is smaller than the query or the largest map the bank holds");
   }
-  if (!aligned(queries->desc, 16) || !aligned(queries->xyz, 16) || !aligned(pairs->fixed_xyz, 16) || !aligned(pairs->fixed_desc, 16) ||
-      !aligned(pairs->moving_xyz, 16) || !aligned(pairs->moving_desc, 16)) {
+  if (!aligned_to(queries->desc, 16) || !aligned_to(queries->xyz, 16) || !aligned_to(pairs->fixed_xyz, 16) || !aligned_to(pairs->fixed_desc, 16) ||
+      !aligned_to(pairs->moving_xyz, 16) || !aligned_to(pairs->moving_desc, 16)) {
     return ctx_fail(ctx, PRS_ERR_UNSUPPORTED, "prs_place_bank_gather_pairs: rows must be 16-byte aligned");
   }
   (void) hipSetDevice(ctx->device);
@@ -1468,13 +1451,8 @@ int prs_place_bank_gather_pairs(prs_place_bank* bank, const prs_place_params* pa
   g.o    = *pairs;
   g.d    = bank_dev(bank);
   g.maxc = params->max_candidates;
-  const size_t slots = (size_t) queries->batch * (size_t) params->max_candidates;
-  hipLaunchKernelGGL(place_bank_gather_kernel, dim3((unsigned) ((slots + 3) / 4)), dim3(kPdThreads), 0, ctx_stream(ctx), g);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    return ctx_fail_hip(ctx, e, "prs_place_bank_gather_pairs launch");
-  }
-  return PRS_OK;
+  const int64_t slots = (int64_t) queries->batch * params->max_candidates;
+  return Launches(ctx, "prs_place_bank_gather_pairs", ctx_stream(ctx)).one((slots + 3) / 4, kPdThreads, place_bank_gather_kernel, 0, g);
 }
 
 }  // extern "C"

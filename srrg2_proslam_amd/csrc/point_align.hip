@@ -320,10 +320,6 @@ __global__ __launch_bounds__(kThreads) void point_align_kernel(const PointAlignA
   res->warnings            = warn;
 }
 
-bool aligned(const void* ptr, size_t a) {
-  return (reinterpret_cast<uintptr_t>(ptr) & (a - 1)) == 0;
-}
-
 }  // namespace
 
 // instantiation by corr_stride: every correspondence parked up to 64 per pair (K = 1) and 256 (K = 4); beyond, 384 parked and the
@@ -355,7 +351,7 @@ int point_align_launch(prs_context* ctx, const prs_point_align_params* params, c
   if (batch->corr_stride > kMaxCorrStride) {
     return ctx_fail(ctx, PRS_ERR_UNSUPPORTED, "prs_point_align_batch: corr_stride above 8192");
   }
-  if (!aligned(batch->fixed, 16) || !aligned(batch->moving, 16) || !aligned(batch->corr, 4) || !aligned(batch->X, 4)) {
+  if (!aligned_to(batch->fixed, 16) || !aligned_to(batch->moving, 16) || !aligned_to(batch->corr, 4) || !aligned_to(batch->X, 4)) {
     return ctx_fail(ctx, PRS_ERR_UNSUPPORTED, "prs_point_align_batch: point rows must be 16-byte aligned");
   }
   PointAlignArgs a;
@@ -363,19 +359,17 @@ int point_align_launch(prs_context* ctx, const prs_point_align_params* params, c
   a.b = *batch;
   a.p = *params;
   const int k = K != 0 ? K : (batch->corr_stride <= 64 ? 1 : (batch->corr_stride <= 256 ? 4 : 6));
-  const dim3 grid((unsigned) ((batch->batch + kPairsPerBlock - 1) / kPairsPerBlock));
+  Launches on(ctx, "prs_point_align_batch", ctx_stream(ctx));
+  const Grid grid = on.grid(((int64_t) batch->batch + kPairsPerBlock - 1) / kPairsPerBlock, kThreads);
+  PRS_TRY(on.check());
   if (k == 1) {
-    hipLaunchKernelGGL(point_align_kernel<1>, grid, dim3(kThreads), 0, ctx_stream(ctx), a);
+    on.launch(point_align_kernel<1>, grid, 0, a);
   } else if (k == 4) {
-    hipLaunchKernelGGL(point_align_kernel<4>, grid, dim3(kThreads), 0, ctx_stream(ctx), a);
+    on.launch(point_align_kernel<4>, grid, 0, a);
   } else {
-    hipLaunchKernelGGL(point_align_kernel<6>, grid, dim3(kThreads), 0, ctx_stream(ctx), a);
+    on.launch(point_align_kernel<6>, grid, 0, a);
   }
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    return ctx_fail_hip(ctx, e, "prs_point_align_batch launch");
-  }
-  return PRS_OK;
+  return on.finish();
 }
 
 }  // namespace prs

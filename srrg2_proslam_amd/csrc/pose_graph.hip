@@ -829,18 +829,14 @@ int check_batch(prs_context* ctx, const std::string& who, const prs_pose_graphs*
 template <class Kernel, class Args>
 int launch_one_wave_per_graph(prs_context* ctx, const std::string& who, Kernel kernel, const Args& a, const int batch, const int node_stride) {
   const size_t lds = lds_fixed_bytes(node_stride) + (size_t) a.rb_cols * 6 * sizeof(double);
-  hipError_t e     = hipSuccess;
-  if (lds > 64u * 1024u) {
-    e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds);
-  }
+  Launches on(ctx, who.c_str(), ctx_stream(ctx));
+  const Grid grid = on.grid(batch, kThreads);
+  PRS_TRY(on.check());
+  const hipError_t e = allow_lds(kernel, lds);
   if (e == hipSuccess) {
-    hipLaunchKernelGGL(kernel, dim3((unsigned) batch), dim3(kThreads), lds, ctx_stream(ctx), a);
-    e = hipGetLastError();
+    on.launch(kernel, grid, lds, a);
   }
-  if (e != hipSuccess) {
-    return ctx_fail_hip(ctx, e, (who + " launch").c_str());
-  }
-  return PRS_OK;
+  return on.finish(e);
 }
 
 }  // namespace
@@ -924,12 +920,7 @@ int pose_graph_append_launch(prs_context* ctx, const prs_pose_graph_params* para
   a.g           = *graphs;
   a.c           = *closures;
   a.information = params->closure_information;
-  hipLaunchKernelGGL(append_closures_kernel, dim3((unsigned) graphs->batch), dim3(kThreads), 0, ctx_stream(ctx), a);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    return ctx_fail_hip(ctx, e, "prs_pose_graph_append_closures launch");
-  }
-  return PRS_OK;
+  return Launches(ctx, "prs_pose_graph_append_closures", ctx_stream(ctx)).one(graphs->batch, kThreads, append_closures_kernel, 0, a);
 }
 
 // The host-pointer entry of either algorithm: sizes the envelope, stages, runs `launch(descriptor, device result)`, downloads.

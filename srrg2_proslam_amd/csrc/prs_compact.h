@@ -41,8 +41,4 @@ __device__ __forceinline__ int chunk_position(const uint64_t mask, int* s_wave, 
   return lanes_below(mask, pos);
 }
 
-inline bool aligned_to(const void* p, uintptr_t to) {
-  return (reinterpret_cast<uintptr_t>(p) & (to - 1)) == 0;
-}
-
 }  // namespace prs

@@ -7,6 +7,7 @@
 #include <string>
 
 #include "../../include/proslam_hip.h"
+#include "prs_launch.h"
 
 namespace prs {
 
@@ -67,8 +68,6 @@ struct prs_context {
 
 namespace prs {
 
-int ctx_fail(prs_context* ctx, int status, const char* what);
-int ctx_fail_hip(prs_context* ctx, hipError_t e, const char* what);
 inline hipStream_t ctx_stream(prs_context* ctx) {
   return ctx->stream;
 }
@@ -81,10 +80,14 @@ inline hipStream_t ctx_stream(prs_context* ctx) {
     }                         \
   } while (0)
 
-// whether one launch may have this grid: HIP takes no launch of 2^32 or more work-items in a dimension (hip_runtime_api.h, the note
-// on hipModuleLaunchKernel), which for 256 threads is 2^24 - 1 workgroups.  No product here overflows for any int64 count
-inline bool grid_fits(const int64_t workgroups, const int threads) {
-  return workgroups >= 1 && threads >= 1 && threads <= 1024 && workgroups <= 0xffffffffll / threads;
+// (ctx_fail, ctx_fail_hip, grid_fits and the launch path: prs_launch.h)
+inline bool aligned_to(const void* p, uintptr_t to) {
+  return (reinterpret_cast<uintptr_t>(p) & (to - 1)) == 0;
+}
+// whether two arrays of a batch share a byte
+inline bool overlap(const void* a, size_t na, const void* b, size_t nb) {
+  const uintptr_t x = reinterpret_cast<uintptr_t>(a), y = reinterpret_cast<uintptr_t>(b);
+  return x < y + nb && y < x + na;
 }
 
 inline size_t align256(size_t v) {
@@ -177,8 +180,9 @@ void ctx_report_stamps(prs_context* ctx, int blocks, int n_stamps, const char* l
 // brute-force matcher, merger) each have a *_plan function next to them: pure host code (no HIP call, no getenv, no context, no
 // batch pointer followed) from the parameter structs, the batch descriptor's strides / counts / which optional pointers are set
 // and a DispatchEnv to a plan -- a refusal, or the launches (kernel = index into the family's variant table, grid, block, dynamic
-// LDS bytes) plus the kernel argument struct with every layout field set.  The launcher validates pointers, takes the plan,
-// allocates what the plan sizes, adds the pointers and launches.  The prs_*_plan entry points show the same plans to tests.
+// LDS bytes) plus the kernel argument struct with every layout field set.  Plan::add checks every grid it takes (prs_launch.h), so a
+// plan that is PRS_OK holds launches HIP accepts.  The launcher validates pointers, takes the plan, allocates what the plan sizes,
+// adds the pointers and launches through launch_planned.  The prs_*_plan entry points show the same plans to tests.
 using DispatchEnv = prs_dispatch_env;  // everything outside the arguments a dispatch depends on
 // the context's knobs and CU count, and the two brute-force switches from the environment as it is now
 DispatchEnv dispatch_env(const prs_context* ctx);
@@ -213,9 +217,10 @@ struct Plan {
   int status          = PRS_OK;
   const char* message = nullptr;
   int n_launches      = 0;  // 0 with PRS_OK: an empty batch
+  const char* too_large = "dispatch: more work-items than one launch holds";  // (each family puts its entry point's name in front)
   struct Launch {
     int kernel;  // index into the family's variant table
-    unsigned grid_x, grid_y, block;
+    Grid grid;
     size_t lds;
   } launch[PRS_PLAN_MAX_LAUNCHES];
   void refuse(int code, const char* what) {
@@ -223,11 +228,14 @@ struct Plan {
     message    = what;
     n_launches = 0;
   }
-  void add(int kernel, unsigned grid_x, unsigned grid_y, unsigned block, size_t lds) {
+  void add(int kernel, int64_t grid_x, int64_t grid_y, int block, size_t lds) {
+    const Grid grid = Grid::checked(grid_x, grid_y, 1, block);
     if (kernel < 0) {
       refuse(PRS_ERR_UNSUPPORTED, "dispatch: no kernel instantiation for this shape");
+    } else if (!grid) {
+      refuse(PRS_ERR_UNSUPPORTED, too_large);
     } else if (status == PRS_OK) {
-      launch[n_launches++] = {kernel, grid_x, grid_y, block, lds};
+      launch[n_launches++] = {kernel, grid, lds};
     }
   }
 };
@@ -240,7 +248,7 @@ inline void export_plan(const Plan& p, const Variant<Args> (&table)[N], prs_disp
   out->n_launches = p.n_launches;
   for (int i = 0; i < p.n_launches; ++i) {
     const Plan::Launch& l = p.launch[i];
-    out->launch[i]        = {table[l.kernel].name, (int32_t) l.grid_x, (int32_t) l.grid_y, (int32_t) l.block, (uint32_t) l.lds};
+    out->launch[i]        = {table[l.kernel].name, (int32_t) l.grid.x(), (int32_t) l.grid.y(), (int32_t) l.grid.threads(), (uint32_t) l.lds};
   }
 }
 // the index-th name of each family's variant tables, nullptr past the end (prs_dispatch_kernel_name)
@@ -248,13 +256,6 @@ const char* stereo_kernel_name(int index);
 const char* align_kernel_name(int index);
 const char* bruteforce_kernel_name(int index);
 const char* merge_kernel_name(int index);
-// the request a kernel needs before it may be launched with more than 64 KiB of dynamic LDS
-template <class Args>
-inline hipError_t allow_lds(void (*kernel)(Args), size_t lds) {
-  return lds > 64u * 1024u ? hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds)
-                           : hipSuccess;
-}
-
 // exact integer form of `best < max_distance && best / second < max_ratio` (epipolar_impl.cpp:171-173),
 // evaluated on the host with the same IEEE float operations the reference performs:
 // accept iff best < *best_lim && best <= bmax[second] (index 257 = no second candidate)
@@ -286,7 +287,13 @@ int recip_selftest_launch(prs_context* ctx, unsigned long long* d_counts);
 int bruteforce_batch_launch(prs_context* ctx, const prs_bruteforce_params* params, const prs_bruteforce_batch* batch);
 int selection_order_launch(prs_context* ctx, const uint8_t* response_dev, int n, int32_t* order_dev, int32_t* status_dev);
 int extract_features_launch(prs_context* ctx, const prs_extractor_params* params, const prs_extract_batch* batch);
-int describe_selected_launch(prs_context* ctx, const prs_extract_batch* batch, uint32_t* kept);
+// descriptors of keypoints another unit selected: that unit declares these grids among its own, checks, and launches last
+struct DescribeGrids {
+  Grid tiles, describe;
+  int chunks = 0;
+};
+DescribeGrids describe_selected_grids(Launches& on, const prs_extract_batch& batch);
+int describe_selected_launch(prs_context* ctx, const Launches& on, const DescribeGrids& grids, const prs_extract_batch* batch, uint32_t* kept);
 int selective_extract_launch(prs_context* ctx, const prs_selective_extractor_params* params, const prs_selective_extract_batch* batch);
 int depth_measurements_launch(prs_context* ctx, const prs_depth_params* params, const prs_depth_batch* batch);
 int point_align_launch(prs_context* ctx, const prs_point_align_params* params, const prs_point_align_pairs* batch);
@@ -307,9 +314,14 @@ int world_map_launch(prs_context* ctx, const prs_world_map_params* params, const
 int world_voxel_launch(prs_context* ctx, const prs_world_voxel_params* params, const prs_world_voxel_batch* batch);
 int depth_cloud_launch(prs_context* ctx, const prs_depth_cloud_params* params, const prs_depth_cloud_batch* batch);
 int dense_stereo_launch(prs_context* ctx, const prs_dense_stereo_params* params, const prs_dense_stereo_batch* batch);
-// dense stereo's census and finish launches, shared with the semi-global stage (checked batches only; false: a grid too large)
-bool dense_census_enqueue(hipStream_t st, const prs_dense_stereo_batch& o, uint64_t* census_l, uint64_t* census_r);
-bool dense_finish_enqueue(hipStream_t st, const prs_dense_stereo_params& p, const prs_dense_stereo_batch& o, uint2* rec_l, int16_t* win_r);
+// dense stereo's census and finish launches, shared with the semi-global stage (checked batches only): *_blocks is the grid the
+// caller declares, at kDenseThreads a workgroup, and has checked when it enqueues
+constexpr int kDenseThreads = 256;
+int64_t dense_census_blocks(const prs_dense_stereo_batch& o);
+int64_t dense_finish_blocks(const prs_dense_stereo_batch& o);
+void dense_census_enqueue(const Launches& on, const Grid& grid, const prs_dense_stereo_batch& o, uint64_t* census_l, uint64_t* census_r);
+void dense_finish_enqueue(const Launches& on, const Grid& grid, const prs_dense_stereo_params& p, const prs_dense_stereo_batch& o, uint2* rec_l,
+                          int16_t* win_r);
 int sgm_stereo_launch(prs_context* ctx, const prs_sgm_stereo_params* params, const prs_sgm_stereo_batch* batch);
 int speckle_launch(prs_context* ctx, const prs_speckle_params* params, const prs_speckle_batch* batch);
 int depth_consistency_launch(prs_context* ctx, const prs_depth_consistency_params* params, const prs_depth_consistency_batch* batch);

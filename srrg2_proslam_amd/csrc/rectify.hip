@@ -327,18 +327,18 @@ uint32_t border_value(const prs_rectify_params* params) {
 }
 
 template <typename T>
-void launch(prs_context* ctx, const RectifyArgs& a, bool bilinear, bool stage, unsigned grid) {
+void launch_rectify(const Launches& on, const Grid& grid, const RectifyArgs& a, bool bilinear, bool stage) {
   if constexpr (sizeof(T) == 1) {  // bilinear exists for 8-bit pixels only, and only it stages
     if (bilinear && stage) {
-      hipLaunchKernelGGL((rectify_kernel<T, true, true>), dim3(grid), dim3(kThreads), 0, ctx_stream(ctx), a);
+      on.launch(rectify_kernel<T, true, true>, grid, 0, a);
       return;
     }
     if (bilinear) {
-      hipLaunchKernelGGL((rectify_kernel<T, true, false>), dim3(grid), dim3(kThreads), 0, ctx_stream(ctx), a);
+      on.launch(rectify_kernel<T, true, false>, grid, 0, a);
       return;
     }
   }
-  hipLaunchKernelGGL((rectify_kernel<T, false, false>), dim3(grid), dim3(kThreads), 0, ctx_stream(ctx), a);
+  on.launch(rectify_kernel<T, false, false>, grid, 0, a);
 }
 
 }  // namespace
@@ -401,10 +401,9 @@ int rectify_launch(prs_context* ctx, const prs_rectify_params* params, const prs
     }
   }
   a.chunk = (int) chunk;
-  const int64_t grid = tiles * ((batch->batch + chunk - 1) / chunk);
-  if (!grid_fits(grid, kThreads)) {
-    return ctx_fail(ctx, PRS_ERR_UNSUPPORTED, "prs_rectify_batch_run: more than 2^32 - 1 work-items in one launch");
-  }
+  Launches on(ctx, "prs_rectify_batch_run", ctx_stream(ctx));
+  const Grid grid = on.grid(tiles * ((batch->batch + chunk - 1) / chunk), kThreads);
+  PRS_TRY(on.check());
   a.stage_ok     = (s0 % 16 == 0 && batch->src_pitch % 16 == 0) ? 1 : 0;
   a.vector_store = (d0 % (uintptr_t) (4 * elem) == 0 && batch->dst_pitch % (4 * elem) == 0) ? 1 : 0;
   if (batch->n_border) {
@@ -415,17 +414,13 @@ int rectify_launch(prs_context* ctx, const prs_rectify_params* params, const prs
   }
   const bool bilinear = interp == PRS_RECTIFY_BILINEAR;
   if (type == PRS_PIXEL_U8) {
-    launch<uint8_t>(ctx, a, bilinear, stage, (unsigned) grid);
+    launch_rectify<uint8_t>(on, grid, a, bilinear, stage);
   } else if (type == PRS_PIXEL_U16) {
-    launch<uint16_t>(ctx, a, false, false, (unsigned) grid);
+    launch_rectify<uint16_t>(on, grid, a, false, false);
   } else {
-    launch<uint32_t>(ctx, a, false, false, (unsigned) grid);
+    launch_rectify<uint32_t>(on, grid, a, false, false);
   }
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    return ctx_fail_hip(ctx, e, "prs_rectify_batch_run launch");
-  }
-  return PRS_OK;
+  return on.finish();
 }
 
 }  // namespace prs

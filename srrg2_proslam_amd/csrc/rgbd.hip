@@ -113,10 +113,6 @@ __global__ __launch_bounds__(kThreads) void depth_kernel(const DepthArgs a) {
   }
 }
 
-bool aligned(const void* p, size_t bytes) {
-  return (reinterpret_cast<uintptr_t>(p) & (bytes - 1)) == 0;
-}
-
 // call-level checks shared by both entry points; returns PRS_OK or the failure (already recorded in ctx)
 int check_params(prs_context* ctx, const prs_depth_params* params, int rows, int cols, int pitch, const char* who) {
   if (params->depth_type != PRS_DEPTH_U16 && params->depth_type != PRS_DEPTH_F32) {
@@ -154,24 +150,20 @@ int depth_measurements_launch(prs_context* ctx, const prs_depth_params* params, 
     return ctx_fail(ctx, PRS_ERR_RANGE, "prs_depth_measurements_batch: stride below 1");
   }
   const int elem = params->depth_type == PRS_DEPTH_U16 ? 2 : 4;
-  if (!aligned(batch->fixed, 16) || !aligned(batch->fixed_desc, 16) || !aligned(batch->descriptors, 16) || !aligned(batch->keypoints, 8) ||
-      !aligned(batch->depth, (size_t) elem)) {
+  if (!aligned_to(batch->fixed, 16) || !aligned_to(batch->fixed_desc, 16) || !aligned_to(batch->descriptors, 16) || !aligned_to(batch->keypoints, 8) ||
+      !aligned_to(batch->depth, (size_t) elem)) {
     return ctx_fail(ctx, PRS_ERR_UNSUPPORTED, "prs_depth_measurements_batch: fixed / descriptor rows must be 16-byte aligned");
   }
-  if (!grid_fits(batch->batch, kThreads)) {
-    return ctx_fail(ctx, PRS_ERR_UNSUPPORTED, "prs_depth_measurements_batch: more work-items than one launch holds");
-  }
+  Launches on(ctx, "prs_depth_measurements_batch", ctx_stream(ctx));
+  const Grid grid = on.grid(batch->batch, kThreads);
+  PRS_TRY(on.check());
   DepthArgs a;
   memset(&a, 0, sizeof(a));
   a.b          = *batch;
   a.depth_type = params->depth_type;
   a.scale      = params->depth_scaling_factor_to_meters;
-  hipLaunchKernelGGL(depth_kernel, dim3(batch->batch), dim3(kThreads), 0, ctx_stream(ctx), a);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    return ctx_fail_hip(ctx, e, "prs_depth_measurements_batch launch");
-  }
-  return PRS_OK;
+  on.launch(depth_kernel, grid, 0, a);
+  return on.finish();
 }
 
 }  // namespace prs

@@ -262,30 +262,28 @@ int scene_clip_launch(prs_context* ctx, const prs_projector* projector, const fl
   a.tiles    = (batch->stride + kClipTile - 1) / kClipTile;
   a.counts   = nullptr;
   a.info_lut = nullptr;
+  // many scenes (or short ones): one workgroup walks a scene; few long scenes: tile-parallel
+  const bool walk = batch->batch >= 128 || a.tiles <= 2;
+  Launches on(ctx, "prs_scene_clip", ctx_stream(ctx));
+  const Grid grid = walk ? on.grid(batch->batch, kClipThreads) : on.grid(a.tiles, batch->batch, kClipThreads);
+  PRS_TRY(on.check());
   if (batch->scene_n_opt) {
     a.info_lut = ctx_info_scale_table(ctx);
     if (!a.info_lut) {
       return ctx_fail(ctx, PRS_ERR_HIP, "prs_scene_clip: information scale table allocation failed");
     }
   }
-  hipStream_t stream = ctx_stream(ctx);
-  // many scenes (or short ones): one workgroup walks a scene; few long scenes: tile-parallel
-  const bool walk = batch->batch >= 128 || a.tiles <= 2;
   if (walk) {
-    hipLaunchKernelGGL(scene_clip_kernel<kClipWalk>, dim3(batch->batch), dim3(kClipThreads), 0, stream, a);
+    on.launch(scene_clip_kernel<kClipWalk>, grid, 0, a);
   } else {
     a.counts = static_cast<int*>(ctx_arena(ctx, ARENA_WORK_3, (size_t) batch->batch * a.tiles * sizeof(int)));
     if (!a.counts) {
       return ctx_fail(ctx, PRS_ERR_HIP, "prs_scene_clip: scratch allocation failed");
     }
-    hipLaunchKernelGGL(scene_clip_kernel<kClipCount>, dim3(a.tiles, batch->batch), dim3(kClipThreads), 0, stream, a);
-    hipLaunchKernelGGL(scene_clip_kernel<kClipScatter>, dim3(a.tiles, batch->batch), dim3(kClipThreads), 0, stream, a);
+    on.launch(scene_clip_kernel<kClipCount>, grid, 0, a);
+    on.launch(scene_clip_kernel<kClipScatter>, grid, 0, a);
   }
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    return ctx_fail_hip(ctx, e, "prs_scene_clip launch");
-  }
-  return PRS_OK;
+  return on.finish();
 }
 
 }  // namespace prs

@@ -509,6 +509,26 @@ int selective_extract_launch(prs_context* ctx, const prs_selective_extractor_par
   if (lds_sel > kMaxLds) {
     return ctx_fail(ctx, PRS_ERR_UNSUPPORTED, "prs_extract_features_selective_batch: max_candidates and target_number_of_keypoints exceed the LDS");
   }
+  prs_extract_batch eb;
+  eb.batch       = batch->batch;
+  eb.rows        = batch->rows;
+  eb.cols        = batch->cols;
+  eb.pitch       = batch->pitch;
+  eb.images      = batch->images;
+  eb.stride      = batch->stride;
+  eb.keypoints   = batch->keypoints;
+  eb.intensity   = batch->intensity;
+  eb.descriptors = batch->descriptors;
+  eb.n_features  = batch->n_features;
+  eb.status      = batch->status;
+  hipStream_t stream = ctx_stream(ctx);
+  Launches on(ctx, "prs_extract_features_selective_batch", stream);  // its own launches and the describe stage's
+  const Grid mask     = on.grid(((int64_t) batch->rows + kMaskRows - 1) / kMaskRows, batch->batch, kMaskThreads);
+  const Grid tiles    = on.grid(((int64_t) batch->cols + kRespW - 1) / kRespW, ((int64_t) batch->rows + kRespH - 1) / kRespH, batch->batch, kRespThreads);
+  const Grid select   = on.grid(batch->batch, 2, kSelThreads);
+  const Grid finalize = on.grid(batch->batch, 256);
+  const DescribeGrids describe = describe_selected_grids(on, eb);
+  PRS_TRY(on.check());
   const size_t B = (size_t) batch->batch;
   a.wpr = (batch->cols + 31) / 32;
   const size_t b_mask = align256(B * batch->rows * a.wpr * 4), b_small = align256(B * 5 * 4), b_cand = align256(B * 2 * cap * 8);
@@ -525,42 +545,25 @@ int selective_extract_launch(prs_context* ctx, const prs_selective_extractor_par
   a.sel    = reinterpret_cast<uint32_t*>(d + b_mask + b_small + b_cand);
   a.n_sel  = reinterpret_cast<int32_t*>(d + b_mask + b_small + b_cand + b_sel);
   a.kept   = reinterpret_cast<uint32_t*>(d + b_mask + b_small + b_cand + b_sel + b_nsel);
-  hipStream_t stream = ctx_stream(ctx);
-  hipError_t e       = hipMemsetAsync(a.maxima, 0, B * 5 * 4, stream);
+  hipError_t e = hipMemsetAsync(a.maxima, 0, B * 5 * 4, stream);
   if (e != hipSuccess) {
     return ctx_fail_hip(ctx, e, "prs_extract_features_selective_batch: counters");
   }
   const size_t lds_mask = (size_t) kMaskRows * (batch->cols + 1) * sizeof(int);
-  e = hipFuncSetAttribute(reinterpret_cast<const void*>(mask_raster_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds_mask);
+  e = allow_lds(mask_raster_kernel, lds_mask, true);
   if (e == hipSuccess) {
-    e = hipFuncSetAttribute(reinterpret_cast<const void*>(select_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds_sel);
+    e = allow_lds(select_kernel, lds_sel, true);
   }
   if (e != hipSuccess) {
     return ctx_fail_hip(ctx, e, "prs_extract_features_selective_batch: LDS of the mask / selection kernels");
   }
-  const dim3 tiles((batch->cols + kRespW - 1) / kRespW, (batch->rows + kRespH - 1) / kRespH, batch->batch);
-  hipLaunchKernelGGL(mask_raster_kernel, dim3((batch->rows + kMaskRows - 1) / kMaskRows, batch->batch), dim3(kMaskThreads), lds_mask, stream, a);
-  hipLaunchKernelGGL(response_kernel<0>, tiles, dim3(kRespThreads), 0, stream, a);
-  hipLaunchKernelGGL(response_kernel<1>, tiles, dim3(kRespThreads), 0, stream, a);
-  hipLaunchKernelGGL(select_kernel, dim3(batch->batch, 2), dim3(kSelThreads), lds_sel, stream, a);
-  hipLaunchKernelGGL(finalize_kernel, dim3(batch->batch), dim3(256), 0, stream, a);
-  e = hipGetLastError();
-  if (e != hipSuccess) {
-    return ctx_fail_hip(ctx, e, "prs_extract_features_selective_batch launch");
-  }
-  prs_extract_batch eb;
-  eb.batch       = batch->batch;
-  eb.rows        = batch->rows;
-  eb.cols        = batch->cols;
-  eb.pitch       = batch->pitch;
-  eb.images      = batch->images;
-  eb.stride      = batch->stride;
-  eb.keypoints   = batch->keypoints;
-  eb.intensity   = batch->intensity;
-  eb.descriptors = batch->descriptors;
-  eb.n_features  = batch->n_features;
-  eb.status      = batch->status;
-  return describe_selected_launch(ctx, &eb, a.kept);
+  on.launch(mask_raster_kernel, mask, lds_mask, a);
+  on.launch(response_kernel<0>, tiles, 0, a);
+  on.launch(response_kernel<1>, tiles, 0, a);
+  on.launch(select_kernel, select, lds_sel, a);
+  on.launch(finalize_kernel, finalize, 0, a);
+  PRS_TRY(on.finish());
+  return describe_selected_launch(ctx, on, describe, &eb, a.kept);
 }
 
 }  // namespace prs

@@ -701,10 +701,6 @@ __global__ __launch_bounds__(kThreads) void session_reenter_kernel(const Reenter
   copy_span(r.merge_corr + (size_t) b * r.corr_stride, r.corr + sl * r.corr_stride, (size_t) sh.nc * sizeof(prs_corr), tid);
 }
 
-bool aligned(const void* p, uintptr_t to) {
-  return (reinterpret_cast<uintptr_t>(p) & (to - 1)) == 0;
-}
-
 }  // namespace
 
 // the message of a refused call, built on the failure path only
@@ -732,8 +728,8 @@ static int step_prepare(prs_context* ctx, const char* who, const prs_session_par
   if (s.handover_desc && s.handover_stride < s.capacity) {
     return ctx_fail(ctx, PRS_ERR_CAPACITY, fail_text(who, ": handover_stride below the maps' capacity").c_str());
   }
-  if (!aligned(s.coords, 16) || !aligned(s.desc, 16) || !aligned(s.graph_X, 8) || !aligned(s.n_meas, 4) ||
-      (s.handover_desc && (!aligned(s.handover_desc, 16) || !aligned(s.handover_xyz, 16)))) {
+  if (!aligned_to(s.coords, 16) || !aligned_to(s.desc, 16) || !aligned_to(s.graph_X, 8) || !aligned_to(s.n_meas, 4) ||
+      (s.handover_desc && (!aligned_to(s.handover_desc, 16) || !aligned_to(s.handover_xyz, 16)))) {
     return ctx_fail(ctx, PRS_ERR_UNSUPPORTED, fail_text(who, ": coords, desc and the hand-over arrays must be 16-byte aligned, graph_X 8-byte").c_str());
   }
   if (!s.omega && (params->split_information != 1.0f || params->lost_information != 1.0f)) {
@@ -760,12 +756,7 @@ int session_step_launch(prs_context* ctx, const prs_session_params* params, cons
   }
   StepArgs a;
   PRS_TRY(step_prepare(ctx, who, params, batch, &a));
-  hipLaunchKernelGGL(session_step_kernel, dim3((unsigned) batch->batch), dim3(kThreads), 0, ctx_stream(ctx), a);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    return ctx_fail_hip(ctx, e, "prs_session_step_batch launch");
-  }
-  return PRS_OK;
+  return Launches(ctx, who, ctx_stream(ctx)).one(batch->batch, kThreads, session_step_kernel, 0, a);
 }
 
 // the archive and the live map's statistics arrays against the session batch (who: the entry point's name)
@@ -786,9 +777,9 @@ static int archive_prepare(prs_context* ctx, const char* who, const prs_session_
                    ar.max_frames != maps->max_frames))) {
     return ctx_fail(ctx, PRS_ERR_RANGE, fail_text(who, ": batch, capacity, node_stride or the history's shape differ between the structs, or slot_stride below 1").c_str());
   }
-  if (!aligned(ar.coords, 16) || !aligned(ar.desc, 16) || !aligned(ar.state, 16) || !aligned(maps->state, 16) || !aligned(ar.covariance, 4) ||
-      !aligned(maps->covariance, 4) || !aligned(ar.n_opt, 4) || !aligned(maps->n_opt, 4) || !aligned(ar.n_meas, 4) ||
-      (ar.meas && (!aligned(ar.meas, 4) || !aligned(maps->meas, 4) || !aligned(ar.poses, 4) || !aligned(maps->poses, 4)))) {
+  if (!aligned_to(ar.coords, 16) || !aligned_to(ar.desc, 16) || !aligned_to(ar.state, 16) || !aligned_to(maps->state, 16) || !aligned_to(ar.covariance, 4) ||
+      !aligned_to(maps->covariance, 4) || !aligned_to(ar.n_opt, 4) || !aligned_to(maps->n_opt, 4) || !aligned_to(ar.n_meas, 4) ||
+      (ar.meas && (!aligned_to(ar.meas, 4) || !aligned_to(maps->meas, 4) || !aligned_to(ar.poses, 4) || !aligned_to(maps->poses, 4)))) {
     return ctx_fail(ctx, PRS_ERR_UNSUPPORTED, fail_text(who, ": coords, desc and state must be 16-byte aligned, the other arrays 4-byte").c_str());
   }
   ArchiveArgs& aa = *out;
@@ -815,12 +806,7 @@ int session_step_archive_launch(prs_context* ctx, const prs_session_params* para
   ArchiveStepArgs k;
   PRS_TRY(step_prepare(ctx, who, params, batch, &k.a));
   PRS_TRY(archive_prepare(ctx, who, *batch, maps, archive, &k.aa));
-  hipLaunchKernelGGL(session_step_archive_kernel, dim3((unsigned) batch->batch), dim3(kThreads), 0, ctx_stream(ctx), k);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    return ctx_fail_hip(ctx, e, "prs_session_step_archive_batch launch");
-  }
-  return PRS_OK;
+  return Launches(ctx, who, ctx_stream(ctx)).one(batch->batch, kThreads, session_step_archive_kernel, 0, k);
 }
 
 int session_reenter_launch(prs_context* ctx, const prs_reentry_params* params, const prs_session_batch* batch, const prs_merge_batch* maps,
@@ -845,7 +831,7 @@ int session_reenter_launch(prs_context* ctx, const prs_reentry_params* params, c
       std::isnan(params->relocalize_max_chi_inliers)) {
     return ctx_fail(ctx, PRS_ERR_RANGE, fail_text(who, ": a stride, the capacity or max_candidates below 1, or a parameter not finite or negative").c_str());
   }
-  if (!aligned(s.coords, 16) || !aligned(s.desc, 16) || !aligned(s.graph_X, 8) || !aligned(s.n_meas, 4)) {
+  if (!aligned_to(s.coords, 16) || !aligned_to(s.desc, 16) || !aligned_to(s.graph_X, 8) || !aligned_to(s.n_meas, 4)) {
     return ctx_fail(ctx, PRS_ERR_UNSUPPORTED, fail_text(who, ": coords and desc must be 16-byte aligned, graph_X 8-byte").c_str());
   }
   ReenterArgs a;
@@ -855,12 +841,7 @@ int session_reenter_launch(prs_context* ctx, const prs_reentry_params* params, c
   a.r      = r;
   a.p      = *params;
   a.max_t2 = params->max_translation * params->max_translation;
-  hipLaunchKernelGGL(session_reenter_kernel, dim3((unsigned) s.batch), dim3(kThreads), 0, ctx_stream(ctx), a);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    return ctx_fail_hip(ctx, e, "prs_session_reenter_batch launch");
-  }
-  return PRS_OK;
+  return Launches(ctx, who, ctx_stream(ctx)).one(s.batch, kThreads, session_reenter_kernel, 0, a);
 }
 
 int session_unroll_launch(prs_context* ctx, const prs_session_batch* batch, float* out) {
@@ -876,17 +857,9 @@ int session_unroll_launch(prs_context* ctx, const prs_session_batch* batch, floa
   if (batch->frame_stride < 1 || batch->node_stride < 1) {
     return ctx_fail(ctx, PRS_ERR_RANGE, "prs_session_unroll_batch: a stride below 1");
   }
-  const long long total  = (long long) batch->batch * batch->frame_stride;
-  const long long blocks = (total + kThreads - 1) / kThreads;
-  if (!grid_fits(blocks, kThreads)) {
-    return ctx_fail(ctx, PRS_ERR_UNSUPPORTED, "prs_session_unroll_batch: batch * frame_stride beyond the work-items of one launch");
-  }
-  hipLaunchKernelGGL(session_unroll_kernel, dim3((unsigned) blocks), dim3(kThreads), 0, ctx_stream(ctx), *batch, out);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    return ctx_fail_hip(ctx, e, "prs_session_unroll_batch launch");
-  }
-  return PRS_OK;
+  const int64_t total = (int64_t) batch->batch * batch->frame_stride;
+  return Launches(ctx, "prs_session_unroll_batch", ctx_stream(ctx)).one((total + kThreads - 1) / kThreads, kThreads, session_unroll_kernel,
+                                                                        0, *batch, out);
 }
 
 }  // namespace prs

@@ -26,7 +26,6 @@
 
 #include <string>
 
-#include "prs_compact.h"
 #include "prs_device.h"
 #include "prs_host.h"
 
@@ -451,16 +450,24 @@ int sgm_stereo_launch(prs_context* ctx, const prs_sgm_stereo_params* params, con
   a.rec_l     = reinterpret_cast<uint2*>(ws + 2 * l.census);
   a.win_r     = lr ? reinterpret_cast<int16_t*>(ws + 2 * l.census + l.rec) : nullptr;
   a.vol       = reinterpret_cast<uint16_t*>(ws + 2 * l.census + l.rec + l.right);
-  // the largest grids of the call, before anything is launched: each factor is below 2^31
-  const int64_t lines = o.rows > o.cols ? o.rows : o.cols;
-  const int64_t path_blocks_max   = (in_flight * lines + kWaves - 1) / kWaves;
-  const int64_t winner_blocks_max = (in_flight * a.runs + kWaves - 1) / kWaves;
-  const int64_t census_blocks = images * 2 * ((o.cols + 63) / 64) * ((o.rows + 15) / 16), finish_blocks = images * ((o.rows + 7) / 8);
-  const int64_t right_blocks_max = in_flight * o.rows * a.rtiles;
-  if ((lr && !grid_fits(right_blocks_max, kThreads)) || !grid_fits(path_blocks_max, kThreads) || !grid_fits(winner_blocks_max, kThreads) ||
-      !grid_fits(census_blocks, kThreads) || !grid_fits(finish_blocks, kThreads)) {
-    return ctx_fail(ctx, PRS_ERR_UNSUPPORTED, (who + ": more work-items than one launch holds").c_str());
-  }
+  // the grids of the call, before anything is launched (each factor is below 2^31): census and finish over every image, the rest
+  // over the images in flight -- every group of them but the last is full
+  static_assert(kThreads == kDenseThreads, "the shared launches' workgroup");
+  Launches on(ctx, who.c_str(), ctx_stream(ctx));
+  const Grid census = on.grid(dense_census_blocks(db), kThreads), finish = on.grid(dense_finish_blocks(db), kThreads);
+  struct GroupGrids {
+    Grid path_along_rows, path_along_cols, winner, right;  // a wave per image row or column (path), per run of pixels (winner)
+  };
+  const auto group_grids = [&](const int64_t n_chunk) {
+    GroupGrids g;
+    g.path_along_rows = on.grid((n_chunk * o.rows + kWaves - 1) / kWaves, kThreads);
+    g.path_along_cols = on.grid((n_chunk * o.cols + kWaves - 1) / kWaves, kThreads);
+    g.winner          = on.grid((n_chunk * a.runs + kWaves - 1) / kWaves, kThreads);
+    g.right           = lr ? on.grid(n_chunk * o.rows * a.rtiles, kThreads) : Grid();
+    return g;
+  };
+  const GroupGrids full = group_grids(in_flight), last = images % in_flight ? group_grids(images % in_flight) : full;
+  PRS_TRY(on.check());
   const int n = p.n_disparities;
   const PathKernel path = n <= 64    ? sgm_path_kernel<1, true>
                           : n <= 128 ? (n % 2 == 0 ? sgm_path_kernel<2, true> : sgm_path_kernel<2, false>)
@@ -469,30 +476,22 @@ int sgm_stereo_launch(prs_context* ctx, const prs_sgm_stereo_params* params, con
   const WinnerKernel right = n % 4 == 0 ? sgm_right_kernel<4> : n % 2 == 0 ? sgm_right_kernel<2> : sgm_right_kernel<1>;
   static const int kDirections[8][2] = {{0, 1}, {0, -1}, {1, 0}, {-1, 0}, {1, 1}, {1, -1}, {-1, 1}, {-1, -1}};  // (dy, dx)
 
-  hipStream_t st = ctx_stream(ctx);
-  if (!dense_census_enqueue(st, db, const_cast<uint64_t*>(a.census_l), const_cast<uint64_t*>(a.census_r))) {
-    return ctx_fail(ctx, PRS_ERR_UNSUPPORTED, (who + ": more work-items than one launch holds").c_str());
-  }
+  dense_census_enqueue(on, census, db, const_cast<uint64_t*>(a.census_l), const_cast<uint64_t*>(a.census_r));
   for (int64_t image0 = 0; image0 < images; image0 += in_flight) {
+    const GroupGrids& g = images - image0 < in_flight ? last : full;
     a.image0  = (int32_t) image0;
     a.n_chunk = (int32_t) (images - image0 < in_flight ? images - image0 : in_flight);
     for (int r = 0; r < p.n_paths; ++r) {
       const int dy = kDirections[r][0], dx = kDirections[r][1];
-      const int64_t waves = (int64_t) a.n_chunk * (dy == 0 ? o.rows : o.cols);
-      hipLaunchKernelGGL(path, dim3((unsigned) ((waves + kWaves - 1) / kWaves)), dim3(kThreads), 0, st, a, dy, dx, r == 0 ? 1 : 0);
+      on.launch(path, dy == 0 ? g.path_along_rows : g.path_along_cols, 0, a, dy, dx, r == 0 ? 1 : 0);
     }
-    const int64_t waves = (int64_t) a.n_chunk * a.runs;
-    hipLaunchKernelGGL(winner, dim3((unsigned) ((waves + kWaves - 1) / kWaves)), dim3(kThreads), 0, st, a);
+    on.launch(winner, g.winner, 0, a);
     if (lr) {
-      hipLaunchKernelGGL(right, dim3((unsigned) ((int64_t) a.n_chunk * o.rows * a.rtiles)), dim3(kThreads), 0, st, a);
+      on.launch(right, g.right, 0, a);
     }
   }
-  (void) dense_finish_enqueue(st, dp, db, a.rec_l, a.win_r);  // its grid was checked above
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    return ctx_fail_hip(ctx, e, "prs_sgm_stereo_batch_run launch");
-  }
-  return PRS_OK;
+  dense_finish_enqueue(on, finish, dp, db, a.rec_l, a.win_r);
+  return on.finish();
 }
 
 }  // namespace prs

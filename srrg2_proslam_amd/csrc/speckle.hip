@@ -25,7 +25,6 @@
 
 #include <string>
 
-#include "prs_compact.h"
 #include "prs_device.h"
 #include "prs_host.h"
 
@@ -389,11 +388,6 @@ inline int64_t element_bytes(const int type) {
   return type == PRS_PIXEL_U16 ? 2 : type == PRS_PIXEL_F32 ? 4 : 0;
 }
 
-inline bool overlap(const void* p, const uint64_t p_bytes, const void* q, const uint64_t q_bytes) {
-  const uintptr_t p0 = reinterpret_cast<uintptr_t>(p), q0 = reinterpret_cast<uintptr_t>(q);
-  return p0 < q0 + q_bytes && q0 < p0 + p_bytes;
-}
-
 }  // namespace
 
 int speckle_launch(prs_context* ctx, const prs_speckle_params* params, const prs_speckle_batch* batch) {
@@ -443,25 +437,21 @@ int speckle_launch(prs_context* ctx, const prs_speckle_params* params, const prs
   a.sblocks = (int32_t) ((seams + kThreads - 1) / kThreads);
   a.pblocks = (int32_t) (((int64_t) o.rows * o.cols + kChunk - 1) / kChunk);
   const int64_t images = (int64_t) o.batch * o.frames;
-  const int64_t tile_blocks = images * a.tiles_x * a.tiles_y, seam_blocks = images * a.sblocks, pixel_blocks = images * a.pblocks;
-  if (!grid_fits(tile_blocks, kThreads) || (seam_blocks > 0 && !grid_fits(seam_blocks, kThreads)) || !grid_fits(pixel_blocks, kThreads)) {
-    return ctx_fail(ctx, PRS_ERR_UNSUPPORTED, (who + ": more work-items than one launch holds").c_str());
-  }
+  Launches on(ctx, who.c_str(), ctx_stream(ctx));
+  const Grid tiles  = on.grid(images * a.tiles_x * a.tiles_y, kThreads);
+  const Grid seam   = a.sblocks > 0 ? on.grid(images * a.sblocks, kThreads) : Grid();  // an image of one tile has no border
+  const Grid pixels_grid = on.grid(images * a.pblocks, kThreads);                       // flatten and apply
+  PRS_TRY(on.check());
   uint8_t* ws = static_cast<uint8_t*>(o.workspace);
   a.parent    = reinterpret_cast<int32_t*>(ws);
   a.size      = reinterpret_cast<int32_t*>(ws + up16(4 * pixels));
-  hipStream_t st = ctx_stream(ctx);
-  hipLaunchKernelGGL(speckle_tile_kernel, dim3((unsigned) tile_blocks), dim3(kThreads), 0, st, a);
-  if (seam_blocks > 0) {  // an image of one tile has no border
-    hipLaunchKernelGGL(speckle_seam_kernel, dim3((unsigned) seam_blocks), dim3(kThreads), 0, st, a);
+  on.launch(speckle_tile_kernel, tiles, 0, a);
+  if (seam) {
+    on.launch(speckle_seam_kernel, seam, 0, a);
   }
-  hipLaunchKernelGGL(speckle_flatten_kernel, dim3((unsigned) pixel_blocks), dim3(kThreads), 0, st, a);
-  hipLaunchKernelGGL(speckle_apply_kernel, dim3((unsigned) pixel_blocks), dim3(kThreads), 0, st, a);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    return ctx_fail_hip(ctx, e, "prs_speckle_batch_run launch");
-  }
-  return PRS_OK;
+  on.launch(speckle_flatten_kernel, pixels_grid, 0, a);
+  on.launch(speckle_apply_kernel, pixels_grid, 0, a);
+  return on.finish();
 }
 
 }  // namespace prs

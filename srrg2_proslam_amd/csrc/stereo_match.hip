@@ -742,6 +742,7 @@ struct StereoPlan : Plan {  // launch[0].kernel: an index into the v5 table when
 
 static StereoPlan stereo_plan(const prs_stereo_params& params, const prs_stereo_batch& batch, const DispatchEnv& env) {
   StereoPlan p;
+  p.too_large = "prs_stereo_match_batch: more work-items than one launch holds";
   if (batch.batch <= 0) {
     return p;
   }
@@ -757,7 +758,7 @@ static StereoPlan stereo_plan(const prs_stereo_params& params, const prs_stereo_
   p.epilogue = batch.fixed_uvuv && batch.fixed_desc && batch.n_fixed && batch.fixed_xyz && batch.triangulator;
   p.best_lim = accept_limit(params);
   // both generations are persistent where they stage: one workgroup per CU (the LDS footprint allows no more), frames strided over them
-  const unsigned persistent = batch.batch < env.cus ? batch.batch : env.cus;
+  const int64_t persistent = batch.batch < env.cus ? batch.batch : env.cus;
   // instruction-lean staged kernel for frames of <= 2048 keypoints (stereo_match_v5.hip)
   p.v5 = stereo_v5_layout(params, stride, p.epilogue, p.best_lim, env);
   if (p.v5.why == kV5Taken) {
@@ -832,12 +833,7 @@ int stereo_match_batch_launch(prs_context* ctx, const prs_stereo_params* params,
   }
   fill_accept_table(params, &a.best_lim, a.bmax);
   a.stamps     = ctx_stamps(ctx, (size_t) batch->batch * 16 * sizeof(unsigned long long));
-  auto kernel  = kStereoVariants[l.kernel].fn;
-  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int) l.lds);
-  if (e == hipSuccess) {
-    hipLaunchKernelGGL(kernel, dim3(l.grid_x), dim3(l.block), l.lds, ctx_stream(ctx), a);
-    e = hipGetLastError();
-  }
+  const hipError_t e = launch_planned(kStereoVariants[l.kernel].fn, l.grid, l.lds, ctx_stream(ctx), a, true);
   if (e != hipSuccess) {
     return ctx_fail_hip(ctx, e, "prs_stereo_match_batch launch");
   }
@@ -855,17 +851,8 @@ int triangulate_launch(prs_context* ctx, const prs_triangulator_params* params, 
   if (n <= 0) {
     return PRS_OK;
   }
-  int64_t blocks = (n + 255) / 256;
-  if (blocks > 2048) {
-    blocks = 2048;
-  }
-  hipLaunchKernelGGL(triangulate_kernel, dim3((unsigned) blocks), dim3(256), 0, ctx_stream(ctx), *params,
-                     reinterpret_cast<const float4*>(d_uvuv), n, reinterpret_cast<float4*>(d_xyz4));
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    return ctx_fail_hip(ctx, e, "prs_triangulate launch");
-  }
-  return PRS_OK;
+  return Launches(ctx, "prs_triangulate", ctx_stream(ctx)).one(n < 2048 * 256 ? (n + 255) / 256 : 2048, 256, triangulate_kernel,
+                                                               0, *params, reinterpret_cast<const float4*>(d_uvuv), n, reinterpret_cast<float4*>(d_xyz4));
 }
 
 } // namespace prs
@@ -882,8 +869,8 @@ extern "C" int prs_stereo_plan(const prs_stereo_params* params, const prs_stereo
   out->n_launches = p.n_launches;
   if (p.n_launches) {
     const prs::Plan::Launch& l = p.launch[0];
-    out->launch[0] = {prs::stereo_kernel_name(v5 ? l.kernel : prs::kStereoV5Variants + l.kernel), (int32_t) l.grid_x, (int32_t) l.grid_y, (int32_t) l.block,
-                      (uint32_t) l.lds};
+    out->launch[0] = {prs::stereo_kernel_name(v5 ? l.kernel : prs::kStereoV5Variants + l.kernel), (int32_t) l.grid.x(), (int32_t) l.grid.y(),
+                      (int32_t) l.grid.threads(), (uint32_t) l.lds};
   }
   int32_t* f = out->fact;
   f[PRS_PLAN_STEREO_V5] = p.n_launches && v5, f[PRS_PLAN_STEREO_V5_WHY] = p.v5.why, f[PRS_PLAN_STEREO_CAP] = p.v5.cap;

@@ -864,13 +864,8 @@ int stereo_match_v5_launch(prs_context* ctx, const prs_stereo_params* params, co
   }
   fill_accept_table(params, &a.best_lim, a.bmax);
   a.stamps           = ctx_stamps(ctx, (size_t) batch->batch * 16 * sizeof(unsigned long long));
-  auto kernel        = kV5Variants[launch.kernel].fn;
-  hipError_t e       = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int) launch.lds);
-  if (e == hipSuccess) {
-    // persistent: one workgroup per CU (the LDS footprint allows no more), frames strided over them
-    hipLaunchKernelGGL(kernel, dim3(launch.grid_x), dim3(launch.block), launch.lds, ctx_stream(ctx), a);
-    e = hipGetLastError();
-  }
+  // persistent: one workgroup per CU (the LDS footprint allows no more), frames strided over them
+  const hipError_t e = launch_planned(kV5Variants[launch.kernel].fn, launch.grid, launch.lds, ctx_stream(ctx), a, true);
   if (e != hipSuccess) {
     return ctx_fail_hip(ctx, e, "prs_stereo_match_batch launch");
   }

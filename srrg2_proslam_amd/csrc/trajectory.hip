@@ -786,16 +786,15 @@ int trajectory_eval_launch(prs_context* ctx, const prs_trajectory_params* params
   a.stage_clouds      = clouds <= kStageLimit;
   a.stage_dist        = p.kitti_step > 0 && clouds + dist <= kStageLimit;
   const size_t lds    = a.stage_clouds ? clouds + (a.stage_dist ? dist : 0) : 0;
-  hipError_t e = allow_lds(trajectory_eval_kernel, lds);
+  Launches on(ctx, "prs_trajectory_eval_batch", ctx_stream(ctx));
+  const Grid grid = on.grid(t.batch, kThreads);
+  PRS_TRY(on.check());
+  const hipError_t e = allow_lds(trajectory_eval_kernel, lds);
   if (e != hipSuccess) {
     return ctx_fail_hip(ctx, e, "prs_trajectory_eval_batch: LDS request");
   }
-  hipLaunchKernelGGL(trajectory_eval_kernel, dim3((unsigned) t.batch), dim3(kThreads), lds, ctx_stream(ctx), a);
-  e = hipGetLastError();
-  if (e != hipSuccess) {
-    return ctx_fail_hip(ctx, e, "prs_trajectory_eval_batch launch");
-  }
-  return PRS_OK;
+  on.launch(trajectory_eval_kernel, grid, lds, a);
+  return on.finish();
 }
 
 }  // namespace prs

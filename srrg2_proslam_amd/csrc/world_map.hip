@@ -497,15 +497,22 @@ int world_map_launch(prs_context* ctx, const prs_world_map_params* params, const
   }
   const long long M = (long long) ar.slot_stride + 1, C = ((long long) s.capacity + kChunk - 1) / kChunk;
   const long long blocks = (long long) s.batch * M * C;
-  if (!grid_fits(blocks, kThreads) || M * (long long) s.capacity > 0x7fffffffll) {
-    return ctx_fail(ctx, PRS_ERR_UNSUPPORTED, (who + ": batch * (slot_stride + 1) * chunks beyond the work-items of one launch, or a sequence's rows beyond 2^31").c_str());
+  if (M * (long long) s.capacity > 0x7fffffffll) {
+    return ctx_fail(ctx, PRS_ERR_UNSUPPORTED, (who + ": a sequence's rows beyond 2^31").c_str());
   }
+  const auto wide  = [](long long items) { return (int) std::min<long long>(kWideThreads, (items + PRS_WAVE - 1) / PRS_WAVE * PRS_WAVE); };
+  const bool write = o.xyz != nullptr;
+  Launches on(ctx, who.c_str(), ctx_stream(ctx));
+  const Grid chunks = on.grid(blocks, kThreads);  // count and scatter: batch * (slot_stride + 1) * chunks
+  const Grid scan   = on.grid(s.batch, wide(s.node_stride));
+  const Grid bounds = write && o.bounds ? on.grid(s.batch, wide(M * C)) : Grid();
+  PRS_TRY(on.check());
   WorldMapArgs a = {};
   a.p = *params;
   a.o = o;
   a.batch = s.batch, a.capacity = s.capacity, a.node_stride = s.node_stride, a.slot_stride = ar.slot_stride;
   a.maps = (int32_t) M, a.chunks = (int32_t) C;
-  a.write_out     = o.xyz != nullptr;
+  a.write_out     = write;
   a.live_coords   = s.coords;
   a.live_desc     = s.desc;
   a.live_n_points = s.n_points;
@@ -527,21 +534,15 @@ int world_map_launch(prs_context* ctx, const prs_world_map_params* params, const
   a.ws_nonfinite  = ws + blocks;
   a.ws_bounds     = reinterpret_cast<float*>(ws + 2 * blocks);
   a.ws_node       = ws + 8 * blocks;
-  hipStream_t st  = ctx_stream(ctx);
-  hipLaunchKernelGGL(world_map_count_kernel, dim3((unsigned) blocks), dim3(kThreads), 0, st, a);
-  const auto wide = [](long long items) { return (unsigned) std::min<long long>(kWideThreads, (items + PRS_WAVE - 1) / PRS_WAVE * PRS_WAVE); };
-  hipLaunchKernelGGL(world_map_scan_kernel, dim3((unsigned) s.batch), dim3(wide(s.node_stride)), 0, st, a);
-  if (a.write_out || refresh) {
-    hipLaunchKernelGGL(world_map_scatter_kernel, dim3((unsigned) blocks), dim3(kThreads), 0, st, a);
+  on.launch(world_map_count_kernel, chunks, 0, a);
+  on.launch(world_map_scan_kernel, scan, 0, a);
+  if (write || refresh) {
+    on.launch(world_map_scatter_kernel, chunks, 0, a);
   }
-  if (a.write_out && o.bounds) {
-    hipLaunchKernelGGL(world_map_bounds_kernel, dim3((unsigned) s.batch), dim3(wide(M * C)), 0, st, a);
+  if (bounds) {
+    on.launch(world_map_bounds_kernel, bounds, 0, a);
   }
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    return ctx_fail_hip(ctx, e, "prs_world_map_batch_run launch");
-  }
-  return PRS_OK;
+  return on.finish();
 }
 
 }  // namespace prs

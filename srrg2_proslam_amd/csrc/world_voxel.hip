@@ -385,9 +385,11 @@ int world_voxel_launch(prs_context* ctx, const prs_world_voxel_params* params, c
   }
   const long long C = chunks_of(o.in_stride), TC = chunks_of(o.table_stride);
   const long long blocks = (long long) o.batch * C, clear_blocks = (long long) o.batch * TC;
-  if (!grid_fits(blocks, kThreads) || !grid_fits(clear_blocks, kThreads)) {  // (the scan has at most 64 * C threads a sequence)
-    return ctx_fail(ctx, PRS_ERR_UNSUPPORTED, (who + ": batch * ceil(in_stride / 256) or batch * ceil(table_stride / 256) beyond the work-items of one launch").c_str());
-  }
+  const int wide = (int) std::min<long long>(kWideThreads, ((C + kCompactBatch - 1) / kCompactBatch + PRS_WAVE - 1) / PRS_WAVE * PRS_WAVE);
+  Launches on(ctx, who.c_str(), ctx_stream(ctx));
+  const Grid clear = on.grid(clear_blocks, kThreads), chunks = on.grid(blocks, kThreads);  // (chunks: insert, flag and scatter)
+  const Grid scan  = on.grid(o.batch, wide);
+  PRS_TRY(on.check());
   WorldVoxelArgs a = {};
   a.p = *params;
   a.o = o;
@@ -399,20 +401,14 @@ int world_voxel_launch(prs_context* ctx, const prs_world_voxel_params* params, c
   a.drops        = reinterpret_cast<Drops*>(ws + l.table);
   a.ws_slot      = reinterpret_cast<int32_t*>(ws + l.table + l.drops);
   a.ws_count     = reinterpret_cast<int32_t*>(ws + l.table + l.drops + l.slots);
-  hipStream_t st = ctx_stream(ctx);
-  hipLaunchKernelGGL(world_voxel_clear_kernel, dim3((unsigned) clear_blocks), dim3(kThreads), 0, st, a);
-  hipLaunchKernelGGL(world_voxel_insert_kernel, dim3((unsigned) blocks), dim3(kThreads), 0, st, a);
-  hipLaunchKernelGGL(world_voxel_flag_kernel, dim3((unsigned) blocks), dim3(kThreads), 0, st, a);
-  const unsigned wide = (unsigned) std::min<long long>(kWideThreads, ((C + kCompactBatch - 1) / kCompactBatch + PRS_WAVE - 1) / PRS_WAVE * PRS_WAVE);
-  hipLaunchKernelGGL(world_voxel_scan_kernel, dim3((unsigned) o.batch), dim3(wide), 0, st, a);
+  on.launch(world_voxel_clear_kernel, clear, 0, a);
+  on.launch(world_voxel_insert_kernel, chunks, 0, a);
+  on.launch(world_voxel_flag_kernel, chunks, 0, a);
+  on.launch(world_voxel_scan_kernel, scan, 0, a);
   if (a.write_out) {
-    hipLaunchKernelGGL(world_voxel_scatter_kernel, dim3((unsigned) blocks), dim3(kThreads), 0, st, a);
+    on.launch(world_voxel_scatter_kernel, chunks, 0, a);
   }
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    return ctx_fail_hip(ctx, e, "prs_world_voxel_batch_run launch");
-  }
-  return PRS_OK;
+  return on.finish();
 }
 
 }  // namespace prs
