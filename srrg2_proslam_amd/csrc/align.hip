@@ -2770,10 +2770,6 @@ __global__ void gn_step_kernel(const float* H, const float* b, float damping, in
   *ok = r ? 1 : 0;
 }
 
-static inline uint32_t align_up16(uint32_t v) {
-  return (v + 15u) / 16u * 16u;
-}
-
 // an enqueued batch of the split pipeline (kept in the context between align_batch_launch and align_batch_finish)
 struct SplitJob {
   bool active = false;
@@ -2924,22 +2920,22 @@ static AlignPlan align_plan(const prs_pcf_params& finder, const prs_aligner_para
   const uint32_t cs_entries = kdtree && nf + 4u > (uint32_t) g.ncells + 2u ? nf + 4u : (uint32_t) g.ncells + 2u;
   auto carve = [&](AlignArgs& g, bool with_operands) -> size_t {
     uint32_t off = 0;
-    g.off_db       = off; off = align_up16(off + (nf + 1) * 8);  // (+ the sentinel entry behind the last one: the scan reads one entry past a segment)
-    g.off_inv      = off; off = align_up16(off + nf * 2);
-    g.off_cellstart = off; off = align_up16(off + cs_entries * 2);
-    g.off_cfix     = off; off = align_up16(off + (with_operands ? nf * 16 : 0));
-    g.off_cmov     = off; off = align_up16(off + (with_operands ? nf * 16 : 0));
-    g.off_cls      = off; off = align_up16(off + (with_operands ? nf : 0));
-    g.off_sh       = off; off = align_up16(off + (uint32_t) sizeof(AlignShared));
+    g.off_db       = off; off = up16(off + (nf + 1) * 8);  // (+ the sentinel entry behind the last one: the scan reads one entry past a segment)
+    g.off_inv      = off; off = up16(off + nf * 2);
+    g.off_cellstart = off; off = up16(off + cs_entries * 2);
+    g.off_cfix     = off; off = up16(off + (with_operands ? nf * 16 : 0));
+    g.off_cmov     = off; off = up16(off + (with_operands ? nf * 16 : 0));
+    g.off_cls      = off; off = up16(off + (with_operands ? nf : 0));
+    g.off_sh       = off; off = up16(off + (uint32_t) sizeof(AlignShared));
     g.off_u        = off;
     // search-phase arrays
     uint32_t u = off;
-    g.off_fdesc  = u; u = align_up16(u + nf * 32);
-    g.off_fuv    = u; u = align_up16(u + (kdtree ? nf * 8 : 0));
-    g.off_best   = u; u = align_up16(u + nf * 4);
-    g.off_second = u; u = align_up16(u + nf * 4);
-    g.off_lut    = u; u = align_up16(u + lut_cap * 2);
-    g.off_surv   = u; u = align_up16(u + (uint32_t) (with_operands ? kAlignThreads : kSearchThreads) * (uint32_t) g.surv_slots * 2);  // slots x u16 per thread
+    g.off_fdesc  = u; u = up16(u + nf * 32);
+    g.off_fuv    = u; u = up16(u + (kdtree ? nf * 8 : 0));
+    g.off_best   = u; u = up16(u + nf * 4);
+    g.off_second = u; u = up16(u + nf * 4);
+    g.off_lut    = u; u = up16(u + lut_cap * 2);
+    g.off_surv   = u; u = up16(u + (uint32_t) (with_operands ? kAlignThreads : kSearchThreads) * (uint32_t) g.surv_slots * 2);  // slots x u16 per thread
     // GN-phase terms; the region also serves the database build and the disparity column
     g.off_terms = off;
     uint32_t terms_bytes       = kTerms * kAlignThreads * 4;
@@ -2952,7 +2948,7 @@ static AlignPlan align_plan(const prs_pcf_params& finder, const prs_aligner_para
     if (kdtree && kd_bytes > terms_bytes) {
       terms_bytes = kd_bytes;
     }
-    const uint32_t t_end = align_up16(off + terms_bytes);
+    const uint32_t t_end = up16(off + terms_bytes);
     return u > t_end ? u : t_end;
   };
   g.surv_slots     = 4;
@@ -2994,7 +2990,7 @@ static AlignPlan align_plan(const prs_pcf_params& finder, const prs_aligner_para
     }
   }
   // image of the lattice arrays (contiguous in LDS: db | inv | cellstart), kept per frame between search launches
-  gs.db_blob = align_up16(gs.off_cellstart + cs_entries * 2) - gs.off_db;
+  gs.db_blob = up16(gs.off_cellstart + cs_entries * 2) - gs.off_db;
   // two waves per frame (eight frames resident per CU: the kernel is bound by its single-wave phases and by
   // instruction issue, more independent frames fill the idle slots)
   p.add(find_variant(kAlignVariants, {kSearchThreads, 1, finder.search_type, gs.surv_slots}), batch.batch, 1, kSearchThreads, lds_search);

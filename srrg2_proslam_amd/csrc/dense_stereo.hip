@@ -27,6 +27,7 @@
 
 #include "prs_device.h"
 #include "prs_host.h"
+#include "prs_image.h"
 
 namespace prs {
 
@@ -39,8 +40,6 @@ constexpr int kGroup      = 4;   // disparity pairs a wave takes between two wav
 constexpr int kFinishRows = 8;   // rows of a finish workgroup
 constexpr int kCensusRows = 16;  // the census tile is PRS_WAVE x kCensusRows
 constexpr int kHaloX = 4, kHaloY = 3;
-constexpr uint32_t kNoCost = 0xffffu;      // above every aggregated cost
-constexpr uint32_t kNoBest = 0xffffffffu;  // above every (cost << 16) | i
 
 struct DenseStereoArgs {
   prs_dense_stereo_params p;
@@ -57,23 +56,6 @@ struct DenseStereoArgs {
   int16_t* win_r;       // [images][rows][cols] i* of the right pixel or -1 (lr_max_diff >= 0 only)
 };
 
-__device__ __forceinline__ int clampi(const int v, const int lo, const int hi) {
-  return v < lo ? lo : (v > hi ? hi : v);
-}
-
-// the images of sequence b the call works on; -1 when n_images[b] is out of range (the sequence is refused)
-__device__ __forceinline__ int images_of(const DenseStereoArgs& a, const int b) {
-  const int n = a.o.n_images ? a.o.n_images[b] : a.o.frames;
-  return (n < 0 || n > a.o.frames) ? -1 : n;
-}
-
-// LDS written by one lane is read by other lanes of the wave
-__device__ __forceinline__ void wave_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
 // ---- census: blockIdx.x = ((image * 2 + side) * ctiles_y + ty) * ctiles_x + tx ----------------------------------------------------
 __global__ __launch_bounds__(kThreads) void dense_census_kernel(const DenseStereoArgs a) {
   constexpr int W = PRS_WAVE + 2 * kHaloX, H = kCensusRows + 2 * kHaloY;
@@ -86,8 +68,8 @@ __global__ __launch_bounds__(kThreads) void dense_census_kernel(const DenseStere
   id /= (uint32_t) a.ctiles_y;
   const int side       = (int) (id & 1u);
   const uint32_t image = id >> 1;
-  const int f = (int) (image % (uint32_t) a.o.frames), b = (int) (image / (uint32_t) a.o.frames);
-  const int n_img  = images_of(a, b);
+  const int f = frame_of(image, a.o.frames), b = sequence_of(image, a.o.frames);
+  const int n_img  = images_of(a.o, b);
   const bool first = side == 0 && tx == 0 && ty == 0 && tid == 0;
   if (first && f == 0) {
     a.o.status[b] = n_img < 0 ? PRS_ERR_RANGE : PRS_OK;
@@ -163,8 +145,7 @@ __global__ __launch_bounds__(kThreads) void dense_match_kernel(const DenseStereo
   id /= (uint32_t) a.tiles;
   const int band       = (int) (id % (uint32_t) a.bands);
   const uint32_t image = id / (uint32_t) a.bands;
-  const int f = (int) (image % (uint32_t) a.o.frames), b = (int) (image / (uint32_t) a.o.frames);
-  if (f >= images_of(a, b)) {
+  if (!image_served(a.o, image)) {
     return;
   }
   const int rows = a.o.rows, cols = a.o.cols;
@@ -200,7 +181,7 @@ __global__ __launch_bounds__(kThreads) void dense_match_kernel(const DenseStereo
     const uint64_t ref_e = ref[(size_t) enter * (size_t) cols + xc];
     const uint64_t ref_l = leave ? ref[(size_t) leaving * (size_t) cols + xc] : 0;
     __syncthreads();
-    uint32_t best = kNoBest;
+    uint32_t best = kStereoNoBest;
     // kGroup pairs between two wave syncs: their LDS round trips overlap
     for (int dp0 = w; dp0 < npairs; dp0 += kWaves * kGroup) {
 #pragma unroll
@@ -251,17 +232,16 @@ __global__ __launch_bounds__(kThreads) void dense_match_kernel(const DenseStereo
     s_best[tid] = best;
     __syncthreads();
     best = min(min(s_best[lane], s_best[PRS_WAVE + lane]), min(s_best[2 * PRS_WAVE + lane], s_best[3 * PRS_WAVE + lane]));
-    const bool has  = best != kNoBest;
     const int istar = (int) (best & 0xffffu);
     const size_t px = at_image + (size_t) (v0 + t) * (size_t) cols + (size_t) u;
     if (RIGHT) {
       if (w == 0 && out) {
-        a.win_r[px] = has ? (int16_t) istar : (int16_t) -1;
+        a.win_r[px] = best != kStereoNoBest ? (int16_t) istar : (int16_t) -1;
       }
       continue;
     }
     // the least cost two or more disparities away from the winner
-    uint32_t a2 = kNoCost;
+    uint32_t a2 = kStereoNoCost;
     for (int dp = w; dp < npairs; dp += kWaves) {
       const uint32_t A = s_A[dp * PRS_WAVE + lane];
       const int i      = 2 * dp;
@@ -276,26 +256,13 @@ __global__ __launch_bounds__(kThreads) void dense_match_kernel(const DenseStereo
     __syncthreads();
     if (w == 0 && out) {
       a2 = min(min(s_a2[lane], s_a2[PRS_WAVE + lane]), min(s_a2[2 * PRS_WAVE + lane], s_a2[3 * PRS_WAVE + lane]));
-      float s = 0.0f;
-      if (has) {
-        const int A0    = (int) (best >> 16);
-        const int q     = a.p.uniqueness_percent;
-        const bool keep = q == 0 || a2 == kNoCost || 100 * A0 < (100 - q) * (int) a2;
-        if (keep) {
-          float delta = 0.0f;
-          if (istar >= 1 && istar + 1 < i_end) {  // both neighbours in the range and admissible
-            const uint32_t wm = s_A[((istar - 1) >> 1) * PRS_WAVE + lane], wp = s_A[((istar + 1) >> 1) * PRS_WAVE + lane];
-            const int Am  = (int) (((istar - 1) & 1) ? wm >> 16 : wm & 0xffffu);
-            const int Ap  = (int) (((istar + 1) & 1) ? wp >> 16 : wp & 0xffffu);
-            const int den = (Am + Ap) - 2 * A0;
-            if (den > 0) {
-              delta = (float) (Am - Ap) / (float) (2 * den);
-            }
-          }
-          s = (float) (d0 + istar) + delta;
-        }
+      int Am = 0, Ap = 0;  // the winner's neighbours, read where both are in the range and admissible
+      if (istar >= 1 && istar + 1 < i_end) {
+        const uint32_t wm = s_A[((istar - 1) >> 1) * PRS_WAVE + lane], wp = s_A[((istar + 1) >> 1) * PRS_WAVE + lane];
+        Am = (int) (((istar - 1) & 1) ? wm >> 16 : wm & 0xffffu);
+        Ap = (int) (((istar + 1) & 1) ? wp >> 16 : wp & 0xffffu);
       }
-      a.rec_l[px] = make_uint2(__float_as_uint(s), has ? (uint32_t) istar : 0xffffffffu);
+      a.rec_l[px] = stereo_winner_record(best, a2, Am, Ap, i_end, d0, a.p.uniqueness_percent);
     }
   }
 }
@@ -313,8 +280,7 @@ __global__ __launch_bounds__(kThreads) void dense_finish_kernel(const DenseStere
   const int tid        = threadIdx.x;
   const int block      = (int) (blockIdx.x % (uint32_t) a.fblocks);
   const uint32_t image = blockIdx.x / (uint32_t) a.fblocks;
-  const int f = (int) (image % (uint32_t) a.o.frames), b = (int) (image / (uint32_t) a.o.frames);
-  if (f >= images_of(a, b)) {
+  if (!image_served(a.o, image)) {
     return;
   }
   const int cols = a.o.cols, v0 = block * kFinishRows;
@@ -363,29 +329,43 @@ __global__ __launch_bounds__(kThreads) void dense_finish_kernel(const DenseStere
   }
 }
 
-// the parts of the workspace, in bytes; pixels 0 when a size is not one the launcher takes
-struct Layout {
-  uint64_t pixels, census, rec, right, total;
-};
+}  // namespace
 
-Layout layout_of(const int64_t batch, const int64_t frames, const int64_t rows, const int64_t cols, const int64_t n_disparities, const bool lr) {
-  Layout l = {};
-  if (batch < 1 || frames < 1 || rows < 1 || cols < 1 || n_disparities < 1 || n_disparities > 256) {
+DenseLayout dense_layout_of(const int64_t batch, const int64_t frames, const int64_t rows, const int64_t cols, const int64_t n_disparities, const bool lr) {
+  DenseLayout l = {};
+  if (n_disparities < 1 || n_disparities > 256) {
     return l;
   }
-  if (batch * frames > 0x7fffffffll || rows * cols > 0x7fffffffll || batch * frames * rows * cols > 0x7fffffffll) {  // each below 2^62
-    return l;
-  }
-  const auto up = [](const uint64_t v) { return (v + 15) & ~(uint64_t) 15; };
-  l.pixels = (uint64_t) (batch * frames * rows * cols);
-  l.census = up(8 * l.pixels);
-  l.rec    = up(8 * l.pixels);
-  l.right  = lr ? up(2 * l.pixels) : 0;
+  l.pixels = image_pixels(batch, frames, rows, cols);
+  l.census = up16(8 * l.pixels);
+  l.rec    = up16(8 * l.pixels);
+  l.right  = lr ? up16(2 * l.pixels) : 0;
   l.total  = 2 * l.census + l.rec + l.right;
   return l;
 }
 
-}  // namespace
+int stereo_call_check(prs_context* ctx, const std::string& who, const prs_dense_stereo_params& p, const prs_dense_stereo_batch& o,
+                      const bool stage_ok, const char* stage_rule, const int64_t stage_size, const char* stage_size_name) {
+  if (!o.left || !o.right || !o.status || !o.workspace || (!o.disparity && !o.depth)) {
+    return ctx_fail(ctx, PRS_ERR_NULL, (who + ": left, right, status or the workspace not set, or neither disparity nor depth").c_str());
+  }
+  if (p.n_disparities < 1 || p.n_disparities > 256 || p.min_disparity < 0 || p.min_disparity + p.n_disparities > 4096 || !stage_ok ||
+      p.uniqueness_percent < 0 || p.uniqueness_percent > 99 || p.lr_max_diff < -1 || p.lr_max_diff > 255 || !std::isfinite(p.bf) || !(p.bf > 0.0f)) {
+    return ctx_fail(ctx, PRS_ERR_RANGE, (who + ": n_disparities outside 1..256, min_disparity below 0 or min_disparity + n_disparities above 4096, " + stage_rule + ", uniqueness_percent outside 0..99, lr_max_diff outside -1..255, or bf not finite and positive").c_str());
+  }
+  if (o.batch < 1 || o.frames < 1 || o.rows < 1 || o.cols < 1 || stage_size < 1 || o.left_pitch < o.cols || o.right_pitch < o.cols ||
+      !pitch_ok(o.out_pitch, o.cols, 4)) {
+    return ctx_fail(ctx, PRS_ERR_RANGE, (who + ": a size" + stage_size_name + " below 1, an image pitch below cols, or out_pitch below cols floats or not a multiple of 4").c_str());
+  }
+  if (!aligned_to(o.disparity, 4) || !aligned_to(o.depth, 4) || !aligned_to(o.workspace, 16) || !aligned_to(o.n_images, 4) ||
+      !aligned_to(o.n_valid, 4) || !aligned_to(o.status, 4)) {
+    return ctx_fail(ctx, PRS_ERR_UNSUPPORTED, (who + ": the workspace must be 16-byte aligned, the other arrays but the images 4-byte").c_str());
+  }
+  if (image_pixels(o.batch, o.frames, o.rows, o.cols) < 1) {
+    return ctx_fail(ctx, PRS_ERR_UNSUPPORTED, (who + ": batch * frames * rows * cols beyond 2^31 - 1").c_str());
+  }
+  return PRS_OK;
+}
 
 // the census and the finish launch for the stages that share them (sgm_stereo.hip): the caller has checked the batch, declared
 // *_blocks workgroups of kDenseThreads among its launches and checked those
@@ -434,27 +414,9 @@ int dense_stereo_launch(prs_context* ctx, const prs_dense_stereo_params* params,
   }
   const prs_dense_stereo_params& p = *params;
   const prs_dense_stereo_batch& o  = *batch;
-  if (!o.left || !o.right || !o.status || !o.workspace || (!o.disparity && !o.depth)) {
-    return ctx_fail(ctx, PRS_ERR_NULL, (who + ": left, right, status or the workspace not set, or neither disparity nor depth").c_str());
-  }
-  if (p.n_disparities < 1 || p.n_disparities > 256 || p.min_disparity < 0 || p.min_disparity + p.n_disparities > 4096 ||
-      p.aggregation_radius < 0 || p.aggregation_radius > 7 || p.uniqueness_percent < 0 || p.uniqueness_percent > 99 || p.lr_max_diff < -1 ||
-      p.lr_max_diff > 255 || !std::isfinite(p.bf) || !(p.bf > 0.0f)) {
-    return ctx_fail(ctx, PRS_ERR_RANGE, (who + ": n_disparities outside 1..256, min_disparity below 0 or min_disparity + n_disparities above 4096, aggregation_radius outside 0..7, uniqueness_percent outside 0..99, lr_max_diff outside -1..255, or bf not finite and positive").c_str());
-  }
-  if (o.batch < 1 || o.frames < 1 || o.rows < 1 || o.cols < 1 || o.left_pitch < o.cols || o.right_pitch < o.cols || o.out_pitch % 4 != 0 ||
-      (int64_t) o.out_pitch < (int64_t) o.cols * 4) {
-    return ctx_fail(ctx, PRS_ERR_RANGE, (who + ": a size below 1, an image pitch below cols, or out_pitch below cols floats or not a multiple of 4").c_str());
-  }
-  if (!aligned_to(o.disparity, 4) || !aligned_to(o.depth, 4) || !aligned_to(o.workspace, 16) || !aligned_to(o.n_images, 4) ||
-      !aligned_to(o.n_valid, 4) || !aligned_to(o.status, 4)) {
-    return ctx_fail(ctx, PRS_ERR_UNSUPPORTED, (who + ": the workspace must be 16-byte aligned, the other arrays but the images 4-byte").c_str());
-  }
-  const bool lr  = p.lr_max_diff >= 0;
-  const Layout l = layout_of(o.batch, o.frames, o.rows, o.cols, p.n_disparities, lr);
-  if (l.pixels < 1) {
-    return ctx_fail(ctx, PRS_ERR_UNSUPPORTED, (who + ": batch * frames * rows * cols beyond 2^31 - 1").c_str());
-  }
+  PRS_TRY(stereo_call_check(ctx, who, p, o, p.aggregation_radius >= 0 && p.aggregation_radius <= 7, "aggregation_radius outside 0..7"));
+  const bool lr       = p.lr_max_diff >= 0;
+  const DenseLayout l = dense_layout_of(o.batch, o.frames, o.rows, o.cols, p.n_disparities, lr);
   DenseStereoArgs a = {};
   a.p = p;
   a.o = o;
@@ -504,7 +466,7 @@ void prs_dense_stereo_struct_sizes(uint64_t* sizes2) {
 }
 
 uint64_t prs_dense_stereo_workspace_bytes(int32_t batch, int32_t frames, int32_t rows, int32_t cols, int32_t n_disparities, int32_t lr_check) {
-  return layout_of(batch, frames, rows, cols, n_disparities, lr_check != 0).total;
+  return dense_layout_of(batch, frames, rows, cols, n_disparities, lr_check != 0).total;
 }
 
 int prs_dense_stereo_batch_run(prs_context* ctx, const prs_dense_stereo_params* params, const prs_dense_stereo_batch* batch) {

@@ -20,6 +20,7 @@
 #include "prs_depth.h"
 #include "prs_device.h"
 #include "prs_host.h"
+#include "prs_image.h"
 #include "prs_se3.h"
 
 namespace prs {
@@ -61,7 +62,7 @@ __global__ __launch_bounds__(kThreads) void depth_cloud_kernel(const DepthCloudA
   const uint32_t cf = (uint32_t) a.chunks_per_frame;
   const uint32_t image = id / cf;  // b * frames + f
   const int c = (int) (id % cf);
-  const int f = (int) (image % (uint32_t) a.o.frames), b = (int) (image / (uint32_t) a.o.frames);
+  const int f = frame_of(image, a.o.frames), b = sequence_of(image, a.o.frames);
   int base = 0;
   if (SCATTER) {
     base = __builtin_amdgcn_readfirstlane(a.ws_count[id]);
@@ -300,17 +301,17 @@ int depth_cloud_launch(prs_context* ctx, const prs_depth_cloud_params* params, c
   if (!o.depth || !o.n_images || !o.pose || !o.n_out || !o.n_total || !o.n_skipped || !o.status || !o.workspace) {
     return ctx_fail(ctx, PRS_ERR_NULL, (who + ": depth, n_images, pose, a per-sequence output or the workspace not set").c_str());
   }
-  if (p.depth_type != PRS_DEPTH_U16 && p.depth_type != PRS_DEPTH_F32) {
+  const int64_t elem = depth_bytes(p.depth_type);
+  if (elem == 0) {
     return ctx_fail(ctx, PRS_ERR_UNSUPPORTED, (who + ": unknown depth_type").c_str());
   }
-  const int64_t elem = p.depth_type == PRS_DEPTH_U16 ? 2 : 4;
   bool finite        = std::isfinite(p.depth_scaling_factor_to_meters) && std::isfinite(p.fx) && std::isfinite(p.fy) && std::isfinite(p.cx) &&
                 std::isfinite(p.cy) && std::isfinite(p.range_min) && std::isfinite(p.range_max);
   for (int i = 0; i < 16; ++i) {
     finite = finite && std::isfinite(p.sensor_in_robot[i]);
   }
-  if (o.batch < 1 || o.frames < 1 || o.rows < 1 || o.cols < 1 || o.pose_stride < 1 || p.step < 1 || o.pitch % elem != 0 ||
-      (int64_t) o.pitch < (int64_t) o.cols * elem || (o.gray && o.gray_pitch < o.cols) || !finite || !(p.depth_scaling_factor_to_meters > 0.0f) ||
+  if (o.batch < 1 || o.frames < 1 || o.rows < 1 || o.cols < 1 || o.pose_stride < 1 || p.step < 1 || !pitch_ok(o.pitch, o.cols, elem) ||
+      (o.gray && o.gray_pitch < o.cols) || !finite || !(p.depth_scaling_factor_to_meters > 0.0f) ||
       p.range_min < 0.0f || p.range_min > p.range_max || (o.xyz && o.out_stride < 1)) {
     return ctx_fail(ctx, PRS_ERR_RANGE, (who + ": a size or step below 1, a pitch below the row's bytes or not a multiple of the element, a parameter not finite, a scale not positive, range_min negative or above range_max, or out_stride below 1 with xyz set").c_str());
   }

@@ -18,6 +18,7 @@
 #include "prs_depth.h"
 #include "prs_device.h"
 #include "prs_host.h"
+#include "prs_image.h"
 #include "prs_se3.h"
 
 namespace prs {
@@ -189,7 +190,7 @@ __global__ __launch_bounds__(kThreads) void depth_consistency_filter_kernel(cons
     if (state == kImageFiltered) {
       float p[3];
       depth_point(u, v, d, a.p.fx, a.p.fy, a.p.cx, a.p.cy, p);
-      const int f = (int) (image % (uint32_t) a.o.frames);
+      const int f = frame_of(image, a.o.frames);
       const int window = a.p.window;
       for (int s = 0; s < slots; ++s) {
         const float* M = reinterpret_cast<const float*>(s_rec + s * kRecWords);
@@ -276,10 +277,10 @@ int depth_consistency_launch(prs_context* ctx, const prs_depth_consistency_param
   if (!o.depth || !o.pose || !o.out || !o.status || !o.workspace) {
     return ctx_fail(ctx, PRS_ERR_NULL, (who + ": depth, pose, out, status or the workspace not set").c_str());
   }
-  if (p.depth_type != PRS_DEPTH_U16 && p.depth_type != PRS_DEPTH_F32) {
+  const int64_t elem = depth_bytes(p.depth_type);
+  if (elem == 0) {
     return ctx_fail(ctx, PRS_ERR_UNSUPPORTED, (who + ": unknown depth_type").c_str());
   }
-  const int64_t elem = p.depth_type == PRS_DEPTH_U16 ? 2 : 4;
   bool finite        = std::isfinite(p.depth_scaling_factor_to_meters) && std::isfinite(p.fx) && std::isfinite(p.fy) && std::isfinite(p.cx) &&
                 std::isfinite(p.cy) && std::isfinite(p.range_min) && std::isfinite(p.range_max) && std::isfinite(p.max_rel_diff);
   for (int i = 0; i < 16; ++i) {
@@ -287,8 +288,8 @@ int depth_consistency_launch(prs_context* ctx, const prs_depth_consistency_param
   }
   if (o.batch < 1 || o.frames < 1 || o.rows < 1 || o.cols < 1 || o.pose_stride < 1 || p.window < 1 || p.window > kMaxSlots / 2 || p.stride < 1 ||
       p.min_support < 0 || p.min_support > kMaxSlots || p.max_violation < 0 || p.max_violation > kMaxSlots || !finite || p.max_rel_diff < 0.0f ||
-      !(p.depth_scaling_factor_to_meters > 0.0f) || p.range_min < 0.0f || p.range_min > p.range_max || o.pitch % elem != 0 ||
-      (int64_t) o.pitch < (int64_t) o.cols * elem || o.out_pitch % elem != 0 || (int64_t) o.out_pitch < (int64_t) o.cols * elem ||
+      !(p.depth_scaling_factor_to_meters > 0.0f) || p.range_min < 0.0f || p.range_min > p.range_max || !pitch_ok(o.pitch, o.cols, elem) ||
+      !pitch_ok(o.out_pitch, o.cols, elem) ||
       ((o.support || o.violation) && o.count_pitch < o.cols)) {
     return ctx_fail(ctx, PRS_ERR_RANGE, (who + ": a size or stride below 1, window outside 1 .. 8, min_support or max_violation outside 0 .. 16, a parameter not finite, max_rel_diff below 0, a scale not positive, range_min negative or above range_max, or a pitch below the row's bytes or not a multiple of the element").c_str());
   }

@@ -84,10 +84,6 @@ __device__ __forceinline__ uint32_t bytes_odd(uint32_t x) { return __builtin_amd
 __device__ __forceinline__ uint32_t nonzero_bytes(uint32_t w) {  // bit j <=> byte j of the word is non-zero
   return ((w & 0xffu) ? 1u : 0u) | ((w & 0xff00u) ? 2u : 0u) | ((w & 0xff0000u) ? 4u : 0u) | ((w & 0xff000000u) ? 8u : 0u);
 }
-__device__ __forceinline__ void wave_sync_lds() {
-  __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");  // LDS written by one lane is read by other lanes of the wave
-  __builtin_amdgcn_wave_barrier();
-}
 
 constexpr int kTileWords  = kTilePitch / 4;   // 18 words per tile row
 constexpr int kTileRows   = kTileH + 8;       // 4-px halo above and below
@@ -733,7 +729,7 @@ __device__ __forceinline__ int std_partition_wave(uint32_t* v, const int first, 
     v[first]         = v[pick];
     v[pick]          = t;
   }
-  wave_sync_lds();
+  wave_sync();
   const uint32_t pr              = v[first] & 0xffu;
   const unsigned long long below = (1ull << lane) - 1ull;
   int lo = first + 1, hi = last;
@@ -749,7 +745,7 @@ __device__ __forceinline__ int std_partition_wave(uint32_t* v, const int first, 
     if (fr) {
       tr[__popcll(br & below)] = ph;
     }
-    wave_sync_lds();
+    wave_sync();
     const int nl = __popcll(bl), nr = __popcll(br);
     const int m  = nl < nr ? nl : nr;
     int pa = 0, pb = 0;
@@ -764,7 +760,7 @@ __device__ __forceinline__ int std_partition_wave(uint32_t* v, const int first, 
       v[pa]             = vb;
       v[pb]             = va;
     }
-    wave_sync_lds();
+    wave_sync();
     if (crossed) {
       const int l = tl[jstar];
       if (jstar == 0) {
@@ -777,7 +773,7 @@ __device__ __forceinline__ int std_partition_wave(uint32_t* v, const int first, 
     const int hi_next = jstar > 0 ? tr[jstar - 1] : (nr == 0 ? hi - 64 : hi);
     lo                = lo_next;
     hi                = hi_next;
-    wave_sync_lds();  // tl / tr are rewritten by the next round
+    wave_sync();  // tl / tr are rewritten by the next round
   }
 }
 
@@ -805,7 +801,7 @@ __device__ __forceinline__ void std_sort_small_wave(uint32_t* v, const int first
       if (dry) {
         v[first + lane] = x;
       }
-      wave_sync_lds();
+      wave_sync();
       while (heads) {
         const int h = (int) __ffsll((long long) heads) - 1;
         heads &= heads - 1ull;
@@ -814,7 +810,7 @@ __device__ __forceinline__ void std_sort_small_wave(uint32_t* v, const int first
           std_heapsort(v + first + h, l - h);
         }
       }
-      wave_sync_lds();
+      wave_sync();
       if (dry) {
         x      = v[first + lane];
         heaped = true;  // heap-sorted: the final insertion pass finds nothing to move
@@ -890,11 +886,11 @@ __device__ __forceinline__ void std_sort_small_wave(uint32_t* v, const int first
     const uint32_t rj = (uint32_t) __shfl((int) r, j < 64 ? j : 63, 64);
     rank += (j < sl && (rj > r || (rj == r && j < lane))) ? 1 : 0;
   }
-  wave_sync_lds();
+  wave_sync();
   if (lane < n) {
     v[first + (heaped ? lane : sf + rank)] = x;
   }
-  wave_sync_lds();
+  wave_sync();
 }
 
 // GNU libstdc++'s std::sort of every region, replayed by ALL waves of the workgroup: the ranges __introsort_loop recurses into
@@ -954,7 +950,7 @@ __device__ __forceinline__ void std_sort_worker(uint32_t* v, SortQueue& sq, cons
       first = stack[3 * sp];
       last  = stack[3 * sp + 1];
       depth = stack[3 * sp + 2];
-      wave_sync_lds();
+      wave_sync();
     } else {
       int got = 0;
       uint2 e = make_uint2(0u, 0u);
@@ -1012,7 +1008,7 @@ __device__ __forceinline__ void std_sort_worker(uint32_t* v, SortQueue& sq, cons
         if (lane == 0) {
           std_heapsort(v + first, size);
         }
-        wave_sync_lds();
+        wave_sync();
         finished += size;  // heap-sorted: the final insertion pass finds nothing to move
         break;
       }
@@ -1046,7 +1042,7 @@ __device__ __forceinline__ void std_sort_worker(uint32_t* v, SortQueue& sq, cons
             stack[3 * sp + 2] = depth;
           }
           ++sp;
-          wave_sync_lds();
+          wave_sync();
         }
       }
       last = cut;
@@ -1108,7 +1104,7 @@ __global__ __launch_bounds__(kSelThreads) void select_describe_kernel(const Feat
     for (int g = lane; g < a.regions; g += 64) {
       wcnt[g] = 0;
     }
-    wave_sync_lds();
+    wave_sync();
     for (int i0 = span_from; i0 < span_to; i0 += 64) {
       const int i       = i0 + lane;
       const bool valid  = i < span_to;
@@ -1122,7 +1118,7 @@ __global__ __launch_bounds__(kSelThreads) void select_describe_kernel(const Feat
           wcnt[gl] += (uint32_t) __popcll(b);
         }
         todo &= ~b;
-        wave_sync_lds();
+        wave_sync();
       }
     }
     __syncthreads();
@@ -1160,12 +1156,12 @@ __global__ __launch_bounds__(kSelThreads) void select_describe_kernel(const Feat
           const uint32_t rank = (uint32_t) __popcll(b & ((1ull << lane) - 1ull));
           keys[start[gl] + wcnt[gl] + rank] = (gl << 23) | ((uint32_t) i << 8) | (rw >> 24);
         }
-        wave_sync_lds();
+        wave_sync();
         if (lane == leader) {
           wcnt[gl] += (uint32_t) __popcll(b);
         }
         todo &= ~b;
-        wave_sync_lds();
+        wave_sync();
       }
     }
     __syncthreads();
@@ -1356,7 +1352,7 @@ __global__ __launch_bounds__(kDescThreads) void describe_kernel(const FeatureArg
     for (int u = 0; u < 4; ++u) {
       win[lane + 64 * u] = v[u];
     }
-    wave_sync_lds();
+    wave_sync();
     const int c = __builtin_amdgcn_readlane(my_c, i);
     const uint8_t* win8 = reinterpret_cast<const uint8_t*>(win) + ((c - kWinRadius) & 3);
     uint32_t word = 0;

@@ -54,6 +54,13 @@ __device__ __forceinline__ uint32_t popc_acc(uint32_t x, uint32_t acc) {
   return r;
 }
 
+// LDS written by one lane is read by other lanes of the wave
+__device__ __forceinline__ void wave_sync() {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
 __device__ __forceinline__ uint64_t wave_inclusive_scan_u64(uint64_t v) {
   const int lane = threadIdx.x & (PRS_WAVE - 1);
 #pragma unroll

@@ -5,6 +5,7 @@
 #include <stdint.h>
 
 #include <string>
+#include <type_traits>
 
 #include "../../include/proslam_hip.h"
 #include "prs_launch.h"
@@ -83,6 +84,12 @@ inline hipStream_t ctx_stream(prs_context* ctx) {
 // (ctx_fail, ctx_fail_hip, grid_fits and the launch path: prs_launch.h)
 inline bool aligned_to(const void* p, uintptr_t to) {
   return (reinterpret_cast<uintptr_t>(p) & (to - 1)) == 0;
+}
+// v rounded up to a multiple of 16, the alignment of every part of a workspace or an LDS layout (uint32_t or uint64_t)
+template <class T>
+constexpr T up16(const T v) {
+  static_assert(std::is_unsigned<T>::value, "up16 takes an unsigned size");
+  return (v + 15) & ~(T) 15;
 }
 // whether two arrays of a batch share a byte
 inline bool overlap(const void* a, size_t na, const void* b, size_t nb) {
@@ -322,6 +329,15 @@ int64_t dense_finish_blocks(const prs_dense_stereo_batch& o);
 void dense_census_enqueue(const Launches& on, const Grid& grid, const prs_dense_stereo_batch& o, uint64_t* census_l, uint64_t* census_r);
 void dense_finish_enqueue(const Launches& on, const Grid& grid, const prs_dense_stereo_params& p, const prs_dense_stereo_batch& o, uint2* rec_l,
                           int16_t* win_r);
+// what a dense and a semi-global call share on the host.  The checks of both entry points in their order and words: pointers, parameters
+// (stage_ok / stage_rule: the stage's own fields and how the refusal names them), sizes (stage_size / stage_size_name: one more that
+// must be at least 1) and pitches, alignment, pixel count.  And the workspace's parts in bytes, pixels 0 for a size the launchers refuse
+int stereo_call_check(prs_context* ctx, const std::string& who, const prs_dense_stereo_params& p, const prs_dense_stereo_batch& o, bool stage_ok,
+                      const char* stage_rule, int64_t stage_size = 1, const char* stage_size_name = "");
+struct DenseLayout {
+  uint64_t pixels, census, rec, right, total;
+};
+DenseLayout dense_layout_of(int64_t batch, int64_t frames, int64_t rows, int64_t cols, int64_t n_disparities, bool lr);
 int sgm_stereo_launch(prs_context* ctx, const prs_sgm_stereo_params* params, const prs_sgm_stereo_batch* batch);
 int speckle_launch(prs_context* ctx, const prs_speckle_params* params, const prs_speckle_batch* batch);
 int depth_consistency_launch(prs_context* ctx, const prs_depth_consistency_params* params, const prs_depth_consistency_batch* batch);

@@ -24,6 +24,7 @@
 
 #include "prs_device.h"
 #include "prs_host.h"
+#include "prs_image.h"
 
 namespace prs {
 
@@ -351,7 +352,8 @@ int rectify_launch(prs_context* ctx, const prs_rectify_params* params, const prs
     return ctx_fail(ctx, PRS_ERR_NULL, "prs_rectify_batch_run: src, dst, maps or status not set");
   }
   const int type = params->pixel_type, interp = params->interpolation;
-  if (type != PRS_PIXEL_U8 && type != PRS_PIXEL_U16 && type != PRS_PIXEL_F32) {
+  const int64_t elem = pixel_bytes(type);
+  if (elem == 0) {
     return ctx_fail(ctx, PRS_ERR_UNSUPPORTED, "prs_rectify_batch_run: unknown pixel_type");
   }
   if (interp != PRS_RECTIFY_BILINEAR && interp != PRS_RECTIFY_NEAREST) {
@@ -360,12 +362,10 @@ int rectify_launch(prs_context* ctx, const prs_rectify_params* params, const prs
   if (interp == PRS_RECTIFY_BILINEAR && type != PRS_PIXEL_U8) {
     return ctx_fail(ctx, PRS_ERR_UNSUPPORTED, "prs_rectify_batch_run: bilinear interpolation is for 8-bit pixels only (depth is sampled nearest)");
   }
-  const int64_t elem = type == PRS_PIXEL_U8 ? 1 : type == PRS_PIXEL_U16 ? 2 : 4;
   if (batch->batch < 1 || batch->n_maps < 1 || batch->src_rows < 1 || batch->src_cols < 1 || batch->dst_rows < 1 || batch->dst_cols < 1) {
     return ctx_fail(ctx, PRS_ERR_RANGE, "prs_rectify_batch_run: batch, n_maps or an image size below 1");
   }
-  if (batch->src_pitch % elem != 0 || batch->src_pitch < batch->src_cols * elem || batch->dst_pitch % elem != 0 ||
-      batch->dst_pitch < batch->dst_cols * elem) {
+  if (!pitch_ok(batch->src_pitch, batch->src_cols, elem) || !pitch_ok(batch->dst_pitch, batch->dst_cols, elem)) {
     return ctx_fail(ctx, PRS_ERR_RANGE, "prs_rectify_batch_run: a pitch below cols * element size or not a multiple of the element size");
   }
   const int64_t src_image = (int64_t) batch->src_rows * batch->src_pitch, dst_image = (int64_t) batch->dst_rows * batch->dst_pitch;

@@ -15,6 +15,7 @@
 
 #include "prs_device.h"
 #include "prs_host.h"
+#include "prs_image.h"
 
 namespace prs {
 
@@ -115,14 +116,14 @@ __global__ __launch_bounds__(kThreads) void depth_kernel(const DepthArgs a) {
 
 // call-level checks shared by both entry points; returns PRS_OK or the failure (already recorded in ctx)
 int check_params(prs_context* ctx, const prs_depth_params* params, int rows, int cols, int pitch, const char* who) {
-  if (params->depth_type != PRS_DEPTH_U16 && params->depth_type != PRS_DEPTH_F32) {
+  const int64_t elem = depth_bytes(params->depth_type);
+  if (elem == 0) {
     return ctx_fail(ctx, PRS_ERR_UNSUPPORTED, who);
   }
   if (!isfinite(params->depth_scaling_factor_to_meters)) {
     return ctx_fail(ctx, PRS_ERR_RANGE, who);
   }
-  const int elem = params->depth_type == PRS_DEPTH_U16 ? 2 : 4;
-  if (rows < 1 || cols < 1 || pitch % elem != 0 || (int64_t) pitch < (int64_t) cols * elem) {
+  if (rows < 1 || cols < 1 || !pitch_ok(pitch, cols, elem)) {
     return ctx_fail(ctx, PRS_ERR_RANGE, who);
   }
   return PRS_OK;
@@ -149,7 +150,7 @@ int depth_measurements_launch(prs_context* ctx, const prs_depth_params* params, 
   if (batch->stride < 1) {
     return ctx_fail(ctx, PRS_ERR_RANGE, "prs_depth_measurements_batch: stride below 1");
   }
-  const int elem = params->depth_type == PRS_DEPTH_U16 ? 2 : 4;
+  const int64_t elem = depth_bytes(params->depth_type);
   if (!aligned_to(batch->fixed, 16) || !aligned_to(batch->fixed_desc, 16) || !aligned_to(batch->descriptors, 16) || !aligned_to(batch->keypoints, 8) ||
       !aligned_to(batch->depth, (size_t) elem)) {
     return ctx_fail(ctx, PRS_ERR_UNSUPPORTED, "prs_depth_measurements_batch: fixed / descriptor rows must be 16-byte aligned");
@@ -197,7 +198,7 @@ int prs_depth_measurements(prs_context* ctx, const prs_depth_params* params, con
   (void) hipSetDevice(ctx->device);
   const bool with_int      = intensity && intensity_out;
   const size_t cap         = (size_t) (n > 0 ? n : 1);
-  const size_t elem        = params->depth_type == PRS_DEPTH_U16 ? 2 : 4;
+  const size_t elem        = (size_t) depth_bytes(params->depth_type);
   const size_t depth_bytes = (size_t) (rows - 1) * (size_t) pitch + (size_t) cols * elem;
   struct Meta {
     int32_t n_features, status, n_fixed;

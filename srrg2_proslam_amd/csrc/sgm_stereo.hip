@@ -21,13 +21,13 @@
 //   right    with the left-right check: the right winners from the diagonals S(y, x + d_i, i), a workgroup 128 right pixels of a
 //            row, the row's slice of the volume staged in LDS 64 disparities at a time (see the kernel)
 // Plain launches: no persistent workgroup, no spinning, no workgroup waits for another.
-#include <math.h>
 #include <stddef.h>
 
 #include <string>
 
 #include "prs_device.h"
 #include "prs_host.h"
+#include "prs_image.h"
 
 namespace prs {
 
@@ -40,8 +40,6 @@ constexpr int kRightTile  = 128;                     // right pixels of a right-
 constexpr int kRightRows  = kRightTile + PRS_WAVE;   // the pixels it stages for 64 disparities (kRightTile + 63 are reached)
 constexpr int kRightPitch = PRS_WAVE + 2;            // halfwords of a staged pixel: 33 words
 constexpr uint32_t kBig    = 1u << 20;       // a path cost that is not there: above 4157 + 4095, and far from wrapping
-constexpr uint32_t kNoCost = 0xffffu;        // above every S
-constexpr uint32_t kNoBest = 0xffffffffu;    // above every (S << 16) | i
 
 struct SgmArgs {
   prs_sgm_stereo_params p;
@@ -253,19 +251,18 @@ __global__ __launch_bounds__(kThreads) void sgm_winner_kernel(const SgmArgs a) {
     const int x     = (int) (px % cols);
     const int i_end = min(n, x - d0 + 1);  // admissible disparity indices of the left pixel: i < i_end
     uint32_t v[K];
-    uint32_t best = kNoBest;
+    uint32_t best = kStereoNoBest;
 #pragma unroll
     for (int k = 0; k < K; ++k) {
       const int i = k * PRS_WAVE + lane;
-      v[k]        = i < n ? (uint32_t) vol[(size_t) px * (size_t) n + (size_t) i] : kNoCost;
+      v[k]        = i < n ? (uint32_t) vol[(size_t) px * (size_t) n + (size_t) i] : kStereoNoCost;
       if (i < i_end) {
         best = min(best, (v[k] << 16) | (uint32_t) i);
       }
     }
     best = wave_min_u32(best);
-    const bool has  = best != kNoBest;
     const int istar = (int) (best & 0xffffu);
-    uint32_t a2 = kNoCost;  // the least cost two or more disparities away from the winner
+    uint32_t a2 = kStereoNoCost;  // the least cost two or more disparities away from the winner
 #pragma unroll
     for (int k = 0; k < K; ++k) {
       const int i = k * PRS_WAVE + lane;
@@ -281,23 +278,9 @@ __global__ __launch_bounds__(kThreads) void sgm_winner_kernel(const SgmArgs a) {
       Am = ((istar - 1) >> 6) == k ? tm : Am;
       Ap = ((istar + 1) >> 6) == k ? tp : Ap;
     }
-    float s = 0.0f;  // every operand is the same in every lane
-    if (has) {
-      const int A0    = (int) (best >> 16);
-      const bool keep = q == 0 || a2 == kNoCost || 100 * A0 < (100 - q) * (int) a2;
-      if (keep) {
-        float delta = 0.0f;
-        if (istar >= 1 && istar + 1 < i_end) {  // both neighbours in the range and admissible
-          const int den = (Am + Ap) - 2 * A0;
-          if (den > 0) {
-            delta = (float) (Am - Ap) / (float) (2 * den);
-          }
-        }
-        s = (float) (d0 + istar) + delta;
-      }
-    }
+    const uint2 r = stereo_winner_record(best, a2, Am, Ap, i_end, d0, q);  // every operand is the same in every lane
     if (lane == (int) (px - px0)) {
-      rec = make_uint2(__float_as_uint(s), has ? (uint32_t) istar : 0xffffffffu);
+      rec = r;
     }
   }
   if (lane < (int) (px1 - px0)) {
@@ -332,7 +315,7 @@ __global__ __launch_bounds__(kThreads) void sgm_right_kernel(const SgmArgs a) {
   const uint16_t* row   = a.vol + ((size_t) slot * image_px + (size_t) y * (size_t) cols) * (size_t) n;  // S(y, ., .)
   const int x0 = tile * kRightTile, r = tid & (kRightTile - 1), half = tid / kRightTile;
   const int64_t x = (int64_t) x0 + r;  // the thread's right pixel
-  uint32_t best = kNoBest;
+  uint32_t best = kStereoNoBest;
   for (int c0 = 0; c0 < n; c0 += PRS_WAVE) {
     const int64_t p0 = (int64_t) x0 + d0 + c0;  // the first staged pixel
     __syncthreads();  // the readers of the last 64 disparities are through
@@ -365,35 +348,32 @@ __global__ __launch_bounds__(kThreads) void sgm_right_kernel(const SgmArgs a) {
   __syncthreads();
   if (tid < kRightTile && x < cols) {
     best = min(s_best[tid], s_best[tid + kRightTile]);
-    a.win_r[(size_t) image * image_px + (size_t) y * (size_t) cols + (size_t) x] = best != kNoBest ? (int16_t) (best & 0xffffu) : (int16_t) -1;
+    a.win_r[(size_t) image * image_px + (size_t) y * (size_t) cols + (size_t) x] = best != kStereoNoBest ? (int16_t) (best & 0xffffu) : (int16_t) -1;
   }
 }
 
 using PathKernel   = void (*)(SgmArgs, int, int, int);
 using WinnerKernel = void (*)(SgmArgs);
 
-// the parts of the workspace, in bytes; pixels 0 when a size is not one the launcher takes
+// the parts of the workspace, in bytes: dense stereo's and behind them the volume; pixels 0 when a size is not one the launcher takes
 struct Layout {
-  uint64_t pixels, in_flight, census, rec, right, volume, total;
+  DenseLayout dense;
+  uint64_t in_flight, volume, total;
 };
 
 Layout layout_of(const int64_t batch, const int64_t frames, const int64_t rows, const int64_t cols, const int64_t n_disparities, const bool lr,
                  const int64_t images_in_flight) {
   Layout l = {};
-  if (batch < 1 || frames < 1 || rows < 1 || cols < 1 || n_disparities < 1 || n_disparities > 256 || images_in_flight < 1) {
+  if (images_in_flight < 1) {
     return l;
   }
-  if (batch * frames > 0x7fffffffll || rows * cols > 0x7fffffffll || batch * frames * rows * cols > 0x7fffffffll) {  // each below 2^62
+  l.dense = dense_layout_of(batch, frames, rows, cols, n_disparities, lr);
+  if (l.dense.pixels < 1) {
     return l;
   }
-  const auto up = [](const uint64_t v) { return (v + 15) & ~(uint64_t) 15; };
-  l.pixels    = (uint64_t) (batch * frames * rows * cols);
   l.in_flight = (uint64_t) (images_in_flight < batch * frames ? images_in_flight : batch * frames);
-  l.census    = up(8 * l.pixels);
-  l.rec       = up(8 * l.pixels);
-  l.right     = lr ? up(2 * l.pixels) : 0;
-  l.volume    = up(2 * l.in_flight * (uint64_t) (rows * cols) * (uint64_t) n_disparities);  // below 2^31 * 2^8 * 2
-  l.total     = 2 * l.census + l.rec + l.right + l.volume;
+  l.volume    = up16(2 * l.in_flight * (uint64_t) (rows * cols) * (uint64_t) n_disparities);  // below 2^31 * 2^8 * 2
+  l.total     = l.dense.total + l.volume;
   return l;
 }
 
@@ -406,28 +386,7 @@ int sgm_stereo_launch(prs_context* ctx, const prs_sgm_stereo_params* params, con
   }
   const prs_sgm_stereo_params& p = *params;
   const prs_sgm_stereo_batch& o  = *batch;
-  if (!o.left || !o.right || !o.status || !o.workspace || (!o.disparity && !o.depth)) {
-    return ctx_fail(ctx, PRS_ERR_NULL, (who + ": left, right, status or the workspace not set, or neither disparity nor depth").c_str());
-  }
-  if (p.n_disparities < 1 || p.n_disparities > 256 || p.min_disparity < 0 || p.min_disparity + p.n_disparities > 4096 ||
-      (p.n_paths != 4 && p.n_paths != 8) || p.p1 < 0 || p.p2 < p.p1 || p.p2 > 4095 || p.uniqueness_percent < 0 || p.uniqueness_percent > 99 ||
-      p.lr_max_diff < -1 || p.lr_max_diff > 255 || !std::isfinite(p.bf) || !(p.bf > 0.0f)) {
-    return ctx_fail(ctx, PRS_ERR_RANGE, (who + ": n_disparities outside 1..256, min_disparity below 0 or min_disparity + n_disparities above 4096, n_paths not 4 or 8, p1 below 0, p2 below p1 or above 4095, uniqueness_percent outside 0..99, lr_max_diff outside -1..255, or bf not finite and positive").c_str());
-  }
-  if (o.batch < 1 || o.frames < 1 || o.rows < 1 || o.cols < 1 || o.images_in_flight < 1 || o.left_pitch < o.cols || o.right_pitch < o.cols ||
-      o.out_pitch % 4 != 0 || (int64_t) o.out_pitch < (int64_t) o.cols * 4) {
-    return ctx_fail(ctx, PRS_ERR_RANGE, (who + ": a size or images_in_flight below 1, an image pitch below cols, or out_pitch below cols floats or not a multiple of 4").c_str());
-  }
-  if (!aligned_to(o.disparity, 4) || !aligned_to(o.depth, 4) || !aligned_to(o.workspace, 16) || !aligned_to(o.n_images, 4) ||
-      !aligned_to(o.n_valid, 4) || !aligned_to(o.status, 4)) {
-    return ctx_fail(ctx, PRS_ERR_UNSUPPORTED, (who + ": the workspace must be 16-byte aligned, the other arrays but the images 4-byte").c_str());
-  }
-  const bool lr  = p.lr_max_diff >= 0;
-  const Layout l = layout_of(o.batch, o.frames, o.rows, o.cols, p.n_disparities, lr, o.images_in_flight);
-  if (l.pixels < 1) {
-    return ctx_fail(ctx, PRS_ERR_UNSUPPORTED, (who + ": batch * frames * rows * cols beyond 2^31 - 1").c_str());
-  }
-  // the stages this one shares its census and finish kernels with read these two
+  // the stages this one shares its checks and its census and finish kernels with read these two
   prs_dense_stereo_params dp = {};
   dp.n_disparities = p.n_disparities, dp.min_disparity = p.min_disparity, dp.uniqueness_percent = p.uniqueness_percent;
   dp.lr_max_diff = p.lr_max_diff, dp.bf = p.bf;
@@ -436,6 +395,10 @@ int sgm_stereo_launch(prs_context* ctx, const prs_sgm_stereo_params* params, con
   db.left_pitch = o.left_pitch, db.right_pitch = o.right_pitch, db.out_pitch = o.out_pitch;
   db.left = o.left, db.right = o.right, db.n_images = o.n_images, db.disparity = o.disparity, db.depth = o.depth;
   db.n_valid = o.n_valid, db.status = o.status, db.workspace = o.workspace;
+  PRS_TRY(stereo_call_check(ctx, who, dp, db, (p.n_paths == 4 || p.n_paths == 8) && p.p1 >= 0 && p.p2 >= p.p1 && p.p2 <= 4095,
+                            "n_paths not 4 or 8, p1 below 0, p2 below p1 or above 4095", o.images_in_flight, " or images_in_flight"));
+  const bool lr  = p.lr_max_diff >= 0;
+  const Layout l = layout_of(o.batch, o.frames, o.rows, o.cols, p.n_disparities, lr, o.images_in_flight);
 
   SgmArgs a = {};
   a.p = p;
@@ -446,10 +409,10 @@ int sgm_stereo_launch(prs_context* ctx, const prs_sgm_stereo_params* params, con
   a.rtiles = (int32_t) (((int64_t) o.cols + kRightTile - 1) / kRightTile);
   uint8_t* ws = static_cast<uint8_t*>(o.workspace);
   a.census_l  = reinterpret_cast<uint64_t*>(ws);
-  a.census_r  = reinterpret_cast<uint64_t*>(ws + l.census);
-  a.rec_l     = reinterpret_cast<uint2*>(ws + 2 * l.census);
-  a.win_r     = lr ? reinterpret_cast<int16_t*>(ws + 2 * l.census + l.rec) : nullptr;
-  a.vol       = reinterpret_cast<uint16_t*>(ws + 2 * l.census + l.rec + l.right);
+  a.census_r  = reinterpret_cast<uint64_t*>(ws + l.dense.census);
+  a.rec_l     = reinterpret_cast<uint2*>(ws + 2 * l.dense.census);
+  a.win_r     = lr ? reinterpret_cast<int16_t*>(ws + 2 * l.dense.census + l.dense.rec) : nullptr;
+  a.vol       = reinterpret_cast<uint16_t*>(ws + l.dense.total);
   // the grids of the call, before anything is launched (each factor is below 2^31): census and finish over every image, the rest
   // over the images in flight -- every group of them but the last is full
   static_assert(kThreads == kDenseThreads, "the shared launches' workgroup");

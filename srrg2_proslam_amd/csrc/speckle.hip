@@ -27,6 +27,7 @@
 
 #include "prs_device.h"
 #include "prs_host.h"
+#include "prs_image.h"
 
 namespace prs {
 
@@ -48,12 +49,6 @@ struct SpeckleArgs {
   int32_t* parent;  // [images][rows * cols]
   int32_t* size;    // [images][rows * cols], read at roots
 };
-
-// the images of sequence b the call works on; -1 when n_images[b] is out of range (the sequence is refused)
-__device__ __forceinline__ int images_of(const SpeckleArgs& a, const int b) {
-  const int n = a.o.n_images ? a.o.n_images[b] : a.o.frames;
-  return (n < 0 || n > a.o.frames) ? -1 : n;
-}
 
 // element (v, u) of an image as a float, NaN when it is not valid.  valid: x > 0, which for a float is 0 < bits <= those of +inf
 __device__ __forceinline__ float value_at(const void* image, const int type, const size_t row_bytes, const int u) {
@@ -138,8 +133,8 @@ __global__ __launch_bounds__(kThreads) void speckle_tile_kernel(const SpeckleArg
   id /= (uint32_t) a.tiles_x;
   const int ty         = (int) (id % (uint32_t) a.tiles_y);
   const uint32_t image = id / (uint32_t) a.tiles_y;
-  const int f = (int) (image % (uint32_t) a.o.frames), b = (int) (image / (uint32_t) a.o.frames);
-  const int n_img  = images_of(a, b);
+  const int f = frame_of(image, a.o.frames), b = sequence_of(image, a.o.frames);
+  const int n_img  = images_of(a.o, b);
   const bool first = tx == 0 && ty == 0 && tid == 0;
   if (first && f == 0) {
     a.o.status[b] = n_img < 0 ? PRS_ERR_RANGE : PRS_OK;
@@ -213,9 +208,9 @@ __global__ __launch_bounds__(kThreads) void speckle_tile_kernel(const SpeckleArg
 __global__ __launch_bounds__(kThreads) void speckle_seam_kernel(const SpeckleArgs a) {
   const int block      = (int) (blockIdx.x % (uint32_t) a.sblocks);
   const uint32_t image = blockIdx.x / (uint32_t) a.sblocks;
-  const int f = (int) (image % (uint32_t) a.o.frames), b = (int) (image / (uint32_t) a.o.frames);
+  const int f = frame_of(image, a.o.frames), b = sequence_of(image, a.o.frames);
   const int s = block * kThreads + (int) threadIdx.x;
-  if (f >= images_of(a, b) || s >= a.seams) {
+  if (f >= images_of(a.o, b) || s >= a.seams) {
     return;
   }
   const int rows = a.o.rows, cols = a.o.cols;
@@ -256,8 +251,7 @@ __global__ __launch_bounds__(kThreads) void speckle_seam_kernel(const SpeckleArg
 __global__ __launch_bounds__(kThreads) void speckle_flatten_kernel(const SpeckleArgs a) {
   const int block      = (int) (blockIdx.x % (uint32_t) a.pblocks);
   const uint32_t image = blockIdx.x / (uint32_t) a.pblocks;
-  const int f = (int) (image % (uint32_t) a.o.frames), b = (int) (image / (uint32_t) a.o.frames);
-  if (f >= images_of(a, b)) {
+  if (!image_served(a.o, image)) {
     return;
   }
   const int pixels = a.o.rows * a.o.cols;
@@ -316,8 +310,7 @@ __global__ __launch_bounds__(kThreads) void speckle_apply_kernel(const SpeckleAr
   const int tid        = threadIdx.x;
   const int block      = (int) (blockIdx.x % (uint32_t) a.pblocks);
   const uint32_t image = blockIdx.x / (uint32_t) a.pblocks;
-  const int f = (int) (image % (uint32_t) a.o.frames), b = (int) (image / (uint32_t) a.o.frames);
-  if (f >= images_of(a, b)) {
+  if (!image_served(a.o, image)) {
     return;
   }
   const int rows = a.o.rows, cols = a.o.cols, pixels = rows * cols;
@@ -369,23 +362,9 @@ __global__ __launch_bounds__(kThreads) void speckle_apply_kernel(const SpeckleAr
   }
 }
 
-// pixels of the call; 0 when a size is not one the launcher takes
-uint64_t pixels_of(const int64_t batch, const int64_t frames, const int64_t rows, const int64_t cols) {
-  if (batch < 1 || frames < 1 || rows < 1 || cols < 1) {
-    return 0;
-  }
-  if (batch * frames > 0x7fffffffll || rows * cols > 0x7fffffffll || batch * frames * rows * cols > 0x7fffffffll) {  // each below 2^62
-    return 0;
-  }
-  return (uint64_t) (batch * frames * rows * cols);
-}
-
-inline uint64_t up16(const uint64_t v) {
-  return (v + 15) & ~(uint64_t) 15;
-}
-
+// bytes of an element of a type the filter takes (disparity or depth: no 8-bit image), 0 for any other
 inline int64_t element_bytes(const int type) {
-  return type == PRS_PIXEL_U16 ? 2 : type == PRS_PIXEL_F32 ? 4 : 0;
+  return type == PRS_PIXEL_U8 ? 0 : pixel_bytes(type);
 }
 
 }  // namespace
@@ -405,7 +384,7 @@ int speckle_launch(prs_context* ctx, const prs_speckle_params* params, const prs
   }
   // a pitch is judged by its element; a type without one is refused below
   const int64_t es = element_bytes(p.pixel_type), ces = o.companion ? element_bytes(p.companion_type) : 0;
-  const auto bad_pitch = [&](const int64_t pitch, const int64_t e) { return e > 0 && (pitch % e != 0 || pitch < (int64_t) o.cols * e); };
+  const auto bad_pitch = [&](const int64_t pitch, const int64_t e) { return e > 0 && !pitch_ok(pitch, o.cols, e); };
   if (o.batch < 1 || o.frames < 1 || o.rows < 1 || o.cols < 1 || bad_pitch(o.pitch, es) || bad_pitch(o.companion_pitch, ces) ||
       (o.label && bad_pitch(o.label_pitch, 4))) {
     return ctx_fail(ctx, PRS_ERR_RANGE, (who + ": a size below 1, or a pitch below cols elements or not a multiple of the element size").c_str());
@@ -417,7 +396,7 @@ int speckle_launch(prs_context* ctx, const prs_speckle_params* params, const prs
       !aligned_to(o.n_images, 4) || !aligned_to(o.label, 4) || !aligned_to(o.n_kept, 4) || !aligned_to(o.n_removed, 4) || !aligned_to(o.status, 4)) {
     return ctx_fail(ctx, PRS_ERR_UNSUPPORTED, (who + ": the workspace must be 16-byte aligned, image and companion to their element, the other arrays 4-byte").c_str());
   }
-  const uint64_t pixels = pixels_of(o.batch, o.frames, o.rows, o.cols);
+  const uint64_t pixels = image_pixels(o.batch, o.frames, o.rows, o.cols);
   if (pixels < 1) {
     return ctx_fail(ctx, PRS_ERR_UNSUPPORTED, (who + ": rows * cols or batch * frames * rows * cols beyond 2^31 - 1").c_str());
   }
@@ -466,7 +445,7 @@ void prs_speckle_struct_sizes(uint64_t* sizes2) {
 }
 
 uint64_t prs_speckle_workspace_bytes(int32_t batch, int32_t frames, int32_t rows, int32_t cols) {
-  return 2 * up16(4 * pixels_of(batch, frames, rows, cols));
+  return 2 * up16(4 * image_pixels(batch, frames, rows, cols));
 }
 
 int prs_speckle_batch_run(prs_context* ctx, const prs_speckle_params* params, const prs_speckle_batch* batch) {

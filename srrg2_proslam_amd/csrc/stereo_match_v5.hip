@@ -780,10 +780,6 @@ __global__ __launch_bounds__(kT) void stereo_match5_kernel(const Args5 a) {
   }
 }
 
-inline uint32_t up16(uint32_t v) {
-  return (v + 15u) & ~15u;
-}
-
 }  // namespace v5
 using namespace v5;
 

@@ -23,6 +23,11 @@ def _check(ctx, rc, what):
     return rc
 
 
+def _run(ctx, entry, *args):
+    """call the entry point `entry` of the library on the context: its status, ProslamHipError on a failure"""
+    return _check(ctx, getattr(_lib.load(), entry)(ctx._h, *args), entry)
+
+
 class Context:
     """prs_context: one device, one stream, scratch. Not re-entrant (like the reference's finders).
 
@@ -69,7 +74,7 @@ class Context:
         _check(self, _lib.load().prs_context_synchronize(self._h), "prs_context_synchronize")
 
     def set_bruteforce_dense_phase(self, mode):
-        """BF_DENSE_POPCOUNT (default) / BF_DENSE_MATRIX_WHEN_FULL / BF_DENSE_MATRIX: which kernels score the brute-force matcher's
+        """BF_DENSE_POPCOUNT / BF_DENSE_MATRIX_WHEN_FULL (default) / BF_DENSE_MATRIX: which kernels score the brute-force matcher's
         N_f x N_m pairs (prs_context_set_bruteforce_dense_phase; same results, the matrix cores pay only when candidates are rare)"""
         _check(self, _lib.load().prs_context_set_bruteforce_dense_phase(self._h, int(mode)), "prs_context_set_bruteforce_dense_phase")
 
@@ -262,9 +267,7 @@ class StereoFrames:
 def stereo_match_batch(ctx, params, frames, tri_params=None):
     """enqueue the batched matcher on the context stream (asynchronous)"""
     d = frames.descriptor(tri_params)
-    rc = _lib.load().prs_stereo_match_batch(ctx._h, C.byref(params), C.byref(d))
-    _check(ctx, rc, "prs_stereo_match_batch")
-    return rc
+    return _run(ctx, "prs_stereo_match_batch", C.byref(params), C.byref(d))
 
 
 # =================================================================================================
@@ -555,24 +558,18 @@ class AlignFrames:
 def align_batch(ctx, finder_params, aligner_params_, frames, mode=_lib.MODE_ALIGN):
     """prs_align_batch_run: the finder + aligner loop of every frame of the batch (mode ALIGN blocks until it is complete)"""
     d = frames.descriptor()
-    rc = _lib.load().prs_align_batch_run(ctx._h, C.byref(finder_params), C.byref(aligner_params_), C.byref(d), int(mode))
-    _check(ctx, rc, "prs_align_batch_run")
-    return rc
+    return _run(ctx, "prs_align_batch_run", C.byref(finder_params), C.byref(aligner_params_), C.byref(d), int(mode))
 
 
 def align_batch_enqueue(ctx, finder_params, aligner_params_, frames, rounds=0):
     """prs_align_batch_enqueue: `rounds` search + Gauss-Newton rounds on the context stream, no host synchronisation"""
     d = frames.descriptor()
-    rc = _lib.load().prs_align_batch_enqueue(ctx._h, C.byref(finder_params), C.byref(aligner_params_), C.byref(d), int(rounds))
-    _check(ctx, rc, "prs_align_batch_enqueue")
-    return rc
+    return _run(ctx, "prs_align_batch_enqueue", C.byref(finder_params), C.byref(aligner_params_), C.byref(d), int(rounds))
 
 
 def align_batch_finish(ctx):
     """prs_align_batch_finish: wait for the enqueued batch, run more rounds for frames that are still pending"""
-    rc = _lib.load().prs_align_batch_finish(ctx._h)
-    _check(ctx, rc, "prs_align_batch_finish")
-    return rc
+    return _run(ctx, "prs_align_batch_finish")
 
 
 def align_batch_rearm(ctx, replay_stream=None):
@@ -664,9 +661,7 @@ def scene_clip_batch(ctx, projector, sensor_in_robot, scenes):
     """enqueue the clipper for every scene of the batch on the context stream (asynchronous)"""
     S = _np(sensor_in_robot, np.float32, (16,))
     d = scenes.descriptor()
-    rc = _lib.load().prs_scene_clip_batch(ctx._h, C.byref(projector), _p(S), C.byref(d))
-    _check(ctx, rc, "prs_scene_clip_batch")
-    return rc
+    return _run(ctx, "prs_scene_clip_batch", C.byref(projector), _p(S), C.byref(d))
 
 
 # ---- bijective brute-force matcher (CF/correspondence_finder_descriptor_based_bruteforce_impl.cpp) ----
@@ -734,9 +729,7 @@ class BruteforceClouds:
 def bruteforce_match_batch(ctx, params, clouds):
     """enqueue the matcher for every cloud pair of the batch on the context stream (asynchronous)"""
     d = clouds.descriptor()
-    rc = _lib.load().prs_bruteforce_match_batch(ctx._h, C.byref(params), C.byref(d))
-    _check(ctx, rc, "prs_bruteforce_match_batch")
-    return rc
+    return _run(ctx, "prs_bruteforce_match_batch", C.byref(params), C.byref(d))
 
 
 # ---- loop aligner (MultiAligner3DQR "loop_aligner" + AlignerSliceProcessor3D, registration/aligner_slice_processor_3d.hpp:7-22) ----
@@ -849,9 +842,7 @@ class PointAlignBatch:
 def point_align_batch(ctx, params, pairs):
     """enqueue the loop aligner for every pair of the batch on the context stream (asynchronous)"""
     d = pairs.descriptor()
-    rc = _lib.load().prs_point_align_batch(ctx._h, C.byref(params), C.byref(d))
-    _check(ctx, rc, "prs_point_align_batch")
-    return rc
+    return _run(ctx, "prs_point_align_batch", C.byref(params), C.byref(d))
 
 
 class LoopClosureBatch:
@@ -1399,17 +1390,13 @@ class PoseGraphBatch:
         c.status, c.n_appended = self.append_status.data_ptr(), self.n_appended.data_ptr()
         p = params if params is not None else pose_graph_params(dict(damping=0.0, max_iterations=0, epsilon=0.0))
         d = self.descriptor()
-        rc = _lib.load().prs_pose_graph_append_closures(ctx._h, C.byref(p), C.byref(d), C.byref(c))
-        _check(ctx, rc, "prs_pose_graph_append_closures")
-        return rc
+        return _run(ctx, "prs_pose_graph_append_closures", C.byref(p), C.byref(d), C.byref(c))
 
 
 def pose_graph_optimize_batch(ctx, params, graphs):
     """enqueue the optimiser for every graph of the batch on the context stream (asynchronous, one launch)"""
     d = graphs.descriptor()
-    rc = _lib.load().prs_pose_graph_optimize_batch(ctx._h, C.byref(params), C.byref(d))
-    _check(ctx, rc, "prs_pose_graph_optimize_batch")
-    return rc
+    return _run(ctx, "prs_pose_graph_optimize_batch", C.byref(params), C.byref(d))
 
 
 def pose_graph_optimize_lm_batch(ctx, params, graphs):
@@ -1417,9 +1404,7 @@ def pose_graph_optimize_lm_batch(ctx, params, graphs):
     graphs.lm_result.  A batch built without lm=True has a workspace without the 28 doubles per node: its graphs whose envelope
     no longer fits report PRS_ERR_CAPACITY."""
     d = graphs.descriptor()
-    rc = _lib.load().prs_pose_graph_optimize_lm_batch(ctx._h, C.byref(params), C.byref(d), graphs.lm_result.data_ptr())
-    _check(ctx, rc, "prs_pose_graph_optimize_lm_batch")
-    return rc
+    return _run(ctx, "prs_pose_graph_optimize_lm_batch", C.byref(params), C.byref(d), graphs.lm_result.data_ptr())
 
 
 # ---- landmark estimators + projective mergers (mapping/mergers, mapping/landmarks) ----
@@ -1479,9 +1464,7 @@ class MapBatch:
 def merge_batch(ctx, params, maps):
     """enqueue MergerProjective_::compute for every (map, frame) pair of the batch (asynchronous)"""
     d = maps.descriptor()
-    rc = _lib.load().prs_merge_batch_run(ctx._h, C.byref(params), C.byref(d))
-    _check(ctx, rc, "prs_merge_batch_run")
-    return rc
+    return _run(ctx, "prs_merge_batch_run", C.byref(params), C.byref(d))
 
 
 class MapHandle:
@@ -1734,25 +1717,19 @@ class ClosureMergeBatch:
 def closure_merge_batch(ctx, params, pairs):
     """enqueue the closure merger for every pair of the batch on the context stream (asynchronous, one launch)"""
     d = pairs.descriptor()
-    rc = _lib.load().prs_closure_merge_batch_run(ctx._h, C.byref(params), C.byref(d))
-    _check(ctx, rc, "prs_closure_merge_batch_run")
-    return rc
+    return _run(ctx, "prs_closure_merge_batch_run", C.byref(params), C.byref(d))
 
 
 def pose_compose_batch(ctx, prediction, X, pose_out):
     """pose_out[b] = prediction[b] * X[b]^-1 on device tensors of shape [B, 16] / [B, 4, 4] (asynchronous)"""
     batch = int(prediction.shape[0])
-    rc = _lib.load().prs_pose_compose_batch(ctx._h, batch, prediction.data_ptr(), X.data_ptr(), pose_out.data_ptr())
-    _check(ctx, rc, "prs_pose_compose_batch")
-    return rc
+    return _run(ctx, "prs_pose_compose_batch", batch, prediction.data_ptr(), X.data_ptr(), pose_out.data_ptr())
 
 
 def motion_predict_batch(ctx, pose_prev2, pose_prev1, pose_pred):
     """MotionModelConstantVelocity3D on the device: pose_pred = pose_prev1 * (pose_prev2^-1 * pose_prev1), [B, 4, 4] float32"""
     batch = int(pose_prev1.shape[0])
-    rc = _lib.load().prs_motion_predict_batch(ctx._h, batch, pose_prev2.data_ptr(), pose_prev1.data_ptr(), pose_pred.data_ptr())
-    _check(ctx, rc, "prs_motion_predict_batch")
-    return rc
+    return _run(ctx, "prs_motion_predict_batch", batch, pose_prev2.data_ptr(), pose_prev1.data_ptr(), pose_pred.data_ptr())
 
 
 # ---- local-map manager: per-sequence splits, graph growth, trajectories (include/proslam_hip.h prs_session_*) ----
@@ -1838,9 +1815,7 @@ class SessionBatch:
     def step(self, ctx, params):
         """enqueue the per-frame step of every sequence (asynchronous, one launch); per-sequence status lands in self.status"""
         d = self.descriptor()
-        rc = _lib.load().prs_session_step_batch(ctx._h, C.byref(params), C.byref(d))
-        _check(ctx, rc, "prs_session_step_batch")
-        return rc
+        return _run(ctx, "prs_session_step_batch", C.byref(params), C.byref(d))
 
     def unroll(self, ctx):
         """enqueue the unrolling of the logged trajectories through the graphs as they stand -> self.trajectory [B, frame_stride, 16]
@@ -1962,9 +1937,7 @@ class TrajectoryEvalBatch:
     def evaluate(self, ctx, params):
         """enqueue the evaluation of every sequence (asynchronous, one launch); per-sequence status lands in the results"""
         d = self.descriptor()
-        rc = _lib.load().prs_trajectory_eval_batch(ctx._h, C.byref(params), C.byref(d))
-        _check(ctx, rc, "prs_trajectory_eval_batch")
-        return rc
+        return _run(ctx, "prs_trajectory_eval_batch", C.byref(params), C.byref(d))
 
     def results(self):
         """the B results as dicts (field names of prs_trajectory_result, S as [4, 4]); copies `result` to the host when called"""
@@ -2104,17 +2077,13 @@ class ReentryBatch:
         """enqueue the per-frame step of every sequence with the archive behind it (asynchronous, one launch); the session's status
         lands in session.status, the archive's in archive.status"""
         s, m, a = self.session.descriptor(), self.maps.descriptor(), self.archive.descriptor()
-        rc = _lib.load().prs_session_step_archive_batch(ctx._h, C.byref(params), C.byref(s), C.byref(m), C.byref(a))
-        _check(ctx, rc, "prs_session_step_archive_batch")
-        return rc
+        return _run(ctx, "prs_session_step_archive_batch", C.byref(params), C.byref(s), C.byref(m), C.byref(a))
 
     def reenter(self, ctx, params):
         """enqueue the re-entry of every sequence whose split found an accepted closure into an archived map (asynchronous, one
         launch); per-sequence status lands in self.status, the decision in self.reentered"""
         s, m, a, r = self.session.descriptor(), self.maps.descriptor(), self.archive.descriptor(), self.descriptor()
-        rc = _lib.load().prs_session_reenter_batch(ctx._h, C.byref(params), C.byref(s), C.byref(m), C.byref(a), C.byref(r))
-        _check(ctx, rc, "prs_session_reenter_batch")
-        return rc
+        return _run(ctx, "prs_session_reenter_batch", C.byref(params), C.byref(s), C.byref(m), C.byref(a), C.byref(r))
 
     def result_of(self, b):
         """dict(status, reentered, cur_node, n_corr, transform [4, 4], scene_in_world [4, 4], gate (the winner's aligner result))"""
@@ -2183,9 +2152,7 @@ class WorldMapBatch:
 
     def _launch(self, ctx, params, count_only):
         s, m, a, d = self.session.descriptor(), self.maps.descriptor(), self.archive.descriptor(), self.descriptor(count_only)
-        rc = _lib.load().prs_world_map_batch_run(ctx._h, C.byref(params), C.byref(s), C.byref(m), C.byref(a), C.byref(d))
-        _check(ctx, rc, "prs_world_map_batch_run")
-        return rc
+        return _run(ctx, "prs_world_map_batch_run", C.byref(params), C.byref(s), C.byref(m), C.byref(a), C.byref(d))
 
     def run(self, ctx, params):
         """enqueue the export of every sequence's cloud (asynchronous); per-sequence status lands in self.status"""
@@ -2286,9 +2253,7 @@ class WorldVoxelBatch:
 
     def _launch(self, ctx, params, cloud, count_only):
         d = self.descriptor(cloud, count_only)
-        rc = _lib.load().prs_world_voxel_batch_run(ctx._h, C.byref(params), C.byref(d))
-        _check(ctx, rc, "prs_world_voxel_batch_run")
-        return rc
+        return _run(ctx, "prs_world_voxel_batch_run", C.byref(params), C.byref(d))
 
     def run(self, ctx, params, cloud):
         """enqueue the filter of every sequence's cloud (asynchronous); per-sequence status lands in self.status"""
@@ -2400,9 +2365,7 @@ def extract_features_selective_batch(ctx, params, images, keypoints, descriptors
     d.keypoints, d.descriptors = keypoints.data_ptr(), descriptors.data_ptr()
     d.intensity = intensity.data_ptr() if intensity is not None else None
     d.n_features, d.status = n_features.data_ptr(), status.data_ptr()
-    rc = _lib.load().prs_extract_features_selective_batch(ctx._h, C.byref(params), C.byref(d))
-    _check(ctx, rc, "prs_extract_features_selective_batch")
-    return rc
+    return _run(ctx, "prs_extract_features_selective_batch", C.byref(params), C.byref(d))
 
 
 def selftest_reciprocal(ctx):
@@ -2433,9 +2396,7 @@ def extract_features_batch(ctx, params, images, keypoints, descriptors, n_featur
     d.keypoints, d.descriptors = keypoints.data_ptr(), descriptors.data_ptr()
     d.intensity = intensity.data_ptr() if intensity is not None else None
     d.n_features, d.status = n_features.data_ptr(), status.data_ptr()
-    rc = _lib.load().prs_extract_features_batch(ctx._h, C.byref(params), C.byref(d))
-    _check(ctx, rc, "prs_extract_features_batch")
-    return rc
+    return _run(ctx, "prs_extract_features_batch", C.byref(params), C.byref(d))
 
 
 # ---- RGB-D preprocessing (RawDataPreprocessorMonocularDepth: extractor keypoints + depth image -> (u, v, d) measurements) ----
@@ -2493,9 +2454,7 @@ def depth_measurements_batch(ctx, params, depth, keypoints, descriptors, n_featu
     d.extract_status = extract_status.data_ptr() if extract_status is not None else None
     d.fixed, d.fixed_desc, d.n_fixed, d.status = fixed.data_ptr(), fixed_desc.data_ptr(), n_fixed.data_ptr(), status.data_ptr()
     d.fixed_intensity = fixed_intensity.data_ptr() if fixed_intensity is not None else None
-    rc = _lib.load().prs_depth_measurements_batch(ctx._h, C.byref(params), C.byref(d))
-    _check(ctx, rc, "prs_depth_measurements_batch")
-    return rc
+    return _run(ctx, "prs_depth_measurements_batch", C.byref(params), C.byref(d))
 
 
 class RGBDFrames:
@@ -2560,6 +2519,89 @@ def rgbd_params(cfg, selection_order=SELECT_LIBSTDCXX, max_raw_detections=32768,
     return ep, depth_params(depth_type, r["depth_scaling_factor_to_meters"])
 
 
+# ---- what the adapters of the image stages share: each [batch][frames][rows][cols] stage below states only what is its own ----
+def _depth_type(depth_type, known=False):
+    """PRS_DEPTH_* of "u16" / "f32" or of an integer, which goes to the library as it is unless it has to be a known one"""
+    if depth_type not in _DEPTH_TYPES if isinstance(depth_type, str) else known and int(depth_type) not in _DEPTH_TYPES.values():
+        raise ValueError("depth_type: one of %s" % (sorted(_DEPTH_TYPES),))
+    return _DEPTH_TYPES[depth_type] if isinstance(depth_type, str) else int(depth_type)
+
+
+def _zeros_on(device):
+    """zeros(shape, dtype) on a device: an index is that GPU, a torch.device itself"""
+    import torch
+    dev = torch.device("cuda", device) if isinstance(device, int) else device
+    return lambda shape, dt: torch.zeros(shape, dtype=dt, device=dev)
+
+
+def _padded_rows(z, lead, cols, dtype, wanted=True):
+    """(storage, view, pitch in elements) of an array [*lead, cols] whose rows are padded to a multiple of four elements; the view
+    has the cols columns.  Not wanted: (None, None, pitch)"""
+    padded = (cols + 3) // 4 * 4
+    storage = z(tuple(lead) + (padded,), dtype) if wanted else None
+    return storage, (storage[..., :cols] if wanted else None), padded
+
+
+def _subset(outputs, known):
+    if set(outputs) - set(known):
+        raise ValueError("outputs: a subset of %s" % (known,))
+
+
+def _follow(t, rows, strict=False):
+    """whether the images of t, [..., rows, cols], follow one another at rows * pitch; a dimension of length 1 may have any stride
+    unless strict"""
+    step, dense = rows * int(t.stride(-2)), True
+    for n, stride in zip(t.shape[-3::-1], t.stride()[-3::-1]):
+        dense = dense and ((n == 1 and not strict) or int(stride) == step)
+        step *= int(n)
+    return dense
+
+
+def _images(t, name, dtype, shape, type_name=None, in_bytes=False):
+    """(pointer, pitch in elements or in bytes) of a tensor of this dtype, shape = [B, frames, rows, cols] or [B * frames, rows,
+    cols], whose images follow one another at rows * pitch (a pitch above cols is allowed)"""
+    B, F, rows, cols = shape
+    if t.dtype != dtype or t.stride(-1) != 1 or tuple(t.shape) not in ((B, F, rows, cols), (B * F, rows, cols)):
+        raise ValueError("%s must be a %s tensor [%d, %d, %d, %d] or [%d, %d, %d] with contiguous rows" % (name, type_name or dtype, B, F, rows, cols, B * F, rows, cols))
+    if int(t.stride(-2)) < cols or not _follow(t, rows):
+        raise ValueError("the images of %s must follow one another at rows * pitch" % name)
+    return t.data_ptr(), int(t.stride(-2)) * (t.element_size() if in_bytes else 1)
+
+
+def _int32_ptr(t, name, shape, any_type=False):
+    """the pointer of an optional contiguous int32 tensor of this shape (None stays None); any_type: its type is not looked at"""
+    import torch
+    if t is None:
+        return None
+    if tuple(t.shape) != tuple(shape) or not (any_type or t.dtype == torch.int32) or not t.is_contiguous():
+        raise ValueError("%s must be a contiguous %s[%s]" % (name, "" if any_type else "int32 tensor ", ", ".join("%d" % n for n in shape)))
+    return t.data_ptr()
+
+
+def _n_images_ptr(n_images, batch):
+    """n_images must be a contiguous int32 tensor [batch], or None: every sequence has `frames` images"""
+    return _int32_ptr(n_images, "n_images", (batch,))
+
+
+def _stereo_common(p, camera, n_disparities, min_disparity, uniqueness_percent, lr_max_diff):
+    """the fields and the refusals that prs_dense_stereo_params and prs_sgm_stereo_params share; bf = float32(float64(fx) *
+    float64(baseline_m))"""
+    p.n_disparities, p.min_disparity, p.uniqueness_percent, p.lr_max_diff = int(n_disparities), int(min_disparity), int(uniqueness_percent), int(lr_max_diff)
+    with np.errstate(over="ignore"):  # a product beyond float32 becomes inf and is refused below
+        p.bf = float(np.float32(np.float64(camera["fx"]) * np.float64(camera["baseline_m"])))
+    if not 1 <= p.n_disparities <= 256:
+        raise ValueError("n_disparities must lie in 1 .. 256")
+    if p.min_disparity < 0 or p.min_disparity + p.n_disparities > 4096:
+        raise ValueError("min_disparity must be at least 0 and min_disparity + n_disparities at most 4096")
+    if not 0 <= p.uniqueness_percent <= 99:
+        raise ValueError("uniqueness_percent must lie in 0 .. 99")
+    if not -1 <= p.lr_max_diff <= 255:
+        raise ValueError("lr_max_diff must lie in -1 .. 255")
+    if not (np.isfinite(p.bf) and p.bf > 0.0):
+        raise ValueError("fx * baseline_m must be finite and positive as a float32")
+    return p
+
+
 # ---- dense RGB-D cloud: the depth pixels of a sequence's frames in the world frame (include/proslam_hip.h prs_depth_cloud_*) ----
 def depth_cloud_params(camera, range_min=0.1, range_max=10.0, step=1, depth_type="u16", scale=1.0, sensor_in_robot=None):
     """prs_depth_cloud_params.  camera: a dictionary with fx, fy, cx, cy (configs.*["camera"]); range_min / range_max in metres
@@ -2567,9 +2609,7 @@ def depth_cloud_params(camera, range_min=0.1, range_max=10.0, step=1, depth_type
     PRS_DEPTH_* value; scale = depth_scaling_factor_to_meters (1e-3 for the 16-bit millimetre images of icl and tum);
     sensor_in_robot [4, 4] or 16 values, row-major (None: the identity, the poses are the camera's)"""
     p = _lib.DepthCloudParams()
-    if isinstance(depth_type, str) and depth_type not in _DEPTH_TYPES:
-        raise ValueError("depth_type: one of %s" % (sorted(_DEPTH_TYPES),))
-    p.depth_type = _DEPTH_TYPES[depth_type] if isinstance(depth_type, str) else int(depth_type)
+    p.depth_type = _depth_type(depth_type)
     p.depth_scaling_factor_to_meters = float(scale)
     p.fx, p.fy, p.cx, p.cy = (float(camera[k]) for k in ("fx", "fy", "cx", "cy"))
     p.range_min, p.range_max, p.step = float(range_min), float(range_max), int(step)
@@ -2597,14 +2637,12 @@ class DepthCloudBatch:
 
     def __init__(self, batch, frames, rows, cols, out_stride, outputs=OPTIONAL, device=0):
         import torch
-        if set(outputs) - set(self.OPTIONAL):
-            raise ValueError("outputs: a subset of %s" % (self.OPTIONAL,))
+        _subset(outputs, self.OPTIONAL)
         B, F, n = int(batch), int(frames), int(out_stride)
         if B < 1 or F < 1 or int(rows) < 1 or int(cols) < 1 or n < 1:
             raise ValueError("batch, frames, rows, cols and out_stride must be at least 1")
         self.batch, self.frames, self.rows, self.cols, self.out_stride = B, F, int(rows), int(cols), n
-        dev = torch.device("cuda", device) if isinstance(device, int) else device
-        z = lambda shape, dt: torch.zeros(shape, dtype=dt, device=dev)  # noqa: E731
+        z = _zeros_on(device)
         self.xyz = z((B, n, 4), torch.float32)
         self.node = z((B, n), torch.int32) if "frame" in outputs else None  # the image of a row, where a world map has the node
         self.row = z((B, n), torch.int32) if "pixel" in outputs else None   # v * cols + u, where a world map has the landmark's row
@@ -2622,7 +2660,7 @@ class DepthCloudBatch:
         B, F = self.batch, self.frames
         if depth.dim() != 4 or tuple(depth.shape[:3]) != (B, F, self.rows) or int(depth.shape[3]) < self.cols or depth.stride(3) != 1:
             raise ValueError("depth must be [%d, %d, %d, >= %d] with contiguous rows" % (B, F, self.rows, self.cols))
-        if int(depth.stride(1)) != self.rows * int(depth.stride(2)) or int(depth.stride(0)) != F * int(depth.stride(1)):
+        if not _follow(depth, self.rows, strict=True):
             raise ValueError("the images of depth must follow one another at rows * pitch")
         if pose.dim() != 3 or int(pose.shape[0]) != B or int(pose.shape[2]) != 16 or not pose.is_contiguous():
             raise ValueError("pose must be a contiguous [%d, pose_stride, 16]" % B)
@@ -2632,13 +2670,10 @@ class DepthCloudBatch:
         d.depth, d.pose, d.n_images = depth.data_ptr(), pose.data_ptr(), n_images.data_ptr()
         if gray is not None:
             if tuple(gray.shape[:3]) != (B, F, self.rows) or int(gray.shape[3]) < self.cols or gray.stride(3) != 1 or \
-                    int(gray.stride(1)) != self.rows * int(gray.stride(2)) or int(gray.stride(0)) != F * int(gray.stride(1)):
+                    not _follow(gray, self.rows, strict=True):
                 raise ValueError("gray must be laid out like depth")
             d.gray, d.gray_pitch = gray.data_ptr(), int(gray.stride(2))
-        if frame_index is not None:
-            if tuple(frame_index.shape) != (B, F) or not frame_index.is_contiguous():
-                raise ValueError("frame_index must be a contiguous [%d, %d]" % (B, F))
-            d.frame_index = frame_index.data_ptr()
+        d.frame_index = _int32_ptr(frame_index, "frame_index", (B, F), any_type=True)
         d.n_base = self.n_out.data_ptr() if append else None
         for name in ("n_out", "n_total", "n_skipped", "status", "workspace"):
             setattr(d, name, getattr(self, name).data_ptr())
@@ -2649,9 +2684,7 @@ class DepthCloudBatch:
         return d
 
     def _launch(self, ctx, params, d):
-        rc = _lib.load().prs_depth_cloud_batch_run(ctx._h, C.byref(params), C.byref(d))
-        _check(ctx, rc, "prs_depth_cloud_batch_run")
-        return rc
+        return _run(ctx, "prs_depth_cloud_batch_run", C.byref(params), C.byref(d))
 
     def run(self, ctx, params, depth, pose, n_images, frame_index=None, gray=None, append=False):
         """enqueue the clouds of every sequence (asynchronous); per-sequence status lands in self.status.  append: the rows go behind
@@ -2681,23 +2714,10 @@ def dense_stereo_params(camera, n_disparities=128, min_disparity=0, aggregation_
     returns); bf = float32(float64(fx) * float64(baseline_m)).  Disparities min_disparity .. min_disparity + n_disparities - 1, a box of
     (2 * aggregation_radius + 1)^2 census costs, uniqueness_percent 0 = no test, lr_max_diff -1 = no left-right check.  Raises
     ValueError on every value the library refuses"""
-    p = _lib.DenseStereoParams()
-    p.n_disparities, p.min_disparity, p.aggregation_radius = int(n_disparities), int(min_disparity), int(aggregation_radius)
-    p.uniqueness_percent, p.lr_max_diff = int(uniqueness_percent), int(lr_max_diff)
-    with np.errstate(over="ignore"):  # a product beyond float32 becomes inf and is refused below
-        p.bf = float(np.float32(np.float64(camera["fx"]) * np.float64(camera["baseline_m"])))
-    if not 1 <= p.n_disparities <= 256:
-        raise ValueError("n_disparities must lie in 1 .. 256")
-    if p.min_disparity < 0 or p.min_disparity + p.n_disparities > 4096:
-        raise ValueError("min_disparity must be at least 0 and min_disparity + n_disparities at most 4096")
+    p = _stereo_common(_lib.DenseStereoParams(), camera, n_disparities, min_disparity, uniqueness_percent, lr_max_diff)
+    p.aggregation_radius = int(aggregation_radius)
     if not 0 <= p.aggregation_radius <= 7:
         raise ValueError("aggregation_radius must lie in 0 .. 7")
-    if not 0 <= p.uniqueness_percent <= 99:
-        raise ValueError("uniqueness_percent must lie in 0 .. 99")
-    if not -1 <= p.lr_max_diff <= 255:
-        raise ValueError("lr_max_diff must lie in -1 .. 255")
-    if not (np.isfinite(p.bf) and p.bf > 0.0):
-        raise ValueError("fx * baseline_m must be finite and positive as a float32")
     return p
 
 
@@ -2711,21 +2731,16 @@ class DenseStereoBatch:
 
     def __init__(self, batch, frames, rows, cols, outputs=OUTPUTS, device=0):
         import torch
-        if set(outputs) - set(self.OUTPUTS):
-            raise ValueError("outputs: a subset of %s" % (self.OUTPUTS,))
+        _subset(outputs, self.OUTPUTS)
         if "disparity" not in outputs and "depth" not in outputs:
             raise ValueError("outputs: disparity, depth or both")
         B, F = int(batch), int(frames)
         if B < 1 or F < 1 or int(rows) < 1 or int(cols) < 1:
             raise ValueError("batch, frames, rows and cols must be at least 1")
         self.batch, self.frames, self.rows, self.cols = B, F, int(rows), int(cols)
-        dev = torch.device("cuda", device) if isinstance(device, int) else device
-        z = lambda shape, dt: torch.zeros(shape, dtype=dt, device=dev)  # noqa: E731
-        padded = (self.cols + 3) // 4 * 4
-        self._disparity = z((B, F, self.rows, padded), torch.float32) if "disparity" in outputs else None
-        self._depth = z((B, F, self.rows, padded), torch.float32) if "depth" in outputs else None
-        self.disparity = self._disparity[..., :self.cols] if self._disparity is not None else None
-        self.depth = self._depth[..., :self.cols] if self._depth is not None else None
+        z = _zeros_on(device)
+        self._disparity, self.disparity, padded = _padded_rows(z, (B, F, self.rows), self.cols, torch.float32, "disparity" in outputs)
+        self._depth, self.depth, padded = _padded_rows(z, (B, F, self.rows), self.cols, torch.float32, "depth" in outputs)
         self.out_pitch = padded * 4
         self.n_valid = z((B, F), torch.int32) if "n_valid" in outputs else None
         self.status = z((B,), torch.int32)
@@ -2737,23 +2752,6 @@ class DenseStereoBatch:
     def _workspace_bytes(self):
         return int(_lib.load().prs_dense_stereo_workspace_bytes(self.batch, self.frames, self.rows, self.cols, 1, 1))
 
-    def _images(self, t, name):
-        """(pointer, pitch in bytes) of a uint8 tensor [B, frames, rows, cols] or [B * frames, rows, cols] whose images follow one
-        another at rows * pitch (a pitch above cols is allowed)"""
-        import torch
-        B, F, rows, cols = self.batch, self.frames, self.rows, self.cols
-        if t.dtype != torch.uint8 or t.stride(-1) != 1 or tuple(t.shape) not in ((B, F, rows, cols), (B * F, rows, cols)):
-            raise ValueError("%s must be a uint8 tensor [%d, %d, %d, %d] or [%d, %d, %d] with contiguous rows" % (name, B, F, rows, cols, B * F, rows, cols))
-        pitch = int(t.stride(-2))
-        image = rows * pitch
-        if t.dim() == 4:
-            dense = (F == 1 or int(t.stride(1)) == image) and (B == 1 or int(t.stride(0)) == F * image)
-        else:
-            dense = B * F == 1 or int(t.stride(0)) == image
-        if pitch < cols or not dense:
-            raise ValueError("the images of %s must follow one another at rows * pitch" % name)
-        return t.data_ptr(), pitch
-
     def descriptor(self, left, right, n_images=None):
         """the prs_dense_stereo_batch of device tensors: left, right uint8 [B, frames, rows, cols] or [B * frames, rows, cols] (the two
         halves of a RectifyBatch's dst, with their pitch), n_images [B] int32 or None = frames"""
@@ -2763,12 +2761,11 @@ class DenseStereoBatch:
 
     def _fill(self, d, left, right, n_images):
         d.batch, d.frames, d.rows, d.cols, d.out_pitch = self.batch, self.frames, self.rows, self.cols, self.out_pitch
-        d.left, d.left_pitch = self._images(left, "left")
-        d.right, d.right_pitch = self._images(right, "right")
-        if n_images is not None:
-            if tuple(n_images.shape) != (self.batch,) or n_images.dtype != self.status.dtype or not n_images.is_contiguous():
-                raise ValueError("n_images must be a contiguous int32 tensor [%d]" % self.batch)
-            d.n_images = n_images.data_ptr()
+        import torch
+        shape = (self.batch, self.frames, self.rows, self.cols)
+        d.left, d.left_pitch = _images(left, "left", torch.uint8, shape, "uint8")
+        d.right, d.right_pitch = _images(right, "right", torch.uint8, shape, "uint8")
+        d.n_images = _n_images_ptr(n_images, self.batch)
         d.disparity = self._disparity.data_ptr() if self._disparity is not None else None
         d.depth = self._depth.data_ptr() if self._depth is not None else None
         d.n_valid = self.n_valid.data_ptr() if self.n_valid is not None else None
@@ -2777,9 +2774,7 @@ class DenseStereoBatch:
     def run(self, ctx, params, left, right, n_images=None):
         """enqueue the disparity and depth images of every pair (asynchronous); per-sequence status lands in self.status"""
         d = self.descriptor(left, right, n_images)
-        rc = _lib.load().prs_dense_stereo_batch_run(ctx._h, C.byref(params), C.byref(d))
-        _check(ctx, rc, "prs_dense_stereo_batch_run")
-        return rc
+        return _run(ctx, "prs_dense_stereo_batch_run", C.byref(params), C.byref(d))
 
 
 # ---- semi-global dense stereo: rectified pairs to disparity and depth images by path aggregation (include/proslam_hip.h prs_sgm_stereo_*) ----
@@ -2790,25 +2785,12 @@ def sgm_stereo_params(camera, n_disparities=configs.SGM_STEREO["n_disparities"],
     min_disparity .. min_disparity + n_disparities - 1, the penalties 0 <= p1 <= p2 <= 4095 of a path's step of one disparity and of a
     larger one, n_paths 4 or 8, uniqueness_percent 0 = no test, lr_max_diff -1 = no left-right check.  The defaults are
     configs.SGM_STEREO (128, 0, 10, 120, 8, 10, 1).  Raises ValueError on every value the library refuses"""
-    p = _lib.SgmStereoParams()
-    p.n_disparities, p.min_disparity, p.p1, p.p2, p.n_paths = int(n_disparities), int(min_disparity), int(p1), int(p2), int(n_paths)
-    p.uniqueness_percent, p.lr_max_diff = int(uniqueness_percent), int(lr_max_diff)
-    with np.errstate(over="ignore"):  # a product beyond float32 becomes inf and is refused below
-        p.bf = float(np.float32(np.float64(camera["fx"]) * np.float64(camera["baseline_m"])))
-    if not 1 <= p.n_disparities <= 256:
-        raise ValueError("n_disparities must lie in 1 .. 256")
-    if p.min_disparity < 0 or p.min_disparity + p.n_disparities > 4096:
-        raise ValueError("min_disparity must be at least 0 and min_disparity + n_disparities at most 4096")
+    p = _stereo_common(_lib.SgmStereoParams(), camera, n_disparities, min_disparity, uniqueness_percent, lr_max_diff)
+    p.p1, p.p2, p.n_paths = int(p1), int(p2), int(n_paths)
     if not 0 <= p.p1 <= p.p2 <= 4095:
         raise ValueError("the penalties must satisfy 0 <= p1 <= p2 <= 4095")
     if p.n_paths not in (4, 8):
         raise ValueError("n_paths must be 4 or 8")
-    if not 0 <= p.uniqueness_percent <= 99:
-        raise ValueError("uniqueness_percent must lie in 0 .. 99")
-    if not -1 <= p.lr_max_diff <= 255:
-        raise ValueError("lr_max_diff must lie in -1 .. 255")
-    if not (np.isfinite(p.bf) and p.bf > 0.0):
-        raise ValueError("fx * baseline_m must be finite and positive as a float32")
     return p
 
 
@@ -2853,9 +2835,7 @@ class SgmStereoBatch(DenseStereoBatch):
         if params.n_disparities > self.n_disparities:
             raise ValueError("the workspace was sized for %d disparities, the params have %d" % (self.n_disparities, params.n_disparities))
         d = self.descriptor(left, right, n_images)
-        rc = _lib.load().prs_sgm_stereo_batch_run(ctx._h, C.byref(params), C.byref(d))
-        _check(ctx, rc, "prs_sgm_stereo_batch_run")
-        return rc
+        return _run(ctx, "prs_sgm_stereo_batch_run", C.byref(params), C.byref(d))
 
 
 # ---- speckle filter: the small segments of a disparity or depth image set to 0 in place (include/proslam_hip.h prs_speckle_*) ----
@@ -2890,17 +2870,13 @@ class SpeckleFilterBatch:
 
     def __init__(self, batch, frames, rows, cols, outputs=("n_kept", "n_removed"), device=0):
         import torch
-        if set(outputs) - set(self.OUTPUTS):
-            raise ValueError("outputs: a subset of %s" % (self.OUTPUTS,))
+        _subset(outputs, self.OUTPUTS)
         B, F = int(batch), int(frames)
         if B < 1 or F < 1 or int(rows) < 1 or int(cols) < 1:
             raise ValueError("batch, frames, rows and cols must be at least 1")
         self.batch, self.frames, self.rows, self.cols = B, F, int(rows), int(cols)
-        dev = torch.device("cuda", device) if isinstance(device, int) else device
-        z = lambda shape, dt: torch.zeros(shape, dtype=dt, device=dev)  # noqa: E731
-        padded = (self.cols + 3) // 4 * 4
-        self._label = z((B, F, self.rows, padded), torch.int32) if "label" in outputs else None
-        self.label = self._label[..., :self.cols] if self._label is not None else None
+        z = _zeros_on(device)
+        self._label, self.label, padded = _padded_rows(z, (B, F, self.rows), self.cols, torch.int32, "label" in outputs)
         self.label_pitch = padded * 4
         self.n_kept = z((B, F), torch.int32) if "n_kept" in outputs else None
         self.n_removed = z((B, F), torch.int32) if "n_removed" in outputs else None
@@ -2910,35 +2886,16 @@ class SpeckleFilterBatch:
             raise ValueError("rows * cols and batch * frames * rows * cols must stay below 2^31")
         self.workspace = z((nbytes,), torch.uint8)
 
-    def _images(self, t, name, pixel_type):
-        """(pointer, pitch in bytes) of a tensor of the pixel type, [B, frames, rows, cols] or [B * frames, rows, cols], whose images
-        follow one another at rows * pitch (a pitch above cols is allowed)"""
-        import torch
-        B, F, rows, cols = self.batch, self.frames, self.rows, self.cols
-        dtype = {PIXEL_U16: torch.uint16, PIXEL_F32: torch.float32}[pixel_type]
-        if t.dtype != dtype or t.stride(-1) != 1 or tuple(t.shape) not in ((B, F, rows, cols), (B * F, rows, cols)):
-            raise ValueError("%s must be a %s tensor [%d, %d, %d, %d] or [%d, %d, %d] with contiguous rows" % (name, dtype, B, F, rows, cols, B * F, rows, cols))
-        pitch = int(t.stride(-2))
-        image = rows * pitch
-        if t.dim() == 4:
-            dense = (F == 1 or int(t.stride(1)) == image) and (B == 1 or int(t.stride(0)) == F * image)
-        else:
-            dense = B * F == 1 or int(t.stride(0)) == image
-        if pitch < cols or not dense:
-            raise ValueError("the images of %s must follow one another at rows * pitch" % name)
-        return t.data_ptr(), pitch * t.element_size()
-
     def descriptor(self, params, image, companion=None, n_images=None):
         """the prs_speckle_batch of device tensors: image (and companion) of params' pixel types, n_images [B] int32 or None = frames"""
         d = _lib.SpeckleBatch()
         d.batch, d.frames, d.rows, d.cols = self.batch, self.frames, self.rows, self.cols
-        d.image, d.pitch = self._images(image, "image", params.pixel_type)
+        import torch
+        types, shape = {PIXEL_U16: torch.uint16, PIXEL_F32: torch.float32}, (self.batch, self.frames, self.rows, self.cols)
+        d.image, d.pitch = _images(image, "image", types[params.pixel_type], shape, in_bytes=True)
         if companion is not None:
-            d.companion, d.companion_pitch = self._images(companion, "companion", params.companion_type)
-        if n_images is not None:
-            if tuple(n_images.shape) != (self.batch,) or n_images.dtype != self.status.dtype or not n_images.is_contiguous():
-                raise ValueError("n_images must be a contiguous int32 tensor [%d]" % self.batch)
-            d.n_images = n_images.data_ptr()
+            d.companion, d.companion_pitch = _images(companion, "companion", types[params.companion_type], shape, in_bytes=True)
+        d.n_images = _n_images_ptr(n_images, self.batch)
         if self._label is not None:
             d.label, d.label_pitch = self._label.data_ptr(), self.label_pitch
         d.n_kept = self.n_kept.data_ptr() if self.n_kept is not None else None
@@ -2949,9 +2906,7 @@ class SpeckleFilterBatch:
     def run(self, ctx, params, image, companion=None, n_images=None):
         """enqueue the filter of every image, in place (asynchronous); per-sequence status lands in self.status"""
         d = self.descriptor(params, image, companion, n_images)
-        rc = _lib.load().prs_speckle_batch_run(ctx._h, C.byref(params), C.byref(d))
-        _check(ctx, rc, "prs_speckle_batch_run")
-        return rc
+        return _run(ctx, "prs_speckle_batch_run", C.byref(params), C.byref(d))
 
 
 # ---- depth consistency filter: depth pixels cross-checked against the neighbouring frames (include/proslam_hip.h prs_depth_consistency_*) ----
@@ -2963,11 +2918,7 @@ def depth_consistency_params(camera, window=2, stride=1, max_rel_diff=0.02, min_
     configs.DEPTH_CONSISTENCY); range_min / range_max, depth_type, scale and sensor_in_robot as in depth_cloud_params.  Raises
     ValueError on every value the library refuses"""
     p = _lib.DepthConsistencyParams()
-    if isinstance(depth_type, str) and depth_type not in _DEPTH_TYPES:
-        raise ValueError("depth_type: one of %s" % (sorted(_DEPTH_TYPES),))
-    p.depth_type = _DEPTH_TYPES[depth_type] if isinstance(depth_type, str) else int(depth_type)
-    if p.depth_type not in _DEPTH_TYPES.values():
-        raise ValueError("depth_type: one of %s" % (sorted(_DEPTH_TYPES),))
+    p.depth_type = _depth_type(depth_type, known=True)
     for name, value, lo, hi in (("window", window, 1, 8), ("stride", stride, 1, 0x7fffffff), ("min_support", min_support, 0, 16),
                                 ("max_violation", max_violation, 0, 16)):
         if int(value) != value or not lo <= int(value) <= hi:
@@ -3002,13 +2953,8 @@ class DepthConsistencyBatch:
 
     def __init__(self, batch, frames, rows, cols, window, depth_type="u16", outputs=("n_kept", "n_removed"), device=0):
         import torch
-        if set(outputs) - set(self.OUTPUTS):
-            raise ValueError("outputs: a subset of %s" % (self.OUTPUTS,))
-        if isinstance(depth_type, str) and depth_type not in _DEPTH_TYPES:
-            raise ValueError("depth_type: one of %s" % (sorted(_DEPTH_TYPES),))
-        self.depth_type = _DEPTH_TYPES[depth_type] if isinstance(depth_type, str) else int(depth_type)
-        if self.depth_type not in _DEPTH_TYPES.values():
-            raise ValueError("depth_type: one of %s" % (sorted(_DEPTH_TYPES),))
+        _subset(outputs, self.OUTPUTS)
+        self.depth_type = _depth_type(depth_type, known=True)
         B, F = int(batch), int(frames)
         if B < 1 or F < 1 or int(rows) < 1 or int(cols) < 1:
             raise ValueError("batch, frames, rows and cols must be at least 1")
@@ -3016,15 +2962,10 @@ class DepthConsistencyBatch:
             raise ValueError("window must lie in 1 .. 8")
         self.batch, self.frames, self.rows, self.cols, self.window = B, F, int(rows), int(cols), int(window)
         self.dtype = torch.uint16 if self.depth_type == DEPTH_U16 else torch.float32
-        dev = torch.device("cuda", device) if isinstance(device, int) else device
-        z = lambda shape, dt: torch.zeros(shape, dtype=dt, device=dev)  # noqa: E731
-        padded = (self.cols + 3) // 4 * 4
-        self._out = z((B, F, self.rows, padded), self.dtype)
-        self.out = self._out[..., :self.cols]
-        self._support = z((B, F, self.rows, padded), torch.uint8) if "support" in outputs else None
-        self._violation = z((B, F, self.rows, padded), torch.uint8) if "violation" in outputs else None
-        self.support = self._support[..., :self.cols] if self._support is not None else None
-        self.violation = self._violation[..., :self.cols] if self._violation is not None else None
+        z = _zeros_on(device)
+        self._out, self.out, _ = _padded_rows(z, (B, F, self.rows), self.cols, self.dtype)
+        self._support, self.support, _ = _padded_rows(z, (B, F, self.rows), self.cols, torch.uint8, "support" in outputs)
+        self._violation, self.violation, _ = _padded_rows(z, (B, F, self.rows), self.cols, torch.uint8, "violation" in outputs)
         self.n_kept = z((B, F), torch.int32) if "n_kept" in outputs else None
         self.n_removed = z((B, F), torch.int32) if "n_removed" in outputs else None
         self.n_skipped = z((B,), torch.int32) if "n_skipped" in outputs else None
@@ -3042,7 +2983,7 @@ class DepthConsistencyBatch:
         if depth.dtype != self.dtype or depth.dim() != 4 or tuple(depth.shape[:3]) != (B, F, self.rows) or int(depth.shape[3]) < self.cols or \
                 depth.stride(3) != 1:
             raise ValueError("depth must be a %s tensor [%d, %d, %d, >= %d] with contiguous rows" % (self.dtype, B, F, self.rows, self.cols))
-        if int(depth.stride(1)) != self.rows * int(depth.stride(2)) or int(depth.stride(0)) != F * int(depth.stride(1)):
+        if not _follow(depth, self.rows, strict=True):
             raise ValueError("the images of depth must follow one another at rows * pitch")
         if pose.dim() != 3 or int(pose.shape[0]) != B or int(pose.shape[2]) != 16 or not pose.is_contiguous():
             raise ValueError("pose must be a contiguous [%d, pose_stride, 16]" % B)
@@ -3052,14 +2993,8 @@ class DepthConsistencyBatch:
         d.pitch, d.out_pitch, d.count_pitch = int(depth.stride(2)) * es, int(self._out.stride(2)) * es, int(self._out.stride(2))
         d.pose_stride = int(pose.shape[1])
         d.depth, d.pose, d.out = depth.data_ptr(), pose.data_ptr(), self._out.data_ptr()
-        if n_images is not None:
-            if tuple(n_images.shape) != (B,) or n_images.dtype != self.status.dtype or not n_images.is_contiguous():
-                raise ValueError("n_images must be a contiguous int32 tensor [%d]" % B)
-            d.n_images = n_images.data_ptr()
-        if frame_index is not None:
-            if tuple(frame_index.shape) != (B, F) or frame_index.dtype != self.status.dtype or not frame_index.is_contiguous():
-                raise ValueError("frame_index must be a contiguous int32 tensor [%d, %d]" % (B, F))
-            d.frame_index = frame_index.data_ptr()
+        d.n_images = _n_images_ptr(n_images, B)
+        d.frame_index = _int32_ptr(frame_index, "frame_index", (B, F))
         for name, t in (("support", self._support), ("violation", self._violation), ("n_kept", self.n_kept), ("n_removed", self.n_removed),
                         ("n_skipped", self.n_skipped)):
             setattr(d, name, t.data_ptr() if t is not None else None)
@@ -3072,8 +3007,7 @@ class DepthConsistencyBatch:
         if params.window > self.window:
             raise ValueError("params.window %d exceeds the window %d this batch was sized for" % (params.window, self.window))
         d = self.descriptor(depth, pose, n_images, frame_index)
-        rc = _lib.load().prs_depth_consistency_batch_run(ctx._h, C.byref(params), C.byref(d))
-        _check(ctx, rc, "prs_depth_consistency_batch_run")
+        _run(ctx, "prs_depth_consistency_batch_run", C.byref(params), C.byref(d))
         return self.out
 
 
@@ -3213,15 +3147,12 @@ class RectifyBatch:
             raise ValueError("image sizes must be at least 1")
         self.np_dtype = _PIXEL_NP.get(params.pixel_type, np.uint8)  # an unknown type is the library's to refuse
         self.dtype = {np.uint8: torch.uint8, np.uint16: torch.uint16, np.float32: torch.float32}[self.np_dtype]
-        dev = torch.device("cuda", ctx.device)
+        dev, z = torch.device("cuda", ctx.device), _zeros_on(ctx.device)
         arr = (_lib.RectifyMap * len(maps))(*[m.struct() for m in maps])
         host = np.frombuffer(arr, dtype=np.uint8).copy()
         self.maps = torch.from_numpy(host).to(dev)
-        rows, cols = self.dst_shape
-        self._dst = torch.zeros((B, rows, (cols + 3) // 4 * 4), dtype=self.dtype, device=dev)
-        self.dst = self._dst[:, :, :cols]
-        self.n_border = torch.zeros((B,), dtype=torch.int32, device=dev)
-        self.status = torch.zeros((B,), dtype=torch.int32, device=dev)
+        self._dst, self.dst, _ = _padded_rows(z, (B, self.dst_shape[0]), self.dst_shape[1], self.dtype)
+        self.n_border, self.status = z((B,), torch.int32), z((B,), torch.int32)
         self.map_of = None
         if stereo:
             self.map_of = torch.cat([torch.zeros(B // 2, dtype=torch.int32), torch.ones(B // 2, dtype=torch.int32)]).to(dev)
@@ -3232,15 +3163,12 @@ class RectifyBatch:
         if src.dtype != self.dtype or tuple(src.shape) != (self.batch, rows, cols) or src.stride(2) != 1 or \
                 (self.batch > 1 and src.stride(0) != rows * src.stride(1)):
             raise ValueError("src must be a %s tensor [%d, %d, %d] with dense images (stride(0) = rows * pitch)" % (self.dtype, self.batch, rows, cols))
-        map_of = self.map_of if map_of is None else map_of
-        if map_of is not None and (map_of.dtype != self.n_border.dtype or tuple(map_of.shape) != (self.batch,) or not map_of.is_contiguous()):
-            raise ValueError("map_of must be a contiguous int32 tensor [%d]" % self.batch)
         d = _lib.RectifyBatch()
+        d.map_of = _int32_ptr(self.map_of if map_of is None else map_of, "map_of", (self.batch,))
         es = src.element_size()
         d.batch, d.src_rows, d.src_cols, d.src_pitch, d.src = self.batch, rows, cols, int(src.stride(1)) * es, src.data_ptr()
         d.dst_rows, d.dst_cols, d.dst_pitch, d.dst = self.dst_shape[0], self.dst_shape[1], int(self._dst.stride(1)) * es, self._dst.data_ptr()
         d.n_maps, d.maps = self.n_maps, self.maps.data_ptr()
-        d.map_of = map_of.data_ptr() if map_of is not None else None
         d.n_border, d.status = self.n_border.data_ptr(), self.status.data_ptr()
         return d
 
@@ -3248,6 +3176,5 @@ class RectifyBatch:
         """enqueue the rectification of src [batch, rows, cols] (asynchronous; map_of: int32 [batch] or None = the stereo layout's,
         else map 0 for every image); returns dst.  Per-image status and border counts land in self.status and self.n_border."""
         d = self.descriptor(src, map_of)
-        rc = _lib.load().prs_rectify_batch_run(self.ctx._h, C.byref(self.params), C.byref(d))
-        _check(self.ctx, rc, "prs_rectify_batch_run")
+        _run(self.ctx, "prs_rectify_batch_run", C.byref(self.params), C.byref(d))
         return self.dst

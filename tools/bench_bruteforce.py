@@ -1,7 +1,8 @@
 """brute-force matcher throughput: B cloud pairs of N x N descriptors resident in HBM
 usage: python tools/bench_bruteforce.py [B] [N] [max_dist]                       uniform random rows, one true partner per point
        python tools/bench_bruteforce.py real [B] [max_dist] [target] [capacity]  descriptors of real KITTI stereo pairs
-the dense phase is the context's default (popcount kernels) unless PRS_BF_MFMA=1 / auto is set; run(..., dense=ops.BF_DENSE_*) picks one"""
+the dense phase is the context's default (PRS_BF_DENSE_MATRIX_WHEN_FULL: the matrix cores for 32 or more large pairs, else the popcount
+kernels) unless PRS_BF_MFMA = 0 / auto / 1 sets another; run(..., dense=ops.BF_DENSE_*) picks one"""
 import os
 import sys
 
