@@ -24,6 +24,20 @@
  *   keypoint coordinates 0 <= u < 32768, 0 <= v < image_rows <= 4096; keypoints per image <= 8192
  *   (stereo matcher) / fixed points <= 32767 (lattice finder, the reference's own int16 limit,
  *   CF/correspondence_finder_projective_square_impl.cpp:20-22).
+ *
+ * Extent of a device array (what the caller must own; tests/test_guard_*_gpu.py run the entry points they cover with nothing more):
+ *   - an array [batch][stride][...] has batch * stride whole rows, also where a count is below its stride; rows from the count to
+ *     the stride are neither read nor written unless the entry point says so;
+ *   - a pitched image array [images][rows][pitch] ends at the LAST PIXEL of the last row of the last image:
+ *     ((images * rows - 1) * pitch + cols * element size) bytes.  The padding behind the last row need not exist, so a view of the
+ *     right half of a side-by-side allocation, whose last row ends where the allocation ends, is a valid argument.  Padding between
+ *     rows is never written and its values reach no result.  This holds for images and seeding_mask of the two extractors, depth of
+ *     prs_depth_batch, dst of the rectifier, depth and gray of the dense cloud, left, right, disparity and depth of both stereo
+ *     stages, image, companion and label of the speckle filter and depth, out, support and violation of the consistency filter.
+ *     The one exception is src of prs_rectify_batch when src and src_pitch are both multiples of 16 bytes (see there): its last row
+ *     then has cols * element size rounded up to 16 bytes, which lies inside the pitch;
+ *   - a workspace has exactly the bytes its prs_*_workspace_bytes function returns for the sizes and switches of that call; it need
+ *     not be cleared.
  */
 #ifndef PROSLAM_HIP_H
 #define PROSLAM_HIP_H
@@ -200,8 +214,8 @@ PRS_API int prs_stereo_match(prs_context* ctx,
 typedef struct {
   int32_t batch;
   int32_t stride;            /* keypoint capacity per image and frame (elements) */
-  const prs_kp2* left_kp;    /* [batch][stride] */
-  const uint8_t* left_desc;  /* [batch][stride][32], 16-byte aligned */
+  const prs_kp2* left_kp;    /* [batch][stride], 8-byte aligned (so is right_kp) */
+  const uint8_t* left_desc;  /* [batch][stride][32], 16-byte aligned (so are right_desc and the epilogue's fixed_uvuv, fixed_desc, fixed_xyz) */
   const int32_t* n_left;     /* [batch] */
   const prs_kp2* right_kp;
   const uint8_t* right_desc;
@@ -236,7 +250,8 @@ PRS_API int prs_triangulate(prs_context* ctx,
                             float* xyz,        /* host [n][3] */
                             uint8_t* valid);   /* host [n] */
 
-/* device: uvuv [n][4] -> xyz4 [n][4] = (x, y, z, valid).  At most 2048 workgroups stride over the points: any n fits one launch */
+/* device: uvuv [n][4] -> xyz4 [n][4] = (x, y, z, valid), both 16-byte aligned (a row moves as one float4; PRS_ERR_UNSUPPORTED
+ * otherwise, nothing launched).  At most 2048 workgroups stride over the points: any n fits one launch */
 PRS_API int prs_triangulate_dev(prs_context* ctx,
                                 const prs_triangulator_params* params,
                                 const float* d_uvuv,
@@ -546,7 +561,8 @@ PRS_API void prs_info_scale_from_nopt(const uint32_t* n_opt, int32_t n, float* s
 typedef struct {
   int32_t batch;                   /* independent scenes (one per sequence) */
   int32_t stride;                  /* row stride (points) of every per-scene array */
-  const float* scene_xyzw;         /* [batch][stride][4] local-map points; w is carried through (information scale) */
+  const float* scene_xyzw;         /* [batch][stride][4] local-map points; w is carried through (information scale); this array,
+                                      scene_desc, clipped_xyzw and clipped_desc are 16-byte aligned: a row moves in 16-byte pieces */
   const uint8_t* scene_desc;       /* [batch][stride][32] or NULL (then clipped_desc must be NULL too) */
   const int32_t* n_scene;          /* [batch] */
   const float* robot_in_local_map; /* [batch][16] row-major */
@@ -604,7 +620,7 @@ typedef struct {
   int32_t batch;               /* independent (fixed, moving) cloud pairs */
   int32_t fixed_stride;        /* <= 8192 */
   int32_t moving_stride;       /* <= 65535 */
-  const uint8_t* fixed_desc;   /* [batch][fixed_stride][32] */
+  const uint8_t* fixed_desc;   /* [batch][fixed_stride][32], 16-byte aligned like moving_desc: a descriptor is read as two 16-byte pieces */
   const int32_t* n_fixed;      /* [batch] */
   const uint8_t* moving_desc;  /* [batch][moving_stride][32] */
   const int32_t* n_moving;     /* [batch] */
@@ -1018,7 +1034,8 @@ PRS_API int prs_extract_features_selective(prs_context* ctx,
  * the reference's _status = Error, :131-136; also what the extractor reports for an image without keypoints) and
  * PRS_WARN_SPARSE_DEPTH ((float) without_depth / (float) n > 0.25, :139-145).  An image with an error has n_fixed 0 and
  * outputs that are not valid; the other images of the batch are unaffected.
- * Call-level errors: PRS_ERR_UNSUPPORTED (unknown depth_type, or an output row pointer not 16-byte aligned), PRS_ERR_RANGE
+ * Call-level errors: PRS_ERR_UNSUPPORTED (unknown depth_type; fixed, fixed_desc or descriptors not 16-byte aligned -- a descriptor
+ * moves as two 16-byte pieces --, keypoints not 8-byte aligned, depth not aligned to its element), PRS_ERR_RANGE
  * (non-finite scale, rows or cols below 1, stride below 1, pitch below cols * element size or not a multiple of it),
  * PRS_ERR_NULL (a required pointer unset, or exactly one of intensity / fixed_intensity set).
  * ============================================================================================== */
@@ -1034,9 +1051,9 @@ typedef struct {
   int32_t batch, rows, cols, pitch;       /* depth image size; pitch in bytes, a multiple of the element size */
   const void* depth;                      /* [batch][rows][pitch] */
   int32_t stride;                         /* row stride of every per-feature array below, in and out */
-  const prs_kp2* keypoints;               /* [batch][stride] (u, v): the extractor's output */
+  const prs_kp2* keypoints;               /* [batch][stride] (u, v): the extractor's output; 8-byte aligned */
   const float* intensity;                 /* [batch][stride] or NULL */
-  const uint8_t* descriptors;             /* [batch][stride][32] */
+  const uint8_t* descriptors;             /* [batch][stride][32], 16-byte aligned */
   const int32_t* n_features;              /* [batch] */
   const int32_t* extract_status;          /* the extractor's per-image status, or NULL; may alias `status` */
   float* fixed;                           /* out [batch][stride][4] (u, v, d, 0): the layout of prs_align_batch.fixed and
@@ -2315,8 +2332,11 @@ PRS_API void prs_trajectory_struct_sizes(uint64_t* sizes3);
  * tools).  For 8-bit bilinear the workgroup stages the tile's source footprint -- the box around the taps it holds, in whole
  * 16-byte pieces of the source rows -- in LDS per image and reads the taps from there, when src and src_pitch are multiples of 16
  * bytes and the box fits 8 KB; otherwise, and for nearest, the lanes fetch their taps from global memory (PRS_RECTIFY_VARIANT = 0
- * forces that: tools).  Staging reads a source row up to the next multiple of 16 bytes, which lies inside src_pitch.  There is no
- * host-pointer variant and no C++ adapter in plugin/: the reference has no class to mirror.
+ * forces that: tools).  Staging reads a source row up to the next multiple of 16 bytes, which lies inside src_pitch: with src and
+ * src_pitch multiples of 16 bytes the LAST row of src therefore has cols rounded up to 16 bytes that belong to the array (their
+ * values reach no pixel); in every other case src ends at its last pixel, and dst always does (a lane's four-pixel store is issued
+ * only when all four lie inside dst_cols).  There is no host-pointer variant and no C++ adapter in plugin/: the reference has no
+ * class to mirror.
  * ============================================================================================== */
 enum { PRS_DISTORTION_RADTAN = 0 };
 enum { PRS_PIXEL_U8 = 0, PRS_PIXEL_U16 = 1, PRS_PIXEL_F32 = 2 };
@@ -2343,7 +2363,8 @@ typedef struct {
 typedef struct {
   int32_t batch;
   int32_t src_rows, src_cols, src_pitch;   /* pitches in bytes, multiples of the element size */
-  const void* src;                         /* [batch][src_rows][src_pitch] */
+  const void* src;                         /* [batch][src_rows][src_pitch]; ends at its last pixel, or, with src and src_pitch
+                                              multiples of 16, at the last row's cols rounded up to 16 bytes (see above) */
   int32_t dst_rows, dst_cols, dst_pitch;   /* the destination's size may differ from the source's */
   void* dst;                               /* out [batch][dst_rows][dst_pitch], 4-byte aligned; must not overlap src */
   int32_t n_maps;

@@ -851,6 +851,9 @@ int triangulate_launch(prs_context* ctx, const prs_triangulator_params* params, 
   if (n <= 0) {
     return PRS_OK;
   }
+  if (!aligned_to(d_uvuv, 16) || !aligned_to(d_xyz4, 16)) {  // the kernel moves a row as one float4
+    return ctx_fail(ctx, PRS_ERR_UNSUPPORTED, "prs_triangulate: uvuv and xyz4 must be 16-byte aligned");
+  }
   return Launches(ctx, "prs_triangulate", ctx_stream(ctx)).one(n < 2048 * 256 ? (n + 255) / 256 : 2048, 256, triangulate_kernel,
                                                                0, *params, reinterpret_cast<const float4*>(d_uvuv), n, reinterpret_cast<float4*>(d_xyz4));
 }

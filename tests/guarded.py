@@ -1,0 +1,284 @@
+"""Guard bands for the arrays a test hands to the library.
+
+An Arena is one uint8 allocation; every array of a call is carved from it with a band of fill bytes before and behind it, at
+exactly the alignment include/proslam_hip.h demands for that array (a multiple of `align`, never of 2 * align), so nothing of what
+torch's allocator gives for free -- 256-byte alignment, sizes rounded up, small tensors packed into one block -- reaches a kernel.
+After the call, check() lists every band byte that is no longer the fill.  Run a case once with fill 0x00 and once with 0xFF (NaN
+as float32 / float64, -1 as int32, 65535 as uint16): a result that differs between the two has read a byte it must not read.
+
+    arena = Arena(0xFF, device="cuda")
+    x = arena.take((n, 4), torch.float32, 16, "xyz")      # a new array, painted with the fill
+    arena.adopt(batch, "status", 4)                       # batch.status moves into the arena, values kept
+    ... run ...
+    arena.check()
+
+adopt_all moves every tensor of an ops batch (shared tensors once, views rebuilt), hooked does so for every batch a stage test's own
+helpers build inside a with block, both_fills runs a case under both fills and compares the two runs.
+
+What the harness cannot see: a read past an array's end whose value reaches no result, and anything in memory the library owns.
+"""
+import contextlib
+
+import torch
+
+MIN_BAND = 4096
+FILLS = (0x00, 0xFF)
+
+
+def _span(shape, strides):
+    """elements from the first to the last element of a strided array, both included (0 for an empty one)"""
+    if any(int(n) == 0 for n in shape):
+        return 0
+    return 1 + sum((int(n) - 1) * int(s) for n, s in zip(shape, strides))
+
+
+def _contiguous(shape):
+    strides, step = [], 1
+    for n in reversed(shape):
+        strides.append(step)
+        step *= max(int(n), 1)
+    return tuple(reversed(strides))
+
+
+class Violation(AssertionError):
+    pass
+
+
+class Arena:
+    def __init__(self, fill, nbytes=32 << 20, device="cuda"):
+        if fill not in FILLS:
+            raise ValueError("fill: 0x00 or 0xFF")
+        self.fill, self.nbytes = int(fill), int(nbytes)
+        self.buf = torch.full((self.nbytes,), self.fill, dtype=torch.uint8, device=device)
+        self.base = self.buf.data_ptr()
+        self.cursor = 0          # the first byte no array or band has claimed
+        self.arrays = []         # dict(name, start, extent, before, after): offsets into buf; the bands are [before, start) and [start + extent, after)
+
+    # ---- placing ----
+    def band_bytes(self, shape, strides, itemsize):
+        """at least one whole outermost element of the array, never below MIN_BAND"""
+        outer = int(strides[0]) * itemsize if len(shape) > 1 else itemsize
+        return max(MIN_BAND, outer)
+
+    def take(self, shape, dtype, align=None, name=None, extent=None, strides=None, band=None):
+        """a view of this shape (and these strides, in elements) whose address is a multiple of `align` and not of 2 * align, painted
+        with the fill.  extent: the bytes the harness believes the array to have, counted from its first byte (default: up to its
+        last element); the memory behind the view is always the whole array's, so a smaller extent only moves where the trailing band
+        begins."""
+        shape = tuple(int(n) for n in (shape if hasattr(shape, "__len__") else (shape,)))
+        itemsize = torch.empty((), dtype=dtype).element_size()
+        align = itemsize if align is None else int(align)
+        if align < itemsize or align % itemsize or align & (align - 1):
+            raise ValueError("align must be a power of two and a multiple of the element size")
+        strides = _contiguous(shape) if strides is None else tuple(int(s) for s in strides)
+        real = _span(shape, strides) * itemsize
+        believed = real if extent is None else int(extent)
+        if not 0 <= believed <= real:
+            raise ValueError("extent must lie within the array")
+        band = max(self.band_bytes(shape, strides, itemsize), int(band or 0))
+        before = self.cursor
+        addr = self.base + before + band
+        addr = (addr + 2 * align - 1) // (2 * align) * (2 * align) + align   # odd multiple of align
+        start = addr - self.base
+        after = start + real + band
+        if after >= self.nbytes:  # '>=': the last band ends inside the allocation as well
+            raise MemoryError("the arena of %d bytes is full" % self.nbytes)
+        self.cursor = after
+        name = name or "array%d" % len(self.arrays)
+        self.arrays.append(dict(name=name, start=start, extent=believed, real=real, before=before, after=after))
+        if real == 0:
+            return torch.empty(shape, dtype=dtype, device=self.buf.device)
+        flat = self.buf[start:start + real].view(dtype)
+        return torch.as_strided(flat, shape, strides)
+
+    def adopt(self, obj, attr, align=None, extent=None, name=None):
+        """move the tensor obj.attr (obj[attr] of a dict or list) into the arena: same shape, strides and values; -> the new view, which is
+        also assigned back.  Slack inside it keeps the values it had: paint() it where the contract says it is not read."""
+        item = isinstance(obj, (dict, list))
+        t = obj[attr] if item else getattr(obj, attr)
+        new = self.take(tuple(t.shape), t.dtype, align, name or str(attr), extent, tuple(t.stride()))
+        if t.numel():
+            flat_new = torch.as_strided(new, (_span(t.shape, t.stride()),), (1,))
+            flat_old = torch.as_strided(t, (_span(t.shape, t.stride()),), (1,), t.storage_offset())
+            flat_new.copy_(flat_old)
+        if item:
+            obj[attr] = new
+        else:
+            setattr(obj, attr, new)
+        return new
+
+    def owns(self, t):
+        return t.device == self.buf.device and self.base <= t.data_ptr() < self.base + self.nbytes
+
+    def adopt_all(self, objects, aligns=None, skip=()):
+        """every tensor attribute of the objects of a dict name -> ops.* batch moves into the arena.  aligns: "name.attr" or "attr"
+        -> what the header demands, or a function of (name, tensor) (default: row_align).  A tensor two objects share (maps.n_corr is session.n_corr_merge)
+        moves once; a view of an adopted tensor (disparity of _disparity) is rebuilt over the new storage.  -> the arena"""
+        moved = getattr(self, "_moved", {})
+        self._moved = moved  # id(old) -> (old, new); the old tensor is kept so that its id stays its own
+        known = self._objects = getattr(self, "_objects", {})
+        table = aligns or {}
+        align_of = (lambda name, t: row_align(name, t)) if aligns is None else \
+            (aligns if callable(aligns) else lambda name, t: table.get(name, table.get(name.rsplit(".", 1)[-1], row_align(name, t))))
+        found = []
+        for prefix, obj in objects.items():
+            for attr, t in sorted(vars(obj).items()):
+                if isinstance(t, torch.Tensor) and not (attr in skip or prefix + "." + attr in skip or self.owns(t)):
+                    found.append((-_span(t.shape, t.stride()) * t.element_size(), prefix + "." + attr, obj, attr, t))
+        for nbytes, name, obj, attr, t in sorted(found, key=lambda f: f[:2]):  # the widest first: a storage before its views
+            if id(t) in moved:
+                setattr(obj, attr, moved[id(t)][1])
+                continue
+            lo, hi = t.data_ptr(), t.data_ptr() - nbytes
+            for old, new in list(moved.values()):
+                end = old.data_ptr() + _span(old.shape, old.stride()) * old.element_size()
+                if old.dtype == t.dtype and old.device == t.device and old.data_ptr() <= lo and hi <= end and t.numel():
+                    offset = new.storage_offset() + (lo - old.data_ptr()) // t.element_size()
+                    moved[id(t)] = (t, torch.as_strided(new, tuple(t.shape), tuple(t.stride()), offset))
+                    setattr(obj, attr, moved[id(t)][1])
+                    break
+            else:
+                moved[id(t)] = (t, self.adopt(obj, attr, align_of(name, t), name=name))
+        # an object adopted earlier may hold a tensor that only now moved (SessionBatch points maps.n_corr at its own n_corr_merge)
+        known.update({id(obj): obj for obj in objects.values()})
+        for obj in known.values():
+            for attr, t in vars(obj).items():
+                if isinstance(t, torch.Tensor) and id(t) in moved and moved[id(t)][1] is not t:
+                    setattr(obj, attr, moved[id(t)][1])
+        return self
+
+    def adopt_pitched(self, obj, attr, cols, align=None, whole_pitches=False, name=None):
+        """adopt() for the storage [..., rows, pitch] of images of `cols` columns: the extent ends at the last pixel of the last row of
+        the last image and the pitch padding of every row is painted, the last row's being band.  whole_pitches: the header says the
+        array is read or written in whole pitches, so the extent is rows * pitch"""
+        t = obj[attr] if isinstance(obj, (dict, list)) else getattr(obj, attr)
+        pad = (int(t.shape[-1]) - int(cols)) * t.element_size()
+        assert pad >= 0 and t.is_contiguous()
+        real = t.numel() * t.element_size()
+        new = self.adopt(obj, attr, align, None if whole_pitches else real - pad, name)
+        self.paint(new[..., int(cols):])
+        return new
+
+    def workspace(self, obj, nbytes, name="workspace"):
+        """obj.workspace becomes exactly nbytes of the arena, 16-byte aligned and painted; nbytes is what the library's
+        prs_*_workspace_bytes answered for the parameters of this very run"""
+        nbytes = int(nbytes)
+        assert nbytes > 0, "the library refused to size a workspace for these parameters"
+        obj.workspace = self.take((nbytes,), torch.uint8, 16, name)
+        return obj.workspace
+
+    def paint(self, view):
+        """every byte of a view (of any tensor, usually slack inside an adopted array) becomes the fill; -> the view"""
+        if view is not None and view.numel():
+            if view.dim() == 0 or view.stride(-1) != 1:
+                view = view.unsqueeze(-1)
+            view.view(torch.uint8).fill_(self.fill)
+        return view
+
+    # ---- checking ----
+    def violations(self):
+        """[(name, "before" | "after", offset)] of every band byte that is not the fill.  "after": offset 0 is the first byte behind
+        the array's extent; "before": offset -1 is the byte in front of its first"""
+        out = []
+        for a in self.arrays:
+            for side, lo, hi, origin in (("before", a["before"], a["start"], a["start"]),
+                                         ("after", a["start"] + a["extent"], a["after"], a["start"] + a["extent"])):
+                bad = (self.buf[lo:hi] != self.fill).nonzero().flatten().cpu().tolist()
+                out.extend((a["name"], side, lo + i - origin) for i in bad)
+        return out
+
+    def check(self):
+        bad = self.violations()
+        if bad:
+            shown = ", ".join("%s %s %+d" % v for v in bad[:20])
+            raise Violation("%d band bytes changed (fill 0x%02X): %s%s" % (len(bad), self.fill, shown, " ..." if len(bad) > 20 else ""))
+
+
+ROWS_OF_16 = ("coords", "desc", "state", "xyz", "fixed", "moving", "measurement", "measurement_desc", "fixed_desc", "moving_desc",
+              "fixed_xyz", "moving_xyz", "handover_desc", "handover_xyz", "estimate", "ground_truth",
+              "left_desc", "right_desc", "fixed_uvuv", "scene_xyzw", "scene_desc", "clipped_xyzw", "clipped_desc")
+
+
+def row_align(name, t):
+    """the alignment include/proslam_hip.h demands of the arrays of the sparse stages: 16 bytes for rows of four floats, for
+    descriptors and for poses (they move in 16-byte pieces) and for a workspace of bytes, the element size for every other array"""
+    attr = name.rsplit(".", 1)[-1].lstrip("_")
+    wide = t.dim() >= 3 and (t.shape[-1] * t.element_size()) % 16 == 0 and t.dtype in (torch.float32, torch.uint8)
+    if (wide and attr in ROWS_OF_16) or (attr == "workspace" and t.dtype == torch.uint8):
+        return 16
+    if t.dim() >= 3 and t.dtype == torch.float32 and t.shape[-1] == 2:  # prs_kp2 keypoints
+        return 8
+    return t.element_size()
+
+
+def ops_objects(**roots):
+    """name -> object for the roots and every srrg2_proslam_amd.ops object reachable through their attributes (a detector's
+    queries, links and closures; a closure batch's clouds and pairs), the context left out"""
+    out, seen = {}, set()
+
+    def walk(name, obj):
+        if id(obj) in seen or not hasattr(obj, "__dict__"):
+            return
+        seen.add(id(obj))
+        out[name] = obj
+        for attr, v in sorted(vars(obj).items()):
+            if type(v).__module__.endswith(".ops") and type(v).__name__ != "Context":
+                walk(name + "." + attr, v)
+
+    for name, obj in roots.items():
+        walk(name, obj)
+    return out
+
+
+@contextlib.contextmanager
+def hooked(arena, *classes, aligns=None, after=None):
+    """inside the with block every instance of these classes moves its tensors (and those of the ops objects it holds) into the arena
+    as soon as it is built, so the stage tests' own helpers, which build their batches themselves, run on guarded memory.
+    after(obj): called behind the adoption (slack to paint, an exact workspace, a pointer the library has to be told again)"""
+    saved = [(cls, cls.__init__) for cls in classes]
+
+    def wrap(orig):
+        def init(self, *a, **kw):
+            orig(self, *a, **kw)
+            arena.adopt_all(ops_objects(**{type(self).__name__: self}), aligns)
+            if after is not None:
+                after(self)
+        return init
+
+    try:
+        for cls, orig in saved:
+            cls.__init__ = wrap(orig)
+        yield arena
+    finally:
+        for cls, orig in saved:
+            cls.__init__ = orig
+
+
+def host_fill(dtype, fill):
+    """the element of a numpy dtype whose every byte is the fill: what a host array's slack is set to before it is uploaded"""
+    import numpy as np
+    return np.frombuffer(bytes([fill]) * np.dtype(dtype).itemsize, dtype=dtype)[0]
+
+
+def both_fills(case, **kw):
+    """case(arena) builds, adopts, runs, synchronises, asserts against the reference and returns its outputs as a dict of numpy
+    arrays.  It is run in an arena of each fill; the bands must be clean after each run and the two runs byte-identical"""
+    outs = []
+    for fill in FILLS:
+        arena = Arena(fill, **kw)
+        outs.append(case(arena))
+        arena.check()
+    same_bytes(*outs)
+    return outs
+
+
+def same_bytes(a, b):
+    """two dicts of numpy arrays, the outputs of the 0x00 run and of the 0xFF run, are byte-identical -- but for the bytes no call
+    wrote, which hold 0x00 in the one and 0xFF in the other (each run has compared them with its own expectation already)"""
+    import numpy as np
+    assert sorted(a) == sorted(b)
+    for k in a:
+        x, y = (np.frombuffer(np.ascontiguousarray(v).tobytes(), np.uint8) for v in (a[k], b[k]))
+        assert x.shape == y.shape, k
+        moved = (x != y) & ~((x == FILLS[0]) & (y == FILLS[1]))
+        assert not moved.any(), "%s differs between fill 0x00 and fill 0xFF at bytes %s" % (k, np.nonzero(moved)[0][:8].tolist())
