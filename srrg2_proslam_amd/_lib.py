@@ -797,6 +797,32 @@ SYMBOLS = {
     "prs_scene_clip": (C.c_int, [_vp, C.POINTER(Projector), _vp, _vp, _vp, _vp, C.c_int32, _vp, _vp, _vp, C.c_int32, _i32p]),
 }
 
+# every *_struct_sizes entry with the mirrors of the structs it reports, in the order its function writes them; load() compares them
+STRUCT_SIZES = (
+    ("prs_place_bank_struct_sizes", (PlaceBankAppend, PlaceBankLinks)),
+    ("prs_pose_graph_struct_sizes", (PoseGraphParams, PoseGraphResult, PoseGraphs, PoseGraphClosures)),
+    ("prs_pose_graph_lm_struct_sizes", (PoseGraphLmParams, PoseGraphLmResult)),
+    ("prs_closure_merge_struct_sizes", (ClosureMergerParams, ClosureMergeBatch)),
+    ("prs_session_struct_sizes", (SessionParams, SessionBatch)),
+    ("prs_map_archive_struct_sizes", (MapArchive, ReentryParams, ReentryBatch)),
+    ("prs_dispatch_struct_sizes", (DispatchEnv, DispatchPlan)),
+    ("prs_trajectory_struct_sizes", (TrajectoryParams, TrajectoryResult, TrajectoryBatch)),
+    ("prs_world_map_struct_sizes", (WorldMapParams, WorldMapBatch)),
+    ("prs_world_voxel_struct_sizes", (WorldVoxelParams, WorldVoxelBatch)),
+    ("prs_rectify_struct_sizes", (RectifyMap, RectifyParams, RectifyBatch)),
+    ("prs_depth_cloud_struct_sizes", (DepthCloudParams, DepthCloudBatch)),
+    ("prs_dense_stereo_struct_sizes", (DenseStereoParams, DenseStereoBatch)),
+    ("prs_speckle_struct_sizes", (SpeckleParams, SpeckleBatch)),
+    ("prs_sgm_stereo_struct_sizes", (SgmStereoParams, SgmStereoBatch)),
+    ("prs_depth_consistency_struct_sizes", (DepthConsistencyParams, DepthConsistencyBatch)),
+)
+
+
+def c_name(mirror):
+    """the header struct a mirror stands for: the first word of its docstring"""
+    return mirror.__doc__.split()[0].rstrip(":")
+
+
 _lib = None
 
 
@@ -837,67 +863,13 @@ def load():
                           "rebuild with `python -c 'import __graft_entry__ as g; g.build()'`"
                           % (lib.prs_version(), ABI_VERSION, C.sizeof(StereoParams), C.sizeof(PcfParams), C.sizeof(AlignerParams), C.sizeof(AlignBatch)))
     # the structs of the later sections have their own size queries
-    sizes = (C.c_uint64 * 3)()
-    lib.prs_map_archive_struct_sizes(sizes)
-    if list(sizes) != [C.sizeof(MapArchive), C.sizeof(ReentryParams), C.sizeof(ReentryBatch)]:
-        raise ImportError("libproslam_hip.so lays out prs_map_archive / prs_reentry_params / prs_reentry_batch as %s bytes, the Python "
-                          "binding as %s: rebuild with `python -c 'import __graft_entry__ as g; g.build()'`"
-                          % (list(sizes), [C.sizeof(MapArchive), C.sizeof(ReentryParams), C.sizeof(ReentryBatch)]))
-    sizes = (C.c_uint64 * 2)()
-    lib.prs_dispatch_struct_sizes(sizes)
-    if list(sizes) != [C.sizeof(DispatchEnv), C.sizeof(DispatchPlan)]:
-        raise ImportError("libproslam_hip.so lays out prs_dispatch_env / prs_dispatch_plan as %s bytes, the Python binding as %s: rebuild "
-                          "with `python -c 'import __graft_entry__ as g; g.build()'`"
-                          % (list(sizes), [C.sizeof(DispatchEnv), C.sizeof(DispatchPlan)]))
-    sizes = (C.c_uint64 * 3)()
-    lib.prs_trajectory_struct_sizes(sizes)
-    if list(sizes) != [C.sizeof(TrajectoryParams), C.sizeof(TrajectoryResult), C.sizeof(TrajectoryBatch)]:
-        raise ImportError("libproslam_hip.so lays out prs_trajectory_params / prs_trajectory_result / prs_trajectory_batch as %s bytes, "
-                          "the Python binding as %s: rebuild with `python -c 'import __graft_entry__ as g; g.build()'`"
-                          % (list(sizes), [C.sizeof(TrajectoryParams), C.sizeof(TrajectoryResult), C.sizeof(TrajectoryBatch)]))
-    sizes = (C.c_uint64 * 2)()
-    lib.prs_world_map_struct_sizes(sizes)
-    if list(sizes) != [C.sizeof(WorldMapParams), C.sizeof(WorldMapBatch)]:
-        raise ImportError("libproslam_hip.so lays out prs_world_map_params / prs_world_map_batch as %s bytes, the Python binding as %s: "
-                          "rebuild with `python -c 'import __graft_entry__ as g; g.build()'`"
-                          % (list(sizes), [C.sizeof(WorldMapParams), C.sizeof(WorldMapBatch)]))
-    lib.prs_world_voxel_struct_sizes(sizes)
-    if list(sizes) != [C.sizeof(WorldVoxelParams), C.sizeof(WorldVoxelBatch)]:
-        raise ImportError("libproslam_hip.so lays out prs_world_voxel_params / prs_world_voxel_batch as %s bytes, the Python binding as %s: "
-                          "rebuild with `python -c 'import __graft_entry__ as g; g.build()'`"
-                          % (list(sizes), [C.sizeof(WorldVoxelParams), C.sizeof(WorldVoxelBatch)]))
-    sizes = (C.c_uint64 * 3)()
-    lib.prs_rectify_struct_sizes(sizes)
-    if list(sizes) != [C.sizeof(RectifyMap), C.sizeof(RectifyParams), C.sizeof(RectifyBatch)]:
-        raise ImportError("libproslam_hip.so lays out prs_rectify_map / prs_rectify_params / prs_rectify_batch as %s bytes, the Python "
-                          "binding as %s: rebuild with `python -c 'import __graft_entry__ as g; g.build()'`"
-                          % (list(sizes), [C.sizeof(RectifyMap), C.sizeof(RectifyParams), C.sizeof(RectifyBatch)]))
-    sizes = (C.c_uint64 * 2)()
-    lib.prs_depth_cloud_struct_sizes(sizes)
-    if list(sizes) != [C.sizeof(DepthCloudParams), C.sizeof(DepthCloudBatch)]:
-        raise ImportError("libproslam_hip.so lays out prs_depth_cloud_params / prs_depth_cloud_batch as %s bytes, the Python binding as %s: "
-                          "rebuild with `python -c 'import __graft_entry__ as g; g.build()'`"
-                          % (list(sizes), [C.sizeof(DepthCloudParams), C.sizeof(DepthCloudBatch)]))
-    sizes = (C.c_uint64 * 2)()
-    lib.prs_dense_stereo_struct_sizes(sizes)
-    if list(sizes) != [C.sizeof(DenseStereoParams), C.sizeof(DenseStereoBatch)]:
-        raise ImportError("libproslam_hip.so lays out prs_dense_stereo_params / prs_dense_stereo_batch as %s bytes, the Python binding as "
-                          "%s: rebuild with `python -c 'import __graft_entry__ as g; g.build()'`"
-                          % (list(sizes), [C.sizeof(DenseStereoParams), C.sizeof(DenseStereoBatch)]))
-    lib.prs_speckle_struct_sizes(sizes)
-    if list(sizes) != [C.sizeof(SpeckleParams), C.sizeof(SpeckleBatch)]:
-        raise ImportError("libproslam_hip.so lays out prs_speckle_params / prs_speckle_batch as %s bytes, the Python binding as %s: "
-                          "rebuild with `python -c 'import __graft_entry__ as g; g.build()'`"
-                          % (list(sizes), [C.sizeof(SpeckleParams), C.sizeof(SpeckleBatch)]))
-    lib.prs_sgm_stereo_struct_sizes(sizes)
-    if list(sizes) != [C.sizeof(SgmStereoParams), C.sizeof(SgmStereoBatch)]:
-        raise ImportError("libproslam_hip.so lays out prs_sgm_stereo_params / prs_sgm_stereo_batch as %s bytes, the Python binding as %s: "
-                          "rebuild with `python -c 'import __graft_entry__ as g; g.build()'`"
-                          % (list(sizes), [C.sizeof(SgmStereoParams), C.sizeof(SgmStereoBatch)]))
-    lib.prs_depth_consistency_struct_sizes(sizes)
-    if list(sizes) != [C.sizeof(DepthConsistencyParams), C.sizeof(DepthConsistencyBatch)]:
-        raise ImportError("libproslam_hip.so lays out prs_depth_consistency_params / prs_depth_consistency_batch as %s bytes, the Python "
-                          "binding as %s: rebuild with `python -c 'import __graft_entry__ as g; g.build()'`"
-                          % (list(sizes), [C.sizeof(DepthConsistencyParams), C.sizeof(DepthConsistencyBatch)]))
+    for query, mirrors in STRUCT_SIZES:
+        sizes = (C.c_uint64 * len(mirrors))()
+        getattr(lib, query)(sizes)
+        mine = [C.sizeof(m) for m in mirrors]
+        if list(sizes) != mine:
+            raise ImportError("libproslam_hip.so lays out %s as %s bytes, the Python binding as %s: rebuild with "
+                              "`python -c 'import __graft_entry__ as g; g.build()'`"
+                              % (" / ".join(c_name(m) for m in mirrors), list(sizes), mine))
     _lib = lib
     return lib

@@ -1,4 +1,5 @@
-"""The C-ABI library loads and exports every symbol include/proslam_hip.h declares (no GPU needed)."""
+"""prs_abi_check's refusals, the loud failure without a GPU, and the package's independence of the oracle (no GPU needed).  What the
+header declares against what the library exports and the binding restates is tests/test_abi_layout.py."""
 import ctypes as C
 import os
 import re
@@ -6,16 +7,6 @@ import re
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def declared_symbols():
-    names = []
-    inc = os.path.join(ROOT, "include")
-    for fn in sorted(os.listdir(inc)):
-        if fn.endswith(".h"):
-            text = open(os.path.join(inc, fn)).read()
-            names += re.findall(r"PRS_API\s+[\w\s\*]+?\b(prs_\w+)\s*\(", text)
-    return sorted(set(names))
 
 
 @pytest.fixture(scope="module")
@@ -26,24 +17,8 @@ def built():
     return _lib
 
 
-def test_header_declares_entry_points():
-    names = declared_symbols()
-    for must in ("prs_context_create", "prs_stereo_match", "prs_stereo_match_batch", "prs_triangulate"):
-        assert must in names
-
-
-def test_library_exports_every_declared_symbol(built):
-    lib = C.CDLL(built.LIB_PATH)
-    missing = [n for n in declared_symbols() if not hasattr(lib, n)]
-    assert not missing, "declared in include/*.h but not exported: %s" % missing
-
-
-def test_python_binding_covers_header(built):
-    assert sorted(built.SYMBOLS.keys()) == declared_symbols()
+def test_abi_check_refuses_another_version_or_size(built):
     lib = built.load()
-    assert lib.prs_version() == built.ABI_VERSION
-    header = open(os.path.join(ROOT, "include", "proslam_hip.h")).read()
-    assert "#define PRS_ABI_VERSION %d" % built.ABI_VERSION in header
     # a client built against another header, or with a shorter parameter struct, is refused instead of read past
     sizes = [C.sizeof(built.StereoParams), C.sizeof(built.PcfParams), C.sizeof(built.AlignerParams), C.sizeof(built.AlignBatch)]
     assert lib.prs_abi_check(built.ABI_VERSION, *sizes) == 0

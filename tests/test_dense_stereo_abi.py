@@ -1,6 +1,5 @@
-"""Dense stereo's part of the C-ABI: entry points exported and bound, struct layouts agreed between the library, the header's
-declared sizes and the ctypes mirrors, the workspace size, the params helper, and the ABI version unchanged (new entries under the
-current version).  No GPU needed."""
+"""Dense stereo's part of the C-ABI: the workspace size, the null-context refusal and the params helper (the layouts are
+tests/test_abi_layout.py).  No GPU needed."""
 import ctypes as C
 
 import numpy as np
@@ -17,41 +16,6 @@ def built():
     return _lib
 
 
-def test_entry_points_exported(built):
-    lib = C.CDLL(built.LIB_PATH)
-    for name in ("prs_dense_stereo_batch_run", "prs_dense_stereo_workspace_bytes", "prs_dense_stereo_struct_sizes"):
-        assert hasattr(lib, name), name
-        assert name in built.SYMBOLS
-
-
-def test_struct_sizes_and_offsets_match_the_library(built):
-    lib = built.load()
-    sizes = (C.c_uint64 * 2)()
-    lib.prs_dense_stereo_struct_sizes(sizes)
-    assert list(sizes) == [C.sizeof(built.DenseStereoParams), C.sizeof(built.DenseStereoBatch)]
-    # as the header lays them out: 6 words and 6 reserved ones; 8 int32 and 8 pointers
-    assert list(sizes) == [48, 96]
-    P, B = built.DenseStereoParams, built.DenseStereoBatch
-    assert [(n, getattr(P, n).offset) for n, _ in P._fields_] == [
-        ("n_disparities", 0), ("min_disparity", 4), ("aggregation_radius", 8), ("uniqueness_percent", 12), ("lr_max_diff", 16), ("bf", 20),
-        ("reserved", 24)]
-    assert [n for n, _ in B._fields_] == ["batch", "frames", "rows", "cols", "left_pitch", "right_pitch", "out_pitch", "reserved0", "left",
-                                          "right", "n_images", "disparity", "depth", "n_valid", "status", "workspace"]
-    assert [getattr(B, n).offset for n, _ in B._fields_] == list(range(0, 32, 4)) + list(range(32, 96, 8))
-
-
-def test_header_declares_the_structs_in_that_order(built):
-    import os
-    import re
-    header = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include", "proslam_hip.h")).read()
-    strip = lambda body: re.findall(r"(\w+)(?:\[\d+\])?;", re.sub(r"/\*.*?\*/", "", body, flags=re.S))  # noqa: E731
-    body = re.search(r"typedef struct \{([^}]*)\} prs_dense_stereo_batch;", header).group(1)
-    assert strip(body) == ["batch", "frames", "cols"] + [n for n, _ in built.DenseStereoBatch._fields_][4:]  # "int32_t rows, cols;"
-    assert "rows, cols;" in body
-    body = re.search(r"typedef struct \{([^}]*)\} prs_dense_stereo_params;", header).group(1)
-    assert strip(body) == [n for n, _ in built.DenseStereoParams._fields_]
-
-
 def test_workspace_bytes(built):
     f = built.load().prs_dense_stereo_workspace_bytes
     up = lambda x: (x + 15) // 16 * 16  # noqa: E731
@@ -64,10 +28,6 @@ def test_workspace_bytes(built):
     for bad in ((0, 1, 1, 1, 1, 1), (1, 0, 1, 1, 1, 1), (1, 1, 0, 1, 1, 1), (1, 1, 1, 0, 1, 1), (1, 1, 1, 1, 0, 1), (1, 1, 1, 1, 257, 1),
                 (-1, 1, 1, 1, 1, 1), (1, 1, 1 << 16, 1 << 16, 16, 1), (1, 1 << 12, 1 << 10, 1 << 10, 16, 0), (1 << 20, 1 << 20, 1, 1, 16, 0)):
         assert f(*bad) == 0, bad
-
-
-def test_version_unchanged(built):
-    assert built.load().prs_version() == 104 == built.ABI_VERSION
 
 
 def test_null_context_is_refused(built):

@@ -1,6 +1,5 @@
-"""The dense RGB-D cloud's part of the C-ABI: entry points exported and bound, struct layouts agreed between the library, the header's
-declared sizes and the ctypes mirrors, the workspace size, the params helper, and the ABI version unchanged (new entries under the
-current version).  No GPU needed."""
+"""The dense RGB-D cloud's part of the C-ABI: the workspace size, the null-context refusal and the params helper (the layouts are
+tests/test_abi_layout.py).  No GPU needed."""
 import ctypes as C
 
 import numpy as np
@@ -17,41 +16,6 @@ def built():
     return _lib
 
 
-def test_entry_points_exported(built):
-    lib = C.CDLL(built.LIB_PATH)
-    for name in ("prs_depth_cloud_batch_run", "prs_depth_cloud_workspace_bytes", "prs_depth_cloud_struct_sizes"):
-        assert hasattr(lib, name), name
-        assert name in built.SYMBOLS
-
-
-def test_struct_sizes_and_offsets_match_the_library(built):
-    lib = built.load()
-    sizes = (C.c_uint64 * 2)()
-    lib.prs_depth_cloud_struct_sizes(sizes)
-    assert list(sizes) == [C.sizeof(built.DepthCloudParams), C.sizeof(built.DepthCloudBatch)]
-    # as the header lays them out: 9 words, 16 floats, 3 reserved words; 8 int32 and 14 pointers
-    assert list(sizes) == [112, 144]
-    P, B = built.DepthCloudParams, built.DepthCloudBatch
-    assert [(n, getattr(P, n).offset) for n, _ in P._fields_] == [
-        ("depth_type", 0), ("depth_scaling_factor_to_meters", 4), ("fx", 8), ("fy", 12), ("cx", 16), ("cy", 20), ("range_min", 24),
-        ("range_max", 28), ("step", 32), ("sensor_in_robot", 36), ("reserved", 100)]
-    assert [n for n, _ in B._fields_] == ["batch", "frames", "rows", "cols", "pitch", "gray_pitch", "pose_stride", "out_stride", "depth",
-                                          "gray", "n_images", "pose", "frame_index", "n_base", "xyz", "frame", "pixel", "n_out", "n_total",
-                                          "n_skipped", "status", "workspace"]
-    assert [getattr(B, n).offset for n, _ in B._fields_] == list(range(0, 32, 4)) + list(range(32, 144, 8))
-
-
-def test_header_declares_the_structs_in_that_order(built):
-    import os
-    import re
-    header = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include", "proslam_hip.h")).read()
-    body = re.search(r"typedef struct \{([^}]*)\} prs_depth_cloud_batch;", header).group(1)
-    names = re.findall(r"(\w+);", re.sub(r"/\*.*?\*/", "", body, flags=re.S))
-    assert names == ["batch", "frames", "cols", "pitch", "gray_pitch", "pose_stride", "out_stride"] + \
-        [n for n, _ in built.DepthCloudBatch._fields_][8:]  # "int32_t rows, cols;" declares two
-    assert "rows, cols;" in body
-
-
 def test_workspace_bytes(built):
     f = built.load().prs_depth_cloud_workspace_bytes
     # one count per chunk of 1024 sampled pixels of an image, rounded up to 16 bytes
@@ -62,10 +26,6 @@ def test_workspace_bytes(built):
     for bad in ((0, 1, 1, 1, 1), (1, 0, 1, 1, 1), (1, 1, 0, 1, 1), (1, 1, 1, 0, 1), (1, 1, 1, 1, 0), (-1, 1, 1, 1, 1), (1, 1, 1 << 16, 1 << 16, 1),
                 (1, 1 << 12, 1 << 10, 1 << 10, 1)):
         assert f(*bad) == 0, bad
-
-
-def test_version_unchanged(built):
-    assert built.load().prs_version() == 104 == built.ABI_VERSION
 
 
 def test_null_context_is_refused(built):

@@ -1,9 +1,7 @@
-"""The depth consistency filter's part of the C-ABI: entry points exported and bound, struct layouts agreed between the library, the
-header's declared order and the ctypes mirrors, the workspace size, the params helper, and the ABI version unchanged (new entries
-under the current version).  No GPU needed."""
+"""The depth consistency filter's part of the C-ABI: what the header says it leaves out, the workspace size, the null-context refusal
+and the params helper (the layouts are tests/test_abi_layout.py).  No GPU needed."""
 import ctypes as C
 import os
-import re
 
 import numpy as np
 import pytest
@@ -17,46 +15,8 @@ def built():
     return _lib
 
 
-def test_entry_points_exported(built):
-    lib = C.CDLL(built.LIB_PATH)
-    for name in ("prs_depth_consistency_batch_run", "prs_depth_consistency_workspace_bytes", "prs_depth_consistency_struct_sizes"):
-        assert hasattr(lib, name), name
-        assert name in built.SYMBOLS
-
-
-def test_struct_sizes_and_offsets_match_the_library(built):
-    lib = built.load()
-    sizes = (C.c_uint64 * 2)()
-    lib.prs_depth_consistency_struct_sizes(sizes)
-    P, B = built.DepthConsistencyParams, built.DepthConsistencyBatch
-    assert list(sizes) == [C.sizeof(P), C.sizeof(B)]
-    # as the header lays them out: 13 words, sensor_in_robot and 3 reserved words; 8 int32 and 12 pointers
-    assert list(sizes) == [4 * (13 + 16 + 3), 8 * 4 + 12 * 8]
-    assert [(n, getattr(P, n).offset) for n, _ in P._fields_] == [
-        ("depth_type", 0), ("depth_scaling_factor_to_meters", 4), ("fx", 8), ("fy", 12), ("cx", 16), ("cy", 20), ("range_min", 24),
-        ("range_max", 28), ("window", 32), ("stride", 36), ("max_rel_diff", 40), ("min_support", 44), ("max_violation", 48),
-        ("sensor_in_robot", 52), ("reserved", 116)]
-    assert [n for n, _ in B._fields_] == ["batch", "frames", "rows", "cols", "pitch", "out_pitch", "count_pitch", "pose_stride", "depth",
-                                          "n_images", "pose", "frame_index", "out", "support", "violation", "n_kept", "n_removed",
-                                          "n_skipped", "status", "workspace"]
-    assert [getattr(B, n).offset for n, _ in B._fields_] == list(range(0, 32, 4)) + list(range(32, 128, 8))
-
-
-def test_header_declares_the_structs_in_that_order(built):
+def test_header_says_what_the_stage_leaves_out():
     header = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include", "proslam_hip.h")).read()
-
-    def names(struct):
-        body = re.sub(r"/\*.*?\*/", "", re.search(r"typedef struct \{([^}]*)\} %s;" % struct, header).group(1), flags=re.S)
-        out = []
-        for declaration in body.split(";"):
-            words = re.sub(r"\[\d+\]", "", declaration).replace("*", " ").split()
-            if words:  # "const int32_t* n_images" / "float fx, fy, cx, cy": the names follow the type
-                first = next(i for i, w in enumerate(words) if w.endswith(",")) if "," in declaration else len(words) - 1
-                out += [w.rstrip(",") for w in words[first:]]
-        return out
-
-    assert names("prs_depth_consistency_params") == [n for n, _ in built.DepthConsistencyParams._fields_]
-    assert names("prs_depth_consistency_batch") == [n for n, _ in built.DepthConsistencyBatch._fields_]
     section = header[header.index(" * Depth consistency filter:"):header.index("} prs_depth_consistency_params;")]
     for left_out in ("a fused (averaged) depth", "a back-projection pixel-error test", "per-frame intrinsics", "bilinear", "a companion image",
                      "a host-pointer"):
@@ -72,10 +32,6 @@ def test_workspace_bytes(built):
     for bad in ((0, 1, 1), (1, 0, 1), (1, 1, 0), (-1, 1, 1), (1, -3, 2), (1, 1, -1), (1, 1, 9), (4, 4, 100), (2 ** 16, 2 ** 15, 1),
                 (2 ** 31 - 1, 2 ** 31 - 1, 1)):
         assert f(*bad) == 0, bad
-
-
-def test_version_unchanged(built):
-    assert built.load().prs_version() == 104 == built.ABI_VERSION
 
 
 def test_null_context_is_refused(built):

@@ -1,6 +1,5 @@
-"""Semi-global dense stereo's part of the C-ABI: entry points exported and bound, struct layouts agreed between the library, the
-header's declared sizes and the ctypes mirrors, the workspace size with its volume term, the params helper, and the ABI version
-unchanged (new entries under the current version).  No GPU needed."""
+"""Semi-global dense stereo's part of the C-ABI: its batch against dense stereo's, the workspace size with its volume term, the
+null-context refusal and the params helper (the layouts are tests/test_abi_layout.py).  No GPU needed."""
 import ctypes as C
 
 import numpy as np
@@ -17,44 +16,12 @@ def built():
     return _lib
 
 
-def test_entry_points_exported(built):
-    lib = C.CDLL(built.LIB_PATH)
-    for name in ("prs_sgm_stereo_batch_run", "prs_sgm_stereo_workspace_bytes", "prs_sgm_stereo_struct_sizes"):
-        assert hasattr(lib, name), name
-        assert name in built.SYMBOLS
-
-
-def test_struct_sizes_and_offsets_match_the_library(built):
-    lib = built.load()
-    sizes = (C.c_uint64 * 2)()
-    lib.prs_sgm_stereo_struct_sizes(sizes)
-    assert list(sizes) == [C.sizeof(built.SgmStereoParams), C.sizeof(built.SgmStereoBatch)]
-    # as the header lays them out: 8 words and 4 reserved ones; 8 int32 and 8 pointers
-    assert list(sizes) == [48, 96]
-    P, B = built.SgmStereoParams, built.SgmStereoBatch
-    assert [(n, getattr(P, n).offset) for n, _ in P._fields_] == [
-        ("n_disparities", 0), ("min_disparity", 4), ("p1", 8), ("p2", 12), ("n_paths", 16), ("uniqueness_percent", 20), ("lr_max_diff", 24),
-        ("bf", 28), ("reserved", 32)]
-    assert [n for n, _ in B._fields_] == ["batch", "frames", "rows", "cols", "left_pitch", "right_pitch", "out_pitch", "images_in_flight",
-                                          "left", "right", "n_images", "disparity", "depth", "n_valid", "status", "workspace"]
-    assert [getattr(B, n).offset for n, _ in B._fields_] == list(range(0, 32, 4)) + list(range(32, 96, 8))
-    # the fields of prs_dense_stereo_batch, with images_in_flight in the place of reserved0
-    D = built.DenseStereoBatch
+def test_batch_is_the_dense_stereo_batch_with_images_in_flight(built):
+    """the fields of prs_dense_stereo_batch, with images_in_flight in the place of reserved0"""
+    B, D = built.SgmStereoBatch, built.DenseStereoBatch
     assert [(n, getattr(B, n).offset) for n, _ in B._fields_ if n != "images_in_flight"] == \
         [(n, getattr(D, n).offset) for n, _ in D._fields_ if n != "reserved0"]
     assert B.images_in_flight.offset == D.reserved0.offset
-
-
-def test_header_declares_the_structs_in_that_order(built):
-    import os
-    import re
-    header = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include", "proslam_hip.h")).read()
-    strip = lambda body: re.findall(r"(\w+)(?:\[\d+\])?;", re.sub(r"/\*.*?\*/", "", body, flags=re.S))  # noqa: E731
-    body = re.search(r"typedef struct \{([^}]*)\} prs_sgm_stereo_batch;", header).group(1)
-    assert strip(body) == ["batch", "frames", "cols"] + [n for n, _ in built.SgmStereoBatch._fields_][4:]  # "int32_t rows, cols;"
-    assert "rows, cols;" in body
-    body = re.search(r"typedef struct \{([^}]*)\} prs_sgm_stereo_params;", header).group(1)
-    assert strip(body) == [n for n, _ in built.SgmStereoParams._fields_]
 
 
 def test_workspace_bytes(built):
@@ -80,10 +47,6 @@ def test_workspace_bytes(built):
                 (1, 1, 1, 1, 257, 1, 1), (1, 1, 1, 1, 1, 1, 0), (1, 1, 1, 1, 1, 1, -3), (-1, 1, 1, 1, 1, 1, 1), (1, 1, 1 << 16, 1 << 16, 16, 1, 1),
                 (1, 1 << 12, 1 << 10, 1 << 10, 16, 0, 1), (1 << 20, 1 << 20, 1, 1, 16, 0, 1)):
         assert f(*bad) == 0, bad
-
-
-def test_version_unchanged(built):
-    assert built.load().prs_version() == 104 == built.ABI_VERSION
 
 
 def test_null_context_is_refused(built):

@@ -1,6 +1,5 @@
-"""The speckle filter's part of the C-ABI: entry points exported and bound, struct layouts agreed between the library, the header's
-declared sizes and the ctypes mirrors, the workspace size, the params helper, and the ABI version unchanged (new entries under the
-current version).  No GPU needed."""
+"""The speckle filter's part of the C-ABI: the header's pointer to it, the workspace size, the null-context refusal and the params
+helper (the layouts are tests/test_abi_layout.py).  No GPU needed."""
 import ctypes as C
 
 import numpy as np
@@ -15,39 +14,10 @@ def built():
     return _lib
 
 
-def test_entry_points_exported(built):
-    lib = C.CDLL(built.LIB_PATH)
-    for name in ("prs_speckle_batch_run", "prs_speckle_workspace_bytes", "prs_speckle_struct_sizes"):
-        assert hasattr(lib, name), name
-        assert name in built.SYMBOLS
-
-
-def test_struct_sizes_and_offsets_match_the_library(built):
-    lib = built.load()
-    sizes = (C.c_uint64 * 2)()
-    lib.prs_speckle_struct_sizes(sizes)
-    assert list(sizes) == [C.sizeof(built.SpeckleParams), C.sizeof(built.SpeckleBatch)]
-    # as the header lays them out: 4 words and 4 reserved ones; 8 int32 and 8 pointers
-    assert list(sizes) == [32, 96]
-    P, B = built.SpeckleParams, built.SpeckleBatch
-    assert [(n, getattr(P, n).offset) for n, _ in P._fields_] == [
-        ("pixel_type", 0), ("companion_type", 4), ("max_diff", 8), ("max_size", 12), ("reserved", 16)]
-    assert [n for n, _ in B._fields_] == ["batch", "frames", "rows", "cols", "pitch", "companion_pitch", "label_pitch", "reserved0", "image",
-                                          "companion", "n_images", "label", "n_kept", "n_removed", "status", "workspace"]
-    assert [getattr(B, n).offset for n, _ in B._fields_] == list(range(0, 32, 4)) + list(range(32, 96, 8))
-
-
-def test_header_declares_the_structs_in_that_order(built):
+def test_dense_stereo_section_points_to_the_filter():
+    """dense stereo no longer lists the filter among what it left out"""
     import os
-    import re
     header = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include", "proslam_hip.h")).read()
-    strip = lambda body: re.findall(r"(\w+)(?:\[\d+\])?;", re.sub(r"/\*.*?\*/", "", body, flags=re.S))  # noqa: E731
-    body = re.search(r"typedef struct \{([^}]*)\} prs_speckle_batch;", header).group(1)
-    assert strip(body) == ["batch", "frames", "cols"] + [n for n, _ in built.SpeckleBatch._fields_][4:]  # "int32_t rows, cols;"
-    assert "rows, cols;" in body
-    body = re.search(r"typedef struct \{([^}]*)\} prs_speckle_params;", header).group(1)
-    assert strip(body) == [n for n, _ in built.SpeckleParams._fields_]
-    # dense stereo no longer lists the filter among what it left out
     dense = header[header.index(" * Dense stereo:"):header.index("} prs_dense_stereo_params;")]
     assert "a speckle filter," not in dense and "prs_speckle_batch_run" in dense
 
@@ -63,10 +33,6 @@ def test_workspace_bytes(built):
     for bad in ((0, 1, 1, 1), (1, 0, 1, 1), (1, 1, 0, 1), (1, 1, 1, 0), (-1, 1, 1, 1), (1, 1, 1, -5), (1, 1, 1 << 16, 1 << 15),
                 (1, 1 << 12, 1 << 10, 1 << 10), (1 << 20, 1 << 20, 1, 1), (2, 1, 1, 1 << 30)):
         assert f(*bad) == 0, bad
-
-
-def test_version_unchanged(built):
-    assert built.load().prs_version() == 104 == built.ABI_VERSION
 
 
 def test_null_context_is_refused(built):

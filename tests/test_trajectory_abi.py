@@ -1,5 +1,5 @@
-"""The trajectory evaluator's part of the C-ABI: entry points exported, struct layouts agreed between the library, the header's
-declared sizes and the ctypes mirrors, and the ABI version unchanged (new entries under the current version).  No GPU needed."""
+"""The trajectory evaluator's part of the C-ABI: the null-context refusal and the params helper (the layouts, the result's numpy
+dtype among them, are tests/test_abi_layout.py).  No GPU needed."""
 import ctypes as C
 
 import pytest
@@ -11,31 +11,6 @@ def built():
     g.build()
     from srrg2_proslam_amd import _lib
     return _lib
-
-
-def test_entry_points_exported(built):
-    lib = C.CDLL(built.LIB_PATH)
-    for name in ("prs_trajectory_eval_batch", "prs_trajectory_struct_sizes"):
-        assert hasattr(lib, name), name
-        assert name in built.SYMBOLS
-
-
-def test_struct_sizes_match_the_library(built):
-    lib = built.load()
-    sizes = (C.c_uint64 * 3)()
-    lib.prs_trajectory_struct_sizes(sizes)
-    assert list(sizes) == [C.sizeof(built.TrajectoryParams), C.sizeof(built.TrajectoryResult), C.sizeof(built.TrajectoryBatch)]
-    # as the header lays them out: 4 int32 + 8 float; 4 int32 + 56 double + 8 int32; 2 int32 + 7 pointers
-    assert list(sizes) == [48, 496, 64]
-    assert built.TrajectoryResult.S.offset == 16 and built.TrajectoryResult.kitti_n_len.offset == 464
-    from srrg2_proslam_amd import ops
-    assert ops._TRAJ_RESULT_DTYPE.itemsize == 496
-    for name, _ in built.TrajectoryResult._fields_:
-        assert ops._TRAJ_RESULT_DTYPE.fields[name][1] == getattr(built.TrajectoryResult, name).offset, name
-
-
-def test_version_unchanged(built):
-    assert built.load().prs_version() == 104 == built.ABI_VERSION
 
 
 def test_null_context_is_refused(built):

@@ -1,5 +1,5 @@
-"""The world map's part of the C-ABI: entry points exported, struct layouts agreed between the library, the header's declared sizes
-and the ctypes mirrors, the workspace size, and the ABI version unchanged (new entries under the current version).  No GPU needed."""
+"""The world map's part of the C-ABI: the workspace size, the null-context refusal and the params helper (the layouts are
+tests/test_abi_layout.py).  No GPU needed."""
 import ctypes as C
 
 import pytest
@@ -13,27 +13,6 @@ def built():
     return _lib
 
 
-def test_entry_points_exported(built):
-    lib = C.CDLL(built.LIB_PATH)
-    for name in ("prs_world_map_batch_run", "prs_world_map_workspace_bytes", "prs_world_map_struct_sizes"):
-        assert hasattr(lib, name), name
-        assert name in built.SYMBOLS
-
-
-def test_struct_sizes_and_offsets_match_the_library(built):
-    lib = built.load()
-    sizes = (C.c_uint64 * 2)()
-    lib.prs_world_map_struct_sizes(sizes)
-    assert list(sizes) == [C.sizeof(built.WorldMapParams), C.sizeof(built.WorldMapBatch)]
-    # as the header lays them out: 4 x 4 bytes; 2 int32 + 11 pointers
-    assert list(sizes) == [16, 96]
-    P, B = built.WorldMapParams, built.WorldMapBatch
-    assert [getattr(P, n).offset for n, _ in P._fields_] == [0, 4, 8, 12]
-    assert [n for n, _ in B._fields_] == ["out_stride", "reserved", "xyz", "desc", "node", "row", "n_opt", "n_out", "n_total",
-                                          "n_nonfinite", "bounds", "status", "workspace"]
-    assert [getattr(B, n).offset for n, _ in B._fields_] == [0, 4] + list(range(8, 96, 8))
-
-
 def test_workspace_bytes(built):
     lib = built.load()
     f = lib.prs_world_map_workspace_bytes
@@ -44,10 +23,6 @@ def test_workspace_bytes(built):
     assert f(4096, 4, 4096) % 16 == 0
     for bad in ((0, 1, 1), (1, 0, 1), (1, 1, 0), (-1, 1, 1)):
         assert f(*bad) == 0
-
-
-def test_version_unchanged(built):
-    assert built.load().prs_version() == 104 == built.ABI_VERSION
 
 
 def test_null_context_is_refused(built):
