@@ -247,6 +247,13 @@ DEPTH_CONSISTENCY = {"window": 2, "stride": 1, "max_rel_diff": 0.02, "min_suppor
                      "range_max": 10.0}
 
 
+# depth normals behind the dense cloud (include/proslam_hip_normals.h prs_depth_normals_params; ops.depth_normals_params).
+# BUILD-DEFINED: the reference has no dense stage.  Neighbours two pixels out, a 3 x 3 smoothing window, and a depth edge where a
+# neighbour's depth differs by more than 5 % of the centre's: the stereo depth of the matchers is quantised, so the gate is wider
+# than the consistency filter's 2 %; the range is the dense cloud's.
+DEPTH_NORMALS = {"radius": 2, "smooth": 1, "max_rel_diff": 0.05, "range_min": 0.1, "range_max": 10.0}
+
+
 def _gate(mean_t, std_t, mean_r, std_r, where):
     return {"mean_translation": (mean_t,) * 3, "std_translation": (std_t,) * 3, "mean_rotation": (mean_r,) * 3,
             "std_rotation": (std_r,) * 3, "source": where}

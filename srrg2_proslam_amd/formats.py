@@ -157,16 +157,23 @@ def associate(stamps_est, stamps_gt, max_difference=0.02):
     return gt_row, (gt_row >= 0).astype(np.uint8)
 
 
-def write_ply(path, xyz, desc=None):
+def write_ply(path, xyz, desc=None, normals=None):
     """a minimal binary-little-endian PLY of a landmark cloud (ops.WorldMapBatch.cloud_of: xyz [n, 3] or [n, 4], the first three
-    columns are written; desc: optional uint8 [n, 32], written as 32 uchar properties d0 .. d31 of every vertex)"""
+    columns are written; desc: optional uint8 [n, 32], written as 32 uchar properties d0 .. d31 of every vertex; normals: optional
+    [n, 3] or [n, 4] (ops.DepthNormalsBatch.rows_of), the first three columns written as nx ny nz behind x y z)"""
     xyz = np.asarray(xyz, np.float32)
     if xyz.ndim != 2 or xyz.shape[1] not in (3, 4):
         raise ValueError("xyz must be [n, 3] or [n, 4]")
     n = xyz.shape[0]
-    fields = [("x", "<f4"), ("y", "<f4"), ("z", "<f4")] + ([("d%d" % i, "u1") for i in range(32)] if desc is not None else [])
+    fields = [("x", "<f4"), ("y", "<f4"), ("z", "<f4")] + ([("nx", "<f4"), ("ny", "<f4"), ("nz", "<f4")] if normals is not None else []) + \
+        ([("d%d" % i, "u1") for i in range(32)] if desc is not None else [])
     rec = np.zeros(n, np.dtype(fields))
     rec["x"], rec["y"], rec["z"] = xyz[:, 0], xyz[:, 1], xyz[:, 2]
+    if normals is not None:
+        normals = np.asarray(normals, np.float32)
+        if normals.ndim != 2 or normals.shape[0] != n or normals.shape[1] not in (3, 4):
+            raise ValueError("normals must be [n, 3] or [n, 4]")
+        rec["nx"], rec["ny"], rec["nz"] = normals[:, 0], normals[:, 1], normals[:, 2]
     if desc is not None:
         desc = np.asarray(desc, np.uint8)
         if desc.shape != (n, 32):

@@ -9,7 +9,7 @@ import weakref
 
 import numpy as np
 
-from . import _lib, configs
+from . import _lib, _lib_normals, configs
 from ._lib import ProslamHipError, StereoBatch, StereoParams, TriangulatorParams
 
 CORR_DTYPE = np.dtype([("fixed_idx", np.int32), ("moving_idx", np.int32), ("response", np.float32)])
@@ -26,6 +26,11 @@ def _check(ctx, rc, what):
 def _run(ctx, entry, *args):
     """call the entry point `entry` of the library on the context: its status, ProslamHipError on a failure"""
     return _check(ctx, getattr(_lib.load(), entry)(ctx._h, *args), entry)
+
+
+def _run_normals(ctx, entry, *args):
+    """_run for an entry point of the second header (include/proslam_hip_normals.h, bound by _lib_normals)"""
+    return _check(ctx, getattr(_lib_normals.load(), entry)(ctx._h, *args), entry)
 
 
 class Context:
@@ -3009,6 +3014,130 @@ class DepthConsistencyBatch:
         d = self.descriptor(depth, pose, n_images, frame_index)
         _run(ctx, "prs_depth_consistency_batch_run", C.byref(params), C.byref(d))
         return self.out
+
+
+# ---- depth normals: depth images to oriented surface normals, per pixel and per cloud row (include/proslam_hip_normals.h) ----
+def depth_normals_params(camera, radius=configs.DEPTH_NORMALS["radius"], smooth=configs.DEPTH_NORMALS["smooth"],
+                         max_rel_diff=configs.DEPTH_NORMALS["max_rel_diff"], range_min=configs.DEPTH_NORMALS["range_min"],
+                         range_max=configs.DEPTH_NORMALS["range_max"], depth_type="u16", scale=1.0, sensor_in_robot=None):
+    """prs_depth_normals_params.  camera: a dictionary with fx, fy, cx, cy (configs.*["camera"]); the tangents reach `radius` pixels
+    (1 .. 8) to each side, the raw normals are summed over a (2 smooth + 1)^2 window (smooth 0 .. 3, 0: none); a neighbour counts
+    when its depth lies within max_rel_diff (relative) of the centre's; range_min / range_max, depth_type, scale and sensor_in_robot
+    as in depth_cloud_params.  Raises ValueError on every value the library refuses"""
+    p = _lib_normals.DepthNormalsParams()
+    p.depth_type = _depth_type(depth_type, known=True)
+    for name, value, lo, hi in (("radius", radius, 1, 8), ("smooth", smooth, 0, 3)):
+        if int(value) != value or not lo <= int(value) <= hi:
+            raise ValueError("%s must be an integer in %d .. %d" % (name, lo, hi))
+    p.radius, p.smooth = int(radius), int(smooth)
+    with np.errstate(over="ignore"):  # a value beyond float32 becomes inf and is refused below
+        p.max_rel_diff = float(np.float32(max_rel_diff))
+    if not (np.isfinite(p.max_rel_diff) and p.max_rel_diff >= 0.0):
+        raise ValueError("max_rel_diff must be finite as a float32 and at least 0")
+    p.depth_scaling_factor_to_meters = float(scale)
+    p.fx, p.fy, p.cx, p.cy = (float(camera[k]) for k in ("fx", "fy", "cx", "cy"))
+    p.range_min, p.range_max = float(range_min), float(range_max)
+    S = np.eye(4, dtype=np.float32) if sensor_in_robot is None else np.asarray(sensor_in_robot, np.float32).reshape(4, 4)
+    p.sensor_in_robot[:] = [float(x) for x in S.reshape(16)]
+    values = [p.depth_scaling_factor_to_meters, p.fx, p.fy, p.cx, p.cy, p.range_min, p.range_max] + list(p.sensor_in_robot)
+    if not np.isfinite(values).all():
+        raise ValueError("every parameter must be finite as a float32")
+    if not p.depth_scaling_factor_to_meters > 0.0:
+        raise ValueError("scale must be positive as a float32")
+    if not 0.0 <= p.range_min <= p.range_max:
+        raise ValueError("0 <= range_min <= range_max must hold")
+    return p
+
+
+class DepthNormalsBatch:
+    """the normals of B sequences of up to `frames` depth images of rows x cols pixels: owns normal [B, frames, rows, cols, 4]
+    (n0, n1, n2, w in the camera frame), n_normal [B, frames] when "n_normal" is among `outputs`, and status.  With row_stride, the
+    out_stride of an ops.DepthCloudBatch over the same images, it also owns row_normal [B, row_stride, 4], one world-frame normal per
+    cloud row, n_bad_rows [B] and n_rows [B], the rows it has written so far."""
+
+    OPTIONAL = ("n_normal",)
+
+    def __init__(self, batch, frames, rows, cols, row_stride=None, outputs=OPTIONAL, device=0):
+        import torch
+        _subset(outputs, self.OPTIONAL)
+        B, F = int(batch), int(frames)
+        if B < 1 or F < 1 or int(rows) < 1 or int(cols) < 1 or (row_stride is not None and int(row_stride) < 1):
+            raise ValueError("batch, frames, rows, cols and row_stride must be at least 1")
+        if B * F * int(rows) * int(cols) > 0x7fffffff:
+            raise ValueError("batch * frames * rows * cols must stay below 2^31")
+        _lib_normals.load()
+        self.batch, self.frames, self.rows, self.cols = B, F, int(rows), int(cols)
+        self.row_stride = None if row_stride is None else int(row_stride)
+        z = _zeros_on(device)
+        self.normal = z((B, F, self.rows, self.cols, 4), torch.float32)
+        self.n_normal = z((B, F), torch.int32) if "n_normal" in outputs else None
+        self.status = z((B,), torch.int32)
+        with_rows = self.row_stride is not None
+        self.row_normal = z((B, self.row_stride, 4), torch.float32) if with_rows else None
+        self.n_bad_rows = z((B,), torch.int32) if with_rows else None
+        self.n_rows = z((B,), torch.int32) if with_rows else None
+
+    def descriptor(self, params, depth, pose=None, n_images=None, frame_index=None, cloud=None, append=False):
+        """the prs_depth_normals_batch of device tensors: depth [B, frames, rows, cols (a view of longer rows is allowed: the
+        pitch)] of params' depth type, n_images [B] int32 or None = frames, and with cloud (an ops.DepthCloudBatch that kept "frame"
+        and "pixel", run on the same images) pose [B, pose_stride, 16] float32 and frame_index [B, frames] int32 or None"""
+        import torch
+        B, F = self.batch, self.frames
+        dtype = torch.uint16 if params.depth_type == DEPTH_U16 else torch.float32
+        if depth.dtype != dtype or depth.dim() != 4 or tuple(depth.shape[:3]) != (B, F, self.rows) or int(depth.shape[3]) < self.cols or \
+                depth.stride(3) != 1:
+            raise ValueError("depth must be a %s tensor [%d, %d, %d, >= %d] with contiguous rows" % (dtype, B, F, self.rows, self.cols))
+        if not _follow(depth, self.rows, strict=True):
+            raise ValueError("the images of depth must follow one another at rows * pitch")
+        d = _lib_normals.DepthNormalsBatch()
+        d.batch, d.frames, d.rows, d.cols = B, F, self.rows, self.cols
+        d.pitch = int(depth.stride(2)) * depth.element_size()
+        d.depth, d.normal, d.status = depth.data_ptr(), self.normal.data_ptr(), self.status.data_ptr()
+        d.n_images = _n_images_ptr(n_images, B)
+        d.n_normal = self.n_normal.data_ptr() if self.n_normal is not None else None
+        if cloud is None:
+            if append:
+                raise ValueError("append needs a cloud")
+            return d
+        if self.row_stride is None:
+            raise ValueError("this batch was built without row_stride: it has no rows for a cloud")
+        if (cloud.batch, cloud.frames, cloud.rows, cloud.cols, cloud.out_stride) != (B, F, self.rows, self.cols, self.row_stride):
+            raise ValueError("the cloud must have this batch's batch, frames, rows and cols, and row_stride as its out_stride")
+        if cloud.node is None or cloud.row is None:
+            raise ValueError('the cloud must keep its "frame" and "pixel" outputs')
+        if pose is None or pose.dim() != 3 or int(pose.shape[0]) != B or int(pose.shape[2]) != 16 or pose.dtype != torch.float32 or \
+                not pose.is_contiguous():
+            raise ValueError("with a cloud, pose must be a contiguous float32 [%d, pose_stride, 16]" % B)
+        d.pose, d.pose_stride, d.row_stride = pose.data_ptr(), int(pose.shape[1]), self.row_stride
+        d.frame_index = _int32_ptr(frame_index, "frame_index", (B, F))
+        d.row_frame, d.row_pixel, d.row_n = cloud.node.data_ptr(), cloud.row.data_ptr(), cloud.n_out.data_ptr()
+        d.row_base = self.n_rows.data_ptr() if append else None
+        d.row_normal, d.n_bad_rows = self.row_normal.data_ptr(), self.n_bad_rows.data_ptr()
+        return d
+
+    def run(self, ctx, params, depth, pose=None, n_images=None, frame_index=None, cloud=None, append=False):
+        """enqueue the normals of every image (asynchronous) and return normal; per-sequence status lands in self.status.  cloud: the
+        ops.DepthCloudBatch whose run on the same images and poses came before; its node, row and n_out are read in place and its
+        rows get their world-frame normals in row_normal.  append: the cloud was run with append, so the rows an earlier call of this
+        batch wrote (n_rows) stay as they are"""
+        d = self.descriptor(params, depth, pose, n_images, frame_index, cloud, append)
+        _run_normals(ctx, "prs_depth_normals_batch_run", C.byref(params), C.byref(d))
+        if cloud is not None:
+            self.n_rows.copy_(cloud.n_out)  # on the stream of the launch: the next append starts behind these rows
+        return self.normal
+
+    def rows_of(self, index):
+        """row_normal gathered on the device by index [B, n] (any integer type), the input row of every output row as
+        ops.WorldVoxelBatch keeps it in `index`: [B, n, 4] float32.  An index outside [0, row_stride) gives a row of zeros"""
+        import torch
+        if self.row_normal is None:
+            raise ValueError("this batch was built without row_stride: it has no rows")
+        if index.dim() != 2 or int(index.shape[0]) != self.batch or index.dtype.is_floating_point:
+            raise ValueError("index must be an integer tensor [%d, n]" % self.batch)
+        i = index.to(torch.int64)
+        inside = (i >= 0) & (i < self.row_stride)
+        rows = torch.gather(self.row_normal, 1, i.clamp(0, self.row_stride - 1).unsqueeze(-1).expand(-1, -1, 4))
+        return torch.where(inside.unsqueeze(-1), rows, torch.zeros((), dtype=rows.dtype, device=rows.device))
 
 
 # ---- image rectifier: undistort and stereo-rectify raw frames in front of the extractors (include/proslam_hip.h prs_rectify_*) ----
