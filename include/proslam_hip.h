@@ -428,23 +428,31 @@ enum {
 /* device-resident batch of B independent frames (one per sequence).
  * fixed:  [batch][fixed_stride][4] floats: (u,v,-,-) mono, (u,v,d,-) depth, (uL,vL,uR,vR) stereo
  * moving: [batch][moving_stride][4] floats: (x,y,z, information scale of the point:
- *         1 + log(numberOfOptimizations) if > 2 else 1, aligner_slice_processor_projective.cpp:46-52) */
+ *         1 + log(numberOfOptimizations) if > 2 else 1, aligner_slice_processor_projective.cpp:46-52)
+ * Alignment (the widest piece the kernels move an array in; csrc/align.hip): fixed, moving, fixed_desc and moving_desc 16 bytes -- a
+ * row of fixed / moving is one float4, a descriptor row two 16-byte halves; PRS_ERR_UNSUPPORTED otherwise, nothing launched and
+ * nothing written --, state 8 (its uint64_t members), every other array 4, inputs_changed 1.
+ * Extent: every array has batch (x stride) whole rows.  Of frame b the kernels read rows [0, n_fixed[b]) of fixed and fixed_desc and
+ * rows [0, n_moving[b]) of moving and moving_desc (counts clamped to [0, stride]); rows from the count to the stride are never read.
+ * corr: rows [0, n_corr[b]) are read where the vector is an input (PRS_MODE_LINEARIZE, a finder with nothing new to do); rows
+ * [0, n_fixed[b]) may be written (a frame has at most one correspondence per fixed point, and an earlier iteration's vector may
+ * have been longer than the final one); rows from n_fixed[b] to the stride are neither read nor written. */
 typedef struct {
   int32_t batch;
   int32_t fixed_stride;
   int32_t moving_stride;
-  const float* fixed;
-  const uint8_t* fixed_desc;     /* [batch][fixed_stride][32] */
+  const float* fixed;            /* 16-byte aligned */
+  const uint8_t* fixed_desc;     /* [batch][fixed_stride][32], 16-byte aligned */
   const int32_t* n_fixed;        /* [batch] */
-  const float* moving;
-  const uint8_t* moving_desc;    /* [batch][moving_stride][32] */
+  const float* moving;           /* 16-byte aligned */
+  const uint8_t* moving_desc;    /* [batch][moving_stride][32], 16-byte aligned */
   const int32_t* n_moving;       /* [batch] */
   const uint8_t* inputs_changed; /* [batch] setFixed/setMoving since the last call; NULL = all changed */
-  prs_pcf_state* state;          /* [batch] in/out */
-  float* X;                      /* [batch][16] in: movingInFixed guess, out: estimate (row-major 4x4) */
-  prs_corr* corr;                /* [batch][fixed_stride] in/out: the caller-owned CorrespondenceVector */
+  prs_pcf_state* state;          /* [batch] in/out, 8-byte aligned */
+  float* X;                      /* [batch][16] in: movingInFixed guess, out: estimate (row-major 4x4); read and written by element */
+  prs_corr* corr;                /* [batch][fixed_stride] in/out: the caller-owned CorrespondenceVector; 4-byte aligned */
   int32_t* n_corr;               /* [batch] in/out */
-  prs_align_result* result;      /* [batch] */
+  prs_align_result* result;      /* [batch], 4-byte aligned */
   const float* prior;            /* optional [batch][42]: additive H0 (36) and b0 (6) (an externally linearised slice) */
   const float* prior_mean;       /* optional [batch][16]: mean Z of the motion prior (NULL = identity) */
   int32_t max_fixed;             /* 0 = fixed_stride; else an upper bound on n_fixed[] the kernel sizes its LDS
@@ -895,15 +903,23 @@ typedef struct {
   int32_t max_raw_detections;             /* FAST detections per image the selection can hold: 0 = 8192, at most 32768 */
 } prs_extractor_params;
 
+/* Alignment (the widest piece the kernels move an array in; csrc/features.hip): images any (pixels are read by the byte, four at a
+ * time inside a row where a tile lies inside the image), keypoints 8 bytes (a keypoint is stored as one piece), descriptors 4 (a
+ * descriptor is stored in 32-bit words; give them 16 where they go on to a matcher), intensity, n_features and status 4.  Keypoints
+ * below 8 or descriptors below 4: PRS_ERR_UNSUPPORTED, nothing launched and nothing written.
+ * Extent: images end at the last pixel of the last row of the last image, (batch * rows - 1) * pitch + cols bytes: the pitch
+ * padding is never read.  keypoints, intensity and descriptors have batch * stride whole rows, of which rows [0, n_features[b]) of
+ * image b are written and no other; n_features and status have `batch` elements (the descriptor launch rounds the batch up to 8,
+ * the images beyond `batch` do not exist for it). */
 typedef struct {
   int32_t batch;
   int32_t rows, cols;     /* image size */
   int32_t pitch;          /* bytes between image rows (>= cols) */
-  const uint8_t* images;  /* [batch][rows][pitch] 8-bit intensity */
+  const uint8_t* images;  /* [batch][rows][pitch] 8-bit intensity, any alignment, to the last pixel */
   int32_t stride;         /* feature capacity per image = row stride of the outputs */
-  prs_kp2* keypoints;     /* out [batch][stride] (u, v) = (column, row) */
+  prs_kp2* keypoints;     /* out [batch][stride] (u, v) = (column, row), 8-byte aligned */
   float* intensity;       /* out [batch][stride] or NULL */
-  uint8_t* descriptors;   /* out [batch][stride][32] */
+  uint8_t* descriptors;   /* out [batch][stride][32], 4-byte aligned */
   int32_t* n_features;    /* out [batch] */
   int32_t* status;        /* out [batch] */
 } prs_extract_batch;
@@ -974,21 +990,28 @@ typedef struct {
   int32_t max_candidates;                /* GFTT candidates per run the selection sort holds: 0 = 8192, at most 16384 */
 } prs_selective_extractor_params;
 
+/* Alignment (csrc/selective.hip, and csrc/features.hip for the outputs): images and seeding_mask any (read by the byte), projections
+ * and keypoints 8 bytes (a prs_kp2 moves as one piece), descriptors 4 (stored in 32-bit words), every other array 4.  Projections or
+ * keypoints below 8, descriptors below 4: PRS_ERR_UNSUPPORTED, nothing launched and nothing written.
+ * Extent: images and seeding_mask end at the last pixel of the last row of the last image; the pitch padding is never read, and
+ * the mask of an image in tracking mode is not read at all.  projections has batch * projection_stride rows, of which rows
+ * [0, n_projections[b]) of image b are read; detection_radius[b] is read only where image b has projections.  The outputs as in
+ * prs_extract_batch: rows [0, n_features[b]) of image b are written and no other. */
 typedef struct {
   int32_t batch;
   int32_t rows, cols;           /* image size, each in [8, 4096] */
   int32_t pitch;                /* bytes between image rows (>= cols) */
-  const uint8_t* images;        /* [batch][rows][pitch] 8-bit intensity */
+  const uint8_t* images;        /* [batch][rows][pitch] 8-bit intensity, any alignment, to the last pixel */
   int32_t projection_stride;    /* row stride of projections (0 when projections is NULL) */
-  const prs_kp2* projections;   /* [batch][projection_stride] (u, v) or NULL = every image seeds */
+  const prs_kp2* projections;   /* [batch][projection_stride] (u, v) or NULL = every image seeds; 8-byte aligned */
   const int32_t* n_projections; /* [batch] projections of image b (0 = seeding mode), or NULL with projections */
   const int32_t* detection_radius; /* [batch] radius of image b's projections (setProjections), or NULL = 0 */
   const uint8_t* seeding_mask;  /* [batch][rows][pitch], non-zero = detect, used in seeding mode only (setKeypointDetectionMask);
-                                   NULL = none */
+                                   NULL = none; any alignment, to the last pixel */
   int32_t stride;               /* feature capacity per image = row stride of the outputs */
-  prs_kp2* keypoints;           /* out [batch][stride] (u, v) = (column, row) */
+  prs_kp2* keypoints;           /* out [batch][stride] (u, v) = (column, row), 8-byte aligned */
   float* intensity;             /* out [batch][stride] or NULL */
-  uint8_t* descriptors;         /* out [batch][stride][32] */
+  uint8_t* descriptors;         /* out [batch][stride][32], 4-byte aligned */
   int32_t* n_features;          /* out [batch] */
   int32_t* status;              /* out [batch] */
 } prs_selective_extract_batch;

@@ -3027,6 +3027,10 @@ int align_batch_launch(prs_context* ctx, const prs_pcf_params* finder, const prs
       !batch->moving_desc || !batch->n_moving || !batch->state || !batch->X || !batch->corr || !batch->n_corr || !batch->result) {
     return ctx_fail(ctx, PRS_ERR_NULL, "prs_align_batch_run: fixed, moving, correspondences, state or result not set");
   }
+  if (!aligned_to(batch->fixed, 16) || !aligned_to(batch->moving, 16) || !aligned_to(batch->fixed_desc, 16) || !aligned_to(batch->moving_desc, 16)) {
+    // a row of fixed / moving moves as one float4, a descriptor row as two 16-byte halves
+    return ctx_fail(ctx, PRS_ERR_UNSUPPORTED, "prs_align_batch_run: fixed, moving, fixed_desc and moving_desc must be 16-byte aligned");
+  }
   const AlignPlan plan = align_plan(*finder, *aligner, *batch, mode, dispatch_env(ctx));
   if (plan.status != PRS_OK) {
     return ctx_fail(ctx, plan.status, plan.message);

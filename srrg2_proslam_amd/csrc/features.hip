@@ -1449,6 +1449,9 @@ int extract_features_launch(prs_context* ctx, const prs_extractor_params* params
     // intensity_feature_extractor_base.cpp:59-64: "target feature buffer not set"
     return ctx_fail(ctx, PRS_ERR_NULL, "prs_extract_features_batch: target feature buffer not set");
   }
+  if (!aligned_to(batch->keypoints, 8) || !aligned_to(batch->descriptors, 4)) {  // describe_kernel stores a keypoint as one piece, a descriptor in words
+    return ctx_fail(ctx, PRS_ERR_UNSUPPORTED, "prs_extract_features_batch: keypoints must be 8-byte aligned, descriptors 4-byte");
+  }
   if (batch->batch <= 0) {
     return PRS_OK;
   }

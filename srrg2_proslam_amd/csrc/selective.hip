@@ -469,6 +469,10 @@ int selective_extract_launch(prs_context* ctx, const prs_selective_extractor_par
   if (batch->projections && (!batch->n_projections || batch->projection_stride <= 0)) {
     return ctx_fail(ctx, PRS_ERR_NULL, "prs_extract_features_selective_batch: projections without n_projections / projection_stride");
   }
+  if (!aligned_to(batch->keypoints, 8) || !aligned_to(batch->descriptors, 4) || !aligned_to(batch->projections, 8)) {
+    // mask_raster_kernel loads a projection, describe_kernel stores a keypoint as one piece and a descriptor in words
+    return ctx_fail(ctx, PRS_ERR_UNSUPPORTED, "prs_extract_features_selective_batch: keypoints and projections must be 8-byte aligned, descriptors 4-byte");
+  }
   if (batch->batch <= 0) {
     return PRS_OK;
   }

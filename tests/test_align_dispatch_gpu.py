@@ -95,7 +95,7 @@ def _cases(cfg_name, seed, n, max_fixed, n_kp=None, full=0):
     return configs.get(cfg_name), out
 
 
-def _oracle_frame(oracle, cfg, c, fkw, akw, sensor=False, mprior=False, of=None):
+def _oracle_frame(oracle, cfg, c, fkw, akw, sensor=False, mprior=False, of=None, prior=None):
     if of is None:
         of = oracle.ProjectiveFinder(pcf_params_from_cfg(oracle, cfg, **fkw))
     of.set_fixed(c["fixed"], c["dfix"])
@@ -110,7 +110,7 @@ def _oracle_frame(oracle, cfg, c, fkw, akw, sensor=False, mprior=False, of=None)
         oap.enable_motion_prior = 1
         for i, v in enumerate(MPRIOR_INFO):
             oap.motion_prior_info[i] = v
-    res, corr = oracle.align_frame(of, oap, c["fixed"], c["xyz"], c["scale"], c["X0"], prior_mean=c["X0"] if mprior else None)
+    res, corr = oracle.align_frame(of, oap, c["fixed"], c["xyz"], c["scale"], c["X0"], prior=prior, prior_mean=c["X0"] if mprior else None)
     return of, res, corr
 
 

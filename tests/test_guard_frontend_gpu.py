@@ -2,7 +2,9 @@
 prs_stereo_match_batch, prs_triangulate_dev, prs_bruteforce_match_batch and prs_scene_clip_batch.  One case each; the last frame,
 pair or scene is the full one, so its counts equal the strides and its last row adjoins a band.  Each case runs with fill 0x00 and
 with fill 0xFF, equals the oracle as the stage's own test asserts it, gives the same bytes in both runs and leaves every band
-clean.  Not covered here: the two feature extractors and prs_align_batch_run."""
+clean.  The two feature extractors and prs_align_batch_run: tests/test_guard_tracking_gpu.py.  What stays invisible to these cases: a
+read past an array's end whose value reaches no result, and memory the library owns (the context's scratch arenas), which
+cannot be placed."""
 import ctypes as C
 
 import numpy as np
