@@ -127,6 +127,55 @@ PRS_API int prs_version(void);
  * dimension, so a launch of `workgroups` workgroups of `threads` threads fits iff workgroups >= 1, 1 <= threads <= 1024 and
  * workgroups * threads <= 2^32 - 1 -- 2^24 - 1 workgroups of 256 threads.  1 when it fits, else 0 (pure: no context, no device). */
 PRS_API int prs_launch_fits(int64_t workgroups, int32_t threads);
+/* ---- guard mode: the library's own device and pinned memory between guard bands (tests and tools).
+ * Every block the library allocates -- the context's work, staging and pinned arenas, the aligner's six job buffers, the arrays of a
+ * prs_map, a prs_pcf handle's device and pinned block, a place database's and a place bank's arrays, the information table -- goes
+ * through one allocation path, each with a short name.  The environment variable PRS_GUARD_FILL=00 or ff, read when the context is
+ * created (any other value: off), turns guard mode on for that context and everything created on it:
+ *   - a block is [front band | user bytes | tail band].  The front band has PRS_GUARD_BAND bytes, so the user pointer keeps the
+ *     allocator's alignment; the tail band begins at the first byte behind the bytes the site requested, without rounding, and has
+ *     max(PRS_GUARD_BAND, the slack the site's rule adds to that request with guard off) bytes: whatever stays inside its block
+ *     without guard mode stays inside it with it, so guard mode cannot turn a silent overrun into a fault.  Both bands are painted
+ *     with PRS_GUARD_PATTERN, the user bytes with the fill;
+ *   - the grow-only blocks whose contents belong to whatever call runs next -- every work and staging arena, the pinned arena, the
+ *     aligner's job buffers -- are painted with the fill again at every request, on the stream in front of the launches.  Memory that
+ *     carries state between calls (a prs_map, a prs_pcf handle's block, a place database or bank, the information table) is painted
+ *     when it is allocated only;
+ *   - before a block is freed -- by growth, by a handle's destroy, by prs_context_destroy -- its bands are checked, and a damaged
+ *     one is latched in the context with its name.  prs_context_destroy prints what is latched to stderr and returns the count.
+ * With guard mode off every site requests the bytes it always did (prs_guard_layout with guard = 0 is that rule) and nothing is
+ * painted or checked.
+ * prs_guard_layout: the layout rule (pure: no context, no device).  slack_rule: PRS_GUARD_SLACK_EXACT (bytes), _QUARTER
+ * (bytes + bytes / 4 + 4096: the work arenas, the small staging arenas, the aligner's job buffers) or _HALF (bytes + bytes / 2 + 4096:
+ * the default staging arena and the pinned arena).  With guard = 0: total = that size, user_offset = 0, tail_bytes = the slack.
+ * PRS_ERR_NULL without `out`, PRS_ERR_UNSUPPORTED for an unknown rule.
+ * prs_context_guard_regions: the context's live blocks in allocation order, at most `capacity` of them written; returns how many
+ * there are.  prs_context_guard_check: synchronises the context's stream, copies every live block's bands to the host and returns
+ * the number of damaged (block, side) pairs, those latched from freed blocks included; `report` (may be NULL) receives one line
+ * "name front|tail offset" for each, offset = the first damaged byte counted from the band's start, truncated to report_bytes with
+ * a terminating 0.  Both return PRS_ERR_UNSUPPORTED on a context that is not in guard mode. */
+#define PRS_GUARD_SLACK_EXACT 0
+#define PRS_GUARD_SLACK_QUARTER 1
+#define PRS_GUARD_SLACK_HALF 2
+#define PRS_GUARD_BAND 4096
+#define PRS_GUARD_PATTERN 0xA5
+typedef struct {
+  uint64_t total;       /* bytes the allocator is asked for */
+  uint64_t user_offset; /* of the user bytes in the block */
+  uint64_t tail_bytes;  /* behind the user bytes: the tail band, or with guard off the slack */
+} prs_guard_extent;
+typedef struct {
+  void* user;          /* first user byte (device memory, or pinned host memory) */
+  uint64_t bytes;      /* user bytes: what the site requested when it allocated the block */
+  uint64_t tail_bytes; /* the tail band, at user + bytes */
+  int32_t pinned;      /* 1: pinned host memory */
+  int32_t reserved;
+  char name[48];
+} prs_guard_region;
+PRS_API int prs_guard_layout(uint64_t bytes, int32_t slack_rule, int32_t guard, prs_guard_extent* out);
+PRS_API int prs_context_guard_check(prs_context* ctx, char* report, uint64_t report_bytes);
+PRS_API int prs_context_guard_regions(prs_context* ctx, prs_guard_region* out, int32_t capacity);
+PRS_API void prs_guard_struct_sizes(uint64_t* sizes2);
 /* The parameter structs below carry no size field and grow at their END between versions (round 5 added three int32 fields to
  * prs_aligner_params).  PRS_ABI_VERSION is what this header describes, prs_version() what the loaded library was built from; a
  * client checks that they agree once (prs_abi_check: also the sizes of the structs it will pass, as the client's compiler laid
@@ -159,7 +208,8 @@ PRS_API int prs_launch_fits(int64_t workgroups, int32_t threads);
  * prs_speckle_batch_run and prs_speckle_struct_sizes; and semi-global dense stereo: prs_sgm_stereo_params, prs_sgm_stereo_batch,
  * prs_sgm_stereo_workspace_bytes, prs_sgm_stereo_batch_run and prs_sgm_stereo_struct_sizes; and the depth consistency filter:
  * prs_depth_consistency_params, prs_depth_consistency_batch, prs_depth_consistency_workspace_bytes, prs_depth_consistency_batch_run
- * and prs_depth_consistency_struct_sizes).  Callers memset() parameter structs before
+ * and prs_depth_consistency_struct_sizes; and guard mode for tests and tools: prs_guard_extent, prs_guard_region, prs_guard_layout,
+ * prs_context_guard_check, prs_context_guard_regions and prs_guard_struct_sizes).  Callers memset() parameter structs before
  * filling them, so that fields they do not know select the shipped defaults (all zero). */
 #define PRS_ABI_VERSION 104
 PRS_API int prs_abi_check(int32_t header_version, uint64_t sizeof_stereo_params, uint64_t sizeof_pcf_params, uint64_t sizeof_aligner_params,

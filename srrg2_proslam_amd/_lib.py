@@ -630,6 +630,20 @@ class DispatchPlan(C.Structure):
     _fields_ = [("status", C.c_int32), ("message", C.c_char_p), ("n_launches", C.c_int32), ("launch", PlanLaunch * 4), ("fact", C.c_int32 * 48)]
 
 
+class GuardExtent(C.Structure):
+    """prs_guard_extent: what prs_guard_layout answers"""
+    _fields_ = [("total", C.c_uint64), ("user_offset", C.c_uint64), ("tail_bytes", C.c_uint64)]
+
+
+class GuardRegion(C.Structure):
+    """prs_guard_region: a live block of a context in guard mode"""
+    _fields_ = [("user", C.c_void_p), ("bytes", C.c_uint64), ("tail_bytes", C.c_uint64), ("pinned", C.c_int32), ("reserved", C.c_int32),
+                ("name", C.c_char * 48)]
+
+
+GUARD_SLACK_EXACT, GUARD_SLACK_QUARTER, GUARD_SLACK_HALF = 0, 1, 2
+GUARD_BAND, GUARD_PATTERN = 4096, 0xA5
+
 DISPATCH_STEREO, DISPATCH_ALIGN, DISPATCH_BRUTEFORCE, DISPATCH_MERGE = 0, 1, 2, 3
 # the PRS_PLAN_<FAMILY>_* enumerators in order, lower case
 PLAN_FACTS = {
@@ -651,6 +665,10 @@ _i32p = C.POINTER(C.c_int32)
 SYMBOLS = {
     "prs_version": (C.c_int, []),
     "prs_launch_fits": (C.c_int, [C.c_int64, C.c_int32]),
+    "prs_guard_layout": (C.c_int, [C.c_uint64, C.c_int32, C.c_int32, C.POINTER(GuardExtent)]),
+    "prs_context_guard_check": (C.c_int, [_vp, C.c_char_p, C.c_uint64]),
+    "prs_context_guard_regions": (C.c_int, [_vp, C.POINTER(GuardRegion), C.c_int32]),
+    "prs_guard_struct_sizes": (None, [C.POINTER(C.c_uint64)]),
     "prs_abi_check": (C.c_int, [C.c_int32, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64]),
     "prs_status_string": (C.c_char_p, [C.c_int]),
     "prs_context_create": (C.c_int, [C.c_int, C.POINTER(_vp)]),
@@ -799,6 +817,7 @@ SYMBOLS = {
 
 # every *_struct_sizes entry with the mirrors of the structs it reports, in the order its function writes them; load() compares them
 STRUCT_SIZES = (
+    ("prs_guard_struct_sizes", (GuardExtent, GuardRegion)),
     ("prs_place_bank_struct_sizes", (PlaceBankAppend, PlaceBankLinks)),
     ("prs_pose_graph_struct_sizes", (PoseGraphParams, PoseGraphResult, PoseGraphs, PoseGraphClosures)),
     ("prs_pose_graph_lm_struct_sizes", (PoseGraphLmParams, PoseGraphLmResult)),

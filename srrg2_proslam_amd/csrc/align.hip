@@ -2781,29 +2781,31 @@ struct SplitJob {
   size_t own_bytes[6] = {0, 0, 0, 0, 0, 0};
   hipStream_t stream  = nullptr;  // the stream the rounds run on: where they were enqueued, or where the captured graph was last replayed (finish synchronises this one)
   hipStream_t capture_stream = nullptr;  // the stream align_batch_launch enqueued / captured on (what a rearm without a stream goes back to)
+  prs_context* ctx = nullptr;  // the owner: the buffers are blocks of its owned-allocation path
   ~SplitJob() {
     for (void* p : own) {
-      if (p) {
-        (void) hipFree(p);
-      }
+      owned_free(ctx, p);
     }
   }
+  // (guard mode: a buffer that is reused is painted with the fill again on `s`, in front of the batch's launches -- nothing in
+  // these six carries over from one batch to the next; split_init_kernel writes every control word a launch reads)
   void* buffer(hipStream_t s, int i, size_t bytes) {
+    static const char* const kName[6] = {"align.ctl", "align.ops", "align.lattice", "align.rowcache", "align.qcache", "align.missq"};
     if (bytes <= own_bytes[i]) {
+      owned_repaint(ctx, own[i], bytes, s);
       return own[i];
     }
     if (own[i]) {
       (void) hipStreamSynchronize(s);
-      (void) hipFree(own[i]);
+      owned_free(ctx, own[i]);
       own[i]       = nullptr;
       own_bytes[i] = 0;
     }
-    const size_t want = bytes + bytes / 4 + 4096;
-    if (hipMalloc(&own[i], want) != hipSuccess) {
+    if (owned_alloc(ctx, kName[i], &own[i], bytes, PRS_GUARD_SLACK_QUARTER) != hipSuccess) {
       own[i] = nullptr;
       return nullptr;
     }
-    own_bytes[i] = want;
+    own_bytes[i] = ctx->guard_fill >= 0 ? bytes : (size_t) guard_layout(bytes, PRS_GUARD_SLACK_QUARTER, false).total;
     return own[i];
   }
   AlignArgs g, gs;                      // Gauss-Newton / search kernel arguments
@@ -3074,6 +3076,7 @@ int align_batch_launch(prs_context* ctx, const prs_pcf_params* finder, const prs
   SplitJob* job = static_cast<SplitJob*>(ctx->align_job);
   if (!job) {
     job                 = new SplitJob();
+    job->ctx            = ctx;
     ctx->align_job      = job;
     ctx->align_job_free = [](void* p) { delete static_cast<SplitJob*>(p); };
   }

@@ -23,26 +23,133 @@ int ctx_fail_hip(prs_context* ctx, hipError_t e, const char* what) {
   return PRS_ERR_HIP;
 }
 
+namespace {
+
+// the two bands of a live block against PRS_GUARD_PATTERN: appends "name front|tail offset" for each damaged one.  The caller has
+// drained the streams that use the block
+hipError_t guard_examine(const GuardBlock& b, std::vector<std::string>* found) {
+  const size_t front = PRS_GUARD_BAND;
+  std::vector<unsigned char> host;
+  const unsigned char* base = static_cast<const unsigned char*>(b.user) - front;
+  const unsigned char* band[2] = {base, static_cast<const unsigned char*>(b.user) + b.bytes};
+  const size_t len[2]          = {front, b.tail};
+  for (int side = 0; side < 2; ++side) {
+    const unsigned char* seen = band[side];
+    if (!b.pinned) {
+      host.resize(len[side]);
+      const hipError_t e = hipMemcpy(host.data(), band[side], len[side], hipMemcpyDeviceToHost);
+      if (e != hipSuccess) {
+        return e;
+      }
+      seen = host.data();
+    }
+    for (size_t i = 0; i < len[side]; ++i) {
+      if (seen[i] != PRS_GUARD_PATTERN) {
+        found->push_back(std::string(b.name) + (side == 0 ? " front " : " tail ") + std::to_string(i));
+        break;
+      }
+    }
+  }
+  return hipSuccess;
+}
+
+}  // namespace
+
+hipError_t owned_alloc(prs_context* ctx, const char* name, void** p, size_t bytes, int rule, bool pinned) {
+  *p                     = nullptr;
+  const bool guard       = ctx->guard_fill >= 0;
+  const prs_guard_extent x = guard_layout(bytes, rule, guard);
+  void* base             = nullptr;
+  hipError_t e           = pinned ? hipHostMalloc(&base, x.total, hipHostMallocDefault) : hipMalloc(&base, x.total);
+  if (e != hipSuccess || !guard) {
+    *p = e == hipSuccess ? base : nullptr;
+    return e;
+  }
+  unsigned char* b = static_cast<unsigned char*>(base);
+  if (pinned) {
+    memset(b, PRS_GUARD_PATTERN, x.user_offset);
+    memset(b + x.user_offset, ctx->guard_fill, bytes);
+    memset(b + x.user_offset + bytes, PRS_GUARD_PATTERN, x.tail_bytes);
+  } else {
+    e = hipMemsetAsync(b, PRS_GUARD_PATTERN, x.user_offset, ctx->stream);
+    if (e == hipSuccess && bytes > 0) {
+      e = hipMemsetAsync(b + x.user_offset, ctx->guard_fill, bytes, ctx->stream);
+    }
+    if (e == hipSuccess) {
+      e = hipMemsetAsync(b + x.user_offset + bytes, PRS_GUARD_PATTERN, x.tail_bytes, ctx->stream);
+    }
+    if (e == hipSuccess) {
+      e = hipStreamSynchronize(ctx->stream);
+    }
+    if (e != hipSuccess) {
+      (void) hipFree(base);
+      return e;
+    }
+  }
+  ctx->guard_blocks.push_back({b + x.user_offset, bytes, (size_t) x.tail_bytes, name, pinned});
+  *p = b + x.user_offset;
+  return hipSuccess;
+}
+
+void owned_free(prs_context* ctx, void* p, bool pinned) {
+  if (!p) {
+    return;
+  }
+  if (ctx->guard_fill >= 0) {
+    for (size_t i = 0; i < ctx->guard_blocks.size(); ++i) {
+      if (ctx->guard_blocks[i].user == p) {
+        // the evidence goes with the block: look at it first (a copy that fails is latched as such)
+        if (guard_examine(ctx->guard_blocks[i], &ctx->guard_latched) != hipSuccess) {
+          (void) hipGetLastError();
+          ctx->guard_latched.push_back(std::string(ctx->guard_blocks[i].name) + " unreadable 0");
+        }
+        pinned = ctx->guard_blocks[i].pinned;
+        ctx->guard_blocks.erase(ctx->guard_blocks.begin() + (ptrdiff_t) i);
+        p = static_cast<unsigned char*>(p) - PRS_GUARD_BAND;
+        break;
+      }
+    }
+  }
+  (void) (pinned ? hipHostFree(p) : hipFree(p));
+}
+
+void owned_repaint(prs_context* ctx, void* p, size_t bytes, hipStream_t stream, bool pinned) {
+  if (ctx->guard_fill < 0 || !p || bytes == 0) {
+    return;
+  }
+  if (pinned) {
+    (void) hipStreamSynchronize(ctx->stream);  // (an entry point has synchronised before it returned; a copy still in flight would be a finding of its own)
+    memset(p, ctx->guard_fill, bytes);
+  } else {
+    (void) hipMemsetAsync(p, ctx->guard_fill, bytes, stream);
+  }
+}
+
+static const char* const kArenaName[ARENA_COUNT] = {"arena.work0", "arena.work1", "arena.work2", "arena.work3", "arena.stage",
+                                                    "arena.stage_bruteforce", "arena.stage_solver", "arena.stage_pose_graph", "arena.pinned"};
+
 void* ctx_arena(prs_context* ctx, Arena arena, size_t bytes) {
-  auto& a = ctx->arena[arena];
+  auto& a           = ctx->arena[arena];
+  const bool pinned = arena == ARENA_PINNED;
   if (bytes <= a.size) {
+    // what a work or staging arena holds belongs to whatever call runs next: guard mode paints the request again
+    owned_repaint(ctx, a.p, bytes, ctx->stream, pinned);
     return a.p;
   }
-  const bool pinned = arena == ARENA_PINNED;
   if (a.p) {
     (void) hipStreamSynchronize(ctx->stream);  // whatever was enqueued on the old block finishes before it goes
-    (void) (pinned ? hipHostFree(a.p) : hipFree(a.p));
+    owned_free(ctx, a.p, pinned);
     a.p    = nullptr;
     a.size = 0;
   }
   // slack: the default staging pair grows by half, the work arenas and the two small staging arenas by a quarter
-  const size_t want = bytes + bytes / (arena == ARENA_STAGE || pinned ? 2 : 4) + 4096;
-  void* p           = nullptr;
-  if ((pinned ? hipHostMalloc(&p, want, hipHostMallocDefault) : hipMalloc(&p, want)) != hipSuccess) {
+  const int rule = arena == ARENA_STAGE || pinned ? PRS_GUARD_SLACK_HALF : PRS_GUARD_SLACK_QUARTER;
+  void* p        = nullptr;
+  if (owned_alloc(ctx, kArenaName[arena], &p, bytes, rule, pinned) != hipSuccess) {
     return nullptr;
   }
   a.p    = p;
-  a.size = want;
+  a.size = ctx->guard_fill >= 0 ? bytes : (size_t) guard_layout(bytes, rule, false).total;  // (guard mode: the tail band begins behind the request)
   return p;
 }
 
@@ -106,11 +213,11 @@ const float* ctx_info_scale_table(prs_context* ctx) {
     }
     prs_info_scale_from_nopt(n, kN, scale);
     float* d = nullptr;
-    if (hipMalloc(&d, sizeof(scale)) != hipSuccess) {
+    if (owned_alloc(ctx, "info_lut", &d, sizeof(scale)) != hipSuccess) {
       return nullptr;
     }
     if (hipMemcpy(d, scale, sizeof(scale), hipMemcpyHostToDevice) != hipSuccess) {
-      (void) hipFree(d);
+      owned_free(ctx, d);
       return nullptr;
     }
     ctx->d_info_lut = d;
@@ -124,9 +231,9 @@ unsigned long long* ctx_stamps(prs_context* ctx, size_t bytes) {
   }
   if (bytes > ctx->d_stamps_size) {
     if (ctx->d_stamps) {
-      (void) hipFree(ctx->d_stamps);
+      owned_free(ctx, ctx->d_stamps);
     }
-    if (hipMalloc(reinterpret_cast<void**>(&ctx->d_stamps), bytes) != hipSuccess) {
+    if (owned_alloc(ctx, "stamps", &ctx->d_stamps, bytes) != hipSuccess) {
       ctx->d_stamps      = nullptr;
       ctx->d_stamps_size = 0;
       return nullptr;
@@ -261,6 +368,8 @@ int prs_context_create(int device_id, prs_context** out) {
   ctx->bf_mfma         = !bfm || bfm[0] == 'a' ? PRS_BF_DENSE_MATRIX_WHEN_FULL : (bfm[0] == '1' ? PRS_BF_DENSE_MATRIX : PRS_BF_DENSE_POPCOUNT);
   const char* mfused   = getenv("PRS_MERGE_FUSED");
   ctx->merge_fused     = mfused && mfused[0] == '1';
+  const char* gfill    = getenv("PRS_GUARD_FILL");  // guard mode (tests): "00" or "ff", anything else is off
+  ctx->guard_fill      = gfill && !strcmp(gfill, "00") ? 0x00 : (gfill && !strcmp(gfill, "ff") ? 0xFF : -1);
   *out                 = ctx;
   return PRS_OK;
 }
@@ -297,16 +406,15 @@ int prs_context_destroy(prs_context* ctx) {
   if (ctx->align_job && ctx->align_job_free) {
     ctx->align_job_free(ctx->align_job);
   }
-  if (ctx->d_stamps) {
-    (void) hipFree(ctx->d_stamps);
-  }
-  if (ctx->d_info_lut) {
-    (void) hipFree(ctx->d_info_lut);
-  }
+  owned_free(ctx, ctx->d_stamps);
+  owned_free(ctx, ctx->d_info_lut);
   for (int i = 0; i < ARENA_COUNT; ++i) {
-    if (ctx->arena[i].p) {
-      (void) (i == ARENA_PINNED ? hipHostFree(ctx->arena[i].p) : hipFree(ctx->arena[i].p));
-    }
+    owned_free(ctx, ctx->arena[i].p, i == ARENA_PINNED);
+  }
+  // guard mode: every block has been looked at before it went; what was damaged does not leave silently with the context
+  const int damaged = (int) ctx->guard_latched.size();
+  for (const std::string& v : ctx->guard_latched) {
+    fprintf(stderr, "[prs guard] damaged band: %s\n", v.c_str());
   }
   if (ctx->own) {
     (void) hipStreamDestroy(ctx->own);
@@ -317,7 +425,73 @@ int prs_context_destroy(prs_context* ctx) {
     }
   }
   delete ctx;
+  return damaged;
+}
+
+int prs_guard_layout(uint64_t bytes, int32_t slack_rule, int32_t guard, prs_guard_extent* out) {
+  if (!out) {
+    return PRS_ERR_NULL;
+  }
+  if (slack_rule != PRS_GUARD_SLACK_EXACT && slack_rule != PRS_GUARD_SLACK_QUARTER && slack_rule != PRS_GUARD_SLACK_HALF) {
+    return PRS_ERR_UNSUPPORTED;
+  }
+  *out = guard_layout(bytes, slack_rule, guard != 0);
   return PRS_OK;
+}
+
+void prs_guard_struct_sizes(uint64_t* sizes2) {
+  sizes2[0] = sizeof(prs_guard_extent);
+  sizes2[1] = sizeof(prs_guard_region);
+}
+
+int prs_context_guard_regions(prs_context* ctx, prs_guard_region* out, int32_t capacity) {
+  if (!ctx) {
+    return PRS_ERR_NULL;
+  }
+  if (ctx->guard_fill < 0) {
+    return ctx_fail(ctx, PRS_ERR_UNSUPPORTED, "prs_context_guard_regions: the context is not in guard mode (PRS_GUARD_FILL=00 or ff at prs_context_create)");
+  }
+  const int32_t n = (int32_t) ctx->guard_blocks.size();
+  for (int32_t i = 0; out && i < n && i < capacity; ++i) {
+    const GuardBlock& b = ctx->guard_blocks[(size_t) i];
+    prs_guard_region r;
+    memset(&r, 0, sizeof(r));
+    r.user       = b.user;
+    r.bytes      = b.bytes;
+    r.tail_bytes = b.tail;
+    r.pinned     = b.pinned ? 1 : 0;
+    strncpy(r.name, b.name, sizeof(r.name) - 1);
+    out[i] = r;
+  }
+  return n;
+}
+
+int prs_context_guard_check(prs_context* ctx, char* report, uint64_t report_bytes) {
+  if (!ctx) {
+    return PRS_ERR_NULL;
+  }
+  if (ctx->guard_fill < 0) {
+    return ctx_fail(ctx, PRS_ERR_UNSUPPORTED, "prs_context_guard_check: the context is not in guard mode (PRS_GUARD_FILL=00 or ff at prs_context_create)");
+  }
+  (void) hipSetDevice(ctx->device);
+  hipError_t e = hipStreamSynchronize(ctx->stream);
+  std::vector<std::string> found = ctx->guard_latched;
+  for (size_t i = 0; e == hipSuccess && i < ctx->guard_blocks.size(); ++i) {
+    e = guard_examine(ctx->guard_blocks[i], &found);
+  }
+  if (e != hipSuccess) {
+    return ctx_fail_hip(ctx, e, "prs_context_guard_check");
+  }
+  if (report && report_bytes > 0) {
+    std::string text;
+    for (const std::string& v : found) {
+      text += v + "\n";
+    }
+    const size_t n = text.size() < report_bytes - 1 ? text.size() : (size_t) report_bytes - 1;
+    memcpy(report, text.data(), n);
+    report[n] = 0;
+  }
+  return (int) found.size();
 }
 
 int prs_context_set_bruteforce_dense_phase(prs_context* ctx, int32_t mode) {

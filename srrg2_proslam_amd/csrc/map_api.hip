@@ -68,18 +68,17 @@ int fail(prs_map* h, int status, const char* what) {
     }                                                        \
   } while (0)
 
+// (the map's arrays carry its state from call to call: guard mode paints them when they are allocated and never again)
 template <typename T>
-hipError_t alloc(T** p, size_t n) {
-  return hipMalloc(reinterpret_cast<void**>(p), (n ? n : 1) * sizeof(T));
+hipError_t alloc(prs_context* ctx, const char* name, T** p, size_t n) {
+  return prs::owned_alloc(ctx, name, p, (n ? n : 1) * sizeof(T));
 }
 
 void release(prs_map* h) {
   void* ptrs[] = {h->d_coords, h->d_desc, h->d_state, h->d_cov, h->d_n_opt, h->d_inlier, h->d_n_meas, h->d_meas,
                   h->d_poses, h->d_measurement, h->d_mdesc, h->d_corr, h->d_index_map, h->d_small};
   for (void* p : ptrs) {
-    if (p) {
-      (void) hipFree(p);
-    }
+    prs::owned_free(h->ctx, p);
   }
 }
 
@@ -102,20 +101,20 @@ int prs_map_create(prs_context* ctx, int32_t capacity, int32_t max_measurements,
   h->max_frames = max_frames;
   h->max_measured = max_measured;
   const size_t cap = (size_t) capacity;
-  hipError_t e = alloc(&h->d_coords, cap * 4);
-  e = e == hipSuccess ? alloc(&h->d_desc, cap * PRS_DESC_BYTES) : e;
-  e = e == hipSuccess ? alloc(&h->d_state, cap * 4) : e;
-  e = e == hipSuccess ? alloc(&h->d_cov, cap * 9) : e;
-  e = e == hipSuccess ? alloc(&h->d_n_opt, cap) : e;
-  e = e == hipSuccess ? alloc(&h->d_inlier, cap) : e;
-  e = e == hipSuccess ? alloc(&h->d_n_meas, cap) : e;
-  e = e == hipSuccess ? alloc(&h->d_meas, cap * (size_t) (max_measurements > 0 ? max_measurements : 1)) : e;
-  e = e == hipSuccess ? alloc(&h->d_poses, (size_t) max_frames) : e;
-  e = e == hipSuccess ? alloc(&h->d_measurement, (size_t) max_measured * 4) : e;
-  e = e == hipSuccess ? alloc(&h->d_mdesc, (size_t) max_measured * PRS_DESC_BYTES) : e;
-  e = e == hipSuccess ? alloc(&h->d_corr, (size_t) max_measured) : e;
-  e = e == hipSuccess ? alloc(&h->d_index_map, cap) : e;
-  e = e == hipSuccess ? alloc(&h->d_small, kSmall) : e;
+  hipError_t e = alloc(ctx, "map.coords", &h->d_coords, cap * 4);
+  e = e == hipSuccess ? alloc(ctx, "map.desc", &h->d_desc, cap * PRS_DESC_BYTES) : e;
+  e = e == hipSuccess ? alloc(ctx, "map.state", &h->d_state, cap * 4) : e;
+  e = e == hipSuccess ? alloc(ctx, "map.cov", &h->d_cov, cap * 9) : e;
+  e = e == hipSuccess ? alloc(ctx, "map.n_opt", &h->d_n_opt, cap) : e;
+  e = e == hipSuccess ? alloc(ctx, "map.inlier", &h->d_inlier, cap) : e;
+  e = e == hipSuccess ? alloc(ctx, "map.n_meas", &h->d_n_meas, cap) : e;
+  e = e == hipSuccess ? alloc(ctx, "map.meas", &h->d_meas, cap * (size_t) (max_measurements > 0 ? max_measurements : 1)) : e;
+  e = e == hipSuccess ? alloc(ctx, "map.poses", &h->d_poses, (size_t) max_frames) : e;
+  e = e == hipSuccess ? alloc(ctx, "map.measurement", &h->d_measurement, (size_t) max_measured * 4) : e;
+  e = e == hipSuccess ? alloc(ctx, "map.mdesc", &h->d_mdesc, (size_t) max_measured * PRS_DESC_BYTES) : e;
+  e = e == hipSuccess ? alloc(ctx, "map.corr", &h->d_corr, (size_t) max_measured) : e;
+  e = e == hipSuccess ? alloc(ctx, "map.index_map", &h->d_index_map, cap) : e;
+  e = e == hipSuccess ? alloc(ctx, "map.small", &h->d_small, kSmall) : e;
   if (e == hipSuccess) {
     e = hipMemsetAsync(h->d_small, 0, kSmall, ctx->stream);
   }
@@ -158,15 +157,16 @@ int prs_map_reserve(prs_map* h, int32_t capacity) {
   uint32_t *n_opt = nullptr, *n_meas = nullptr;
   prs_camera_measurement* meas = nullptr;
   int32_t* index_map           = nullptr;
-  hipError_t e = alloc(&coords, cap * 4);
-  e = e == hipSuccess ? alloc(&desc, cap * PRS_DESC_BYTES) : e;
-  e = e == hipSuccess ? alloc(&state, cap * 4) : e;
-  e = e == hipSuccess ? alloc(&cov, cap * 9) : e;
-  e = e == hipSuccess ? alloc(&n_opt, cap) : e;
-  e = e == hipSuccess ? alloc(&inlier, cap) : e;
-  e = e == hipSuccess ? alloc(&n_meas, cap) : e;
-  e = e == hipSuccess ? alloc(&meas, cap * mm) : e;
-  e = e == hipSuccess ? alloc(&index_map, cap) : e;
+  prs_context* ctx = h->ctx;
+  hipError_t e = alloc(ctx, "map.coords", &coords, cap * 4);
+  e = e == hipSuccess ? alloc(ctx, "map.desc", &desc, cap * PRS_DESC_BYTES) : e;
+  e = e == hipSuccess ? alloc(ctx, "map.state", &state, cap * 4) : e;
+  e = e == hipSuccess ? alloc(ctx, "map.cov", &cov, cap * 9) : e;
+  e = e == hipSuccess ? alloc(ctx, "map.n_opt", &n_opt, cap) : e;
+  e = e == hipSuccess ? alloc(ctx, "map.inlier", &inlier, cap) : e;
+  e = e == hipSuccess ? alloc(ctx, "map.n_meas", &n_meas, cap) : e;
+  e = e == hipSuccess ? alloc(ctx, "map.meas", &meas, cap * mm) : e;
+  e = e == hipSuccess ? alloc(ctx, "map.index_map", &index_map, cap) : e;
   auto copy = [&](void* dst, const void* src, size_t bytes) {
     if (e == hipSuccess && bytes) {
       e = hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, s);
@@ -186,15 +186,13 @@ int prs_map_reserve(prs_map* h, int32_t capacity) {
   void* fresh[] = {coords, desc, state, cov, n_opt, inlier, n_meas, meas, index_map};
   if (e != hipSuccess) {
     for (void* p : fresh) {
-      if (p) {
-        (void) hipFree(p);
-      }
+      prs::owned_free(ctx, p);
     }
     return prs::ctx_fail_hip(h->ctx, e, "prs_map_reserve: device allocation / copy");
   }
   void* old[] = {h->d_coords, h->d_desc, h->d_state, h->d_cov, h->d_n_opt, h->d_inlier, h->d_n_meas, h->d_meas, h->d_index_map};
   for (void* p : old) {
-    (void) hipFree(p);
+    prs::owned_free(ctx, p);
   }
   h->d_coords = coords;
   h->d_desc = desc;

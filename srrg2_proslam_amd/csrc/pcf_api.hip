@@ -78,9 +78,10 @@ int ensure_capacity(prs_pcf* h, int nf, int nm) {
   n.d_block        = nullptr;
   n.h_block        = nullptr;
   (void) hipStreamSynchronize(h->ctx->stream);
-  PCF_TRY(hipMalloc(reinterpret_cast<void**>(&n.d_block), n.block_bytes));
-  if (hipHostMalloc(reinterpret_cast<void**>(&n.h_block), n.block_bytes, hipHostMallocDefault) != hipSuccess) {
-    (void) hipFree(n.d_block);
+  // (the block carries the handle's clouds and correspondences from call to call: guard mode paints it here and never again)
+  PCF_TRY(prs::owned_alloc(h->ctx, "pcf.d_block", &n.d_block, n.block_bytes));
+  if (prs::owned_alloc(h->ctx, "pcf.h_block", &n.h_block, n.block_bytes, PRS_GUARD_SLACK_EXACT, true) != hipSuccess) {
+    prs::owned_free(h->ctx, n.d_block);
     return fail(h, PRS_ERR_HIP, "prs_pcf: pinned staging allocation failed");
   }
   memset(n.h_block, 0, n.block_bytes);
@@ -90,8 +91,8 @@ int ensure_capacity(prs_pcf* h, int nf, int nm) {
     memcpy(n.h_block + n.off_fdesc, h->h_block + h->off_fdesc, (size_t) PRS_DESC_BYTES * (size_t) h->n_fixed);
     memcpy(n.h_block + n.off_moving, h->h_block + h->off_moving, sizeof(float) * 4 * (size_t) h->n_moving);
     memcpy(n.h_block + n.off_mdesc, h->h_block + h->off_mdesc, (size_t) PRS_DESC_BYTES * (size_t) h->n_moving);
-    (void) hipHostFree(h->h_block);
-    (void) hipFree(h->d_block);
+    prs::owned_free(h->ctx, h->h_block, true);
+    prs::owned_free(h->ctx, h->d_block);
   }
   n.fixed_dirty  = h->fixed_set;
   n.moving_dirty = h->moving_set;
@@ -228,12 +229,8 @@ int prs_pcf_destroy(prs_pcf* h) {
   }
   (void) hipSetDevice(h->ctx->device);
   (void) hipStreamSynchronize(h->ctx->stream);
-  if (h->d_block) {
-    (void) hipFree(h->d_block);
-  }
-  if (h->h_block) {
-    (void) hipHostFree(h->h_block);
-  }
+  prs::owned_free(h->ctx, h->d_block);
+  prs::owned_free(h->ctx, h->h_block, true);
   delete h;
   return PRS_OK;
 }

@@ -586,9 +586,10 @@ int place_query_launch(prs_place_db* db, const prs_place_params* p, const prs_pl
 }
 
 template <typename T>
-int grow(prs_context* ctx, T*& ptr, const size_t old_n, const size_t new_n) {
+int grow(prs_context* ctx, const char* name, T*& ptr, const size_t old_n, const size_t new_n) {
+  // (the database's arrays carry its rows from call to call: guard mode paints them here, and the zeroing below follows)
   T* p = nullptr;
-  if (hipMalloc(&p, new_n * sizeof(T) > 0 ? new_n * sizeof(T) : sizeof(T)) != hipSuccess) {
+  if (owned_alloc(ctx, name, &p, new_n * sizeof(T) > 0 ? new_n * sizeof(T) : sizeof(T)) != hipSuccess) {
     return ctx_fail(ctx, PRS_ERR_HIP, "prs_place_db: device allocation failed");
   }
   hipError_t e = hipMemsetAsync(p, 0, new_n * sizeof(T), ctx->stream);
@@ -599,12 +600,10 @@ int grow(prs_context* ctx, T*& ptr, const size_t old_n, const size_t new_n) {
     e = hipStreamSynchronize(ctx->stream);
   }
   if (e != hipSuccess) {
-    (void) hipFree(p);
+    owned_free(ctx, p);
     return ctx_fail_hip(ctx, e, "prs_place_db: growth copy");
   }
-  if (ptr) {
-    (void) hipFree(ptr);
-  }
+  owned_free(ctx, ptr);
   ptr = p;
   return PRS_OK;
 }
@@ -618,9 +617,9 @@ int db_reserve(prs_place_db* db, int64_t maps, int64_t rows) {
   (void) hipSetDevice(ctx->device);
   if (maps > db->map_cap) {
     const size_t o = (size_t) db->maps, n = (size_t) maps;
-    int rc = grow(ctx, db->map_off, o, n);
-    rc     = rc == PRS_OK ? grow(ctx, db->map_rows, o, n) : rc;
-    rc     = rc == PRS_OK ? grow(ctx, db->map_gid, o, n) : rc;
+    int rc = grow(ctx, "place_db.map_off", db->map_off, o, n);
+    rc     = rc == PRS_OK ? grow(ctx, "place_db.map_rows", db->map_rows, o, n) : rc;
+    rc     = rc == PRS_OK ? grow(ctx, "place_db.map_gid", db->map_gid, o, n) : rc;
     if (rc != PRS_OK) {
       return rc;
     }
@@ -628,10 +627,10 @@ int db_reserve(prs_place_db* db, int64_t maps, int64_t rows) {
   }
   if (rows > db->row_cap) {
     const size_t o = (size_t) db->rows, n = (size_t) rows;
-    int rc = grow(ctx, db->desc, o * PRS_DESC_BYTES, n * PRS_DESC_BYTES);
-    rc     = rc == PRS_OK ? grow(ctx, db->xyz, o * 4, n * 4) : rc;
-    rc     = rc == PRS_OK ? grow(ctx, db->row_pidx, o, n) : rc;
-    rc     = rc == PRS_OK ? grow(ctx, db->tile_map, o / 16, n / 16) : rc;
+    int rc = grow(ctx, "place_db.desc", db->desc, o * PRS_DESC_BYTES, n * PRS_DESC_BYTES);
+    rc     = rc == PRS_OK ? grow(ctx, "place_db.xyz", db->xyz, o * 4, n * 4) : rc;
+    rc     = rc == PRS_OK ? grow(ctx, "place_db.row_pidx", db->row_pidx, o, n) : rc;
+    rc     = rc == PRS_OK ? grow(ctx, "place_db.tile_map", db->tile_map, o / 16, n / 16) : rc;
     if (rc != PRS_OK) {
       return rc;
     }
@@ -922,9 +921,7 @@ int prs_place_db_destroy(prs_place_db* db) {
   (void) hipStreamSynchronize(db->ctx->stream);
   void* ptrs[] = {db->desc, db->xyz, db->row_pidx, db->tile_map, db->map_off, db->map_rows, db->map_gid};
   for (void* p : ptrs) {
-    if (p) {
-      (void) hipFree(p);
-    }
+    owned_free(db->ctx, p);
   }
   delete db;
   return PRS_OK;
@@ -1236,15 +1233,16 @@ int prs_place_bank_create(prs_context* ctx, int32_t batch, int32_t map_stride, i
   k->map_stride = map_stride;
   k->row_stride = (row_stride + 15) / 16 * 16;
   const size_t rows = (size_t) batch * (size_t) k->row_stride, maps = (size_t) batch * (size_t) map_stride;
-  bool ok = hipMalloc(&k->desc, rows * PRS_DESC_BYTES) == hipSuccess;
-  ok      = ok && hipMalloc(&k->xyz, rows * 16) == hipSuccess;
-  ok      = ok && hipMalloc(&k->row_pidx, rows * 4) == hipSuccess;
-  ok      = ok && hipMalloc(&k->tile_map, rows / 16 * 4) == hipSuccess;
-  ok      = ok && hipMalloc(&k->map_off, maps * 4) == hipSuccess;
-  ok      = ok && hipMalloc(&k->map_rows, maps * 4) == hipSuccess;
-  ok      = ok && hipMalloc(&k->map_gid, maps * 8) == hipSuccess;
-  ok      = ok && hipMalloc(&k->own_nodes, maps * 4) == hipSuccess;
-  ok      = ok && hipMalloc(&k->counters, (size_t) batch * 3 * 4) == hipSuccess;
+  // (the bank's arrays carry its rows from call to call: guard mode paints them here and never again)
+  bool ok = owned_alloc(ctx, "place_bank.desc", &k->desc, rows * PRS_DESC_BYTES) == hipSuccess;
+  ok      = ok && owned_alloc(ctx, "place_bank.xyz", &k->xyz, rows * 16) == hipSuccess;
+  ok      = ok && owned_alloc(ctx, "place_bank.row_pidx", &k->row_pidx, rows * 4) == hipSuccess;
+  ok      = ok && owned_alloc(ctx, "place_bank.tile_map", &k->tile_map, rows / 16 * 4) == hipSuccess;
+  ok      = ok && owned_alloc(ctx, "place_bank.map_off", &k->map_off, maps * 4) == hipSuccess;
+  ok      = ok && owned_alloc(ctx, "place_bank.map_rows", &k->map_rows, maps * 4) == hipSuccess;
+  ok      = ok && owned_alloc(ctx, "place_bank.map_gid", &k->map_gid, maps * 8) == hipSuccess;
+  ok      = ok && owned_alloc(ctx, "place_bank.own_nodes", &k->own_nodes, maps * 4) == hipSuccess;
+  ok      = ok && owned_alloc(ctx, "place_bank.counters", &k->counters, (size_t) batch * 3 * 4) == hipSuccess;
   k->node_of_map = k->own_nodes;
   if (!ok || prs_place_bank_clear(k) != PRS_OK) {
     (void) hipGetLastError();
@@ -1264,9 +1262,7 @@ int prs_place_bank_destroy(prs_place_bank* bank) {
   void* ptrs[] = {bank->desc, bank->xyz, bank->row_pidx, bank->tile_map, bank->map_off, bank->map_rows, bank->map_gid, bank->own_nodes,
                   bank->counters};
   for (void* p : ptrs) {
-    if (p) {
-      (void) hipFree(p);
-    }
+    owned_free(bank->ctx, p);
   }
   delete bank;
   return PRS_OK;

@@ -6,6 +6,7 @@
 
 #include <string>
 #include <type_traits>
+#include <vector>
 
 #include "../../include/proslam_hip.h"
 #include "prs_launch.h"
@@ -26,6 +27,29 @@ enum Arena {
   ARENA_STAGE_POSE_GRAPH,  // the same for prs_pose_graph_optimize, whose block also holds the graph's envelope
   ARENA_PINNED,            // host side (pinned) of all of them: an entry point synchronises before it returns
   ARENA_COUNT
+};
+
+// ---- memory the library owns.  Every device or pinned block of the library is allocated and freed through owned_alloc /
+// owned_free (api.hip), each with a short name.  guard_layout is the one rule for how large a block is and where its user bytes
+// lie: with guard off it is the size the site always asked for (the exact bytes, or the grow-only blocks' slack on top); with
+// guard on (PRS_GUARD_FILL=00 / ff at prs_context_create) the block is [front band | user bytes | tail band], the tail band
+// begins at the first byte behind `bytes` and is never smaller than the slack, so what stayed inside its block stays inside it.
+inline uint64_t guard_slack(uint64_t bytes, int rule) {
+  return rule == PRS_GUARD_SLACK_QUARTER ? bytes / 4 + 4096 : (rule == PRS_GUARD_SLACK_HALF ? bytes / 2 + 4096 : 0);
+}
+inline prs_guard_extent guard_layout(uint64_t bytes, int rule, bool guard) {
+  const uint64_t slack = guard_slack(bytes, rule);
+  if (!guard) {
+    return {bytes + slack, 0, slack};
+  }
+  const uint64_t tail = slack > PRS_GUARD_BAND ? slack : PRS_GUARD_BAND;
+  return {PRS_GUARD_BAND + bytes + tail, PRS_GUARD_BAND, tail};
+}
+struct GuardBlock {  // a live block of a context in guard mode
+  void* user;
+  size_t bytes, tail;
+  const char* name;  // a string literal of the allocating site
+  bool pinned;
 };
 
 }  // namespace prs
@@ -65,6 +89,10 @@ struct prs_context {
   bool stamps_enabled   = false;
   unsigned long long* d_stamps = nullptr;
   size_t d_stamps_size  = 0;
+  // guard mode (PRS_GUARD_FILL=00 / ff, tests): -1 = off, else the byte every owned block is painted with
+  int guard_fill        = -1;
+  std::vector<prs::GuardBlock> guard_blocks;  // live blocks, in allocation order
+  std::vector<std::string> guard_latched;     // damaged bands found when a block was freed: "name side offset"
 };
 
 namespace prs {
@@ -103,6 +131,23 @@ inline size_t align256(size_t v) {
 // grows (never shrinks) one of the context's arenas to at least `bytes`, after the stream has drained if a block has to be
 // freed; returns nullptr on failure
 void* ctx_arena(prs_context* ctx, Arena arena, size_t bytes);
+// one owned block of `bytes` user bytes (device, or pinned host memory), sized by guard_layout: *p is the user pointer, nullptr
+// when the request is 0 bytes with guard off, as hipMalloc answers it.  In guard mode the bands are painted with
+// PRS_GUARD_PATTERN and the user bytes with the context's fill before it returns.  `name` is a string literal.
+hipError_t owned_alloc(prs_context* ctx, const char* name, void** p, size_t bytes, int rule = PRS_GUARD_SLACK_EXACT, bool pinned = false);
+template <class T>
+inline hipError_t owned_alloc(prs_context* ctx, const char* name, T** p, size_t bytes, int rule = PRS_GUARD_SLACK_EXACT, bool pinned = false) {
+  void* v            = nullptr;
+  const hipError_t e = owned_alloc(ctx, name, &v, bytes, rule, pinned);
+  *p                 = static_cast<T*>(v);
+  return e;
+}
+// frees a block of owned_alloc (nullptr: nothing).  In guard mode its bands are checked first and a damaged one is latched in
+// the context; the caller has drained whatever stream still used the block, as it always had to
+void owned_free(prs_context* ctx, void* p, bool pinned = false);
+// guard mode: the first `bytes` user bytes of a reused block painted with the fill again, on `stream` in front of the launches
+// (a pinned block: on the host, after the context's stream has drained).  Nothing with guard off
+void owned_repaint(prs_context* ctx, void* p, size_t bytes, hipStream_t stream, bool pinned = false);
 
 // The staging block of a host-pointer entry point: sections in declaration order, each starting on a 256-byte boundary, with
 // the same layout in a device arena and in the pinned arena.  Declare the sections, commit(), fill the .h() side, upload()

@@ -60,7 +60,8 @@ class Context:
         if getattr(self, "_h", None):
             for child in list(self._children):  # a finder handle must never outlive its context
                 child.close()
-            _lib.load().prs_context_destroy(self._h)
+            # (guard mode: the damaged bands latched when the context went, which it has printed; else 0)
+            self.close_status = _lib.load().prs_context_destroy(self._h)
             self._h = None
 
     def __del__(self):
@@ -98,6 +99,22 @@ class Context:
         h, m = C.c_int64(0), C.c_int64(0)
         _check(self, _lib.load().prs_context_get_search_reuse(self._h, C.byref(h), C.byref(m)), "prs_context_get_search_reuse")
         return h.value, m.value
+
+    def guard_regions(self):
+        """guard mode (PRS_GUARD_FILL=00 / ff when the context was created): the library's live blocks on this context in allocation
+        order -> [dict(name, user, bytes, tail_bytes, pinned)]; ProslamHipError on a context that is not in guard mode"""
+        lib = _lib.load()
+        n = _check(self, lib.prs_context_guard_regions(self._h, None, 0), "prs_context_guard_regions")
+        out = (_lib.GuardRegion * max(n, 1))()
+        n = min(n, _check(self, lib.prs_context_guard_regions(self._h, out, n), "prs_context_guard_regions"))
+        return [dict(name=r.name.decode(), user=r.user or 0, bytes=r.bytes, tail_bytes=r.tail_bytes, pinned=bool(r.pinned)) for r in out[:n]]
+
+    def guard_check(self, report=False):
+        """guard mode: synchronises, looks at the bands of every live block and -> the number of damaged (block, side) pairs, those
+        latched from freed blocks included; report=True -> (count, ["name front|tail offset", ...])"""
+        text = C.create_string_buffer(1 << 16)
+        n = _check(self, _lib.load().prs_context_guard_check(self._h, text, len(text)), "prs_context_guard_check")
+        return (n, text.value.decode().splitlines()) if report else n
 
     def align_round_timing(self):
         """-> (search_ms[16], gn_ms[16], batches): the timed launches by round of the batch (mean per batch = value / batches)"""

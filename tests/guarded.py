@@ -15,7 +15,8 @@ as float32 / float64, -1 as int32, 65535 as uint16): a result that differs betwe
 adopt_all moves every tensor of an ops batch (shared tensors once, views rebuilt), hooked does so for every batch a stage test's own
 helpers build inside a with block, both_fills runs a case under both fills and compares the two runs.
 
-What the harness cannot see: a read past an array's end whose value reaches no result, and anything in memory the library owns.
+What the harness cannot see: a read past an array's end whose value reaches no result.  Memory the library owns is not its to
+place: the library's guard mode (PRS_GUARD_FILL, include/proslam_hip.h) does the same there, and tests/test_guard_owned_gpu.py runs it.
 """
 import contextlib
 

@@ -5,7 +5,7 @@ those build into an arena the moment they are built, at exactly the demanded ali
 side.  Each case runs with fill 0x00 and with fill 0xFF: both runs equal the reference as the stage's own test asserts it, equal
 each other byte for byte, and leave every band clean.  B = 3 and the last sequence is the full one: its counts equal the strides, so
 its last row adjoins a band.  Memory the library owns (the aligner's job buffers, a place bank's arenas, a prs_map) cannot be
-placed and is not covered."""
+placed from here: tests/test_guard_owned_gpu.py puts it between bands through the library's guard mode (PRS_GUARD_FILL)."""
 import numpy as np
 import pytest
 import torch
