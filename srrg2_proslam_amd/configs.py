@@ -254,6 +254,13 @@ DEPTH_CONSISTENCY = {"window": 2, "stride": 1, "max_rel_diff": 0.02, "min_suppor
 DEPTH_NORMALS = {"radius": 2, "smooth": 1, "max_rel_diff": 0.05, "range_min": 0.1, "range_max": 10.0}
 
 
+# TSDF fusion of the depth images (include/proslam_hip_tsdf.h prs_tsdf_params; ops.tsdf_params).  BUILD-DEFINED: the reference has
+# no dense stage.  Voxels of 2 cm and a truncation of four voxels (KinectFusion's ratio: the band has to hold the depth noise and a
+# few voxels on either side of the crossing for the normal), a weight that saturates at 64 observations so that the volume follows a
+# scene that changes, every voxel seen once is surface; the range is the dense cloud's.
+TSDF = {"voxel_size": 0.02, "truncation": 0.08, "max_weight": 64.0, "min_weight": 1.0, "range_min": 0.1, "range_max": 10.0}
+
+
 def _gate(mean_t, std_t, mean_r, std_r, where):
     return {"mean_translation": (mean_t,) * 3, "std_translation": (std_t,) * 3, "mean_rotation": (mean_r,) * 3,
             "std_rotation": (std_r,) * 3, "source": where}

@@ -9,7 +9,7 @@ import weakref
 
 import numpy as np
 
-from . import _lib, _lib_normals, configs
+from . import _lib, _lib_normals, _lib_tsdf, configs
 from ._lib import ProslamHipError, StereoBatch, StereoParams, TriangulatorParams
 
 CORR_DTYPE = np.dtype([("fixed_idx", np.int32), ("moving_idx", np.int32), ("response", np.float32)])
@@ -31,6 +31,11 @@ def _run(ctx, entry, *args):
 def _run_normals(ctx, entry, *args):
     """_run for an entry point of the second header (include/proslam_hip_normals.h, bound by _lib_normals)"""
     return _check(ctx, getattr(_lib_normals.load(), entry)(ctx._h, *args), entry)
+
+
+def _run_tsdf(ctx, entry, *args):
+    """_run for an entry point of the third header (include/proslam_hip_tsdf.h, bound by _lib_tsdf)"""
+    return _check(ctx, getattr(_lib_tsdf.load(), entry)(ctx._h, *args), entry)
 
 
 class Context:
@@ -3155,6 +3160,136 @@ class DepthNormalsBatch:
         inside = (i >= 0) & (i < self.row_stride)
         rows = torch.gather(self.row_normal, 1, i.clamp(0, self.row_stride - 1).unsqueeze(-1).expand(-1, -1, 4))
         return torch.where(inside.unsqueeze(-1), rows, torch.zeros((), dtype=rows.dtype, device=rows.device))
+
+
+# ---- TSDF fusion: depth images to a truncated signed distance volume and its surface (include/proslam_hip_tsdf.h) ----
+def tsdf_params(camera, voxel_size=configs.TSDF["voxel_size"], truncation=configs.TSDF["truncation"],
+                max_weight=configs.TSDF["max_weight"], min_weight=configs.TSDF["min_weight"], range_min=configs.TSDF["range_min"],
+                range_max=configs.TSDF["range_max"], depth_type="u16", scale=1.0, sensor_in_robot=None):
+    """prs_tsdf_params.  camera: a dictionary with fx, fy, cx, cy (configs.*["camera"]); voxel_size and truncation in metres; a
+    voxel's weight saturates at max_weight (>= 1); the surface call reads the voxels whose weight is at least min_weight;
+    range_min / range_max, depth_type, scale and sensor_in_robot as in depth_cloud_params.  Raises ValueError on every value the
+    library refuses"""
+    p = _lib_tsdf.TsdfParams()
+    p.depth_type = _depth_type(depth_type, known=True)
+    with np.errstate(over="ignore"):  # a value beyond float32 becomes inf and is refused below
+        p.voxel_size, p.truncation = float(np.float32(voxel_size)), float(np.float32(truncation))
+        p.max_weight, p.min_weight = float(np.float32(max_weight)), float(np.float32(min_weight))
+    p.depth_scaling_factor_to_meters = float(scale)
+    p.fx, p.fy, p.cx, p.cy = (float(camera[k]) for k in ("fx", "fy", "cx", "cy"))
+    p.range_min, p.range_max = float(range_min), float(range_max)
+    S = np.eye(4, dtype=np.float32) if sensor_in_robot is None else np.asarray(sensor_in_robot, np.float32).reshape(4, 4)
+    p.sensor_in_robot[:] = [float(x) for x in S.reshape(16)]
+    values = [p.depth_scaling_factor_to_meters, p.fx, p.fy, p.cx, p.cy, p.range_min, p.range_max, p.voxel_size, p.truncation,
+              p.max_weight, p.min_weight] + list(p.sensor_in_robot)
+    if not np.isfinite(values).all():
+        raise ValueError("every parameter must be finite as a float32")
+    if not p.depth_scaling_factor_to_meters > 0.0:
+        raise ValueError("scale must be positive as a float32")
+    if not 0.0 <= p.range_min <= p.range_max:
+        raise ValueError("0 <= range_min <= range_max must hold")
+    if not (p.voxel_size > 0.0 and p.truncation > 0.0):
+        raise ValueError("voxel_size and truncation must be positive as float32")
+    if not p.max_weight >= 1.0:
+        raise ValueError("max_weight must be at least 1")
+    return p
+
+
+class TsdfVolumeBatch:
+    """the TSDF volumes of B sequences, nx x ny x nz voxels each, fed with up to `frames` depth images of rows x cols pixels a call:
+    owns volume [B, nz, ny, nx, 2] (tsdf, weight), origin [B, 4] (the world position of the corner of voxel (0, 0, 0); set it before
+    the first call), n_updates [B, frames], n_skipped [B] and status [B] of the integrate call and, with out_stride, xyz and normal
+    [B, out_stride, 4], cell [B, out_stride], n_out, n_total and surface_status [B] of the surface call, and both workspaces."""
+
+    def __init__(self, batch, nx, ny, nz, frames, rows, cols, out_stride=None, device=0):
+        import torch
+        B, F = int(batch), int(frames)
+        if B < 1 or F < 1 or int(rows) < 1 or int(cols) < 1 or int(nx) < 1 or int(ny) < 1 or int(nz) < 1 or \
+                (out_stride is not None and int(out_stride) < 1):
+            raise ValueError("batch, nx, ny, nz, frames, rows, cols and out_stride must be at least 1")
+        if int(nx) * int(ny) * int(nz) > 0x7fffffff // 3:
+            raise ValueError("nx * ny * nz must stay within (2^31 - 1) / 3")
+        lib = _lib_tsdf.load()
+        self.batch, self.frames, self.rows, self.cols = B, F, int(rows), int(cols)
+        self.nx, self.ny, self.nz = int(nx), int(ny), int(nz)
+        self.out_stride = None if out_stride is None else int(out_stride)
+        z = _zeros_on(device)
+        self.volume = z((B, self.nz, self.ny, self.nx, 2), torch.float32)
+        self.origin = z((B, 4), torch.float32)
+        self.n_updates, self.n_skipped, self.status = z((B, F), torch.int32), z((B,), torch.int32), z((B,), torch.int32)
+        nbytes = int(lib.prs_tsdf_workspace_bytes(B, F))
+        if nbytes < 1:
+            raise ValueError("batch * frames must stay below 2^31")
+        self.workspace = z((nbytes,), torch.uint8)
+        n = self.out_stride
+        self.xyz = z((B, n, 4), torch.float32) if n else None
+        self.normal = z((B, n, 4), torch.float32) if n else None
+        self.cell = z((B, n), torch.int32) if n else None
+        self.n_out, self.n_total, self.surface_status = z((B,), torch.int32), z((B,), torch.int32), z((B,), torch.int32)
+        self.surface_workspace = z((int(lib.prs_tsdf_surface_workspace_bytes(B, self.nx, self.ny, self.nz)),), torch.uint8)
+
+    def clear(self):
+        """every voxel back to never observed: a memset on torch's current stream (asynchronous)"""
+        self.volume.zero_()
+
+    def descriptor(self, params, depth, pose, n_images=None, frame_index=None):
+        """the prs_tsdf_batch of device tensors: depth [B, frames, rows, cols (a view of longer rows is allowed: the pitch)] of
+        params' depth type, pose [B, pose_stride, 16] float32, n_images [B] int32 or None = frames, frame_index [B, frames] int32 or
+        None"""
+        import torch
+        B, F = self.batch, self.frames
+        dtype = torch.uint16 if params.depth_type == DEPTH_U16 else torch.float32
+        if depth.dtype != dtype or depth.dim() != 4 or tuple(depth.shape[:3]) != (B, F, self.rows) or int(depth.shape[3]) < self.cols or \
+                depth.stride(3) != 1:
+            raise ValueError("depth must be a %s tensor [%d, %d, %d, >= %d] with contiguous rows" % (dtype, B, F, self.rows, self.cols))
+        if not _follow(depth, self.rows, strict=True):
+            raise ValueError("the images of depth must follow one another at rows * pitch")
+        if pose.dim() != 3 or int(pose.shape[0]) != B or int(pose.shape[2]) != 16 or pose.dtype != torch.float32 or not pose.is_contiguous():
+            raise ValueError("pose must be a contiguous float32 [%d, pose_stride, 16]" % B)
+        d = _lib_tsdf.TsdfBatch()
+        d.batch, d.frames, d.rows, d.cols = B, F, self.rows, self.cols
+        d.pitch, d.pose_stride = int(depth.stride(2)) * depth.element_size(), int(pose.shape[1])
+        d.nx, d.ny, d.nz = self.nx, self.ny, self.nz
+        d.depth, d.pose = depth.data_ptr(), pose.data_ptr()
+        d.n_images = _n_images_ptr(n_images, B)
+        d.frame_index = _int32_ptr(frame_index, "frame_index", (B, F))
+        for name in ("origin", "volume", "n_updates", "n_skipped", "status", "workspace"):
+            setattr(d, name, getattr(self, name).data_ptr())
+        return d
+
+    def surface_descriptor(self, count_only=False):
+        """the prs_tsdf_surface_batch of this batch's tensors"""
+        if self.out_stride is None and not count_only:
+            raise ValueError("this batch was built without out_stride: it has no rows for a surface")
+        d = _lib_tsdf.TsdfSurfaceBatch()
+        d.batch, d.nx, d.ny, d.nz, d.out_stride = self.batch, self.nx, self.ny, self.nz, self.out_stride or 0
+        d.origin, d.volume = self.origin.data_ptr(), self.volume.data_ptr()
+        d.n_out, d.n_total, d.status = self.n_out.data_ptr(), self.n_total.data_ptr(), self.surface_status.data_ptr()
+        d.workspace = self.surface_workspace.data_ptr()
+        if not count_only:
+            d.xyz, d.normal, d.cell = self.xyz.data_ptr(), self.normal.data_ptr(), self.cell.data_ptr()
+        return d
+
+    def integrate(self, ctx, params, depth, pose, n_images=None, frame_index=None):
+        """enqueue the fusion of every sequence's images into its volume (asynchronous) and return volume; per-sequence status lands
+        in self.status.  Calls add up: a long sequence is fed `frames` images at a time"""
+        d = self.descriptor(params, depth, pose, n_images, frame_index)
+        _run_tsdf(ctx, "prs_tsdf_integrate_batch_run", C.byref(params), C.byref(d))
+        return self.volume
+
+    def surface(self, ctx, params):
+        """enqueue the surface of every volume (asynchronous) -> (xyz, normal, n_out): the first n_out[b] rows of xyz[b] and
+        normal[b] are the zero crossings and their normals, which formats.write_ply(path, xyz[b, :n], normals=normal[b, :n]) takes as
+        they are; PRS_ERR_CAPACITY lands in self.surface_status[b] when out_stride rows did not hold them all (n_total[b])"""
+        d = self.surface_descriptor()
+        _run_tsdf(ctx, "prs_tsdf_surface_batch_run", C.byref(params), C.byref(d))
+        return self.xyz, self.normal, self.n_out
+
+    def count(self, ctx, params):
+        """enqueue the count-only surface call (asynchronous): n_total and surface_status; n_out becomes 0"""
+        d = self.surface_descriptor(count_only=True)
+        _run_tsdf(ctx, "prs_tsdf_surface_batch_run", C.byref(params), C.byref(d))
+        return self.n_total
 
 
 # ---- image rectifier: undistort and stereo-rectify raw frames in front of the extractors (include/proslam_hip.h prs_rectify_*) ----
