@@ -9,11 +9,13 @@ for each of B independent sequences (per GPU) one tracked frame =
 All inputs are resident in HBM before the timed region.  Sequences are independent, so ranks
 shard them with no data-path collective (weak scaling: per-GPU work is fixed).
 
-    python bench.py --gpus 1 --steps 10 --warmup 2
+    python bench.py --gpus 1 --steps 10 --warmup 2   (the headline alone: set up, warm up, time the steps, print the line)
+    python bench.py --gpus 1 --steps 10 --warmup 2 --full   (+ everything listed below, after the timed steps)
     python bench.py --gpus N ...                     (no launcher: starts N ranks itself, one per device, RCCL rendezvous on 127.0.0.1)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
-Rank 0 prints ONE JSON line (contract in the task statement).  Besides the contract's fields:
+Rank 0 prints ONE JSON line (contract in the task statement): the contract's fields and `config`, what the timed steps themselves
+produced (counts per frame, executed iterations, success fraction; a per-frame error of the kernels is loud).  With `--full` also:
   roofline          the time-dominant kernel of the step (a copy of one of the three below)
   roofline_search / roofline_gn / roofline_matcher
                     projective search kernel and stereo matcher kernel (the one BASELINE.json's north star prices): achieved
@@ -71,8 +73,8 @@ def parse():
     ap.add_argument("--batch", type=int, default=55296,
                     help="independent sequences (frames per step) per GPU; 55296 = 216 per CU, a multiple of the 1 / 3 / 8 workgroups per CU the "
                          "matcher / search / GN kernels keep resident (no partial last wave); ~28 GB of the 288 GB.  Rounds 1-3 used 18432: the "
-                         "fifth search / GN round of a step (the ~15 % of the frames whose finder latches one projection later) is a latency-bound "
-                         "0.6 ms whatever the batch, so a three times larger batch is 4.6 % faster per frame (1.194 -> 1.250 M frames/s)")
+                         "fifth search / GN round of a step (the ~15 %% of the frames whose finder latches one projection later) is a latency-bound "
+                         "0.6 ms whatever the batch, so a three times larger batch is 4.6 %% faster per frame (1.194 -> 1.250 M frames/s)")
     ap.add_argument("--keypoints", type=int, default=2000, help="keypoints per image (KITTI config: ~2000)")
     ap.add_argument("--moving", type=int, default=2000, help="local-map points per frame")
     ap.add_argument("--max-fixed", type=int, default=896, help="LDS sizing bound on stereo matches per frame")
@@ -81,11 +83,14 @@ def parse():
                          "workgroup b runs on XCD b mod 8 and with eight resident frames per CU, so a count that shares a factor with 8 or 256 "
                          "pins every unique frame to one XCD / CU slot (measured in round 4 with 8 unique frames: the frames that need a fifth "
                          "search round all sat on three XCDs, the other five idled, the GN time of the leg doubled)")
-    ap.add_argument("--cpu-frames", type=int, default=1024, help="frames of the CPU-baseline sample (0 = skip)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-steady-state", action="store_true", help="skip the steady-state leg (profiles of the headline workload alone)")
-    ap.add_argument("--no-other-configs", action="store_true", help="skip the EuRoC / TUM / KITTI-1000 legs and the closed loop")
-    ap.add_argument("--timing-steps", type=int, default=4, help="steps of the untimed per-kernel timing pass")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline also run everything else this file measures or checks: per-kernel times and rooflines, the steady-state "
+                         "leg, CPU baselines and parity, every side leg (see the module docstring).  Off: set up, warm up, time the steps, print the line")
+    ap.add_argument("--cpu-frames", type=int, default=1024, help="--full: frames of the CPU-baseline sample (0 = skip)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baselines and the legs that check against the CPU checker")
+    ap.add_argument("--no-steady-state", action="store_true", help="--full without the steady-state leg")
+    ap.add_argument("--no-other-configs", action="store_true", help="--full without the EuRoC / TUM / KITTI-1000 legs, the side legs and the closed loop")
+    ap.add_argument("--timing-steps", type=int, default=4, help="--full: steps of the untimed per-kernel timing pass")
     ap.add_argument("--mode", choices=["frame", "closed-loop"], default="frame",
                     help="frame: the section-8(a) hot path on B independent frames per step (the headline); closed-loop: the "
                          "stateful per-frame loop incl. clipper and merger along the KITTI-00 trajectory (tools/bench_tracking.py)")
@@ -1247,6 +1252,16 @@ SIDE_LEGS = ("latency_b1", "roofline_f1", "roofline_f2", "roofline_f3", "rooflin
 LEG_SUMMARY_KEYS = ("value", "unit", "ms_per_step", "ms_per_launch", "ms_per_frame_median", "achieved", "frac", "error")
 
 
+def extras(args, rank, world):
+    """what a frame-mode run does after its timed steps, besides reading their results back: nothing without --full.  The
+    per-kernel timing pass runs on every rank; the legs need the whole device and the host's cores, so rank 0 of a 1-GPU run"""
+    alone = args.full and rank == 0 and world == 1
+    return {"kernel_times": args.full,  # + the roofline objects, which price its times
+            "steady_state": alone and not args.no_steady_state,
+            "cpu_baseline": alone and not args.no_cpu_baseline and args.cpu_frames > 0,  # + parity_on_bench_inputs, all cores, latency_b1
+            "other_configs": alone and not args.no_other_configs}  # + f rows, a13_alt, tolerance_exit, small_batch, streamed, closed_loop
+
+
 def leg_summary(leg):
     """the headline numbers of a side leg for the result line: LEG_SUMMARY_KEYS and parity records, nested records likewise"""
     if not isinstance(leg, dict):
@@ -1331,84 +1346,10 @@ def dry_run(args):
     sharding.shutdown()
 
 
-def main():
-    args = parse()
-    if args.cpu_worker > 0:
-        cpu_worker(args)
-        return
-    if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
-        spawn_ranks(args)
-        return
-    if args.dry_run:
-        dry_run(args)
-        return
-    if args.mode == "closed-loop":
-        closed_loop(args)
-        return
-    import torch
-
-    from srrg2_proslam_amd import sharding
-    rank, world, local_rank = sharding.rank_world()
-    # test hook for 1-GPU boxes: all ranks share device 0 and the rendezvous runs on gloo, so that the
-    # multi-rank control flow (barriers, MAX over ranks, rank-0 reporting) can be exercised without 8 GPUs
-    shared = os.environ.get("PRS_BENCH_SHARE_GPU", "0") == "1"
-    if shared:
-        local_rank = 0
-    if world != args.gpus and world > 1:
-        raise SystemExit("WORLD_SIZE (%d) != --gpus (%d)" % (world, args.gpus))
-    torch.cuda.set_device(local_rank)
-    sharding.init_distributed("gloo" if shared else "nccl", local_rank)
-    red_dev = "cpu" if shared else torch.device("cuda", local_rank)
-
-    from srrg2_proslam_amd import configs, synthetic as syn
-
-    cfg = configs.get("kitti")
+def rooflines(args, world, snap, kt, it_exec, elapsed):
+    """--full: the roofline objects of the result line: the per-kernel times `kt` of the untimed pass and the whole step's time
+    `elapsed` / steps against the algorithmic bytes / flops of what the timed steps produced (`snap`, `it_exec`)"""
     B, N, NM = args.batch, args.keypoints, args.moving
-    # synthetic KITTI-00-shaped inputs: distinct seeds per rank (independent sequences)
-    w = FrameWorkload(cfg, local_rank, B, N, NM, args.max_fixed, args.unique, syn.seed_for(1, 0) + 100000 * rank, args.all_iterations)
-    stream = torch.cuda.Stream(device=w.dev)
-
-    def barrier():
-        torch.cuda.synchronize()
-        sharding.barrier()
-
-    with torch.cuda.stream(stream):
-        w.ctx.use_torch_stream()
-        for _ in range(args.warmup):
-            w.step()
-        barrier()
-        t0 = time.perf_counter()
-        for _ in range(args.steps):
-            w.step()
-        barrier()
-        elapsed_local = time.perf_counter() - t0
-        fps, elapsed = sharding.aggregate_throughput(B * args.steps, elapsed_local, red_dev)
-        fps_per_rank = sharding.gather_over_ranks(B * args.steps / elapsed_local, red_dev)
-        snap = w.snapshot()  # results of the timed configuration
-        status_ok, it_exec = w.check(snap)
-        dumped = w.dump_outputs(args.dump_outputs) if rank == 0 and args.dump_outputs else None  # before any further step
-        kt = w.kernel_times(max(args.timing_steps, 1))  # per-kernel times: a separate pass, outside the timed region
-        # ---- steady state: the same frames again with the finders carried over (radius / threshold schedule adapted) ----
-        steady = None
-        if rank == 0 and world == 1 and not args.no_steady_state:
-            for _ in range(6):  # radius 50 -> 10 px in steps of 10, threshold 25 -> 50
-                w.step(fresh_finders=False)
-            torch.cuda.synchronize()
-            n_st = max(args.steps // 2, 1)
-            t1 = time.perf_counter()
-            for _ in range(n_st):
-                w.step(fresh_finders=False)
-            torch.cuda.synchronize()
-            dt = time.perf_counter() - t1
-            st = w.aframes.state_of(0)
-            skt = w.kernel_times(2, fresh_finders=False)
-            steady = {"value": B * n_st / dt, "unit": "frames/s", "ms_per_step": dt / n_st * 1e3,
-                      "search_radius_pixels": int(st.search_radius_pixels), "descriptor_distance": float(st.descriptor_distance),
-                      "aligner_correspondences_per_frame": w.aframes.n_corr.float().mean().item(),
-                      "ms_per_kernel": {"stereo_match5_kernel": skt["matcher_ms"], "align_kernel (search)": skt["search_ms"], "gn_kernel": skt["gn_ms"]},
-                      "note": "finder objects live across steps like the reference's (correspondence_finder_projective_base_impl.cpp:277-287): "
-                              "after six tracked frames the search radius has shrunk to its minimum and the descriptor threshold has grown"}
-
     # ---- algorithmic bytes / flops per kernel -----------------------------------------------------------------
     n_match, n_fixed, n_corr = snap["n_match"], snap["n_fixed"], snap["n_corr"]
     ms_match, ms_search, ms_gn = kt["matcher_ms"], kt["search_ms"], kt["gn_ms"]
@@ -1480,6 +1421,101 @@ def main():
                     "cycles are its own barriers and single-wave scans (56 % of the wave cycles parked, profiles/r04/matcher_pmc.txt)"}
     dominant = max((ms_search, "search", roof_search), (ms_gn, "gn", roof_gn), (ms_match, "matcher", roof_match))
     total_k = ms_match + ms_search + ms_gn
+    return {
+        "roofline": dict(dominant[2], dominant_of="the three kernels of the step (%s)" % dominant[1]),
+        "roofline_search": roof_search,
+        "roofline_gn": roof_gn,
+        "roofline_matcher": roof_match,
+        # SURVEY 8(d) single-pass definition of a tracked frame (inputs read once, outputs written once, everything else on chip):
+        # 40 (N_L + N_R) + 29 M + 48 N_m + 64 + 12 N_c + 64 bytes, against the whole step's time
+        "roofline_whole_step": (lambda bytes_frame: {
+            "bound": "hbm", "achieved": B * world * bytes_frame / (elapsed / args.steps) / 1e9, "peak": HBM_PEAK_GBPS * world, "unit": "GB/s",
+            "frac": B * bytes_frame / (elapsed / args.steps) / 1e9 / HBM_PEAK_GBPS, "algorithmic_bytes_per_frame": bytes_frame,
+            "note": "the step is bound by vector issue (GN, search) and by the serial 100-iteration chain, not by HBM: this is the figure SURVEY 8(d) "
+                    "prices the whole frame with"})(40.0 * (2 * N) + 29.0 * n_match + 48.0 * NM + 64 + 12.0 * n_corr + 64),
+        "kernel_time_share": {"stereo_match5_kernel": ms_match / total_k, "align_kernel (search)": ms_search / total_k, "gn_kernel": ms_gn / total_k},
+        "kernel_timing": "HIP events on the launch stream in a separate pass of %d steps after the timed loop (the timed loop carries no events)" % max(args.timing_steps, 1),
+    }
+
+
+def main():
+    args = parse()
+    if args.cpu_worker > 0:
+        cpu_worker(args)
+        return
+    if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
+        spawn_ranks(args)
+        return
+    if args.dry_run:
+        dry_run(args)
+        return
+    if args.mode == "closed-loop":
+        closed_loop(args)
+        return
+    import torch
+
+    from srrg2_proslam_amd import sharding
+    rank, world, local_rank = sharding.rank_world()
+    # test hook for 1-GPU boxes: all ranks share device 0 and the rendezvous runs on gloo, so that the
+    # multi-rank control flow (barriers, MAX over ranks, rank-0 reporting) can be exercised without 8 GPUs
+    shared = os.environ.get("PRS_BENCH_SHARE_GPU", "0") == "1"
+    if shared:
+        local_rank = 0
+    if world != args.gpus and world > 1:
+        raise SystemExit("WORLD_SIZE (%d) != --gpus (%d)" % (world, args.gpus))
+    torch.cuda.set_device(local_rank)
+    sharding.init_distributed("gloo" if shared else "nccl", local_rank)
+    red_dev = "cpu" if shared else torch.device("cuda", local_rank)
+    todo = extras(args, rank, world)
+
+    from srrg2_proslam_amd import configs, synthetic as syn
+
+    cfg = configs.get("kitti")
+    B, N, NM = args.batch, args.keypoints, args.moving
+    # synthetic KITTI-00-shaped inputs: distinct seeds per rank (independent sequences)
+    w = FrameWorkload(cfg, local_rank, B, N, NM, args.max_fixed, args.unique, syn.seed_for(1, 0) + 100000 * rank, args.all_iterations)
+    stream = torch.cuda.Stream(device=w.dev)
+
+    def barrier():
+        torch.cuda.synchronize()
+        sharding.barrier()
+
+    with torch.cuda.stream(stream):
+        w.ctx.use_torch_stream()
+        for _ in range(args.warmup):
+            w.step()
+        barrier()
+        t0 = time.perf_counter()
+        for _ in range(args.steps):
+            w.step()
+        barrier()
+        elapsed_local = time.perf_counter() - t0
+        fps, elapsed = sharding.aggregate_throughput(B * args.steps, elapsed_local, red_dev)
+        fps_per_rank = sharding.gather_over_ranks(B * args.steps / elapsed_local, red_dev)
+        snap = w.snapshot()  # results of the timed configuration
+        status_ok, it_exec = w.check(snap)
+        dumped = w.dump_outputs(args.dump_outputs) if rank == 0 and args.dump_outputs else None  # before any further step
+        kt = w.kernel_times(max(args.timing_steps, 1)) if todo["kernel_times"] else None  # a separate pass, outside the timed region
+        # ---- steady state: the same frames again with the finders carried over (radius / threshold schedule adapted) ----
+        steady = None
+        if todo["steady_state"]:
+            for _ in range(6):  # radius 50 -> 10 px in steps of 10, threshold 25 -> 50
+                w.step(fresh_finders=False)
+            torch.cuda.synchronize()
+            n_st = max(args.steps // 2, 1)
+            t1 = time.perf_counter()
+            for _ in range(n_st):
+                w.step(fresh_finders=False)
+            torch.cuda.synchronize()
+            dt = time.perf_counter() - t1
+            st = w.aframes.state_of(0)
+            skt = w.kernel_times(2, fresh_finders=False)
+            steady = {"value": B * n_st / dt, "unit": "frames/s", "ms_per_step": dt / n_st * 1e3,
+                      "search_radius_pixels": int(st.search_radius_pixels), "descriptor_distance": float(st.descriptor_distance),
+                      "aligner_correspondences_per_frame": w.aframes.n_corr.float().mean().item(),
+                      "ms_per_kernel": {"stereo_match5_kernel": skt["matcher_ms"], "align_kernel (search)": skt["search_ms"], "gn_kernel": skt["gn_ms"]},
+                      "note": "finder objects live across steps like the reference's (correspondence_finder_projective_base_impl.cpp:277-287): "
+                              "after six tracked frames the search radius has shrunk to its minimum and the descriptor threshold has grown"}
 
     out = {
         "metric": "tracked frames/sec on KITTI-00 stereo (1241x376, ~2k kp); SE(3) vs ref",
@@ -1501,26 +1537,15 @@ def main():
             "frames_per_step_per_gpu": B,
             "keypoints_per_image": N,
             "local_map_points": NM,
-            "stereo_matches_per_frame": n_match,
-            "aligner_correspondences_per_frame": n_corr,
+            "stereo_matches_per_frame": snap["n_match"],
+            "aligner_correspondences_per_frame": snap["n_corr"],
             "parallelism": "independent sequences sharded one set per GPU, no collectives",
             "gn_iterations_executed_mean": it_exec,
             "aligner_success_fraction": status_ok,
         },
-        "roofline": dict(dominant[2], dominant_of="the three kernels of the step (%s)" % dominant[1]),
-        "roofline_search": roof_search,
-        "roofline_gn": roof_gn,
-        "roofline_matcher": roof_match,
-        # SURVEY 8(d) single-pass definition of a tracked frame (inputs read once, outputs written once, everything else on chip):
-        # 40 (N_L + N_R) + 29 M + 48 N_m + 64 + 12 N_c + 64 bytes, against the whole step's time
-        "roofline_whole_step": (lambda bytes_frame: {
-            "bound": "hbm", "achieved": B * world * bytes_frame / (elapsed / args.steps) / 1e9, "peak": HBM_PEAK_GBPS * world, "unit": "GB/s",
-            "frac": B * bytes_frame / (elapsed / args.steps) / 1e9 / HBM_PEAK_GBPS, "algorithmic_bytes_per_frame": bytes_frame,
-            "note": "the step is bound by vector issue (GN, search) and by the serial 100-iteration chain, not by HBM: this is the figure SURVEY 8(d) "
-                    "prices the whole frame with"})(40.0 * (2 * N) + 29.0 * n_match + 48.0 * NM + 64 + 12.0 * n_corr + 64),
-        "kernel_time_share": {"stereo_match5_kernel": ms_match / total_k, "align_kernel (search)": ms_search / total_k, "gn_kernel": ms_gn / total_k},
-        "kernel_timing": "HIP events on the launch stream in a separate pass of %d steps after the timed loop (the timed loop carries no events)" % max(args.timing_steps, 1),
     }
+    if todo["kernel_times"]:
+        out.update(rooflines(args, world, snap, kt, it_exec, elapsed))
     if world > 1:
         out["ranks"] = {"backend": "gloo (PRS_BENCH_SHARE_GPU=1: all ranks on device 0)" if shared else "nccl (RCCL)",
                         "backend_world_size": sharding.backend_world_size(), "fps_per_rank": fps_per_rank,
@@ -1530,7 +1555,7 @@ def main():
     if dumped is not None:
         out["dump_outputs"] = {"dir": args.dump_outputs, "bytes": dumped}
 
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and args.cpu_frames > 0:
+    if todo["cpu_baseline"]:
         cpu_fps, cpu_s, poses = cpu_baseline(cfg, w.uniq, args.cpu_frames)
         out["cpu_baseline"] = {
             "value": cpu_fps,
@@ -1563,7 +1588,7 @@ def main():
         out["latency_b1"] = latency_b1(cfg, uniq_frames)
 
     # ---- the other BASELINE configurations and the stateful loop, outside the headline timing (rank 0, single GPU) ----
-    if rank == 0 and world == 1 and not args.no_other_configs:
+    if todo["other_configs"]:
         small = min(B, 6144)  # 24 frames per CU: whole resident sets of the GN kernel (8 frames per CU) and of the search kernel (3)
         others = {}
         for name, cname, kp, mv, mf, cidx in (("euroc", "euroc", 1000, 1000, 512, 2), ("tum", "tum", 1000, 1000, 1024, 3), ("kitti_n1000", "kitti", 1000, 1000, 512, 1)):

@@ -33,6 +33,60 @@ def test_steps_below_one_are_refused():
     assert run.returncode == 2 and "--steps" in run.stderr
 
 
+def test_help_prints_and_names_full():
+    run = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--help"], capture_output=True, text=True, timeout=120)
+    assert run.returncode == 0 and "--full" in run.stdout, run.stderr[-2000:]
+
+
+def _parse(monkeypatch, *argv):
+    import bench
+    monkeypatch.setattr(sys, "argv", ["bench.py"] + list(argv))
+    return bench.parse()
+
+
+def test_a_plain_run_does_nothing_besides_its_headline(monkeypatch):
+    """without --full nothing follows the timed steps, on any rank; the flags that narrow --full do not switch anything on"""
+    import bench
+    for argv in ([], ["--gpus", "1", "--steps", "10", "--warmup", "2"], ["--no-cpu-baseline"], ["--timing-steps", "8", "--cpu-frames", "64"]):
+        args = _parse(monkeypatch, *argv)
+        assert args.full is False
+        for rank, world in ((0, 1), (0, 2), (1, 2)):
+            assert not any(bench.extras(args, rank, world).values()), (argv, rank, world)
+
+
+def test_full_runs_everything_and_its_flags_narrow_it(monkeypatch):
+    import bench
+    everything = {"kernel_times", "steady_state", "cpu_baseline", "other_configs"}
+    on = lambda *argv, rank=0, world=1: {k for k, v in bench.extras(_parse(monkeypatch, "--full", *argv), rank, world).items() if v}  # noqa: E731
+    assert on() == on("--gpus", "1", "--steps", "10", "--warmup", "2") == everything
+    assert on("--no-steady-state") == everything - {"steady_state"}
+    assert on("--no-cpu-baseline") == on("--cpu-frames", "0") == everything - {"cpu_baseline"}
+    assert on("--no-other-configs") == everything - {"other_configs"}
+    # the legs take the whole device and the host's cores: rank 0 of a 1-GPU run; the per-kernel pass runs on every rank
+    assert on(rank=0, world=2) == on(rank=1, world=2) == {"kernel_times"}
+
+
+@pytest.mark.gpu
+def test_a_plain_run_prints_the_headline_alone(tmp_path):
+    """bench.py end to end without --full at a small shape: the line holds the contract's fields and what the timed steps produced,
+    none of the objects that take runs of their own; --dump-outputs still writes the last timed step"""
+    import bench
+    run = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--batch", "512",
+                          "--keypoints", "1000", "--moving", "1000", "--max-fixed", "512", "--unique", "13", "--dump-outputs", str(tmp_path / "out")],
+                         capture_output=True, text=True, timeout=300)
+    assert run.returncode == 0, run.stderr[-2000:]
+    lines = [l for l in run.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1
+    line = json.loads(lines[0])
+    assert set(line) == {"metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype",
+                         "data", "config", "dump_outputs"}
+    assert not set(line) & set(bench.SIDE_LEGS)
+    assert line["unit"] == "frames/s" and line["higher_is_better"] is True and line["n_gpus"] == 1 and line["steps"] == 2 and line["warmup"] == 1
+    assert line["value"] > 0 and abs(line["value"] - 512 / (line["ms_per_step"] * 1e-3)) <= 1e-6 * line["value"]
+    assert line["config"]["frames_per_step_per_gpu"] == 512 and line["dump_outputs"]["bytes"] > 0
+    assert np.load(tmp_path / "out" / "pose.npy").shape == (512, 4, 4)
+
+
 @pytest.mark.gpu
 def test_dump_outputs_holds_what_the_last_step_computed(tmp_path):
     import torch
