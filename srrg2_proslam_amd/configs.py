@@ -260,6 +260,11 @@ DEPTH_NORMALS = {"radius": 2, "smooth": 1, "max_rel_diff": 0.05, "range_min": 0.
 # scene that changes, every voxel seen once is surface; the range is the dense cloud's.
 TSDF = {"voxel_size": 0.02, "truncation": 0.08, "max_weight": 64.0, "min_weight": 1.0, "range_min": 0.1, "range_max": 10.0}
 
+# TSDF raycast of the fused volume (include/proslam_hip_tsdf_raycast.h prs_tsdf_raycast_params; ops.tsdf_raycast_params).
+# BUILD-DEFINED.  A step of one default voxel, a quarter of the default truncation: a ray cannot cross the band between two samples;
+# the weight threshold and the range are the fusion's.
+TSDF_RAYCAST = {"step": 0.02, "min_weight": 1.0, "range_min": 0.1, "range_max": 10.0}
+
 
 def _gate(mean_t, std_t, mean_r, std_r, where):
     return {"mean_translation": (mean_t,) * 3, "std_translation": (std_t,) * 3, "mean_rotation": (mean_r,) * 3,

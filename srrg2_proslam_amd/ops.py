@@ -9,7 +9,7 @@ import weakref
 
 import numpy as np
 
-from . import _lib, _lib_normals, _lib_tsdf, configs
+from . import _lib, _lib_normals, _lib_tsdf, _lib_tsdf_raycast, configs
 from ._lib import ProslamHipError, StereoBatch, StereoParams, TriangulatorParams
 
 CORR_DTYPE = np.dtype([("fixed_idx", np.int32), ("moving_idx", np.int32), ("response", np.float32)])
@@ -36,6 +36,11 @@ def _run_normals(ctx, entry, *args):
 def _run_tsdf(ctx, entry, *args):
     """_run for an entry point of the third header (include/proslam_hip_tsdf.h, bound by _lib_tsdf)"""
     return _check(ctx, getattr(_lib_tsdf.load(), entry)(ctx._h, *args), entry)
+
+
+def _run_tsdf_raycast(ctx, entry, *args):
+    """_run for an entry point of the fourth header (include/proslam_hip_tsdf_raycast.h, bound by _lib_tsdf_raycast)"""
+    return _check(ctx, getattr(_lib_tsdf_raycast.load(), entry)(ctx._h, *args), entry)
 
 
 class Context:
@@ -3290,6 +3295,93 @@ class TsdfVolumeBatch:
         d = self.surface_descriptor(count_only=True)
         _run_tsdf(ctx, "prs_tsdf_surface_batch_run", C.byref(params), C.byref(d))
         return self.n_total
+
+
+# ---- TSDF raycast: a fused volume rendered into depth and normal images (include/proslam_hip_tsdf_raycast.h) ----
+TSDF_RAYCAST_MAX_STEPS = 1048576.0                   # steps the diagonal of a volume may hold
+
+
+def tsdf_raycast_params(camera, voxel_size=configs.TSDF["voxel_size"], step=configs.TSDF_RAYCAST["step"],
+                        min_weight=configs.TSDF_RAYCAST["min_weight"], range_min=configs.TSDF_RAYCAST["range_min"],
+                        range_max=configs.TSDF_RAYCAST["range_max"], sensor_in_robot=None):
+    """prs_tsdf_raycast_params.  camera: a dictionary with fx, fy, cx, cy of the rendered images; voxel_size: the volume's, in
+    metres; step: metres of z depth between two samples of a ray; a voxel whose weight is below min_weight counts as unobserved;
+    range_min / range_max bound the z depth of a ray's samples and of its hit; sensor_in_robot as in tsdf_params.  Raises ValueError
+    on every value the library refuses whatever the volume is"""
+    p = _lib_tsdf_raycast.TsdfRaycastParams()
+    with np.errstate(over="ignore"):  # a value beyond float32 becomes inf and is refused below
+        p.voxel_size, p.step, p.min_weight = float(np.float32(voxel_size)), float(np.float32(step)), float(np.float32(min_weight))
+        p.range_min, p.range_max = float(np.float32(range_min)), float(np.float32(range_max))
+    p.fx, p.fy, p.cx, p.cy = (float(camera[k]) for k in ("fx", "fy", "cx", "cy"))
+    S = np.eye(4, dtype=np.float32) if sensor_in_robot is None else np.asarray(sensor_in_robot, np.float32).reshape(4, 4)
+    p.sensor_in_robot[:] = [float(x) for x in S.reshape(16)]
+    values = [p.fx, p.fy, p.cx, p.cy, p.range_min, p.range_max, p.voxel_size, p.step, p.min_weight] + list(p.sensor_in_robot)
+    if not np.isfinite(values).all():
+        raise ValueError("every parameter must be finite as a float32")
+    if not 0.0 <= p.range_min <= p.range_max:
+        raise ValueError("0 <= range_min <= range_max must hold")
+    if not (p.voxel_size > 0.0 and p.step > 0.0):
+        raise ValueError("voxel_size and step must be positive as float32")
+    return p
+
+
+class TsdfRaycastBatch:
+    """the images rendered out of the volumes of an ops.TsdfVolumeBatch, `views` images of rows x cols pixels per sequence: owns
+    depth [B, views, rows, cols] float32 metres (0 = no surface), normal [B, views, rows, cols, 4] (the model's normal in the
+    camera's frame and 1, or zeros), n_hit [B, views], n_skipped [B], status [B] and the workspace; reads volumes.volume and
+    volumes.origin in place.  depth is a float32 depth image at scale 1: DepthCloudBatch, DepthNormalsBatch and
+    TsdfVolumeBatch.integrate take it as it stands with params of depth_type "f32" and scale 1."""
+
+    def __init__(self, ctx, volumes, views, rows, cols):
+        import torch
+        V = int(views)
+        if V < 1 or int(rows) < 1 or int(cols) < 1:
+            raise ValueError("views, rows and cols must be at least 1")
+        if int(rows) * int(cols) > 0x7fffffff:
+            raise ValueError("rows * cols must stay below 2^31")
+        lib = _lib_tsdf_raycast.load()
+        self.ctx, self.volumes = ctx, volumes
+        B = self.batch = volumes.batch
+        self.views, self.rows, self.cols = V, int(rows), int(cols)
+        nbytes = int(lib.prs_tsdf_raycast_workspace_bytes(B, V))
+        if nbytes < 1:
+            raise ValueError("batch * views must stay below 2^31")
+        z = _zeros_on(volumes.volume.device)
+        self.depth = z((B, V, self.rows, self.cols), torch.float32)
+        self.normal = z((B, V, self.rows, self.cols, 4), torch.float32)
+        self.n_hit, self.n_skipped, self.status = z((B, V), torch.int32), z((B,), torch.int32), z((B,), torch.int32)
+        self.workspace = z((nbytes,), torch.uint8)
+
+    def descriptor(self, pose, view_index=None, n_views=None):
+        """the prs_tsdf_raycast_batch of device tensors: pose [B, pose_stride, 16] float32, view_index [B, views] int32 or None (view
+        r takes pose r), n_views [B] int32 or None = views"""
+        import torch
+        B, V, vol = self.batch, self.views, self.volumes
+        if pose.dim() != 3 or int(pose.shape[0]) != B or int(pose.shape[2]) != 16 or pose.dtype != torch.float32 or not pose.is_contiguous():
+            raise ValueError("pose must be a contiguous float32 [%d, pose_stride, 16]" % B)
+        d = _lib_tsdf_raycast.TsdfRaycastBatch()
+        d.batch, d.views, d.rows, d.cols = B, V, self.rows, self.cols
+        d.pitch, d.pose_stride = self.cols * 4, int(pose.shape[1])
+        d.nx, d.ny, d.nz = vol.nx, vol.ny, vol.nz
+        d.origin, d.volume, d.pose = vol.origin.data_ptr(), vol.volume.data_ptr(), pose.data_ptr()
+        d.view_index = _int32_ptr(view_index, "view_index", (B, V))
+        d.n_views = _int32_ptr(n_views, "n_views", (B,))
+        for name in ("depth", "normal", "n_hit", "n_skipped", "status", "workspace"):
+            setattr(d, name, getattr(self, name).data_ptr())
+        return d
+
+    def run(self, params, pose, view_index=None, n_views=None):
+        """enqueue the rendering of every sequence's views (asynchronous) -> (depth, normal, n_hit); per-sequence status lands in
+        self.status.  Raises ValueError when the volume's diagonal holds more than 2^20 steps, which the library refuses"""
+        vol = self.volumes
+        f32 = np.float32
+        with np.errstate(over="ignore"):
+            steps = ((f32(vol.nx) + f32(vol.ny)) + f32(vol.nz)) * f32(params.voxel_size) / f32(params.step)
+        if not steps <= f32(TSDF_RAYCAST_MAX_STEPS):
+            raise ValueError("(nx + ny + nz) * voxel_size / step must stay within 2^20: the steps a ray may take")
+        d = self.descriptor(pose, view_index, n_views)
+        _run_tsdf_raycast(self.ctx, "prs_tsdf_raycast_batch_run", C.byref(params), C.byref(d))
+        return self.depth, self.normal, self.n_hit
 
 
 # ---- image rectifier: undistort and stereo-rectify raw frames in front of the extractors (include/proslam_hip.h prs_rectify_*) ----
