@@ -265,6 +265,14 @@ TSDF = {"voxel_size": 0.02, "truncation": 0.08, "max_weight": 64.0, "min_weight"
 # the weight threshold and the range are the fusion's.
 TSDF_RAYCAST = {"step": 0.02, "min_weight": 1.0, "range_min": 0.1, "range_max": 10.0}
 
+# dense frame-to-model aligner (include/proslam_hip_dense_align.h prs_dense_align_params; ops.dense_align_params).  BUILD-DEFINED.
+# KinectFusion's gates in spirit: a pair is dropped when its points lie more than 20 cm apart or its normals more than about 37
+# degrees; a point-to-plane residual beyond 10 cm is an outlier, down-weighted rather than dropped so that a coarse start still
+# pulls; no damping; a step needs 100 inliers.  The schedule is (step, max_iterations) coarse to fine, KinectFusion's 4, 5, 10
+# iterations on every fourth, every second and every pixel; the range is the dense cloud's.
+DENSE_ALIGN = {"max_distance": 0.2, "min_normal_cos": 0.8, "robustifier": "saturated", "chi_threshold": 0.01, "damping": 0.0,
+               "min_num_inliers": 100, "range_min": 0.1, "range_max": 10.0, "schedule": [(4, 4), (2, 5), (1, 10)]}
+
 
 def _gate(mean_t, std_t, mean_r, std_r, where):
     return {"mean_translation": (mean_t,) * 3, "std_translation": (std_t,) * 3, "mean_rotation": (mean_r,) * 3,

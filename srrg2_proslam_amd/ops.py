@@ -9,7 +9,7 @@ import weakref
 
 import numpy as np
 
-from . import _lib, _lib_normals, _lib_tsdf, _lib_tsdf_raycast, configs
+from . import _lib, _lib_dense_align, _lib_normals, _lib_tsdf, _lib_tsdf_raycast, configs
 from ._lib import ProslamHipError, StereoBatch, StereoParams, TriangulatorParams
 
 CORR_DTYPE = np.dtype([("fixed_idx", np.int32), ("moving_idx", np.int32), ("response", np.float32)])
@@ -41,6 +41,11 @@ def _run_tsdf(ctx, entry, *args):
 def _run_tsdf_raycast(ctx, entry, *args):
     """_run for an entry point of the fourth header (include/proslam_hip_tsdf_raycast.h, bound by _lib_tsdf_raycast)"""
     return _check(ctx, getattr(_lib_tsdf_raycast.load(), entry)(ctx._h, *args), entry)
+
+
+def _run_dense_align(ctx, entry, *args):
+    """_run for an entry point of the fifth header (include/proslam_hip_dense_align.h, bound by _lib_dense_align)"""
+    return _check(ctx, getattr(_lib_dense_align.load(), entry)(ctx._h, *args), entry)
 
 
 class Context:
@@ -3382,6 +3387,203 @@ class TsdfRaycastBatch:
         d = self.descriptor(pose, view_index, n_views)
         _run_tsdf_raycast(self.ctx, "prs_tsdf_raycast_batch_run", C.byref(params), C.byref(d))
         return self.depth, self.normal, self.n_hit
+
+
+# ---- dense align: a live depth image against a rendered model view, point-to-plane on SE(3) (include/proslam_hip_dense_align.h) ----
+DENSE_ALIGN_RESULT_DTYPE = np.dtype([("H", np.float32, (6, 6)), ("b", np.float32, (6,)), ("chi_inliers", np.float32),
+                                     ("chi_total", np.float32), ("num_inliers", np.int32), ("num_outliers", np.int32),
+                                     ("num_rejected", np.int32), ("num_invalid", np.int32), ("num_unmatched", np.int32),
+                                     ("num_samples", np.int32), ("status", np.int32), ("iterations", np.int32),
+                                     ("steps_taken", np.int32), ("warnings", np.int32), ("reserved", np.int32, (2,))])
+
+
+def dense_align_params(camera, depth_type="u16", scale=1.0, max_distance=configs.DENSE_ALIGN["max_distance"],
+                       min_normal_cos=configs.DENSE_ALIGN["min_normal_cos"], robustifier=configs.DENSE_ALIGN["robustifier"],
+                       chi_threshold=configs.DENSE_ALIGN["chi_threshold"], damping=configs.DENSE_ALIGN["damping"],
+                       max_iterations=10, min_num_inliers=configs.DENSE_ALIGN["min_num_inliers"],
+                       range_min=configs.DENSE_ALIGN["range_min"], range_max=configs.DENSE_ALIGN["range_max"], linearize_only=0):
+    """prs_dense_align_params.  camera: a dictionary with fx, fy, cx, cy of both images; depth_type and scale: the live image's, as in
+    depth_cloud_params; max_distance (metres) and min_normal_cos: the two gates; robustifier "clamp" / "saturated" or a
+    PRS_ROBUSTIFIER_* value; chi_threshold in square metres of point-to-plane distance.  Raises ValueError on every value the library
+    refuses"""
+    p = _lib_dense_align.DenseAlignParams()
+    p.depth_type = _depth_type(depth_type, known=True)
+    if isinstance(robustifier, str):
+        if robustifier not in ("clamp", "saturated"):
+            raise ValueError('robustifier: "clamp" or "saturated"')
+        p.robustifier = _lib.ROBUSTIFIER_SATURATED if robustifier == "saturated" else _lib.ROBUSTIFIER_CLAMP
+    else:
+        p.robustifier = int(robustifier)
+    with np.errstate(over="ignore"):  # a value beyond float32 becomes inf and is refused below
+        p.depth_scaling_factor_to_meters = float(np.float32(scale))
+        p.max_distance, p.min_normal_cos = float(np.float32(max_distance)), float(np.float32(min_normal_cos))
+        p.chi_threshold, p.damping = float(np.float32(chi_threshold)), float(np.float32(damping))
+        p.range_min, p.range_max = float(np.float32(range_min)), float(np.float32(range_max))
+    p.fx, p.fy, p.cx, p.cy = (float(camera[k]) for k in ("fx", "fy", "cx", "cy"))
+    p.max_iterations, p.min_num_inliers, p.linearize_only = int(max_iterations), int(min_num_inliers), int(linearize_only)
+    values = [p.depth_scaling_factor_to_meters, p.fx, p.fy, p.cx, p.cy, p.range_min, p.range_max, p.max_distance, p.min_normal_cos,
+              p.chi_threshold, p.damping]
+    if not np.isfinite(values).all():
+        raise ValueError("every parameter must be finite as a float32")
+    if not p.depth_scaling_factor_to_meters > 0.0 or not p.max_distance > 0.0:
+        raise ValueError("scale and max_distance must be positive as float32")
+    if not 0.0 <= p.range_min <= p.range_max:
+        raise ValueError("0 <= range_min <= range_max must hold")
+    if p.chi_threshold < 0.0 or p.damping < 0.0 or not -1.0 <= p.min_normal_cos <= 1.0:
+        raise ValueError("chi_threshold and damping must not be negative, min_normal_cos must lie in [-1, 1]")
+    if p.robustifier not in (_lib.ROBUSTIFIER_CLAMP, _lib.ROBUSTIFIER_SATURATED):
+        raise ValueError("robustifier: PRS_ROBUSTIFIER_CLAMP or PRS_ROBUSTIFIER_SATURATED")
+    if p.max_iterations < 0 or (p.max_iterations < 1 and not p.linearize_only):
+        raise ValueError("max_iterations must be at least 1 (0 with linearize_only)")
+    return p
+
+
+def _pair_images(t, name, dtype, batch, rows, cols, channels=None):
+    """a tensor [B, rows, >= cols] (channels: [B, rows, cols, channels], contiguous) of one image a pair, or the same with a second
+    dimension of length 1, as a raycast of one view and a depth batch of one frame have it -> (the tensor without it, pitch in bytes)"""
+    if t.dim() == (4 if channels is None else 5) and int(t.shape[1]) == 1:
+        t = t[:, 0]
+    if channels is not None:
+        if t.dtype != dtype or tuple(t.shape) != (batch, rows, cols, channels) or not t.is_contiguous():
+            raise ValueError("%s must be a contiguous %s tensor [%d, %d, %d, %d]" % (name, dtype, batch, rows, cols, channels))
+        return t, cols * channels * t.element_size()
+    if t.dtype != dtype or t.dim() != 3 or tuple(t.shape[:2]) != (batch, rows) or int(t.shape[2]) < cols or t.stride(2) != 1 or \
+            (batch > 1 and int(t.stride(0)) != rows * int(t.stride(1))):
+        raise ValueError("%s must be a %s tensor [%d, %d, >= %d] with contiguous rows whose images follow one another at rows * pitch"
+                         % (name, dtype, batch, rows, cols))
+    return t, int(t.stride(1)) * t.element_size()
+
+
+class DenseAlignBatch:
+    """B independent pairs of a model view and a live image of rows x cols pixels: owns X [B, 16] (liveInModel, in / out: set it
+    before run), result [B] (DENSE_ALIGN_RESULT_DTYPE through results()), mask (with mask=True; [B, N] of the last call through
+    mask_of(step)) and the workspace, sized for step 1.  The model is the depth and normal of an ops.TsdfRaycastBatch of one view, the
+    live image a depth batch of one frame and optionally the normal of an ops.DepthNormalsBatch, all read in place."""
+
+    def __init__(self, ctx, batch, rows, cols, mask=False, device=0):
+        import torch
+        B = int(batch)
+        if B < 1 or int(rows) < 1 or int(cols) < 1:
+            raise ValueError("batch, rows and cols must be at least 1")
+        lib = _lib_dense_align.load()
+        self.ctx, self.batch, self.rows, self.cols = ctx, B, int(rows), int(cols)
+        nbytes = int(lib.prs_dense_align_workspace_bytes(B, self.rows, self.cols, 1))
+        if nbytes < 1:
+            raise ValueError("rows * cols and batch * chunks must stay below 2^31")
+        z = _zeros_on(device)
+        self.X = z((B, 16), torch.float32)
+        self.X[:, 0::5] = 1.0
+        self.result = z((B, DENSE_ALIGN_RESULT_DTYPE.itemsize), torch.uint8)
+        self.mask = z((B * self.rows * self.cols,), torch.uint8) if mask else None
+        self.workspace = z((nbytes,), torch.uint8)
+
+    def samples(self, step):
+        """N of a call with this step"""
+        return ((self.rows + step - 1) // step) * ((self.cols + step - 1) // step)
+
+    def mask_of(self, step):
+        """the [B, N] view of mask a call with this step wrote"""
+        return self.mask[:self.batch * self.samples(step)].view(self.batch, -1)
+
+    def descriptor(self, params, model_depth, model_normal, live_depth, live_normal=None, step=1):
+        """the prs_dense_align_batch of device tensors: model_depth [B, rows, >= cols] float32 and model_normal [B, rows, cols, 4]
+        float32 (or with a second dimension of 1 view), live_depth likewise of params' depth type, live_normal [B, rows, cols, 4] or
+        None (no normal gate)"""
+        import torch
+        B, rows, cols = self.batch, self.rows, self.cols
+        if int(step) < 1:
+            raise ValueError("step must be at least 1")
+        dtype = torch.uint16 if params.depth_type == DEPTH_U16 else torch.float32
+        d = _lib_dense_align.DenseAlignBatch()
+        d.batch, d.rows, d.cols, d.step = B, rows, cols, int(step)
+        md, d.model_pitch = _pair_images(model_depth, "model_depth", torch.float32, B, rows, cols)
+        ld, d.live_pitch = _pair_images(live_depth, "live_depth", dtype, B, rows, cols)
+        mn, _ = _pair_images(model_normal, "model_normal", torch.float32, B, rows, cols, 4)
+        d.model_depth, d.model_normal, d.live_depth = md.data_ptr(), mn.data_ptr(), ld.data_ptr()
+        if live_normal is not None:
+            d.live_normal = _pair_images(live_normal, "live_normal", torch.float32, B, rows, cols, 4)[0].data_ptr()
+        d.X, d.result, d.workspace = self.X.data_ptr(), self.result.data_ptr(), self.workspace.data_ptr()
+        d.mask = self.mask.data_ptr() if self.mask is not None else None
+        return d
+
+    def run(self, params, model_depth, model_normal, live_depth, live_normal=None, step=1):
+        """enqueue one call (asynchronous): params.max_iterations times (linearise, step) on every step-th pixel -> X"""
+        d = self.descriptor(params, model_depth, model_normal, live_depth, live_normal, step)
+        _run_dense_align(self.ctx, "prs_dense_align_batch_run", C.byref(params), C.byref(d))
+        return self.X
+
+    def align(self, params, model_depth, model_normal, live_depth, live_normal=None, schedule=None):
+        """enqueue the coarse-to-fine schedule, a list of (step, max_iterations) (None: configs.DENSE_ALIGN["schedule"]), on the same
+        X -> X; result and mask are the last call's"""
+        for step, iterations in (configs.DENSE_ALIGN["schedule"] if schedule is None else schedule):
+            p = _lib_dense_align.DenseAlignParams.from_buffer_copy(bytes(params))
+            p.max_iterations = int(iterations)
+            self.run(p, model_depth, model_normal, live_depth, live_normal, step)
+        return self.X
+
+    def results(self):
+        """result on the host (synchronises): a numpy array [B] of DENSE_ALIGN_RESULT_DTYPE"""
+        return np.frombuffer(self.result.cpu().numpy().tobytes(), DENSE_ALIGN_RESULT_DTYPE)
+
+
+class DenseTrackerBatch:
+    """raycast -> align -> integrate for B sequences of depth images: a dense tracker over an ops.TsdfVolumeBatch built with
+    frames = 1.  The poses are the camera's own (sensor_in_robot is the identity: a sensor offset is not handled here).  Owns pose
+    [B, pose_stride, 16], the raycast of one view, the aligner and the live frame.  start() fuses frame 0 at pose 0 (set pose[:, 0]
+    first); step(k, depth) renders the model at pose k - 1, aligns frame k from X = identity, writes pose k = pose k - 1 * X and fuses
+    frame k there.  Every call is asynchronous and a whole step can be captured into a graph; k is written into the captured fills
+    and copies, so a captured step is step k alone: replay it on another frame k (the tensor `depth` is read in place), not on another
+    k."""
+
+    def __init__(self, ctx, volumes, pose_stride, camera, depth_type="u16", scale=1.0, tsdf=None, raycast=None, align=None,
+                 schedule=None, mask=False):
+        import torch
+        if volumes.frames != 1:
+            raise ValueError("the volumes must be built with frames = 1: a step fuses one image")
+        self.ctx, self.volumes, self.schedule = ctx, volumes, schedule
+        B, rows, cols = volumes.batch, volumes.rows, volumes.cols
+        self.batch, self.pose_stride = B, int(pose_stride)
+        self.tsdf_params = tsdf_params(camera, depth_type=depth_type, scale=scale, **(tsdf or {}))
+        self.raycast_params = tsdf_raycast_params(camera, voxel_size=self.tsdf_params.voxel_size, **(raycast or {}))
+        self.align_params = dense_align_params(camera, depth_type=depth_type, scale=scale, **(align or {}))
+        dev = volumes.volume.device
+        z = _zeros_on(dev)
+        self.pose = z((B, self.pose_stride, 16), torch.float32)
+        self.pose[:, :, 0::5] = 1.0
+        self.model = TsdfRaycastBatch(ctx, volumes, 1, rows, cols)
+        self.aligner = DenseAlignBatch(ctx, B, rows, cols, mask=mask, device=dev)
+        self.live = z((B, 1, rows, cols), torch.uint16 if self.tsdf_params.depth_type == DEPTH_U16 else torch.float32)
+        self.index = z((B, 1), torch.int32)                       # the pose row of the view rendered and of the frame fused
+        self.identity = z((B, 16), torch.float32)
+        self.identity[:, 0::5] = 1.0
+        self._prev, self._inverse, self._next = z((B, 16), torch.float32), z((B, 16), torch.float32), z((B, 16), torch.float32)
+
+    def _integrate(self, k):
+        """self.live into the volumes at pose[:, k]"""
+        self.index.fill_(int(k))
+        self.volumes.integrate(self.ctx, self.tsdf_params, self.live, self.pose, frame_index=self.index)
+
+    def start(self, depth):
+        """fuse frame 0, depth [B, rows, cols], at pose[:, 0]"""
+        self.live[:, 0].copy_(depth)
+        self._integrate(0)
+
+    def step(self, k, depth):
+        """frame k >= 1, depth [B, rows, cols]: pose[:, k] from the model seen at pose[:, k - 1], then the frame into the volume -> X"""
+        if not 1 <= int(k) < self.pose_stride:
+            raise ValueError("k must lie in [1, pose_stride)")
+        self.index.fill_(int(k) - 1)
+        depth_m, normal_m, _ = self.model.run(self.raycast_params, self.pose, view_index=self.index)
+        self.live[:, 0].copy_(depth)
+        self.aligner.X.copy_(self.identity)
+        X = self.aligner.align(self.align_params, depth_m, normal_m, self.live, None, self.schedule)
+        # pose_compose_batch(P, X) is P * X^-1: once on the identity for X^-1, once more for pose k - 1 * X
+        self._prev.copy_(self.pose[:, int(k) - 1])
+        pose_compose_batch(self.ctx, self.identity, X, self._inverse)
+        pose_compose_batch(self.ctx, self._prev, self._inverse, self._next)
+        self.pose[:, int(k)].copy_(self._next)
+        self._integrate(k)
+        return X
 
 
 # ---- image rectifier: undistort and stereo-rectify raw frames in front of the extractors (include/proslam_hip.h prs_rectify_*) ----

@@ -1,0 +1,401 @@
+"""prs_dense_align_batch_run on the device against tests/dense_align_ref.py, byte for byte, through tests/dense_align_rig.py:
+
+1. image shapes at the edges of the reduction's shape (one sample, one row, one chunk exactly, a second chunk of one sample, more
+   than 64 chunks), steps 1 .. 4, both depth types, padded pitches on both depth images
+2. with and without live_normal and mask; both robustifiers; max_iterations 1 and 5; linearize_only
+3. batches of three pairs with different estimates: the same pair at position 0 and at position 2 gives identical bytes; a pair
+   that takes no step and a pair whose estimate is not finite beside good ones
+4. every call-level refusal, with the outputs untouched; what the Python layer refuses
+5. a captured graph, replayed twice and on changed inputs
+6. the chain integrate -> raycast -> depth normals -> DenseAlignBatch.align through ops, a DenseTrackerBatch run, and one of its steps
+   captured into a graph"""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+import dense_align_cases as cases
+import dense_align_ref as ref
+import dense_align_rig as rig_
+from dense_align_rig import Rig, pair_of, params_pair
+from srrg2_proslam_amd import _lib_dense_align, configs, ops
+from tsdf_rig import SENTINEL
+
+pytestmark = pytest.mark.gpu
+F = np.float32
+
+
+def counts_of(want):
+    return [[w[1][k] for k in ("num_unmatched", "num_inliers", "num_outliers", "num_rejected", "num_invalid")] for w in want]
+
+
+# ---- 1. shapes -------------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("rows,cols,step,depth_type,pads", [
+    (1, 1, 1, "f32", (0, 0)), (1, 70, 1, "u16", (1, 3)), (17, 9, 1, "f32", (2, 0)), (17, 9, 2, "u16", (0, 1)),
+    (32, 32, 1, "u16", (0, 0)),    # exactly one chunk at P = 4
+    (41, 25, 1, "f32", (3, 1)),    # the second chunk holds one sample
+    (41, 25, 3, "u16", (0, 0)), (41, 25, 4, "f32", (0, 2)), (60, 80, 2, "f32", (0, 0)), (60, 80, 3, "u16", (4, 4))])
+def test_image_shapes_steps_depth_types_and_padded_pitches(hip_ctx, rows, cols, step, depth_type, pads):
+    pairs = [pair_of(rows, cols, depth_type, seed) for seed in range(2)]
+    r = Rig(hip_ctx, pairs, step, *pads)
+    p, rp = params_pair(ops, pairs[0], min_num_inliers=1)
+    want = r.check(p, rp, (rows, cols, step))
+    assert r.n == ref.shape_of(rows, cols, step)[2] == want[0][1]["num_samples"]
+    if r.n >= 1000:
+        assert all(min(c) > 0 for c in counts_of(want)), counts_of(want)    # every class in every pair
+        assert all(w[1]["steps_taken"] == 2 for w in want)
+    if (rows, cols, step) == (32, 32, 1):
+        assert ref.shape_of(rows, cols, step)[3] == 1 and r.n == 256 * ref.P
+    if (rows, cols, step) == (41, 25, 1):
+        assert ref.shape_of(rows, cols, step)[3] == 2 and r.n == 256 * ref.P + 1
+
+
+def test_more_than_64_chunks(hip_ctx):
+    """320 x 240 at step 1: 75 chunks at P = 4, so the second-level loop runs twice on the first lanes"""
+    s = pair_of(240, 320, "u16", 3)
+    assert ref.shape_of(240, 320, 1)[3] == 75 > 64
+    r = Rig(hip_ctx, [s], 1)
+    want = r.check(*params_pair(ops, s, max_iterations=2), "320 x 240")
+    assert min(counts_of(want)[0]) > 100 and want[0][1]["steps_taken"] == 2
+
+
+# ---- 2. options ------------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("live_normal", [False, True])
+@pytest.mark.parametrize("mask", [False, True])
+def test_with_and_without_live_normal_and_mask(hip_ctx, live_normal, mask):
+    pairs = [pair_of(24, 40, "f32", seed) for seed in (4, 5)]
+    r = Rig(hip_ctx, pairs, 1, 1, 1)
+    want = r.check(*params_pair(ops, pairs[0]), (live_normal, mask), live_normal=live_normal, mask=mask)
+    other = r.expected(params_pair(ops, pairs[0])[1], live_normal=not live_normal)
+    assert [w[1]["num_rejected"] for w in want] != [w[1]["num_rejected"] for w in other]       # the gate is what differs
+    assert all(w[1]["num_rejected"] > 0 for w in want)
+
+
+@pytest.mark.parametrize("robustifier", [ref.CLAMP, ref.SATURATED])
+@pytest.mark.parametrize("iterations,linearize_only", [(1, 0), (5, 0), (0, 1), (3, 1)])
+def test_robustifiers_iterations_and_linearize_only(hip_ctx, robustifier, iterations, linearize_only):
+    pairs = [pair_of(30, 36, "u16", seed) for seed in (6, 7)]
+    r = Rig(hip_ctx, pairs, 1)
+    p, rp = params_pair(ops, pairs[0], robustifier=robustifier, max_iterations=iterations, linearize_only=linearize_only)
+    want = r.check(p, rp, (robustifier, iterations, linearize_only))
+    for X, res, _ in want:
+        assert res["num_outliers"] > 50 or iterations == 5     # (five steps in, the estimate has left the outliers behind)
+        assert res["iterations"] == (1 if linearize_only else iterations)
+        assert res["steps_taken"] == (0 if linearize_only else iterations)
+
+
+# ---- 3. batches ------------------------------------------------------------------------------------------------------------------------
+def test_a_pair_gives_the_same_bytes_at_every_position_of_a_batch(hip_ctx):
+    a, b, c = pair_of(41, 25, "f32", 8), pair_of(41, 25, "f32", 9), pair_of(41, 25, "f32", 10)
+    b["X0"] = cases.offset((0.01, 0.01, -0.01), (0.0, 0.01, 0.01))
+    first = Rig(hip_ctx, [a, b, c])
+    p, rp = params_pair(ops, a, max_iterations=3)
+    first.check(p, rp, "a b c")
+    one = first.outputs()
+    second = Rig(hip_ctx, [c, b, a])
+    second.check(p, rp, "c b a")
+    two = second.outputs()
+    alone = Rig(hip_ctx, [a])
+    alone.check(p, rp, "a")
+    n = first.n
+
+    def of(o, b):
+        return o["X"][b].tobytes(), o["result"][b].tobytes(), o["mask"][b * n:(b + 1) * n].tobytes()
+    assert of(one, 0) == of(two, 2) == of(alone.outputs(), 0) and of(one, 2) == of(two, 0) and of(one, 1) == of(two, 1)
+    assert of(one, 0) != of(one, 1) and of(one, 0) != of(one, 2)
+
+
+def test_a_pair_that_takes_no_step_and_an_estimate_that_is_not_finite_beside_good_ones(hip_ctx):
+    good, few, nan, inf, last = (pair_of(20, 24, "u16", seed) for seed in (11, 12, 13, 14, 15))
+    few["live_depth"] = np.where(np.arange(24)[None, :] < 2, few["live_depth"], 0).astype(np.uint16)   # a handful of inliers
+    nan["X0"][1, 2] = np.nan
+    inf["X0"][2, 3] = np.inf
+    # a plane alone leaves three degrees free: the inliers suffice, the first pivot is 0, the estimate stays
+    flat = dict(good, model_depth=np.full((20, 24), 2.5, F), live_depth=np.full((20, 24), 2500, np.uint16),
+                model_normal=np.tile(np.array([0, 0, -1, 1], F), (20, 24, 1)), live_normal=np.tile(np.array([0, 0, -1, 1], F), (20, 24, 1)),
+                X0=np.eye(4, dtype=F))
+    pairs = [good, few, nan, flat, inf, last]
+    r = Rig(hip_ctx, pairs)
+    p, rp = params_pair(ops, good, max_iterations=3, min_num_inliers=40)
+    want = r.check(p, rp, "mixed")
+    res = [w[1] for w in want]
+    assert [x["warnings"] for x in res] == [0, 0, ref.PRS_ERR_RANGE, 0, ref.PRS_ERR_RANGE, 0]
+    assert [x["steps_taken"] for x in res] == [3, 0, 0, 0, 0, 3] and [x["iterations"] for x in res] == [3, 3, 0, 3, 0, 3]
+    assert 0 < res[1]["num_inliers"] < 40 and res[1]["status"] == 0 and (res[3]["status"], res[3]["num_inliers"]) == (1, 480)
+    for b in (1, 2, 3, 4):
+        assert want[b][0].tobytes() == np.asarray(pairs[b]["X0"], F).tobytes()
+    assert not want[2][2].any() and not want[4][2].any() and res[2]["num_samples"] == 480
+
+
+# ---- 4. refusals -----------------------------------------------------------------------------------------------------------------------
+def test_call_level_refusals_write_nothing(hip_ctx):
+    pairs = [pair_of(20, 24, "u16", seed) for seed in (16, 17)]
+    r = Rig(hip_ctx, pairs, 1, 1, 1)
+    lib, ctx = _lib_dense_align.load(), r.ctx._h
+    p, _ = params_pair(ops, pairs[0])
+    r.fill_outputs()
+    before = r.outputs()
+
+    def run(d, q=None):
+        q = p if q is None else q
+        return lib.prs_dense_align_batch_run(ctx, C.byref(q) if q != "null" else None, C.byref(d) if d is not None else None)
+
+    def changed(**fields):
+        q, _ = params_pair(ops, pairs[0])
+        for k, v in fields.items():
+            setattr(q, k, v)
+        return q
+
+    D = r.descriptor
+    nan, inf = float("nan"), float("inf")
+    # PRS_ERR_NULL
+    assert run(None) == -1 and run(D(), "null") == -1
+    for field in ("model_depth", "model_normal", "live_depth", "X", "result", "workspace"):
+        d = D()
+        setattr(d, field, None)
+        assert run(d) == -1, field
+    # PRS_ERR_RANGE
+    for field, value in (("batch", 0), ("rows", 0), ("cols", -1), ("step", 0), ("step", -2), ("model_pitch", 4 * 24 - 4), ("model_pitch", 4 * 24 + 2),
+                         ("live_pitch", 2 * 24 - 2), ("live_pitch", 2 * 24 + 1), ("live_pitch", -48)):
+        d = D()
+        setattr(d, field, value)
+        assert run(d) == ref.PRS_ERR_RANGE, (field, value)
+    for field, value in (("max_iterations", -1), ("max_iterations", 0), ("depth_scaling_factor_to_meters", 0.0),
+                         ("depth_scaling_factor_to_meters", -1e-3), ("depth_scaling_factor_to_meters", nan), ("fx", inf), ("fy", nan),
+                         ("cx", -inf), ("cy", nan), ("range_min", -1.0), ("range_min", 11.0), ("range_min", nan), ("range_max", inf),
+                         ("max_distance", 0.0), ("max_distance", -0.1), ("max_distance", inf), ("chi_threshold", -1e-6),
+                         ("chi_threshold", nan), ("damping", -1e-6), ("damping", inf), ("min_normal_cos", 1.001), ("min_normal_cos", -1.5),
+                         ("min_normal_cos", nan), ("robustifier", 2), ("robustifier", -1)):
+        assert run(D(), changed(**{field: value})) == ref.PRS_ERR_RANGE, (field, value)
+    assert run(D(), changed(max_iterations=-1, linearize_only=1)) == ref.PRS_ERR_RANGE
+    # PRS_ERR_UNSUPPORTED
+    for value in (2, -1, 7):
+        assert run(D(), changed(depth_type=value)) == -5, value
+    for field, step in (("model_normal", 8), ("model_normal", 4), ("live_normal", 8), ("X", 8), ("X", 4), ("workspace", 8), ("workspace", 4),
+                        ("model_depth", 2), ("live_depth", 1), ("result", 2)):
+        d = D()
+        setattr(d, field, getattr(d, field) + step)
+        assert run(d) == -5, (field, step)
+    d = D()
+    d.rows, d.cols, d.model_pitch, d.live_pitch = 1 << 16, 1 << 15, 4 << 15, 2 << 15       # rows * cols beyond 2^31 - 1
+    assert run(d) == -5
+    d = D()
+    d.batch, d.rows, d.cols, d.model_pitch, d.live_pitch = 1 << 22, 1 << 10, 1 << 10, 4 << 10, 2 << 10   # batch * chunks = 2^32
+    assert run(d) == -5
+    r.ctx.synchronize()
+    after = r.outputs()
+    for name in rig_.OUTPUTS:
+        assert after[name].tobytes() == before[name].tobytes(), name
+    assert (after["result"].view(np.uint8) == SENTINEL).all() and (after["mask"] == SENTINEL).all()
+    assert b"prs_dense_align_batch_run" in lib.prs_last_error(ctx)
+    assert run(D()) == 0 and run(D(), changed(max_iterations=0, linearize_only=1)) == 0
+    r.ctx.synchronize()
+
+
+def test_the_python_layer_refuses_what_it_cannot_describe(hip_ctx):
+    import torch
+    ab = ops.DenseAlignBatch(hip_ctx, 2, 5, 6, mask=True)
+    assert tuple(ab.X.shape) == (2, 16) and ab.X.cpu().numpy().reshape(2, 4, 4).tolist() == [np.eye(4).tolist()] * 2
+    assert ab.samples(1) == 30 and ab.samples(4) == 4 and tuple(ab.mask_of(4).shape) == (2, 4)
+    p = ops.dense_align_params(cases.CAMERA, "f32")
+    z = lambda *shape, dt=torch.float32: torch.zeros(shape, dtype=dt, device="cuda")  # noqa: E731
+    md, mn, ld = z(2, 5, 6), z(2, 5, 6, 4), z(2, 1, 5, 8)[..., :6]
+    d = ab.descriptor(p, md, mn, ld, None, 2)
+    assert (d.model_pitch, d.live_pitch, d.step, d.live_normal, d.model_depth, d.live_depth) == (24, 32, 2, None, md.data_ptr(), ld.data_ptr())
+    assert ab.descriptor(p, md.unsqueeze(1), mn.unsqueeze(1), ld, mn).live_normal == mn.data_ptr()
+    for bad in (dict(model_depth=md[:1]), dict(model_depth=md.to(torch.float64)), dict(model_depth=z(2, 5, 12)[..., ::2]),
+                dict(model_depth=z(2, 6, 6)[:, :5]), dict(model_normal=z(2, 5, 6, 3)), dict(model_normal=z(2, 5, 6, 8)[..., :4]),
+                dict(live_depth=z(2, 5, 6, dt=torch.uint16)), dict(live_normal=z(2, 5, 6)), dict(step=0)):
+        with pytest.raises(ValueError):
+            ab.descriptor(p, **dict(dict(model_depth=md, model_normal=mn, live_depth=ld), **bad))
+    for bad in (dict(batch=0), dict(rows=0), dict(cols=-1), dict(rows=1 << 16, cols=1 << 15)):
+        with pytest.raises(ValueError):
+            ops.DenseAlignBatch(hip_ctx, **dict(dict(batch=1, rows=2, cols=2), **bad))
+    vb = ops.TsdfVolumeBatch(1, 4, 4, 4, 2, 5, 6)
+    with pytest.raises(ValueError):
+        ops.DenseTrackerBatch(hip_ctx, vb, 3, cases.CAMERA)             # frames = 2: a step fuses one image
+
+
+# ---- 5. capture ------------------------------------------------------------------------------------------------------------------------
+def test_a_captured_graph_replayed_twice_equals_the_eager_bytes(hip_ctx):
+    import torch
+    ctx = hip_ctx
+    pairs = [pair_of(41, 25, "f32", seed) for seed in (18, 19)]
+    r = Rig(ctx, pairs, 1, 1, 0)
+    p, rp = params_pair(ops, pairs[0], max_iterations=3)
+    r.check(p, rp, "eager")
+    eager = {k: v.tobytes() for k, v in r.outputs().items()}
+    s = torch.cuda.Stream()
+    s.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(s):
+        ctx.use_torch_stream()
+        assert r.run(p) == 0  # warm-up on the capture stream
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g, stream=s):
+            assert r.run(p) == 0
+    torch.cuda.current_stream().wait_stream(s)
+    ctx.use_torch_stream()
+    torch.cuda.synchronize()
+    for replay in range(2):
+        r.fill_outputs()
+        torch.cuda.synchronize()
+        g.replay()
+        torch.cuda.synchronize()
+        assert {k: v.tobytes() for k, v in r.outputs().items()} == eager, replay
+    # and on other images and estimates, one of which is not finite now
+    r.pairs = [pair_of(41, 25, "f32", seed) for seed in (20, 21)]
+    r.pairs[1]["X0"][0, 0] = np.nan
+    r.upload()
+    r.fill_outputs()
+    torch.cuda.synchronize()
+    g.replay()
+    torch.cuda.synchronize()
+    want = r.expected(rp)
+    r.compare(want, "replay on other pairs")
+    assert [w[1]["warnings"] for w in want] == [0, ref.PRS_ERR_RANGE] and want[0][1]["steps_taken"] == 3
+
+
+# ---- 6. the chain and the tracker ------------------------------------------------------------------------------------------------------
+VS, DIMS, ORIGIN = 0.04, (70, 55, 60), (-1.4, -1.1, 1.1, 0.0)
+LOOKS = (((0.0, 0.0, 0.0), (0.0, 0.0, 0.0)), ((0.1, 0.0, 0.0), (0.0, -0.05, 0.0)), ((-0.1, 0.05, 0.0), (0.03, 0.05, 0.0)))
+
+
+def fused_corner(hip_ctx, rows=cases.ROWS, cols=cases.COLS, camera=cases.CAMERA):
+    """the corner fused from three poses through ops -> the volume batch (one image a call)"""
+    import torch
+    vb = ops.TsdfVolumeBatch(1, *DIMS, 1, rows, cols)
+    vb.origin.copy_(torch.tensor([ORIGIN], dtype=torch.float32))
+    fp = ops.tsdf_params(camera, voxel_size=VS, truncation=4 * VS, depth_type="f32")
+    for t, a in LOOKS:
+        P = cases.offset(t, a)
+        depth = torch.from_numpy(cases.render(P, camera, rows, cols)[0]).cuda()[None, None]
+        vb.integrate(hip_ctx, fp, depth, torch.from_numpy(P.reshape(1, 1, 16)).cuda())
+    return vb
+
+
+def test_integrate_raycast_depth_normals_and_align_through_ops(hip_ctx):
+    """the model is a raycast of the fused corner at the identity, the live image a raycast at a planted X with the normals of the
+    depth-normals stage: the default schedule recovers X within the bound of tests/test_dense_align_ref.py (measured there on the
+    restated chain: 0.25 mm, 0.20 mrad), and every output equals the restatement run on the device's own images"""
+    import torch
+    from test_dense_align_ref import MAX_ROTATION, MAX_TRANSLATION
+    vb = fused_corner(hip_ctx)
+    Xt = cases.offset((0.03, -0.02, 0.025), (0.02, -0.03, 0.025))
+    rb = ops.TsdfRaycastBatch(hip_ctx, vb, 2, cases.ROWS, cases.COLS)
+    pose = torch.from_numpy(np.stack([np.eye(4, dtype=F).reshape(16), Xt.reshape(16)])[None]).cuda()
+    depth, normal, n_hit = rb.run(ops.tsdf_raycast_params(cases.CAMERA, voxel_size=VS, step=VS), pose)
+    live = depth[0, 1].clone()[None, None]                             # [1, 1, rows, cols]: a depth batch of one frame
+    nb = ops.DepthNormalsBatch(1, 1, cases.ROWS, cases.COLS)
+    live_normal = nb.run(hip_ctx, ops.depth_normals_params(cases.CAMERA, depth_type="f32"), live)
+    ab = ops.DenseAlignBatch(hip_ctx, 1, cases.ROWS, cases.COLS, mask=True)
+    p = ops.dense_align_params(cases.CAMERA, "f32")
+    X = ab.align(p, depth[:, 0:1], normal[:, 0:1], live, live_normal)
+    hip_ctx.synchronize()
+    assert X.data_ptr() == ab.X.data_ptr() and n_hit.cpu().min() > 3000
+    got = X.cpu().numpy().reshape(4, 4)
+    dt, dr = ref.pose_error(got, Xt)
+    print("chain: %.3g m, %.3g rad left" % (dt, dr))
+    assert dt < MAX_TRANSLATION and dr < MAX_ROTATION
+    d, n, ln = depth.cpu().numpy()[0], normal.cpu().numpy()[0], live_normal.cpu().numpy()[0, 0]
+    Xr, res, cls = ref.align_schedule(ref.params(cases.CAMERA, "f32"), np.eye(4), d[0], n[0], d[1], ln, configs.DENSE_ALIGN["schedule"])
+    assert got.tobytes() == Xr.tobytes() and ab.results()[0].tobytes() == rig_.result_bytes(res)
+    assert (ab.mask_of(1).cpu().numpy()[0] == cls).all() and res["num_inliers"] > 3000 and res["num_rejected"] > 100
+
+
+def tracker_scene():
+    """four 24 x 20 frames of the corner along a small motion -> (camera, frames [1, rows, cols] on the device, schedule, the
+    tracker's settings, a function that builds an empty volume batch)"""
+    import torch
+    rows, cols = 20, 24
+    cam = cases.small_camera(rows, cols)
+    motion = [cases.offset((0.01 * k, -0.005 * k, 0.004 * k), (0.002 * k, -0.004 * k, 0.003 * k)) for k in range(4)]
+    frames = [torch.from_numpy(cases.render(P, cam, rows, cols)[0]).cuda()[None] for P in motion]
+    kw = dict(tsdf=dict(voxel_size=VS, truncation=4 * VS), raycast=dict(step=VS), align=dict(min_num_inliers=50))
+
+    def volumes():
+        vb = ops.TsdfVolumeBatch(1, *DIMS, 1, rows, cols)
+        vb.origin.copy_(torch.tensor([ORIGIN], dtype=torch.float32))
+        return vb
+    return cam, frames, [(2, 3), (1, 4)], kw, volumes
+
+
+def test_a_tracker_run_equals_the_same_calls_made_one_by_one(hip_ctx):
+    """DenseTrackerBatch against raycast, align, compose and integrate called by hand.  (24 x 20 pixels against 4 cm voxels are too
+    coarse to say how well the motion is followed: the chain test above bounds the error at a size that can.)"""
+    import torch
+    cam, frames, schedule, kw, volumes = tracker_scene()
+    rows, cols = frames[0].shape[1:]
+    tracker = ops.DenseTrackerBatch(hip_ctx, volumes(), 4, cam, "f32", schedule=schedule, **kw)
+    tracker.start(frames[0])
+    for k in range(1, 4):
+        tracker.step(k, frames[k])
+    hip_ctx.synchronize()
+    poses = tracker.pose.cpu().numpy()[0].reshape(4, 4, 4)
+    for k in range(1, 4):  # every step moved the pose and kept it rigid
+        assert poses[k].tobytes() != poses[k - 1].tobytes() and np.allclose(poses[k][:3, :3] @ poses[k][:3, :3].T, np.eye(3), atol=1e-5)
+
+    vb = volumes()
+    fp = ops.tsdf_params(cam, depth_type="f32", voxel_size=VS, truncation=4 * VS)
+    rp = ops.tsdf_raycast_params(cam, voxel_size=VS, step=VS)
+    ap = ops.dense_align_params(cam, "f32", min_num_inliers=50)
+    rb, ab = ops.TsdfRaycastBatch(hip_ctx, vb, 1, rows, cols), ops.DenseAlignBatch(hip_ctx, 1, rows, cols)
+    pose = torch.zeros((1, 4, 16), dtype=torch.float32, device="cuda")
+    pose[:, :, 0::5] = 1.0
+    eye = pose[:, 0].clone()
+    index = torch.zeros((1, 1), dtype=torch.int32, device="cuda")
+    vb.integrate(hip_ctx, fp, frames[0][:, None], pose, frame_index=index)
+    for k in range(1, 4):
+        index.fill_(k - 1)
+        depth, normal, _ = rb.run(rp, pose, view_index=index)
+        ab.X.copy_(eye)
+        X = ab.align(ap, depth, normal, frames[k][:, None], None, schedule)
+        inverse, nxt = torch.empty_like(eye), torch.empty_like(eye)
+        ops.pose_compose_batch(hip_ctx, eye, X, inverse)
+        ops.pose_compose_batch(hip_ctx, pose[:, k - 1].contiguous(), inverse, nxt)
+        pose[:, k] = nxt
+        index.fill_(k)
+        vb.integrate(hip_ctx, fp, frames[k][:, None], pose, frame_index=index)
+    hip_ctx.synchronize()
+    assert pose.cpu().numpy().tobytes() == tracker.pose.cpu().numpy().tobytes()
+    assert vb.volume.cpu().numpy().tobytes() == tracker.volumes.volume.cpu().numpy().tobytes()
+    assert ab.results().tobytes() == tracker.aligner.results().tobytes() and ab.results()[0]["steps_taken"] == 4
+
+
+def test_a_captured_tracker_step_replayed_equals_the_eager_step(hip_ctx):
+    """step 2 captured into a graph and replayed on the state step 1 left equals step 2 made eagerly: pose, volume, X and result"""
+    import torch
+    ctx = hip_ctx
+    cam, frames, schedule, kw, volumes = tracker_scene()
+    eager = ops.DenseTrackerBatch(ctx, volumes(), 4, cam, "f32", schedule=schedule, **kw)
+    eager.start(frames[0])
+    eager.step(1, frames[1])
+    eager.step(2, frames[2])
+    t = ops.DenseTrackerBatch(ctx, volumes(), 4, cam, "f32", schedule=schedule, **kw)
+    t.start(frames[0])
+    t.step(1, frames[1])
+    ctx.synchronize()
+    volume, pose = t.volumes.volume.clone(), t.pose.clone()
+    frame = torch.zeros_like(frames[2])                   # the captured step reads this tensor in place
+    s = torch.cuda.Stream()
+    s.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(s):
+        ctx.use_torch_stream()
+        t.step(2, frame)  # warm-up on the capture stream
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g, stream=s):
+            t.step(2, frame)
+    torch.cuda.current_stream().wait_stream(s)
+    ctx.use_torch_stream()
+    torch.cuda.synchronize()
+    for replay in range(2):
+        t.volumes.volume.copy_(volume)
+        t.pose.copy_(pose)
+        frame.copy_(frames[2])
+        t.aligner.result.fill_(SENTINEL)
+        torch.cuda.synchronize()
+        g.replay()
+        torch.cuda.synchronize()
+        assert t.pose.cpu().numpy().tobytes() == eager.pose.cpu().numpy().tobytes(), replay
+        assert t.volumes.volume.cpu().numpy().tobytes() == eager.volumes.volume.cpu().numpy().tobytes(), replay
+        assert t.aligner.X.cpu().numpy().tobytes() == eager.aligner.X.cpu().numpy().tobytes(), replay
+        assert t.aligner.results().tobytes() == eager.aligner.results().tobytes() and t.aligner.results()[0]["steps_taken"] == 4, replay
