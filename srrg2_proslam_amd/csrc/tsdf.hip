@@ -30,6 +30,7 @@
 #include "prs_host.h"
 #include "prs_image.h"
 #include "prs_se3.h"
+#include "prs_tsdf_cross.h"
 
 namespace prs {
 
@@ -231,10 +232,6 @@ struct SurfaceArgs {
   int32_t* ws_count;  // [batch][chunks] crossings of the chunk; after the scan: the chunk's first output row, -1 = keep out
 };
 
-__device__ __forceinline__ bool in_band(const float2 c, const float min_weight) {
-  return c.y >= min_weight && fabsf(c.x) < 1.0f;
-}
-
 // blockIdx.x = b * chunks + c.  SCATTER: write the rows (else: count them)
 template <bool SCATTER>
 __global__ __launch_bounds__(kThreads) void tsdf_surface_kernel(const SurfaceArgs a) {
@@ -325,45 +322,14 @@ __global__ __launch_bounds__(kThreads) void tsdf_surface_kernel(const SurfaceArg
       if (row >= cap) {
         continue;
       }
-      const float ta = va[s].x, tn = vn[s][e].x;
-      const float sfrac = ta / (ta - tn);
-      float p[3];
-#pragma unroll
-      for (int d = 0; d < 3; ++d) {
-        p[d] = o[d] + ((float) at[s][d] + 0.5f) * vs;
-      }
-      p[e] = p[e] + sfrac * vs;
-      const float wa = va[s].y, wn = vn[s][e].y;
-      reinterpret_cast<float4*>(a.o.xyz)[out0 + (size_t) row] = make_float4(p[0], p[1], p[2], wn < wa ? wn : wa);
+      // the crossing's point and normal: prs_tsdf_cross.h, which the mesh call runs too
+      reinterpret_cast<float4*>(a.o.xyz)[out0 + (size_t) row] = crossing_point(o, at[s][0], at[s][1], at[s][2], e, va[s], vn[s][e], vs);
       if (a.o.cell) {
         a.o.cell[out0 + (size_t) row] = 3 * lin + e;
       }
       if (a.o.normal) {
-        const bool at_n = fabsf(tn) < fabsf(ta);
-        const int g = at_n ? lin + stride[e] : lin;
-        const float tg = at_n ? tn : ta;
-        float m[3];
-#pragma unroll
-        for (int d = 0; d < 3; ++d) {
-          const int gd = at[s][d] + ((at_n && d == e) ? 1 : 0);
-          float hi = tg, lo = tg;
-          if (gd + 1 < n[d]) {
-            const float2 h = vol[g + stride[d]];
-            hi = h.y >= mw ? h.x : tg;
-          }
-          if (gd >= 1) {
-            const float2 l = vol[g - stride[d]];
-            lo = l.y >= mw ? l.x : tg;
-          }
-          m[d] = hi - lo;
-        }
-        const float len2 = (m[0] * m[0] + m[1] * m[1]) + m[2] * m[2];
-        float4 nrm = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-        if (len2 > 0.0f && len2 <= FLT_MAX) {
-          const float len = sqrtf(len2);
-          nrm = make_float4(m[0] / len, m[1] / len, m[2] / len, 1.0f);
-        }
-        reinterpret_cast<float4*>(a.o.normal)[out0 + (size_t) row] = nrm;
+        reinterpret_cast<float4*>(a.o.normal)[out0 + (size_t) row] =
+            crossing_normal(vol, lin, at[s][0], at[s][1], at[s][2], e, stride[e], va[s].x, vn[s][e].x, nx, ny, nz, mw);
       }
     }
   }

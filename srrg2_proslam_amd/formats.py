@@ -157,10 +157,13 @@ def associate(stamps_est, stamps_gt, max_difference=0.02):
     return gt_row, (gt_row >= 0).astype(np.uint8)
 
 
-def write_ply(path, xyz, desc=None, normals=None):
+def write_ply(path, xyz, desc=None, normals=None, faces=None):
     """a minimal binary-little-endian PLY of a landmark cloud (ops.WorldMapBatch.cloud_of: xyz [n, 3] or [n, 4], the first three
     columns are written; desc: optional uint8 [n, 32], written as 32 uchar properties d0 .. d31 of every vertex; normals: optional
-    [n, 3] or [n, 4] (ops.DepthNormalsBatch.rows_of), the first three columns written as nx ny nz behind x y z)"""
+    [n, 3] or [n, 4] (ops.DepthNormalsBatch.rows_of), the first three columns written as nx ny nz behind x y z; faces: optional
+    integer [m, 3] or [m, 4] of vertex rows (ops.TsdfMeshBatch.mesh_of), written behind the vertices as `element face m` with
+    `property list uchar int vertex_indices`; an index outside [0, n) raises ValueError.  Without faces the file has no face
+    element at all)"""
     xyz = np.asarray(xyz, np.float32)
     if xyz.ndim != 2 or xyz.shape[1] not in (3, 4):
         raise ValueError("xyz must be [n, 3] or [n, 4]")
@@ -182,9 +185,21 @@ def write_ply(path, xyz, desc=None, normals=None):
             rec["d%d" % i] = desc[:, i]
     header = ["ply", "format binary_little_endian 1.0", "element vertex %d" % n]
     header += ["property %s %s" % ("float" if rec.dtype[name].kind == "f" else "uchar", name) for name in rec.dtype.names]
+    face_rec = None
+    if faces is not None:
+        faces = np.asarray(faces)
+        if faces.ndim != 2 or faces.shape[1] not in (3, 4) or faces.dtype.kind not in "iu":
+            raise ValueError("faces must be an integer [m, 3] or [m, 4]")
+        if faces.size and (int(faces.min()) < 0 or int(faces.max()) >= n):
+            raise ValueError("faces names a vertex outside [0, %d)" % n)
+        face_rec = np.zeros(faces.shape[0], np.dtype([("count", "u1"), ("vertex_indices", "<i4", (faces.shape[1],))]))
+        face_rec["count"], face_rec["vertex_indices"] = faces.shape[1], faces
+        header += ["element face %d" % faces.shape[0], "property list uchar int vertex_indices"]
     with open(path, "wb") as f:
         f.write(("\n".join(header + ["end_header"]) + "\n").encode("ascii"))
         f.write(rec.tobytes())
+        if face_rec is not None:
+            f.write(face_rec.tobytes())
 
 
 # ---------------------------------------------------------------- .conf reader (subset)

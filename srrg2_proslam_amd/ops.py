@@ -9,7 +9,7 @@ import weakref
 
 import numpy as np
 
-from . import _lib, _lib_dense_align, _lib_normals, _lib_tsdf, _lib_tsdf_raycast, configs
+from . import _lib, _lib_dense_align, _lib_normals, _lib_tsdf, _lib_tsdf_mesh, _lib_tsdf_raycast, configs
 from ._lib import ProslamHipError, StereoBatch, StereoParams, TriangulatorParams
 
 CORR_DTYPE = np.dtype([("fixed_idx", np.int32), ("moving_idx", np.int32), ("response", np.float32)])
@@ -46,6 +46,11 @@ def _run_tsdf_raycast(ctx, entry, *args):
 def _run_dense_align(ctx, entry, *args):
     """_run for an entry point of the fifth header (include/proslam_hip_dense_align.h, bound by _lib_dense_align)"""
     return _check(ctx, getattr(_lib_dense_align.load(), entry)(ctx._h, *args), entry)
+
+
+def _run_tsdf_mesh(ctx, entry, *args):
+    """_run for an entry point of the sixth header (include/proslam_hip_tsdf_mesh.h, bound by _lib_tsdf_mesh)"""
+    return _check(ctx, getattr(_lib_tsdf_mesh.load(), entry)(ctx._h, *args), entry)
 
 
 class Context:
@@ -3387,6 +3392,95 @@ class TsdfRaycastBatch:
         d = self.descriptor(pose, view_index, n_views)
         _run_tsdf_raycast(self.ctx, "prs_tsdf_raycast_batch_run", C.byref(params), C.byref(d))
         return self.depth, self.normal, self.n_hit
+
+
+# ---- TSDF mesh: a fused volume as an indexed quad mesh, by surface nets (include/proslam_hip_tsdf_mesh.h) ----
+TSDF_MESH_OUTPUTS = ("normal", "cube", "edge")
+
+
+class TsdfMeshBatch:
+    """the meshes of the volumes of an ops.TsdfVolumeBatch, up to vertex_stride vertices and quad_stride quads per sequence: owns
+    vertex [B, vertex_stride, 4] (x, y, z and the crossings it averages), quad [B, quad_stride, 4] int32 (vertex rows of the
+    sequence, counter-clockwise seen from the observed free side), n_vertices, n_vertices_total, n_quads, n_quads_total and status
+    [B], the workspace and, as `outputs` names them, normal [B, vertex_stride, 4], cube [B, vertex_stride] and edge [B, quad_stride]
+    (the voxel of a vertex's cube; the surface call's `cell` of a quad's crossing); reads volumes.volume and volumes.origin in
+    place."""
+
+    def __init__(self, volumes, vertex_stride, quad_stride, outputs=TSDF_MESH_OUTPUTS):
+        import torch
+        nv, nq = int(vertex_stride), int(quad_stride)
+        if nv < 1 or nq < 1:
+            raise ValueError("vertex_stride and quad_stride must be at least 1")
+        outputs = tuple(outputs)
+        if any(name not in TSDF_MESH_OUTPUTS for name in outputs):
+            raise ValueError("outputs: any of %s" % ", ".join(TSDF_MESH_OUTPUTS))
+        lib = _lib_tsdf_mesh.load()
+        self.volumes, self.vertex_stride, self.quad_stride = volumes, nv, nq
+        B = self.batch = volumes.batch
+        nbytes = int(lib.prs_tsdf_mesh_workspace_bytes(B, volumes.nx, volumes.ny, volumes.nz))
+        if nbytes < 1:
+            raise ValueError("nx * ny * nz must stay within (2^31 - 1) / 3 and batch * ceil(nx * ny * nz / 1024) within 2^24 - 1")
+        z = _zeros_on(volumes.volume.device)
+        self.vertex, self.quad = z((B, nv, 4), torch.float32), z((B, nq, 4), torch.int32)
+        self.normal = z((B, nv, 4), torch.float32) if "normal" in outputs else None
+        self.cube = z((B, nv), torch.int32) if "cube" in outputs else None
+        self.edge = z((B, nq), torch.int32) if "edge" in outputs else None
+        self.n_vertices, self.n_vertices_total = z((B,), torch.int32), z((B,), torch.int32)
+        self.n_quads, self.n_quads_total, self.status = z((B,), torch.int32), z((B,), torch.int32), z((B,), torch.int32)
+        self.workspace = z((nbytes,), torch.uint8)
+
+    def descriptor(self, count_only=False):
+        """the prs_tsdf_mesh_batch of this batch's tensors and its volumes'"""
+        vol = self.volumes
+        d = _lib_tsdf_mesh.TsdfMeshBatch()
+        d.batch, d.nx, d.ny, d.nz = self.batch, vol.nx, vol.ny, vol.nz
+        d.vertex_stride, d.quad_stride = self.vertex_stride, self.quad_stride
+        d.origin, d.volume = vol.origin.data_ptr(), vol.volume.data_ptr()
+        for name in ("n_vertices", "n_vertices_total", "n_quads", "n_quads_total", "status", "workspace"):
+            setattr(d, name, getattr(self, name).data_ptr())
+        if not count_only:
+            for name in ("vertex", "quad") + TSDF_MESH_OUTPUTS:
+                t = getattr(self, name)
+                setattr(d, name, None if t is None else t.data_ptr())
+        return d
+
+    @staticmethod
+    def _checked(params):
+        """raises ValueError on the params the library refuses: of prs_tsdf_params the call reads voxel_size and min_weight"""
+        if not (np.isfinite(params.voxel_size) and params.voxel_size > 0.0 and np.isfinite(params.min_weight)):
+            raise ValueError("voxel_size must be finite and positive, min_weight finite")
+
+    def run(self, ctx, params):
+        """enqueue the mesh of every volume (asynchronous) -> (vertex, quad, n_vertices, n_quads): the first n_vertices[b] rows of
+        vertex[b] and the first n_quads[b] rows of quad[b]; PRS_ERR_CAPACITY lands in self.status[b] when a stride did not hold them
+        all (n_vertices_total[b], n_quads_total[b])"""
+        self._checked(params)
+        d = self.descriptor()
+        _run_tsdf_mesh(ctx, "prs_tsdf_mesh_batch_run", C.byref(params), C.byref(d))
+        return self.vertex, self.quad, self.n_vertices, self.n_quads
+
+    def count(self, ctx, params):
+        """enqueue the count-only call (asynchronous) -> (n_vertices_total, n_quads_total); n_vertices and n_quads become 0"""
+        self._checked(params)
+        d = self.descriptor(count_only=True)
+        _run_tsdf_mesh(ctx, "prs_tsdf_mesh_batch_run", C.byref(params), C.byref(d))
+        return self.n_vertices_total, self.n_quads_total
+
+    def mesh_of(self, b):
+        """the mesh of sequence b after run (synchronises to read its two counts) -> (xyz [n, 4], normal [n, 4] or None,
+        triangles [2 * n_quads, 3] int32) as device tensors: the triangles (v0, v1, v2) and (v0, v2, v3) of quad i are rows 2 i and
+        2 i + 1, which formats.write_ply(path, xyz, normals=normal, faces=triangles) takes once they are on the host.  Raises
+        ValueError when the sequence overflowed a stride: its quads may then name vertices that were not written"""
+        b = int(b)
+        if not 0 <= b < self.batch:
+            raise ValueError("b must lie in [0, %d)" % self.batch)
+        if int(self.status[b]) != 0:
+            raise ValueError("sequence %d holds %d vertices and %d quads: more than vertex_stride or quad_stride"
+                             % (b, int(self.n_vertices_total[b]), int(self.n_quads_total[b])))
+        n, m = int(self.n_vertices[b]), int(self.n_quads[b])
+        quad = self.quad[b, :m]
+        triangles = quad[:, [0, 1, 2, 0, 2, 3]].reshape(2 * m, 3).contiguous()
+        return self.vertex[b, :n], (None if self.normal is None else self.normal[b, :n]), triangles
 
 
 # ---- dense align: a live depth image against a rendered model view, point-to-plane on SE(3) (include/proslam_hip_dense_align.h) ----
