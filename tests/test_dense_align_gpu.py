@@ -320,8 +320,8 @@ def tracker_scene():
 
 
 def test_a_tracker_run_equals_the_same_calls_made_one_by_one(hip_ctx):
-    """DenseTrackerBatch against raycast, align, compose and integrate called by hand.  (24 x 20 pixels against 4 cm voxels are too
-    coarse to say how well the motion is followed: the chain test above bounds the error at a size that can.)"""
+    """DenseTrackerBatch against raycast, align, compose and integrate called by hand.  How well the motion is followed, and on which
+    side X is composed, is tests/test_dense_loop_gpu.py's: 80 x 60 frames in a turned world frame against the true trajectory."""
     import torch
     cam, frames, schedule, kw, volumes = tracker_scene()
     rows, cols = frames[0].shape[1:]
